@@ -6,10 +6,15 @@ one rank per GPU over RCCL).  One "step" = one pass of the hot path over a batch
 main() renders a 36-frame orbit per run): closest-hit (+ shadow rays) and shading kernels over this rank's part
 of every frame, then (N > 1) ONE gather of the framebuffer tiles to rank 0.  Prints ONE JSON line on rank 0.
 
-The line carries, beside the throughput: `parity` (the last rendered frame against the committed reference golden /
-the CPU oracle: BASELINE.json's metric names both halves), `roofline` (the bound is chosen from counters collected IN
-THIS RUN: three short rocprofv3 --pmc passes of this same script as child processes, --no-pmc skips them) and
-`cpu_baseline`.
+A plain run does only what the headline needs: set up, warm up, time the K steps, count the rays of one frame (one untimed
+launch of the counting build) and print the line (`value`, `ms_per_step`, `config`).  `--dump-outputs DIR` also writes
+what the last timed step computed as DIR/<name>.npy (see dump_outputs).
+
+With `--full` the line also carries: `parity` (the last rendered frame against the committed reference golden /
+the CPU oracle: BASELINE.json's metric names both halves), `roofline` and `kernels` (per-kernel times from eager
+launches; the bound is chosen from counters collected IN THIS RUN: three short rocprofv3 --pmc passes of this same
+script as child processes, --no-pmc skips them), `cpu_baseline` / `cpu_reference`, the soup as a second measurement
+(--no-soup skips it) and, at N > 1, the per-phase times and the check of the gathered frames.
 
 Workload (config.workload): BASELINE.json configs[2], the configuration the north_star quotes its
 target on: stanford-bunny over a ground slab, 1920x1080, 1 light sample; scene from
@@ -45,7 +50,7 @@ BLOCK_COLS = 0                  # > 0: tiles of 8 x BLOCK_COLS pixels dealt in t
 def parse_args():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=30)
+    ap.add_argument("--steps", type=int, default=30, help="timed steps (at least 1)")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--frames", type=int, default=36, help="frames rendered per step (the reference renders a 36-frame orbit per run)")
     ap.add_argument("--workload", default="ground_bunny", choices=["ground_bunny", "cube_ground", "main_nocats", "k4", "soup"])
@@ -88,7 +93,16 @@ def parse_args():
     ap.add_argument("--no-soup", action="store_true",
                     help="skip the second, short measurement the default workload adds: the 1 M-triangle soup at the same resolution and split "
                          "(north_star asks for the 1 / 2 / 4 / 8-GPU curve on the soup; it is reported as `soup` beside the headline value)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: parity, per-kernel times and roofline (with the --pmc child passes), CPU baseline and "
+                         "reference, the soup, N > 1 per-phase times and the gathered-frame check (the --no-* options above trim it)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32 / float64, finite: +inf / NaN "
+                         "as -1, under 64 MB)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 _setup = None
@@ -309,15 +323,20 @@ def measure(args):
     # frames 0, S, 2S, ... of a step, all the same picture -- copied out before anything else renders into them
     timed = None
     last_slot = (args.warmup + args.steps - 1) % SLOTS if (args.warmup + args.steps) else 0
-    if rank == 0 and world == 1 and not emu and not args.no_parity:
+    if args.dump_outputs and rank == 0:
+        # N > 1: the frames rank 0 assembled from the last gather; else this rank's framebuffers of the last step and the per-handle
+        # buffers (hit ids, t, linear colour of the last frame each handle rendered)
+        dump_outputs(args.dump_outputs, {"rgb8": gather.frame} if world > 1 else
+                     {"rgb8": gather.tiles[last_slot][:, :rows, :Wl], "hit_id": hit, "t": tbuf, "rgb_linear": lin})
+    if args.full and rank == 0 and world == 1 and not emu and not args.no_parity:
         timed = (hit[0].cpu().numpy().copy(), tbuf[0].cpu().numpy().copy(), lin[0].cpu().numpy().copy(), gather.tiles[last_slot][0].cpu().numpy().copy())
     # the phases of a step one by one (N > 1: the SCALE records need them to be read)
     phases = phase_times(gather, (lambda slot: graphs[slot].replay()) if graphs is not None else (lambda slot: render_frames(p, slot)),
-                         world, dev, args.backend) if world > 1 else None
+                         world, dev, args.backend) if args.full and world > 1 else None
     # N > 1: what rank 0 holds after the last gather must be the frame one GPU renders (every step renders the same frames)
     gathered_ok = None
     gathered_parity = None
-    if world > 1 and rank == 0 and FG == 1 and gather.frame is not None:
+    if args.full and world > 1 and rank == 0 and FG == 1 and gather.frame is not None:
         whole = lib.DeviceScene(g.flat, device=local_rank).render(abi.make_params(W, H, lights, spp=args.spp), want=("rgb8",))["rgb8"]
         got = gather.frame.cpu().numpy()
         gathered_ok = bool(all(np.array_equal(got[f], whole) for f in (0, got.shape[0] - 1)))
@@ -332,9 +351,11 @@ def measure(args):
     # a captured graph cannot be read back), averaged by srt_sync
     for sc_ in scenes_:
         sc_.sync()
-    render_frames(p, streams=False)
-    torch.cuda.synchronize()
-    st = scene.sync()
+    st = None
+    if args.full:
+        render_frames(p, streams=False)
+        torch.cuda.synchronize()
+        st = scene.sync()
     pipeline = scene.pipeline                  # what the library launched for this frame (the counting launch below may take another route)
     rgb8 = gather.tiles[0][0]
 
@@ -352,7 +373,7 @@ def measure(args):
     rays_rank = sc["primary_rays"] + sc["shadow_rays"]        # of one of this rank's frames (its scanline blocks)
     # ---- parity of the frame the timed region rendered last (rank 0, whole frames only) -------------------------------
     parity = None
-    if rank == 0 and world == 1 and not emu and not args.no_parity:
+    if timed is not None:
         parity = parity_block(g, args, W, H, L, lights, *timed)
         parity["frame_compared"] = ("frame 0 of the last step of the TIMED region (" + ("hipGraph replay" if graph is not None else "eager launches") +
                                     f", {S} stream(s)), copied out before any other render")
@@ -368,55 +389,57 @@ def measure(args):
     value = rays_total * B_total / (dt / args.steps) / 1e6
 
     if rank == 0:
-        # with --spp n^2 a frame is n^2 launch pairs: counts are per LAUNCH (averaged over the sub-frames), like the kernel times
-        sc = dict(sc)
-        for k in ("hit_rays", "node_tests_primary", "tri_tests_primary", "node_tests_shadow", "tri_tests_shadow"):
-            sc[k] = sc[k] // args.spp
-        if args.spp > 1:        # the event pair around the traversal spans all sub-frames: per launch = / spp (includes the small shade / accumulate launches in between)
-            st = dict(st); st["ms_primary"] = st["ms_primary"] / args.spp
-        pixels = int(sc["primary_rays"]) // args.spp      # pixels of the image this rank renders
-        hits, miss = sc["hit_rays"], pixels - sc["hit_rays"]
-        items = hits * L
-        # algorithmic bytes per launch: 32 B per slab test + 36 B per Moller-Trumbore test of the kernel's own
-        # traversal + the per-pixel / per-item records each kernel must read and write
-        b_closest = NODE_BYTES * sc["node_tests_primary"] + TRI_BYTES * sc["tri_tests_primary"] + 8 * pixels + 15 * miss
-        b_shadow = NODE_BYTES * sc["node_tests_shadow"] + TRI_BYTES * sc["tri_tests_shadow"] + 4 * pixels + 8 * hits + items // 8
-        b_shade = 4 * pixels + (4 + 12 + 4 + 15) * hits + items // 8
-        names = pipeline.split("+")                      # what the library launched, e.g. k_trace_nq+k_shade_tile
-        if args.variant == 1:
-            kern = {"k_closest_hit": dict(ms=st["ms_primary"], bytes=NODE_BYTES * sc["node_tests_primary"] + TRI_BYTES * sc["tri_tests_primary"] + 8 * pixels),
-                    "k_shade": dict(ms=st["ms_shade"], bytes=NODE_BYTES * sc["node_tests_shadow"] + TRI_BYTES * sc["tri_tests_shadow"] + 12 * hits + 23 * pixels)}
-        elif names[0] == "k_trace_nq":                   # closest hit + shadow rays in one launch
-            kern = {"k_trace_nq": dict(ms=st["ms_primary"] + st["ms_shadow"], bytes=b_closest + b_shadow), "k_shade_tile": dict(ms=st["ms_shade"], bytes=b_shade)}
-        else:
-            kern = {names[0]: dict(ms=st["ms_primary"], bytes=b_closest)}
-            if len(names) == 3:
-                kern[names[1]] = dict(ms=st["ms_shadow"], bytes=b_shadow)
-            kern["k_shade_tile"] = dict(ms=st["ms_shade"], bytes=b_shade)
-        dom = max(kern, key=lambda k: kern[k]["ms"])
-        dom_ms = kern[dom]["ms"]
-        effective = kern[dom]["bytes"] / (dom_ms * 1e-3) / 1e9 if dom_ms > 0 else 0.0
-        # ---- counters of THIS run: three rocprofv3 --pmc passes of this script as child processes -------------------
-        pmc = None
-        if world == 1 and not args.no_pmc and not args.emulate_split:
-            pmc = collect_pmc(sys.argv[1:], dom)
-        if pmc is None and world == 1:
-            pmc = committed_pmc(args.workload, dom, W, H, L)
-        roof = roofline_block(dom, dom_ms, kern[dom]["bytes"], effective, pmc, g)
-        pk = (pmc or {}).get("per_kernel") or {}
-        if roof.get("valu") and pk and args.spp == 1 and all("SQ_INSTS_VALU" in v for v in pk.values()):
-            # the same counters against the TIMED region: the frame's VALU wave-instructions (all kernels of the pipeline, per launch =
-            # per frame) over the cycles a frame takes there, frames overlapped on S streams
-            insts_f = sum(v["SQ_INSTS_VALU"] for v in pk.values())
-            lanes_f = sum(v.get("SQ_THREAD_CYCLES_VALU", 0.0) for v in pk.values()) / insts_f if insts_f else 0.0
-            cyc_f = (ms_step / B_total) * 1e-3 * roof["valu"]["clock_GHz"] * 1e9
-            issue_f = insts_f * VALU_CYCLES_PER_WAVE_INST / (N_SIMD * cyc_f) if cyc_f else 0.0
-            roof["timed_region"] = {"valu_issue_frac": round(issue_f, 4), "lanes_active_of_64": round(lanes_f, 1),
-                                    "frac_of_lane_peak": round(issue_f * lanes_f / 64.0, 4), "kernels": sorted(pk),
-                                    "note": "VALU wave-instructions of ALL kernels of a frame (counters of the kernels running alone) x 2 / (1024 SIMDs x the cycles a frame "
-                                            "takes in the timed region): what the overlap of frames on streams adds to the single kernel's `frac`"}
-        roof["kernel_ms_note"] = ("HIP events around eager launches on ONE stream (the kernel running alone, as in profiles/*_kernel_stats.csv and the --pmc "
-                                  f"passes); the timed region overlaps the frames of a step on {S} stream(s), where a per-kernel duration is not defined")
+        kern = roof = None
+        if args.full:
+            # with --spp n^2 a frame is n^2 launch pairs: counts are per LAUNCH (averaged over the sub-frames), like the kernel times
+            sc = dict(sc)
+            for k in ("hit_rays", "node_tests_primary", "tri_tests_primary", "node_tests_shadow", "tri_tests_shadow"):
+                sc[k] = sc[k] // args.spp
+            if args.spp > 1:        # the event pair around the traversal spans all sub-frames: per launch = / spp (includes the small shade / accumulate launches in between)
+                st = dict(st); st["ms_primary"] = st["ms_primary"] / args.spp
+            pixels = int(sc["primary_rays"]) // args.spp      # pixels of the image this rank renders
+            hits, miss = sc["hit_rays"], pixels - sc["hit_rays"]
+            items = hits * L
+            # algorithmic bytes per launch: 32 B per slab test + 36 B per Moller-Trumbore test of the kernel's own
+            # traversal + the per-pixel / per-item records each kernel must read and write
+            b_closest = NODE_BYTES * sc["node_tests_primary"] + TRI_BYTES * sc["tri_tests_primary"] + 8 * pixels + 15 * miss
+            b_shadow = NODE_BYTES * sc["node_tests_shadow"] + TRI_BYTES * sc["tri_tests_shadow"] + 4 * pixels + 8 * hits + items // 8
+            b_shade = 4 * pixels + (4 + 12 + 4 + 15) * hits + items // 8
+            names = pipeline.split("+")                      # what the library launched, e.g. k_trace_nq+k_shade_tile
+            if args.variant == 1:
+                kern = {"k_closest_hit": dict(ms=st["ms_primary"], bytes=NODE_BYTES * sc["node_tests_primary"] + TRI_BYTES * sc["tri_tests_primary"] + 8 * pixels),
+                        "k_shade": dict(ms=st["ms_shade"], bytes=NODE_BYTES * sc["node_tests_shadow"] + TRI_BYTES * sc["tri_tests_shadow"] + 12 * hits + 23 * pixels)}
+            elif names[0] == "k_trace_nq":                   # closest hit + shadow rays in one launch
+                kern = {"k_trace_nq": dict(ms=st["ms_primary"] + st["ms_shadow"], bytes=b_closest + b_shadow), "k_shade_tile": dict(ms=st["ms_shade"], bytes=b_shade)}
+            else:
+                kern = {names[0]: dict(ms=st["ms_primary"], bytes=b_closest)}
+                if len(names) == 3:
+                    kern[names[1]] = dict(ms=st["ms_shadow"], bytes=b_shadow)
+                kern["k_shade_tile"] = dict(ms=st["ms_shade"], bytes=b_shade)
+            dom = max(kern, key=lambda k: kern[k]["ms"])
+            dom_ms = kern[dom]["ms"]
+            effective = kern[dom]["bytes"] / (dom_ms * 1e-3) / 1e9 if dom_ms > 0 else 0.0
+            # ---- counters of THIS run: three rocprofv3 --pmc passes of this script as child processes -------------------
+            pmc = None
+            if world == 1 and not args.no_pmc and not args.emulate_split:
+                pmc = collect_pmc(sys.argv[1:], dom)
+            if pmc is None and world == 1:
+                pmc = committed_pmc(args.workload, dom, W, H, L)
+            roof = roofline_block(dom, dom_ms, kern[dom]["bytes"], effective, pmc, g)
+            pk = (pmc or {}).get("per_kernel") or {}
+            if roof.get("valu") and pk and args.spp == 1 and all("SQ_INSTS_VALU" in v for v in pk.values()):
+                # the same counters against the TIMED region: the frame's VALU wave-instructions (all kernels of the pipeline, per launch =
+                # per frame) over the cycles a frame takes there, frames overlapped on S streams
+                insts_f = sum(v["SQ_INSTS_VALU"] for v in pk.values())
+                lanes_f = sum(v.get("SQ_THREAD_CYCLES_VALU", 0.0) for v in pk.values()) / insts_f if insts_f else 0.0
+                cyc_f = (ms_step / B_total) * 1e-3 * roof["valu"]["clock_GHz"] * 1e9
+                issue_f = insts_f * VALU_CYCLES_PER_WAVE_INST / (N_SIMD * cyc_f) if cyc_f else 0.0
+                roof["timed_region"] = {"valu_issue_frac": round(issue_f, 4), "lanes_active_of_64": round(lanes_f, 1),
+                                        "frac_of_lane_peak": round(issue_f * lanes_f / 64.0, 4), "kernels": sorted(pk),
+                                        "note": "VALU wave-instructions of ALL kernels of a frame (counters of the kernels running alone) x 2 / (1024 SIMDs x the cycles a frame "
+                                                "takes in the timed region): what the overlap of frames on streams adds to the single kernel's `frac`"}
+            roof["kernel_ms_note"] = ("HIP events around eager launches on ONE stream (the kernel running alone, as in profiles/*_kernel_stats.csv and the --pmc "
+                                      f"passes); the timed region overlaps the frames of a step on {S} stream(s), where a per-kernel duration is not defined")
         out = {
             "metric": "Mrays/sec (primary+shadow) at 1920x1080; max per-pixel |dRGB| vs CPU ref", "value": round(value, 3), "unit": "Mrays/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_step, 5),
@@ -444,13 +467,14 @@ def measure(args):
                                        "; one RCCL gather of all tiles per step, overlapped with the next step's rendering"),
                        "frames_per_step": B_total, "ms_per_frame": round(ms_step / B_total, 5), "launch": ("hipGraph replay" if graph is not None else "eager") + (f", srt_render_device_batch (frames share launches), {len(batches[0])} batch(es) of {nb} on {G} stream(s)" if batches is not None else f", {S} stream(s)"),
                        "primary_rays_per_frame": prim_total, "shadow_rays_per_frame": shad_total},
-            "roofline": roof,
-            "kernels": {k: {"ms": round(v["ms"], 5), "algorithmic_bytes": v["bytes"]} for k, v in kern.items()},
         }
+        if args.full:
+            out["roofline"] = roof
+            out["kernels"] = {k: {"ms": round(v["ms"], 5), "algorithmic_bytes": v["bytes"]} for k, v in kern.items()}
         out["config"]["pipeline"] = pipeline
         if parity is not None:
             out["parity"] = parity
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(g, W, H, L, lights)
             if L == 1:
                 out["cpu_reference"] = cpu_reference(g, W, H)
@@ -533,6 +557,39 @@ def dry_run(args):
     return 0 if (ok or rank != 0) else 1
 
 
+DUMP_BYTES = 56 << 20          # --dump-outputs: what the files of one dump hold at most (under 64 MB with the .npy headers)
+DUMP_SEED = 0x5eed
+DUMP_NONFINITE = -1.0         # what --dump-outputs writes for +inf / NaN: no distance is negative
+
+
+def dump_outputs(dirname, outs):
+    """--dump-outputs DIR: the device arrays `outs` (name -> tensor [lead, rows, cols(, 3)]: frames or scene handles first, then the
+    pixel grid) as DIR/<name>.npy, float32 (int32 hit ids as float64, exact).  Every value written is finite: a non-finite one becomes
+    DUMP_NONFINITE (t is +inf where no surface was hit -- hit_id -1 marks those pixels --, and a mesh without normals shades to NaN).
+    When all of them would exceed DUMP_BYTES, every array keeps the same fixed, seeded sample of pixels (sorted), and
+    DIR/pixel_index.npy holds their flat index row * cols + col."""
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    rows, cols = next(iter(outs.values())).shape[1:3]
+    npix = rows * cols
+    per_px = 8 + sum((8 if a.dtype == torch.int32 else 4) * (a.numel() // npix) for a in outs.values())
+    n = min(npix, DUMP_BYTES // per_px)
+    index = os.path.join(dirname, "pixel_index.npy")
+    idx = None
+    if n < npix:
+        sel = np.sort(np.random.default_rng(DUMP_SEED).choice(npix, n, replace=False))
+        np.save(index, sel.astype(np.float64))
+        idx = torch.as_tensor(sel, device=next(iter(outs.values())).device)
+    elif os.path.exists(index):
+        os.remove(index)
+    for name, a in outs.items():
+        if idx is not None:
+            a = a.reshape(a.shape[0], npix, *a.shape[3:]).index_select(1, idx)
+        a = a.cpu().numpy().astype(np.float64 if a.dtype == torch.int32 else np.float32)
+        a[~np.isfinite(a)] = DUMP_NONFINITE
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 def phase_times(gather, render_slot, world, dev, backend, reps=3):
     """What a step is made of, phase by phase and NOT overlapped (the timed region overlaps them: the gather of step s runs beside the
     rendering of step s + 1, and rank 0 assembles on a stream of its own): render (max over ranks), the collective, rank 0's assembly.
@@ -573,11 +630,12 @@ def main():
         sys.exit(dry_run(args))
     out = measure(args)
     rank, _, world = setup(args)
-    if args.workload == "ground_bunny" and not args.no_soup and not args.emulate_split and args.spp == 1 and args.variant == 0:
+    if args.full and args.workload == "ground_bunny" and not args.no_soup and not args.emulate_split and args.spp == 1 and args.variant == 0:
         # north_star's scaling curve is quoted on the synthetic soup: same resolution, same split, a short run
         a2 = copy.copy(args)
         a2.workload, a2.frames, a2.steps, a2.warmup, a2.lights = "soup", 4, 3, 1, 1      # 4 frames: one per stream
         a2.no_cpu_baseline = a2.no_pmc = a2.no_parity = True
+        a2.dump_outputs = ""                                                              # the dump is the headline workload's
         o2 = measure(a2)
         if rank == 0:
             out["soup"] = {k: o2[k] for k in ("value", "unit", "n_gpus", "steps", "ms_per_step")}
@@ -627,9 +685,9 @@ def collect_pmc(argv, kernel):
     for a in argv:                                  # the child renders the same workload, briefly
         if skip:
             skip = False; continue
-        if a in ("--steps", "--warmup", "--frames", "--streams"):
+        if a in ("--steps", "--warmup", "--frames", "--streams", "--dump-outputs"):
             skip = True; continue
-        if a.startswith(("--steps=", "--warmup=", "--frames=", "--streams=")) or a in ("--no-cpu-baseline", "--no-pmc", "--no-parity", "--no-soup"):
+        if a.startswith(("--steps=", "--warmup=", "--frames=", "--streams=", "--dump-outputs=")) or a in ("--no-cpu-baseline", "--no-pmc", "--no-parity", "--no-soup"):
             continue
         keep.append(a)
     child = ["python3", os.path.join(ROOT, "bench.py")] + keep + ["--steps", "2", "--warmup", "1", "--frames", "4", "--streams", "1",       # one stream: the counters of a kernel that runs alone

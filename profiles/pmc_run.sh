@@ -32,6 +32,6 @@ esac
 i=0
 for ctrs in "${GROUPS_[@]}"; do
   i=$((i+1))
-  rocprofv3 --kernel-trace --pmc $ctrs --output-format csv -d "$ROOT/$OUT/pass$i" -- python3 "$ROOT/bench.py" --steps ${PMC_STEPS:-10} --warmup 2 --no-cpu-baseline --no-pmc --no-parity --no-soup "$@" > "$ROOT/$OUT/pass$i.log" 2>&1 || echo "pass $i failed"
+  rocprofv3 --kernel-trace --pmc $ctrs --output-format csv -d "$ROOT/$OUT/pass$i" -- python3 "$ROOT/bench.py" --full --steps ${PMC_STEPS:-10} --warmup 2 --no-cpu-baseline --no-pmc --no-parity --no-soup "$@" > "$ROOT/$OUT/pass$i.log" 2>&1 || echo "pass $i failed"
 done
 echo done

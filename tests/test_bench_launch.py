@@ -33,6 +33,47 @@ def test_plain_shell_launch_of_n_ranks(n, extra):
     assert d["gather_bytes"] // (n - 1) >= B * (H // n) * W * 3 * 0.9          # one padded tile set per peer
 
 
+def test_dump_outputs_is_small_fixed_and_exact(tmp_path):
+    """--dump-outputs: finite float32 / float64 files under 64 MB in all (+inf / NaN written as -1).  A 1920x1080 step's arrays keep
+    one fixed, seeded pixel sample (the same in every array and every run, pixel_index.npy says which); a small frame is written
+    whole.  Values are exact."""
+    import importlib.util
+    import numpy as np
+    import torch
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(ROOT, "bench.py"))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    B, H, W, NB = 8, 1080, 1920, 4
+    g = torch.Generator().manual_seed(1)
+    outs = {"rgb8": torch.randint(0, 256, (B, H, W, 3), dtype=torch.uint8, generator=g),
+            "hit_id": torch.randint(-1, 1 << 20, (NB, H, W), dtype=torch.int32, generator=g),
+            "t": torch.rand((NB, H, W), generator=g), "rgb_linear": torch.rand((NB, H, W, 3), generator=g)}
+    outs["t"][outs["hit_id"] < 0] = float("inf")                 # the library's t where no surface was hit
+    outs["rgb_linear"][:, ::7, ::5, 1] = float("nan")            # shading of a mesh without normals
+    for d in ("a", "b"):
+        b.dump_outputs(str(tmp_path / d), outs)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["hit_id.npy", "pixel_index.npy", "rgb8.npy", "rgb_linear.npy", "t.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) < 64e6
+    for f in files:
+        x = np.load(tmp_path / "a" / f)
+        assert x.dtype in (np.float32, np.float64), f
+        assert np.isfinite(x).all(), f
+        assert np.array_equal(x, np.load(tmp_path / "b" / f)), f
+    idx = np.load(tmp_path / "a" / "pixel_index.npy").astype(np.int64)
+    assert 0 < idx.size < H * W and np.all(np.diff(idx) > 0)
+    assert np.array_equal(np.load(tmp_path / "a" / "rgb8.npy"), outs["rgb8"].reshape(B, -1, 3).numpy()[:, idx].astype(np.float32))
+    assert np.array_equal(np.load(tmp_path / "a" / "hit_id.npy"), outs["hit_id"].reshape(NB, -1).numpy()[:, idx].astype(np.float64))
+    lin = outs["rgb_linear"].reshape(NB, -1, 3).numpy()[:, idx]
+    assert np.isnan(lin).any() and np.array_equal(np.load(tmp_path / "a" / "rgb_linear.npy"), np.where(np.isnan(lin), np.float32(-1), lin))
+    t = outs["t"].reshape(NB, -1).numpy()[:, idx]
+    assert np.isinf(t).any() and np.array_equal(np.load(tmp_path / "a" / "t.npy"), np.where(np.isinf(t), np.float32(-1), t))
+    small = outs["rgb8"][:2, :96, :128]
+    b.dump_outputs(str(tmp_path / "s"), {"rgb8": small})
+    assert os.listdir(tmp_path / "s") == ["rgb8.npy"]
+    assert np.array_equal(np.load(tmp_path / "s" / "rgb8.npy"), small.numpy().astype(np.float32))
+
+
 def test_a_failing_rank_fails_the_launch():
     """Without --dry-run the ranks need a GPU; here they exit with an error, and the parent must report it (not hang, not return 0)."""
     import torch

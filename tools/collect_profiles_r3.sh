@@ -14,15 +14,15 @@ CFG[k4]="--workload k4 --width 3840 --height 2160 --lights 64 --frames 12";     
 CFG[k5]="--workload soup --width 2048 --height 2048 --frames 4";                PROBE[k5]="--workload soup --width 2048 --height 2048 --frames 3"
 CFG[k5_1080p]="--workload soup --frames 4";                                     PROBE[k5_1080p]="--workload soup --frames 3"
 for k in k3 k4 k5 k5_1080p; do
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${k}_stats -- python3 $ROOT/bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-pmc --no-parity --streams 1 ${CFG[$k]} > $OUT/${k}_s1_bench.json 2> $OUT/${k}_stats.log || echo "stats $k failed"
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${k}_stats -- python3 $ROOT/bench.py --full --steps 5 --warmup 1 --no-cpu-baseline --no-pmc --no-parity --streams 1 ${CFG[$k]} > $OUT/${k}_s1_bench.json 2> $OUT/${k}_stats.log || echo "stats $k failed"
   cp $(ls $OUT/${k}_stats/*/*kernel_stats.csv | head -1) $OUT/${k}_kernel_stats.csv 2>/dev/null
   rm -rf $OUT/${k}_stats
   if [ $k != k3 ]; then
-    timeout -k 10 300 python3 $ROOT/bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-pmc ${CFG[$k]} > $OUT/${k}_bench.json 2> $OUT/${k}_bench.log || echo "bench $k failed"
+    timeout -k 10 300 python3 $ROOT/bench.py --full --steps 5 --warmup 1 --no-cpu-baseline --no-pmc ${CFG[$k]} > $OUT/${k}_bench.json 2> $OUT/${k}_bench.log || echo "bench $k failed"
   fi
 done
-# the headline line as the driver runs it (PMC child passes, parity, cpu_baseline, the soup's secondary measurement)
-timeout -k 10 400 python3 $ROOT/bench.py > $OUT/k3_bench.json 2> $OUT/k3_bench.log || echo "bench k3 failed"
+# the headline line with everything --full adds (PMC child passes, parity, cpu_baseline, the soup's secondary measurement)
+timeout -k 10 400 python3 $ROOT/bench.py --full > $OUT/k3_bench.json 2> $OUT/k3_bench.log || echo "bench k3 failed"
 G_A="SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_THREAD_CYCLES_VALU SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU"
 G_B="GRBM_GUI_ACTIVE SQ_INSTS_SALU SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_LDS SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_LDS SQ_INSTS_SMEM"
 G_E="TCC_HIT_sum TCC_MISS_sum TCC_REQ_sum"

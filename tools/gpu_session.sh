@@ -14,7 +14,7 @@ fi
 i=0
 for args in "$@"; do
   i=$((i+1))
-  timeout -k 10 300 python bench.py $args > $OUT/bench$i.json 2> $OUT/bench$i.err; rc=$?
+  timeout -k 10 300 python bench.py --full $args > $OUT/bench$i.json 2> $OUT/bench$i.err; rc=$?
   echo "bench$i [$args] rc=$rc: $(python - <<PY
 import json
 try:
