@@ -807,6 +807,7 @@ static int check_params(const srt_params* p) {
     { const uint32_t n = (uint32_t)std::lround(std::sqrt((double)p->spp)); if (n * n != p->spp) return SRT_ERR_ARG; }   // n x n sub-pixel grid
     if ((uint64_t)p->width * p->height >= (1ull << 31)) return SRT_ERR_LIMIT;
     if ((uint64_t)p->width * p->height * (p->n_lights ? p->n_lights : 1) >= (1ull << 32)) return SRT_ERR_LIMIT;   // 32-bit work-item index
+    if (p->spp > 1 && (uint64_t)srt_cols_owned(p) * srt_rows_owned(p) * 3 >= (1ull << 32)) return SRT_ERR_LIMIT;   // the accumulation buffer's 32-bit float index
     return SRT_OK;
 }
 
@@ -1138,7 +1139,7 @@ static int render_device_impl(srt_scene* s, const srt_params* p, void* stream_, 
             rc = launch_frame(fp, k == 0 ? d_hit_id : s->ws_sub_hit, k == 0 ? d_t : s->ws_sub_t, s->ws_sub, nullptr, nullptr,
                               (k == spp - 1) ? ev : nullptr);
             if (rc != SRT_OK) return rc;
-            hipLaunchKernelGGL(k_accumulate, dim3(gq), block, 0, stream, s->ws_acc, s->ws_sub, (uint32_t)(pixels * 3), k == 0 ? 1 : 0);
+            hipLaunchKernelGGL(k_accumulate, dim3(gq), block, 0, stream, dp, s->ws_acc, s->ws_sub, (uint32_t)(pixels * 3), k == 0 ? 1 : 0);      // (< 2^32: check_params)
             HIP_TRY(hipGetLastError());
         }
         hipLaunchKernelGGL(k_resolve, dim3((uint32_t)((pixels + 255) / 256)), block, 0, stream, dp, s->ws_acc, (float)spp, (uint32_t)pixels,

@@ -1769,16 +1769,21 @@ __global__ __launch_bounds__(256, INT_SHIN ? 8 : 1) void k_shade_tile_batch(cons
 // Supersampling extension (spp = n x n > 1; not in the reference): the sub-frames' pre-tone-map
 // sums are added in sub-sample order, divided by spp, then tone-mapped / quantised once.
 // =================================================================================================
-__global__ __launch_bounds__(256) void k_accumulate(float* __restrict__ acc, const float* __restrict__ sub, uint32_t n, int first) {
+// The sub-frames write the live pixels only: the padding of a tile deal is left alone here and in k_resolve (include/srt.h:
+// "not written"), or the caller's padding would receive whatever the workspace holds.
+__device__ __forceinline__ bool resolve_live(const DevParams& p, uint32_t i) {
+    return !p.col_block || pixel_live(p, i % p.W, i / p.W);
+}
+__global__ __launch_bounds__(256) void k_accumulate(DevParams p, float* __restrict__ acc, const float* __restrict__ sub, uint32_t n, int first) {
     const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-    if (i < n) acc[i] = first ? sub[i] : acc[i] + sub[i];
+    if (i < n && resolve_live(p, i / 3u)) acc[i] = first ? sub[i] : acc[i] + sub[i];
 }
 __global__ __launch_bounds__(256) void k_resolve(DevParams p, const float* __restrict__ acc, float spp, uint32_t n_pixels,
                                                  float* __restrict__ rgb_linear, uint8_t* __restrict__ rgb8,
                                                  unsigned long long* __restrict__ counters_next) {
     if (blockIdx.x == 0) for (int i = threadIdx.x; i < NCTR; i += 256) counters_next[i] = 0ull;
     const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n_pixels) return;
+    if (i >= n_pixels || !resolve_live(p, i)) return;
     const float a0 = acc[(size_t)i * 3] / spp, a1 = acc[(size_t)i * 3 + 1] / spp, a2 = acc[(size_t)i * 3 + 2] / spp;
     if (rgb_linear) { rgb_linear[(size_t)i * 3] = a0; rgb_linear[(size_t)i * 3 + 1] = a1; rgb_linear[(size_t)i * 3 + 2] = a2; }
     if (rgb8) {
