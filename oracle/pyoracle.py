@@ -42,6 +42,10 @@ def oracle_lib():
         L.oracle_render.restype = C.c_int
         L.oracle_render.argtypes = [C.POINTER(abi.SceneDesc), C.POINTER(abi.Params), _i32p, _f32p, _f32p, _f32p, _u8p,
                                     C.POINTER(abi.Stats), C.c_int]
+        L.oracle_render_pow.restype = C.c_int
+        L.oracle_render_pow.argtypes = L.oracle_render.argtypes + [C.c_int]
+        L.oracle_phong_pow.argtypes = [C.c_uint32, _f32p, _f32p, C.c_int]
+        L.oracle_tonemap_pow.argtypes = [C.c_uint32, _f32p, C.c_float, C.c_float, _f32p, _i32p, C.c_int]
         L.oracle_rows_owned.restype = C.c_uint32
         L.oracle_rows_owned.argtypes = [C.POINTER(abi.Params)]
         L.oracle_cols_owned.restype = C.c_uint32
@@ -55,8 +59,21 @@ def _p(a, ty):
     return a.ctypes.data_as(ty)
 
 
-def render(scene: abi.FlatScene, params: abi.Params, n_threads=0):
+# The pow of Phong's specular term and of the tone map (oracle/srt_oracle.h ORACLE_POW_*): "host" is glibc powf, what the
+# reference calls; "device" restates the kernels' pow_like_host (integer exponents in [1, 64] by square-and-multiply in double,
+# otherwise the f64 library pow rounded once), so that every other shading operation can be compared with the device bit for bit.
+POW_MODES = {"host": 0, "device": 1}
+
+
+def _pow_mode(pow):
+    if pow not in POW_MODES:
+        raise ValueError(f"pow must be one of {sorted(POW_MODES)}, not {pow!r}")
+    return POW_MODES[pow]
+
+
+def render(scene: abi.FlatScene, params: abi.Params, n_threads=0, pow="host"):
     """Run the C restatement.  Returns dict(hit_id, t, rgb_linear, rgb_tone, rgb8, stats)."""
+    mode = _pow_mode(pow)
     L = oracle_lib()
     rows = L.oracle_rows_owned(C.byref(params))
     W = L.oracle_cols_owned(C.byref(params))           # width of the rows this call writes (padding of a tile deal stays zero)
@@ -65,8 +82,8 @@ def render(scene: abi.FlatScene, params: abi.Params, n_threads=0):
                rgb8=np.zeros((rows, W, 3), np.uint8))
     st = abi.Stats()
     d = scene.desc()
-    rc = L.oracle_render(C.byref(d), C.byref(params), _p(out["hit_id"], _i32p), _p(out["t"], _f32p),
-                         _p(out["rgb_linear"], _f32p), _p(out["rgb_tone"], _f32p), _p(out["rgb8"], _u8p), C.byref(st), n_threads)
+    rc = L.oracle_render_pow(C.byref(d), C.byref(params), _p(out["hit_id"], _i32p), _p(out["t"], _f32p),
+                             _p(out["rgb_linear"], _f32p), _p(out["rgb_tone"], _f32p), _p(out["rgb8"], _u8p), C.byref(st), n_threads, mode)
     if rc != 0:
         raise RuntimeError(f"oracle_render failed: {rc}")
     out["stats"] = st.as_dict()
@@ -89,10 +106,11 @@ def ray_aabb(ray_od, box):
     return h
 
 
-def phong(inp):
+def phong(inp, pow="host"):
     L = oracle_lib()
+    mode = _pow_mode(pow)
     inp = np.ascontiguousarray(inp, np.float32); n = inp.shape[0]; rgb = np.empty((n, 3), np.float32)
-    L.oracle_phong(C.c_uint32(n), _p(inp, _f32p), _p(rgb, _f32p))
+    L.oracle_phong_pow(C.c_uint32(n), _p(inp, _f32p), _p(rgb, _f32p), mode)
     return rgb
 
 
@@ -103,11 +121,12 @@ def barycentric(inp):
     return uvw
 
 
-def tonemap(lin, reinhard=0.5, gamma=1.1):
+def tonemap(lin, reinhard=0.5, gamma=1.1, pow="host"):
     L = oracle_lib()
+    mode = _pow_mode(pow)
     lin = np.ascontiguousarray(lin, np.float32).reshape(-1, 3); n = lin.shape[0]
     tone = np.empty((n, 3), np.float32); q = np.empty((n, 3), np.int32)
-    L.oracle_tonemap(C.c_uint32(n), _p(lin, _f32p), C.c_float(reinhard), C.c_float(gamma), _p(tone, _f32p), _p(q, _i32p))
+    L.oracle_tonemap_pow(C.c_uint32(n), _p(lin, _f32p), C.c_float(reinhard), C.c_float(gamma), _p(tone, _f32p), _p(q, _i32p), mode)
     return tone, q
 
 

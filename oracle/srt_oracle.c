@@ -108,8 +108,23 @@ static inline v3 interp_normal(const float* n9, v3 bc) {
     return normalize3(n);
 }
 
+/* ---- the two pows: glibc powf (ORACLE_POW_HOST, the reference's) or the device's (ORACLE_POW_DEVICE) ---------------- */
+/* simple_raytracer_amd/csrc/srt_device.h pow_like_host / pow_small_int, restated: an integer exponent in [1, 64] on a base in
+ * (1e-30, 1e30) is square-and-multiply in double with one rounding to float (reproducible exactly here); every other input is
+ * the f64 library pow rounded once.  The device's general branch is a polynomial that returns the f64 library pow's float on all
+ * but ~1e-6 of inputs: that residual is the one thing this mode does not reproduce (srt_kat_pow returns both values). */
+static inline float pow_device(float x, float y) {
+    if (x > 1.0e-30f && x < 1.0e30f && y >= 1.0f && y <= 64.0f && y == truncf(y)) {
+        double r = 1.0, b = (double)x;
+        for (uint32_t e = (uint32_t)y; e; e >>= 1) { if (e & 1u) r *= b; b *= b; }
+        return (float)r;
+    }
+    return (float)pow((double)x, (double)y);
+}
+static inline float pow_of(float x, float y, int mode) { return mode == ORACLE_POW_DEVICE ? pow_device(x, y) : powf(x, y); }
+
 /* ---- a8: phongIllumination :144-200 (lightColor = (1,1,1), :433) ------------------------------ */
-static inline v3 phong(v3 n, v3 o, v3 d, v3 L, v3 objColor, float ka, float ks, float shin, float t) {
+static inline v3 phong(v3 n, v3 o, v3 d, v3 L, v3 objColor, float ka, float ks, float shin, float t, int pm) {
     const float rView = 1.0f / 3.14159265358979323846264338327950288f;   /* :153, glm::pi<float>() */
     const v3 lightColor = { 1.0f, 1.0f, 1.0f };
     v3 P = v3add(o, v3scale(d, t));                          /* :156  origin + distance*direction */
@@ -127,7 +142,7 @@ static inline v3 phong(v3 n, v3 o, v3 d, v3 L, v3 objColor, float ka, float ks, 
     v3 I = v3neg(l);                                         /* reflect(-l, n) = I - n*dot(n,I)*2  :191 */
     float ndi = dot3(n, I);
     v3 r = v3make(I.x - (n.x * ndi) * 2.0f, I.y - (n.y * ndi) * 2.0f, I.z - (n.z * ndi) * 2.0f);
-    float sp = powf(glm_max(dot3(r, v), 0.0f), shin);        /* :196 */
+    float sp = pow_of(glm_max(dot3(r, v), 0.0f), shin, pm);     /* :196 */
     v3 specular = v3make(((lightColor.x * ks) * m) * sp, ((lightColor.y * ks) * m) * sp,
                          ((lightColor.z * ks) * m) * sp);
     return v3make((diffuse.x + specular.x) + ambient.x, (diffuse.y + specular.y) + ambient.y,
@@ -135,9 +150,9 @@ static inline v3 phong(v3 n, v3 o, v3 d, v3 L, v3 objColor, float ka, float ks, 
 }
 
 /* ---- a9: Reinhard + gamma (:391-398) and quantiser (:447-449) --------------------------------- */
-static inline float tone1(float c, float reinhard, float gamma) {
+static inline float tone1(float c, float reinhard, float gamma, int pm) {
     c = c / (c + reinhard);
-    return powf(c, gamma);
+    return pow_of(c, gamma, pm);
 }
 /* int(c*255): truncation; c in [0,1) for every finite non-negative sum.  NaN / out of range is
  * undefined behaviour in the reference (x86 yields 0 in the low byte): defined here as clamp, NaN->0. */
@@ -252,9 +267,10 @@ static int in_shadow(const scene_view* s, int32_t self_obj, v3 L, float t, v3 d,
     return 0;
 }
 
-int oracle_render(const srt_scene_desc* d, const srt_params* p,
-                  int32_t* hit_id, float* t_out, float* rgb_linear, float* rgb_tone, uint8_t* rgb8,
-                  srt_stats* stats, int n_threads) {
+int oracle_render_pow(const srt_scene_desc* d, const srt_params* p,
+                      int32_t* hit_id, float* t_out, float* rgb_linear, float* rgb_tone, uint8_t* rgb8,
+                      srt_stats* stats, int n_threads, int pow_mode) {
+    if (pow_mode != ORACLE_POW_HOST && pow_mode != ORACLE_POW_DEVICE) return SRT_ERR_ARG;
     if (!d || !p || !p->width || !p->height || !p->block_rows || !p->block_stride) return SRT_ERR_ARG;
     if (p->n_lights && !p->light_pos) return SRT_ERR_ARG;
     const uint32_t spp = p->spp, spp_n = (uint32_t)lroundf(sqrtf((float)p->spp));
@@ -343,7 +359,7 @@ int oracle_render(const srt_scene_desc* d, const srt_params* p,
                 for (uint32_t l = 0; l < p->n_lights; l++) {                    /* softShadow:366-383 */
                     v3 L = v3make(p->light_pos[l * 3], p->light_pos[l * 3 + 1], p->light_pos[l * 3 + 2]);
                     int sh_hit = in_shadow(&s, obj, L, best, dir, &ws, cam, o);
-                    v3 c = phong(nrm, o, dir, L, color, ka, ks, sh, best);
+                    v3 c = phong(nrm, o, dir, L, color, ka, ks, sh, best, pow_mode);
                     if (sh_hit) c = v3make(c.x / p->shadow_div, c.y / p->shadow_div, c.z / p->shadow_div);   /* :369 */
                     ssum = v3add(ssum, c);                                       /* :370 */
                 }
@@ -351,7 +367,8 @@ int oracle_render(const srt_scene_desc* d, const srt_params* p,
             sum = ss == 0 ? ssum : v3add(sum, ssum);
             }
             if (spp > 1) sum = v3make(sum.x / (float)spp, sum.y / (float)spp, sum.z / (float)spp);
-            tone = v3make(tone1(sum.x, p->reinhard, p->gamma), tone1(sum.y, p->reinhard, p->gamma), tone1(sum.z, p->reinhard, p->gamma));
+            tone = v3make(tone1(sum.x, p->reinhard, p->gamma, pow_mode), tone1(sum.y, p->reinhard, p->gamma, pow_mode),
+                          tone1(sum.z, p->reinhard, p->gamma, pow_mode));
             q[0] = quant1(tone.x); q[1] = quant1(tone.y); q[2] = quant1(tone.z);
             if (rgb_linear) { rgb_linear[pix * 3] = sum.x; rgb_linear[pix * 3 + 1] = sum.y; rgb_linear[pix * 3 + 2] = sum.z; }
             if (rgb_tone) { rgb_tone[pix * 3] = tone.x; rgb_tone[pix * 3 + 1] = tone.y; rgb_tone[pix * 3 + 2] = tone.z; }
@@ -393,11 +410,17 @@ void oracle_ray_aabb(uint32_t n, const float* ray_od, const float* box, uint8_t*
         hit[i] = (uint8_t)ray_aabb(v3make(r[0], r[1], r[2]), v3make(r[3], r[4], r[5]), box + 6 * (size_t)i, box + 6 * (size_t)i + 3);
     }
 }
-void oracle_phong(uint32_t n, const float* in, float* rgb) {
+int oracle_render(const srt_scene_desc* d, const srt_params* p,
+                  int32_t* hit_id, float* t_out, float* rgb_linear, float* rgb_tone, uint8_t* rgb8,
+                  srt_stats* stats, int n_threads) {
+    return oracle_render_pow(d, p, hit_id, t_out, rgb_linear, rgb_tone, rgb8, stats, n_threads, ORACLE_POW_HOST);
+}
+
+void oracle_phong_pow(uint32_t n, const float* in, float* rgb, int pow_mode) {
     for (uint32_t i = 0; i < n; i++) {
         const float* q = in + 28 * (size_t)i;
         v3 c = phong(face_normal(q + 6), v3make(q[0], q[1], q[2]), v3make(q[3], q[4], q[5]), v3make(q[18], q[19], q[20]),
-                     v3make(q[21], q[22], q[23]), q[24], q[25], q[26], q[27]);
+                     v3make(q[21], q[22], q[23]), q[24], q[25], q[26], q[27], pow_mode);
         rgb[i * 3] = c.x; rgb[i * 3 + 1] = c.y; rgb[i * 3 + 2] = c.z;
     }
 }
@@ -416,6 +439,10 @@ void oracle_interp_normal(uint32_t n, const float* in12, float* out3) {
         out3[i * 3] = r.x; out3[i * 3 + 1] = r.y; out3[i * 3 + 2] = r.z;
     }
 }
+void oracle_phong(uint32_t n, const float* in, float* rgb) { oracle_phong_pow(n, in, rgb, ORACLE_POW_HOST); }
+void oracle_tonemap_pow(uint32_t n, const float* lin, float reinhard, float gamma, float* tone, int32_t* q, int pow_mode) {
+    for (uint32_t i = 0; i < 3 * n; i++) { tone[i] = tone1(lin[i], reinhard, gamma, pow_mode); q[i] = quant1(tone[i]); }
+}
 void oracle_tonemap(uint32_t n, const float* lin, float reinhard, float gamma, float* tone, int32_t* q) {
-    for (uint32_t i = 0; i < 3 * n; i++) { tone[i] = tone1(lin[i], reinhard, gamma); q[i] = quant1(tone[i]); }
+    oracle_tonemap_pow(n, lin, reinhard, gamma, tone, q, ORACLE_POW_HOST);
 }

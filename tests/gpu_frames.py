@@ -1,5 +1,6 @@
 """Helpers of the GPU mode tests (tests/test_gpu_modes.py): srt_render_device into pinned host buffers (srt_host_alloc) that carry
-sentinels and one guard row, and the comparison with the oracle at the suite's bars."""
+sentinels and one guard row, the comparison with the oracle at the suite's bars (compare), and the strict colour check against the
+oracle run with the device's pow (compare_exact), which tests/test_gpu_parity.py shares."""
 import ctypes as C
 
 import numpy as np
@@ -114,3 +115,139 @@ def compare(o, c, own, what=""):
         check_rgb8(o["rgb8"][live], c["rgb8"][live])
     for k in ("primary_rays", "hit_rays", "shadow_rays"):
         assert o["stats"][k] == c["stats"][k], (what, k, o["stats"][k], c["stats"][k])
+
+
+# ---- the strict colour bar ------------------------------------------------------------------------------------------------------
+# With pow="device" the oracle computes pow as the kernels' pow_like_host does, except in that function's general branch (a polynomial
+# the host cannot reproduce: it returns the f64 library pow's float on all but ~1e-6 of inputs).  Every other shading operation is
+# the same IEEE operation in the same order on both sides, so the colours are compared bit for bit; what may differ is bounded or
+# explained by srt_kat_pow, which returns both the shipped pow and the library's on the same input.
+RESIDUALS = {"frames": 0, "lin_elements": 0, "lin_differ": 0, "rgb8_explained": 0, "tone_explained": 0}
+LIN_ULP = 2                # at most this many ulp on a differing rgb_linear element of a frame with a general-branch shininess
+LIN_FRAC = 1e-5            # ... on at most max(2, LIN_FRAC * elements) elements
+
+
+def int_shininess_only(flat):
+    """Every object with specular weight has an integer shininess in [1, 64]: the device's pow and the device-mode oracle's are then
+    the same function on every specular input (square-and-multiply, or the library below 1e-30), and rgb_linear is bitwise."""
+    m = np.asarray(flat.obj_material, np.float32).reshape(-1, 3)
+    ks, sh = m[:, 1], m[:, 2]
+    return bool(np.all((ks == 0) | ((sh >= 1) & (sh <= 64) & (sh == np.trunc(sh)))))
+
+
+def same_f32(a, b):
+    """Elementwise: the same bits, or NaN on both sides (a NaN's payload is not part of the contract)."""
+    a = np.ascontiguousarray(a, np.float32); b = np.ascontiguousarray(b, np.float32)
+    return (a.view(np.uint32) == b.view(np.uint32)) | (np.isnan(a) & np.isnan(b))
+
+
+def ulp(a, b):
+    """|a - b| in float32 ulp (NaN on one side only: a huge distance)."""
+    def key(x):
+        i = np.ascontiguousarray(x, np.float32).view(np.int32).astype(np.int64)
+        return np.where(i < 0, -(i & 0x7FFFFFFF), i)
+    na, nb = np.isnan(a), np.isnan(b)
+    return np.where(na & nb, 0, np.where(na | nb, 1 << 40, np.abs(key(a) - key(b))))
+
+
+def tone_inputs(lin, reinhard):
+    """c / (c + reinhard) in float32: what tone1 hands to pow."""
+    c = np.asarray(lin, np.float32)
+    with np.errstate(all="ignore"):
+        return c / (c + np.float32(reinhard))
+
+
+def quant(tone):
+    """quant1: int(c * 255) with the product in float32, clamped to [0, 255], NaN -> 0."""
+    with np.errstate(all="ignore"):
+        s = np.asarray(tone, np.float32) * np.float32(255.0)
+        return np.floor(np.minimum(np.where(s > 0, s, 0).astype(np.float64), 255.0)).astype(np.int32)
+
+
+def _first(mask, idx, cols, o, c, name):
+    """The first set element of mask ((n, 3) over the pixels idx of a frame `cols` wide): where it is and both values."""
+    k = int(np.flatnonzero(mask.reshape(-1))[0])
+    row, col = divmod(int(idx[k // 3]), cols)
+    return f"{name} at local (row {row}, col {col}) channel {k % 3}: device {o.reshape(-1)[k]!r}, oracle {c.reshape(-1)[k]!r}"
+
+
+def compare_exact(srt, o, c, own, flat, p, what=""):
+    """A device frame `o` against the oracle's frame `c` rendered with pow="device", on the live pixels (own >= 0):
+      * hit ids and t bit for bit;
+      * rgb_linear bit for bit when int_shininess_only(flat); otherwise every differing element within LIN_ULP ulp and at most
+        max(2, LIN_FRAC * elements) of them;
+      * rgb8 (and rgb_tone when the frame has it) bit for bit, except on a pixel where the device's pow and the library's disagree on
+        one of its channels' tone-map inputs, recomputed in float32 from the device's rgb_linear (srt_kat_pow), or whose rgb_linear
+        differed above: there the device's bytes must be the quantised tone of the shipped pow, with the black -> background rule;
+      * primary, hit and shadow ray counts equal.
+    `srt` is simple_raytracer_amd.lib (for srt_kat_pow).  Returns the number of (rgb_linear elements, rgb8 pixels) that differed."""
+    live = own >= 0
+    pix, cols = np.flatnonzero(live.reshape(-1)), own.shape[-1]
+    assert np.array_equal(o["hit_id"][live], c["hit_id"][live]), f"{what}: {int((o['hit_id'][live] != c['hit_id'][live]).sum())} hit ids differ"
+    assert np.array_equal(bits(o["t"][live]), bits(c["t"][live])), f"{what}: t differs"
+    for k in ("primary_rays", "hit_rays", "shadow_rays"):
+        assert o["stats"][k] == c["stats"][k], (what, k, o["stats"][k], c["stats"][k])
+    ol, cl = o["rgb_linear"][live], c["rgb_linear"][live]
+    lin_bad = ~same_f32(ol, cl)                                                  # (n, 3)
+    n_lin = int(lin_bad.sum())
+    RESIDUALS["frames"] += 1
+    RESIDUALS["lin_elements"] += int(lin_bad.size)
+    RESIDUALS["lin_differ"] += n_lin
+    if n_lin:
+        head = f"{what}: {n_lin} of {lin_bad.size} rgb_linear elements differ from the device-mode oracle; first " + _first(lin_bad, pix, cols, ol, cl, "rgb_linear")
+        assert not int_shininess_only(flat), head + " (every specular shininess is an integer in [1, 64]: bitwise expected)"
+        d = ulp(ol, cl)
+        assert d.max() <= LIN_ULP, head + f"; max {int(d.max())} ulp"
+        assert n_lin <= max(2, int(LIN_FRAC * lin_bad.size)), head
+    o8, c8 = o["rgb8"][live], c["rgb8"][live]
+    bad8 = np.any(o8 != c8, axis=-1) | np.any(lin_bad, axis=-1)                   # pixels whose bytes must be explained
+    tone_bad = None
+    if "rgb_tone" in o:
+        tone_bad = ~same_f32(o["rgb_tone"][live], c["rgb_tone"][live])
+        bad8 |= np.any(tone_bad, axis=-1)
+    if bad8.any():
+        x = tone_inputs(ol[bad8], p.reinhard)
+        fast, lib = srt.kat_pow(x.reshape(-1), np.full(x.size, p.gamma, np.float32))
+        fast, lib = fast.reshape(x.shape), lib.reshape(x.shape)
+        why = ~same_f32(fast, lib)
+        explained = np.any(why, axis=-1) | np.any(lin_bad[bad8], axis=-1)
+        q = quant(fast)
+        black = np.all(q == 0, axis=-1)
+        q[black] = np.frombuffer(bytes(p.background), np.uint8)[:3]
+        unexplained = ~explained & np.any(o8[bad8] != c8[bad8], axis=-1)
+        assert not unexplained.any(), f"{what}: {int(unexplained.sum())} rgb8 pixels differ with no pow residual to explain them; first " + \
+            _first(np.repeat(unexplained[:, None], 3, 1) & (o8[bad8] != c8[bad8]), pix[bad8], cols, o8[bad8], c8[bad8], "rgb8")
+        wrong = np.any(q != o8[bad8], axis=-1)
+        assert not wrong.any(), f"{what}: {int(wrong.sum())} rgb8 pixels are not the quantised tone of the device's own pow; first " + \
+            _first(np.repeat(wrong[:, None], 3, 1) & (q != o8[bad8]), pix[bad8], cols, o8[bad8], q, "rgb8")
+        RESIDUALS["rgb8_explained"] += int(np.any(o8[bad8] != c8[bad8], axis=-1).sum())
+        if tone_bad is not None:
+            tb = tone_bad[bad8]
+            assert np.all(same_f32(o["rgb_tone"][live][bad8], fast) | ~tb), f"{what}: rgb_tone is not the device's own pow"
+            assert not (tb & ~(why | lin_bad[bad8])).any(), f"{what}: rgb_tone differs with no pow residual to explain it"
+            RESIDUALS["tone_explained"] += int(tb.sum())
+    return n_lin, int(np.any(o8 != c8, axis=-1).sum())
+
+
+def phong_pow_inputs(in28):
+    """What phong hands to pow for each srt_kat_phong / oracle.phong input row (28 floats: o, d, triangle points, light, colour, ka,
+    ks, shininess, t): max(dot(reflect(-l, n), normalize(-d)), 0) in float32 with phong's expression tree, and the shininess."""
+    q = np.asarray(in28, np.float32)
+    one, two = np.float32(1.0), np.float32(2.0)
+
+    def dot(a, b):
+        return (a[:, 0] * b[:, 0] + a[:, 1] * b[:, 1]) + a[:, 2] * b[:, 2]
+
+    def normalize(v):
+        with np.errstate(all="ignore"):
+            return v * (one / np.sqrt(dot(v, v)))[:, None]
+
+    o, d, pts, light, t = q[:, 0:3], q[:, 3:6], q[:, 6:18].reshape(-1, 3, 4)[..., :3], q[:, 18:21], q[:, 27]
+    a, b = pts[:, 1] - pts[:, 0], pts[:, 2] - pts[:, 0]
+    n = normalize(np.stack([a[:, 1] * b[:, 2] - b[:, 1] * a[:, 2], a[:, 2] * b[:, 0] - b[:, 2] * a[:, 0], a[:, 0] * b[:, 1] - b[:, 0] * a[:, 1]], 1))
+    l = normalize(light - (o + d * t[:, None]))
+    v = normalize(-d)
+    i = -l
+    r = i - (n * dot(n, i)[:, None]) * two
+    sx = dot(r, v)
+    return np.where(sx < 0, np.float32(0.0), sx), q[:, 26].copy()

@@ -7,7 +7,9 @@ against float64.
 Frames go through srt_render_device into pinned host buffers filled with sentinels and carrying one guard row: after every render
 the padding of a tile deal (include/srt.h: "not written") and the guard row must still hold the sentinels.
 Bars as in tests/test_gpu_parity.py: hit id and t bit for bit, pre-tone-map RGB within TOL_LINEAR (relative to the frame's
-maximum), rgb8 <= 1 LSB on at most 1e-3 of the pixels, primary / hit / shadow ray counts equal."""
+maximum), rgb8 <= 1 LSB on at most 1e-3 of the pixels, primary / hit / shadow ray counts equal.  Next to that every frame meets the
+strict bar of tests/gpu_frames.compare_exact against the oracle run with the device's pow: colours bit for bit up to the residual of
+the device pow's general branch, which srt_kat_pow explains."""
 import copy
 
 import numpy as np
@@ -127,14 +129,22 @@ class World:
     def params(self, name, W, H, L, camera=False, flags=0, **kw):
         return abi.make_params(W, H, abi.light_staircase(self.flat(name)[1], L), ray_matrix=camera_matrix() if camera else None, flags=flags, **kw)
 
-    def oracle(self, oracle, name, p):
+    def oracle(self, oracle, name, p, pow="host"):
         """The oracle's frame; cached by everything the oracle reads (the hint and the variant bits are not among it)."""
-        key = (name, tuple(getattr(p, k) for k in ("width", "height", "block_rows", "block_first", "block_stride", "block_cols", "focal",
+        key = (name, pow, tuple(getattr(p, k) for k in ("width", "height", "block_rows", "block_first", "block_stride", "block_cols", "focal",
                                                     "n_lights", "shadow_div", "reinhard", "gamma", "spp")),
                bytes(p.background), p.flags & abi.SRT_FLAG_SMOOTH_NORMALS, p._lights.tobytes(), getattr(p, "_ray_matrix", np.zeros(0)).tobytes())
         if key not in self.oracle_cache:
-            self.oracle_cache[key] = oracle.render(self.flat(name)[0], p)
+            self.oracle_cache[key] = oracle.render(self.flat(name)[0], p, pow=pow)
         return self.oracle_cache[key]
+
+    def check(self, srt, oracle, name, o, p, what):
+        """Both bars: compare against the oracle as the reference computes pow, compare_exact against the device-mode oracle."""
+        own = gf.owned(p)
+        c = self.oracle(oracle, name, p)
+        gf.compare(o, c, own, what)
+        gf.compare_exact(srt, o, self.oracle(oracle, name, p, pow="device"), own, self.flat(name)[0], p, what)
+        return c
 
 
 @pytest.fixture(scope="module")
@@ -161,8 +171,7 @@ def render_check(srt, oracle, world, chain, p, what):
     scene, _, _, _, want = CHAINS[chain]
     o, pipe = gf.render_pinned(srt, world.ds(scene), p)
     assert pipe == want, (what, pipe)
-    c = world.oracle(oracle, scene, p)
-    gf.compare(o, c, gf.owned(p), what)
+    c = world.check(srt, oracle, scene, o, p, what)
     return o, c
 
 
@@ -236,8 +245,7 @@ def test_call_that_owns_no_rows(srt, oracle, world, chain):
         empty.check_untouched(gf.owned(p0), "no rows behind a pending frame")
         out = frame.out()
         out["stats"] = st
-        c = world.oracle(oracle, scene, p)
-        gf.compare(out, c, gf.owned(p), f"{chain}: pending frame")
+        world.check(srt, oracle, scene, out, p, f"{chain}: pending frame")
         assert st["hit_rays"] > 0
     finally:
         empty.free()
@@ -271,8 +279,7 @@ def test_light_count_boundaries(srt, oracle, world, name, L):
         p = world.params(name, 64, 48, L, **kw)
         o, pipe = gf.render_pinned(srt, ds, p)
         assert pipe == bucket_pipeline(L, ds.overlap_estimate), (L, pipe)
-        c = world.oracle(oracle, name, p)
-        gf.compare(o, c, gf.owned(p), f"{name} L {L} {kw}")
+        c = world.check(srt, oracle, name, o, p, f"{name} L {L} {kw}")
         assert (c["hit_id"] >= 0).sum() > 100
 
 
@@ -373,7 +380,63 @@ def test_device_pow_at_its_cutoffs(srt):
     assert (d > 0).sum() <= max(1, int(1e-5 * d.size))
 
 
-# ---- 6. limits -----------------------------------------------------------------------------------------------------------------
+# ---- 6. the shading arithmetic, bit for bit ---------------------------------------------------------------------------------------
+# Materials, colours, shadow divisors, light counts and supersampling that move the colours and nothing else, each through every
+# shipped chain and checked with compare_exact only: a reordered sum, a reciprocal for a divide or a contracted multiply-add in the
+# shading path changes a few ulp, which the 1e-4 bar of compare cannot see.
+SHADING = {
+    **{f"shininess {s:g}": dict(material=(0.2, 0.5, s)) for s in (1.0, 2.0, 15.0, 63.0, 64.0, 65.0, 64.5, 0.5, 0.0)},   # integer path edges; pow(0, 0)
+    **{f"shadow_div {d:g}": dict(shadow_div=d) for d in (2.0, 3.0, 0.7)},
+    "ka ks 0": dict(material=(0.0, 0.0, 15.0)),
+    "ka ks 1": dict(material=(1.0, 1.0, 15.0)),
+    "ka ks above 1": dict(material=(2.5, 3.75, 7.0)),
+    "ka 0 ks above 1 shininess 64.5": dict(material=(0.0, 1.7, 64.5)),
+    "colour 0": dict(color=(0.0, 0.0, 0.0)),
+    "colour above 1": dict(color=(1.75, 0.0, 3.2), material=(1.3, 0.25, 33.0)),
+    **{f"lights {n}": dict(lights=n) for n in (63, 64, 65, 128, 129)},      # where a kernel could split the light sum into groups
+    "spp 4": dict(spp=4, material=(0.2, 0.5, 2.5)),
+    "spp 4 smooth": dict(spp=4, smooth=True),
+    "spp 16 smooth": dict(spp=16, smooth=True, material=(0.4, 1.5, 64.5)),
+}
+
+
+def shaded_flat(flat, case):
+    """The chain's scene with every object's colour and / or material replaced (textured triangles keep their texels)."""
+    f = copy.copy(flat)
+    if "material" in case:
+        f.obj_material = np.ascontiguousarray(np.tile(np.asarray(case["material"], np.float32), (f.n_objects, 1)))
+    if "color" in case:
+        f.obj_color = np.ascontiguousarray(np.tile(np.asarray(case["color"], np.float32), (f.n_objects, 1)))
+    return f
+
+
+@pytest.mark.parametrize("case", list(SHADING))
+def test_shading_arithmetic_bitwise(srt, oracle, world, case):
+    """One shading case through all twelve chains (camera mode, the XCD row deal and the unlit kernels included), 64 x 48 frames (the
+    light-count cases move the chain to the pipeline of that count).  Every frame is the device-mode oracle's, bit for bit up to the
+    residual of pow's general branch."""
+    kw = SHADING[case]
+    flats, scenes = {}, {}
+    try:
+        for chain, (scene, L, cam, variant, want) in CHAINS.items():
+            if scene not in scenes:
+                flats[scene] = shaded_flat(world.flat(scene)[0], kw)
+                scenes[scene] = srt.DeviceScene(flats[scene])
+            n = kw.get("lights", L)
+            p = world.params(scene, 64, 48, n, camera=cam, flags=(variant << 8) | (abi.SRT_FLAG_SMOOTH_NORMALS if kw.get("smooth") else 0),
+                             spp=kw.get("spp", 1), shadow_div=kw.get("shadow_div", 5.0))
+            what = f"{case}: {chain}"
+            o, pipe = gf.render_pinned(srt, scenes[scene], p)
+            assert pipe == want or "lights" in kw, (what, pipe)
+            c = oracle.render(flats[scene], p, pow="device")
+            gf.compare_exact(srt, o, c, gf.owned(p), flats[scene], p, what)
+            assert (c["hit_id"] >= 0).sum() > 10, what
+    finally:
+        for ds in scenes.values():
+            ds.close()
+
+
+# ---- 7. limits -----------------------------------------------------------------------------------------------------------------
 def test_supersampled_frame_beyond_the_accumulation_index_is_refused(srt, world):
     """spp > 1 accumulates 3 floats per pixel under a 32-bit index: 40000 x 40000 at spp = 4 is refused with SRT_ERR_LIMIT before
     anything is allocated or launched, by srt_render, srt_render_device and the batch call."""

@@ -182,3 +182,86 @@ def test_emitted_pixel_counts_of_the_survey(oracle):
         p.background[0] = p.background[1] = p.background[2] = 0          # black = "not emitted"
         o = oracle.render(g.flat, p)
         assert int((o["rgb8"].reshape(-1, 3).max(1) > 0).sum()) == want, (name, W, H)
+
+
+# ---- the device-pow mode (pow="device"): the kernels' pow in place of glibc powf, nothing else ----------------------------------
+def test_device_pow_mode_of_the_leaf_functions(oracle, kat):
+    """oracle.phong / oracle.tonemap with pow="device" differ from the default only on inputs where glibc powf and the device's pow
+    (tonemap_ref.pow_device_ref) return different floats for what phong / tone1 hand to pow; the device-mode tone map is that pow
+    of c / (c + r) bit for bit, at every test literal."""
+    inp = kat["ph_in"]
+    host, dev = oracle.phong(inp), oracle.phong(inp, pow="device")
+    assert np.array_equal(bits(host), bits(kat["ph_rgb"]))                 # the default is still the reference's
+    import gpu_frames as gf
+    sx, sh = gf.phong_pow_inputs(inp)
+    with np.errstate(all="ignore"):
+        glibc = np.power(sx, sh)                                            # float32 power: the C library's powf
+    differs = ~gf.same_f32(glibc, tr.pow_device_ref(sx, sh))
+    changed = np.any(~gf.same_f32(host, dev), axis=1)
+    assert not (changed & ~differs).any(), np.flatnonzero(changed & ~differs)[:5]
+    for reinhard in tr.REINHARD:
+        for gamma in tr.GAMMA:
+            lin = tr.inputs(reinhard, gamma, n_random=6000)
+            tone, q = oracle.tonemap(lin, reinhard, gamma, pow="device")
+            want = tr.pow_device_ref(gf.tone_inputs(lin, reinhard), np.float32(gamma))
+            assert np.array_equal(bits(tone)[~np.isnan(want)], bits(want)[~np.isnan(want)]) and np.isnan(tone[np.isnan(want)]).all(), (reinhard, gamma)
+            assert np.array_equal(q, tr.quant_ref(tone))
+    with pytest.raises(ValueError):
+        oracle.tonemap(kat["tm_lin"], pow="glibc")
+
+
+def _pixel_phong_rows(flat, p, y, x, hit, t, lights):
+    """The 28-float phong input of every light at one pixel of a 1-spp frame without camera (o = 0, the reference's ray), the colour
+    from the object or its texel as softShadow reads it (simple_raytracer.cpp:350-361)."""
+    W, H = p.width, p.height
+    d = np.array([np.float32(int(-W / 2) + x), np.float32(int(-H / 2) + y), np.float32(p.focal)], np.float32)
+    obj = int(flat.tri_obj[hit])
+    color = np.asarray(flat.obj_color, np.float32).reshape(-1, 3)[obj]
+    tex = int(flat.tri_tex[hit]) if flat.tri_tex is not None else -1
+    pts = np.asarray(flat.tri_points, np.float32).reshape(-1, 12)[hit]
+    if tex >= 0:
+        P = d * np.float32(t)
+        bc_in = np.concatenate([pts, P]).astype(np.float32)[None]
+        bc = oracle_bary(bc_in)[0]
+        tc = np.asarray(flat.tri_texcoord, np.float32).reshape(-1, 6)[hit]
+        tx = (bc[0] * tc[0] + bc[1] * tc[2]) + bc[2] * tc[4]
+        ty = (bc[0] * tc[1] + bc[1] * tc[3]) + bc[2] * tc[5]
+        w, h = int(flat.tex_w[tex]), int(flat.tex_h[tex])
+        i = min(max((int(ty) * w + int(tx)) * 3, 0), w * h * 3 - 3)
+        td = flat.tex_rgb[int(flat.tex_off[tex]) + i:][:3]
+        color = td.astype(np.float32) / np.float32(255.0)
+    mat = np.asarray(flat.obj_material, np.float32).reshape(-1, 3)[obj]
+    rows = np.zeros((len(lights), 28), np.float32)
+    rows[:, 3:6] = d; rows[:, 6:18] = pts; rows[:, 18:21] = lights; rows[:, 21:24] = color; rows[:, 24:27] = mat; rows[:, 27] = t
+    return rows
+
+
+def oracle_bary(inp):
+    from oracle import pyoracle
+    return pyoracle.barycentric(inp)
+
+
+@pytest.mark.parametrize("name", gu.SCENES)
+def test_device_pow_mode_changes_colours_only_through_pow(oracle, name):
+    """pow="device" on every golden scene (its smallest render): hit ids, t and the ray counts are the default mode's bit for bit;
+    an rgb_linear element changes only where the specular pow of one of the pixel's lights returns another float under the two
+    functions (the pixel's phong inputs rebuilt and run through oracle.phong in both modes); rgb_tone is tone1 of the device pow on the
+    frame's own rgb_linear."""
+    g = gu.GoldenScene(name)
+    W, H, L = min(g.renders, key=lambda r: (r[0] * r[1] * r[2], r))
+    p = g.params(W, H, L)
+    a, b = oracle.render(g.flat, p), oracle.render(g.flat, p, pow="device")
+    assert np.array_equal(a["hit_id"], b["hit_id"]) and np.array_equal(bits(a["t"]), bits(b["t"]))
+    for k in ("primary_rays", "hit_rays", "shadow_rays", "node_tests_primary", "node_tests_shadow", "tri_tests_primary", "tri_tests_shadow"):
+        assert a["stats"][k] == b["stats"][k], k
+    lights = abi.light_staircase(g.light, L)
+    changed = np.argwhere(~np.all(bits(a["rgb_linear"]) == bits(b["rgb_linear"]), axis=-1))
+    assert len(changed) <= max(2, int(1e-3 * W * H)), len(changed)
+    for y, x in changed:
+        rows = _pixel_phong_rows(g.flat, p, int(y), int(x), int(a["hit_id"][y, x]), a["t"][y, x], lights)
+        by_light = ~np.all(bits(oracle.phong(rows)) == bits(oracle.phong(rows, pow="device")), axis=0)
+        ch = bits(a["rgb_linear"][y, x]) != bits(b["rgb_linear"][y, x])
+        assert not (ch & ~by_light).any(), (name, int(y), int(x))
+    tone, q = oracle.tonemap(b["rgb_linear"], p.reinhard, p.gamma, pow="device")
+    assert np.array_equal(bits(tone.reshape(b["rgb_tone"].shape)), bits(b["rgb_tone"]))
+    assert np.array_equal(bits(oracle.tonemap(a["rgb_linear"], p.reinhard, p.gamma)[0].reshape(a["rgb_tone"].shape)), bits(a["rgb_tone"]))

@@ -15,6 +15,23 @@ def tone_ref(lin, reinhard, gamma):
         return np.power(ratio.astype(np.float64), np.float64(np.float32(gamma))).astype(np.float32)
 
 
+def pow_device_ref(x, y):
+    """The device's pow as the oracle's device mode restates it (simple_raytracer_amd/csrc/srt_device.h pow_like_host): x^e for an
+    integer e in [1, 64] and x in (1e-30, 1e30) by square-and-multiply in float64 with one rounding, otherwise the float64 pow
+    rounded once.  Elementwise over float32 arrays."""
+    x = np.asarray(x, np.float32); y = np.broadcast_to(np.asarray(y, np.float32), x.shape)
+    with np.errstate(all="ignore"):
+        out = np.power(x.astype(np.float64), y.astype(np.float64)).astype(np.float32)
+        small = (x > np.float32(1e-30)) & (x < np.float32(1e30)) & (y >= 1) & (y <= 64) & (y == np.trunc(y))
+        r, b = np.ones(x.shape, np.float64), x.astype(np.float64)
+        e = np.where(small, y, 0).astype(np.int64)
+        while e.any():
+            r = np.where(e & 1, r * b, r)
+            b = b * b
+            e >>= 1
+        return np.where(small, r.astype(np.float32), out)
+
+
 def quant_ref(tone):
     """int(c * 255) with the product in float32, clamped to [0, 255], NaN -> 0."""
     with np.errstate(all="ignore"):
