@@ -292,6 +292,11 @@ double srt_scene_overlap_estimate(const srt_scene* s);
 int srt_kat_ray_aabb(int device, uint32_t n, const float* ray_od, const float* box, uint8_t* exact, uint8_t* branchless,
                      uint8_t* filtered, uint8_t* ambiguous);
 int srt_kat_ray_triangle(int device, uint32_t n, const float* ray_od, const float* tri_points, float* t);
+/* rayTriangleIntersection for rays FROM THE ORIGIN, as every primary ray runs it: both triangle records are derived as
+ * srt_scene_create derives them and the test reads the one that carries tvec and qvec.  dir = n x 3; t as above. */
+int srt_kat_ray_triangle_origin(int device, uint32_t n, const float* dir /* n x 3 */, const float* tri_points, float* t);
+/* calculateBarycentricCoords (:79-117): in15 = tri_points(12) point(3), out3 = (u, v, w) */
+int srt_kat_barycentric(int device, uint32_t n, const float* in15, float* out3);
 int srt_kat_phong(int device, uint32_t n, const float* in28, float* rgb);
 int srt_kat_interp_normal(int device, uint32_t n, const float* in12 /* 3 normals + barycentrics */, float* out3);   /* interpolateNormal :132-140 */
 int srt_kat_pow(int device, uint32_t n, const float* x, const float* y, float* fast, float* lib);   /* the device powf: shipped form vs (float)pow(double) */

@@ -125,14 +125,34 @@ __device__ __forceinline__ bool ray_aabb_nb(V3 o, V3 d, float mnx, float mny, fl
 // minZ <= hi, so the box passes iff  tnear = max3(minX, minY, minZ) <= tfar = min3(maxX, maxY, maxZ).
 // min / max selection is 1-Lipschitz, so tnear and tfar carry the quotients' relative error and ONE
 // comparison with a margin that covers both decides; if it falls inside the margin `ambiguous` is set and
-// the caller must evaluate ray_aabb_nb (the reference's comparisons one by one).  Non-finite quotients
-// (d = 0, 0 * inf, the FLT_MAX boxes of empty leaves) end up as an infinity or NaN in tnear / tfar -- a
-// NaN quotient always has an infinite partner from the same rcp, and v_min / v_max return the other
-// operand -- which makes the margin infinite or the difference NaN: ambiguous as well.
+// the caller must evaluate ray_aabb_nb (the reference's comparisons one by one).  An infinite quotient
+// (an overflowing product, an infinite box coordinate, the FLT_MAX boxes of empty leaves) ends up as an
+// infinity in tnear / tfar, which makes the margin infinite or the difference NaN: ambiguous as well.
+// What the comparison cannot see is a quotient that v_min / v_max DROP or that stops binding:
+//   * d = 0 on an axis where the box is flat at the origin's coordinate: both quotients are 0 * inf = NaN, v_min /
+//     v_max return the other operand, and tnear / tfar come from the other two axes alone, finite -- while the
+//     reference, whose comparisons with a NaN are all false, passes or rejects the box by other rules;
+//   * a NaN direction component: the same;
+//   * |d| below 2^-126: the reciprocal overflows (or the subnormal is flushed) and the axis becomes (-inf, +inf)
+//     where the true interval is finite and may reject;
+//   * |d| above 2^126: the reciprocal is subnormal and may be flushed to 0, which collapses the axis to [0, 0].
+// All four are properties of the RAY, so ray_rcp decides them once per ray: a ray with a direction component that is
+// zero, subnormal, above 2^126, infinite or NaN gets NaN for ALL THREE reciprocals.  Then every quotient is NaN, so
+// are tnear, tfar and their difference, and every box is ambiguous for that ray (in a frame: the pixel column i = 0
+// and the pixel row j = 0).  Whoever assembles a RayRcp from parts must keep that all-or-nothing rule (rcp_axis_ok).
 // When `ambiguous` is false the returned bool equals the reference's.
 struct RayRcp { float x, y, z; };
+// a direction component whose reciprocal the filter may use: normal, and with a normal reciprocal (false for NaN)
+__device__ __forceinline__ bool rcp_axis_ok(float d) {
+    const float a = __builtin_fabsf(d);
+    return (a >= 0x1p-126f) & (a <= 0x1p126f);
+}
 __device__ __forceinline__ RayRcp ray_rcp(V3 d) {
-    RayRcp r; r.x = __builtin_amdgcn_rcpf(d.x); r.y = __builtin_amdgcn_rcpf(d.y); r.z = __builtin_amdgcn_rcpf(d.z); return r;
+    RayRcp r;
+    const bool ok = rcp_axis_ok(d.x) & rcp_axis_ok(d.y) & rcp_axis_ok(d.z);
+    const float nan = __builtin_nanf("");
+    r.x = ok ? __builtin_amdgcn_rcpf(d.x) : nan; r.y = ok ? __builtin_amdgcn_rcpf(d.y) : nan; r.z = ok ? __builtin_amdgcn_rcpf(d.z) : nan;
+    return r;
 }
 __device__ __forceinline__ bool ray_aabb_filtered(V3 o, RayRcp rc, float mnx, float mny, float mnz, float mxx, float mxy, float mxz,
                                                   bool& ambiguous) {

@@ -1384,6 +1384,34 @@ int srt_kat_ray_triangle(int device, uint32_t n, const float* ray_od, const floa
     });
 }
 
+int srt_kat_ray_triangle_origin(int device, uint32_t n, const float* dir, const float* tri_points, float* t) {
+    if (!n || !dir || !tri_points || !t) return SRT_ERR_ARG;
+    return guarded([&]() -> int {
+    HIP_TRY(hipSetDevice(device));
+    std::vector<DevTriO> tris_o(n);           // both records as srt_scene_create derives them
+    for (uint32_t i = 0; i < n; i++) tris_o[i] = derive_triangle_origin(derive_triangle(tri_points + 12 * (size_t)i));
+    DevBuf r, q, o;
+    KAT_TRY(r.up(dir, (size_t)n * 12)); KAT_TRY(q.up(tris_o.data(), (size_t)n * sizeof(DevTriO))); KAT_TRY(o.alloc((size_t)n * 4));
+    hipLaunchKernelGGL(k_kat_ray_triangle_origin, dim3((n + 255) / 256), dim3(256), 0, 0, n, (const float*)r.p, (const DevTriO*)q.p, (float*)o.p);
+    HIP_TRY(hipGetLastError()); HIP_TRY(hipDeviceSynchronize());
+    return o.down(t, (size_t)n * 4);
+    });
+}
+
+int srt_kat_barycentric(int device, uint32_t n, const float* in15, float* out3) {
+    if (!n || !in15 || !out3) return SRT_ERR_ARG;
+    return guarded([&]() -> int {
+    HIP_TRY(hipSetDevice(device));
+    std::vector<DevTri> tris(n);
+    for (uint32_t i = 0; i < n; i++) tris[i] = derive_triangle(in15 + 15 * (size_t)i);
+    DevBuf a, q, o;
+    KAT_TRY(a.up(in15, (size_t)n * 60)); KAT_TRY(q.up(tris.data(), (size_t)n * sizeof(DevTri))); KAT_TRY(o.alloc((size_t)n * 12));
+    hipLaunchKernelGGL(k_kat_barycentric, dim3((n + 255) / 256), dim3(256), 0, 0, n, (const float*)a.p, (const DevTri*)q.p, (float*)o.p);
+    HIP_TRY(hipGetLastError()); HIP_TRY(hipDeviceSynchronize());
+    return o.down(out3, (size_t)n * 12);
+    });
+}
+
 int srt_kat_phong(int device, uint32_t n, const float* in28, float* rgb) {
     if (!n || !in28 || !rgb) return SRT_ERR_ARG;
     return guarded([&]() -> int {

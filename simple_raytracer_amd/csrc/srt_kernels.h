@@ -408,7 +408,7 @@ __device__ __forceinline__ void closest_hit_phase(const DevScene& s, const DevPa
         best[lane] = ~0ull;
         if (live) dmine = primary_dir(p, px, image_row(p, r));
         if (CAM) dir[lane] = make_float4(dmine.x, dmine.y, dmine.z, 0.f);
-        else dir[lane] = make_float4(dmine.x, dmine.y, __builtin_amdgcn_rcpf(dmine.x), __builtin_amdgcn_rcpf(dmine.y));   // + reciprocals for the filtered slab test
+        else { const RayRcp rq = ray_rcp(dmine); dir[lane] = make_float4(dmine.x, dmine.y, rq.x, rq.y); }   // + reciprocals for the filtered slab test (all NaN for a ray the filter must not decide; dmine.z is p.focal)
     }
     const float rcp_focal = __builtin_amdgcn_rcpf(p.focal);
     const unsigned long long livem = __ballot(live);
@@ -520,7 +520,7 @@ __device__ __forceinline__ void closest_hit_phase(const DevScene& s, const DevPa
                 const V3 d = mk(dxy.x, dxy.y, CAM ? dxy.z : p.focal);
                 RayRcp rc;
                 if (CAM) rc = ray_rcp(d);
-                else { rc.x = dxy.z; rc.y = dxy.w; rc.z = rcp_focal; }
+                else { rc.x = dxy.z; rc.y = dxy.w; rc.z = __builtin_fmaf(dxy.z, 0.0f, rcp_focal); }      // rcp_focal, or NaN with the other two (ray_rcp's rule)
                 if (COUNT) n_node++;
                 ok = slab_pass<FILTER>(o, d, rc, a.x, a.y, a.z, a.w, b.x, b.y);
             }
@@ -561,7 +561,7 @@ __device__ __forceinline__ void closest_hit_phase(const DevScene& s, const DevPa
                 d = mk(dxy.x, dxy.y, CAM ? dxy.z : p.focal);
                 RayRcp rc;
                 if (CAM) rc = ray_rcp(d);
-                else { rc.x = dxy.z; rc.y = dxy.w; rc.z = rcp_focal; }
+                else { rc.x = dxy.z; rc.y = dxy.w; rc.z = __builtin_fmaf(dxy.z, 0.0f, rcp_focal); }      // rcp_focal, or NaN with the other two (ray_rcp's rule)
                 linfo = r3.x; rinfo = r3.y; node = r3.z; rnode = r3.w;
                 if (COUNT) n_node += 2;
                 bool pass_l, pass_r;
@@ -689,7 +689,7 @@ __device__ __forceinline__ void closest_hit_phase(const DevScene& s, const DevPa
                     bool amb;
                     RayRcp rc;
                     if (CAM) rc = ray_rcp(d);
-                    else { rc.x = dxy.z; rc.y = dxy.w; rc.z = rcp_focal; }
+                    else { rc.x = dxy.z; rc.y = dxy.w; rc.z = __builtin_fmaf(dxy.z, 0.0f, rcp_focal); }      // rcp_focal, or NaN with the other two (ray_rcp's rule)
                     pass = ray_aabb_filtered(o, rc, a.x, a.y, a.z, a.w, b.x, b.y, amb);
                     if (amb) pass = ray_aabb_nb(o, d, a.x, a.y, a.z, a.w, b.x, b.y);      // rare: exact divides decide
                 } else {
@@ -1945,6 +1945,21 @@ __global__ void k_kat_ray_triangle(uint32_t n, const float* __restrict__ ray_od,
     if (i >= n) return;
     const float* r = ray_od + 6 * (size_t)i; const DevTri q = tris[i];
     t[i] = ray_triangle(mk(r[0], r[1], r[2]), mk(r[3], r[4], r[5]), mk(q.p1x, q.p1y, q.p1z), mk(q.e1x, q.e1y, q.e1z), mk(q.e2x, q.e2y, q.e2z));
+}
+// the test every primary ray runs: a ray from the origin on the record that carries tvec and qvec
+__global__ void k_kat_ray_triangle_origin(uint32_t n, const float* __restrict__ dir, const DevTriO* __restrict__ tris_o, float* __restrict__ t) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float* r = dir + 3 * (size_t)i; const DevTriO q = tris_o[i];
+    t[i] = ray_triangle_origin(mk(r[0], r[1], r[2]), mk(q.tx, q.ty, q.tz), mk(q.e1x, q.e1y, q.e1z), mk(q.e2x, q.e2y, q.e2z), mk(q.qx, q.qy, q.qz));
+}
+// in15: the triangle's points (12) and the point whose coordinates are asked for (3)
+__global__ void k_kat_barycentric(uint32_t n, const float* __restrict__ in15, const DevTri* __restrict__ tris, float* __restrict__ out3) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float* q = in15 + 15 * (size_t)i; const DevTri tr = tris[i];
+    const V3 b = barycentric(mk(tr.p1x, tr.p1y, tr.p1z), mk(tr.e1x, tr.e1y, tr.e1z), mk(tr.e2x, tr.e2y, tr.e2z), mk(q[12], q[13], q[14]));
+    out3[i * 3] = b.x; out3[i * 3 + 1] = b.y; out3[i * 3 + 2] = b.z;
 }
 // in: ray_od(6) normal-from-DevTri(3 via tris) light(3) color(3) props(3) t(1)
 __global__ void k_kat_phong(uint32_t n, const float* __restrict__ in, const DevTri* __restrict__ tris, float* __restrict__ rgb) {

@@ -19,7 +19,7 @@ LIB_PATH = os.path.join(_HERE, "libsrt_hip.so")
 ABI_SYMBOLS = ("srt_params_default", "srt_light_staircase", "srt_rows_owned", "srt_cols_owned", "srt_scene_create", "srt_scene_destroy", "srt_scene_update", "srt_scene_share",
                "srt_render_device", "srt_render_device_batch", "srt_render", "srt_render_async", "srt_host_alloc", "srt_host_free", "srt_sync", "srt_scene_device_bytes", "srt_strerror",
                "srt_last_hip_error", "srt_abi_version", "srt_kat_ray_aabb", "srt_kat_ray_triangle", "srt_kat_phong", "srt_kat_tonemap", "srt_kat_interp_normal", "srt_kat_pow",
-               "srt_debug_fail_host_allocs", "srt_debug_valu_rate", "srt_debug_scene_records", "srt_scene_set_source", "srt_scene_update_frame",
+               "srt_kat_ray_triangle_origin", "srt_kat_barycentric", "srt_debug_fail_host_allocs", "srt_debug_valu_rate", "srt_debug_scene_records", "srt_scene_set_source", "srt_scene_update_frame",
                "srt_scene_pipeline", "srt_scene_overlap_estimate")
 
 _f32p, _i32p, _u8p = C.POINTER(C.c_float), C.POINTER(C.c_int32), C.POINTER(C.c_uint8)
@@ -86,6 +86,8 @@ def load():
         L.srt_debug_fail_host_allocs.restype = None
         L.srt_kat_ray_aabb.argtypes = [C.c_int, C.c_uint32, _f32p, _f32p, _u8p, _u8p, _u8p, _u8p]
         L.srt_kat_ray_triangle.argtypes = [C.c_int, C.c_uint32, _f32p, _f32p, _f32p]
+        L.srt_kat_ray_triangle_origin.argtypes = [C.c_int, C.c_uint32, _f32p, _f32p, _f32p]
+        L.srt_kat_barycentric.argtypes = [C.c_int, C.c_uint32, _f32p, _f32p]
         L.srt_kat_phong.argtypes = [C.c_int, C.c_uint32, _f32p, _f32p]
         L.srt_kat_interp_normal.argtypes = [C.c_int, C.c_uint32, _f32p, _f32p]
         L.srt_kat_pow.argtypes = [C.c_int, C.c_uint32, _f32p, _f32p, _f32p, _f32p]
@@ -263,6 +265,19 @@ def kat_ray_triangle(ray_od, tri_points, device=0):
     L = load(); ray_od, tri_points = _f(ray_od), _f(tri_points); n = ray_od.shape[0]; t = np.empty(n, np.float32)
     _check(L.srt_kat_ray_triangle(device, n, ray_od.ctypes.data_as(_f32p), tri_points.ctypes.data_as(_f32p), t.ctypes.data_as(_f32p)), "srt_kat_ray_triangle")
     return t
+
+
+def kat_ray_triangle_origin(dir3, tri_points, device=0):
+    """The origin form of the triangle test (what primary rays run): directions n x 3, the record derived as srt_scene_create does."""
+    L = load(); dir3, tri_points = _f(dir3), _f(tri_points); n = dir3.shape[0]; t = np.empty(n, np.float32)
+    _check(L.srt_kat_ray_triangle_origin(device, n, dir3.ctypes.data_as(_f32p), tri_points.ctypes.data_as(_f32p), t.ctypes.data_as(_f32p)), "srt_kat_ray_triangle_origin")
+    return t
+
+
+def kat_barycentric(in15, device=0):
+    L = load(); in15 = _f(in15); n = in15.shape[0]; out = np.empty((n, 3), np.float32)
+    _check(L.srt_kat_barycentric(device, n, in15.ctypes.data_as(_f32p), out.ctypes.data_as(_f32p)), "srt_kat_barycentric")
+    return out
 
 
 def kat_phong(in28, device=0):

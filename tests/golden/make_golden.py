@@ -9,6 +9,8 @@ Runs only in the build container (needs /root/reference and oracle/_ref/libsrt_r
 Fixtures (all produced by the reference's own functions through oracle/ref_harness.cpp):
   kat.npz                  leaf-function known-answer vectors (a4, a5, a8, a8b, a9, light staircase,
                            Transformation.h factories + glm inverse / mat*vec)
+  leaf_kat.npz             the same leaf functions on a subsample of the input families of tests/leaf_vectors.py (far beyond
+                           scene scale); inputs and outputs
   meshes/<key>.npz         triangle meshes as the reference's loader (tinyobjloader) produced them
   jpeg.npz                 small synthetic JPEG files (encoded here with Pillow) and the bytes the reference's
                            stbi_load decodes them to; sha256 of the decode of the reference's own JPEG textures
@@ -351,6 +353,28 @@ def make_kat():
     print("kat.npz", os.path.getsize(os.path.join(HERE, "kat.npz")) // 1024, "KiB")
 
 
+def make_leaf_kat():
+    """The reference's leaf functions on a fixed subsample of every family of tests/leaf_vectors.py (inputs far beyond scene scale:
+    2^-120 .. 2^116, w != 1, zero / subnormal / non-finite direction components, flat and infinite boxes): the subsample's inputs, so
+    that a drift of the generators is noticed, and the reference's outputs -- hit flags as packed bits."""
+    import leaf_vectors as lv
+    d = {}
+    ray, box, names, rows = lv.recorded_rows(lv.box_families())
+    d["box_ray"], d["box_box"], d["box_family"], d["box_row"] = ray, box, names, rows.astype(np.int32)
+    d["box_hit_bits"] = np.packbits(po.ref_kat_ray_aabb(ray, box)[0])
+    fams = lv.tri_families()
+    ray, tri, names, rows = lv.recorded_rows(fams)
+    d["tri_ray"], d["tri_tri"], d["tri_family"], d["tri_row"] = ray, tri, names, rows.astype(np.int32)
+    d["tri_t"] = po.ref_kat_ray_triangle(ray, tri)
+    sub = [lv.Family(f.name, "tri", f.ray[lv.subsample(f.ray.shape[0])], tri=f.tri[lv.subsample(f.ray.shape[0])]) for f in fams]
+    d["bc_uvw"] = po.ref_kat_barycentric(lv.bary_inputs(sub))
+    d["in_out"] = po.ref_kat_interp_normal(lv.interp_inputs(sub))
+    path = os.path.join(HERE, "leaf_kat.npz")
+    np.savez_compressed(path, **d)
+    print("leaf_kat.npz", os.path.getsize(path) // 1024, "KiB")
+    assert os.path.getsize(path) < (1 << 20)
+
+
 def make_jpeg():
     """Small synthetic JPEGs (encoded here with Pillow: our own inputs) and what the reference's stbi_load(path, ..., 3)
     (Object.cpp:57) decodes them to: baseline / progressive, 4:4:4 / 4:2:2 / 4:2:0 / grey / CMYK, restart intervals,
@@ -458,9 +482,10 @@ def make_k4(meshes=None):
 
 def main():
     assert po.ref_available(), "build oracle/_ref first: make -C oracle ref"
-    if len(sys.argv) > 1 and sys.argv[1] in ("jpeg", "polygons", "k4"):
-        {"jpeg": make_jpeg, "polygons": make_polygons, "k4": make_k4}[sys.argv[1]]()
+    if len(sys.argv) > 1 and sys.argv[1] in ("jpeg", "polygons", "k4", "leaf_kat"):
+        {"jpeg": make_jpeg, "polygons": make_polygons, "k4": make_k4, "leaf_kat": make_leaf_kat}[sys.argv[1]]()
         return
+    make_leaf_kat()
     make_jpeg()
     make_polygons()
     meshes = {k: export_mesh(k) for k in REF_OBJ}

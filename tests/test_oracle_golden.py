@@ -265,3 +265,147 @@ def test_device_pow_mode_changes_colours_only_through_pow(oracle, name):
     tone, q = oracle.tonemap(b["rgb_linear"], p.reinhard, p.gamma, pow="device")
     assert np.array_equal(bits(tone.reshape(b["rgb_tone"].shape)), bits(b["rgb_tone"]))
     assert np.array_equal(bits(oracle.tonemap(a["rgb_linear"], p.reinhard, p.gamma)[0].reshape(a["rgb_tone"].shape)), bits(a["rgb_tone"]))
+
+
+# ---- the leaf functions beyond scene-scale inputs (tests/leaf_vectors.py) ------------------------------------------------------------
+import os
+
+import leaf_vectors as lv
+
+
+def same(a, b):
+    """the same bits, or NaN on both sides"""
+    a = np.ascontiguousarray(a, np.float32); b = np.ascontiguousarray(b, np.float32)
+    return (a.view(np.uint32) == b.view(np.uint32)) | (np.isnan(a) & np.isnan(b))
+
+
+@pytest.fixture(scope="module")
+def leaf():
+    return {"box": lv.box_families(), "tri": lv.tri_families(), "kat": np.load(os.path.join(gu.GOLDEN, "leaf_kat.npz"))}
+
+
+def test_leaf_families_are_real_tests(oracle, leaf):
+    """Every family holds at least 5 % passes and 5 % misses by the oracle, or is named "always pass" / "always miss" in the generator
+    and is.  (A triangle family's "miss": no positive distance, see leaf_vectors._tri_always.)  Every scale and every family of the
+    issue is there; arrays are finite unless the family says otherwise."""
+    names = {f.name for f in leaf["box"]} | {f.name for f in leaf["tri"]}
+    for base in ("primary", "shadow", "camera", "corner", "zero_dir", "hole1_x", "flat", "behind", "kat_rt", "kat_rt2", "w_pos", "w_neg",
+                 "degenerate", "origin_on"):
+        for e in lv.SCALES:
+            assert f"{base}@2^{e}" in names, (base, e)
+    for one in ("empty@2^0", "special_dir@2^0", "inf_box@2^0", "dir_sweep@2^0", "w_extreme@2^0"):
+        assert one in names
+    for f in leaf["box"]:
+        assert f.nonfinite or f.tags["empty"] or (np.isfinite(f.ray).all() and np.isfinite(f.box).all()), f.name
+        h = oracle.ray_aabb(f.ray, f.box).astype(bool)
+        if f.always:
+            assert f.always.startswith("pass:") and h.all(), (f.name, f.always, float(h.mean()))
+        else:
+            assert 0.05 <= h.mean() <= 0.95, (f.name, float(h.mean()))
+    for f in leaf["tri"]:
+        assert np.isfinite(f.ray).all() and np.isfinite(f.tri).all(), f.name
+        t = oracle.ray_triangle(f.ray, f.tri)
+        if f.always:
+            assert f.always.startswith("miss:") and not (t > 0).any(), (f.name, f.always, int((t > 0).sum()))
+        else:
+            assert 0.05 <= (t >= 0).mean() <= 0.95, (f.name, float((t >= 0).mean()))
+    # the special inputs are where they are meant to be
+    d = {f.name: f for f in leaf["box"]}
+    sp = d["special_dir@2^0"].ray[:, 3:]
+    assert np.isnan(sp).any() and np.isinf(sp).any() and ((sp != 0) & (np.abs(sp) < 2.0 ** -126)).any()
+    assert np.isinf(d["inf_box@2^0"].box).any()
+    sw = np.abs(d["dir_sweep@2^0"].ray[:, 3:])
+    assert ((sw > 0) & (sw < 2.0 ** -126)).any() and (sw > 2.0 ** 126).any() and np.isfinite(sw).all()
+    z = d["zero_dir@2^0"]
+    zero = z.ray[:, 3:] == 0
+    both = zero & (z.box[:, :3] == z.ray[:, :3]) & (z.box[:, 3:] == z.ray[:, :3])
+    assert np.signbit(z.ray[:, 3:][zero]).any() and (~np.signbit(z.ray[:, 3:][zero])).any()
+    assert both[:, 0].any() and both[:, 1].any() and both[:, 2].any() and (zero.sum(1) == 3).any() and (z.ray[:, :3] != 0).any()
+    for base in ("shadow", "camera", "corner"):
+        assert (d[f"{base}@2^0"].ray[:, :3] != 0).any(), base
+
+
+def test_leaf_hole1_family_has_boxes_the_other_axes_would_reject(oracle, leaf):
+    """d.x = 0 and a box flat on x at the origin's x: the oracle passes every such box (NaN against everything is false), also where
+    the y and z intervals alone -- what a min / max that drops NaN is left with -- are disjoint.  Those rows are the ones a filter
+    that does not notice the NaN pair decides wrongly."""
+    for f in leaf["box"]:
+        if not f.name.startswith("hole1_x"):
+            continue
+        o, d = f.ray[:, :3].astype(np.float64), f.ray[:, 3:].astype(np.float64)
+        assert np.all(d[:, 0] == 0) and np.all(f.box[:, 0] == f.ray[:, 0]) and np.all(f.box[:, 3] == f.ray[:, 0])
+        with np.errstate(all="ignore"):
+            q0, q1 = (f.box[:, 1:3] - o[:, 1:]) / d[:, 1:], (f.box[:, 4:6] - o[:, 1:]) / d[:, 1:]
+        lo, hi = np.minimum(q0, q1), np.maximum(q0, q1)
+        disjoint = (lo.max(1) > hi.min(1) * (1 + 1e-9)) & np.isfinite(lo).all(1) & np.isfinite(hi).all(1)
+        assert disjoint.mean() > 0.2, (f.name, float(disjoint.mean()))
+        assert oracle.ray_aabb(f.ray, f.box)[disjoint].all(), f.name
+
+
+def test_leaf_ordinary_families_show_both_outcomes_under_emulation(oracle, leaf):
+    """The families the device test requires decided AND ambiguous rows of (primary-, shadow-, camera-like and corner rays at scales
+    2^-60 .. 2^60) have both when the filter is emulated in numpy with the reciprocal shifted by -1, 0 and +1 ulp, and the emulated
+    filter is sound on them -- the reasoning behind that requirement, checked where no device is."""
+    n = 0
+    for f in leaf["box"]:
+        if not f.ordinary:
+            continue
+        n += 1
+        h = oracle.ray_aabb(f.ray, f.box).astype(bool)
+        for ulp in (-1, 0, 1):
+            p, amb = lv.filter_emulated(f.ray, f.box, ulp=ulp)
+            assert amb.any() and (~amb).any(), (f.name, ulp)
+            assert np.array_equal(p[~amb], h[~amb]), (f.name, ulp)
+    assert n == 4 * len(lv.ORDINARY_SCALES)
+
+
+def test_leaf_origin_rows_hit(oracle, leaf):
+    """the rows of the origin-form test: all from the origin, with hits at finite t among them"""
+    dirs, tris, _ = lv.origin0_rows(leaf["tri"])
+    ray = np.zeros((dirs.shape[0], 6), np.float32); ray[:, 3:] = dirs
+    t = oracle.ray_triangle(ray, tris)
+    assert (np.isfinite(t) & (t > 0)).sum() > 2000 and (t == -np.inf).sum() > 2000 and np.isnan(t).any()
+
+
+def _sub(fams):
+    return [lv.Family(f.name, "tri", f.ray[lv.subsample(f.ray.shape[0])], tri=f.tri[lv.subsample(f.ray.shape[0])]) for f in fams]
+
+
+def test_leaf_oracle_matches_recorded_reference(oracle, leaf):
+    """Without the live reference: the oracle on the subsample of every family that tests/golden/leaf_kat.npz records from the compiled
+    reference (make_golden.make_leaf_kat), bit for bit.  The inputs are recorded too: the generators must still draw them."""
+    k = leaf["kat"]
+    ray, box, names, rows = lv.recorded_rows(leaf["box"])
+    assert np.array_equal(names, k["box_family"]) and np.array_equal(rows, k["box_row"])
+    assert same(ray, k["box_ray"]).all() and same(box, k["box_box"]).all(), "the generators no longer draw the recorded inputs"
+    want = np.unpackbits(k["box_hit_bits"])[: ray.shape[0]]
+    got = oracle.ray_aabb(k["box_ray"], k["box_box"])
+    assert np.array_equal(got, want), [str(x) for x in np.unique(names[got != want])]
+    ray, tri, names, rows = lv.recorded_rows(leaf["tri"])
+    assert np.array_equal(names, k["tri_family"]) and np.array_equal(rows, k["tri_row"])
+    assert same(ray, k["tri_ray"]).all() and same(tri, k["tri_tri"]).all(), "the generators no longer draw the recorded inputs"
+    bad = ~same(oracle.ray_triangle(k["tri_ray"], k["tri_tri"]), k["tri_t"])
+    assert not bad.any(), [str(x) for x in np.unique(names[bad])]
+    sub = _sub(leaf["tri"])
+    assert same(oracle.barycentric(lv.bary_inputs(sub)), k["bc_uvw"]).all()
+    assert same(oracle.interp_normal(lv.interp_inputs(sub)), k["in_out"]).all()
+    assert os.path.getsize(os.path.join(gu.GOLDEN, "leaf_kat.npz")) < (1 << 20)
+
+
+def test_leaf_oracle_matches_live_reference_on_every_family(oracle, leaf):
+    """Where the compiled reference is present: ray_aabb, ray_triangle, barycentric and interp_normal of the oracle against the
+    reference's own functions on EVERY row of every family, bit for bit (NaN equals NaN) -- the pin of the oracle over the range the
+    device tests rely on."""
+    if not oracle.ref_available():
+        pytest.skip("oracle/_ref not built (no reference sources here)")
+    for f in leaf["box"]:
+        assert np.array_equal(oracle.ray_aabb(f.ray, f.box), oracle.ref_kat_ray_aabb(f.ray, f.box)[0]), f.name
+    for f in leaf["tri"]:
+        assert same(oracle.ray_triangle(f.ray, f.tri), oracle.ref_kat_ray_triangle(f.ray, f.tri)).all(), f.name
+        b = lv.bary_inputs([f])
+        assert same(oracle.barycentric(b), oracle.ref_kat_barycentric(b)).all(), f.name
+        q = lv.interp_inputs([f])
+        assert same(oracle.interp_normal(q), oracle.ref_kat_interp_normal(q)).all(), f.name
+    pts, _ = lv.record_points()
+    b = np.concatenate([pts.reshape(-1, 12), pts[:, 0, :3] + np.float32(1.0)], 1)
+    assert same(oracle.barycentric(b), oracle.ref_kat_barycentric(b)).all()
