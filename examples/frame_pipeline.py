@@ -3,7 +3,7 @@
 
 The reference rebuilds everything per frame (simple_raytracer.cpp:534-618 -- load, transform into view space,
 createBoundingHierarchy, render, draw), so with the HIP path the host stages ARE the frame.  K3 scene (bunny + ground slab,
-1920x1080), a small orbit, four ways through the host mirror and the C ABI:
+1920x1080), a small orbit, five ways through the host mirror and the C ABI:
 
   stages     every stage timed on its own, a device scene created and destroyed per frame (what round 1 shipped)
   renderer   srt_host::Renderer: one device scene for the whole orbit -- srt_scene_update into the existing allocations through
@@ -12,6 +12,9 @@ createBoundingHierarchy, render, draw), so with the HIP path the host stages ARE
              flattened, uploaded, rendered and collected (EXACT: every frame is the reference's frame)
   camera     camera mode (EXTENSION, srt_params.ray_matrix): the scene stays in world space, hierarchies are built once, each frame
              passes the viewMatrix -- different rounding, pinned by the oracle run in the same mode
+  pose       pose mode (EXTENSION, srt_scene_pose): the scene is created once from frame 0's view-space geometry and frame k is
+             rendered after pose(M_k), M_k = inverse(view_k) * view_0 -- the tree keeps its shape, the device moves the points and
+             refits the boxes; pinned by the oracle on the same flat scene (include/srt.h, POSE)
 
     python examples/frame_pipeline.py [--frames 12] [--width 1920] [--height 1080]
 
@@ -164,16 +167,39 @@ def main():
     host.set_build_tasks(True)
 
     # ---- 4. camera mode: world-space scene, hierarchies built once, one matrix per frame ---------------------------------------
+    # The orbit of modes 4 and 5: the camera turns half a degree per frame about its own position, view_k = the viewMatrix of frame k.
+    # The K3 placement is frame 0's VIEW-SPACE geometry, so the world-space scene is view_0 * placement and the light's world position
+    # view_0 * LIGHT; both modes then render the same pictures (up to their own rounding).
+    views = [scenes.orbit_view_matrix(T, 0.0, 0.5 * f, 0.0, 0.0) for f in range(N + 1)]
+    light_w = T.mul_vec4(views[0], LIGHT)
     om = build_frame(0, bunny, cube)
+    for name in ("bunny", "cube"):
+        om.transformTriangles(name, views[0]); om.createBoundingHierarchy(name)
     rc_ = host.Renderer(0)
-    view = np.eye(4, dtype=np.float32).reshape(16)          # the K3 bench placement has the identity view
-    rc_.render_from_camera(om, W, H, LIGHT, view, scene_changed=True, image=False)
+    rc_.render_from_camera(om, W, H, light_w, views[0], scene_changed=True, image=False)
     t0 = time.perf_counter()
-    for f in range(N):
-        view = scenes.orbit_view_matrix(T, 0.0, 0.5 * f, 0.0, 0.0)            # the camera turns half a degree per frame
-        n = rc_.render_from_camera(om, W, H, LIGHT, view, image=False)
+    for f in range(1, N + 1):
+        n = rc_.render_from_camera(om, W, H, light_w, views[f], image=False)
     wall_c = (time.perf_counter() - t0) * 1e3 / N
     print(f" 4. camera mode (EXTENSION: scene uploaded once, viewMatrix per frame; result incl. ImageData): {wall_c:.3f} ms per frame")
+
+    # ---- 5. pose mode: the scene created once from frame 0's view-space geometry, one matrix per object per frame, refit on the device
+    om0 = build_frame(0, bunny, cube)
+    n_obj = len(om0.flatten().names)
+    rp = host.Renderer(0)
+    eye = np.tile(np.eye(4, dtype=np.float32).reshape(16), (n_obj, 1))
+    rp.render_posed(om0, W, H, LIGHT, eye, scene_changed=True, image=False)
+    per_pose = []
+    t0 = time.perf_counter()
+    for f in range(1, N + 1):
+        a0 = time.perf_counter()
+        inv = T.inverse(views[f])
+        m = T.mul(inv, views[0])                                              # M_k = inverse(view_k) * view_0, the same for every object here
+        n = rp.render_posed(om0, W, H, T.mul_vec4(inv, light_w), np.tile(m, (n_obj, 1)), image=False)
+        per_pose.append((time.perf_counter() - a0) * 1e3)
+    wall_p = (time.perf_counter() - t0) * 1e3 / N
+    print(f" 5. pose mode (EXTENSION: scene uploaded once, one matrix per object per frame, points / records / boxes on the device; one host "
+          f"thread; result incl. ImageData): {wall_p:.3f} ms per frame (median {np.median(per_pose):.3f})")
 
 
 if __name__ == "__main__":

@@ -226,6 +226,39 @@ int srt_scene_set_source(srt_scene* s, const float* tri_texcoord, const float* t
  * behind the renders already enqueued there; the arrays are only read during the call. */
 int srt_scene_update_frame(srt_scene* s, const srt_frame_geometry* g, void* stream);
 
+/* ---- POSE, an opt-in EXTENSION (like camera mode and spp): move objects by matrix, the hierarchy REFITTED on the device -------------
+ * What a frame costs the host on the exact path above is the reference's rebuild (sort, boxes) plus 52 bytes a triangle over PCIe.  When
+ * the objects only MOVE -- rigidly or by any 4x4 matrix -- the tree can keep its shape and the triangles their order: the points are
+ * transformed, the triangle records derived and every node box recomputed on the device, from one matrix per object (64 bytes an object
+ * per frame, no host work proportional to triangles or nodes).  Unlike camera mode it moves objects against each other and against the
+ * light, stays in the reference's frame (rays from the origin: every shipped pipeline applies), and needs no rebuild on the host.
+ * PARITY: the tree is the one built at the pose the scene was created (or last updated) from, not the one the reference would build at
+ * the new pose.  Triangle ids keep the numbering of that scene, and equal-t ties and grazing box culls may resolve differently from the
+ * reference's frame at that pose.  What is pinned, bit for bit, is: the oracle rendering the SAME flat scene -- same order, same tree
+ * shape, moved points, refitted boxes -- gives the same hit ids, t bits and colours.  The arithmetic (all without contraction):
+ *   point    per component i, glm's mat4 * vec4: (m[0][i]*x + m[1][i]*y) + (m[2][i]*z + m[3][i]*w), all four components;
+ *   records  as srt_scene_create derives them, from the moved points;
+ *   box      per component from (+FLT_MAX, -FLT_MAX), over the node's triangles in visit order, points one, two, three, raw xyz:
+ *            if (v < mn) mn = v; if (mx < v) mx = v;  (a leaf without triangles keeps the start values; a NaN never enters a box);
+ *   the union of the root boxes as srt_scene_create computes it.
+ * Pipeline choice: srt_scene_overlap_estimate and the packet / node-queue decision keep the value last computed on the host (create,
+ * update, update_frame); results never depend on that choice.
+ *
+ * srt_scene_set_pose_source: the points the poses are applied to, n_tris x 3 x 4 floats in the scene's CURRENT visit order (the layout
+ * of srt_scene_desc.tri_points).  Copied to the device once (48 B a triangle); waits for the device.  They belong to the device records,
+ * so every handle of srt_scene_share sees them.  A later srt_scene_update or srt_scene_update_frame changes the visit order and discards
+ * them: set them again before the next srt_scene_pose.  NULL handle or points: SRT_ERR_ARG. */
+int srt_scene_set_pose_source(srt_scene* s, const float* tri_points);
+
+/* The next frame from one matrix per object: obj_matrix = n_objects x 16 floats, column-major like glm::mat4; every point of object k
+ * becomes obj_matrix[k] * (its pose-source point) -- poses do not accumulate.  obj_color / obj_material: n_objects x 3 or NULL
+ * (unchanged), as in srt_frame_geometry.  Asynchronous on `stream` (NULL = the scene's own stream), ordered behind the renders already
+ * enqueued there; the arrays are only read during the call.  Through a shared handle it rewrites the records all handles read, under
+ * the ordering rule of srt_scene_update (see srt_scene_share).  Errors, all before anything is touched: NULL handle or obj_matrix, or no
+ * valid pose source: SRT_ERR_ARG; n_objects other than the scene's: SRT_ERR_LAYOUT. */
+int srt_scene_pose(srt_scene* s, uint32_t n_objects, const float* obj_matrix,
+                   const float* obj_color, const float* obj_material, void* stream);
+
 /* Render into DEVICE buffers (rows = srt_rows_owned(p)); any output pointer may be NULL.
  *   d_hit_id     rows x W   int32   canonical triangle id, -1 = miss
  *   d_t          rows x W   f32     closest-hit distance (+inf on miss)

@@ -1158,6 +1158,7 @@ bool Renderer::upload_frame(ObjectManager* om) {
 // the ObjectManager's current state into the device scene: the device half of the rebuild when the resident scene is this one with
 // other positions (upload_frame), else flattened -- in place when the counts allow it, else a new scene
 void Renderer::upload(ObjectManager* objManager) {
+    pose_source_ = false;
     if (upload_frame(objManager)) return;
     FlatScene flat = flattenScene(objManager);
     srt_scene_desc d = flat.desc();
@@ -1243,6 +1244,26 @@ ImageData Renderer::renderFromCamera(const vec2& imageSize, const vec4& lightPos
     if (pending_) throw std::runtime_error("Renderer::renderFromCamera: collect() the previous frame first");
     if (!scene_ || sceneChanged) upload(objManager);
     enqueue(imageSize, lightPosWorld, lightAmount, &viewMatrix);
+    return collect();
+}
+
+// POSE: the resident scene moved by one matrix per object (srt_scene_pose); nothing proportional to triangles happens on the host
+// unless the scene has to be uploaded.
+ImageData Renderer::renderPosed(const vec2& imageSize, const vec4& lightPos, const std::vector<mat4>& objMatrices, ObjectManager* objManager,
+                                int lightAmount, bool sceneChanged) {
+    if (pending_) throw std::runtime_error("Renderer::renderPosed: collect() the previous frame first");
+    if (!scene_ || sceneChanged || !pose_source_) {
+        upload(objManager);
+        const FlatScene flat = flattenScene(objManager);       // the resident scene's visit order: the points the poses apply to
+        const int rc = srt_scene_set_pose_source(scene_, flat.tri_points.data());
+        if (rc != SRT_OK) throw std::runtime_error(std::string("srt_scene_set_pose_source: ") + srt_strerror(rc));
+        pose_source_ = true;
+    }
+    std::vector<float> m16(16 * objMatrices.size());
+    for (size_t k = 0; k < objMatrices.size(); k++) for (int c = 0; c < 4; c++) for (int r = 0; r < 4; r++) m16[16 * k + 4 * c + r] = objMatrices[k][c][r];
+    const int rc = srt_scene_pose(scene_, (uint32_t)objMatrices.size(), m16.data(), nullptr, nullptr, nullptr);
+    if (rc != SRT_OK) throw std::runtime_error(std::string("srt_scene_pose: ") + srt_strerror(rc));
+    enqueue(imageSize, lightPos, lightAmount, nullptr);
     return collect();
 }
 

@@ -163,7 +163,11 @@ ImageData sendRaysAndIntersectPointsColors(const vec2& imageSize, const vec4& li
 //                         overlaps with the GPU;
 //   renderFromCamera()  = CAMERA MODE (an extension, include/srt.h srt_params.ray_matrix): the scene stays in world space and is
 //                         uploaded only when `sceneChanged`; each frame passes the viewMatrix whose inverse the reference would
-//                         have applied to every triangle, and the light's WORLD position.
+//                         have applied to every triangle, and the light's WORLD position;
+//   renderPosed()       = POSE (an extension, include/srt.h srt_scene_pose): the scene is uploaded only when `sceneChanged` (or first),
+//                         its hierarchies are kept, and each frame hands over one mat4 per object -- in the scene's object order,
+//                         objTriangles iteration order -- that is applied to the points the scene was uploaded with; triangle
+//                         records and boxes follow on the device.  Never taken implicitly: render() / submit() keep rebuilding.
 class Renderer {
 public:
     explicit Renderer(int device = 0);
@@ -175,6 +179,8 @@ public:
     ImageData collect();
     ImageData renderFromCamera(const vec2& imageSize, const vec4& lightPosWorld, const mat4& viewMatrix, ObjectManager* objManager,
                                int lightAmount = 1, bool sceneChanged = false);
+    ImageData renderPosed(const vec2& imageSize, const vec4& lightPos, const std::vector<mat4>& objMatrices, ObjectManager* objManager,
+                          int lightAmount = 1, bool sceneChanged = false);
     // upload() takes the device half of the per-frame rebuild (srt_scene_update_frame: 52 bytes a triangle, records derived on the
     // device) whenever the ObjectManager has the objects (names, order, triangle and node counts), textures and a sample of the
     // per-triangle attributes of the scene that is resident; anything else goes through flattenScene + srt_scene_update / create.
@@ -189,6 +195,7 @@ private:
     srt_scene* scene_ = nullptr;
     std::vector<std::string> sig_names_; std::vector<uint32_t> sig_tris_, sig_nodes_; uint64_t sig_attr_ = 0;      // what is resident
     bool fast_path_ = true; uint64_t fast_frames_ = 0;
+    bool pose_source_ = false;       // the resident scene has its pose source (any upload discards it)
     uint8_t* rgb8_ = nullptr; size_t rgb8_bytes_ = 0;      // pinned
     uint32_t W_ = 0, H_ = 0;
     bool pending_ = false;

@@ -221,6 +221,18 @@ int64_t srth_renderer_render_from_camera(void* r, void* om, uint32_t W, uint32_t
     } catch (const std::exception& e) { g_err = e.what(); return -1; }
 }
 
+// pose: mats = n_mats x 16 floats, column-major, one per object in the scene's object order
+int64_t srth_renderer_render_posed(void* r, void* om, uint32_t W, uint32_t H, const float* light4, const float* mats, uint32_t n_mats, int light_amount,
+                                   int scene_changed, float* rgb) {
+    try {
+        std::vector<mat4> ms(n_mats);
+        for (uint32_t k = 0; k < n_mats; k++) ms[k] = to_mat(mats + 16 * (size_t)k);
+        ImageData d = ((Renderer*)r)->renderPosed(vec2((float)W, (float)H), vec4(light4[0], light4[1], light4[2], light4[3]), ms, (ObjectManager*)om,
+                                                 light_amount, scene_changed != 0);
+        return rgb ? image_to_dense(d, W, H, rgb) : (int64_t)d.imagePoints.size();
+    } catch (const std::exception& e) { g_err = e.what(); return -1; }
+}
+
 // MultiRenderer: several devices, one process (the framebuffer split on the C++ host)
 void* srth_multi_new(const int* devices, uint32_t n, uint32_t block_rows) {
     try { return new MultiRenderer(std::vector<int>(devices, devices + n), block_rows); } catch (const std::exception& e) { g_err = e.what(); return nullptr; }

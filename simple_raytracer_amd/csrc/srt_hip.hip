@@ -71,6 +71,10 @@ struct SceneRecords {
     // f1, device half: node -> DevWide index (static), this frame's inputs, the per-triangle attributes in source order
     int32_t* d_widx = nullptr; float4* d_src_points = nullptr; uint32_t* d_order = nullptr; float* d_box_min = nullptr; float* d_box_max = nullptr;
     float* d_src_tc = nullptr; float* d_src_nrm = nullptr; int32_t* d_src_tex = nullptr; bool have_source = false;
+    // pose (srt_scene_pose): the points the poses are applied to (visit order), each triangle's own box, this frame's matrices, and the
+    // static schedule of the refit -- node heights, the roots of the bottom subtrees, per object the nodes above them sorted by height
+    float4* d_pose_points = nullptr; float2* d_tri_box = nullptr; float* d_obj_matrix = nullptr; uint8_t* d_height = nullptr;
+    int32_t* d_sub_root = nullptr; int32_t* d_top_nodes = nullptr; int32_t* d_top_off = nullptr; uint32_t n_sub = 0; bool have_pose = false;
     ~SceneRecords() { (void)hipSetDevice(device); for (void* d : allocs) (void)hipFree(d); }
 };
 
@@ -643,6 +647,7 @@ static int scene_update_impl(srt_scene* s, const srt_scene_desc* d, hipStream_t 
         for (uint32_t i = 0; i < d->n_nodes; i++) r.h_leaf[i] = nodes[i].leaf;
         HIP_TRY(hipMemcpyAsync(r.d_widx, h + o_widx, nN * 4, hipMemcpyHostToDevice, stream));
         r.have_source = false;                                  // attributes in source order belong to the previous contents
+        r.have_pose = false;                                    // ... and so do the pose source's order and the refit's schedule
     }
     return SRT_OK;
 }
@@ -690,7 +695,7 @@ static int scene_update_frame_impl(srt_scene* s, const srt_frame_geometry* g, hi
     HIP_TRY(hipSetDevice(s->device));
     const size_t nN = s->dev.n_nodes, nT = s->dev.n_tris;
     if (!r.d_src_points) {        // the device side of the staging, once
-        auto make = [&](auto** dst, size_t bytes) -> int { void* d = nullptr; HIP_TRY(hipMalloc(&d, bytes ? bytes : 1)); r.allocs.push_back(d); *dst = (std::remove_pointer_t<decltype(dst)>)d; s->bytes += bytes; return SRT_OK; };
+        auto make = [&](auto** dst, size_t bytes) -> int { if (*dst) return SRT_OK; void* d = nullptr; HIP_TRY(hipMalloc(&d, bytes ? bytes : 1)); r.allocs.push_back(d); *dst = (std::remove_pointer_t<decltype(dst)>)d; s->bytes += bytes; return SRT_OK; };
         rc = make(&r.d_src_points, nT * 48); if (rc == SRT_OK) rc = make(&r.d_order, nT * 4);
         if (rc == SRT_OK) rc = make(&r.d_box_min, nN * 12); if (rc == SRT_OK) rc = make(&r.d_box_max, nN * 12);
         if (rc != SRT_OK) return rc;
@@ -745,6 +750,7 @@ static int scene_update_frame_impl(srt_scene* s, const srt_frame_geometry* g, hi
     hipLaunchKernelGGL(k_update_roots, dim3((nO + 63) / 64), dim3(64), 0, stream, nO, s->dev.obj_range, (const float*)r.d_box_min, (const float*)r.d_box_max,
                        s->dev.nodes, const_cast<DevNode*>(s->dev.root_nodes));
     HIP_TRY(hipGetLastError());
+    r.have_pose = false;                                        // another visit order: the pose source is no longer these triangles
     // expected slab tests per ray from this frame's boxes (what overlap_estimate computes from the records)
     {
         const float* bmin = (const float*)(h + o_bmin); const float* bmax = (const float*)(h + o_bmax);
@@ -765,6 +771,114 @@ static int scene_update_frame_impl(srt_scene* s, const srt_frame_geometry* g, hi
         r.prefer_packet = r.overlap > PACKET_OVERLAP_THRESHOLD;
     }
     return SRT_OK;
+}
+
+// ---- pose: one matrix per object, the hierarchy refitted on the device (srt_kernels.h, "Pose") -----------------------------------
+// Everything proportional to triangles or nodes happens HERE, once: the points go to the device and the refit's static schedule is
+// derived from the tree's shape.  Synchronous (a set-up call): waits for the device, so that no earlier pose still reads what it replaces.
+static int scene_set_pose_source_impl(srt_scene* s, const float* tri_points) {
+    if (!s || !tri_points) return SRT_ERR_ARG;
+    SceneRecords& r = *s->rec;
+    const size_t nN = s->dev.n_nodes, nT = s->dev.n_tris, nO = s->dev.n_objects;
+    // height of every node (children follow their parent in pre-order); bottom subtrees = maximal subtrees of height <= POSE_SUB_HEIGHT
+    alloc_gate();
+    std::vector<uint8_t> height(nN, 0);
+    std::vector<int32_t> parent(nN, -1), sub_root, top_nodes, top_off(nO + 1, 0);
+    for (size_t i = nN; i-- > 0;) {
+        if (r.h_leaf[i] >= 0) continue;
+        const size_t l = i + 1, rr = (size_t)(~r.h_leaf[i]);
+        if (l >= nN || rr >= nN || rr <= l) return SRT_ERR_LAYOUT;                 // (build_device_records has made this impossible)
+        const int h = 1 + std::max((int)height[l], (int)height[rr]);
+        if (h > 255) return SRT_ERR_LIMIT;
+        height[i] = (uint8_t)h; parent[l] = (int32_t)i; parent[rr] = (int32_t)i;
+    }
+    for (size_t k = 0; k < nO; k++) {
+        top_off[k] = (int32_t)top_nodes.size();
+        for (int32_t i = r.h_ranges[k].x; i < r.h_ranges[k].y; i++) {
+            if (height[i] > POSE_SUB_HEIGHT) top_nodes.push_back(i);
+            else if (parent[i] < 0 || height[parent[i]] > POSE_SUB_HEIGHT) sub_root.push_back(i);
+        }
+        std::stable_sort(top_nodes.begin() + top_off[k], top_nodes.end(), [&](int32_t a, int32_t b) { return height[a] < height[b]; });
+    }
+    top_off[nO] = (int32_t)top_nodes.size();
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipDeviceSynchronize());
+    auto put = [&](auto** dst, const void* src, size_t cap_bytes, size_t bytes) -> int {
+        if (!*dst) { void* d = nullptr; HIP_TRY(hipMalloc(&d, cap_bytes ? cap_bytes : 1)); r.allocs.push_back(d); *dst = (std::remove_pointer_t<decltype(dst)>)d; s->bytes += cap_bytes; }
+        if (src && bytes) HIP_TRY(hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
+        return SRT_OK;
+    };
+    int rc = put(&r.d_pose_points, tri_points, nT * 48, nT * 48);
+    if (rc == SRT_OK) rc = put(&r.d_tri_box, nullptr, nT * 24, 0);
+    if (rc == SRT_OK) rc = put(&r.d_obj_matrix, nullptr, nO * 64, 0);
+    if (rc == SRT_OK) rc = put(&r.d_height, height.data(), nN, nN);
+    if (rc == SRT_OK) rc = put(&r.d_sub_root, sub_root.data(), nN * 4, sub_root.size() * 4);      // (capacities for any tree of these counts)
+    if (rc == SRT_OK) rc = put(&r.d_top_nodes, top_nodes.data(), nN * 4, top_nodes.size() * 4);
+    if (rc == SRT_OK) rc = put(&r.d_top_off, top_off.data(), (nO + 1) * 4, (nO + 1) * 4);
+    if (rc == SRT_OK) rc = put(&r.d_box_min, nullptr, nN * 12, 0);
+    if (rc == SRT_OK) rc = put(&r.d_box_max, nullptr, nN * 12, 0);
+    if (rc != SRT_OK) return rc;
+    r.n_sub = (uint32_t)sub_root.size();
+    r.have_pose = true;
+    return SRT_OK;
+}
+
+int srt_scene_set_pose_source(srt_scene* s, const float* tri_points) {
+    return guarded([&] { return scene_set_pose_source_impl(s, tri_points); });
+}
+
+// Per frame the host copies 64 bytes an object (+ 24 for colours and materials) into the staging block and enqueues six launches; it
+// neither looks at a triangle or a node nor waits for the device (but for the staging block's previous use, as srt_scene_update_frame).
+static int scene_pose_impl(srt_scene* s, uint32_t n_objects, const float* obj_matrix, const float* obj_color, const float* obj_material, hipStream_t stream) {
+    if (!s || !obj_matrix) return SRT_ERR_ARG;
+    SceneRecords& r = *s->rec;
+    if (!r.have_pose) return SRT_ERR_ARG;
+    const uint32_t nO = s->dev.n_objects;
+    if (n_objects != nO) return SRT_ERR_LAYOUT;
+    int rc;
+    if (!stream) { rc = own_stream(s, &stream); if (rc != SRT_OK) return rc; }
+    HIP_TRY(hipSetDevice(s->device));
+    const size_t nN = s->dev.n_nodes, nT = s->dev.n_tris;
+    auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t o_mtx = 0, o_col = o_mtx + pad((size_t)nO * 64), o_mat = o_col + pad((size_t)nO * 12), total = o_mat + pad((size_t)nO * 12);
+    if (s->stage_bytes < total) {
+        if (s->stage) { HIP_TRY(hipEventSynchronize(s->staged)); (void)hipHostFree(s->stage); s->stage = nullptr; s->stage_bytes = 0; }
+        HIP_TRY(hipHostMalloc(&s->stage, total, hipHostMallocDefault));
+        s->stage_bytes = total;
+        if (!s->staged) HIP_TRY(hipEventCreateWithFlags(&s->staged, hipEventDisableTiming));
+    } else {
+        HIP_TRY(hipEventSynchronize(s->staged));               // the previous copies have left the staging block
+    }
+    char* h = (char*)s->stage;
+    // every copy out of the staging block is enqueued before the event that guards the block is recorded
+    std::memcpy(h + o_mtx, obj_matrix, (size_t)nO * 64);
+    HIP_TRY(hipMemcpyAsync(r.d_obj_matrix, h + o_mtx, (size_t)nO * 64, hipMemcpyHostToDevice, stream));
+    if (obj_color) { std::memcpy(h + o_col, obj_color, (size_t)nO * 12); HIP_TRY(hipMemcpyAsync((void*)s->dev.obj_color, h + o_col, (size_t)nO * 12, hipMemcpyHostToDevice, stream)); }
+    if (obj_material) { std::memcpy(h + o_mat, obj_material, (size_t)nO * 12); HIP_TRY(hipMemcpyAsync((void*)s->dev.obj_mat, h + o_mat, (size_t)nO * 12, hipMemcpyHostToDevice, stream)); }
+    HIP_TRY(hipEventRecord(s->staged, stream));
+    if (obj_material) {
+        bool ish = true;
+        for (uint32_t k = 0; k < nO; k++) { const float sh = obj_material[3 * (size_t)k + 2]; ish = ish && sh >= 1.0f && sh <= 64.0f && sh == std::trunc(sh); }
+        r.int_shin = ish;
+    }
+    if (nT) hipLaunchKernelGGL(k_pose_tris, dim3((uint32_t)((nT + 255) / 256)), dim3(256), 0, stream, (uint32_t)nT, s->dev.tri_obj, (const float*)r.d_obj_matrix,
+                               (const float4*)r.d_pose_points, const_cast<DevTri*>(s->dev.tris), const_cast<DevTriO*>(s->dev.tris_o), r.d_tri_box);
+    hipLaunchKernelGGL(k_pose_boxes, dim3(r.n_sub), dim3(128), 0, stream, (const int32_t*)r.d_sub_root, s->dev.nodes, (const uint8_t*)r.d_height,
+                       (const float2*)r.d_tri_box, r.d_box_min, r.d_box_max);
+    hipLaunchKernelGGL(k_pose_top, dim3(nO), dim3(256), 0, stream, (const int32_t*)r.d_top_off, (const int32_t*)r.d_top_nodes, s->dev.nodes,
+                       (const uint8_t*)r.d_height, r.d_box_min, r.d_box_max);
+    hipLaunchKernelGGL(k_update_nodes, dim3((uint32_t)((nN + 255) / 256)), dim3(256), 0, stream, (uint32_t)nN, (const float*)r.d_box_min, (const float*)r.d_box_max,
+                       const_cast<DevNode*>(s->dev.nodes), const_cast<DevWide*>(s->dev.wide), (const int32_t*)r.d_widx);
+    hipLaunchKernelGGL(k_update_roots, dim3((nO + 63) / 64), dim3(64), 0, stream, nO, s->dev.obj_range, (const float*)r.d_box_min, (const float*)r.d_box_max,
+                       s->dev.nodes, const_cast<DevNode*>(s->dev.root_nodes));
+    hipLaunchKernelGGL(k_pose_scene_box, dim3(1), dim3(256), 0, stream, nO, s->dev.obj_range, (const float*)r.d_box_min, (const float*)r.d_box_max,
+                       const_cast<float*>(s->dev.scene_box));
+    HIP_TRY(hipGetLastError());
+    return SRT_OK;
+}
+
+int srt_scene_pose(srt_scene* s, uint32_t n_objects, const float* obj_matrix, const float* obj_color, const float* obj_material, void* stream) {
+    return guarded([&] { return scene_pose_impl(s, n_objects, obj_matrix, obj_color, obj_material, (hipStream_t)stream); });
 }
 
 int srt_scene_update_frame(srt_scene* s, const srt_frame_geometry* g, void* stream) {

@@ -1878,6 +1878,149 @@ __global__ void k_update_roots(uint32_t n_objects, const int2* __restrict__ obj_
 }
 
 // =================================================================================================
+// Pose (srt_scene_pose, an extension): one matrix per object, the hierarchy REFITTED on the device -- tree shape and triangle order
+// stay, the points move, the boxes are recomputed.  Data goes from one stage to the next at kernel boundaries on the stream, or
+// inside ONE workgroup behind __syncthreads(); no workgroup ever waits for another inside a launch (the per-XCD L2s are not coherent).
+//   k_pose_tris       one lane per triangle: p' = M[object] * p, both triangle records, the triangle's own box (24 B)
+//   k_pose_boxes      one workgroup per bottom subtree (height <= POSE_SUB_HEIGHT): leaf boxes from the triangles' boxes, the climb in LDS
+//   k_pose_top        one workgroup per object: the few nodes above the bottom subtrees, height by height
+//   k_update_nodes / k_update_roots (above) put the boxes into the 32 B, 64 B and root records; k_pose_scene_box folds the root boxes.
+// A box is a chain of compares that keeps the LEFT operand on ties (fold: `if (v < mn) mn = v; if (mx < v) mx = v;`, Object.cpp:205-221;
+// combine(a, b): `b < a ? b : a`), which is associative: folding triangles into their own boxes first and combining those in visit
+// order, leaf by leaf and then child by child, gives the value of the reference's one fold over the node's triangles.  A NaN coordinate
+// never enters a box (both compares are false); a leaf without triangles keeps (+FLT_MAX, -FLT_MAX).
+// =================================================================================================
+constexpr int POSE_SUB_HEIGHT = 6;                                  // a bottom subtree has at most 2^6 leaves ...
+constexpr int POSE_SUB_NODES = (2 << POSE_SUB_HEIGHT) - 1;          // ... and 127 nodes, a contiguous run in pre-order
+
+// glm's mat4 * vec4 (type_mat4x4.inl:562-573) per component: (m0 * x + m1 * y) + (m2 * z + m3 * w); m = 16 floats, column-major
+__host__ __device__ inline float4 pose_point(const float* m, const float4 p) {
+    float4 r;
+    r.x = (m[0] * p.x + m[4] * p.y) + (m[8] * p.z + m[12] * p.w);
+    r.y = (m[1] * p.x + m[5] * p.y) + (m[9] * p.z + m[13] * p.w);
+    r.z = (m[2] * p.x + m[6] * p.y) + (m[10] * p.z + m[14] * p.w);
+    r.w = (m[3] * p.x + m[7] * p.y) + (m[11] * p.z + m[15] * p.w);
+    return r;
+}
+struct PoseBox { float mn[3], mx[3]; };
+__device__ __forceinline__ PoseBox pose_box_empty() { PoseBox b; for (int a = 0; a < 3; a++) { b.mn[a] = 3.402823466e+38f; b.mx[a] = -3.402823466e+38f; } return b; }
+__device__ __forceinline__ void pose_box_point(PoseBox& b, const float4 p) {      // raw xyz, no w-divide (Object.cpp:205-221)
+    const float v[3] = { p.x, p.y, p.z };
+    for (int a = 0; a < 3; a++) { if (v[a] < b.mn[a]) b.mn[a] = v[a]; if (b.mx[a] < v[a]) b.mx[a] = v[a]; }
+}
+__device__ __forceinline__ void pose_box_combine(PoseBox& l, const float* rmn, const float* rmx) {      // l = combine(l, r): l stays on ties
+    for (int a = 0; a < 3; a++) { if (rmn[a] < l.mn[a]) l.mn[a] = rmn[a]; if (l.mx[a] < rmx[a]) l.mx[a] = rmx[a]; }
+}
+
+__global__ __launch_bounds__(256) void k_pose_tris(uint32_t n_tris, const int32_t* __restrict__ tri_obj, const float* __restrict__ obj_matrix,
+                                                   const float4* __restrict__ src_points, DevTri* __restrict__ tris, DevTriO* __restrict__ tris_o,
+                                                   float2* __restrict__ tri_box) {
+    const uint32_t g = blockIdx.x * 256 + threadIdx.x;
+    if (g >= n_tris) return;
+    // triangles are in object order: all lanes of a wave belong to one object except where two objects meet, so the matrix comes
+    // through the scalar cache from a wave-uniform address; a wave that straddles objects gathers per lane
+    const int32_t ob = tri_obj[g], ob0 = __builtin_amdgcn_readfirstlane(ob);
+    float m[16];
+    if (__all(ob == ob0)) {
+        const float* M = obj_matrix + 16 * (size_t)ob0;
+#pragma unroll
+        for (int k = 0; k < 16; k++) m[k] = M[k];
+    } else {
+        const float4* M = (const float4*)(obj_matrix + 16 * (size_t)ob);
+#pragma unroll
+        for (int c = 0; c < 4; c++) { const float4 q = M[c]; m[4 * c] = q.x; m[4 * c + 1] = q.y; m[4 * c + 2] = q.z; m[4 * c + 3] = q.w; }
+    }
+    const float4 a = pose_point(m, src_points[3 * (size_t)g]), b = pose_point(m, src_points[3 * (size_t)g + 1]), c = pose_point(m, src_points[3 * (size_t)g + 2]);
+    const float p[12] = { a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w, c.x, c.y, c.z, c.w };
+    const DevTri t = derive_triangle(p);
+    tris[g] = t;
+    tris_o[g] = derive_triangle_origin(t);
+    PoseBox bx = pose_box_empty();
+    pose_box_point(bx, a); pose_box_point(bx, b); pose_box_point(bx, c);
+    tri_box[3 * (size_t)g] = make_float2(bx.mn[0], bx.mn[1]); tri_box[3 * (size_t)g + 1] = make_float2(bx.mn[2], bx.mx[0]);
+    tri_box[3 * (size_t)g + 2] = make_float2(bx.mx[1], bx.mx[2]);
+}
+
+// Workgroup b owns the bottom subtree rooted at node sub_root[b]: nodes [r, skip[r]), at most POSE_SUB_NODES of them.  `height`: 0 for
+// a leaf, 1 + max(children) for an inner node (static, derived on the host from the tree's shape).
+__global__ __launch_bounds__(128) void k_pose_boxes(const int32_t* __restrict__ sub_root, const DevNode* __restrict__ nodes, const uint8_t* __restrict__ height,
+                                                    const float2* __restrict__ tri_box, float* __restrict__ box_min, float* __restrict__ box_max) {
+    __shared__ float s_mn[POSE_SUB_NODES][3], s_mx[POSE_SUB_NODES][3];
+    const int32_t r = sub_root[blockIdx.x];
+    int32_t n = nodes[r].skip - r;
+    if (n > POSE_SUB_NODES) n = POSE_SUB_NODES;                      // (cannot happen for a height <= POSE_SUB_HEIGHT; keeps every LDS index in range)
+    const int32_t j = (int32_t)threadIdx.x;                          // 128 lanes >= 127 nodes: one node per lane
+    int32_t leaf = 0, h = 0;
+    if (j < n) {
+        leaf = nodes[r + j].leaf; h = height[r + j];
+        if (leaf >= 0) {
+            PoseBox bx = pose_box_empty();
+            const size_t first = (size_t)(leaf >> LEAF_SHIFT); const int32_t cnt = leaf & LEAF_MAX;
+            for (int32_t i = 0; i < cnt; i++) {
+                const float2 q0 = tri_box[3 * (first + i)], q1 = tri_box[3 * (first + i) + 1], q2 = tri_box[3 * (first + i) + 2];
+                const float mn[3] = { q0.x, q0.y, q1.x }, mx[3] = { q1.y, q2.x, q2.y };
+                pose_box_combine(bx, mn, mx);
+            }
+            for (int a = 0; a < 3; a++) { s_mn[j][a] = bx.mn[a]; s_mx[j][a] = bx.mx[a]; }
+        }
+    }
+    const int32_t H = height[r];
+    for (int32_t lv = 1; lv <= H && lv <= POSE_SUB_HEIGHT; lv++) {
+        __syncthreads();
+        if (j < n && leaf < 0 && h == lv) {
+            const int32_t l = j + 1, rr = ~leaf - r;
+            if (l < n && rr > l && rr < n) {
+                PoseBox bx; for (int a = 0; a < 3; a++) { bx.mn[a] = s_mn[l][a]; bx.mx[a] = s_mx[l][a]; }
+                pose_box_combine(bx, s_mn[rr], s_mx[rr]);
+                for (int a = 0; a < 3; a++) { s_mn[j][a] = bx.mn[a]; s_mx[j][a] = bx.mx[a]; }
+            }
+        }
+    }
+    __syncthreads();
+    if (j < n) for (int a = 0; a < 3; a++) { box_min[3 * (size_t)(r + j) + a] = s_mn[j][a]; box_max[3 * (size_t)(r + j) + a] = s_mx[j][a]; }
+}
+
+// Workgroup k owns object k's nodes ABOVE the bottom subtrees: top_nodes[top_off[k] .. top_off[k + 1]), sorted by height.  A child is
+// either the root of a bottom subtree (its box was written by the launch before this one) or a node this workgroup wrote one height
+// earlier, behind a __syncthreads() (which orders the workgroup's global stores and loads as well as its LDS).
+__global__ __launch_bounds__(256) void k_pose_top(const int32_t* __restrict__ top_off, const int32_t* __restrict__ top_nodes, const DevNode* __restrict__ nodes,
+                                                  const uint8_t* __restrict__ height, float* box_min, float* box_max) {
+    const int32_t b = top_off[blockIdx.x], e = top_off[blockIdx.x + 1];
+    if (b == e) return;
+    const int32_t H = height[top_nodes[e - 1]];                      // the root: the highest node, last in the list
+    for (int32_t lv = POSE_SUB_HEIGHT + 1; lv <= H; lv++) {
+        for (int32_t i = b + (int32_t)threadIdx.x; i < e; i += 256) {
+            const int32_t j = top_nodes[i];
+            if (height[j] != lv) continue;
+            const size_t l = (size_t)j + 1, r = (size_t)(~nodes[j].leaf);
+            PoseBox bx; for (int a = 0; a < 3; a++) { bx.mn[a] = box_min[3 * l + a]; bx.mx[a] = box_max[3 * l + a]; }
+            pose_box_combine(bx, box_min + 3 * r, box_max + 3 * r);
+            for (int a = 0; a < 3; a++) { box_min[3 * (size_t)j + a] = bx.mn[a]; box_max[3 * (size_t)j + a] = bx.mx[a]; }
+        }
+        __syncthreads();
+    }
+}
+
+// The union of the root boxes (what union_of_roots computes on the host, compare for compare, objects in order): one workgroup; lane t
+// folds a contiguous run of objects, lane 0 folds the 256 partial boxes in lane order.
+__global__ __launch_bounds__(256) void k_pose_scene_box(uint32_t n_objects, const int2* __restrict__ obj_range, const float* __restrict__ box_min,
+                                                        const float* __restrict__ box_max, float* __restrict__ scene_box) {
+    __shared__ float s_lo[256][3], s_hi[256][3];
+    const uint32_t per = (n_objects + 255) / 256, k0 = threadIdx.x * per, k1 = k0 + per < n_objects ? k0 + per : n_objects;
+    float lo[3] = { 3.402823466e+38f, 3.402823466e+38f, 3.402823466e+38f }, hi[3] = { -3.402823466e+38f, -3.402823466e+38f, -3.402823466e+38f };
+    for (uint32_t k = k0; k < k1; k++) {
+        const size_t r = (size_t)obj_range[k].x;
+        for (int a = 0; a < 3; a++) { const float mn = box_min[3 * r + a], mx = box_max[3 * r + a]; if (mn < lo[a]) lo[a] = mn; if (mx > hi[a]) hi[a] = mx; }
+    }
+    for (int a = 0; a < 3; a++) { s_lo[threadIdx.x][a] = lo[a]; s_hi[threadIdx.x][a] = hi[a]; }
+    __syncthreads();
+    if (threadIdx.x) return;
+    const uint32_t n_part = (n_objects + per - 1) / per;          // lanes that had objects (<= 256); the others hold the start values
+    for (uint32_t t = 1; t < n_part; t++) for (int a = 0; a < 3; a++) { if (s_lo[t][a] < lo[a]) lo[a] = s_lo[t][a]; if (s_hi[t][a] > hi[a]) hi[a] = s_hi[t][a]; }
+    scene_box[0] = lo[0]; scene_box[1] = lo[1]; scene_box[2] = lo[2]; scene_box[3] = hi[0]; scene_box[4] = hi[1]; scene_box[5] = hi[2]; scene_box[6] = 0.f; scene_box[7] = 0.f;
+}
+
+// =================================================================================================
 // The chip's VALU issue rate, measured (srt_debug_valu_rate): every wave runs `iters` x 64 v_fma_f32 over 16 independent accumulators
 // between two pairs of stamps (s_memtime = shader cycles, s_memrealtime = the constant 100 MHz counter all CUs share) and notes the
 // SIMD it ran on.  With several such waves per SIMD the SIMDs issue back to back, so a SIMD's instructions over the cycles between its

@@ -69,6 +69,8 @@ def load():
         L.srth_renderer_collect.restype = C.c_int64
         L.srth_renderer_render_from_camera.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, _f32p, _f32p, C.c_int, C.c_int, _f32p]
         L.srth_renderer_render_from_camera.restype = C.c_int64
+        L.srth_renderer_render_posed.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, _f32p, _f32p, C.c_uint32, C.c_int, C.c_int, _f32p]
+        L.srth_renderer_render_posed.restype = C.c_int64
         L.srth_write_bmp.argtypes = [C.c_char_p, C.c_uint32, C.c_uint32, _u8p]
         L.srth_radians.argtypes = [C.c_float]
         L.srth_radians.restype = C.c_float
@@ -265,7 +267,7 @@ class ObjectManager:
 
 
 class Renderer:
-    """srt_host::Renderer: a device scene kept across frames (in-place scene updates, pinned buffers, asynchronous frames, camera mode)."""
+    """srt_host::Renderer: a device scene kept across frames (in-place scene updates, pinned buffers, asynchronous frames, camera mode, pose mode)."""
 
     def __init__(self, device=0):
         self.L = load()
@@ -312,6 +314,13 @@ class Renderer:
         light4_world, view16 = _f(light4_world), _f(view16); rgb = self._out(W, H, image)
         return self._ret(self.L.srth_renderer_render_from_camera(self.h, om.om, W, H, _p(light4_world), _p(view16), light_amount, int(scene_changed),
                                                                  _p(rgb) if image else None), rgb)
+
+    def render_posed(self, om, W, H, light4, matrices, light_amount=1, scene_changed=False, image=True):
+        """POSE (extension): the resident scene moved by one column-major 4x4 per object (objects in om.flatten().names order), applied to
+        the points the scene was uploaded with; the scene is uploaded first, or again when scene_changed."""
+        light4, m = _f(light4), _f(matrices).reshape(-1, 16); rgb = self._out(W, H, image)
+        return self._ret(self.L.srth_renderer_render_posed(self.h, om.om, W, H, _p(light4), _p(m), m.shape[0], light_amount, int(scene_changed),
+                                                           _p(rgb) if image else None), rgb)
 
 
 class MultiRenderer:

@@ -20,7 +20,7 @@ ABI_SYMBOLS = ("srt_params_default", "srt_light_staircase", "srt_rows_owned", "s
                "srt_render_device", "srt_render_device_batch", "srt_render", "srt_render_async", "srt_host_alloc", "srt_host_free", "srt_sync", "srt_scene_device_bytes", "srt_strerror",
                "srt_last_hip_error", "srt_abi_version", "srt_kat_ray_aabb", "srt_kat_ray_triangle", "srt_kat_phong", "srt_kat_tonemap", "srt_kat_interp_normal", "srt_kat_pow",
                "srt_kat_ray_triangle_origin", "srt_kat_barycentric", "srt_debug_fail_host_allocs", "srt_debug_valu_rate", "srt_debug_scene_records", "srt_scene_set_source", "srt_scene_update_frame",
-               "srt_scene_pipeline", "srt_scene_overlap_estimate")
+               "srt_scene_pipeline", "srt_scene_overlap_estimate", "srt_scene_set_pose_source", "srt_scene_pose")
 
 _f32p, _i32p, _u8p = C.POINTER(C.c_float), C.POINTER(C.c_int32), C.POINTER(C.c_uint8)
 _lib = None
@@ -78,6 +78,10 @@ def load():
         L.srt_scene_pipeline.restype = C.c_char_p
         L.srt_scene_overlap_estimate.argtypes = [C.c_void_p]
         L.srt_scene_overlap_estimate.restype = C.c_double
+        L.srt_scene_set_pose_source.argtypes = [C.c_void_p, _f32p]
+        L.srt_scene_set_pose_source.restype = C.c_int
+        L.srt_scene_pose.argtypes = [C.c_void_p, C.c_uint32, _f32p, _f32p, _f32p, C.c_void_p]
+        L.srt_scene_pose.restype = C.c_int
         L.srt_strerror.argtypes = [C.c_int]
         L.srt_strerror.restype = C.c_char_p
         L.srt_last_hip_error.restype = C.c_int
@@ -155,6 +159,20 @@ class DeviceScene:
         g.obj_material = mat.ctypes.data_as(_f32p) if mat is not None else None
         self.L.srt_scene_update_frame.argtypes = [C.c_void_p, C.POINTER(abi.FrameGeometry), C.c_void_p]
         _check(self.L.srt_scene_update_frame(self.h, C.byref(g), C.c_void_p(stream)), "srt_scene_update_frame")
+
+    def set_pose_source(self, tri_points=None):
+        """srt_scene_set_pose_source: the points (n_tris x 3 x 4, the scene's visit order) the poses are applied to; default: the flat scene's."""
+        pts = np.ascontiguousarray(self.flat.tri_points if tri_points is None else tri_points, np.float32)
+        assert pts.size == 12 * self.flat.n_tris, "tri_points: n_tris x 3 x 4"
+        _check(self.L.srt_scene_set_pose_source(self.h, pts.ctypes.data_as(_f32p)), "srt_scene_set_pose_source")
+
+    def pose(self, matrices, obj_color=None, obj_material=None, stream=0):
+        """srt_scene_pose: one column-major 4x4 matrix per object (n_objects x 16); points, triangle records and boxes follow on the device."""
+        m = np.ascontiguousarray(matrices, np.float32).reshape(-1, 16)
+        col = None if obj_color is None else np.ascontiguousarray(obj_color, np.float32)
+        mat = None if obj_material is None else np.ascontiguousarray(obj_material, np.float32)
+        _check(self.L.srt_scene_pose(self.h, m.shape[0], m.ctypes.data_as(_f32p), col.ctypes.data_as(_f32p) if col is not None else None,
+                                     mat.ctypes.data_as(_f32p) if mat is not None else None, C.c_void_p(stream)), "srt_scene_pose")
 
     def records(self):
         """srt_debug_scene_records: the device records as raw numpy arrays (dict)."""
