@@ -12,7 +12,9 @@
 #include <cstdlib>
 #include <cstring>
 #include <algorithm>
+#include <array>
 #include <atomic>
+#include <deque>
 #include <map>
 #include <memory>
 #include <new>
@@ -54,16 +56,63 @@ static inline void alloc_gate() {
     if (n > 0) throw std::bad_alloc();
 }
 
+#define SRT_TRY(expr) do { int rc_ = (expr); if (rc_ != SRT_OK) return rc_; } while (0)
+
 constexpr double PACKET_OVERLAP_THRESHOLD = 150.;     // expected slab tests per ray from which primary rays use the packet walk (measured: DESIGN.md s5)
 constexpr int RING = 64;         // HIP-event triples kept for per-kernel timing between two srt_sync calls
+
+// ---- owners: whatever a handle or the records allocate is freed by the destructor of one of these, with the device already current ----
+// Device (or pinned host) memory of `cap` units of K elements each; reads as a plain T* wherever one is expected.  Grow-only: reserve frees
+// first and allocates second, so the peak is the larger block alone, and a failed allocation leaves p null and cap 0 for the next call to
+// try again.  The owner knows nothing of enqueued work: whoever grows a buffer that a render may still read waits first (grow, stage_acquire).
+template <typename T, size_t K, bool PINNED>
+struct Buf {
+    T* p = nullptr; size_t cap = 0;
+    Buf() = default;
+    Buf(const Buf&) = delete; Buf& operator=(const Buf&) = delete;
+    ~Buf() { release(); }
+    operator T*() const { return p; }
+    void release() { if (p) { if (PINNED) (void)hipHostFree(p); else (void)hipFree(p); } p = nullptr; cap = 0; }
+    hipError_t reserve(size_t n) {
+        if (n <= cap) return hipSuccess;
+        release();
+        const hipError_t e = PINNED ? hipHostMalloc((void**)&p, n * K * sizeof(T), hipHostMallocDefault) : hipMalloc((void**)&p, n * K * sizeof(T));
+        if (e == hipSuccess) cap = n; else p = nullptr;
+        return e;
+    }
+};
+template <typename T, size_t K = 1> using DevArray = Buf<T, K, false>;
+template <typename T, size_t K = 1> using Pinned = Buf<T, K, true>;
+
+struct Event {
+    hipEvent_t e = nullptr;
+    Event() = default;
+    Event(const Event&) = delete; Event& operator=(const Event&) = delete;
+    ~Event() { if (e) (void)hipEventDestroy(e); }
+    operator hipEvent_t() const { return e; }
+};
+struct EventRing {                   // per render: start, closest-hit done, shadow done, shade done; a slot's events are made on first use
+    hipEvent_t ev[RING][4] = {};
+    EventRing() = default;
+    EventRing(const EventRing&) = delete; EventRing& operator=(const EventRing&) = delete;
+    ~EventRing() { for (auto& slot : ev) for (hipEvent_t e : slot) if (e) (void)hipEventDestroy(e); }
+    hipEvent_t* operator[](size_t i) { return ev[i]; }
+};
+struct Stream {
+    hipStream_t st = nullptr;
+    Stream() = default;
+    Stream(const Stream&) = delete; Stream& operator=(const Stream&) = delete;
+    ~Stream() { if (st) (void)hipStreamDestroy(st); }
+    operator hipStream_t() const { return st; }
+};
 
 // The device records of a scene: owned by the handle that uploaded them and by every handle made from it with srt_scene_share.
 struct SceneRecords {
     int device = 0;
-    std::vector<void*> allocs;
+    std::deque<DevArray<char>> owned;        // every array below and every array of DevScene: made once, freed with the last handle
     std::vector<uint64_t> tex_off; std::vector<uint32_t> tex_w, tex_h;      // the uploaded texture table (host copy) ...
     uint64_t tex_bytes = 0, tex_hash = 0;                                    // ... and the size and content hash of the uploaded images
-    double overlap = 0.;             // expected slab tests per ray (surface-area estimate, see scene_create_impl)
+    double overlap = 0.;             // expected slab tests per ray (surface-area estimate, see overlap_estimate)
     bool prefer_packet = false;      // hierarchy of heavily overlapping boxes: primary rays take the packet walk too
     bool int_shin = false;           // every object's shininess is an integer in [1, 64]: the shading kernel without the general pow
     // host copies of the static topology (srt_scene_update_frame checks counts against them and re-estimates the overlap from a frame's boxes)
@@ -75,7 +124,13 @@ struct SceneRecords {
     // static schedule of the refit -- node heights, the roots of the bottom subtrees, per object the nodes above them sorted by height
     float4* d_pose_points = nullptr; float2* d_tri_box = nullptr; float* d_obj_matrix = nullptr; uint8_t* d_height = nullptr;
     int32_t* d_sub_root = nullptr; int32_t* d_top_nodes = nullptr; int32_t* d_top_off = nullptr; uint32_t n_sub = 0; bool have_pose = false;
-    ~SceneRecords() { (void)hipSetDevice(device); for (void* d : allocs) (void)hipFree(d); }
+    ~SceneRecords() { (void)hipSetDevice(device); }      // (the arrays go with `owned`, after this body)
+    hipError_t make(void** out, size_t bytes) {
+        owned.emplace_back();
+        const hipError_t e = owned.back().reserve(bytes ? bytes : 1);
+        if (e == hipSuccess) *out = owned.back().p; else owned.pop_back();
+        return e;
+    }
 };
 
 struct srt_scene {
@@ -83,23 +138,23 @@ struct srt_scene {
     DevScene dev{};
     std::shared_ptr<SceneRecords> rec;
     uint64_t bytes = 0;
-    // workspace
-    int32_t* ws_hit = nullptr; float* ws_t = nullptr; size_t ws_pixels = 0;
-    float* ws_lin = nullptr; uint8_t* ws_rgb8 = nullptr; size_t ws_out_pixels = 0;
-    float* d_lights = nullptr; float* h_lights = nullptr; uint32_t lights_cap = 0, lights_valid = 0;
-    unsigned long long* d_counters = nullptr; unsigned long long* h_counters = nullptr;   // device: two sets used alternately
+    // workspace; capacities count pixels, light samples, words or bytes (K of the owner = elements per unit)
+    DevArray<int32_t> ws_hit; DevArray<float> ws_t;
+    DevArray<float, 3> ws_lin; DevArray<uint8_t, 3> ws_rgb8;
+    DevArray<float, 3> d_lights; Pinned<float, 3> h_lights; uint32_t lights_valid = 0;
+    DevArray<unsigned long long> d_counters; Pinned<unsigned long long> h_counters;       // device: two sets used alternately
     unsigned long long* d_ctr_last = nullptr;     // set written by the most recent render
     uint64_t render_seq = 0;
     bool ctr_dirty = false;                       // a render returned an error after its first launch
     char pipeline[96] = "";                       // kernels of the last render, in launch order
     uint32_t n_textures = 0; bool has_tex = false;
-    void* stage = nullptr; size_t stage_bytes = 0; hipEvent_t staged = nullptr;      // pinned staging of srt_scene_update
-    hipStream_t stream = nullptr;                 // the scene's own stream (srt_render, srt_render_async, srt_scene_update with stream NULL)
-    unsigned long long* ws_shadow = nullptr; size_t ws_shadow_words = 0;
-    uint32_t* ws_qlist = nullptr; uint32_t* d_qcount = nullptr; uint32_t qcap = 0;      // quadrants with hits: 64 shard lists of qcap entries, their counters
-    float* ws_acc = nullptr; float* ws_sub = nullptr; int32_t* ws_sub_hit = nullptr; float* ws_sub_t = nullptr; size_t ws_acc_pixels = 0;
+    Pinned<char> stage; Event staged;             // pinned staging of srt_scene_update / _update_frame / _pose (stage_acquire)
+    Stream stream;                                // the scene's own stream (srt_render, srt_render_async, srt_scene_update with stream NULL)
+    DevArray<unsigned long long> ws_shadow;
+    DevArray<uint32_t, 3> ws_qlist; DevArray<uint32_t> d_qcount; uint32_t qcap = 0;      // quadrants with hits: 64 shard lists of qcap entries, their counters
+    DevArray<float, 3> ws_acc, ws_sub; DevArray<int32_t> ws_sub_hit; DevArray<float> ws_sub_t;
     int n_cu = 256;
-    hipEvent_t ev[RING][4] = {};     // start, closest-hit done, shadow done, shade done
+    EventRing ev;
     uint32_t ring_count = 0;         // renders since the last srt_sync
     hipEvent_t last_done = nullptr;  // ev[..][2] of the most recent render
     hipStream_t last_stream = nullptr;
@@ -107,15 +162,30 @@ struct srt_scene {
     srt_stats last{};
 };
 
+// Wait for the work of earlier renders before their buffers are reused or freed.
+static hipError_t wait_idle(srt_scene* s) {
+    if (!s->pending) return hipSuccess;
+    return s->last_done ? hipEventSynchronize(s->last_done) : hipStreamSynchronize(s->last_stream);
+}
+
+// Workspace that shares a capacity, to n units each: nothing when all of it is that large, else wait for the renders that may still use
+// it, free all of it, then allocate all of it.  A failure leaves some of it empty, and the next call starts over.
+template <typename... B>
+static int grow(srt_scene* s, size_t n, B&... bufs) {
+    if (((bufs.cap >= n) && ...)) return SRT_OK;
+    HIP_TRY(wait_idle(s));
+    (bufs.release(), ...);
+    hipError_t e = hipSuccess;
+    ((e = e == hipSuccess ? bufs.reserve(n) : e), ...);
+    HIP_TRY(e);
+    return SRT_OK;
+}
+
+// An array of the records that is made on first use (the sources of update_frame and pose): `bytes` of device memory, then src_bytes from src.
 template <typename T>
-static int upload(srt_scene* s, const T* host, size_t n, const T** out) {
-    void* d = nullptr;
-    size_t bytes = sizeof(T) * (n ? n : 1);
-    HIP_TRY(hipMalloc(&d, bytes));
-    s->rec->allocs.push_back(d);
-    if (n) HIP_TRY(hipMemcpy(d, host, sizeof(T) * n, hipMemcpyHostToDevice));
-    s->bytes += bytes;
-    *out = (const T*)d;
+static int lazy_array(srt_scene* s, T** dst, size_t bytes, const void* src = nullptr, size_t src_bytes = 0) {
+    if (!*dst) { HIP_TRY(s->rec->make((void**)dst, bytes)); s->bytes += bytes; }
+    if (src && src_bytes) HIP_TRY(hipMemcpy(*dst, src, src_bytes, hipMemcpyHostToDevice));
     return SRT_OK;
 }
 
@@ -197,37 +267,12 @@ uint32_t srt_rows_owned(const srt_params* p) {
     return rows;
 }
 
-// Wait for the work of earlier renders before their buffers are reused or freed.
-static hipError_t wait_idle(srt_scene* s) {
-    if (!s->pending) return hipSuccess;
-    return s->last_done ? hipEventSynchronize(s->last_done) : hipStreamSynchronize(s->last_stream);
-}
-
 int srt_scene_destroy(srt_scene* s) {
     if (!s) return SRT_ERR_ARG;
     (void)hipSetDevice(s->device);
     (void)wait_idle(s);
-    s->rec.reset();                      // frees the records with their last handle
-    if (s->ws_hit) (void)hipFree(s->ws_hit);
-    if (s->ws_t) (void)hipFree(s->ws_t);
-    if (s->ws_lin) (void)hipFree(s->ws_lin);
-    if (s->ws_rgb8) (void)hipFree(s->ws_rgb8);
-    if (s->ws_shadow) (void)hipFree(s->ws_shadow);
-    if (s->ws_qlist) (void)hipFree(s->ws_qlist);
-    if (s->d_qcount) (void)hipFree(s->d_qcount);
-    if (s->stream) { (void)hipStreamSynchronize(s->stream); (void)hipStreamDestroy(s->stream); }
-    if (s->stage) (void)hipHostFree(s->stage);
-    if (s->staged) (void)hipEventDestroy(s->staged);
-    if (s->ws_acc) (void)hipFree(s->ws_acc);
-    if (s->ws_sub) (void)hipFree(s->ws_sub);
-    if (s->ws_sub_hit) (void)hipFree(s->ws_sub_hit);
-    if (s->ws_sub_t) (void)hipFree(s->ws_sub_t);
-    if (s->d_lights) (void)hipFree(s->d_lights);
-    if (s->h_lights) (void)hipHostFree(s->h_lights);
-    if (s->d_counters) (void)hipFree(s->d_counters);
-    if (s->h_counters) (void)hipHostFree(s->h_counters);
-    for (auto& tr : s->ev) for (auto& e : tr) if (e) (void)hipEventDestroy(e);
-    delete s;
+    if (s->stream) (void)hipStreamSynchronize(s->stream);
+    delete s;                            // the owners free what the handle holds; the records go with their last handle
     return SRT_OK;
 }
 
@@ -313,12 +358,24 @@ static void build_wide_records(const DevNode* nodes, uint32_t n_nodes, const int
     }
 }
 
+// Boxes by node index, from either form the host has them in: the records, or the min / max arrays of a frame (srt_frame_geometry).
+struct Boxes {
+    const DevNode* nodes; const float* bmin; const float* bmax;
+    explicit Boxes(const DevNode* nodes_) : nodes(nodes_), bmin(nullptr), bmax(nullptr) {}
+    Boxes(const float* bmin_, const float* bmax_) : nodes(nullptr), bmin(bmin_), bmax(bmax_) {}
+    void operator()(size_t i, float* mn, float* mx) const {
+        if (nodes) { const DevNode& n = nodes[i]; mn[0] = n.minx; mn[1] = n.miny; mn[2] = n.minz; mx[0] = n.maxx; mx[1] = n.maxy; mx[2] = n.maxz; }
+        else for (int a = 0; a < 3; a++) { mn[a] = bmin[3 * i + a]; mx[a] = bmax[3 * i + a]; }
+    }
+};
+
 // the union of the objects' root boxes, in a node's box layout (min.xyz max.x | max.yz 0 0): what a tile's rays are tested against
 // before the roots themselves in scenes of several objects (srt_kernels.h background_test_wave)
-static void union_of_roots(const DevNode* roots, uint32_t n, float* out8) {
+static void union_of_roots(const Boxes& box, const int2* ranges, uint32_t n_objects, float* out8) {
     float lo[3] = { FLT_MAX, FLT_MAX, FLT_MAX }, hi[3] = { -FLT_MAX, -FLT_MAX, -FLT_MAX };
-    for (uint32_t k = 0; k < n; k++) {
-        const float mn[3] = { roots[k].minx, roots[k].miny, roots[k].minz }, mx[3] = { roots[k].maxx, roots[k].maxy, roots[k].maxz };
+    for (uint32_t k = 0; k < n_objects; k++) {
+        float mn[3], mx[3];
+        box((size_t)ranges[k].x, mn, mx);
         for (int a = 0; a < 3; a++) { if (mn[a] < lo[a]) lo[a] = mn[a]; if (mx[a] > hi[a]) hi[a] = mx[a]; }
     }
     out8[0] = lo[0]; out8[1] = lo[1]; out8[2] = lo[2]; out8[3] = hi[0]; out8[4] = hi[1]; out8[5] = hi[2]; out8[6] = 0.f; out8[7] = 0.f;
@@ -347,15 +404,16 @@ static uint64_t content_hash(const uint8_t* p, size_t n) {
 // hierarchy gives a few dozen (bunny: boxes shrink with depth); a median split by first vertex of a random soup gives hundreds
 // to thousands (boxes stay as wide as the scene in two axes).  In the second case neighbouring rays test nearly the same nodes
 // and the packet walk (srt_packet.h) wins for primary rays as well.
-static double overlap_estimate(const DevNode* nodes, uint32_t n_nodes, const int2* ranges, uint32_t n_objects) {
+// leaf[i] < 0: node i is an inner node (DevNode::leaf, SceneRecords::h_leaf).  The sum runs over the inner nodes in index order.
+static double overlap_estimate(const Boxes& box, const int32_t* leaf, uint32_t n_nodes, const int2* ranges, uint32_t n_objects) {
     float lo[3] = { 3.0e38f, 3.0e38f, 3.0e38f }, hi[3] = { -3.0e38f, -3.0e38f, -3.0e38f };
     auto area = [](const float* a, const float* b) -> double {
         const double x = (double)b[0] - a[0], y = (double)b[1] - a[1], z = (double)b[2] - a[2];
         return (x < 0 || y < 0 || z < 0) ? 0. : x * y + y * z + z * x;
     };
+    float mn[3], mx[3];
     for (uint32_t k = 0; k < n_objects; k++) {
-        const DevNode& n = nodes[ranges[k].x];
-        const float mn[3] = { n.minx, n.miny, n.minz }, mx[3] = { n.maxx, n.maxy, n.maxz };
+        box((size_t)ranges[k].x, mn, mx);
         if (area(mn, mx) <= 0.) continue;
         for (int a = 0; a < 3; a++) { lo[a] = mn[a] < lo[a] ? mn[a] : lo[a]; hi[a] = mx[a] > hi[a] ? mx[a] : hi[a]; }
     }
@@ -363,9 +421,8 @@ static double overlap_estimate(const DevNode* nodes, uint32_t n_nodes, const int
     if (!(total > 0.)) return 0.;
     double sum = 0.;
     for (uint32_t i = 0; i < n_nodes; i++) {
-        const DevNode& n = nodes[i];
-        if (n.leaf >= 0) continue;                       // the children of an inner node are tested when its box is crossed
-        const float mn[3] = { n.minx, n.miny, n.minz }, mx[3] = { n.maxx, n.maxy, n.maxz };
+        if (leaf[i] >= 0) continue;                      // the children of an inner node are tested when its box is crossed
+        box(i, mn, mx);
         sum += 2. * area(mn, mx);
     }
     return (double)n_objects + sum / total;              // + every root
@@ -402,9 +459,9 @@ static void derive_tri_first(const srt_scene_desc* d, int32_t* first) {
     for (uint32_t k = d->n_objects; k-- > 0;) if (first[k] > first[k + 1]) first[k] = first[k + 1];      // objects without triangles
 }
 
-static bool all_integer_shininess(const srt_scene_desc* d) {
-    for (uint32_t k = 0; k < d->n_objects; k++) {
-        const float sh = d->obj_material[3 * (size_t)k + 2];
+static bool all_integer_shininess(const float* obj_material, uint32_t n_objects) {
+    for (uint32_t k = 0; k < n_objects; k++) {
+        const float sh = obj_material[3 * (size_t)k + 2];
         if (!(sh >= 1.0f && sh <= 64.0f && sh == std::trunc(sh))) return false;
     }
     return true;
@@ -425,110 +482,147 @@ static int check_desc(const srt_scene_desc* d) {
     return SRT_OK;
 }
 
+static bool any_textured(const srt_scene_desc* d) {
+    bool any_tex = false;
+    if (d->n_textures && d->tri_tex) for (uint32_t i = 0; i < d->n_tris; i++) any_tex |= d->tri_tex[i] >= 0;
+    return any_tex;
+}
+
 // What every handle has of its own besides the records: the two counter sets, the quadrant-list counters, the pinned counter image.
 static hipError_t init_handle_state(srt_scene* s) {
-    hipError_t e = hipMalloc((void**)&s->d_counters, 2 * NCTR * sizeof(unsigned long long));
+    hipError_t e = s->d_counters.reserve(2 * NCTR);
     if (e == hipSuccess) e = hipMemset(s->d_counters, 0, 2 * NCTR * sizeof(unsigned long long));
-    if (e == hipSuccess) e = hipMalloc((void**)&s->d_qcount, QL_COUNTERS * QL_STRIDE * sizeof(uint32_t));
+    if (e == hipSuccess) e = s->d_qcount.reserve(QL_COUNTERS * QL_STRIDE);
     if (e == hipSuccess) e = hipMemset(s->d_qcount, 0, QL_COUNTERS * QL_STRIDE * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipHostMalloc((void**)&s->h_counters, NCTR * sizeof(unsigned long long), hipHostMallocDefault);
+    if (e == hipSuccess) e = s->h_counters.reserve(NCTR);
     hipDeviceProp_t prop;
     if (e == hipSuccess) e = hipGetDeviceProperties(&prop, s->device);
     if (e == hipSuccess && prop.multiProcessorCount > 0) s->n_cu = prop.multiProcessorCount;
     return e;
 }
 
+// ---- the record arrays of a scene, stated once -----------------------------------------------------------------------------------
+// One row per array that srt_scene_create allocates and fills and srt_scene_update fills again, numbered in the order of the device
+// allocations.  elem x n is the array's size (an array of no elements still gets an allocation of one); elem = 0: not in this scene, or
+// not in this call.  src: the caller's array when it goes to the device as it is, null when derive_records writes it.  off: its place in
+// the host block the rows are derived and staged in.  A new array is a new row here (and its derivation, if it has one).
+enum RecordId { R_NODES, R_WIDE, R_ROOT_INFO, R_ROOTS, R_SCENE_BOX, R_TRIS, R_TRIS_O, R_TRI_OBJ, R_RANGES, R_TRI_FIRST, R_COLOR, R_MAT, R_NORMALS,
+                R_TRI_TEX, R_TRI_TC, R_TEX, R_TEX_OFF, R_TEX_SIZE, R_TEX_W, R_TEX_H, R_WIDX, R_COUNT };
+struct RecordArray { void** dev; size_t elem, n; const void* src; size_t off; size_t bytes() const { return elem * n; } };
+using RecordList = std::array<RecordArray, R_COUNT>;
+
+// tex_bytes: the texture images' size when they are to be uploaded, else 0; tex_table: offsets and sizes too (they never change after
+// srt_scene_create).  stage_sources: the host block has room for the caller's arrays as well (pinned staging), not only for the derived ones.
+static RecordList record_list(DevScene& v, SceneRecords& r, const srt_scene_desc* d, bool any_tex, size_t tex_bytes, bool tex_table, bool stage_sources, size_t* host_bytes) {
+    const size_t nN = d->n_nodes, nT = d->n_tris, nO = d->n_objects, nX = d->n_textures;
+    const size_t nrm = d->tri_normals && nT ? 1 : 0, tex = any_tex ? 1 : 0, img = tex_bytes ? 1 : 0, tab = any_tex && tex_table ? 1 : 0;
+    RecordList l{};
+    #define ROW(id, ptr, elem, n, src) l[id] = RecordArray{ (void**)&(ptr), (elem), (n), (src), 0 }
+    ROW(R_NODES, v.nodes, sizeof(DevNode), nN, nullptr);
+    ROW(R_WIDE, v.wide, sizeof(DevWide), wide_count(d->n_nodes, d->n_objects), nullptr);
+    ROW(R_ROOT_INFO, v.obj_root_info, 4, nO, nullptr);
+    ROW(R_ROOTS, v.root_nodes, sizeof(DevNode), nO, nullptr);
+    ROW(R_SCENE_BOX, v.scene_box, 4, 8, nullptr);
+    ROW(R_TRIS, v.tris, sizeof(DevTri), nT, nullptr);
+    ROW(R_TRIS_O, v.tris_o, sizeof(DevTriO), nT, nullptr);
+    ROW(R_TRI_OBJ, v.tri_obj, 4, nT, d->tri_obj);
+    ROW(R_RANGES, v.obj_range, sizeof(int2), nO, nullptr);
+    ROW(R_TRI_FIRST, v.obj_tri_first, 4, nO + 1, nullptr);
+    ROW(R_COLOR, v.obj_color, 4, nO * 3, d->obj_color);
+    ROW(R_MAT, v.obj_mat, 4, nO * 3, d->obj_material);
+    ROW(R_NORMALS, v.tri_normals, nrm * 4, nT * 9, d->tri_normals);
+    ROW(R_TRI_TEX, v.tri_tex, tex * 4, nT, d->tri_tex);
+    ROW(R_TRI_TC, v.tri_tc, tex * 4, nT * 6, d->tri_texcoord);
+    ROW(R_TEX, v.tex, img, tex_bytes, d->tex_rgb);
+    ROW(R_TEX_OFF, v.tex_off, tab * 8, nX, nullptr);
+    ROW(R_TEX_SIZE, v.tex_size, tab * 8, nX, nullptr);
+    ROW(R_TEX_W, v.tex_w, tab * 4, nX, d->tex_w);
+    ROW(R_TEX_H, v.tex_h, tab * 4, nX, d->tex_h);
+    ROW(R_WIDX, r.d_widx, 4, nN, nullptr);
+    #undef ROW
+    size_t off = 0;
+    for (RecordArray& a : l) { a.off = off; if (a.elem && (stage_sources || !a.src)) off += (a.bytes() + 255) & ~(size_t)255; }
+    *host_bytes = off;
+    return l;
+}
+
+// Every row without a source, derived into its place in the host block h -- a vector when a scene is created, the pinned staging
+// block when it is updated.  Validates the layout contract on the way (build_device_records).
+static int derive_records(const srt_scene_desc* d, const RecordList& l, char* h) {
+    DevNode* nodes = (DevNode*)(h + l[R_NODES].off); int2* ranges = (int2*)(h + l[R_RANGES].off); DevNode* roots = (DevNode*)(h + l[R_ROOTS].off);
+    SRT_TRY(build_device_records(d, nodes, ranges));
+    build_wide_records(nodes, d->n_nodes, ranges, d->n_objects, (DevWide*)(h + l[R_WIDE].off), (int32_t*)(h + l[R_ROOT_INFO].off), (int32_t*)(h + l[R_WIDX].off));
+    for (uint32_t k = 0; k < d->n_objects; k++) roots[k] = nodes[ranges[k].x];
+    union_of_roots(Boxes(nodes), ranges, d->n_objects, (float*)(h + l[R_SCENE_BOX].off));
+    derive_triangles(d, (DevTri*)(h + l[R_TRIS].off), (DevTriO*)(h + l[R_TRIS_O].off));
+    derive_tri_first(d, (int32_t*)(h + l[R_TRI_FIRST].off));
+    if (l[R_TEX_OFF].elem) {
+        unsigned long long* off = (unsigned long long*)(h + l[R_TEX_OFF].off); unsigned long long* size = (unsigned long long*)(h + l[R_TEX_SIZE].off);
+        for (uint32_t k = 0; k < d->n_textures; k++) { off[k] = d->tex_off[k]; size[k] = (unsigned long long)d->tex_w[k] * d->tex_h[k] * 3; }
+    }
+    return SRT_OK;
+}
+
+// What the host keeps of the records in h: the estimates that steer the pipeline, and the topology srt_scene_update_frame and
+// srt_scene_set_pose_source rely on (after an update it may differ from the previous contents': same counts, other trees).
+static void note_records(SceneRecords& r, const srt_scene_desc* d, const RecordList& l, const char* h) {
+    const DevNode* nodes = (const DevNode*)(h + l[R_NODES].off); const int2* ranges = (const int2*)(h + l[R_RANGES].off);
+    const int32_t* first = (const int32_t*)(h + l[R_TRI_FIRST].off);
+    r.h_ranges.assign(ranges, ranges + d->n_objects);
+    r.h_tri_first.assign(first, first + d->n_objects + 1);
+    r.h_leaf.resize(d->n_nodes); for (uint32_t i = 0; i < d->n_nodes; i++) r.h_leaf[i] = nodes[i].leaf;
+    r.overlap = overlap_estimate(Boxes(nodes), r.h_leaf.data(), d->n_nodes, ranges, d->n_objects);
+    r.prefer_packet = r.overlap > PACKET_OVERLAP_THRESHOLD;
+    r.int_shin = all_integer_shininess(d->obj_material, d->n_objects);
+    r.have_source = false;               // attributes in source order belong to the previous contents
+    r.have_pose = false;                 // ... and so do the pose source's order and the refit's schedule
+}
+
 static int scene_create_impl(int device, const srt_scene_desc* d, srt_scene** out) {
     if (!d || !out) return SRT_ERR_ARG;
     *out = nullptr;
-    int rc = check_desc(d);
-    if (rc != SRT_OK) return rc;
+    SRT_TRY(check_desc(d));
+    const bool any_tex = any_textured(d);
+    unsigned long long tex_total = 0;
+    bool tex_empty = false;
+    if (any_tex) for (uint32_t k = 0; k < d->n_textures; k++) {
+        const unsigned long long size = (unsigned long long)d->tex_w[k] * d->tex_h[k] * 3;
+        tex_empty |= size < 3;
+        if (d->tex_off[k] + size > tex_total) tex_total = d->tex_off[k] + size;
+    }
     // host-side records first (validates the layout contract; pure CPU work), then the device
     alloc_gate();
-    std::vector<DevNode> nodes(d->n_nodes); std::vector<int2> ranges(d->n_objects);
-    rc = build_device_records(d, nodes.data(), ranges.data());
-    if (rc != SRT_OK) return rc;
-    const double overlap = overlap_estimate(nodes.data(), d->n_nodes, ranges.data(), d->n_objects);
-    const uint32_t n_wide = wide_count(d->n_nodes, d->n_objects);
-    std::vector<DevWide> wide(n_wide); std::vector<int32_t> root_info(d->n_objects);
-    std::vector<int32_t> widx(d->n_nodes);
-    build_wide_records(nodes.data(), d->n_nodes, ranges.data(), d->n_objects, wide.data(), root_info.data(), widx.data());
-    std::vector<DevTri> tris(d->n_tris);
-    std::vector<DevTriO> tris_o(d->n_tris);
-    derive_triangles(d, tris.data(), tris_o.data());
+    std::unique_ptr<srt_scene> s(new srt_scene());       // (a failed create has enqueued nothing: the owners free what it got so far)
+    s->rec = std::make_shared<SceneRecords>();
+    SceneRecords& r = *s->rec;
+    size_t host_bytes = 0;
+    const RecordList l = record_list(s->dev, r, d, any_tex, (size_t)tex_total, true, false, &host_bytes);
+    std::vector<char> host(host_bytes);
+    SRT_TRY(derive_records(d, l, host.data()));
+    note_records(r, d, l, host.data());
 
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return SRT_ERR_NO_GPU;
     if (device < 0 || device >= ndev) return SRT_ERR_ARG;
     HIP_TRY(hipSetDevice(device));
-    srt_scene* s = new (std::nothrow) srt_scene();
-    if (!s) return SRT_ERR_OOM;
-    s->device = device;
-    s->rec = std::make_shared<SceneRecords>(); s->rec->device = device;
-    #define UP(expr) do { rc = (expr); if (rc != SRT_OK) { srt_scene_destroy(s); return rc; } } while (0)
-    UP(upload(s, nodes.data(), nodes.size(), &s->dev.nodes));
-    UP(upload(s, wide.data(), wide.size(), &s->dev.wide));
-    UP(upload(s, root_info.data(), root_info.size(), &s->dev.obj_root_info));
-    {
-        std::vector<DevNode> roots(d->n_objects);
-        for (uint32_t k = 0; k < d->n_objects; k++) roots[k] = nodes[ranges[k].x];
-        UP(upload(s, roots.data(), roots.size(), &s->dev.root_nodes));
-        float ub[8];
-        union_of_roots(roots.data(), d->n_objects, ub);
-        UP(upload(s, ub, 8, &s->dev.scene_box));
+    if (tex_empty) return SRT_ERR_TEXTURE;
+    s->device = device; r.device = device;
+    for (const RecordArray& a : l) {     // one allocation per array, in the list's order
+        if (!a.elem) continue;
+        const size_t cap = a.elem * (a.n ? a.n : 1);
+        HIP_TRY(r.make(a.dev, cap));
+        s->bytes += cap;
+        if (a.n) HIP_TRY(hipMemcpy(*a.dev, a.src ? a.src : host.data() + a.off, a.bytes(), hipMemcpyHostToDevice));
     }
-    UP(upload(s, tris.data(), tris.size(), &s->dev.tris));
-    UP(upload(s, tris_o.data(), tris_o.size(), &s->dev.tris_o));
-    UP(upload(s, d->tri_obj, d->n_tris, &s->dev.tri_obj));
-    UP(upload(s, ranges.data(), ranges.size(), &s->dev.obj_range));
-    {
-        std::vector<int32_t> first(d->n_objects + 1);
-        derive_tri_first(d, first.data());
-        UP(upload(s, first.data(), first.size(), &s->dev.obj_tri_first));
-    }
-    UP(upload(s, d->obj_color, (size_t)d->n_objects * 3, &s->dev.obj_color));
-    UP(upload(s, d->obj_material, (size_t)d->n_objects * 3, &s->dev.obj_mat));
-    if (d->tri_normals && d->n_tris) UP(upload(s, d->tri_normals, (size_t)d->n_tris * 9, &s->dev.tri_normals));
-    bool any_tex = false;
-    if (d->n_textures && d->tri_tex) for (uint32_t i = 0; i < d->n_tris; i++) any_tex |= d->tri_tex[i] >= 0;
     if (any_tex) {
-        std::vector<unsigned long long> off(d->n_textures), size(d->n_textures);
-        unsigned long long total = 0;
-        for (uint32_t k = 0; k < d->n_textures; k++) {
-            off[k] = d->tex_off[k]; size[k] = (unsigned long long)d->tex_w[k] * d->tex_h[k] * 3;
-            if (size[k] < 3) { srt_scene_destroy(s); return SRT_ERR_TEXTURE; }
-            if (off[k] + size[k] > total) total = off[k] + size[k];
-        }
-        UP(upload(s, d->tri_tex, d->n_tris, &s->dev.tri_tex));
-        UP(upload(s, d->tri_texcoord, (size_t)d->n_tris * 6, &s->dev.tri_tc));
-        UP(upload(s, d->tex_rgb, (size_t)total, &s->dev.tex));
-        UP(upload(s, off.data(), off.size(), &s->dev.tex_off));
-        UP(upload(s, size.data(), size.size(), &s->dev.tex_size));
-        UP(upload(s, d->tex_w, d->n_textures, &s->dev.tex_w));
-        UP(upload(s, d->tex_h, d->n_textures, &s->dev.tex_h));
-        s->rec->tex_off.assign(d->tex_off, d->tex_off + d->n_textures);
-        s->rec->tex_w.assign(d->tex_w, d->tex_w + d->n_textures); s->rec->tex_h.assign(d->tex_h, d->tex_h + d->n_textures);
-        s->rec->tex_bytes = total; s->rec->tex_hash = content_hash(d->tex_rgb, (size_t)total);
+        r.tex_off.assign(d->tex_off, d->tex_off + d->n_textures);
+        r.tex_w.assign(d->tex_w, d->tex_w + d->n_textures); r.tex_h.assign(d->tex_h, d->tex_h + d->n_textures);
+        r.tex_bytes = tex_total; r.tex_hash = content_hash(d->tex_rgb, (size_t)tex_total);
     }
-    #undef UP
     s->dev.n_nodes = d->n_nodes; s->dev.n_tris = d->n_tris; s->dev.n_objects = d->n_objects;
     s->n_textures = d->n_textures; s->has_tex = any_tex;
-    s->rec->overlap = overlap;
-    s->rec->prefer_packet = overlap > PACKET_OVERLAP_THRESHOLD;
-    s->rec->int_shin = all_integer_shininess(d);
-    {   // what srt_scene_update_frame needs of the topology
-        SceneRecords& r = *s->rec;
-        r.h_ranges = ranges;
-        r.h_tri_first.resize(d->n_objects + 1); derive_tri_first(d, r.h_tri_first.data());
-        r.h_leaf.resize(d->n_nodes); for (uint32_t i = 0; i < d->n_nodes; i++) r.h_leaf[i] = nodes[i].leaf;
-        const int32_t* dw = nullptr;
-        rc = upload(s, widx.data(), widx.size(), &dw);
-        if (rc != SRT_OK) { srt_scene_destroy(s); return rc; }
-        r.d_widx = const_cast<int32_t*>(dw);
-    }
-    const hipError_t e = init_handle_state(s);
-    if (e != hipSuccess) { g_last_hip = (int)e; srt_scene_destroy(s); return SRT_ERR_DEVICE; }
-    *out = s;
+    HIP_TRY(init_handle_state(s.get()));
+    *out = s.release();
     return SRT_OK;
 }
 
@@ -538,12 +632,11 @@ static int scene_share_impl(srt_scene* src, srt_scene** out) {
     *out = nullptr;
     HIP_TRY(hipSetDevice(src->device));
     alloc_gate();
-    srt_scene* s = new srt_scene();
+    std::unique_ptr<srt_scene> s(new srt_scene());
     s->device = src->device; s->dev = src->dev; s->rec = src->rec; s->bytes = src->bytes;
     s->n_textures = src->n_textures; s->has_tex = src->has_tex;
-    const hipError_t e = init_handle_state(s);
-    if (e != hipSuccess) { g_last_hip = (int)e; srt_scene_destroy(s); return SRT_ERR_DEVICE; }
-    *out = s;
+    HIP_TRY(init_handle_state(s.get()));
+    *out = s.release();
     return SRT_OK;
 }
 
@@ -555,29 +648,44 @@ int srt_scene_create(int device, const srt_scene_desc* d, srt_scene** out) {
     return guarded([&] { return scene_create_impl(device, d, out); });
 }
 
+// The scene's own stream: srt_render / srt_render_async / srt_scene_update(stream = NULL) are ordered on it.
+static int own_stream(srt_scene* s, hipStream_t* out) {
+    if (!s->stream) HIP_TRY(hipStreamCreateWithFlags(&s->stream.st, hipStreamNonBlocking));
+    *out = s->stream;
+    return SRT_OK;
+}
+
+// The pinned staging block of srt_scene_update, srt_scene_update_frame and srt_scene_pose, at least `bytes` large and free to be written:
+// the copies the previous call enqueued out of it have left it (the event `staged`).  For that to hold, EVERY copy out of the block is
+// enqueued BEFORE its caller records `staged` on the stream -- a copy behind the event could still be reading what the next call writes.
+static int stage_acquire(srt_scene* s, size_t bytes, char** out) {
+    if (!s->staged) HIP_TRY(hipEventCreateWithFlags(&s->staged.e, hipEventDisableTiming));
+    else HIP_TRY(hipEventSynchronize(s->staged));
+    HIP_TRY(s->stage.reserve(bytes));
+    *out = s->stage;
+    return SRT_OK;
+}
+
 // New geometry into the EXISTING device allocations: the reference re-transforms every triangle and rebuilds every hierarchy per
 // frame (simple_raytracer.cpp:534-618), so a drop-in caller hands over a new flat scene per frame -- with the same counts (the
 // builder's tree shape depends only on the triangle count).  Records are derived straight into one pinned staging block and go
 // to the device with asynchronous copies on `stream`: no hipMalloc / hipFree, no pageable copy, no synchronisation with the
 // renders already enqueued on that stream (the copies are ordered behind them).
-static int own_stream(srt_scene* s, hipStream_t* out);
 static int scene_update_impl(srt_scene* s, const srt_scene_desc* d, hipStream_t stream) {
     if (!s || !d) return SRT_ERR_ARG;
-    int rc = check_desc(d);
-    if (rc != SRT_OK) return rc;
-    if (!stream) { rc = own_stream(s, &stream); if (rc != SRT_OK) return rc; }
-    bool any_tex = false;
-    if (d->n_textures && d->tri_tex) for (uint32_t i = 0; i < d->n_tris; i++) any_tex |= d->tri_tex[i] >= 0;
+    SRT_TRY(check_desc(d));
+    if (!stream) SRT_TRY(own_stream(s, &stream));
+    const bool any_tex = any_textured(d);
     if (d->n_objects != s->dev.n_objects || d->n_nodes != s->dev.n_nodes || d->n_tris != s->dev.n_tris || d->n_textures != s->n_textures ||
         any_tex != s->has_tex || (d->tri_normals != nullptr) != (s->dev.tri_normals != nullptr)) return SRT_ERR_LAYOUT;      // counts differ: create a new scene
     // Texture images: the table (offsets, sizes) must be the uploaded one -- the kernels index with the uploaded tex_w / tex_off --
     // and the image bytes are uploaded again when their content hash differs from what is on the device.  (A second scene with the
     // same counts but other pictures, handed to a renderer that keeps one device scene, must not be shaded with the first one's.)
+    SceneRecords& r = *s->rec;
     size_t tex_total = 0;
     bool tex_changed = false;
     uint64_t tex_hash_new = 0;
     if (any_tex) {
-        SceneRecords& r = *s->rec;
         for (uint32_t k = 0; k < d->n_textures; k++) {
             if (d->tex_off[k] != r.tex_off[k] || d->tex_w[k] != r.tex_w[k] || d->tex_h[k] != r.tex_h[k]) return SRT_ERR_LAYOUT;      // another table: create a new scene
             const size_t end = (size_t)d->tex_off[k] + (size_t)d->tex_w[k] * d->tex_h[k] * 3;
@@ -588,67 +696,19 @@ static int scene_update_impl(srt_scene* s, const srt_scene_desc* d, hipStream_t 
         tex_changed = tex_hash_new != r.tex_hash;
     }
     HIP_TRY(hipSetDevice(s->device));
-    const size_t nN = d->n_nodes, nT = d->n_tris, nO = d->n_objects, nW = wide_count(d->n_nodes, d->n_objects);
-    auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t o_nodes = 0, o_tris = o_nodes + pad(nN * sizeof(DevNode)), o_triso = o_tris + pad(nT * sizeof(DevTri)),
-                 o_triobj = o_triso + pad(nT * sizeof(DevTriO)), o_ranges = o_triobj + pad(nT * 4), o_first = o_ranges + pad(nO * sizeof(int2)),
-                 o_color = o_first + pad((nO + 1) * 4), o_mat = o_color + pad(nO * 12), o_nrm = o_mat + pad(nO * 12),
-                 o_tex = o_nrm + pad(d->tri_normals ? nT * 36 : 0), o_tc = o_tex + pad(any_tex ? nT * 4 : 0), o_wide = o_tc + pad(any_tex ? nT * 24 : 0),
-                 o_rinfo = o_wide + pad(nW * sizeof(DevWide)), o_widx = o_rinfo + pad(nO * 4), o_roots = o_widx + pad(nN * 4), o_ubox = o_roots + pad(nO * sizeof(DevNode)), o_img = o_ubox + pad(32),
-                 total = o_img + pad(tex_changed ? tex_total : 0);
-    if (s->stage_bytes < total) {
-        if (s->stage) { HIP_TRY(hipEventSynchronize(s->staged)); (void)hipHostFree(s->stage); s->stage = nullptr; s->stage_bytes = 0; }
-        HIP_TRY(hipHostMalloc(&s->stage, total, hipHostMallocDefault));
-        s->stage_bytes = total;
-        if (!s->staged) HIP_TRY(hipEventCreateWithFlags(&s->staged, hipEventDisableTiming));
-    } else {
-        HIP_TRY(hipEventSynchronize(s->staged));               // the previous update's copies have left the staging block
+    size_t stage_bytes = 0;
+    const RecordList l = record_list(s->dev, r, d, any_tex, tex_changed ? tex_total : 0, false, true, &stage_bytes);
+    char* h = nullptr;
+    SRT_TRY(stage_acquire(s, stage_bytes, &h));
+    SRT_TRY(derive_records(d, l, h));
+    for (const RecordArray& a : l) {
+        if (!a.bytes()) continue;
+        if (a.src) std::memcpy(h + a.off, a.src, a.bytes());
+        HIP_TRY(hipMemcpyAsync(*a.dev, h + a.off, a.bytes(), hipMemcpyHostToDevice, stream));
     }
-    char* h = (char*)s->stage;
-    DevNode* nodes = (DevNode*)(h + o_nodes); int2* ranges = (int2*)(h + o_ranges);
-    rc = build_device_records(d, nodes, ranges);
-    if (rc != SRT_OK) return rc;
-    build_wide_records(nodes, d->n_nodes, ranges, d->n_objects, (DevWide*)(h + o_wide), (int32_t*)(h + o_rinfo), (int32_t*)(h + o_widx));
-    for (uint32_t k = 0; k < d->n_objects; k++) ((DevNode*)(h + o_roots))[k] = nodes[ranges[k].x];
-    union_of_roots((const DevNode*)(h + o_roots), d->n_objects, (float*)(h + o_ubox));
-    if (tex_changed) std::memcpy(h + o_img, d->tex_rgb, tex_total);
-    derive_triangles(d, (DevTri*)(h + o_tris), (DevTriO*)(h + o_triso));
-    derive_tri_first(d, (int32_t*)(h + o_first));
-    std::memcpy(h + o_triobj, d->tri_obj, nT * 4);
-    std::memcpy(h + o_color, d->obj_color, nO * 12);
-    std::memcpy(h + o_mat, d->obj_material, nO * 12);
-    if (d->tri_normals) std::memcpy(h + o_nrm, d->tri_normals, nT * 36);
-    if (any_tex) { std::memcpy(h + o_tex, d->tri_tex, nT * 4); std::memcpy(h + o_tc, d->tri_texcoord, nT * 24); }
-    #define CP(dst, off, bytes) do { if (bytes) HIP_TRY(hipMemcpyAsync((void*)(dst), h + (off), (bytes), hipMemcpyHostToDevice, stream)); } while (0)
-    CP(s->dev.nodes, o_nodes, nN * sizeof(DevNode));
-    CP(s->dev.wide, o_wide, nW * sizeof(DevWide));
-    CP(s->dev.obj_root_info, o_rinfo, nO * 4);
-    CP(s->dev.root_nodes, o_roots, nO * sizeof(DevNode));
-    CP(s->dev.scene_box, o_ubox, 32);
-    if (tex_changed) { CP(s->dev.tex, o_img, tex_total); s->rec->tex_hash = tex_hash_new; }
-    CP(s->dev.tris, o_tris, nT * sizeof(DevTri));
-    CP(s->dev.tris_o, o_triso, nT * sizeof(DevTriO));
-    CP(s->dev.tri_obj, o_triobj, nT * 4);
-    CP(s->dev.obj_range, o_ranges, nO * sizeof(int2));
-    CP(s->dev.obj_tri_first, o_first, (nO + 1) * 4);
-    CP(s->dev.obj_color, o_color, nO * 12);
-    CP(s->dev.obj_mat, o_mat, nO * 12);
-    if (d->tri_normals) CP(s->dev.tri_normals, o_nrm, nT * 36);
-    if (any_tex) { CP(s->dev.tri_tex, o_tex, nT * 4); CP(s->dev.tri_tc, o_tc, nT * 24); }
-    #undef CP
     HIP_TRY(hipEventRecord(s->staged, stream));
-    s->rec->overlap = overlap_estimate(nodes, d->n_nodes, ranges, d->n_objects);
-    s->rec->prefer_packet = s->rec->overlap > PACKET_OVERLAP_THRESHOLD;
-    s->rec->int_shin = all_integer_shininess(d);
-    {   // the topology may differ from the previous contents' (same counts, other trees): refresh what srt_scene_update_frame relies on
-        SceneRecords& r = *s->rec;
-        for (uint32_t k = 0; k < d->n_objects; k++) r.h_ranges[k] = ranges[k];
-        derive_tri_first(d, r.h_tri_first.data());
-        for (uint32_t i = 0; i < d->n_nodes; i++) r.h_leaf[i] = nodes[i].leaf;
-        HIP_TRY(hipMemcpyAsync(r.d_widx, h + o_widx, nN * 4, hipMemcpyHostToDevice, stream));
-        r.have_source = false;                                  // attributes in source order belong to the previous contents
-        r.have_pose = false;                                    // ... and so do the pose source's order and the refit's schedule
-    }
+    if (tex_changed) r.tex_hash = tex_hash_new;
+    note_records(r, d, l, h);
     return SRT_OK;
 }
 
@@ -661,16 +721,8 @@ static int scene_set_source_impl(srt_scene* s, const float* tri_texcoord, const 
     if (s->dev.tri_normals && !tri_normals) return SRT_ERR_ARG;
     HIP_TRY(hipSetDevice(s->device));
     HIP_TRY(wait_idle(s));
-    auto put = [&](auto** dst, const auto* src, size_t n) -> int {
-        using T = std::remove_pointer_t<std::remove_pointer_t<decltype(dst)>>;
-        if (!*dst) { void* d = nullptr; HIP_TRY(hipMalloc(&d, sizeof(T) * (n ? n : 1))); r.allocs.push_back(d); *dst = (T*)d; s->bytes += sizeof(T) * n; }
-        if (n) HIP_TRY(hipMemcpy(*dst, src, sizeof(T) * n, hipMemcpyHostToDevice));
-        return SRT_OK;
-    };
-    int rc = SRT_OK;
-    if (s->has_tex) { rc = put(&r.d_src_tc, tri_texcoord, nT * 6); if (rc == SRT_OK) rc = put(&r.d_src_tex, tri_tex, nT); }
-    if (rc == SRT_OK && s->dev.tri_normals) rc = put(&r.d_src_nrm, tri_normals, nT * 9);
-    if (rc != SRT_OK) return rc;
+    if (s->has_tex) { SRT_TRY(lazy_array(s, &r.d_src_tc, nT * 24, tri_texcoord, nT * 24)); SRT_TRY(lazy_array(s, &r.d_src_tex, nT * 4, tri_tex, nT * 4)); }
+    if (s->dev.tri_normals) SRT_TRY(lazy_array(s, &r.d_src_nrm, nT * 36, tri_normals, nT * 36));
     r.have_source = true;
     return SRT_OK;
 }
@@ -690,28 +742,17 @@ static int scene_update_frame_impl(srt_scene* s, const srt_frame_geometry* g, hi
         if (!g->obj_node_min[k] || !g->obj_node_max[k]) return SRT_ERR_ARG;
     }
     if ((s->has_tex || s->dev.tri_normals) && !r.have_source) return SRT_ERR_ARG;       // attributes cannot be permuted without their source order
-    int rc;
-    if (!stream) { rc = own_stream(s, &stream); if (rc != SRT_OK) return rc; }
+    if (!stream) SRT_TRY(own_stream(s, &stream));
     HIP_TRY(hipSetDevice(s->device));
     const size_t nN = s->dev.n_nodes, nT = s->dev.n_tris;
-    if (!r.d_src_points) {        // the device side of the staging, once
-        auto make = [&](auto** dst, size_t bytes) -> int { if (*dst) return SRT_OK; void* d = nullptr; HIP_TRY(hipMalloc(&d, bytes ? bytes : 1)); r.allocs.push_back(d); *dst = (std::remove_pointer_t<decltype(dst)>)d; s->bytes += bytes; return SRT_OK; };
-        rc = make(&r.d_src_points, nT * 48); if (rc == SRT_OK) rc = make(&r.d_order, nT * 4);
-        if (rc == SRT_OK) rc = make(&r.d_box_min, nN * 12); if (rc == SRT_OK) rc = make(&r.d_box_max, nN * 12);
-        if (rc != SRT_OK) return rc;
-    }
+    // the device side of the staging, once
+    SRT_TRY(lazy_array(s, &r.d_src_points, nT * 48)); SRT_TRY(lazy_array(s, &r.d_order, nT * 4));
+    SRT_TRY(lazy_array(s, &r.d_box_min, nN * 12)); SRT_TRY(lazy_array(s, &r.d_box_max, nN * 12));
     auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
     const size_t o_pts = 0, o_ord = o_pts + pad(nT * 48), o_bmin = o_ord + pad(nT * 4), o_bmax = o_bmin + pad(nN * 12), o_col = o_bmax + pad(nN * 12),
                  o_mat = o_col + pad(nO * 12), o_ubox = o_mat + pad(nO * 12), total = o_ubox + pad(32);
-    if (s->stage_bytes < total) {
-        if (s->stage) { HIP_TRY(hipEventSynchronize(s->staged)); (void)hipHostFree(s->stage); s->stage = nullptr; s->stage_bytes = 0; }
-        HIP_TRY(hipHostMalloc(&s->stage, total, hipHostMallocDefault));
-        s->stage_bytes = total;
-        if (!s->staged) HIP_TRY(hipEventCreateWithFlags(&s->staged, hipEventDisableTiming));
-    } else {
-        HIP_TRY(hipEventSynchronize(s->staged));               // the previous update's copies have left the staging block
-    }
-    char* h = (char*)s->stage;
+    char* h = nullptr;
+    SRT_TRY(stage_acquire(s, total, &h));
     for (uint32_t k = 0; k < nO; k++) {
         const size_t t0 = (size_t)r.h_tri_first[k], nt = g->obj_n_tris[k], n0 = (size_t)r.h_ranges[k].x, nn = g->obj_n_nodes[k];
         if (nt) { std::memcpy(h + o_pts + t0 * 48, g->obj_points[k], nt * 48); std::memcpy(h + o_ord + t0 * 4, g->obj_order[k], nt * 4); }
@@ -720,23 +761,14 @@ static int scene_update_frame_impl(srt_scene* s, const srt_frame_geometry* g, hi
         for (size_t i = 0; i < nt; i += 4099) if (ord[i] >= nt) return SRT_ERR_LAYOUT;       // (spot check: an index outside the object would read another object's points)
     }
     #define CP(dst, off, bytes) do { if (bytes) HIP_TRY(hipMemcpyAsync((void*)(dst), h + (off), (bytes), hipMemcpyHostToDevice, stream)); } while (0)
-    {   // the union of this frame's root boxes
-        float* ub = (float*)(h + o_ubox);
-        float lo[3] = { FLT_MAX, FLT_MAX, FLT_MAX }, hi[3] = { -FLT_MAX, -FLT_MAX, -FLT_MAX };
-        for (uint32_t k = 0; k < nO; k++) {
-            const float* mn = (const float*)(h + o_bmin) + 3 * (size_t)r.h_ranges[k].x; const float* mx = (const float*)(h + o_bmax) + 3 * (size_t)r.h_ranges[k].x;
-            for (int a = 0; a < 3; a++) { if (mn[a] < lo[a]) lo[a] = mn[a]; if (mx[a] > hi[a]) hi[a] = mx[a]; }
-        }
-        ub[0] = lo[0]; ub[1] = lo[1]; ub[2] = lo[2]; ub[3] = hi[0]; ub[4] = hi[1]; ub[5] = hi[2]; ub[6] = 0.f; ub[7] = 0.f;
-    }
+    const Boxes boxes((const float*)(h + o_bmin), (const float*)(h + o_bmax));      // this frame's
+    union_of_roots(boxes, r.h_ranges.data(), nO, (float*)(h + o_ubox));
     CP(r.d_src_points, o_pts, nT * 48); CP(r.d_order, o_ord, nT * 4); CP(r.d_box_min, o_bmin, nN * 12); CP(r.d_box_max, o_bmax, nN * 12);
     CP(s->dev.scene_box, o_ubox, 32);
     if (g->obj_color) { std::memcpy(h + o_col, g->obj_color, nO * 12); CP(s->dev.obj_color, o_col, nO * 12); }
     if (g->obj_material) {
         std::memcpy(h + o_mat, g->obj_material, nO * 12); CP(s->dev.obj_mat, o_mat, nO * 12);
-        bool ish = true;
-        for (uint32_t k = 0; k < nO; k++) { const float sh = g->obj_material[3 * (size_t)k + 2]; ish = ish && sh >= 1.0f && sh <= 64.0f && sh == std::trunc(sh); }
-        r.int_shin = ish;
+        r.int_shin = all_integer_shininess(g->obj_material, nO);
     }
     #undef CP
     HIP_TRY(hipEventRecord(s->staged, stream));
@@ -751,25 +783,8 @@ static int scene_update_frame_impl(srt_scene* s, const srt_frame_geometry* g, hi
                        s->dev.nodes, const_cast<DevNode*>(s->dev.root_nodes));
     HIP_TRY(hipGetLastError());
     r.have_pose = false;                                        // another visit order: the pose source is no longer these triangles
-    // expected slab tests per ray from this frame's boxes (what overlap_estimate computes from the records)
-    {
-        const float* bmin = (const float*)(h + o_bmin); const float* bmax = (const float*)(h + o_bmax);
-        auto area = [](const float* a, const float* b) -> double {
-            const double x = (double)b[0] - a[0], y = (double)b[1] - a[1], z = (double)b[2] - a[2];
-            return (x < 0 || y < 0 || z < 0) ? 0. : x * y + y * z + z * x;
-        };
-        float lo[3] = { 3.0e38f, 3.0e38f, 3.0e38f }, hi[3] = { -3.0e38f, -3.0e38f, -3.0e38f };
-        for (uint32_t k = 0; k < nO; k++) {
-            const float* mn = bmin + 3 * (size_t)r.h_ranges[k].x; const float* mx = bmax + 3 * (size_t)r.h_ranges[k].x;
-            if (area(mn, mx) <= 0.) continue;
-            for (int a = 0; a < 3; a++) { lo[a] = mn[a] < lo[a] ? mn[a] : lo[a]; hi[a] = mx[a] > hi[a] ? mx[a] : hi[a]; }
-        }
-        const double tot = area(lo, hi);
-        double sum = 0.;
-        if (tot > 0.) for (size_t i = 0; i < nN; i++) if (r.h_leaf[i] < 0) sum += 2. * area(bmin + 3 * i, bmax + 3 * i);
-        r.overlap = tot > 0. ? (double)nO + sum / tot : 0.;
-        r.prefer_packet = r.overlap > PACKET_OVERLAP_THRESHOLD;
-    }
+    r.overlap = overlap_estimate(boxes, r.h_leaf.data(), (uint32_t)nN, r.h_ranges.data(), nO);      // expected slab tests per ray, from this frame's boxes
+    r.prefer_packet = r.overlap > PACKET_OVERLAP_THRESHOLD;
     return SRT_OK;
 }
 
@@ -803,21 +818,15 @@ static int scene_set_pose_source_impl(srt_scene* s, const float* tri_points) {
     top_off[nO] = (int32_t)top_nodes.size();
     HIP_TRY(hipSetDevice(s->device));
     HIP_TRY(hipDeviceSynchronize());
-    auto put = [&](auto** dst, const void* src, size_t cap_bytes, size_t bytes) -> int {
-        if (!*dst) { void* d = nullptr; HIP_TRY(hipMalloc(&d, cap_bytes ? cap_bytes : 1)); r.allocs.push_back(d); *dst = (std::remove_pointer_t<decltype(dst)>)d; s->bytes += cap_bytes; }
-        if (src && bytes) HIP_TRY(hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
-        return SRT_OK;
-    };
-    int rc = put(&r.d_pose_points, tri_points, nT * 48, nT * 48);
-    if (rc == SRT_OK) rc = put(&r.d_tri_box, nullptr, nT * 24, 0);
-    if (rc == SRT_OK) rc = put(&r.d_obj_matrix, nullptr, nO * 64, 0);
-    if (rc == SRT_OK) rc = put(&r.d_height, height.data(), nN, nN);
-    if (rc == SRT_OK) rc = put(&r.d_sub_root, sub_root.data(), nN * 4, sub_root.size() * 4);      // (capacities for any tree of these counts)
-    if (rc == SRT_OK) rc = put(&r.d_top_nodes, top_nodes.data(), nN * 4, top_nodes.size() * 4);
-    if (rc == SRT_OK) rc = put(&r.d_top_off, top_off.data(), (nO + 1) * 4, (nO + 1) * 4);
-    if (rc == SRT_OK) rc = put(&r.d_box_min, nullptr, nN * 12, 0);
-    if (rc == SRT_OK) rc = put(&r.d_box_max, nullptr, nN * 12, 0);
-    if (rc != SRT_OK) return rc;
+    SRT_TRY(lazy_array(s, &r.d_pose_points, nT * 48, tri_points, nT * 48));
+    SRT_TRY(lazy_array(s, &r.d_tri_box, nT * 24));
+    SRT_TRY(lazy_array(s, &r.d_obj_matrix, nO * 64));
+    SRT_TRY(lazy_array(s, &r.d_height, nN, height.data(), nN));
+    SRT_TRY(lazy_array(s, &r.d_sub_root, nN * 4, sub_root.data(), sub_root.size() * 4));      // (capacities for any tree of these counts)
+    SRT_TRY(lazy_array(s, &r.d_top_nodes, nN * 4, top_nodes.data(), top_nodes.size() * 4));
+    SRT_TRY(lazy_array(s, &r.d_top_off, (nO + 1) * 4, top_off.data(), (nO + 1) * 4));
+    SRT_TRY(lazy_array(s, &r.d_box_min, nN * 12));
+    SRT_TRY(lazy_array(s, &r.d_box_max, nN * 12));
     r.n_sub = (uint32_t)sub_root.size();
     r.have_pose = true;
     return SRT_OK;
@@ -835,32 +844,19 @@ static int scene_pose_impl(srt_scene* s, uint32_t n_objects, const float* obj_ma
     if (!r.have_pose) return SRT_ERR_ARG;
     const uint32_t nO = s->dev.n_objects;
     if (n_objects != nO) return SRT_ERR_LAYOUT;
-    int rc;
-    if (!stream) { rc = own_stream(s, &stream); if (rc != SRT_OK) return rc; }
+    if (!stream) SRT_TRY(own_stream(s, &stream));
     HIP_TRY(hipSetDevice(s->device));
     const size_t nN = s->dev.n_nodes, nT = s->dev.n_tris;
     auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
     const size_t o_mtx = 0, o_col = o_mtx + pad((size_t)nO * 64), o_mat = o_col + pad((size_t)nO * 12), total = o_mat + pad((size_t)nO * 12);
-    if (s->stage_bytes < total) {
-        if (s->stage) { HIP_TRY(hipEventSynchronize(s->staged)); (void)hipHostFree(s->stage); s->stage = nullptr; s->stage_bytes = 0; }
-        HIP_TRY(hipHostMalloc(&s->stage, total, hipHostMallocDefault));
-        s->stage_bytes = total;
-        if (!s->staged) HIP_TRY(hipEventCreateWithFlags(&s->staged, hipEventDisableTiming));
-    } else {
-        HIP_TRY(hipEventSynchronize(s->staged));               // the previous copies have left the staging block
-    }
-    char* h = (char*)s->stage;
-    // every copy out of the staging block is enqueued before the event that guards the block is recorded
+    char* h = nullptr;
+    SRT_TRY(stage_acquire(s, total, &h));
     std::memcpy(h + o_mtx, obj_matrix, (size_t)nO * 64);
     HIP_TRY(hipMemcpyAsync(r.d_obj_matrix, h + o_mtx, (size_t)nO * 64, hipMemcpyHostToDevice, stream));
     if (obj_color) { std::memcpy(h + o_col, obj_color, (size_t)nO * 12); HIP_TRY(hipMemcpyAsync((void*)s->dev.obj_color, h + o_col, (size_t)nO * 12, hipMemcpyHostToDevice, stream)); }
     if (obj_material) { std::memcpy(h + o_mat, obj_material, (size_t)nO * 12); HIP_TRY(hipMemcpyAsync((void*)s->dev.obj_mat, h + o_mat, (size_t)nO * 12, hipMemcpyHostToDevice, stream)); }
     HIP_TRY(hipEventRecord(s->staged, stream));
-    if (obj_material) {
-        bool ish = true;
-        for (uint32_t k = 0; k < nO; k++) { const float sh = obj_material[3 * (size_t)k + 2]; ish = ish && sh >= 1.0f && sh <= 64.0f && sh == std::trunc(sh); }
-        r.int_shin = ish;
-    }
+    if (obj_material) r.int_shin = all_integer_shininess(obj_material, nO);
     if (nT) hipLaunchKernelGGL(k_pose_tris, dim3((uint32_t)((nT + 255) / 256)), dim3(256), 0, stream, (uint32_t)nT, s->dev.tri_obj, (const float*)r.d_obj_matrix,
                                (const float4*)r.d_pose_points, const_cast<DevTri*>(s->dev.tris), const_cast<DevTriO*>(s->dev.tris_o), r.d_tri_box);
     hipLaunchKernelGGL(k_pose_boxes, dim3(r.n_sub), dim3(128), 0, stream, (const int32_t*)r.d_sub_root, s->dev.nodes, (const uint8_t*)r.d_height,
@@ -954,25 +950,12 @@ static int render_device_impl(srt_scene* s, const srt_params* p, void* stream_, 
     s->last.primary_rays = pixels_owned(p);
     const size_t pixels = (size_t)wl * rows;
     // workspace for hit ids / t when the caller does not want them (the shade kernel does)
-    if ((!d_hit_id || !d_t) && s->ws_pixels < pixels) {
-        HIP_TRY(wait_idle(s));
-        if (s->ws_hit) (void)hipFree(s->ws_hit);
-        if (s->ws_t) (void)hipFree(s->ws_t);
-        s->ws_hit = nullptr; s->ws_t = nullptr; s->ws_pixels = 0;
-        HIP_TRY(hipMalloc((void**)&s->ws_hit, pixels * sizeof(int32_t)));
-        HIP_TRY(hipMalloc((void**)&s->ws_t, pixels * sizeof(float)));
-        s->ws_pixels = pixels;
-    }
+    if (!d_hit_id || !d_t) SRT_TRY(grow(s, pixels, s->ws_hit, s->ws_t));
     if (!d_hit_id) d_hit_id = s->ws_hit;
     if (!d_t) d_t = s->ws_t;
-    if (p->n_lights > s->lights_cap) {
-        HIP_TRY(wait_idle(s));
-        if (s->d_lights) (void)hipFree(s->d_lights);
-        if (s->h_lights) (void)hipHostFree(s->h_lights);
-        s->d_lights = nullptr; s->h_lights = nullptr; s->lights_cap = 0;
-        HIP_TRY(hipMalloc((void**)&s->d_lights, (size_t)p->n_lights * 3 * sizeof(float)));
-        HIP_TRY(hipHostMalloc((void**)&s->h_lights, (size_t)p->n_lights * 3 * sizeof(float), hipHostMallocDefault));
-        s->lights_cap = p->n_lights; s->lights_valid = 0;
+    if (p->n_lights > s->d_lights.cap || p->n_lights > s->h_lights.cap) {
+        s->lights_valid = 0;               // new buffers: nothing of the old contents is on the device
+        SRT_TRY(grow(s, p->n_lights, s->d_lights, s->h_lights));
     }
     const size_t light_bytes = (size_t)p->n_lights * 3 * sizeof(float);
     if (p->n_lights && !(s->lights_valid == p->n_lights && std::memcmp(s->h_lights, p->light_pos, light_bytes) == 0)) {
@@ -1032,37 +1015,18 @@ static int render_device_impl(srt_scene* s, const srt_params* p, void* stream_, 
     // samples, packet shadow kernel): room for either
     const size_t words_tile = (size_t)grid8.x * grid8.y * (p->n_lights ? p->n_lights : 1), words_px = pixels * ((p->n_lights + 63) / 64);
     const size_t shadow_words = words_tile > words_px ? words_tile : words_px;
-    if (variant != 1 && s->ws_shadow_words < shadow_words) {
-        HIP_TRY(wait_idle(s));
-        if (s->ws_shadow) (void)hipFree(s->ws_shadow);
-        s->ws_shadow = nullptr; s->ws_shadow_words = 0;
-        HIP_TRY(hipMalloc((void**)&s->ws_shadow, shadow_words * sizeof(unsigned long long)));
-        s->ws_shadow_words = shadow_words;
-    }
+    if (variant != 1) SRT_TRY(grow(s, shadow_words, s->ws_shadow));
     const size_t n_tiles = (size_t)grid8.x * grid8.y;
     const uint32_t qcap_need = (uint32_t)((n_tiles + QL_SHARDS - 1) / QL_SHARDS) * 4u;      // a shard gets every 64th tile, four quadrants each
     if (variant != 1 && s->qcap < qcap_need) {
-        HIP_TRY(wait_idle(s));
-        if (s->ws_qlist) (void)hipFree(s->ws_qlist);
-        s->ws_qlist = nullptr; s->qcap = 0;
-        // two words per entry, and behind the lists one word per quadrant: the cost map the shadow kernel leaves for the next frame's list
-        HIP_TRY(hipMalloc((void**)&s->ws_qlist, (size_t)QL_SHARDS * qcap_need * 3 * sizeof(uint32_t)));
+        // per shard entry three words: two for the entry, and behind the lists one word per quadrant, the cost map the shadow kernel leaves
+        // for the next frame's list -- which starts empty
+        s->qcap = 0;
+        SRT_TRY(grow(s, (size_t)QL_SHARDS * qcap_need, s->ws_qlist));
         HIP_TRY(hipMemset(s->ws_qlist + (size_t)QL_SHARDS * qcap_need * 2, 0, (size_t)QL_SHARDS * qcap_need * sizeof(uint32_t)));
         s->qcap = qcap_need;
     }
-    if (spp > 1 && s->ws_acc_pixels < pixels) {                    // supersampling extension: accumulation buffers
-        HIP_TRY(wait_idle(s));
-        if (s->ws_acc) (void)hipFree(s->ws_acc);
-        if (s->ws_sub) (void)hipFree(s->ws_sub);
-        if (s->ws_sub_hit) (void)hipFree(s->ws_sub_hit);
-        if (s->ws_sub_t) (void)hipFree(s->ws_sub_t);
-        s->ws_acc = nullptr; s->ws_sub = nullptr; s->ws_sub_hit = nullptr; s->ws_sub_t = nullptr; s->ws_acc_pixels = 0;
-        HIP_TRY(hipMalloc((void**)&s->ws_acc, pixels * 3 * sizeof(float)));
-        HIP_TRY(hipMalloc((void**)&s->ws_sub, pixels * 3 * sizeof(float)));
-        HIP_TRY(hipMalloc((void**)&s->ws_sub_hit, pixels * sizeof(int32_t)));
-        HIP_TRY(hipMalloc((void**)&s->ws_sub_t, pixels * sizeof(float)));
-        s->ws_acc_pixels = pixels;
-    }
+    if (spp > 1) SRT_TRY(grow(s, pixels, s->ws_acc, s->ws_sub, s->ws_sub_hit, s->ws_sub_t));      // supersampling extension: accumulation buffers
 
     // One pass of the path over this call's pixels: closest hit (+ shadow rays) and shading.
     auto launch_frame = [&](const DevParams& fp_in, int32_t* o_hit, float* o_t, float* o_lin, uint8_t* o_rgb8,
@@ -1395,13 +1359,6 @@ int srt_sync(srt_scene* s, srt_stats* stats) {
     return SRT_OK;
 }
 
-// The scene's own stream: srt_render / srt_render_async / srt_scene_update(stream = NULL) are ordered on it.
-static int own_stream(srt_scene* s, hipStream_t* out) {
-    if (!s->stream) HIP_TRY(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
-    *out = s->stream;
-    return SRT_OK;
-}
-
 static int render_async_impl(srt_scene* s, const srt_params* p, int32_t* hit_id, float* t, float* rgb_linear, uint8_t* rgb8, bool wait, srt_stats* stats) {
     if (!s) return SRT_ERR_ARG;
     int rc = check_params(p);
@@ -1412,15 +1369,7 @@ static int render_async_impl(srt_scene* s, const srt_params* p, int32_t* hit_id,
     if (rc != SRT_OK) return rc;
     const uint32_t rows = srt_rows_owned(p);
     const size_t pixels = (size_t)srt_cols_owned(p) * rows;
-    if (pixels > s->ws_out_pixels) {
-        HIP_TRY(wait_idle(s));
-        if (s->ws_lin) (void)hipFree(s->ws_lin);
-        if (s->ws_rgb8) (void)hipFree(s->ws_rgb8);
-        s->ws_lin = nullptr; s->ws_rgb8 = nullptr; s->ws_out_pixels = 0;
-        HIP_TRY(hipMalloc((void**)&s->ws_lin, pixels * 3 * sizeof(float)));
-        HIP_TRY(hipMalloc((void**)&s->ws_rgb8, pixels * 3));
-        s->ws_out_pixels = pixels;
-    }
+    SRT_TRY(grow(s, pixels, s->ws_lin, s->ws_rgb8));
     rc = render_device_impl(s, p, st, nullptr, nullptr, rgb_linear ? s->ws_lin : nullptr, rgb8 ? s->ws_rgb8 : nullptr);
     if (rc != SRT_OK) return rc;
     if (wait) {        // srt_render: the caller's buffers are ordinary (pageable) memory as a rule, where a synchronous copy is the fast one
@@ -1460,27 +1409,24 @@ void srt_host_free(void* p) { if (p) (void)hipHostFree(p); }
 
 // ---- known-answer entry points (device leaf functions on caller vectors; host pointers in and out) ----
 namespace {
-struct DevBuf {
-    void* p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    int alloc(size_t bytes) { hipError_t e = hipMalloc(&p, bytes ? bytes : 1); if (e != hipSuccess) { g_last_hip = (int)e; return SRT_ERR_DEVICE; } return SRT_OK; }
-    int up(const void* h, size_t bytes) { int rc = alloc(bytes); if (rc) return rc; HIP_TRY(hipMemcpy(p, h, bytes, hipMemcpyHostToDevice)); return SRT_OK; }
+struct DevBuf : DevArray<char> {
+    int alloc(size_t bytes) { HIP_TRY(reserve(bytes ? bytes : 1)); return SRT_OK; }
+    int up(const void* h, size_t bytes) { SRT_TRY(alloc(bytes)); HIP_TRY(hipMemcpy(p, h, bytes, hipMemcpyHostToDevice)); return SRT_OK; }
     int down(void* h, size_t bytes) { HIP_TRY(hipMemcpy(h, p, bytes, hipMemcpyDeviceToHost)); return SRT_OK; }
 };
 }
-#define KAT_TRY(expr) do { int rc_ = (expr); if (rc_ != SRT_OK) return rc_; } while (0)
 
 int srt_kat_ray_aabb(int device, uint32_t n, const float* ray_od, const float* box, uint8_t* exact, uint8_t* branchless,
                      uint8_t* filtered, uint8_t* ambiguous) {
     if (!n || !ray_od || !box || !exact || !branchless || !filtered || !ambiguous) return SRT_ERR_ARG;
     HIP_TRY(hipSetDevice(device));
     DevBuf r, b, o0, o1, o2, o3;
-    KAT_TRY(r.up(ray_od, (size_t)n * 24)); KAT_TRY(b.up(box, (size_t)n * 24));
-    KAT_TRY(o0.alloc(n)); KAT_TRY(o1.alloc(n)); KAT_TRY(o2.alloc(n)); KAT_TRY(o3.alloc(n));
+    SRT_TRY(r.up(ray_od, (size_t)n * 24)); SRT_TRY(b.up(box, (size_t)n * 24));
+    SRT_TRY(o0.alloc(n)); SRT_TRY(o1.alloc(n)); SRT_TRY(o2.alloc(n)); SRT_TRY(o3.alloc(n));
     hipLaunchKernelGGL(k_kat_ray_aabb, dim3((n + 255) / 256), dim3(256), 0, 0, n, (const float*)r.p, (const float*)b.p,
                        (uint8_t*)o0.p, (uint8_t*)o1.p, (uint8_t*)o2.p, (uint8_t*)o3.p);
     HIP_TRY(hipGetLastError()); HIP_TRY(hipDeviceSynchronize());
-    KAT_TRY(o0.down(exact, n)); KAT_TRY(o1.down(branchless, n)); KAT_TRY(o2.down(filtered, n)); KAT_TRY(o3.down(ambiguous, n));
+    SRT_TRY(o0.down(exact, n)); SRT_TRY(o1.down(branchless, n)); SRT_TRY(o2.down(filtered, n)); SRT_TRY(o3.down(ambiguous, n));
     return SRT_OK;
 }
 
@@ -1491,7 +1437,7 @@ int srt_kat_ray_triangle(int device, uint32_t n, const float* ray_od, const floa
     std::vector<DevTri> tris(n);
     for (uint32_t i = 0; i < n; i++) tris[i] = derive_triangle(tri_points + 12 * (size_t)i);
     DevBuf r, q, o;
-    KAT_TRY(r.up(ray_od, (size_t)n * 24)); KAT_TRY(q.up(tris.data(), (size_t)n * sizeof(DevTri))); KAT_TRY(o.alloc((size_t)n * 4));
+    SRT_TRY(r.up(ray_od, (size_t)n * 24)); SRT_TRY(q.up(tris.data(), (size_t)n * sizeof(DevTri))); SRT_TRY(o.alloc((size_t)n * 4));
     hipLaunchKernelGGL(k_kat_ray_triangle, dim3((n + 255) / 256), dim3(256), 0, 0, n, (const float*)r.p, (const DevTri*)q.p, (float*)o.p);
     HIP_TRY(hipGetLastError()); HIP_TRY(hipDeviceSynchronize());
     return o.down(t, (size_t)n * 4);
@@ -1505,7 +1451,7 @@ int srt_kat_ray_triangle_origin(int device, uint32_t n, const float* dir, const 
     std::vector<DevTriO> tris_o(n);           // both records as srt_scene_create derives them
     for (uint32_t i = 0; i < n; i++) tris_o[i] = derive_triangle_origin(derive_triangle(tri_points + 12 * (size_t)i));
     DevBuf r, q, o;
-    KAT_TRY(r.up(dir, (size_t)n * 12)); KAT_TRY(q.up(tris_o.data(), (size_t)n * sizeof(DevTriO))); KAT_TRY(o.alloc((size_t)n * 4));
+    SRT_TRY(r.up(dir, (size_t)n * 12)); SRT_TRY(q.up(tris_o.data(), (size_t)n * sizeof(DevTriO))); SRT_TRY(o.alloc((size_t)n * 4));
     hipLaunchKernelGGL(k_kat_ray_triangle_origin, dim3((n + 255) / 256), dim3(256), 0, 0, n, (const float*)r.p, (const DevTriO*)q.p, (float*)o.p);
     HIP_TRY(hipGetLastError()); HIP_TRY(hipDeviceSynchronize());
     return o.down(t, (size_t)n * 4);
@@ -1519,7 +1465,7 @@ int srt_kat_barycentric(int device, uint32_t n, const float* in15, float* out3) 
     std::vector<DevTri> tris(n);
     for (uint32_t i = 0; i < n; i++) tris[i] = derive_triangle(in15 + 15 * (size_t)i);
     DevBuf a, q, o;
-    KAT_TRY(a.up(in15, (size_t)n * 60)); KAT_TRY(q.up(tris.data(), (size_t)n * sizeof(DevTri))); KAT_TRY(o.alloc((size_t)n * 12));
+    SRT_TRY(a.up(in15, (size_t)n * 60)); SRT_TRY(q.up(tris.data(), (size_t)n * sizeof(DevTri))); SRT_TRY(o.alloc((size_t)n * 12));
     hipLaunchKernelGGL(k_kat_barycentric, dim3((n + 255) / 256), dim3(256), 0, 0, n, (const float*)a.p, (const DevTri*)q.p, (float*)o.p);
     HIP_TRY(hipGetLastError()); HIP_TRY(hipDeviceSynchronize());
     return o.down(out3, (size_t)n * 12);
@@ -1533,7 +1479,7 @@ int srt_kat_phong(int device, uint32_t n, const float* in28, float* rgb) {
     std::vector<DevTri> tris(n);
     for (uint32_t i = 0; i < n; i++) tris[i] = derive_triangle(in28 + 28 * (size_t)i + 6);
     DevBuf a, q, o;
-    KAT_TRY(a.up(in28, (size_t)n * 28 * 4)); KAT_TRY(q.up(tris.data(), (size_t)n * sizeof(DevTri))); KAT_TRY(o.alloc((size_t)n * 12));
+    SRT_TRY(a.up(in28, (size_t)n * 28 * 4)); SRT_TRY(q.up(tris.data(), (size_t)n * sizeof(DevTri))); SRT_TRY(o.alloc((size_t)n * 12));
     hipLaunchKernelGGL(k_kat_phong, dim3((n + 255) / 256), dim3(256), 0, 0, n, (const float*)a.p, (const DevTri*)q.p, (float*)o.p);
     HIP_TRY(hipGetLastError()); HIP_TRY(hipDeviceSynchronize());
     return o.down(rgb, (size_t)n * 12);
@@ -1544,7 +1490,7 @@ int srt_kat_interp_normal(int device, uint32_t n, const float* in12, float* out3
     if (!n || !in12 || !out3) return SRT_ERR_ARG;
     HIP_TRY(hipSetDevice(device));
     DevBuf a, o;
-    KAT_TRY(a.up(in12, (size_t)n * 48)); KAT_TRY(o.alloc((size_t)n * 12));
+    SRT_TRY(a.up(in12, (size_t)n * 48)); SRT_TRY(o.alloc((size_t)n * 12));
     hipLaunchKernelGGL(k_kat_interp_normal, dim3((n + 255) / 256), dim3(256), 0, 0, n, (const float*)a.p, (float*)o.p);
     HIP_TRY(hipGetLastError()); HIP_TRY(hipDeviceSynchronize());
     return o.down(out3, (size_t)n * 12);
@@ -1554,10 +1500,10 @@ int srt_kat_pow(int device, uint32_t n, const float* x, const float* y, float* f
     if (!n || !x || !y || !fast || !lib) return SRT_ERR_ARG;
     HIP_TRY(hipSetDevice(device));
     DevBuf a, b, o, o2;
-    KAT_TRY(a.up(x, (size_t)n * 4)); KAT_TRY(b.up(y, (size_t)n * 4)); KAT_TRY(o.alloc((size_t)n * 4)); KAT_TRY(o2.alloc((size_t)n * 4));
+    SRT_TRY(a.up(x, (size_t)n * 4)); SRT_TRY(b.up(y, (size_t)n * 4)); SRT_TRY(o.alloc((size_t)n * 4)); SRT_TRY(o2.alloc((size_t)n * 4));
     hipLaunchKernelGGL(k_kat_pow, dim3((n + 255) / 256), dim3(256), 0, 0, n, (const float*)a.p, (const float*)b.p, (float*)o.p, (float*)o2.p);
     HIP_TRY(hipGetLastError()); HIP_TRY(hipDeviceSynchronize());
-    KAT_TRY(o.down(fast, (size_t)n * 4));
+    SRT_TRY(o.down(fast, (size_t)n * 4));
     return o2.down(lib, (size_t)n * 4);
 }
 
@@ -1575,7 +1521,7 @@ int srt_debug_valu_rate(int device, uint32_t iters, double* out) {
     const uint32_t n_cu = prop.multiProcessorCount > 0 ? (uint32_t)prop.multiProcessorCount : 256u;
     const uint32_t wgs = n_cu * 8u;                            // 8 workgroups of 4 waves per CU = 8 waves per SIMD, all resident
     DevBuf sink, st;
-    KAT_TRY(sink.alloc((size_t)wgs * 256 * 4)); KAT_TRY(st.alloc((size_t)wgs * 4 * 8 * 8));
+    SRT_TRY(sink.alloc((size_t)wgs * 256 * 4)); SRT_TRY(st.alloc((size_t)wgs * 4 * 8 * 8));
     for (int rep = 0; rep < 2; rep++) {                        // the first launch warms the clock
         static const bool packed = std::getenv("SRT_VALU_PACKED") != nullptr;        // measure v_pk_fma_f32 instead (same instruction count)
         if (packed) hipLaunchKernelGGL(k_valu_rate<true>, dim3(wgs), dim3(256), 0, 0, iters, (float*)sink.p, (unsigned long long*)st.p);
@@ -1583,7 +1529,7 @@ int srt_debug_valu_rate(int device, uint32_t iters, double* out) {
         HIP_TRY(hipGetLastError()); HIP_TRY(hipDeviceSynchronize());
     }
     std::vector<unsigned long long> h((size_t)wgs * 32);
-    KAT_TRY(st.down(h.data(), h.size() * 8));
+    SRT_TRY(st.down(h.data(), h.size() * 8));
     const size_t nw = (size_t)wgs * 4;
     std::vector<double> clk(nw);
     unsigned long long rmin = ~0ull, rmax = 0;
@@ -1616,10 +1562,10 @@ int srt_kat_tonemap(int device, uint32_t n, const float* lin, float reinhard, fl
     if (!n || !lin || !tone || !q) return SRT_ERR_ARG;
     HIP_TRY(hipSetDevice(device));
     DevBuf a, o, o2;
-    KAT_TRY(a.up(lin, (size_t)n * 12)); KAT_TRY(o.alloc((size_t)n * 12)); KAT_TRY(o2.alloc((size_t)n * 12));
+    SRT_TRY(a.up(lin, (size_t)n * 12)); SRT_TRY(o.alloc((size_t)n * 12)); SRT_TRY(o2.alloc((size_t)n * 12));
     hipLaunchKernelGGL(k_kat_tonemap, dim3((3 * n + 255) / 256), dim3(256), 0, 0, n, (const float*)a.p, reinhard, gamma, (float*)o.p, (int32_t*)o2.p);
     HIP_TRY(hipGetLastError()); HIP_TRY(hipDeviceSynchronize());
-    KAT_TRY(o.down(tone, (size_t)n * 12));
+    SRT_TRY(o.down(tone, (size_t)n * 12));
     return o2.down(q, (size_t)n * 12);
 }
 
