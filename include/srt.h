@@ -133,7 +133,8 @@ typedef struct srt_params {
                                     * once; hit_id / t report sub-sample 0                            */
     uint32_t flags;                /* SRT_FLAG_* in bits 0..7; bits 8..15: kernel-variant selector for A/B measurements and
                                     * the parity tests (0 = the shipped pipeline; the others compute the same results with
-                                    * older or differently configured kernels, DESIGN.md s5 lists them)                  */
+                                    * older or differently configured kernels; `enum Variant` in
+                                    * simple_raytracer_amd/csrc/srt_hip.hip is the list of the numbers)                  */
 } srt_params;
 
 typedef struct srt_stats {
@@ -273,13 +274,17 @@ int srt_render_device(srt_scene* s, const srt_params* p, void* stream,
 /* The frames of a step (the reference's main() renders a 36-frame orbit, simple_raytracer.cpp:534) in ONE set of launches:
  * frame i = srt_render_device(scenes[i], &params[i], stream, d_hit_id[i], ...), with bitwise the same outputs.  The handles must
  * be n DISTINCT handles on one device (a handle's workspace serves one frame at a time; srt_scene_share gives n handles on one
- * copy of a scene); each output table may be NULL, and so may its entries.  Frames that take the default pipeline at one common
- * size share the launches -- those with 1..7 light samples one pair of launches, those with 8 and more three -- which fills the
- * chip where one frame, or the eighth of it one of eight GPUs owns, does not (a silhouette tile occupies its workgroup for the
- * better part of such a launch); any other frame is launched on its own as srt_render_device would.  The frames' arguments travel
+ * copy of a scene); each output table may be NULL, and so may its entries.  Frames of two classes are held back and share launches,
+ * which fills the chip where one frame, or the eighth of it one of eight GPUs owns, does not (a silhouette tile occupies its
+ * workgroup for the better part of such a launch).  Both classes: variant 0, one common size, spp 1, no SRT_FLAG_COUNT_WORK, no camera
+ * matrix, a scene without the packet preference (srt_scene_overlap_estimate <= 150).  Class one, a pair of launches: 1..7 light
+ * samples, records of at most 32 MiB.  Class two, three launches: the frames whose shadow rays take the packet kernel -- 16 and more
+ * samples, or 8..15 on a scene whose estimate is 14 or more.  Any other frame is launched on its own as srt_render_device would:
+ * among them 8..15 samples on a scene of few nodes (estimate < 14), which take the chunked node-queue shadow launch.  srt_scene_pipeline
+ * says "(batched)" for a held frame.  The frames' arguments travel
  * by value with the launches (up to 36 frames a launch, more frames = more launches): nothing is allocated or copied, and the call
  * may be captured into a hipGraph like any other (ABI version 3; earlier versions kept argument tables in device memory and could not
- * make one while capturing).  Frames with 16 and more light samples: the shadow-ray launch of a call remembers which 4x4-pixel
+ * make one while capturing).  Frames of class two: the shadow-ray launch of a call remembers which 4x4-pixel
  * quadrants had long walks and the next call on the same handles deals those early -- order only, results do not depend on it
  * (SRT_HEAVY_STEPS=0 in the environment turns it off; single frames without SRT_FLAG_FRAMES_IN_FLIGHT do the same).  No per-frame times: srt_sync()'s ms_* keep the values of the last timed
  * render of each handle. */

@@ -906,11 +906,99 @@ uint64_t srt_scene_device_bytes(const srt_scene* s) { return s ? s->bytes : 0; }
 const char* srt_scene_pipeline(const srt_scene* s) { return s ? s->pipeline : ""; }
 double srt_scene_overlap_estimate(const srt_scene* s) { return s ? s->rec->overlap : 0.; }
 
+// ---- which kernels a frame runs ---------------------------------------------------------------------------------------------
+// srt_params.flags bits 8..15 select a kernel variant.  This is the list of the numbers (include/srt.h and DESIGN.md s5 point here): 0 is
+// what ships, every other number computes the same frame with older or differently configured kernels -- the independent
+// implementations the parity tests pin the shipped kernels with, and the A/B measurements of DESIGN.md s5.
+enum Variant : uint32_t {
+    V_SHIPPED = 0,                // the pipeline plan_frame picks per scene and light-sample count
+    V_REFERENCE = 1,              // the first kernels: a ray per lane with an inline triangle loop, per-pixel shading (no workspaces, no smooth normals)
+    V_TRI_QUEUE = 2,              // a ray per lane with a wave triangle queue, then the node-queue shadow kernel
+    V_NQ_TINY = 3,                // unfused node-queue kernels, 160-entry queue and exact divides: the stackless overflow walk
+    V_NQ_EXACT = 4,               // unfused node-queue kernels, shipped geometry with exact divides only
+    V_NQ_8X4 = 5,                 // unfused, 8x4 pixels per wave and a 1024-entry queue (tile-size experiment)
+    V_NQ_TINY_FILTER = 6,         // unfused, 160-entry queue with the filtered slab test: the overflow walk as shipped
+    V_UNFUSED = 10,               // the shipped node-queue kernels unfused (closest hit, then shadow)
+    V_FUSED_5_WAVES = 11,         // the fused kernel built for 5 waves per SIMD
+    V_FUSED_ROOTS_AGAIN = 12,     // the fused kernel with the roots re-tested by every wave (round-1 form)
+    V_FUSED_64_RAYS = 17,         // the fused kernel with 64 shadow rays in flight per wave
+    V_XCD_ROWS = 18,              // whole tile rows dealt to XCDs (what records beyond 32 MiB get), forced
+    V_CHUNKED = 20,               // never fused; 8+ samples: node-queue shadow kernel, samples cut into chunks over blockIdx.z (round-1 form)
+    V_NQ_PK = 21,                 // node-queue closest hit + packet shadow kernel at any sample count
+    V_PK_PK = 22,                 // packet closest hit + packet shadow kernel
+    V_PK_NQ = 23,                 // packet closest hit + node-queue shadow kernel
+    V_NO_PACKET = 24,             // the shipped choice for a scene WITHOUT the packet preference (A/B on soups)
+    V_PK_WINDOWS = 25,            // shipped choice, the packet shadow kernel reading its records through LDS windows
+    V_COARSE_GRID = 27,           // shipped choice, 2 x 2 tiles per workgroup in the unfused closest-hit launch
+    V_TRACE_SHADE = 28,           // the fused kernel shades its tiles itself: the frame in one launch (below 64 samples, no XCD rows)
+    V_PK_ENTRY_ORDER = 29,        // shipped choice, the packet shadow kernel's units in entry order
+    V_CAMERA_PK = 35,             // shipped choice, camera mode on the packet closest-hit kernel at every sample count
+    V_ROUND2_FORM = 40,           // shipped choice, the round-2 form everywhere: 32 B node records, queue pushes in lane order
+    V_ALL_WIDE = 41,              // shipped choice, 64 B node records in every node-queue kernel
+    V_ALL_NARROW = 42,            // shipped choice, 32 B node records in every node-queue kernel
+    V_LANE_ORDER = 43,            // shipped choice, queue pushes in lane order
+    V_GENERAL_SHADE = 44,         // shipped choice, the general shading kernel where the integer-shininess one would run
+    V_ROOT_LOOP = 45,             // shipped choice, a tile's root tests by the round-2 loop of dependent loads
+    V_NO_UNION_BOX = 46,          // shipped choice, without the test against the union of the root boxes
+    V_WIDE_STEP_COUNTERS = 47,    // shipped choice, diagnostic counters of the wide shadow kernel's steps
+    V_HIT_6_WAVES = 53,           // shipped choice, the unfused closest-hit kernel without the 7-wave bound
+    V_FUSED_6_WAVES = 54,         // shipped choice, the fused kernel built for 6 waves per SIMD
+    V_PK_AHEAD = 55,              // shipped choice, packet shadow walk with the record of i + 1 requested ahead
+    V_PK_AHEAD_SKIP = 56,         // shipped choice, ... and skip[i] / the leaf's first triangle
+    V_PK_PLAIN = 57,              // shipped choice, the plain packet shadow walk under a number (never the heavy lists)
+    V_PK_CLOCKS = 58,             // shipped choice, the plain walk with per-wave clock stamps (SRT_DIAG_COUNTERS)
+    V_SHADOW_PLAIN_ROWS = 62,     // shipped choice, the node-queue shadow kernel in plain tile order where XCD rows are on
+};
+// Numbers without a name keep two fallbacks: 7..9 run the unfused node-queue chain of the shipped kernels, any other number a
+// configuration of the fused kernel (the shipped one) at every sample count.
 static inline uint32_t variant_of(const srt_params* p) { return (p->flags >> 8) & 0xffu; }
+// These run the pipeline the dispatcher picks for 0.  They are NOT 0 for what only the shipped frame gets: the batch hold-back, the
+// chunked launch for scenes of few nodes, the heavy-quadrant lists and the camera build of the fused kernel.  28 is deliberately not
+// among them: it is a configuration of the fused kernel (fused_config in plan_frame) and takes the fused launch at every sample count.
+static inline bool shipped_choice(uint32_t v) {
+    return v == V_SHIPPED || v == V_NO_PACKET || v == V_PK_WINDOWS || v == V_COARSE_GRID || v == V_PK_ENTRY_ORDER || v == V_CAMERA_PK ||
+           (v >= V_ROUND2_FORM && v <= V_SHADOW_PLAIN_ROWS);
+}
 
-static int check_params(const srt_params* p) {
+// Kernels of one argument list have one type: a plan names the instantiation as a value, one statement per list launches it.
+using RefHitFn = decltype(&k_closest_hit<false>);
+using RefShadeFn = decltype(&k_shade<false>);
+using QHitFn = decltype(&k_closest_hit_q<false>);
+using NqHitFn = decltype(&k_closest_hit_nq<false, 512, 2, 2, true>);
+using PkHitFn = decltype(&k_closest_hit_pk<false, true, false>);
+using TraceFn = decltype(&k_trace_nq<false, 512, true, 7, 16>);
+using TraceShadeFn = decltype(&k_trace_shade_nq<512, true, 6, 16>);
+using ShadowPkFn = decltype(&k_shadow_pk<false, true, false>);
+using ShadowNqFn = decltype(&k_shadow_nq<false, 512, true, 16, 6>);
+using ShadeTileFn = decltype(&k_shade_tile<0>);
+
+// CONSTRAINT on plan_frame and the batch launches below: every kernel is named in a chain of plain assignments, in this order.  The
+// compiler emits the instantiations in the order it meets them, and ?: chains are met last operand first: reordering the statements
+// or folding them into ?: changes no behaviour, but the code object's layout, and with it tools/kernel_regs.py --digest, the check
+// that a host-only change left the kernels alone.
+
+enum BatchState { NOT_BATCHED, BATCH_FITS, BATCH_OTHER_SIZE };      // srt_render_device_batch is collecting, and this frame has the size of the frames it holds (or not)
+enum Hold { HOLD_NONE, HOLD_FUSED, HOLD_PK };                       // the two classes of frames a batch call launches together
+
+// What the choice of a frame's kernels depends on besides the caller's params: estimates and sizes of the scene, the device's CU
+// count, the process's environment.
+struct SceneFacts {
+    bool prefer_packet, int_shin, normals; double overlap; uint64_t bytes; uint32_t n_cu;
+    uint32_t heavy_steps, pk_units, pk_take;      // SRT_HEAVY_STEPS, SRT_PK_UNITS, SRT_PK_TAKE (read once per process)
+};
+static SceneFacts scene_facts(const srt_scene* s) {
+    static const auto env = [](const char* name, uint32_t dflt) { const char* e = std::getenv(name); return e ? (uint32_t)std::strtoul(e, nullptr, 10) : dflt; };
+    static const uint32_t heavy_steps = env("SRT_HEAVY_STEPS", 64u);      // walks of this many node steps make a quadrant a heavy one (0 = off)
+    static const uint32_t pk_units = env("SRT_PK_UNITS", 64u), pk_take = env("SRT_PK_TAKE", 4u);
+    return SceneFacts{s->rec->prefer_packet, s->rec->int_shin, s->dev.tri_normals != nullptr, s->rec->overlap, s->bytes, (uint32_t)s->n_cu,
+                      heavy_steps, pk_units, pk_take};
+}
+
+// Every check of a render's arguments: before any state of the handle changes (counter sets, pending work).
+static int check_frame(const SceneFacts& f, const srt_params* p) {
     if (!p || !p->width || !p->height || !p->block_rows || !p->block_stride) return SRT_ERR_ARG;
-    if (p->ray_matrix && (((p->flags >> 8) & 0xffu) != 0 && ((p->flags >> 8) & 0xffu) != 22 && ((p->flags >> 8) & 0xffu) != 35)) return SRT_ERR_ARG;      // camera mode: shipped pipelines only
+    const uint32_t v = variant_of(p);
+    if (p->ray_matrix && v != V_SHIPPED && v != V_PK_PK && v != V_CAMERA_PK) return SRT_ERR_ARG;      // camera mode: shipped pipelines only
     if (p->n_lights && !p->light_pos) return SRT_ERR_ARG;
     if (p->block_cols && ((p->block_cols & 7u) || (p->block_rows & 7u) || p->block_first >= p->block_stride)) return SRT_ERR_ARG;   // tiles of whole 8x8 pixel blocks
     if (p->spp < 1 || p->spp > 4096) return SRT_ERR_ARG;
@@ -918,41 +1006,268 @@ static int check_params(const srt_params* p) {
     if ((uint64_t)p->width * p->height >= (1ull << 31)) return SRT_ERR_LIMIT;
     if ((uint64_t)p->width * p->height * (p->n_lights ? p->n_lights : 1) >= (1ull << 32)) return SRT_ERR_LIMIT;   // 32-bit work-item index
     if (p->spp > 1 && (uint64_t)srt_cols_owned(p) * srt_rows_owned(p) * 3 >= (1ull << 32)) return SRT_ERR_LIMIT;   // the accumulation buffer's 32-bit float index
-    return SRT_OK;
+    return (p->flags & SRT_FLAG_SMOOTH_NORMALS) && (!f.normals || v == V_REFERENCE) ? SRT_ERR_ARG : SRT_OK;   // needs vertex normals
+}
+
+// One render's launches.  Pipelines (variant 0 picks per scene and light count; the numbered variants force one):
+//   fused        k_trace_nq (node-queue closest hit + shadow rays in one launch): 1..7 light samples
+//   nq + pk      node-queue closest hit, then the packet shadow kernel over the list of quadrants with hits: 8+ light samples
+//                (the samples of a pixel walk the other objects' trees in lock step), or variant 21 at any count
+//   pk + nq      packet closest hit, then the node-queue shadow kernel: hierarchies of heavily overlapping boxes (the 1 M soup:
+//                neighbouring primary rays test the same ~2,500 nodes, while the shadow rays of a tile start all over the
+//                scene), 1..7 light samples, or variant 23
+//   pk + pk      both packet kernels: such scenes with 8+ light samples, or variant 22
+//   nq chunked   k_shadow_nq with 64 rays in flight and the samples cut over blockIdx.z: 8..15 samples on scenes of few nodes, or variant 20
+// camera mode (rays that do not start at the origin): the fused node-queue kernel has a build for rays with an origin (1..7
+// samples, variant 0); everything else in camera mode goes through the packet closest-hit kernel, which takes a general ray.  The
+// shadow kernels start from the hit point either way.
+struct FramePlan {
+    // stage 1, closest hit or the fused trace: one of these
+    RefHitFn ref_hit = nullptr; QHitFn q_hit = nullptr; NqHitFn nq_hit = nullptr; PkHitFn pk_hit = nullptr; TraceFn trace = nullptr; TraceShadeFn trace_shade = nullptr;
+    // stage 2, shadow rays: at most one (none without light samples and behind a trace kernel); l_chunk: k_shadow_nq's light samples per blockIdx.z
+    ShadowPkFn shadow_pk = nullptr; ShadowNqFn shadow_nq = nullptr; uint32_t l_chunk = 0xffffffffu;
+    // stage 3, shading: one of these (none behind k_trace_shade_nq)
+    RefShadeFn ref_shade = nullptr; ShadeTileFn shade_tile = nullptr;
+    dim3 grid_hit, grid_shadow, grid_shade;
+    // the DevParams fields that belong to the choice (dev_params copies them); xcd_rows as the shadow stage sees it, shadow_px_major as
+    // the shading stage does
+    uint32_t exp = 0, heavy_steps = 0, pk_units = 0, pk_take = 1, xcd_rows = 0, shadow_xcd_rows = 0, shadow_px_major = 0;
+    // workspaces
+    size_t shadow_words = 0; uint32_t qcap_need = 0;      // shadow bits; entries per shard of the quadrant list.  0: none (variant 1 only -- a
+                                                          // frame that owns a row owns a tile, so every other plan needs at least one word and one entry)
+    bool quadrants_consumed = false;              // the closest-hit kernel fills the quadrant list only for a consumer
+    Hold hold = HOLD_NONE;                        // held back for the batch call's launches: no stage kernel is set
+    char pipeline[96] = "";                       // srt_scene_pipeline
+};
+
+// Decides a render: touches nothing, calls nothing of HIP.  p has passed check_frame and owns at least one row.
+static FramePlan plan_frame(const SceneFacts& f, const srt_params* p, BatchState batch) {
+    FramePlan pl;
+    const uint32_t v = variant_of(p), L = p->n_lights, wl = srt_cols_owned(p), rows = srt_rows_owned(p);
+    const bool count = (p->flags & SRT_FLAG_COUNT_WORK) != 0, in_flight = (p->flags & SRT_FLAG_FRAMES_IN_FLIGHT) != 0, cam = p->ray_matrix != nullptr, shipped = shipped_choice(v);
+    const dim3 grid16((wl + 15) / 16, (rows + 15) / 16), grid8((wl + 7) / 8, (rows + 7) / 8);      // grid8: 8x8 pixels per workgroup, 4 waves x (4x4 pixels)
+    const auto xcd_pad = [](uint32_t y) { return (y + 7) / 8 * 8; };      // whole tile rows per XCD: y padded to 8 rows
+    const size_t n_tiles = (size_t)grid8.x * grid8.y, pixels = (size_t)wl * rows;
+
+    pl.exp = ((v == V_ROUND2_FORM || v == V_LANE_ORDER) ? 1u : 0u) | (v == V_ROOT_LOOP ? 2u : 0u) | (v == V_WIDE_STEP_COUNTERS ? 4u : 0u) | (v == V_NO_UNION_BOX ? 8u : 0u) |
+             ((v == V_TRACE_SHADE || v == V_TRI_QUEUE) ? 32u : 0u);      // (32: the kernel counts the hits itself -- the hit statistic is not the shading kernel's)
+    pl.xcd_rows = (f.bytes > (32ull << 20) || v == V_XCD_ROWS) ? 1u : 0u;      // records far beyond one XCD's 4 MiB L2
+    pl.pk_units = in_flight ? f.pk_units : 0u; pl.pk_take = in_flight && f.pk_take ? f.pk_take : 1u;
+    pl.grid_shade = grid16;
+
+    if (v == V_REFERENCE) {
+        if (count) pl.ref_hit = &k_closest_hit<true>; else pl.ref_hit = &k_closest_hit<false>;
+        if (count) pl.ref_shade = &k_shade<true>; else pl.ref_shade = &k_shade<false>;
+        pl.grid_hit = grid16;
+        std::snprintf(pl.pipeline, sizeof(pl.pipeline), "k_closest_hit+k_shade");
+        return pl;
+    }
+    // workspace of the tile pipeline.  Shadow bits: tile-major (one 64-bit word per 8x8 tile and light sample, node-queue kernels) or
+    // pixel-major (one word per pixel and 64 light samples, packet shadow kernel): room for either.  Quadrant list: a shard gets
+    // every 64th tile, four quadrants each
+    const size_t words_tile = n_tiles * (L ? L : 1), words_px = pixels * ((L + 63) / 64);
+    pl.shadow_words = words_tile > words_px ? words_tile : words_px;
+    pl.qcap_need = (uint32_t)((n_tiles + QL_SHARDS - 1) / QL_SHARDS) * 4u;
+
+    // (check_frame: camera mode takes 0, 22 and 35)
+    const bool cam_nq = cam && v == V_SHIPPED && !count && !f.prefer_packet && L >= 1 && L < 8 && !pl.xcd_rows;
+    const bool pk_closest = (cam && !cam_nq) || v == V_PK_PK || v == V_PK_NQ || (shipped && f.prefer_packet && v != V_NO_PACKET);
+    // 8 .. 15 samples on a scene whose rays test few nodes (expected slab tests per ray < 14: cube scenes 3-6, bunny over a slab 12):
+    // the node-queue shadow kernel with the samples cut over blockIdx.z beats the packet walk since round 3's queue order (K3 with
+    // 8 / 12 samples 0.212 / 0.281 ms against 0.254 / 0.321, cube over ground with 8: 0.107 against 0.197); the composite scene
+    // (seven objects, tree crowns; estimate 17+) and 16+ samples stay with the packet walk (K4 with 8 / 12: 0.390 / 0.473 against 0.416 / 0.621)
+    const bool few_nodes_mid = v == V_SHIPPED && !count && !cam && L >= 8 && L < 16 && f.overlap < 14.0 && !f.prefer_packet;
+    const bool pk_shadow = L && (v == V_NQ_PK || v == V_PK_PK || (shipped && L >= 8 && !few_nodes_mid));
+    const bool chunked = L >= 8 && !count && (v == V_CHUNKED || few_nodes_mid);
+    // The two fallback rows for numbers without a name.  Above 10: a configuration of the fused kernel at every sample count, as the
+    // named 11, 12, 17, 18 and 28 (20 .. 23 force a pipeline through chunked / pk_shadow / pk_closest).  7 .. 9: neither row below, so
+    // the unfused chain of the `default` branch -- the 7-wave closest-hit build, then k_shadow_nq.
+    const bool fused_config = !shipped && v > 10 && v != V_CHUNKED;
+    const bool fused = L && (shipped || fused_config) && !chunked && !pk_shadow && !pk_closest;
+    pl.quadrants_consumed = pk_shadow; pl.shadow_px_major = pk_shadow ? 1u : 0u;
+
+    // held back: the batch call launches this frame together with the others (same kernels, same arguments)
+    const bool holdable = batch == BATCH_FITS && v == V_SHIPPED && !count && p->spp == 1 && !pk_closest;
+    if (holdable && (fused ? !pl.xcd_rows && !cam : pk_shadow)) {
+        // 8+ light samples (HOLD_PK): node-queue closest hit, packet shadow kernel and shading of the batch's frames in three launches.
+        // Packet shadow walks of heavy_steps node steps put their quadrant on the heavy list of the next frame (srt_kernels.h): the
+        // shadow rays of a batch are ONE launch and its tail is idle machine (a K4 step of eight share-frames 2.24 -> 1.73 ms).
+        // pk_take: unit numbers four at a time, fewer same-address atomics (srt_packet.h).  pk_units 0: the frames of a batch share the
+        // machine, every frame keeps its part of the grid (K3 with 16 samples, an eighth: 0.45 ms per step against 0.68 with surplus waves leaving)
+        pl.hold = fused ? HOLD_FUSED : HOLD_PK;
+        if (!fused) { pl.heavy_steps = f.heavy_steps; pl.pk_take = f.pk_take ? f.pk_take : 1u; pl.pk_units = 0u; }
+        std::snprintf(pl.pipeline, sizeof(pl.pipeline), fused ? "k_trace_nq+k_shade_tile (batched)" : "k_closest_hit_nq+k_shadow_pk+k_shade_tile (batched)");
+        return pl;
+    }
+    // A frame that has the device to itself (no in-flight hint, not part of a batch call): quadrants whose walks were long in this
+    // handle's previous frame are dealt early (srt_kernels.h) -- nothing else fills the slots the launch's tail frees.  Same box:
+    // K3 with 16 samples on one stream 4.04 -> 3.70 ms per 8 frames, K4 11.89 -> 11.72.  Frames launched one by one on several streams
+    // pipeline -- the next frame's closest-hit launch fills the slots a tail frees -- and the lists LOSE (K4 on four streams 9.41 ->
+    // 9.64, the reference's main() scene 6.55 -> 6.91), so the hint turns them off.
+    if (pk_shadow && v == V_SHIPPED && !count && !in_flight && batch == NOT_BATCHED) pl.heavy_steps = f.heavy_steps;
+
+    // stage 1
+    // closest-hit kernel: CAP = node queue entries, TWL/THL = log2 tile size per wave, FILTER = filtered slab test
+    #define NQ_HIT(CAP, TWL, THL, FILTER) do { \
+        if (count) pl.nq_hit = &k_closest_hit_nq<true, CAP, TWL, THL, FILTER>; else pl.nq_hit = &k_closest_hit_nq<false, CAP, TWL, THL, FILTER>; \
+        pl.grid_hit = dim3((wl + (2u << TWL) - 1) / (2u << TWL), (rows + (2u << THL) - 1) / (2u << THL)); } while (0)
+    pl.grid_hit = grid8;
+    switch (v) {
+    case V_TRI_QUEUE:
+        if (count) pl.q_hit = &k_closest_hit_q<true>; else pl.q_hit = &k_closest_hit_q<false>;
+        pl.grid_hit = grid16; break;
+    case V_NQ_TINY:        NQ_HIT(160, 2, 2, false); break;
+    case V_NQ_EXACT:       NQ_HIT(512, 2, 2, false); break;
+    case V_NQ_TINY_FILTER: NQ_HIT(160, 2, 2, true); break;
+    case V_NQ_8X4:         NQ_HIT(1024, 3, 2, false); break;
+    case V_UNFUSED:        NQ_HIT(512, 2, 2, true); break;
+    default:
+        if (pk_closest) {              // one wavefront per 8x8 tile walks the trees in lock step; a workgroup = 2 x 2 tiles
+            const bool xcd = pl.xcd_rows && !cam && !count;
+            if (cam && count)  pl.pk_hit = &k_closest_hit_pk<true, true, false, true>;
+            else if (cam)      pl.pk_hit = &k_closest_hit_pk<false, true, false, true>;
+            else if (count)    pl.pk_hit = &k_closest_hit_pk<true, true, false>;
+            else if (xcd)      pl.pk_hit = &k_closest_hit_pk<false, true, true>;
+            else               pl.pk_hit = &k_closest_hit_pk<false, true, false>;
+            pl.grid_hit = dim3((grid8.x + 1) / 2, xcd ? xcd_pad((grid8.y + 1) / 2) : (grid8.y + 1) / 2);
+        } else if (fused && v == V_TRACE_SHADE && !count && !pl.xcd_rows && L < 64) {
+            pl.trace_shade = &k_trace_shade_nq<512, true, 6, 16>;
+        } else if (fused) {            // closest hit + shadow rays in one launch
+            if (cam_nq)                        pl.trace = &k_trace_nq<false, 512, true, 5, 16, false, false, true>;      // camera mode on the node queues
+            else if (count)                    pl.trace = &k_trace_nq<true, 512, true, 5, 16>;
+            else if (v == V_FUSED_5_WAVES)     pl.trace = &k_trace_nq<false, 512, true, 5, 16>;
+            else if (v == V_FUSED_ROOTS_AGAIN) pl.trace = &k_trace_nq<false, 512, true, 6, 16, false, true>;
+            else if (v == V_FUSED_64_RAYS)     pl.trace = &k_trace_nq<false, 512, true, 5, 64>;
+            else if (v == V_FUSED_6_WAVES)     pl.trace = &k_trace_nq<false, 512, true, 6, 16>;
+            else if (v == V_ALL_WIDE)          pl.trace = &k_trace_nq<false, 512, true, 6, 16, false, false, false, true>;
+            else if (pl.xcd_rows)            { pl.trace = &k_trace_nq<false, 512, true, 6, 16, true>; pl.grid_hit.y = xcd_pad(grid8.y); }
+            else                               pl.trace = &k_trace_nq<false, 512, true, 7, 16>;      // 72 VGPRs (14 spills), 7 waves per SIMD: since the node-major order 3 % ahead of the 6-wave build (80 VGPRs, 5 spills); round 2's kernel lost 2.5 % that way
+        } else if (!count && v == V_COARSE_GRID) {
+            // 2 x 2 tiles per workgroup (a quarter of the workgroups for frames that are mostly background).  Measured and NOT
+            // shipped: K4 closest hit 0.44 ms against 0.29 with one tile per workgroup, K3 0.22 against 0.10 -- the launch is not
+            // dispatch-bound, and a workgroup that walks its live tiles one after the other is a longer tail
+            pl.nq_hit = &k_closest_hit_nq<false, 512, 2, 2, true, true>;
+            pl.grid_hit = dim3((grid8.x + 1) / 2, (grid8.y + 1) / 2);
+        } else if (!count && v == V_ALL_WIDE) {
+            pl.nq_hit = &k_closest_hit_nq<false, 512, 2, 2, true, false, true>;
+        } else if (!count && v != V_HIT_6_WAVES) {
+            // built for 7 waves per SIMD (72 VGPRs, 5 spills; 76 without the bound: 6 waves): a frame of mostly background tiles is a stream
+            // of short workgroups, and one more resident per SIMD is worth the spills -- K4 closest hit 0.234 -> 0.223 ms, frame 1.285 -> 1.236
+            pl.nq_hit = &k_closest_hit_nq<false, 512, 2, 2, true, false, false, 7>;
+        } else {
+            NQ_HIT(512, 2, 2, true);
+        }
+    }
+    #undef NQ_HIT
+    // stage 2
+    if (pk_shadow) {
+        // a fixed number of waves pull units (the shadow rays of 64 / n_lights pixels) from the quadrant list: no grid over the image
+        const uint64_t max_units = (uint64_t)n_tiles * 4u * 2u * ((L + 7) / 8);
+        pl.grid_shadow = dim3((uint32_t)(max_units / 4 + 1 < (uint64_t)f.n_cu * 8 ? max_units / 4 + 1 : (uint64_t)f.n_cu * 8));      // (8 per CU: every wave slot; fewer was measured)
+        if (count)                       pl.shadow_pk = &k_shadow_pk<true, true, false>;
+        else if (v == V_PK_ENTRY_ORDER)  pl.shadow_pk = &k_shadow_pk<false, true, false, true>;
+        else if (v == V_PK_AHEAD)        pl.shadow_pk = &k_shadow_pk<false, true, false, false, 1>;
+        else if (v == V_PK_AHEAD_SKIP)   pl.shadow_pk = &k_shadow_pk<false, true, false, false, 2>;
+        else if (pl.heavy_steps)         pl.shadow_pk = &k_shadow_pk<false, true, false, false, 0, true>;      // heavy quadrants dealt early (a frame alone on the device)
+        else if (v == V_PK_CLOCKS)       pl.shadow_pk = &k_shadow_pk<false, true, false, false, -1>;
+        else if (v == V_PK_PLAIN)        pl.shadow_pk = &k_shadow_pk<false, true, false, false, 0>;
+        else if (v == V_PK_WINDOWS)      pl.shadow_pk = &k_shadow_pk<false, true, true>;
+        else                             pl.shadow_pk = &k_shadow_pk<false, true, false>;
+    } else if (L && !fused) {
+        // scenes far bigger than an L2 (xcd_rows): whole tile rows per XCD for the shadow rays too
+        pl.shadow_xcd_rows = v == V_SHADOW_PLAIN_ROWS ? 0u : pl.xcd_rows;
+        if (chunked) pl.l_chunk = L / 4 > 4 ? (L + 3) / 4 : 4;
+        pl.grid_shadow = dim3(grid8.x, pl.shadow_xcd_rows ? xcd_pad(grid8.y) : grid8.y, chunked ? (L + pl.l_chunk - 1) / pl.l_chunk : 1);
+        if (chunked)                                       pl.shadow_nq = &k_shadow_nq<false, 512, true, 64, 6>;
+        else if (count)                                    pl.shadow_nq = &k_shadow_nq<true, 512, false>;
+        else if (v == V_NQ_TINY)                           pl.shadow_nq = &k_shadow_nq<false, 160, false>;
+        else if (v == V_NQ_TINY_FILTER)                    pl.shadow_nq = &k_shadow_nq<false, 160, true>;
+        else if (v == V_NQ_EXACT)                          pl.shadow_nq = &k_shadow_nq<false, 512, false>;
+        else if (v == V_ROUND2_FORM || v == V_ALL_NARROW)  pl.shadow_nq = &k_shadow_nq<false, 512, true, 16, 6, false>;
+        else                                               pl.shadow_nq = &k_shadow_nq<false, 512, true, 16, 6>;      // 80 VGPRs: six waves per SIMD (86 without the bound: five)
+    }
+    // stage 3
+    if (pl.trace_shade) { std::snprintf(pl.pipeline, sizeof(pl.pipeline), "k_trace_shade_nq"); return pl; }
+    if (f.int_shin && v != V_GENERAL_SHADE) pl.shade_tile = &k_shade_tile<1>; else pl.shade_tile = &k_shade_tile<0>;
+    std::snprintf(pl.pipeline, sizeof(pl.pipeline), "%s%s+k_shade_tile", fused ? "k_trace_nq" : (pk_closest ? "k_closest_hit_pk" : "k_closest_hit_nq"),
+                  fused || !L ? "" : (pk_shadow ? "+k_shadow_pk" : "+k_shadow_nq"));
+    return pl;
+}
+
+// A frame's kernel parameters: geometry and literals from the caller's params, the rest from the plan.
+struct FrameParams {
+    DevParams hit, shadow, shade;      // per stage: the same but for xcd_rows (shadow) and shadow_px_major (shade)
+    void sub_pixel(float x, float y) { hit.sub_x = shadow.sub_x = shade.sub_x = x; hit.sub_y = shadow.sub_y = shade.sub_y = y; }
+};
+static FrameParams dev_params(const srt_scene* s, const srt_params* p, const FramePlan& pl) {
+    DevParams dp;
+    dp.smooth = (p->flags & SRT_FLAG_SMOOTH_NORMALS) ? 1u : 0u; dp.shadow_px_major = 0u;
+    dp.cam = p->ray_matrix ? 1u : 0u;
+    for (int c = 0; c < 4; c++) for (int r3 = 0; r3 < 3; r3++) dp.cm[c * 3 + r3] = p->ray_matrix ? p->ray_matrix[c * 4 + r3] : 0.0f;
+    dp.W = srt_cols_owned(p); dp.Wimg = p->width; dp.col_block = p->block_cols; dp.H = p->height; dp.rows = srt_rows_owned(p);
+    dp.block_rows = p->block_rows; dp.block_first = p->block_first; dp.block_stride = p->block_stride;
+    dp.i0 = (int)(-(float)p->width / 2); dp.j0 = (int)(-(float)p->height / 2);       // :511,513
+    dp.sub_x = 0.0f; dp.sub_y = 0.0f;                                                 // rayXY = (0, 0), :507,514-515
+    dp.focal = p->focal; dp.n_lights = p->n_lights; dp.lights = s->d_lights;
+    dp.shadow_div = p->shadow_div; dp.reinhard = p->reinhard; dp.gamma = p->gamma;
+    dp.bg = (uint32_t)p->background[0] | ((uint32_t)p->background[1] << 8) | ((uint32_t)p->background[2] << 16);
+    dp.xcd_rows = pl.xcd_rows; dp.exp = pl.exp; dp.heavy_steps = pl.heavy_steps; dp.pk_units = pl.pk_units; dp.pk_take = pl.pk_take;
+    FrameParams fp{dp, dp, dp};
+    fp.shadow.xcd_rows = pl.shadow_xcd_rows; fp.shade.shadow_px_major = pl.shadow_px_major;
+    return fp;
 }
 
 // Frames whose launches srt_render_device_batch holds back to issue them as one grid (k_trace_nq_batch + k_shade_tile_batch).
 struct BatchCollector {
     std::vector<FrameItem> items;        // frames of the fused pipeline (1..7 light samples): k_trace_nq_batch + k_shade_tile_batch
     std::vector<FrameItem> items_pk;     // frames of the 8+-sample pipeline: k_closest_hit_nq_batch + k_shadow_pk_batch + k_shade_tile_batch
-    uint32_t wl = 0, rows = 0;           // every held frame writes the same local width and row count: one grid fits all
-    uint32_t max_lights = 0;
-    bool accepts(uint32_t w, uint32_t r) { if (items.empty() && items_pk.empty()) { wl = w; rows = r; } return w == wl && r == rows; }
+    uint32_t wl = 0, rows = 0, max_lights = 0;      // every held frame writes the same local width and row count: one grid fits all
+    bool fits(uint32_t w, uint32_t r) const { return (items.empty() && items_pk.empty()) || (w == wl && r == rows); }
 };
+
+// One pass of a plan over this call's pixels: closest hit (+ shadow rays) and shading, the event records between them.
+static int launch_stages(srt_scene* s, const FramePlan& pl, const FrameParams& fp, hipStream_t stream, int32_t* o_hit, float* o_t, float* o_lin, uint8_t* o_rgb8, unsigned long long* ctr, unsigned long long* zero_next, hipEvent_t* ev) {
+    const dim3 block(256);
+    uint32_t* const ql = pl.quadrants_consumed ? s->ws_qlist.p : nullptr, * const ql_cnt = pl.quadrants_consumed ? s->d_qcount.p : nullptr;
+    if (pl.ref_hit)          hipLaunchKernelGGL(pl.ref_hit, pl.grid_hit, block, 0, stream, s->dev, fp.hit, o_hit, o_t, ctr);
+    else if (pl.q_hit)       hipLaunchKernelGGL(pl.q_hit, pl.grid_hit, block, 0, stream, s->dev, fp.hit, o_hit, o_t, o_lin, o_rgb8, ctr);
+    else if (pl.nq_hit)      hipLaunchKernelGGL(pl.nq_hit, pl.grid_hit, block, 0, stream, s->dev, fp.hit, o_hit, o_t, o_lin, o_rgb8, ctr, ql_cnt, ql, s->qcap);
+    else if (pl.pk_hit)      hipLaunchKernelGGL(pl.pk_hit, pl.grid_hit, block, 0, stream, s->dev, fp.hit, o_hit, o_t, o_lin, o_rgb8, ql_cnt, ql, s->qcap, ctr);
+    else if (pl.trace)       hipLaunchKernelGGL(pl.trace, pl.grid_hit, block, 0, stream, s->dev, fp.hit, o_hit, o_t, o_lin, o_rgb8, s->ws_shadow, ctr);
+    else                     hipLaunchKernelGGL(pl.trace_shade, pl.grid_hit, block, 0, stream, s->dev, fp.hit, o_hit, o_t, o_lin, o_rgb8, ctr, zero_next, s->d_qcount);
+    HIP_TRY(hipGetLastError());
+    if (ev) HIP_TRY(hipEventRecord(ev[1], stream));
+    if (pl.shadow_pk)        hipLaunchKernelGGL(pl.shadow_pk, pl.grid_shadow, block, 0, stream, s->dev, fp.hit, o_hit, o_t, s->d_qcount, s->ws_qlist, s->qcap, s->ws_shadow, ctr);
+    else if (pl.shadow_nq)   hipLaunchKernelGGL(pl.shadow_nq, pl.grid_shadow, block, 0, stream, s->dev, fp.shadow, o_hit, o_t, s->ws_shadow, ctr, pl.l_chunk);
+    if (pl.shadow_pk || pl.shadow_nq) HIP_TRY(hipGetLastError());
+    if (ev) HIP_TRY(hipEventRecord(ev[2], stream));
+    if (pl.ref_shade)        hipLaunchKernelGGL(pl.ref_shade, pl.grid_shade, block, 0, stream, s->dev, fp.shade, o_hit, o_t, o_lin, o_rgb8, ctr, zero_next);
+    else if (pl.shade_tile)  hipLaunchKernelGGL(pl.shade_tile, pl.grid_shade, block, 0, stream, s->dev, fp.shade, o_hit, o_t, s->ws_shadow, o_lin, o_rgb8, zero_next, s->d_qcount, ctr);
+    if (pl.ref_shade || pl.shade_tile) HIP_TRY(hipGetLastError());
+    std::snprintf(s->pipeline, sizeof(s->pipeline), "%s", pl.pipeline);
+    return SRT_OK;
+}
 
 static int render_device_impl(srt_scene* s, const srt_params* p, void* stream_, int32_t* d_hit_id, float* d_t,
                               float* d_rgb_linear, uint8_t* d_rgb8, BatchCollector* bc = nullptr) {
     if (!s) return SRT_ERR_ARG;
-    int rc = check_params(p);
-    if (rc != SRT_OK) return rc;
-    // every argument check comes before any state of the handle changes (counter sets, pending work)
-    if ((p->flags & SRT_FLAG_SMOOTH_NORMALS) && (!s->dev.tri_normals || variant_of(p) == 1)) return SRT_ERR_ARG;   // needs vertex normals
+    const SceneFacts facts = scene_facts(s);
+    SRT_TRY(check_frame(facts, p));
     hipStream_t stream = (hipStream_t)stream_;
     HIP_TRY(hipSetDevice(s->device));
-    const uint32_t rows = srt_rows_owned(p);
-    const uint32_t wl = srt_cols_owned(p);    // width of the rows this call writes
+    const uint32_t rows = srt_rows_owned(p), wl = srt_cols_owned(p);      // wl: width of the rows this call writes
     if (!rows) {                              // nothing to launch; work of an earlier render stays pending
         if (!s->pending) std::memset(&s->last, 0, sizeof(s->last));
         return SRT_OK;
     }
+    const FramePlan plan = plan_frame(facts, p, !bc ? NOT_BATCHED : bc->fits(wl, rows) ? BATCH_FITS : BATCH_OTHER_SIZE);
     std::memset(&s->last, 0, sizeof(s->last));
     s->last.rows = rows;
     s->last.primary_rays = pixels_owned(p);
     const size_t pixels = (size_t)wl * rows;
     // workspace for hit ids / t when the caller does not want them (the shade kernel does)
     if (!d_hit_id || !d_t) SRT_TRY(grow(s, pixels, s->ws_hit, s->ws_t));
-    if (!d_hit_id) d_hit_id = s->ws_hit;
-    if (!d_t) d_t = s->ws_t;
+    if (!d_hit_id) d_hit_id = s->ws_hit; if (!d_t) d_t = s->ws_t;
     if (p->n_lights > s->d_lights.cap || p->n_lights > s->h_lights.cap) {
         s->lights_valid = 0;               // new buffers: nothing of the old contents is on the device
         SRT_TRY(grow(s, p->n_lights, s->d_lights, s->h_lights));
@@ -977,247 +1292,45 @@ static int render_device_impl(srt_scene* s, const srt_params* p, void* stream_, 
     // a counting run must not inherit whatever replayed graphs left in the set (their frames use fixed sets)
     if (p->flags & SRT_FLAG_COUNT_WORK) HIP_TRY(hipMemsetAsync(ctr, 0, NCTR * sizeof(unsigned long long), stream));
 
-    DevParams dp;
-    dp.smooth = (p->flags & SRT_FLAG_SMOOTH_NORMALS) ? 1u : 0u;
-    dp.shadow_px_major = 0u;
-    dp.cam = p->ray_matrix ? 1u : 0u;
-    for (int c = 0; c < 4; c++) for (int r3 = 0; r3 < 3; r3++) dp.cm[c * 3 + r3] = p->ray_matrix ? p->ray_matrix[c * 4 + r3] : 0.0f;
-    dp.xcd_rows = (s->bytes > (32ull << 20) || variant_of(p) == 18) ? 1u : 0u;       // records far beyond one XCD's 4 MiB L2 (variant 18: forced, for the tests)
-    dp.W = wl; dp.Wimg = p->width; dp.col_block = p->block_cols; dp.H = p->height; dp.rows = rows;
-    dp.block_rows = p->block_rows; dp.block_first = p->block_first; dp.block_stride = p->block_stride;
-    dp.i0 = (int)(-(float)p->width / 2); dp.j0 = (int)(-(float)p->height / 2);       // :511,513
-    dp.sub_x = 0.0f; dp.sub_y = 0.0f;                                                 // rayXY = (0, 0), :507,514-515
-    dp.focal = p->focal; dp.n_lights = p->n_lights; dp.lights = s->d_lights;
-    dp.shadow_div = p->shadow_div; dp.reinhard = p->reinhard; dp.gamma = p->gamma;
-    dp.bg = (uint32_t)p->background[0] | ((uint32_t)p->background[1] << 8) | ((uint32_t)p->background[2] << 16);
-
-    const dim3 block(256), grid((wl + 15) / 16, (rows + 15) / 16);
-    const dim3 grid8((wl + 7) / 8, (rows + 7) / 8);                // 8x8 pixels per workgroup: 4 waves x (4x4 pixels)
-    const bool count = (p->flags & SRT_FLAG_COUNT_WORK) != 0;
-    uint32_t variant = (p->flags >> 8) & 0xffu;            // experimental kernel selector (0 = shipped pipeline)
-    const bool force_nq = variant == 24;                   // 24: what variant 0 does for a scene WITHOUT the packet preference (A/B on soups)
-    const bool coarse_grid = variant == 27;                // 27: variant 0 with 2 x 2 tiles per workgroup in the unfused closest-hit launch (A/B, not shipped)
-    // 40: the round-2 form everywhere (32 B node records, queue pushes in lane order); 41 / 42: the 64 B / the 32 B records in every
-    // node-queue kernel (node-major order); 43: the shipped kernels with pushes in lane order.  Shipped (0): node-major order; 32 B records
-    // in the fused and the closest-hit kernel, 64 B records in the stand-alone shadow kernel
-    const bool all_narrow = variant == 40 || variant == 42, all_wide = variant == 41;
-    dp.exp = ((variant == 40 || variant == 43) ? 1u : 0u) | (variant == 45 ? 2u : 0u) | (variant == 47 ? 4u : 0u) | (variant == 46 ? 8u : 0u) | ((variant == 28 || variant == 2) ? 32u : 0u);      // (28: k_trace_shade_nq has no shading launch behind it, 2: k_closest_hit_q counts itself: the hit statistic is not the shading kernel's)      // (47: diagnostic counters of the wide shadow kernel's steps)      // 45: the tile's root tests by the round-2 loop of dependent loads (A/B)
-    dp.heavy_steps = 0u;                                   // (set below: frames a batch call holds back, and single frames that have the device to themselves)
-    static const uint32_t heavy_default = [] { const char* e = std::getenv("SRT_HEAVY_STEPS"); return e ? (uint32_t)std::strtoul(e, nullptr, 10) : 64u; }();      // walks of this many node steps make a quadrant a heavy one (0 = off)
-    static const uint32_t pk_units_default = [] { const char* e = std::getenv("SRT_PK_UNITS"); return e ? (uint32_t)std::strtoul(e, nullptr, 10) : 64u; }();
-    static const uint32_t pk_take_default = [] { const char* e = std::getenv("SRT_PK_TAKE"); return e ? (uint32_t)std::strtoul(e, nullptr, 10) : 4u; }();
-    const bool in_flight = (p->flags & SRT_FLAG_FRAMES_IN_FLIGHT) != 0;
-    dp.pk_units = in_flight ? pk_units_default : 0u; dp.pk_take = in_flight && pk_take_default ? pk_take_default : 1u;      // (batch frames: set where they are held back)
-    if (force_nq || variant == 25 || variant == 29 || variant == 35 || coarse_grid || (variant >= 40 && variant <= 62)) variant = 0;      // (44: the general shading kernel forced)            // 25: variant 0 with the packet shadow kernel reading records through LDS windows (A/B)
-    const uint32_t spp = p->spp;
-    // workspace of the tile pipeline: per 8x8 tile and light sample one 64-bit word of shadow bits
-    // shadow bits: tile-major (one word per tile and light sample, node-queue kernels) or pixel-major (one word per pixel and 64 light
-    // samples, packet shadow kernel): room for either
-    const size_t words_tile = (size_t)grid8.x * grid8.y * (p->n_lights ? p->n_lights : 1), words_px = pixels * ((p->n_lights + 63) / 64);
-    const size_t shadow_words = words_tile > words_px ? words_tile : words_px;
-    if (variant != 1) SRT_TRY(grow(s, shadow_words, s->ws_shadow));
-    const size_t n_tiles = (size_t)grid8.x * grid8.y;
-    const uint32_t qcap_need = (uint32_t)((n_tiles + QL_SHARDS - 1) / QL_SHARDS) * 4u;      // a shard gets every 64th tile, four quadrants each
-    if (variant != 1 && s->qcap < qcap_need) {
+    // the workspaces the plan needs: all of them before the first launch
+    if (plan.shadow_words) SRT_TRY(grow(s, plan.shadow_words, s->ws_shadow));
+    if (s->qcap < plan.qcap_need) {
         // per shard entry three words: two for the entry, and behind the lists one word per quadrant, the cost map the shadow kernel leaves
         // for the next frame's list -- which starts empty
         s->qcap = 0;
-        SRT_TRY(grow(s, (size_t)QL_SHARDS * qcap_need, s->ws_qlist));
-        HIP_TRY(hipMemset(s->ws_qlist + (size_t)QL_SHARDS * qcap_need * 2, 0, (size_t)QL_SHARDS * qcap_need * sizeof(uint32_t)));
-        s->qcap = qcap_need;
+        SRT_TRY(grow(s, (size_t)QL_SHARDS * plan.qcap_need, s->ws_qlist));
+        HIP_TRY(hipMemset(s->ws_qlist + (size_t)QL_SHARDS * plan.qcap_need * 2, 0, (size_t)QL_SHARDS * plan.qcap_need * sizeof(uint32_t)));
+        s->qcap = plan.qcap_need;
     }
+    const uint32_t spp = p->spp;
     if (spp > 1) SRT_TRY(grow(s, pixels, s->ws_acc, s->ws_sub, s->ws_sub_hit, s->ws_sub_t));      // supersampling extension: accumulation buffers
-
-    // One pass of the path over this call's pixels: closest hit (+ shadow rays) and shading.
-    auto launch_frame = [&](const DevParams& fp_in, int32_t* o_hit, float* o_t, float* o_lin, uint8_t* o_rgb8,
-                            unsigned long long* zero_next, hipEvent_t* ev) -> int {
-        DevParams fp = fp_in;
-        if (variant == 1) {                // v0 reference kernels: per-lane walk with inline triangle loop, per-pixel shade
-            if (count) hipLaunchKernelGGL(k_closest_hit<true>, grid, block, 0, stream, s->dev, fp, o_hit, o_t, ctr);
-            else       hipLaunchKernelGGL(k_closest_hit<false>, grid, block, 0, stream, s->dev, fp, o_hit, o_t, ctr);
-            HIP_TRY(hipGetLastError());
-            if (ev) { HIP_TRY(hipEventRecord(ev[1], stream)); HIP_TRY(hipEventRecord(ev[2], stream)); }
-            if (count) hipLaunchKernelGGL(k_shade<true>, grid, block, 0, stream, s->dev, fp, o_hit, o_t, o_lin, o_rgb8, ctr, zero_next);
-            else       hipLaunchKernelGGL(k_shade<false>, grid, block, 0, stream, s->dev, fp, o_hit, o_t, o_lin, o_rgb8, ctr, zero_next);
-            HIP_TRY(hipGetLastError());
-            std::snprintf(s->pipeline, sizeof(s->pipeline), "k_closest_hit+k_shade");
-            return SRT_OK;
-        }
-        // closest-hit kernel: CAP = node queue entries, TWL/THL = log2 tile size per wave, FILTER = filtered slab test
-        #define LAUNCH_NQ(CAP, TWL, THL, FILTER) do { \
-            const dim3 g_((wl + (2u << TWL) - 1) / (2u << TWL), (rows + (2u << THL) - 1) / (2u << THL)); \
-            if (count) hipLaunchKernelGGL((k_closest_hit_nq<true, CAP, TWL, THL, FILTER>), g_, block, 0, stream, s->dev, fp, o_hit, o_t, o_lin, o_rgb8, ctr, ql_cnt, ql, s->qcap); \
-            else       hipLaunchKernelGGL((k_closest_hit_nq<false, CAP, TWL, THL, FILTER>), g_, block, 0, stream, s->dev, fp, o_hit, o_t, o_lin, o_rgb8, ctr, ql_cnt, ql, s->qcap); } while (0)
-        // Pipelines (variant 0 picks per scene and light count; the numbered variants force one):
-        //   fused        k_trace_nq (node-queue closest hit + shadow rays in one launch): 1..7 light samples
-        //   nq + pk      node-queue closest hit, then the packet shadow kernel over the list of quadrants with hits: 8+ light samples
-        //                (the samples of a pixel walk the other objects' trees in lock step), or variant 21 at any count
-        //   pk + nq      packet closest hit, then the node-queue shadow kernel: hierarchies of heavily overlapping boxes (the 1 M soup:
-        //                neighbouring primary rays test the same ~2,500 nodes, while the shadow rays of a tile start all over the
-        //                scene), 1..7 light samples, or variant 23
-        //   pk + pk      both packet kernels: such scenes with 8+ light samples, or variant 22
-        //   nq chunked   the round-1 form for 8+ samples (k_shadow_nq, 64 rays in flight, samples cut over blockIdx.z): variant 20
-        // camera mode (rays that do not start at the origin): closest hit on the packet kernel, which takes a general ray; the shadow
-        // kernels start from the hit point either way
-        // camera mode: the fused node-queue kernel has a build for rays with an origin (1..7 samples, variant 0); everything else
-        // in camera mode goes through the packet closest-hit kernel, which takes a general ray
-        const bool cam_nq = fp.cam && variant == 0 && !count && !s->rec->prefer_packet && p->n_lights >= 1 && p->n_lights < 8 && !fp.xcd_rows && (p->flags >> 8 & 0xffu) != 35;
-        const bool pk_closest = (fp.cam && !cam_nq) || variant == 22 || variant == 23 || (variant == 0 && s->rec->prefer_packet && !force_nq);
-        // 8 .. 15 samples on a scene whose rays test few nodes (expected slab tests per ray < 14: cube scenes 3-6, bunny over a slab 12):
-        // the node-queue shadow kernel with the samples cut over blockIdx.z beats the packet walk since round 3's queue order (K3 with
-        // 8 / 12 samples 0.212 / 0.281 ms against 0.254 / 0.321, cube over ground with 8: 0.107 against 0.197); the composite scene
-        // (seven objects, tree crowns; estimate 17+) and 16+ samples stay with the packet walk (K4 with 8 / 12: 0.390 / 0.473 against 0.416 / 0.621)
-        const bool few_nodes_mid = variant == 0 && !count && !fp.cam && p->n_lights >= 8 && p->n_lights < 16 && s->rec->overlap < 14.0 && !s->rec->prefer_packet &&
-                                   (p->flags >> 8 & 0xffu) == 0;
-        const bool pk_shadow = p->n_lights && (variant == 21 || variant == 22 || (variant == 0 && p->n_lights >= 8 && !few_nodes_mid));
-        // A frame that has the device to itself (no in-flight hint, not part of a batch call): quadrants whose walks were long in this
-        // handle's previous frame are dealt early (srt_kernels.h) -- nothing else fills the slots the launch's tail frees.  Same box:
-        // K3 with 16 samples on one stream 4.04 -> 3.70 ms per 8 frames, K4 11.89 -> 11.72; with frames on four streams the lists LOSE
-        // (K4 9.41 -> 9.64, the reference's main() scene 6.55 -> 6.91), so the hint turns them off.
-        if (pk_shadow && variant == 0 && (p->flags >> 8 & 0xffu) == 0 && !count && !in_flight && !bc) fp.heavy_steps = heavy_default;
-        uint32_t* const ql = pk_shadow ? s->ws_qlist : nullptr;      // the closest-hit kernel fills the quadrant list only for a consumer
-        uint32_t* const ql_cnt = pk_shadow ? s->d_qcount : nullptr;
-        const uint32_t L_CHUNK = p->n_lights / 4 > 4 ? (p->n_lights + 3) / 4 : 4;
-        const bool chunked = p->n_lights >= 8 && !count && (variant == 20 || few_nodes_mid);
-        const bool fused = (variant == 0 || variant > 10) && p->n_lights && !chunked && !pk_shadow && !pk_closest && variant != 20;     // (variants 11, 17, 18 are configurations of the fused kernel)
-        const dim3 grid8x(grid8.x, fp.xcd_rows ? (grid8.y + 7) / 8 * 8 : grid8.y);      // whole tile rows per XCD: y padded to 8 rows
-        bool shaded = false;               // the trace launch shaded its tiles itself
-        switch (variant) {
-        case 2:                        // one ray per lane + triangle queue
-            if (count) hipLaunchKernelGGL((k_closest_hit_q<true>), grid, block, 0, stream, s->dev, fp, o_hit, o_t, o_lin, o_rgb8, ctr);
-            else       hipLaunchKernelGGL((k_closest_hit_q<false>), grid, block, 0, stream, s->dev, fp, o_hit, o_t, o_lin, o_rgb8, ctr);
-            break;
-        case 3: LAUNCH_NQ(160, 2, 2, false); break;      // tiny node queue: exercises the stackless overflow path
-        case 4: LAUNCH_NQ(512, 2, 2, false); break;      // shipped geometry with exact divides only
-        case 6: LAUNCH_NQ(160, 2, 2, true); break;       // tiny node queue + filtered slab test: the overflow walk as shipped
-        case 5: LAUNCH_NQ(1024, 3, 2, false); break;     // 8x4 pixels per wave, 1024-entry queue (tile-size experiment)
-        case 10: LAUNCH_NQ(512, 2, 2, true); break;      // shipped kernels, unfused (closest hit, then shadow)
-        default:
-            if (pk_closest) {          // one wavefront per 8x8 tile walks the trees in lock step; a workgroup = 2 x 2 tiles
-                const dim3 gp((grid8.x + 1) / 2, fp.xcd_rows ? ((grid8.y + 1) / 2 + 7) / 8 * 8 : (grid8.y + 1) / 2);
-                if (fp.cam && count)  hipLaunchKernelGGL((k_closest_hit_pk<true, true, false, true>), dim3((grid8.x + 1) / 2, (grid8.y + 1) / 2), block, 0, stream, s->dev, fp, o_hit, o_t, o_lin, o_rgb8, ql_cnt, ql, s->qcap, ctr);
-                else if (fp.cam)      hipLaunchKernelGGL((k_closest_hit_pk<false, true, false, true>), dim3((grid8.x + 1) / 2, (grid8.y + 1) / 2), block, 0, stream, s->dev, fp, o_hit, o_t, o_lin, o_rgb8, ql_cnt, ql, s->qcap, ctr);
-                else if (count)       hipLaunchKernelGGL((k_closest_hit_pk<true, true, false>), dim3((grid8.x + 1) / 2, (grid8.y + 1) / 2), block, 0, stream, s->dev, fp, o_hit, o_t, o_lin, o_rgb8, ql_cnt, ql, s->qcap, ctr);
-                else if (fp.xcd_rows) hipLaunchKernelGGL((k_closest_hit_pk<false, true, true>), gp, block, 0, stream, s->dev, fp, o_hit, o_t, o_lin, o_rgb8, ql_cnt, ql, s->qcap, ctr);
-                else                  hipLaunchKernelGGL((k_closest_hit_pk<false, true, false>), gp, block, 0, stream, s->dev, fp, o_hit, o_t, o_lin, o_rgb8, ql_cnt, ql, s->qcap, ctr);
-            } else if (fused && bc && !count && (p->flags >> 8 & 0xffu) == 0 && !fp.xcd_rows && !fp.cam && spp == 1 && bc->accepts(wl, rows)) {
-                // held back: the batch call launches this frame together with the others (same kernels, same arguments)
-                bc->items.push_back(FrameItem{s->dev, fp, o_hit, o_t, o_lin, o_rgb8, s->ws_shadow, ctr, zero_next, s->d_qcount});
-                std::snprintf(s->pipeline, sizeof(s->pipeline), "k_trace_nq+k_shade_tile (batched)");
-                return SRT_OK;
-            } else if (fused && variant == 28 && !count && !fp.xcd_rows && p->n_lights < 64) {      // 28 (A/B): the whole frame in one launch
-                hipLaunchKernelGGL((k_trace_shade_nq<512, true, 6, 16>), grid8, block, 0, stream, s->dev, fp, o_hit, o_t, o_lin, o_rgb8, ctr, zero_next, s->d_qcount);
-                shaded = true;
-            } else if (fused && cam_nq) {      // camera mode on the node queues
-                hipLaunchKernelGGL((k_trace_nq<false, 512, true, 5, 16, false, false, true>), grid8, block, 0, stream, s->dev, fp, o_hit, o_t, o_lin, o_rgb8, s->ws_shadow, ctr);
-            } else if (fused) {        // closest hit + shadow rays in one launch
-                if (count)              hipLaunchKernelGGL((k_trace_nq<true, 512, true, 5, 16>), grid8, block, 0, stream, s->dev, fp, o_hit, o_t, o_lin, o_rgb8, s->ws_shadow, ctr);
-                else if (variant == 11) hipLaunchKernelGGL((k_trace_nq<false, 512, true, 5, 16>), grid8, block, 0, stream, s->dev, fp, o_hit, o_t, o_lin, o_rgb8, s->ws_shadow, ctr);
-                else if (variant == 12) hipLaunchKernelGGL((k_trace_nq<false, 512, true, 6, 16, false, true>), grid8, block, 0, stream, s->dev, fp, o_hit, o_t, o_lin, o_rgb8, s->ws_shadow, ctr);      // round-1 form: roots re-tested per wave (A/B)
-                else if (variant == 17) hipLaunchKernelGGL((k_trace_nq<false, 512, true, 5, 64>), grid8, block, 0, stream, s->dev, fp, o_hit, o_t, o_lin, o_rgb8, s->ws_shadow, ctr);      // 64 shadow rays in flight per wave
-                else if ((p->flags >> 8 & 0xffu) == 54) hipLaunchKernelGGL((k_trace_nq<false, 512, true, 6, 16>), grid8, block, 0, stream, s->dev, fp, o_hit, o_t, o_lin, o_rgb8, s->ws_shadow, ctr);      // (A/B) the build for 6 waves per SIMD (rounds 1-2)
-                else if (all_wide)      hipLaunchKernelGGL((k_trace_nq<false, 512, true, 6, 16, false, false, false, true>), grid8, block, 0, stream, s->dev, fp, o_hit, o_t, o_lin, o_rgb8, s->ws_shadow, ctr);
-                else if (fp.xcd_rows)   hipLaunchKernelGGL((k_trace_nq<false, 512, true, 6, 16, true>), grid8x, block, 0, stream, s->dev, fp, o_hit, o_t, o_lin, o_rgb8, s->ws_shadow, ctr);
-                else                    hipLaunchKernelGGL((k_trace_nq<false, 512, true, 7, 16>), grid8, block, 0, stream, s->dev, fp, o_hit, o_t, o_lin, o_rgb8, s->ws_shadow, ctr);      // 72 VGPRs (14 spills), 7 waves per SIMD: since the node-major order 3 % ahead of the 6-wave build (80 VGPRs, 5 spills); round 2's kernel lost 2.5 % that way
-            } else if (bc && !count && (p->flags >> 8 & 0xffu) == 0 && pk_shadow && !pk_closest && spp == 1 && bc->accepts(wl, rows)) {
-                // 8+ light samples, held back: node-queue closest hit, packet shadow kernel and shading of the batch's frames in three launches
-                FrameItem it{s->dev, fp, o_hit, o_t, o_lin, o_rgb8, s->ws_shadow, ctr, zero_next, s->d_qcount, s->ws_qlist, s->qcap, 0u};
-                it.p.shadow_px_major = 1u;
-                // packet shadow walks of this many node steps put their quadrant on the heavy list of the next frame (srt_kernels.h).  Only
-                // for the frames of a batch: their shadow rays are ONE launch and its tail is idle machine (a K4 step of eight share-frames
-                // 2.24 -> 1.73 ms).  Frames launched one by one on several streams pipeline -- the next frame's closest-hit launch fills the
-                // slots a tail frees -- and lose that when the launch ends abruptly (K4 on four streams 10.1 -> 10.5-11.1 ms per 8 frames,
-                // K3 with 16 samples 3.38 -> 3.6-4.0; one stream: no difference): k_shadow_pk is built without the heavy lists.
-                it.p.heavy_steps = heavy_default;
-                it.p.pk_take = pk_take_default ? pk_take_default : 1u;      // unit numbers four at a time: fewer same-address atomics (srt_packet.h)
-                it.p.pk_units = 0u;                   // the frames of a batch share the machine: every frame keeps its part of the grid (K3 with 16 samples, an eighth: 0.45 ms per step against 0.68 with surplus waves leaving)
-                bc->items_pk.push_back(it);
-                if (p->n_lights > bc->max_lights) bc->max_lights = p->n_lights;
-                std::snprintf(s->pipeline, sizeof(s->pipeline), "k_closest_hit_nq+k_shadow_pk+k_shade_tile (batched)");
-                return SRT_OK;
-            } else if (!count && coarse_grid) {
-                // 2 x 2 tiles per workgroup (a quarter of the workgroups for frames that are mostly background).  Measured and NOT
-                // shipped: K4 closest hit 0.44 ms against 0.29 with one tile per workgroup, K3 0.22 against 0.10 -- the launch is not
-                // dispatch-bound, and a workgroup that walks its live tiles one after the other is a longer tail
-                hipLaunchKernelGGL((k_closest_hit_nq<false, 512, 2, 2, true, true>), dim3((grid8.x + 1) / 2, (grid8.y + 1) / 2), block, 0, stream,
-                                   s->dev, fp, o_hit, o_t, o_lin, o_rgb8, ctr, ql_cnt, ql, s->qcap);
-            } else if (all_wide && !count) {
-                hipLaunchKernelGGL((k_closest_hit_nq<false, 512, 2, 2, true, false, true>), grid8, block, 0, stream, s->dev, fp, o_hit, o_t, o_lin, o_rgb8, ctr, ql_cnt, ql, s->qcap);
-            } else if (!count && (p->flags >> 8 & 0xffu) != 53) {
-                // built for 7 waves per SIMD (72 VGPRs, 5 spills; 76 without the bound: 6 waves): a frame of mostly background tiles is a stream
-                // of short workgroups, and one more resident per SIMD is worth the spills -- K4 closest hit 0.234 -> 0.223 ms, frame 1.285 -> 1.236
-                // (variant 53 = the unbounded build, A/B)
-                hipLaunchKernelGGL((k_closest_hit_nq<false, 512, 2, 2, true, false, false, 7>), grid8, block, 0, stream, s->dev, fp, o_hit, o_t, o_lin, o_rgb8, ctr, ql_cnt, ql, s->qcap);
-            } else {
-                LAUNCH_NQ(512, 2, 2, true);
-            }
-            break;
-        }
-        #undef LAUNCH_NQ
-        HIP_TRY(hipGetLastError());
-        if (ev) HIP_TRY(hipEventRecord(ev[1], stream));
-        if (pk_shadow) {
-            // a fixed number of waves pull units (the shadow rays of 64 / n_lights pixels) from the quadrant list: no grid over the image
-            const uint64_t max_units = (uint64_t)n_tiles * 4u * 2u * ((p->n_lights + 7) / 8);
-            const uint32_t wgs = (uint32_t)(max_units / 4 + 1 < (uint64_t)s->n_cu * 8 ? max_units / 4 + 1 : (uint64_t)s->n_cu * 8);      // (8 per CU: every wave slot; fewer was measured)
-            if (count)                                hipLaunchKernelGGL((k_shadow_pk<true, true, false>), dim3(wgs), block, 0, stream, s->dev, fp, o_hit, o_t, s->d_qcount, s->ws_qlist, s->qcap, s->ws_shadow, ctr);
-            else if ((p->flags >> 8 & 0xffu) == 29)   hipLaunchKernelGGL((k_shadow_pk<false, true, false, true>), dim3(wgs), block, 0, stream, s->dev, fp, o_hit, o_t, s->d_qcount, s->ws_qlist, s->qcap, s->ws_shadow, ctr);    // units in entry order (A/B)
-            else if ((p->flags >> 8 & 0xffu) == 55)   hipLaunchKernelGGL((k_shadow_pk<false, true, false, false, 1>), dim3(wgs), block, 0, stream, s->dev, fp, o_hit, o_t, s->d_qcount, s->ws_qlist, s->qcap, s->ws_shadow, ctr);    // record of i + 1 requested ahead (A/B)
-            else if ((p->flags >> 8 & 0xffu) == 56)   hipLaunchKernelGGL((k_shadow_pk<false, true, false, false, 2>), dim3(wgs), block, 0, stream, s->dev, fp, o_hit, o_t, s->d_qcount, s->ws_qlist, s->qcap, s->ws_shadow, ctr);    // + skip[i] / first triangle (A/B)
-            else if (fp.heavy_steps)                  hipLaunchKernelGGL((k_shadow_pk<false, true, false, false, 0, true>), dim3(wgs), block, 0, stream, s->dev, fp, o_hit, o_t, s->d_qcount, s->ws_qlist, s->qcap, s->ws_shadow, ctr);    // heavy quadrants dealt early (a frame alone on the device)
-            else if ((p->flags >> 8 & 0xffu) == 58)   hipLaunchKernelGGL((k_shadow_pk<false, true, false, false, -1>), dim3(wgs), block, 0, stream, s->dev, fp, o_hit, o_t, s->d_qcount, s->ws_qlist, s->qcap, s->ws_shadow, ctr);    // the shipped walk with wave clocks (SRT_DIAG_COUNTERS)
-            else if ((p->flags >> 8 & 0xffu) == 57)   hipLaunchKernelGGL((k_shadow_pk<false, true, false, false, 0>), dim3(wgs), block, 0, stream, s->dev, fp, o_hit, o_t, s->d_qcount, s->ws_qlist, s->qcap, s->ws_shadow, ctr);    // the plain walk (A/B)
-            else if ((p->flags >> 8 & 0xffu) == 25)   hipLaunchKernelGGL((k_shadow_pk<false, true, true>), dim3(wgs), block, 0, stream, s->dev, fp, o_hit, o_t, s->d_qcount, s->ws_qlist, s->qcap, s->ws_shadow, ctr);    // records through LDS windows (A/B)
-            else                                      hipLaunchKernelGGL((k_shadow_pk<false, true, false>), dim3(wgs), block, 0, stream, s->dev, fp, o_hit, o_t, s->d_qcount, s->ws_qlist, s->qcap, s->ws_shadow, ctr);
-            HIP_TRY(hipGetLastError());
-        } else if (p->n_lights && !fused) {
-            // scenes far bigger than an L2 (fp.xcd_rows): whole tile rows per XCD for the shadow rays too (variant 62 = the plain order, A/B)
-            DevParams sq = fp;
-            if ((p->flags >> 8 & 0xffu) == 62) sq.xcd_rows = 0u;
-            const dim3 gq(grid8.x, sq.xcd_rows ? (grid8.y + 7) / 8 * 8 : grid8.y);
-            if (chunked)           hipLaunchKernelGGL((k_shadow_nq<false, 512, true, 64, 6>), dim3(gq.x, gq.y, (p->n_lights + L_CHUNK - 1) / L_CHUNK), block, 0, stream,
-                                                      s->dev, sq, o_hit, o_t, s->ws_shadow, ctr, L_CHUNK);
-            else if (count)        hipLaunchKernelGGL((k_shadow_nq<true, 512, false>), gq, block, 0, stream, s->dev, sq, o_hit, o_t, s->ws_shadow, ctr);
-            else if (variant == 3) hipLaunchKernelGGL((k_shadow_nq<false, 160, false>), gq, block, 0, stream, s->dev, sq, o_hit, o_t, s->ws_shadow, ctr);
-            else if (variant == 6) hipLaunchKernelGGL((k_shadow_nq<false, 160, true>), gq, block, 0, stream, s->dev, sq, o_hit, o_t, s->ws_shadow, ctr);
-            else if (variant == 4) hipLaunchKernelGGL((k_shadow_nq<false, 512, false>), gq, block, 0, stream, s->dev, sq, o_hit, o_t, s->ws_shadow, ctr);
-            else if (all_narrow)   hipLaunchKernelGGL((k_shadow_nq<false, 512, true, 16, 6, false>), gq, block, 0, stream, s->dev, sq, o_hit, o_t, s->ws_shadow, ctr);
-            else                   hipLaunchKernelGGL((k_shadow_nq<false, 512, true, 16, 6>), gq, block, 0, stream, s->dev, sq, o_hit, o_t, s->ws_shadow, ctr);      // 80 VGPRs: six waves per SIMD (86 without the bound: five)
-            HIP_TRY(hipGetLastError());
-        }
-        if (ev) HIP_TRY(hipEventRecord(ev[2], stream));
-        std::snprintf(s->pipeline, sizeof(s->pipeline), "%s%s+k_shade_tile", fused ? "k_trace_nq" : (pk_closest ? "k_closest_hit_pk" : "k_closest_hit_nq"),
-                      fused || !p->n_lights ? "" : (pk_shadow ? "+k_shadow_pk" : "+k_shadow_nq"));
-        if (shaded) { std::snprintf(s->pipeline, sizeof(s->pipeline), "k_trace_shade_nq"); return SRT_OK; }
-        DevParams sp = fp;
-        sp.shadow_px_major = pk_shadow ? 1u : 0u;
-        if (s->rec->int_shin && variant_of(p) != 44) hipLaunchKernelGGL(k_shade_tile<1>, grid, block, 0, stream, s->dev, sp, o_hit, o_t, s->ws_shadow, o_lin, o_rgb8, zero_next, s->d_qcount, ctr);
-        else                                         hipLaunchKernelGGL(k_shade_tile<0>, grid, block, 0, stream, s->dev, sp, o_hit, o_t, s->ws_shadow, o_lin, o_rgb8, zero_next, s->d_qcount, ctr);      // (44: the general form forced, A/B)
-        HIP_TRY(hipGetLastError());
-        return SRT_OK;
-    };
+    FrameParams fp = dev_params(s, p, plan);      // (after the lights' buffer has its size)
 
     // SRT_FLAG_NO_TIMING: no event records (a caller capturing the launches into a hipGraph)
     hipEvent_t* ev = ((p->flags & SRT_FLAG_NO_TIMING) || bc) ? nullptr : s->ev[s->ring_count % RING];      // (a batch has no per-frame times)
     if (ev && !ev[0]) for (int i = 0; i < 4; i++) HIP_TRY(hipEventCreate(&ev[i]));      // a ring slot's events are made on first use
     if (ev) HIP_TRY(hipEventRecord(ev[0], stream));
-    if (spp == 1) {
-        rc = launch_frame(dp, d_hit_id, d_t, d_rgb_linear, d_rgb8, ctr_next, ev);
-        if (rc != SRT_OK) return rc;
+    if (plan.hold != HOLD_NONE) {
+        // the batch call launches this frame with the others of its class; the shading stage's parameters are the whole frame's
+        if (bc->items.empty() && bc->items_pk.empty()) { bc->wl = wl; bc->rows = rows; }
+        const FrameItem it{s->dev, fp.shade, d_hit_id, d_t, d_rgb_linear, d_rgb8, s->ws_shadow, ctr, ctr_next, s->d_qcount,
+                           plan.hold == HOLD_PK ? s->ws_qlist.p : nullptr, plan.hold == HOLD_PK ? s->qcap : 0u, 0u};
+        (plan.hold == HOLD_PK ? bc->items_pk : bc->items).push_back(it);
+        if (plan.hold == HOLD_PK && p->n_lights > bc->max_lights) bc->max_lights = p->n_lights;
+        std::snprintf(s->pipeline, sizeof(s->pipeline), "%s", plan.pipeline);
+    } else if (spp == 1) {
+        SRT_TRY(launch_stages(s, plan, fp, stream, d_hit_id, d_t, d_rgb_linear, d_rgb8, ctr, ctr_next, ev));
     } else {
         // Supersampling (extension): n x n regular sub-pixel grid, offsets (k+0.5)/n - 0.5 added to
         // dir.xy; the pre-tone-map sums are added in sub-sample order, divided by spp, then tone-mapped once.
         // hit_id / t report sub-sample 0.  Per-kernel times are those of the last sub-frame.
-        const uint32_t n = (uint32_t)std::lround(std::sqrt((double)spp));
-        const uint32_t gq = (uint32_t)((pixels * 3 + 255) / 256);
+        const uint32_t n = (uint32_t)std::lround(std::sqrt((double)spp)), gq = (uint32_t)((pixels * 3 + 255) / 256);
+        const dim3 block(256); const DevParams dp = fp.hit;
         for (uint32_t k = 0; k < spp; k++) {
-            DevParams fp = dp;
-            fp.sub_x = ((float)(k % n) + 0.5f) / (float)n - 0.5f;
-            fp.sub_y = ((float)(k / n) + 0.5f) / (float)n - 0.5f;
-            rc = launch_frame(fp, k == 0 ? d_hit_id : s->ws_sub_hit, k == 0 ? d_t : s->ws_sub_t, s->ws_sub, nullptr, nullptr,
-                              (k == spp - 1) ? ev : nullptr);
-            if (rc != SRT_OK) return rc;
-            hipLaunchKernelGGL(k_accumulate, dim3(gq), block, 0, stream, dp, s->ws_acc, s->ws_sub, (uint32_t)(pixels * 3), k == 0 ? 1 : 0);      // (< 2^32: check_params)
+            fp.sub_pixel(((float)(k % n) + 0.5f) / (float)n - 0.5f, ((float)(k / n) + 0.5f) / (float)n - 0.5f);
+            SRT_TRY(launch_stages(s, plan, fp, stream, k == 0 ? d_hit_id : s->ws_sub_hit.p, k == 0 ? d_t : s->ws_sub_t.p, s->ws_sub, nullptr, ctr, nullptr,
+                                  (k == spp - 1) ? ev : nullptr));
+            hipLaunchKernelGGL(k_accumulate, dim3(gq), block, 0, stream, dp, s->ws_acc, s->ws_sub, (uint32_t)(pixels * 3), k == 0 ? 1 : 0);      // (< 2^32: check_frame)
             HIP_TRY(hipGetLastError());
         }
         hipLaunchKernelGGL(k_resolve, dim3((uint32_t)((pixels + 255) / 256)), block, 0, stream, dp, s->ws_acc, (float)spp, (uint32_t)pixels,
@@ -1246,8 +1359,9 @@ int srt_render_device(srt_scene* s, const srt_params* p, void* stream, int32_t* 
 }
 
 // The frames of a step in as few launches as their arguments fit (srt.h).  Every frame goes through render_device_impl -- the same
-// checks, workspaces, light upload and counter sets as a single render; frames that take the fused pipeline at one size are held back
-// and launched together, the others (another pipeline, counting build, supersampling, a different size) are launched as they come.
+// checks, workspaces, light upload and counter sets as a single render; frames that plan_frame puts into one of the two held classes
+// at one size are held back and launched together, the others (another pipeline, counting build, supersampling, a different size)
+// are launched as they come.
 static int render_device_batch_impl(uint32_t n, srt_scene* const* scenes, const srt_params* params, void* stream_,
                                     int32_t* const* d_hit_id, float* const* d_t, float* const* d_rgb_linear, uint8_t* const* d_rgb8) {
     if (!n) return SRT_OK;
@@ -1256,9 +1370,7 @@ static int render_device_batch_impl(uint32_t n, srt_scene* const* scenes, const 
     for (uint32_t i = 0; i < n; i++) {
         if (!scenes[i] || scenes[i]->device != scenes[0]->device) return SRT_ERR_ARG;
         for (uint32_t k = 0; k < i; k++) if (scenes[k] == scenes[i]) return SRT_ERR_ARG;      // a handle's workspace serves one frame at a time
-        const int rc = check_params(&params[i]);                                               // nothing is enqueued if any frame is malformed
-        if (rc != SRT_OK) return rc;
-        if ((params[i].flags & SRT_FLAG_SMOOTH_NORMALS) && (!scenes[i]->dev.tri_normals || variant_of(&params[i]) == 1)) return SRT_ERR_ARG;
+        SRT_TRY(check_frame(scene_facts(scenes[i]), &params[i]));                              // nothing is enqueued if any frame is malformed
     }
     hipStream_t stream = (hipStream_t)stream_;
     bool batch_int_shin = true;                               // the specialised shading kernel only if every scene of the batch qualifies
@@ -1267,38 +1379,34 @@ static int render_device_batch_impl(uint32_t n, srt_scene* const* scenes, const 
     for (uint32_t i = 0; i < n; i++) {
         const int rc = render_device_impl(scenes[i], &params[i], stream_, d_hit_id ? d_hit_id[i] : nullptr, d_t ? d_t[i] : nullptr,
                                           d_rgb_linear ? d_rgb_linear[i] : nullptr, d_rgb8 ? d_rgb8[i] : nullptr, &bc);
-        if (rc != SRT_OK) { bc.items.clear(); bc.items_pk.clear(); for (uint32_t k = 0; k <= i; k++) scenes[k]->ctr_dirty = true; return rc; }   // held frames are dropped: their counter sets may be half-used
+        if (rc != SRT_OK) { for (uint32_t k = 0; k <= i; k++) scenes[k]->ctr_dirty = true; return rc; }   // held frames are dropped: their counter sets may be half-used
     }
-    // the held frames, FRAME_TAB_MAX at a time: their arguments by value in the launch (srt_kernels.h: FrameTab)
+    // The held frames, class by class in the launches of their class, FRAME_TAB_MAX at a time: their arguments by value in the launch
+    // (srt_kernels.h: FrameTab)
     int rc = SRT_OK;
-    const dim3 block(256);
-    for (size_t first = 0; first < bc.items_pk.size() && rc == SRT_OK; first += FRAME_TAB_MAX) {
-        const uint32_t held_pk = (uint32_t)std::min<size_t>(FRAME_TAB_MAX, bc.items_pk.size() - first);
-        FrameTab tab;
-        std::memset(&tab, 0, sizeof(tab));
-        std::memcpy(tab.it, bc.items_pk.data() + first, held_pk * sizeof(FrameItem));
-        const dim3 g8((bc.wl + 7) / 8, (bc.rows + 7) / 8, held_pk), g16((bc.wl + 15) / 16, (bc.rows + 15) / 16, held_pk);
-        const uint64_t n_tiles = (uint64_t)g8.x * g8.y, max_units = n_tiles * 4u * 2u * ((bc.max_lights + 7) / 8);
-        const uint64_t wgs_all = (uint64_t)scenes[0]->n_cu * 8;         // the chip's worth of waves, shared by the frames
-        uint32_t wgs = (uint32_t)((wgs_all + held_pk - 1) / held_pk);
-        if ((uint64_t)wgs > max_units / 4 + 1) wgs = (uint32_t)(max_units / 4 + 1);
-        // grid = (tiles per row, frames, tile rows): the same tile row of all the frames is in flight together (srt_kernels.h)
-        hipLaunchKernelGGL((k_closest_hit_nq_batch<512, true, true>), dim3(g8.x, held_pk, g8.y), block, 0, stream, tab);
-        hipLaunchKernelGGL((k_shadow_pk_batch<true>), dim3(wgs, held_pk), block, 0, stream, tab);
-        if (batch_int_shin) hipLaunchKernelGGL(k_shade_tile_batch<1>, g16, block, 0, stream, tab);
-        else                hipLaunchKernelGGL(k_shade_tile_batch<0>, g16, block, 0, stream, tab);
-        if (hipGetLastError() != hipSuccess) rc = SRT_ERR_DEVICE;
-    }
-    for (size_t first = 0; first < bc.items.size() && rc == SRT_OK; first += FRAME_TAB_MAX) {
-        const uint32_t held = (uint32_t)std::min<size_t>(FRAME_TAB_MAX, bc.items.size() - first);
-        FrameTab tab;
-        std::memset(&tab, 0, sizeof(tab));
-        std::memcpy(tab.it, bc.items.data() + first, held * sizeof(FrameItem));
-        const dim3 g_trace((bc.wl + 7) / 8, (bc.rows + 7) / 8, held), g_shade((bc.wl + 15) / 16, (bc.rows + 15) / 16, held);
-        hipLaunchKernelGGL((k_trace_nq_batch<512, true, 7, 16, true>), dim3(g_trace.x, held, g_trace.y), block, 0, stream, tab);
-        if (batch_int_shin) hipLaunchKernelGGL(k_shade_tile_batch<1>, g_shade, block, 0, stream, tab);
-        else                hipLaunchKernelGGL(k_shade_tile_batch<0>, g_shade, block, 0, stream, tab);
-        if (hipGetLastError() != hipSuccess) rc = SRT_ERR_DEVICE;
+    const dim3 block(256), g8((bc.wl + 7) / 8, (bc.rows + 7) / 8), g16((bc.wl + 15) / 16, (bc.rows + 15) / 16);
+    for (const Hold cls : {HOLD_PK, HOLD_FUSED}) {
+        const std::vector<FrameItem>& items = cls == HOLD_PK ? bc.items_pk : bc.items;
+        for (size_t first = 0; first < items.size() && rc == SRT_OK; first += FRAME_TAB_MAX) {
+            const uint32_t held = (uint32_t)std::min<size_t>(FRAME_TAB_MAX, items.size() - first);
+            FrameTab tab;
+            std::memset(&tab, 0, sizeof(tab));
+            std::memcpy(tab.it, items.data() + first, held * sizeof(FrameItem));
+            // grid = (tiles per row, frames, tile rows): the same tile row of all the frames is in flight together (srt_kernels.h)
+            if (cls == HOLD_PK) {
+                const uint64_t n_tiles = (uint64_t)g8.x * g8.y, max_units = n_tiles * 4u * 2u * ((bc.max_lights + 7) / 8);
+                const uint64_t wgs_all = (uint64_t)scenes[0]->n_cu * 8;         // the chip's worth of waves, shared by the frames
+                uint32_t wgs = (uint32_t)((wgs_all + held - 1) / held);
+                if ((uint64_t)wgs > max_units / 4 + 1) wgs = (uint32_t)(max_units / 4 + 1);
+                hipLaunchKernelGGL((k_closest_hit_nq_batch<512, true, true>), dim3(g8.x, held, g8.y), block, 0, stream, tab);
+                hipLaunchKernelGGL((k_shadow_pk_batch<true>), dim3(wgs, held), block, 0, stream, tab);
+            }
+            decltype(&k_shade_tile_batch<0>) shade;
+            if (batch_int_shin) shade = &k_shade_tile_batch<1>; else shade = &k_shade_tile_batch<0>;
+            if (cls == HOLD_FUSED) hipLaunchKernelGGL((k_trace_nq_batch<512, true, 7, 16, true>), dim3(g8.x, held, g8.y), block, 0, stream, tab);
+            hipLaunchKernelGGL(shade, dim3(g16.x, g16.y, held), block, 0, stream, tab);
+            if (hipGetLastError() != hipSuccess) rc = SRT_ERR_DEVICE;
+        }
     }
     if (rc != SRT_OK) for (uint32_t k = 0; k < n; k++) scenes[k]->ctr_dirty = true;       // the set the shading would have zeroed
     return rc;
@@ -1361,7 +1469,7 @@ int srt_sync(srt_scene* s, srt_stats* stats) {
 
 static int render_async_impl(srt_scene* s, const srt_params* p, int32_t* hit_id, float* t, float* rgb_linear, uint8_t* rgb8, bool wait, srt_stats* stats) {
     if (!s) return SRT_ERR_ARG;
-    int rc = check_params(p);
+    int rc = check_frame(scene_facts(s), p);
     if (rc != SRT_OK) return rc;
     HIP_TRY(hipSetDevice(s->device));
     hipStream_t st;

@@ -34,7 +34,7 @@ struct DevScene {
     const uint32_t* tex_h;
     const unsigned long long* tex_size;
     uint32_t n_nodes, n_tris, n_objects;
-    uint32_t pad_;                // explicit: argument tables are compared bytewise (frame_table), so no implicit padding anywhere
+    uint32_t pad_;                // explicit: the struct travels by value inside FrameTab, whose size is asserted: no implicit padding anywhere
 };
 static_assert(sizeof(DevScene) == 20 * 8 + 16, "DevScene has no implicit padding");
 
@@ -1638,8 +1638,8 @@ __global__ __launch_bounds__(256, MINW) void k_trace_shade_nq(DevScene s, DevPar
 // launch lasts a whole number of such rounds.  The 1080p frame has ~2,500 heavy tiles (1.6 rounds in 0.125 ms); the eighth of it
 // that one of eight GPUs owns has ~310 and still takes 0.072 ms as its own launch, nine eighths launched together take 0.199 ms
 // (two rounds) where 0.142 would be their share -- measured with tools/strip_probe.py, whatever the height of the scanline blocks.
-// With ALL frames of a step in one grid the rounds are filled.  A frame's arguments come from a table in device memory (368 bytes
-// a frame; the kernarg segment's 4 KiB would hold ten), read with scalar loads: the index is blockIdx.z, the table is read-only.
+// With ALL frames of a step in one grid the rounds are filled.  A frame's arguments are one entry (416 bytes) of a table that
+// travels by value with the launch (FrameTab below), read with scalar loads: the index is the frame's grid coordinate.
 struct FrameItem {
     DevScene s; DevParams p;
     int32_t* hit_id; float* t_out; float* rgb_linear; uint8_t* rgb8;
