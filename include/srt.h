@@ -307,6 +307,49 @@ void  srt_host_free(void* p);
 /* Wait for the last srt_render_device / srt_render_async on this scene and collect its stats. */
 int srt_sync(srt_scene* s, srt_stats* stats);
 
+/* ---- RAY QUERIES, an opt-in EXTENSION (the reference traces only the pixels of its own camera) -------------------------------------
+ * What does THIS ray hit, and is the way from here towards there blocked -- for rays the caller supplies (picking, placing an object on
+ * the ground, a probe or range sensor, visibility between arbitrary points), against the records a scene keeps on the device.
+ * rays = n x 6 floats: origin xyz, direction xyz, in the space of the scene's records.
+ * Directions are NOT normalised; t is in units of the direction, as everywhere in the reference.
+ * PARITY: the reference cannot take a ray from a caller, so what is pinned, bit for bit, is the oracle on the same flat scene.  A ray
+ * (o, d) is the one pixel of a 1 x 1 camera-mode frame with focal 1 and ray_matrix columns (0, 0, d, o); a W x H camera-mode frame is
+ * W * H rays with directions (M[0] * dx + M[1] * dy) + M[2] * dz.  The query's hit id and t bits are those frames' -- the literal slab
+ * test with the ray's origin, the general Moller-Trumbore test on the triangle's points, no t pruning, strict '<' (lowest id among equal
+ * t) -- and the occlusion bit is shadowIntersection:321-342 on that scene.  Results never depend on the order of the rays in a call.
+ * Non-finite rays are memory-safe and give whatever the walk gives.  n == 0: SRT_OK, nothing happens.
+ * Errors, all before anything is touched: NULL handle, NULL rays with n > 0, flags other than 0 or SRT_FLAG_COUNT_WORK: SRT_ERR_ARG.
+ *
+ * Closest hit.  Any output pointer may be NULL.
+ *   hit_id  n       int32  canonical triangle id, -1 = miss
+ *   t       n       f32    distance in units of the direction, +inf on a miss
+ *   bary    n x 3   f32    calculateBarycentricCoords (:79-117) (u, v, w) at origin + direction * t, the operations the textured shading
+ *                          path runs; (0, 0, 0) on a miss
+ * Occlusion.  occluded[i] = 1 if any object's tree but skip_obj[i]'s yields a candidate triangle whose Moller-Trumbore result is not
+ * -inf (NaN included, as the reference), else 0; t is unbounded, as in the reference.  skip_obj: the object whose own tree is left out
+ * (the hit object's, for a shadow ray), n entries or NULL; an entry of -1 -- or any entry outside [0, n_objects), which is not
+ * validated on the host -- leaves nothing out.
+ * A NULL occluded / d_occluded leaves the call nothing to report: it returns SRT_OK and launches nothing.
+ *
+ * The _device entry points take device pointers (rays that are 8-byte aligned are read with wide loads), are asynchronous on `stream`
+ * (NULL = the scene's own stream), ordered behind the updates, poses and renders already enqueued there, allocate nothing and copy
+ * nothing; without SRT_FLAG_COUNT_WORK they may be captured into a hipGraph.  They leave alone what srt_sync and srt_scene_pipeline
+ * report and the alternating counter sets of the renders; through a handle of srt_scene_share they read the one copy of the records.
+ * The host entry points take host pointers, stage through the handle's pinned staging block, wait, and fill *stats (may be NULL):
+ * primary_rays = n, hit_rays, and under SRT_FLAG_COUNT_WORK node_tests_primary / tri_tests_primary, from a counter set private to
+ * queries; every other field is 0.  That set belongs to the handle, and only the host entry points report it (they zero it, count
+ * into it and read it back within the call).  A _device call with SRT_FLAG_COUNT_WORK runs the counting build and zeroes and fills
+ * the same set, which no call hands to a device caller: it is there to measure the counting build, and it must not be in flight
+ * while another query runs on the same handle.  Queries on several streams at once: without the flag, or one handle of
+ * srt_scene_share each. */
+int srt_trace_rays_device(srt_scene* s, uint32_t n, const float* d_rays, uint32_t flags, void* stream,
+                          int32_t* d_hit_id, float* d_t, float* d_bary /* n x 3 (u,v,w) or NULL */);
+int srt_trace_rays(srt_scene* s, uint32_t n, const float* rays, uint32_t flags,
+                   int32_t* hit_id, float* t, float* bary, srt_stats* stats);
+int srt_occluded_device(srt_scene* s, uint32_t n, const float* d_rays, const int32_t* d_skip_obj /* n or NULL */,
+                        void* stream, uint8_t* d_occluded);
+int srt_occluded(srt_scene* s, uint32_t n, const float* rays, const int32_t* skip_obj, uint8_t* occluded);
+
 /* Device-resident size of the scene records and the per-record algorithmic byte sizes used by
  * the bytes model: 32 B per node test, 36 B per triangle test. */
 uint64_t srt_scene_device_bytes(const srt_scene* s);

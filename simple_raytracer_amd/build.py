@@ -33,7 +33,7 @@ def _stale(target, sources):
 
 def build_hip(force=False, verbose=False):
     srcs = [os.path.join(CSRC, "srt_hip.hip")]
-    deps = srcs + [os.path.join(CSRC, "srt_device.h"), os.path.join(CSRC, "srt_kernels.h"), os.path.join(CSRC, "srt_packet.h"), os.path.join(HERE, "..", "include", "srt.h")]
+    deps = srcs + [os.path.join(CSRC, "srt_device.h"), os.path.join(CSRC, "srt_kernels.h"), os.path.join(CSRC, "srt_packet.h"), os.path.join(CSRC, "srt_query.h"), os.path.join(HERE, "..", "include", "srt.h")]
     if not force and not _stale(LIB_HIP, deps):
         return LIB_HIP
     cmd = [hipcc()] + HIPCC_FLAGS + ["-o", LIB_HIP] + srcs
@@ -112,7 +112,7 @@ def build_c_example(force=False, verbose=False):
 def stale_artefacts():
     """Names of the product's native artefacts that are missing or older than their sources (nothing is built)."""
     hdir = os.path.join(CSRC, "host")
-    hip_deps = [os.path.join(CSRC, f) for f in ("srt_hip.hip", "srt_device.h", "srt_kernels.h", "srt_packet.h")] + [os.path.join(HERE, "..", "include", "srt.h")]
+    hip_deps = [os.path.join(CSRC, f) for f in ("srt_hip.hip", "srt_device.h", "srt_kernels.h", "srt_packet.h", "srt_query.h")] + [os.path.join(HERE, "..", "include", "srt.h")]
     host_deps = [os.path.join(hdir, f) for f in ("srt_host.cpp", "srt_jpeg.cpp", "srt_host_c.cpp", "srt_host.h")]
     out = []
     if _stale(LIB_HIP, hip_deps):

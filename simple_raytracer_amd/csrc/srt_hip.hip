@@ -29,6 +29,7 @@ using namespace srt;
 
 #include "srt_kernels.h"
 #include "srt_packet.h"
+#include "srt_query.h"
 
 // =================================================================================================
 // Host side of the ABI
@@ -153,6 +154,10 @@ struct srt_scene {
     DevArray<unsigned long long> ws_shadow;
     DevArray<uint32_t, 3> ws_qlist; DevArray<uint32_t> d_qcount; uint32_t qcap = 0;      // quadrants with hits: 64 shard lists of qcap entries, their counters
     DevArray<float, 3> ws_acc, ws_sub; DevArray<int32_t> ws_sub_hit; DevArray<float> ws_sub_t;
+    // ray queries (srt_trace_rays / srt_occluded, the host entry points): the rays and results of one call, capacities count rays; and the
+    // counter set private to queries (laid out like a render's), which no render reads, zeroes or reports
+    DevArray<float, 6> rq_rays; DevArray<int32_t> rq_hit; DevArray<float> rq_t; DevArray<float, 3> rq_bary; DevArray<int32_t> rq_skip; DevArray<uint8_t> rq_occ;
+    DevArray<unsigned long long> d_qctr;
     int n_cu = 256;
     EventRing ev;
     uint32_t ring_count = 0;         // renders since the last srt_sync
@@ -495,6 +500,8 @@ static hipError_t init_handle_state(srt_scene* s) {
     if (e == hipSuccess) e = s->d_qcount.reserve(QL_COUNTERS * QL_STRIDE);
     if (e == hipSuccess) e = hipMemset(s->d_qcount, 0, QL_COUNTERS * QL_STRIDE * sizeof(uint32_t));
     if (e == hipSuccess) e = s->h_counters.reserve(NCTR);
+    if (e == hipSuccess) e = s->d_qctr.reserve(NCTR);
+    if (e == hipSuccess) e = hipMemset(s->d_qctr, 0, NCTR * sizeof(unsigned long long));
     hipDeviceProp_t prop;
     if (e == hipSuccess) e = hipGetDeviceProperties(&prop, s->device);
     if (e == hipSuccess && prop.multiProcessorCount > 0) s->n_cu = prop.multiProcessorCount;
@@ -1506,6 +1513,116 @@ int srt_render_async(srt_scene* s, const srt_params* p, int32_t* hit_id, float* 
 
 int srt_render(srt_scene* s, const srt_params* p, int32_t* hit_id, float* t, float* rgb_linear, uint8_t* rgb8, srt_stats* stats) {
     return guarded([&] { return render_async_impl(s, p, hit_id, t, rgb_linear, rgb8, true, stats); });
+}
+
+// ---- ray queries (include/srt.h, RAY QUERIES; kernels in srt_query.h) ------------------------------------------------------------
+// The device entry points enqueue and return: a memset of the private counter set when it is used, one launch.  They touch neither the
+// render counters nor the state srt_sync reports from (pending, the event ring, the pipeline string).
+static int check_query(const srt_scene* s, uint32_t n, const float* rays, uint32_t flags) {
+    if (!s || (n && !rays) || (flags & ~(uint32_t)SRT_FLAG_COUNT_WORK)) return SRT_ERR_ARG;
+    return SRT_OK;
+}
+static inline uint32_t rays_wide(const float* d_rays) { return ((uintptr_t)d_rays & 7u) == 0 ? 1u : 0u; }      // srt_query.h load_ray
+
+// count_hits: the host entry point wants hit_rays also without SRT_FLAG_COUNT_WORK
+static int trace_rays_device_impl(srt_scene* s, uint32_t n, const float* d_rays, uint32_t flags, hipStream_t stream, int32_t* d_hit_id, float* d_t,
+                                  float* d_bary, bool count_hits) {
+    SRT_TRY(check_query(s, n, d_rays, flags));
+    if (!n) return SRT_OK;
+    HIP_TRY(hipSetDevice(s->device));
+    if (!stream) SRT_TRY(own_stream(s, &stream));
+    const bool count = (flags & SRT_FLAG_COUNT_WORK) != 0;
+    unsigned long long* ctr = (count || count_hits) ? s->d_qctr.p : nullptr;
+    if (ctr) HIP_TRY(hipMemsetAsync(ctr, 0, NCTR * sizeof(unsigned long long), stream));
+    decltype(&k_query_closest<false, false>) k;
+    if (count) { if (d_bary) k = &k_query_closest<true, true>; else k = &k_query_closest<true, false>; }
+    else { if (d_bary) k = &k_query_closest<false, true>; else k = &k_query_closest<false, false>; }
+    hipLaunchKernelGGL(k, dim3((uint32_t)(((uint64_t)n + 255u) / 256u)), dim3(256), 0, stream, s->dev, n, d_rays, rays_wide(d_rays), d_hit_id, d_t, d_bary, ctr);
+    HIP_TRY(hipGetLastError());
+    return SRT_OK;
+}
+
+static int occluded_device_impl(srt_scene* s, uint32_t n, const float* d_rays, const int32_t* d_skip_obj, hipStream_t stream, uint8_t* d_occluded) {
+    SRT_TRY(check_query(s, n, d_rays, 0));
+    if (!n || !d_occluded) return SRT_OK;
+    HIP_TRY(hipSetDevice(s->device));
+    if (!stream) SRT_TRY(own_stream(s, &stream));
+    hipLaunchKernelGGL(k_query_any, dim3((uint32_t)(((uint64_t)n + 255u) / 256u)), dim3(256), 0, stream, s->dev, n, d_rays, rays_wide(d_rays), d_skip_obj, d_occluded);
+    HIP_TRY(hipGetLastError());
+    return SRT_OK;
+}
+
+// The host entry points: the caller's rays go through the pinned staging block (stage_acquire, as every update does) into the handle's
+// own ray buffer on the scene's stream, the device entry point runs behind them, the call waits and copies the results out.
+static int stage_rays(srt_scene* s, uint32_t n, const float* rays, const int32_t* skip_obj, hipStream_t st) {
+    auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t o_rays = 0, o_skip = pad((size_t)n * 24), total = o_skip + (skip_obj ? pad((size_t)n * 4) : 0);
+    SRT_TRY(grow(s, n, s->rq_rays));
+    if (skip_obj) SRT_TRY(grow(s, n, s->rq_skip));
+    char* h = nullptr;
+    SRT_TRY(stage_acquire(s, total, &h));
+    std::memcpy(h + o_rays, rays, (size_t)n * 24);
+    HIP_TRY(hipMemcpyAsync(s->rq_rays, h + o_rays, (size_t)n * 24, hipMemcpyHostToDevice, st));
+    if (skip_obj) {
+        std::memcpy(h + o_skip, skip_obj, (size_t)n * 4);
+        HIP_TRY(hipMemcpyAsync(s->rq_skip, h + o_skip, (size_t)n * 4, hipMemcpyHostToDevice, st));
+    }
+    HIP_TRY(hipEventRecord(s->staged, st));
+    return SRT_OK;
+}
+
+static int trace_rays_impl(srt_scene* s, uint32_t n, const float* rays, uint32_t flags, int32_t* hit_id, float* t, float* bary, srt_stats* stats) {
+    SRT_TRY(check_query(s, n, rays, flags));
+    if (stats) std::memset(stats, 0, sizeof(*stats));
+    if (!n) return SRT_OK;
+    HIP_TRY(hipSetDevice(s->device));
+    hipStream_t st;
+    SRT_TRY(own_stream(s, &st));
+    if (hit_id) SRT_TRY(grow(s, n, s->rq_hit));
+    if (t) SRT_TRY(grow(s, n, s->rq_t));
+    if (bary) SRT_TRY(grow(s, n, s->rq_bary));
+    SRT_TRY(stage_rays(s, n, rays, nullptr, st));
+    SRT_TRY(trace_rays_device_impl(s, n, s->rq_rays, flags, st, hit_id ? s->rq_hit.p : nullptr, t ? s->rq_t.p : nullptr, bary ? s->rq_bary.p : nullptr, true));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (hit_id) HIP_TRY(hipMemcpy(hit_id, s->rq_hit, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (t) HIP_TRY(hipMemcpy(t, s->rq_t, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+    if (bary) HIP_TRY(hipMemcpy(bary, s->rq_bary, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToHost));
+    if (stats) {
+        std::array<unsigned long long, NCTR> c;
+        HIP_TRY(hipMemcpy(c.data(), s->d_qctr, NCTR * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+        stats->primary_rays = n;
+        for (int k = 0; k < HIT_SHARDS; k++) stats->hit_rays += c[CTR_HIT_BASE + 8 * k];
+        stats->node_tests_primary = c[1];
+        stats->tri_tests_primary = c[2];
+    }
+    return SRT_OK;
+}
+
+static int occluded_impl(srt_scene* s, uint32_t n, const float* rays, const int32_t* skip_obj, uint8_t* occluded) {
+    SRT_TRY(check_query(s, n, rays, 0));
+    if (!n || !occluded) return SRT_OK;
+    HIP_TRY(hipSetDevice(s->device));
+    hipStream_t st;
+    SRT_TRY(own_stream(s, &st));
+    SRT_TRY(grow(s, n, s->rq_occ));
+    SRT_TRY(stage_rays(s, n, rays, skip_obj, st));
+    SRT_TRY(occluded_device_impl(s, n, s->rq_rays, skip_obj ? s->rq_skip.p : nullptr, st, s->rq_occ));
+    HIP_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipMemcpy(occluded, s->rq_occ, (size_t)n, hipMemcpyDeviceToHost));
+    return SRT_OK;
+}
+
+int srt_trace_rays_device(srt_scene* s, uint32_t n, const float* d_rays, uint32_t flags, void* stream, int32_t* d_hit_id, float* d_t, float* d_bary) {
+    return guarded([&] { return trace_rays_device_impl(s, n, d_rays, flags, (hipStream_t)stream, d_hit_id, d_t, d_bary, false); });
+}
+int srt_trace_rays(srt_scene* s, uint32_t n, const float* rays, uint32_t flags, int32_t* hit_id, float* t, float* bary, srt_stats* stats) {
+    return guarded([&] { return trace_rays_impl(s, n, rays, flags, hit_id, t, bary, stats); });
+}
+int srt_occluded_device(srt_scene* s, uint32_t n, const float* d_rays, const int32_t* d_skip_obj, void* stream, uint8_t* d_occluded) {
+    return guarded([&] { return occluded_device_impl(s, n, d_rays, d_skip_obj, (hipStream_t)stream, d_occluded); });
+}
+int srt_occluded(srt_scene* s, uint32_t n, const float* rays, const int32_t* skip_obj, uint8_t* occluded) {
+    return guarded([&] { return occluded_impl(s, n, rays, skip_obj, occluded); });
 }
 
 void* srt_host_alloc(size_t bytes) {

@@ -1,0 +1,197 @@
+// srt_query.h -- ray queries (include/srt.h, RAY QUERIES): closest hit and occlusion for rays the CALLER supplies.  Included by
+// srt_hip.hip only, after srt_kernels.h.
+//
+// The unit of work is a ray, not a pixel of a tile: lane i of the grid owns ray i (origin xyz, direction xyz, 24 B), whatever its
+// neighbours are.  Nothing here may assume a common origin, so there is no tile, no root mask and no union-box shortcut; what is kept
+// of the render kernels is the walk itself -- the stackless pre-order walk over the 32 B DevNode records with skip links, the slab
+// test through slab_pass (reciprocal filter, exact fallback) -- and, for the closest hit, the per-wave triangle queue of
+// k_closest_hit_q.  The candidate set of a ray is the reference's (every leaf whose ancestors all pass the literal slab test, no t
+// pruning) and the merge is the order-independent (t, id) minimum, so a ray's result depends on the ray alone, never on its place in
+// the batch.
+#pragma once
+#include "srt_kernels.h"
+
+// A ray as lane `i` reads it.  wide: the array is 8-byte aligned, so the 24 B are three dwordx2 loads (a wave reads its 1.5 KB
+// contiguously either way); a caller's pointer that is only float-aligned takes six dword loads.
+__device__ __forceinline__ void load_ray(const float* __restrict__ rays, size_t i, bool wide, V3& o, V3& d) {
+    if (wide) {
+        const float2* r2 = reinterpret_cast<const float2*>(rays) + 3 * i;
+        const float2 a = r2[0], b = r2[1], c = r2[2];
+        o = mk(a.x, a.y, b.x); d = mk(b.y, c.x, c.y);
+    } else {
+        const float* r = rays + 6 * i;
+        o = mk(r[0], r[1], r[2]); d = mk(r[3], r[4], r[5]);
+    }
+}
+
+// =================================================================================================
+// Closest hit of caller-supplied rays: the oracle's closest_in_tree over the objects in order, with the ray's own origin.
+// One ray per lane.  The lanes of a wave walk on their own (the rays may be unrelated); a lane whose ray passes a leaf's box pushes
+// (triangle, lane) pairs into the wave's LDS queue, and whenever 64 pairs are queued the whole wave runs the general Moller-Trumbore
+// test on them, one pair per lane, with the OWNING lane's ray (kept in LDS), and merges with a 64-bit LDS atomicMin on
+// (t bits << 32 | triangle id) -- k_closest_hit_q's scheme, +-0 handling included.
+// counters: null, or a set laid out like a render's -- [1] / [2] node / triangle tests (COUNT), [8 + 8 * shard] hit rays.
+// =================================================================================================
+template <bool COUNT, bool BARY>
+__global__ __launch_bounds__(256) void k_query_closest(DevScene s, uint32_t n_rays, const float* __restrict__ rays, uint32_t wide,
+                                                       int32_t* __restrict__ hit_id, float* __restrict__ t_out, float* __restrict__ bary,
+                                                       unsigned long long* __restrict__ counters) {
+    __shared__ uint32_t q_all[4][QCAP];
+    __shared__ unsigned long long best_all[256];
+    __shared__ float ray_all[4][6][64];
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint32_t* q = q_all[wave];
+    unsigned long long* best = best_all + wave * 64;
+    float (*wray)[64] = ray_all[wave];
+    const size_t ri = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const bool live = ri < (size_t)n_rays;
+    unsigned long long n_node = 0, n_tri = 0;
+    best[lane] = ~0ull;
+    V3 o = mk(0.0f, 0.0f, 0.0f), d = mk(0.0f, 0.0f, 1.0f);
+    if (live) load_ray(rays, ri, wide != 0, o, d);
+    wray[0][lane] = o.x; wray[1][lane] = o.y; wray[2][lane] = o.z;
+    wray[3][lane] = d.x; wray[4][lane] = d.y; wray[5][lane] = d.z;
+    const RayRcp rc = ray_rcp(d);
+    const float4* nodes4 = reinterpret_cast<const float4*>(s.nodes);
+    const float4* tris4 = reinterpret_cast<const float4*>(s.tris);
+    const int32_t n = (int32_t)s.n_nodes;
+    int32_t i = live ? 0 : n;
+    int32_t leaf_off = 0;
+    uint32_t qn = 0;                                    // wave-uniform queue length
+    float4 na = make_float4(0.0f, 0.0f, 0.0f, 0.0f), nb = na;      // node i (valid while i < n)
+    if (i < n) { na = nodes4[0]; nb = nodes4[1]; }      // (a lane without a ray, or a scene without nodes, reads no record)
+    __builtin_amdgcn_wave_barrier();
+    for (;;) {
+        const bool active = i < n;
+        const unsigned long long act = __ballot(active);
+        if (act) {
+            uint32_t cnt = 0, first = 0;
+            if (active) {
+                const float4 a = na, b = nb;
+                const int32_t skip = __float_as_int(b.z), leaf = __float_as_int(b.w);
+                if (COUNT && leaf_off == 0) n_node++;
+                int32_t next;
+                bool stay = false;
+                // (a leaf pushed in slices is tested again per slice: same ray, same box, same answer)
+                if (slab_pass<true>(o, d, rc, a.x, a.y, a.z, a.w, b.x, b.y)) {
+                    next = i + 1;
+                    if (leaf >= 0) {
+                        const int32_t c = (leaf & LEAF_MAX) - leaf_off;
+                        first = (uint32_t)((leaf >> LEAF_SHIFT) + leaf_off);
+                        cnt = (uint32_t)(c < PUSH_MAX ? c : PUSH_MAX);
+                        if (c > PUSH_MAX) { leaf_off += PUSH_MAX; stay = true; } else leaf_off = 0;
+                    }
+                } else {
+                    next = skip;
+                }
+                if (!stay) {
+                    if (next < n) { na = nodes4[2 * (size_t)next]; nb = nodes4[2 * (size_t)next + 1]; }
+                    i = next;
+                }
+            }
+            // wave-wide exclusive prefix sum of cnt (0..8) by bit planes
+            uint32_t pre = 0, tot = 0;
+            #pragma unroll
+            for (int bit = 0; bit < 4; bit++) {
+                const unsigned long long m = __ballot((cnt >> bit) & 1u);
+                pre += lane_prefix(m) << bit;
+                tot += (uint32_t)__popcll(m) << bit;
+            }
+            for (uint32_t k = 0; k < cnt; k++) q[qn + pre + k] = ((first + k) << 6) | lane;
+            qn += tot;
+        } else if (qn == 0) {
+            break;
+        }
+        __builtin_amdgcn_wave_barrier();
+        while (qn >= 64 || (!act && qn)) {
+            const uint32_t m = qn < 64 ? qn : 64;
+            qn -= m;
+            if (lane < m) {
+                const uint32_t e = q[qn + lane];
+                const uint32_t src = e & 63u, tri = e >> 6;
+                const V3 os = mk(wray[0][src], wray[1][src], wray[2][src]), ds = mk(wray[3][src], wray[4][src], wray[5][src]);
+                const size_t ti = (size_t)tri * 3;
+                const float4 t0 = tris4[ti], t1 = tris4[ti + 1];
+                const float e2z = reinterpret_cast<const float*>(tris4 + ti + 2)[0];
+                if (COUNT) n_tri++;
+                const float t = ray_triangle(os, ds, mk(t0.x, t0.y, t0.z), mk(t0.w, t1.x, t1.y), mk(t1.z, t1.w, e2z));
+                // candidate iff t != -inf && t < +inf (the initial distanceComparison, :408); NaN fails '<'
+                if (t != SRT_NEG_INF && t < __builtin_inff()) {
+                    const uint32_t tb = (t == 0.0f) ? 0u : __float_as_uint(t);     // -0.0 ties with +0.0
+                    atomicMin(&best[src], ((unsigned long long)tb << 32) | tri);
+                }
+            }
+            __builtin_amdgcn_wave_barrier();
+        }
+    }
+    __builtin_amdgcn_wave_barrier();
+    bool is_hit = false;
+    if (live) {
+        const unsigned long long key = best[lane];
+        int32_t id = -1;
+        float t = __builtin_inff();
+        V3 bc = mk(0.0f, 0.0f, 0.0f);
+        if (key != ~0ull) {
+            id = (int32_t)(uint32_t)key;
+            // the winner's t with its own bits (incl. the sign of a zero): same function, same inputs
+            const size_t ti = (size_t)id * 3;
+            const float4 t0 = tris4[ti], t1 = tris4[ti + 1];
+            const float e2z = reinterpret_cast<const float*>(tris4 + ti + 2)[0];
+            const V3 p1 = mk(t0.x, t0.y, t0.z), e1 = mk(t0.w, t1.x, t1.y), e2 = mk(t1.z, t1.w, e2z);
+            t = ray_triangle(o, d, p1, e1, e2);
+            if (BARY) bc = barycentric(p1, e1, e2, o + d * t);       // calculateBarycentricCoords at the hit point, as the textured shading path
+        }
+        if (hit_id) hit_id[ri] = id;
+        if (t_out) t_out[ri] = t;
+        if (BARY) { bary[ri * 3] = bc.x; bary[ri * 3 + 1] = bc.y; bary[ri * 3 + 2] = bc.z; }
+        is_hit = id >= 0;
+    }
+    if (counters) count_hits(counters, is_hit, blockIdx.x);
+    if (COUNT) { wave_add(counters + 1, n_node); wave_add(counters + 2, n_tri); }
+}
+
+// =================================================================================================
+// Occlusion of caller-supplied rays: shadowIntersection:321-342 over every object but skip_obj[i] -- the oracle's anyhit_in_tree,
+// t unbounded, any Moller-Trumbore result other than -inf counts (NaN included).  One ray per lane, per-lane walk as any_hit_range
+// does it (the skipped object's node range is stepped over), the lane leaves at its first hit.
+// An entry of skip_obj outside [0, n_objects) skips nothing.
+// =================================================================================================
+__global__ __launch_bounds__(256) void k_query_any(DevScene s, uint32_t n_rays, const float* __restrict__ rays, uint32_t wide,
+                                                   const int32_t* __restrict__ skip_obj, uint8_t* __restrict__ occluded) {
+    const size_t ri = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (ri >= (size_t)n_rays) return;
+    V3 o, d;
+    load_ray(rays, ri, wide != 0, o, d);
+    const RayRcp rc = ray_rcp(d);
+    int2 self = make_int2(-1, -1);
+    if (skip_obj) {
+        const int32_t k = skip_obj[ri];
+        if (k >= 0 && (uint32_t)k < s.n_objects) self = s.obj_range[k];
+    }
+    const float4* nodes4 = reinterpret_cast<const float4*>(s.nodes);
+    const float4* tris4 = reinterpret_cast<const float4*>(s.tris);
+    const int32_t n = (int32_t)s.n_nodes;
+    int32_t i = 0;
+    bool hit = false;
+    while (i < n && !hit) {
+        if (i == self.x) { i = self.y; continue; }
+        const float4 a = nodes4[2 * (size_t)i], b = nodes4[2 * (size_t)i + 1];
+        const int32_t skip = __float_as_int(b.z), leaf = __float_as_int(b.w);
+        if (slab_pass<true>(o, d, rc, a.x, a.y, a.z, a.w, b.x, b.y)) {
+            if (leaf >= 0) {
+                const int32_t first = leaf >> LEAF_SHIFT, cnt = leaf & LEAF_MAX;
+                for (int32_t k = 0; k < cnt && !hit; k++) {
+                    const size_t ti = (size_t)(first + k) * 3;
+                    const float4 t0 = tris4[ti], t1 = tris4[ti + 1];
+                    const float e2z = reinterpret_cast<const float*>(tris4 + ti + 2)[0];
+                    const float t = ray_triangle(o, d, mk(t0.x, t0.y, t0.z), mk(t0.w, t1.x, t1.y), mk(t1.z, t1.w, e2z));
+                    hit = t != SRT_NEG_INF;                      // any t >= 0, NaN included (:335)
+                }
+            }
+            i = i + 1;
+        } else {
+            i = skip;
+        }
+    }
+    occluded[ri] = hit ? 1 : 0;
+}

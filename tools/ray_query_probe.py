@@ -1,0 +1,117 @@
+#!/usr/bin/env python3
+"""Ray-query timings on one GPU (DESIGN.md s5 "Ray queries"): K3 (bunny + ground) at 1920 x 1080, the frame's
+2,073,600 primary rays handed to srt_trace_rays_device in three orders -- (a) the renderer's tile order (8 x 8 pixels a wave), (b)
+row-major, (c) randomly permuted -- beside ms_primary of the reference-frame render with the wave-triangle-queue variant (flags 2 << 8:
+the same per-lane walk, specialised to rays from the origin) and of the shipped pipeline; the occlusion query on the frame's shadow rays;
+the host entry point end to end for 1 ray and for all of them.
+Usage: python tools/ray_query_probe.py [--reps N] [--trace]     (--trace: few repetitions, for a run under rocprofv3 --kernel-trace --stats)"""
+import argparse, os, sys, time
+import numpy as np
+import torch                                   # first: torch initialises HIP before the library does
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
+from simple_raytracer_amd import abi, lib      # noqa: E402
+import golden_util as gu                       # noqa: E402
+
+W, H, FOCAL = 1920, 1080, 400.0
+
+
+def frame_rays():
+    """The reference frame's rays: origin 0, direction (i, j, focal), row-major."""
+    i0, j0 = int(-np.float32(W) / 2), int(-np.float32(H) / 2)
+    r = np.zeros((H, W, 6), np.float32)
+    r[..., 3] = (i0 + np.arange(W)).astype(np.float32)[None, :]
+    r[..., 4] = (j0 + np.arange(H)).astype(np.float32)[:, None]
+    r[..., 5] = FOCAL
+    return r.reshape(-1, 6)
+
+
+def tile_order():
+    """Pixel indices in the order the render kernels deal them: 16 x 16 pixels a workgroup, 8 x 8 a wave, row-major inside."""
+    y, x = np.mgrid[0:H, 0:W]
+    key = ((y // 16) * ((W + 15) // 16) + x // 16) * 256 + (((y % 16) // 8) * 2 + (x % 16) // 8) * 64 + (y % 8) * 8 + x % 8
+    return np.argsort(key.reshape(-1), kind="stable")
+
+
+def timed(fn, reps, stream):
+    """ms a call: events on `stream`, the stream the calls are enqueued on (a stream of its own: NULL would be the scene's own stream)."""
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    fn(); fn(); stream.synchronize()
+    a.record(stream)
+    for _ in range(reps):
+        fn()
+    b.record(stream); stream.synchronize()
+    return a.elapsed_time(b) / reps
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--trace", action="store_true")
+    a = ap.parse_args()
+    reps = 3 if a.trace else a.reps
+    dev = torch.device("cuda", 0); torch.zeros(1, device=dev)
+    g = gu.GoldenScene("ground_bunny")
+    ds = lib.DeviceScene(g.flat)
+    side = torch.cuda.Stream(device=dev)
+    cur = side.cuda_stream
+    assert cur != 0
+    print(f"K3 ground_bunny {W}x{H}: {g.flat.n_tris} triangles, {g.flat.n_nodes} nodes, {reps} repetitions each")
+    # the yardsticks: ms_primary of the renders (HIP events inside the library, averaged over the renders since the last sync)
+    ms = {}
+    for name, flags in (("render, variant 2 (wave triangle queue)", 2 << 8), ("render, shipped pipeline", 0)):
+        p = g.params(W, H, 1, flags=flags)
+        for _ in range(2):
+            ds.render(p, want=())
+        for _ in range(reps):
+            ds.render_device(p, stream=cur)
+        st = ds.sync()
+        ms[name] = st["ms_primary"]
+        print(f"{name:44s} ms_primary {st['ms_primary']:8.3f}   ({ds.pipeline}, {st['launches']} launches)")
+    yard = ms["render, variant 2 (wave triangle queue)"]
+    rays = frame_rays()
+    n = rays.shape[0]
+    frame = ds.render(g.params(W, H, 1), want=("hit_id", "t"))
+    hit_ref, t_ref = frame["hit_id"].reshape(-1), frame["t"].reshape(-1)
+    orders = (("(a) tile order, 8x8 pixels a wave", tile_order()), ("(b) row-major", np.arange(n)), ("(c) randomly permuted", np.random.default_rng(1).permutation(n)))
+    hit = torch.empty(n, dtype=torch.int32, device=dev); t = torch.empty(n, dtype=torch.float32, device=dev); bary = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    for name, order in orders:
+        d_rays = torch.from_numpy(np.ascontiguousarray(rays[order])).to(dev)
+        torch.cuda.synchronize()
+        m1 = timed(lambda: ds.trace_rays_device(n, d_rays.data_ptr(), stream=cur, hit_id=hit.data_ptr(), t=t.data_ptr()), reps, side)
+        ok = np.array_equal(hit.cpu().numpy(), hit_ref[order]) and np.array_equal(t.cpu().numpy().view(np.uint32), t_ref[order].view(np.uint32))
+        m2 = timed(lambda: ds.trace_rays_device(n, d_rays.data_ptr(), stream=cur, hit_id=hit.data_ptr(), t=t.data_ptr(), bary=bary.data_ptr()), reps, side)
+        print(f"query {name:38s} ms {m1:8.3f}   {n / m1 / 1e6:7.2f} Grays/s   x{m1 / yard:5.2f} of variant 2   with bary {m2:8.3f} ms   same bits as the frame: {ok}")
+        assert ok
+    # occlusion: the frame's shadow rays (so = d * t, sd = L - so), hit object skipped, in tile order and permuted
+    sel = hit_ref >= 0
+    L = np.asarray(g.light, np.float32).reshape(1, 3)
+    so = rays[sel, 3:6] * t_ref[sel, None]
+    sray = np.ascontiguousarray(np.concatenate([so, L - so], 1), np.float32)
+    skip = g.flat.tri_obj[hit_ref[sel]].astype(np.int32)
+    m = sray.shape[0]
+    rank = np.empty(n, np.int64); rank[orders[0][1]] = np.arange(n)
+    occ = torch.empty(m, dtype=torch.uint8, device=dev)
+    for name, order in (("tile order", np.argsort(rank[sel], kind="stable")), ("randomly permuted", np.random.default_rng(2).permutation(m))):
+        d_s = torch.from_numpy(np.ascontiguousarray(sray[order])).to(dev); d_k = torch.from_numpy(np.ascontiguousarray(skip[order])).to(dev)
+        torch.cuda.synchronize()
+        mo = timed(lambda: ds.occluded_device(m, d_s.data_ptr(), occ.data_ptr(), skip_obj=d_k.data_ptr(), stream=cur), reps, side)
+        side.synchronize()
+        print(f"occlusion, {m} shadow rays, {name:18s} ms {mo:8.3f}   {m / mo / 1e6:7.2f} Grays/s   occluded {int(occ.sum().item())}")
+    # host entry point, end to end (staging, copies, wait)
+    for k in (1, n):
+        r = np.ascontiguousarray(rays[orders[0][1]][:k])
+        ds.trace_rays(r); ds.trace_rays(r)
+        t0 = time.perf_counter()
+        for _ in range(reps):
+            ds.trace_rays(r)
+        full = (time.perf_counter() - t0) / reps * 1e3
+        t0 = time.perf_counter()
+        for _ in range(reps):
+            ds.trace_rays(r, want=())
+        print(f"srt_trace_rays end to end, {k:8d} rays: {full:9.3f} ms a call (hit_id, t, bary to host arrays); without the copies back {(time.perf_counter() - t0) / reps * 1e3:9.3f} ms")
+
+
+if __name__ == "__main__":
+    main()
