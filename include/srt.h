@@ -350,6 +350,48 @@ int srt_occluded_device(srt_scene* s, uint32_t n, const float* d_rays, const int
                         void* stream, uint8_t* d_occluded);
 int srt_occluded(srt_scene* s, uint32_t n, const float* rays, const int32_t* skip_obj, uint8_t* occluded);
 
+/* Shaded colour: what comes back along each ray -- everything the library does after the closest hit for the pixels of its own camera
+ * (texture lookup, the soft-shadow light samples, Phong, smooth normals, tone map, quantiser, background rule), for rays the caller
+ * supplies: a mirror, a second view, a probe that sees light, a picking preview.  rays as above.  srt_params is reused, so that
+ * srt_params_default still supplies the reference's literals.  Fields READ: n_lights and light_pos (host pointer, n_lights x 3),
+ * shadow_div, reinhard, gamma, background, flags.  Fields IGNORED: width, height, block_rows, block_first, block_stride, block_cols,
+ * focal, ray_matrix, spp.
+ * PARITY: per ray the one pixel of the oracle's 1 x 1 camera-mode frame for that ray (see above) with those lights, literals and flags:
+ *   hit_id      n       int32  exactly what srt_trace_rays gives; -1 on a miss
+ *   t           n       f32    exactly what srt_trace_rays gives; +inf on a miss
+ *   rgb_linear  n x 3   f32    the pre-tone-map sum over the light samples (softShadow:362-383), in light order l = 0 .. n_lights - 1, one
+ *                              f32 add per sample; a sample whose shadow ray (shadowIntersection:321-342 from so = o + d * t towards
+ *                              sd = L - so, the hit object's tree left out, t unbounded, NaN counts) is blocked is divided by shadow_div
+ *                              per component.  Colour = the object's, or the texel found through calculateBarycentricCoords at o + d * t
+ *                              (index clamped into the image, as the render kernels do); normal = the record's face normal, or
+ *                              interpolateNormal under SRT_FLAG_SMOOTH_NORMALS; Phong with the ray's own origin and direction.
+ *                              (0, 0, 0) on a miss
+ *   rgb8        n x 3   u8     tone-mapped, quantised (:391-398,447-449); all-black -- a miss, or a hit that sums to black -- becomes
+ *                              `background` (:518, drawImage:476-487)
+ * n_lights == 0 is allowed: a hit then has rgb_linear 0 and rgb8 = background.  Any output pointer may be NULL, and so may all of them.
+ * Flags: 0, SRT_FLAG_COUNT_WORK, SRT_FLAG_SMOOTH_NORMALS or both; SRT_FLAG_SMOOTH_NORMALS on a scene without normals fails as
+ * srt_render_device does (SRT_ERR_ARG); any other bit, the variant bits 8..15 included: SRT_ERR_ARG.
+ * Errors, all before anything is touched: NULL handle, NULL p, NULL rays with n > 0, n_lights > 0 with NULL light_pos: SRT_ERR_ARG;
+ * n * max(n_lights, 1) >= 2^32: SRT_ERR_LIMIT.  n == 0 (with valid arguments): SRT_OK, nothing happens.
+ * The _device form: device pointers, one launch, asynchronous on `stream` (NULL = the scene's own stream), ordered behind the updates,
+ * poses and renders already enqueued there; it allocates nothing proportional to n and leaves alone what srt_sync and srt_scene_pipeline
+ * report and the renders' alternating counter sets.  The light table goes to the device as a render's does -- through a pinned copy, and
+ * again only when its bytes differ from the last query's -- into a buffer PRIVATE TO QUERIES (a render's table may be in use on another
+ * stream).  Like the query counter set it belongs to the handle: ONE light table per handle at a time -- a call with another table must
+ * not be enqueued while a query with the previous one is in flight on a different stream; for concurrent calls with different tables take
+ * one handle of srt_scene_share each.  Without SRT_FLAG_COUNT_WORK, and with the table already on the device -- an earlier call
+ * with the same table on the same stream, or on any stream once its upload has completed (a wait on that stream, or any host-form call) --
+ * the call is a single kernel launch and may be captured into a hipGraph; while an upload made on ANOTHER stream is still pending, the
+ * call first makes its stream wait for it.  SRT_FLAG_COUNT_WORK: as for srt_trace_rays_device.
+ * The host form stages the rays through the handle's pinned block, waits, copies out and fills *stats (may be NULL): primary_rays = n,
+ * hit_rays, shadow_rays = hit_rays x n_lights, and under SRT_FLAG_COUNT_WORK node_tests_primary / tri_tests_primary / node_tests_shadow /
+ * tri_tests_shadow -- the oracle's algorithmic counts: every shadow ray walked on its own, objects in order, the hit object's tree left
+ * out, left at the first hit; every other field is 0. */
+int srt_shade_rays_device(srt_scene* s, uint32_t n, const float* d_rays, const srt_params* p, void* stream,
+                          int32_t* d_hit_id, float* d_t, float* d_rgb_linear /* n x 3 */, uint8_t* d_rgb8 /* n x 3 */);
+int srt_shade_rays(srt_scene* s, uint32_t n, const float* rays, const srt_params* p,
+                   int32_t* hit_id, float* t, float* rgb_linear, uint8_t* rgb8, srt_stats* stats);
+
 /* Device-resident size of the scene records and the per-record algorithmic byte sizes used by
  * the bytes model: 32 B per node test, 36 B per triangle test. */
 uint64_t srt_scene_device_bytes(const srt_scene* s);

@@ -158,6 +158,11 @@ struct srt_scene {
     // counter set private to queries (laid out like a render's), which no render reads, zeroes or reports
     DevArray<float, 6> rq_rays; DevArray<int32_t> rq_hit; DevArray<float> rq_t; DevArray<float, 3> rq_bary; DevArray<int32_t> rq_skip; DevArray<uint8_t> rq_occ;
     DevArray<unsigned long long> d_qctr;
+    // srt_shade_rays: the query's own result buffers and its own light table (a render's d_lights may be in use on another stream): the
+    // pinned copy, the event behind its last upload, the stream that upload went to, and whether it is known to have arrived
+    DevArray<float, 3> rq_lin; DevArray<uint8_t, 3> rq_rgb8;
+    DevArray<float, 3> d_qlights; Pinned<float, 3> h_qlights; uint32_t qlights_valid = 0;
+    Event qlights_sent; hipStream_t qlights_stream = nullptr; bool qlights_settled = true;
     int n_cu = 256;
     EventRing ev;
     uint32_t ring_count = 0;         // renders since the last srt_sync
@@ -1612,6 +1617,103 @@ static int occluded_impl(srt_scene* s, uint32_t n, const float* rays, const int3
     return SRT_OK;
 }
 
+// ---- srt_shade_rays: closest hit, shadow rays, Phong, tone map for caller-supplied rays, one launch (k_query_shade) ----------------
+// Every check, before anything is touched.
+static int check_shade(const srt_scene* s, uint32_t n, const float* rays, const srt_params* p) {
+    if (!s || !p || (n && !rays) || (p->n_lights && !p->light_pos)) return SRT_ERR_ARG;
+    if (p->flags & ~(uint32_t)(SRT_FLAG_COUNT_WORK | SRT_FLAG_SMOOTH_NORMALS)) return SRT_ERR_ARG;
+    if ((p->flags & SRT_FLAG_SMOOTH_NORMALS) && !s->dev.tri_normals) return SRT_ERR_ARG;      // needs vertex normals, as check_frame
+    if ((uint64_t)n * (p->n_lights ? p->n_lights : 1) >= (1ull << 32)) return SRT_ERR_LIMIT;
+    return SRT_OK;
+}
+
+// The light table of a query, as a render sends its own: through a pinned copy, again only when the bytes differ from what the device
+// holds.  The upload is ordered on `stream`; a later call with the same table on ANOTHER stream is ordered behind it by the event.
+static int query_lights(srt_scene* s, const srt_params* p, hipStream_t stream) {
+    const uint32_t L = p->n_lights;
+    if (!L) return SRT_OK;
+    const size_t bytes = (size_t)L * 3 * sizeof(float);
+    if (s->qlights_valid == L && L <= s->h_qlights.cap && std::memcmp(s->h_qlights, p->light_pos, bytes) == 0) {
+        if (!s->qlights_settled && stream != s->qlights_stream) {
+            // has the upload arrived?  Then it never needs waiting for again; else this stream waits behind it
+            const hipError_t e = hipEventQuery(s->qlights_sent);
+            if (e == hipSuccess) s->qlights_settled = true;
+            else if (e == hipErrorNotReady) HIP_TRY(hipStreamWaitEvent(stream, s->qlights_sent, 0));
+            else HIP_TRY(e);
+        }
+        return SRT_OK;
+    }
+    if (!s->qlights_sent) HIP_TRY(hipEventCreateWithFlags(&s->qlights_sent.e, hipEventDisableTiming));
+    else if (!s->qlights_settled) HIP_TRY(hipEventSynchronize(s->qlights_sent));      // the pinned copy may still be read
+    s->qlights_settled = true;
+    s->qlights_valid = 0;
+    if (L > s->d_qlights.cap) HIP_TRY(s->d_qlights.reserve(L));      // (hipFree waits for whatever still reads the old block)
+    HIP_TRY(s->h_qlights.reserve(L));
+    std::memcpy(s->h_qlights, p->light_pos, bytes);
+    HIP_TRY(hipMemcpyAsync(s->d_qlights, s->h_qlights, bytes, hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipEventRecord(s->qlights_sent, stream));
+    s->qlights_valid = L; s->qlights_stream = stream; s->qlights_settled = false;
+    return SRT_OK;
+}
+
+static int shade_rays_device_impl(srt_scene* s, uint32_t n, const float* d_rays, const srt_params* p, hipStream_t stream, int32_t* d_hit_id, float* d_t,
+                                  float* d_rgb_linear, uint8_t* d_rgb8, bool count_hits) {
+    SRT_TRY(check_shade(s, n, d_rays, p));
+    if (!n) return SRT_OK;
+    HIP_TRY(hipSetDevice(s->device));
+    if (!stream) SRT_TRY(own_stream(s, &stream));
+    SRT_TRY(query_lights(s, p, stream));
+    const bool count = (p->flags & SRT_FLAG_COUNT_WORK) != 0, smooth = (p->flags & SRT_FLAG_SMOOTH_NORMALS) != 0;
+    unsigned long long* ctr = (count || count_hits) ? s->d_qctr.p : nullptr;
+    if (ctr) HIP_TRY(hipMemsetAsync(ctr, 0, NCTR * sizeof(unsigned long long), stream));
+    QueryShade q;
+    q.lights = s->d_qlights; q.n_lights = p->n_lights;
+    q.shadow_div = p->shadow_div; q.reinhard = p->reinhard; q.gamma = p->gamma;
+    q.bg = (uint32_t)p->background[0] | ((uint32_t)p->background[1] << 8) | ((uint32_t)p->background[2] << 16);
+    q.spread = p->n_lights >= 8 ? 1u : 0u;      // (measured at 1 and 16 samples, DESIGN.md s5: the spread costs phase 1, and pays with the shadow work)
+    // the build: counting, smooth normals, and the integer-shininess pow where every object of the scene allows it (as k_shade_tile)
+    static const decltype(&k_query_shade<false, false, false>) builds[8] = {
+        &k_query_shade<false, false, false>, &k_query_shade<false, false, true>, &k_query_shade<false, true, false>, &k_query_shade<false, true, true>,
+        &k_query_shade<true, false, false>,  &k_query_shade<true, false, true>,  &k_query_shade<true, true, false>,  &k_query_shade<true, true, true> };
+    const auto k = builds[(count ? 4 : 0) | (smooth ? 2 : 0) | (s->rec->int_shin ? 1 : 0)];
+    hipLaunchKernelGGL(k, dim3((uint32_t)(((uint64_t)n + 255u) / 256u)), dim3(256), 0, stream, s->dev, n, d_rays, rays_wide(d_rays), q, d_hit_id, d_t, d_rgb_linear, d_rgb8, ctr);
+    HIP_TRY(hipGetLastError());
+    return SRT_OK;
+}
+
+static int shade_rays_impl(srt_scene* s, uint32_t n, const float* rays, const srt_params* p, int32_t* hit_id, float* t, float* rgb_linear, uint8_t* rgb8,
+                           srt_stats* stats) {
+    SRT_TRY(check_shade(s, n, rays, p));
+    if (stats) std::memset(stats, 0, sizeof(*stats));
+    if (!n) return SRT_OK;
+    HIP_TRY(hipSetDevice(s->device));
+    hipStream_t st;
+    SRT_TRY(own_stream(s, &st));
+    if (hit_id) SRT_TRY(grow(s, n, s->rq_hit));
+    if (t) SRT_TRY(grow(s, n, s->rq_t));
+    if (rgb_linear) SRT_TRY(grow(s, n, s->rq_lin));
+    if (rgb8) SRT_TRY(grow(s, n, s->rq_rgb8));
+    SRT_TRY(stage_rays(s, n, rays, nullptr, st));
+    SRT_TRY(shade_rays_device_impl(s, n, s->rq_rays, p, st, hit_id ? s->rq_hit.p : nullptr, t ? s->rq_t.p : nullptr, rgb_linear ? s->rq_lin.p : nullptr,
+                                   rgb8 ? s->rq_rgb8.p : nullptr, true));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (s->qlights_stream == st) s->qlights_settled = true;
+    if (hit_id) HIP_TRY(hipMemcpy(hit_id, s->rq_hit, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (t) HIP_TRY(hipMemcpy(t, s->rq_t, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+    if (rgb_linear) HIP_TRY(hipMemcpy(rgb_linear, s->rq_lin, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToHost));
+    if (rgb8) HIP_TRY(hipMemcpy(rgb8, s->rq_rgb8, (size_t)n * 3, hipMemcpyDeviceToHost));
+    if (stats) {
+        std::array<unsigned long long, NCTR> c;
+        HIP_TRY(hipMemcpy(c.data(), s->d_qctr, NCTR * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+        stats->primary_rays = n;
+        for (int k = 0; k < HIT_SHARDS; k++) stats->hit_rays += c[CTR_HIT_BASE + 8 * k];
+        stats->shadow_rays = stats->hit_rays * p->n_lights;
+        stats->node_tests_primary = c[1]; stats->tri_tests_primary = c[2];
+        stats->node_tests_shadow = c[3]; stats->tri_tests_shadow = c[4];
+    }
+    return SRT_OK;
+}
+
 int srt_trace_rays_device(srt_scene* s, uint32_t n, const float* d_rays, uint32_t flags, void* stream, int32_t* d_hit_id, float* d_t, float* d_bary) {
     return guarded([&] { return trace_rays_device_impl(s, n, d_rays, flags, (hipStream_t)stream, d_hit_id, d_t, d_bary, false); });
 }
@@ -1623,6 +1725,14 @@ int srt_occluded_device(srt_scene* s, uint32_t n, const float* d_rays, const int
 }
 int srt_occluded(srt_scene* s, uint32_t n, const float* rays, const int32_t* skip_obj, uint8_t* occluded) {
     return guarded([&] { return occluded_impl(s, n, rays, skip_obj, occluded); });
+}
+int srt_shade_rays_device(srt_scene* s, uint32_t n, const float* d_rays, const srt_params* p, void* stream, int32_t* d_hit_id, float* d_t,
+                          float* d_rgb_linear, uint8_t* d_rgb8) {
+    return guarded([&] { return shade_rays_device_impl(s, n, d_rays, p, (hipStream_t)stream, d_hit_id, d_t, d_rgb_linear, d_rgb8, false); });
+}
+int srt_shade_rays(srt_scene* s, uint32_t n, const float* rays, const srt_params* p, int32_t* hit_id, float* t, float* rgb_linear, uint8_t* rgb8,
+                   srt_stats* stats) {
+    return guarded([&] { return shade_rays_impl(s, n, rays, p, hit_id, t, rgb_linear, rgb8, stats); });
 }
 
 void* srt_host_alloc(size_t bytes) {

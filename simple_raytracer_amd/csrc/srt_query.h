@@ -32,23 +32,13 @@ __device__ __forceinline__ void load_ray(const float* __restrict__ rays, size_t 
 // (t bits << 32 | triangle id) -- k_closest_hit_q's scheme, +-0 handling included.
 // counters: null, or a set laid out like a render's -- [1] / [2] node / triangle tests (COUNT), [8 + 8 * shard] hit rays.
 // =================================================================================================
-template <bool COUNT, bool BARY>
-__global__ __launch_bounds__(256) void k_query_closest(DevScene s, uint32_t n_rays, const float* __restrict__ rays, uint32_t wide,
-                                                       int32_t* __restrict__ hit_id, float* __restrict__ t_out, float* __restrict__ bary,
-                                                       unsigned long long* __restrict__ counters) {
-    __shared__ uint32_t q_all[4][QCAP];
-    __shared__ unsigned long long best_all[256];
-    __shared__ float ray_all[4][6][64];
-    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t* q = q_all[wave];
-    unsigned long long* best = best_all + wave * 64;
-    float (*wray)[64] = ray_all[wave];
-    const size_t ri = (size_t)blockIdx.x * 256 + threadIdx.x;
-    const bool live = ri < (size_t)n_rays;
-    unsigned long long n_node = 0, n_tri = 0;
+// The walk and the merge for the 64 rays of one wave, shared by k_query_closest and k_query_shade: on return best[lane] holds the
+// lane's minimum of (t bits << 32 | triangle id), ~0 on a miss.  q (QCAP words), best (64 words) and wray (the wave's rays) are the
+// wave's own LDS.
+template <bool COUNT>
+__device__ __forceinline__ void query_closest_walk(const DevScene& s, const bool live, const V3 o, const V3 d, const uint32_t lane, uint32_t* q,
+                                                   unsigned long long* best, float (*wray)[64], unsigned long long& n_node, unsigned long long& n_tri) {
     best[lane] = ~0ull;
-    V3 o = mk(0.0f, 0.0f, 0.0f), d = mk(0.0f, 0.0f, 1.0f);
-    if (live) load_ray(rays, ri, wide != 0, o, d);
     wray[0][lane] = o.x; wray[1][lane] = o.y; wray[2][lane] = o.z;
     wray[3][lane] = d.x; wray[4][lane] = d.y; wray[5][lane] = d.z;
     const RayRcp rc = ray_rcp(d);
@@ -125,6 +115,24 @@ __global__ __launch_bounds__(256) void k_query_closest(DevScene s, uint32_t n_ra
         }
     }
     __builtin_amdgcn_wave_barrier();
+}
+
+template <bool COUNT, bool BARY>
+__global__ __launch_bounds__(256) void k_query_closest(DevScene s, uint32_t n_rays, const float* __restrict__ rays, uint32_t wide,
+                                                       int32_t* __restrict__ hit_id, float* __restrict__ t_out, float* __restrict__ bary,
+                                                       unsigned long long* __restrict__ counters) {
+    __shared__ uint32_t q_all[4][QCAP];
+    __shared__ unsigned long long best_all[256];
+    __shared__ float ray_all[4][6][64];
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    unsigned long long* best = best_all + wave * 64;
+    const size_t ri = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const bool live = ri < (size_t)n_rays;
+    unsigned long long n_node = 0, n_tri = 0;
+    V3 o = mk(0.0f, 0.0f, 0.0f), d = mk(0.0f, 0.0f, 1.0f);
+    if (live) load_ray(rays, ri, wide != 0, o, d);
+    query_closest_walk<COUNT>(s, live, o, d, lane, q_all[wave], best, ray_all[wave], n_node, n_tri);
+    const float4* tris4 = reinterpret_cast<const float4*>(s.tris);
     bool is_hit = false;
     if (live) {
         const unsigned long long key = best[lane];
@@ -156,18 +164,13 @@ __global__ __launch_bounds__(256) void k_query_closest(DevScene s, uint32_t n_ra
 // does it (the skipped object's node range is stepped over), the lane leaves at its first hit.
 // An entry of skip_obj outside [0, n_objects) skips nothing.
 // =================================================================================================
-__global__ __launch_bounds__(256) void k_query_any(DevScene s, uint32_t n_rays, const float* __restrict__ rays, uint32_t wide,
-                                                   const int32_t* __restrict__ skip_obj, uint8_t* __restrict__ occluded) {
-    const size_t ri = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (ri >= (size_t)n_rays) return;
-    V3 o, d;
-    load_ray(rays, ri, wide != 0, o, d);
+// The walk of one ray on its own lane, shared by k_query_any and k_query_shade.  self: the node range that is stepped over.
+// COUNT: the oracle's algorithmic counts -- a sequential walk, objects in order, one slab test per node met, one Moller-Trumbore test per
+// triangle up to and including the first hit.
+template <bool COUNT>
+__device__ __forceinline__ bool query_any_walk(const DevScene& s, const int2 self, const V3 o, const V3 d, unsigned long long& n_node,
+                                               unsigned long long& n_tri) {
     const RayRcp rc = ray_rcp(d);
-    int2 self = make_int2(-1, -1);
-    if (skip_obj) {
-        const int32_t k = skip_obj[ri];
-        if (k >= 0 && (uint32_t)k < s.n_objects) self = s.obj_range[k];
-    }
     const float4* nodes4 = reinterpret_cast<const float4*>(s.nodes);
     const float4* tris4 = reinterpret_cast<const float4*>(s.tris);
     const int32_t n = (int32_t)s.n_nodes;
@@ -177,6 +180,7 @@ __global__ __launch_bounds__(256) void k_query_any(DevScene s, uint32_t n_rays, 
         if (i == self.x) { i = self.y; continue; }
         const float4 a = nodes4[2 * (size_t)i], b = nodes4[2 * (size_t)i + 1];
         const int32_t skip = __float_as_int(b.z), leaf = __float_as_int(b.w);
+        if (COUNT) n_node++;
         if (slab_pass<true>(o, d, rc, a.x, a.y, a.z, a.w, b.x, b.y)) {
             if (leaf >= 0) {
                 const int32_t first = leaf >> LEAF_SHIFT, cnt = leaf & LEAF_MAX;
@@ -184,6 +188,7 @@ __global__ __launch_bounds__(256) void k_query_any(DevScene s, uint32_t n_rays, 
                     const size_t ti = (size_t)(first + k) * 3;
                     const float4 t0 = tris4[ti], t1 = tris4[ti + 1];
                     const float e2z = reinterpret_cast<const float*>(tris4 + ti + 2)[0];
+                    if (COUNT) n_tri++;
                     const float t = ray_triangle(o, d, mk(t0.x, t0.y, t0.z), mk(t0.w, t1.x, t1.y), mk(t1.z, t1.w, e2z));
                     hit = t != SRT_NEG_INF;                      // any t >= 0, NaN included (:335)
                 }
@@ -193,5 +198,150 @@ __global__ __launch_bounds__(256) void k_query_any(DevScene s, uint32_t n_rays, 
             i = skip;
         }
     }
-    occluded[ri] = hit ? 1 : 0;
+    return hit;
+}
+
+__global__ __launch_bounds__(256) void k_query_any(DevScene s, uint32_t n_rays, const float* __restrict__ rays, uint32_t wide,
+                                                   const int32_t* __restrict__ skip_obj, uint8_t* __restrict__ occluded) {
+    const size_t ri = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (ri >= (size_t)n_rays) return;
+    V3 o, d;
+    load_ray(rays, ri, wide != 0, o, d);
+    int2 self = make_int2(-1, -1);
+    if (skip_obj) {
+        const int32_t k = skip_obj[ri];
+        if (k >= 0 && (uint32_t)k < s.n_objects) self = s.obj_range[k];
+    }
+    unsigned long long n_node = 0, n_tri = 0;
+    occluded[ri] = query_any_walk<false>(s, self, o, d, n_node, n_tri) ? 1 : 0;
+}
+
+// =================================================================================================
+// Shaded colour of caller-supplied rays (srt_shade_rays): per ray the one pixel of the oracle's 1 x 1 camera-mode frame -- closest hit,
+// softShadow:348-401 (shadow rays, Phong, the light-sample sum), tone map, quantiser, background rule -- in ONE launch: hit id and t stay
+// in registers between the two phases, so the call needs no buffer of its own.
+// Phase 1 is k_query_closest's walk (query_closest_walk).
+// Phase 2, a wave at a time and with no barrier between waves: the wave's h hit rays are ranked (ballot + mbcnt) and leave their shadow
+// origin so = o + d * t and their object's node range in the wave's LDS, by rank (the rays' slots: phase 1 is over).  The light samples go
+// in chunks of up to 64, in light order; a chunk's h * m work items (rank, sample) are dealt to the 64 lanes round after round --
+// consecutive lanes take consecutive samples of one hit, so a round's rays leave few points -- each lane runs query_any_walk for its item
+// and ORs the answer into the hit's 64-bit word in LDS.  After a chunk every hit's own lane adds the chunk's Phong samples in light order
+// (one f32 add per sample: the oracle's sum), dividing the shadowed ones.  A wave with 3 hits and 16 samples so keeps 48 lanes walking
+// where one lane per ray would keep 3.
+// Colour (object colour or texel, the render kernels' clamp), normal (face normal or interpolateNormal) and material are fetched once per
+// hit, before the first chunk.  counters: as k_query_closest's, and [3] / [4] node / triangle tests of the shadow rays (COUNT).
+// =================================================================================================
+struct QueryShade {
+    const float* lights;          // device, n_lights x 3
+    uint32_t n_lights;
+    float shadow_div, reinhard, gamma;
+    uint32_t bg;                  // r | g << 8 | b << 16
+    uint32_t spread;              // a wave owns 8 groups of 8 consecutive rays, the groups a 64th of the batch apart, instead of 64 consecutive rays
+};
+
+template <bool COUNT, bool SMOOTH, bool INT_SHIN>
+__global__ __launch_bounds__(256) void k_query_shade(DevScene s, uint32_t n_rays, const float* __restrict__ rays, uint32_t wide, QueryShade p,
+                                                     int32_t* __restrict__ hit_id, float* __restrict__ t_out, float* __restrict__ rgb_linear,
+                                                     uint8_t* __restrict__ rgb8, unsigned long long* __restrict__ counters) {
+    __shared__ uint32_t q_all[4][QCAP];
+    __shared__ unsigned long long best_all[256];
+    __shared__ float ray_all[4][6][64];
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    unsigned long long* best = best_all + wave * 64;
+    float (*wray)[64] = ray_all[wave];
+    // spread: the shadow walks of a batch are few long ones among many short ones, and the long ones sit together (the pixels in one
+    // object's shadow); a wave of 64 such neighbours walks them one round after the other while the rest of the machine has left.
+    // Groups of 8 neighbours keep most of phase 1's coherence and put a region's hits into 8 times as many waves.
+    const size_t n_waves = (size_t)gridDim.x * 4, wv = (size_t)blockIdx.x * 4 + wave;
+    const size_t ri = p.spread ? ((size_t)(lane >> 3) * n_waves + wv) * 8 + (lane & 7u) : (size_t)blockIdx.x * 256 + threadIdx.x;
+    const bool live = ri < (size_t)n_rays;
+    unsigned long long n_node = 0, n_tri = 0, n_node_s = 0, n_tri_s = 0;
+    V3 o = mk(0.0f, 0.0f, 0.0f), d = mk(0.0f, 0.0f, 1.0f);
+    if (live) load_ray(rays, ri, wide != 0, o, d);
+    query_closest_walk<COUNT>(s, live, o, d, lane, q_all[wave], best, wray, n_node, n_tri);
+    const unsigned long long key = live ? best[lane] : ~0ull;
+    const bool is_hit = key != ~0ull;
+    const int32_t id = is_hit ? (int32_t)(uint32_t)key : -1;
+    float t = __builtin_inff();
+    V3 color = mk(0.0f, 0.0f, 0.0f), nrm = color;
+    float ka = 0.0f, ks = 0.0f, sh = 1.0f;
+    const unsigned long long hm = __ballot(is_hit);
+    const uint32_t nh = (uint32_t)__popcll(hm), rank = lane_prefix(hm);
+    __builtin_amdgcn_wave_barrier();                    // every lane has read its key: the slots are free
+    if (is_hit) {
+        const float4* tp = reinterpret_cast<const float4*>(s.tris) + (size_t)id * 3;
+        const float4 t0 = tp[0], t1 = tp[1], t2 = tp[2];
+        const V3 p1 = mk(t0.x, t0.y, t0.z), e1 = mk(t0.w, t1.x, t1.y), e2 = mk(t1.z, t1.w, t2.x);
+        t = ray_triangle(o, d, p1, e1, e2);             // the winner's t with its own bits (incl. the sign of a zero)
+        const int32_t obj = s.tri_obj[id];
+        const V3 P = o + d * t;                         // shadowIntersection:325-326 in camera mode: so = o + d * t
+        const int2 self = s.obj_range[obj];
+        wray[0][rank] = P.x; wray[1][rank] = P.y; wray[2][rank] = P.z;
+        wray[3][rank] = __int_as_float(self.x); wray[4][rank] = __int_as_float(self.y);
+        color = mk(s.obj_color[obj * 3], s.obj_color[obj * 3 + 1], s.obj_color[obj * 3 + 2]);     // :437-440
+        const int32_t tex = s.tri_tex ? s.tri_tex[id] : -1;
+        V3 bc = mk(0.0f, 0.0f, 0.0f);
+        if (tex >= 0 || SMOOTH) bc = barycentric(p1, e1, e2, P);
+        if (tex >= 0) {                                                                             // :350-361
+            const float* tc = s.tri_tc + (size_t)id * 6;
+            const float tx = (bc.x * tc[0] + bc.y * tc[2]) + bc.z * tc[4];                          // :123-125
+            const float ty = (bc.x * tc[1] + bc.y * tc[3]) + bc.z * tc[5];
+            long long idx = ((long long)((int)ty * (int)s.tex_w[tex] + (int)tx)) * 3;               // :357
+            // the reference reads out of bounds if the texel index leaves the image (UB); clamp instead, as the render kernels
+            const long long last = (long long)s.tex_size[tex] - 3;
+            idx = idx < 0 ? 0 : (idx > last ? last : idx);
+            const uint8_t* td = s.tex + s.tex_off[tex] + idx;
+            color = mk(td[0] / 255.0f, td[1] / 255.0f, td[2] / 255.0f);
+        }
+        ka = s.obj_mat[obj * 3]; ks = s.obj_mat[obj * 3 + 1]; sh = s.obj_mat[obj * 3 + 2];
+        nrm = mk(t2.y, t2.z, t2.w);
+        if (SMOOTH) {      // phongIllumination:159,162 with the interpolateNormal line enabled (opt-in mode)
+            const float* n9 = s.tri_normals + (size_t)id * 9;
+            nrm = normalize3(mk((bc.x * n9[0] + bc.y * n9[3]) + bc.z * n9[6], (bc.x * n9[1] + bc.y * n9[4]) + bc.z * n9[7],
+                                (bc.x * n9[2] + bc.y * n9[5]) + bc.z * n9[8]));
+        }
+    }
+    if (live) {
+        if (hit_id) hit_id[ri] = id;
+        if (t_out) t_out[ri] = t;
+    }
+    V3 sum = mk(0.0f, 0.0f, 0.0f);
+    for (uint32_t l0 = 0; l0 < p.n_lights; l0 += 64u) {                                             // wave-uniform
+        const uint32_t m = p.n_lights - l0 < 64u ? p.n_lights - l0 : 64u;
+        if (is_hit) best[rank] = 0ull;
+        __builtin_amdgcn_wave_barrier();
+        const uint32_t items = nh * m;                                                              // <= 4096
+        for (uint32_t w = lane; w < items; w += 64u) {
+            const uint32_t r = w / m, k = w - r * m;
+            const V3 so = mk(wray[0][r], wray[1][r], wray[2][r]);
+            const int2 self = make_int2(__float_as_int(wray[3][r]), __float_as_int(wray[4][r]));
+            const float* lp = p.lights + (size_t)(l0 + k) * 3;
+            const V3 sd = mk(lp[0], lp[1], lp[2]) - so;
+            if (query_any_walk<COUNT>(s, self, so, sd, n_node_s, n_tri_s)) atomicOr(&best[r], 1ull << k);
+        }
+        __builtin_amdgcn_wave_barrier();
+        if (is_hit) {
+            const unsigned long long mask = best[rank];
+            for (uint32_t k = 0; k < m; k++) {                                                      // :366-383
+                const float* lp = p.lights + (size_t)(l0 + k) * 3;
+                V3 c = phong<INT_SHIN>(nrm, o, d, mk(lp[0], lp[1], lp[2]), color, ka, ks, sh, t);
+                if ((mask >> k) & 1ull) c = mk(c.x / p.shadow_div, c.y / p.shadow_div, c.z / p.shadow_div);       // :369
+                sum = sum + c;                                                                      // :370
+            }
+        }
+        __builtin_amdgcn_wave_barrier();
+    }
+    if (live) {
+        if (rgb_linear) { rgb_linear[ri * 3] = sum.x; rgb_linear[ri * 3 + 1] = sum.y; rgb_linear[ri * 3 + 2] = sum.z; }
+        if (rgb8) {
+            int q0 = 0, q1 = 0, q2 = 0;
+            if (is_hit) {                                                                           // :391-398,447-449
+                q0 = quant1(tone1(sum.x, p.reinhard, p.gamma)); q1 = quant1(tone1(sum.y, p.reinhard, p.gamma)); q2 = quant1(tone1(sum.z, p.reinhard, p.gamma));
+            }
+            if ((q0 | q1 | q2) == 0) { q0 = p.bg & 255; q1 = (p.bg >> 8) & 255; q2 = (p.bg >> 16) & 255; }   // :518, :476-487
+            rgb8[ri * 3] = (uint8_t)q0; rgb8[ri * 3 + 1] = (uint8_t)q1; rgb8[ri * 3 + 2] = (uint8_t)q2;
+        }
+    }
+    if (counters) count_hits(counters, is_hit, blockIdx.x);
+    if (COUNT) { wave_add(counters + 1, n_node); wave_add(counters + 2, n_tri); wave_add(counters + 3, n_node_s); wave_add(counters + 4, n_tri_s); }
 }

@@ -21,7 +21,7 @@ ABI_SYMBOLS = ("srt_params_default", "srt_light_staircase", "srt_rows_owned", "s
                "srt_last_hip_error", "srt_abi_version", "srt_kat_ray_aabb", "srt_kat_ray_triangle", "srt_kat_phong", "srt_kat_tonemap", "srt_kat_interp_normal", "srt_kat_pow",
                "srt_kat_ray_triangle_origin", "srt_kat_barycentric", "srt_debug_fail_host_allocs", "srt_debug_valu_rate", "srt_debug_scene_records", "srt_scene_set_source", "srt_scene_update_frame",
                "srt_scene_pipeline", "srt_scene_overlap_estimate", "srt_scene_set_pose_source", "srt_scene_pose",
-               "srt_trace_rays_device", "srt_trace_rays", "srt_occluded_device", "srt_occluded")
+               "srt_trace_rays_device", "srt_trace_rays", "srt_occluded_device", "srt_occluded", "srt_shade_rays_device", "srt_shade_rays")
 
 _f32p, _i32p, _u8p = C.POINTER(C.c_float), C.POINTER(C.c_int32), C.POINTER(C.c_uint8)
 _lib = None
@@ -91,6 +91,10 @@ def load():
         L.srt_occluded_device.restype = C.c_int
         L.srt_occluded.argtypes = [C.c_void_p, C.c_uint32, _f32p, _i32p, _u8p]
         L.srt_occluded.restype = C.c_int
+        L.srt_shade_rays_device.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(abi.Params), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.srt_shade_rays_device.restype = C.c_int
+        L.srt_shade_rays.argtypes = [C.c_void_p, C.c_uint32, _f32p, C.POINTER(abi.Params), _i32p, _f32p, _f32p, _u8p, C.POINTER(abi.Stats)]
+        L.srt_shade_rays.restype = C.c_int
         L.srt_strerror.argtypes = [C.c_int]
         L.srt_strerror.restype = C.c_char_p
         L.srt_last_hip_error.restype = C.c_int
@@ -281,6 +285,36 @@ class DeviceScene:
     def occluded_device(self, n, rays, occluded, skip_obj=0, stream=0):
         """srt_occluded_device: raw device pointers in, asynchronous on `stream`."""
         _check(self.L.srt_occluded_device(self.h, n, C.c_void_p(rays), C.c_void_p(skip_obj), C.c_void_p(stream), C.c_void_p(occluded)), "srt_occluded_device")
+
+    def shade_rays(self, rays, params: abi.Params, want=("hit_id", "t", "rgb_linear", "rgb8"), count=False):
+        """srt_shade_rays: the colour that comes back along every ray of `rays` (n x 6, host array) under the lights, literals and flags
+        of `params` (its frame geometry is ignored).  Returns a dict of the arrays named in `want` (hit_id n, t n, rgb_linear n x 3,
+        rgb8 n x 3) + 'stats'; count=True adds SRT_FLAG_COUNT_WORK for this call."""
+        r = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
+        n = r.shape[0]
+        out = {}
+        if "hit_id" in want: out["hit_id"] = np.empty(n, np.int32)
+        if "t" in want: out["t"] = np.empty(n, np.float32)
+        if "rgb_linear" in want: out["rgb_linear"] = np.empty((n, 3), np.float32)
+        if "rgb8" in want: out["rgb8"] = np.empty((n, 3), np.uint8)
+        st = abi.Stats()
+        g = lambda k, ty: out[k].ctypes.data_as(ty) if k in out else ty()
+        flags = params.flags
+        if count: params.flags = flags | abi.SRT_FLAG_COUNT_WORK
+        try:
+            rc = self.L.srt_shade_rays(self.h, n, r.ctypes.data_as(_f32p), C.byref(params), g("hit_id", _i32p), g("t", _f32p), g("rgb_linear", _f32p),
+                                       g("rgb8", _u8p), C.byref(st))
+        finally:
+            params.flags = flags
+        _check(rc, "srt_shade_rays")
+        out["stats"] = st.as_dict()
+        return out
+
+    def shade_rays_device(self, n, rays, params: abi.Params, stream=0, hit_id=0, t=0, rgb_linear=0, rgb8=0):
+        """srt_shade_rays_device: raw device pointers (ints, e.g. torch.Tensor.data_ptr()) in, asynchronous on `stream`; the light table
+        of `params` is a host array."""
+        _check(self.L.srt_shade_rays_device(self.h, n, C.c_void_p(rays), C.byref(params), C.c_void_p(stream), C.c_void_p(hit_id), C.c_void_p(t),
+                                            C.c_void_p(rgb_linear), C.c_void_p(rgb8)), "srt_shade_rays_device")
 
     def sync(self):
         st = abi.Stats()

@@ -4,7 +4,11 @@
 row-major, (c) randomly permuted -- beside ms_primary of the reference-frame render with the wave-triangle-queue variant (flags 2 << 8:
 the same per-lane walk, specialised to rays from the origin) and of the shipped pipeline; the occlusion query on the frame's shadow rays;
 the host entry point end to end for 1 ray and for all of them.
-Usage: python tools/ray_query_probe.py [--reps N] [--trace]     (--trace: few repetitions, for a run under rocprofv3 --kernel-trace --stats)"""
+--shade: instead, the shaded-ray query on the same frame's rays at 1 and 16 light samples, in row-major order and shuffled: (a)
+srt_shade_rays_device, (b) the camera-mode srt_render_device of the same frame (identity matrix: the same rays, the same result), (c) the
+composition of the older queries -- srt_trace_rays_device, shadow rays built with torch, srt_occluded_device on hits x samples rays (it
+stops short of shading: no Phong, no tone map).
+Usage: python tools/ray_query_probe.py [--reps N] [--trace] [--shade]     (--trace: few repetitions, for a run under rocprofv3 --kernel-trace --stats)"""
 import argparse, os, sys, time
 import numpy as np
 import torch                                   # first: torch initialises HIP before the library does
@@ -45,12 +49,60 @@ def timed(fn, reps, stream):
     return a.elapsed_time(b) / reps
 
 
+def shade_section(reps):
+    dev = torch.device("cuda", 0); torch.zeros(1, device=dev)
+    g = gu.GoldenScene("ground_bunny")
+    ds = lib.DeviceScene(g.flat)
+    side = torch.cuda.Stream(device=dev)
+    cur = side.cuda_stream
+    rays = frame_rays()
+    n = rays.shape[0]
+    eye = np.eye(4, dtype=np.float32).reshape(-1)
+    tri_obj = torch.from_numpy(g.flat.tri_obj.astype(np.int64)).to(dev)
+    hit = torch.empty(n, dtype=torch.int32, device=dev); t = torch.empty(n, dtype=torch.float32, device=dev)
+    lin = torch.empty((n, 3), dtype=torch.float32, device=dev); rgb8 = torch.empty((n, 3), dtype=torch.uint8, device=dev)
+    f8 = torch.empty((H, W, 3), dtype=torch.uint8, device=dev)
+    print(f"shaded rays, K3 ground_bunny {W}x{H}: {n} rays, {reps} repetitions each; ms a call")
+    print(f"{'samples':>7s} {'order':>9s} {'(a) shade_rays':>15s} {'(b) render':>11s} {'(c) trace+occluded':>19s} {'(a)/(b)':>8s} {'(a)/(c)':>8s}   same rgb8 as the frame")
+    for L in (1, 16):
+        lights = abi.light_staircase(g.light, L)
+        p_frame = abi.make_params(W, H, lights, focal=FOCAL, ray_matrix=eye, flags=abi.SRT_FLAG_NO_TIMING)
+        p_rays = abi.make_params(1, 1, lights)
+        d_lights = torch.from_numpy(lights).to(dev)
+        mb = timed(lambda: ds.render_device(p_frame, stream=cur, rgb8=f8.data_ptr()), reps, side)
+        frame8 = f8.cpu().numpy().reshape(-1, 3)
+        for name, order in (("row-major", np.arange(n)), ("shuffled", np.random.default_rng(1).permutation(n))):
+            d_rays = torch.from_numpy(np.ascontiguousarray(rays[order])).to(dev)
+            torch.cuda.synchronize()
+            ma = timed(lambda: ds.shade_rays_device(n, d_rays.data_ptr(), p_rays, stream=cur, hit_id=hit.data_ptr(), t=t.data_ptr(), rgb_linear=lin.data_ptr(),
+                                                    rgb8=rgb8.data_ptr()), reps, side)
+            ok = np.array_equal(rgb8.cpu().numpy(), frame8[order])
+
+            def composed():
+                ds.trace_rays_device(n, d_rays.data_ptr(), stream=cur, hit_id=hit.data_ptr(), t=t.data_ptr())
+                with torch.cuda.stream(side):
+                    sel = torch.nonzero(hit >= 0).squeeze(1)
+                    r = d_rays[sel]
+                    so = r[:, 0:3] + r[:, 3:6] * t[sel, None]
+                    sray = torch.cat([so[:, None, :].expand(-1, L, -1), d_lights[None, :, :] - so[:, None, :]], dim=2).reshape(-1, 6).contiguous()
+                    skip = tri_obj[hit[sel].long()].to(torch.int32)[:, None].expand(-1, L).reshape(-1).contiguous()
+                    occ = torch.empty(sray.shape[0], dtype=torch.uint8, device=dev)
+                ds.occluded_device(sray.shape[0], sray.data_ptr(), occ.data_ptr(), skip_obj=skip.data_ptr(), stream=cur)
+                return occ
+            mc = timed(composed, reps, side)
+            print(f"{L:7d} {name:>9s} {ma:15.3f} {mb:11.3f} {mc:19.3f} {ma / mb:8.2f} {ma / mc:8.2f}   {ok}")
+            assert ok
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--trace", action="store_true")
+    ap.add_argument("--shade", action="store_true")
     a = ap.parse_args()
     reps = 3 if a.trace else a.reps
+    if a.shade:
+        return shade_section(reps)
     dev = torch.device("cuda", 0); torch.zeros(1, device=dev)
     g = gu.GoldenScene("ground_bunny")
     ds = lib.DeviceScene(g.flat)
