@@ -363,7 +363,7 @@ int srt_occluded(srt_scene* s, uint32_t n, const float* rays, const int32_t* ski
  *                              f32 add per sample; a sample whose shadow ray (shadowIntersection:321-342 from so = o + d * t towards
  *                              sd = L - so, the hit object's tree left out, t unbounded, NaN counts) is blocked is divided by shadow_div
  *                              per component.  Colour = the object's, or the texel found through calculateBarycentricCoords at o + d * t
- *                              (index clamped into the image, as the render kernels do); normal = the record's face normal, or
+ *                              (index clamped into the image, as in a render); normal = the record's face normal, or
  *                              interpolateNormal under SRT_FLAG_SMOOTH_NORMALS; Phong with the ray's own origin and direction.
  *                              (0, 0, 0) on a miss
  *   rgb8        n x 3   u8     tone-mapped, quantised (:391-398,447-449); all-black -- a miss, or a hit that sums to black -- becomes

@@ -220,6 +220,14 @@ __device__ __forceinline__ float ray_triangle(V3 o, V3 d, V3 p1, V3 e1, V3 e2) {
     return t;
 }
 
+// Triangle `tri` of the DevTri array as that test reads it: two dwordx4 loads and the one word of the third that is not the face normal.
+__device__ __forceinline__ void load_tri_edges(const float4* __restrict__ tris4, size_t tri, V3& p1, V3& e1, V3& e2) {
+    const size_t ti = tri * 3;
+    const float4 t0 = tris4[ti], t1 = tris4[ti + 1];
+    const float e2z = reinterpret_cast<const float*>(tris4 + ti + 2)[0];
+    p1 = mk(t0.x, t0.y, t0.z); e1 = mk(t0.w, t1.x, t1.y); e2 = mk(t1.z, t1.w, e2z);
+}
+
 // The same test for a ray from the origin, on the record that carries tvec and qvec (DevTriO)
 __device__ __forceinline__ float ray_triangle_origin(V3 d, V3 tvec, V3 e1, V3 e2, V3 qvec) {
     V3 pvec = cross3(d, e2);

@@ -1521,104 +1521,13 @@ int srt_render(srt_scene* s, const srt_params* p, int32_t* hit_id, float* t, flo
 }
 
 // ---- ray queries (include/srt.h, RAY QUERIES; kernels in srt_query.h) ------------------------------------------------------------
-// The device entry points enqueue and return: a memset of the private counter set when it is used, one launch.  They touch neither the
-// render counters nor the state srt_sync reports from (pending, the event ring, the pipeline string).
+// The device entry points enqueue and return: the light table when it changed (srt_shade_rays), a memset of the private counter set when it
+// is used, one launch.  They touch neither the render counters nor the state srt_sync reports from (pending, the event ring, the pipeline
+// string).  Every check runs before anything is touched.
 static int check_query(const srt_scene* s, uint32_t n, const float* rays, uint32_t flags) {
     if (!s || (n && !rays) || (flags & ~(uint32_t)SRT_FLAG_COUNT_WORK)) return SRT_ERR_ARG;
     return SRT_OK;
 }
-static inline uint32_t rays_wide(const float* d_rays) { return ((uintptr_t)d_rays & 7u) == 0 ? 1u : 0u; }      // srt_query.h load_ray
-
-// count_hits: the host entry point wants hit_rays also without SRT_FLAG_COUNT_WORK
-static int trace_rays_device_impl(srt_scene* s, uint32_t n, const float* d_rays, uint32_t flags, hipStream_t stream, int32_t* d_hit_id, float* d_t,
-                                  float* d_bary, bool count_hits) {
-    SRT_TRY(check_query(s, n, d_rays, flags));
-    if (!n) return SRT_OK;
-    HIP_TRY(hipSetDevice(s->device));
-    if (!stream) SRT_TRY(own_stream(s, &stream));
-    const bool count = (flags & SRT_FLAG_COUNT_WORK) != 0;
-    unsigned long long* ctr = (count || count_hits) ? s->d_qctr.p : nullptr;
-    if (ctr) HIP_TRY(hipMemsetAsync(ctr, 0, NCTR * sizeof(unsigned long long), stream));
-    decltype(&k_query_closest<false, false>) k;
-    if (count) { if (d_bary) k = &k_query_closest<true, true>; else k = &k_query_closest<true, false>; }
-    else { if (d_bary) k = &k_query_closest<false, true>; else k = &k_query_closest<false, false>; }
-    hipLaunchKernelGGL(k, dim3((uint32_t)(((uint64_t)n + 255u) / 256u)), dim3(256), 0, stream, s->dev, n, d_rays, rays_wide(d_rays), d_hit_id, d_t, d_bary, ctr);
-    HIP_TRY(hipGetLastError());
-    return SRT_OK;
-}
-
-static int occluded_device_impl(srt_scene* s, uint32_t n, const float* d_rays, const int32_t* d_skip_obj, hipStream_t stream, uint8_t* d_occluded) {
-    SRT_TRY(check_query(s, n, d_rays, 0));
-    if (!n || !d_occluded) return SRT_OK;
-    HIP_TRY(hipSetDevice(s->device));
-    if (!stream) SRT_TRY(own_stream(s, &stream));
-    hipLaunchKernelGGL(k_query_any, dim3((uint32_t)(((uint64_t)n + 255u) / 256u)), dim3(256), 0, stream, s->dev, n, d_rays, rays_wide(d_rays), d_skip_obj, d_occluded);
-    HIP_TRY(hipGetLastError());
-    return SRT_OK;
-}
-
-// The host entry points: the caller's rays go through the pinned staging block (stage_acquire, as every update does) into the handle's
-// own ray buffer on the scene's stream, the device entry point runs behind them, the call waits and copies the results out.
-static int stage_rays(srt_scene* s, uint32_t n, const float* rays, const int32_t* skip_obj, hipStream_t st) {
-    auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t o_rays = 0, o_skip = pad((size_t)n * 24), total = o_skip + (skip_obj ? pad((size_t)n * 4) : 0);
-    SRT_TRY(grow(s, n, s->rq_rays));
-    if (skip_obj) SRT_TRY(grow(s, n, s->rq_skip));
-    char* h = nullptr;
-    SRT_TRY(stage_acquire(s, total, &h));
-    std::memcpy(h + o_rays, rays, (size_t)n * 24);
-    HIP_TRY(hipMemcpyAsync(s->rq_rays, h + o_rays, (size_t)n * 24, hipMemcpyHostToDevice, st));
-    if (skip_obj) {
-        std::memcpy(h + o_skip, skip_obj, (size_t)n * 4);
-        HIP_TRY(hipMemcpyAsync(s->rq_skip, h + o_skip, (size_t)n * 4, hipMemcpyHostToDevice, st));
-    }
-    HIP_TRY(hipEventRecord(s->staged, st));
-    return SRT_OK;
-}
-
-static int trace_rays_impl(srt_scene* s, uint32_t n, const float* rays, uint32_t flags, int32_t* hit_id, float* t, float* bary, srt_stats* stats) {
-    SRT_TRY(check_query(s, n, rays, flags));
-    if (stats) std::memset(stats, 0, sizeof(*stats));
-    if (!n) return SRT_OK;
-    HIP_TRY(hipSetDevice(s->device));
-    hipStream_t st;
-    SRT_TRY(own_stream(s, &st));
-    if (hit_id) SRT_TRY(grow(s, n, s->rq_hit));
-    if (t) SRT_TRY(grow(s, n, s->rq_t));
-    if (bary) SRT_TRY(grow(s, n, s->rq_bary));
-    SRT_TRY(stage_rays(s, n, rays, nullptr, st));
-    SRT_TRY(trace_rays_device_impl(s, n, s->rq_rays, flags, st, hit_id ? s->rq_hit.p : nullptr, t ? s->rq_t.p : nullptr, bary ? s->rq_bary.p : nullptr, true));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (hit_id) HIP_TRY(hipMemcpy(hit_id, s->rq_hit, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (t) HIP_TRY(hipMemcpy(t, s->rq_t, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
-    if (bary) HIP_TRY(hipMemcpy(bary, s->rq_bary, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToHost));
-    if (stats) {
-        std::array<unsigned long long, NCTR> c;
-        HIP_TRY(hipMemcpy(c.data(), s->d_qctr, NCTR * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-        stats->primary_rays = n;
-        for (int k = 0; k < HIT_SHARDS; k++) stats->hit_rays += c[CTR_HIT_BASE + 8 * k];
-        stats->node_tests_primary = c[1];
-        stats->tri_tests_primary = c[2];
-    }
-    return SRT_OK;
-}
-
-static int occluded_impl(srt_scene* s, uint32_t n, const float* rays, const int32_t* skip_obj, uint8_t* occluded) {
-    SRT_TRY(check_query(s, n, rays, 0));
-    if (!n || !occluded) return SRT_OK;
-    HIP_TRY(hipSetDevice(s->device));
-    hipStream_t st;
-    SRT_TRY(own_stream(s, &st));
-    SRT_TRY(grow(s, n, s->rq_occ));
-    SRT_TRY(stage_rays(s, n, rays, skip_obj, st));
-    SRT_TRY(occluded_device_impl(s, n, s->rq_rays, skip_obj ? s->rq_skip.p : nullptr, st, s->rq_occ));
-    HIP_TRY(hipStreamSynchronize(st));
-    HIP_TRY(hipMemcpy(occluded, s->rq_occ, (size_t)n, hipMemcpyDeviceToHost));
-    return SRT_OK;
-}
-
-// ---- srt_shade_rays: closest hit, shadow rays, Phong, tone map for caller-supplied rays, one launch (k_query_shade) ----------------
-// Every check, before anything is touched.
 static int check_shade(const srt_scene* s, uint32_t n, const float* rays, const srt_params* p) {
     if (!s || !p || (n && !rays) || (p->n_lights && !p->light_pos)) return SRT_ERR_ARG;
     if (p->flags & ~(uint32_t)(SRT_FLAG_COUNT_WORK | SRT_FLAG_SMOOTH_NORMALS)) return SRT_ERR_ARG;
@@ -1626,6 +1535,8 @@ static int check_shade(const srt_scene* s, uint32_t n, const float* rays, const 
     if ((uint64_t)n * (p->n_lights ? p->n_lights : 1) >= (1ull << 32)) return SRT_ERR_LIMIT;
     return SRT_OK;
 }
+
+static inline uint32_t rays_wide(const float* d_rays) { return ((uintptr_t)d_rays & 7u) == 0 ? 1u : 0u; }      // srt_query.h load_ray
 
 // The light table of a query, as a render sends its own: through a pinned copy, again only when the bytes differ from what the device
 // holds.  The upload is ordered on `stream`; a later call with the same table on ANOTHER stream is ordered behind it by the event.
@@ -1656,29 +1567,149 @@ static int query_lights(srt_scene* s, const srt_params* p, hipStream_t stream) {
     return SRT_OK;
 }
 
+// What every device entry point does before its launch: the device, the stream (the scene's own where the caller names none), the light
+// table of a shading query, the private counter set -- cleared on that stream when the call uses it -- and the grid of one lane per ray.
+struct QueryLaunch { hipStream_t stream; unsigned long long* ctr; dim3 grid; };
+static int query_prologue(srt_scene* s, uint32_t n, hipStream_t stream, const srt_params* shade, bool use_counters, QueryLaunch* q) {
+    HIP_TRY(hipSetDevice(s->device));
+    if (!stream) SRT_TRY(own_stream(s, &stream));
+    if (shade) SRT_TRY(query_lights(s, shade, stream));
+    q->stream = stream;
+    q->ctr = use_counters ? s->d_qctr.p : nullptr;
+    if (q->ctr) HIP_TRY(hipMemsetAsync(q->ctr, 0, NCTR * sizeof(unsigned long long), stream));
+    q->grid = dim3((uint32_t)(((uint64_t)n + 255u) / 256u));
+    return SRT_OK;
+}
+
+// count_hits: the host entry point wants hit_rays also without SRT_FLAG_COUNT_WORK
+static int trace_rays_device_impl(srt_scene* s, uint32_t n, const float* d_rays, uint32_t flags, hipStream_t stream, int32_t* d_hit_id, float* d_t,
+                                  float* d_bary, bool count_hits) {
+    SRT_TRY(check_query(s, n, d_rays, flags));
+    if (!n) return SRT_OK;
+    const bool count = (flags & SRT_FLAG_COUNT_WORK) != 0;
+    QueryLaunch q;
+    SRT_TRY(query_prologue(s, n, stream, nullptr, count || count_hits, &q));
+    static const decltype(&k_query_closest<false, false>) builds[4] = {
+        &k_query_closest<false, false>, &k_query_closest<false, true>, &k_query_closest<true, false>, &k_query_closest<true, true> };
+    hipLaunchKernelGGL(builds[(count ? 2 : 0) | (d_bary ? 1 : 0)], q.grid, dim3(256), 0, q.stream, s->dev, n, d_rays, rays_wide(d_rays), d_hit_id, d_t, d_bary, q.ctr);
+    HIP_TRY(hipGetLastError());
+    return SRT_OK;
+}
+
+static int occluded_device_impl(srt_scene* s, uint32_t n, const float* d_rays, const int32_t* d_skip_obj, hipStream_t stream, uint8_t* d_occluded) {
+    SRT_TRY(check_query(s, n, d_rays, 0));
+    if (!n || !d_occluded) return SRT_OK;
+    QueryLaunch q;
+    SRT_TRY(query_prologue(s, n, stream, nullptr, false, &q));
+    hipLaunchKernelGGL(k_query_any, q.grid, dim3(256), 0, q.stream, s->dev, n, d_rays, rays_wide(d_rays), d_skip_obj, d_occluded);
+    HIP_TRY(hipGetLastError());
+    return SRT_OK;
+}
+
+// srt_shade_rays: closest hit, shadow rays, Phong, tone map for caller-supplied rays, one launch (k_query_shade)
 static int shade_rays_device_impl(srt_scene* s, uint32_t n, const float* d_rays, const srt_params* p, hipStream_t stream, int32_t* d_hit_id, float* d_t,
                                   float* d_rgb_linear, uint8_t* d_rgb8, bool count_hits) {
     SRT_TRY(check_shade(s, n, d_rays, p));
     if (!n) return SRT_OK;
-    HIP_TRY(hipSetDevice(s->device));
-    if (!stream) SRT_TRY(own_stream(s, &stream));
-    SRT_TRY(query_lights(s, p, stream));
     const bool count = (p->flags & SRT_FLAG_COUNT_WORK) != 0, smooth = (p->flags & SRT_FLAG_SMOOTH_NORMALS) != 0;
-    unsigned long long* ctr = (count || count_hits) ? s->d_qctr.p : nullptr;
-    if (ctr) HIP_TRY(hipMemsetAsync(ctr, 0, NCTR * sizeof(unsigned long long), stream));
-    QueryShade q;
-    q.lights = s->d_qlights; q.n_lights = p->n_lights;
-    q.shadow_div = p->shadow_div; q.reinhard = p->reinhard; q.gamma = p->gamma;
-    q.bg = (uint32_t)p->background[0] | ((uint32_t)p->background[1] << 8) | ((uint32_t)p->background[2] << 16);
-    q.spread = p->n_lights >= 8 ? 1u : 0u;      // (measured at 1 and 16 samples, DESIGN.md s5: the spread costs phase 1, and pays with the shadow work)
+    QueryLaunch q;
+    SRT_TRY(query_prologue(s, n, stream, p, count || count_hits, &q));
+    QueryShade qs;
+    qs.lights = s->d_qlights; qs.n_lights = p->n_lights;
+    qs.shadow_div = p->shadow_div; qs.reinhard = p->reinhard; qs.gamma = p->gamma;
+    qs.bg = (uint32_t)p->background[0] | ((uint32_t)p->background[1] << 8) | ((uint32_t)p->background[2] << 16);
+    qs.spread = p->n_lights >= 8 ? 1u : 0u;      // (measured at 1 and 16 samples, DESIGN.md s5: the spread costs phase 1, and pays with the shadow work)
     // the build: counting, smooth normals, and the integer-shininess pow where every object of the scene allows it (as k_shade_tile)
     static const decltype(&k_query_shade<false, false, false>) builds[8] = {
         &k_query_shade<false, false, false>, &k_query_shade<false, false, true>, &k_query_shade<false, true, false>, &k_query_shade<false, true, true>,
         &k_query_shade<true, false, false>,  &k_query_shade<true, false, true>,  &k_query_shade<true, true, false>,  &k_query_shade<true, true, true> };
     const auto k = builds[(count ? 4 : 0) | (smooth ? 2 : 0) | (s->rec->int_shin ? 1 : 0)];
-    hipLaunchKernelGGL(k, dim3((uint32_t)(((uint64_t)n + 255u) / 256u)), dim3(256), 0, stream, s->dev, n, d_rays, rays_wide(d_rays), q, d_hit_id, d_t, d_rgb_linear, d_rgb8, ctr);
+    hipLaunchKernelGGL(k, q.grid, dim3(256), 0, q.stream, s->dev, n, d_rays, rays_wide(d_rays), qs, d_hit_id, d_t, d_rgb_linear, d_rgb8, q.ctr);
     HIP_TRY(hipGetLastError());
     return SRT_OK;
+}
+
+// The host entry points: the caller's rays go through the pinned staging block (stage_acquire, as every update does) into the handle's
+// own ray buffer on the scene's stream, the device entry point runs behind them, the call waits and copies the results out.
+static int stage_rays(srt_scene* s, uint32_t n, const float* rays, const int32_t* skip_obj, hipStream_t st) {
+    auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t o_rays = 0, o_skip = pad((size_t)n * 24), total = o_skip + (skip_obj ? pad((size_t)n * 4) : 0);
+    SRT_TRY(grow(s, n, s->rq_rays));
+    if (skip_obj) SRT_TRY(grow(s, n, s->rq_skip));
+    char* h = nullptr;
+    SRT_TRY(stage_acquire(s, total, &h));
+    std::memcpy(h + o_rays, rays, (size_t)n * 24);
+    HIP_TRY(hipMemcpyAsync(s->rq_rays, h + o_rays, (size_t)n * 24, hipMemcpyHostToDevice, st));
+    if (skip_obj) {
+        std::memcpy(h + o_skip, skip_obj, (size_t)n * 4);
+        HIP_TRY(hipMemcpyAsync(s->rq_skip, h + o_skip, (size_t)n * 4, hipMemcpyHostToDevice, st));
+    }
+    HIP_TRY(hipEventRecord(s->staged, st));
+    return SRT_OK;
+}
+
+extern "C++" {
+// One result array of a host query: where the caller wants it (null: not wanted) and the handle's buffer for it.
+template <typename T, size_t K>
+struct QueryOut {
+    T* host; DevArray<T, K>& dev;
+    static constexpr size_t unit = K * sizeof(T);             // bytes per ray
+    T* wanted() const { return host ? dev.p : nullptr; }      // (after the round trip has grown it)
+};
+template <typename T, size_t K>
+static QueryOut<T, K> query_out(T* host, DevArray<T, K>& dev) { return QueryOut<T, K>{ host, dev }; }
+
+// The round trip of a host query on the scene's own stream: grow the wanted result buffers, stage the rays, launch(stream) -- the device
+// entry point --, wait, copy each wanted array out.
+template <typename Launch, typename... O>
+static int query_round_trip(srt_scene* s, uint32_t n, const float* rays, const int32_t* skip_obj, Launch launch, const O&... outs) {
+    HIP_TRY(hipSetDevice(s->device));
+    hipStream_t st;
+    SRT_TRY(own_stream(s, &st));
+    int rc = SRT_OK;
+    ((rc = (rc == SRT_OK && outs.host) ? grow(s, n, outs.dev) : rc), ...);
+    SRT_TRY(rc);
+    SRT_TRY(stage_rays(s, n, rays, skip_obj, st));
+    SRT_TRY(launch(st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (s->qlights_stream == st) s->qlights_settled = true;      // a light table sent on this stream has arrived
+    hipError_t e = hipSuccess;
+    ((e = (e == hipSuccess && outs.host) ? hipMemcpy(outs.host, outs.dev.p, (size_t)n * outs.unit, hipMemcpyDeviceToHost) : e), ...);
+    HIP_TRY(e);
+    return SRT_OK;
+}
+
+}      // extern "C++"
+
+// The private counter set of the query that just ran (cleared before its launch), as srt_stats; n_lights: shadow rays per hit.
+static int query_stats(srt_scene* s, uint32_t n, uint32_t n_lights, srt_stats* stats) {
+    std::array<unsigned long long, NCTR> c;
+    HIP_TRY(hipMemcpy(c.data(), s->d_qctr, NCTR * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    stats->primary_rays = n;
+    for (int k = 0; k < HIT_SHARDS; k++) stats->hit_rays += c[CTR_HIT_BASE + 8 * k];
+    stats->shadow_rays = stats->hit_rays * n_lights;
+    stats->node_tests_primary = c[1]; stats->tri_tests_primary = c[2];
+    stats->node_tests_shadow = c[3]; stats->tri_tests_shadow = c[4];
+    return SRT_OK;
+}
+
+static int trace_rays_impl(srt_scene* s, uint32_t n, const float* rays, uint32_t flags, int32_t* hit_id, float* t, float* bary, srt_stats* stats) {
+    SRT_TRY(check_query(s, n, rays, flags));
+    if (stats) std::memset(stats, 0, sizeof(*stats));
+    if (!n) return SRT_OK;
+    const auto o_hit = query_out(hit_id, s->rq_hit); const auto o_t = query_out(t, s->rq_t); const auto o_bary = query_out(bary, s->rq_bary);
+    SRT_TRY(query_round_trip(s, n, rays, nullptr, [&](hipStream_t st) {
+        return trace_rays_device_impl(s, n, s->rq_rays, flags, st, o_hit.wanted(), o_t.wanted(), o_bary.wanted(), true);
+    }, o_hit, o_t, o_bary));
+    return stats ? query_stats(s, n, 0, stats) : SRT_OK;
+}
+
+static int occluded_impl(srt_scene* s, uint32_t n, const float* rays, const int32_t* skip_obj, uint8_t* occluded) {
+    SRT_TRY(check_query(s, n, rays, 0));
+    if (!n || !occluded) return SRT_OK;
+    return query_round_trip(s, n, rays, skip_obj, [&](hipStream_t st) {
+        return occluded_device_impl(s, n, s->rq_rays, skip_obj ? s->rq_skip.p : nullptr, st, s->rq_occ);
+    }, query_out(occluded, s->rq_occ));
 }
 
 static int shade_rays_impl(srt_scene* s, uint32_t n, const float* rays, const srt_params* p, int32_t* hit_id, float* t, float* rgb_linear, uint8_t* rgb8,
@@ -1686,32 +1717,12 @@ static int shade_rays_impl(srt_scene* s, uint32_t n, const float* rays, const sr
     SRT_TRY(check_shade(s, n, rays, p));
     if (stats) std::memset(stats, 0, sizeof(*stats));
     if (!n) return SRT_OK;
-    HIP_TRY(hipSetDevice(s->device));
-    hipStream_t st;
-    SRT_TRY(own_stream(s, &st));
-    if (hit_id) SRT_TRY(grow(s, n, s->rq_hit));
-    if (t) SRT_TRY(grow(s, n, s->rq_t));
-    if (rgb_linear) SRT_TRY(grow(s, n, s->rq_lin));
-    if (rgb8) SRT_TRY(grow(s, n, s->rq_rgb8));
-    SRT_TRY(stage_rays(s, n, rays, nullptr, st));
-    SRT_TRY(shade_rays_device_impl(s, n, s->rq_rays, p, st, hit_id ? s->rq_hit.p : nullptr, t ? s->rq_t.p : nullptr, rgb_linear ? s->rq_lin.p : nullptr,
-                                   rgb8 ? s->rq_rgb8.p : nullptr, true));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (s->qlights_stream == st) s->qlights_settled = true;
-    if (hit_id) HIP_TRY(hipMemcpy(hit_id, s->rq_hit, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (t) HIP_TRY(hipMemcpy(t, s->rq_t, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
-    if (rgb_linear) HIP_TRY(hipMemcpy(rgb_linear, s->rq_lin, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToHost));
-    if (rgb8) HIP_TRY(hipMemcpy(rgb8, s->rq_rgb8, (size_t)n * 3, hipMemcpyDeviceToHost));
-    if (stats) {
-        std::array<unsigned long long, NCTR> c;
-        HIP_TRY(hipMemcpy(c.data(), s->d_qctr, NCTR * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-        stats->primary_rays = n;
-        for (int k = 0; k < HIT_SHARDS; k++) stats->hit_rays += c[CTR_HIT_BASE + 8 * k];
-        stats->shadow_rays = stats->hit_rays * p->n_lights;
-        stats->node_tests_primary = c[1]; stats->tri_tests_primary = c[2];
-        stats->node_tests_shadow = c[3]; stats->tri_tests_shadow = c[4];
-    }
-    return SRT_OK;
+    const auto o_hit = query_out(hit_id, s->rq_hit); const auto o_t = query_out(t, s->rq_t);
+    const auto o_lin = query_out(rgb_linear, s->rq_lin); const auto o_rgb8 = query_out(rgb8, s->rq_rgb8);
+    SRT_TRY(query_round_trip(s, n, rays, nullptr, [&](hipStream_t st) {
+        return shade_rays_device_impl(s, n, s->rq_rays, p, st, o_hit.wanted(), o_t.wanted(), o_lin.wanted(), o_rgb8.wanted(), true);
+    }, o_hit, o_t, o_lin, o_rgb8));
+    return stats ? query_stats(s, n, p->n_lights, stats) : SRT_OK;
 }
 
 int srt_trace_rays_device(srt_scene* s, uint32_t n, const float* d_rays, uint32_t flags, void* stream, int32_t* d_hit_id, float* d_t, float* d_bary) {

@@ -126,6 +126,25 @@ __device__ __forceinline__ bool tile_pixel(const DevParams& p, uint32_t& px, uin
     r  = blockIdx.y * 16 + (wave >> 1) * 8 + (lane >> 3);
     return pixel_live(p, px, r);
 }
+
+// A finished pixel, wherever it comes from: the light sum as it is into rgb_linear, and into rgb8 Reinhard + gamma (:391-398), the
+// quantiser (:447-449) and the black -> background rule (:518, drawImage:476-487).  lit = false (a miss, a ray without a hit): no tone
+// map, the background bytes.  Either output may be absent.
+__device__ __forceinline__ void store_pixel(float* __restrict__ rgb_linear, uint8_t* __restrict__ rgb8, const size_t pix, const V3 sum, const bool lit,
+                                            const float reinhard, const float gamma, const uint32_t bg) {
+    if (rgb_linear) { rgb_linear[pix * 3] = sum.x; rgb_linear[pix * 3 + 1] = sum.y; rgb_linear[pix * 3 + 2] = sum.z; }
+    if (rgb8) {
+        int q0 = 0, q1 = 0, q2 = 0;
+        if (lit) { q0 = quant1(tone1(sum.x, reinhard, gamma)); q1 = quant1(tone1(sum.y, reinhard, gamma)); q2 = quant1(tone1(sum.z, reinhard, gamma)); }
+        if ((q0 | q1 | q2) == 0) { q0 = bg & 255; q1 = (bg >> 8) & 255; q2 = (bg >> 16) & 255; }
+        rgb8[pix * 3] = (uint8_t)q0; rgb8[pix * 3 + 1] = (uint8_t)q1; rgb8[pix * 3 + 2] = (uint8_t)q2;
+    }
+}
+// A miss is final where it is found: zero light sum, background pixel.
+__device__ __forceinline__ void store_miss(float* __restrict__ rgb_linear, uint8_t* __restrict__ rgb8, const size_t pix, const uint32_t bg) {
+    store_pixel(rgb_linear, rgb8, pix, mk(0.0f, 0.0f, 0.0f), false, 0.0f, 0.0f, bg);
+}
+
 // =================================================================================================
 // Kernel 1: closest hit.  rayIntersection:405-431 with boundingBoxIntersection:296-317 fused in:
 // walk ALL slab-passing nodes of ALL objects in pre-order (== reference visit order), test leaf
@@ -156,11 +175,10 @@ __global__ __launch_bounds__(256) void k_closest_hit(DevScene s, DevParams p, in
                 if (leaf >= 0) {
                     const int32_t first = leaf >> LEAF_SHIFT, cnt = leaf & LEAF_MAX;
                     for (int32_t k = 0; k < cnt; k++) {
-                        const size_t ti = (size_t)(first + k) * 3;
-                        const float4 t0 = tris4[ti], t1 = tris4[ti + 1];
-                        const float e2z = reinterpret_cast<const float*>(tris4 + ti + 2)[0];
+                        V3 p1, e1, e2;
+                        load_tri_edges(tris4, (size_t)(first + k), p1, e1, e2);
                         if (COUNT) n_tri++;
-                        const float t = ray_triangle(o, d, mk(t0.x, t0.y, t0.z), mk(t0.w, t1.x, t1.y), mk(t1.z, t1.w, e2z));
+                        const float t = ray_triangle(o, d, p1, e1, e2);
                         if (t != SRT_NEG_INF && t < best) { best = t; best_id = first + k; }
                     }
                 }
@@ -262,11 +280,10 @@ __global__ __launch_bounds__(256) void k_closest_hit_q(DevScene s, DevParams p, 
                 const uint32_t e = q[qn + lane];
                 const uint32_t src = e & 63u, tri = e >> 6;
                 const V3 ds = primary_dir(p, tile_x + (src & 7), image_row(p, tile_r + (src >> 3)));
-                const size_t ti = (size_t)tri * 3;
-                const float4 t0 = tris4[ti], t1 = tris4[ti + 1];
-                const float e2z = reinterpret_cast<const float*>(tris4 + ti + 2)[0];
+                V3 p1, e1, e2;
+                load_tri_edges(tris4, tri, p1, e1, e2);
                 if (COUNT) n_tri++;
-                const float t = ray_triangle(o, ds, mk(t0.x, t0.y, t0.z), mk(t0.w, t1.x, t1.y), mk(t1.z, t1.w, e2z));
+                const float t = ray_triangle(o, ds, p1, e1, e2);
                 // candidate iff t != -inf && t < +inf (the initial distanceComparison, :408); NaN fails '<'
                 if (t != SRT_NEG_INF && t < __builtin_inff()) {
                     const uint32_t tb = (t == 0.0f) ? 0u : __float_as_uint(t);     // -0.0 ties with +0.0
@@ -285,18 +302,14 @@ __global__ __launch_bounds__(256) void k_closest_hit_q(DevScene s, DevParams p, 
         if (key != ~0ull) {
             id = (int32_t)(uint32_t)key;
             // the winner's t with its own bits (incl. the sign of a zero): same function, same inputs
-            const size_t ti = (size_t)id * 3;
-            const float4 t0 = tris4[ti], t1 = tris4[ti + 1];
-            const float e2z = reinterpret_cast<const float*>(tris4 + ti + 2)[0];
-            t = ray_triangle(o, d, mk(t0.x, t0.y, t0.z), mk(t0.w, t1.x, t1.y), mk(t1.z, t1.w, e2z));
+            V3 p1, e1, e2;
+            load_tri_edges(tris4, (size_t)id, p1, e1, e2);
+            t = ray_triangle(o, d, p1, e1, e2);
         }
         const size_t pix = (size_t)r * p.W + px;
         hit_id[pix] = id;
         t_out[pix] = t;
-        if (id < 0) {      // a miss is final here: zero light sum, background pixel (:518, drawImage:476-487)
-            if (rgb_linear) { rgb_linear[pix * 3] = 0.0f; rgb_linear[pix * 3 + 1] = 0.0f; rgb_linear[pix * 3 + 2] = 0.0f; }
-            if (rgb8) { rgb8[pix * 3] = (uint8_t)(p.bg & 255); rgb8[pix * 3 + 1] = (uint8_t)((p.bg >> 8) & 255); rgb8[pix * 3 + 2] = (uint8_t)((p.bg >> 16) & 255); }
-        }
+        if (id < 0) store_miss(rgb_linear, rgb8, pix, p.bg);
         is_hit = id >= 0;
     }
     count_hits(counters, is_hit, blockIdx.y * gridDim.x + blockIdx.x);
@@ -770,19 +783,15 @@ __device__ __forceinline__ void closest_hit_phase(const DevScene& s, const DevPa
             // zero is evaluated again, to get its sign (same function, same inputs)
             t = __uint_as_float((uint32_t)(key >> 32));
             if (t == 0.0f) {
-                const size_t ti = (size_t)id * 3;
-                const float4 t0 = tris4[ti], t1 = tris4[ti + 1];
-                const float e2z = reinterpret_cast<const float*>(tris4 + ti + 2)[0];
-                t = ray_triangle(o, dmine, mk(t0.x, t0.y, t0.z), mk(t0.w, t1.x, t1.y), mk(t1.z, t1.w, e2z));
+                V3 p1, e1, e2;
+                load_tri_edges(tris4, (size_t)id, p1, e1, e2);
+                t = ray_triangle(o, dmine, p1, e1, e2);
             }
         }
         const size_t pix = (size_t)r * p.W + px;
         hit_id[pix] = id;
         t_out[pix] = t;
-        if (id < 0) {      // a miss is final here: zero light sum, background pixel (:518, drawImage:476-487)
-            if (rgb_linear) { rgb_linear[pix * 3] = 0.0f; rgb_linear[pix * 3 + 1] = 0.0f; rgb_linear[pix * 3 + 2] = 0.0f; }
-            if (rgb8) { rgb8[pix * 3] = (uint8_t)(p.bg & 255); rgb8[pix * 3 + 1] = (uint8_t)((p.bg >> 8) & 255); rgb8[pix * 3 + 2] = (uint8_t)((p.bg >> 16) & 255); }
-        }
+        if (id < 0) store_miss(rgb_linear, rgb8, pix, p.bg);
         is_hit = id >= 0;
         out_id = id; out_t = t;
     }
@@ -884,12 +893,11 @@ __device__ __forceinline__ bool background_test_wave(const DevScene& s, const De
     if (root_pass) root_pass[lane] = live ? pmask : 0u;
     const unsigned long long m = __ballot(live && any);
     if (m == 0ull) {
-        if (live) {      // what closest_hit_phase writes for a miss (:518, drawImage:476-487)
+        if (live) {      // what closest_hit_phase writes for a miss
             const size_t pix = (size_t)r * p.W + px;
             hit_id[pix] = -1;
             t_out[pix] = __builtin_inff();
-            if (rgb_linear) { rgb_linear[pix * 3] = 0.0f; rgb_linear[pix * 3 + 1] = 0.0f; rgb_linear[pix * 3 + 2] = 0.0f; }
-            if (rgb8) { rgb8[pix * 3] = (uint8_t)(p.bg & 255); rgb8[pix * 3 + 1] = (uint8_t)((p.bg >> 8) & 255); rgb8[pix * 3 + 2] = (uint8_t)((p.bg >> 16) & 255); }
+            store_miss(rgb_linear, rgb8, pix, p.bg);
         }
         if (shadow_bits) {
             const size_t tile_index = (size_t)by * gx + bx;
@@ -961,33 +969,40 @@ __global__ __launch_bounds__(256, MINW) void k_closest_hit_nq(DevScene s, DevPar
 
 // =================================================================================================
 // Kernel 2: shadow rays + shading + tone map.  softShadow:348-401 -> shadowIntersection:321-342 +
-// phongIllumination:144-200, then the quantiser (:447-449) and the black -> background rule
-// (:518, drawImage:476-487).  Shading runs once, for the closest hit (the reference re-shades every
-// improving hit and keeps the last: same value).  The hit object's own tree is skipped (the reference
-// walks it and discards the result, :328/:331) and the any-hit walk exits at the first hit.
+// phongIllumination:144-200, then the pixel (store_pixel).  Shading runs once, for the closest hit (the
+// reference re-shades every improving hit and keeps the last: same value).  The hit object's own tree is
+// skipped (the reference walks it and discards the result, :328/:331) and the any-hit walk exits at the
+// first hit.
 // =================================================================================================
-template <bool COUNT>
+// One shadow ray on its own lane: shadowIntersection:321-342 over every node outside [self.x, self.y), t unbounded, any
+// Moller-Trumbore result other than -inf counts (NaN included); the lane leaves at its first hit.
+// FILTER: the slab test through slab_pass (reciprocal filter, exact fallback) instead of the exact divides alone -- the same answers.
+// COUNT: the oracle's algorithmic counts -- objects in order, one slab test per node met, one triangle test up to and including the
+// first hit.
+template <bool COUNT, bool FILTER>
 __device__ __forceinline__ bool any_hit_range(const DevScene& s, int2 self, V3 so, V3 sd,
                                               unsigned long long& n_node, unsigned long long& n_tri) {
     const float4* nodes4 = reinterpret_cast<const float4*>(s.nodes);
     const float4* tris4 = reinterpret_cast<const float4*>(s.tris);
-    int32_t i = 0;
+    RayRcp rc;
+    if (FILTER) rc = ray_rcp(sd);
     const int32_t n = (int32_t)s.n_nodes;
-    while (i < n) {
+    int32_t i = 0;
+    bool hit = false;
+    while (i < n && !hit) {
         if (i == self.x) { i = self.y; continue; }
         const float4 a = nodes4[2 * (size_t)i], b = nodes4[2 * (size_t)i + 1];
         const int32_t skip = __float_as_int(b.z), leaf = __float_as_int(b.w);
         if (COUNT) n_node++;
-        if (ray_aabb(so, sd, a.x, a.y, a.z, a.w, b.x, b.y)) {
+        if (FILTER ? slab_pass<true>(so, sd, rc, a.x, a.y, a.z, a.w, b.x, b.y) : ray_aabb(so, sd, a.x, a.y, a.z, a.w, b.x, b.y)) {
             if (leaf >= 0) {
                 const int32_t first = leaf >> LEAF_SHIFT, cnt = leaf & LEAF_MAX;
-                for (int32_t k = 0; k < cnt; k++) {
-                    const size_t ti = (size_t)(first + k) * 3;
-                    const float4 t0 = tris4[ti], t1 = tris4[ti + 1];
-                    const float e2z = reinterpret_cast<const float*>(tris4 + ti + 2)[0];
+                for (int32_t k = 0; k < cnt && !hit; k++) {
+                    V3 p1, e1, e2;
+                    load_tri_edges(tris4, (size_t)(first + k), p1, e1, e2);
                     if (COUNT) n_tri++;
-                    const float t = ray_triangle(so, sd, mk(t0.x, t0.y, t0.z), mk(t0.w, t1.x, t1.y), mk(t1.z, t1.w, e2z));
-                    if (t != SRT_NEG_INF) return true;       // any t >= 0, NaN included (:335)
+                    const float t = ray_triangle(so, sd, p1, e1, e2);
+                    hit = t != SRT_NEG_INF;                  // any t >= 0, NaN included (:335)
                 }
             }
             i = i + 1;
@@ -995,14 +1010,66 @@ __device__ __forceinline__ bool any_hit_range(const DevScene& s, int2 self, V3 s
             i = skip;
         }
     }
-    return false;
-}
-template <bool COUNT>
-__device__ __forceinline__ bool any_hit(const DevScene& s, int32_t self_obj, V3 so, V3 sd,
-                                        unsigned long long& n_node, unsigned long long& n_tri) {
-    return any_hit_range<COUNT>(s, s.obj_range[self_obj], so, sd, n_node, n_tri);
+    return hit;
 }
 
+// What shading needs to know of the surface at a hit.
+struct Surface {
+    V3 color;              // the object's colour (:437-440), or the texel under the hit point (:350-361)
+    V3 nrm;                // the face normal, or interpolateNormal's (phongIllumination:159,162, opt-in mode)
+    float ka, ks, sh;
+};
+// The surface of triangle `id` where the ray o + d * t meets it.  The barycentric coordinates are taken once, for a textured triangle
+// and for smooth normals.
+__device__ __forceinline__ Surface surface_at(const DevScene& s, const int32_t id, const V3 o, const V3 d, const float t, const bool smooth) {
+    Surface f;
+    const int32_t obj = s.tri_obj[id];
+    const float4* tp = reinterpret_cast<const float4*>(s.tris) + (size_t)id * 3;
+    const float4 t2 = tp[2];
+    f.nrm = mk(t2.y, t2.z, t2.w);
+    f.color = mk(s.obj_color[obj * 3], s.obj_color[obj * 3 + 1], s.obj_color[obj * 3 + 2]);
+    const int32_t tex = s.tri_tex ? s.tri_tex[id] : -1;
+    V3 bc = mk(0.0f, 0.0f, 0.0f);
+    if (tex >= 0 || smooth) {
+        const float4 t0 = tp[0], t1 = tp[1];
+        bc = barycentric(mk(t0.x, t0.y, t0.z), mk(t0.w, t1.x, t1.y), mk(t1.z, t1.w, t2.x), o + d * t);
+    }
+    if (tex >= 0) {
+        const float* tc = s.tri_tc + (size_t)id * 6;
+        const float tx = (bc.x * tc[0] + bc.y * tc[2]) + bc.z * tc[4];                          // :123-125
+        const float ty = (bc.x * tc[1] + bc.y * tc[3]) + bc.z * tc[5];
+        long long idx = ((long long)((int)ty * (int)s.tex_w[tex] + (int)tx)) * 3;               // :357
+        // the reference reads out of bounds if the texel index leaves the image (UB); this project clamps into the texture instead
+        const long long last = (long long)s.tex_size[tex] - 3;
+        idx = idx < 0 ? 0 : (idx > last ? last : idx);
+        const uint8_t* td = s.tex + s.tex_off[tex] + idx;
+        f.color = mk(td[0] / 255.0f, td[1] / 255.0f, td[2] / 255.0f);
+    }
+    f.ka = s.obj_mat[obj * 3]; f.ks = s.obj_mat[obj * 3 + 1]; f.sh = s.obj_mat[obj * 3 + 2];
+    if (smooth) {
+        const float* n9 = s.tri_normals + (size_t)id * 9;
+        f.nrm = normalize3(mk((bc.x * n9[0] + bc.y * n9[3]) + bc.z * n9[6], (bc.x * n9[1] + bc.y * n9[4]) + bc.z * n9[7],
+                              (bc.x * n9[2] + bc.y * n9[5]) + bc.z * n9[8]));
+    }
+    return f;
+}
+
+// The light-sample sum of softShadow:366-383 over samples [l0, l0 + m), in light order: Phong per sample, a shadowed sample divided
+// (:369), one f32 add per component and sample into `sum` (:370).  `shadowed(l)` says whether sample l's shadow ray was blocked.
+template <bool INT_SHIN, typename SH>
+__device__ __forceinline__ void add_light_samples(V3& sum, const Surface& f, const V3 o, const V3 d, const float t, const float* __restrict__ lights,
+                                                  const uint32_t l0, const uint32_t m, const float shadow_div, SH shadowed) {
+    for (uint32_t l = l0; l < l0 + m; l++) {
+        const float* lp = lights + (size_t)l * 3;
+        const V3 L = mk(lp[0], lp[1], lp[2]);
+        const bool sd = shadowed(l);
+        V3 c = phong<INT_SHIN>(f.nrm, o, d, L, f.color, f.ka, f.ks, f.sh, t);
+        if (sd) c = mk(c.x / shadow_div, c.y / shadow_div, c.z / shadow_div);
+        sum = sum + c;
+    }
+}
+
+// One thread per pixel: the shadow rays walk on their own lanes (exact slab test: variant 1 and its counts are defined by it).
 template <bool COUNT>
 __global__ __launch_bounds__(256) void k_shade(DevScene s, DevParams p, const int32_t* __restrict__ hit_id,
                                                const float* __restrict__ t_in, float* __restrict__ rgb_linear,
@@ -1017,50 +1084,20 @@ __global__ __launch_bounds__(256) void k_shade(DevScene s, DevParams p, const in
         const size_t pix = (size_t)r * p.W + px;
         const int32_t id = hit_id[pix];
         V3 sum = mk(0.0f, 0.0f, 0.0f);
-        int q0 = 0, q1 = 0, q2 = 0;
         if (id >= 0) {
             is_hit = true;
             const float t = t_in[pix];
             const V3 o = mk(0.0f, 0.0f, 0.0f);
             const V3 d = primary_dir(p, px, image_row(p, r));
-            const int32_t obj = s.tri_obj[id];
-            const float4* tp = reinterpret_cast<const float4*>(s.tris) + (size_t)id * 3;
-            const float4 t0 = tp[0], t1 = tp[1], t2 = tp[2];
-            const V3 nrm = mk(t2.y, t2.z, t2.w);
-            V3 color = mk(s.obj_color[obj * 3], s.obj_color[obj * 3 + 1], s.obj_color[obj * 3 + 2]);     // :437-440
-            const int32_t tex = s.tri_tex ? s.tri_tex[id] : -1;
-            if (tex >= 0) {                                                                             // :350-361
-                const V3 P = o + d * t;
-                const V3 bc = barycentric(mk(t0.x, t0.y, t0.z), mk(t0.w, t1.x, t1.y), mk(t1.z, t1.w, t2.x), P);
-                const float* tc = s.tri_tc + (size_t)id * 6;
-                const float tx = (bc.x * tc[0] + bc.y * tc[2]) + bc.z * tc[4];                          // :123-125
-                const float ty = (bc.x * tc[1] + bc.y * tc[3]) + bc.z * tc[5];
-                long long idx = ((long long)((int)ty * (int)s.tex_w[tex] + (int)tx)) * 3;               // :357
-                // the reference reads out of bounds here if the texel index leaves the image (UB);
-                // this kernel clamps into the texture instead of faulting
-                const long long last = (long long)s.tex_size[tex] - 3;
-                idx = idx < 0 ? 0 : (idx > last ? last : idx);
-                const uint8_t* td = s.tex + s.tex_off[tex] + idx;
-                color = mk(td[0] / 255.0f, td[1] / 255.0f, td[2] / 255.0f);
-            }
-            const float ka = s.obj_mat[obj * 3], ks = s.obj_mat[obj * 3 + 1], sh = s.obj_mat[obj * 3 + 2];
+            const Surface f = surface_at(s, id, o, d, t, false);
+            const int2 self = s.obj_range[s.tri_obj[id]];
             const V3 dt = d * t;                      // shadowIntersection:325-326: origin d*t, dir L - d*t
-            for (uint32_t l = 0; l < p.n_lights; l++) {                                                 // :366-383
+            add_light_samples<false>(sum, f, o, d, t, p.lights, 0u, p.n_lights, p.shadow_div, [&](uint32_t l) -> bool {
                 const V3 L = mk(p.lights[l * 3], p.lights[l * 3 + 1], p.lights[l * 3 + 2]);
-                const bool shadowed = any_hit<COUNT>(s, obj, dt, L - dt, n_node, n_tri);
-                V3 c = phong(nrm, o, d, L, color, ka, ks, sh, t);
-                if (shadowed) c = mk(c.x / p.shadow_div, c.y / p.shadow_div, c.z / p.shadow_div);       // :369
-                sum = sum + c;                                                                          // :370
-            }
-            q0 = quant1(tone1(sum.x, p.reinhard, p.gamma));                                             // :391-398,447-449
-            q1 = quant1(tone1(sum.y, p.reinhard, p.gamma));
-            q2 = quant1(tone1(sum.z, p.reinhard, p.gamma));
+                return any_hit_range<COUNT, false>(s, self, dt, L - dt, n_node, n_tri);
+            });
         }
-        if (rgb_linear) { rgb_linear[pix * 3] = sum.x; rgb_linear[pix * 3 + 1] = sum.y; rgb_linear[pix * 3 + 2] = sum.z; }
-        if (rgb8) {
-            if ((q0 | q1 | q2) == 0) { q0 = p.bg & 255; q1 = (p.bg >> 8) & 255; q2 = (p.bg >> 16) & 255; }   // :518, :476-487
-            rgb8[pix * 3] = (uint8_t)q0; rgb8[pix * 3 + 1] = (uint8_t)q1; rgb8[pix * 3 + 2] = (uint8_t)q2;
-        }
+        store_pixel(rgb_linear, rgb8, pix, sum, is_hit, p.reinhard, p.gamma, p.bg);
     }
     count_hits(counters, is_hit, blockIdx.y * gridDim.x + blockIdx.x);
     if (COUNT) { wave_add(counters + 3, n_node); wave_add(counters + 4, n_tri); }
@@ -1243,7 +1280,7 @@ __device__ __forceinline__ void shadow_phase(const DevScene& s, const DevParams&
             }
             bool shadowed = false;
             if (SEQ) {
-                if (valid) shadowed = any_hit_range<true>(s, self, so, sd, n_node, n_tri);
+                if (valid) shadowed = any_hit_range<true, false>(s, self, so, sd, n_node, n_tri);
             } else {
                 if (lane < RS) {
                     ray[lane] = make_float4(so.x, so.y, so.z, 0.f);
@@ -1487,54 +1524,12 @@ __global__ __launch_bounds__(256, MINW) void k_shadow_nq(DevScene s, DevParams p
 template <bool INT_SHIN = false, typename SH>
 __device__ __forceinline__ void shade_hit_pixel(const DevScene& s, const DevParams& p, const int32_t id, const float t, const uint32_t px, const uint32_t r,
                                                 SH shadowed, float* __restrict__ rgb_linear, uint8_t* __restrict__ rgb8) {
-    const size_t pix = (size_t)r * p.W + px;
     const V3 o = ray_origin(p);
     const V3 d = primary_dir(p, px, image_row(p, r));
-    const int32_t obj = s.tri_obj[id];
-    const float4* tp = reinterpret_cast<const float4*>(s.tris) + (size_t)id * 3;
-    const float4 t2 = tp[2];
-    const V3 nrm = mk(t2.y, t2.z, t2.w);
-    V3 color = mk(s.obj_color[obj * 3], s.obj_color[obj * 3 + 1], s.obj_color[obj * 3 + 2]);     // :437-440
-    const int32_t tex = s.tri_tex ? s.tri_tex[id] : -1;
-    if (tex >= 0) {                                                                             // :350-361
-        const float4 t0 = tp[0], t1 = tp[1];
-        const V3 P = o + d * t;
-        const V3 bc = barycentric(mk(t0.x, t0.y, t0.z), mk(t0.w, t1.x, t1.y), mk(t1.z, t1.w, t2.x), P);
-        const float* tc = s.tri_tc + (size_t)id * 6;
-        const float tx = (bc.x * tc[0] + bc.y * tc[2]) + bc.z * tc[4];                          // :123-125
-        const float ty = (bc.x * tc[1] + bc.y * tc[3]) + bc.z * tc[5];
-        long long idx = ((long long)((int)ty * (int)s.tex_w[tex] + (int)tx)) * 3;               // :357
-        // the reference reads out of bounds if the texel index leaves the image (UB); clamp instead
-        const long long last = (long long)s.tex_size[tex] - 3;
-        idx = idx < 0 ? 0 : (idx > last ? last : idx);
-        const uint8_t* td = s.tex + s.tex_off[tex] + idx;
-        color = mk(td[0] / 255.0f, td[1] / 255.0f, td[2] / 255.0f);
-    }
-    const float ka = s.obj_mat[obj * 3], ks = s.obj_mat[obj * 3 + 1], sh = s.obj_mat[obj * 3 + 2];
-    V3 nrm_use = nrm;
-    if (p.smooth) {        // phongIllumination:159,162 with the interpolateNormal line enabled (opt-in mode)
-        const float4 t0 = tp[0], t1 = tp[1];
-        const V3 bc = barycentric(mk(t0.x, t0.y, t0.z), mk(t0.w, t1.x, t1.y), mk(t1.z, t1.w, t2.x), o + d * t);
-        const float* n9 = s.tri_normals + (size_t)id * 9;
-        nrm_use = normalize3(mk((bc.x * n9[0] + bc.y * n9[3]) + bc.z * n9[6], (bc.x * n9[1] + bc.y * n9[4]) + bc.z * n9[7],
-                                (bc.x * n9[2] + bc.y * n9[5]) + bc.z * n9[8]));
-    }
+    const Surface f = surface_at(s, id, o, d, t, p.smooth != 0u);
     V3 sum = mk(0.0f, 0.0f, 0.0f);
-    for (uint32_t l = 0; l < p.n_lights; l++) {                                                 // :366-383
-        const V3 L = mk(p.lights[l * 3], p.lights[l * 3 + 1], p.lights[l * 3 + 2]);
-        const bool sd = shadowed(l);
-        V3 c = phong<INT_SHIN>(nrm_use, o, d, L, color, ka, ks, sh, t);
-        if (sd) c = mk(c.x / p.shadow_div, c.y / p.shadow_div, c.z / p.shadow_div);             // :369
-        sum = sum + c;                                                                          // :370
-    }
-    int q0 = quant1(tone1(sum.x, p.reinhard, p.gamma));                                         // :391-398,447-449
-    int q1 = quant1(tone1(sum.y, p.reinhard, p.gamma));
-    int q2 = quant1(tone1(sum.z, p.reinhard, p.gamma));
-    if (rgb_linear) { rgb_linear[pix * 3] = sum.x; rgb_linear[pix * 3 + 1] = sum.y; rgb_linear[pix * 3 + 2] = sum.z; }
-    if (rgb8) {
-        if ((q0 | q1 | q2) == 0) { q0 = p.bg & 255; q1 = (p.bg >> 8) & 255; q2 = (p.bg >> 16) & 255; }   // :518, :476-487
-        rgb8[pix * 3] = (uint8_t)q0; rgb8[pix * 3 + 1] = (uint8_t)q1; rgb8[pix * 3 + 2] = (uint8_t)q2;
-    }
+    add_light_samples<INT_SHIN>(sum, f, o, d, t, p.lights, 0u, p.n_lights, p.shadow_div, shadowed);
+    store_pixel(rgb_linear, rgb8, (size_t)r * p.W + px, sum, true, p.reinhard, p.gamma, p.bg);
 }
 
 // =================================================================================================
@@ -1784,13 +1779,8 @@ __global__ __launch_bounds__(256) void k_resolve(DevParams p, const float* __res
     if (blockIdx.x == 0) for (int i = threadIdx.x; i < NCTR; i += 256) counters_next[i] = 0ull;
     const uint32_t i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n_pixels || !resolve_live(p, i)) return;
-    const float a0 = acc[(size_t)i * 3] / spp, a1 = acc[(size_t)i * 3 + 1] / spp, a2 = acc[(size_t)i * 3 + 2] / spp;
-    if (rgb_linear) { rgb_linear[(size_t)i * 3] = a0; rgb_linear[(size_t)i * 3 + 1] = a1; rgb_linear[(size_t)i * 3 + 2] = a2; }
-    if (rgb8) {
-        int q0 = quant1(tone1(a0, p.reinhard, p.gamma)), q1 = quant1(tone1(a1, p.reinhard, p.gamma)), q2 = quant1(tone1(a2, p.reinhard, p.gamma));
-        if ((q0 | q1 | q2) == 0) { q0 = p.bg & 255; q1 = (p.bg >> 8) & 255; q2 = (p.bg >> 16) & 255; }
-        rgb8[(size_t)i * 3] = (uint8_t)q0; rgb8[(size_t)i * 3 + 1] = (uint8_t)q1; rgb8[(size_t)i * 3 + 2] = (uint8_t)q2;
-    }
+    const V3 a = mk(acc[(size_t)i * 3] / spp, acc[(size_t)i * 3 + 1] / spp, acc[(size_t)i * 3 + 2] / spp);
+    store_pixel(rgb_linear, rgb8, (size_t)i, a, true, p.reinhard, p.gamma, p.bg);
 }
 
 // =================================================================================================

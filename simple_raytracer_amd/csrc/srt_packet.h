@@ -342,10 +342,7 @@ __global__ __launch_bounds__(256) void k_closest_hit_pk(DevScene s, DevParams p,
         const size_t pix = (size_t)r * p.W + px;
         hit_id[pix] = id;
         t_out[pix] = best;
-        if (id < 0) {      // a miss is final here: zero light sum, background pixel (:518, drawImage:476-487)
-            if (rgb_linear) { rgb_linear[pix * 3] = 0.0f; rgb_linear[pix * 3 + 1] = 0.0f; rgb_linear[pix * 3 + 2] = 0.0f; }
-            if (rgb8) { rgb8[pix * 3] = (uint8_t)(p.bg & 255); rgb8[pix * 3 + 1] = (uint8_t)((p.bg >> 8) & 255); rgb8[pix * 3 + 2] = (uint8_t)((p.bg >> 16) & 255); }
-        }
+        if (id < 0) store_miss(rgb_linear, rgb8, pix, p.bg);
     }
     const unsigned long long hm = __ballot(live && id >= 0);
     if (lane == 0 && hm) {

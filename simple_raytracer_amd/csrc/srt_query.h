@@ -100,11 +100,10 @@ __device__ __forceinline__ void query_closest_walk(const DevScene& s, const bool
                 const uint32_t e = q[qn + lane];
                 const uint32_t src = e & 63u, tri = e >> 6;
                 const V3 os = mk(wray[0][src], wray[1][src], wray[2][src]), ds = mk(wray[3][src], wray[4][src], wray[5][src]);
-                const size_t ti = (size_t)tri * 3;
-                const float4 t0 = tris4[ti], t1 = tris4[ti + 1];
-                const float e2z = reinterpret_cast<const float*>(tris4 + ti + 2)[0];
+                V3 p1, e1, e2;
+                load_tri_edges(tris4, tri, p1, e1, e2);
                 if (COUNT) n_tri++;
-                const float t = ray_triangle(os, ds, mk(t0.x, t0.y, t0.z), mk(t0.w, t1.x, t1.y), mk(t1.z, t1.w, e2z));
+                const float t = ray_triangle(os, ds, p1, e1, e2);
                 // candidate iff t != -inf && t < +inf (the initial distanceComparison, :408); NaN fails '<'
                 if (t != SRT_NEG_INF && t < __builtin_inff()) {
                     const uint32_t tb = (t == 0.0f) ? 0u : __float_as_uint(t);     // -0.0 ties with +0.0
@@ -142,12 +141,10 @@ __global__ __launch_bounds__(256) void k_query_closest(DevScene s, uint32_t n_ra
         if (key != ~0ull) {
             id = (int32_t)(uint32_t)key;
             // the winner's t with its own bits (incl. the sign of a zero): same function, same inputs
-            const size_t ti = (size_t)id * 3;
-            const float4 t0 = tris4[ti], t1 = tris4[ti + 1];
-            const float e2z = reinterpret_cast<const float*>(tris4 + ti + 2)[0];
-            const V3 p1 = mk(t0.x, t0.y, t0.z), e1 = mk(t0.w, t1.x, t1.y), e2 = mk(t1.z, t1.w, e2z);
+            V3 p1, e1, e2;
+            load_tri_edges(tris4, (size_t)id, p1, e1, e2);
             t = ray_triangle(o, d, p1, e1, e2);
-            if (BARY) bc = barycentric(p1, e1, e2, o + d * t);       // calculateBarycentricCoords at the hit point, as the textured shading path
+            if (BARY) bc = barycentric(p1, e1, e2, o + d * t);       // calculateBarycentricCoords at the hit point
         }
         if (hit_id) hit_id[ri] = id;
         if (t_out) t_out[ri] = t;
@@ -159,48 +156,10 @@ __global__ __launch_bounds__(256) void k_query_closest(DevScene s, uint32_t n_ra
 }
 
 // =================================================================================================
-// Occlusion of caller-supplied rays: shadowIntersection:321-342 over every object but skip_obj[i] -- the oracle's anyhit_in_tree,
-// t unbounded, any Moller-Trumbore result other than -inf counts (NaN included).  One ray per lane, per-lane walk as any_hit_range
-// does it (the skipped object's node range is stepped over), the lane leaves at its first hit.
+// Occlusion of caller-supplied rays: shadowIntersection:321-342 over every object but skip_obj[i] -- the oracle's anyhit_in_tree.
+// One ray per lane, each on its own walk (any_hit_range, filtered slab test; the skipped object's node range is stepped over).
 // An entry of skip_obj outside [0, n_objects) skips nothing.
 // =================================================================================================
-// The walk of one ray on its own lane, shared by k_query_any and k_query_shade.  self: the node range that is stepped over.
-// COUNT: the oracle's algorithmic counts -- a sequential walk, objects in order, one slab test per node met, one Moller-Trumbore test per
-// triangle up to and including the first hit.
-template <bool COUNT>
-__device__ __forceinline__ bool query_any_walk(const DevScene& s, const int2 self, const V3 o, const V3 d, unsigned long long& n_node,
-                                               unsigned long long& n_tri) {
-    const RayRcp rc = ray_rcp(d);
-    const float4* nodes4 = reinterpret_cast<const float4*>(s.nodes);
-    const float4* tris4 = reinterpret_cast<const float4*>(s.tris);
-    const int32_t n = (int32_t)s.n_nodes;
-    int32_t i = 0;
-    bool hit = false;
-    while (i < n && !hit) {
-        if (i == self.x) { i = self.y; continue; }
-        const float4 a = nodes4[2 * (size_t)i], b = nodes4[2 * (size_t)i + 1];
-        const int32_t skip = __float_as_int(b.z), leaf = __float_as_int(b.w);
-        if (COUNT) n_node++;
-        if (slab_pass<true>(o, d, rc, a.x, a.y, a.z, a.w, b.x, b.y)) {
-            if (leaf >= 0) {
-                const int32_t first = leaf >> LEAF_SHIFT, cnt = leaf & LEAF_MAX;
-                for (int32_t k = 0; k < cnt && !hit; k++) {
-                    const size_t ti = (size_t)(first + k) * 3;
-                    const float4 t0 = tris4[ti], t1 = tris4[ti + 1];
-                    const float e2z = reinterpret_cast<const float*>(tris4 + ti + 2)[0];
-                    if (COUNT) n_tri++;
-                    const float t = ray_triangle(o, d, mk(t0.x, t0.y, t0.z), mk(t0.w, t1.x, t1.y), mk(t1.z, t1.w, e2z));
-                    hit = t != SRT_NEG_INF;                      // any t >= 0, NaN included (:335)
-                }
-            }
-            i = i + 1;
-        } else {
-            i = skip;
-        }
-    }
-    return hit;
-}
-
 __global__ __launch_bounds__(256) void k_query_any(DevScene s, uint32_t n_rays, const float* __restrict__ rays, uint32_t wide,
                                                    const int32_t* __restrict__ skip_obj, uint8_t* __restrict__ occluded) {
     const size_t ri = (size_t)blockIdx.x * 256 + threadIdx.x;
@@ -213,7 +172,7 @@ __global__ __launch_bounds__(256) void k_query_any(DevScene s, uint32_t n_rays, 
         if (k >= 0 && (uint32_t)k < s.n_objects) self = s.obj_range[k];
     }
     unsigned long long n_node = 0, n_tri = 0;
-    occluded[ri] = query_any_walk<false>(s, self, o, d, n_node, n_tri) ? 1 : 0;
+    occluded[ri] = any_hit_range<false, true>(s, self, o, d, n_node, n_tri) ? 1 : 0;
 }
 
 // =================================================================================================
@@ -224,12 +183,11 @@ __global__ __launch_bounds__(256) void k_query_any(DevScene s, uint32_t n_rays, 
 // Phase 2, a wave at a time and with no barrier between waves: the wave's h hit rays are ranked (ballot + mbcnt) and leave their shadow
 // origin so = o + d * t and their object's node range in the wave's LDS, by rank (the rays' slots: phase 1 is over).  The light samples go
 // in chunks of up to 64, in light order; a chunk's h * m work items (rank, sample) are dealt to the 64 lanes round after round --
-// consecutive lanes take consecutive samples of one hit, so a round's rays leave few points -- each lane runs query_any_walk for its item
-// and ORs the answer into the hit's 64-bit word in LDS.  After a chunk every hit's own lane adds the chunk's Phong samples in light order
-// (one f32 add per sample: the oracle's sum), dividing the shadowed ones.  A wave with 3 hits and 16 samples so keeps 48 lanes walking
-// where one lane per ray would keep 3.
-// Colour (object colour or texel, the render kernels' clamp), normal (face normal or interpolateNormal) and material are fetched once per
-// hit, before the first chunk.  counters: as k_query_closest's, and [3] / [4] node / triangle tests of the shadow rays (COUNT).
+// consecutive lanes take consecutive samples of one hit, so a round's rays leave few points -- each lane runs any_hit_range for its item
+// and ORs the answer into the hit's 64-bit word in LDS.  After a chunk every hit's own lane adds the chunk's samples with the chunk's
+// mask (add_light_samples).  A wave with 3 hits and 16 samples so keeps 48 lanes walking where one lane per ray would keep 3.
+// The surface (surface_at) is fetched once per hit, before the first chunk; the pixel leaves through store_pixel.
+// counters: as k_query_closest's, and [3] / [4] node / triangle tests of the shadow rays (COUNT).
 // =================================================================================================
 struct QueryShade {
     const float* lights;          // device, n_lights x 3
@@ -263,43 +221,20 @@ __global__ __launch_bounds__(256) void k_query_shade(DevScene s, uint32_t n_rays
     const bool is_hit = key != ~0ull;
     const int32_t id = is_hit ? (int32_t)(uint32_t)key : -1;
     float t = __builtin_inff();
-    V3 color = mk(0.0f, 0.0f, 0.0f), nrm = color;
-    float ka = 0.0f, ks = 0.0f, sh = 1.0f;
+    Surface f;
+    f.color = mk(0.0f, 0.0f, 0.0f); f.nrm = f.color; f.ka = 0.0f; f.ks = 0.0f; f.sh = 1.0f;
     const unsigned long long hm = __ballot(is_hit);
     const uint32_t nh = (uint32_t)__popcll(hm), rank = lane_prefix(hm);
     __builtin_amdgcn_wave_barrier();                    // every lane has read its key: the slots are free
     if (is_hit) {
-        const float4* tp = reinterpret_cast<const float4*>(s.tris) + (size_t)id * 3;
-        const float4 t0 = tp[0], t1 = tp[1], t2 = tp[2];
-        const V3 p1 = mk(t0.x, t0.y, t0.z), e1 = mk(t0.w, t1.x, t1.y), e2 = mk(t1.z, t1.w, t2.x);
+        V3 p1, e1, e2;
+        load_tri_edges(reinterpret_cast<const float4*>(s.tris), (size_t)id, p1, e1, e2);
         t = ray_triangle(o, d, p1, e1, e2);             // the winner's t with its own bits (incl. the sign of a zero)
-        const int32_t obj = s.tri_obj[id];
         const V3 P = o + d * t;                         // shadowIntersection:325-326 in camera mode: so = o + d * t
-        const int2 self = s.obj_range[obj];
+        const int2 self = s.obj_range[s.tri_obj[id]];
         wray[0][rank] = P.x; wray[1][rank] = P.y; wray[2][rank] = P.z;
         wray[3][rank] = __int_as_float(self.x); wray[4][rank] = __int_as_float(self.y);
-        color = mk(s.obj_color[obj * 3], s.obj_color[obj * 3 + 1], s.obj_color[obj * 3 + 2]);     // :437-440
-        const int32_t tex = s.tri_tex ? s.tri_tex[id] : -1;
-        V3 bc = mk(0.0f, 0.0f, 0.0f);
-        if (tex >= 0 || SMOOTH) bc = barycentric(p1, e1, e2, P);
-        if (tex >= 0) {                                                                             // :350-361
-            const float* tc = s.tri_tc + (size_t)id * 6;
-            const float tx = (bc.x * tc[0] + bc.y * tc[2]) + bc.z * tc[4];                          // :123-125
-            const float ty = (bc.x * tc[1] + bc.y * tc[3]) + bc.z * tc[5];
-            long long idx = ((long long)((int)ty * (int)s.tex_w[tex] + (int)tx)) * 3;               // :357
-            // the reference reads out of bounds if the texel index leaves the image (UB); clamp instead, as the render kernels
-            const long long last = (long long)s.tex_size[tex] - 3;
-            idx = idx < 0 ? 0 : (idx > last ? last : idx);
-            const uint8_t* td = s.tex + s.tex_off[tex] + idx;
-            color = mk(td[0] / 255.0f, td[1] / 255.0f, td[2] / 255.0f);
-        }
-        ka = s.obj_mat[obj * 3]; ks = s.obj_mat[obj * 3 + 1]; sh = s.obj_mat[obj * 3 + 2];
-        nrm = mk(t2.y, t2.z, t2.w);
-        if (SMOOTH) {      // phongIllumination:159,162 with the interpolateNormal line enabled (opt-in mode)
-            const float* n9 = s.tri_normals + (size_t)id * 9;
-            nrm = normalize3(mk((bc.x * n9[0] + bc.y * n9[3]) + bc.z * n9[6], (bc.x * n9[1] + bc.y * n9[4]) + bc.z * n9[7],
-                                (bc.x * n9[2] + bc.y * n9[5]) + bc.z * n9[8]));
-        }
+        f = surface_at(s, id, o, d, t, SMOOTH);
     }
     if (live) {
         if (hit_id) hit_id[ri] = id;
@@ -317,31 +252,16 @@ __global__ __launch_bounds__(256) void k_query_shade(DevScene s, uint32_t n_rays
             const int2 self = make_int2(__float_as_int(wray[3][r]), __float_as_int(wray[4][r]));
             const float* lp = p.lights + (size_t)(l0 + k) * 3;
             const V3 sd = mk(lp[0], lp[1], lp[2]) - so;
-            if (query_any_walk<COUNT>(s, self, so, sd, n_node_s, n_tri_s)) atomicOr(&best[r], 1ull << k);
+            if (any_hit_range<COUNT, true>(s, self, so, sd, n_node_s, n_tri_s)) atomicOr(&best[r], 1ull << k);
         }
         __builtin_amdgcn_wave_barrier();
         if (is_hit) {
             const unsigned long long mask = best[rank];
-            for (uint32_t k = 0; k < m; k++) {                                                      // :366-383
-                const float* lp = p.lights + (size_t)(l0 + k) * 3;
-                V3 c = phong<INT_SHIN>(nrm, o, d, mk(lp[0], lp[1], lp[2]), color, ka, ks, sh, t);
-                if ((mask >> k) & 1ull) c = mk(c.x / p.shadow_div, c.y / p.shadow_div, c.z / p.shadow_div);       // :369
-                sum = sum + c;                                                                      // :370
-            }
+            add_light_samples<INT_SHIN>(sum, f, o, d, t, p.lights, l0, m, p.shadow_div, [&](uint32_t l) -> bool { return (mask >> (l - l0)) & 1ull; });
         }
         __builtin_amdgcn_wave_barrier();
     }
-    if (live) {
-        if (rgb_linear) { rgb_linear[ri * 3] = sum.x; rgb_linear[ri * 3 + 1] = sum.y; rgb_linear[ri * 3 + 2] = sum.z; }
-        if (rgb8) {
-            int q0 = 0, q1 = 0, q2 = 0;
-            if (is_hit) {                                                                           // :391-398,447-449
-                q0 = quant1(tone1(sum.x, p.reinhard, p.gamma)); q1 = quant1(tone1(sum.y, p.reinhard, p.gamma)); q2 = quant1(tone1(sum.z, p.reinhard, p.gamma));
-            }
-            if ((q0 | q1 | q2) == 0) { q0 = p.bg & 255; q1 = (p.bg >> 8) & 255; q2 = (p.bg >> 16) & 255; }   // :518, :476-487
-            rgb8[ri * 3] = (uint8_t)q0; rgb8[ri * 3 + 1] = (uint8_t)q1; rgb8[ri * 3 + 2] = (uint8_t)q2;
-        }
-    }
+    if (live) store_pixel(rgb_linear, rgb8, ri, sum, is_hit, p.reinhard, p.gamma, p.bg);
     if (counters) count_hits(counters, is_hit, blockIdx.x);
     if (COUNT) { wave_add(counters + 1, n_node); wave_add(counters + 2, n_tri); wave_add(counters + 3, n_node_s); wave_add(counters + 4, n_tri_s); }
 }

@@ -11,10 +11,7 @@ from simple_raytracer_amd import abi, lib      # noqa: E402
 import golden_util as gu                       # noqa: E402
 import ray_query_ref as rq                     # noqa: E402
 import shade_query_ref as sq                   # noqa: E402
-
-W, H, FOCAL = 192, 108, 40.0
-STAT_KEYS = ("primary_rays", "hit_rays", "shadow_rays", "node_tests_primary", "tri_tests_primary", "node_tests_shadow", "tri_tests_shadow", "rows")
-bits = sq.bits
+from query_device_common import W, H, FOCAL, bits, UntouchedRender, float_aligned, through_shared_handle      # noqa: E402
 
 
 def setup():
@@ -55,39 +52,19 @@ def device_case():
     dev, g, ds, rays, params, host = setup()
     n = rays.shape[0]
     d_rays = torch.from_numpy(rays).to(dev)
-    p = g.params(W, H, 2, flags=abi.SRT_FLAG_COUNT_WORK)
-    fhit = torch.zeros((H, W), dtype=torch.int32, device=dev); flin = torch.zeros((H, W, 3), dtype=torch.float32, device=dev)
-    cur = torch.cuda.current_stream().cuda_stream
-
-    def render():
-        fhit.fill_(-5); flin.zero_(); torch.cuda.synchronize()
-        ds.render_device(p, stream=cur, hit_id=fhit.data_ptr(), rgb_linear=flin.data_ptr())
-        st = ds.sync()
-        torch.cuda.synchronize()
-        return fhit.cpu().numpy().copy(), flin.cpu().numpy().copy(), {k: st[k] for k in STAT_KEYS}, ds.pipeline
-
-    base = [render(), render()]                                # both alternating counter sets
-    assert base[0][2] == base[1][2] and base[0][2]["node_tests_primary"] > 0
+    frame = UntouchedRender(dev, g, ds)
     side = torch.cuda.Stream(device=dev)
     out = Outputs(dev, n)
     for rep in range(2):
-        # a render is enqueued, the query runs on a second stream while it is pending, then srt_sync: the render's statistics
-        fhit.fill_(-5); flin.zero_(); torch.cuda.synchronize()
-        ds.render_device(p, stream=cur, hit_id=fhit.data_ptr(), rgb_linear=flin.data_ptr())
-        q = params[0]
-        q.flags = abi.SRT_FLAG_COUNT_WORK if rep == 1 else 0
-        ds.shade_rays_device(n, d_rays.data_ptr(), q, stream=side.cuda_stream, **out.ptrs())
-        q.flags = 0
-        pipe = ds.pipeline
-        st = ds.sync()
-        side.synchronize(); torch.cuda.synchronize()
-        assert {k: st[k] for k in STAT_KEYS} == base[0][2], (rep, st, base[0][2])
-        assert pipe == base[0][3] == ds.pipeline
-        assert np.array_equal(fhit.cpu().numpy(), base[0][0]) and np.array_equal(bits(flin.cpu().numpy()), bits(base[0][1])), rep
+        def queries():
+            q = params[0]
+            q.flags = abi.SRT_FLAG_COUNT_WORK if rep == 1 else 0
+            ds.shade_rays_device(n, d_rays.data_ptr(), q, stream=side.cuda_stream, **out.ptrs())
+            q.flags = 0
+        frame.pending_beside(rep, side, queries)
         out.same(host[0], f"second stream, rep {rep}")
         out.reset()
-    after = render()
-    assert after[2] == base[0][2] and np.array_equal(after[0], base[0][0]) and np.array_equal(bits(after[1]), bits(base[0][1]))
+    frame.after()
     # the light table changes between two calls on one stream: each call sees its own (the second upload is ordered behind the first query)
     other = Outputs(dev, n)
     ds.shade_rays_device(n, d_rays.data_ptr(), params[0], stream=side.cuda_stream, **out.ptrs())
@@ -103,22 +80,17 @@ def device_case():
     torch.cuda.synchronize()
     out.same(host[1], "own stream")
     out.reset()
-    # rays that are only float-aligned take the narrow loads: same results
-    odd = torch.empty(n * 6 + 1, dtype=torch.float32, device=dev)
-    odd[1:].copy_(d_rays.reshape(-1))
-    assert odd[1:].data_ptr() % 8 == 4
-    torch.cuda.synchronize()
-    ds.shade_rays_device(n, odd[1:].data_ptr(), params[0], stream=side.cuda_stream, **out.ptrs())
+    odd = float_aligned(dev, d_rays)
+    ds.shade_rays_device(n, odd.data_ptr(), params[0], stream=side.cuda_stream, **out.ptrs())
     side.synchronize()
     out.same(host[0], "float-aligned rays")
     out.reset()
-    # through a shared handle: the one copy of the records, a light table of its own
-    sh = ds.share()
-    sh.shade_rays_device(n, d_rays.data_ptr(), params[1], stream=side.cuda_stream, **out.ptrs())
-    side.synchronize()
-    out.same(host[1], "shared handle")
-    assert sh.device_bytes == ds.device_bytes
-    sh.close()
+
+    def shared(sh):      # (a light table of its own)
+        sh.shade_rays_device(n, d_rays.data_ptr(), params[1], stream=side.cuda_stream, **out.ptrs())
+        side.synchronize()
+        out.same(host[1], "shared handle")
+    through_shared_handle(ds, shared)
     print("shade query device case: ok")
 
 

@@ -7,11 +7,15 @@ an int(c*255) truncation boundary (<= 1 LSB, counted and bounded).  Next to ever
 oracle, strict() applies the bar of tests/gpu_frames.compare_exact against the oracle run with the
 device's pow: colours bit for bit up to the residual of the device pow's general branch, which
 srt_kat_pow explains."""
+import dataclasses
+
 import numpy as np
 import pytest
 
 import golden_util as gu
 import gpu_frames as gf
+import ray_query_ref as rq
+import shade_query_ref as sq
 from simple_raytracer_amd import abi
 
 pytestmark = pytest.mark.gpu
@@ -1066,6 +1070,66 @@ def test_integer_shininess_kernel_equals_general(srt, name, W, H, L):
     b = ds.render(g.params(W, H, L, flags=44 << 8))
     assert np.array_equal(bits(a["rgb_linear"]), bits(b["rgb_linear"])) and np.array_equal(a["rgb8"], b["rgb8"])
     assert np.array_equal(a["hit_id"], b["hit_id"])
+
+
+def unclamped_texel_index(oracle, flat, rays, hit, t):
+    """For every textured hit of `rays` ((n, 6): origin, direction): the byte index softShadow:357 computes BEFORE any clamp, from
+    the oracle's hit ids and t -- the hit point and the texcoord sums in float32 with the kernels' association, the barycentric
+    coordinates by the oracle's leaf function -- and the last valid index of the triangle's image."""
+    tex = np.where(hit >= 0, flat.tri_tex[np.maximum(hit, 0)], -1)
+    ids, r = hit[tex >= 0], rays[tex >= 0]
+    P = r[:, 0:3] + r[:, 3:6] * t[tex >= 0].astype(np.float32)[:, None]
+    bc = oracle.barycentric(np.concatenate([flat.tri_points[ids].reshape(-1, 12), P], axis=1))
+    tc = np.asarray(flat.tri_texcoord, np.float32)[ids]
+    tx = (bc[:, 0] * tc[:, 0] + bc[:, 1] * tc[:, 2]) + bc[:, 2] * tc[:, 4]
+    ty = (bc[:, 0] * tc[:, 1] + bc[:, 1] * tc[:, 3]) + bc[:, 2] * tc[:, 5]
+    w, h = flat.tex_w[tex[tex >= 0]].astype(np.int64), flat.tex_h[tex[tex >= 0]].astype(np.int64)
+    return (ty.astype(np.int32).astype(np.int64) * w + tx.astype(np.int32)) * 3, w * h * 3 - 3
+
+
+def test_texel_index_outside_the_image_is_clamped_on_every_path(srt, oracle):
+    """The reference reads out of bounds when a texel index leaves the image; this project clamps it into the image, in one place
+    (surface_at) that every shading path goes through.  texquad with its texture rows stretched fourfold about the middle row
+    (ty' = 4 ty - 72: chosen on the oracle -- of the 3072 hit pixels of the 64 x 48 frame 512 fall below index 0, 477 beyond the last
+    texel and 2083 inside; of the sheared camera frame's 1649 hits 521, 511 and 617) through the shipped pipeline, the general shading
+    kernel (44), k_shade (1), the one-launch kernel (28), the shipped pipeline with smooth normals and srt_shade_rays: bit for bit the
+    oracle with the device's pow."""
+    g = gu.GoldenScene("texquad")
+    flat = sq.texquad_with_normals(g)
+    tc = np.asarray(flat.tri_texcoord, np.float32) * np.tile(np.float32([1.0, 4.0]), 3) - np.tile(np.float32([0.0, 72.0]), 3)
+    flat = dataclasses.replace(flat, tri_texcoord=np.ascontiguousarray(tc, np.float32))
+    W, H, L = 64, 48, 2
+    lights = abi.light_staircase(g.light, L)
+    focal_cam = 120.0
+    identity = np.eye(4, dtype=np.float32).reshape(-1)
+
+    def classes(c, rays, what):
+        idx, last = unclamped_texel_index(oracle, flat, rays, c["hit_id"].reshape(-1), c["t"].reshape(-1))
+        n = (int((idx < 0).sum()), int((idx > last).sum()), int(((idx >= 0) & (idx <= last)).sum()))
+        print(what, "texel indices below / beyond / inside the image:", n)
+        assert min(n) >= 100, (what, n)
+
+    ds = srt.DeviceScene(flat)
+    for what, flags, pipe in (("shipped", 0, None), ("variant 44", 44 << 8, None), ("variant 1", 1 << 8, "k_shade"), ("variant 28", 28 << 8, "k_trace_shade_nq"),
+                              ("smooth normals", abi.SRT_FLAG_SMOOTH_NORMALS, None)):
+        p = abi.make_params(W, H, lights, flags=flags)
+        o = ds.render(p)
+        if pipe:
+            assert pipe in ds.pipeline.split("+"), (what, ds.pipeline)
+        c = strict(srt, oracle, o, flat, p, "clamp, " + what)
+        assert gf.int_shininess_only(flat)       # (so strict() has compared rgb_linear bit for bit)
+        if flags in (0, abi.SRT_FLAG_SMOOTH_NORMALS):
+            classes(c, rq.frame_rays(W, H, identity, p.focal), what)
+    # the query path: the rays of a sheared camera frame against the oracle's frame
+    rays = rq.frame_rays(W, H, rq.SHEAR, focal_cam)
+    for what, flags in (("shade_rays", 0), ("shade_rays, smooth normals", abi.SRT_FLAG_SMOOTH_NORMALS)):
+        c = sq.frame_shade(oracle, flat, W, H, rq.SHEAR, focal_cam, lights, flags=flags)
+        classes(c, rays, what)
+        o = ds.shade_rays(rays, sq.shade_params(lights, flags=flags))
+        assert np.array_equal(o["hit_id"], c["hit_id"].reshape(-1)) and np.array_equal(bits(o["t"]), bits(c["t"]).reshape(-1)), what
+        assert np.array_equal(bits(o["rgb_linear"]), bits(c["rgb_linear"]).reshape(-1, 3)), what
+        assert np.array_equal(o["rgb8"], c["rgb8"].reshape(-1, 3)), what
+    ds.close()
 
 
 def test_valu_issue_rate_is_the_guides(srt):
