@@ -326,7 +326,7 @@ int srt_sync(srt_scene* s, srt_stats* stats);
  *   bary    n x 3   f32    calculateBarycentricCoords (:79-117) (u, v, w) at origin + direction * t, the operations the textured shading
  *                          path runs; (0, 0, 0) on a miss
  * Occlusion.  occluded[i] = 1 if any object's tree but skip_obj[i]'s yields a candidate triangle whose Moller-Trumbore result is not
- * -inf (NaN included, as the reference), else 0; t is unbounded, as in the reference.  skip_obj: the object whose own tree is left out
+ * -inf (NaN included, as the reference), else 0; t is unbounded, as in the reference (srt_occluded_range bounds it).  skip_obj: the object whose own tree is left out
  * (the hit object's, for a shadow ray), n entries or NULL; an entry of -1 -- or any entry outside [0, n_objects), which is not
  * validated on the host -- leaves nothing out.
  * A NULL occluded / d_occluded leaves the call nothing to report: it returns SRT_OK and launches nothing.
@@ -349,6 +349,35 @@ int srt_trace_rays(srt_scene* s, uint32_t n, const float* rays, uint32_t flags,
 int srt_occluded_device(srt_scene* s, uint32_t n, const float* d_rays, const int32_t* d_skip_obj /* n or NULL */,
                         void* stream, uint8_t* d_occluded);
 int srt_occluded(srt_scene* s, uint32_t n, const float* rays, const int32_t* skip_obj, uint8_t* occluded);
+
+/* A t interval per ray.  The _range forms take t_range = n x 2 floats, (t_min, t_max) per ray, and answer for the part of each ray inside
+ * its interval: visibility between two points as a segment (d = B - A, range (0, 1)), a sensor with a reach, a ray that starts ON a
+ * surface (t_min a little above 0, the origin not moved), the second hit along a ray (t_min = the next float after the first hit's t).
+ * Unless said here everything is as for the forms above: the layout of rays and of every output, the flags, the ordering on `stream`,
+ * what the host forms stage (t_range travels through the same pinned block as the rays), wait for and report in *stats, the private
+ * counter set, hipGraph capture of the _device forms without SRT_FLAG_COUNT_WORK, the rules of srt_scene_share, the errors, n == 0, a NULL
+ * occluded.  t_range is read like rays: host memory in the host forms; in the _device forms a device pointer, one 8-byte load per ray where
+ * it is 8-byte aligned and two 4-byte loads where it is only float-aligned.
+ * DEFINITION.  The candidate set of a ray is unchanged -- the reference's: every leaf whose ancestors all pass the literal slab test, no
+ * pruning by t -- and a candidate's t is the same Moller-Trumbore result on the same operands.  A candidate is IN RANGE iff
+ * !(t < t_min) && !(t > t_max): the interval is closed, a NaN bound bounds nothing, a NaN t is in range.
+ *   Closest hit: among the candidates with t != -inf && t < +inf that are in range, the minimum t; equal t goes to the lowest id, and +0
+ *                and -0 tie as they do without an interval.  The reported t is the winner's own bits, bary is taken at
+ *                origin + direction * t.  No such candidate: -1, +inf, (0, 0, 0).
+ *   Occlusion:   1 iff a candidate outside skip_obj[i]'s tree has t != -inf (NaN included) and is in range.
+ *   Identities:  a NULL t_range, or a ray whose interval is (0, +inf), (-inf, +inf) or (NaN, NaN), gives bit for bit what the unbounded
+ *                call gives for that ray, NaN candidates included.  t_min > t_max: a miss / not occluded.
+ * Boxes are NOT rejected by t_max: the walk visits exactly the nodes the unbounded call visits, so under SRT_FLAG_COUNT_WORK the
+ * closest-hit form reports the node_tests_primary and tri_tests_primary of the unbounded call on the same rays; the interval costs
+ * 8 bytes per ray and two comparisons per tested triangle, and saves no work.
+ * srt_shade_rays takes no interval: the colour of a hit that is not the closest one has no reduction to an oracle frame yet. */
+int srt_trace_rays_range_device(srt_scene* s, uint32_t n, const float* d_rays, const float* d_t_range /* n x 2: t_min, t_max; or NULL */,
+                                uint32_t flags, void* stream, int32_t* d_hit_id, float* d_t, float* d_bary);
+int srt_trace_rays_range(srt_scene* s, uint32_t n, const float* rays, const float* t_range, uint32_t flags,
+                         int32_t* hit_id, float* t, float* bary, srt_stats* stats);
+int srt_occluded_range_device(srt_scene* s, uint32_t n, const float* d_rays, const float* d_t_range,
+                              const int32_t* d_skip_obj, void* stream, uint8_t* d_occluded);
+int srt_occluded_range(srt_scene* s, uint32_t n, const float* rays, const float* t_range, const int32_t* skip_obj, uint8_t* occluded);
 
 /* Shaded colour: what comes back along each ray -- everything the library does after the closest hit for the pixels of its own camera
  * (texture lookup, the soft-shadow light samples, Phong, smooth normals, tone map, quantiser, background rule), for rays the caller

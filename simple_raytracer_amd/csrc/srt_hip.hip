@@ -157,6 +157,7 @@ struct srt_scene {
     // ray queries (srt_trace_rays / srt_occluded, the host entry points): the rays and results of one call, capacities count rays; and the
     // counter set private to queries (laid out like a render's), which no render reads, zeroes or reports
     DevArray<float, 6> rq_rays; DevArray<int32_t> rq_hit; DevArray<float> rq_t; DevArray<float, 3> rq_bary; DevArray<int32_t> rq_skip; DevArray<uint8_t> rq_occ;
+    DevArray<float, 2> rq_range;                  // the t intervals of a call that brings them
     DevArray<unsigned long long> d_qctr;
     // srt_shade_rays: the query's own result buffers and its own light table (a render's d_lights may be in use on another stream): the
     // pinned copy, the event behind its last upload, the stream that upload went to, and whether it is known to have arrived
@@ -1537,6 +1538,7 @@ static int check_shade(const srt_scene* s, uint32_t n, const float* rays, const 
 }
 
 static inline uint32_t rays_wide(const float* d_rays) { return ((uintptr_t)d_rays & 7u) == 0 ? 1u : 0u; }      // srt_query.h load_ray
+static inline QueryRange query_range(const float* d_t_range) { return QueryRange{ d_t_range, rays_wide(d_t_range) }; }      // srt_query.h load_range
 
 // The light table of a query, as a render sends its own: through a pinned copy, again only when the bytes differ from what the device
 // holds.  The upload is ordered on `stream`; a later call with the same table on ANOTHER stream is ordered behind it by the event.
@@ -1581,27 +1583,32 @@ static int query_prologue(srt_scene* s, uint32_t n, hipStream_t stream, const sr
     return SRT_OK;
 }
 
+// d_t_range: the rays' t intervals (srt_*_range), or null: nothing bounds t, and the kernels are the ones without the interval.
 // count_hits: the host entry point wants hit_rays also without SRT_FLAG_COUNT_WORK
-static int trace_rays_device_impl(srt_scene* s, uint32_t n, const float* d_rays, uint32_t flags, hipStream_t stream, int32_t* d_hit_id, float* d_t,
-                                  float* d_bary, bool count_hits) {
+static int trace_rays_device_impl(srt_scene* s, uint32_t n, const float* d_rays, const float* d_t_range, uint32_t flags, hipStream_t stream, int32_t* d_hit_id,
+                                  float* d_t, float* d_bary, bool count_hits) {
     SRT_TRY(check_query(s, n, d_rays, flags));
     if (!n) return SRT_OK;
     const bool count = (flags & SRT_FLAG_COUNT_WORK) != 0;
     QueryLaunch q;
     SRT_TRY(query_prologue(s, n, stream, nullptr, count || count_hits, &q));
-    static const decltype(&k_query_closest<false, false>) builds[4] = {
-        &k_query_closest<false, false>, &k_query_closest<false, true>, &k_query_closest<true, false>, &k_query_closest<true, true> };
-    hipLaunchKernelGGL(builds[(count ? 2 : 0) | (d_bary ? 1 : 0)], q.grid, dim3(256), 0, q.stream, s->dev, n, d_rays, rays_wide(d_rays), d_hit_id, d_t, d_bary, q.ctr);
+    static const decltype(&k_query_closest<false, false, false>) builds[8] = {
+        &k_query_closest<false, false, false>, &k_query_closest<false, true, false>, &k_query_closest<true, false, false>, &k_query_closest<true, true, false>,
+        &k_query_closest<false, false, true>,  &k_query_closest<false, true, true>,  &k_query_closest<true, false, true>,  &k_query_closest<true, true, true> };
+    hipLaunchKernelGGL(builds[(d_t_range ? 4 : 0) | (count ? 2 : 0) | (d_bary ? 1 : 0)], q.grid, dim3(256), 0, q.stream, s->dev, n, d_rays, rays_wide(d_rays), d_hit_id, d_t,
+                       d_bary, q.ctr, query_range(d_t_range));
     HIP_TRY(hipGetLastError());
     return SRT_OK;
 }
 
-static int occluded_device_impl(srt_scene* s, uint32_t n, const float* d_rays, const int32_t* d_skip_obj, hipStream_t stream, uint8_t* d_occluded) {
+static int occluded_device_impl(srt_scene* s, uint32_t n, const float* d_rays, const float* d_t_range, const int32_t* d_skip_obj, hipStream_t stream,
+                                uint8_t* d_occluded) {
     SRT_TRY(check_query(s, n, d_rays, 0));
     if (!n || !d_occluded) return SRT_OK;
     QueryLaunch q;
     SRT_TRY(query_prologue(s, n, stream, nullptr, false, &q));
-    hipLaunchKernelGGL(k_query_any, q.grid, dim3(256), 0, q.stream, s->dev, n, d_rays, rays_wide(d_rays), d_skip_obj, d_occluded);
+    hipLaunchKernelGGL(d_t_range ? &k_query_any<true> : &k_query_any<false>, q.grid, dim3(256), 0, q.stream, s->dev, n, d_rays, rays_wide(d_rays), d_skip_obj, d_occluded,
+                       query_range(d_t_range));
     HIP_TRY(hipGetLastError());
     return SRT_OK;
 }
@@ -1631,11 +1638,12 @@ static int shade_rays_device_impl(srt_scene* s, uint32_t n, const float* d_rays,
 
 // The host entry points: the caller's rays go through the pinned staging block (stage_acquire, as every update does) into the handle's
 // own ray buffer on the scene's stream, the device entry point runs behind them, the call waits and copies the results out.
-static int stage_rays(srt_scene* s, uint32_t n, const float* rays, const int32_t* skip_obj, hipStream_t st) {
+static int stage_rays(srt_scene* s, uint32_t n, const float* rays, const float* t_range, const int32_t* skip_obj, hipStream_t st) {
     auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t o_rays = 0, o_skip = pad((size_t)n * 24), total = o_skip + (skip_obj ? pad((size_t)n * 4) : 0);
+    const size_t o_rays = 0, o_skip = pad((size_t)n * 24), o_range = o_skip + (skip_obj ? pad((size_t)n * 4) : 0), total = o_range + (t_range ? pad((size_t)n * 8) : 0);
     SRT_TRY(grow(s, n, s->rq_rays));
     if (skip_obj) SRT_TRY(grow(s, n, s->rq_skip));
+    if (t_range) SRT_TRY(grow(s, n, s->rq_range));
     char* h = nullptr;
     SRT_TRY(stage_acquire(s, total, &h));
     std::memcpy(h + o_rays, rays, (size_t)n * 24);
@@ -1643,6 +1651,10 @@ static int stage_rays(srt_scene* s, uint32_t n, const float* rays, const int32_t
     if (skip_obj) {
         std::memcpy(h + o_skip, skip_obj, (size_t)n * 4);
         HIP_TRY(hipMemcpyAsync(s->rq_skip, h + o_skip, (size_t)n * 4, hipMemcpyHostToDevice, st));
+    }
+    if (t_range) {
+        std::memcpy(h + o_range, t_range, (size_t)n * 8);
+        HIP_TRY(hipMemcpyAsync(s->rq_range, h + o_range, (size_t)n * 8, hipMemcpyHostToDevice, st));
     }
     HIP_TRY(hipEventRecord(s->staged, st));
     return SRT_OK;
@@ -1659,17 +1671,17 @@ struct QueryOut {
 template <typename T, size_t K>
 static QueryOut<T, K> query_out(T* host, DevArray<T, K>& dev) { return QueryOut<T, K>{ host, dev }; }
 
-// The round trip of a host query on the scene's own stream: grow the wanted result buffers, stage the rays, launch(stream) -- the device
-// entry point --, wait, copy each wanted array out.
+// The round trip of a host query on the scene's own stream: grow the wanted result buffers, stage the rays (and what comes with them: t
+// intervals, skipped objects), launch(stream) -- the device entry point --, wait, copy each wanted array out.
 template <typename Launch, typename... O>
-static int query_round_trip(srt_scene* s, uint32_t n, const float* rays, const int32_t* skip_obj, Launch launch, const O&... outs) {
+static int query_round_trip(srt_scene* s, uint32_t n, const float* rays, const float* t_range, const int32_t* skip_obj, Launch launch, const O&... outs) {
     HIP_TRY(hipSetDevice(s->device));
     hipStream_t st;
     SRT_TRY(own_stream(s, &st));
     int rc = SRT_OK;
     ((rc = (rc == SRT_OK && outs.host) ? grow(s, n, outs.dev) : rc), ...);
     SRT_TRY(rc);
-    SRT_TRY(stage_rays(s, n, rays, skip_obj, st));
+    SRT_TRY(stage_rays(s, n, rays, t_range, skip_obj, st));
     SRT_TRY(launch(st));
     HIP_TRY(hipStreamSynchronize(st));
     if (s->qlights_stream == st) s->qlights_settled = true;      // a light table sent on this stream has arrived
@@ -1693,22 +1705,23 @@ static int query_stats(srt_scene* s, uint32_t n, uint32_t n_lights, srt_stats* s
     return SRT_OK;
 }
 
-static int trace_rays_impl(srt_scene* s, uint32_t n, const float* rays, uint32_t flags, int32_t* hit_id, float* t, float* bary, srt_stats* stats) {
+static int trace_rays_impl(srt_scene* s, uint32_t n, const float* rays, const float* t_range, uint32_t flags, int32_t* hit_id, float* t, float* bary,
+                           srt_stats* stats) {
     SRT_TRY(check_query(s, n, rays, flags));
     if (stats) std::memset(stats, 0, sizeof(*stats));
     if (!n) return SRT_OK;
     const auto o_hit = query_out(hit_id, s->rq_hit); const auto o_t = query_out(t, s->rq_t); const auto o_bary = query_out(bary, s->rq_bary);
-    SRT_TRY(query_round_trip(s, n, rays, nullptr, [&](hipStream_t st) {
-        return trace_rays_device_impl(s, n, s->rq_rays, flags, st, o_hit.wanted(), o_t.wanted(), o_bary.wanted(), true);
+    SRT_TRY(query_round_trip(s, n, rays, t_range, nullptr, [&](hipStream_t st) {
+        return trace_rays_device_impl(s, n, s->rq_rays, t_range ? s->rq_range.p : nullptr, flags, st, o_hit.wanted(), o_t.wanted(), o_bary.wanted(), true);
     }, o_hit, o_t, o_bary));
     return stats ? query_stats(s, n, 0, stats) : SRT_OK;
 }
 
-static int occluded_impl(srt_scene* s, uint32_t n, const float* rays, const int32_t* skip_obj, uint8_t* occluded) {
+static int occluded_impl(srt_scene* s, uint32_t n, const float* rays, const float* t_range, const int32_t* skip_obj, uint8_t* occluded) {
     SRT_TRY(check_query(s, n, rays, 0));
     if (!n || !occluded) return SRT_OK;
-    return query_round_trip(s, n, rays, skip_obj, [&](hipStream_t st) {
-        return occluded_device_impl(s, n, s->rq_rays, skip_obj ? s->rq_skip.p : nullptr, st, s->rq_occ);
+    return query_round_trip(s, n, rays, t_range, skip_obj, [&](hipStream_t st) {
+        return occluded_device_impl(s, n, s->rq_rays, t_range ? s->rq_range.p : nullptr, skip_obj ? s->rq_skip.p : nullptr, st, s->rq_occ);
     }, query_out(occluded, s->rq_occ));
 }
 
@@ -1719,23 +1732,36 @@ static int shade_rays_impl(srt_scene* s, uint32_t n, const float* rays, const sr
     if (!n) return SRT_OK;
     const auto o_hit = query_out(hit_id, s->rq_hit); const auto o_t = query_out(t, s->rq_t);
     const auto o_lin = query_out(rgb_linear, s->rq_lin); const auto o_rgb8 = query_out(rgb8, s->rq_rgb8);
-    SRT_TRY(query_round_trip(s, n, rays, nullptr, [&](hipStream_t st) {
+    SRT_TRY(query_round_trip(s, n, rays, nullptr, nullptr, [&](hipStream_t st) {
         return shade_rays_device_impl(s, n, s->rq_rays, p, st, o_hit.wanted(), o_t.wanted(), o_lin.wanted(), o_rgb8.wanted(), true);
     }, o_hit, o_t, o_lin, o_rgb8));
     return stats ? query_stats(s, n, p->n_lights, stats) : SRT_OK;
 }
 
 int srt_trace_rays_device(srt_scene* s, uint32_t n, const float* d_rays, uint32_t flags, void* stream, int32_t* d_hit_id, float* d_t, float* d_bary) {
-    return guarded([&] { return trace_rays_device_impl(s, n, d_rays, flags, (hipStream_t)stream, d_hit_id, d_t, d_bary, false); });
+    return guarded([&] { return trace_rays_device_impl(s, n, d_rays, nullptr, flags, (hipStream_t)stream, d_hit_id, d_t, d_bary, false); });
+}
+int srt_trace_rays_range_device(srt_scene* s, uint32_t n, const float* d_rays, const float* d_t_range, uint32_t flags, void* stream, int32_t* d_hit_id, float* d_t,
+                                float* d_bary) {
+    return guarded([&] { return trace_rays_device_impl(s, n, d_rays, d_t_range, flags, (hipStream_t)stream, d_hit_id, d_t, d_bary, false); });
 }
 int srt_trace_rays(srt_scene* s, uint32_t n, const float* rays, uint32_t flags, int32_t* hit_id, float* t, float* bary, srt_stats* stats) {
-    return guarded([&] { return trace_rays_impl(s, n, rays, flags, hit_id, t, bary, stats); });
+    return guarded([&] { return trace_rays_impl(s, n, rays, nullptr, flags, hit_id, t, bary, stats); });
+}
+int srt_trace_rays_range(srt_scene* s, uint32_t n, const float* rays, const float* t_range, uint32_t flags, int32_t* hit_id, float* t, float* bary, srt_stats* stats) {
+    return guarded([&] { return trace_rays_impl(s, n, rays, t_range, flags, hit_id, t, bary, stats); });
 }
 int srt_occluded_device(srt_scene* s, uint32_t n, const float* d_rays, const int32_t* d_skip_obj, void* stream, uint8_t* d_occluded) {
-    return guarded([&] { return occluded_device_impl(s, n, d_rays, d_skip_obj, (hipStream_t)stream, d_occluded); });
+    return guarded([&] { return occluded_device_impl(s, n, d_rays, nullptr, d_skip_obj, (hipStream_t)stream, d_occluded); });
+}
+int srt_occluded_range_device(srt_scene* s, uint32_t n, const float* d_rays, const float* d_t_range, const int32_t* d_skip_obj, void* stream, uint8_t* d_occluded) {
+    return guarded([&] { return occluded_device_impl(s, n, d_rays, d_t_range, d_skip_obj, (hipStream_t)stream, d_occluded); });
 }
 int srt_occluded(srt_scene* s, uint32_t n, const float* rays, const int32_t* skip_obj, uint8_t* occluded) {
-    return guarded([&] { return occluded_impl(s, n, rays, skip_obj, occluded); });
+    return guarded([&] { return occluded_impl(s, n, rays, nullptr, skip_obj, occluded); });
+}
+int srt_occluded_range(srt_scene* s, uint32_t n, const float* rays, const float* t_range, const int32_t* skip_obj, uint8_t* occluded) {
+    return guarded([&] { return occluded_impl(s, n, rays, t_range, skip_obj, occluded); });
 }
 int srt_shade_rays_device(srt_scene* s, uint32_t n, const float* d_rays, const srt_params* p, void* stream, int32_t* d_hit_id, float* d_t,
                           float* d_rgb_linear, uint8_t* d_rgb8) {

@@ -979,9 +979,11 @@ __global__ __launch_bounds__(256, MINW) void k_closest_hit_nq(DevScene s, DevPar
 // FILTER: the slab test through slab_pass (reciprocal filter, exact fallback) instead of the exact divides alone -- the same answers.
 // COUNT: the oracle's algorithmic counts -- objects in order, one slab test per node met, one triangle test up to and including the
 // first hit.
-template <bool COUNT, bool FILTER>
+// RANGE (the occlusion query with a t interval, srt_query.h): a result counts only if it is in range, !(t < t_min) && !(t > t_max) --
+// closed, a NaN bound bounds nothing, a NaN t is in range; the walk visits the same nodes, and the lane leaves at its first hit in range.
+template <bool COUNT, bool FILTER, bool RANGE = false>
 __device__ __forceinline__ bool any_hit_range(const DevScene& s, int2 self, V3 so, V3 sd,
-                                              unsigned long long& n_node, unsigned long long& n_tri) {
+                                              unsigned long long& n_node, unsigned long long& n_tri, const float t_min = 0.0f, const float t_max = 0.0f) {
     const float4* nodes4 = reinterpret_cast<const float4*>(s.nodes);
     const float4* tris4 = reinterpret_cast<const float4*>(s.tris);
     RayRcp rc;
@@ -1002,7 +1004,7 @@ __device__ __forceinline__ bool any_hit_range(const DevScene& s, int2 self, V3 s
                     load_tri_edges(tris4, (size_t)(first + k), p1, e1, e2);
                     if (COUNT) n_tri++;
                     const float t = ray_triangle(so, sd, p1, e1, e2);
-                    hit = t != SRT_NEG_INF;                  // any t >= 0, NaN included (:335)
+                    hit = t != SRT_NEG_INF && (!RANGE || (!(t < t_min) && !(t > t_max)));      // any t >= 0, NaN included (:335)
                 }
             }
             i = i + 1;

@@ -7,7 +7,7 @@
 // test through slab_pass (reciprocal filter, exact fallback) -- and, for the closest hit, the per-wave triangle queue of
 // k_closest_hit_q.  The candidate set of a ray is the reference's (every leaf whose ancestors all pass the literal slab test, no t
 // pruning) and the merge is the order-independent (t, id) minimum, so a ray's result depends on the ray alone, never on its place in
-// the batch.
+// the batch.  RANGE builds of the two kernels bound t per ray (load_range below); they visit the same nodes and test the same triangles.
 #pragma once
 #include "srt_kernels.h"
 
@@ -24,6 +24,20 @@ __device__ __forceinline__ void load_ray(const float* __restrict__ rays, size_t 
     }
 }
 
+// The t interval of ray `i` (include/srt.h, "A t interval per ray"): t_range = n x 2 floats (t_min, t_max), read like the rays -- one
+// dwordx2 load where the array is 8-byte aligned, two dword loads where it is only float-aligned.  A candidate is IN RANGE iff
+// !(t < t_min) && !(t > t_max): the interval is closed, a NaN bound bounds nothing, a NaN t is in range.  The interval never prunes the
+// walk: the candidate set and the nodes visited are those of the unbounded query.
+struct QueryRange { const float* t; uint32_t wide; };
+__device__ __forceinline__ void load_range(const QueryRange tr, size_t i, float& t_min, float& t_max) {
+    if (tr.wide) {
+        const float2 a = reinterpret_cast<const float2*>(tr.t)[i];
+        t_min = a.x; t_max = a.y;
+    } else {
+        t_min = tr.t[2 * i]; t_max = tr.t[2 * i + 1];
+    }
+}
+
 // =================================================================================================
 // Closest hit of caller-supplied rays: the oracle's closest_in_tree over the objects in order, with the ray's own origin.
 // One ray per lane.  The lanes of a wave walk on their own (the rays may be unrelated); a lane whose ray passes a leaf's box pushes
@@ -35,12 +49,16 @@ __device__ __forceinline__ void load_ray(const float* __restrict__ rays, size_t 
 // The walk and the merge for the 64 rays of one wave, shared by k_query_closest and k_query_shade: on return best[lane] holds the
 // lane's minimum of (t bits << 32 | triangle id), ~0 on a miss.  q (QCAP words), best (64 words) and wray (the wave's rays) are the
 // wave's own LDS.
-template <bool COUNT>
+// RANGE: the lane's t interval goes into two more rows of wray (8 rows instead of 6) -- a queued pair is tested by whichever lane draws
+// it, so the interval has to live where the ray lives -- and a result joins the merge only if it is in range of its OWNER's interval.
+template <bool COUNT, bool RANGE = false>
 __device__ __forceinline__ void query_closest_walk(const DevScene& s, const bool live, const V3 o, const V3 d, const uint32_t lane, uint32_t* q,
-                                                   unsigned long long* best, float (*wray)[64], unsigned long long& n_node, unsigned long long& n_tri) {
+                                                   unsigned long long* best, float (*wray)[64], unsigned long long& n_node, unsigned long long& n_tri,
+                                                   const float t_min = 0.0f, const float t_max = 0.0f) {
     best[lane] = ~0ull;
     wray[0][lane] = o.x; wray[1][lane] = o.y; wray[2][lane] = o.z;
     wray[3][lane] = d.x; wray[4][lane] = d.y; wray[5][lane] = d.z;
+    if (RANGE) { wray[6][lane] = t_min; wray[7][lane] = t_max; }
     const RayRcp rc = ray_rcp(d);
     const float4* nodes4 = reinterpret_cast<const float4*>(s.nodes);
     const float4* tris4 = reinterpret_cast<const float4*>(s.tris);
@@ -100,12 +118,14 @@ __device__ __forceinline__ void query_closest_walk(const DevScene& s, const bool
                 const uint32_t e = q[qn + lane];
                 const uint32_t src = e & 63u, tri = e >> 6;
                 const V3 os = mk(wray[0][src], wray[1][src], wray[2][src]), ds = mk(wray[3][src], wray[4][src], wray[5][src]);
+                float lo = 0.0f, hi = 0.0f;
+                if (RANGE) { lo = wray[6][src]; hi = wray[7][src]; }
                 V3 p1, e1, e2;
                 load_tri_edges(tris4, tri, p1, e1, e2);
                 if (COUNT) n_tri++;
                 const float t = ray_triangle(os, ds, p1, e1, e2);
                 // candidate iff t != -inf && t < +inf (the initial distanceComparison, :408); NaN fails '<'
-                if (t != SRT_NEG_INF && t < __builtin_inff()) {
+                if (t != SRT_NEG_INF && t < __builtin_inff() && (!RANGE || (!(t < lo) && !(t > hi)))) {
                     const uint32_t tb = (t == 0.0f) ? 0u : __float_as_uint(t);     // -0.0 ties with +0.0
                     atomicMin(&best[src], ((unsigned long long)tb << 32) | tri);
                 }
@@ -116,21 +136,24 @@ __device__ __forceinline__ void query_closest_walk(const DevScene& s, const bool
     __builtin_amdgcn_wave_barrier();
 }
 
-template <bool COUNT, bool BARY>
+// RANGE: the closest hit among the candidates in range of the ray's own interval tr (the winner is in range, so its recomputed t is too).
+template <bool COUNT, bool BARY, bool RANGE>
 __global__ __launch_bounds__(256) void k_query_closest(DevScene s, uint32_t n_rays, const float* __restrict__ rays, uint32_t wide,
                                                        int32_t* __restrict__ hit_id, float* __restrict__ t_out, float* __restrict__ bary,
-                                                       unsigned long long* __restrict__ counters) {
+                                                       unsigned long long* __restrict__ counters, QueryRange tr) {
     __shared__ uint32_t q_all[4][QCAP];
     __shared__ unsigned long long best_all[256];
-    __shared__ float ray_all[4][6][64];
+    __shared__ float ray_all[4][RANGE ? 8 : 6][64];
     const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     unsigned long long* best = best_all + wave * 64;
     const size_t ri = (size_t)blockIdx.x * 256 + threadIdx.x;
     const bool live = ri < (size_t)n_rays;
     unsigned long long n_node = 0, n_tri = 0;
     V3 o = mk(0.0f, 0.0f, 0.0f), d = mk(0.0f, 0.0f, 1.0f);
+    float t_min = 0.0f, t_max = 0.0f;
     if (live) load_ray(rays, ri, wide != 0, o, d);
-    query_closest_walk<COUNT>(s, live, o, d, lane, q_all[wave], best, ray_all[wave], n_node, n_tri);
+    if (RANGE && live) load_range(tr, ri, t_min, t_max);
+    query_closest_walk<COUNT, RANGE>(s, live, o, d, lane, q_all[wave], best, ray_all[wave], n_node, n_tri, t_min, t_max);
     const float4* tris4 = reinterpret_cast<const float4*>(s.tris);
     bool is_hit = false;
     if (live) {
@@ -159,9 +182,11 @@ __global__ __launch_bounds__(256) void k_query_closest(DevScene s, uint32_t n_ra
 // Occlusion of caller-supplied rays: shadowIntersection:321-342 over every object but skip_obj[i] -- the oracle's anyhit_in_tree.
 // One ray per lane, each on its own walk (any_hit_range, filtered slab test; the skipped object's node range is stepped over).
 // An entry of skip_obj outside [0, n_objects) skips nothing.
+// RANGE: only a result in range of the ray's own interval tr blocks.
 // =================================================================================================
+template <bool RANGE>
 __global__ __launch_bounds__(256) void k_query_any(DevScene s, uint32_t n_rays, const float* __restrict__ rays, uint32_t wide,
-                                                   const int32_t* __restrict__ skip_obj, uint8_t* __restrict__ occluded) {
+                                                   const int32_t* __restrict__ skip_obj, uint8_t* __restrict__ occluded, QueryRange tr) {
     const size_t ri = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (ri >= (size_t)n_rays) return;
     V3 o, d;
@@ -171,8 +196,10 @@ __global__ __launch_bounds__(256) void k_query_any(DevScene s, uint32_t n_rays, 
         const int32_t k = skip_obj[ri];
         if (k >= 0 && (uint32_t)k < s.n_objects) self = s.obj_range[k];
     }
+    float t_min = 0.0f, t_max = 0.0f;
+    if (RANGE) load_range(tr, ri, t_min, t_max);
     unsigned long long n_node = 0, n_tri = 0;
-    occluded[ri] = any_hit_range<false, true>(s, self, o, d, n_node, n_tri) ? 1 : 0;
+    occluded[ri] = any_hit_range<false, true, RANGE>(s, self, o, d, n_node, n_tri, t_min, t_max) ? 1 : 0;
 }
 
 // =================================================================================================

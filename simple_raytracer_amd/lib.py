@@ -21,7 +21,8 @@ ABI_SYMBOLS = ("srt_params_default", "srt_light_staircase", "srt_rows_owned", "s
                "srt_last_hip_error", "srt_abi_version", "srt_kat_ray_aabb", "srt_kat_ray_triangle", "srt_kat_phong", "srt_kat_tonemap", "srt_kat_interp_normal", "srt_kat_pow",
                "srt_kat_ray_triangle_origin", "srt_kat_barycentric", "srt_debug_fail_host_allocs", "srt_debug_valu_rate", "srt_debug_scene_records", "srt_scene_set_source", "srt_scene_update_frame",
                "srt_scene_pipeline", "srt_scene_overlap_estimate", "srt_scene_set_pose_source", "srt_scene_pose",
-               "srt_trace_rays_device", "srt_trace_rays", "srt_occluded_device", "srt_occluded", "srt_shade_rays_device", "srt_shade_rays")
+               "srt_trace_rays_device", "srt_trace_rays", "srt_occluded_device", "srt_occluded", "srt_shade_rays_device", "srt_shade_rays",
+               "srt_trace_rays_range_device", "srt_trace_rays_range", "srt_occluded_range_device", "srt_occluded_range")
 
 _f32p, _i32p, _u8p = C.POINTER(C.c_float), C.POINTER(C.c_int32), C.POINTER(C.c_uint8)
 _lib = None
@@ -91,6 +92,14 @@ def load():
         L.srt_occluded_device.restype = C.c_int
         L.srt_occluded.argtypes = [C.c_void_p, C.c_uint32, _f32p, _i32p, _u8p]
         L.srt_occluded.restype = C.c_int
+        L.srt_trace_rays_range_device.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.srt_trace_rays_range_device.restype = C.c_int
+        L.srt_trace_rays_range.argtypes = [C.c_void_p, C.c_uint32, _f32p, _f32p, C.c_uint32, _i32p, _f32p, _f32p, C.POINTER(abi.Stats)]
+        L.srt_trace_rays_range.restype = C.c_int
+        L.srt_occluded_range_device.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.srt_occluded_range_device.restype = C.c_int
+        L.srt_occluded_range.argtypes = [C.c_void_p, C.c_uint32, _f32p, _f32p, _i32p, _u8p]
+        L.srt_occluded_range.restype = C.c_int
         L.srt_shade_rays_device.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(abi.Params), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.srt_shade_rays_device.restype = C.c_int
         L.srt_shade_rays.argtypes = [C.c_void_p, C.c_uint32, _f32p, C.POINTER(abi.Params), _i32p, _f32p, _f32p, _u8p, C.POINTER(abi.Stats)]
@@ -250,41 +259,63 @@ class DeviceScene:
         _check(self.L.srt_render_device(self.h, C.byref(params), C.c_void_p(stream), C.c_void_p(hit_id), C.c_void_p(t),
                                         C.c_void_p(rgb_linear), C.c_void_p(rgb8)), "srt_render_device")
 
-    def trace_rays(self, rays, want=("hit_id", "t", "bary"), count=False):
+    def trace_rays(self, rays, want=("hit_id", "t", "bary"), count=False, t_range=None):
         """srt_trace_rays: the closest hit of every ray of `rays` (n x 6: origin xyz, direction xyz; host array).  Returns a dict of
-        the arrays named in `want` (hit_id n, t n, bary n x 3) + 'stats'; count=True fills the node / triangle test counts."""
+        the arrays named in `want` (hit_id n, t n, bary n x 3) + 'stats'; count=True fills the node / triangle test counts.
+        t_range (n x 2: t_min, t_max per ray): srt_trace_rays_range, the closest hit inside each ray's closed interval."""
         r = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
         n = r.shape[0]
+        tr = _t_range(t_range, n)
         out = {}
         if "hit_id" in want: out["hit_id"] = np.empty(n, np.int32)
         if "t" in want: out["t"] = np.empty(n, np.float32)
         if "bary" in want: out["bary"] = np.empty((n, 3), np.float32)
         st = abi.Stats()
         g = lambda k, ty: out[k].ctypes.data_as(ty) if k in out else ty()
-        _check(self.L.srt_trace_rays(self.h, n, r.ctypes.data_as(_f32p), abi.SRT_FLAG_COUNT_WORK if count else 0, g("hit_id", _i32p), g("t", _f32p),
-                                     g("bary", _f32p), C.byref(st)), "srt_trace_rays")
+        flags = abi.SRT_FLAG_COUNT_WORK if count else 0
+        if tr is None:
+            _check(self.L.srt_trace_rays(self.h, n, r.ctypes.data_as(_f32p), flags, g("hit_id", _i32p), g("t", _f32p), g("bary", _f32p), C.byref(st)), "srt_trace_rays")
+        else:
+            _check(self.L.srt_trace_rays_range(self.h, n, r.ctypes.data_as(_f32p), tr.ctypes.data_as(_f32p), flags, g("hit_id", _i32p), g("t", _f32p), g("bary", _f32p),
+                                               C.byref(st)), "srt_trace_rays_range")
         out["stats"] = st.as_dict()
         return out
 
-    def occluded(self, rays, skip_obj=None):
-        """srt_occluded: one uint8 per ray of `rays` (n x 6, host array), 1 = something other than object skip_obj[i] is hit at any t."""
+    def occluded(self, rays, skip_obj=None, t_range=None):
+        """srt_occluded: one uint8 per ray of `rays` (n x 6, host array), 1 = something other than object skip_obj[i] is hit at any t.
+        t_range (n x 2: t_min, t_max per ray): srt_occluded_range, ... is hit at a t inside the ray's closed interval."""
         r = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
         n = r.shape[0]
+        tr = _t_range(t_range, n)
         sk = None if skip_obj is None else np.ascontiguousarray(skip_obj, np.int32).reshape(-1)
         assert sk is None or sk.shape[0] == n, "skip_obj: one entry per ray"
         occ = np.empty(n, np.uint8)
-        _check(self.L.srt_occluded(self.h, n, r.ctypes.data_as(_f32p), sk.ctypes.data_as(_i32p) if sk is not None else None, occ.ctypes.data_as(_u8p)),
-               "srt_occluded")
+        skp = sk.ctypes.data_as(_i32p) if sk is not None else None
+        if tr is None:
+            _check(self.L.srt_occluded(self.h, n, r.ctypes.data_as(_f32p), skp, occ.ctypes.data_as(_u8p)), "srt_occluded")
+        else:
+            _check(self.L.srt_occluded_range(self.h, n, r.ctypes.data_as(_f32p), tr.ctypes.data_as(_f32p), skp, occ.ctypes.data_as(_u8p)), "srt_occluded_range")
         return occ
 
-    def trace_rays_device(self, n, rays, stream=0, hit_id=0, t=0, bary=0, count=False):
-        """srt_trace_rays_device: raw device pointers (ints, e.g. torch.Tensor.data_ptr()) in, asynchronous on `stream`."""
-        _check(self.L.srt_trace_rays_device(self.h, n, C.c_void_p(rays), abi.SRT_FLAG_COUNT_WORK if count else 0, C.c_void_p(stream), C.c_void_p(hit_id),
-                                            C.c_void_p(t), C.c_void_p(bary)), "srt_trace_rays_device")
+    def trace_rays_device(self, n, rays, stream=0, hit_id=0, t=0, bary=0, count=False, t_range=None):
+        """srt_trace_rays_device: raw device pointers (ints, e.g. torch.Tensor.data_ptr()) in, asynchronous on `stream`.
+        t_range (a device pointer to n x 2 floats): srt_trace_rays_range_device."""
+        flags = abi.SRT_FLAG_COUNT_WORK if count else 0
+        if t_range is None:
+            _check(self.L.srt_trace_rays_device(self.h, n, C.c_void_p(rays), flags, C.c_void_p(stream), C.c_void_p(hit_id), C.c_void_p(t), C.c_void_p(bary)),
+                   "srt_trace_rays_device")
+        else:
+            _check(self.L.srt_trace_rays_range_device(self.h, n, C.c_void_p(rays), C.c_void_p(t_range), flags, C.c_void_p(stream), C.c_void_p(hit_id), C.c_void_p(t),
+                                                      C.c_void_p(bary)), "srt_trace_rays_range_device")
 
-    def occluded_device(self, n, rays, occluded, skip_obj=0, stream=0):
-        """srt_occluded_device: raw device pointers in, asynchronous on `stream`."""
-        _check(self.L.srt_occluded_device(self.h, n, C.c_void_p(rays), C.c_void_p(skip_obj), C.c_void_p(stream), C.c_void_p(occluded)), "srt_occluded_device")
+    def occluded_device(self, n, rays, occluded, skip_obj=0, stream=0, t_range=None):
+        """srt_occluded_device: raw device pointers in, asynchronous on `stream`.  t_range (a device pointer to n x 2 floats):
+        srt_occluded_range_device."""
+        if t_range is None:
+            _check(self.L.srt_occluded_device(self.h, n, C.c_void_p(rays), C.c_void_p(skip_obj), C.c_void_p(stream), C.c_void_p(occluded)), "srt_occluded_device")
+        else:
+            _check(self.L.srt_occluded_range_device(self.h, n, C.c_void_p(rays), C.c_void_p(t_range), C.c_void_p(skip_obj), C.c_void_p(stream), C.c_void_p(occluded)),
+                   "srt_occluded_range_device")
 
     def shade_rays(self, rays, params: abi.Params, want=("hit_id", "t", "rgb_linear", "rgb8"), count=False):
         """srt_shade_rays: the colour that comes back along every ray of `rays` (n x 6, host array) under the lights, literals and flags
@@ -348,6 +379,15 @@ class FrameBatch:
 
 def _f(a):
     return np.ascontiguousarray(a, np.float32)
+
+
+def _t_range(t_range, n):
+    """The t intervals of n rays as a host array (n x 2 float32), or None."""
+    if t_range is None:
+        return None
+    tr = np.ascontiguousarray(t_range, np.float32).reshape(-1, 2)
+    assert tr.shape[0] == n, "t_range: one (t_min, t_max) per ray"
+    return tr
 
 
 def kat_ray_aabb(ray_od, box, device=0):

@@ -8,7 +8,11 @@ the host entry point end to end for 1 ray and for all of them.
 srt_shade_rays_device, (b) the camera-mode srt_render_device of the same frame (identity matrix: the same rays, the same result), (c) the
 composition of the older queries -- srt_trace_rays_device, shadow rays built with torch, srt_occluded_device on hits x samples rays (it
 stops short of shading: no Phong, no tone map).
-Usage: python tools/ray_query_probe.py [--reps N] [--trace] [--shade]     (--trace: few repetitions, for a run under rocprofv3 --kernel-trace --stats)"""
+--range: instead, what the per-ray t interval costs (srt_trace_rays_range_device, srt_occluded_range_device) on the same frame's rays,
+row-major and shuffled: the unbounded closest-hit call beside the range call with (0, +inf) -- the same answers -- and with t_max at the
+frame's median hit t; both forms of occlusion on the frame's shadow rays.  Every figure is the median of --rounds rounds of --reps
+calls, the forms alternating within a round, with the rounds' minimum and maximum: the spread the ratios are to be read against.
+Usage: python tools/ray_query_probe.py [--reps N] [--trace] [--shade | --range [--rounds R]]     (--trace: few repetitions, for a run under rocprofv3 --kernel-trace --stats)"""
 import argparse, os, sys, time
 import numpy as np
 import torch                                   # first: torch initialises HIP before the library does
@@ -94,15 +98,85 @@ def shade_section(reps):
             assert ok
 
 
+def range_section(reps, rounds):
+    dev = torch.device("cuda", 0); torch.zeros(1, device=dev)
+    g = gu.GoldenScene("ground_bunny")
+    ds = lib.DeviceScene(g.flat)
+    side = torch.cuda.Stream(device=dev)
+    cur = side.cuda_stream
+    rays = frame_rays()
+    n = rays.shape[0]
+    frame = ds.render(g.params(W, H, 1), want=("hit_id", "t"))
+    hit_ref, t_ref = frame["hit_id"].reshape(-1), frame["t"].reshape(-1)
+    sel = hit_ref >= 0
+    t_med = np.float32(np.median(t_ref[sel]))
+    hit = torch.empty(n, dtype=torch.int32, device=dev); t = torch.empty(n, dtype=torch.float32, device=dev)
+
+    def rounds_of(forms):
+        """forms: name -> call.  Per form the ms a call of every round (the forms alternate within a round)."""
+        ms = {k: [] for k in forms}
+        for _ in range(rounds):
+            for k, fn in forms.items():
+                ms[k].append(timed(fn, reps, side))
+        return ms
+
+    def report(title, ms, yard):
+        med = {k: float(np.median(v)) for k, v in ms.items()}
+        for k, v in ms.items():
+            print(f"{title:34s} {k:34s} {med[k]:8.3f} {min(v):8.3f} {max(v):8.3f} {med[k] / med[yard]:7.3f}")
+
+    print(f"t interval, K3 ground_bunny {W}x{H}: {n} rays, {int(sel.sum())} hits, median hit t {t_med:.6g}; {rounds} rounds of {reps} calls, forms alternating; ms a call")
+    print(f"{'rays':34s} {'form':34s} {'median':>8s} {'min':>8s} {'max':>8s} {'/ first':>7s}")
+    for name, order in (("closest hit, row-major", np.arange(n)), ("closest hit, shuffled", np.random.default_rng(1).permutation(n))):
+        d_rays = torch.from_numpy(np.ascontiguousarray(rays[order])).to(dev)
+        d_open = torch.from_numpy(np.tile(np.float32([0.0, np.inf]), (n, 1))).to(dev)
+        d_far = torch.from_numpy(np.tile(np.array([0.0, t_med], np.float32), (n, 1))).to(dev)
+        torch.cuda.synchronize()
+        call = lambda tr: (lambda: ds.trace_rays_device(n, d_rays.data_ptr(), stream=cur, hit_id=hit.data_ptr(), t=t.data_ptr(), t_range=tr))
+        ms = rounds_of({"unbounded": call(None), "range (0, +inf)": call(d_open.data_ptr()), "range (0, median hit t)": call(d_far.data_ptr())})
+        report(name, ms, "unbounded")
+        # what the forms answer: (0, +inf) the frame, (0, median) the frame's hits up to the median and misses beyond
+        call(d_open.data_ptr())(); side.synchronize()
+        assert np.array_equal(hit.cpu().numpy(), hit_ref[order]) and np.array_equal(t.cpu().numpy().view(np.uint32), t_ref[order].view(np.uint32))
+        call(d_far.data_ptr())(); side.synchronize()
+        near = sel[order] & (t_ref[order] <= t_med)
+        assert np.array_equal(hit.cpu().numpy(), np.where(near, hit_ref[order], -1))
+    # occlusion: the frame's shadow rays as segments (so = d * t, sd = L - so, range (0, 1)), the hit object skipped
+    L = np.asarray(g.light, np.float32).reshape(1, 3)
+    so = rays[sel, 3:6] * t_ref[sel, None]
+    sray = np.ascontiguousarray(np.concatenate([so, L - so], 1), np.float32)
+    skip = g.flat.tri_obj[hit_ref[sel]].astype(np.int32)
+    m = sray.shape[0]
+    occ = torch.empty(m, dtype=torch.uint8, device=dev)
+    for name, order in (("occlusion, frame order", np.arange(m)), ("occlusion, shuffled", np.random.default_rng(2).permutation(m))):
+        d_s = torch.from_numpy(np.ascontiguousarray(sray[order])).to(dev); d_k = torch.from_numpy(np.ascontiguousarray(skip[order])).to(dev)
+        d_open = torch.from_numpy(np.tile(np.float32([0.0, np.inf]), (m, 1))).to(dev)
+        d_seg = torch.from_numpy(np.tile(np.float32([0.0, 1.0]), (m, 1))).to(dev)
+        torch.cuda.synchronize()
+        call = lambda tr: (lambda: ds.occluded_device(m, d_s.data_ptr(), occ.data_ptr(), skip_obj=d_k.data_ptr(), stream=cur, t_range=tr))
+        ms = rounds_of({"unbounded": call(None), "range (0, +inf)": call(d_open.data_ptr()), "range (0, 1): segments": call(d_seg.data_ptr())})
+        report(name, ms, "unbounded")
+        counts = []
+        for tr in (None, d_open.data_ptr(), d_seg.data_ptr()):
+            call(tr)(); side.synchronize()
+            counts.append(int(occ.sum().item()))
+        print(f"{'':34s} occluded of {m}: unbounded {counts[0]}, (0, +inf) {counts[1]}, (0, 1) {counts[2]}")
+        assert counts[0] == counts[1] >= counts[2]
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--trace", action="store_true")
     ap.add_argument("--shade", action="store_true")
+    ap.add_argument("--range", action="store_true", dest="t_range")
+    ap.add_argument("--rounds", type=int, default=7)
     a = ap.parse_args()
     reps = 3 if a.trace else a.reps
     if a.shade:
         return shade_section(reps)
+    if a.t_range:
+        return range_section(reps, 2 if a.trace else a.rounds)
     dev = torch.device("cuda", 0); torch.zeros(1, device=dev)
     g = gu.GoldenScene("ground_bunny")
     ds = lib.DeviceScene(g.flat)
