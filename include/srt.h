@@ -248,7 +248,8 @@ int srt_scene_update_frame(srt_scene* s, const srt_frame_geometry* g, void* stre
  * srt_scene_set_pose_source: the points the poses are applied to, n_tris x 3 x 4 floats in the scene's CURRENT visit order (the layout
  * of srt_scene_desc.tri_points).  Copied to the device once (48 B a triangle); waits for the device.  They belong to the device records,
  * so every handle of srt_scene_share sees them.  A later srt_scene_update or srt_scene_update_frame changes the visit order and discards
- * them: set them again before the next srt_scene_pose.  NULL handle or points: SRT_ERR_ARG. */
+ * them: set them again before the next srt_scene_pose.  NULL handle or points: SRT_ERR_ARG.  A tree of height above 255 (a root
+ * that is a leaf has height 0): SRT_ERR_LIMIT, before anything is touched -- the scene keeps rendering, and has no pose source. */
 int srt_scene_set_pose_source(srt_scene* s, const float* tri_points);
 
 /* The next frame from one matrix per object: obj_matrix = n_objects x 16 floats, column-major like glm::mat4; every point of object k

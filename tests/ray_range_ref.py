@@ -118,3 +118,34 @@ def next_up(t):
 
 def next_down(t):
     return np.nextafter(np.asarray(t, np.float32), np.float32(-np.inf))
+
+
+def mixed_intervals(c, seed):
+    """One interval per ray, the kinds dealt round robin so that neighbours differ.  t1 = the ray's closest hit without bounds (a miss
+    takes the batch's median instead): 0 (next_up(t1), inf) -- the second hit; 1 (0, next_down(t1)) -- a miss; 2 (t1, t1) -- closed, the
+    same id; 3 t_min > t_max; 4 and 5 random intervals around t1; 6 one bound NaN."""
+    rng = np.random.default_rng(seed)
+    n = c.n_rays
+    hit, t1 = closest(c)
+    mid = np.float32(np.median(t1[hit >= 0])) if (hit >= 0).any() else np.float32(1.0)
+    base = np.where(hit >= 0, t1, mid).astype(np.float32)
+    a = (base * rng.uniform(0.0, 2.0, n)).astype(np.float32)
+    b = (a + base * rng.uniform(0.0, 2.0, n)).astype(np.float32)
+    kind = np.arange(n) % 7
+    tr = np.empty((n, 2), np.float32)
+    tr[:, 0] = np.select([kind == 0, kind == 1, kind == 2, kind == 3, kind == 6], [next_up(base), 0.0, base, next_up(b), np.float32(np.nan)], a)
+    tr[:, 1] = np.select([kind == 0, kind == 1, kind == 2, kind == 3, kind == 6], [np.float32(np.inf), next_down(base), base, a, a], b)
+    swap = (kind == 6) & (np.arange(n) % 2 == 1)
+    tr[swap] = tr[swap][:, ::-1]
+    return tr, kind, hit
+
+
+def want_bary(oracle, flat, rays, hit, t):
+    """calculateBarycentricCoords of every hit at o + d * t (three float32 operations), (0, 0, 0) on a miss."""
+    out = np.zeros((rays.shape[0], 3), np.float32)
+    sel = hit >= 0
+    dt = rays[sel, 3:6] * t[sel, None]
+    P = rays[sel, 0:3] + dt
+    pts = np.ascontiguousarray(flat.tri_points, np.float32).reshape(-1, 12)[hit[sel]]
+    out[sel] = oracle.barycentric(np.concatenate([pts, P], axis=1))
+    return out

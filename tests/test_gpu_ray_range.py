@@ -2,8 +2,8 @@
 (include/srt.h, RAY QUERIES, "A t interval per ray") -- pinned bit for bit by tests/ray_range_ref.py: the oracle's slab test on every
 node, its triangle test on every triangle of the reached leaves, and the header's definition in numpy.  Every batch mixes its intervals
 ray by ray, so that neighbouring lanes carry different bounds: a kernel that took the testing lane's interval instead of the owner's
-would fail.  No golden scene has a leaf of more than 8 triangles (checked below), so the sliced push of a leaf is covered only by what
-test_gpu_ray_query.py covers of it."""
+would fail.  The golden scenes have leaves of at most 8 triangles; the sliced push of larger leaves is covered by
+tests/test_gpu_tree_shapes.py, with the same interval batches (ray_range_ref.mixed_intervals)."""
 import ctypes as C
 import functools
 import os
@@ -17,6 +17,7 @@ import golden_util as gu
 import pose_ref
 import ray_query_ref as rq
 import ray_range_ref as rr
+from ray_range_ref import mixed_intervals, want_bary
 from simple_raytracer_amd import abi
 
 pytestmark = pytest.mark.gpu
@@ -44,33 +45,12 @@ def T():
     return host.Transformation
 
 
-def mixed_intervals(c, seed):
-    """One interval per ray, the kinds dealt round robin so that neighbours differ.  t1 = the ray's closest hit without bounds (a miss
-    takes the batch's median instead): 0 (next_up(t1), inf) -- the second hit; 1 (0, next_down(t1)) -- a miss; 2 (t1, t1) -- closed, the
-    same id; 3 t_min > t_max; 4 and 5 random intervals around t1; 6 one bound NaN."""
-    rng = np.random.default_rng(seed)
-    n = c.n_rays
-    hit, t1 = rr.closest(c)
-    mid = np.float32(np.median(t1[hit >= 0])) if (hit >= 0).any() else np.float32(1.0)
-    base = np.where(hit >= 0, t1, mid).astype(np.float32)
-    a = (base * rng.uniform(0.0, 2.0, n)).astype(np.float32)
-    b = (a + base * rng.uniform(0.0, 2.0, n)).astype(np.float32)
-    kind = np.arange(n) % 7
-    tr = np.empty((n, 2), np.float32)
-    tr[:, 0] = np.select([kind == 0, kind == 1, kind == 2, kind == 3, kind == 6], [rr.next_up(base), 0.0, base, rr.next_up(b), NAN], a)
-    tr[:, 1] = np.select([kind == 0, kind == 1, kind == 2, kind == 3, kind == 6], [INF, rr.next_down(base), base, a, a], b)
-    swap = (kind == 6) & (np.arange(n) % 2 == 1)
-    tr[swap] = tr[swap][:, ::-1]
-    return tr, kind, hit
-
-
 @functools.lru_cache(maxsize=None)
 def reference(name, n, seed):
     """Computed once and shared: the scene, n unrelated rays, their candidates, a mixed interval batch, skipped objects, and what the
     yardstick says of them."""
     g = gu.GoldenScene(name)
     flat = g.flat
-    assert int(flat.node_count.max()) <= 8, "a golden with a leaf of more than 8 triangles: cover the sliced push with it"
     from oracle import pyoracle
     rays = rq.unrelated_rays(flat, n, seed=seed)
     c = rr.candidates(pyoracle, flat, rays)
@@ -79,16 +59,6 @@ def reference(name, n, seed):
     want_hit, want_t = rr.closest(c, tr)
     return dict(g=g, flat=flat, rays=rays, c=c, tr=tr, kind=kind, hit0=hit0, skip=skip, hit=want_hit, t=want_t,
                 occ=rr.occluded(c, flat, tr, skip), occ_all=rr.occluded(c, flat, tr, None))
-
-
-def want_bary(oracle, flat, rays, hit, t):
-    out = np.zeros((rays.shape[0], 3), np.float32)
-    sel = hit >= 0
-    dt = rays[sel, 3:6] * t[sel, None]
-    P = rays[sel, 0:3] + dt
-    pts = np.ascontiguousarray(flat.tri_points, np.float32).reshape(-1, 12)[hit[sel]]
-    out[sel] = oracle.barycentric(np.concatenate([pts, P], axis=1))
-    return out
 
 
 def check_closest(o, hit, t, what):
