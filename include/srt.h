@@ -353,7 +353,8 @@ int srt_occluded(srt_scene* s, uint32_t n, const float* rays, const int32_t* ski
 
 /* A t interval per ray.  The _range forms take t_range = n x 2 floats, (t_min, t_max) per ray, and answer for the part of each ray inside
  * its interval: visibility between two points as a segment (d = B - A, range (0, 1)), a sensor with a reach, a ray that starts ON a
- * surface (t_min a little above 0, the origin not moved), the second hit along a ray (t_min = the next float after the first hit's t).
+ * surface (t_min a little above 0, the origin not moved), the second hit along a ray (t_min = the next float after the first hit's t;
+ * srt_trace_rays_multi below gives the K nearest hits in one walk, ties included).
  * Unless said here everything is as for the forms above: the layout of rays and of every output, the flags, the ordering on `stream`,
  * what the host forms stage (t_range travels through the same pinned block as the rays), wait for and report in *stats, the private
  * counter set, hipGraph capture of the _device forms without SRT_FLAG_COUNT_WORK, the rules of srt_scene_share, the errors, n == 0, a NULL
@@ -379,6 +380,38 @@ int srt_trace_rays_range(srt_scene* s, uint32_t n, const float* rays, const floa
 int srt_occluded_range_device(srt_scene* s, uint32_t n, const float* d_rays, const float* d_t_range,
                               const int32_t* d_skip_obj, void* stream, uint8_t* d_occluded);
 int srt_occluded_range(srt_scene* s, uint32_t n, const float* rays, const float* t_range, const int32_t* skip_obj, uint8_t* occluded);
+
+/* The K nearest hits of a ray in one walk: what lies BEHIND the first hit -- the exit point of a solid, the thickness a ray passes
+ * through, how many surfaces it crosses, the first hit a later filter accepts.  (The chain of srt_trace_rays_range calls with t_min = the
+ * next float after the last t steps over every other candidate with the same t -- coplanar duplicates, the +0 / -0 pair -- and costs one
+ * full walk and one round trip per hit.)  k = the hits wanted per ray, 1 .. SRT_MULTI_HIT_MAX.
+ * Unless said here everything is as for srt_trace_rays_range: the layout of rays and t_range with wide loads where they are 8-byte
+ * aligned, a NULL t_range, the flags, the ordering on `stream`, the private counter set, the rules of srt_scene_share, n == 0, the errors.
+ * DEFINITION.  The candidate set of a ray and each candidate's t are exactly those of srt_trace_rays_range: every leaf whose ancestors all
+ * pass the literal slab test, no pruning by t -- not by the interval, and not by the k-th hit found so far.  The QUALIFYING set Q of a ray
+ * holds its candidates with t != -inf && t < +inf that are in range, !(t < t_min) && !(t > t_max); a NULL t_range bounds nothing.
+ *   n_hits  n           u32    |Q|, the full count: it may exceed k.  Each triangle id counts once (a leaf the walk takes in slices adds
+ *                              nothing twice).
+ *   hit_id  n x k       int32  row i: the min(|Q|, k) first elements of Q in ascending order of (t with -0 keyed as +0, id) -- equal t
+ *   t       n x k       f32    goes to the lowest id first, the two zeros tie -- each t with that candidate's own bits, the sign of a zero
+ *   bary    n x k x 3   f32    included, each bary calculateBarycentricCoords at origin + direction * t of THAT hit.  The remaining slots
+ *                              of a row are -1, +inf, (0, 0, 0).
+ * Any output pointer may be NULL; the _device form with all four NULL returns SRT_OK and launches nothing.
+ *   Identities:  column 0 of every row is bit for bit what srt_trace_rays_range gives for that ray, for any k and any interval (the four
+ *                identity intervals included); n_hits[i] > 0 iff that call hits; results never depend on the order of the rays; the row
+ *                of a ray at a smaller k is a prefix of its row at a larger k.
+ * The _device form allocates and copies nothing; without SRT_FLAG_COUNT_WORK it is one launch and may be captured into a hipGraph.  The
+ * host form stages through the handle's pinned block, waits, and fills *stats: primary_rays = n, hit_rays = the rays with n_hits > 0, and
+ * under SRT_FLAG_COUNT_WORK the node_tests_primary / tri_tests_primary of the unbounded srt_trace_rays on the same rays -- the walk visits
+ * the same nodes and tests the same triangles.
+ * Errors beyond those of srt_trace_rays_range, before anything is touched: k == 0: SRT_ERR_ARG; k > SRT_MULTI_HIT_MAX: SRT_ERR_LIMIT. */
+#define SRT_MULTI_HIT_MAX 16
+int srt_trace_rays_multi_device(srt_scene* s, uint32_t n, const float* d_rays, const float* d_t_range /* n x 2 or NULL */,
+                                uint32_t k, uint32_t flags, void* stream,
+                                uint32_t* d_n_hits /* n */, int32_t* d_hit_id /* n x k */, float* d_t /* n x k */,
+                                float* d_bary /* n x k x 3 */);
+int srt_trace_rays_multi(srt_scene* s, uint32_t n, const float* rays, const float* t_range, uint32_t k, uint32_t flags,
+                         uint32_t* n_hits, int32_t* hit_id, float* t, float* bary, srt_stats* stats);
 
 /* Shaded colour: what comes back along each ray -- everything the library does after the closest hit for the pixels of its own camera
  * (texture lookup, the soft-shadow light samples, Phong, smooth normals, tone map, quantiser, background rule), for rays the caller

@@ -158,6 +158,7 @@ struct srt_scene {
     // counter set private to queries (laid out like a render's), which no render reads, zeroes or reports
     DevArray<float, 6> rq_rays; DevArray<int32_t> rq_hit; DevArray<float> rq_t; DevArray<float, 3> rq_bary; DevArray<int32_t> rq_skip; DevArray<uint8_t> rq_occ;
     DevArray<float, 2> rq_range;                  // the t intervals of a call that brings them
+    DevArray<uint32_t> rq_nhits;                  // srt_trace_rays_multi: hits per ray (its n x k rows go through rq_hit / rq_t / rq_bary, k units a ray)
     DevArray<unsigned long long> d_qctr;
     // srt_shade_rays: the query's own result buffers and its own light table (a render's d_lights may be in use on another stream): the
     // pinned copy, the event behind its last upload, the stream that upload went to, and whether it is known to have arrived
@@ -1601,6 +1602,32 @@ static int trace_rays_device_impl(srt_scene* s, uint32_t n, const float* d_rays,
     return SRT_OK;
 }
 
+// srt_trace_rays_multi: the k nearest hits per ray in one walk (k_query_multi); the build reserves 4, 8 or 16 slots a ray
+static int check_multi(const srt_scene* s, uint32_t n, const float* rays, uint32_t k, uint32_t flags) {
+    SRT_TRY(check_query(s, n, rays, flags));
+    if (k == 0) return SRT_ERR_ARG;
+    if (k > SRT_MULTI_HIT_MAX) return SRT_ERR_LIMIT;
+    return SRT_OK;
+}
+static int trace_rays_multi_device_impl(srt_scene* s, uint32_t n, const float* d_rays, const float* d_t_range, uint32_t k, uint32_t flags, hipStream_t stream,
+                                        uint32_t* d_n_hits, int32_t* d_hit_id, float* d_t, float* d_bary, bool count_hits) {
+    SRT_TRY(check_multi(s, n, d_rays, k, flags));
+    if (!n || (!count_hits && !d_n_hits && !d_hit_id && !d_t && !d_bary)) return SRT_OK;
+    const bool count = (flags & SRT_FLAG_COUNT_WORK) != 0;
+    QueryLaunch q;
+    SRT_TRY(query_prologue(s, n, stream, nullptr, count || count_hits, &q));
+    static const decltype(&k_query_multi<false, false, 4>) builds[12] = {
+        &k_query_multi<false, false, 4>,  &k_query_multi<false, true, 4>,  &k_query_multi<true, false, 4>,  &k_query_multi<true, true, 4>,
+        &k_query_multi<false, false, 8>,  &k_query_multi<false, true, 8>,  &k_query_multi<true, false, 8>,  &k_query_multi<true, true, 8>,
+        &k_query_multi<false, false, 16>, &k_query_multi<false, true, 16>, &k_query_multi<true, false, 16>, &k_query_multi<true, true, 16> };
+    static_assert(SRT_MULTI_HIT_MAX == 16, "the largest bucket holds SRT_MULTI_HIT_MAX slots");
+    const int bucket = k <= 4 ? 0 : k <= 8 ? 1 : 2;
+    hipLaunchKernelGGL(builds[bucket * 4 + (count ? 2 : 0) + (d_bary ? 1 : 0)], q.grid, dim3(256), 0, q.stream, s->dev, n, d_rays, rays_wide(d_rays), query_range(d_t_range),
+                       k, d_n_hits, d_hit_id, d_t, d_bary, q.ctr);
+    HIP_TRY(hipGetLastError());
+    return SRT_OK;
+}
+
 static int occluded_device_impl(srt_scene* s, uint32_t n, const float* d_rays, const float* d_t_range, const int32_t* d_skip_obj, hipStream_t stream,
                                 uint8_t* d_occluded) {
     SRT_TRY(check_query(s, n, d_rays, 0));
@@ -1665,11 +1692,12 @@ extern "C++" {
 template <typename T, size_t K>
 struct QueryOut {
     T* host; DevArray<T, K>& dev;
-    static constexpr size_t unit = K * sizeof(T);             // bytes per ray
+    size_t per;                                               // units per ray (k of srt_trace_rays_multi, else 1)
+    static constexpr size_t unit = K * sizeof(T);             // bytes per unit
     T* wanted() const { return host ? dev.p : nullptr; }      // (after the round trip has grown it)
 };
 template <typename T, size_t K>
-static QueryOut<T, K> query_out(T* host, DevArray<T, K>& dev) { return QueryOut<T, K>{ host, dev }; }
+static QueryOut<T, K> query_out(T* host, DevArray<T, K>& dev, size_t per = 1) { return QueryOut<T, K>{ host, dev, per }; }
 
 // The round trip of a host query on the scene's own stream: grow the wanted result buffers, stage the rays (and what comes with them: t
 // intervals, skipped objects), launch(stream) -- the device entry point --, wait, copy each wanted array out.
@@ -1679,14 +1707,14 @@ static int query_round_trip(srt_scene* s, uint32_t n, const float* rays, const f
     hipStream_t st;
     SRT_TRY(own_stream(s, &st));
     int rc = SRT_OK;
-    ((rc = (rc == SRT_OK && outs.host) ? grow(s, n, outs.dev) : rc), ...);
+    ((rc = (rc == SRT_OK && outs.host) ? grow(s, (size_t)n * outs.per, outs.dev) : rc), ...);
     SRT_TRY(rc);
     SRT_TRY(stage_rays(s, n, rays, t_range, skip_obj, st));
     SRT_TRY(launch(st));
     HIP_TRY(hipStreamSynchronize(st));
     if (s->qlights_stream == st) s->qlights_settled = true;      // a light table sent on this stream has arrived
     hipError_t e = hipSuccess;
-    ((e = (e == hipSuccess && outs.host) ? hipMemcpy(outs.host, outs.dev.p, (size_t)n * outs.unit, hipMemcpyDeviceToHost) : e), ...);
+    ((e = (e == hipSuccess && outs.host) ? hipMemcpy(outs.host, outs.dev.p, (size_t)n * outs.per * outs.unit, hipMemcpyDeviceToHost) : e), ...);
     HIP_TRY(e);
     return SRT_OK;
 }
@@ -1714,6 +1742,20 @@ static int trace_rays_impl(srt_scene* s, uint32_t n, const float* rays, const fl
     SRT_TRY(query_round_trip(s, n, rays, t_range, nullptr, [&](hipStream_t st) {
         return trace_rays_device_impl(s, n, s->rq_rays, t_range ? s->rq_range.p : nullptr, flags, st, o_hit.wanted(), o_t.wanted(), o_bary.wanted(), true);
     }, o_hit, o_t, o_bary));
+    return stats ? query_stats(s, n, 0, stats) : SRT_OK;
+}
+
+static int trace_rays_multi_impl(srt_scene* s, uint32_t n, const float* rays, const float* t_range, uint32_t k, uint32_t flags, uint32_t* n_hits, int32_t* hit_id,
+                                 float* t, float* bary, srt_stats* stats) {
+    SRT_TRY(check_multi(s, n, rays, k, flags));
+    if (stats) std::memset(stats, 0, sizeof(*stats));
+    if (!n) return SRT_OK;
+    const auto o_n = query_out(n_hits, s->rq_nhits); const auto o_hit = query_out(hit_id, s->rq_hit, k);
+    const auto o_t = query_out(t, s->rq_t, k); const auto o_bary = query_out(bary, s->rq_bary, k);
+    SRT_TRY(query_round_trip(s, n, rays, t_range, nullptr, [&](hipStream_t st) {
+        return trace_rays_multi_device_impl(s, n, s->rq_rays, t_range ? s->rq_range.p : nullptr, k, flags, st, o_n.wanted(), o_hit.wanted(), o_t.wanted(), o_bary.wanted(),
+                                            true);
+    }, o_n, o_hit, o_t, o_bary));
     return stats ? query_stats(s, n, 0, stats) : SRT_OK;
 }
 
@@ -1750,6 +1792,14 @@ int srt_trace_rays(srt_scene* s, uint32_t n, const float* rays, uint32_t flags, 
 }
 int srt_trace_rays_range(srt_scene* s, uint32_t n, const float* rays, const float* t_range, uint32_t flags, int32_t* hit_id, float* t, float* bary, srt_stats* stats) {
     return guarded([&] { return trace_rays_impl(s, n, rays, t_range, flags, hit_id, t, bary, stats); });
+}
+int srt_trace_rays_multi_device(srt_scene* s, uint32_t n, const float* d_rays, const float* d_t_range, uint32_t k, uint32_t flags, void* stream, uint32_t* d_n_hits,
+                                int32_t* d_hit_id, float* d_t, float* d_bary) {
+    return guarded([&] { return trace_rays_multi_device_impl(s, n, d_rays, d_t_range, k, flags, (hipStream_t)stream, d_n_hits, d_hit_id, d_t, d_bary, false); });
+}
+int srt_trace_rays_multi(srt_scene* s, uint32_t n, const float* rays, const float* t_range, uint32_t k, uint32_t flags, uint32_t* n_hits, int32_t* hit_id, float* t,
+                         float* bary, srt_stats* stats) {
+    return guarded([&] { return trace_rays_multi_impl(s, n, rays, t_range, k, flags, n_hits, hit_id, t, bary, stats); });
 }
 int srt_occluded_device(srt_scene* s, uint32_t n, const float* d_rays, const int32_t* d_skip_obj, void* stream, uint8_t* d_occluded) {
     return guarded([&] { return occluded_device_impl(s, n, d_rays, nullptr, d_skip_obj, (hipStream_t)stream, d_occluded); });

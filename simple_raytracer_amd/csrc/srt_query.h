@@ -51,11 +51,23 @@ __device__ __forceinline__ void load_range(const QueryRange tr, size_t i, float&
 // wave's own LDS.
 // RANGE: the lane's t interval goes into two more rows of wray (8 rows instead of 6) -- a queued pair is tested by whichever lane draws
 // it, so the interval has to live where the ray lives -- and a result joins the merge only if it is in range of its OWNER's interval.
-template <bool COUNT, bool RANGE = false>
-__device__ __forceinline__ void query_closest_walk(const DevScene& s, const bool live, const V3 o, const V3 d, const uint32_t lane, uint32_t* q,
-                                                   unsigned long long* best, float (*wray)[64], unsigned long long& n_node, unsigned long long& n_tri,
-                                                   const float t_min = 0.0f, const float t_max = 0.0f) {
-    best[lane] = ~0ull;
+// What is kept of the qualifying candidates is the MERGE's business (MergeClosest here, MergeMulti below): init(lane) before the walk by
+// the owning lane, offer(owner, triangle, t) by whichever lane tested the pair -- so a merge is atomic in LDS and independent of order.
+__device__ __forceinline__ unsigned long long hit_key(const float t, const uint32_t tri) {
+    const uint32_t tb = (t == 0.0f) ? 0u : __float_as_uint(t);     // -0.0 ties with +0.0
+    return ((unsigned long long)tb << 32) | tri;
+}
+struct MergeClosest {
+    unsigned long long* best;     // 64 words: the lane's minimum of (t bits << 32 | triangle id), ~0 on a miss
+    __device__ __forceinline__ void init(const uint32_t lane) const { best[lane] = ~0ull; }
+    __device__ __forceinline__ void offer(const uint32_t src, const uint32_t tri, const float t) const { atomicMin(&best[src], hit_key(t, tri)); }
+};
+
+template <bool COUNT, bool RANGE, typename Merge>
+__device__ __forceinline__ void query_walk(const DevScene& s, const bool live, const V3 o, const V3 d, const uint32_t lane, uint32_t* q,
+                                           const Merge mg, float (*wray)[64], unsigned long long& n_node, unsigned long long& n_tri,
+                                           const float t_min = 0.0f, const float t_max = 0.0f) {
+    mg.init(lane);
     wray[0][lane] = o.x; wray[1][lane] = o.y; wray[2][lane] = o.z;
     wray[3][lane] = d.x; wray[4][lane] = d.y; wray[5][lane] = d.z;
     if (RANGE) { wray[6][lane] = t_min; wray[7][lane] = t_max; }
@@ -125,10 +137,7 @@ __device__ __forceinline__ void query_closest_walk(const DevScene& s, const bool
                 if (COUNT) n_tri++;
                 const float t = ray_triangle(os, ds, p1, e1, e2);
                 // candidate iff t != -inf && t < +inf (the initial distanceComparison, :408); NaN fails '<'
-                if (t != SRT_NEG_INF && t < __builtin_inff() && (!RANGE || (!(t < lo) && !(t > hi)))) {
-                    const uint32_t tb = (t == 0.0f) ? 0u : __float_as_uint(t);     // -0.0 ties with +0.0
-                    atomicMin(&best[src], ((unsigned long long)tb << 32) | tri);
-                }
+                if (t != SRT_NEG_INF && t < __builtin_inff() && (!RANGE || (!(t < lo) && !(t > hi)))) mg.offer(src, tri, t);
             }
             __builtin_amdgcn_wave_barrier();
         }
@@ -153,7 +162,7 @@ __global__ __launch_bounds__(256) void k_query_closest(DevScene s, uint32_t n_ra
     float t_min = 0.0f, t_max = 0.0f;
     if (live) load_ray(rays, ri, wide != 0, o, d);
     if (RANGE && live) load_range(tr, ri, t_min, t_max);
-    query_closest_walk<COUNT, RANGE>(s, live, o, d, lane, q_all[wave], best, ray_all[wave], n_node, n_tri, t_min, t_max);
+    query_walk<COUNT, RANGE>(s, live, o, d, lane, q_all[wave], MergeClosest{ best }, ray_all[wave], n_node, n_tri, t_min, t_max);
     const float4* tris4 = reinterpret_cast<const float4*>(s.tris);
     bool is_hit = false;
     if (live) {
@@ -173,6 +182,108 @@ __global__ __launch_bounds__(256) void k_query_closest(DevScene s, uint32_t n_ra
         if (t_out) t_out[ri] = t;
         if (BARY) { bary[ri * 3] = bc.x; bary[ri * 3 + 1] = bc.y; bary[ri * 3 + 2] = bc.z; }
         is_hit = id >= 0;
+    }
+    if (counters) count_hits(counters, is_hit, blockIdx.x);
+    if (COUNT) { wave_add(counters + 1, n_node); wave_add(counters + 2, n_tri); }
+}
+
+// =================================================================================================
+// The K nearest hits of caller-supplied rays (srt_trace_rays_multi): query_walk as it stands -- the same nodes, the same pairs, the same
+// tests with the owner's ray and interval -- with a merge that keeps more than the minimum.
+// MergeMulti: k slots of 64 keys per wave (slot[j][owner], all ~0 at the start) and one counter per ray.  A key is carried down the slots:
+//     old = atomicMin(&slot[j][owner], carry); carry = max(old, carry);        stop at carry == ~0
+// Slot j keeps the minimum of everything offered to it and passes on everything else (and one ~0), so by induction it ends as the
+// (j + 1)-th smallest key of the ray, whatever the interleaving of the lanes that offer; keys of one ray differ because ids differ, and
+// a qualifying t is >= 0 or -0 (srt_device.h), so key order is (t with -0 as +0, id) order.  What falls off slot k - 1 is dropped.
+// After the walk the owning lane turns each kept key into (id, t): t is recomputed from the lane's own ray, as k_query_closest does for
+// its winner, because the key holds -0 as +0.  Rows leave TRANSPOSED: the (id, t bits) pairs go back into the lane's own slots, and the
+// wave then stores its 64 x k ids and its 64 x k t as 64 consecutive words per instruction (row i of the output IS words i*k .. i*k+k-1);
+// SRT_MULTI_LANE_STORES builds the other choice, every lane storing its own row (measured: DESIGN.md s5).  bary, 3 floats a hit, is
+// stored by the owning lane either way.
+// KB: the slots the build reserves (k <= KB): 4, 8 or 16 -- 8, 16 or 32 KB of LDS a workgroup -- so that a small k keeps its occupancy.
+// A NULL interval runs the RANGE walk with (NaN, NaN), which bounds nothing.
+// counters: as k_query_closest's; a hit ray is one with n_hits > 0.
+// =================================================================================================
+struct MergeMulti {
+    unsigned long long (*slot)[64];
+    uint32_t* cnt;                // 64 words: qualifying candidates of the lane's ray
+    uint32_t k;
+    __device__ __forceinline__ void init(const uint32_t lane) const {
+        for (uint32_t j = 0; j < k; j++) slot[j][lane] = ~0ull;
+        cnt[lane] = 0u;
+    }
+    __device__ __forceinline__ void offer(const uint32_t src, const uint32_t tri, const float t) const {
+        atomicAdd(&cnt[src], 1u);
+        unsigned long long carry = hit_key(t, tri);
+        for (uint32_t j = 0; j < k && carry != ~0ull; j++) {
+            const unsigned long long old = atomicMin(&slot[j][src], carry);
+            carry = old > carry ? old : carry;
+        }
+    }
+};
+
+template <bool COUNT, bool BARY, int KB>
+__global__ __launch_bounds__(256) void k_query_multi(DevScene s, uint32_t n_rays, const float* __restrict__ rays, uint32_t wide, QueryRange tr, uint32_t k,
+                                                     uint32_t* __restrict__ n_hits, int32_t* __restrict__ hit_id, float* __restrict__ t_out,
+                                                     float* __restrict__ bary, unsigned long long* __restrict__ counters) {
+    __shared__ uint32_t q_all[4][QCAP];
+    __shared__ unsigned long long slot_all[4][KB][64];
+    __shared__ uint32_t cnt_all[256];
+    __shared__ float ray_all[4][8][64];
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    unsigned long long (*slot)[64] = slot_all[wave];
+    uint32_t* cnt = cnt_all + wave * 64;
+    k = k < (uint32_t)KB ? k : (uint32_t)KB;            // (the host picks KB >= k)
+    const size_t base = (size_t)blockIdx.x * 256 + wave * 64, ri = base + lane;
+    const bool live = ri < (size_t)n_rays;
+    unsigned long long n_node = 0, n_tri = 0;
+    V3 o = mk(0.0f, 0.0f, 0.0f), d = mk(0.0f, 0.0f, 1.0f);
+    float t_min = __builtin_nanf(""), t_max = __builtin_nanf("");
+    if (live) load_ray(rays, ri, wide != 0, o, d);
+    if (tr.t && live) load_range(tr, ri, t_min, t_max);
+    query_walk<COUNT, true>(s, live, o, d, lane, q_all[wave], MergeMulti{ slot, cnt, k }, ray_all[wave], n_node, n_tri, t_min, t_max);
+    const float4* tris4 = reinterpret_cast<const float4*>(s.tris);
+    const bool is_hit = live && cnt[lane] != 0u;
+    if (n_hits && live) n_hits[ri] = cnt[lane];
+    if (hit_id || t_out || BARY) {
+        for (uint32_t j = 0; j < k; j++) {
+            const unsigned long long key = slot[j][lane];
+            int32_t id = -1;
+            float t = __builtin_inff();
+            V3 bc = mk(0.0f, 0.0f, 0.0f);
+            if (key != ~0ull) {
+                id = (int32_t)(uint32_t)key;
+                // the hit's t with its own bits (incl. the sign of a zero): same function, same inputs
+                V3 p1, e1, e2;
+                load_tri_edges(tris4, (size_t)id, p1, e1, e2);
+                t = ray_triangle(o, d, p1, e1, e2);
+                if (BARY) bc = barycentric(p1, e1, e2, o + d * t);       // calculateBarycentricCoords at THIS hit's point
+            }
+            if (live) {
+                const size_t at = ri * k + j;
+#ifdef SRT_MULTI_LANE_STORES
+                if (hit_id) hit_id[at] = id;
+                if (t_out) t_out[at] = t;
+#endif
+                if (BARY) { bary[at * 3] = bc.x; bary[at * 3 + 1] = bc.y; bary[at * 3 + 2] = bc.z; }
+            }
+#ifndef SRT_MULTI_LANE_STORES
+            slot[j][lane] = ((unsigned long long)__float_as_uint(t) << 32) | (uint32_t)id;
+#endif
+        }
+#ifndef SRT_MULTI_LANE_STORES
+        __builtin_amdgcn_wave_barrier();
+        if (base < (size_t)n_rays) {                    // wave-uniform
+            const size_t left = (size_t)n_rays - base;
+            const uint32_t words = (uint32_t)(left < 64 ? left : 64) * k;      // the wave's rows are words [base * k, base * k + words)
+            for (uint32_t w = lane; w < words; w += 64u) {
+                const uint32_t r = w / k, j = w - r * k;
+                const unsigned long long v = slot[j][r];
+                if (hit_id) hit_id[base * k + w] = (int32_t)(uint32_t)v;
+                if (t_out) t_out[base * k + w] = __uint_as_float((uint32_t)(v >> 32));
+            }
+        }
+#endif
     }
     if (counters) count_hits(counters, is_hit, blockIdx.x);
     if (COUNT) { wave_add(counters + 1, n_node); wave_add(counters + 2, n_tri); }
@@ -206,7 +317,7 @@ __global__ __launch_bounds__(256) void k_query_any(DevScene s, uint32_t n_rays, 
 // Shaded colour of caller-supplied rays (srt_shade_rays): per ray the one pixel of the oracle's 1 x 1 camera-mode frame -- closest hit,
 // softShadow:348-401 (shadow rays, Phong, the light-sample sum), tone map, quantiser, background rule -- in ONE launch: hit id and t stay
 // in registers between the two phases, so the call needs no buffer of its own.
-// Phase 1 is k_query_closest's walk (query_closest_walk).
+// Phase 1 is k_query_closest's walk (query_walk with MergeClosest).
 // Phase 2, a wave at a time and with no barrier between waves: the wave's h hit rays are ranked (ballot + mbcnt) and leave their shadow
 // origin so = o + d * t and their object's node range in the wave's LDS, by rank (the rays' slots: phase 1 is over).  The light samples go
 // in chunks of up to 64, in light order; a chunk's h * m work items (rank, sample) are dealt to the 64 lanes round after round --
@@ -243,7 +354,7 @@ __global__ __launch_bounds__(256) void k_query_shade(DevScene s, uint32_t n_rays
     unsigned long long n_node = 0, n_tri = 0, n_node_s = 0, n_tri_s = 0;
     V3 o = mk(0.0f, 0.0f, 0.0f), d = mk(0.0f, 0.0f, 1.0f);
     if (live) load_ray(rays, ri, wide != 0, o, d);
-    query_closest_walk<COUNT>(s, live, o, d, lane, q_all[wave], best, wray, n_node, n_tri);
+    query_walk<COUNT, false>(s, live, o, d, lane, q_all[wave], MergeClosest{ best }, wray, n_node, n_tri);
     const unsigned long long key = live ? best[lane] : ~0ull;
     const bool is_hit = key != ~0ull;
     const int32_t id = is_hit ? (int32_t)(uint32_t)key : -1;

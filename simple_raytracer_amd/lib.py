@@ -22,9 +22,11 @@ ABI_SYMBOLS = ("srt_params_default", "srt_light_staircase", "srt_rows_owned", "s
                "srt_kat_ray_triangle_origin", "srt_kat_barycentric", "srt_debug_fail_host_allocs", "srt_debug_valu_rate", "srt_debug_scene_records", "srt_scene_set_source", "srt_scene_update_frame",
                "srt_scene_pipeline", "srt_scene_overlap_estimate", "srt_scene_set_pose_source", "srt_scene_pose",
                "srt_trace_rays_device", "srt_trace_rays", "srt_occluded_device", "srt_occluded", "srt_shade_rays_device", "srt_shade_rays",
-               "srt_trace_rays_range_device", "srt_trace_rays_range", "srt_occluded_range_device", "srt_occluded_range")
+               "srt_trace_rays_range_device", "srt_trace_rays_range", "srt_occluded_range_device", "srt_occluded_range",
+               "srt_trace_rays_multi_device", "srt_trace_rays_multi")
+MULTI_HIT_MAX = 16                # SRT_MULTI_HIT_MAX
 
-_f32p, _i32p, _u8p = C.POINTER(C.c_float), C.POINTER(C.c_int32), C.POINTER(C.c_uint8)
+_f32p, _i32p, _u8p, _u32p = C.POINTER(C.c_float), C.POINTER(C.c_int32), C.POINTER(C.c_uint8), C.POINTER(C.c_uint32)
 _lib = None
 
 
@@ -100,6 +102,11 @@ def load():
         L.srt_occluded_range_device.restype = C.c_int
         L.srt_occluded_range.argtypes = [C.c_void_p, C.c_uint32, _f32p, _f32p, _i32p, _u8p]
         L.srt_occluded_range.restype = C.c_int
+        L.srt_trace_rays_multi_device.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                  C.c_void_p]
+        L.srt_trace_rays_multi_device.restype = C.c_int
+        L.srt_trace_rays_multi.argtypes = [C.c_void_p, C.c_uint32, _f32p, _f32p, C.c_uint32, C.c_uint32, _u32p, _i32p, _f32p, _f32p, C.POINTER(abi.Stats)]
+        L.srt_trace_rays_multi.restype = C.c_int
         L.srt_shade_rays_device.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(abi.Params), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.srt_shade_rays_device.restype = C.c_int
         L.srt_shade_rays.argtypes = [C.c_void_p, C.c_uint32, _f32p, C.POINTER(abi.Params), _i32p, _f32p, _f32p, _u8p, C.POINTER(abi.Stats)]
@@ -316,6 +323,34 @@ class DeviceScene:
         else:
             _check(self.L.srt_occluded_range_device(self.h, n, C.c_void_p(rays), C.c_void_p(t_range), C.c_void_p(skip_obj), C.c_void_p(stream), C.c_void_p(occluded)),
                    "srt_occluded_range_device")
+
+    def trace_rays_multi(self, rays, k, want=("n_hits", "hit_id", "t", "bary"), count=False, t_range=None):
+        """srt_trace_rays_multi: the k nearest hits of every ray of `rays` (n x 6, host array) in one walk, nearest first, equal t by id.
+        Returns a dict of the arrays named in `want` (n_hits n uint32 -- the full count, it may exceed k --, hit_id n x k, t n x k,
+        bary n x k x 3; unused slots -1, +inf, 0) + 'stats'.  t_range (n x 2: t_min, t_max per ray): only hits inside the closed interval."""
+        r = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
+        n, k = r.shape[0], int(k)
+        tr = _t_range(t_range, n)
+        kk = max(k, 0)
+        out = {}
+        if "n_hits" in want: out["n_hits"] = np.empty(n, np.uint32)
+        if "hit_id" in want: out["hit_id"] = np.empty((n, kk), np.int32)
+        if "t" in want: out["t"] = np.empty((n, kk), np.float32)
+        if "bary" in want: out["bary"] = np.empty((n, kk, 3), np.float32)
+        st = abi.Stats()
+        g = lambda key, ty: out[key].ctypes.data_as(ty) if key in out else ty()
+        flags = abi.SRT_FLAG_COUNT_WORK if count else 0
+        _check(self.L.srt_trace_rays_multi(self.h, n, r.ctypes.data_as(_f32p), tr.ctypes.data_as(_f32p) if tr is not None else None, k, flags, g("n_hits", _u32p),
+                                           g("hit_id", _i32p), g("t", _f32p), g("bary", _f32p), C.byref(st)), "srt_trace_rays_multi")
+        out["stats"] = st.as_dict()
+        return out
+
+    def trace_rays_multi_device(self, n, rays, k, stream=0, n_hits=0, hit_id=0, t=0, bary=0, count=False, t_range=None):
+        """srt_trace_rays_multi_device: raw device pointers (ints, e.g. torch.Tensor.data_ptr()) in, asynchronous on `stream`; t_range a
+        device pointer to n x 2 floats, or None."""
+        flags = abi.SRT_FLAG_COUNT_WORK if count else 0
+        _check(self.L.srt_trace_rays_multi_device(self.h, n, C.c_void_p(rays), C.c_void_p(t_range or 0), k, flags, C.c_void_p(stream), C.c_void_p(n_hits),
+                                                  C.c_void_p(hit_id), C.c_void_p(t), C.c_void_p(bary)), "srt_trace_rays_multi_device")
 
     def shade_rays(self, rays, params: abi.Params, want=("hit_id", "t", "rgb_linear", "rgb8"), count=False):
         """srt_shade_rays: the colour that comes back along every ray of `rays` (n x 6, host array) under the lights, literals and flags

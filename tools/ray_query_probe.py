@@ -12,7 +12,10 @@ stops short of shading: no Phong, no tone map).
 row-major and shuffled: the unbounded closest-hit call beside the range call with (0, +inf) -- the same answers -- and with t_max at the
 frame's median hit t; both forms of occlusion on the frame's shadow rays.  Every figure is the median of --rounds rounds of --reps
 calls, the forms alternating within a round, with the rounds' minimum and maximum: the spread the ratios are to be read against.
-Usage: python tools/ray_query_probe.py [--reps N] [--trace] [--shade | --range [--rounds R]]     (--trace: few repetitions, for a run under rocprofv3 --kernel-trace --stats)"""
+--multi: instead, the K nearest hits in one walk (srt_trace_rays_multi_device) on the same frame's rays in the three orders: k = 1, 4, 8
+and 16 without an interval beside srt_trace_rays_range_device with (0, +inf) on the same rays in the same rounds; k hits by the next_up
+chain of k range calls (t_min made on the device with torch.nextafter) beside the one multi call; the host forms end to end at k = 4.
+Usage: python tools/ray_query_probe.py [--reps N] [--trace] [--shade | --range | --multi [--rounds R]]     (--trace: few repetitions, for a run under rocprofv3 --kernel-trace --stats)"""
 import argparse, os, sys, time
 import numpy as np
 import torch                                   # first: torch initialises HIP before the library does
@@ -164,15 +167,93 @@ def range_section(reps, rounds):
         assert counts[0] == counts[1] >= counts[2]
 
 
+def multi_section(reps, rounds):
+    dev = torch.device("cuda", 0); torch.zeros(1, device=dev)
+    g = gu.GoldenScene("ground_bunny")
+    ds = lib.DeviceScene(g.flat)
+    side = torch.cuda.Stream(device=dev)
+    cur = side.cuda_stream
+    rays = frame_rays()
+    n = rays.shape[0]
+    KS = (1, 4, 8, 16)
+    hit = torch.empty(n, dtype=torch.int32, device=dev); t = torch.empty(n, dtype=torch.float32, device=dev)
+    cnt = torch.empty(n, dtype=torch.int32, device=dev)
+    mhit = torch.empty(n * 16, dtype=torch.int32, device=dev); mt = torch.empty(n * 16, dtype=torch.float32, device=dev)
+    d_open = torch.from_numpy(np.tile(np.float32([0.0, np.inf]), (n, 1))).to(dev)
+    d_tr = d_open.clone()
+    inf = torch.full((n,), float("inf"), device=dev)
+    print(f"K nearest hits, K3 ground_bunny {W}x{H}: {n} rays; {rounds} rounds of {reps} calls, forms alternating; ms a call (n_hits, hit_id, t written)")
+    print(f"{'rays':34s} {'form':34s} {'median':>8s} {'min':>8s} {'max':>8s} {'/ first':>7s}")
+
+    def rounds_of(forms):
+        ms = {k: [] for k in forms}
+        for _ in range(rounds):
+            for k, fn in forms.items():
+                ms[k].append(timed(fn, reps, side))
+        return ms
+
+    def report(title, ms):
+        med = {k: float(np.median(v)) for k, v in ms.items()}
+        yard = next(iter(med))
+        for k, v in ms.items():
+            print(f"{title:34s} {k:34s} {med[k]:8.3f} {min(v):8.3f} {max(v):8.3f} {med[k] / med[yard]:7.3f}")
+
+    for name, order in (("(a) tile order", tile_order()), ("(b) row-major", np.arange(n)), ("(c) randomly permuted", np.random.default_rng(1).permutation(n))):
+        d_rays = torch.from_numpy(np.ascontiguousarray(rays[order])).to(dev)
+        torch.cuda.synchronize()
+        rng_call = lambda: ds.trace_rays_device(n, d_rays.data_ptr(), stream=cur, hit_id=hit.data_ptr(), t=t.data_ptr(), t_range=d_open.data_ptr())
+        multi = lambda k: (lambda: ds.trace_rays_multi_device(n, d_rays.data_ptr(), k, stream=cur, n_hits=cnt.data_ptr(), hit_id=mhit.data_ptr(), t=mt.data_ptr()))
+        forms = {"range (0, +inf)": rng_call}
+        forms.update({f"multi k = {k}": multi(k) for k in KS})
+        report(name, rounds_of(forms))
+        # column 0 of the multi call is the range call
+        rng_call(); multi(8)(); side.synchronize()
+        assert torch.equal(mhit[:n * 8].view(n, 8)[:, 0], hit) and torch.equal(mt[:n * 8].view(n, 8)[:, 0].view(torch.int32), t.view(torch.int32))
+        hist = torch.bincount(cnt.clamp(max=17).long(), minlength=18).cpu().numpy()
+        print(f"{'':34s} hits per ray (0, 1, 2, ...; last = 17 and more): {hist.tolist()}")
+        if name != "(b) row-major":
+            continue
+
+        def chain(k):
+            def run():
+                with torch.cuda.stream(side):
+                    d_tr.copy_(d_open)
+                for j in range(k):
+                    ds.trace_rays_device(n, d_rays.data_ptr(), stream=cur, hit_id=hit.data_ptr(), t=t.data_ptr(), t_range=d_tr.data_ptr())
+                    if j + 1 < k:
+                        with torch.cuda.stream(side):
+                            d_tr[:, 0] = torch.where(hit >= 0, torch.nextafter(t, inf), inf)
+            return run
+        for k in (4, 8):
+            report(f"{k} hits, row-major", rounds_of({f"multi k = {k}, one call": multi(k), f"next_up chain, {k} range calls": chain(k)}))
+    # the host forms, end to end (staging, wait, copies back)
+    r = np.ascontiguousarray(rays)
+    tr = np.tile(np.float32([0.0, np.inf]), (n, 1))
+    ms = {"srt_trace_rays_range (hit_id, t)": [], "srt_trace_rays_multi k = 4 (n_hits, hit_id, t)": []}
+    for _ in range(rounds):
+        for key, fn in (("srt_trace_rays_range (hit_id, t)", lambda: ds.trace_rays(r, want=("hit_id", "t"), t_range=tr)),
+                        ("srt_trace_rays_multi k = 4 (n_hits, hit_id, t)", lambda: ds.trace_rays_multi(r, 4, want=("n_hits", "hit_id", "t")))):
+            fn()
+            t0 = time.perf_counter()
+            for _ in range(3):
+                fn()
+            ms[key].append((time.perf_counter() - t0) / 3 * 1e3)
+    for key, v in ms.items():
+        print(f"{'host form, end to end':34s} {key:46s} {float(np.median(v)):8.3f} {min(v):8.3f} {max(v):8.3f}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--trace", action="store_true")
     ap.add_argument("--shade", action="store_true")
     ap.add_argument("--range", action="store_true", dest="t_range")
+    ap.add_argument("--multi", action="store_true")
     ap.add_argument("--rounds", type=int, default=7)
     a = ap.parse_args()
     reps = 3 if a.trace else a.reps
+    if a.multi:
+        return multi_section(reps, 2 if a.trace else a.rounds)
     if a.shade:
         return shade_section(reps)
     if a.t_range:
