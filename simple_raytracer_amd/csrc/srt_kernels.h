@@ -66,6 +66,11 @@ __device__ __forceinline__ void wave_add(unsigned long long* ctr, unsigned long 
     if ((threadIdx.x & 63) == 0 && v) atomicAdd(ctr, v);
 }
 
+// bits of a ballot below this lane: its rank among the lanes that voted
+__device__ __forceinline__ uint32_t lane_prefix(unsigned long long m) {
+    return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+}
+
 // Hit-pixel statistic without a hot atomic: one word takes ~12 ns per atomic, so 32 k waves adding to one
 // address would serialise for ~0.4 ms.  64 shards, 64 B apart, summed on the host.
 constexpr int HIT_SHARDS = 64;
@@ -204,10 +209,6 @@ __global__ __launch_bounds__(256) void k_closest_hit(DevScene s, DevParams p, in
 // =================================================================================================
 constexpr int QCAP = 64 + 64 * 8 + 64;      // leftover (< 64) + one push round (64 lanes x <= 8) + slack
 constexpr int PUSH_MAX = 8;                 // per lane per round; larger leaves are pushed in slices
-
-__device__ __forceinline__ uint32_t lane_prefix(unsigned long long m) {
-    return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-}
 
 template <bool COUNT>
 __global__ __launch_bounds__(256) void k_closest_hit_q(DevScene s, DevParams p, int32_t* __restrict__ hit_id,
@@ -371,6 +372,51 @@ __device__ __forceinline__ void quadrant_list_append(uint32_t* __restrict__ qcou
 constexpr int NQ_P = 16;                    // rays per wavefront of the shadow kernel (4x4 pixel quadrant)
 constexpr int LQ_WORDS = 2 * (64 + 128);    // (leaf, ray) pair queue of the node-queue kernels: < 64 left over + <= 128 per push (two children per lane), 2 words each
 
+// ---- the queues of closest_hit_phase and shadow_phase ------------------------------------------------------------------------
+// A wave serves up to 64 rays, each known by its SLOT (the pixel lane of the closest-hit phase, the ray slot of the shadow phase),
+// and keeps two LIFO queues in LDS with wave-uniform lengths:
+//   nq: one word per entry, node << 6 | slot.  Narrow form: a 32 B DevNode still to be tested.  Wide form: a 64 B DevWide record of
+//       an inner node that is known to pass; a pop tests BOTH its children.
+//   tq: two words per entry, a passing leaf's (first << 5 | count) and the slot.  Whenever 64 entries are queued the phase's own
+//       `drain` (its tri_batch) takes 64 of them, one per lane, so at most 63 wait when a push begins.
+// A step pops <= 64 nq entries, one per lane, and pushes the children of the passing inner nodes and the passing leaves.
+// `lane_order` (p.exp & 1) says where: false = node-major, all entries of one child side before those of the other, so that rays that
+// visit one node stay neighbours; true = each lane's entries side by side.  If nq cannot take a step's children the wave finishes
+// those subtrees with the stackless pre-order walk over the DevNode records (i = pass ? i + 1 : skip[i]): any tree shape is handled
+// with bounded LDS.  Such a walk takes the exact test only (it is rare), and a shadow ray that has its hit leaves it at once.
+// The leaf-queue pushes are shared below.  The node pops, the child pushes and the overflow walks are still written out per phase
+// and form: stated as shared functions they compile to different code (more spills in the shipped kernels).
+// queue each lane's passing leaf (is_leaf = false: nothing)
+template <typename DRAIN>
+__device__ __forceinline__ void leaf_queue_push(uint32_t* tq, uint32_t& tqn, uint32_t info, bool is_leaf, uint32_t slot, DRAIN drain) {
+    const unsigned long long lm = __ballot(is_leaf);
+    if (lm) {
+        if (is_leaf) {
+            const uint32_t pos = tqn + lane_prefix(lm);
+            tq[2 * pos] = info; tq[2 * pos + 1] = slot;
+        }
+        tqn += (uint32_t)__popcll(lm);
+        __builtin_amdgcn_wave_barrier();
+        while (tqn >= 64) drain();
+    }
+}
+// the same for up to two passing leaves per lane (the two children of a DevWide record)
+template <typename DRAIN>
+__device__ __forceinline__ void leaf_queue_push2(uint32_t* tq, uint32_t& tqn, bool lane_order, uint32_t info_a, bool leaf_a, uint32_t info_b, bool leaf_b,
+                                                 uint32_t slot, DRAIN drain) {
+    const unsigned long long ma = __ballot(leaf_a), mb = __ballot(leaf_b);
+    if (ma | mb) {
+        uint32_t pos = tqn + lane_prefix(ma) + lane_prefix(mb), q = pos + (leaf_a ? 1u : 0u);
+        if (!lane_order) { pos = tqn + lane_prefix(ma); q = tqn + (uint32_t)__popcll(ma) + lane_prefix(mb); }      // node-major
+        if (leaf_a) { tq[2 * pos] = info_a; tq[2 * pos + 1] = slot; }
+        if (leaf_b) { tq[2 * q] = info_b; tq[2 * q + 1] = slot; }
+        tqn += (uint32_t)__popcll(ma) + (uint32_t)__popcll(mb);
+        __builtin_amdgcn_wave_barrier();
+        while (tqn >= 64) drain();
+    }
+}
+
+
 // TWL / THL: log2 of the tile width / height a wavefront owns (shipped: 4x4); FILTER: filtered slab predicate.
 #ifdef SRT_DIAG
 // Diagnostic build only (python -m simple_raytracer_amd.build --diag -> libsrt_hip_diag.so, never shipped): per-wave
@@ -484,34 +530,6 @@ __device__ __forceinline__ void closest_hit_phase(const DevScene& s, const DevPa
         SRT_STAMP(c1); dg_tri += c1 - c0;
 #endif
     };
-    // queue each lane's passing leaf (is_leaf = false: nothing)
-    auto push_tris = [&](uint32_t info, bool is_leaf, uint32_t pl) {
-        const unsigned long long lm = __ballot(is_leaf);
-        if (lm) {
-            if (is_leaf) {
-                const uint32_t pos = tqn + lane_prefix(lm);
-                tq[2 * pos] = info; tq[2 * pos + 1] = pl;
-            }
-            tqn += (uint32_t)__popcll(lm);
-            __builtin_amdgcn_wave_barrier();
-            while (tqn >= 64) tri_batch();
-        }
-    };
-
-    // the same for up to two passing leaves per lane (the two children of a DevWide record)
-    auto push_tris2 = [&](uint32_t info_a, bool leaf_a, uint32_t info_b, bool leaf_b, uint32_t pl) {
-        const unsigned long long ma = __ballot(leaf_a), mb = __ballot(leaf_b);
-        if (ma | mb) {
-            uint32_t pos = tqn + lane_prefix(ma) + lane_prefix(mb), q = pos + (leaf_a ? 1u : 0u);
-            if (!(p.exp & 1u)) { pos = tqn + lane_prefix(ma); q = tqn + (uint32_t)__popcll(ma) + lane_prefix(mb); }      // node-major
-            if (leaf_a) { tq[2 * pos] = info_a; tq[2 * pos + 1] = pl; }
-            if (leaf_b) { tq[2 * q] = info_b; tq[2 * q + 1] = pl; }
-            tqn += (uint32_t)__popcll(ma) + (uint32_t)__popcll(mb);
-            __builtin_amdgcn_wave_barrier();
-            while (tqn >= 64) tri_batch();
-        }
-    };
-
     const uint32_t n_obj = s.n_objects;
     const uint32_t nlive = (uint32_t)__popcll(livem);
     constexpr uint32_t OBJ_G = (NQCAP / (2 * P)) < 16 ? (NQCAP / (2 * P)) : 16;      // roots pushed at once: P * OBJ_G <= NQCAP / 2
@@ -543,7 +561,7 @@ __device__ __forceinline__ void closest_hit_phase(const DevScene& s, const DevPa
             const unsigned long long im = __ballot(inner);
             if (inner) nq[nqn + lane_prefix(im)] = ((uint32_t)(~info) << 6) | pl;
             nqn += (uint32_t)__popcll(im);
-            push_tris2((uint32_t)info, leafp, 0u, false, pl);
+            leaf_queue_push2(tq, tqn, p.exp & 1u, (uint32_t)info, leafp, 0u, false, pl, tri_batch);
         }
         __builtin_amdgcn_wave_barrier();
         while (nqn) {
@@ -598,12 +616,12 @@ __device__ __forceinline__ void closest_hit_phase(const DevScene& s, const DevPa
                 if (in_l) nq[pos + (in_r ? 1u : 0u)] = ((uint32_t)(~linfo) << 6) | pl;      // left child on top: popped first
                 }
                 nqn += n_in;
-                push_tris2((uint32_t)linfo, lf_l, (uint32_t)rinfo, lf_r, pl);
+                leaf_queue_push2(tq, tqn, p.exp & 1u, (uint32_t)linfo, lf_l, (uint32_t)rinfo, lf_r, pl, tri_batch);
             } else {
                 // queue full: finish the passing children's subtrees with the stackless pre-order walk over the 32 B records
                 // (i = pass ? i + 1 : skip[i]).  Left subtree = nodes (node + 2 .. rnode), right = (rnode + 1 .. skip[rnode]); with both
                 // the walk runs through and hops over the right child itself, which has been tested above.
-                push_tris2((uint32_t)linfo, lf_l, (uint32_t)rinfo, lf_r, pl);
+                leaf_queue_push2(tq, tqn, p.exp & 1u, (uint32_t)linfo, lf_l, (uint32_t)rinfo, lf_r, pl, tri_batch);
                 int32_t i = 0, end = 0, hop = -1;
                 if (in_l | in_r) {
                     i = in_l ? node + 2 : rnode + 1;
@@ -628,7 +646,7 @@ __device__ __forceinline__ void closest_hit_phase(const DevScene& s, const DevPa
                             }
                         }
                     }
-                    push_tris2((uint32_t)inf2, lp2, 0u, false, pl);
+                    leaf_queue_push2(tq, tqn, p.exp & 1u, (uint32_t)inf2, lp2, 0u, false, pl, tri_batch);
                 }
             }
             __builtin_amdgcn_wave_barrier();
@@ -659,7 +677,7 @@ __device__ __forceinline__ void closest_hit_phase(const DevScene& s, const DevPa
                     nq[pos1] = ((uint32_t)(root + 1) << 6) | pl;      // left child on top: popped first
                 }
                 nqn += 2 * (uint32_t)__popcll(im);
-                push_tris((uint32_t)info, leafp, pl);
+                leaf_queue_push(tq, tqn, (uint32_t)info, leafp, pl, tri_batch);
             }
         } else
         for (uint32_t base = 0; base < P * g; base += 64) {
@@ -727,10 +745,10 @@ __device__ __forceinline__ void closest_hit_phase(const DevScene& s, const DevPa
                     nq[pos1] = ((uint32_t)(node + 1) << 6) | pl;      // left child on top: popped first
                 }
                 nqn += 2 * n_in;
-                push_tris((uint32_t)info, leafp, pl);
+                leaf_queue_push(tq, tqn, (uint32_t)info, leafp, pl, tri_batch);
             } else {
                 // queue full: finish these subtrees with the stackless pre-order walk (i = pass ? i+1 : skip[i])
-                push_tris((uint32_t)info, leafp, pl);
+                leaf_queue_push(tq, tqn, (uint32_t)info, leafp, pl, tri_batch);
                 int32_t i = inner ? node + 1 : 0, end = inner ? skip : 0;
                 while (__ballot(i < end)) {
                     int32_t inf2 = -1;
@@ -747,7 +765,7 @@ __device__ __forceinline__ void closest_hit_phase(const DevScene& s, const DevPa
                             i = sk;
                         }
                     }
-                    push_tris((uint32_t)inf2, lp2, pl);
+                    leaf_queue_push(tq, tqn, (uint32_t)inf2, lp2, pl, tri_batch);
                 }
             }
             __builtin_amdgcn_wave_barrier();
@@ -1228,19 +1246,7 @@ __device__ __forceinline__ void shadow_phase(const DevScene& s, const DevParams&
         }
         __builtin_amdgcn_wave_barrier();
     };
-    auto push_tris = [&](uint32_t info, bool is_leaf, uint32_t rs) {
-        const unsigned long long lm = __ballot(is_leaf);
-        if (lm) {
-            if (is_leaf) {
-                const uint32_t pos = tqn + lane_prefix(lm);
-                tq[2 * pos] = info; tq[2 * pos + 1] = rs;
-            }
-            tqn += (uint32_t)__popcll(lm);
-            __builtin_amdgcn_wave_barrier();
-            while (tqn >= 64) tri_batch();
-        }
-    };
-
+    // (the two-leaf push stays a copy of leaf_queue_push2 here: sharing it changes the code of the wide filtered shadow kernels)
     auto push_tris2 = [&](uint32_t info_a, bool leaf_a, uint32_t info_b, bool leaf_b, uint32_t rs) {
         const unsigned long long ma = __ballot(leaf_a), mb = __ballot(leaf_b);
         if (ma | mb) {
@@ -1366,7 +1372,7 @@ __device__ __forceinline__ void shadow_phase(const DevScene& s, const DevParams&
                             nqn += n_in;
                             push_tris2((uint32_t)linfo, lf_l, (uint32_t)rinfo, lf_r, rs);
                         } else {
-                            // queue full: the passing children's subtrees by the stackless walk (see closest_hit_phase)
+                            // queue full: the passing children's subtrees by the stackless walk
                             push_tris2((uint32_t)linfo, lf_l, (uint32_t)rinfo, lf_r, rs);
                             int32_t i = 0, end = 0, hop = -1;
                             if (in_l | in_r) {
@@ -1452,9 +1458,9 @@ __device__ __forceinline__ void shadow_phase(const DevScene& s, const DevParams&
                                 nq[pos1] = ((uint32_t)(node + 1) << 6) | rs;
                             }
                             nqn += 2 * n_in;
-                            push_tris((uint32_t)info, leafp, rs);
+                            leaf_queue_push(tq, tqn, (uint32_t)info, leafp, rs, tri_batch);
                         } else {
-                            push_tris((uint32_t)info, leafp, rs);
+                            leaf_queue_push(tq, tqn, (uint32_t)info, leafp, rs, tri_batch);
                             int32_t i = inner ? node + 1 : 0, end = inner ? skip : 0;
                             while (__ballot(i < end)) {
                                 int32_t inf2 = -1;
@@ -1473,7 +1479,7 @@ __device__ __forceinline__ void shadow_phase(const DevScene& s, const DevParams&
                                         }
                                     }
                                 }
-                                push_tris((uint32_t)inf2, lp2, rs);
+                                leaf_queue_push(tq, tqn, (uint32_t)inf2, lp2, rs, tri_batch);
                             }
                         }
                         __builtin_amdgcn_wave_barrier();
