@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """A mirror floor from a ray query: render the K3 scene (bunny on its ground slab) in camera mode, build with numpy one reflected ray per
-ground pixel from the caller's own triangle points, ask srt_shade_rays what colour comes back along each, mix the linear colours and
-tone-map.  The library has no recursion; the caller composes it from this call.
+ground pixel from the caller's own triangle points, ask srt_shade_rays_range what colour comes back along each, mix the linear colours
+and tone-map.  A reflected ray starts AT the hit point -- the origin is not moved, so the shadow origin o + d * t and Phong's view vector
+are those of the true ray -- and its interval (T_MIN, +inf) keeps it off the slab it starts on.  The library has no recursion; the
+caller composes it from this call.
 Usage: python examples/mirror.py [out.bmp [width height [reflectance]]]     (needs a GPU)"""
 import os, struct, sys
 import numpy as np
@@ -13,6 +15,7 @@ import golden_util as gu                       # noqa: E402
 
 GROUND = 0            # object 0 of the scene is the slab (cube.obj), object 1 the bunny
 N_LIGHTS = 4
+T_MIN = 1e-4          # in units of the reflected direction (as long as the primary one: (i, j, focal), some hundreds): about 1e-2 off the slab
 
 
 def display_tone(lin, reinhard=0.5, gamma=1.1):
@@ -67,9 +70,10 @@ def main():
     n = np.where(np.sum(n * dg, axis=1, keepdims=True) > 0, -n, n)                 # the side the ray arrives on
     point = dg * t[ground, None]
     r = dg - 2.0 * np.sum(dg * n, axis=1, keepdims=True) * n
-    rays = np.ascontiguousarray(np.concatenate([point + n * np.float32(1e-2), r], axis=1), np.float32)      # lifted off the slab
+    rays = np.ascontiguousarray(np.concatenate([point, r], axis=1), np.float32)      # from the hit point itself
+    t_range = np.tile(np.float32([T_MIN, np.inf]), (rays.shape[0], 1))
     p = abi.make_params(1, 1, lights)                      # lights, literals, flags: the frame fields are ignored
-    back = ds.shade_rays(rays, p, want=("hit_id", "rgb_linear"))
+    back = ds.shade_rays(rays, p, want=("hit_id", "rgb_linear"), t_range=t_range)
     seen = back["hit_id"] >= 0
     lin[ground[seen]] = (np.float32(1.0) - k) * lin[ground[seen]] + k * back["rgb_linear"][seen]
     rgb8 = display_tone(lin)

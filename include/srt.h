@@ -372,7 +372,7 @@ int srt_occluded(srt_scene* s, uint32_t n, const float* rays, const int32_t* ski
  * Boxes are NOT rejected by t_max: the walk visits exactly the nodes the unbounded call visits, so under SRT_FLAG_COUNT_WORK the
  * closest-hit form reports the node_tests_primary and tri_tests_primary of the unbounded call on the same rays; the interval costs
  * 8 bytes per ray and two comparisons per tested triangle, and saves no work.
- * srt_shade_rays takes no interval: the colour of a hit that is not the closest one has no reduction to an oracle frame yet. */
+ * The shaded query takes an interval too: srt_shade_rays_range, declared after srt_shade_rays below. */
 int srt_trace_rays_range_device(srt_scene* s, uint32_t n, const float* d_rays, const float* d_t_range /* n x 2: t_min, t_max; or NULL */,
                                 uint32_t flags, void* stream, int32_t* d_hit_id, float* d_t, float* d_bary);
 int srt_trace_rays_range(srt_scene* s, uint32_t n, const float* rays, const float* t_range, uint32_t flags,
@@ -454,6 +454,33 @@ int srt_shade_rays_device(srt_scene* s, uint32_t n, const float* d_rays, const s
                           int32_t* d_hit_id, float* d_t, float* d_rgb_linear /* n x 3 */, uint8_t* d_rgb8 /* n x 3 */);
 int srt_shade_rays(srt_scene* s, uint32_t n, const float* rays, const srt_params* p,
                    int32_t* hit_id, float* t, float* rgb_linear, uint8_t* rgb8, srt_stats* stats);
+
+/* Shaded colour inside a t interval per ray: the colour of the closest hit IN RANGE -- a reflected ray that starts ON a surface (t_min a
+ * little above 0, the origin not moved, so that the shadow origin and Phong's view vector keep their bits), the colour seen through a first
+ * surface, the colour at the exit point of a solid.
+ * Unless said here everything is as for srt_shade_rays: the params fields read and ignored, the flags, the errors (checked before anything
+ * is touched), n == 0, NULL outputs, the one-light-table-per-handle rule, hipGraph capture of the _device form, srt_scene_share.  t_range is
+ * read exactly as srt_trace_rays_range reads it: n x 2 floats (t_min, t_max), one 8-byte load per ray where the pointer is 8-byte aligned,
+ * two 4-byte loads where it is only float-aligned; the host form stages it through the same pinned block as the rays.
+ * DEFINITION.
+ *   hit_id, t         bit for bit what srt_trace_rays_range gives for that ray and interval: the candidate set is unchanged, a candidate is
+ *                     in range iff !(t < t_min) && !(t > t_max), equal t goes to the lowest id, +0 ties with -0, and the reported t has the
+ *                     winner's own bits.
+ *   rgb_linear, rgb8  everything srt_shade_rays computes after the closest hit, applied to THAT hit: the surface lookup at o + d * t, the
+ *                     shadow rays from so = o + d * t towards L - so, Phong with the ray's own o and d, the sum in light order, the tone
+ *                     map, the quantiser and the background rule.  The origin is never moved.  The shadow rays stay unbounded, with the hit
+ *                     object's tree left out, as in the reference: the interval bounds the primary ray only.
+ *   No in-range candidate: -1, +inf, (0, 0, 0) and the background.
+ *   Identities:  a NULL t_range gives srt_shade_rays' bits in every output for every ray (and launches its kernels); so does a ray whose
+ *                interval is (0, +inf), (-inf, +inf) or (NaN, NaN).  t_min > t_max: a miss.
+ * *stats: primary_rays = n, hit_rays = the rays with an in-range hit, shadow_rays = hit_rays x n_lights.  Under SRT_FLAG_COUNT_WORK
+ * node_tests_primary and tri_tests_primary are those of the unbounded srt_trace_rays on the same rays (the walk is the same: boxes are not
+ * rejected by t_max), node_tests_shadow and tri_tests_shadow the oracle's algorithmic counts for the shadow rays of the hits reported. */
+int srt_shade_rays_range_device(srt_scene* s, uint32_t n, const float* d_rays, const float* d_t_range /* n x 2 or NULL */,
+                                const srt_params* p, void* stream,
+                                int32_t* d_hit_id, float* d_t, float* d_rgb_linear, uint8_t* d_rgb8);
+int srt_shade_rays_range(srt_scene* s, uint32_t n, const float* rays, const float* t_range, const srt_params* p,
+                         int32_t* hit_id, float* t, float* rgb_linear, uint8_t* rgb8, srt_stats* stats);
 
 /* Device-resident size of the scene records and the per-record algorithmic byte sizes used by
  * the bytes model: 32 B per node test, 36 B per triangle test. */

@@ -1641,8 +1641,9 @@ static int occluded_device_impl(srt_scene* s, uint32_t n, const float* d_rays, c
 }
 
 // srt_shade_rays: closest hit, shadow rays, Phong, tone map for caller-supplied rays, one launch (k_query_shade)
-static int shade_rays_device_impl(srt_scene* s, uint32_t n, const float* d_rays, const srt_params* p, hipStream_t stream, int32_t* d_hit_id, float* d_t,
-                                  float* d_rgb_linear, uint8_t* d_rgb8, bool count_hits) {
+// d_t_range: the rays' t intervals (srt_shade_rays_range), or null: the builds without the interval, as trace_rays_device_impl chooses its own
+static int shade_rays_device_impl(srt_scene* s, uint32_t n, const float* d_rays, const float* d_t_range, const srt_params* p, hipStream_t stream, int32_t* d_hit_id,
+                                  float* d_t, float* d_rgb_linear, uint8_t* d_rgb8, bool count_hits) {
     SRT_TRY(check_shade(s, n, d_rays, p));
     if (!n) return SRT_OK;
     const bool count = (p->flags & SRT_FLAG_COUNT_WORK) != 0, smooth = (p->flags & SRT_FLAG_SMOOTH_NORMALS) != 0;
@@ -1654,11 +1655,13 @@ static int shade_rays_device_impl(srt_scene* s, uint32_t n, const float* d_rays,
     qs.bg = (uint32_t)p->background[0] | ((uint32_t)p->background[1] << 8) | ((uint32_t)p->background[2] << 16);
     qs.spread = p->n_lights >= 8 ? 1u : 0u;      // (measured at 1 and 16 samples, DESIGN.md s5: the spread costs phase 1, and pays with the shadow work)
     // the build: counting, smooth normals, and the integer-shininess pow where every object of the scene allows it (as k_shade_tile)
-    static const decltype(&k_query_shade<false, false, false>) builds[8] = {
-        &k_query_shade<false, false, false>, &k_query_shade<false, false, true>, &k_query_shade<false, true, false>, &k_query_shade<false, true, true>,
-        &k_query_shade<true, false, false>,  &k_query_shade<true, false, true>,  &k_query_shade<true, true, false>,  &k_query_shade<true, true, true> };
-    const auto k = builds[(count ? 4 : 0) | (smooth ? 2 : 0) | (s->rec->int_shin ? 1 : 0)];
-    hipLaunchKernelGGL(k, q.grid, dim3(256), 0, q.stream, s->dev, n, d_rays, rays_wide(d_rays), qs, d_hit_id, d_t, d_rgb_linear, d_rgb8, q.ctr);
+    static const decltype(&k_query_shade<false, false, false, false>) builds[16] = {
+        &k_query_shade<false, false, false, false>, &k_query_shade<false, false, true, false>, &k_query_shade<false, true, false, false>, &k_query_shade<false, true, true, false>,
+        &k_query_shade<true, false, false, false>,  &k_query_shade<true, false, true, false>,  &k_query_shade<true, true, false, false>,  &k_query_shade<true, true, true, false>,
+        &k_query_shade<false, false, false, true>,  &k_query_shade<false, false, true, true>,  &k_query_shade<false, true, false, true>,  &k_query_shade<false, true, true, true>,
+        &k_query_shade<true, false, false, true>,   &k_query_shade<true, false, true, true>,   &k_query_shade<true, true, false, true>,   &k_query_shade<true, true, true, true> };
+    const auto k = builds[(d_t_range ? 8 : 0) | (count ? 4 : 0) | (smooth ? 2 : 0) | (s->rec->int_shin ? 1 : 0)];
+    hipLaunchKernelGGL(k, q.grid, dim3(256), 0, q.stream, s->dev, n, d_rays, rays_wide(d_rays), qs, d_hit_id, d_t, d_rgb_linear, d_rgb8, q.ctr, query_range(d_t_range));
     HIP_TRY(hipGetLastError());
     return SRT_OK;
 }
@@ -1767,15 +1770,15 @@ static int occluded_impl(srt_scene* s, uint32_t n, const float* rays, const floa
     }, query_out(occluded, s->rq_occ));
 }
 
-static int shade_rays_impl(srt_scene* s, uint32_t n, const float* rays, const srt_params* p, int32_t* hit_id, float* t, float* rgb_linear, uint8_t* rgb8,
-                           srt_stats* stats) {
+static int shade_rays_impl(srt_scene* s, uint32_t n, const float* rays, const float* t_range, const srt_params* p, int32_t* hit_id, float* t, float* rgb_linear,
+                           uint8_t* rgb8, srt_stats* stats) {
     SRT_TRY(check_shade(s, n, rays, p));
     if (stats) std::memset(stats, 0, sizeof(*stats));
     if (!n) return SRT_OK;
     const auto o_hit = query_out(hit_id, s->rq_hit); const auto o_t = query_out(t, s->rq_t);
     const auto o_lin = query_out(rgb_linear, s->rq_lin); const auto o_rgb8 = query_out(rgb8, s->rq_rgb8);
-    SRT_TRY(query_round_trip(s, n, rays, nullptr, nullptr, [&](hipStream_t st) {
-        return shade_rays_device_impl(s, n, s->rq_rays, p, st, o_hit.wanted(), o_t.wanted(), o_lin.wanted(), o_rgb8.wanted(), true);
+    SRT_TRY(query_round_trip(s, n, rays, t_range, nullptr, [&](hipStream_t st) {
+        return shade_rays_device_impl(s, n, s->rq_rays, t_range ? s->rq_range.p : nullptr, p, st, o_hit.wanted(), o_t.wanted(), o_lin.wanted(), o_rgb8.wanted(), true);
     }, o_hit, o_t, o_lin, o_rgb8));
     return stats ? query_stats(s, n, p->n_lights, stats) : SRT_OK;
 }
@@ -1815,11 +1818,19 @@ int srt_occluded_range(srt_scene* s, uint32_t n, const float* rays, const float*
 }
 int srt_shade_rays_device(srt_scene* s, uint32_t n, const float* d_rays, const srt_params* p, void* stream, int32_t* d_hit_id, float* d_t,
                           float* d_rgb_linear, uint8_t* d_rgb8) {
-    return guarded([&] { return shade_rays_device_impl(s, n, d_rays, p, (hipStream_t)stream, d_hit_id, d_t, d_rgb_linear, d_rgb8, false); });
+    return guarded([&] { return shade_rays_device_impl(s, n, d_rays, nullptr, p, (hipStream_t)stream, d_hit_id, d_t, d_rgb_linear, d_rgb8, false); });
+}
+int srt_shade_rays_range_device(srt_scene* s, uint32_t n, const float* d_rays, const float* d_t_range, const srt_params* p, void* stream, int32_t* d_hit_id, float* d_t,
+                                float* d_rgb_linear, uint8_t* d_rgb8) {
+    return guarded([&] { return shade_rays_device_impl(s, n, d_rays, d_t_range, p, (hipStream_t)stream, d_hit_id, d_t, d_rgb_linear, d_rgb8, false); });
 }
 int srt_shade_rays(srt_scene* s, uint32_t n, const float* rays, const srt_params* p, int32_t* hit_id, float* t, float* rgb_linear, uint8_t* rgb8,
                    srt_stats* stats) {
-    return guarded([&] { return shade_rays_impl(s, n, rays, p, hit_id, t, rgb_linear, rgb8, stats); });
+    return guarded([&] { return shade_rays_impl(s, n, rays, nullptr, p, hit_id, t, rgb_linear, rgb8, stats); });
+}
+int srt_shade_rays_range(srt_scene* s, uint32_t n, const float* rays, const float* t_range, const srt_params* p, int32_t* hit_id, float* t, float* rgb_linear,
+                         uint8_t* rgb8, srt_stats* stats) {
+    return guarded([&] { return shade_rays_impl(s, n, rays, t_range, p, hit_id, t, rgb_linear, rgb8, stats); });
 }
 
 void* srt_host_alloc(size_t bytes) {

@@ -325,6 +325,8 @@ __global__ __launch_bounds__(256) void k_query_any(DevScene s, uint32_t n_rays, 
 // and ORs the answer into the hit's 64-bit word in LDS.  After a chunk every hit's own lane adds the chunk's samples with the chunk's
 // mask (add_light_samples).  A wave with 3 hits and 16 samples so keeps 48 lanes walking where one lane per ray would keep 3.
 // The surface (surface_at) is fetched once per hit, before the first chunk; the pixel leaves through store_pixel.
+// RANGE (srt_shade_rays_range): phase 1 keeps the closest candidate in range of the ray's own interval tr, as k_query_closest<.., true> does;
+// phase 2 is the same code on that hit -- the origin is not moved, the shadow rays stay unbounded.
 // counters: as k_query_closest's, and [3] / [4] node / triangle tests of the shadow rays (COUNT).
 // =================================================================================================
 struct QueryShade {
@@ -335,13 +337,13 @@ struct QueryShade {
     uint32_t spread;              // a wave owns 8 groups of 8 consecutive rays, the groups a 64th of the batch apart, instead of 64 consecutive rays
 };
 
-template <bool COUNT, bool SMOOTH, bool INT_SHIN>
+template <bool COUNT, bool SMOOTH, bool INT_SHIN, bool RANGE>
 __global__ __launch_bounds__(256) void k_query_shade(DevScene s, uint32_t n_rays, const float* __restrict__ rays, uint32_t wide, QueryShade p,
                                                      int32_t* __restrict__ hit_id, float* __restrict__ t_out, float* __restrict__ rgb_linear,
-                                                     uint8_t* __restrict__ rgb8, unsigned long long* __restrict__ counters) {
+                                                     uint8_t* __restrict__ rgb8, unsigned long long* __restrict__ counters, QueryRange tr) {
     __shared__ uint32_t q_all[4][QCAP];
     __shared__ unsigned long long best_all[256];
-    __shared__ float ray_all[4][6][64];
+    __shared__ float ray_all[4][RANGE ? 8 : 6][64];
     const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     unsigned long long* best = best_all + wave * 64;
     float (*wray)[64] = ray_all[wave];
@@ -353,8 +355,10 @@ __global__ __launch_bounds__(256) void k_query_shade(DevScene s, uint32_t n_rays
     const bool live = ri < (size_t)n_rays;
     unsigned long long n_node = 0, n_tri = 0, n_node_s = 0, n_tri_s = 0;
     V3 o = mk(0.0f, 0.0f, 0.0f), d = mk(0.0f, 0.0f, 1.0f);
+    float t_min = 0.0f, t_max = 0.0f;
     if (live) load_ray(rays, ri, wide != 0, o, d);
-    query_walk<COUNT, false>(s, live, o, d, lane, q_all[wave], MergeClosest{ best }, wray, n_node, n_tri);
+    if (RANGE && live) load_range(tr, ri, t_min, t_max);
+    query_walk<COUNT, RANGE>(s, live, o, d, lane, q_all[wave], MergeClosest{ best }, wray, n_node, n_tri, t_min, t_max);
     const unsigned long long key = live ? best[lane] : ~0ull;
     const bool is_hit = key != ~0ull;
     const int32_t id = is_hit ? (int32_t)(uint32_t)key : -1;
@@ -367,7 +371,7 @@ __global__ __launch_bounds__(256) void k_query_shade(DevScene s, uint32_t n_rays
     if (is_hit) {
         V3 p1, e1, e2;
         load_tri_edges(reinterpret_cast<const float4*>(s.tris), (size_t)id, p1, e1, e2);
-        t = ray_triangle(o, d, p1, e1, e2);             // the winner's t with its own bits (incl. the sign of a zero)
+        t = ray_triangle(o, d, p1, e1, e2);             // the winner's t with its own bits (incl. the sign of a zero); the walk's value, hence in range
         const V3 P = o + d * t;                         // shadowIntersection:325-326 in camera mode: so = o + d * t
         const int2 self = s.obj_range[s.tri_obj[id]];
         wray[0][rank] = P.x; wray[1][rank] = P.y; wray[2][rank] = P.z;

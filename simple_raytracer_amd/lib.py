@@ -23,7 +23,7 @@ ABI_SYMBOLS = ("srt_params_default", "srt_light_staircase", "srt_rows_owned", "s
                "srt_scene_pipeline", "srt_scene_overlap_estimate", "srt_scene_set_pose_source", "srt_scene_pose",
                "srt_trace_rays_device", "srt_trace_rays", "srt_occluded_device", "srt_occluded", "srt_shade_rays_device", "srt_shade_rays",
                "srt_trace_rays_range_device", "srt_trace_rays_range", "srt_occluded_range_device", "srt_occluded_range",
-               "srt_trace_rays_multi_device", "srt_trace_rays_multi")
+               "srt_trace_rays_multi_device", "srt_trace_rays_multi", "srt_shade_rays_range_device", "srt_shade_rays_range")
 MULTI_HIT_MAX = 16                # SRT_MULTI_HIT_MAX
 
 _f32p, _i32p, _u8p, _u32p = C.POINTER(C.c_float), C.POINTER(C.c_int32), C.POINTER(C.c_uint8), C.POINTER(C.c_uint32)
@@ -111,6 +111,11 @@ def load():
         L.srt_shade_rays_device.restype = C.c_int
         L.srt_shade_rays.argtypes = [C.c_void_p, C.c_uint32, _f32p, C.POINTER(abi.Params), _i32p, _f32p, _f32p, _u8p, C.POINTER(abi.Stats)]
         L.srt_shade_rays.restype = C.c_int
+        L.srt_shade_rays_range_device.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(abi.Params), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                  C.c_void_p]
+        L.srt_shade_rays_range_device.restype = C.c_int
+        L.srt_shade_rays_range.argtypes = [C.c_void_p, C.c_uint32, _f32p, _f32p, C.POINTER(abi.Params), _i32p, _f32p, _f32p, _u8p, C.POINTER(abi.Stats)]
+        L.srt_shade_rays_range.restype = C.c_int
         L.srt_strerror.argtypes = [C.c_int]
         L.srt_strerror.restype = C.c_char_p
         L.srt_last_hip_error.restype = C.c_int
@@ -352,12 +357,14 @@ class DeviceScene:
         _check(self.L.srt_trace_rays_multi_device(self.h, n, C.c_void_p(rays), C.c_void_p(t_range or 0), k, flags, C.c_void_p(stream), C.c_void_p(n_hits),
                                                   C.c_void_p(hit_id), C.c_void_p(t), C.c_void_p(bary)), "srt_trace_rays_multi_device")
 
-    def shade_rays(self, rays, params: abi.Params, want=("hit_id", "t", "rgb_linear", "rgb8"), count=False):
+    def shade_rays(self, rays, params: abi.Params, want=("hit_id", "t", "rgb_linear", "rgb8"), count=False, t_range=None):
         """srt_shade_rays: the colour that comes back along every ray of `rays` (n x 6, host array) under the lights, literals and flags
         of `params` (its frame geometry is ignored).  Returns a dict of the arrays named in `want` (hit_id n, t n, rgb_linear n x 3,
-        rgb8 n x 3) + 'stats'; count=True adds SRT_FLAG_COUNT_WORK for this call."""
+        rgb8 n x 3) + 'stats'; count=True adds SRT_FLAG_COUNT_WORK for this call.
+        t_range (n x 2: t_min, t_max per ray): srt_shade_rays_range, the colour of the closest hit inside each ray's closed interval."""
         r = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
         n = r.shape[0]
+        tr = _t_range(t_range, n)
         out = {}
         if "hit_id" in want: out["hit_id"] = np.empty(n, np.int32)
         if "t" in want: out["t"] = np.empty(n, np.float32)
@@ -368,19 +375,27 @@ class DeviceScene:
         flags = params.flags
         if count: params.flags = flags | abi.SRT_FLAG_COUNT_WORK
         try:
-            rc = self.L.srt_shade_rays(self.h, n, r.ctypes.data_as(_f32p), C.byref(params), g("hit_id", _i32p), g("t", _f32p), g("rgb_linear", _f32p),
-                                       g("rgb8", _u8p), C.byref(st))
+            if tr is None:
+                rc = self.L.srt_shade_rays(self.h, n, r.ctypes.data_as(_f32p), C.byref(params), g("hit_id", _i32p), g("t", _f32p), g("rgb_linear", _f32p),
+                                           g("rgb8", _u8p), C.byref(st))
+            else:
+                rc = self.L.srt_shade_rays_range(self.h, n, r.ctypes.data_as(_f32p), tr.ctypes.data_as(_f32p), C.byref(params), g("hit_id", _i32p), g("t", _f32p),
+                                                 g("rgb_linear", _f32p), g("rgb8", _u8p), C.byref(st))
         finally:
             params.flags = flags
-        _check(rc, "srt_shade_rays")
+        _check(rc, "srt_shade_rays" if tr is None else "srt_shade_rays_range")
         out["stats"] = st.as_dict()
         return out
 
-    def shade_rays_device(self, n, rays, params: abi.Params, stream=0, hit_id=0, t=0, rgb_linear=0, rgb8=0):
+    def shade_rays_device(self, n, rays, params: abi.Params, stream=0, hit_id=0, t=0, rgb_linear=0, rgb8=0, t_range=None):
         """srt_shade_rays_device: raw device pointers (ints, e.g. torch.Tensor.data_ptr()) in, asynchronous on `stream`; the light table
-        of `params` is a host array."""
-        _check(self.L.srt_shade_rays_device(self.h, n, C.c_void_p(rays), C.byref(params), C.c_void_p(stream), C.c_void_p(hit_id), C.c_void_p(t),
-                                            C.c_void_p(rgb_linear), C.c_void_p(rgb8)), "srt_shade_rays_device")
+        of `params` is a host array.  t_range (a device pointer to n x 2 floats): srt_shade_rays_range_device."""
+        if t_range is None:
+            _check(self.L.srt_shade_rays_device(self.h, n, C.c_void_p(rays), C.byref(params), C.c_void_p(stream), C.c_void_p(hit_id), C.c_void_p(t),
+                                                C.c_void_p(rgb_linear), C.c_void_p(rgb8)), "srt_shade_rays_device")
+        else:
+            _check(self.L.srt_shade_rays_range_device(self.h, n, C.c_void_p(rays), C.c_void_p(t_range), C.byref(params), C.c_void_p(stream), C.c_void_p(hit_id),
+                                                      C.c_void_p(t), C.c_void_p(rgb_linear), C.c_void_p(rgb8)), "srt_shade_rays_range_device")
 
     def sync(self):
         st = abi.Stats()

@@ -15,7 +15,10 @@ calls, the forms alternating within a round, with the rounds' minimum and maximu
 --multi: instead, the K nearest hits in one walk (srt_trace_rays_multi_device) on the same frame's rays in the three orders: k = 1, 4, 8
 and 16 without an interval beside srt_trace_rays_range_device with (0, +inf) on the same rays in the same rounds; k hits by the next_up
 chain of k range calls (t_min made on the device with torch.nextafter) beside the one multi call; the host forms end to end at k = 4.
-Usage: python tools/ray_query_probe.py [--reps N] [--trace] [--shade | --range | --multi [--rounds R]]     (--trace: few repetitions, for a run under rocprofv3 --kernel-trace --stats)"""
+--shade-range: instead, what the interval costs the shaded query (srt_shade_rays_range_device) on the same frame's rays, row-major and
+shuffled, at 1 and 16 light samples: the unbounded srt_shade_rays_device beside the range call with (0, +inf) -- the same bytes -- and
+with t_min just behind the frame's hit (next_up(t): the colour at the exit point / behind the first surface), in the same rounds.
+Usage: python tools/ray_query_probe.py [--reps N] [--trace] [--shade | --range | --shade-range | --multi [--rounds R]]     (--trace: few repetitions, for a run under rocprofv3 --kernel-trace --stats)"""
 import argparse, os, sys, time
 import numpy as np
 import torch                                   # first: torch initialises HIP before the library does
@@ -54,6 +57,23 @@ def timed(fn, reps, stream):
         fn()
     b.record(stream); stream.synchronize()
     return a.elapsed_time(b) / reps
+
+
+def rounds_of(forms, reps, rounds, stream):
+    """forms: name -> call.  Per form the ms a call of every round (the forms alternate within a round)."""
+    ms = {k: [] for k in forms}
+    for _ in range(rounds):
+        for k, fn in forms.items():
+            ms[k].append(timed(fn, reps, stream))
+    return ms
+
+
+def report(title, ms, yard=None):
+    """One line per form: median, minimum and maximum of its rounds, and the median over the median of form `yard` (default: the first)."""
+    med = {k: float(np.median(v)) for k, v in ms.items()}
+    yard = next(iter(med)) if yard is None else yard
+    for k, v in ms.items():
+        print(f"{title:34s} {k:34s} {med[k]:8.3f} {min(v):8.3f} {max(v):8.3f} {med[k] / med[yard]:7.3f}")
 
 
 def shade_section(reps):
@@ -115,19 +135,6 @@ def range_section(reps, rounds):
     t_med = np.float32(np.median(t_ref[sel]))
     hit = torch.empty(n, dtype=torch.int32, device=dev); t = torch.empty(n, dtype=torch.float32, device=dev)
 
-    def rounds_of(forms):
-        """forms: name -> call.  Per form the ms a call of every round (the forms alternate within a round)."""
-        ms = {k: [] for k in forms}
-        for _ in range(rounds):
-            for k, fn in forms.items():
-                ms[k].append(timed(fn, reps, side))
-        return ms
-
-    def report(title, ms, yard):
-        med = {k: float(np.median(v)) for k, v in ms.items()}
-        for k, v in ms.items():
-            print(f"{title:34s} {k:34s} {med[k]:8.3f} {min(v):8.3f} {max(v):8.3f} {med[k] / med[yard]:7.3f}")
-
     print(f"t interval, K3 ground_bunny {W}x{H}: {n} rays, {int(sel.sum())} hits, median hit t {t_med:.6g}; {rounds} rounds of {reps} calls, forms alternating; ms a call")
     print(f"{'rays':34s} {'form':34s} {'median':>8s} {'min':>8s} {'max':>8s} {'/ first':>7s}")
     for name, order in (("closest hit, row-major", np.arange(n)), ("closest hit, shuffled", np.random.default_rng(1).permutation(n))):
@@ -136,7 +143,7 @@ def range_section(reps, rounds):
         d_far = torch.from_numpy(np.tile(np.array([0.0, t_med], np.float32), (n, 1))).to(dev)
         torch.cuda.synchronize()
         call = lambda tr: (lambda: ds.trace_rays_device(n, d_rays.data_ptr(), stream=cur, hit_id=hit.data_ptr(), t=t.data_ptr(), t_range=tr))
-        ms = rounds_of({"unbounded": call(None), "range (0, +inf)": call(d_open.data_ptr()), "range (0, median hit t)": call(d_far.data_ptr())})
+        ms = rounds_of({"unbounded": call(None), "range (0, +inf)": call(d_open.data_ptr()), "range (0, median hit t)": call(d_far.data_ptr())}, reps, rounds, side)
         report(name, ms, "unbounded")
         # what the forms answer: (0, +inf) the frame, (0, median) the frame's hits up to the median and misses beyond
         call(d_open.data_ptr())(); side.synchronize()
@@ -157,7 +164,7 @@ def range_section(reps, rounds):
         d_seg = torch.from_numpy(np.tile(np.float32([0.0, 1.0]), (m, 1))).to(dev)
         torch.cuda.synchronize()
         call = lambda tr: (lambda: ds.occluded_device(m, d_s.data_ptr(), occ.data_ptr(), skip_obj=d_k.data_ptr(), stream=cur, t_range=tr))
-        ms = rounds_of({"unbounded": call(None), "range (0, +inf)": call(d_open.data_ptr()), "range (0, 1): segments": call(d_seg.data_ptr())})
+        ms = rounds_of({"unbounded": call(None), "range (0, +inf)": call(d_open.data_ptr()), "range (0, 1): segments": call(d_seg.data_ptr())}, reps, rounds, side)
         report(name, ms, "unbounded")
         counts = []
         for tr in (None, d_open.data_ptr(), d_seg.data_ptr()):
@@ -165,6 +172,43 @@ def range_section(reps, rounds):
             counts.append(int(occ.sum().item()))
         print(f"{'':34s} occluded of {m}: unbounded {counts[0]}, (0, +inf) {counts[1]}, (0, 1) {counts[2]}")
         assert counts[0] == counts[1] >= counts[2]
+
+
+def shade_range_section(reps, rounds):
+    dev = torch.device("cuda", 0); torch.zeros(1, device=dev)
+    g = gu.GoldenScene("ground_bunny")
+    ds = lib.DeviceScene(g.flat)
+    side = torch.cuda.Stream(device=dev)
+    cur = side.cuda_stream
+    rays = frame_rays()
+    n = rays.shape[0]
+    frame = ds.render(g.params(W, H, 1), want=("hit_id", "t"))
+    hit_ref, t_ref = frame["hit_id"].reshape(-1), frame["t"].reshape(-1)
+    behind = np.stack([np.nextafter(t_ref, np.float32(np.inf)), np.full(n, np.inf, np.float32)], axis=1).astype(np.float32)      # a miss: (inf, inf)
+    hit = torch.empty(n, dtype=torch.int32, device=dev); t = torch.empty(n, dtype=torch.float32, device=dev)
+    lin = torch.empty((n, 3), dtype=torch.float32, device=dev); rgb8 = torch.empty((n, 3), dtype=torch.uint8, device=dev)
+    print(f"shaded rays with a t interval, K3 ground_bunny {W}x{H}: {n} rays, {int((hit_ref >= 0).sum())} hits; {rounds} rounds of {reps} calls, forms alternating; ms a call")
+    print(f"{'samples, rays':34s} {'form':34s} {'median':>8s} {'min':>8s} {'max':>8s} {'/ first':>7s}")
+    for L in (1, 16):
+        p = abi.make_params(1, 1, abi.light_staircase(g.light, L))
+        for name, order in (("row-major", np.arange(n)), ("shuffled", np.random.default_rng(1).permutation(n))):
+            d_rays = torch.from_numpy(np.ascontiguousarray(rays[order])).to(dev)
+            d_open = torch.from_numpy(np.tile(np.float32([0.0, np.inf]), (n, 1))).to(dev)
+            d_behind = torch.from_numpy(np.ascontiguousarray(behind[order])).to(dev)
+            torch.cuda.synchronize()
+            call = lambda tr: (lambda: ds.shade_rays_device(n, d_rays.data_ptr(), p, stream=cur, hit_id=hit.data_ptr(), t=t.data_ptr(), rgb_linear=lin.data_ptr(),
+                                                            rgb8=rgb8.data_ptr(), t_range=tr))
+            forms = {"unbounded": call(None), "range (0, +inf)": call(d_open.data_ptr()), "range (next_up(t), +inf)": call(d_behind.data_ptr())}
+            report(f"{L:2d} samples, {name}", rounds_of(forms, reps, rounds, side))
+            # what the forms answer: (0, +inf) the unbounded call's bytes; behind the first hit another triangle or nothing
+            got = []
+            for tr in (None, d_open.data_ptr(), d_behind.data_ptr()):
+                call(tr)(); side.synchronize()
+                got.append((hit.cpu().numpy(), t.cpu().numpy().view(np.uint32), lin.cpu().numpy().view(np.uint32), rgb8.cpu().numpy()))
+            assert np.array_equal(got[0][0], hit_ref[order]) and all(np.array_equal(a, b) for a, b in zip(got[0], got[1]))
+            second = got[2][0]
+            assert ((second < 0) | (second != got[0][0])).all()
+            print(f"{'':34s} hits: unbounded {int((got[0][0] >= 0).sum())}, behind the first hit {int((second >= 0).sum())}")
 
 
 def multi_section(reps, rounds):
@@ -185,19 +229,6 @@ def multi_section(reps, rounds):
     print(f"K nearest hits, K3 ground_bunny {W}x{H}: {n} rays; {rounds} rounds of {reps} calls, forms alternating; ms a call (n_hits, hit_id, t written)")
     print(f"{'rays':34s} {'form':34s} {'median':>8s} {'min':>8s} {'max':>8s} {'/ first':>7s}")
 
-    def rounds_of(forms):
-        ms = {k: [] for k in forms}
-        for _ in range(rounds):
-            for k, fn in forms.items():
-                ms[k].append(timed(fn, reps, side))
-        return ms
-
-    def report(title, ms):
-        med = {k: float(np.median(v)) for k, v in ms.items()}
-        yard = next(iter(med))
-        for k, v in ms.items():
-            print(f"{title:34s} {k:34s} {med[k]:8.3f} {min(v):8.3f} {max(v):8.3f} {med[k] / med[yard]:7.3f}")
-
     for name, order in (("(a) tile order", tile_order()), ("(b) row-major", np.arange(n)), ("(c) randomly permuted", np.random.default_rng(1).permutation(n))):
         d_rays = torch.from_numpy(np.ascontiguousarray(rays[order])).to(dev)
         torch.cuda.synchronize()
@@ -205,7 +236,7 @@ def multi_section(reps, rounds):
         multi = lambda k: (lambda: ds.trace_rays_multi_device(n, d_rays.data_ptr(), k, stream=cur, n_hits=cnt.data_ptr(), hit_id=mhit.data_ptr(), t=mt.data_ptr()))
         forms = {"range (0, +inf)": rng_call}
         forms.update({f"multi k = {k}": multi(k) for k in KS})
-        report(name, rounds_of(forms))
+        report(name, rounds_of(forms, reps, rounds, side))
         # column 0 of the multi call is the range call
         rng_call(); multi(8)(); side.synchronize()
         assert torch.equal(mhit[:n * 8].view(n, 8)[:, 0], hit) and torch.equal(mt[:n * 8].view(n, 8)[:, 0].view(torch.int32), t.view(torch.int32))
@@ -225,7 +256,7 @@ def multi_section(reps, rounds):
                             d_tr[:, 0] = torch.where(hit >= 0, torch.nextafter(t, inf), inf)
             return run
         for k in (4, 8):
-            report(f"{k} hits, row-major", rounds_of({f"multi k = {k}, one call": multi(k), f"next_up chain, {k} range calls": chain(k)}))
+            report(f"{k} hits, row-major", rounds_of({f"multi k = {k}, one call": multi(k), f"next_up chain, {k} range calls": chain(k)}, reps, rounds, side))
     # the host forms, end to end (staging, wait, copies back)
     r = np.ascontiguousarray(rays)
     tr = np.tile(np.float32([0.0, np.inf]), (n, 1))
@@ -248,6 +279,7 @@ def main():
     ap.add_argument("--trace", action="store_true")
     ap.add_argument("--shade", action="store_true")
     ap.add_argument("--range", action="store_true", dest="t_range")
+    ap.add_argument("--shade-range", action="store_true", dest="shade_range")
     ap.add_argument("--multi", action="store_true")
     ap.add_argument("--rounds", type=int, default=7)
     a = ap.parse_args()
@@ -256,6 +288,8 @@ def main():
         return multi_section(reps, 2 if a.trace else a.rounds)
     if a.shade:
         return shade_section(reps)
+    if a.shade_range:
+        return shade_range_section(reps, 2 if a.trace else a.rounds)
     if a.t_range:
         return range_section(reps, 2 if a.trace else a.rounds)
     dev = torch.device("cuda", 0); torch.zeros(1, device=dev)
