@@ -482,6 +482,54 @@ int srt_shade_rays_range_device(srt_scene* s, uint32_t n, const float* d_rays, c
 int srt_shade_rays_range(srt_scene* s, uint32_t n, const float* rays, const float* t_range, const srt_params* p,
                          int32_t* hit_id, float* t, float* rgb_linear, uint8_t* rgb8, srt_stats* stats);
 
+/* The surface at a hit, and the reflected ray: WHAT is there -- the normal, the owning object, the colour and the material shading would
+ * use -- and the mirrored ray, ready to go back into any _range query: a multi-bounce mirror, a deferred shader, a normal or albedo probe
+ * on device arrays, with no copy of the geometry on the caller's side.  srt_surface_rays finds the hit itself; srt_surface_hits takes hits
+ * the caller already holds (a render's hit_id / t with the frame's rays, any column of srt_trace_rays_multi) and walks nothing.
+ * Unless said here everything is as for srt_trace_rays_range: the layout of rays and t_range with wide loads where they are 8-byte aligned,
+ * a NULL t_range, the ordering on `stream`, the rules of srt_scene_share, n == 0, the private counter set, what the host form stages (through
+ * the handle's pinned block), waits for and reports in *stats -- primary_rays = n, hit_rays, and under SRT_FLAG_COUNT_WORK the
+ * node_tests_primary / tri_tests_primary of the unbounded srt_trace_rays on the same rays --, hipGraph capture of the _device form without
+ * SRT_FLAG_COUNT_WORK, as one launch.
+ * DEFINITION (srt_surface_rays).
+ *   hit_id, t   bit for bit what srt_trace_rays_range gives for that ray and interval (the candidate set, the range rule, the ties, the
+ *               winner's own t bits, the four identity intervals); a NULL t_range gives srt_trace_rays' bits.
+ *   the fields of srt_surface_out, any of which may be NULL: exactly what srt_shade_rays(_range) shades that hit with.  Neither the origin nor
+ *               the normal is moved or flipped.
+ *   bounce      origin = point; direction r, in f32 without contraction, with N the `normal` output:
+ *                   k = (d.x * N.x + d.y * N.y) + d.z * N.z        r_i = d_i - (N_i * k) * 2
+ *               glm::reflect's association; the same under N -> -N, so it needs no orientation.  d is not normalised, and neither is r.
+ *   A miss:     hit_id -1, t +inf, obj -1, every float output 0, the six of bounce included.  When feeding bounce back into a _range query
+ *               give such rays the interval (1, 0): t_min > t_max is a miss by definition.  For the hits, t_min a little above 0 keeps the
+ *               ray off the surface it starts on; the origin is not moved.
+ *   Degenerate triangles and non-finite rays give whatever the stated arithmetic gives; the call stays memory-safe.
+ * out == NULL, or every field of it NULL: the call IS srt_trace_rays_range without bary, and launches that kernel.
+ * Flags: 0, SRT_FLAG_COUNT_WORK, SRT_FLAG_SMOOTH_NORMALS or both; SRT_FLAG_SMOOTH_NORMALS on a scene without normals fails as
+ * srt_shade_rays does (SRT_ERR_ARG); any other bit: SRT_ERR_ARG.  Errors are checked before anything is touched.
+ * DEFINITION (srt_surface_hits).  Row i is a miss row (as above) if hit_id[i] is outside [0, n_tris); otherwise it is the surface of triangle
+ * hit_id[i] where the ray o_i + d_i * t[i] meets it, and the fields above.  t is taken as given and not validated (the texel index is
+ * clamped into the image, so any t is memory-safe); no node record is read.  Identity: fed the hit_id / t that srt_surface_rays returned for
+ * the same rays and flags, every field equals that call's bit for bit.  Flags: 0 or SRT_FLAG_SMOOTH_NORMALS; there is no stats and no
+ * counter set.  rays, hit_id or t NULL with n > 0: SRT_ERR_ARG.  One launch; it may be captured into a hipGraph.  With out NULL, or every
+ * field of it NULL, the call checks its arguments and launches nothing. */
+typedef struct srt_surface_out {   /* device pointers in the _device forms, host pointers in the host forms; any may be NULL */
+    int32_t* obj;        /* n      owning object (tri_obj of the hit); -1 on a miss                                    */
+    float*   point;      /* n x 3  o + d * t, per component one multiply and one add, no contraction                   */
+    float*   normal;     /* n x 3  the normal Phong is given for this hit: the record's face normal                    */
+                         /*        (calculateTriangleNormal:32-37), or interpolateNormal's under SRT_FLAG_SMOOTH_NORMALS */
+    float*   color;      /* n x 3  the colour shading uses: the object's, or the texel (softShadow:350-361, clamped)   */
+    float*   material;   /* n x 3  ambient, specularStrength, shininess of the object                                  */
+    float*   bounce;     /* n x 6  the mirrored ray: origin = point, direction = r (above)                             */
+} srt_surface_out;
+int srt_surface_rays_device(srt_scene* s, uint32_t n, const float* d_rays, const float* d_t_range /* n x 2 or NULL */,
+                            uint32_t flags, void* stream, int32_t* d_hit_id, float* d_t, const srt_surface_out* out);
+int srt_surface_rays(srt_scene* s, uint32_t n, const float* rays, const float* t_range, uint32_t flags,
+                     int32_t* hit_id, float* t, const srt_surface_out* out, srt_stats* stats);
+int srt_surface_hits_device(srt_scene* s, uint32_t n, const float* d_rays, const int32_t* d_hit_id, const float* d_t,
+                            uint32_t flags, void* stream, const srt_surface_out* out);
+int srt_surface_hits(srt_scene* s, uint32_t n, const float* rays, const int32_t* hit_id, const float* t,
+                     uint32_t flags, const srt_surface_out* out);
+
 /* Device-resident size of the scene records and the per-record algorithmic byte sizes used by
  * the bytes model: 32 B per node test, 36 B per triangle test. */
 uint64_t srt_scene_device_bytes(const srt_scene* s);

@@ -74,6 +74,17 @@ class Stats(C.Structure):
         return d
 
 
+class SurfaceOut(C.Structure):
+    """srt_surface_out: the arrays a surface query fills, as addresses (host arrays in the host forms, device pointers in the _device
+    forms); 0 = not wanted."""
+    _fields_ = [("obj", C.c_void_p), ("point", C.c_void_p), ("normal", C.c_void_p), ("color", C.c_void_p), ("material", C.c_void_p), ("bounce", C.c_void_p)]
+
+
+# the fields of srt_surface_out: name -> (dtype, floats or ints per ray)
+SURFACE_FIELDS = {"obj": (np.int32, 1), "point": (np.float32, 3), "normal": (np.float32, 3), "color": (np.float32, 3), "material": (np.float32, 3),
+                  "bounce": (np.float32, 6)}
+
+
 def _ptr(a, ty):
     return a.ctypes.data_as(ty) if a is not None else ty()
 

@@ -137,8 +137,27 @@ def build_diag(verbose=False):
     return out
 
 
+LIB_SURFACE_LANE = os.path.join(HERE, "libsrt_hip_surface_lane.so")
+
+
+def build_surface_lane_stores(force=False):
+    """The surface kernels' other store form (-DSRT_SURFACE_LANE_STORES, srt_query.h): libsrt_hip_surface_lane.so, never loaded by the
+    product; tools/ray_query_probe.py --surface times it beside the shipped library."""
+    deps = [os.path.join(CSRC, f) for f in ("srt_hip.hip", "srt_device.h", "srt_kernels.h", "srt_packet.h", "srt_query.h")] + [os.path.join(HERE, "..", "include", "srt.h")]
+    if not force and not _stale(LIB_SURFACE_LANE, deps):
+        return LIB_SURFACE_LANE
+    cmd = [hipcc()] + HIPCC_FLAGS + ["-DSRT_SURFACE_LANE_STORES", "-o", LIB_SURFACE_LANE, os.path.join(CSRC, "srt_hip.hip")]
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    if r.returncode:
+        sys.stderr.write(r.stdout + r.stderr)
+        raise RuntimeError("hipcc failed for the lane-stores build")
+    return LIB_SURFACE_LANE
+
+
 if __name__ == "__main__":
     if "--diag" in sys.argv:
         print(build_diag(verbose=True))
+    elif "--surface-lane-stores" in sys.argv:
+        print(build_surface_lane_stores())
     else:
         build_all(force="--force" in sys.argv, verbose=True)

@@ -163,6 +163,8 @@ struct srt_scene {
     // srt_shade_rays: the query's own result buffers and its own light table (a render's d_lights may be in use on another stream): the
     // pinned copy, the event behind its last upload, the stream that upload went to, and whether it is known to have arrived
     DevArray<float, 3> rq_lin; DevArray<uint8_t, 3> rq_rgb8;
+    // srt_surface_rays / srt_surface_hits: the six arrays of srt_surface_out, and the t of the hits a caller brings (their ids go through rq_skip)
+    DevArray<int32_t> rq_sobj; DevArray<float, 3> rq_spoint, rq_snormal, rq_scolor, rq_smat; DevArray<float, 6> rq_sbounce; DevArray<float> rq_tin;
     DevArray<float, 3> d_qlights; Pinned<float, 3> h_qlights; uint32_t qlights_valid = 0;
     Event qlights_sent; hipStream_t qlights_stream = nullptr; bool qlights_settled = true;
     int n_cu = 256;
@@ -1666,14 +1668,59 @@ static int shade_rays_device_impl(srt_scene* s, uint32_t n, const float* d_rays,
     return SRT_OK;
 }
 
+// srt_surface_rays / srt_surface_hits: the surface under each hit and the mirrored ray (k_query_surface, k_query_surface_hits)
+static int check_surface(const srt_scene* s, uint32_t n, const float* rays, uint32_t flags, uint32_t allowed) {
+    if (!s || (n && !rays) || (flags & ~allowed)) return SRT_ERR_ARG;
+    if ((flags & SRT_FLAG_SMOOTH_NORMALS) && !s->dev.tri_normals) return SRT_ERR_ARG;      // needs vertex normals, as check_shade
+    return SRT_OK;
+}
+static inline bool surface_wanted(const srt_surface_out* o) { return o && (o->obj || o->point || o->normal || o->color || o->material || o->bounce); }
+
+static int surface_rays_device_impl(srt_scene* s, uint32_t n, const float* d_rays, const float* d_t_range, uint32_t flags, hipStream_t stream, int32_t* d_hit_id,
+                                    float* d_t, const srt_surface_out* out, bool count_hits) {
+    SRT_TRY(check_surface(s, n, d_rays, flags, SRT_FLAG_COUNT_WORK | SRT_FLAG_SMOOTH_NORMALS));
+    // nothing of the surface wanted: the call is srt_trace_rays_range without bary, and launches its kernel
+    if (!surface_wanted(out)) return trace_rays_device_impl(s, n, d_rays, d_t_range, flags & SRT_FLAG_COUNT_WORK, stream, d_hit_id, d_t, nullptr, count_hits);
+    if (!n) return SRT_OK;
+    const bool count = (flags & SRT_FLAG_COUNT_WORK) != 0, smooth = (flags & SRT_FLAG_SMOOTH_NORMALS) != 0;
+    QueryLaunch q;
+    SRT_TRY(query_prologue(s, n, stream, nullptr, count || count_hits, &q));
+    static const decltype(&k_query_surface<false, false, false>) builds[8] = {
+        &k_query_surface<false, false, false>, &k_query_surface<false, true, false>, &k_query_surface<true, false, false>, &k_query_surface<true, true, false>,
+        &k_query_surface<false, false, true>,  &k_query_surface<false, true, true>,  &k_query_surface<true, false, true>,  &k_query_surface<true, true, true> };
+    hipLaunchKernelGGL(builds[(d_t_range ? 4 : 0) | (count ? 2 : 0) | (smooth ? 1 : 0)], q.grid, dim3(256), 0, q.stream, s->dev, n, d_rays, rays_wide(d_rays), d_hit_id, d_t,
+                       *out, q.ctr, query_range(d_t_range));
+    HIP_TRY(hipGetLastError());
+    return SRT_OK;
+}
+
+static int check_surface_hits(const srt_scene* s, uint32_t n, const float* rays, const int32_t* hit_id, const float* t, uint32_t flags) {
+    SRT_TRY(check_surface(s, n, rays, flags, SRT_FLAG_SMOOTH_NORMALS));
+    return (n && (!hit_id || !t)) ? SRT_ERR_ARG : SRT_OK;
+}
+static int surface_hits_device_impl(srt_scene* s, uint32_t n, const float* d_rays, const int32_t* d_hit_id, const float* d_t, uint32_t flags, hipStream_t stream,
+                                    const srt_surface_out* out) {
+    SRT_TRY(check_surface_hits(s, n, d_rays, d_hit_id, d_t, flags));
+    if (!n || !surface_wanted(out)) return SRT_OK;
+    QueryLaunch q;
+    SRT_TRY(query_prologue(s, n, stream, nullptr, false, &q));
+    hipLaunchKernelGGL((flags & SRT_FLAG_SMOOTH_NORMALS) ? &k_query_surface_hits<true> : &k_query_surface_hits<false>, q.grid, dim3(256), 0, q.stream, s->dev, n, d_rays,
+                       rays_wide(d_rays), d_hit_id, d_t, *out);
+    HIP_TRY(hipGetLastError());
+    return SRT_OK;
+}
+
 // The host entry points: the caller's rays go through the pinned staging block (stage_acquire, as every update does) into the handle's
 // own ray buffer on the scene's stream, the device entry point runs behind them, the call waits and copies the results out.
-static int stage_rays(srt_scene* s, uint32_t n, const float* rays, const float* t_range, const int32_t* skip_obj, hipStream_t st) {
+// skip_obj: n int32 a call brings -- the skipped objects of srt_occluded, the hit ids of srt_surface_hits; t_in: the t of those hits
+static int stage_rays(srt_scene* s, uint32_t n, const float* rays, const float* t_range, const int32_t* skip_obj, const float* t_in, hipStream_t st) {
     auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t o_rays = 0, o_skip = pad((size_t)n * 24), o_range = o_skip + (skip_obj ? pad((size_t)n * 4) : 0), total = o_range + (t_range ? pad((size_t)n * 8) : 0);
+    const size_t o_rays = 0, o_skip = pad((size_t)n * 24), o_range = o_skip + (skip_obj ? pad((size_t)n * 4) : 0), o_tin = o_range + (t_range ? pad((size_t)n * 8) : 0),
+                 total = o_tin + (t_in ? pad((size_t)n * 4) : 0);
     SRT_TRY(grow(s, n, s->rq_rays));
     if (skip_obj) SRT_TRY(grow(s, n, s->rq_skip));
     if (t_range) SRT_TRY(grow(s, n, s->rq_range));
+    if (t_in) SRT_TRY(grow(s, n, s->rq_tin));
     char* h = nullptr;
     SRT_TRY(stage_acquire(s, total, &h));
     std::memcpy(h + o_rays, rays, (size_t)n * 24);
@@ -1685,6 +1732,10 @@ static int stage_rays(srt_scene* s, uint32_t n, const float* rays, const float* 
     if (t_range) {
         std::memcpy(h + o_range, t_range, (size_t)n * 8);
         HIP_TRY(hipMemcpyAsync(s->rq_range, h + o_range, (size_t)n * 8, hipMemcpyHostToDevice, st));
+    }
+    if (t_in) {
+        std::memcpy(h + o_tin, t_in, (size_t)n * 4);
+        HIP_TRY(hipMemcpyAsync(s->rq_tin, h + o_tin, (size_t)n * 4, hipMemcpyHostToDevice, st));
     }
     HIP_TRY(hipEventRecord(s->staged, st));
     return SRT_OK;
@@ -1703,16 +1754,16 @@ template <typename T, size_t K>
 static QueryOut<T, K> query_out(T* host, DevArray<T, K>& dev, size_t per = 1) { return QueryOut<T, K>{ host, dev, per }; }
 
 // The round trip of a host query on the scene's own stream: grow the wanted result buffers, stage the rays (and what comes with them: t
-// intervals, skipped objects), launch(stream) -- the device entry point --, wait, copy each wanted array out.
+// intervals, skipped objects, the hits of srt_surface_hits), launch(stream) -- the device entry point --, wait, copy each wanted array out.
 template <typename Launch, typename... O>
-static int query_round_trip(srt_scene* s, uint32_t n, const float* rays, const float* t_range, const int32_t* skip_obj, Launch launch, const O&... outs) {
+static int query_round_trip(srt_scene* s, uint32_t n, const float* rays, const float* t_range, const int32_t* skip_obj, const float* t_in, Launch launch, const O&... outs) {
     HIP_TRY(hipSetDevice(s->device));
     hipStream_t st;
     SRT_TRY(own_stream(s, &st));
     int rc = SRT_OK;
     ((rc = (rc == SRT_OK && outs.host) ? grow(s, (size_t)n * outs.per, outs.dev) : rc), ...);
     SRT_TRY(rc);
-    SRT_TRY(stage_rays(s, n, rays, t_range, skip_obj, st));
+    SRT_TRY(stage_rays(s, n, rays, t_range, skip_obj, t_in, st));
     SRT_TRY(launch(st));
     HIP_TRY(hipStreamSynchronize(st));
     if (s->qlights_stream == st) s->qlights_settled = true;      // a light table sent on this stream has arrived
@@ -1742,7 +1793,7 @@ static int trace_rays_impl(srt_scene* s, uint32_t n, const float* rays, const fl
     if (stats) std::memset(stats, 0, sizeof(*stats));
     if (!n) return SRT_OK;
     const auto o_hit = query_out(hit_id, s->rq_hit); const auto o_t = query_out(t, s->rq_t); const auto o_bary = query_out(bary, s->rq_bary);
-    SRT_TRY(query_round_trip(s, n, rays, t_range, nullptr, [&](hipStream_t st) {
+    SRT_TRY(query_round_trip(s, n, rays, t_range, nullptr, nullptr, [&](hipStream_t st) {
         return trace_rays_device_impl(s, n, s->rq_rays, t_range ? s->rq_range.p : nullptr, flags, st, o_hit.wanted(), o_t.wanted(), o_bary.wanted(), true);
     }, o_hit, o_t, o_bary));
     return stats ? query_stats(s, n, 0, stats) : SRT_OK;
@@ -1755,7 +1806,7 @@ static int trace_rays_multi_impl(srt_scene* s, uint32_t n, const float* rays, co
     if (!n) return SRT_OK;
     const auto o_n = query_out(n_hits, s->rq_nhits); const auto o_hit = query_out(hit_id, s->rq_hit, k);
     const auto o_t = query_out(t, s->rq_t, k); const auto o_bary = query_out(bary, s->rq_bary, k);
-    SRT_TRY(query_round_trip(s, n, rays, t_range, nullptr, [&](hipStream_t st) {
+    SRT_TRY(query_round_trip(s, n, rays, t_range, nullptr, nullptr, [&](hipStream_t st) {
         return trace_rays_multi_device_impl(s, n, s->rq_rays, t_range ? s->rq_range.p : nullptr, k, flags, st, o_n.wanted(), o_hit.wanted(), o_t.wanted(), o_bary.wanted(),
                                             true);
     }, o_n, o_hit, o_t, o_bary));
@@ -1765,7 +1816,7 @@ static int trace_rays_multi_impl(srt_scene* s, uint32_t n, const float* rays, co
 static int occluded_impl(srt_scene* s, uint32_t n, const float* rays, const float* t_range, const int32_t* skip_obj, uint8_t* occluded) {
     SRT_TRY(check_query(s, n, rays, 0));
     if (!n || !occluded) return SRT_OK;
-    return query_round_trip(s, n, rays, t_range, skip_obj, [&](hipStream_t st) {
+    return query_round_trip(s, n, rays, t_range, skip_obj, nullptr, [&](hipStream_t st) {
         return occluded_device_impl(s, n, s->rq_rays, t_range ? s->rq_range.p : nullptr, skip_obj ? s->rq_skip.p : nullptr, st, s->rq_occ);
     }, query_out(occluded, s->rq_occ));
 }
@@ -1777,10 +1828,39 @@ static int shade_rays_impl(srt_scene* s, uint32_t n, const float* rays, const fl
     if (!n) return SRT_OK;
     const auto o_hit = query_out(hit_id, s->rq_hit); const auto o_t = query_out(t, s->rq_t);
     const auto o_lin = query_out(rgb_linear, s->rq_lin); const auto o_rgb8 = query_out(rgb8, s->rq_rgb8);
-    SRT_TRY(query_round_trip(s, n, rays, t_range, nullptr, [&](hipStream_t st) {
+    SRT_TRY(query_round_trip(s, n, rays, t_range, nullptr, nullptr, [&](hipStream_t st) {
         return shade_rays_device_impl(s, n, s->rq_rays, t_range ? s->rq_range.p : nullptr, p, st, o_hit.wanted(), o_t.wanted(), o_lin.wanted(), o_rgb8.wanted(), true);
     }, o_hit, o_t, o_lin, o_rgb8));
     return stats ? query_stats(s, n, p->n_lights, stats) : SRT_OK;
+}
+
+// The host forms of the surface queries: the caller's srt_surface_out names host arrays; `dev` names the handle's buffers for the wanted ones.
+static int surface_rays_impl(srt_scene* s, uint32_t n, const float* rays, const float* t_range, uint32_t flags, int32_t* hit_id, float* t, const srt_surface_out* out,
+                             srt_stats* stats) {
+    SRT_TRY(check_surface(s, n, rays, flags, SRT_FLAG_COUNT_WORK | SRT_FLAG_SMOOTH_NORMALS));
+    if (stats) std::memset(stats, 0, sizeof(*stats));
+    if (!n) return SRT_OK;
+    const srt_surface_out h = out ? *out : srt_surface_out{};
+    const auto o_hit = query_out(hit_id, s->rq_hit); const auto o_t = query_out(t, s->rq_t);
+    const auto o_obj = query_out(h.obj, s->rq_sobj); const auto o_pt = query_out(h.point, s->rq_spoint); const auto o_nrm = query_out(h.normal, s->rq_snormal);
+    const auto o_col = query_out(h.color, s->rq_scolor); const auto o_mat = query_out(h.material, s->rq_smat); const auto o_bnc = query_out(h.bounce, s->rq_sbounce);
+    SRT_TRY(query_round_trip(s, n, rays, t_range, nullptr, nullptr, [&](hipStream_t st) {
+        const srt_surface_out dev = { o_obj.wanted(), o_pt.wanted(), o_nrm.wanted(), o_col.wanted(), o_mat.wanted(), o_bnc.wanted() };
+        return surface_rays_device_impl(s, n, s->rq_rays, t_range ? s->rq_range.p : nullptr, flags, st, o_hit.wanted(), o_t.wanted(), &dev, true);
+    }, o_hit, o_t, o_obj, o_pt, o_nrm, o_col, o_mat, o_bnc));
+    return stats ? query_stats(s, n, 0, stats) : SRT_OK;
+}
+
+static int surface_hits_impl(srt_scene* s, uint32_t n, const float* rays, const int32_t* hit_id, const float* t, uint32_t flags, const srt_surface_out* out) {
+    SRT_TRY(check_surface_hits(s, n, rays, hit_id, t, flags));
+    if (!n || !surface_wanted(out)) return SRT_OK;
+    const srt_surface_out h = *out;
+    const auto o_obj = query_out(h.obj, s->rq_sobj); const auto o_pt = query_out(h.point, s->rq_spoint); const auto o_nrm = query_out(h.normal, s->rq_snormal);
+    const auto o_col = query_out(h.color, s->rq_scolor); const auto o_mat = query_out(h.material, s->rq_smat); const auto o_bnc = query_out(h.bounce, s->rq_sbounce);
+    return query_round_trip(s, n, rays, nullptr, hit_id, t, [&](hipStream_t st) {
+        const srt_surface_out dev = { o_obj.wanted(), o_pt.wanted(), o_nrm.wanted(), o_col.wanted(), o_mat.wanted(), o_bnc.wanted() };
+        return surface_hits_device_impl(s, n, s->rq_rays, s->rq_skip, s->rq_tin, flags, st, &dev);
+    }, o_obj, o_pt, o_nrm, o_col, o_mat, o_bnc);
 }
 
 int srt_trace_rays_device(srt_scene* s, uint32_t n, const float* d_rays, uint32_t flags, void* stream, int32_t* d_hit_id, float* d_t, float* d_bary) {
@@ -1831,6 +1911,22 @@ int srt_shade_rays(srt_scene* s, uint32_t n, const float* rays, const srt_params
 int srt_shade_rays_range(srt_scene* s, uint32_t n, const float* rays, const float* t_range, const srt_params* p, int32_t* hit_id, float* t, float* rgb_linear,
                          uint8_t* rgb8, srt_stats* stats) {
     return guarded([&] { return shade_rays_impl(s, n, rays, t_range, p, hit_id, t, rgb_linear, rgb8, stats); });
+}
+
+int srt_surface_rays_device(srt_scene* s, uint32_t n, const float* d_rays, const float* d_t_range, uint32_t flags, void* stream, int32_t* d_hit_id, float* d_t,
+                            const srt_surface_out* out) {
+    return guarded([&] { return surface_rays_device_impl(s, n, d_rays, d_t_range, flags, (hipStream_t)stream, d_hit_id, d_t, out, false); });
+}
+int srt_surface_rays(srt_scene* s, uint32_t n, const float* rays, const float* t_range, uint32_t flags, int32_t* hit_id, float* t, const srt_surface_out* out,
+                     srt_stats* stats) {
+    return guarded([&] { return surface_rays_impl(s, n, rays, t_range, flags, hit_id, t, out, stats); });
+}
+int srt_surface_hits_device(srt_scene* s, uint32_t n, const float* d_rays, const int32_t* d_hit_id, const float* d_t, uint32_t flags, void* stream,
+                            const srt_surface_out* out) {
+    return guarded([&] { return surface_hits_device_impl(s, n, d_rays, d_hit_id, d_t, flags, (hipStream_t)stream, out); });
+}
+int srt_surface_hits(srt_scene* s, uint32_t n, const float* rays, const int32_t* hit_id, const float* t, uint32_t flags, const srt_surface_out* out) {
+    return guarded([&] { return surface_hits_impl(s, n, rays, hit_id, t, flags, out); });
 }
 
 void* srt_host_alloc(size_t bytes) {

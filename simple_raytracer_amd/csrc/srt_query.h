@@ -407,3 +407,128 @@ __global__ __launch_bounds__(256) void k_query_shade(DevScene s, uint32_t n_rays
     if (counters) count_hits(counters, is_hit, blockIdx.x);
     if (COUNT) { wave_add(counters + 1, n_node); wave_add(counters + 2, n_tri); wave_add(counters + 3, n_node_s); wave_add(counters + 4, n_tri_s); }
 }
+
+// =================================================================================================
+// The surface at a hit (srt_surface_rays, srt_surface_hits): what k_query_shade looks up for its Phong and then drops -- the owning
+// object, the point o + d * t, the normal, the colour (the object's or the texel), the material -- and the mirrored ray, as arrays of
+// their own.  Neither kernel restates anything: the walk is query_walk with MergeClosest as k_query_closest instantiates it, the surface
+// is surface_at, and both kernels leave through surface_store, so that the two entry points cannot drift apart.
+// The mirrored direction is glm::reflect's association, d - (N * dot(N, d)) * 2 with dot = (x + y) + z, in f32 without contraction; it
+// is the same under N -> -N, so the normal needs no orientation.  A miss row: obj -1, every float 0.
+// The stores: an n x 3 (n x 6) output is 12 B (24 B) a row, a stride no lane-per-row store coalesces.  Rows leave TRANSPOSED instead, as
+// k_query_multi's do: every lane puts its row into `stage` -- 64 * 6 words of the wave's own LDS, the rays' slots once the walk is over
+// -- and the wave writes the 192 (384) words of its rows as 3 (6) stores of 64 consecutive words; words lane * 3 + c fall on distinct
+// banks.  SRT_SURFACE_LANE_STORES builds the other choice, every lane storing its own row (measured: DESIGN.md s5).  obj, one word a
+// row, is coalesced as it stands.  A NULL output costs a wave-uniform branch on a kernel argument.
+// =================================================================================================
+// rows: the wave's live rays (its first `rows` lanes), base: the wave's first ray; K words a row from v[] to dst[(base + lane) * K ..].
+template <int K>
+__device__ __forceinline__ void store_rows(float* __restrict__ dst, const size_t base, const uint32_t lane, const uint32_t rows, const float (&v)[K], float* stage) {
+#ifdef SRT_SURFACE_LANE_STORES
+    if (lane < rows) {
+        #pragma unroll
+        for (int c = 0; c < K; c++) dst[(base + lane) * K + c] = v[c];
+    }
+#else
+    #pragma unroll
+    for (int c = 0; c < K; c++) stage[lane * K + c] = v[c];
+    __builtin_amdgcn_wave_barrier();
+    #pragma unroll
+    for (int j = 0; j < K; j++) {
+        const uint32_t w = (uint32_t)j * 64u + lane;
+        if (w < rows * K) dst[base * K + w] = stage[w];
+    }
+    __builtin_amdgcn_wave_barrier();                    // the next output reuses the stage
+#endif
+}
+
+// (is_hit, id, o, d, t, the surface there) -> the row of every wanted output.  Called by the whole wave (base < n_rays is wave-uniform).
+__device__ __forceinline__ void surface_store(const DevScene& s, const srt_surface_out& out, const size_t base, const uint32_t lane, const uint32_t rows,
+                                              const bool is_hit, const int32_t id, const V3 o, const V3 d, const float t, const Surface& f, float* stage) {
+    const V3 zero = mk(0.0f, 0.0f, 0.0f);
+    const V3 P = is_hit ? o + d * t : zero;
+    const V3 N = is_hit ? f.nrm : zero;
+    if (out.obj && lane < rows) out.obj[base + lane] = is_hit ? s.tri_obj[id] : -1;
+    if (out.point) { const float v[3] = { P.x, P.y, P.z }; store_rows<3>(out.point, base, lane, rows, v, stage); }
+    if (out.normal) { const float v[3] = { N.x, N.y, N.z }; store_rows<3>(out.normal, base, lane, rows, v, stage); }
+    if (out.color) {
+        const V3 c = is_hit ? f.color : zero;
+        const float v[3] = { c.x, c.y, c.z };
+        store_rows<3>(out.color, base, lane, rows, v, stage);
+    }
+    if (out.material) {
+        const float v[3] = { is_hit ? f.ka : 0.0f, is_hit ? f.ks : 0.0f, is_hit ? f.sh : 0.0f };
+        store_rows<3>(out.material, base, lane, rows, v, stage);
+    }
+    if (out.bounce) {
+        const float k = (d.x * N.x + d.y * N.y) + d.z * N.z;
+        const V3 r = is_hit ? mk(d.x - (N.x * k) * 2.0f, d.y - (N.y * k) * 2.0f, d.z - (N.z * k) * 2.0f) : zero;
+        const float v[6] = { P.x, P.y, P.z, r.x, r.y, r.z };
+        store_rows<6>(out.bounce, base, lane, rows, v, stage);
+    }
+}
+
+// srt_surface_rays: k_query_closest's walk and winner, then the surface under it.  RANGE: as k_query_closest<.., true>.
+// counters: as k_query_closest's.
+template <bool COUNT, bool SMOOTH, bool RANGE>
+__global__ __launch_bounds__(256) void k_query_surface(DevScene s, uint32_t n_rays, const float* __restrict__ rays, uint32_t wide, int32_t* __restrict__ hit_id,
+                                                       float* __restrict__ t_out, srt_surface_out out, unsigned long long* __restrict__ counters, QueryRange tr) {
+    __shared__ uint32_t q_all[4][QCAP];
+    __shared__ unsigned long long best_all[256];
+    __shared__ float ray_all[4][RANGE ? 8 : 6][64];
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    unsigned long long* best = best_all + wave * 64;
+    float (*wray)[64] = ray_all[wave];
+    const size_t base = (size_t)blockIdx.x * 256 + wave * 64, ri = base + lane;
+    const bool live = ri < (size_t)n_rays;
+    unsigned long long n_node = 0, n_tri = 0;
+    V3 o = mk(0.0f, 0.0f, 0.0f), d = mk(0.0f, 0.0f, 1.0f);
+    float t_min = 0.0f, t_max = 0.0f;
+    if (live) load_ray(rays, ri, wide != 0, o, d);
+    if (RANGE && live) load_range(tr, ri, t_min, t_max);
+    query_walk<COUNT, RANGE>(s, live, o, d, lane, q_all[wave], MergeClosest{ best }, wray, n_node, n_tri, t_min, t_max);
+    const unsigned long long key = live ? best[lane] : ~0ull;
+    const bool is_hit = key != ~0ull;
+    const int32_t id = is_hit ? (int32_t)(uint32_t)key : -1;
+    float t = __builtin_inff();
+    Surface f;
+    f.color = mk(0.0f, 0.0f, 0.0f); f.nrm = f.color; f.ka = 0.0f; f.ks = 0.0f; f.sh = 0.0f;
+    if (is_hit) {
+        V3 p1, e1, e2;
+        load_tri_edges(reinterpret_cast<const float4*>(s.tris), (size_t)id, p1, e1, e2);
+        t = ray_triangle(o, d, p1, e1, e2);             // the winner's t with its own bits (incl. the sign of a zero): same function, same inputs
+        f = surface_at(s, id, o, d, t, SMOOTH);
+    }
+    if (live) {
+        if (hit_id) hit_id[ri] = id;
+        if (t_out) t_out[ri] = t;
+    }
+    if (base < (size_t)n_rays) {                        // wave-uniform; the walk is over: the rays' slots are the stage
+        const size_t left = (size_t)n_rays - base;
+        surface_store(s, out, base, lane, (uint32_t)(left < 64 ? left : 64), is_hit, id, o, d, t, f, &wray[0][0]);
+    }
+    if (counters) count_hits(counters, is_hit, blockIdx.x);
+    if (COUNT) { wave_add(counters + 1, n_node); wave_add(counters + 2, n_tri); }
+}
+
+// srt_surface_hits: the same rows for hits the caller already holds -- no walk, no node record, no queue; one lane per row.  A row whose
+// id is outside [0, n_tris) is a miss row; t is taken as given (the texel index is clamped, so any t is memory-safe).
+template <bool SMOOTH>
+__global__ __launch_bounds__(256) void k_query_surface_hits(DevScene s, uint32_t n_rays, const float* __restrict__ rays, uint32_t wide,
+                                                            const int32_t* __restrict__ hit_id, const float* __restrict__ t_in, srt_surface_out out) {
+    __shared__ float stage_all[4][6 * 64];
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const size_t base = (size_t)blockIdx.x * 256 + wave * 64, ri = base + lane;
+    if (base >= (size_t)n_rays) return;                 // wave-uniform
+    const bool live = ri < (size_t)n_rays;
+    V3 o = mk(0.0f, 0.0f, 0.0f), d = mk(0.0f, 0.0f, 1.0f);
+    int32_t id = -1;
+    float t = __builtin_inff();
+    if (live) { load_ray(rays, ri, wide != 0, o, d); id = hit_id[ri]; t = t_in[ri]; }
+    const bool is_hit = id >= 0 && (uint32_t)id < s.n_tris;
+    Surface f;
+    f.color = mk(0.0f, 0.0f, 0.0f); f.nrm = f.color; f.ka = 0.0f; f.ks = 0.0f; f.sh = 0.0f;
+    if (is_hit) f = surface_at(s, id, o, d, t, SMOOTH);
+    const size_t left = (size_t)n_rays - base;
+    surface_store(s, out, base, lane, (uint32_t)(left < 64 ? left : 64), is_hit, id, o, d, t, f, stage_all[wave]);
+}

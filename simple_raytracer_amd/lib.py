@@ -23,7 +23,8 @@ ABI_SYMBOLS = ("srt_params_default", "srt_light_staircase", "srt_rows_owned", "s
                "srt_scene_pipeline", "srt_scene_overlap_estimate", "srt_scene_set_pose_source", "srt_scene_pose",
                "srt_trace_rays_device", "srt_trace_rays", "srt_occluded_device", "srt_occluded", "srt_shade_rays_device", "srt_shade_rays",
                "srt_trace_rays_range_device", "srt_trace_rays_range", "srt_occluded_range_device", "srt_occluded_range",
-               "srt_trace_rays_multi_device", "srt_trace_rays_multi", "srt_shade_rays_range_device", "srt_shade_rays_range")
+               "srt_trace_rays_multi_device", "srt_trace_rays_multi", "srt_shade_rays_range_device", "srt_shade_rays_range",
+               "srt_surface_rays_device", "srt_surface_rays", "srt_surface_hits_device", "srt_surface_hits")
 MULTI_HIT_MAX = 16                # SRT_MULTI_HIT_MAX
 
 _f32p, _i32p, _u8p, _u32p = C.POINTER(C.c_float), C.POINTER(C.c_int32), C.POINTER(C.c_uint8), C.POINTER(C.c_uint32)
@@ -38,14 +39,15 @@ class SrtError(RuntimeError):
         self.code = code
 
 
-def load():
-    """Load libsrt_hip.so; fail loudly if it has not been built (python -m simple_raytracer_amd.build)."""
+def load(path=None):
+    """Load libsrt_hip.so; fail loudly if it has not been built (python -m simple_raytracer_amd.build).
+    path: another build of the same library (a measurement variant, see build.py) -- loaded and bound, not kept as the product's."""
     global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise RuntimeError(f"{LIB_PATH} is missing: the HIP extension must be built "
+    if _lib is None or path is not None:
+        if not os.path.exists(path or LIB_PATH):
+            raise RuntimeError(f"{path or LIB_PATH} is missing: the HIP extension must be built "
                                "(python -m simple_raytracer_amd.build); there is no CPU fallback")
-        L = C.CDLL(LIB_PATH)
+        L = C.CDLL(path or LIB_PATH)
         L.srt_params_default.argtypes = [C.POINTER(abi.Params), C.c_uint32, C.c_uint32]
         L.srt_params_default.restype = None
         L.srt_light_staircase.argtypes = [_f32p, C.c_uint32, _f32p]
@@ -116,6 +118,14 @@ def load():
         L.srt_shade_rays_range_device.restype = C.c_int
         L.srt_shade_rays_range.argtypes = [C.c_void_p, C.c_uint32, _f32p, _f32p, C.POINTER(abi.Params), _i32p, _f32p, _f32p, _u8p, C.POINTER(abi.Stats)]
         L.srt_shade_rays_range.restype = C.c_int
+        L.srt_surface_rays_device.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(abi.SurfaceOut)]
+        L.srt_surface_rays_device.restype = C.c_int
+        L.srt_surface_rays.argtypes = [C.c_void_p, C.c_uint32, _f32p, _f32p, C.c_uint32, _i32p, _f32p, C.POINTER(abi.SurfaceOut), C.POINTER(abi.Stats)]
+        L.srt_surface_rays.restype = C.c_int
+        L.srt_surface_hits_device.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(abi.SurfaceOut)]
+        L.srt_surface_hits_device.restype = C.c_int
+        L.srt_surface_hits.argtypes = [C.c_void_p, C.c_uint32, _f32p, _i32p, _f32p, C.c_uint32, C.POINTER(abi.SurfaceOut)]
+        L.srt_surface_hits.restype = C.c_int
         L.srt_strerror.argtypes = [C.c_int]
         L.srt_strerror.restype = C.c_char_p
         L.srt_last_hip_error.restype = C.c_int
@@ -130,6 +140,8 @@ def load():
         L.srt_kat_interp_normal.argtypes = [C.c_int, C.c_uint32, _f32p, _f32p]
         L.srt_kat_pow.argtypes = [C.c_int, C.c_uint32, _f32p, _f32p, _f32p, _f32p]
         L.srt_kat_tonemap.argtypes = [C.c_int, C.c_uint32, _f32p, C.c_float, C.c_float, _f32p, _i32p]
+        if path is not None:
+            return L
         _lib = L
     return _lib
 
@@ -142,8 +154,8 @@ def _check(rc, where):
 class DeviceScene:
     """A flat scene resident on one HIP device (opaque srt_scene handle)."""
 
-    def __init__(self, flat: abi.FlatScene, device: int = 0):
-        self.L = load()
+    def __init__(self, flat: abi.FlatScene, device: int = 0, library=None):
+        self.L = library if library is not None else load()
         self.flat = flat
         self.device = device
         h = C.c_void_p()
@@ -397,6 +409,53 @@ class DeviceScene:
             _check(self.L.srt_shade_rays_range_device(self.h, n, C.c_void_p(rays), C.c_void_p(t_range), C.byref(params), C.c_void_p(stream), C.c_void_p(hit_id),
                                                       C.c_void_p(t), C.c_void_p(rgb_linear), C.c_void_p(rgb8)), "srt_shade_rays_range_device")
 
+    def surface_rays(self, rays, want=("hit_id", "t", "obj", "point", "normal", "color", "material", "bounce"), smooth=False, count=False, t_range=None):
+        """srt_surface_rays: the closest hit of every ray of `rays` (n x 6, host array) and the surface under it.  Returns a dict of the
+        arrays named in `want` (hit_id n, t n, obj n, point / normal / color / material n x 3, bounce n x 6: the mirrored ray) + 'stats'.
+        smooth: SRT_FLAG_SMOOTH_NORMALS; count: SRT_FLAG_COUNT_WORK; t_range (n x 2: t_min, t_max per ray): the closest hit inside each
+        ray's closed interval."""
+        r = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
+        n = r.shape[0]
+        tr = _t_range(t_range, n)
+        out = {}
+        if "hit_id" in want: out["hit_id"] = np.empty(n, np.int32)
+        if "t" in want: out["t"] = np.empty(n, np.float32)
+        so = _surface_arrays(n, want, out)
+        st = abi.Stats()
+        g = lambda k, ty: out[k].ctypes.data_as(ty) if k in out else ty()
+        flags = (abi.SRT_FLAG_SMOOTH_NORMALS if smooth else 0) | (abi.SRT_FLAG_COUNT_WORK if count else 0)
+        _check(self.L.srt_surface_rays(self.h, n, r.ctypes.data_as(_f32p), tr.ctypes.data_as(_f32p) if tr is not None else None, flags, g("hit_id", _i32p), g("t", _f32p),
+                                       C.byref(so), C.byref(st)), "srt_surface_rays")
+        out["stats"] = st.as_dict()
+        return out
+
+    def surface_rays_device(self, n, rays, stream=0, hit_id=0, t=0, obj=0, point=0, normal=0, color=0, material=0, bounce=0, smooth=False, count=False, t_range=None):
+        """srt_surface_rays_device: raw device pointers (ints, e.g. torch.Tensor.data_ptr()) in, asynchronous on `stream`; t_range a device
+        pointer to n x 2 floats, or None."""
+        so = abi.SurfaceOut(obj or None, point or None, normal or None, color or None, material or None, bounce or None)
+        flags = (abi.SRT_FLAG_SMOOTH_NORMALS if smooth else 0) | (abi.SRT_FLAG_COUNT_WORK if count else 0)
+        _check(self.L.srt_surface_rays_device(self.h, n, C.c_void_p(rays), C.c_void_p(t_range or 0), flags, C.c_void_p(stream), C.c_void_p(hit_id), C.c_void_p(t),
+                                              C.byref(so)), "srt_surface_rays_device")
+
+    def surface_hits(self, rays, hit_id, t, want=("obj", "point", "normal", "color", "material", "bounce"), smooth=False):
+        """srt_surface_hits: the surface under hits the caller already holds -- `hit_id` (n) and `t` (n) of the rays `rays` (n x 6, host
+        arrays): a render's, srt_trace_rays', a column of srt_trace_rays_multi.  No walk.  Returns a dict of the arrays named in `want`."""
+        r = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
+        n = r.shape[0]
+        hid = np.ascontiguousarray(hit_id, np.int32).reshape(-1); tt = np.ascontiguousarray(t, np.float32).reshape(-1)
+        assert hid.shape[0] == n and tt.shape[0] == n, "hit_id, t: one entry per ray"
+        out = {}
+        so = _surface_arrays(n, want, out)
+        _check(self.L.srt_surface_hits(self.h, n, r.ctypes.data_as(_f32p), hid.ctypes.data_as(_i32p), tt.ctypes.data_as(_f32p), abi.SRT_FLAG_SMOOTH_NORMALS if smooth else 0,
+                                       C.byref(so)), "srt_surface_hits")
+        return out
+
+    def surface_hits_device(self, n, rays, hit_id, t, stream=0, obj=0, point=0, normal=0, color=0, material=0, bounce=0, smooth=False):
+        """srt_surface_hits_device: raw device pointers (ints) in -- the rays, their hit ids and t --, asynchronous on `stream`."""
+        so = abi.SurfaceOut(obj or None, point or None, normal or None, color or None, material or None, bounce or None)
+        _check(self.L.srt_surface_hits_device(self.h, n, C.c_void_p(rays), C.c_void_p(hit_id), C.c_void_p(t), abi.SRT_FLAG_SMOOTH_NORMALS if smooth else 0,
+                                              C.c_void_p(stream), C.byref(so)), "srt_surface_hits_device")
+
     def sync(self):
         st = abi.Stats()
         _check(self.L.srt_sync(self.h, C.byref(st)), "srt_sync")
@@ -429,6 +488,16 @@ class FrameBatch:
 
 def _f(a):
     return np.ascontiguousarray(a, np.float32)
+
+
+def _surface_arrays(n, want, out):
+    """Host arrays for the fields of srt_surface_out named in `want`, added to `out`; returns the struct that points at them."""
+    so = abi.SurfaceOut()
+    for name, (ty, k) in abi.SURFACE_FIELDS.items():
+        if name in want:
+            out[name] = np.empty(n if k == 1 else (n, k), ty)
+            setattr(so, name, out[name].ctypes.data)
+    return so
 
 
 def _t_range(t_range, n):

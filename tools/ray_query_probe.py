@@ -18,7 +18,12 @@ chain of k range calls (t_min made on the device with torch.nextafter) beside th
 --shade-range: instead, what the interval costs the shaded query (srt_shade_rays_range_device) on the same frame's rays, row-major and
 shuffled, at 1 and 16 light samples: the unbounded srt_shade_rays_device beside the range call with (0, +inf) -- the same bytes -- and
 with t_min just behind the frame's hit (next_up(t): the colour at the exit point / behind the first surface), in the same rounds.
-Usage: python tools/ray_query_probe.py [--reps N] [--trace] [--shade | --range | --shade-range | --multi [--rounds R]]     (--trace: few repetitions, for a run under rocprofv3 --kernel-trace --stats)"""
+--surface: instead, the surface at a hit (srt_surface_rays_device, srt_surface_hits_device) on the same frame's rays, row-major and
+shuffled, in the same rounds: srt_trace_rays_device (the yardstick: k_query_closest on the same rays), srt_surface_rays_device with all
+outputs and with normal + bounce only, srt_surface_hits_device on the frame's hits, and srt_surface_rays_device of the OTHER store form
+-- the library built with -DSRT_SURFACE_LANE_STORES (python -m simple_raytracer_amd.build --surface-lane-stores), loaded beside the
+shipped one, on a scene of its own.
+Usage: python tools/ray_query_probe.py [--reps N] [--trace] [--shade | --range | --shade-range | --multi | --surface [--rounds R]]     (--trace: few repetitions, for a run under rocprofv3 --kernel-trace --stats)"""
 import argparse, os, sys, time
 import numpy as np
 import torch                                   # first: torch initialises HIP before the library does
@@ -273,6 +278,45 @@ def multi_section(reps, rounds):
         print(f"{'host form, end to end':34s} {key:46s} {float(np.median(v)):8.3f} {min(v):8.3f} {max(v):8.3f}")
 
 
+def surface_section(reps, rounds):
+    from simple_raytracer_amd import build
+    dev = torch.device("cuda", 0); torch.zeros(1, device=dev)
+    g = gu.GoldenScene("ground_bunny")
+    ds = lib.DeviceScene(g.flat)
+    lane = lib.DeviceScene(g.flat, library=lib.load(build.build_surface_lane_stores()))
+    side = torch.cuda.Stream(device=dev)
+    cur = side.cuda_stream
+    rays = frame_rays()
+    n = rays.shape[0]
+    hit = torch.empty(n, dtype=torch.int32, device=dev); t = torch.empty(n, dtype=torch.float32, device=dev)
+    f = {k: torch.empty((n,) if c == 1 else (n, c), dtype=torch.int32 if ty is np.int32 else torch.float32, device=dev) for k, (ty, c) in abi.SURFACE_FIELDS.items()}
+    f2 = {k: torch.empty_like(v) for k, v in f.items()}
+    ptr = lambda d, keys=None: {k: v.data_ptr() for k, v in d.items() if keys is None or k in keys}
+    print(f"surface at a hit, K3 ground_bunny {W}x{H}: {n} rays; {rounds} rounds of {reps} calls, forms alternating; ms a call")
+    print(f"{'rays':34s} {'form':34s} {'median':>8s} {'min':>8s} {'max':>8s} {'/ first':>7s}")
+    for name, order in (("row-major", np.arange(n)), ("shuffled", np.random.default_rng(1).permutation(n))):
+        d_rays = torch.from_numpy(np.ascontiguousarray(rays[order])).to(dev)
+        torch.cuda.synchronize()
+        trace = lambda: ds.trace_rays_device(n, d_rays.data_ptr(), stream=cur, hit_id=hit.data_ptr(), t=t.data_ptr())
+        full = lambda h, out: (lambda: h.surface_rays_device(n, d_rays.data_ptr(), stream=cur, hit_id=hit.data_ptr(), t=t.data_ptr(), **ptr(out)))
+        two = lambda h, out: (lambda: h.surface_rays_device(n, d_rays.data_ptr(), stream=cur, hit_id=hit.data_ptr(), t=t.data_ptr(), **ptr(out, ("normal", "bounce"))))
+        trace(); side.synchronize()
+        h0, t0 = hit.clone(), t.clone()
+        hits = lambda h, out: (lambda: h.surface_hits_device(n, d_rays.data_ptr(), h0.data_ptr(), t0.data_ptr(), stream=cur, **ptr(out)))
+        forms = {"trace_rays (k_query_closest)": trace,
+                 "surface_rays, all outputs": full(ds, f), "surface_rays, all, lane stores": full(lane, f2),
+                 "surface_rays, normal + bounce": two(ds, f), "surface_rays, n + b, lane stores": two(lane, f2),
+                 "surface_hits, all outputs": hits(ds, f), "surface_hits, all, lane stores": hits(lane, f2)}
+        report(name, rounds_of(forms, reps, rounds, side))
+        # the forms answer alike: the two store forms bit for bit, surface_hits as surface_rays, hit ids as the closest-hit query
+        full(ds, f)(); full(lane, f2)(); side.synchronize()
+        assert torch.equal(hit, h0) and torch.equal(t.view(torch.int32), t0.view(torch.int32))
+        assert all(torch.equal(f[k].view(torch.int32), f2[k].view(torch.int32)) for k in f)
+        hits(lane, f2)(); side.synchronize()
+        assert all(torch.equal(f[k].view(torch.int32), f2[k].view(torch.int32)) for k in f)
+        print(f"{'':34s} hits {int((h0 >= 0).sum().item())}; both store forms and surface_hits give the same bits")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
@@ -281,11 +325,14 @@ def main():
     ap.add_argument("--range", action="store_true", dest="t_range")
     ap.add_argument("--shade-range", action="store_true", dest="shade_range")
     ap.add_argument("--multi", action="store_true")
+    ap.add_argument("--surface", action="store_true")
     ap.add_argument("--rounds", type=int, default=7)
     a = ap.parse_args()
     reps = 3 if a.trace else a.reps
     if a.multi:
         return multi_section(reps, 2 if a.trace else a.rounds)
+    if a.surface:
+        return surface_section(reps, 2 if a.trace else a.rounds)
     if a.shade:
         return shade_section(reps)
     if a.shade_range:
