@@ -530,6 +530,63 @@ int srt_surface_hits_device(srt_scene* s, uint32_t n, const float* d_rays, const
 int srt_surface_hits(srt_scene* s, uint32_t n, const float* rays, const int32_t* hit_id, const float* t,
                      uint32_t flags, const srt_surface_out* out);
 
+/* Mirror paths: a ray followed through up to `depth` mirror bounces, every hit shaded, the bounces mixed by a per-object reflectance and the
+ * finished pixel written, in ONE launch -- the chain srt_shade_rays_range -> srt_surface_rays (bounce) -> srt_shade_rays_range -> ... with
+ * each mirrored ray walked once and nothing of a bounce written for a next launch to read back.
+ * Unless said here everything is as for srt_shade_rays_range: the layout of rays and t_range with wide loads where they are 8-byte aligned,
+ * a NULL t_range, the params fields read and ignored, the flags, the errors (checked before anything is touched), n == 0, NULL outputs,
+ * the one-light-table-per-handle rule, the ordering on `stream`, srt_scene_share, what the host form stages, waits for and copies out.
+ * DEFINITION.  A path is a row of SEGMENTS b = 0 .. depth - 1, each a ray with a t interval:
+ *   segment 0       the caller's ray and interval.  hit_id, t and rgb_linear are bit for bit what srt_shade_rays_range gives for them, obj
+ *                   what srt_surface_rays gives.
+ *   segment b + 1   of a ray whose segment b HIT: the ray is the `bounce` row srt_surface_rays defines for segment b's hit under the call's
+ *                   flags -- origin o + d * t, not moved; direction r_i = d_i - (N_i * k) * 2 with N the normal shading uses (the smooth one
+ *                   under SRT_FLAG_SMOOTH_NORMALS) -- and the interval is (bounce_t_min, +inf); a NaN bounce_t_min bounds nothing.  Its
+ *                   outputs are what the same two calls give for that ray and interval.
+ *                   of a ray whose segment b MISSED: not walked.  Its rows, and those of every later segment, are miss rows: hit_id -1,
+ *                   t +inf, obj -1, rgb_linear (0, 0, 0), a zero ray.
+ *   Shadow rays are as in srt_shade_rays: from the segment's hit point, unbounded, with the hit object's tree left out.
+ *   The walks are purely geometric: reflectance never ends a path, and no value of it changes which segments are walked.
+ *   The mix, in f32 without contraction, from the near end (lin_b = segment b's rgb_linear, obj_b its object):
+ *       acc = (0, 0, 0); W = 1
+ *       for b = 0 .. depth - 1, while segment b hits:
+ *           k = (b + 1 < depth && segment b + 1 hits) ? reflectance[obj_b] : 0          (a NULL table: 0)
+ *           a = W * (1 - k);   acc_i = acc_i + a * lin_b_i   (one multiply, then one add);   W = W * k
+ *   rgb_linear = acc; rgb8 = the tone map, the quantiser and the background rule on acc: a ray whose segment 0 misses, or a sum that is all
+ *   black, gets `background`.  Reflectance values are not validated: NaN, negative values and values above 1 give what the arithmetic gives.
+ *   Identities:  depth 1: rgb_linear, rgb8 and row 0 of seg are srt_shade_rays_range's bits for every ray.  A NULL or all-zero table: the
+ *                mixed output is segment 0's.  The per-segment rows at depth D are the first D rows of the same call at any larger depth.
+ *                Results never depend on the order of the rays.
+ * seg (may be NULL, as may any field): per SEGMENT outputs, segment-major -- row b of a field is an n-array laid out like the matching
+ * output of srt_shade_rays_range / srt_surface_rays, at element offset b * n (x 3, x 6).
+ * Errors beyond those of srt_shade_rays_range, before anything is touched: NULL path, depth == 0: SRT_ERR_ARG; depth > SRT_PATH_DEPTH_MAX:
+ * SRT_ERR_LIMIT.  A call with every output NULL returns SRT_OK and launches nothing.
+ * The _device form is one kernel launch; it allocates and copies nothing proportional to n; path->reflectance is read from the caller's
+ * DEVICE memory (n_objects floats) when the kernel runs.  Without SRT_FLAG_COUNT_WORK, and with the light table already on the device, it may
+ * be captured into a hipGraph.
+ * The host form stages rays, intervals, the reflectance table and every wanted output through the handle's pinned block and buffers, waits,
+ * and fills *stats (may be NULL): primary_rays = n, hit_rays = the hits of all segments together, shadow_rays = hit_rays x n_lights; under
+ * SRT_FLAG_COUNT_WORK the four test counters are the sums, over the segments actually walked, of what srt_shade_rays_range reports for that
+ * segment's ray and interval. */
+#define SRT_PATH_DEPTH_MAX 8
+typedef struct srt_path_desc {
+    uint32_t     depth;          /* segments per ray, 1 .. SRT_PATH_DEPTH_MAX                                   */
+    float        bounce_t_min;   /* a mirrored ray's interval is (bounce_t_min, +inf); NaN bounds nothing        */
+    const float* reflectance;    /* n_objects floats or NULL (= all 0); device pointer in the _device form       */
+} srt_path_desc;
+typedef struct srt_path_out {    /* per SEGMENT, segment-major: row b is an n-array laid out like the matching  */
+    int32_t* hit_id;             /* depth x n          output of srt_shade_rays_range / srt_surface_rays;       */
+    float*   t;                  /* depth x n          any pointer may be NULL, and so may the struct           */
+    int32_t* obj;                /* depth x n                                                                    */
+    float*   rgb_linear;         /* depth x n x 3      the segment's own pre-tone-map sum                       */
+    float*   rays;               /* depth x n x 6      the ray the segment walked (row 0 = the caller's ray)    */
+} srt_path_out;
+int srt_shade_paths_device(srt_scene* s, uint32_t n, const float* d_rays, const float* d_t_range /* n x 2 or NULL */,
+                           const srt_params* p, const srt_path_desc* path, void* stream,
+                           float* d_rgb_linear /* n x 3, mixed */, uint8_t* d_rgb8 /* n x 3 */, const srt_path_out* seg);
+int srt_shade_paths(srt_scene* s, uint32_t n, const float* rays, const float* t_range, const srt_params* p,
+                    const srt_path_desc* path, float* rgb_linear, uint8_t* rgb8, const srt_path_out* seg, srt_stats* stats);
+
 /* Device-resident size of the scene records and the per-record algorithmic byte sizes used by
  * the bytes model: 32 B per node test, 36 B per triangle test. */
 uint64_t srt_scene_device_bytes(const srt_scene* s);

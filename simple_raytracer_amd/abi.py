@@ -80,6 +80,23 @@ class SurfaceOut(C.Structure):
     _fields_ = [("obj", C.c_void_p), ("point", C.c_void_p), ("normal", C.c_void_p), ("color", C.c_void_p), ("material", C.c_void_p), ("bounce", C.c_void_p)]
 
 
+SRT_PATH_DEPTH_MAX = 8
+
+
+class PathDesc(C.Structure):
+    """srt_path_desc: segments per ray, the lower bound of a mirrored ray's interval, the per-object reflectance table as an address
+    (a host array in the host form, a device pointer in the _device form; 0 = all 0)."""
+    _fields_ = [("depth", C.c_uint32), ("bounce_t_min", C.c_float), ("reflectance", C.c_void_p)]
+
+
+class PathOut(C.Structure):
+    """srt_path_out: the per-segment arrays of srt_shade_paths (segment-major, depth x n rows), as addresses; 0 = not wanted."""
+    _fields_ = [("hit_id", C.c_void_p), ("t", C.c_void_p), ("obj", C.c_void_p), ("rgb_linear", C.c_void_p), ("rays", C.c_void_p)]
+
+
+# the fields of srt_path_out: name -> (dtype, floats or ints per ray and segment)
+PATH_FIELDS = {"hit_id": (np.int32, 1), "t": (np.float32, 1), "obj": (np.int32, 1), "rgb_linear": (np.float32, 3), "rays": (np.float32, 6)}
+
 # the fields of srt_surface_out: name -> (dtype, floats or ints per ray)
 SURFACE_FIELDS = {"obj": (np.int32, 1), "point": (np.float32, 3), "normal": (np.float32, 3), "color": (np.float32, 3), "material": (np.float32, 3),
                   "bounce": (np.float32, 6)}

@@ -165,6 +165,9 @@ struct srt_scene {
     DevArray<float, 3> rq_lin; DevArray<uint8_t, 3> rq_rgb8;
     // srt_surface_rays / srt_surface_hits: the six arrays of srt_surface_out, and the t of the hits a caller brings (their ids go through rq_skip)
     DevArray<int32_t> rq_sobj; DevArray<float, 3> rq_spoint, rq_snormal, rq_scolor, rq_smat; DevArray<float, 6> rq_sbounce; DevArray<float> rq_tin;
+    // srt_shade_paths: the reflectance table of a host call (capacity counts objects) and the per-segment sums (capacity counts depth x n rows);
+    // the other per-segment rows go through rq_hit / rq_t / rq_sobj / rq_sbounce, depth units a ray
+    DevArray<float> rq_refl; DevArray<float, 3> rq_plin;
     DevArray<float, 3> d_qlights; Pinned<float, 3> h_qlights; uint32_t qlights_valid = 0;
     Event qlights_sent; hipStream_t qlights_stream = nullptr; bool qlights_settled = true;
     int n_cu = 256;
@@ -1642,6 +1645,16 @@ static int occluded_device_impl(srt_scene* s, uint32_t n, const float* d_rays, c
     return SRT_OK;
 }
 
+// What a shading kernel takes of the params (after query_prologue: the light table is the handle's device copy)
+static QueryShade query_shade(const srt_scene* s, const srt_params* p) {
+    QueryShade qs;
+    qs.lights = s->d_qlights; qs.n_lights = p->n_lights;
+    qs.shadow_div = p->shadow_div; qs.reinhard = p->reinhard; qs.gamma = p->gamma;
+    qs.bg = (uint32_t)p->background[0] | ((uint32_t)p->background[1] << 8) | ((uint32_t)p->background[2] << 16);
+    qs.spread = p->n_lights >= 8 ? 1u : 0u;      // (measured at 1 and 16 samples, DESIGN.md s5: the spread costs phase 1, and pays with the shadow work)
+    return qs;
+}
+
 // srt_shade_rays: closest hit, shadow rays, Phong, tone map for caller-supplied rays, one launch (k_query_shade)
 // d_t_range: the rays' t intervals (srt_shade_rays_range), or null: the builds without the interval, as trace_rays_device_impl chooses its own
 static int shade_rays_device_impl(srt_scene* s, uint32_t n, const float* d_rays, const float* d_t_range, const srt_params* p, hipStream_t stream, int32_t* d_hit_id,
@@ -1651,11 +1664,7 @@ static int shade_rays_device_impl(srt_scene* s, uint32_t n, const float* d_rays,
     const bool count = (p->flags & SRT_FLAG_COUNT_WORK) != 0, smooth = (p->flags & SRT_FLAG_SMOOTH_NORMALS) != 0;
     QueryLaunch q;
     SRT_TRY(query_prologue(s, n, stream, p, count || count_hits, &q));
-    QueryShade qs;
-    qs.lights = s->d_qlights; qs.n_lights = p->n_lights;
-    qs.shadow_div = p->shadow_div; qs.reinhard = p->reinhard; qs.gamma = p->gamma;
-    qs.bg = (uint32_t)p->background[0] | ((uint32_t)p->background[1] << 8) | ((uint32_t)p->background[2] << 16);
-    qs.spread = p->n_lights >= 8 ? 1u : 0u;      // (measured at 1 and 16 samples, DESIGN.md s5: the spread costs phase 1, and pays with the shadow work)
+    const QueryShade qs = query_shade(s, p);
     // the build: counting, smooth normals, and the integer-shininess pow where every object of the scene allows it (as k_shade_tile)
     static const decltype(&k_query_shade<false, false, false, false>) builds[16] = {
         &k_query_shade<false, false, false, false>, &k_query_shade<false, false, true, false>, &k_query_shade<false, true, false, false>, &k_query_shade<false, true, true, false>,
@@ -1664,6 +1673,33 @@ static int shade_rays_device_impl(srt_scene* s, uint32_t n, const float* d_rays,
         &k_query_shade<true, false, false, true>,   &k_query_shade<true, false, true, true>,   &k_query_shade<true, true, false, true>,   &k_query_shade<true, true, true, true> };
     const auto k = builds[(d_t_range ? 8 : 0) | (count ? 4 : 0) | (smooth ? 2 : 0) | (s->rec->int_shin ? 1 : 0)];
     hipLaunchKernelGGL(k, q.grid, dim3(256), 0, q.stream, s->dev, n, d_rays, rays_wide(d_rays), qs, d_hit_id, d_t, d_rgb_linear, d_rgb8, q.ctr, query_range(d_t_range));
+    HIP_TRY(hipGetLastError());
+    return SRT_OK;
+}
+
+// srt_shade_paths: up to path->depth mirror bounces per ray, shaded and mixed, one launch (k_query_path)
+static int check_paths(const srt_scene* s, uint32_t n, const float* rays, const srt_params* p, const srt_path_desc* path) {
+    SRT_TRY(check_shade(s, n, rays, p));
+    if (!path || path->depth == 0) return SRT_ERR_ARG;
+    if (path->depth > SRT_PATH_DEPTH_MAX) return SRT_ERR_LIMIT;
+    return SRT_OK;
+}
+static inline bool paths_wanted(const float* rgb_linear, const uint8_t* rgb8, const srt_path_out* o) {
+    return rgb_linear || rgb8 || (o && (o->hit_id || o->t || o->obj || o->rgb_linear || o->rays));
+}
+static int shade_paths_device_impl(srt_scene* s, uint32_t n, const float* d_rays, const float* d_t_range, const srt_params* p, const srt_path_desc* path,
+                                   hipStream_t stream, float* d_rgb_linear, uint8_t* d_rgb8, const srt_path_out* seg, bool count_hits) {
+    SRT_TRY(check_paths(s, n, d_rays, p, path));
+    if (!n || (!count_hits && !paths_wanted(d_rgb_linear, d_rgb8, seg))) return SRT_OK;
+    const bool count = (p->flags & SRT_FLAG_COUNT_WORK) != 0, smooth = (p->flags & SRT_FLAG_SMOOTH_NORMALS) != 0;
+    QueryLaunch q;
+    SRT_TRY(query_prologue(s, n, stream, p, count || count_hits, &q));
+    static const decltype(&k_query_path<false, false, false>) builds[8] = {
+        &k_query_path<false, false, false>, &k_query_path<false, false, true>, &k_query_path<false, true, false>, &k_query_path<false, true, true>,
+        &k_query_path<true, false, false>,  &k_query_path<true, false, true>,  &k_query_path<true, true, false>,  &k_query_path<true, true, true> };
+    const auto k = builds[(count ? 4 : 0) | (smooth ? 2 : 0) | (s->rec->int_shin ? 1 : 0)];
+    hipLaunchKernelGGL(k, q.grid, dim3(256), 0, q.stream, s->dev, n, d_rays, rays_wide(d_rays), query_shade(s, p), query_range(d_t_range), *path, d_rgb_linear, d_rgb8,
+                       seg ? *seg : srt_path_out{}, q.ctr);
     HIP_TRY(hipGetLastError());
     return SRT_OK;
 }
@@ -1713,14 +1749,17 @@ static int surface_hits_device_impl(srt_scene* s, uint32_t n, const float* d_ray
 // The host entry points: the caller's rays go through the pinned staging block (stage_acquire, as every update does) into the handle's
 // own ray buffer on the scene's stream, the device entry point runs behind them, the call waits and copies the results out.
 // skip_obj: n int32 a call brings -- the skipped objects of srt_occluded, the hit ids of srt_surface_hits; t_in: the t of those hits
-static int stage_rays(srt_scene* s, uint32_t n, const float* rays, const float* t_range, const int32_t* skip_obj, const float* t_in, hipStream_t st) {
+// refl: the n_refl floats of srt_shade_paths' reflectance table
+static int stage_rays(srt_scene* s, uint32_t n, const float* rays, const float* t_range, const int32_t* skip_obj, const float* t_in, hipStream_t st,
+                      const float* refl = nullptr, uint32_t n_refl = 0) {
     auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
     const size_t o_rays = 0, o_skip = pad((size_t)n * 24), o_range = o_skip + (skip_obj ? pad((size_t)n * 4) : 0), o_tin = o_range + (t_range ? pad((size_t)n * 8) : 0),
-                 total = o_tin + (t_in ? pad((size_t)n * 4) : 0);
+                 o_refl = o_tin + (t_in ? pad((size_t)n * 4) : 0), total = o_refl + (refl ? pad((size_t)n_refl * 4) : 0);
     SRT_TRY(grow(s, n, s->rq_rays));
     if (skip_obj) SRT_TRY(grow(s, n, s->rq_skip));
     if (t_range) SRT_TRY(grow(s, n, s->rq_range));
     if (t_in) SRT_TRY(grow(s, n, s->rq_tin));
+    if (refl) SRT_TRY(grow(s, n_refl, s->rq_refl));
     char* h = nullptr;
     SRT_TRY(stage_acquire(s, total, &h));
     std::memcpy(h + o_rays, rays, (size_t)n * 24);
@@ -1736,6 +1775,10 @@ static int stage_rays(srt_scene* s, uint32_t n, const float* rays, const float* 
     if (t_in) {
         std::memcpy(h + o_tin, t_in, (size_t)n * 4);
         HIP_TRY(hipMemcpyAsync(s->rq_tin, h + o_tin, (size_t)n * 4, hipMemcpyHostToDevice, st));
+    }
+    if (refl && n_refl) {
+        std::memcpy(h + o_refl, refl, (size_t)n_refl * 4);
+        HIP_TRY(hipMemcpyAsync(s->rq_refl, h + o_refl, (size_t)n_refl * 4, hipMemcpyHostToDevice, st));
     }
     HIP_TRY(hipEventRecord(s->staged, st));
     return SRT_OK;
@@ -1754,16 +1797,18 @@ template <typename T, size_t K>
 static QueryOut<T, K> query_out(T* host, DevArray<T, K>& dev, size_t per = 1) { return QueryOut<T, K>{ host, dev, per }; }
 
 // The round trip of a host query on the scene's own stream: grow the wanted result buffers, stage the rays (and what comes with them: t
-// intervals, skipped objects, the hits of srt_surface_hits), launch(stream) -- the device entry point --, wait, copy each wanted array out.
+// intervals, skipped objects, the hits of srt_surface_hits, the reflectance table of srt_shade_paths), launch(stream) -- the device entry
+// point --, wait, copy each wanted array out.
 template <typename Launch, typename... O>
-static int query_round_trip(srt_scene* s, uint32_t n, const float* rays, const float* t_range, const int32_t* skip_obj, const float* t_in, Launch launch, const O&... outs) {
+static int query_round_trip_refl(srt_scene* s, uint32_t n, const float* rays, const float* t_range, const int32_t* skip_obj, const float* t_in, const float* refl,
+                                 uint32_t n_refl, Launch launch, const O&... outs) {
     HIP_TRY(hipSetDevice(s->device));
     hipStream_t st;
     SRT_TRY(own_stream(s, &st));
     int rc = SRT_OK;
     ((rc = (rc == SRT_OK && outs.host) ? grow(s, (size_t)n * outs.per, outs.dev) : rc), ...);
     SRT_TRY(rc);
-    SRT_TRY(stage_rays(s, n, rays, t_range, skip_obj, t_in, st));
+    SRT_TRY(stage_rays(s, n, rays, t_range, skip_obj, t_in, st, refl, n_refl));
     SRT_TRY(launch(st));
     HIP_TRY(hipStreamSynchronize(st));
     if (s->qlights_stream == st) s->qlights_settled = true;      // a light table sent on this stream has arrived
@@ -1771,6 +1816,10 @@ static int query_round_trip(srt_scene* s, uint32_t n, const float* rays, const f
     ((e = (e == hipSuccess && outs.host) ? hipMemcpy(outs.host, outs.dev.p, (size_t)n * outs.per * outs.unit, hipMemcpyDeviceToHost) : e), ...);
     HIP_TRY(e);
     return SRT_OK;
+}
+template <typename Launch, typename... O>
+static int query_round_trip(srt_scene* s, uint32_t n, const float* rays, const float* t_range, const int32_t* skip_obj, const float* t_in, Launch launch, const O&... outs) {
+    return query_round_trip_refl(s, n, rays, t_range, skip_obj, t_in, nullptr, 0, launch, outs...);
 }
 
 }      // extern "C++"
@@ -1831,6 +1880,25 @@ static int shade_rays_impl(srt_scene* s, uint32_t n, const float* rays, const fl
     SRT_TRY(query_round_trip(s, n, rays, t_range, nullptr, nullptr, [&](hipStream_t st) {
         return shade_rays_device_impl(s, n, s->rq_rays, t_range ? s->rq_range.p : nullptr, p, st, o_hit.wanted(), o_t.wanted(), o_lin.wanted(), o_rgb8.wanted(), true);
     }, o_hit, o_t, o_lin, o_rgb8));
+    return stats ? query_stats(s, n, p->n_lights, stats) : SRT_OK;
+}
+
+// srt_shade_paths: the per-segment rows are depth units a ray; hit_rays counts the hits of all segments, hence the shadow rays
+static int shade_paths_impl(srt_scene* s, uint32_t n, const float* rays, const float* t_range, const srt_params* p, const srt_path_desc* path, float* rgb_linear,
+                            uint8_t* rgb8, const srt_path_out* seg, srt_stats* stats) {
+    SRT_TRY(check_paths(s, n, rays, p, path));
+    if (stats) std::memset(stats, 0, sizeof(*stats));
+    if (!n || (!stats && !paths_wanted(rgb_linear, rgb8, seg))) return SRT_OK;
+    const srt_path_out h = seg ? *seg : srt_path_out{};
+    const size_t D = path->depth;
+    const auto o_lin = query_out(rgb_linear, s->rq_lin); const auto o_rgb8 = query_out(rgb8, s->rq_rgb8);
+    const auto o_hit = query_out(h.hit_id, s->rq_hit, D); const auto o_t = query_out(h.t, s->rq_t, D); const auto o_obj = query_out(h.obj, s->rq_sobj, D);
+    const auto o_slin = query_out(h.rgb_linear, s->rq_plin, D); const auto o_rays = query_out(h.rays, s->rq_sbounce, D);
+    SRT_TRY(query_round_trip_refl(s, n, rays, t_range, nullptr, nullptr, path->reflectance, path->reflectance ? s->dev.n_objects : 0u, [&](hipStream_t st) {
+        const srt_path_desc dpath = { path->depth, path->bounce_t_min, path->reflectance ? s->rq_refl.p : nullptr };
+        const srt_path_out dev = { o_hit.wanted(), o_t.wanted(), o_obj.wanted(), o_slin.wanted(), o_rays.wanted() };
+        return shade_paths_device_impl(s, n, s->rq_rays, t_range ? s->rq_range.p : nullptr, p, &dpath, st, o_lin.wanted(), o_rgb8.wanted(), &dev, stats != nullptr);
+    }, o_lin, o_rgb8, o_hit, o_t, o_obj, o_slin, o_rays));
     return stats ? query_stats(s, n, p->n_lights, stats) : SRT_OK;
 }
 
@@ -1911,6 +1979,14 @@ int srt_shade_rays(srt_scene* s, uint32_t n, const float* rays, const srt_params
 int srt_shade_rays_range(srt_scene* s, uint32_t n, const float* rays, const float* t_range, const srt_params* p, int32_t* hit_id, float* t, float* rgb_linear,
                          uint8_t* rgb8, srt_stats* stats) {
     return guarded([&] { return shade_rays_impl(s, n, rays, t_range, p, hit_id, t, rgb_linear, rgb8, stats); });
+}
+int srt_shade_paths_device(srt_scene* s, uint32_t n, const float* d_rays, const float* d_t_range, const srt_params* p, const srt_path_desc* path, void* stream,
+                           float* d_rgb_linear, uint8_t* d_rgb8, const srt_path_out* seg) {
+    return guarded([&] { return shade_paths_device_impl(s, n, d_rays, d_t_range, p, path, (hipStream_t)stream, d_rgb_linear, d_rgb8, seg, false); });
+}
+int srt_shade_paths(srt_scene* s, uint32_t n, const float* rays, const float* t_range, const srt_params* p, const srt_path_desc* path, float* rgb_linear, uint8_t* rgb8,
+                    const srt_path_out* seg, srt_stats* stats) {
+    return guarded([&] { return shade_paths_impl(s, n, rays, t_range, p, path, rgb_linear, rgb8, seg, stats); });
 }
 
 int srt_surface_rays_device(srt_scene* s, uint32_t n, const float* d_rays, const float* d_t_range, uint32_t flags, void* stream, int32_t* d_hit_id, float* d_t,

@@ -337,6 +337,64 @@ struct QueryShade {
     uint32_t spread;              // a wave owns 8 groups of 8 consecutive rays, the groups a 64th of the batch apart, instead of 64 consecutive rays
 };
 
+// Phase 2 of a shading query (the header comment above) for the 64 rays of one wave after their walk, as functions: k_query_path shades
+// every segment through them.  k_query_shade below still carries the same statements inline: called from there, the functions kept its
+// VGPR, scratch and LDS figures but moved the SGPR count of its four COUNT + INT_SHIN builds from 80 to 84 and rescheduled all sixteen
+// (profiles/shade_paths_kernels.txt), so that kernel was left as it was.  Whoever changes one changes the other: tests/test_gpu_shade_paths.py
+// compares the two bit for bit.  Two steps, because a kernel stores hit_id and t between them.
+// shade_hits_rank: the wave's hits are ranked; a hit gets its t (the winner's own bits) and its surface, and leaves its shadow origin and
+// its object's node range in the wave's LDS by rank.  A lane without a hit gets t = +inf and a surface that shades to nothing.
+struct WaveHits { uint32_t nh, rank; };       // hits in the wave; this lane's rank among them
+template <bool SMOOTH>
+__device__ __forceinline__ WaveHits shade_hits_rank(const DevScene& s, const bool is_hit, const int32_t id, const V3 o, const V3 d, float& t, Surface& f,
+                                                    float (*wray)[64]) {
+    t = __builtin_inff();
+    f.color = mk(0.0f, 0.0f, 0.0f); f.nrm = f.color; f.ka = 0.0f; f.ks = 0.0f; f.sh = 1.0f;
+    const unsigned long long hm = __ballot(is_hit);
+    const uint32_t nh = (uint32_t)__popcll(hm), rank = lane_prefix(hm);
+    __builtin_amdgcn_wave_barrier();                    // every lane has read its key: the slots are free
+    if (is_hit) {
+        V3 p1, e1, e2;
+        load_tri_edges(reinterpret_cast<const float4*>(s.tris), (size_t)id, p1, e1, e2);
+        t = ray_triangle(o, d, p1, e1, e2);             // the winner's t with its own bits (incl. the sign of a zero); the walk's value, hence in range
+        const V3 P = o + d * t;                         // shadowIntersection:325-326 in camera mode: so = o + d * t
+        const int2 self = s.obj_range[s.tri_obj[id]];
+        wray[0][rank] = P.x; wray[1][rank] = P.y; wray[2][rank] = P.z;
+        wray[3][rank] = __int_as_float(self.x); wray[4][rank] = __int_as_float(self.y);
+        f = surface_at(s, id, o, d, t, SMOOTH);
+    }
+    return WaveHits{ nh, rank };
+}
+// shade_hits_lights: the shadow rays of the wave's hits in chunks of 64 light samples, dealt to all 64 lanes, and each hit's light-sample sum.
+template <bool COUNT, bool INT_SHIN>
+__device__ __forceinline__ V3 shade_hits_lights(const DevScene& s, const QueryShade& p, const uint32_t lane, const bool is_hit, const WaveHits wh, const V3 o, const V3 d,
+                                                const float t, const Surface& f, float (*wray)[64], unsigned long long* best, unsigned long long& n_node_s,
+                                                unsigned long long& n_tri_s) {
+    const uint32_t nh = wh.nh, rank = wh.rank;
+    V3 sum = mk(0.0f, 0.0f, 0.0f);
+    for (uint32_t l0 = 0; l0 < p.n_lights; l0 += 64u) {                                             // wave-uniform
+        const uint32_t m = p.n_lights - l0 < 64u ? p.n_lights - l0 : 64u;
+        if (is_hit) best[rank] = 0ull;
+        __builtin_amdgcn_wave_barrier();
+        const uint32_t items = nh * m;                                                              // <= 4096
+        for (uint32_t w = lane; w < items; w += 64u) {
+            const uint32_t r = w / m, k = w - r * m;
+            const V3 so = mk(wray[0][r], wray[1][r], wray[2][r]);
+            const int2 self = make_int2(__float_as_int(wray[3][r]), __float_as_int(wray[4][r]));
+            const float* lp = p.lights + (size_t)(l0 + k) * 3;
+            const V3 sd = mk(lp[0], lp[1], lp[2]) - so;
+            if (any_hit_range<COUNT, true>(s, self, so, sd, n_node_s, n_tri_s)) atomicOr(&best[r], 1ull << k);
+        }
+        __builtin_amdgcn_wave_barrier();
+        if (is_hit) {
+            const unsigned long long mask = best[rank];
+            add_light_samples<INT_SHIN>(sum, f, o, d, t, p.lights, l0, m, p.shadow_div, [&](uint32_t l) -> bool { return (mask >> (l - l0)) & 1ull; });
+        }
+        __builtin_amdgcn_wave_barrier();
+    }
+    return sum;
+}
+
 template <bool COUNT, bool SMOOTH, bool INT_SHIN, bool RANGE>
 __global__ __launch_bounds__(256) void k_query_shade(DevScene s, uint32_t n_rays, const float* __restrict__ rays, uint32_t wide, QueryShade p,
                                                      int32_t* __restrict__ hit_id, float* __restrict__ t_out, float* __restrict__ rgb_linear,
@@ -442,6 +500,12 @@ __device__ __forceinline__ void store_rows(float* __restrict__ dst, const size_t
 #endif
 }
 
+// The mirrored direction of d at a surface with normal N (srt_surface_out.bounce, and the next segment of k_query_path).
+__device__ __forceinline__ V3 mirror_dir(const V3 d, const V3 N) {
+    const float k = (d.x * N.x + d.y * N.y) + d.z * N.z;
+    return mk(d.x - (N.x * k) * 2.0f, d.y - (N.y * k) * 2.0f, d.z - (N.z * k) * 2.0f);
+}
+
 // (is_hit, id, o, d, t, the surface there) -> the row of every wanted output.  Called by the whole wave (base < n_rays is wave-uniform).
 __device__ __forceinline__ void surface_store(const DevScene& s, const srt_surface_out& out, const size_t base, const uint32_t lane, const uint32_t rows,
                                               const bool is_hit, const int32_t id, const V3 o, const V3 d, const float t, const Surface& f, float* stage) {
@@ -461,8 +525,7 @@ __device__ __forceinline__ void surface_store(const DevScene& s, const srt_surfa
         store_rows<3>(out.material, base, lane, rows, v, stage);
     }
     if (out.bounce) {
-        const float k = (d.x * N.x + d.y * N.y) + d.z * N.z;
-        const V3 r = is_hit ? mk(d.x - (N.x * k) * 2.0f, d.y - (N.y * k) * 2.0f, d.z - (N.z * k) * 2.0f) : zero;
+        const V3 r = is_hit ? mirror_dir(d, N) : zero;
         const float v[6] = { P.x, P.y, P.z, r.x, r.y, r.z };
         store_rows<6>(out.bounce, base, lane, rows, v, stage);
     }
@@ -531,4 +594,130 @@ __global__ __launch_bounds__(256) void k_query_surface_hits(DevScene s, uint32_t
     if (is_hit) f = surface_at(s, id, o, d, t, SMOOTH);
     const size_t left = (size_t)n_rays - base;
     surface_store(s, out, base, lane, (uint32_t)(left < 64 ? left : 64), is_hit, id, o, d, t, f, stage_all[wave]);
+}
+
+// =================================================================================================
+// Mirror paths (srt_shade_paths): a ray followed through up to path.depth mirror bounces in ONE launch, every segment shaded as
+// srt_shade_rays_range shades it, the segments mixed by a per-object reflectance, the finished pixel written.  The kernel restates nothing:
+// a segment is query_walk<COUNT, true, MergeClosest> (a NULL interval runs as (NaN, NaN), as in k_query_multi), then k_query_shade's
+// phase 2 as it stands (shade_hits_rank, shade_hits_lights), and the next segment's ray is (o + d * t, mirror_dir(d, f.nrm)) -- the
+// bounce row of surface_store -- with the interval (bounce_t_min, +inf).  What the chain of launches hands on through HBM -- the mirrored
+// ray, the interval, the object, the colour -- stays in registers here, and each mirrored ray is walked once instead of twice.
+// The loop over segments is wave-uniform.  A lane whose path has ended goes into the walk with live = false (no node is read, no pair
+// pushed; it still tests queued pairs of its neighbours) and has no hit, so phase 2 gives it no work; the wave leaves the loop when no
+// lane is alive and then writes the miss rows of the segments left.  The walks are purely geometric: reflectance ends no path and
+// skips no walk.
+// The mix runs from the near end, so that a lane carries acc (3), W (1) and ONE pending segment (its sum, 3, and its reflectance, 1)
+// instead of an array of depth colours: segment b's weight W * (1 - k_b) needs to know whether segment b + 1 hit, so b's sum waits
+// while b + 1 is walked and is added then; the last pending segment is added after the loop with k = 0.
+// LDS: k_query_shade<.., RANGE = true>'s, reused per segment.  The rays' 8 x 64 slots are, in turn, the walk's rays, phase 2's ranked
+// hits and the stage of the transposed row stores.  The deal of rays to waves is k_query_shade's, QueryShade::spread included; under
+// spread a wave's rays are 8 groups of 8 consecutive rays, so rows go out through store_rows_dealt, which is store_rows with the ray of
+// a lane given by the deal instead of base + lane (without spread the addresses are store_rows' own).
+// seg's rows are segment-major: row b of a field starts n_rays elements (x 3, x 6) after row b - 1.
+// counters: as k_query_shade's, summed over the segments walked; a hit counts once per segment.
+// =================================================================================================
+template <int K, typename RayOf>
+__device__ __forceinline__ void store_rows_dealt(float* __restrict__ dst, const uint32_t lane, const size_t n_rays, const float (&v)[K], float* stage, RayOf ray_of) {
+#ifdef SRT_SURFACE_LANE_STORES
+    const size_t r = ray_of(lane);
+    if (r < n_rays) {
+        #pragma unroll
+        for (int c = 0; c < K; c++) dst[r * K + c] = v[c];
+    }
+#else
+    #pragma unroll
+    for (int c = 0; c < K; c++) stage[lane * K + c] = v[c];
+    __builtin_amdgcn_wave_barrier();
+    #pragma unroll
+    for (int j = 0; j < K; j++) {
+        const uint32_t w = (uint32_t)j * 64u + lane, l = w / (uint32_t)K, c = w - l * (uint32_t)K;      // word w of the stage: lane l's component c
+        const size_t r = ray_of(l);
+        if (r < n_rays) dst[r * K + c] = stage[w];
+    }
+    __builtin_amdgcn_wave_barrier();                    // the next output reuses the stage
+#endif
+}
+
+template <bool COUNT, bool SMOOTH, bool INT_SHIN>
+__global__ __launch_bounds__(256) void k_query_path(DevScene s, uint32_t n_rays, const float* __restrict__ rays, uint32_t wide, QueryShade p, QueryRange tr,
+                                                    srt_path_desc path, float* __restrict__ rgb_linear, uint8_t* __restrict__ rgb8, srt_path_out seg,
+                                                    unsigned long long* __restrict__ counters) {
+    __shared__ uint32_t q_all[4][QCAP];
+    __shared__ unsigned long long best_all[256];
+    __shared__ float ray_all[4][8][64];
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    unsigned long long* best = best_all + wave * 64;
+    float (*wray)[64] = ray_all[wave];
+    float* stage = &wray[0][0];
+    const size_t n_waves = (size_t)gridDim.x * 4, wv = (size_t)blockIdx.x * 4 + wave, n = (size_t)n_rays;
+    const uint32_t spread = p.spread;
+    const auto ray_of = [=](const uint32_t l) -> size_t { return spread ? ((size_t)(l >> 3) * n_waves + wv) * 8 + (l & 7u) : wv * 64 + l; };
+    const size_t ri = ray_of(lane);
+    const bool live = ri < n;
+    unsigned long long n_node = 0, n_tri = 0, n_node_s = 0, n_tri_s = 0;
+    V3 o = mk(0.0f, 0.0f, 0.0f), d = mk(0.0f, 0.0f, 1.0f);
+    float t_min = __builtin_nanf(""), t_max = __builtin_nanf("");
+    if (live) load_ray(rays, ri, wide != 0, o, d);
+    if (tr.t && live) load_range(tr, ri, t_min, t_max);
+    V3 acc = mk(0.0f, 0.0f, 0.0f), pend = acc;          // the mix so far; the sum of the segment that waits for its weight
+    float W = 1.0f, pend_k = 0.0f;                      // the weight of what follows; the waiting segment's reflectance
+    bool alive = live, waiting = false, hit0 = false;
+    uint32_t b = 0;
+    for (; b < path.depth && __ballot(alive); b++) {                                                // wave-uniform
+        query_walk<COUNT, true>(s, alive, o, d, lane, q_all[wave], MergeClosest{ best }, wray, n_node, n_tri, t_min, t_max);
+        const unsigned long long key = alive ? best[lane] : ~0ull;
+        const bool is_hit = key != ~0ull;
+        const int32_t id = is_hit ? (int32_t)(uint32_t)key : -1;
+        float t;
+        Surface f;
+        const WaveHits wh = shade_hits_rank<SMOOTH>(s, is_hit, id, o, d, t, f, wray);
+        const int32_t obj = is_hit ? s.tri_obj[id] : -1;
+        const size_t row = (size_t)b * n;
+        if (live) {
+            if (seg.hit_id) seg.hit_id[row + ri] = id;
+            if (seg.t) seg.t[row + ri] = t;
+            if (seg.obj) seg.obj[row + ri] = obj;
+        }
+        const V3 sum = shade_hits_lights<COUNT, INT_SHIN>(s, p, lane, is_hit, wh, o, d, t, f, wray, best, n_node_s, n_tri_s);
+        __builtin_amdgcn_wave_barrier();                // phase 2 is over: the rays' slots are the stage
+        if (seg.rgb_linear) { const float v[3] = { sum.x, sum.y, sum.z }; store_rows_dealt<3>(seg.rgb_linear + row * 3, lane, n, v, stage, ray_of); }
+        if (seg.rays) {
+            const float v[6] = { alive ? o.x : 0.0f, alive ? o.y : 0.0f, alive ? o.z : 0.0f, alive ? d.x : 0.0f, alive ? d.y : 0.0f, alive ? d.z : 0.0f };
+            store_rows_dealt<6>(seg.rays + row * 6, lane, n, v, stage, ray_of);
+        }
+        if (counters) count_hits(counters, is_hit, blockIdx.x);
+        if (waiting) {                                  // segment b - 1 hit: its weight is known now
+            const float k = is_hit ? pend_k : 0.0f, a = W * (1.0f - k);
+            acc = mk(acc.x + a * pend.x, acc.y + a * pend.y, acc.z + a * pend.z);
+            W = W * k;
+        }
+        waiting = is_hit;
+        if (b == 0) hit0 = is_hit;
+        if (is_hit) {
+            pend = sum;
+            pend_k = path.reflectance ? path.reflectance[obj] : 0.0f;
+            const V3 P = o + d * t;                     // the bounce row of surface_store: the point, not moved, and the mirrored direction
+            d = mirror_dir(d, f.nrm);
+            o = P;
+            t_min = path.bounce_t_min; t_max = __builtin_inff();
+        }
+        alive = is_hit;
+    }
+    if (waiting) {                                      // the last segment that hit: nothing follows it, k = 0
+        const float a = W * (1.0f - 0.0f);
+        acc = mk(acc.x + a * pend.x, acc.y + a * pend.y, acc.z + a * pend.z);
+    }
+    for (; b < path.depth; b++) {                       // wave-uniform: the segments no lane of the wave walked are miss rows
+        const size_t row = (size_t)b * n;
+        if (live) {
+            if (seg.hit_id) seg.hit_id[row + ri] = -1;
+            if (seg.t) seg.t[row + ri] = __builtin_inff();
+            if (seg.obj) seg.obj[row + ri] = -1;
+        }
+        if (seg.rgb_linear) { const float v[3] = { 0.0f, 0.0f, 0.0f }; store_rows_dealt<3>(seg.rgb_linear + row * 3, lane, n, v, stage, ray_of); }
+        if (seg.rays) { const float v[6] = { 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f }; store_rows_dealt<6>(seg.rays + row * 6, lane, n, v, stage, ray_of); }
+    }
+    if (live) store_pixel(rgb_linear, rgb8, ri, acc, hit0, p.reinhard, p.gamma, p.bg);
+    if (COUNT) { wave_add(counters + 1, n_node); wave_add(counters + 2, n_tri); wave_add(counters + 3, n_node_s); wave_add(counters + 4, n_tri_s); }
 }

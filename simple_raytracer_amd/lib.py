@@ -24,7 +24,7 @@ ABI_SYMBOLS = ("srt_params_default", "srt_light_staircase", "srt_rows_owned", "s
                "srt_trace_rays_device", "srt_trace_rays", "srt_occluded_device", "srt_occluded", "srt_shade_rays_device", "srt_shade_rays",
                "srt_trace_rays_range_device", "srt_trace_rays_range", "srt_occluded_range_device", "srt_occluded_range",
                "srt_trace_rays_multi_device", "srt_trace_rays_multi", "srt_shade_rays_range_device", "srt_shade_rays_range",
-               "srt_surface_rays_device", "srt_surface_rays", "srt_surface_hits_device", "srt_surface_hits")
+               "srt_surface_rays_device", "srt_surface_rays", "srt_surface_hits_device", "srt_surface_hits", "srt_shade_paths_device", "srt_shade_paths")
 MULTI_HIT_MAX = 16                # SRT_MULTI_HIT_MAX
 
 _f32p, _i32p, _u8p, _u32p = C.POINTER(C.c_float), C.POINTER(C.c_int32), C.POINTER(C.c_uint8), C.POINTER(C.c_uint32)
@@ -126,6 +126,12 @@ def load(path=None):
         L.srt_surface_hits_device.restype = C.c_int
         L.srt_surface_hits.argtypes = [C.c_void_p, C.c_uint32, _f32p, _i32p, _f32p, C.c_uint32, C.POINTER(abi.SurfaceOut)]
         L.srt_surface_hits.restype = C.c_int
+        L.srt_shade_paths_device.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(abi.Params), C.POINTER(abi.PathDesc), C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.POINTER(abi.PathOut)]
+        L.srt_shade_paths_device.restype = C.c_int
+        L.srt_shade_paths.argtypes = [C.c_void_p, C.c_uint32, _f32p, _f32p, C.POINTER(abi.Params), C.POINTER(abi.PathDesc), _f32p, _u8p, C.POINTER(abi.PathOut),
+                                      C.POINTER(abi.Stats)]
+        L.srt_shade_paths.restype = C.c_int
         L.srt_strerror.argtypes = [C.c_int]
         L.srt_strerror.restype = C.c_char_p
         L.srt_last_hip_error.restype = C.c_int
@@ -455,6 +461,50 @@ class DeviceScene:
         so = abi.SurfaceOut(obj or None, point or None, normal or None, color or None, material or None, bounce or None)
         _check(self.L.srt_surface_hits_device(self.h, n, C.c_void_p(rays), C.c_void_p(hit_id), C.c_void_p(t), abi.SRT_FLAG_SMOOTH_NORMALS if smooth else 0,
                                               C.c_void_p(stream), C.byref(so)), "srt_surface_hits_device")
+
+    def shade_paths(self, rays, params: abi.Params, depth, reflectance=None, bounce_t_min=1e-3, t_range=None,
+                    want=("rgb_linear", "rgb8", "seg_hit_id", "seg_t", "seg_obj", "seg_rgb_linear", "seg_rays"), count=False, smooth=False):
+        """srt_shade_paths: every ray of `rays` (n x 6, host array) followed through up to `depth` mirror bounces, each hit shaded as
+        shade_rays(t_range=...) shades it, the segments mixed by `reflectance` (one float per object, or None = all 0).  A mirrored ray's
+        interval is (bounce_t_min, +inf); t_range (n x 2) bounds segment 0.  Returns a dict of the arrays named in `want` -- rgb_linear
+        n x 3 (mixed), rgb8 n x 3, and per segment seg_hit_id / seg_t / seg_obj depth x n, seg_rgb_linear depth x n x 3, seg_rays
+        depth x n x 6 -- + 'stats'.  count / smooth add SRT_FLAG_COUNT_WORK / SRT_FLAG_SMOOTH_NORMALS for this call."""
+        r = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
+        n = r.shape[0]
+        tr = _t_range(t_range, n)
+        refl = None if reflectance is None else np.ascontiguousarray(reflectance, np.float32).reshape(-1)
+        out = {}
+        if "rgb_linear" in want: out["rgb_linear"] = np.empty((n, 3), np.float32)
+        if "rgb8" in want: out["rgb8"] = np.empty((n, 3), np.uint8)
+        po = abi.PathOut()
+        rows = max(int(depth), 0)
+        for name, (ty, k) in abi.PATH_FIELDS.items():
+            if "seg_" + name in want:
+                out["seg_" + name] = np.empty((rows, n) if k == 1 else (rows, n, k), ty)
+                setattr(po, name, out["seg_" + name].ctypes.data)
+        pd = abi.PathDesc(depth, bounce_t_min, refl.ctypes.data if refl is not None else None)
+        st = abi.Stats()
+        g = lambda k, ty: out[k].ctypes.data_as(ty) if k in out else ty()
+        flags = params.flags
+        params.flags = flags | (abi.SRT_FLAG_COUNT_WORK if count else 0) | (abi.SRT_FLAG_SMOOTH_NORMALS if smooth else 0)
+        try:
+            rc = self.L.srt_shade_paths(self.h, n, r.ctypes.data_as(_f32p), tr.ctypes.data_as(_f32p) if tr is not None else None, C.byref(params), C.byref(pd),
+                                        g("rgb_linear", _f32p), g("rgb8", _u8p), C.byref(po), C.byref(st))
+        finally:
+            params.flags = flags
+        _check(rc, "srt_shade_paths")
+        out["stats"] = st.as_dict()
+        return out
+
+    def shade_paths_device(self, n, rays, params: abi.Params, depth, reflectance=0, bounce_t_min=1e-3, t_range=None, stream=0, rgb_linear=0, rgb8=0, seg_hit_id=0,
+                           seg_t=0, seg_obj=0, seg_rgb_linear=0, seg_rays=0):
+        """srt_shade_paths_device: raw device pointers (ints, e.g. torch.Tensor.data_ptr()) in, asynchronous on `stream`, one launch.  The
+        light table of `params` is a host array; `reflectance` is a DEVICE pointer to n_objects floats (0 = all 0); t_range a device
+        pointer to n x 2 floats, or None; the seg_* outputs are depth x n rows, segment-major.  The flags are those of `params`."""
+        pd = abi.PathDesc(depth, bounce_t_min, reflectance or None)
+        po = abi.PathOut(seg_hit_id or None, seg_t or None, seg_obj or None, seg_rgb_linear or None, seg_rays or None)
+        _check(self.L.srt_shade_paths_device(self.h, n, C.c_void_p(rays), C.c_void_p(t_range or 0), C.byref(params), C.byref(pd), C.c_void_p(stream),
+                                             C.c_void_p(rgb_linear), C.c_void_p(rgb8), C.byref(po)), "srt_shade_paths_device")
 
     def sync(self):
         st = abi.Stats()
