@@ -587,6 +587,44 @@ int srt_shade_paths_device(srt_scene* s, uint32_t n, const float* d_rays, const 
 int srt_shade_paths(srt_scene* s, uint32_t n, const float* rays, const float* t_range, const srt_params* p,
                     const srt_path_desc* path, float* rgb_linear, uint8_t* rgb8, const srt_path_out* seg, srt_stats* stats);
 
+/* Mirror paths in a frame: srt_shade_paths for the rays of a frame's own pixels, in ONE launch and with no ray array -- a pixel's ray is made
+ * on the device, as srt_render_device makes it.  Unless said here everything is as for srt_shade_paths: the definition of a path, the mix,
+ * seg, the one-light-table-per-handle rule, the ordering on `stream`, srt_scene_share.
+ * PIXELS.  n = srt_rows_owned(p) x srt_cols_owned(p) local pixels, row-major; local pixel <-> image pixel by srt_params' block_rows /
+ * block_first / block_stride / block_cols.  rgb_linear (n x 3) and rgb8 (n x 3) are laid out exactly as srt_render_device lays them out;
+ * every field of seg is depth x n, segment-major: row b starts at element offset b * n (x 3 for rgb_linear, x 6 for rays).  Padding pixels of
+ * a tile deal (image column >= width) are not written in any output.
+ * THE RAY of a pixel is the frame's own: direction (i, j, focal) with i = x + (int)(-W / 2), j = y + (int)(-H / 2), plus the sub-pixel
+ * offsets for spp > 1; with ray_matrix M the direction is (M[0] * dx + M[1] * dy) + M[2] * dz and the origin M[3].xyz, without it the origin
+ * is (0, 0, 0) and the direction (dx, dy, dz) as it stands -- the bits the identity matrix gives.
+ * spp == 1: every output of a live pixel is bit for bit what srt_shade_paths gives for that ray with a NULL t_range, the same p (lights,
+ * literals, flags) and the same path: the mixed rgb_linear and rgb8 with the background rule, and every row of seg.
+ * spp = m x m > 1: sub-sample k has srt_render_device's offsets, ((k % m) + 0.5) / m - 0.5 in x and ((k / m) + 0.5) / m - 0.5 in y, added to
+ * dir.xy before the matrix.  The mixed sums acc_k of the sub-samples are added in the order k = 0, 1, ... starting from acc_0, one f32 add a
+ * component; each component is divided by (float)spp; tone map, quantiser and the black -> background rule run once on the quotient.  seg
+ * reports sub-sample 0.  All sub-samples run in the one launch; there are no accumulation buffers.
+ * Identities:  depth 1: rgb_linear and rgb8 are srt_render_device's for the same p, and rows 0 of seg.hit_id / seg.t its hit_id / t -- in
+ *              camera mode and without a matrix, at any spp.  A call that owns a share of the frame writes exactly the whole-frame call's
+ *              values at its owned pixels.  Results do not depend on how pixels are dealt to waves.
+ * Flags: SRT_FLAG_COUNT_WORK and SRT_FLAG_SMOOTH_NORMALS as in srt_shade_paths; SRT_FLAG_NO_TIMING and SRT_FLAG_FRAMES_IN_FLIGHT are accepted
+ * and ignored (the call records no events), so that a p prepared for srt_render_device can be reused; any other bit, the variant bits 8..15
+ * included: SRT_ERR_ARG.
+ * Errors, all before anything is touched: whatever srt_render_device rejects in the frame fields (sizes, block fields, spp), with its codes;
+ * whatever srt_shade_paths rejects -- NULL path, depth 0 or above SRT_PATH_DEPTH_MAX, smooth normals on a scene without normals, n_lights > 0
+ * with NULL light_pos, n x max(n_lights, 1) >= 2^32.  A call with every output NULL returns SRT_OK and launches nothing.
+ * It is a query-family call: it uses the handle's query light table and query counter set, and leaves alone srt_sync, srt_scene_pipeline,
+ * the renders' alternating counter sets and their workspaces.  The _device form is one kernel launch; it allocates and copies nothing
+ * proportional to n; path->reflectance is read from DEVICE memory.  Without SRT_FLAG_COUNT_WORK, and with the light table already on the
+ * device, it may be captured into a hipGraph.
+ * The host form stages no rays; the reflectance table and the wanted outputs go through the handle's pinned block and buffers, and the call
+ * waits.  *stats (may be NULL): primary_rays = owned image pixels x spp (padding excluded), hit_rays = the hits of all segments of all
+ * sub-samples, shadow_rays = hit_rays x n_lights; under SRT_FLAG_COUNT_WORK the four test counters are the sums of what srt_shade_paths
+ * reports for those rays. */
+int srt_render_paths_device(srt_scene* s, const srt_params* p, const srt_path_desc* path, void* stream,
+                            float* d_rgb_linear /* n x 3, mixed */, uint8_t* d_rgb8 /* n x 3 */, const srt_path_out* seg);
+int srt_render_paths(srt_scene* s, const srt_params* p, const srt_path_desc* path,
+                     float* rgb_linear, uint8_t* rgb8, const srt_path_out* seg, srt_stats* stats);
+
 /* Device-resident size of the scene records and the per-record algorithmic byte sizes used by
  * the bytes model: 32 B per node test, 36 B per triangle test. */
 uint64_t srt_scene_device_bytes(const srt_scene* s);

@@ -1704,6 +1704,37 @@ static int shade_paths_device_impl(srt_scene* s, uint32_t n, const float* d_rays
     return SRT_OK;
 }
 
+// srt_render_paths: mirror paths for the pixels of a frame, one launch (k_render_path).  A query-family call: the handle's query light table
+// and query counter set; the render's counter sets, workspaces, event ring and pipeline string are left alone.
+static int check_render_paths(const srt_scene* s, const srt_params* p, const srt_path_desc* path) {
+    if (!s || !p) return SRT_ERR_ARG;
+    if (p->flags & ~(uint32_t)(SRT_FLAG_COUNT_WORK | SRT_FLAG_SMOOTH_NORMALS | SRT_FLAG_NO_TIMING | SRT_FLAG_FRAMES_IN_FLIGHT)) return SRT_ERR_ARG;      // (variant bits included)
+    SRT_TRY(check_frame(scene_facts(s), p));
+    if (!path || path->depth == 0) return SRT_ERR_ARG;
+    if (path->depth > SRT_PATH_DEPTH_MAX) return SRT_ERR_LIMIT;
+    if ((uint64_t)srt_rows_owned(p) * srt_cols_owned(p) * (p->n_lights ? p->n_lights : 1) >= (1ull << 32)) return SRT_ERR_LIMIT;
+    return SRT_OK;
+}
+static int render_paths_device_impl(srt_scene* s, const srt_params* p, const srt_path_desc* path, hipStream_t stream, float* d_rgb_linear, uint8_t* d_rgb8,
+                                    const srt_path_out* seg, bool count_hits) {
+    SRT_TRY(check_render_paths(s, p, path));
+    const uint32_t rows = srt_rows_owned(p), wl = srt_cols_owned(p);
+    if (!rows || !wl || (!count_hits && !paths_wanted(d_rgb_linear, d_rgb8, seg))) return SRT_OK;
+    const bool count = (p->flags & SRT_FLAG_COUNT_WORK) != 0, smooth = (p->flags & SRT_FLAG_SMOOTH_NORMALS) != 0;
+    QueryLaunch q;
+    SRT_TRY(query_prologue(s, 0, stream, p, count || count_hits, &q));
+    const DevParams dp = dev_params(s, p, FramePlan{}).hit;      // the frame's geometry only: the kernel takes lights and literals from QueryShade
+    static const decltype(&k_render_path<false, false, false>) builds[8] = {
+        &k_render_path<false, false, false>, &k_render_path<false, false, true>, &k_render_path<false, true, false>, &k_render_path<false, true, true>,
+        &k_render_path<true, false, false>,  &k_render_path<true, false, true>,  &k_render_path<true, true, false>,  &k_render_path<true, true, true> };
+    const auto k = builds[(count ? 4 : 0) | (smooth ? 2 : 0) | (s->rec->int_shin ? 1 : 0)];
+    const uint32_t m = (uint32_t)std::lround(std::sqrt((double)p->spp));      // (m x m == spp: check_frame)
+    hipLaunchKernelGGL(k, dim3((wl + 15) / 16, (rows + 15) / 16), dim3(256), 0, q.stream, s->dev, dp, p->spp, m, query_shade(s, p), *path, d_rgb_linear, d_rgb8,
+                       seg ? *seg : srt_path_out{}, q.ctr);
+    HIP_TRY(hipGetLastError());
+    return SRT_OK;
+}
+
 // srt_surface_rays / srt_surface_hits: the surface under each hit and the mirrored ray (k_query_surface, k_query_surface_hits)
 static int check_surface(const srt_scene* s, uint32_t n, const float* rays, uint32_t flags, uint32_t allowed) {
     if (!s || (n && !rays) || (flags & ~allowed)) return SRT_ERR_ARG;
@@ -1753,17 +1784,19 @@ static int surface_hits_device_impl(srt_scene* s, uint32_t n, const float* d_ray
 static int stage_rays(srt_scene* s, uint32_t n, const float* rays, const float* t_range, const int32_t* skip_obj, const float* t_in, hipStream_t st,
                       const float* refl = nullptr, uint32_t n_refl = 0) {
     auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t o_rays = 0, o_skip = pad((size_t)n * 24), o_range = o_skip + (skip_obj ? pad((size_t)n * 4) : 0), o_tin = o_range + (t_range ? pad((size_t)n * 8) : 0),
+    const size_t o_rays = 0, o_skip = rays ? pad((size_t)n * 24) : 0, o_range = o_skip + (skip_obj ? pad((size_t)n * 4) : 0), o_tin = o_range + (t_range ? pad((size_t)n * 8) : 0),
                  o_refl = o_tin + (t_in ? pad((size_t)n * 4) : 0), total = o_refl + (refl ? pad((size_t)n_refl * 4) : 0);
-    SRT_TRY(grow(s, n, s->rq_rays));
+    if (rays) SRT_TRY(grow(s, n, s->rq_rays));
     if (skip_obj) SRT_TRY(grow(s, n, s->rq_skip));
     if (t_range) SRT_TRY(grow(s, n, s->rq_range));
     if (t_in) SRT_TRY(grow(s, n, s->rq_tin));
     if (refl) SRT_TRY(grow(s, n_refl, s->rq_refl));
     char* h = nullptr;
     SRT_TRY(stage_acquire(s, total, &h));
-    std::memcpy(h + o_rays, rays, (size_t)n * 24);
-    HIP_TRY(hipMemcpyAsync(s->rq_rays, h + o_rays, (size_t)n * 24, hipMemcpyHostToDevice, st));
+    if (rays) {                                               // (srt_render_paths brings none: a frame's rays are made on the device)
+        std::memcpy(h + o_rays, rays, (size_t)n * 24);
+        HIP_TRY(hipMemcpyAsync(s->rq_rays, h + o_rays, (size_t)n * 24, hipMemcpyHostToDevice, st));
+    }
     if (skip_obj) {
         std::memcpy(h + o_skip, skip_obj, (size_t)n * 4);
         HIP_TRY(hipMemcpyAsync(s->rq_skip, h + o_skip, (size_t)n * 4, hipMemcpyHostToDevice, st));
@@ -1902,6 +1935,40 @@ static int shade_paths_impl(srt_scene* s, uint32_t n, const float* rays, const f
     return stats ? query_stats(s, n, p->n_lights, stats) : SRT_OK;
 }
 
+// srt_render_paths: as shade_paths_impl, with n the call's local pixels and no rays to stage; primary_rays counts image pixels x spp
+static int render_paths_impl(srt_scene* s, const srt_params* p, const srt_path_desc* path, float* rgb_linear, uint8_t* rgb8, const srt_path_out* seg, srt_stats* stats) {
+    SRT_TRY(check_render_paths(s, p, path));
+    if (stats) std::memset(stats, 0, sizeof(*stats));
+    const uint32_t n = srt_rows_owned(p) * srt_cols_owned(p);      // (< 2^32: check_render_paths)
+    if (!n || (!stats && !paths_wanted(rgb_linear, rgb8, seg))) return SRT_OK;
+    const srt_path_out h = seg ? *seg : srt_path_out{};
+    const size_t D = path->depth;
+    const auto o_lin = query_out(rgb_linear, s->rq_lin); const auto o_rgb8 = query_out(rgb8, s->rq_rgb8);
+    const auto o_hit = query_out(h.hit_id, s->rq_hit, D); const auto o_t = query_out(h.t, s->rq_t, D); const auto o_obj = query_out(h.obj, s->rq_sobj, D);
+    const auto o_slin = query_out(h.rgb_linear, s->rq_plin, D); const auto o_rays = query_out(h.rays, s->rq_sbounce, D);
+    const bool padded = p->block_cols != 0;      // padding pixels are not written: what the handle's buffers hold there must not reach the caller
+    SRT_TRY(query_round_trip_refl(s, n, nullptr, nullptr, nullptr, nullptr, path->reflectance, path->reflectance ? s->dev.n_objects : 0u, [&](hipStream_t st) -> int {
+        const srt_path_desc dpath = { path->depth, path->bounce_t_min, path->reflectance ? s->rq_refl.p : nullptr };
+        const srt_path_out dev = { o_hit.wanted(), o_t.wanted(), o_obj.wanted(), o_slin.wanted(), o_rays.wanted() };
+        if (padded) {
+            // The caller's arrays first, so that the copy out returns their padding as it was.  hipMemcpy from pageable memory returns when
+            // the data is on the device, so the launch enqueued on st below is ordered behind these copies without an event.  It costs a
+            // second transfer of the size of the result (a tile deal in the host form is the rare case; a row-wise copy out of the live
+            // columns would save it).
+            hipError_t e = hipSuccess;
+            const auto up = [&](void* d, const void* src, size_t bytes) { if (src && e == hipSuccess) e = hipMemcpy(d, src, bytes, hipMemcpyHostToDevice); };
+            up(dev.hit_id, h.hit_id, D * n * 4); up(dev.t, h.t, D * n * 4); up(dev.obj, h.obj, D * n * 4); up(dev.rgb_linear, h.rgb_linear, D * n * 12);
+            up(dev.rays, h.rays, D * n * 24); up(o_lin.wanted(), rgb_linear, (size_t)n * 12); up(o_rgb8.wanted(), rgb8, (size_t)n * 3);
+            HIP_TRY(e);
+        }
+        return render_paths_device_impl(s, p, &dpath, st, o_lin.wanted(), o_rgb8.wanted(), &dev, stats != nullptr);
+    }, o_lin, o_rgb8, o_hit, o_t, o_obj, o_slin, o_rays));
+    if (!stats) return SRT_OK;
+    SRT_TRY(query_stats(s, n, p->n_lights, stats));
+    stats->primary_rays = pixels_owned(p) * p->spp;
+    return SRT_OK;
+}
+
 // The host forms of the surface queries: the caller's srt_surface_out names host arrays; `dev` names the handle's buffers for the wanted ones.
 static int surface_rays_impl(srt_scene* s, uint32_t n, const float* rays, const float* t_range, uint32_t flags, int32_t* hit_id, float* t, const srt_surface_out* out,
                              srt_stats* stats) {
@@ -1987,6 +2054,12 @@ int srt_shade_paths_device(srt_scene* s, uint32_t n, const float* d_rays, const 
 int srt_shade_paths(srt_scene* s, uint32_t n, const float* rays, const float* t_range, const srt_params* p, const srt_path_desc* path, float* rgb_linear, uint8_t* rgb8,
                     const srt_path_out* seg, srt_stats* stats) {
     return guarded([&] { return shade_paths_impl(s, n, rays, t_range, p, path, rgb_linear, rgb8, seg, stats); });
+}
+int srt_render_paths_device(srt_scene* s, const srt_params* p, const srt_path_desc* path, void* stream, float* d_rgb_linear, uint8_t* d_rgb8, const srt_path_out* seg) {
+    return guarded([&] { return render_paths_device_impl(s, p, path, (hipStream_t)stream, d_rgb_linear, d_rgb8, seg, false); });
+}
+int srt_render_paths(srt_scene* s, const srt_params* p, const srt_path_desc* path, float* rgb_linear, uint8_t* rgb8, const srt_path_out* seg, srt_stats* stats) {
+    return guarded([&] { return render_paths_impl(s, p, path, rgb_linear, rgb8, seg, stats); });
 }
 
 int srt_surface_rays_device(srt_scene* s, uint32_t n, const float* d_rays, const float* d_t_range, uint32_t flags, void* stream, int32_t* d_hit_id, float* d_t,

@@ -639,33 +639,23 @@ __device__ __forceinline__ void store_rows_dealt(float* __restrict__ dst, const 
 #endif
 }
 
-template <bool COUNT, bool SMOOTH, bool INT_SHIN>
-__global__ __launch_bounds__(256) void k_query_path(DevScene s, uint32_t n_rays, const float* __restrict__ rays, uint32_t wide, QueryShade p, QueryRange tr,
-                                                    srt_path_desc path, float* __restrict__ rgb_linear, uint8_t* __restrict__ rgb8, srt_path_out seg,
-                                                    unsigned long long* __restrict__ counters) {
-    __shared__ uint32_t q_all[4][QCAP];
-    __shared__ unsigned long long best_all[256];
-    __shared__ float ray_all[4][8][64];
-    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    unsigned long long* best = best_all + wave * 64;
-    float (*wray)[64] = ray_all[wave];
+// The segments of the paths of one wave's 64 rays (the header comment above), shared by k_query_path and k_render_path: the walk, phase 2,
+// the per-segment rows, the mirrored ray and the near-end mix.  ri: the lane's row in every output (seg's rows are n apart), ray_of: the
+// same for any lane of the wave (>= n: a lane without a ray) -- the transposed row stores need it.  seg: all NULL = no per-segment rows.
+// shard: where the wave's hits are counted.  Returns the mixed sum; hit0: whether segment 0 hit.
+template <bool COUNT, bool SMOOTH, bool INT_SHIN, typename RayOf>
+__device__ __forceinline__ V3 path_segments(const DevScene& s, const QueryShade& p, const srt_path_desc& path, const srt_path_out& seg, const size_t n, const size_t ri,
+                                            const bool live, V3 o, V3 d, float t_min, float t_max, const uint32_t lane, uint32_t* q, unsigned long long* best,
+                                            float (*wray)[64], const RayOf ray_of, unsigned long long* __restrict__ counters, const uint32_t shard, bool& hit0,
+                                            unsigned long long& n_node, unsigned long long& n_tri, unsigned long long& n_node_s, unsigned long long& n_tri_s) {
     float* stage = &wray[0][0];
-    const size_t n_waves = (size_t)gridDim.x * 4, wv = (size_t)blockIdx.x * 4 + wave, n = (size_t)n_rays;
-    const uint32_t spread = p.spread;
-    const auto ray_of = [=](const uint32_t l) -> size_t { return spread ? ((size_t)(l >> 3) * n_waves + wv) * 8 + (l & 7u) : wv * 64 + l; };
-    const size_t ri = ray_of(lane);
-    const bool live = ri < n;
-    unsigned long long n_node = 0, n_tri = 0, n_node_s = 0, n_tri_s = 0;
-    V3 o = mk(0.0f, 0.0f, 0.0f), d = mk(0.0f, 0.0f, 1.0f);
-    float t_min = __builtin_nanf(""), t_max = __builtin_nanf("");
-    if (live) load_ray(rays, ri, wide != 0, o, d);
-    if (tr.t && live) load_range(tr, ri, t_min, t_max);
     V3 acc = mk(0.0f, 0.0f, 0.0f), pend = acc;          // the mix so far; the sum of the segment that waits for its weight
     float W = 1.0f, pend_k = 0.0f;                      // the weight of what follows; the waiting segment's reflectance
-    bool alive = live, waiting = false, hit0 = false;
+    bool alive = live, waiting = false;
+    hit0 = false;
     uint32_t b = 0;
     for (; b < path.depth && __ballot(alive); b++) {                                                // wave-uniform
-        query_walk<COUNT, true>(s, alive, o, d, lane, q_all[wave], MergeClosest{ best }, wray, n_node, n_tri, t_min, t_max);
+        query_walk<COUNT, true>(s, alive, o, d, lane, q, MergeClosest{ best }, wray, n_node, n_tri, t_min, t_max);
         const unsigned long long key = alive ? best[lane] : ~0ull;
         const bool is_hit = key != ~0ull;
         const int32_t id = is_hit ? (int32_t)(uint32_t)key : -1;
@@ -686,7 +676,7 @@ __global__ __launch_bounds__(256) void k_query_path(DevScene s, uint32_t n_rays,
             const float v[6] = { alive ? o.x : 0.0f, alive ? o.y : 0.0f, alive ? o.z : 0.0f, alive ? d.x : 0.0f, alive ? d.y : 0.0f, alive ? d.z : 0.0f };
             store_rows_dealt<6>(seg.rays + row * 6, lane, n, v, stage, ray_of);
         }
-        if (counters) count_hits(counters, is_hit, blockIdx.x);
+        if (counters) count_hits(counters, is_hit, shard);
         if (waiting) {                                  // segment b - 1 hit: its weight is known now
             const float k = is_hit ? pend_k : 0.0f, a = W * (1.0f - k);
             acc = mk(acc.x + a * pend.x, acc.y + a * pend.y, acc.z + a * pend.z);
@@ -718,6 +708,78 @@ __global__ __launch_bounds__(256) void k_query_path(DevScene s, uint32_t n_rays,
         if (seg.rgb_linear) { const float v[3] = { 0.0f, 0.0f, 0.0f }; store_rows_dealt<3>(seg.rgb_linear + row * 3, lane, n, v, stage, ray_of); }
         if (seg.rays) { const float v[6] = { 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f }; store_rows_dealt<6>(seg.rays + row * 6, lane, n, v, stage, ray_of); }
     }
+    return acc;
+}
+
+template <bool COUNT, bool SMOOTH, bool INT_SHIN>
+__global__ __launch_bounds__(256) void k_query_path(DevScene s, uint32_t n_rays, const float* __restrict__ rays, uint32_t wide, QueryShade p, QueryRange tr,
+                                                    srt_path_desc path, float* __restrict__ rgb_linear, uint8_t* __restrict__ rgb8, srt_path_out seg,
+                                                    unsigned long long* __restrict__ counters) {
+    __shared__ uint32_t q_all[4][QCAP];
+    __shared__ unsigned long long best_all[256];
+    __shared__ float ray_all[4][8][64];
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const size_t n_waves = (size_t)gridDim.x * 4, wv = (size_t)blockIdx.x * 4 + wave, n = (size_t)n_rays;
+    const uint32_t spread = p.spread;
+    const auto ray_of = [=](const uint32_t l) -> size_t { return spread ? ((size_t)(l >> 3) * n_waves + wv) * 8 + (l & 7u) : wv * 64 + l; };
+    const size_t ri = ray_of(lane);
+    const bool live = ri < n;
+    unsigned long long n_node = 0, n_tri = 0, n_node_s = 0, n_tri_s = 0;
+    V3 o = mk(0.0f, 0.0f, 0.0f), d = mk(0.0f, 0.0f, 1.0f);
+    float t_min = __builtin_nanf(""), t_max = __builtin_nanf("");
+    if (live) load_ray(rays, ri, wide != 0, o, d);
+    if (tr.t && live) load_range(tr, ri, t_min, t_max);
+    bool hit0;
+    const V3 acc = path_segments<COUNT, SMOOTH, INT_SHIN>(s, p, path, seg, n, ri, live, o, d, t_min, t_max, lane, q_all[wave], best_all + wave * 64, ray_all[wave], ray_of,
+                                                          counters, blockIdx.x, hit0, n_node, n_tri, n_node_s, n_tri_s);
     if (live) store_pixel(rgb_linear, rgb8, ri, acc, hit0, p.reinhard, p.gamma, p.bg);
+    if (COUNT) { wave_add(counters + 1, n_node); wave_add(counters + 2, n_tri); wave_add(counters + 3, n_node_s); wave_add(counters + 4, n_tri_s); }
+}
+
+// =================================================================================================
+// Mirror paths in a frame (srt_render_paths): k_query_path's paths for the rays of a frame's own pixels.  The front end is the render
+// kernels': a wave owns one 8 x 8 pixel tile and a workgroup 16 x 16 (tile_pixel), the grid is 2-D over the call's local output, and a
+// pixel's ray is primary_dir / ray_origin under the call's block or tile deal -- nothing is loaded per ray, and the 64 rays of a wave are
+// neighbours that walk the same nodes.  Everything behind the ray is path_segments as k_query_path calls it; a lane's row in every output
+// is its local pixel r * W + px, so the transposed stores write a tile row's 8 pixels as one 96 B (192 B) run.  Padding pixels of a tile
+// deal and pixels beyond the frame are lanes without a ray: they walk nothing and write nothing.
+// spp = m x m > 1: the sub-samples run one after the other in this launch (the loop is wave-uniform), each with srt_render_device's
+// offsets added to dir.xy before the matrix; their mixed sums are added in order starting from sub-sample 0's, divided by (float)spp,
+// and the pixel leaves once, as k_accumulate / k_resolve make it (tone-mapped whatever was hit: a black quotient is the background).
+// seg's rows are sub-sample 0's.  counters: as k_query_path's, over all sub-samples; the hit shard is the 2-D workgroup number.
+// =================================================================================================
+template <bool COUNT, bool SMOOTH, bool INT_SHIN>
+__global__ __launch_bounds__(256) void k_render_path(DevScene s, DevParams fp, uint32_t spp, uint32_t spp_m, QueryShade p, srt_path_desc path,
+                                                     float* __restrict__ rgb_linear, uint8_t* __restrict__ rgb8, srt_path_out seg,
+                                                     unsigned long long* __restrict__ counters) {
+    __shared__ uint32_t q_all[4][QCAP];
+    __shared__ unsigned long long best_all[256];
+    __shared__ float ray_all[4][8][64];
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint32_t px, r;
+    const bool live = tile_pixel(fp, px, r);
+    const unsigned long long live_mask = __ballot(live);
+    const uint32_t tile_x = blockIdx.x * 16 + (wave & 1) * 8, tile_r = blockIdx.y * 16 + (wave >> 1) * 8, W = fp.W;
+    const auto ray_of = [=](const uint32_t l) -> size_t { return (live_mask >> l) & 1ull ? (size_t)(tile_r + (l >> 3)) * W + tile_x + (l & 7u) : ~(size_t)0; };
+    const size_t n = (size_t)fp.rows * W, ri = (size_t)r * W + px;
+    const uint32_t shard = blockIdx.y * gridDim.x + blockIdx.x, y = live ? image_row(fp, r) : 0u;
+    unsigned long long n_node = 0, n_tri = 0, n_node_s = 0, n_tri_s = 0;
+    const V3 o = ray_origin(fp);
+    V3 total = mk(0.0f, 0.0f, 0.0f);
+    bool hit0 = false;
+    for (uint32_t k = 0; k < spp; k++) {                                                            // wave-uniform
+        if (spp > 1) {
+            fp.sub_x = ((float)(k % spp_m) + 0.5f) / (float)spp_m - 0.5f;
+            fp.sub_y = ((float)(k / spp_m) + 0.5f) / (float)spp_m - 0.5f;
+        }
+        const V3 d = live ? primary_dir(fp, px, y) : mk(0.0f, 0.0f, 1.0f);
+        bool h;
+        const V3 acc = path_segments<COUNT, SMOOTH, INT_SHIN>(s, p, path, k == 0 ? seg : srt_path_out{}, n, ri, live, o, d, __builtin_nanf(""), __builtin_nanf(""), lane,
+                                                              q_all[wave], best_all + wave * 64, ray_all[wave], ray_of, counters, shard, h, n_node, n_tri, n_node_s, n_tri_s);
+        if (k == 0) { total = acc; hit0 = h; }
+        else total = mk(total.x + acc.x, total.y + acc.y, total.z + acc.z);
+    }
+    if (spp > 1) { const float f = (float)spp; total = mk(total.x / f, total.y / f, total.z / f); hit0 = true; }
+    if (live) store_pixel(rgb_linear, rgb8, ri, total, hit0, p.reinhard, p.gamma, p.bg);
     if (COUNT) { wave_add(counters + 1, n_node); wave_add(counters + 2, n_tri); wave_add(counters + 3, n_node_s); wave_add(counters + 4, n_tri_s); }
 }

@@ -24,7 +24,8 @@ ABI_SYMBOLS = ("srt_params_default", "srt_light_staircase", "srt_rows_owned", "s
                "srt_trace_rays_device", "srt_trace_rays", "srt_occluded_device", "srt_occluded", "srt_shade_rays_device", "srt_shade_rays",
                "srt_trace_rays_range_device", "srt_trace_rays_range", "srt_occluded_range_device", "srt_occluded_range",
                "srt_trace_rays_multi_device", "srt_trace_rays_multi", "srt_shade_rays_range_device", "srt_shade_rays_range",
-               "srt_surface_rays_device", "srt_surface_rays", "srt_surface_hits_device", "srt_surface_hits", "srt_shade_paths_device", "srt_shade_paths")
+               "srt_surface_rays_device", "srt_surface_rays", "srt_surface_hits_device", "srt_surface_hits", "srt_shade_paths_device", "srt_shade_paths",
+               "srt_render_paths_device", "srt_render_paths")
 MULTI_HIT_MAX = 16                # SRT_MULTI_HIT_MAX
 
 _f32p, _i32p, _u8p, _u32p = C.POINTER(C.c_float), C.POINTER(C.c_int32), C.POINTER(C.c_uint8), C.POINTER(C.c_uint32)
@@ -132,6 +133,10 @@ def load(path=None):
         L.srt_shade_paths.argtypes = [C.c_void_p, C.c_uint32, _f32p, _f32p, C.POINTER(abi.Params), C.POINTER(abi.PathDesc), _f32p, _u8p, C.POINTER(abi.PathOut),
                                       C.POINTER(abi.Stats)]
         L.srt_shade_paths.restype = C.c_int
+        L.srt_render_paths_device.argtypes = [C.c_void_p, C.POINTER(abi.Params), C.POINTER(abi.PathDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(abi.PathOut)]
+        L.srt_render_paths_device.restype = C.c_int
+        L.srt_render_paths.argtypes = [C.c_void_p, C.POINTER(abi.Params), C.POINTER(abi.PathDesc), _f32p, _u8p, C.POINTER(abi.PathOut), C.POINTER(abi.Stats)]
+        L.srt_render_paths.restype = C.c_int
         L.srt_strerror.argtypes = [C.c_int]
         L.srt_strerror.restype = C.c_char_p
         L.srt_last_hip_error.restype = C.c_int
@@ -505,6 +510,48 @@ class DeviceScene:
         po = abi.PathOut(seg_hit_id or None, seg_t or None, seg_obj or None, seg_rgb_linear or None, seg_rays or None)
         _check(self.L.srt_shade_paths_device(self.h, n, C.c_void_p(rays), C.c_void_p(t_range or 0), C.byref(params), C.byref(pd), C.c_void_p(stream),
                                              C.c_void_p(rgb_linear), C.c_void_p(rgb8), C.byref(po)), "srt_shade_paths_device")
+
+    def render_paths(self, params: abi.Params, depth, reflectance=None, bounce_t_min=1e-3,
+                     want=("rgb_linear", "rgb8", "seg_hit_id", "seg_t", "seg_obj", "seg_rgb_linear", "seg_rays"), count=False, smooth=False, fill=None):
+        """srt_render_paths: shade_paths for the rays of the frame's own pixels -- the local pixels of a call with `params` (its block or
+        tile deal, camera matrix and spp included); no ray array is built.  Returns a dict of the arrays named in `want` -- rgb_linear
+        [rows, cols, 3] (mixed), rgb8 [rows, cols, 3], and per segment seg_hit_id / seg_t / seg_obj [depth, rows, cols], seg_rgb_linear
+        [depth, rows, cols, 3], seg_rays [depth, rows, cols, 6] -- + 'stats'.  count / smooth add SRT_FLAG_COUNT_WORK /
+        SRT_FLAG_SMOOTH_NORMALS for this call.  fill: a value every array holds before the call (padding pixels of a tile deal keep it)."""
+        rows, W = self.rows(params), self.cols(params)
+        refl = None if reflectance is None else np.ascontiguousarray(reflectance, np.float32).reshape(-1)
+        new = (lambda shape, ty: np.empty(shape, ty)) if fill is None else (lambda shape, ty: np.full(shape, fill, ty))
+        out = {}
+        if "rgb_linear" in want: out["rgb_linear"] = new((rows, W, 3), np.float32)
+        if "rgb8" in want: out["rgb8"] = new((rows, W, 3), np.uint8)
+        po = abi.PathOut()
+        d = max(int(depth), 0)
+        for name, (ty, k) in abi.PATH_FIELDS.items():
+            if "seg_" + name in want:
+                out["seg_" + name] = new((d, rows, W) if k == 1 else (d, rows, W, k), ty)
+                setattr(po, name, out["seg_" + name].ctypes.data)
+        pd = abi.PathDesc(depth, bounce_t_min, refl.ctypes.data if refl is not None else None)
+        st = abi.Stats()
+        g = lambda k, ty: out[k].ctypes.data_as(ty) if k in out else ty()
+        flags = params.flags
+        params.flags = flags | (abi.SRT_FLAG_COUNT_WORK if count else 0) | (abi.SRT_FLAG_SMOOTH_NORMALS if smooth else 0)
+        try:
+            rc = self.L.srt_render_paths(self.h, C.byref(params), C.byref(pd), g("rgb_linear", _f32p), g("rgb8", _u8p), C.byref(po), C.byref(st))
+        finally:
+            params.flags = flags
+        _check(rc, "srt_render_paths")
+        out["stats"] = st.as_dict()
+        return out
+
+    def render_paths_device(self, params: abi.Params, depth, reflectance=0, bounce_t_min=1e-3, stream=0, rgb_linear=0, rgb8=0, seg_hit_id=0, seg_t=0, seg_obj=0,
+                            seg_rgb_linear=0, seg_rays=0):
+        """srt_render_paths_device: raw device pointers (ints, e.g. torch.Tensor.data_ptr()) in, asynchronous on `stream`, one launch.  The
+        light table of `params` is a host array; `reflectance` is a DEVICE pointer to n_objects floats (0 = all 0); the outputs are
+        [rows, cols, ...] and the seg_* outputs [depth, rows, cols, ...] of the call's local pixels.  The flags are those of `params`."""
+        pd = abi.PathDesc(depth, bounce_t_min, reflectance or None)
+        po = abi.PathOut(seg_hit_id or None, seg_t or None, seg_obj or None, seg_rgb_linear or None, seg_rays or None)
+        _check(self.L.srt_render_paths_device(self.h, C.byref(params), C.byref(pd), C.c_void_p(stream), C.c_void_p(rgb_linear), C.c_void_p(rgb8), C.byref(po)),
+               "srt_render_paths_device")
 
     def sync(self):
         st = abi.Stats()

@@ -23,7 +23,9 @@ shuffled, in the same rounds: srt_trace_rays_device (the yardstick: k_query_clos
 outputs and with normal + bounce only, srt_surface_hits_device on the frame's hits, and srt_surface_rays_device of the OTHER store form
 -- the library built with -DSRT_SURFACE_LANE_STORES (python -m simple_raytracer_amd.build --surface-lane-stores), loaded beside the
 shipped one, on a scene of its own.
-Usage: python tools/ray_query_probe.py [--reps N] [--trace] [--shade | --range | --shade-range | --multi | --surface [--rounds R]]     (--trace: few repetitions, for a run under rocprofv3 --kernel-trace --stats)"""
+--paths: instead, mirror paths of the same frame at depth 1 / 3 and 1 / 16 light samples, four ways in one run: the chain of existing device
+calls, srt_shade_paths_device on rays built beforehand, srt_render_paths_device, and at depth 1 srt_render_device.
+Usage: python tools/ray_query_probe.py [--reps N] [--trace] [--shade | --range | --shade-range | --multi | --surface | --paths [--rounds R]]     (--trace: few repetitions, for a run under rocprofv3 --kernel-trace --stats)"""
 import argparse, os, sys, time
 import numpy as np
 import torch                                   # first: torch initialises HIP before the library does
@@ -317,8 +319,62 @@ def surface_section(reps, rounds):
         print(f"{'':34s} hits {int((h0 >= 0).sum().item())}; both store forms and surface_hits give the same bits")
 
 
+def paths_section(reps, rounds):
+    """Mirror paths of the 1080p frame, four ways in one run: (a) the chain of existing device calls -- per segment srt_shade_rays_range_device
+    and, but for the last, srt_surface_rays_device for the bounce, 2 * depth - 1 launches, with the torch kernels that make the next interval
+    and point the rays of ended paths away from the scene --, (b) srt_shade_paths_device on rays built beforehand, (c) srt_render_paths_device, (d) at depth 1, srt_render_device."""
+    dev = torch.device("cuda", 0); torch.zeros(1, device=dev)
+    g = gu.GoldenScene("ground_bunny")
+    ds = lib.DeviceScene(g.flat)
+    side = torch.cuda.Stream(device=dev)
+    cur = side.cuda_stream
+    n = W * H
+    t_min = 1e-3
+    d_rays = torch.from_numpy(frame_rays()).to(dev)
+    refl = torch.tensor([0.6, 0.25], dtype=torch.float32, device=dev)
+    away = torch.tensor([0.0, 0.0, -1e6, 0.0, 0.0, -1.0], dtype=torch.float32, device=dev)      # behind the camera, looking back
+    f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+    i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)
+    print(f"mirror paths, K3 ground_bunny {W}x{H}: {n} rays; {rounds} rounds of {reps} calls, forms alternating; ms a call; min / max: the spread of the rounds")
+    print(f"{'depth, samples':34s} {'form':34s} {'median':>8s} {'min':>8s} {'max':>8s} {'/ first':>7s}")
+    for depth in (1, 3):
+        for L in (1, 16):
+            lights = abi.light_staircase(g.light, L)
+            p = abi.make_params(W, H, lights, focal=FOCAL, flags=abi.SRT_FLAG_NO_TIMING)
+            pq = abi.make_params(1, 1, lights)
+            lin_a, lin_b, lin_c, lin_d = f32(n, 3), f32(n, 3), f32(H, W, 3), f32(H, W, 3)
+            seg_c, nxt, obj, tr = [f32(n, 3) for _ in range(depth)], [f32(n, 6) for _ in range(depth)], i32(n), f32(n, 2)
+
+            def chain():
+                with torch.cuda.stream(side):
+                    ray, interval = d_rays, None
+                    for b in range(depth):
+                        ds.shade_rays_device(n, ray.data_ptr(), pq, stream=cur, rgb_linear=seg_c[b].data_ptr(), t_range=interval)
+                        if b + 1 < depth:
+                            ds.surface_rays_device(n, ray.data_ptr(), stream=cur, obj=obj.data_ptr(), bounce=nxt[b].data_ptr(), t_range=interval)
+                            tr[:, 0] = torch.where(obj >= 0, t_min, 1.0)
+                            tr[:, 1] = torch.where(obj >= 0, float("inf"), 0.0)
+                            nxt[b][obj < 0] = away                 # a path that has ended: a ray that leaves the scene at once (the zero ray of a
+                            ray, interval = nxt[b], tr.data_ptr()  # miss row has a NaN slab test and walks every node)
+
+            paths = lambda: ds.shade_paths_device(n, d_rays.data_ptr(), pq, depth, reflectance=refl.data_ptr(), bounce_t_min=t_min, stream=cur, rgb_linear=lin_b.data_ptr())
+            frame = lambda: ds.render_paths_device(p, depth, reflectance=refl.data_ptr(), bounce_t_min=t_min, stream=cur, rgb_linear=lin_c.data_ptr())
+            forms = {"(a) chain of device calls": chain, "(b) shade_paths_device": paths, "(c) render_paths_device": frame}
+            if depth == 1:
+                forms["(d) render_device"] = lambda: ds.render_device(p, stream=cur, rgb_linear=lin_d.data_ptr())
+            report(f"depth {depth}, {L} samples", rounds_of(forms, reps, rounds, side))
+            paths(); frame(); side.synchronize()
+            assert torch.equal(lin_b.view(torch.int32), lin_c.view(torch.int32).reshape(n, 3)), "(b) and (c) differ"
+            if depth == 1:
+                forms["(d) render_device"](); chain(); side.synchronize()
+                assert torch.equal(lin_d.view(torch.int32), lin_c.view(torch.int32)) and torch.equal(seg_c[0].view(torch.int32), lin_b.view(torch.int32)), "(a), (d) and (c) differ"
+            print(f"{'':34s} (b) and (c) give the same bits" + (", and so do (a) and (d)" if depth == 1 else ""))
+    ds.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--paths", action="store_true")
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--trace", action="store_true")
     ap.add_argument("--shade", action="store_true")
@@ -329,6 +385,8 @@ def main():
     ap.add_argument("--rounds", type=int, default=7)
     a = ap.parse_args()
     reps = 3 if a.trace else a.reps
+    if a.paths:
+        return paths_section(reps, 2 if a.trace else a.rounds)
     if a.multi:
         return multi_section(reps, 2 if a.trace else a.rounds)
     if a.surface:
