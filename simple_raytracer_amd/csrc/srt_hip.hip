@@ -1160,7 +1160,7 @@ static FramePlan plan_frame(const SceneFacts& f, const srt_params* p, BatchState
             else if (v == V_FUSED_6_WAVES)     pl.trace = &k_trace_nq<false, 512, true, 6, 16>;
             else if (v == V_ALL_WIDE)          pl.trace = &k_trace_nq<false, 512, true, 6, 16, false, false, false, true>;
             else if (pl.xcd_rows)            { pl.trace = &k_trace_nq<false, 512, true, 6, 16, true>; pl.grid_hit.y = xcd_pad(grid8.y); }
-            else                               pl.trace = &k_trace_nq<false, 512, true, 7, 16>;      // 72 VGPRs (14 spills), 7 waves per SIMD: since the node-major order 3 % ahead of the 6-wave build (80 VGPRs, 5 spills); round 2's kernel lost 2.5 % that way
+            else                               pl.trace = &k_trace_nq<false, 512, true, 7, 16>;      // 72 VGPRs, no scratch, 7 waves per SIMD (lane-derived addresses are formed where they are used: lane_again, srt_kernels.h); with 14 spilled registers it was already 3 % ahead of the 6-wave build since the node-major order
         } else if (!count && v == V_COARSE_GRID) {
             // 2 x 2 tiles per workgroup (a quarter of the workgroups for frames that are mostly background).  Measured and NOT
             // shipped: K4 closest hit 0.44 ms against 0.29 with one tile per workgroup, K3 0.22 against 0.10 -- the launch is not

@@ -71,6 +71,15 @@ __device__ __forceinline__ uint32_t lane_prefix(unsigned long long m) {
     return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
 }
 
+// The lane id once more, opaque to the compiler.  What a lane derives from it -- the LDS addresses of its own slots (lane << 2, lane * 16
+// + base), lane >> 4 -- is one or two VALU operations away; derived from the plain lane id it is hoisted out of every loop and, at seven
+// waves per SIMD, kept in scratch across the walks in between (a reload = an L2 round trip on the wave's dependent chain).  Derived from
+// this copy inside a loop it is formed where it is used.
+__device__ __forceinline__ uint32_t lane_again(uint32_t lane) {
+    asm volatile("" : "+v"(lane));
+    return lane;
+}
+
 // Hit-pixel statistic without a hot atomic: one word takes ~12 ns per atomic, so 32 k waves adding to one
 // address would serialise for ~0.4 ms.  64 shards, 64 B apart, summed on the host.
 constexpr int HIT_SHARDS = 64;
@@ -462,8 +471,8 @@ __device__ __forceinline__ void closest_hit_phase(const DevScene& s, const DevPa
     const uint32_t px = tile_x + (lane & ((1u << TWL) - 1)), r = tile_r + ((lane >> TWL) & ((1u << THL) - 1));
     const bool live = lane < P && pixel_live(p, px, r);
     const V3 o = CAM ? ray_origin(p) : mk(0.0f, 0.0f, 0.0f);
-    V3 dmine = mk(0.f, 0.f, p.focal);
     if (lane < P) {
+        V3 dmine = mk(0.f, 0.f, p.focal);
         best[lane] = ~0ull;
         if (live) dmine = primary_dir(p, px, image_row(p, r));
         if (CAM) dir[lane] = make_float4(dmine.x, dmine.y, dmine.z, 0.f);
@@ -540,7 +549,7 @@ __device__ __forceinline__ void closest_hit_phase(const DevScene& s, const DevPa
         // the roots: either tested already (root_pass: wave 0 ran them for the whole tile with full lanes) or tested here, one (ray,
         // object) pair per lane; a passing root that is an inner node is queued, a passing leaf's triangles are
         for (uint32_t base = 0; base < P * g; base += 64) {
-            const uint32_t k = base + lane;
+            const uint32_t k = base + lane_again(lane);
             const uint32_t pl = k & (P - 1), ob = k >> (TWL + THL);
             bool ok = k < P * g && ((livem >> pl) & 1ull);
             if (!COUNT && root_pass) ok = ok && ((root_pass[pl] >> (obj0 + ob)) & 1u);
@@ -663,7 +672,7 @@ __device__ __forceinline__ void closest_hit_phase(const DevScene& s, const DevPa
             // the root tests are done (wave 0 ran them for the whole tile with full lanes): queue what a passing root queues -- its two
             // children, or its triangles -- and skip the first node step, which would run at 16 rays x 2 roots = 32 of 64 lanes
             for (uint32_t base = 0; base < P * g; base += 64) {
-                const uint32_t k = base + lane;
+                const uint32_t k = base + lane_again(lane);
                 const uint32_t pl = k & (P - 1), ob = k >> (TWL + THL);
                 const bool ok = k < P * g && ((livem >> pl) & 1ull) && ((root_pass[pl] >> (obj0 + ob)) & 1u);
                 int32_t root = 0, info = -1;
@@ -681,7 +690,7 @@ __device__ __forceinline__ void closest_hit_phase(const DevScene& s, const DevPa
             }
         } else
         for (uint32_t base = 0; base < P * g; base += 64) {
-            const uint32_t k = base + lane;
+            const uint32_t k = base + lane_again(lane);
             const uint32_t pl = k & (P - 1), ob = k >> (TWL + THL);
             const bool ok = k < P * g && ((livem >> pl) & 1ull);
             const unsigned long long m = __ballot(ok);
@@ -790,8 +799,12 @@ __device__ __forceinline__ void closest_hit_phase(const DevScene& s, const DevPa
 #endif
 
     bool is_hit = false;
-    out_id = -1; out_t = __builtin_inff(); out_d = dmine;
+    out_id = -1; out_t = __builtin_inff(); out_d = mk(0.f, 0.f, p.focal);
     if (live) {
+        // the lane's own ray, as it has stood in dir[] since the set-up (same bits): not kept in registers through the walk
+        const float4 dl = dir[lane];
+        const V3 dmine = mk(dl.x, dl.y, CAM ? dl.z : p.focal);
+        out_d = dmine;
         const unsigned long long key = best[lane];
         int32_t id = -1;
         float t = __builtin_inff();
@@ -1169,6 +1182,7 @@ __device__ __forceinline__ void shadow_phase(const DevScene& s, const DevParams&
     const uint32_t px = tile_x + (lane & 3), r = tile_r + ((lane >> 2) & 3);
     const bool live = lane < NQ_P && pixel_live(p, px, r);
     const size_t tile_index = (size_t)by * gx + bx;
+    const uint32_t wave_s = __builtin_amdgcn_readfirstlane(wave);      // wave-uniform: waits for the stores at the end in a scalar register
     unsigned long long n_node = 0, n_tri = 0;
     if (!live) id = -1;
     const uint32_t hm = (uint32_t)__ballot(id >= 0);
@@ -1214,7 +1228,7 @@ __device__ __forceinline__ void shadow_phase(const DevScene& s, const DevParams&
         }
         if (!__ballot(pass_any)) {
             L.mask[lane] = 0u;                                        // (read by the wave that shades the tile in the one-launch build)
-            if (shadow_bits) for (uint32_t l = l_begin + lane; l < l_end; l += 64u) reinterpret_cast<uint16_t*>(shadow_bits)[(tile_index * p.n_lights + l) * 4 + wave] = 0;
+            if (shadow_bits) for (uint32_t l = l_begin + lane; l < l_end; l += 64u) reinterpret_cast<uint16_t*>(shadow_bits)[(tile_index * p.n_lights + l) * 4 + wave_s] = 0;
             return;
         }
     }
@@ -1225,8 +1239,9 @@ __device__ __forceinline__ void shadow_phase(const DevScene& s, const DevParams&
     auto tri_batch = [&]() {
         const uint32_t m = tqn < 64 ? tqn : 64;
         tqn -= m;
-        if (lane < m) {
-            const uint32_t info = tq[2 * (tqn + lane)], rs = tq[2 * (tqn + lane) + 1];
+        const uint32_t lt = lane_again(lane);
+        if (lt < m) {
+            const uint32_t info = tq[2 * (tqn + lt)], rs = tq[2 * (tqn + lt) + 1];
             if (!flag[rs]) {
                 const uint32_t first = info >> LEAF_SHIFT, cnt = info & LEAF_MAX;
                 const float4 ro4 = ray[rs], rd4 = ray[RS + rs];
@@ -1265,17 +1280,21 @@ __device__ __forceinline__ void shadow_phase(const DevScene& s, const DevParams&
     const uint32_t n_obj = s.n_objects;
     for (uint32_t l0 = l_begin; l0 < l_end; l0 += 64) {              // light samples in groups of 64
         const uint32_t Lg = (l_end - l0) < 64u ? (l_end - l0) : 64u;
-        L.mask[lane] = 0u;
+        L.mask[lane_again(lane)] = 0u;
         __builtin_amdgcn_wave_barrier();
         const uint32_t n_items = nh * Lg;
+        // item / Lg below as a multiplication: exact for item < 16 * Lg, Lg <= 64 ((65536 / Lg + 1) * Lg - 65536 <= Lg, and item < 65536 / Lg).
+        // Wave-uniform, so it waits in a scalar register; the reciprocal of a per-lane division waited in a vector register, or in scratch.
+        const uint32_t lg_magic = __builtin_amdgcn_readfirstlane(0x10000u / Lg + 1u);
         for (uint32_t base = 0; base < n_items; base += RS) {        // RS rays per round
-            const uint32_t item = base + lane;
-            const bool valid = lane < RS && item < n_items;
+            const uint32_t ln = lane_again(lane);                 // (the slots' addresses are formed here, not kept across the rounds)
+            const uint32_t item = base + ln;
+            const bool valid = ln < RS && item < n_items;
             uint32_t pl = 0, lg = 0;
             V3 so = mk(0.f, 0.f, 0.f), sd = mk(0.f, 0.f, 1.f);
             int2 self = make_int2(-1, -1);
             if (valid) {
-                const uint32_t hr = (Lg == 1u) ? item : item / Lg;
+                const uint32_t hr = (Lg == 1u) ? item : (item * lg_magic) >> 16;
                 lg = item - hr * Lg;
                 const float4 pd = pixd[hr];
                 pl = __float_as_uint(pd.y);
@@ -1290,11 +1309,11 @@ __device__ __forceinline__ void shadow_phase(const DevScene& s, const DevParams&
             if (SEQ) {
                 if (valid) shadowed = any_hit_range<true, false>(s, self, so, sd, n_node, n_tri);
             } else {
-                if (lane < RS) {
-                    ray[lane] = make_float4(so.x, so.y, so.z, 0.f);
-                    ray[RS + lane] = make_float4(sd.x, sd.y, sd.z, 0.f);
-                    selfr[lane] = self;
-                    flag[lane] = valid ? 0u : 1u;
+                if (ln < RS) {      // (.w, which no test reads: the ray's pixel lane and light sample wait here during the walk, not in registers)
+                    ray[ln] = make_float4(so.x, so.y, so.z, __uint_as_float(pl));
+                    ray[RS + ln] = make_float4(sd.x, sd.y, sd.z, __uint_as_float(lg));
+                    selfr[ln] = self;
+                    flag[ln] = valid ? 0u : 1u;
                 }
                 const unsigned long long validm = __ballot(valid);
                 __builtin_amdgcn_wave_barrier();
@@ -1303,7 +1322,7 @@ __device__ __forceinline__ void shadow_phase(const DevScene& s, const DevParams&
                     const uint32_t g = (n_obj - obj0) < OBJ_G ? (n_obj - obj0) : OBJ_G;
                     // the other objects' roots, one (ray, object) pair per lane: a passing inner root is queued, a passing leaf's triangles are
                     for (uint32_t kb = 0; kb < RS * g; kb += 64) {
-                        const uint32_t k = kb + lane;
+                        const uint32_t k = kb + lane_again(lane);
                         const uint32_t rs = k & (RS - 1), ob = k / RS;
                         bool ok = k < RS * g && ((validm >> rs) & 1ull);
                         int32_t info = 0;
@@ -1408,7 +1427,7 @@ __device__ __forceinline__ void shadow_phase(const DevScene& s, const DevParams&
                 for (uint32_t obj0 = 0; obj0 < n_obj; obj0 += OBJ_G) {
                     const uint32_t g = (n_obj - obj0) < OBJ_G ? (n_obj - obj0) : OBJ_G;
                     for (uint32_t kb = 0; kb < RS * g; kb += 64) {
-                        const uint32_t k = kb + lane;
+                        const uint32_t k = kb + lane_again(lane);
                         const uint32_t rs = k & (RS - 1), ob = k / RS;
                         bool ok = k < RS * g && ((validm >> rs) & 1ull);
                         int32_t root = 0;
@@ -1487,13 +1506,18 @@ __device__ __forceinline__ void shadow_phase(const DevScene& s, const DevParams&
                 }
                 while (tqn) tri_batch();
                 __builtin_amdgcn_wave_barrier();
-                shadowed = valid && flag[lane] != 0u;
+                if (valid) {
+                    const uint32_t lz = lane_again(lane);
+                    shadowed = flag[lz] != 0u;
+                    pl = __float_as_uint(ray[lz].w); lg = __float_as_uint(ray[RS + lz].w);
+                }
                 __builtin_amdgcn_wave_barrier();
             }
             if (shadowed && valid) atomicOr(&L.mask[lg], 1u << pl);
         }
         __builtin_amdgcn_wave_barrier();
-        if (shadow_bits && lane < Lg) reinterpret_cast<uint16_t*>(shadow_bits)[(tile_index * p.n_lights + l0 + lane) * 4 + wave] = (uint16_t)L.mask[lane];
+        const uint32_t lw = lane_again(lane);      // (the word's address is formed here, not kept across the walk)
+        if (shadow_bits && lw < Lg) reinterpret_cast<uint16_t*>(shadow_bits)[(tile_index * p.n_lights + l0 + lw) * 4 + wave_s] = (uint16_t)L.mask[lw];
         __builtin_amdgcn_wave_barrier();
     }
     if (SEQ) { wave_add(counters + 3, n_node); wave_add(counters + 4, n_tri); }
