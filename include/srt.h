@@ -625,6 +625,49 @@ int srt_render_paths_device(srt_scene* s, const srt_params* p, const srt_path_de
 int srt_render_paths(srt_scene* s, const srt_params* p, const srt_path_desc* path,
                      float* rgb_linear, uint8_t* rgb8, const srt_path_out* seg, srt_stats* stats);
 
+/* Shadow rays with an end: srt_shade_paths / srt_render_paths under a SHADOW RULE -- an interval on every shadow ray, and optionally the hit
+ * object's own tree among the occluders.  The shaded calls above keep the reference's rule (shadowIntersection:321-342): a shadow ray runs
+ * from the hit point towards the light with t unbounded and the hit object's tree left out.  That suits a far light and convex objects; with a
+ * lamp INSIDE the scene an object behind the lamp casts a shadow, and no object ever shadows itself.  A rule cures both.
+ * Unless said here everything is as for srt_shade_paths / srt_render_paths: staging, the one-light-table-per-handle rule, the ordering on
+ * `stream`, srt_scene_share, ONE kernel launch, hipGraph capture of the _device forms without SRT_FLAG_COUNT_WORK, NULL outputs and n == 0,
+ * the frame fields, spp, the tile deals, seg.
+ * DEFINITION.  For a hit of object obj on a ray (o, d) at t, and a light sample L:  so = o + d * t (d * t first, then o +, as ever) and
+ * sd = L - so.  Under a rule r the sample is SHADOWED iff srt_occluded_range answers 1 for the ray (so, sd), the interval (r.t_min, r.t_max)
+ * and skip_obj = (r.flags & SRT_SHADOW_SELF) ? -1 : obj.  So the candidate set is that call's, t is in units of L - so (t = 1 is the light), and
+ * in range means !(t < t_min) && !(t > t_max): the interval is closed, a NaN bound bounds nothing, a NaN t is in range, t_min > t_max shadows
+ * nothing.  Everything else of the shaded call is unchanged -- the closest hit and its interval, the surface, Phong with the ray's own o and d,
+ * the sum in light order with a shadowed sample divided by shadow_div, the mix, tone map, quantiser and background rule.  One rule holds for
+ * every segment of a path and every sub-sample of a pixel.
+ * Identities (the existing call's bits in every output):  a NULL rule -- this one launches the existing kernels; a rule with flags == 0 whose
+ * interval is (0, +inf), (-inf, +inf) or (NaN, NaN): the triangle test returns -inf, -0, a t >= 0 or NaN, never a negative finite t, and the
+ * unbounded walk counts every result but -inf.
+ * Depth 1 under a rule is srt_shade_rays_range under that rule (in a frame: srt_render_device in camera mode under that rule); there is no
+ * further entry point for them.  srt_render_device and srt_render_batch keep the reference's rule: the frame form of a rule is
+ * srt_render_paths_shadow.
+ * Not validated: SRT_SHADOW_SELF with t_min <= 0 gives what the arithmetic gives -- the hit's own triangle is then a candidate near t = 0, and
+ * whether it blocks depends on rounding.  Use a small positive t_min (1e-3 of the way to the light, say) with SRT_SHADOW_SELF.
+ * Errors: flags with any bit but SRT_SHADOW_SELF: SRT_ERR_ARG, before anything is touched; every error of the underlying call keeps its code.
+ * *stats: primary_rays, hit_rays and shadow_rays = hit_rays x n_lights as before.  Under SRT_FLAG_COUNT_WORK the two primary counters are the
+ * NULL-rule call's (the primary walks do not depend on the rule); the two shadow counters count the walk as it runs: objects in order, none
+ * skipped under SRT_SHADOW_SELF, one slab test per node met, triangle tests up to and including the first candidate in range. */
+#define SRT_SHADOW_SELF 1u       /* the hit object's own tree is walked too */
+typedef struct srt_shadow_rule {
+    float    t_min, t_max;       /* a shadow ray blocks only inside the closed (t_min, t_max), in units of L - so: t = 1 is the light */
+    uint32_t flags;              /* 0 or SRT_SHADOW_SELF */
+} srt_shadow_rule;
+int srt_shade_paths_shadow_device(srt_scene* s, uint32_t n, const float* d_rays, const float* d_t_range /* n x 2 or NULL */,
+                                  const srt_params* p, const srt_path_desc* path, const srt_shadow_rule* shadow /* or NULL */, void* stream,
+                                  float* d_rgb_linear /* n x 3, mixed */, uint8_t* d_rgb8 /* n x 3 */, const srt_path_out* seg);
+int srt_shade_paths_shadow(srt_scene* s, uint32_t n, const float* rays, const float* t_range, const srt_params* p,
+                           const srt_path_desc* path, const srt_shadow_rule* shadow, float* rgb_linear, uint8_t* rgb8,
+                           const srt_path_out* seg, srt_stats* stats);
+int srt_render_paths_shadow_device(srt_scene* s, const srt_params* p, const srt_path_desc* path, const srt_shadow_rule* shadow /* or NULL */,
+                                   void* stream, float* d_rgb_linear /* n x 3, mixed */, uint8_t* d_rgb8 /* n x 3 */,
+                                   const srt_path_out* seg);
+int srt_render_paths_shadow(srt_scene* s, const srt_params* p, const srt_path_desc* path, const srt_shadow_rule* shadow,
+                            float* rgb_linear, uint8_t* rgb8, const srt_path_out* seg, srt_stats* stats);
+
 /* Device-resident size of the scene records and the per-record algorithmic byte sizes used by
  * the bytes model: 32 B per node test, 36 B per triangle test. */
 uint64_t srt_scene_device_bytes(const srt_scene* s);

@@ -94,6 +94,23 @@ class PathOut(C.Structure):
     _fields_ = [("hit_id", C.c_void_p), ("t", C.c_void_p), ("obj", C.c_void_p), ("rgb_linear", C.c_void_p), ("rays", C.c_void_p)]
 
 
+SRT_SHADOW_SELF = 1
+
+
+class ShadowRule(C.Structure):
+    """srt_shadow_rule: a shadow ray blocks only inside the closed (t_min, t_max), in units of light - hit point (t = 1 is the light);
+    flags: 0, or SRT_SHADOW_SELF = the hit object's own tree is walked too."""
+    _fields_ = [("t_min", C.c_float), ("t_max", C.c_float), ("flags", C.c_uint32)]
+
+
+def shadow_rule(shadow):
+    """None, a ShadowRule, or (t_min, t_max, self_shadow) -> a ShadowRule, or None."""
+    if shadow is None or isinstance(shadow, ShadowRule):
+        return shadow
+    t_min, t_max, self_shadow = shadow
+    return ShadowRule(t_min, t_max, SRT_SHADOW_SELF if self_shadow else 0)
+
+
 # the fields of srt_path_out: name -> (dtype, floats or ints per ray and segment)
 PATH_FIELDS = {"hit_id": (np.int32, 1), "t": (np.float32, 1), "obj": (np.int32, 1), "rgb_linear": (np.float32, 3), "rays": (np.float32, 6)}
 

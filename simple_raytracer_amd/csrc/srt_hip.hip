@@ -1687,8 +1687,14 @@ static int check_paths(const srt_scene* s, uint32_t n, const float* rays, const 
 static inline bool paths_wanted(const float* rgb_linear, const uint8_t* rgb8, const srt_path_out* o) {
     return rgb_linear || rgb8 || (o && (o->hit_id || o->t || o->obj || o->rgb_linear || o->rays));
 }
+// The shadow rule of the srt_*_paths_shadow calls: NULL (the reference's rule, the existing kernels), or flags within SRT_SHADOW_SELF
+static inline int check_shadow(const srt_shadow_rule* r) { return (r && (r->flags & ~(uint32_t)SRT_SHADOW_SELF)) ? SRT_ERR_ARG : SRT_OK; }
+static inline ShadowRule shadow_rule(const srt_shadow_rule* r) { return ShadowRule{ r->t_min, r->t_max, (r->flags & SRT_SHADOW_SELF) ? 1u : 0u }; }
+
+// shadow: NULL launches k_query_path as ever; a rule launches the k_query_path_shadow build of the same choice
 static int shade_paths_device_impl(srt_scene* s, uint32_t n, const float* d_rays, const float* d_t_range, const srt_params* p, const srt_path_desc* path,
-                                   hipStream_t stream, float* d_rgb_linear, uint8_t* d_rgb8, const srt_path_out* seg, bool count_hits) {
+                                   const srt_shadow_rule* shadow, hipStream_t stream, float* d_rgb_linear, uint8_t* d_rgb8, const srt_path_out* seg, bool count_hits) {
+    SRT_TRY(check_shadow(shadow));
     SRT_TRY(check_paths(s, n, d_rays, p, path));
     if (!n || (!count_hits && !paths_wanted(d_rgb_linear, d_rgb8, seg))) return SRT_OK;
     const bool count = (p->flags & SRT_FLAG_COUNT_WORK) != 0, smooth = (p->flags & SRT_FLAG_SMOOTH_NORMALS) != 0;
@@ -1697,9 +1703,16 @@ static int shade_paths_device_impl(srt_scene* s, uint32_t n, const float* d_rays
     static const decltype(&k_query_path<false, false, false>) builds[8] = {
         &k_query_path<false, false, false>, &k_query_path<false, false, true>, &k_query_path<false, true, false>, &k_query_path<false, true, true>,
         &k_query_path<true, false, false>,  &k_query_path<true, false, true>,  &k_query_path<true, true, false>,  &k_query_path<true, true, true> };
-    const auto k = builds[(count ? 4 : 0) | (smooth ? 2 : 0) | (s->rec->int_shin ? 1 : 0)];
-    hipLaunchKernelGGL(k, q.grid, dim3(256), 0, q.stream, s->dev, n, d_rays, rays_wide(d_rays), query_shade(s, p), query_range(d_t_range), *path, d_rgb_linear, d_rgb8,
-                       seg ? *seg : srt_path_out{}, q.ctr);
+    static const decltype(&k_query_path_shadow<false, false, false>) shadow_builds[8] = {
+        &k_query_path_shadow<false, false, false>, &k_query_path_shadow<false, false, true>, &k_query_path_shadow<false, true, false>, &k_query_path_shadow<false, true, true>,
+        &k_query_path_shadow<true, false, false>,  &k_query_path_shadow<true, false, true>,  &k_query_path_shadow<true, true, false>,  &k_query_path_shadow<true, true, true> };
+    const int build = (count ? 4 : 0) | (smooth ? 2 : 0) | (s->rec->int_shin ? 1 : 0);
+    if (shadow)
+        hipLaunchKernelGGL(shadow_builds[build], q.grid, dim3(256), 0, q.stream, s->dev, n, d_rays, rays_wide(d_rays), query_shade(s, p), query_range(d_t_range), *path,
+                           d_rgb_linear, d_rgb8, seg ? *seg : srt_path_out{}, q.ctr, shadow_rule(shadow));
+    else
+        hipLaunchKernelGGL(builds[build], q.grid, dim3(256), 0, q.stream, s->dev, n, d_rays, rays_wide(d_rays), query_shade(s, p), query_range(d_t_range), *path, d_rgb_linear,
+                           d_rgb8, seg ? *seg : srt_path_out{}, q.ctr);
     HIP_TRY(hipGetLastError());
     return SRT_OK;
 }
@@ -1715,8 +1728,9 @@ static int check_render_paths(const srt_scene* s, const srt_params* p, const srt
     if ((uint64_t)srt_rows_owned(p) * srt_cols_owned(p) * (p->n_lights ? p->n_lights : 1) >= (1ull << 32)) return SRT_ERR_LIMIT;
     return SRT_OK;
 }
-static int render_paths_device_impl(srt_scene* s, const srt_params* p, const srt_path_desc* path, hipStream_t stream, float* d_rgb_linear, uint8_t* d_rgb8,
-                                    const srt_path_out* seg, bool count_hits) {
+static int render_paths_device_impl(srt_scene* s, const srt_params* p, const srt_path_desc* path, const srt_shadow_rule* shadow, hipStream_t stream, float* d_rgb_linear,
+                                    uint8_t* d_rgb8, const srt_path_out* seg, bool count_hits) {
+    SRT_TRY(check_shadow(shadow));
     SRT_TRY(check_render_paths(s, p, path));
     const uint32_t rows = srt_rows_owned(p), wl = srt_cols_owned(p);
     if (!rows || !wl || (!count_hits && !paths_wanted(d_rgb_linear, d_rgb8, seg))) return SRT_OK;
@@ -1727,10 +1741,18 @@ static int render_paths_device_impl(srt_scene* s, const srt_params* p, const srt
     static const decltype(&k_render_path<false, false, false>) builds[8] = {
         &k_render_path<false, false, false>, &k_render_path<false, false, true>, &k_render_path<false, true, false>, &k_render_path<false, true, true>,
         &k_render_path<true, false, false>,  &k_render_path<true, false, true>,  &k_render_path<true, true, false>,  &k_render_path<true, true, true> };
-    const auto k = builds[(count ? 4 : 0) | (smooth ? 2 : 0) | (s->rec->int_shin ? 1 : 0)];
+    static const decltype(&k_render_path_shadow<false, false, false>) shadow_builds[8] = {
+        &k_render_path_shadow<false, false, false>, &k_render_path_shadow<false, false, true>, &k_render_path_shadow<false, true, false>, &k_render_path_shadow<false, true, true>,
+        &k_render_path_shadow<true, false, false>,  &k_render_path_shadow<true, false, true>,  &k_render_path_shadow<true, true, false>,  &k_render_path_shadow<true, true, true> };
+    const int build = (count ? 4 : 0) | (smooth ? 2 : 0) | (s->rec->int_shin ? 1 : 0);
     const uint32_t m = (uint32_t)std::lround(std::sqrt((double)p->spp));      // (m x m == spp: check_frame)
-    hipLaunchKernelGGL(k, dim3((wl + 15) / 16, (rows + 15) / 16), dim3(256), 0, q.stream, s->dev, dp, p->spp, m, query_shade(s, p), *path, d_rgb_linear, d_rgb8,
-                       seg ? *seg : srt_path_out{}, q.ctr);
+    const dim3 grid((wl + 15) / 16, (rows + 15) / 16);
+    if (shadow)
+        hipLaunchKernelGGL(shadow_builds[build], grid, dim3(256), 0, q.stream, s->dev, dp, p->spp, m, query_shade(s, p), *path, d_rgb_linear, d_rgb8,
+                           seg ? *seg : srt_path_out{}, q.ctr, shadow_rule(shadow));
+    else
+        hipLaunchKernelGGL(builds[build], grid, dim3(256), 0, q.stream, s->dev, dp, p->spp, m, query_shade(s, p), *path, d_rgb_linear, d_rgb8,
+                           seg ? *seg : srt_path_out{}, q.ctr);
     HIP_TRY(hipGetLastError());
     return SRT_OK;
 }
@@ -1917,8 +1939,9 @@ static int shade_rays_impl(srt_scene* s, uint32_t n, const float* rays, const fl
 }
 
 // srt_shade_paths: the per-segment rows are depth units a ray; hit_rays counts the hits of all segments, hence the shadow rays
-static int shade_paths_impl(srt_scene* s, uint32_t n, const float* rays, const float* t_range, const srt_params* p, const srt_path_desc* path, float* rgb_linear,
-                            uint8_t* rgb8, const srt_path_out* seg, srt_stats* stats) {
+static int shade_paths_impl(srt_scene* s, uint32_t n, const float* rays, const float* t_range, const srt_params* p, const srt_path_desc* path,
+                            const srt_shadow_rule* shadow, float* rgb_linear, uint8_t* rgb8, const srt_path_out* seg, srt_stats* stats) {
+    SRT_TRY(check_shadow(shadow));
     SRT_TRY(check_paths(s, n, rays, p, path));
     if (stats) std::memset(stats, 0, sizeof(*stats));
     if (!n || (!stats && !paths_wanted(rgb_linear, rgb8, seg))) return SRT_OK;
@@ -1930,13 +1953,15 @@ static int shade_paths_impl(srt_scene* s, uint32_t n, const float* rays, const f
     SRT_TRY(query_round_trip_refl(s, n, rays, t_range, nullptr, nullptr, path->reflectance, path->reflectance ? s->dev.n_objects : 0u, [&](hipStream_t st) {
         const srt_path_desc dpath = { path->depth, path->bounce_t_min, path->reflectance ? s->rq_refl.p : nullptr };
         const srt_path_out dev = { o_hit.wanted(), o_t.wanted(), o_obj.wanted(), o_slin.wanted(), o_rays.wanted() };
-        return shade_paths_device_impl(s, n, s->rq_rays, t_range ? s->rq_range.p : nullptr, p, &dpath, st, o_lin.wanted(), o_rgb8.wanted(), &dev, stats != nullptr);
+        return shade_paths_device_impl(s, n, s->rq_rays, t_range ? s->rq_range.p : nullptr, p, &dpath, shadow, st, o_lin.wanted(), o_rgb8.wanted(), &dev, stats != nullptr);
     }, o_lin, o_rgb8, o_hit, o_t, o_obj, o_slin, o_rays));
     return stats ? query_stats(s, n, p->n_lights, stats) : SRT_OK;
 }
 
 // srt_render_paths: as shade_paths_impl, with n the call's local pixels and no rays to stage; primary_rays counts image pixels x spp
-static int render_paths_impl(srt_scene* s, const srt_params* p, const srt_path_desc* path, float* rgb_linear, uint8_t* rgb8, const srt_path_out* seg, srt_stats* stats) {
+static int render_paths_impl(srt_scene* s, const srt_params* p, const srt_path_desc* path, const srt_shadow_rule* shadow, float* rgb_linear, uint8_t* rgb8,
+                             const srt_path_out* seg, srt_stats* stats) {
+    SRT_TRY(check_shadow(shadow));
     SRT_TRY(check_render_paths(s, p, path));
     if (stats) std::memset(stats, 0, sizeof(*stats));
     const uint32_t n = srt_rows_owned(p) * srt_cols_owned(p);      // (< 2^32: check_render_paths)
@@ -1961,7 +1986,7 @@ static int render_paths_impl(srt_scene* s, const srt_params* p, const srt_path_d
             up(dev.rays, h.rays, D * n * 24); up(o_lin.wanted(), rgb_linear, (size_t)n * 12); up(o_rgb8.wanted(), rgb8, (size_t)n * 3);
             HIP_TRY(e);
         }
-        return render_paths_device_impl(s, p, &dpath, st, o_lin.wanted(), o_rgb8.wanted(), &dev, stats != nullptr);
+        return render_paths_device_impl(s, p, &dpath, shadow, st, o_lin.wanted(), o_rgb8.wanted(), &dev, stats != nullptr);
     }, o_lin, o_rgb8, o_hit, o_t, o_obj, o_slin, o_rays));
     if (!stats) return SRT_OK;
     SRT_TRY(query_stats(s, n, p->n_lights, stats));
@@ -2049,17 +2074,34 @@ int srt_shade_rays_range(srt_scene* s, uint32_t n, const float* rays, const floa
 }
 int srt_shade_paths_device(srt_scene* s, uint32_t n, const float* d_rays, const float* d_t_range, const srt_params* p, const srt_path_desc* path, void* stream,
                            float* d_rgb_linear, uint8_t* d_rgb8, const srt_path_out* seg) {
-    return guarded([&] { return shade_paths_device_impl(s, n, d_rays, d_t_range, p, path, (hipStream_t)stream, d_rgb_linear, d_rgb8, seg, false); });
+    return guarded([&] { return shade_paths_device_impl(s, n, d_rays, d_t_range, p, path, nullptr, (hipStream_t)stream, d_rgb_linear, d_rgb8, seg, false); });
 }
 int srt_shade_paths(srt_scene* s, uint32_t n, const float* rays, const float* t_range, const srt_params* p, const srt_path_desc* path, float* rgb_linear, uint8_t* rgb8,
                     const srt_path_out* seg, srt_stats* stats) {
-    return guarded([&] { return shade_paths_impl(s, n, rays, t_range, p, path, rgb_linear, rgb8, seg, stats); });
+    return guarded([&] { return shade_paths_impl(s, n, rays, t_range, p, path, nullptr, rgb_linear, rgb8, seg, stats); });
 }
 int srt_render_paths_device(srt_scene* s, const srt_params* p, const srt_path_desc* path, void* stream, float* d_rgb_linear, uint8_t* d_rgb8, const srt_path_out* seg) {
-    return guarded([&] { return render_paths_device_impl(s, p, path, (hipStream_t)stream, d_rgb_linear, d_rgb8, seg, false); });
+    return guarded([&] { return render_paths_device_impl(s, p, path, nullptr, (hipStream_t)stream, d_rgb_linear, d_rgb8, seg, false); });
 }
 int srt_render_paths(srt_scene* s, const srt_params* p, const srt_path_desc* path, float* rgb_linear, uint8_t* rgb8, const srt_path_out* seg, srt_stats* stats) {
-    return guarded([&] { return render_paths_impl(s, p, path, rgb_linear, rgb8, seg, stats); });
+    return guarded([&] { return render_paths_impl(s, p, path, nullptr, rgb_linear, rgb8, seg, stats); });
+}
+// The same four calls under a shadow rule (NULL: the call above, with its kernels)
+int srt_shade_paths_shadow_device(srt_scene* s, uint32_t n, const float* d_rays, const float* d_t_range, const srt_params* p, const srt_path_desc* path,
+                                  const srt_shadow_rule* shadow, void* stream, float* d_rgb_linear, uint8_t* d_rgb8, const srt_path_out* seg) {
+    return guarded([&] { return shade_paths_device_impl(s, n, d_rays, d_t_range, p, path, shadow, (hipStream_t)stream, d_rgb_linear, d_rgb8, seg, false); });
+}
+int srt_shade_paths_shadow(srt_scene* s, uint32_t n, const float* rays, const float* t_range, const srt_params* p, const srt_path_desc* path, const srt_shadow_rule* shadow,
+                           float* rgb_linear, uint8_t* rgb8, const srt_path_out* seg, srt_stats* stats) {
+    return guarded([&] { return shade_paths_impl(s, n, rays, t_range, p, path, shadow, rgb_linear, rgb8, seg, stats); });
+}
+int srt_render_paths_shadow_device(srt_scene* s, const srt_params* p, const srt_path_desc* path, const srt_shadow_rule* shadow, void* stream, float* d_rgb_linear,
+                                   uint8_t* d_rgb8, const srt_path_out* seg) {
+    return guarded([&] { return render_paths_device_impl(s, p, path, shadow, (hipStream_t)stream, d_rgb_linear, d_rgb8, seg, false); });
+}
+int srt_render_paths_shadow(srt_scene* s, const srt_params* p, const srt_path_desc* path, const srt_shadow_rule* shadow, float* rgb_linear, uint8_t* rgb8,
+                            const srt_path_out* seg, srt_stats* stats) {
+    return guarded([&] { return render_paths_impl(s, p, path, shadow, rgb_linear, rgb8, seg, stats); });
 }
 
 int srt_surface_rays_device(srt_scene* s, uint32_t n, const float* d_rays, const float* d_t_range, uint32_t flags, void* stream, int32_t* d_hit_id, float* d_t,

@@ -345,9 +345,13 @@ struct QueryShade {
 // shade_hits_rank: the wave's hits are ranked; a hit gets its t (the winner's own bits) and its surface, and leaves its shadow origin and
 // its object's node range in the wave's LDS by rank.  A lane without a hit gets t = +inf and a surface that shades to nothing.
 struct WaveHits { uint32_t nh, rank; };       // hits in the wave; this lane's rank among them
-template <bool SMOOTH>
+// The shadow rule of the srt_*_paths_shadow calls (include/srt.h, "Shadow rays with an end") as the SHADOW builds receive it: a shadow ray
+// blocks only inside the closed (t_min, t_max), in units of L - so, and with self != 0 the hit object's own tree is walked too.  self costs
+// nothing in the walk: shade_hits_rank leaves (-1, -1) -- "skip no object", as k_query_any has it -- where the object's node range would go.
+struct ShadowRule { float t_min, t_max; uint32_t self; };
+template <bool SMOOTH, bool SHADOW = false>
 __device__ __forceinline__ WaveHits shade_hits_rank(const DevScene& s, const bool is_hit, const int32_t id, const V3 o, const V3 d, float& t, Surface& f,
-                                                    float (*wray)[64]) {
+                                                    float (*wray)[64], const uint32_t walk_self = 0u) {
     t = __builtin_inff();
     f.color = mk(0.0f, 0.0f, 0.0f); f.nrm = f.color; f.ka = 0.0f; f.ks = 0.0f; f.sh = 1.0f;
     const unsigned long long hm = __ballot(is_hit);
@@ -358,7 +362,8 @@ __device__ __forceinline__ WaveHits shade_hits_rank(const DevScene& s, const boo
         load_tri_edges(reinterpret_cast<const float4*>(s.tris), (size_t)id, p1, e1, e2);
         t = ray_triangle(o, d, p1, e1, e2);             // the winner's t with its own bits (incl. the sign of a zero); the walk's value, hence in range
         const V3 P = o + d * t;                         // shadowIntersection:325-326 in camera mode: so = o + d * t
-        const int2 self = s.obj_range[s.tri_obj[id]];
+        int2 self = s.obj_range[s.tri_obj[id]];
+        if (SHADOW && walk_self) self = make_int2(-1, -1);
         wray[0][rank] = P.x; wray[1][rank] = P.y; wray[2][rank] = P.z;
         wray[3][rank] = __int_as_float(self.x); wray[4][rank] = __int_as_float(self.y);
         f = surface_at(s, id, o, d, t, SMOOTH);
@@ -366,10 +371,11 @@ __device__ __forceinline__ WaveHits shade_hits_rank(const DevScene& s, const boo
     return WaveHits{ nh, rank };
 }
 // shade_hits_lights: the shadow rays of the wave's hits in chunks of 64 light samples, dealt to all 64 lanes, and each hit's light-sample sum.
-template <bool COUNT, bool INT_SHIN>
+// SHADOW: a shadow ray blocks only in range of (sh_min, sh_max) -- any_hit_range's RANGE walk, the one k_query_any<true> runs.
+template <bool COUNT, bool INT_SHIN, bool SHADOW = false>
 __device__ __forceinline__ V3 shade_hits_lights(const DevScene& s, const QueryShade& p, const uint32_t lane, const bool is_hit, const WaveHits wh, const V3 o, const V3 d,
                                                 const float t, const Surface& f, float (*wray)[64], unsigned long long* best, unsigned long long& n_node_s,
-                                                unsigned long long& n_tri_s) {
+                                                unsigned long long& n_tri_s, const float sh_min = 0.0f, const float sh_max = 0.0f) {
     const uint32_t nh = wh.nh, rank = wh.rank;
     V3 sum = mk(0.0f, 0.0f, 0.0f);
     for (uint32_t l0 = 0; l0 < p.n_lights; l0 += 64u) {                                             // wave-uniform
@@ -383,7 +389,7 @@ __device__ __forceinline__ V3 shade_hits_lights(const DevScene& s, const QuerySh
             const int2 self = make_int2(__float_as_int(wray[3][r]), __float_as_int(wray[4][r]));
             const float* lp = p.lights + (size_t)(l0 + k) * 3;
             const V3 sd = mk(lp[0], lp[1], lp[2]) - so;
-            if (any_hit_range<COUNT, true>(s, self, so, sd, n_node_s, n_tri_s)) atomicOr(&best[r], 1ull << k);
+            if (any_hit_range<COUNT, true, SHADOW>(s, self, so, sd, n_node_s, n_tri_s, sh_min, sh_max)) atomicOr(&best[r], 1ull << k);
         }
         __builtin_amdgcn_wave_barrier();
         if (is_hit) {
@@ -643,11 +649,13 @@ __device__ __forceinline__ void store_rows_dealt(float* __restrict__ dst, const 
 // the per-segment rows, the mirrored ray and the near-end mix.  ri: the lane's row in every output (seg's rows are n apart), ray_of: the
 // same for any lane of the wave (>= n: a lane without a ray) -- the transposed row stores need it.  seg: all NULL = no per-segment rows.
 // shard: where the wave's hits are counted.  Returns the mixed sum; hit0: whether segment 0 hit.
-template <bool COUNT, bool SMOOTH, bool INT_SHIN, typename RayOf>
+// SHADOW: every segment's shadow rays run under `rule` (the builds without it never read it).
+template <bool COUNT, bool SMOOTH, bool INT_SHIN, bool SHADOW, typename RayOf>
 __device__ __forceinline__ V3 path_segments(const DevScene& s, const QueryShade& p, const srt_path_desc& path, const srt_path_out& seg, const size_t n, const size_t ri,
                                             const bool live, V3 o, V3 d, float t_min, float t_max, const uint32_t lane, uint32_t* q, unsigned long long* best,
                                             float (*wray)[64], const RayOf ray_of, unsigned long long* __restrict__ counters, const uint32_t shard, bool& hit0,
-                                            unsigned long long& n_node, unsigned long long& n_tri, unsigned long long& n_node_s, unsigned long long& n_tri_s) {
+                                            unsigned long long& n_node, unsigned long long& n_tri, unsigned long long& n_node_s, unsigned long long& n_tri_s,
+                                            const ShadowRule rule) {
     float* stage = &wray[0][0];
     V3 acc = mk(0.0f, 0.0f, 0.0f), pend = acc;          // the mix so far; the sum of the segment that waits for its weight
     float W = 1.0f, pend_k = 0.0f;                      // the weight of what follows; the waiting segment's reflectance
@@ -661,7 +669,7 @@ __device__ __forceinline__ V3 path_segments(const DevScene& s, const QueryShade&
         const int32_t id = is_hit ? (int32_t)(uint32_t)key : -1;
         float t;
         Surface f;
-        const WaveHits wh = shade_hits_rank<SMOOTH>(s, is_hit, id, o, d, t, f, wray);
+        const WaveHits wh = shade_hits_rank<SMOOTH, SHADOW>(s, is_hit, id, o, d, t, f, wray, rule.self);
         const int32_t obj = is_hit ? s.tri_obj[id] : -1;
         const size_t row = (size_t)b * n;
         if (live) {
@@ -669,7 +677,7 @@ __device__ __forceinline__ V3 path_segments(const DevScene& s, const QueryShade&
             if (seg.t) seg.t[row + ri] = t;
             if (seg.obj) seg.obj[row + ri] = obj;
         }
-        const V3 sum = shade_hits_lights<COUNT, INT_SHIN>(s, p, lane, is_hit, wh, o, d, t, f, wray, best, n_node_s, n_tri_s);
+        const V3 sum = shade_hits_lights<COUNT, INT_SHIN, SHADOW>(s, p, lane, is_hit, wh, o, d, t, f, wray, best, n_node_s, n_tri_s, rule.t_min, rule.t_max);
         __builtin_amdgcn_wave_barrier();                // phase 2 is over: the rays' slots are the stage
         if (seg.rgb_linear) { const float v[3] = { sum.x, sum.y, sum.z }; store_rows_dealt<3>(seg.rgb_linear + row * 3, lane, n, v, stage, ray_of); }
         if (seg.rays) {
@@ -711,10 +719,12 @@ __device__ __forceinline__ V3 path_segments(const DevScene& s, const QueryShade&
     return acc;
 }
 
-template <bool COUNT, bool SMOOTH, bool INT_SHIN>
-__global__ __launch_bounds__(256) void k_query_path(DevScene s, uint32_t n_rays, const float* __restrict__ rays, uint32_t wide, QueryShade p, QueryRange tr,
-                                                    srt_path_desc path, float* __restrict__ rgb_linear, uint8_t* __restrict__ rgb8, srt_path_out seg,
-                                                    unsigned long long* __restrict__ counters) {
+// The body of both k_query_path kernels: k_query_path is what a call without a shadow rule launches, argument for argument what it was;
+// k_query_path_shadow takes the rule as one more argument and is the SHADOW build of the same statements.
+template <bool COUNT, bool SMOOTH, bool INT_SHIN, bool SHADOW>
+__device__ __forceinline__ void query_path_rays(const DevScene& s, const uint32_t n_rays, const float* __restrict__ rays, const uint32_t wide, const QueryShade& p,
+                                                const QueryRange tr, const srt_path_desc& path, float* __restrict__ rgb_linear, uint8_t* __restrict__ rgb8,
+                                                const srt_path_out& seg, unsigned long long* __restrict__ counters, const ShadowRule rule) {
     __shared__ uint32_t q_all[4][QCAP];
     __shared__ unsigned long long best_all[256];
     __shared__ float ray_all[4][8][64];
@@ -730,10 +740,22 @@ __global__ __launch_bounds__(256) void k_query_path(DevScene s, uint32_t n_rays,
     if (live) load_ray(rays, ri, wide != 0, o, d);
     if (tr.t && live) load_range(tr, ri, t_min, t_max);
     bool hit0;
-    const V3 acc = path_segments<COUNT, SMOOTH, INT_SHIN>(s, p, path, seg, n, ri, live, o, d, t_min, t_max, lane, q_all[wave], best_all + wave * 64, ray_all[wave], ray_of,
-                                                          counters, blockIdx.x, hit0, n_node, n_tri, n_node_s, n_tri_s);
+    const V3 acc = path_segments<COUNT, SMOOTH, INT_SHIN, SHADOW>(s, p, path, seg, n, ri, live, o, d, t_min, t_max, lane, q_all[wave], best_all + wave * 64, ray_all[wave],
+                                                                  ray_of, counters, blockIdx.x, hit0, n_node, n_tri, n_node_s, n_tri_s, rule);
     if (live) store_pixel(rgb_linear, rgb8, ri, acc, hit0, p.reinhard, p.gamma, p.bg);
     if (COUNT) { wave_add(counters + 1, n_node); wave_add(counters + 2, n_tri); wave_add(counters + 3, n_node_s); wave_add(counters + 4, n_tri_s); }
+}
+template <bool COUNT, bool SMOOTH, bool INT_SHIN>
+__global__ __launch_bounds__(256) void k_query_path(DevScene s, uint32_t n_rays, const float* __restrict__ rays, uint32_t wide, QueryShade p, QueryRange tr,
+                                                    srt_path_desc path, float* __restrict__ rgb_linear, uint8_t* __restrict__ rgb8, srt_path_out seg,
+                                                    unsigned long long* __restrict__ counters) {
+    query_path_rays<COUNT, SMOOTH, INT_SHIN, false>(s, n_rays, rays, wide, p, tr, path, rgb_linear, rgb8, seg, counters, ShadowRule{ 0.0f, 0.0f, 0u });
+}
+template <bool COUNT, bool SMOOTH, bool INT_SHIN>
+__global__ __launch_bounds__(256) void k_query_path_shadow(DevScene s, uint32_t n_rays, const float* __restrict__ rays, uint32_t wide, QueryShade p, QueryRange tr,
+                                                           srt_path_desc path, float* __restrict__ rgb_linear, uint8_t* __restrict__ rgb8, srt_path_out seg,
+                                                           unsigned long long* __restrict__ counters, ShadowRule rule) {
+    query_path_rays<COUNT, SMOOTH, INT_SHIN, true>(s, n_rays, rays, wide, p, tr, path, rgb_linear, rgb8, seg, counters, rule);
 }
 
 // =================================================================================================
@@ -748,10 +770,11 @@ __global__ __launch_bounds__(256) void k_query_path(DevScene s, uint32_t n_rays,
 // and the pixel leaves once, as k_accumulate / k_resolve make it (tone-mapped whatever was hit: a black quotient is the background).
 // seg's rows are sub-sample 0's.  counters: as k_query_path's, over all sub-samples; the hit shard is the 2-D workgroup number.
 // =================================================================================================
-template <bool COUNT, bool SMOOTH, bool INT_SHIN>
-__global__ __launch_bounds__(256) void k_render_path(DevScene s, DevParams fp, uint32_t spp, uint32_t spp_m, QueryShade p, srt_path_desc path,
-                                                     float* __restrict__ rgb_linear, uint8_t* __restrict__ rgb8, srt_path_out seg,
-                                                     unsigned long long* __restrict__ counters) {
+// The body of both k_render_path kernels, as query_path_rays is k_query_path's.  fp: the frame's geometry; sub_x / sub_y change per sub-sample.
+template <bool COUNT, bool SMOOTH, bool INT_SHIN, bool SHADOW>
+__device__ __forceinline__ void render_path_pixels(const DevScene& s, DevParams& fp, const uint32_t spp, const uint32_t spp_m, const QueryShade& p, const srt_path_desc& path,
+                                                   float* __restrict__ rgb_linear, uint8_t* __restrict__ rgb8, const srt_path_out& seg,
+                                                   unsigned long long* __restrict__ counters, const ShadowRule rule) {
     __shared__ uint32_t q_all[4][QCAP];
     __shared__ unsigned long long best_all[256];
     __shared__ float ray_all[4][8][64];
@@ -774,12 +797,25 @@ __global__ __launch_bounds__(256) void k_render_path(DevScene s, DevParams fp, u
         }
         const V3 d = live ? primary_dir(fp, px, y) : mk(0.0f, 0.0f, 1.0f);
         bool h;
-        const V3 acc = path_segments<COUNT, SMOOTH, INT_SHIN>(s, p, path, k == 0 ? seg : srt_path_out{}, n, ri, live, o, d, __builtin_nanf(""), __builtin_nanf(""), lane,
-                                                              q_all[wave], best_all + wave * 64, ray_all[wave], ray_of, counters, shard, h, n_node, n_tri, n_node_s, n_tri_s);
+        const V3 acc = path_segments<COUNT, SMOOTH, INT_SHIN, SHADOW>(s, p, path, k == 0 ? seg : srt_path_out{}, n, ri, live, o, d, __builtin_nanf(""), __builtin_nanf(""), lane,
+                                                                      q_all[wave], best_all + wave * 64, ray_all[wave], ray_of, counters, shard, h, n_node, n_tri, n_node_s,
+                                                                      n_tri_s, rule);
         if (k == 0) { total = acc; hit0 = h; }
         else total = mk(total.x + acc.x, total.y + acc.y, total.z + acc.z);
     }
     if (spp > 1) { const float f = (float)spp; total = mk(total.x / f, total.y / f, total.z / f); hit0 = true; }
     if (live) store_pixel(rgb_linear, rgb8, ri, total, hit0, p.reinhard, p.gamma, p.bg);
     if (COUNT) { wave_add(counters + 1, n_node); wave_add(counters + 2, n_tri); wave_add(counters + 3, n_node_s); wave_add(counters + 4, n_tri_s); }
+}
+template <bool COUNT, bool SMOOTH, bool INT_SHIN>
+__global__ __launch_bounds__(256) void k_render_path(DevScene s, DevParams fp, uint32_t spp, uint32_t spp_m, QueryShade p, srt_path_desc path,
+                                                     float* __restrict__ rgb_linear, uint8_t* __restrict__ rgb8, srt_path_out seg,
+                                                     unsigned long long* __restrict__ counters) {
+    render_path_pixels<COUNT, SMOOTH, INT_SHIN, false>(s, fp, spp, spp_m, p, path, rgb_linear, rgb8, seg, counters, ShadowRule{ 0.0f, 0.0f, 0u });
+}
+template <bool COUNT, bool SMOOTH, bool INT_SHIN>
+__global__ __launch_bounds__(256) void k_render_path_shadow(DevScene s, DevParams fp, uint32_t spp, uint32_t spp_m, QueryShade p, srt_path_desc path,
+                                                            float* __restrict__ rgb_linear, uint8_t* __restrict__ rgb8, srt_path_out seg,
+                                                            unsigned long long* __restrict__ counters, ShadowRule rule) {
+    render_path_pixels<COUNT, SMOOTH, INT_SHIN, true>(s, fp, spp, spp_m, p, path, rgb_linear, rgb8, seg, counters, rule);
 }

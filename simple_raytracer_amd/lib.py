@@ -25,7 +25,8 @@ ABI_SYMBOLS = ("srt_params_default", "srt_light_staircase", "srt_rows_owned", "s
                "srt_trace_rays_range_device", "srt_trace_rays_range", "srt_occluded_range_device", "srt_occluded_range",
                "srt_trace_rays_multi_device", "srt_trace_rays_multi", "srt_shade_rays_range_device", "srt_shade_rays_range",
                "srt_surface_rays_device", "srt_surface_rays", "srt_surface_hits_device", "srt_surface_hits", "srt_shade_paths_device", "srt_shade_paths",
-               "srt_render_paths_device", "srt_render_paths")
+               "srt_render_paths_device", "srt_render_paths", "srt_shade_paths_shadow_device", "srt_shade_paths_shadow", "srt_render_paths_shadow_device",
+               "srt_render_paths_shadow")
 MULTI_HIT_MAX = 16                # SRT_MULTI_HIT_MAX
 
 _f32p, _i32p, _u8p, _u32p = C.POINTER(C.c_float), C.POINTER(C.c_int32), C.POINTER(C.c_uint8), C.POINTER(C.c_uint32)
@@ -137,6 +138,14 @@ def load(path=None):
         L.srt_render_paths_device.restype = C.c_int
         L.srt_render_paths.argtypes = [C.c_void_p, C.POINTER(abi.Params), C.POINTER(abi.PathDesc), _f32p, _u8p, C.POINTER(abi.PathOut), C.POINTER(abi.Stats)]
         L.srt_render_paths.restype = C.c_int
+        # the same four under a shadow rule: one srt_shadow_rule* after the path
+        _rule = C.POINTER(abi.ShadowRule)
+        L.srt_shade_paths_shadow_device.argtypes = L.srt_shade_paths_device.argtypes[:6] + [_rule] + L.srt_shade_paths_device.argtypes[6:]
+        L.srt_shade_paths_shadow.argtypes = L.srt_shade_paths.argtypes[:6] + [_rule] + L.srt_shade_paths.argtypes[6:]
+        L.srt_render_paths_shadow_device.argtypes = L.srt_render_paths_device.argtypes[:3] + [_rule] + L.srt_render_paths_device.argtypes[3:]
+        L.srt_render_paths_shadow.argtypes = L.srt_render_paths.argtypes[:3] + [_rule] + L.srt_render_paths.argtypes[3:]
+        for f in (L.srt_shade_paths_shadow_device, L.srt_shade_paths_shadow, L.srt_render_paths_shadow_device, L.srt_render_paths_shadow):
+            f.restype = C.c_int
         L.srt_strerror.argtypes = [C.c_int]
         L.srt_strerror.restype = C.c_char_p
         L.srt_last_hip_error.restype = C.c_int
@@ -468,12 +477,15 @@ class DeviceScene:
                                               C.c_void_p(stream), C.byref(so)), "srt_surface_hits_device")
 
     def shade_paths(self, rays, params: abi.Params, depth, reflectance=None, bounce_t_min=1e-3, t_range=None,
-                    want=("rgb_linear", "rgb8", "seg_hit_id", "seg_t", "seg_obj", "seg_rgb_linear", "seg_rays"), count=False, smooth=False):
+                    want=("rgb_linear", "rgb8", "seg_hit_id", "seg_t", "seg_obj", "seg_rgb_linear", "seg_rays"), count=False, smooth=False, shadow=None):
         """srt_shade_paths: every ray of `rays` (n x 6, host array) followed through up to `depth` mirror bounces, each hit shaded as
         shade_rays(t_range=...) shades it, the segments mixed by `reflectance` (one float per object, or None = all 0).  A mirrored ray's
         interval is (bounce_t_min, +inf); t_range (n x 2) bounds segment 0.  Returns a dict of the arrays named in `want` -- rgb_linear
         n x 3 (mixed), rgb8 n x 3, and per segment seg_hit_id / seg_t / seg_obj depth x n, seg_rgb_linear depth x n x 3, seg_rays
-        depth x n x 6 -- + 'stats'.  count / smooth add SRT_FLAG_COUNT_WORK / SRT_FLAG_SMOOTH_NORMALS for this call."""
+        depth x n x 6 -- + 'stats'.  count / smooth add SRT_FLAG_COUNT_WORK / SRT_FLAG_SMOOTH_NORMALS for this call.
+        shadow: None = the reference's shadow rule (unbounded, the hit object left out), or (t_min, t_max, self_shadow): a shadow
+        ray blocks only inside the closed (t_min, t_max) in units of light - hit point, and with self_shadow the hit object's own tree
+        is walked too (srt_*_paths_shadow)."""
         r = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
         n = r.shape[0]
         tr = _t_range(t_range, n)
@@ -492,32 +504,41 @@ class DeviceScene:
         g = lambda k, ty: out[k].ctypes.data_as(ty) if k in out else ty()
         flags = params.flags
         params.flags = flags | (abi.SRT_FLAG_COUNT_WORK if count else 0) | (abi.SRT_FLAG_SMOOTH_NORMALS if smooth else 0)
+        rule = abi.shadow_rule(shadow)
+        head = (self.h, n, r.ctypes.data_as(_f32p), tr.ctypes.data_as(_f32p) if tr is not None else None, C.byref(params), C.byref(pd))
+        tail = (g("rgb_linear", _f32p), g("rgb8", _u8p), C.byref(po), C.byref(st))
         try:
-            rc = self.L.srt_shade_paths(self.h, n, r.ctypes.data_as(_f32p), tr.ctypes.data_as(_f32p) if tr is not None else None, C.byref(params), C.byref(pd),
-                                        g("rgb_linear", _f32p), g("rgb8", _u8p), C.byref(po), C.byref(st))
+            rc = self.L.srt_shade_paths(*head, *tail) if rule is None else self.L.srt_shade_paths_shadow(*head, C.byref(rule), *tail)
         finally:
             params.flags = flags
-        _check(rc, "srt_shade_paths")
+        _check(rc, "srt_shade_paths" if rule is None else "srt_shade_paths_shadow")
         out["stats"] = st.as_dict()
         return out
 
     def shade_paths_device(self, n, rays, params: abi.Params, depth, reflectance=0, bounce_t_min=1e-3, t_range=None, stream=0, rgb_linear=0, rgb8=0, seg_hit_id=0,
-                           seg_t=0, seg_obj=0, seg_rgb_linear=0, seg_rays=0):
+                           seg_t=0, seg_obj=0, seg_rgb_linear=0, seg_rays=0, shadow=None):
         """srt_shade_paths_device: raw device pointers (ints, e.g. torch.Tensor.data_ptr()) in, asynchronous on `stream`, one launch.  The
         light table of `params` is a host array; `reflectance` is a DEVICE pointer to n_objects floats (0 = all 0); t_range a device
-        pointer to n x 2 floats, or None; the seg_* outputs are depth x n rows, segment-major.  The flags are those of `params`."""
+        pointer to n x 2 floats, or None; the seg_* outputs are depth x n rows, segment-major.  The flags are those of `params`.
+        shadow: as in shade_paths."""
         pd = abi.PathDesc(depth, bounce_t_min, reflectance or None)
         po = abi.PathOut(seg_hit_id or None, seg_t or None, seg_obj or None, seg_rgb_linear or None, seg_rays or None)
-        _check(self.L.srt_shade_paths_device(self.h, n, C.c_void_p(rays), C.c_void_p(t_range or 0), C.byref(params), C.byref(pd), C.c_void_p(stream),
-                                             C.c_void_p(rgb_linear), C.c_void_p(rgb8), C.byref(po)), "srt_shade_paths_device")
+        rule = abi.shadow_rule(shadow)
+        head = (self.h, n, C.c_void_p(rays), C.c_void_p(t_range or 0), C.byref(params), C.byref(pd))
+        tail = (C.c_void_p(stream), C.c_void_p(rgb_linear), C.c_void_p(rgb8), C.byref(po))
+        if rule is None:
+            _check(self.L.srt_shade_paths_device(*head, *tail), "srt_shade_paths_device")
+        else:
+            _check(self.L.srt_shade_paths_shadow_device(*head, C.byref(rule), *tail), "srt_shade_paths_shadow_device")
 
     def render_paths(self, params: abi.Params, depth, reflectance=None, bounce_t_min=1e-3,
-                     want=("rgb_linear", "rgb8", "seg_hit_id", "seg_t", "seg_obj", "seg_rgb_linear", "seg_rays"), count=False, smooth=False, fill=None):
+                     want=("rgb_linear", "rgb8", "seg_hit_id", "seg_t", "seg_obj", "seg_rgb_linear", "seg_rays"), count=False, smooth=False, fill=None, shadow=None):
         """srt_render_paths: shade_paths for the rays of the frame's own pixels -- the local pixels of a call with `params` (its block or
         tile deal, camera matrix and spp included); no ray array is built.  Returns a dict of the arrays named in `want` -- rgb_linear
         [rows, cols, 3] (mixed), rgb8 [rows, cols, 3], and per segment seg_hit_id / seg_t / seg_obj [depth, rows, cols], seg_rgb_linear
         [depth, rows, cols, 3], seg_rays [depth, rows, cols, 6] -- + 'stats'.  count / smooth add SRT_FLAG_COUNT_WORK /
-        SRT_FLAG_SMOOTH_NORMALS for this call.  fill: a value every array holds before the call (padding pixels of a tile deal keep it)."""
+        SRT_FLAG_SMOOTH_NORMALS for this call.  fill: a value every array holds before the call (padding pixels of a tile deal keep it).
+        shadow: as in shade_paths."""
         rows, W = self.rows(params), self.cols(params)
         refl = None if reflectance is None else np.ascontiguousarray(reflectance, np.float32).reshape(-1)
         new = (lambda shape, ty: np.empty(shape, ty)) if fill is None else (lambda shape, ty: np.full(shape, fill, ty))
@@ -535,23 +556,32 @@ class DeviceScene:
         g = lambda k, ty: out[k].ctypes.data_as(ty) if k in out else ty()
         flags = params.flags
         params.flags = flags | (abi.SRT_FLAG_COUNT_WORK if count else 0) | (abi.SRT_FLAG_SMOOTH_NORMALS if smooth else 0)
+        rule = abi.shadow_rule(shadow)
+        head = (self.h, C.byref(params), C.byref(pd))
+        tail = (g("rgb_linear", _f32p), g("rgb8", _u8p), C.byref(po), C.byref(st))
         try:
-            rc = self.L.srt_render_paths(self.h, C.byref(params), C.byref(pd), g("rgb_linear", _f32p), g("rgb8", _u8p), C.byref(po), C.byref(st))
+            rc = self.L.srt_render_paths(*head, *tail) if rule is None else self.L.srt_render_paths_shadow(*head, C.byref(rule), *tail)
         finally:
             params.flags = flags
-        _check(rc, "srt_render_paths")
+        _check(rc, "srt_render_paths" if rule is None else "srt_render_paths_shadow")
         out["stats"] = st.as_dict()
         return out
 
     def render_paths_device(self, params: abi.Params, depth, reflectance=0, bounce_t_min=1e-3, stream=0, rgb_linear=0, rgb8=0, seg_hit_id=0, seg_t=0, seg_obj=0,
-                            seg_rgb_linear=0, seg_rays=0):
+                            seg_rgb_linear=0, seg_rays=0, shadow=None):
         """srt_render_paths_device: raw device pointers (ints, e.g. torch.Tensor.data_ptr()) in, asynchronous on `stream`, one launch.  The
         light table of `params` is a host array; `reflectance` is a DEVICE pointer to n_objects floats (0 = all 0); the outputs are
-        [rows, cols, ...] and the seg_* outputs [depth, rows, cols, ...] of the call's local pixels.  The flags are those of `params`."""
+        [rows, cols, ...] and the seg_* outputs [depth, rows, cols, ...] of the call's local pixels.  The flags are those of `params`.
+        shadow: as in shade_paths."""
         pd = abi.PathDesc(depth, bounce_t_min, reflectance or None)
         po = abi.PathOut(seg_hit_id or None, seg_t or None, seg_obj or None, seg_rgb_linear or None, seg_rays or None)
-        _check(self.L.srt_render_paths_device(self.h, C.byref(params), C.byref(pd), C.c_void_p(stream), C.c_void_p(rgb_linear), C.c_void_p(rgb8), C.byref(po)),
-               "srt_render_paths_device")
+        rule = abi.shadow_rule(shadow)
+        head = (self.h, C.byref(params), C.byref(pd))
+        tail = (C.c_void_p(stream), C.c_void_p(rgb_linear), C.c_void_p(rgb8), C.byref(po))
+        if rule is None:
+            _check(self.L.srt_render_paths_device(*head, *tail), "srt_render_paths_device")
+        else:
+            _check(self.L.srt_render_paths_shadow_device(*head, C.byref(rule), *tail), "srt_render_paths_shadow_device")
 
     def sync(self):
         st = abi.Stats()

@@ -25,7 +25,9 @@ outputs and with normal + bounce only, srt_surface_hits_device on the frame's hi
 shipped one, on a scene of its own.
 --paths: instead, mirror paths of the same frame at depth 1 / 3 and 1 / 16 light samples, four ways in one run: the chain of existing device
 calls, srt_shade_paths_device on rays built beforehand, srt_render_paths_device, and at depth 1 srt_render_device.
-Usage: python tools/ray_query_probe.py [--reps N] [--trace] [--shade | --range | --shade-range | --multi | --surface | --paths [--rounds R]]     (--trace: few repetitions, for a run under rocprofv3 --kernel-trace --stats)"""
+--shadow-rule: instead, what a shadow rule costs the two path calls on the same frame at depth 1 / 3 and 1 / 16 light samples, in one run:
+srt_shade_paths_device and srt_render_paths_device with no rule (the existing kernels) beside (1e-3, 1, 0) and (1e-3, 1, SELF).
+Usage: python tools/ray_query_probe.py [--reps N] [--trace] [--shade | --range | --shade-range | --multi | --surface | --paths | --shadow-rule [--rounds R]]     (--trace: few repetitions, for a run under rocprofv3 --kernel-trace --stats)"""
 import argparse, os, sys, time
 import numpy as np
 import torch                                   # first: torch initialises HIP before the library does
@@ -372,8 +374,46 @@ def paths_section(reps, rounds):
     ds.close()
 
 
+def shadow_rule_section(reps, rounds):
+    """What a shadow rule costs srt_shade_paths_device (rays built beforehand) and srt_render_paths_device on the 1080p frame: no rule -- the
+    kernels of --paths' (b) and (c) --, shadow rays that end at the light, and those with the hit object's own tree walked too.  The light is
+    the scene's far one, so the three shade almost the same pixels: the figures are the cost of the bounded walk, which leaves at the first
+    hit IN RANGE instead of the first hit, and of the own tree."""
+    dev = torch.device("cuda", 0); torch.zeros(1, device=dev)
+    g = gu.GoldenScene("ground_bunny")
+    ds = lib.DeviceScene(g.flat)
+    side = torch.cuda.Stream(device=dev)
+    cur = side.cuda_stream
+    n = W * H
+    t_min = 1e-3
+    d_rays = torch.from_numpy(frame_rays()).to(dev)
+    refl = torch.tensor([0.6, 0.25], dtype=torch.float32, device=dev)
+    rules = (("no rule", None), ("(1e-3, 1, 0)", (1e-3, 1.0, False)), ("(1e-3, 1, SELF)", (1e-3, 1.0, True)))
+    print(f"shadow rule, K3 ground_bunny {W}x{H}: {n} rays; {rounds} rounds of {reps} calls, forms alternating; ms a call; min / max: the spread of the rounds")
+    print(f"{'depth, samples':34s} {'form':34s} {'median':>8s} {'min':>8s} {'max':>8s} {'/ first':>7s}")
+    for depth in (1, 3):
+        for L in (1, 16):
+            lights = abi.light_staircase(g.light, L)
+            p = abi.make_params(W, H, lights, focal=FOCAL, flags=abi.SRT_FLAG_NO_TIMING)
+            pq = abi.make_params(1, 1, lights)
+            lin = {name: (torch.empty((n, 3), dtype=torch.float32, device=dev), torch.empty((H, W, 3), dtype=torch.float32, device=dev)) for name, _ in rules}
+            paths = {f"shade_paths_device, {name}": (lambda rule=rule, out=lin[name][0]: ds.shade_paths_device(
+                n, d_rays.data_ptr(), pq, depth, reflectance=refl.data_ptr(), bounce_t_min=t_min, stream=cur, rgb_linear=out.data_ptr(), shadow=rule)) for name, rule in rules}
+            frames = {f"render_paths_device, {name}": (lambda rule=rule, out=lin[name][1]: ds.render_paths_device(
+                p, depth, reflectance=refl.data_ptr(), bounce_t_min=t_min, stream=cur, rgb_linear=out.data_ptr(), shadow=rule)) for name, rule in rules}
+            report(f"depth {depth}, {L} samples", rounds_of(paths, reps, rounds, side))
+            report(f"depth {depth}, {L} samples", rounds_of(frames, reps, rounds, side))
+            side.synchronize()
+            for name, _ in rules:
+                assert torch.equal(lin[name][0].view(torch.int32), lin[name][1].view(torch.int32).reshape(n, 3)), f"{name}: the two calls differ"
+            diff = {name: int((lin[name][0].view(torch.int32) != lin["no rule"][0].view(torch.int32)).any(dim=1).sum().item()) for name, _ in rules[1:]}
+            print(f"{'':34s} both calls give the same bits under every rule; pixels that differ from no rule: {diff}")
+    ds.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--shadow-rule", action="store_true", dest="shadow_rule")
     ap.add_argument("--paths", action="store_true")
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--trace", action="store_true")
@@ -385,6 +425,8 @@ def main():
     ap.add_argument("--rounds", type=int, default=7)
     a = ap.parse_args()
     reps = 3 if a.trace else a.reps
+    if a.shadow_rule:
+        return shadow_rule_section(reps, 2 if a.trace else a.rounds)
     if a.paths:
         return paths_section(reps, 2 if a.trace else a.rounds)
     if a.multi:
