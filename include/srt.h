@@ -261,6 +261,54 @@ int srt_scene_set_pose_source(srt_scene* s, const float* tri_points);
 int srt_scene_pose(srt_scene* s, uint32_t n_objects, const float* obj_matrix,
                    const float* obj_color, const float* obj_material, void* stream);
 
+/* ---- REFIT from device points, an opt-in EXTENSION like pose: the caller's vertex buffer in DEVICE memory, the hierarchy refitted ----
+ * Pose covers rigid motion; a mesh that DEFORMS -- skinning, cloth, morph targets, a simulation step, an optimiser moving vertices --
+ * lives in a device buffer of the caller's.  srt_scene_refit_device takes the points from there: the tree keeps the shape and the
+ * triangles the order of the scene as created or last updated (PARITY as for pose: ids keep that scene's numbering), both triangle
+ * records are derived and every node box recomputed on the device.  No arithmetic is applied to a point or a normal: they are copied,
+ * then the records are derived.
+ * What is pinned, bit for bit: the device records after a refit are byte for byte what srt_scene_create derives from the flat scene with
+ *   points   those points, a stride of 3 meaning w = 1.0f exactly;
+ *   box      pose's fold: per component from (+FLT_MAX, -FLT_MAX), over the node's triangles in visit order, points one, two, three,
+ *            raw xyz: if (v < mn) mn = v; if (mx < v) mx = v;  -- the left operand is kept on ties, a NaN never enters a box, a leaf
+ *            without triangles keeps the start values;
+ *   the union of the root boxes as srt_scene_create computes it;
+ *   normals  d_normals given: tri_normals becomes exactly those floats -- direct form row i, indexed form the three gathered rows in
+ *            point order one, two, three; NULL: unchanged.  Texel coordinates and texture ids stay.
+ * Every render and query afterwards equals the oracle on that same flat scene.  Point values are not validated: non-finite points are
+ * memory-safe and give what the arithmetic gives.  Pipeline choice: srt_scene_overlap_estimate and the packet / node-queue decision keep
+ * the host's last value, as for pose.  A pose source stays valid across refits: poses apply to their source and do not accumulate.
+ *
+ * srt_scene_refit_prepare, a set-up call, once per tree: derives the refit's static schedule from the tree's shape (the one pose uses)
+ * and, for the indexed form, takes the index buffer: tri_vertex = n_tris x 3 entries in HOST memory, in the scene's current visit order;
+ * point j of triangle i is vertex tri_vertex[3 i + j] of a buffer of n_verts vertices.  Every entry is validated: one >= n_verts is
+ * SRT_ERR_LAYOUT, before anything is touched.  The indices are copied to the device once (12 B a triangle) and belong to the device
+ * records, so every handle of srt_scene_share sees the preparation.  tri_vertex == NULL prepares the direct form only (and drops earlier
+ * indices); n_verts is then ignored.  Waits for the device.  A later srt_scene_update or srt_scene_update_frame discards the preparation,
+ * as it discards the pose source.  NULL handle: SRT_ERR_ARG.  A tree of height above 255: SRT_ERR_LIMIT, before anything is touched --
+ * the scene keeps rendering, and is not prepared. */
+int srt_scene_refit_prepare(srt_scene* s, uint32_t n_verts, const uint32_t* tri_vertex);
+
+typedef struct srt_refit_desc {
+    uint32_t     n_verts;    /* 0: DIRECT form, d_points = n_tris x 3 points in the scene's current visit order (the layout of
+                                srt_scene_desc.tri_points); > 0: INDEXED form, d_points = n_verts points, point j of triangle i is
+                                d_points[tri_vertex[3 i + j]]; must equal the prepared n_verts                                       */
+    uint32_t     stride;     /* floats per point: 4 = raw homogeneous xyzw; 3 = xyz, w taken as 1.0f                                 */
+    const float* d_points;   /* DEVICE                                                                                               */
+    const float* d_normals;  /* DEVICE or NULL (= unchanged).  direct: n_tris x 9; indexed: n_verts x 3                              */
+} srt_refit_desc;
+
+/* The next frame from the caller's device buffers.  Asynchronous on `stream` (NULL = the scene's own stream), ordered behind the updates,
+ * poses, renders and queries already enqueued there.  The call allocates nothing, copies nothing and stages nothing; it looks at no
+ * triangle or node on the host and does not wait.  It is a fixed sequence of kernel launches and may be captured into a hipGraph; the
+ * caller's buffers are read when the kernels run, not during the call.  Any float-aligned pointer is legal: points of stride 4 in a
+ * 16-byte aligned buffer are read with 16-byte loads, everything else with 4-byte loads -- a point of stride 3 is read as exactly
+ * 12 bytes, nothing past the last point of a buffer.  Through a handle of srt_scene_share it rewrites the records all handles read,
+ * under the ordering rule of srt_scene_update.  Errors, all before anything is touched: NULL handle, g or d_points, a stride other
+ * than 3 or 4, a scene that is not prepared, the indexed form without prepared indices, d_normals on a scene created without
+ * normals: SRT_ERR_ARG; n_verts other than the prepared one: SRT_ERR_LAYOUT. */
+int srt_scene_refit_device(srt_scene* s, const srt_refit_desc* g, void* stream);
+
 /* Render into DEVICE buffers (rows = srt_rows_owned(p)); any output pointer may be NULL.
  *   d_hit_id     rows x W   int32   canonical triangle id, -1 = miss
  *   d_t          rows x W   f32     closest-hit distance (+inf on miss)

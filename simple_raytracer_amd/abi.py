@@ -46,6 +46,11 @@ class FrameGeometry(C.Structure):
     ]
 
 
+class RefitDesc(C.Structure):
+    """srt_refit_desc (include/srt.h, REFIT): the caller's device buffers as addresses; n_verts 0 = the direct form."""
+    _fields_ = [("n_verts", C.c_uint32), ("stride", C.c_uint32), ("d_points", C.c_void_p), ("d_normals", C.c_void_p)]
+
+
 class Params(C.Structure):
     _fields_ = [
         ("width", C.c_uint32), ("height", C.c_uint32),

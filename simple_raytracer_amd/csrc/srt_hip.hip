@@ -125,6 +125,8 @@ struct SceneRecords {
     // static schedule of the refit -- node heights, the roots of the bottom subtrees, per object the nodes above them sorted by height
     float4* d_pose_points = nullptr; float2* d_tri_box = nullptr; float* d_obj_matrix = nullptr; uint8_t* d_height = nullptr;
     int32_t* d_sub_root = nullptr; int32_t* d_top_nodes = nullptr; int32_t* d_top_off = nullptr; uint32_t n_sub = 0; bool have_pose = false;
+    // refit from device points (srt_scene_refit_device): the same schedule, and the index buffer of the indexed form (visit order)
+    uint32_t* d_tri_vertex = nullptr; uint32_t refit_verts = 0; bool have_refit = false, have_refit_index = false;
     ~SceneRecords() { (void)hipSetDevice(device); }      // (the arrays go with `owned`, after this body)
     hipError_t make(void** out, size_t bytes) {
         owned.emplace_back();
@@ -595,6 +597,7 @@ static void note_records(SceneRecords& r, const srt_scene_desc* d, const RecordL
     r.int_shin = all_integer_shininess(d->obj_material, d->n_objects);
     r.have_source = false;               // attributes in source order belong to the previous contents
     r.have_pose = false;                 // ... and so do the pose source's order and the refit's schedule
+    r.have_refit = r.have_refit_index = false;
 }
 
 static int scene_create_impl(int device, const srt_scene_desc* d, srt_scene** out) {
@@ -802,22 +805,25 @@ static int scene_update_frame_impl(srt_scene* s, const srt_frame_geometry* g, hi
                        s->dev.nodes, const_cast<DevNode*>(s->dev.root_nodes));
     HIP_TRY(hipGetLastError());
     r.have_pose = false;                                        // another visit order: the pose source is no longer these triangles
+    r.have_refit = r.have_refit_index = false;                  // ... nor are the refit's indices
     r.overlap = overlap_estimate(boxes, r.h_leaf.data(), (uint32_t)nN, r.h_ranges.data(), nO);      // expected slab tests per ray, from this frame's boxes
     r.prefer_packet = r.overlap > PACKET_OVERLAP_THRESHOLD;
     return SRT_OK;
 }
 
-// ---- pose: one matrix per object, the hierarchy refitted on the device (srt_kernels.h, "Pose") -----------------------------------
-// Everything proportional to triangles or nodes happens HERE, once: the points go to the device and the refit's static schedule is
-// derived from the tree's shape.  Synchronous (a set-up call): waits for the device, so that no earlier pose still reads what it replaces.
-static int scene_set_pose_source_impl(srt_scene* s, const float* tri_points) {
-    if (!s || !tri_points) return SRT_ERR_ARG;
-    SceneRecords& r = *s->rec;
-    const size_t nN = s->dev.n_nodes, nT = s->dev.n_tris, nO = s->dev.n_objects;
+// ---- pose and refit: the hierarchy refitted on the device (srt_kernels.h, "Pose") -------------------------------------------------
+// The refit's static schedule, derived from the tree's shape: node heights, the roots of the bottom subtrees, per object the nodes
+// above them sorted by height.  Nothing is touched before the tree is known to be within the limit.
+struct RefitSchedule {
+    std::vector<uint8_t> height; std::vector<int32_t> sub_root, top_nodes, top_off;
+};
+static int refit_schedule(const SceneRecords& r, size_t nN, size_t nO, RefitSchedule* out) {
     // height of every node (children follow their parent in pre-order); bottom subtrees = maximal subtrees of height <= POSE_SUB_HEIGHT
     alloc_gate();
-    std::vector<uint8_t> height(nN, 0);
-    std::vector<int32_t> parent(nN, -1), sub_root, top_nodes, top_off(nO + 1, 0);
+    std::vector<uint8_t>& height = out->height; std::vector<int32_t>& sub_root = out->sub_root; std::vector<int32_t>& top_nodes = out->top_nodes;
+    std::vector<int32_t>& top_off = out->top_off;
+    height.assign(nN, 0); top_off.assign(nO + 1, 0);
+    std::vector<int32_t> parent(nN, -1);
     for (size_t i = nN; i-- > 0;) {
         if (r.h_leaf[i] >= 0) continue;
         const size_t l = i + 1, rr = (size_t)(~r.h_leaf[i]);
@@ -835,18 +841,55 @@ static int scene_set_pose_source_impl(srt_scene* s, const float* tri_points) {
         std::stable_sort(top_nodes.begin() + top_off[k], top_nodes.end(), [&](int32_t a, int32_t b) { return height[a] < height[b]; });
     }
     top_off[nO] = (int32_t)top_nodes.size();
+    return SRT_OK;
+}
+
+// The schedule on the device, with the arrays the refit writes between its launches (each triangle's own box, the box arrays).  The
+// device is idle (the caller has waited): no earlier pose or refit still reads what this replaces.
+static int refit_schedule_upload(srt_scene* s, const RefitSchedule& c) {
+    SceneRecords& r = *s->rec;
+    const size_t nN = s->dev.n_nodes, nT = s->dev.n_tris, nO = s->dev.n_objects;
+    SRT_TRY(lazy_array(s, &r.d_tri_box, nT * 24));
+    SRT_TRY(lazy_array(s, &r.d_height, nN, c.height.data(), nN));
+    SRT_TRY(lazy_array(s, &r.d_sub_root, nN * 4, c.sub_root.data(), c.sub_root.size() * 4));      // (capacities for any tree of these counts)
+    SRT_TRY(lazy_array(s, &r.d_top_nodes, nN * 4, c.top_nodes.data(), c.top_nodes.size() * 4));
+    SRT_TRY(lazy_array(s, &r.d_top_off, (nO + 1) * 4, c.top_off.data(), (nO + 1) * 4));
+    SRT_TRY(lazy_array(s, &r.d_box_min, nN * 12));
+    SRT_TRY(lazy_array(s, &r.d_box_max, nN * 12));
+    r.n_sub = (uint32_t)c.sub_root.size();
+    return SRT_OK;
+}
+
+// Everything behind the per-triangle launch of a pose or a refit: the boxes from the triangles' own boxes up to the roots, into the
+// 32 B, 64 B and root records, and the scene box.  Five launches.
+static void enqueue_refit_boxes(srt_scene* s, hipStream_t stream) {
+    SceneRecords& r = *s->rec;
+    const uint32_t nO = s->dev.n_objects; const size_t nN = s->dev.n_nodes;
+    hipLaunchKernelGGL(k_pose_boxes, dim3(r.n_sub), dim3(128), 0, stream, (const int32_t*)r.d_sub_root, s->dev.nodes, (const uint8_t*)r.d_height,
+                       (const float2*)r.d_tri_box, r.d_box_min, r.d_box_max);
+    hipLaunchKernelGGL(k_pose_top, dim3(nO), dim3(256), 0, stream, (const int32_t*)r.d_top_off, (const int32_t*)r.d_top_nodes, s->dev.nodes,
+                       (const uint8_t*)r.d_height, r.d_box_min, r.d_box_max);
+    hipLaunchKernelGGL(k_update_nodes, dim3((uint32_t)((nN + 255) / 256)), dim3(256), 0, stream, (uint32_t)nN, (const float*)r.d_box_min, (const float*)r.d_box_max,
+                       const_cast<DevNode*>(s->dev.nodes), const_cast<DevWide*>(s->dev.wide), (const int32_t*)r.d_widx);
+    hipLaunchKernelGGL(k_update_roots, dim3((nO + 63) / 64), dim3(64), 0, stream, nO, s->dev.obj_range, (const float*)r.d_box_min, (const float*)r.d_box_max,
+                       s->dev.nodes, const_cast<DevNode*>(s->dev.root_nodes));
+    hipLaunchKernelGGL(k_pose_scene_box, dim3(1), dim3(256), 0, stream, nO, s->dev.obj_range, (const float*)r.d_box_min, (const float*)r.d_box_max,
+                       const_cast<float*>(s->dev.scene_box));
+}
+
+// Everything proportional to triangles or nodes happens HERE, once: the points go to the device and the refit's static schedule is
+// derived from the tree's shape.  Synchronous (a set-up call): waits for the device, so that no earlier pose still reads what it replaces.
+static int scene_set_pose_source_impl(srt_scene* s, const float* tri_points) {
+    if (!s || !tri_points) return SRT_ERR_ARG;
+    SceneRecords& r = *s->rec;
+    const size_t nN = s->dev.n_nodes, nT = s->dev.n_tris, nO = s->dev.n_objects;
+    RefitSchedule c;
+    SRT_TRY(refit_schedule(r, nN, nO, &c));
     HIP_TRY(hipSetDevice(s->device));
     HIP_TRY(hipDeviceSynchronize());
     SRT_TRY(lazy_array(s, &r.d_pose_points, nT * 48, tri_points, nT * 48));
-    SRT_TRY(lazy_array(s, &r.d_tri_box, nT * 24));
     SRT_TRY(lazy_array(s, &r.d_obj_matrix, nO * 64));
-    SRT_TRY(lazy_array(s, &r.d_height, nN, height.data(), nN));
-    SRT_TRY(lazy_array(s, &r.d_sub_root, nN * 4, sub_root.data(), sub_root.size() * 4));      // (capacities for any tree of these counts)
-    SRT_TRY(lazy_array(s, &r.d_top_nodes, nN * 4, top_nodes.data(), top_nodes.size() * 4));
-    SRT_TRY(lazy_array(s, &r.d_top_off, (nO + 1) * 4, top_off.data(), (nO + 1) * 4));
-    SRT_TRY(lazy_array(s, &r.d_box_min, nN * 12));
-    SRT_TRY(lazy_array(s, &r.d_box_max, nN * 12));
-    r.n_sub = (uint32_t)sub_root.size();
+    SRT_TRY(refit_schedule_upload(s, c));
     r.have_pose = true;
     return SRT_OK;
 }
@@ -865,7 +908,7 @@ static int scene_pose_impl(srt_scene* s, uint32_t n_objects, const float* obj_ma
     if (n_objects != nO) return SRT_ERR_LAYOUT;
     if (!stream) SRT_TRY(own_stream(s, &stream));
     HIP_TRY(hipSetDevice(s->device));
-    const size_t nN = s->dev.n_nodes, nT = s->dev.n_tris;
+    const size_t nT = s->dev.n_tris;
     auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
     const size_t o_mtx = 0, o_col = o_mtx + pad((size_t)nO * 64), o_mat = o_col + pad((size_t)nO * 12), total = o_mat + pad((size_t)nO * 12);
     char* h = nullptr;
@@ -878,22 +921,77 @@ static int scene_pose_impl(srt_scene* s, uint32_t n_objects, const float* obj_ma
     if (obj_material) r.int_shin = all_integer_shininess(obj_material, nO);
     if (nT) hipLaunchKernelGGL(k_pose_tris, dim3((uint32_t)((nT + 255) / 256)), dim3(256), 0, stream, (uint32_t)nT, s->dev.tri_obj, (const float*)r.d_obj_matrix,
                                (const float4*)r.d_pose_points, const_cast<DevTri*>(s->dev.tris), const_cast<DevTriO*>(s->dev.tris_o), r.d_tri_box);
-    hipLaunchKernelGGL(k_pose_boxes, dim3(r.n_sub), dim3(128), 0, stream, (const int32_t*)r.d_sub_root, s->dev.nodes, (const uint8_t*)r.d_height,
-                       (const float2*)r.d_tri_box, r.d_box_min, r.d_box_max);
-    hipLaunchKernelGGL(k_pose_top, dim3(nO), dim3(256), 0, stream, (const int32_t*)r.d_top_off, (const int32_t*)r.d_top_nodes, s->dev.nodes,
-                       (const uint8_t*)r.d_height, r.d_box_min, r.d_box_max);
-    hipLaunchKernelGGL(k_update_nodes, dim3((uint32_t)((nN + 255) / 256)), dim3(256), 0, stream, (uint32_t)nN, (const float*)r.d_box_min, (const float*)r.d_box_max,
-                       const_cast<DevNode*>(s->dev.nodes), const_cast<DevWide*>(s->dev.wide), (const int32_t*)r.d_widx);
-    hipLaunchKernelGGL(k_update_roots, dim3((nO + 63) / 64), dim3(64), 0, stream, nO, s->dev.obj_range, (const float*)r.d_box_min, (const float*)r.d_box_max,
-                       s->dev.nodes, const_cast<DevNode*>(s->dev.root_nodes));
-    hipLaunchKernelGGL(k_pose_scene_box, dim3(1), dim3(256), 0, stream, nO, s->dev.obj_range, (const float*)r.d_box_min, (const float*)r.d_box_max,
-                       const_cast<float*>(s->dev.scene_box));
+    enqueue_refit_boxes(s, stream);
     HIP_TRY(hipGetLastError());
     return SRT_OK;
 }
 
 int srt_scene_pose(srt_scene* s, uint32_t n_objects, const float* obj_matrix, const float* obj_color, const float* obj_material, void* stream) {
     return guarded([&] { return scene_pose_impl(s, n_objects, obj_matrix, obj_color, obj_material, (hipStream_t)stream); });
+}
+
+// ---- refit from device points: the caller's vertex buffer in, the same refit behind it (include/srt.h, REFIT) ------------------------
+// The set-up call: the schedule, and for the indexed form the indices -- validated here, every one, so that the kernel can gather
+// without a compare -- copied to the records once.  Synchronous, as srt_scene_set_pose_source.
+static int scene_refit_prepare_impl(srt_scene* s, uint32_t n_verts, const uint32_t* tri_vertex) {
+    if (!s) return SRT_ERR_ARG;
+    SceneRecords& r = *s->rec;
+    const size_t nN = s->dev.n_nodes, nT = s->dev.n_tris, nO = s->dev.n_objects;
+    if (tri_vertex) for (size_t i = 0; i < 3 * nT; i++) if (tri_vertex[i] >= n_verts) return SRT_ERR_LAYOUT;
+    RefitSchedule c;
+    SRT_TRY(refit_schedule(r, nN, nO, &c));
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipDeviceSynchronize());
+    SRT_TRY(refit_schedule_upload(s, c));
+    r.have_refit = true; r.have_refit_index = false; r.refit_verts = 0;
+    if (tri_vertex) {
+        SRT_TRY(lazy_array(s, &r.d_tri_vertex, nT * 12, tri_vertex, nT * 12));
+        r.have_refit_index = true; r.refit_verts = n_verts;
+    }
+    return SRT_OK;
+}
+
+int srt_scene_refit_prepare(srt_scene* s, uint32_t n_verts, const uint32_t* tri_vertex) {
+    return guarded([&] { return scene_refit_prepare_impl(s, n_verts, tri_vertex); });
+}
+
+extern "C++" template <bool INDEXED, bool STRIDE4, bool WIDE>
+static void launch_refit_tris(srt_scene* s, const srt_refit_desc* g, hipStream_t stream) {
+    SceneRecords& r = *s->rec;
+    const uint32_t nT = s->dev.n_tris;
+    const dim3 grid((nT + 255) / 256), block(256);
+    if (g->d_normals)
+        hipLaunchKernelGGL((k_refit_tris<INDEXED, STRIDE4, WIDE, true>), grid, block, 0, stream, nT, g->d_points, (const uint32_t*)r.d_tri_vertex, g->d_normals,
+                           const_cast<DevTri*>(s->dev.tris), const_cast<DevTriO*>(s->dev.tris_o), r.d_tri_box, const_cast<float*>(s->dev.tri_normals));
+    else
+        hipLaunchKernelGGL((k_refit_tris<INDEXED, STRIDE4, WIDE, false>), grid, block, 0, stream, nT, g->d_points, (const uint32_t*)r.d_tri_vertex, (const float*)nullptr,
+                           const_cast<DevTri*>(s->dev.tris), const_cast<DevTriO*>(s->dev.tris_o), r.d_tri_box, (float*)nullptr);
+}
+
+// Per frame: six launches and nothing else -- no allocation, no copy, no staging, no look at a triangle or a node, no wait.
+static int scene_refit_device_impl(srt_scene* s, const srt_refit_desc* g, hipStream_t stream) {
+    if (!s || !g || !g->d_points) return SRT_ERR_ARG;
+    if (g->stride != 3 && g->stride != 4) return SRT_ERR_ARG;
+    SceneRecords& r = *s->rec;
+    if (!r.have_refit) return SRT_ERR_ARG;
+    const bool indexed = g->n_verts != 0;
+    if (indexed && !r.have_refit_index) return SRT_ERR_ARG;
+    if (g->d_normals && !s->dev.tri_normals) return SRT_ERR_ARG;
+    if (indexed && g->n_verts != r.refit_verts) return SRT_ERR_LAYOUT;
+    if (!stream) SRT_TRY(own_stream(s, &stream));
+    HIP_TRY(hipSetDevice(s->device));
+    const bool s4 = g->stride == 4, wide = s4 && ((uintptr_t)g->d_points & 15) == 0;
+    if (s->dev.n_tris) {
+        if (indexed) { if (wide) launch_refit_tris<true, true, true>(s, g, stream); else if (s4) launch_refit_tris<true, true, false>(s, g, stream); else launch_refit_tris<true, false, false>(s, g, stream); }
+        else { if (wide) launch_refit_tris<false, true, true>(s, g, stream); else if (s4) launch_refit_tris<false, true, false>(s, g, stream); else launch_refit_tris<false, false, false>(s, g, stream); }
+    }
+    enqueue_refit_boxes(s, stream);
+    HIP_TRY(hipGetLastError());
+    return SRT_OK;
+}
+
+int srt_scene_refit_device(srt_scene* s, const srt_refit_desc* g, void* stream) {
+    return guarded([&] { return scene_refit_device_impl(s, g, (hipStream_t)stream); });
 }
 
 int srt_scene_update_frame(srt_scene* s, const srt_frame_geometry* g, void* stream) {

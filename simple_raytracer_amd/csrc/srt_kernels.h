@@ -1963,6 +1963,71 @@ __global__ __launch_bounds__(256) void k_pose_tris(uint32_t n_tris, const int32_
     tri_box[3 * (size_t)g + 2] = make_float2(bx.mx[1], bx.mx[2]);
 }
 
+// Refit from device points (srt_scene_refit_device): the front end of the same refit for points the CALLER holds in device memory --
+// no matrix, no arithmetic on a point: each triangle's three points are fetched, both records derived as above, its own box folded.
+//   INDEXED   point j of triangle g is points[tri_vertex[3 g + j]] (indices validated on the host, once); else points[3 g + j]
+//   STRIDE4   a point is xyzw; else xyz with w = 1.0f, read as exactly 12 bytes
+//   WIDE      STRIDE4 and a 16-byte aligned buffer: one 16-byte load a point; else 4-byte loads (any float-aligned address)
+//   NORMALS   the 36 B normal row too: direct n_tris x 9 (a flat copy), indexed the three gathered n_verts x 3 rows
+// Direct points that are not WIDE are a run of 36 (or 48) bytes a lane: read per lane, every one of the 9 loads would touch all 18
+// cache lines of the wave's 2304 bytes.  The workgroup instead reads its contiguous 256 x 36 bytes with consecutive lanes on
+// consecutive dwords into LDS and each lane takes its 9 floats from there (a stride of 9 dwords: no two lanes of a half-wave on one bank).
+template <bool INDEXED, bool STRIDE4, bool WIDE, bool NORMALS>
+__global__ __launch_bounds__(256) void k_refit_tris(uint32_t n_tris, const float* __restrict__ points, const uint32_t* __restrict__ tri_vertex,
+                                                    const float* __restrict__ normals, DevTri* __restrict__ tris, DevTriO* __restrict__ tris_o,
+                                                    float2* __restrict__ tri_box, float* __restrict__ tri_nrm) {
+    static_assert(!WIDE || STRIDE4, "16-byte loads are for xyzw points");
+    constexpr int PF = STRIDE4 ? 4 : 3;                              // floats a point
+    constexpr bool STAGED = !INDEXED && !WIDE;
+    __shared__ float s_pts[STAGED ? 256 * 3 * PF : 1];
+    const uint32_t g0 = blockIdx.x * 256, g = g0 + threadIdx.x;
+    const uint32_t n_here = n_tris - g0 < 256u ? n_tris - g0 : 256u;  // triangles of this workgroup (the grid covers n_tris: g0 < n_tris)
+    if (STAGED) {
+        const float* src = points + (size_t)g0 * (3 * PF);
+#pragma unroll
+        for (int k = 0; k < 3 * PF; k++) { const uint32_t i = threadIdx.x + 256u * k; if (i < n_here * (3 * PF)) s_pts[i] = src[i]; }
+        __syncthreads();
+    }
+    if (NORMALS && !INDEXED) {
+        const float* src = normals + (size_t)g0 * 9; float* dst = tri_nrm + (size_t)g0 * 9;
+#pragma unroll
+        for (int k = 0; k < 9; k++) { const uint32_t i = threadIdx.x + 256u * k; if (i < n_here * 9) dst[i] = src[i]; }
+    }
+    if (g >= n_tris) return;
+    float4 a, b, c;
+    uint32_t v[3] = { 3 * g, 3 * g + 1, 3 * g + 2 };                 // (n_tris x 3 fits 32 bits: the scene's own arrays are indexed so)
+    if (INDEXED) { v[0] = tri_vertex[3 * (size_t)g]; v[1] = tri_vertex[3 * (size_t)g + 1]; v[2] = tri_vertex[3 * (size_t)g + 2]; }
+    if (STAGED) {
+        const float* q = s_pts + threadIdx.x * (3 * PF);
+        a = make_float4(q[0], q[1], q[2], STRIDE4 ? q[3] : 1.0f);
+        b = make_float4(q[PF], q[PF + 1], q[PF + 2], STRIDE4 ? q[PF + 3] : 1.0f);
+        c = make_float4(q[2 * PF], q[2 * PF + 1], q[2 * PF + 2], STRIDE4 ? q[2 * PF + 3] : 1.0f);
+    } else if (WIDE) {
+        const float4* q = (const float4*)points;
+        a = q[v[0]]; b = q[v[1]]; c = q[v[2]];
+    } else {
+        const float* qa = points + (size_t)PF * v[0]; const float* qb = points + (size_t)PF * v[1]; const float* qc = points + (size_t)PF * v[2];
+        a = make_float4(qa[0], qa[1], qa[2], STRIDE4 ? qa[3] : 1.0f);
+        b = make_float4(qb[0], qb[1], qb[2], STRIDE4 ? qb[3] : 1.0f);
+        c = make_float4(qc[0], qc[1], qc[2], STRIDE4 ? qc[3] : 1.0f);
+    }
+    const float p[12] = { a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w, c.x, c.y, c.z, c.w };
+    const DevTri t = derive_triangle(p);
+    tris[g] = t;
+    tris_o[g] = derive_triangle_origin(t);
+    PoseBox bx = pose_box_empty();
+    pose_box_point(bx, a); pose_box_point(bx, b); pose_box_point(bx, c);
+    tri_box[3 * (size_t)g] = make_float2(bx.mn[0], bx.mn[1]); tri_box[3 * (size_t)g + 1] = make_float2(bx.mn[2], bx.mx[0]);
+    tri_box[3 * (size_t)g + 2] = make_float2(bx.mx[1], bx.mx[2]);
+    if (NORMALS && INDEXED) {
+#pragma unroll
+        for (int j = 0; j < 3; j++) {
+            const float* q = normals + 3 * (size_t)v[j];
+            tri_nrm[9 * (size_t)g + 3 * j] = q[0]; tri_nrm[9 * (size_t)g + 3 * j + 1] = q[1]; tri_nrm[9 * (size_t)g + 3 * j + 2] = q[2];
+        }
+    }
+}
+
 // Workgroup b owns the bottom subtree rooted at node sub_root[b]: nodes [r, skip[r]), at most POSE_SUB_NODES of them.  `height`: 0 for
 // a leaf, 1 + max(children) for an inner node (static, derived on the host from the tree's shape).
 __global__ __launch_bounds__(128) void k_pose_boxes(const int32_t* __restrict__ sub_root, const DevNode* __restrict__ nodes, const uint8_t* __restrict__ height,

@@ -21,6 +21,7 @@ ABI_SYMBOLS = ("srt_params_default", "srt_light_staircase", "srt_rows_owned", "s
                "srt_last_hip_error", "srt_abi_version", "srt_kat_ray_aabb", "srt_kat_ray_triangle", "srt_kat_phong", "srt_kat_tonemap", "srt_kat_interp_normal", "srt_kat_pow",
                "srt_kat_ray_triangle_origin", "srt_kat_barycentric", "srt_debug_fail_host_allocs", "srt_debug_valu_rate", "srt_debug_scene_records", "srt_scene_set_source", "srt_scene_update_frame",
                "srt_scene_pipeline", "srt_scene_overlap_estimate", "srt_scene_set_pose_source", "srt_scene_pose",
+               "srt_scene_refit_prepare", "srt_scene_refit_device",
                "srt_trace_rays_device", "srt_trace_rays", "srt_occluded_device", "srt_occluded", "srt_shade_rays_device", "srt_shade_rays",
                "srt_trace_rays_range_device", "srt_trace_rays_range", "srt_occluded_range_device", "srt_occluded_range",
                "srt_trace_rays_multi_device", "srt_trace_rays_multi", "srt_shade_rays_range_device", "srt_shade_rays_range",
@@ -90,6 +91,10 @@ def load(path=None):
         L.srt_scene_set_pose_source.restype = C.c_int
         L.srt_scene_pose.argtypes = [C.c_void_p, C.c_uint32, _f32p, _f32p, _f32p, C.c_void_p]
         L.srt_scene_pose.restype = C.c_int
+        L.srt_scene_refit_prepare.argtypes = [C.c_void_p, C.c_uint32, _u32p]
+        L.srt_scene_refit_prepare.restype = C.c_int
+        L.srt_scene_refit_device.argtypes = [C.c_void_p, C.POINTER(abi.RefitDesc), C.c_void_p]
+        L.srt_scene_refit_device.restype = C.c_int
         L.srt_trace_rays_device.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.srt_trace_rays_device.restype = C.c_int
         L.srt_trace_rays.argtypes = [C.c_void_p, C.c_uint32, _f32p, C.c_uint32, _i32p, _f32p, _f32p, C.POINTER(abi.Stats)]
@@ -239,6 +244,22 @@ class DeviceScene:
         mat = None if obj_material is None else np.ascontiguousarray(obj_material, np.float32)
         _check(self.L.srt_scene_pose(self.h, m.shape[0], m.ctypes.data_as(_f32p), col.ctypes.data_as(_f32p) if col is not None else None,
                                      mat.ctypes.data_as(_f32p) if mat is not None else None, C.c_void_p(stream)), "srt_scene_pose")
+
+    def refit_prepare(self, tri_vertex=None, n_verts=0):
+        """srt_scene_refit_prepare: the refit's schedule, once per tree; tri_vertex (n_tris x 3 vertex numbers, the scene's visit order,
+        host array) and n_verts prepare the indexed form as well."""
+        tv = None
+        if tri_vertex is not None:
+            tv = np.ascontiguousarray(tri_vertex, np.uint32)
+            assert tv.size == 3 * self.flat.n_tris, "tri_vertex: n_tris x 3"
+        _check(self.L.srt_scene_refit_prepare(self.h, n_verts, tv.ctypes.data_as(_u32p) if tv is not None else None), "srt_scene_refit_prepare")
+
+    def refit_device(self, points, stride=4, n_verts=0, normals=0, stream=0):
+        """srt_scene_refit_device: raw device pointers (ints, e.g. torch.Tensor.data_ptr()) in, async on `stream`.  n_verts 0: points =
+        n_tris x 3 points of `stride` floats in visit order (normals n_tris x 9); else n_verts points gathered through the prepared
+        indices (normals n_verts x 3).  self.flat is NOT updated: it keeps the scene the handle was created or last updated from."""
+        g = abi.RefitDesc(n_verts, stride, points, normals)
+        _check(self.L.srt_scene_refit_device(self.h, C.byref(g), C.c_void_p(stream)), "srt_scene_refit_device")
 
     def records(self):
         """srt_debug_scene_records: the device records as raw numpy arrays (dict)."""
