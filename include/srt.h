@@ -716,6 +716,70 @@ int srt_render_paths_shadow_device(srt_scene* s, const srt_params* p, const srt_
 int srt_render_paths_shadow(srt_scene* s, const srt_params* p, const srt_path_desc* path, const srt_shadow_rule* shadow,
                             float* rgb_linear, uint8_t* rgb8, const srt_path_out* seg, srt_stats* stats);
 
+/* Visibility masks: which objects a walk sees -- per object, per ray, and per ray KIND in the shaded calls.  Every call above sees every
+ * object (srt_occluded's skip_obj leaves out one tree); the calls below are their masked forms.
+ * OBJECT MASKS.  A scene carries one uint32_t per object, all 0xFFFFFFFF until set.  srt_scene_set_object_masks replaces the table:
+ *   masks: host memory, n_objects words; NULL = all ones.  The table belongs to the device records, like the pose source: every handle made
+ *   with srt_scene_share sees it, and the ordering rule of srt_scene_update applies (the copy is ordered on `stream`, NULL = the scene's own;
+ *   work enqueued earlier on that stream reads the old table, work enqueued later the new one).
+ *   The table (4 B an object) is allocated by the first call, which may therefore wait; every call stages through the handle's pinned block.
+ *   The masks survive srt_scene_update, _update_frame, _pose and _refit_device: the object count cannot change.
+ *   Errors, before anything is touched: a NULL handle: SRT_ERR_ARG; n_objects other than the scene's: SRT_ERR_LAYOUT (the previous table
+ *   stays in force).
+ *   The table changes no existing call: srt_render* and every query above ignore it entirely.
+ * PARTICIPATION.  Object k takes part in the walk of a ray with mask m iff (obj_mask[k] & m) != 0.  A masked walk's candidate set is the
+ * unmasked call's, restricted to the triangles of participating objects; everything else holds on that set and keeps its definition -- each
+ * candidate's t, the range rule, ties to the lowest id, the +0 / -0 tie, the winner's own t bits.  Triangle ids keep the scene's numbering.
+ * Equivalently: the walk is the oracle on the flat scene with the other objects removed, ids mapped back.  A hidden object's tree is not
+ * walked: under SRT_FLAG_COUNT_WORK its root is neither tested nor counted, and the counters are those of the unmasked call on that reduced
+ * scene.
+ * PER-RAY MASKS (srt_trace_rays_masked, srt_occluded_masked).  ray_mask: n words, or NULL = all ones; a pointer that is only 4-byte aligned
+ * is fine.  Unless said here everything is as for srt_trace_rays_range / srt_occluded_range: layouts, a NULL t_range, flags, errors, n == 0,
+ * a NULL `occluded`, staging (ray_mask goes through the same pinned block as t_range), stats, the private counter set, hipGraph capture of
+ * the _device forms without SRT_FLAG_COUNT_WORK (the table is read when the kernel runs), one launch with no allocation and no copy.
+ *   skip_obj still applies, on top of the masks.  A ray mask of 0 is a miss / not occluded, and no node is tested for that ray.
+ *   Identity: with the table all ones or never set, and ray_mask NULL or all ones, every output has the _range call's bits, and the counters
+ *   are equal too.
+ * PER RAY KIND (srt_shade_paths_masked, srt_render_paths_masked).  Everything is as for srt_shade_paths_shadow / srt_render_paths_shadow,
+ * except which objects a walk sees: segment 0 is walked with vis->primary, every segment b >= 1 with vis->bounce, every shadow ray with
+ * vis->shadow.
+ *   A segment's hit_id / t are srt_trace_rays_masked's for that segment's ray, interval and mask.  A sample is SHADOWED iff
+ *   srt_occluded_masked answers 1 for the shadow ray with mask vis->shadow and the rule's interval and skip; a NULL rule is the reference's:
+ *   unbounded, with the hit's object skipped.  The surface, Phong, the sum, the mix, the tone map and the background rule are unchanged.
+ *   vis == NULL: the call IS the _shadow call, and launches its kernels.
+ *   Identity: a table of all ones with vis = { ~0, ~0, ~0 } gives the _shadow call's bits in every output.
+ *   Depth 1 is the masked form of srt_shade_rays_range (in a frame: of srt_render_device in camera mode); there is no further entry point.
+ *   *stats: as for the _shadow calls; the primary counters count the masked walks, the shadow counters the walk as it runs -- objects in
+ *   order, hidden and skipped objects not entered.
+ * So: a pick among selectable objects is a ray mask; an object that casts no shadow has no bit of vis->shadow; a holdout -- hidden from the
+ * camera, present in mirrors and shadows -- has no bit of vis->primary; an object is switched off for a frame by a mask of 0 in the table.
+ * NOT HERE: masks for srt_trace_rays_multi and srt_surface_rays -- feed a masked trace's hit_id / t to srt_surface_hits instead -- and
+ * per-ray masks inside the shaded calls. */
+typedef struct srt_visibility { uint32_t primary, bounce, shadow; } srt_visibility;
+int srt_scene_set_object_masks(srt_scene* s, uint32_t n_objects, const uint32_t* masks /* host, n_objects; NULL = all ones */, void* stream);
+int srt_trace_rays_masked_device(srt_scene* s, uint32_t n, const float* d_rays, const float* d_t_range /* n x 2 or NULL */,
+                                 const uint32_t* d_ray_mask /* n or NULL = all ones */, uint32_t flags, void* stream,
+                                 int32_t* d_hit_id, float* d_t, float* d_bary);
+int srt_trace_rays_masked(srt_scene* s, uint32_t n, const float* rays, const float* t_range, const uint32_t* ray_mask, uint32_t flags,
+                          int32_t* hit_id, float* t, float* bary, srt_stats* stats);
+int srt_occluded_masked_device(srt_scene* s, uint32_t n, const float* d_rays, const float* d_t_range /* n x 2 or NULL */,
+                               const uint32_t* d_ray_mask /* n or NULL = all ones */, const int32_t* d_skip_obj, void* stream,
+                               uint8_t* d_occluded);
+int srt_occluded_masked(srt_scene* s, uint32_t n, const float* rays, const float* t_range, const uint32_t* ray_mask,
+                        const int32_t* skip_obj, uint8_t* occluded);
+int srt_shade_paths_masked_device(srt_scene* s, uint32_t n, const float* d_rays, const float* d_t_range /* n x 2 or NULL */,
+                                  const srt_params* p, const srt_path_desc* path, const srt_shadow_rule* shadow /* or NULL */,
+                                  const srt_visibility* vis /* or NULL */, void* stream,
+                                  float* d_rgb_linear /* n x 3, mixed */, uint8_t* d_rgb8 /* n x 3 */, const srt_path_out* seg);
+int srt_shade_paths_masked(srt_scene* s, uint32_t n, const float* rays, const float* t_range, const srt_params* p,
+                           const srt_path_desc* path, const srt_shadow_rule* shadow, const srt_visibility* vis,
+                           float* rgb_linear, uint8_t* rgb8, const srt_path_out* seg, srt_stats* stats);
+int srt_render_paths_masked_device(srt_scene* s, const srt_params* p, const srt_path_desc* path, const srt_shadow_rule* shadow /* or NULL */,
+                                   const srt_visibility* vis /* or NULL */, void* stream,
+                                   float* d_rgb_linear /* n x 3, mixed */, uint8_t* d_rgb8 /* n x 3 */, const srt_path_out* seg);
+int srt_render_paths_masked(srt_scene* s, const srt_params* p, const srt_path_desc* path, const srt_shadow_rule* shadow,
+                            const srt_visibility* vis, float* rgb_linear, uint8_t* rgb8, const srt_path_out* seg, srt_stats* stats);
+
 /* Device-resident size of the scene records and the per-record algorithmic byte sizes used by
  * the bytes model: 32 B per node test, 36 B per triangle test. */
 uint64_t srt_scene_device_bytes(const srt_scene* s);

@@ -116,6 +116,20 @@ def shadow_rule(shadow):
     return ShadowRule(t_min, t_max, SRT_SHADOW_SELF if self_shadow else 0)
 
 
+class Visibility(C.Structure):
+    """srt_visibility: the object mask a walk of each ray KIND is made with -- segment 0, every later segment, every shadow ray.  Object k
+    takes part in a walk with mask m iff (obj_mask[k] & m) != 0 (DeviceScene.set_object_masks; all ones until set)."""
+    _fields_ = [("primary", C.c_uint32), ("bounce", C.c_uint32), ("shadow", C.c_uint32)]
+
+
+def visibility(vis):
+    """None, a Visibility, or (primary, bounce, shadow) -> a Visibility, or None."""
+    if vis is None or isinstance(vis, Visibility):
+        return vis
+    primary, bounce, shadow = vis
+    return Visibility(int(primary) & 0xFFFFFFFF, int(bounce) & 0xFFFFFFFF, int(shadow) & 0xFFFFFFFF)
+
+
 # the fields of srt_path_out: name -> (dtype, floats or ints per ray and segment)
 PATH_FIELDS = {"hit_id": (np.int32, 1), "t": (np.float32, 1), "obj": (np.int32, 1), "rgb_linear": (np.float32, 3), "rays": (np.float32, 6)}
 

@@ -127,6 +127,8 @@ struct SceneRecords {
     int32_t* d_sub_root = nullptr; int32_t* d_top_nodes = nullptr; int32_t* d_top_off = nullptr; uint32_t n_sub = 0; bool have_pose = false;
     // refit from device points (srt_scene_refit_device): the same schedule, and the index buffer of the indexed form (visit order)
     uint32_t* d_tri_vertex = nullptr; uint32_t refit_verts = 0; bool have_refit = false, have_refit_index = false;
+    // visibility masks (srt_scene_set_object_masks): one word an object, made by the first call; null reads as all ones
+    uint32_t* d_obj_mask = nullptr;
     ~SceneRecords() { (void)hipSetDevice(device); }      // (the arrays go with `owned`, after this body)
     hipError_t make(void** out, size_t bytes) {
         owned.emplace_back();
@@ -930,6 +932,34 @@ int srt_scene_pose(srt_scene* s, uint32_t n_objects, const float* obj_matrix, co
     return guarded([&] { return scene_pose_impl(s, n_objects, obj_matrix, obj_color, obj_material, (hipStream_t)stream); });
 }
 
+// ---- visibility masks: the scene's table (include/srt.h, "Visibility masks") ------------------------------------------------------------
+// The table is part of the records, so every handle made with srt_scene_share reads it.  The first call makes it (hipMalloc may wait);
+// every call writes it through the pinned staging block with a copy ordered on `stream`, as srt_scene_pose writes its matrices.  Nothing
+// else of the scene is touched, and no update, pose or refit touches the table.
+static int scene_set_object_masks_impl(srt_scene* s, uint32_t n_objects, const uint32_t* masks, hipStream_t stream) {
+    if (!s) return SRT_ERR_ARG;
+    SceneRecords& r = *s->rec;
+    const uint32_t nO = s->dev.n_objects;
+    if (n_objects != nO) return SRT_ERR_LAYOUT;
+    if (!masks && !r.d_obj_mask) return SRT_OK;      // never set, and set to all ones: the same table
+    if (!stream) SRT_TRY(own_stream(s, &stream));
+    HIP_TRY(hipSetDevice(s->device));
+    char* h = nullptr;
+    SRT_TRY(stage_acquire(s, (size_t)nO * 4, &h));
+    if (masks) std::memcpy(h, masks, (size_t)nO * 4);
+    else std::memset(h, 0xFF, (size_t)nO * 4);
+    uint32_t* table = r.d_obj_mask;
+    if (!table) SRT_TRY(lazy_array(s, &table, (size_t)nO * 4));
+    if (nO) HIP_TRY(hipMemcpyAsync(table, h, (size_t)nO * 4, hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipEventRecord(s->staged, stream));
+    r.d_obj_mask = table;      // (only now: a failed first call leaves the scene without a table, i.e. all ones)
+    return SRT_OK;
+}
+
+int srt_scene_set_object_masks(srt_scene* s, uint32_t n_objects, const uint32_t* masks, void* stream) {
+    return guarded([&] { return scene_set_object_masks_impl(s, n_objects, masks, (hipStream_t)stream); });
+}
+
 // ---- refit from device points: the caller's vertex buffer in, the same refit behind it (include/srt.h, REFIT) ------------------------
 // The set-up call: the schedule, and for the indexed form the indices -- validated here, every one, so that the kernel can gather
 // without a compare -- copied to the records once.  Synchronous, as srt_scene_set_pose_source.
@@ -1689,8 +1719,15 @@ static int query_prologue(srt_scene* s, uint32_t n, hipStream_t stream, const sr
 
 // d_t_range: the rays' t intervals (srt_*_range), or null: nothing bounds t, and the kernels are the ones without the interval.
 // count_hits: the host entry point wants hit_rays also without SRT_FLAG_COUNT_WORK
+// The masks of a masked call as its kernels take them: the scene's table as it stands in the records now, the call's per-ray masks, or
+// the three masks per ray kind.
+static inline QueryMask query_mask(const srt_scene* s, const uint32_t* d_ray_mask) { return QueryMask{ s->rec->d_obj_mask, d_ray_mask, ~0u, ~0u, ~0u }; }
+static inline QueryMask query_mask(const srt_scene* s, const srt_visibility* v) { return QueryMask{ s->rec->d_obj_mask, nullptr, v->primary, v->bounce, v->shadow }; }
+struct RayMask { const uint32_t* d; };      // the per-ray masks of srt_*_masked (d may be NULL: all ones); a NULL RayMask*: not a masked call
+
+// mask: NULL launches k_query_closest as ever; otherwise the MASK build of the same choice of COUNT and BARY
 static int trace_rays_device_impl(srt_scene* s, uint32_t n, const float* d_rays, const float* d_t_range, uint32_t flags, hipStream_t stream, int32_t* d_hit_id,
-                                  float* d_t, float* d_bary, bool count_hits) {
+                                  float* d_t, float* d_bary, bool count_hits, const RayMask* mask = nullptr) {
     SRT_TRY(check_query(s, n, d_rays, flags));
     if (!n) return SRT_OK;
     const bool count = (flags & SRT_FLAG_COUNT_WORK) != 0;
@@ -1699,8 +1736,14 @@ static int trace_rays_device_impl(srt_scene* s, uint32_t n, const float* d_rays,
     static const decltype(&k_query_closest<false, false, false>) builds[8] = {
         &k_query_closest<false, false, false>, &k_query_closest<false, true, false>, &k_query_closest<true, false, false>, &k_query_closest<true, true, false>,
         &k_query_closest<false, false, true>,  &k_query_closest<false, true, true>,  &k_query_closest<true, false, true>,  &k_query_closest<true, true, true> };
-    hipLaunchKernelGGL(builds[(d_t_range ? 4 : 0) | (count ? 2 : 0) | (d_bary ? 1 : 0)], q.grid, dim3(256), 0, q.stream, s->dev, n, d_rays, rays_wide(d_rays), d_hit_id, d_t,
-                       d_bary, q.ctr, query_range(d_t_range));
+    static const decltype(&k_query_closest_masked<false, false>) masked_builds[4] = {
+        &k_query_closest_masked<false, false>, &k_query_closest_masked<false, true>, &k_query_closest_masked<true, false>, &k_query_closest_masked<true, true> };
+    if (mask)
+        hipLaunchKernelGGL(masked_builds[(count ? 2 : 0) | (d_bary ? 1 : 0)], q.grid, dim3(256), 0, q.stream, s->dev, n, d_rays, rays_wide(d_rays), d_hit_id, d_t, d_bary, q.ctr,
+                           query_range(d_t_range), query_mask(s, mask->d));
+    else
+        hipLaunchKernelGGL(builds[(d_t_range ? 4 : 0) | (count ? 2 : 0) | (d_bary ? 1 : 0)], q.grid, dim3(256), 0, q.stream, s->dev, n, d_rays, rays_wide(d_rays), d_hit_id, d_t,
+                           d_bary, q.ctr, query_range(d_t_range));
     HIP_TRY(hipGetLastError());
     return SRT_OK;
 }
@@ -1732,13 +1775,17 @@ static int trace_rays_multi_device_impl(srt_scene* s, uint32_t n, const float* d
 }
 
 static int occluded_device_impl(srt_scene* s, uint32_t n, const float* d_rays, const float* d_t_range, const int32_t* d_skip_obj, hipStream_t stream,
-                                uint8_t* d_occluded) {
+                                uint8_t* d_occluded, const RayMask* mask = nullptr) {
     SRT_TRY(check_query(s, n, d_rays, 0));
     if (!n || !d_occluded) return SRT_OK;
     QueryLaunch q;
     SRT_TRY(query_prologue(s, n, stream, nullptr, false, &q));
-    hipLaunchKernelGGL(d_t_range ? &k_query_any<true> : &k_query_any<false>, q.grid, dim3(256), 0, q.stream, s->dev, n, d_rays, rays_wide(d_rays), d_skip_obj, d_occluded,
-                       query_range(d_t_range));
+    if (mask)
+        hipLaunchKernelGGL(&k_query_any_masked, q.grid, dim3(256), 0, q.stream, s->dev, n, d_rays, rays_wide(d_rays), d_skip_obj, d_occluded, query_range(d_t_range),
+                           query_mask(s, mask->d));
+    else
+        hipLaunchKernelGGL(d_t_range ? &k_query_any<true> : &k_query_any<false>, q.grid, dim3(256), 0, q.stream, s->dev, n, d_rays, rays_wide(d_rays), d_skip_obj, d_occluded,
+                           query_range(d_t_range));
     HIP_TRY(hipGetLastError());
     return SRT_OK;
 }
@@ -1789,9 +1836,14 @@ static inline bool paths_wanted(const float* rgb_linear, const uint8_t* rgb8, co
 static inline int check_shadow(const srt_shadow_rule* r) { return (r && (r->flags & ~(uint32_t)SRT_SHADOW_SELF)) ? SRT_ERR_ARG : SRT_OK; }
 static inline ShadowRule shadow_rule(const srt_shadow_rule* r) { return ShadowRule{ r->t_min, r->t_max, (r->flags & SRT_SHADOW_SELF) ? 1u : 0u }; }
 
+// The rule a masked call without one runs under: the reference's, stated as a rule -- no bound, the hit's object skipped
+static inline ShadowRule shadow_rule_or_reference(const srt_shadow_rule* r) { return r ? shadow_rule(r) : ShadowRule{ std::nanf(""), std::nanf(""), 0u }; }
+
 // shadow: NULL launches k_query_path as ever; a rule launches the k_query_path_shadow build of the same choice
+// vis: NULL changes nothing; otherwise the k_query_path_masked build of the same choice, with or without a rule
 static int shade_paths_device_impl(srt_scene* s, uint32_t n, const float* d_rays, const float* d_t_range, const srt_params* p, const srt_path_desc* path,
-                                   const srt_shadow_rule* shadow, hipStream_t stream, float* d_rgb_linear, uint8_t* d_rgb8, const srt_path_out* seg, bool count_hits) {
+                                   const srt_shadow_rule* shadow, hipStream_t stream, float* d_rgb_linear, uint8_t* d_rgb8, const srt_path_out* seg, bool count_hits,
+                                   const srt_visibility* vis = nullptr) {
     SRT_TRY(check_shadow(shadow));
     SRT_TRY(check_paths(s, n, d_rays, p, path));
     if (!n || (!count_hits && !paths_wanted(d_rgb_linear, d_rgb8, seg))) return SRT_OK;
@@ -1805,7 +1857,13 @@ static int shade_paths_device_impl(srt_scene* s, uint32_t n, const float* d_rays
         &k_query_path_shadow<false, false, false>, &k_query_path_shadow<false, false, true>, &k_query_path_shadow<false, true, false>, &k_query_path_shadow<false, true, true>,
         &k_query_path_shadow<true, false, false>,  &k_query_path_shadow<true, false, true>,  &k_query_path_shadow<true, true, false>,  &k_query_path_shadow<true, true, true> };
     const int build = (count ? 4 : 0) | (smooth ? 2 : 0) | (s->rec->int_shin ? 1 : 0);
-    if (shadow)
+    static const decltype(&k_query_path_masked<false, false, false>) masked_builds[8] = {
+        &k_query_path_masked<false, false, false>, &k_query_path_masked<false, false, true>, &k_query_path_masked<false, true, false>, &k_query_path_masked<false, true, true>,
+        &k_query_path_masked<true, false, false>,  &k_query_path_masked<true, false, true>,  &k_query_path_masked<true, true, false>,  &k_query_path_masked<true, true, true> };
+    if (vis)
+        hipLaunchKernelGGL(masked_builds[build], q.grid, dim3(256), 0, q.stream, s->dev, n, d_rays, rays_wide(d_rays), query_shade(s, p), query_range(d_t_range), *path,
+                           d_rgb_linear, d_rgb8, seg ? *seg : srt_path_out{}, q.ctr, shadow_rule_or_reference(shadow), query_mask(s, vis));
+    else if (shadow)
         hipLaunchKernelGGL(shadow_builds[build], q.grid, dim3(256), 0, q.stream, s->dev, n, d_rays, rays_wide(d_rays), query_shade(s, p), query_range(d_t_range), *path,
                            d_rgb_linear, d_rgb8, seg ? *seg : srt_path_out{}, q.ctr, shadow_rule(shadow));
     else
@@ -1827,7 +1885,7 @@ static int check_render_paths(const srt_scene* s, const srt_params* p, const srt
     return SRT_OK;
 }
 static int render_paths_device_impl(srt_scene* s, const srt_params* p, const srt_path_desc* path, const srt_shadow_rule* shadow, hipStream_t stream, float* d_rgb_linear,
-                                    uint8_t* d_rgb8, const srt_path_out* seg, bool count_hits) {
+                                    uint8_t* d_rgb8, const srt_path_out* seg, bool count_hits, const srt_visibility* vis = nullptr) {
     SRT_TRY(check_shadow(shadow));
     SRT_TRY(check_render_paths(s, p, path));
     const uint32_t rows = srt_rows_owned(p), wl = srt_cols_owned(p);
@@ -1845,7 +1903,13 @@ static int render_paths_device_impl(srt_scene* s, const srt_params* p, const srt
     const int build = (count ? 4 : 0) | (smooth ? 2 : 0) | (s->rec->int_shin ? 1 : 0);
     const uint32_t m = (uint32_t)std::lround(std::sqrt((double)p->spp));      // (m x m == spp: check_frame)
     const dim3 grid((wl + 15) / 16, (rows + 15) / 16);
-    if (shadow)
+    static const decltype(&k_render_path_masked<false, false, false>) masked_builds[8] = {
+        &k_render_path_masked<false, false, false>, &k_render_path_masked<false, false, true>, &k_render_path_masked<false, true, false>, &k_render_path_masked<false, true, true>,
+        &k_render_path_masked<true, false, false>,  &k_render_path_masked<true, false, true>,  &k_render_path_masked<true, true, false>,  &k_render_path_masked<true, true, true> };
+    if (vis)
+        hipLaunchKernelGGL(masked_builds[build], grid, dim3(256), 0, q.stream, s->dev, dp, p->spp, m, query_shade(s, p), *path, d_rgb_linear, d_rgb8,
+                           seg ? *seg : srt_path_out{}, q.ctr, shadow_rule_or_reference(shadow), query_mask(s, vis));
+    else if (shadow)
         hipLaunchKernelGGL(shadow_builds[build], grid, dim3(256), 0, q.stream, s->dev, dp, p->spp, m, query_shade(s, p), *path, d_rgb_linear, d_rgb8,
                            seg ? *seg : srt_path_out{}, q.ctr, shadow_rule(shadow));
     else
@@ -1989,14 +2053,20 @@ static int query_stats(srt_scene* s, uint32_t n, uint32_t n_lights, srt_stats* s
     return SRT_OK;
 }
 
+// ray_mask (the masked host forms): n words that travel as t_in does -- through the pinned block into rq_tin, bit for bit (stage_rays only
+// copies them); neither call stages a t of its own.  masked: the call is srt_*_masked, whether or not it brings per-ray masks.
+static inline const float* mask_words(const uint32_t* ray_mask) { return reinterpret_cast<const float*>(ray_mask); }
+static inline RayMask staged_mask(srt_scene* s, const uint32_t* ray_mask) { return RayMask{ ray_mask ? reinterpret_cast<const uint32_t*>(s->rq_tin.p) : nullptr }; }
+
 static int trace_rays_impl(srt_scene* s, uint32_t n, const float* rays, const float* t_range, uint32_t flags, int32_t* hit_id, float* t, float* bary,
-                           srt_stats* stats) {
+                           srt_stats* stats, bool masked = false, const uint32_t* ray_mask = nullptr) {
     SRT_TRY(check_query(s, n, rays, flags));
     if (stats) std::memset(stats, 0, sizeof(*stats));
     if (!n) return SRT_OK;
     const auto o_hit = query_out(hit_id, s->rq_hit); const auto o_t = query_out(t, s->rq_t); const auto o_bary = query_out(bary, s->rq_bary);
-    SRT_TRY(query_round_trip(s, n, rays, t_range, nullptr, nullptr, [&](hipStream_t st) {
-        return trace_rays_device_impl(s, n, s->rq_rays, t_range ? s->rq_range.p : nullptr, flags, st, o_hit.wanted(), o_t.wanted(), o_bary.wanted(), true);
+    SRT_TRY(query_round_trip(s, n, rays, t_range, nullptr, mask_words(ray_mask), [&](hipStream_t st) {
+        const RayMask rm = staged_mask(s, ray_mask);
+        return trace_rays_device_impl(s, n, s->rq_rays, t_range ? s->rq_range.p : nullptr, flags, st, o_hit.wanted(), o_t.wanted(), o_bary.wanted(), true, masked ? &rm : nullptr);
     }, o_hit, o_t, o_bary));
     return stats ? query_stats(s, n, 0, stats) : SRT_OK;
 }
@@ -2015,11 +2085,13 @@ static int trace_rays_multi_impl(srt_scene* s, uint32_t n, const float* rays, co
     return stats ? query_stats(s, n, 0, stats) : SRT_OK;
 }
 
-static int occluded_impl(srt_scene* s, uint32_t n, const float* rays, const float* t_range, const int32_t* skip_obj, uint8_t* occluded) {
+static int occluded_impl(srt_scene* s, uint32_t n, const float* rays, const float* t_range, const int32_t* skip_obj, uint8_t* occluded, bool masked = false,
+                         const uint32_t* ray_mask = nullptr) {
     SRT_TRY(check_query(s, n, rays, 0));
     if (!n || !occluded) return SRT_OK;
-    return query_round_trip(s, n, rays, t_range, skip_obj, nullptr, [&](hipStream_t st) {
-        return occluded_device_impl(s, n, s->rq_rays, t_range ? s->rq_range.p : nullptr, skip_obj ? s->rq_skip.p : nullptr, st, s->rq_occ);
+    return query_round_trip(s, n, rays, t_range, skip_obj, mask_words(ray_mask), [&](hipStream_t st) {
+        const RayMask rm = staged_mask(s, ray_mask);
+        return occluded_device_impl(s, n, s->rq_rays, t_range ? s->rq_range.p : nullptr, skip_obj ? s->rq_skip.p : nullptr, st, s->rq_occ, masked ? &rm : nullptr);
     }, query_out(occluded, s->rq_occ));
 }
 
@@ -2038,7 +2110,8 @@ static int shade_rays_impl(srt_scene* s, uint32_t n, const float* rays, const fl
 
 // srt_shade_paths: the per-segment rows are depth units a ray; hit_rays counts the hits of all segments, hence the shadow rays
 static int shade_paths_impl(srt_scene* s, uint32_t n, const float* rays, const float* t_range, const srt_params* p, const srt_path_desc* path,
-                            const srt_shadow_rule* shadow, float* rgb_linear, uint8_t* rgb8, const srt_path_out* seg, srt_stats* stats) {
+                            const srt_shadow_rule* shadow, float* rgb_linear, uint8_t* rgb8, const srt_path_out* seg, srt_stats* stats,
+                            const srt_visibility* vis = nullptr) {
     SRT_TRY(check_shadow(shadow));
     SRT_TRY(check_paths(s, n, rays, p, path));
     if (stats) std::memset(stats, 0, sizeof(*stats));
@@ -2051,14 +2124,15 @@ static int shade_paths_impl(srt_scene* s, uint32_t n, const float* rays, const f
     SRT_TRY(query_round_trip_refl(s, n, rays, t_range, nullptr, nullptr, path->reflectance, path->reflectance ? s->dev.n_objects : 0u, [&](hipStream_t st) {
         const srt_path_desc dpath = { path->depth, path->bounce_t_min, path->reflectance ? s->rq_refl.p : nullptr };
         const srt_path_out dev = { o_hit.wanted(), o_t.wanted(), o_obj.wanted(), o_slin.wanted(), o_rays.wanted() };
-        return shade_paths_device_impl(s, n, s->rq_rays, t_range ? s->rq_range.p : nullptr, p, &dpath, shadow, st, o_lin.wanted(), o_rgb8.wanted(), &dev, stats != nullptr);
+        return shade_paths_device_impl(s, n, s->rq_rays, t_range ? s->rq_range.p : nullptr, p, &dpath, shadow, st, o_lin.wanted(), o_rgb8.wanted(), &dev, stats != nullptr,
+                                       vis);
     }, o_lin, o_rgb8, o_hit, o_t, o_obj, o_slin, o_rays));
     return stats ? query_stats(s, n, p->n_lights, stats) : SRT_OK;
 }
 
 // srt_render_paths: as shade_paths_impl, with n the call's local pixels and no rays to stage; primary_rays counts image pixels x spp
 static int render_paths_impl(srt_scene* s, const srt_params* p, const srt_path_desc* path, const srt_shadow_rule* shadow, float* rgb_linear, uint8_t* rgb8,
-                             const srt_path_out* seg, srt_stats* stats) {
+                             const srt_path_out* seg, srt_stats* stats, const srt_visibility* vis = nullptr) {
     SRT_TRY(check_shadow(shadow));
     SRT_TRY(check_render_paths(s, p, path));
     if (stats) std::memset(stats, 0, sizeof(*stats));
@@ -2084,7 +2158,7 @@ static int render_paths_impl(srt_scene* s, const srt_params* p, const srt_path_d
             up(dev.rays, h.rays, D * n * 24); up(o_lin.wanted(), rgb_linear, (size_t)n * 12); up(o_rgb8.wanted(), rgb8, (size_t)n * 3);
             HIP_TRY(e);
         }
-        return render_paths_device_impl(s, p, &dpath, shadow, st, o_lin.wanted(), o_rgb8.wanted(), &dev, stats != nullptr);
+        return render_paths_device_impl(s, p, &dpath, shadow, st, o_lin.wanted(), o_rgb8.wanted(), &dev, stats != nullptr, vis);
     }, o_lin, o_rgb8, o_hit, o_t, o_obj, o_slin, o_rays));
     if (!stats) return SRT_OK;
     SRT_TRY(query_stats(s, n, p->n_lights, stats));
@@ -2200,6 +2274,41 @@ int srt_render_paths_shadow_device(srt_scene* s, const srt_params* p, const srt_
 int srt_render_paths_shadow(srt_scene* s, const srt_params* p, const srt_path_desc* path, const srt_shadow_rule* shadow, float* rgb_linear, uint8_t* rgb8,
                             const srt_path_out* seg, srt_stats* stats) {
     return guarded([&] { return render_paths_impl(s, p, path, shadow, rgb_linear, rgb8, seg, stats); });
+}
+// Visibility masks: the closest-hit and occlusion calls with a mask per ray, the four path calls with a mask per ray kind (NULL vis: the
+// _shadow call above, with its kernels)
+int srt_trace_rays_masked_device(srt_scene* s, uint32_t n, const float* d_rays, const float* d_t_range, const uint32_t* d_ray_mask, uint32_t flags, void* stream,
+                                 int32_t* d_hit_id, float* d_t, float* d_bary) {
+    const RayMask rm = { d_ray_mask };
+    return guarded([&] { return trace_rays_device_impl(s, n, d_rays, d_t_range, flags, (hipStream_t)stream, d_hit_id, d_t, d_bary, false, &rm); });
+}
+int srt_trace_rays_masked(srt_scene* s, uint32_t n, const float* rays, const float* t_range, const uint32_t* ray_mask, uint32_t flags, int32_t* hit_id, float* t,
+                          float* bary, srt_stats* stats) {
+    return guarded([&] { return trace_rays_impl(s, n, rays, t_range, flags, hit_id, t, bary, stats, true, ray_mask); });
+}
+int srt_occluded_masked_device(srt_scene* s, uint32_t n, const float* d_rays, const float* d_t_range, const uint32_t* d_ray_mask, const int32_t* d_skip_obj, void* stream,
+                               uint8_t* d_occluded) {
+    const RayMask rm = { d_ray_mask };
+    return guarded([&] { return occluded_device_impl(s, n, d_rays, d_t_range, d_skip_obj, (hipStream_t)stream, d_occluded, &rm); });
+}
+int srt_occluded_masked(srt_scene* s, uint32_t n, const float* rays, const float* t_range, const uint32_t* ray_mask, const int32_t* skip_obj, uint8_t* occluded) {
+    return guarded([&] { return occluded_impl(s, n, rays, t_range, skip_obj, occluded, true, ray_mask); });
+}
+int srt_shade_paths_masked_device(srt_scene* s, uint32_t n, const float* d_rays, const float* d_t_range, const srt_params* p, const srt_path_desc* path,
+                                  const srt_shadow_rule* shadow, const srt_visibility* vis, void* stream, float* d_rgb_linear, uint8_t* d_rgb8, const srt_path_out* seg) {
+    return guarded([&] { return shade_paths_device_impl(s, n, d_rays, d_t_range, p, path, shadow, (hipStream_t)stream, d_rgb_linear, d_rgb8, seg, false, vis); });
+}
+int srt_shade_paths_masked(srt_scene* s, uint32_t n, const float* rays, const float* t_range, const srt_params* p, const srt_path_desc* path, const srt_shadow_rule* shadow,
+                           const srt_visibility* vis, float* rgb_linear, uint8_t* rgb8, const srt_path_out* seg, srt_stats* stats) {
+    return guarded([&] { return shade_paths_impl(s, n, rays, t_range, p, path, shadow, rgb_linear, rgb8, seg, stats, vis); });
+}
+int srt_render_paths_masked_device(srt_scene* s, const srt_params* p, const srt_path_desc* path, const srt_shadow_rule* shadow, const srt_visibility* vis, void* stream,
+                                   float* d_rgb_linear, uint8_t* d_rgb8, const srt_path_out* seg) {
+    return guarded([&] { return render_paths_device_impl(s, p, path, shadow, (hipStream_t)stream, d_rgb_linear, d_rgb8, seg, false, vis); });
+}
+int srt_render_paths_masked(srt_scene* s, const srt_params* p, const srt_path_desc* path, const srt_shadow_rule* shadow, const srt_visibility* vis, float* rgb_linear,
+                            uint8_t* rgb8, const srt_path_out* seg, srt_stats* stats) {
+    return guarded([&] { return render_paths_impl(s, p, path, shadow, rgb_linear, rgb8, seg, stats, vis); });
 }
 
 int srt_surface_rays_device(srt_scene* s, uint32_t n, const float* d_rays, const float* d_t_range, uint32_t flags, void* stream, int32_t* d_hit_id, float* d_t,

@@ -1012,17 +1012,33 @@ __global__ __launch_bounds__(256, MINW) void k_closest_hit_nq(DevScene s, DevPar
 // first hit.
 // RANGE (the occlusion query with a t interval, srt_query.h): a result counts only if it is in range, !(t < t_min) && !(t > t_max) --
 // closed, a NaN bound bounds nothing, a NaN t is in range; the walk visits the same nodes, and the lane leaves at its first hit in range.
-template <bool COUNT, bool FILTER, bool RANGE = false>
+// MASK (visibility masks, include/srt.h): object k takes part iff (obj_mask[k] & ray_m) != 0, a NULL obj_mask reading as all ones.  The
+// objects' ranges are contiguous and i only moves forward, so the lane keeps a cursor -- obj_cur, the object whose root comes next, and
+// obj_root, that root's index.  Whenever i arrives there the cursor moves on, and a hidden object is stepped over like `self`: no record of
+// it is read, nothing is tested or counted.  Each jump goes back to the loop's head, so a self range or a hidden object (or an object
+// without nodes) that follows is met in turn.
+template <bool COUNT, bool FILTER, bool RANGE = false, bool MASK = false>
 __device__ __forceinline__ bool any_hit_range(const DevScene& s, int2 self, V3 so, V3 sd,
-                                              unsigned long long& n_node, unsigned long long& n_tri, const float t_min = 0.0f, const float t_max = 0.0f) {
+                                              unsigned long long& n_node, unsigned long long& n_tri, const float t_min = 0.0f, const float t_max = 0.0f,
+                                              const uint32_t* __restrict__ obj_mask = nullptr, const uint32_t ray_m = 0u) {
     const float4* nodes4 = reinterpret_cast<const float4*>(s.nodes);
     const float4* tris4 = reinterpret_cast<const float4*>(s.tris);
     RayRcp rc;
     if (FILTER) rc = ray_rcp(sd);
     const int32_t n = (int32_t)s.n_nodes;
     int32_t i = 0;
+    int32_t obj_root = 0;
+    uint32_t obj_cur = 0;
     bool hit = false;
     while (i < n && !hit) {
+        if (MASK && i == obj_root && obj_cur < s.n_objects) {
+            const int2 r = s.obj_range[obj_cur];
+            const uint32_t om = obj_mask ? obj_mask[obj_cur] : 0xFFFFFFFFu;
+            obj_cur++;
+            obj_root = r.y;
+            if (!(om & ray_m)) i = r.y;
+            continue;
+        }
         if (i == self.x) { i = self.y; continue; }
         const float4 a = nodes4[2 * (size_t)i], b = nodes4[2 * (size_t)i + 1];
         const int32_t skip = __float_as_int(b.z), leaf = __float_as_int(b.w);

@@ -63,10 +63,31 @@ struct MergeClosest {
     __device__ __forceinline__ void offer(const uint32_t src, const uint32_t tri, const float t) const { atomicMin(&best[src], hit_key(t, tri)); }
 };
 
-template <bool COUNT, bool RANGE, typename Merge>
+// The visibility masks of a masked call (include/srt.h, "Visibility masks"), their own kernel argument: the scene's table (NULL = all
+// ones), the per-ray masks of the closest-hit and occlusion queries (NULL = all ones), and the three masks per ray KIND of the shaded calls.
+struct QueryMask { const uint32_t* obj; const uint32_t* ray; uint32_t primary, bounce, shadow; };
+// The object cursor of a masked walk: `root` is the index of the next object's root and `k` that object's number.  Called with the node
+// the lane is about to go to: while that node is a root, the cursor moves on, and a hidden object -- (obj_mask[k] & m) == 0 -- moves
+// `next` to the end of its range, which is the next root.  One 4-byte mask load and one 8-byte range load, independent of each other, per
+// object per ray; no node record of a hidden object is read.  An object without nodes is passed over either way.
+struct ObjCursor { int32_t root; uint32_t k; };
+__device__ __forceinline__ int32_t skip_hidden(const DevScene& s, const uint32_t* __restrict__ obj_mask, const uint32_t m, ObjCursor& c, int32_t next) {
+    while (next == c.root && c.k < s.n_objects) {
+        const int2 r = s.obj_range[c.k];
+        const uint32_t om = obj_mask ? obj_mask[c.k] : 0xFFFFFFFFu;
+        c.k++;
+        c.root = r.y;
+        if (!(om & m)) next = r.y;
+    }
+    return next;
+}
+
+// MASK: only the objects k with (obj_mask[k] & ray_m) != 0 are walked (skip_hidden); the builds without it never read the two arguments.
+template <bool COUNT, bool RANGE, typename Merge, bool MASK = false>
 __device__ __forceinline__ void query_walk(const DevScene& s, const bool live, const V3 o, const V3 d, const uint32_t lane, uint32_t* q,
                                            const Merge mg, float (*wray)[64], unsigned long long& n_node, unsigned long long& n_tri,
-                                           const float t_min = 0.0f, const float t_max = 0.0f) {
+                                           const float t_min = 0.0f, const float t_max = 0.0f, const uint32_t* __restrict__ obj_mask = nullptr,
+                                           const uint32_t ray_m = 0u) {
     mg.init(lane);
     wray[0][lane] = o.x; wray[1][lane] = o.y; wray[2][lane] = o.z;
     wray[3][lane] = d.x; wray[4][lane] = d.y; wray[5][lane] = d.z;
@@ -76,10 +97,13 @@ __device__ __forceinline__ void query_walk(const DevScene& s, const bool live, c
     const float4* tris4 = reinterpret_cast<const float4*>(s.tris);
     const int32_t n = (int32_t)s.n_nodes;
     int32_t i = live ? 0 : n;
+    ObjCursor cur = { 0, 0u };
+    if (MASK && i < n) i = skip_hidden(s, obj_mask, ray_m, cur, i);      // (the first object may be hidden: node 0 is not tested then)
     int32_t leaf_off = 0;
     uint32_t qn = 0;                                    // wave-uniform queue length
     float4 na = make_float4(0.0f, 0.0f, 0.0f, 0.0f), nb = na;      // node i (valid while i < n)
-    if (i < n) { na = nodes4[0]; nb = nodes4[1]; }      // (a lane without a ray, or a scene without nodes, reads no record)
+    if (MASK) { if (i < n) { na = nodes4[2 * (size_t)i]; nb = nodes4[2 * (size_t)i + 1]; } }
+    else if (i < n) { na = nodes4[0]; nb = nodes4[1]; } // (a lane without a ray, or a scene without nodes, reads no record)
     __builtin_amdgcn_wave_barrier();
     for (;;) {
         const bool active = i < n;
@@ -105,6 +129,7 @@ __device__ __forceinline__ void query_walk(const DevScene& s, const bool live, c
                     next = skip;
                 }
                 if (!stay) {
+                    if (MASK) next = skip_hidden(s, obj_mask, ray_m, cur, next);      // (a slice of a leaf stays: the cursor does not move)
                     if (next < n) { na = nodes4[2 * (size_t)next]; nb = nodes4[2 * (size_t)next + 1]; }
                     i = next;
                 }
@@ -163,6 +188,53 @@ __global__ __launch_bounds__(256) void k_query_closest(DevScene s, uint32_t n_ra
     if (live) load_ray(rays, ri, wide != 0, o, d);
     if (RANGE && live) load_range(tr, ri, t_min, t_max);
     query_walk<COUNT, RANGE>(s, live, o, d, lane, q_all[wave], MergeClosest{ best }, ray_all[wave], n_node, n_tri, t_min, t_max);
+    const float4* tris4 = reinterpret_cast<const float4*>(s.tris);
+    bool is_hit = false;
+    if (live) {
+        const unsigned long long key = best[lane];
+        int32_t id = -1;
+        float t = __builtin_inff();
+        V3 bc = mk(0.0f, 0.0f, 0.0f);
+        if (key != ~0ull) {
+            id = (int32_t)(uint32_t)key;
+            // the winner's t with its own bits (incl. the sign of a zero): same function, same inputs
+            V3 p1, e1, e2;
+            load_tri_edges(tris4, (size_t)id, p1, e1, e2);
+            t = ray_triangle(o, d, p1, e1, e2);
+            if (BARY) bc = barycentric(p1, e1, e2, o + d * t);       // calculateBarycentricCoords at the hit point
+        }
+        if (hit_id) hit_id[ri] = id;
+        if (t_out) t_out[ri] = t;
+        if (BARY) { bary[ri * 3] = bc.x; bary[ri * 3 + 1] = bc.y; bary[ri * 3 + 2] = bc.z; }
+        is_hit = id >= 0;
+    }
+    if (counters) count_hits(counters, is_hit, blockIdx.x);
+    if (COUNT) { wave_add(counters + 1, n_node); wave_add(counters + 2, n_tri); }
+}
+
+// srt_trace_rays_masked: k_query_closest's statements on the MASK walk.  Ray i is walked with qm.ray[i] (a NULL array: all ones) against
+// qm.obj; a mask that selects nothing leaves the lane without a node to test, so it is a miss.  The walk is the RANGE build; a NULL
+// interval runs as (NaN, NaN), which bounds nothing, as in k_query_multi.  counters: as k_query_closest's, of the walk as it runs --
+// a hidden object's root is neither tested nor counted.
+template <bool COUNT, bool BARY>
+__global__ __launch_bounds__(256) void k_query_closest_masked(DevScene s, uint32_t n_rays, const float* __restrict__ rays, uint32_t wide,
+                                                              int32_t* __restrict__ hit_id, float* __restrict__ t_out, float* __restrict__ bary,
+                                                              unsigned long long* __restrict__ counters, QueryRange tr, QueryMask qm) {
+    __shared__ uint32_t q_all[4][QCAP];
+    __shared__ unsigned long long best_all[256];
+    __shared__ float ray_all[4][8][64];
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    unsigned long long* best = best_all + wave * 64;
+    const size_t ri = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const bool live = ri < (size_t)n_rays;
+    unsigned long long n_node = 0, n_tri = 0;
+    V3 o = mk(0.0f, 0.0f, 0.0f), d = mk(0.0f, 0.0f, 1.0f);
+    float t_min = __builtin_nanf(""), t_max = __builtin_nanf("");
+    uint32_t m = 0xFFFFFFFFu;
+    if (live) load_ray(rays, ri, wide != 0, o, d);
+    if (tr.t && live) load_range(tr, ri, t_min, t_max);
+    if (qm.ray && live) m = qm.ray[ri];
+    query_walk<COUNT, true, MergeClosest, true>(s, live, o, d, lane, q_all[wave], MergeClosest{ best }, ray_all[wave], n_node, n_tri, t_min, t_max, qm.obj, m);
     const float4* tris4 = reinterpret_cast<const float4*>(s.tris);
     bool is_hit = false;
     if (live) {
@@ -313,6 +385,26 @@ __global__ __launch_bounds__(256) void k_query_any(DevScene s, uint32_t n_rays, 
     occluded[ri] = any_hit_range<false, true, RANGE>(s, self, o, d, n_node, n_tri, t_min, t_max) ? 1 : 0;
 }
 
+// srt_occluded_masked: k_query_any on the MASK walk; skip_obj still leaves its object out, on top of the masks.  One build: the RANGE
+// walk, a NULL interval running as (NaN, NaN).
+__global__ __launch_bounds__(256) void k_query_any_masked(DevScene s, uint32_t n_rays, const float* __restrict__ rays, uint32_t wide,
+                                                          const int32_t* __restrict__ skip_obj, uint8_t* __restrict__ occluded, QueryRange tr, QueryMask qm) {
+    const size_t ri = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (ri >= (size_t)n_rays) return;
+    V3 o, d;
+    load_ray(rays, ri, wide != 0, o, d);
+    int2 self = make_int2(-1, -1);
+    if (skip_obj) {
+        const int32_t k = skip_obj[ri];
+        if (k >= 0 && (uint32_t)k < s.n_objects) self = s.obj_range[k];
+    }
+    float t_min = __builtin_nanf(""), t_max = __builtin_nanf("");
+    if (tr.t) load_range(tr, ri, t_min, t_max);
+    const uint32_t m = qm.ray ? qm.ray[ri] : 0xFFFFFFFFu;
+    unsigned long long n_node = 0, n_tri = 0;
+    occluded[ri] = any_hit_range<false, true, true, true>(s, self, o, d, n_node, n_tri, t_min, t_max, qm.obj, m) ? 1 : 0;
+}
+
 // =================================================================================================
 // Shaded colour of caller-supplied rays (srt_shade_rays): per ray the one pixel of the oracle's 1 x 1 camera-mode frame -- closest hit,
 // softShadow:348-401 (shadow rays, Phong, the light-sample sum), tone map, quantiser, background rule -- in ONE launch: hit id and t stay
@@ -372,10 +464,12 @@ __device__ __forceinline__ WaveHits shade_hits_rank(const DevScene& s, const boo
 }
 // shade_hits_lights: the shadow rays of the wave's hits in chunks of 64 light samples, dealt to all 64 lanes, and each hit's light-sample sum.
 // SHADOW: a shadow ray blocks only in range of (sh_min, sh_max) -- any_hit_range's RANGE walk, the one k_query_any<true> runs.
-template <bool COUNT, bool INT_SHIN, bool SHADOW = false>
+// MASK: every shadow ray is walked with sh_mask against obj_mask -- any_hit_range's MASK walk, the one k_query_any_masked runs.
+template <bool COUNT, bool INT_SHIN, bool SHADOW = false, bool MASK = false>
 __device__ __forceinline__ V3 shade_hits_lights(const DevScene& s, const QueryShade& p, const uint32_t lane, const bool is_hit, const WaveHits wh, const V3 o, const V3 d,
                                                 const float t, const Surface& f, float (*wray)[64], unsigned long long* best, unsigned long long& n_node_s,
-                                                unsigned long long& n_tri_s, const float sh_min = 0.0f, const float sh_max = 0.0f) {
+                                                unsigned long long& n_tri_s, const float sh_min = 0.0f, const float sh_max = 0.0f,
+                                                const uint32_t* __restrict__ obj_mask = nullptr, const uint32_t sh_mask = 0u) {
     const uint32_t nh = wh.nh, rank = wh.rank;
     V3 sum = mk(0.0f, 0.0f, 0.0f);
     for (uint32_t l0 = 0; l0 < p.n_lights; l0 += 64u) {                                             // wave-uniform
@@ -389,7 +483,7 @@ __device__ __forceinline__ V3 shade_hits_lights(const DevScene& s, const QuerySh
             const int2 self = make_int2(__float_as_int(wray[3][r]), __float_as_int(wray[4][r]));
             const float* lp = p.lights + (size_t)(l0 + k) * 3;
             const V3 sd = mk(lp[0], lp[1], lp[2]) - so;
-            if (any_hit_range<COUNT, true, SHADOW>(s, self, so, sd, n_node_s, n_tri_s, sh_min, sh_max)) atomicOr(&best[r], 1ull << k);
+            if (any_hit_range<COUNT, true, SHADOW, MASK>(s, self, so, sd, n_node_s, n_tri_s, sh_min, sh_max, obj_mask, sh_mask)) atomicOr(&best[r], 1ull << k);
         }
         __builtin_amdgcn_wave_barrier();
         if (is_hit) {
@@ -650,12 +744,14 @@ __device__ __forceinline__ void store_rows_dealt(float* __restrict__ dst, const 
 // same for any lane of the wave (>= n: a lane without a ray) -- the transposed row stores need it.  seg: all NULL = no per-segment rows.
 // shard: where the wave's hits are counted.  Returns the mixed sum; hit0: whether segment 0 hit.
 // SHADOW: every segment's shadow rays run under `rule` (the builds without it never read it).
-template <bool COUNT, bool SMOOTH, bool INT_SHIN, bool SHADOW, typename RayOf>
+// MASK: segment 0 is walked with qm.primary, every later segment with qm.bounce, every shadow ray with qm.shadow, all against qm.obj
+// (the builds without it never read qm).
+template <bool COUNT, bool SMOOTH, bool INT_SHIN, bool SHADOW, bool MASK = false, typename RayOf>
 __device__ __forceinline__ V3 path_segments(const DevScene& s, const QueryShade& p, const srt_path_desc& path, const srt_path_out& seg, const size_t n, const size_t ri,
                                             const bool live, V3 o, V3 d, float t_min, float t_max, const uint32_t lane, uint32_t* q, unsigned long long* best,
                                             float (*wray)[64], const RayOf ray_of, unsigned long long* __restrict__ counters, const uint32_t shard, bool& hit0,
                                             unsigned long long& n_node, unsigned long long& n_tri, unsigned long long& n_node_s, unsigned long long& n_tri_s,
-                                            const ShadowRule rule) {
+                                            const ShadowRule rule, const QueryMask qm = QueryMask{}) {
     float* stage = &wray[0][0];
     V3 acc = mk(0.0f, 0.0f, 0.0f), pend = acc;          // the mix so far; the sum of the segment that waits for its weight
     float W = 1.0f, pend_k = 0.0f;                      // the weight of what follows; the waiting segment's reflectance
@@ -663,7 +759,7 @@ __device__ __forceinline__ V3 path_segments(const DevScene& s, const QueryShade&
     hit0 = false;
     uint32_t b = 0;
     for (; b < path.depth && __ballot(alive); b++) {                                                // wave-uniform
-        query_walk<COUNT, true>(s, alive, o, d, lane, q, MergeClosest{ best }, wray, n_node, n_tri, t_min, t_max);
+        query_walk<COUNT, true, MergeClosest, MASK>(s, alive, o, d, lane, q, MergeClosest{ best }, wray, n_node, n_tri, t_min, t_max, qm.obj, b == 0 ? qm.primary : qm.bounce);
         const unsigned long long key = alive ? best[lane] : ~0ull;
         const bool is_hit = key != ~0ull;
         const int32_t id = is_hit ? (int32_t)(uint32_t)key : -1;
@@ -677,7 +773,7 @@ __device__ __forceinline__ V3 path_segments(const DevScene& s, const QueryShade&
             if (seg.t) seg.t[row + ri] = t;
             if (seg.obj) seg.obj[row + ri] = obj;
         }
-        const V3 sum = shade_hits_lights<COUNT, INT_SHIN, SHADOW>(s, p, lane, is_hit, wh, o, d, t, f, wray, best, n_node_s, n_tri_s, rule.t_min, rule.t_max);
+        const V3 sum = shade_hits_lights<COUNT, INT_SHIN, SHADOW, MASK>(s, p, lane, is_hit, wh, o, d, t, f, wray, best, n_node_s, n_tri_s, rule.t_min, rule.t_max, qm.obj, qm.shadow);
         __builtin_amdgcn_wave_barrier();                // phase 2 is over: the rays' slots are the stage
         if (seg.rgb_linear) { const float v[3] = { sum.x, sum.y, sum.z }; store_rows_dealt<3>(seg.rgb_linear + row * 3, lane, n, v, stage, ray_of); }
         if (seg.rays) {
@@ -721,10 +817,11 @@ __device__ __forceinline__ V3 path_segments(const DevScene& s, const QueryShade&
 
 // The body of both k_query_path kernels: k_query_path is what a call without a shadow rule launches, argument for argument what it was;
 // k_query_path_shadow takes the rule as one more argument and is the SHADOW build of the same statements.
-template <bool COUNT, bool SMOOTH, bool INT_SHIN, bool SHADOW>
+template <bool COUNT, bool SMOOTH, bool INT_SHIN, bool SHADOW, bool MASK = false>
 __device__ __forceinline__ void query_path_rays(const DevScene& s, const uint32_t n_rays, const float* __restrict__ rays, const uint32_t wide, const QueryShade& p,
                                                 const QueryRange tr, const srt_path_desc& path, float* __restrict__ rgb_linear, uint8_t* __restrict__ rgb8,
-                                                const srt_path_out& seg, unsigned long long* __restrict__ counters, const ShadowRule rule) {
+                                                const srt_path_out& seg, unsigned long long* __restrict__ counters, const ShadowRule rule,
+                                                const QueryMask qm = QueryMask{}) {
     __shared__ uint32_t q_all[4][QCAP];
     __shared__ unsigned long long best_all[256];
     __shared__ float ray_all[4][8][64];
@@ -740,8 +837,8 @@ __device__ __forceinline__ void query_path_rays(const DevScene& s, const uint32_
     if (live) load_ray(rays, ri, wide != 0, o, d);
     if (tr.t && live) load_range(tr, ri, t_min, t_max);
     bool hit0;
-    const V3 acc = path_segments<COUNT, SMOOTH, INT_SHIN, SHADOW>(s, p, path, seg, n, ri, live, o, d, t_min, t_max, lane, q_all[wave], best_all + wave * 64, ray_all[wave],
-                                                                  ray_of, counters, blockIdx.x, hit0, n_node, n_tri, n_node_s, n_tri_s, rule);
+    const V3 acc = path_segments<COUNT, SMOOTH, INT_SHIN, SHADOW, MASK>(s, p, path, seg, n, ri, live, o, d, t_min, t_max, lane, q_all[wave], best_all + wave * 64,
+                                                                        ray_all[wave], ray_of, counters, blockIdx.x, hit0, n_node, n_tri, n_node_s, n_tri_s, rule, qm);
     if (live) store_pixel(rgb_linear, rgb8, ri, acc, hit0, p.reinhard, p.gamma, p.bg);
     if (COUNT) { wave_add(counters + 1, n_node); wave_add(counters + 2, n_tri); wave_add(counters + 3, n_node_s); wave_add(counters + 4, n_tri_s); }
 }
@@ -758,6 +855,15 @@ __global__ __launch_bounds__(256) void k_query_path_shadow(DevScene s, uint32_t 
     query_path_rays<COUNT, SMOOTH, INT_SHIN, true>(s, n_rays, rays, wide, p, tr, path, rgb_linear, rgb8, seg, counters, rule);
 }
 
+// srt_shade_paths_masked: the SHADOW build of the same statements on the MASK walks.  A call without a rule sends the reference's rule
+// as one: no bound -- (NaN, NaN) -- and the hit's object skipped.
+template <bool COUNT, bool SMOOTH, bool INT_SHIN>
+__global__ __launch_bounds__(256) void k_query_path_masked(DevScene s, uint32_t n_rays, const float* __restrict__ rays, uint32_t wide, QueryShade p, QueryRange tr,
+                                                           srt_path_desc path, float* __restrict__ rgb_linear, uint8_t* __restrict__ rgb8, srt_path_out seg,
+                                                           unsigned long long* __restrict__ counters, ShadowRule rule, QueryMask qm) {
+    query_path_rays<COUNT, SMOOTH, INT_SHIN, true, true>(s, n_rays, rays, wide, p, tr, path, rgb_linear, rgb8, seg, counters, rule, qm);
+}
+
 // =================================================================================================
 // Mirror paths in a frame (srt_render_paths): k_query_path's paths for the rays of a frame's own pixels.  The front end is the render
 // kernels': a wave owns one 8 x 8 pixel tile and a workgroup 16 x 16 (tile_pixel), the grid is 2-D over the call's local output, and a
@@ -771,10 +877,10 @@ __global__ __launch_bounds__(256) void k_query_path_shadow(DevScene s, uint32_t 
 // seg's rows are sub-sample 0's.  counters: as k_query_path's, over all sub-samples; the hit shard is the 2-D workgroup number.
 // =================================================================================================
 // The body of both k_render_path kernels, as query_path_rays is k_query_path's.  fp: the frame's geometry; sub_x / sub_y change per sub-sample.
-template <bool COUNT, bool SMOOTH, bool INT_SHIN, bool SHADOW>
+template <bool COUNT, bool SMOOTH, bool INT_SHIN, bool SHADOW, bool MASK = false>
 __device__ __forceinline__ void render_path_pixels(const DevScene& s, DevParams& fp, const uint32_t spp, const uint32_t spp_m, const QueryShade& p, const srt_path_desc& path,
                                                    float* __restrict__ rgb_linear, uint8_t* __restrict__ rgb8, const srt_path_out& seg,
-                                                   unsigned long long* __restrict__ counters, const ShadowRule rule) {
+                                                   unsigned long long* __restrict__ counters, const ShadowRule rule, const QueryMask qm = QueryMask{}) {
     __shared__ uint32_t q_all[4][QCAP];
     __shared__ unsigned long long best_all[256];
     __shared__ float ray_all[4][8][64];
@@ -797,9 +903,9 @@ __device__ __forceinline__ void render_path_pixels(const DevScene& s, DevParams&
         }
         const V3 d = live ? primary_dir(fp, px, y) : mk(0.0f, 0.0f, 1.0f);
         bool h;
-        const V3 acc = path_segments<COUNT, SMOOTH, INT_SHIN, SHADOW>(s, p, path, k == 0 ? seg : srt_path_out{}, n, ri, live, o, d, __builtin_nanf(""), __builtin_nanf(""), lane,
-                                                                      q_all[wave], best_all + wave * 64, ray_all[wave], ray_of, counters, shard, h, n_node, n_tri, n_node_s,
-                                                                      n_tri_s, rule);
+        const V3 acc = path_segments<COUNT, SMOOTH, INT_SHIN, SHADOW, MASK>(s, p, path, k == 0 ? seg : srt_path_out{}, n, ri, live, o, d, __builtin_nanf(""), __builtin_nanf(""),
+                                                                            lane, q_all[wave], best_all + wave * 64, ray_all[wave], ray_of, counters, shard, h, n_node, n_tri,
+                                                                            n_node_s, n_tri_s, rule, qm);
         if (k == 0) { total = acc; hit0 = h; }
         else total = mk(total.x + acc.x, total.y + acc.y, total.z + acc.z);
     }
@@ -818,4 +924,11 @@ __global__ __launch_bounds__(256) void k_render_path_shadow(DevScene s, DevParam
                                                             float* __restrict__ rgb_linear, uint8_t* __restrict__ rgb8, srt_path_out seg,
                                                             unsigned long long* __restrict__ counters, ShadowRule rule) {
     render_path_pixels<COUNT, SMOOTH, INT_SHIN, true>(s, fp, spp, spp_m, p, path, rgb_linear, rgb8, seg, counters, rule);
+}
+// srt_render_paths_masked: as k_query_path_masked is k_query_path_shadow's.
+template <bool COUNT, bool SMOOTH, bool INT_SHIN>
+__global__ __launch_bounds__(256) void k_render_path_masked(DevScene s, DevParams fp, uint32_t spp, uint32_t spp_m, QueryShade p, srt_path_desc path,
+                                                            float* __restrict__ rgb_linear, uint8_t* __restrict__ rgb8, srt_path_out seg,
+                                                            unsigned long long* __restrict__ counters, ShadowRule rule, QueryMask qm) {
+    render_path_pixels<COUNT, SMOOTH, INT_SHIN, true, true>(s, fp, spp, spp_m, p, path, rgb_linear, rgb8, seg, counters, rule, qm);
 }

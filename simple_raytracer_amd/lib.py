@@ -27,7 +27,8 @@ ABI_SYMBOLS = ("srt_params_default", "srt_light_staircase", "srt_rows_owned", "s
                "srt_trace_rays_multi_device", "srt_trace_rays_multi", "srt_shade_rays_range_device", "srt_shade_rays_range",
                "srt_surface_rays_device", "srt_surface_rays", "srt_surface_hits_device", "srt_surface_hits", "srt_shade_paths_device", "srt_shade_paths",
                "srt_render_paths_device", "srt_render_paths", "srt_shade_paths_shadow_device", "srt_shade_paths_shadow", "srt_render_paths_shadow_device",
-               "srt_render_paths_shadow")
+               "srt_render_paths_shadow", "srt_scene_set_object_masks", "srt_trace_rays_masked_device", "srt_trace_rays_masked", "srt_occluded_masked_device",
+               "srt_occluded_masked", "srt_shade_paths_masked_device", "srt_shade_paths_masked", "srt_render_paths_masked_device", "srt_render_paths_masked")
 MULTI_HIT_MAX = 16                # SRT_MULTI_HIT_MAX
 
 _f32p, _i32p, _u8p, _u32p = C.POINTER(C.c_float), C.POINTER(C.c_int32), C.POINTER(C.c_uint8), C.POINTER(C.c_uint32)
@@ -151,6 +152,20 @@ def load(path=None):
         L.srt_render_paths_shadow.argtypes = L.srt_render_paths.argtypes[:3] + [_rule] + L.srt_render_paths.argtypes[3:]
         for f in (L.srt_shade_paths_shadow_device, L.srt_shade_paths_shadow, L.srt_render_paths_shadow_device, L.srt_render_paths_shadow):
             f.restype = C.c_int
+        # visibility masks: the table, a ray_mask after t_range, one srt_visibility* after the shadow rule
+        L.srt_scene_set_object_masks.argtypes = [C.c_void_p, C.c_uint32, _u32p, C.c_void_p]
+        L.srt_trace_rays_masked_device.argtypes = L.srt_trace_rays_range_device.argtypes[:4] + [C.c_void_p] + L.srt_trace_rays_range_device.argtypes[4:]
+        L.srt_trace_rays_masked.argtypes = L.srt_trace_rays_range.argtypes[:4] + [_u32p] + L.srt_trace_rays_range.argtypes[4:]
+        L.srt_occluded_masked_device.argtypes = L.srt_occluded_range_device.argtypes[:4] + [C.c_void_p] + L.srt_occluded_range_device.argtypes[4:]
+        L.srt_occluded_masked.argtypes = L.srt_occluded_range.argtypes[:4] + [_u32p] + L.srt_occluded_range.argtypes[4:]
+        _vis = C.POINTER(abi.Visibility)
+        L.srt_shade_paths_masked_device.argtypes = L.srt_shade_paths_shadow_device.argtypes[:7] + [_vis] + L.srt_shade_paths_shadow_device.argtypes[7:]
+        L.srt_shade_paths_masked.argtypes = L.srt_shade_paths_shadow.argtypes[:7] + [_vis] + L.srt_shade_paths_shadow.argtypes[7:]
+        L.srt_render_paths_masked_device.argtypes = L.srt_render_paths_shadow_device.argtypes[:4] + [_vis] + L.srt_render_paths_shadow_device.argtypes[4:]
+        L.srt_render_paths_masked.argtypes = L.srt_render_paths_shadow.argtypes[:4] + [_vis] + L.srt_render_paths_shadow.argtypes[4:]
+        for f in (L.srt_scene_set_object_masks, L.srt_trace_rays_masked_device, L.srt_trace_rays_masked, L.srt_occluded_masked_device, L.srt_occluded_masked,
+                  L.srt_shade_paths_masked_device, L.srt_shade_paths_masked, L.srt_render_paths_masked_device, L.srt_render_paths_masked):
+            f.restype = C.c_int
         L.srt_strerror.argtypes = [C.c_int]
         L.srt_strerror.restype = C.c_char_p
         L.srt_last_hip_error.restype = C.c_int
@@ -245,6 +260,13 @@ class DeviceScene:
         _check(self.L.srt_scene_pose(self.h, m.shape[0], m.ctypes.data_as(_f32p), col.ctypes.data_as(_f32p) if col is not None else None,
                                      mat.ctypes.data_as(_f32p) if mat is not None else None, C.c_void_p(stream)), "srt_scene_pose")
 
+    def set_object_masks(self, masks, stream=0):
+        """srt_scene_set_object_masks: one uint32 per object (host array), or None = all ones.  Object k takes part in a masked walk with
+        mask m iff (masks[k] & m) != 0; every handle that shares this scene's records sees the table; asynchronous on `stream`."""
+        m = None if masks is None else np.ascontiguousarray(masks, np.uint32).reshape(-1)
+        n = self.flat.n_objects if m is None else m.shape[0]
+        _check(self.L.srt_scene_set_object_masks(self.h, n, m.ctypes.data_as(_u32p) if m is not None else None, C.c_void_p(stream)), "srt_scene_set_object_masks")
+
     def refit_prepare(self, tri_vertex=None, n_verts=0):
         """srt_scene_refit_prepare: the refit's schedule, once per tree; tri_vertex (n_tris x 3 vertex numbers, the scene's visit order,
         host array) and n_verts prepare the indexed form as well."""
@@ -324,10 +346,12 @@ class DeviceScene:
         _check(self.L.srt_render_device(self.h, C.byref(params), C.c_void_p(stream), C.c_void_p(hit_id), C.c_void_p(t),
                                         C.c_void_p(rgb_linear), C.c_void_p(rgb8)), "srt_render_device")
 
-    def trace_rays(self, rays, want=("hit_id", "t", "bary"), count=False, t_range=None):
+    def trace_rays(self, rays, want=("hit_id", "t", "bary"), count=False, t_range=None, ray_mask=None):
         """srt_trace_rays: the closest hit of every ray of `rays` (n x 6: origin xyz, direction xyz; host array).  Returns a dict of
         the arrays named in `want` (hit_id n, t n, bary n x 3) + 'stats'; count=True fills the node / triangle test counts.
-        t_range (n x 2: t_min, t_max per ray): srt_trace_rays_range, the closest hit inside each ray's closed interval."""
+        t_range (n x 2: t_min, t_max per ray): srt_trace_rays_range, the closest hit inside each ray's closed interval.
+        ray_mask (n uint32, or True = all ones): srt_trace_rays_masked, the closest hit among the objects whose mask (set_object_masks)
+        shares a bit with the ray's."""
         r = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
         n = r.shape[0]
         tr = _t_range(t_range, n)
@@ -338,7 +362,12 @@ class DeviceScene:
         st = abi.Stats()
         g = lambda k, ty: out[k].ctypes.data_as(ty) if k in out else ty()
         flags = abi.SRT_FLAG_COUNT_WORK if count else 0
-        if tr is None:
+        if ray_mask is not None:
+            rm = _ray_mask(ray_mask, n)
+            _check(self.L.srt_trace_rays_masked(self.h, n, r.ctypes.data_as(_f32p), tr.ctypes.data_as(_f32p) if tr is not None else None,
+                                                rm.ctypes.data_as(_u32p) if rm is not None else None, flags, g("hit_id", _i32p), g("t", _f32p), g("bary", _f32p),
+                                                C.byref(st)), "srt_trace_rays_masked")
+        elif tr is None:
             _check(self.L.srt_trace_rays(self.h, n, r.ctypes.data_as(_f32p), flags, g("hit_id", _i32p), g("t", _f32p), g("bary", _f32p), C.byref(st)), "srt_trace_rays")
         else:
             _check(self.L.srt_trace_rays_range(self.h, n, r.ctypes.data_as(_f32p), tr.ctypes.data_as(_f32p), flags, g("hit_id", _i32p), g("t", _f32p), g("bary", _f32p),
@@ -346,9 +375,10 @@ class DeviceScene:
         out["stats"] = st.as_dict()
         return out
 
-    def occluded(self, rays, skip_obj=None, t_range=None):
+    def occluded(self, rays, skip_obj=None, t_range=None, ray_mask=None):
         """srt_occluded: one uint8 per ray of `rays` (n x 6, host array), 1 = something other than object skip_obj[i] is hit at any t.
-        t_range (n x 2: t_min, t_max per ray): srt_occluded_range, ... is hit at a t inside the ray's closed interval."""
+        t_range (n x 2: t_min, t_max per ray): srt_occluded_range, ... is hit at a t inside the ray's closed interval.
+        ray_mask (n uint32, or True = all ones): srt_occluded_masked, ... among the objects whose mask shares a bit with the ray's."""
         r = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
         n = r.shape[0]
         tr = _t_range(t_range, n)
@@ -356,27 +386,38 @@ class DeviceScene:
         assert sk is None or sk.shape[0] == n, "skip_obj: one entry per ray"
         occ = np.empty(n, np.uint8)
         skp = sk.ctypes.data_as(_i32p) if sk is not None else None
-        if tr is None:
+        if ray_mask is not None:
+            rm = _ray_mask(ray_mask, n)
+            _check(self.L.srt_occluded_masked(self.h, n, r.ctypes.data_as(_f32p), tr.ctypes.data_as(_f32p) if tr is not None else None,
+                                              rm.ctypes.data_as(_u32p) if rm is not None else None, skp, occ.ctypes.data_as(_u8p)), "srt_occluded_masked")
+        elif tr is None:
             _check(self.L.srt_occluded(self.h, n, r.ctypes.data_as(_f32p), skp, occ.ctypes.data_as(_u8p)), "srt_occluded")
         else:
             _check(self.L.srt_occluded_range(self.h, n, r.ctypes.data_as(_f32p), tr.ctypes.data_as(_f32p), skp, occ.ctypes.data_as(_u8p)), "srt_occluded_range")
         return occ
 
-    def trace_rays_device(self, n, rays, stream=0, hit_id=0, t=0, bary=0, count=False, t_range=None):
+    def trace_rays_device(self, n, rays, stream=0, hit_id=0, t=0, bary=0, count=False, t_range=None, ray_mask=None):
         """srt_trace_rays_device: raw device pointers (ints, e.g. torch.Tensor.data_ptr()) in, asynchronous on `stream`.
-        t_range (a device pointer to n x 2 floats): srt_trace_rays_range_device."""
+        t_range (a device pointer to n x 2 floats): srt_trace_rays_range_device.
+        ray_mask (a device pointer to n uint32, or 0 = all ones): srt_trace_rays_masked_device."""
         flags = abi.SRT_FLAG_COUNT_WORK if count else 0
-        if t_range is None:
+        if ray_mask is not None:
+            _check(self.L.srt_trace_rays_masked_device(self.h, n, C.c_void_p(rays), C.c_void_p(t_range or 0), C.c_void_p(ray_mask or 0), flags, C.c_void_p(stream),
+                                                       C.c_void_p(hit_id), C.c_void_p(t), C.c_void_p(bary)), "srt_trace_rays_masked_device")
+        elif t_range is None:
             _check(self.L.srt_trace_rays_device(self.h, n, C.c_void_p(rays), flags, C.c_void_p(stream), C.c_void_p(hit_id), C.c_void_p(t), C.c_void_p(bary)),
                    "srt_trace_rays_device")
         else:
             _check(self.L.srt_trace_rays_range_device(self.h, n, C.c_void_p(rays), C.c_void_p(t_range), flags, C.c_void_p(stream), C.c_void_p(hit_id), C.c_void_p(t),
                                                       C.c_void_p(bary)), "srt_trace_rays_range_device")
 
-    def occluded_device(self, n, rays, occluded, skip_obj=0, stream=0, t_range=None):
+    def occluded_device(self, n, rays, occluded, skip_obj=0, stream=0, t_range=None, ray_mask=None):
         """srt_occluded_device: raw device pointers in, asynchronous on `stream`.  t_range (a device pointer to n x 2 floats):
-        srt_occluded_range_device."""
-        if t_range is None:
+        srt_occluded_range_device.  ray_mask (a device pointer to n uint32, or 0 = all ones): srt_occluded_masked_device."""
+        if ray_mask is not None:
+            _check(self.L.srt_occluded_masked_device(self.h, n, C.c_void_p(rays), C.c_void_p(t_range or 0), C.c_void_p(ray_mask or 0), C.c_void_p(skip_obj),
+                                                     C.c_void_p(stream), C.c_void_p(occluded)), "srt_occluded_masked_device")
+        elif t_range is None:
             _check(self.L.srt_occluded_device(self.h, n, C.c_void_p(rays), C.c_void_p(skip_obj), C.c_void_p(stream), C.c_void_p(occluded)), "srt_occluded_device")
         else:
             _check(self.L.srt_occluded_range_device(self.h, n, C.c_void_p(rays), C.c_void_p(t_range), C.c_void_p(skip_obj), C.c_void_p(stream), C.c_void_p(occluded)),
@@ -498,7 +539,8 @@ class DeviceScene:
                                               C.c_void_p(stream), C.byref(so)), "srt_surface_hits_device")
 
     def shade_paths(self, rays, params: abi.Params, depth, reflectance=None, bounce_t_min=1e-3, t_range=None,
-                    want=("rgb_linear", "rgb8", "seg_hit_id", "seg_t", "seg_obj", "seg_rgb_linear", "seg_rays"), count=False, smooth=False, shadow=None):
+                    want=("rgb_linear", "rgb8", "seg_hit_id", "seg_t", "seg_obj", "seg_rgb_linear", "seg_rays"), count=False, smooth=False, shadow=None,
+                    visibility=None):
         """srt_shade_paths: every ray of `rays` (n x 6, host array) followed through up to `depth` mirror bounces, each hit shaded as
         shade_rays(t_range=...) shades it, the segments mixed by `reflectance` (one float per object, or None = all 0).  A mirrored ray's
         interval is (bounce_t_min, +inf); t_range (n x 2) bounds segment 0.  Returns a dict of the arrays named in `want` -- rgb_linear
@@ -506,7 +548,9 @@ class DeviceScene:
         depth x n x 6 -- + 'stats'.  count / smooth add SRT_FLAG_COUNT_WORK / SRT_FLAG_SMOOTH_NORMALS for this call.
         shadow: None = the reference's shadow rule (unbounded, the hit object left out), or (t_min, t_max, self_shadow): a shadow
         ray blocks only inside the closed (t_min, t_max) in units of light - hit point, and with self_shadow the hit object's own tree
-        is walked too (srt_*_paths_shadow)."""
+        is walked too (srt_*_paths_shadow).
+        visibility: None, or (primary, bounce, shadow) -- the object masks segment 0, every later segment and every shadow ray are
+        walked with (srt_*_paths_masked; set_object_masks gives the objects their bits)."""
         r = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
         n = r.shape[0]
         tr = _t_range(t_range, n)
@@ -528,38 +572,46 @@ class DeviceScene:
         rule = abi.shadow_rule(shadow)
         head = (self.h, n, r.ctypes.data_as(_f32p), tr.ctypes.data_as(_f32p) if tr is not None else None, C.byref(params), C.byref(pd))
         tail = (g("rgb_linear", _f32p), g("rgb8", _u8p), C.byref(po), C.byref(st))
+        vis = abi.visibility(visibility)
         try:
-            rc = self.L.srt_shade_paths(*head, *tail) if rule is None else self.L.srt_shade_paths_shadow(*head, C.byref(rule), *tail)
+            if vis is not None:
+                rc = self.L.srt_shade_paths_masked(*head, C.byref(rule) if rule is not None else None, C.byref(vis), *tail)
+            else:
+                rc = self.L.srt_shade_paths(*head, *tail) if rule is None else self.L.srt_shade_paths_shadow(*head, C.byref(rule), *tail)
         finally:
             params.flags = flags
-        _check(rc, "srt_shade_paths" if rule is None else "srt_shade_paths_shadow")
+        _check(rc, "srt_shade_paths_masked" if vis is not None else "srt_shade_paths" if rule is None else "srt_shade_paths_shadow")
         out["stats"] = st.as_dict()
         return out
 
     def shade_paths_device(self, n, rays, params: abi.Params, depth, reflectance=0, bounce_t_min=1e-3, t_range=None, stream=0, rgb_linear=0, rgb8=0, seg_hit_id=0,
-                           seg_t=0, seg_obj=0, seg_rgb_linear=0, seg_rays=0, shadow=None):
+                           seg_t=0, seg_obj=0, seg_rgb_linear=0, seg_rays=0, shadow=None, visibility=None):
         """srt_shade_paths_device: raw device pointers (ints, e.g. torch.Tensor.data_ptr()) in, asynchronous on `stream`, one launch.  The
         light table of `params` is a host array; `reflectance` is a DEVICE pointer to n_objects floats (0 = all 0); t_range a device
         pointer to n x 2 floats, or None; the seg_* outputs are depth x n rows, segment-major.  The flags are those of `params`.
-        shadow: as in shade_paths."""
+        shadow, visibility: as in shade_paths."""
         pd = abi.PathDesc(depth, bounce_t_min, reflectance or None)
         po = abi.PathOut(seg_hit_id or None, seg_t or None, seg_obj or None, seg_rgb_linear or None, seg_rays or None)
         rule = abi.shadow_rule(shadow)
+        vis = abi.visibility(visibility)
         head = (self.h, n, C.c_void_p(rays), C.c_void_p(t_range or 0), C.byref(params), C.byref(pd))
         tail = (C.c_void_p(stream), C.c_void_p(rgb_linear), C.c_void_p(rgb8), C.byref(po))
-        if rule is None:
+        if vis is not None:
+            _check(self.L.srt_shade_paths_masked_device(*head, C.byref(rule) if rule is not None else None, C.byref(vis), *tail), "srt_shade_paths_masked_device")
+        elif rule is None:
             _check(self.L.srt_shade_paths_device(*head, *tail), "srt_shade_paths_device")
         else:
             _check(self.L.srt_shade_paths_shadow_device(*head, C.byref(rule), *tail), "srt_shade_paths_shadow_device")
 
     def render_paths(self, params: abi.Params, depth, reflectance=None, bounce_t_min=1e-3,
-                     want=("rgb_linear", "rgb8", "seg_hit_id", "seg_t", "seg_obj", "seg_rgb_linear", "seg_rays"), count=False, smooth=False, fill=None, shadow=None):
+                     want=("rgb_linear", "rgb8", "seg_hit_id", "seg_t", "seg_obj", "seg_rgb_linear", "seg_rays"), count=False, smooth=False, fill=None, shadow=None,
+                     visibility=None):
         """srt_render_paths: shade_paths for the rays of the frame's own pixels -- the local pixels of a call with `params` (its block or
         tile deal, camera matrix and spp included); no ray array is built.  Returns a dict of the arrays named in `want` -- rgb_linear
         [rows, cols, 3] (mixed), rgb8 [rows, cols, 3], and per segment seg_hit_id / seg_t / seg_obj [depth, rows, cols], seg_rgb_linear
         [depth, rows, cols, 3], seg_rays [depth, rows, cols, 6] -- + 'stats'.  count / smooth add SRT_FLAG_COUNT_WORK /
         SRT_FLAG_SMOOTH_NORMALS for this call.  fill: a value every array holds before the call (padding pixels of a tile deal keep it).
-        shadow: as in shade_paths."""
+        shadow, visibility: as in shade_paths."""
         rows, W = self.rows(params), self.cols(params)
         refl = None if reflectance is None else np.ascontiguousarray(reflectance, np.float32).reshape(-1)
         new = (lambda shape, ty: np.empty(shape, ty)) if fill is None else (lambda shape, ty: np.full(shape, fill, ty))
@@ -580,26 +632,33 @@ class DeviceScene:
         rule = abi.shadow_rule(shadow)
         head = (self.h, C.byref(params), C.byref(pd))
         tail = (g("rgb_linear", _f32p), g("rgb8", _u8p), C.byref(po), C.byref(st))
+        vis = abi.visibility(visibility)
         try:
-            rc = self.L.srt_render_paths(*head, *tail) if rule is None else self.L.srt_render_paths_shadow(*head, C.byref(rule), *tail)
+            if vis is not None:
+                rc = self.L.srt_render_paths_masked(*head, C.byref(rule) if rule is not None else None, C.byref(vis), *tail)
+            else:
+                rc = self.L.srt_render_paths(*head, *tail) if rule is None else self.L.srt_render_paths_shadow(*head, C.byref(rule), *tail)
         finally:
             params.flags = flags
-        _check(rc, "srt_render_paths" if rule is None else "srt_render_paths_shadow")
+        _check(rc, "srt_render_paths_masked" if vis is not None else "srt_render_paths" if rule is None else "srt_render_paths_shadow")
         out["stats"] = st.as_dict()
         return out
 
     def render_paths_device(self, params: abi.Params, depth, reflectance=0, bounce_t_min=1e-3, stream=0, rgb_linear=0, rgb8=0, seg_hit_id=0, seg_t=0, seg_obj=0,
-                            seg_rgb_linear=0, seg_rays=0, shadow=None):
+                            seg_rgb_linear=0, seg_rays=0, shadow=None, visibility=None):
         """srt_render_paths_device: raw device pointers (ints, e.g. torch.Tensor.data_ptr()) in, asynchronous on `stream`, one launch.  The
         light table of `params` is a host array; `reflectance` is a DEVICE pointer to n_objects floats (0 = all 0); the outputs are
         [rows, cols, ...] and the seg_* outputs [depth, rows, cols, ...] of the call's local pixels.  The flags are those of `params`.
-        shadow: as in shade_paths."""
+        shadow, visibility: as in shade_paths."""
         pd = abi.PathDesc(depth, bounce_t_min, reflectance or None)
         po = abi.PathOut(seg_hit_id or None, seg_t or None, seg_obj or None, seg_rgb_linear or None, seg_rays or None)
         rule = abi.shadow_rule(shadow)
+        vis = abi.visibility(visibility)
         head = (self.h, C.byref(params), C.byref(pd))
         tail = (C.c_void_p(stream), C.c_void_p(rgb_linear), C.c_void_p(rgb8), C.byref(po))
-        if rule is None:
+        if vis is not None:
+            _check(self.L.srt_render_paths_masked_device(*head, C.byref(rule) if rule is not None else None, C.byref(vis), *tail), "srt_render_paths_masked_device")
+        elif rule is None:
             _check(self.L.srt_render_paths_device(*head, *tail), "srt_render_paths_device")
         else:
             _check(self.L.srt_render_paths_shadow_device(*head, C.byref(rule), *tail), "srt_render_paths_shadow_device")
@@ -646,6 +705,15 @@ def _surface_arrays(n, want, out):
             out[name] = np.empty(n if k == 1 else (n, k), ty)
             setattr(so, name, out[name].ctypes.data)
     return so
+
+
+def _ray_mask(ray_mask, n):
+    """The masks of n rays as a host array (n uint32), or None for True (all ones: the masked call without per-ray masks)."""
+    if ray_mask is True:
+        return None
+    rm = np.ascontiguousarray(ray_mask, np.uint32).reshape(-1)
+    assert rm.shape[0] == n, "ray_mask: one uint32 per ray"
+    return rm
 
 
 def _t_range(t_range, n):

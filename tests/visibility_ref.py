@@ -1,0 +1,341 @@
+"""The yardstick of the visibility masks (include/srt.h, "Visibility masks": srt_scene_set_object_masks, srt_trace_rays_masked,
+srt_occluded_masked, srt_shade_paths_masked, srt_render_paths_masked).  It adds no arithmetic: a mask is a FILTER on the candidate set
+ray_range_ref holds for every ray, by the object that owns each candidate.
+
+  * visible(c, flat, ray_mask, obj_mask): the candidates of participating objects -- (obj_mask[tri_obj[tri]] & ray_mask[ray]) != 0.
+  * Closest hit and occlusion: ray_range_ref.closest / ray_range_ref.occluded on the filtered set, as they stand.
+  * Paths: the loop of shadow_rule_ref.trace restated with the filtered winners per segment KIND -- vis.primary for segment 0, vis.bounce
+    for every later one -- and the shadow rays' candidates filtered by vis.shadow.  The colour of a (hit, light) sample does not depend on
+    any mask: shade_range_ref.samples, asked once per (ray, hit) and kept.  What comes out is a list of shadow_rule_ref.Segment, so
+    shadow_rule_ref.shadow_bits and shade_paths_of compose it under any rule, and surface_ref / shade_path_ref.finish do the rest.
+  * Frames: shadow_rule_ref.render_paths' loop over the sub-samples on the paths above.
+  * sub_scene(flat, keep): the flat scene with only the kept objects -- the scene the definition's "oracle on the reduced scene" runs on --
+    and the map from its triangle ids back to the full scene's.
+
+tests/test_visibility_ref.py pins the filter to the oracle's own frames on sub_scene, and the paths to shadow_rule_ref at all-ones masks."""
+import numpy as np
+
+import ray_query_ref as rq
+import ray_range_ref as rr
+import render_paths_ref as rpr
+import shade_path_ref as sp
+import shade_range_ref as sr
+import shadow_rule_ref as sh
+import surface_ref as sf
+from simple_raytracer_amd import abi
+
+F32 = np.float32
+INF = np.float32(np.inf)
+ALL = 0xFFFFFFFF
+
+
+def masks_of(flat, obj_mask):
+    """The scene's table as n_objects uint32 (None: all ones)."""
+    return np.full(flat.n_objects, ALL, np.uint32) if obj_mask is None else np.ascontiguousarray(obj_mask, np.uint32).reshape(flat.n_objects)
+
+
+def visible(c, flat, ray_mask, obj_mask):
+    """The candidates of `c` whose object takes part in the walk of their ray.  ray_mask: None (all ones), one mask, or one per ray."""
+    rm = np.broadcast_to(np.asarray(ALL if ray_mask is None else ray_mask, np.uint32), (c.n_rays,))
+    keep = (masks_of(flat, obj_mask)[flat.tri_obj[c.tri]] & rm[c.ray]) != 0
+    return rr.Candidates(c.n_rays, c.ray[keep], c.tri[keep], c.t[keep])
+
+
+def closest(c, flat, ray_mask, obj_mask, t_range=None):
+    return rr.closest(visible(c, flat, ray_mask, obj_mask), t_range)
+
+
+def occluded(c, flat, ray_mask, obj_mask, t_range=None, skip_obj=None):
+    return rr.occluded(visible(c, flat, ray_mask, obj_mask), flat, t_range, skip_obj)
+
+
+# ---- the reduced scene --------------------------------------------------------------------------------------------------------------
+def node_object(flat):
+    """The object every node belongs to (-1: no root reaches it)."""
+    own = np.full(flat.n_nodes, -1, np.int64)
+    for k, root in enumerate(flat.obj_root):
+        stack = [int(root)]
+        while stack:
+            i = stack.pop()
+            own[i] = k
+            if flat.node_left[i] >= 0:
+                stack += [int(flat.node_left[i]), int(flat.node_right[i])]
+    return own
+
+
+def sub_scene(flat, keep):
+    """(the abi.FlatScene of the objects `keep` (ascending object numbers) alone, ids): nodes re-indexed in their old order, triangles
+    renumbered in their old order, the object tables cut; ids[new triangle id] = the id in `flat`.  Textures stay as they are."""
+    keep = np.asarray(sorted(int(k) for k in keep), np.int64)
+    obj_new = np.full(flat.n_objects, -1, np.int64); obj_new[keep] = np.arange(keep.size)
+    own = node_object(flat)
+    node_keep = (own >= 0) & (obj_new[np.maximum(own, 0)] >= 0)
+    node_new = np.cumsum(node_keep) - 1
+    tri_keep = obj_new[flat.tri_obj] >= 0
+    ids = np.flatnonzero(tri_keep)
+    removed_before = np.concatenate([[0], np.cumsum(~tri_keep)])      # removed triangles with an id below i
+    nk = np.flatnonzero(node_keep)
+    child = lambda a: np.where(a[nk] >= 0, node_new[np.maximum(a[nk], 0)], -1)
+    first = flat.node_first[nk].astype(np.int64)
+    first = first - removed_before[np.clip(first, 0, flat.n_tris)]
+    rows = lambda a, k: None if a is None else np.ascontiguousarray(a.reshape(flat.n_tris, k)[ids])
+    sub = abi.FlatScene(
+        node_min=flat.node_min.reshape(-1, 3)[nk], node_max=flat.node_max.reshape(-1, 3)[nk], node_left=child(flat.node_left), node_right=child(flat.node_right),
+        node_first=first, node_count=flat.node_count[nk], obj_root=node_new[flat.obj_root[keep].astype(np.int64)],
+        tri_points=rows(flat.tri_points, 12), tri_obj=obj_new[flat.tri_obj[ids]], obj_color=flat.obj_color.reshape(-1, 3)[keep],
+        obj_material=flat.obj_material.reshape(-1, 3)[keep], tri_tex=flat.tri_tex[ids], tri_texcoord=rows(flat.tri_texcoord, 6), tri_normals=rows(flat.tri_normals, 9),
+        tex_rgb=flat.tex_rgb, tex_off=flat.tex_off, tex_w=flat.tex_w, tex_h=flat.tex_h)
+    return sub, ids
+
+
+def map_back(hit, ids):
+    """Hit ids of a sub_scene in the full scene's numbering (-1 stays)."""
+    hit = np.asarray(hit, np.int64)
+    return np.where(hit >= 0, ids[np.maximum(hit, 0)] if ids.size else -1, -1).astype(np.int32)
+
+
+def hidden(flat, *objs):
+    """The table in which object k has bit k % 32, and the mask that sees every object but `objs`."""
+    bit = (np.uint32(1) << (np.arange(flat.n_objects, dtype=np.uint32) % np.uint32(32))).astype(np.uint32)
+    m = ALL
+    for k in objs:
+        m &= ~int(bit[k]) & ALL
+    return bit, m
+
+
+# ---- paths ----------------------------------------------------------------------------------------------------------------------------
+class Colours:
+    """shade_range_ref.samples' unshadowed colours, asked once per (ray, hit): no mask changes them."""
+
+    def __init__(self, oracle, flat, lights, flags=0, **literals):
+        self.oracle, self.flat, self.lights, self.flags, self.literals, self.memo = oracle, flat, lights, flags, literals, {}
+
+    def __call__(self, rays, hit, t):
+        sel = np.flatnonzero(hit >= 0)
+        keys = [(rays[i].tobytes(), int(hit[i])) for i in sel]
+        new = [j for j, k in enumerate(keys) if k not in self.memo]
+        if new:
+            idx = sel[new]
+            colour, _ = sr.samples(self.oracle, self.flat, rays[idx], hit[idx], t[idx], self.lights, self.flags, **self.literals)
+            for j, c in zip(new, colour):
+                self.memo[keys[j]] = c
+        nl = self.lights.shape[0]
+        return np.stack([self.memo[k] for k in keys]) if keys else np.zeros((0, nl, 3), np.float32)
+
+
+class CandidateMemo:
+    """ray_range_ref.candidates, asked once per ray: no mask changes a ray's candidate set, and the traces of one case under several
+    triples walk mostly the same rays (the slab tests of a big scene are what a trace costs)."""
+
+    def __init__(self, oracle, flat):
+        self.oracle, self.flat, self.memo = oracle, flat, {}
+
+    def __call__(self, rays):
+        rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
+        keys = [r.tobytes() for r in rays]
+        new = [i for i, k in enumerate(keys) if k not in self.memo]
+        if new:
+            first = {}
+            for i in new:
+                first.setdefault(keys[i], i)
+            idx = np.fromiter(first.values(), np.int64)
+            c = rr.candidates(self.oracle, self.flat, rays[idx])
+            cut = np.searchsorted(c.ray, np.arange(idx.size + 1))
+            for j, i in enumerate(idx):
+                self.memo[keys[i]] = (c.tri[cut[j]:cut[j + 1]], c.t[cut[j]:cut[j + 1]])
+        got = [self.memo[k] for k in keys]
+        cnt = np.fromiter((g[0].size for g in got), np.int64, len(got))
+        tri = np.concatenate([g[0] for g in got]) if got else np.empty(0, np.int64)
+        t = np.concatenate([g[1] for g in got]) if got else np.empty(0, np.float32)
+        return rr.Candidates(rays.shape[0], np.repeat(np.arange(len(got), dtype=np.int64), cnt), tri.astype(np.int64), t.astype(np.float32))
+
+
+def trace(oracle, flat, rays, lights, depth, vis, obj_mask=None, bounce_t_min=1e-3, t_range=None, flags=0, colours=None, cands=None):
+    """shadow_rule_ref.trace under masks: vis = (primary, bounce, shadow), obj_mask the scene's table (None: all ones).  Every Segment's
+    winners are the filtered closest hits of its kind, and its `cand` the shadow rays' candidates filtered by vis[2].
+    colours: a Colours (None: the colours stay zero -- the bits alone, for looking at a case's input conditions).
+    cands: a CandidateMemo to ask for candidate sets (None: ray_range_ref.candidates itself)."""
+    cands = cands if cands is not None else (lambda r: rr.candidates(oracle, flat, r))
+    rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
+    lights = np.ascontiguousarray(lights, np.float32).reshape(-1, 3)
+    n, nl = rays.shape[0], lights.shape[0]
+    smooth = bool(flags & abi.SRT_FLAG_SMOOTH_NORMALS)
+    cur = rays
+    tr = None if t_range is None else np.ascontiguousarray(t_range, np.float32).reshape(-1, 2)
+    going = np.ones(n, bool)
+    segs = []
+    for b in range(depth):
+        if not going.any():
+            break
+        hit, t = closest(cands(cur), flat, vis[0] if b == 0 else vis[1], obj_mask, tr)
+        assert not (hit[~going] >= 0).any(), "an ended path hit something"
+        sel = np.flatnonzero(hit >= 0)
+        skip = flat.tri_obj[hit[sel]].astype(np.int64)
+        srays = (np.concatenate([rq.shadow_rays(cur[sel], t[sel], lights[l]) for l in range(nl)]) if nl and sel.size else np.zeros((0, 6), np.float32))
+        cand = visible(cands(srays), flat, vis[2], obj_mask)
+        s = sf.surface(oracle, flat, cur, hit, t, smooth)
+        colour = colours(cur, hit, t) if colours is not None else np.zeros((sel.size, nl, 3), np.float32)
+        segs.append(sh.Segment(np.where(going[:, None], cur, F32(0.0)), going, hit, t, s["obj"], sel, colour, srays, cand, skip))
+        going = hit >= 0
+        cur = np.ascontiguousarray(s["bounce"])                                  # a miss row: the zero ray
+        tr = np.stack([np.where(going, F32(bounce_t_min), F32(1.0)), np.where(going, INF, F32(0.0))], axis=1).astype(np.float32)
+    return segs
+
+
+def shade_paths_of(oracle, flat, segs, depth, rule=None, reflectance=None, **literals):
+    """shadow_rule_ref.shade_paths_of on a masked trace.  The bits are handed over per segment, n_hit x n_lights also where a segment
+    walked rays and none of them hit (a mask can empty a whole segment; no unmasked case does)."""
+    nl = segs[0].colour.shape[1]
+    bits = [sh.shadow_bits(flat, s, rule) if s.sel.size else np.zeros((0, nl), bool) for s in segs]
+    return sh.shade_paths_of(oracle, flat, segs, depth, rule, reflectance, bits=bits, **literals)
+
+
+def shade_paths(oracle, flat, rays, lights, depth, vis, obj_mask=None, reflectance=None, bounce_t_min=1e-3, t_range=None, flags=0, rule=None, colours=None, **literals):
+    """srt_shade_paths_masked by the yardstick: shadow_rule_ref.shade_paths_of on the masked trace."""
+    colours = colours if colours is not None else Colours(oracle, flat, np.ascontiguousarray(lights, np.float32).reshape(-1, 3), flags, **literals)
+    segs = trace(oracle, flat, rays, lights, depth, vis, obj_mask, bounce_t_min, t_range, flags, colours)
+    return shade_paths_of(oracle, flat, segs, depth, rule, reflectance, **literals)
+
+
+def render_paths(oracle, flat, p, depth, vis, obj_mask=None, reflectance=None, bounce_t_min=1e-3, rule=None, fill=None):
+    """srt_render_paths_masked by the yardstick: shadow_rule_ref.render_paths with the paths above.  Lights, literals and flags are p's."""
+    own = rpr.owned(p)
+    sel = np.flatnonzero((own >= 0).reshape(-1))
+    lit = dict(shadow_div=float(p.shadow_div), reinhard=float(p.reinhard), gamma=float(p.gamma), background=tuple(int(c) for c in p.background[:3]))
+    flags = int(p.flags) & abi.SRT_FLAG_SMOOTH_NORMALS
+    spp = int(p.spp)
+    first, total = None, None
+    for k in range(spp):
+        rays, _ = rpr.frame_rays_owned(p, k)
+        o = shade_paths(oracle, flat, rays.reshape(-1, 6)[sel], rpr.lights_of(p), depth, vis, obj_mask, reflectance, bounce_t_min, flags=flags, rule=rule, **lit)
+        if k == 0:
+            first, total = o, o["rgb_linear"].copy()
+        else:
+            total = (total + o["rgb_linear"]).astype(np.float32)
+    if spp > 1:
+        with np.errstate(all="ignore"):
+            lin = (total / F32(spp)).astype(np.float32)
+        _, q = oracle.tonemap(lin, lit["reinhard"], lit["gamma"], pow="device")
+        q = q.copy()
+        q[np.all(q == 0, axis=1)] = np.asarray(lit["background"], np.int32)
+        first = dict(first, rgb_linear=lin, rgb8=q.astype(np.uint8))
+    out = {}
+    for key in sp.ALL_KEYS:
+        v = first[key]
+        lead = v.shape[:1] if key.startswith("seg_") else ()
+        tail = v.shape[len(lead) + 1:]
+        full = np.zeros(lead + (own.size,) + tail, v.dtype) if fill is None else np.full(lead + (own.size,) + tail, fill, v.dtype)
+        full[(slice(None),) * len(lead) + (sel,)] = v
+        out[key] = full.reshape(lead + own.shape + tail)
+    return out
+
+
+# ---- the cases of tests/test_gpu_visibility.py ------------------------------------------------------------------------------------------
+# The lamp cases of shadow_rule_ref (frames, lamps, depth 3, 3 lights).  In every case object k carries bit k of the table, and a triple
+# names the objects hidden from (segment 0, segments >= 1, shadow rays).  tests/test_visibility_ref.py asserts on the yardstick that each
+# triple changes segment 0 for some paths, a later segment for some paths whose segment 0 stays, and flips some shadow bits but not all.
+# (cube_ground: with the ground hidden from segment 0 every shadow bit left is one the ground casts from beyond the lamp, so a shadow mask
+# flips all of them or none; both of its triples hide the cube from segment 0 and differ in who casts shadows.)
+HIDE = {"cubes4_a40": (((1,), (2,), (3,)), ((0,), (0,), (2,))),
+        "cube_ground": (((1,), (0,), (1,)), ((1,), (0,), (0,))),
+        "ground_bunny": (((1,), (0,), (1,)), ((0,), (1,), (1,)))}
+DEPTH, N_LIGHTS, BOUNCE_T_MIN = sh.DEPTH, sh.N_LIGHTS, sh.BOUNCE_T_MIN
+# The per-ray masks of the closest-hit and occlusion cases, dealt round robin so that neighbours differ: nothing, everything, a bit no object
+# carries, and per entry of HIDDEN_FROM_RAYS all but that object.  Hiding object 1 sends rays to another object, turns rays into misses
+# and leaves rays unchanged in every case; hiding object 0 does so in cubes4_a40 only (in the other two it is the ground: nothing lies
+# behind it).
+NO_OBJECT_BIT = 1 << 31
+HIDDEN_FROM_RAYS = {"cubes4_a40": (1, 0), "cube_ground": (1,), "ground_bunny": (1,)}
+FIRST_HIDING_KIND = 3
+
+
+def case_table(flat):
+    return hidden(flat)[0]
+
+
+def case_vis(name, which):
+    """The srt_visibility triple `which` (0 or 1) of a lamp case, as three masks."""
+    flat = sh.lamp_case(name)[0]
+    return tuple(hidden(flat, *objs)[1] for objs in HIDE[name][which])
+
+
+def ray_masks(name, n):
+    """n per-ray masks over case_table: 3 + len(HIDDEN_FROM_RAYS[name]) kinds dealt round robin.  Returns (masks, kind)."""
+    flat = sh.lamp_case(name)[0]
+    kinds = np.array([0, ALL, NO_OBJECT_BIT] + [hidden(flat, k)[1] for k in HIDDEN_FROM_RAYS[name]], np.uint32)
+    kind = np.arange(n) % kinds.size
+    return kinds[kind], kind
+
+
+_colours, _traces, _refs, _cands = {}, {}, {}, {}
+
+
+def case_memo(oracle, name):
+    if ("memo", name) not in _cands:
+        _cands[("memo", name)] = CandidateMemo(oracle, sh.lamp_case(name)[0])
+    return _cands[("memo", name)]
+
+
+def case_colours(oracle, name):
+    if name not in _colours:
+        flat, _, lights, _ = sh.lamp_case(name)
+        _colours[name] = Colours(oracle, flat, lights)
+    return _colours[name]
+
+
+def case_candidates(oracle, name):
+    """The candidate sets of a lamp case's rays: computed once, shared, never changed."""
+    if name not in _cands:
+        flat, rays, _, _ = sh.lamp_case(name)
+        _cands[name] = case_memo(oracle, name)(rays)
+    return _cands[name]
+
+
+def case_trace(oracle, name, which, colours=True):
+    """The masked trace of a lamp case under triple `which`: computed once, shared, never changed."""
+    key = (name, which, colours)
+    if key not in _traces:
+        flat, rays, lights, _ = sh.lamp_case(name)
+        _traces[key] = trace(oracle, flat, rays, lights, DEPTH, case_vis(name, which), case_table(flat), BOUNCE_T_MIN,
+                             colours=case_colours(oracle, name) if colours else None, cands=case_memo(oracle, name))
+    return _traces[key]
+
+
+def case_reference(oracle, name, which, rule):
+    """The yardstick's rows of a lamp case under triple `which` and `rule`: computed once, shared, never changed."""
+    key = (name, which, None if rule is None else tuple(str(v) for v in rule))
+    if key not in _refs:
+        flat, _, _, refl = sh.lamp_case(name)
+        ref = shade_paths_of(oracle, flat, case_trace(oracle, name, which), DEPTH, rule, refl)
+        for v in ref.values():
+            v.setflags(write=False)
+        _refs[key] = ref
+    return _refs[key]
+
+
+def mask_conditions(flat, c, ray_mask, obj_mask):
+    """What a mask does to a batch, on the yardstick (counts): rays sent to another object, rays turned into misses, rays unchanged."""
+    h0, _ = rr.closest(c)
+    h1, _ = closest(c, flat, ray_mask, obj_mask)
+    return {"other": int(((h1 != h0) & (h1 >= 0)).sum()), "miss": int(((h0 >= 0) & (h1 < 0)).sum()), "same": int(((h1 == h0) & (h0 >= 0)).sum())}
+
+
+def vis_conditions(flat, plain, masked):
+    """What a triple does to a case (counts), `plain` the unmasked trace and `masked` the masked one: paths whose segment 0 changes; paths
+    whose segment 0 stays and a later segment changes; shadow bits flipped and shadowed bits left, over the (segment, ray) pairs that
+    walk the same ray to the same hit in both traces."""
+    n = plain[0].hit.shape[0]
+    rows = lambda segs, b: segs[b].hit if b < len(segs) else np.full(n, -1, np.int32)
+    seg0 = rows(plain, 0) != rows(masked, 0)
+    later = np.zeros(n, bool)
+    for b in range(1, max(len(plain), len(masked))):
+        later |= rows(plain, b) != rows(masked, b)
+    flipped = kept = 0
+    for a, b in zip(plain, masked):
+        both = (a.hit >= 0) & (a.hit == b.hit) & (sf.bits(a.rays) == sf.bits(b.rays)).all(axis=1)
+        ia, ib = np.flatnonzero(both[a.sel]), np.flatnonzero(both[b.sel])
+        if ia.size == 0:
+            continue
+        ba, bb = sh.shadow_bits(flat, a, None)[ia], sh.shadow_bits(flat, b, None)[ib]
+        flipped += int((ba != bb).sum()); kept += int((ba & bb).sum())
+    return {"segment0": int(seg0.sum()), "later": int((later & ~seg0).sum()), "flipped": flipped, "kept": kept}

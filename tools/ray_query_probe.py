@@ -27,7 +27,11 @@ shipped one, on a scene of its own.
 calls, srt_shade_paths_device on rays built beforehand, srt_render_paths_device, and at depth 1 srt_render_device.
 --shadow-rule: instead, what a shadow rule costs the two path calls on the same frame at depth 1 / 3 and 1 / 16 light samples, in one run:
 srt_shade_paths_device and srt_render_paths_device with no rule (the existing kernels) beside (1e-3, 1, 0) and (1e-3, 1, SELF).
-Usage: python tools/ray_query_probe.py [--reps N] [--trace] [--shade | --range | --shade-range | --multi | --surface | --paths | --shadow-rule [--rounds R]]     (--trace: few repetitions, for a run under rocprofv3 --kernel-trace --stats)"""
+--masked: instead, what the visibility masks cost on the same frame, in one run: srt_trace_rays_range_device with (0, +inf) -- the existing
+kernel, the yardstick -- beside srt_trace_rays_masked_device with every mask all ones (the same answers) and with the bunny hidden by the
+ray masks; and srt_shade_paths_shadow_device under (1e-3, 1, 0) beside srt_shade_paths_masked_device with all ones and with the bunny hidden
+from every ray kind, at depth 3 and 1 / 16 light samples.
+Usage: python tools/ray_query_probe.py [--reps N] [--trace] [--shade | --range | --shade-range | --multi | --surface | --paths | --shadow-rule | --masked [--rounds R]]     (--trace: few repetitions, for a run under rocprofv3 --kernel-trace --stats)"""
 import argparse, os, sys, time
 import numpy as np
 import torch                                   # first: torch initialises HIP before the library does
@@ -411,8 +415,59 @@ def shadow_rule_section(reps, rounds):
     ds.close()
 
 
+def masked_section(reps, rounds):
+    """What one more dependent load per object root costs the walks: the masked calls with all-ones masks beside the calls they extend, on
+    the rays of the 1080p frame, and the same calls with the bunny (object 1; object 0 is the ground) hidden."""
+    dev = torch.device("cuda", 0); torch.zeros(1, device=dev)
+    g = gu.GoldenScene("ground_bunny")
+    ds = lib.DeviceScene(g.flat)
+    side = torch.cuda.Stream(device=dev)
+    cur = side.cuda_stream
+    n = W * H
+    t_min = 1e-3
+    nO = g.flat.n_objects
+    bunny = 1
+    ds.set_object_masks((np.uint32(1) << np.arange(nO, dtype=np.uint32)).astype(np.uint32))      # object k carries bit k
+    ds.trace_rays(frame_rays()[:1])                                                                # (a host call on the table's stream: it has arrived)
+    ALL, NO_BUNNY = 0xFFFFFFFF, 0xFFFFFFFF & ~(1 << bunny)
+    d_rays = torch.from_numpy(frame_rays()).to(dev)
+    d_open = torch.from_numpy(np.tile(np.float32([0.0, np.inf]), (n, 1))).to(dev)
+    d_all = torch.from_numpy(np.full(n, ALL, np.uint32).view(np.int32)).to(dev)
+    d_hide = torch.from_numpy(np.full(n, NO_BUNNY, np.uint32).view(np.int32)).to(dev)
+    tri_obj = torch.from_numpy(g.flat.tri_obj.astype(np.int64)).to(dev)
+    hit = {k: torch.empty(n, dtype=torch.int32, device=dev) for k in ("range", "ones", "hidden")}
+    t = {k: torch.empty(n, dtype=torch.float32, device=dev) for k in hit}
+    print(f"visibility masks, K3 ground_bunny {W}x{H}: {n} rays, {nO} objects; {rounds} rounds of {reps} calls, forms alternating; ms a call; min / max: the spread of the rounds")
+    print(f"{'call':34s} {'form':34s} {'median':>8s} {'min':>8s} {'max':>8s} {'/ first':>7s}")
+    call = lambda key, m: (lambda: ds.trace_rays_device(n, d_rays.data_ptr(), stream=cur, hit_id=hit[key].data_ptr(), t=t[key].data_ptr(), t_range=d_open.data_ptr(), ray_mask=m))
+    forms = {"trace_rays_range (yardstick)": call("range", None), "trace_rays_masked, all ones": call("ones", d_all.data_ptr()),
+             "trace_rays_masked, NULL ray_mask": call("ones", 0), "trace_rays_masked, bunny hidden": call("hidden", d_hide.data_ptr())}
+    report("closest hit, row-major", rounds_of(forms, reps, rounds, side))
+    side.synchronize()
+    assert torch.equal(hit["range"], hit["ones"]) and torch.equal(t["range"].view(torch.int32), t["ones"].view(torch.int32)), "all ones is not the range call"
+    on_bunny = lambda h: int((tri_obj[h.clamp(min=0).long()][h >= 0] == bunny).sum().item())
+    assert on_bunny(hit["range"]) > 0 and on_bunny(hit["hidden"]) == 0
+    print(f"{'':34s} all ones gives the range call's bits; hits {int((hit['range'] >= 0).sum().item())}, of the bunny {on_bunny(hit['range'])}; with it hidden {int((hit['hidden'] >= 0).sum().item())}")
+    refl = torch.tensor([0.6, 0.25], dtype=torch.float32, device=dev)
+    rule = (1e-3, 1.0, False)
+    for L in (1, 16):
+        pq = abi.make_params(1, 1, abi.light_staircase(g.light, L))
+        lin = {k: torch.empty((n, 3), dtype=torch.float32, device=dev) for k in ("shadow", "ones", "hidden")}
+        paths = lambda key, vis: (lambda: ds.shade_paths_device(n, d_rays.data_ptr(), pq, 3, reflectance=refl.data_ptr(), bounce_t_min=t_min, stream=cur,
+                                                                rgb_linear=lin[key].data_ptr(), shadow=rule, visibility=vis))
+        forms = {"shade_paths_shadow (yardstick)": paths("shadow", None), "shade_paths_masked, all ones": paths("ones", (ALL, ALL, ALL)),
+                 "shade_paths_masked, bunny hidden": paths("hidden", (NO_BUNNY, NO_BUNNY, NO_BUNNY))}
+        report(f"paths, depth 3, {L} samples", rounds_of(forms, reps, rounds, side))
+        side.synchronize()
+        assert torch.equal(lin["shadow"].view(torch.int32), lin["ones"].view(torch.int32)), "all ones is not the _shadow call"
+        diff = int((lin["hidden"].view(torch.int32) != lin["shadow"].view(torch.int32)).any(dim=1).sum().item())
+        print(f"{'':34s} all ones gives the _shadow call's bits; pixels the hidden bunny changes: {diff}")
+    ds.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--masked", action="store_true")
     ap.add_argument("--shadow-rule", action="store_true", dest="shadow_rule")
     ap.add_argument("--paths", action="store_true")
     ap.add_argument("--reps", type=int, default=20)
@@ -425,6 +480,8 @@ def main():
     ap.add_argument("--rounds", type=int, default=7)
     a = ap.parse_args()
     reps = 3 if a.trace else a.reps
+    if a.masked:
+        return masked_section(reps, 2 if a.trace else a.rounds)
     if a.shadow_rule:
         return shadow_rule_section(reps, 2 if a.trace else a.rounds)
     if a.paths:
