@@ -780,6 +780,56 @@ int srt_render_paths_masked_device(srt_scene* s, const srt_params* p, const srt_
 int srt_render_paths_masked(srt_scene* s, const srt_params* p, const srt_path_desc* path, const srt_shadow_rule* shadow,
                             const srt_visibility* vis, float* rgb_linear, uint8_t* rgb8, const srt_path_out* seg, srt_stats* stats);
 
+/* Refracting paths: glass objects in srt_shade_paths and srt_render_paths.  Until here the only thing a ray does at a surface is bounce
+ * off it; the calls below take one more per-object table, and a hit on a TRANSMITTING object sends the next segment THROUGH the surface,
+ * bent by Snell's law.  Unless said here everything is as for srt_shade_paths_masked / srt_render_paths_masked: the rule, vis, seg, staging
+ * (ior goes through the pinned block exactly as reflectance does), the one-light-table-per-handle rule, ordering on `stream`,
+ * srt_scene_share, ONE kernel launch, hipGraph capture of the _device forms without SRT_FLAG_COUNT_WORK, NULL outputs, n == 0, the frame
+ * fields, spp, the tile deals, *stats.
+ * THE TABLE.  refr->ior: n_objects floats -- a device pointer in the _device forms, a host pointer in the host forms.  Object k transmits
+ * iff ior[k] > 0.0f; with 0, a negative value or NaN it mirrors, as ever.  refr->flags must be 0.
+ * THE RAY of segment b + 1 when segment b hit a transmitting object.  d: the direction of segment b; N: the normal shading uses for that
+ * hit (the smooth one under SRT_FLAG_SMOOTH_NORMALS); n = ior[obj_b].  f32 without contraction, dot3 = (x + y) + z, correctly rounded
+ * square root and divide:
+ *   L   = sqrtf(dot3(d, d));   inv = 1.0f / L;   I_i = d_i * inv            (glm::normalize's operations)
+ *   c   = dot3(N, I)                                                        (N's components on the left)
+ *   entering = c < 0.0f                                                     (N points OUT of the solid: the contract)
+ *   Nf  = entering ? N : -N;   dv = entering ? c : -c;   eta = entering ? 1.0f / n : n
+ *   k   = 1.0f - (eta * eta) * (1.0f - dv * dv)                             (glm::refract's association)
+ *   k < 0.0f  (total internal reflection):   r = the mirrored direction, exactly srt_surface_out.bounce's (d not normalised)
+ *   otherwise (k >= 0 or NaN):               s = eta * dv + sqrtf(k);   u_i = eta * I_i - s * Nf_i;   r_i = u_i * L
+ *   The origin is o + d * t, not moved, and the interval (bounce_t_min, +inf), as for a mirrored ray.  r is scaled back by L, so t of the
+ *   next segment stays in the units of the caller's direction and bounce_t_min means the same on every segment, whichever way the ray went.
+ *   The closest-hit walk does not skip the hit's own object: a ray that enters a solid finds its far side.
+ * THE MIX is unchanged: reflectance[obj] is the weight of what the NEXT segment brings, whether that segment was reflected or transmitted
+ * (a clear glass has a reflectance near 1: most of what one sees on it comes from behind it).
+ * SHADING AND SHADOWS are unchanged: every hit is shaded exactly as before, a hit on a back face from the inside included, and a glass
+ * object shadows like any other -- unless it has no bit of vis->shadow.  Under SRT_SHADOW_SELF a point inside a solid is shadowed by it.
+ * ORIENTATION.  `entering` trusts the normals: a mesh whose normals point inward refracts inside out (it bends rays as a bubble of air in
+ * glass would).  Values are not validated: a zero direction, an ior of +inf and the like give what the arithmetic gives; the call stays
+ * memory-safe.
+ * IDENTITIES, in every output and all four counters: refr == NULL or refr->ior == NULL: the call IS the _masked call and launches its
+ * kernels; a table with no entry > 0 gives the _masked call's bits; depth 1 is unchanged by any table.
+ * ERRORS: refr->flags != 0: SRT_ERR_ARG before anything is touched; every error of the _masked call keeps its code.
+ * NOT HERE: a Fresnel split into two rays, absorption along the way, srt_surface_out reporting a refracted ray. */
+typedef struct srt_refraction {
+    const float* ior;     /* n_objects floats; object k TRANSMITS iff ior[k] > 0.0f (0, negative, NaN: it mirrors) */
+    uint32_t     flags;   /* 0; any other value: SRT_ERR_ARG */
+} srt_refraction;
+int srt_shade_paths_refract_device(srt_scene* s, uint32_t n, const float* d_rays, const float* d_t_range /* n x 2 or NULL */,
+                                   const srt_params* p, const srt_path_desc* path, const srt_shadow_rule* shadow /* or NULL */,
+                                   const srt_visibility* vis /* or NULL */, const srt_refraction* refr /* or NULL */, void* stream,
+                                   float* d_rgb_linear /* n x 3, mixed */, uint8_t* d_rgb8 /* n x 3 */, const srt_path_out* seg);
+int srt_shade_paths_refract(srt_scene* s, uint32_t n, const float* rays, const float* t_range, const srt_params* p,
+                            const srt_path_desc* path, const srt_shadow_rule* shadow, const srt_visibility* vis, const srt_refraction* refr,
+                            float* rgb_linear, uint8_t* rgb8, const srt_path_out* seg, srt_stats* stats);
+int srt_render_paths_refract_device(srt_scene* s, const srt_params* p, const srt_path_desc* path, const srt_shadow_rule* shadow /* or NULL */,
+                                    const srt_visibility* vis /* or NULL */, const srt_refraction* refr /* or NULL */, void* stream,
+                                    float* d_rgb_linear /* n x 3, mixed */, uint8_t* d_rgb8 /* n x 3 */, const srt_path_out* seg);
+int srt_render_paths_refract(srt_scene* s, const srt_params* p, const srt_path_desc* path, const srt_shadow_rule* shadow,
+                             const srt_visibility* vis, const srt_refraction* refr, float* rgb_linear, uint8_t* rgb8, const srt_path_out* seg,
+                             srt_stats* stats);
+
 /* Device-resident size of the scene records and the per-record algorithmic byte sizes used by
  * the bytes model: 32 B per node test, 36 B per triangle test. */
 uint64_t srt_scene_device_bytes(const srt_scene* s);

@@ -130,6 +130,12 @@ def visibility(vis):
     return Visibility(int(primary) & 0xFFFFFFFF, int(bounce) & 0xFFFFFFFF, int(shadow) & 0xFFFFFFFF)
 
 
+class Refraction(C.Structure):
+    """srt_refraction: the per-object table of the refracting path calls.  ior: n_objects floats (a host array's pointer in the host forms,
+    a device pointer in the _device forms); object k transmits iff ior[k] > 0, else it mirrors.  flags: 0."""
+    _fields_ = [("ior", C.c_void_p), ("flags", C.c_uint32)]
+
+
 # the fields of srt_path_out: name -> (dtype, floats or ints per ray and segment)
 PATH_FIELDS = {"hit_id": (np.int32, 1), "t": (np.float32, 1), "obj": (np.int32, 1), "rgb_linear": (np.float32, 3), "rays": (np.float32, 6)}
 

@@ -171,7 +171,7 @@ struct srt_scene {
     DevArray<int32_t> rq_sobj; DevArray<float, 3> rq_spoint, rq_snormal, rq_scolor, rq_smat; DevArray<float, 6> rq_sbounce; DevArray<float> rq_tin;
     // srt_shade_paths: the reflectance table of a host call (capacity counts objects) and the per-segment sums (capacity counts depth x n rows);
     // the other per-segment rows go through rq_hit / rq_t / rq_sobj / rq_sbounce, depth units a ray
-    DevArray<float> rq_refl; DevArray<float, 3> rq_plin;
+    DevArray<float> rq_refl; DevArray<float> rq_ior; DevArray<float, 3> rq_plin;
     DevArray<float, 3> d_qlights; Pinned<float, 3> h_qlights; uint32_t qlights_valid = 0;
     Event qlights_sent; hipStream_t qlights_stream = nullptr; bool qlights_settled = true;
     int n_cu = 256;
@@ -1839,11 +1839,19 @@ static inline ShadowRule shadow_rule(const srt_shadow_rule* r) { return ShadowRu
 // The rule a masked call without one runs under: the reference's, stated as a rule -- no bound, the hit's object skipped
 static inline ShadowRule shadow_rule_or_reference(const srt_shadow_rule* r) { return r ? shadow_rule(r) : ShadowRule{ std::nanf(""), std::nanf(""), 0u }; }
 
+// The refraction table of the srt_*_paths_refract calls: NULL, or flags 0; without a table (NULL, or ior NULL) the call is the _masked call
+static inline int check_refraction(const srt_refraction* r) { return (r && r->flags) ? SRT_ERR_ARG : SRT_OK; }
+static inline const float* refraction_table(const srt_refraction* r) { return r ? r->ior : nullptr; }
+// The masks a refracting call without an srt_visibility runs under: every ray kind sees every object, and the scene's table is not read
+static inline QueryMask query_mask_or_all(const srt_scene* s, const srt_visibility* v) { return v ? query_mask(s, v) : QueryMask{ nullptr, nullptr, ~0u, ~0u, ~0u }; }
+
 // shadow: NULL launches k_query_path as ever; a rule launches the k_query_path_shadow build of the same choice
 // vis: NULL changes nothing; otherwise the k_query_path_masked build of the same choice, with or without a rule
+// refr: without a table nothing changes; otherwise the k_query_path_refract build of the same choice, with or without a rule or masks
 static int shade_paths_device_impl(srt_scene* s, uint32_t n, const float* d_rays, const float* d_t_range, const srt_params* p, const srt_path_desc* path,
                                    const srt_shadow_rule* shadow, hipStream_t stream, float* d_rgb_linear, uint8_t* d_rgb8, const srt_path_out* seg, bool count_hits,
-                                   const srt_visibility* vis = nullptr) {
+                                   const srt_visibility* vis = nullptr, const srt_refraction* refr = nullptr) {
+    SRT_TRY(check_refraction(refr));
     SRT_TRY(check_shadow(shadow));
     SRT_TRY(check_paths(s, n, d_rays, p, path));
     if (!n || (!count_hits && !paths_wanted(d_rgb_linear, d_rgb8, seg))) return SRT_OK;
@@ -1860,7 +1868,13 @@ static int shade_paths_device_impl(srt_scene* s, uint32_t n, const float* d_rays
     static const decltype(&k_query_path_masked<false, false, false>) masked_builds[8] = {
         &k_query_path_masked<false, false, false>, &k_query_path_masked<false, false, true>, &k_query_path_masked<false, true, false>, &k_query_path_masked<false, true, true>,
         &k_query_path_masked<true, false, false>,  &k_query_path_masked<true, false, true>,  &k_query_path_masked<true, true, false>,  &k_query_path_masked<true, true, true> };
-    if (vis)
+    static const decltype(&k_query_path_refract<false, false, false>) refract_builds[8] = {
+        &k_query_path_refract<false, false, false>, &k_query_path_refract<false, false, true>, &k_query_path_refract<false, true, false>, &k_query_path_refract<false, true, true>,
+        &k_query_path_refract<true, false, false>,  &k_query_path_refract<true, false, true>,  &k_query_path_refract<true, true, false>,  &k_query_path_refract<true, true, true> };
+    if (const float* d_ior = refraction_table(refr))
+        hipLaunchKernelGGL(refract_builds[build], q.grid, dim3(256), 0, q.stream, s->dev, n, d_rays, rays_wide(d_rays), query_shade(s, p), query_range(d_t_range), *path,
+                           d_rgb_linear, d_rgb8, seg ? *seg : srt_path_out{}, q.ctr, shadow_rule_or_reference(shadow), query_mask_or_all(s, vis), d_ior);
+    else if (vis)
         hipLaunchKernelGGL(masked_builds[build], q.grid, dim3(256), 0, q.stream, s->dev, n, d_rays, rays_wide(d_rays), query_shade(s, p), query_range(d_t_range), *path,
                            d_rgb_linear, d_rgb8, seg ? *seg : srt_path_out{}, q.ctr, shadow_rule_or_reference(shadow), query_mask(s, vis));
     else if (shadow)
@@ -1885,7 +1899,9 @@ static int check_render_paths(const srt_scene* s, const srt_params* p, const srt
     return SRT_OK;
 }
 static int render_paths_device_impl(srt_scene* s, const srt_params* p, const srt_path_desc* path, const srt_shadow_rule* shadow, hipStream_t stream, float* d_rgb_linear,
-                                    uint8_t* d_rgb8, const srt_path_out* seg, bool count_hits, const srt_visibility* vis = nullptr) {
+                                    uint8_t* d_rgb8, const srt_path_out* seg, bool count_hits, const srt_visibility* vis = nullptr,
+                                    const srt_refraction* refr = nullptr) {
+    SRT_TRY(check_refraction(refr));
     SRT_TRY(check_shadow(shadow));
     SRT_TRY(check_render_paths(s, p, path));
     const uint32_t rows = srt_rows_owned(p), wl = srt_cols_owned(p);
@@ -1906,7 +1922,13 @@ static int render_paths_device_impl(srt_scene* s, const srt_params* p, const srt
     static const decltype(&k_render_path_masked<false, false, false>) masked_builds[8] = {
         &k_render_path_masked<false, false, false>, &k_render_path_masked<false, false, true>, &k_render_path_masked<false, true, false>, &k_render_path_masked<false, true, true>,
         &k_render_path_masked<true, false, false>,  &k_render_path_masked<true, false, true>,  &k_render_path_masked<true, true, false>,  &k_render_path_masked<true, true, true> };
-    if (vis)
+    static const decltype(&k_render_path_refract<false, false, false>) refract_builds[8] = {
+        &k_render_path_refract<false, false, false>, &k_render_path_refract<false, false, true>, &k_render_path_refract<false, true, false>, &k_render_path_refract<false, true, true>,
+        &k_render_path_refract<true, false, false>,  &k_render_path_refract<true, false, true>,  &k_render_path_refract<true, true, false>,  &k_render_path_refract<true, true, true> };
+    if (const float* d_ior = refraction_table(refr))
+        hipLaunchKernelGGL(refract_builds[build], grid, dim3(256), 0, q.stream, s->dev, dp, p->spp, m, query_shade(s, p), *path, d_rgb_linear, d_rgb8,
+                           seg ? *seg : srt_path_out{}, q.ctr, shadow_rule_or_reference(shadow), query_mask_or_all(s, vis), d_ior);
+    else if (vis)
         hipLaunchKernelGGL(masked_builds[build], grid, dim3(256), 0, q.stream, s->dev, dp, p->spp, m, query_shade(s, p), *path, d_rgb_linear, d_rgb8,
                            seg ? *seg : srt_path_out{}, q.ctr, shadow_rule_or_reference(shadow), query_mask(s, vis));
     else if (shadow)
@@ -1964,17 +1986,18 @@ static int surface_hits_device_impl(srt_scene* s, uint32_t n, const float* d_ray
 // The host entry points: the caller's rays go through the pinned staging block (stage_acquire, as every update does) into the handle's
 // own ray buffer on the scene's stream, the device entry point runs behind them, the call waits and copies the results out.
 // skip_obj: n int32 a call brings -- the skipped objects of srt_occluded, the hit ids of srt_surface_hits; t_in: the t of those hits
-// refl: the n_refl floats of srt_shade_paths' reflectance table
+// refl: the n_refl floats of srt_shade_paths' reflectance table; ior: the n_ior floats of srt_shade_paths_refract's table, staged the same way
 static int stage_rays(srt_scene* s, uint32_t n, const float* rays, const float* t_range, const int32_t* skip_obj, const float* t_in, hipStream_t st,
-                      const float* refl = nullptr, uint32_t n_refl = 0) {
+                      const float* refl = nullptr, uint32_t n_refl = 0, const float* ior = nullptr, uint32_t n_ior = 0) {
     auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
     const size_t o_rays = 0, o_skip = rays ? pad((size_t)n * 24) : 0, o_range = o_skip + (skip_obj ? pad((size_t)n * 4) : 0), o_tin = o_range + (t_range ? pad((size_t)n * 8) : 0),
-                 o_refl = o_tin + (t_in ? pad((size_t)n * 4) : 0), total = o_refl + (refl ? pad((size_t)n_refl * 4) : 0);
+                 o_refl = o_tin + (t_in ? pad((size_t)n * 4) : 0), o_ior = o_refl + (refl ? pad((size_t)n_refl * 4) : 0), total = o_ior + (ior ? pad((size_t)n_ior * 4) : 0);
     if (rays) SRT_TRY(grow(s, n, s->rq_rays));
     if (skip_obj) SRT_TRY(grow(s, n, s->rq_skip));
     if (t_range) SRT_TRY(grow(s, n, s->rq_range));
     if (t_in) SRT_TRY(grow(s, n, s->rq_tin));
     if (refl) SRT_TRY(grow(s, n_refl, s->rq_refl));
+    if (ior) SRT_TRY(grow(s, n_ior, s->rq_ior));
     char* h = nullptr;
     SRT_TRY(stage_acquire(s, total, &h));
     if (rays) {                                               // (srt_render_paths brings none: a frame's rays are made on the device)
@@ -1997,6 +2020,10 @@ static int stage_rays(srt_scene* s, uint32_t n, const float* rays, const float* 
         std::memcpy(h + o_refl, refl, (size_t)n_refl * 4);
         HIP_TRY(hipMemcpyAsync(s->rq_refl, h + o_refl, (size_t)n_refl * 4, hipMemcpyHostToDevice, st));
     }
+    if (ior && n_ior) {
+        std::memcpy(h + o_ior, ior, (size_t)n_ior * 4);
+        HIP_TRY(hipMemcpyAsync(s->rq_ior, h + o_ior, (size_t)n_ior * 4, hipMemcpyHostToDevice, st));
+    }
     HIP_TRY(hipEventRecord(s->staged, st));
     return SRT_OK;
 }
@@ -2014,18 +2041,18 @@ template <typename T, size_t K>
 static QueryOut<T, K> query_out(T* host, DevArray<T, K>& dev, size_t per = 1) { return QueryOut<T, K>{ host, dev, per }; }
 
 // The round trip of a host query on the scene's own stream: grow the wanted result buffers, stage the rays (and what comes with them: t
-// intervals, skipped objects, the hits of srt_surface_hits, the reflectance table of srt_shade_paths), launch(stream) -- the device entry
+// intervals, skipped objects, the hits of srt_surface_hits, the reflectance and refraction tables of the path calls), launch(stream) -- the device entry
 // point --, wait, copy each wanted array out.
 template <typename Launch, typename... O>
 static int query_round_trip_refl(srt_scene* s, uint32_t n, const float* rays, const float* t_range, const int32_t* skip_obj, const float* t_in, const float* refl,
-                                 uint32_t n_refl, Launch launch, const O&... outs) {
+                                 uint32_t n_refl, const float* ior, uint32_t n_ior, Launch launch, const O&... outs) {
     HIP_TRY(hipSetDevice(s->device));
     hipStream_t st;
     SRT_TRY(own_stream(s, &st));
     int rc = SRT_OK;
     ((rc = (rc == SRT_OK && outs.host) ? grow(s, (size_t)n * outs.per, outs.dev) : rc), ...);
     SRT_TRY(rc);
-    SRT_TRY(stage_rays(s, n, rays, t_range, skip_obj, t_in, st, refl, n_refl));
+    SRT_TRY(stage_rays(s, n, rays, t_range, skip_obj, t_in, st, refl, n_refl, ior, n_ior));
     SRT_TRY(launch(st));
     HIP_TRY(hipStreamSynchronize(st));
     if (s->qlights_stream == st) s->qlights_settled = true;      // a light table sent on this stream has arrived
@@ -2036,7 +2063,7 @@ static int query_round_trip_refl(srt_scene* s, uint32_t n, const float* rays, co
 }
 template <typename Launch, typename... O>
 static int query_round_trip(srt_scene* s, uint32_t n, const float* rays, const float* t_range, const int32_t* skip_obj, const float* t_in, Launch launch, const O&... outs) {
-    return query_round_trip_refl(s, n, rays, t_range, skip_obj, t_in, nullptr, 0, launch, outs...);
+    return query_round_trip_refl(s, n, rays, t_range, skip_obj, t_in, nullptr, 0, nullptr, 0, launch, outs...);
 }
 
 }      // extern "C++"
@@ -2111,7 +2138,8 @@ static int shade_rays_impl(srt_scene* s, uint32_t n, const float* rays, const fl
 // srt_shade_paths: the per-segment rows are depth units a ray; hit_rays counts the hits of all segments, hence the shadow rays
 static int shade_paths_impl(srt_scene* s, uint32_t n, const float* rays, const float* t_range, const srt_params* p, const srt_path_desc* path,
                             const srt_shadow_rule* shadow, float* rgb_linear, uint8_t* rgb8, const srt_path_out* seg, srt_stats* stats,
-                            const srt_visibility* vis = nullptr) {
+                            const srt_visibility* vis = nullptr, const srt_refraction* refr = nullptr) {
+    SRT_TRY(check_refraction(refr));
     SRT_TRY(check_shadow(shadow));
     SRT_TRY(check_paths(s, n, rays, p, path));
     if (stats) std::memset(stats, 0, sizeof(*stats));
@@ -2121,18 +2149,22 @@ static int shade_paths_impl(srt_scene* s, uint32_t n, const float* rays, const f
     const auto o_lin = query_out(rgb_linear, s->rq_lin); const auto o_rgb8 = query_out(rgb8, s->rq_rgb8);
     const auto o_hit = query_out(h.hit_id, s->rq_hit, D); const auto o_t = query_out(h.t, s->rq_t, D); const auto o_obj = query_out(h.obj, s->rq_sobj, D);
     const auto o_slin = query_out(h.rgb_linear, s->rq_plin, D); const auto o_rays = query_out(h.rays, s->rq_sbounce, D);
-    SRT_TRY(query_round_trip_refl(s, n, rays, t_range, nullptr, nullptr, path->reflectance, path->reflectance ? s->dev.n_objects : 0u, [&](hipStream_t st) {
+    const float* ior = refraction_table(refr);
+    SRT_TRY(query_round_trip_refl(s, n, rays, t_range, nullptr, nullptr, path->reflectance, path->reflectance ? s->dev.n_objects : 0u, ior, ior ? s->dev.n_objects : 0u,
+                                  [&](hipStream_t st) {
         const srt_path_desc dpath = { path->depth, path->bounce_t_min, path->reflectance ? s->rq_refl.p : nullptr };
+        const srt_refraction drefr = { ior ? s->rq_ior.p : nullptr, 0u };
         const srt_path_out dev = { o_hit.wanted(), o_t.wanted(), o_obj.wanted(), o_slin.wanted(), o_rays.wanted() };
         return shade_paths_device_impl(s, n, s->rq_rays, t_range ? s->rq_range.p : nullptr, p, &dpath, shadow, st, o_lin.wanted(), o_rgb8.wanted(), &dev, stats != nullptr,
-                                       vis);
+                                       vis, &drefr);
     }, o_lin, o_rgb8, o_hit, o_t, o_obj, o_slin, o_rays));
     return stats ? query_stats(s, n, p->n_lights, stats) : SRT_OK;
 }
 
 // srt_render_paths: as shade_paths_impl, with n the call's local pixels and no rays to stage; primary_rays counts image pixels x spp
 static int render_paths_impl(srt_scene* s, const srt_params* p, const srt_path_desc* path, const srt_shadow_rule* shadow, float* rgb_linear, uint8_t* rgb8,
-                             const srt_path_out* seg, srt_stats* stats, const srt_visibility* vis = nullptr) {
+                             const srt_path_out* seg, srt_stats* stats, const srt_visibility* vis = nullptr, const srt_refraction* refr = nullptr) {
+    SRT_TRY(check_refraction(refr));
     SRT_TRY(check_shadow(shadow));
     SRT_TRY(check_render_paths(s, p, path));
     if (stats) std::memset(stats, 0, sizeof(*stats));
@@ -2144,8 +2176,11 @@ static int render_paths_impl(srt_scene* s, const srt_params* p, const srt_path_d
     const auto o_hit = query_out(h.hit_id, s->rq_hit, D); const auto o_t = query_out(h.t, s->rq_t, D); const auto o_obj = query_out(h.obj, s->rq_sobj, D);
     const auto o_slin = query_out(h.rgb_linear, s->rq_plin, D); const auto o_rays = query_out(h.rays, s->rq_sbounce, D);
     const bool padded = p->block_cols != 0;      // padding pixels are not written: what the handle's buffers hold there must not reach the caller
-    SRT_TRY(query_round_trip_refl(s, n, nullptr, nullptr, nullptr, nullptr, path->reflectance, path->reflectance ? s->dev.n_objects : 0u, [&](hipStream_t st) -> int {
+    const float* ior = refraction_table(refr);
+    SRT_TRY(query_round_trip_refl(s, n, nullptr, nullptr, nullptr, nullptr, path->reflectance, path->reflectance ? s->dev.n_objects : 0u, ior, ior ? s->dev.n_objects : 0u,
+                                  [&](hipStream_t st) -> int {
         const srt_path_desc dpath = { path->depth, path->bounce_t_min, path->reflectance ? s->rq_refl.p : nullptr };
+        const srt_refraction drefr = { ior ? s->rq_ior.p : nullptr, 0u };
         const srt_path_out dev = { o_hit.wanted(), o_t.wanted(), o_obj.wanted(), o_slin.wanted(), o_rays.wanted() };
         if (padded) {
             // The caller's arrays first, so that the copy out returns their padding as it was.  hipMemcpy from pageable memory returns when
@@ -2158,7 +2193,7 @@ static int render_paths_impl(srt_scene* s, const srt_params* p, const srt_path_d
             up(dev.rays, h.rays, D * n * 24); up(o_lin.wanted(), rgb_linear, (size_t)n * 12); up(o_rgb8.wanted(), rgb8, (size_t)n * 3);
             HIP_TRY(e);
         }
-        return render_paths_device_impl(s, p, &dpath, shadow, st, o_lin.wanted(), o_rgb8.wanted(), &dev, stats != nullptr, vis);
+        return render_paths_device_impl(s, p, &dpath, shadow, st, o_lin.wanted(), o_rgb8.wanted(), &dev, stats != nullptr, vis, &drefr);
     }, o_lin, o_rgb8, o_hit, o_t, o_obj, o_slin, o_rays));
     if (!stats) return SRT_OK;
     SRT_TRY(query_stats(s, n, p->n_lights, stats));
@@ -2309,6 +2344,24 @@ int srt_render_paths_masked_device(srt_scene* s, const srt_params* p, const srt_
 int srt_render_paths_masked(srt_scene* s, const srt_params* p, const srt_path_desc* path, const srt_shadow_rule* shadow, const srt_visibility* vis, float* rgb_linear,
                             uint8_t* rgb8, const srt_path_out* seg, srt_stats* stats) {
     return guarded([&] { return render_paths_impl(s, p, path, shadow, rgb_linear, rgb8, seg, stats, vis); });
+}
+// Refracting paths: the four path calls with a refraction table after the masks (no table: the _masked call above, with its kernels)
+int srt_shade_paths_refract_device(srt_scene* s, uint32_t n, const float* d_rays, const float* d_t_range, const srt_params* p, const srt_path_desc* path,
+                                   const srt_shadow_rule* shadow, const srt_visibility* vis, const srt_refraction* refr, void* stream, float* d_rgb_linear, uint8_t* d_rgb8,
+                                   const srt_path_out* seg) {
+    return guarded([&] { return shade_paths_device_impl(s, n, d_rays, d_t_range, p, path, shadow, (hipStream_t)stream, d_rgb_linear, d_rgb8, seg, false, vis, refr); });
+}
+int srt_shade_paths_refract(srt_scene* s, uint32_t n, const float* rays, const float* t_range, const srt_params* p, const srt_path_desc* path, const srt_shadow_rule* shadow,
+                            const srt_visibility* vis, const srt_refraction* refr, float* rgb_linear, uint8_t* rgb8, const srt_path_out* seg, srt_stats* stats) {
+    return guarded([&] { return shade_paths_impl(s, n, rays, t_range, p, path, shadow, rgb_linear, rgb8, seg, stats, vis, refr); });
+}
+int srt_render_paths_refract_device(srt_scene* s, const srt_params* p, const srt_path_desc* path, const srt_shadow_rule* shadow, const srt_visibility* vis,
+                                    const srt_refraction* refr, void* stream, float* d_rgb_linear, uint8_t* d_rgb8, const srt_path_out* seg) {
+    return guarded([&] { return render_paths_device_impl(s, p, path, shadow, (hipStream_t)stream, d_rgb_linear, d_rgb8, seg, false, vis, refr); });
+}
+int srt_render_paths_refract(srt_scene* s, const srt_params* p, const srt_path_desc* path, const srt_shadow_rule* shadow, const srt_visibility* vis,
+                             const srt_refraction* refr, float* rgb_linear, uint8_t* rgb8, const srt_path_out* seg, srt_stats* stats) {
+    return guarded([&] { return render_paths_impl(s, p, path, shadow, rgb_linear, rgb8, seg, stats, vis, refr); });
 }
 
 int srt_surface_rays_device(srt_scene* s, uint32_t n, const float* d_rays, const float* d_t_range, uint32_t flags, void* stream, int32_t* d_hit_id, float* d_t,

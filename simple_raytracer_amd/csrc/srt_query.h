@@ -606,6 +606,26 @@ __device__ __forceinline__ V3 mirror_dir(const V3 d, const V3 N) {
     return mk(d.x - (N.x * k) * 2.0f, d.y - (N.y * k) * 2.0f, d.z - (N.z * k) * 2.0f);
 }
 
+// The transmitted direction of d at a surface with outward normal N and index of refraction n (include/srt.h, "Refracting paths"): Snell's
+// law in glm::normalize's and glm::refract's operations, every step f32 without contraction.  c < 0: the ray enters the solid (eta = 1 / n),
+// otherwise it leaves it (the normal flipped, eta = n).  The result is scaled back to d's length, so that t of the next segment stays in the
+// caller's units.  k < 0 is total internal reflection: mirror_dir(d, N), d not normalised; a NaN k goes the refracted way and stays NaN.
+// Straight-line code: the choices are selects, and nothing here is live once the direction is returned.
+__device__ __forceinline__ V3 refract_dir(const V3 d, const V3 N, const float n) {
+    const float L = sqrtf(dot3(d, d)), inv = 1.0f / L;
+    const V3 I = mk(d.x * inv, d.y * inv, d.z * inv);
+    const float c = dot3(N, I);
+    const bool entering = c < 0.0f;
+    const V3 Nf = entering ? N : neg(N);
+    const float dv = entering ? c : -c, eta = entering ? 1.0f / n : n;
+    const float k = 1.0f - (eta * eta) * (1.0f - dv * dv);
+    const float sn = eta * dv + sqrtf(k);
+    const V3 r = mk((eta * I.x - sn * Nf.x) * L, (eta * I.y - sn * Nf.y) * L, (eta * I.z - sn * Nf.z) * L);
+    const V3 m = mirror_dir(d, N);
+    const bool tir = k < 0.0f;
+    return mk(tir ? m.x : r.x, tir ? m.y : r.y, tir ? m.z : r.z);
+}
+
 // (is_hit, id, o, d, t, the surface there) -> the row of every wanted output.  Called by the whole wave (base < n_rays is wave-uniform).
 __device__ __forceinline__ void surface_store(const DevScene& s, const srt_surface_out& out, const size_t base, const uint32_t lane, const uint32_t rows,
                                               const bool is_hit, const int32_t id, const V3 o, const V3 d, const float t, const Surface& f, float* stage) {
@@ -716,6 +736,9 @@ __global__ __launch_bounds__(256) void k_query_surface_hits(DevScene s, uint32_t
 // a lane given by the deal instead of base + lane (without spread the addresses are store_rows' own).
 // seg's rows are segment-major: row b of a field starts n_rays elements (x 3, x 6) after row b - 1.
 // counters: as k_query_shade's, summed over the segments walked; a hit counts once per segment.
+// Refracting paths (srt_shade_paths_refract): the REFRACT build of the same statements.  The one thing that differs is the direction of
+// the next segment after a hit on an object k with ior[k] > 0: refract_dir instead of mirror_dir, from the same point, with the same
+// interval.  The walk does not skip the hit's own object, so a ray that enters a solid finds its far side.
 // =================================================================================================
 template <int K, typename RayOf>
 __device__ __forceinline__ void store_rows_dealt(float* __restrict__ dst, const uint32_t lane, const size_t n_rays, const float (&v)[K], float* stage, RayOf ray_of) {
@@ -746,12 +769,14 @@ __device__ __forceinline__ void store_rows_dealt(float* __restrict__ dst, const 
 // SHADOW: every segment's shadow rays run under `rule` (the builds without it never read it).
 // MASK: segment 0 is walked with qm.primary, every later segment with qm.bounce, every shadow ray with qm.shadow, all against qm.obj
 // (the builds without it never read qm).
-template <bool COUNT, bool SMOOTH, bool INT_SHIN, bool SHADOW, bool MASK = false, typename RayOf>
+// REFRACT: a hit on an object k with ior[k] > 0 sends the next segment along refract_dir instead of mirror_dir, chosen per lane by a
+// select (the builds without it never read ior; ior is non-NULL in the builds with it).
+template <bool COUNT, bool SMOOTH, bool INT_SHIN, bool SHADOW, bool MASK = false, bool REFRACT = false, typename RayOf>
 __device__ __forceinline__ V3 path_segments(const DevScene& s, const QueryShade& p, const srt_path_desc& path, const srt_path_out& seg, const size_t n, const size_t ri,
                                             const bool live, V3 o, V3 d, float t_min, float t_max, const uint32_t lane, uint32_t* q, unsigned long long* best,
                                             float (*wray)[64], const RayOf ray_of, unsigned long long* __restrict__ counters, const uint32_t shard, bool& hit0,
                                             unsigned long long& n_node, unsigned long long& n_tri, unsigned long long& n_node_s, unsigned long long& n_tri_s,
-                                            const ShadowRule rule, const QueryMask qm = QueryMask{}) {
+                                            const ShadowRule rule, const QueryMask qm = QueryMask{}, const float* __restrict__ ior = nullptr) {
     float* stage = &wray[0][0];
     V3 acc = mk(0.0f, 0.0f, 0.0f), pend = acc;          // the mix so far; the sum of the segment that waits for its weight
     float W = 1.0f, pend_k = 0.0f;                      // the weight of what follows; the waiting segment's reflectance
@@ -792,7 +817,14 @@ __device__ __forceinline__ V3 path_segments(const DevScene& s, const QueryShade&
             pend = sum;
             pend_k = path.reflectance ? path.reflectance[obj] : 0.0f;
             const V3 P = o + d * t;                     // the bounce row of surface_store: the point, not moved, and the mirrored direction
-            d = mirror_dir(d, f.nrm);
+            if (REFRACT) {
+                const float n_obj = ior[obj];           // (0, negative, NaN: the object mirrors)
+                const V3 m = mirror_dir(d, f.nrm), r = refract_dir(d, f.nrm, n_obj);
+                const bool glass = n_obj > 0.0f;
+                d = mk(glass ? r.x : m.x, glass ? r.y : m.y, glass ? r.z : m.z);
+            } else {
+                d = mirror_dir(d, f.nrm);
+            }
             o = P;
             t_min = path.bounce_t_min; t_max = __builtin_inff();
         }
@@ -817,11 +849,11 @@ __device__ __forceinline__ V3 path_segments(const DevScene& s, const QueryShade&
 
 // The body of both k_query_path kernels: k_query_path is what a call without a shadow rule launches, argument for argument what it was;
 // k_query_path_shadow takes the rule as one more argument and is the SHADOW build of the same statements.
-template <bool COUNT, bool SMOOTH, bool INT_SHIN, bool SHADOW, bool MASK = false>
+template <bool COUNT, bool SMOOTH, bool INT_SHIN, bool SHADOW, bool MASK = false, bool REFRACT = false>
 __device__ __forceinline__ void query_path_rays(const DevScene& s, const uint32_t n_rays, const float* __restrict__ rays, const uint32_t wide, const QueryShade& p,
                                                 const QueryRange tr, const srt_path_desc& path, float* __restrict__ rgb_linear, uint8_t* __restrict__ rgb8,
                                                 const srt_path_out& seg, unsigned long long* __restrict__ counters, const ShadowRule rule,
-                                                const QueryMask qm = QueryMask{}) {
+                                                const QueryMask qm = QueryMask{}, const float* __restrict__ ior = nullptr) {
     __shared__ uint32_t q_all[4][QCAP];
     __shared__ unsigned long long best_all[256];
     __shared__ float ray_all[4][8][64];
@@ -837,8 +869,9 @@ __device__ __forceinline__ void query_path_rays(const DevScene& s, const uint32_
     if (live) load_ray(rays, ri, wide != 0, o, d);
     if (tr.t && live) load_range(tr, ri, t_min, t_max);
     bool hit0;
-    const V3 acc = path_segments<COUNT, SMOOTH, INT_SHIN, SHADOW, MASK>(s, p, path, seg, n, ri, live, o, d, t_min, t_max, lane, q_all[wave], best_all + wave * 64,
-                                                                        ray_all[wave], ray_of, counters, blockIdx.x, hit0, n_node, n_tri, n_node_s, n_tri_s, rule, qm);
+    const V3 acc = path_segments<COUNT, SMOOTH, INT_SHIN, SHADOW, MASK, REFRACT>(s, p, path, seg, n, ri, live, o, d, t_min, t_max, lane, q_all[wave], best_all + wave * 64,
+                                                                                 ray_all[wave], ray_of, counters, blockIdx.x, hit0, n_node, n_tri, n_node_s, n_tri_s, rule, qm,
+                                                                                 ior);
     if (live) store_pixel(rgb_linear, rgb8, ri, acc, hit0, p.reinhard, p.gamma, p.bg);
     if (COUNT) { wave_add(counters + 1, n_node); wave_add(counters + 2, n_tri); wave_add(counters + 3, n_node_s); wave_add(counters + 4, n_tri_s); }
 }
@@ -864,6 +897,15 @@ __global__ __launch_bounds__(256) void k_query_path_masked(DevScene s, uint32_t 
     query_path_rays<COUNT, SMOOTH, INT_SHIN, true, true>(s, n_rays, rays, wide, p, tr, path, rgb_linear, rgb8, seg, counters, rule, qm);
 }
 
+// srt_shade_paths_refract: the SHADOW + MASK + REFRACT build of the same statements.  A call without a rule sends the reference's rule, a
+// call without masks all ones with a NULL table; ior, n_objects floats, travels by value beside the path description.
+template <bool COUNT, bool SMOOTH, bool INT_SHIN>
+__global__ __launch_bounds__(256) void k_query_path_refract(DevScene s, uint32_t n_rays, const float* __restrict__ rays, uint32_t wide, QueryShade p, QueryRange tr,
+                                                            srt_path_desc path, float* __restrict__ rgb_linear, uint8_t* __restrict__ rgb8, srt_path_out seg,
+                                                            unsigned long long* __restrict__ counters, ShadowRule rule, QueryMask qm, const float* __restrict__ ior) {
+    query_path_rays<COUNT, SMOOTH, INT_SHIN, true, true, true>(s, n_rays, rays, wide, p, tr, path, rgb_linear, rgb8, seg, counters, rule, qm, ior);
+}
+
 // =================================================================================================
 // Mirror paths in a frame (srt_render_paths): k_query_path's paths for the rays of a frame's own pixels.  The front end is the render
 // kernels': a wave owns one 8 x 8 pixel tile and a workgroup 16 x 16 (tile_pixel), the grid is 2-D over the call's local output, and a
@@ -877,10 +919,11 @@ __global__ __launch_bounds__(256) void k_query_path_masked(DevScene s, uint32_t 
 // seg's rows are sub-sample 0's.  counters: as k_query_path's, over all sub-samples; the hit shard is the 2-D workgroup number.
 // =================================================================================================
 // The body of both k_render_path kernels, as query_path_rays is k_query_path's.  fp: the frame's geometry; sub_x / sub_y change per sub-sample.
-template <bool COUNT, bool SMOOTH, bool INT_SHIN, bool SHADOW, bool MASK = false>
+template <bool COUNT, bool SMOOTH, bool INT_SHIN, bool SHADOW, bool MASK = false, bool REFRACT = false>
 __device__ __forceinline__ void render_path_pixels(const DevScene& s, DevParams& fp, const uint32_t spp, const uint32_t spp_m, const QueryShade& p, const srt_path_desc& path,
                                                    float* __restrict__ rgb_linear, uint8_t* __restrict__ rgb8, const srt_path_out& seg,
-                                                   unsigned long long* __restrict__ counters, const ShadowRule rule, const QueryMask qm = QueryMask{}) {
+                                                   unsigned long long* __restrict__ counters, const ShadowRule rule, const QueryMask qm = QueryMask{},
+                                                   const float* __restrict__ ior = nullptr) {
     __shared__ uint32_t q_all[4][QCAP];
     __shared__ unsigned long long best_all[256];
     __shared__ float ray_all[4][8][64];
@@ -903,9 +946,9 @@ __device__ __forceinline__ void render_path_pixels(const DevScene& s, DevParams&
         }
         const V3 d = live ? primary_dir(fp, px, y) : mk(0.0f, 0.0f, 1.0f);
         bool h;
-        const V3 acc = path_segments<COUNT, SMOOTH, INT_SHIN, SHADOW, MASK>(s, p, path, k == 0 ? seg : srt_path_out{}, n, ri, live, o, d, __builtin_nanf(""), __builtin_nanf(""),
-                                                                            lane, q_all[wave], best_all + wave * 64, ray_all[wave], ray_of, counters, shard, h, n_node, n_tri,
-                                                                            n_node_s, n_tri_s, rule, qm);
+        const V3 acc = path_segments<COUNT, SMOOTH, INT_SHIN, SHADOW, MASK, REFRACT>(s, p, path, k == 0 ? seg : srt_path_out{}, n, ri, live, o, d, __builtin_nanf(""),
+                                                                                     __builtin_nanf(""), lane, q_all[wave], best_all + wave * 64, ray_all[wave], ray_of, counters,
+                                                                                     shard, h, n_node, n_tri, n_node_s, n_tri_s, rule, qm, ior);
         if (k == 0) { total = acc; hit0 = h; }
         else total = mk(total.x + acc.x, total.y + acc.y, total.z + acc.z);
     }
@@ -931,4 +974,11 @@ __global__ __launch_bounds__(256) void k_render_path_masked(DevScene s, DevParam
                                                             float* __restrict__ rgb_linear, uint8_t* __restrict__ rgb8, srt_path_out seg,
                                                             unsigned long long* __restrict__ counters, ShadowRule rule, QueryMask qm) {
     render_path_pixels<COUNT, SMOOTH, INT_SHIN, true, true>(s, fp, spp, spp_m, p, path, rgb_linear, rgb8, seg, counters, rule, qm);
+}
+// srt_render_paths_refract: as k_query_path_refract is k_query_path_masked's.
+template <bool COUNT, bool SMOOTH, bool INT_SHIN>
+__global__ __launch_bounds__(256) void k_render_path_refract(DevScene s, DevParams fp, uint32_t spp, uint32_t spp_m, QueryShade p, srt_path_desc path,
+                                                             float* __restrict__ rgb_linear, uint8_t* __restrict__ rgb8, srt_path_out seg,
+                                                             unsigned long long* __restrict__ counters, ShadowRule rule, QueryMask qm, const float* __restrict__ ior) {
+    render_path_pixels<COUNT, SMOOTH, INT_SHIN, true, true, true>(s, fp, spp, spp_m, p, path, rgb_linear, rgb8, seg, counters, rule, qm, ior);
 }

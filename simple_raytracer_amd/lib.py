@@ -28,7 +28,8 @@ ABI_SYMBOLS = ("srt_params_default", "srt_light_staircase", "srt_rows_owned", "s
                "srt_surface_rays_device", "srt_surface_rays", "srt_surface_hits_device", "srt_surface_hits", "srt_shade_paths_device", "srt_shade_paths",
                "srt_render_paths_device", "srt_render_paths", "srt_shade_paths_shadow_device", "srt_shade_paths_shadow", "srt_render_paths_shadow_device",
                "srt_render_paths_shadow", "srt_scene_set_object_masks", "srt_trace_rays_masked_device", "srt_trace_rays_masked", "srt_occluded_masked_device",
-               "srt_occluded_masked", "srt_shade_paths_masked_device", "srt_shade_paths_masked", "srt_render_paths_masked_device", "srt_render_paths_masked")
+               "srt_occluded_masked", "srt_shade_paths_masked_device", "srt_shade_paths_masked", "srt_render_paths_masked_device", "srt_render_paths_masked",
+               "srt_shade_paths_refract_device", "srt_shade_paths_refract", "srt_render_paths_refract_device", "srt_render_paths_refract")
 MULTI_HIT_MAX = 16                # SRT_MULTI_HIT_MAX
 
 _f32p, _i32p, _u8p, _u32p = C.POINTER(C.c_float), C.POINTER(C.c_int32), C.POINTER(C.c_uint8), C.POINTER(C.c_uint32)
@@ -165,6 +166,14 @@ def load(path=None):
         L.srt_render_paths_masked.argtypes = L.srt_render_paths_shadow.argtypes[:4] + [_vis] + L.srt_render_paths_shadow.argtypes[4:]
         for f in (L.srt_scene_set_object_masks, L.srt_trace_rays_masked_device, L.srt_trace_rays_masked, L.srt_occluded_masked_device, L.srt_occluded_masked,
                   L.srt_shade_paths_masked_device, L.srt_shade_paths_masked, L.srt_render_paths_masked_device, L.srt_render_paths_masked):
+            f.restype = C.c_int
+        # refracting paths: one srt_refraction* after the srt_visibility*
+        _refr = C.POINTER(abi.Refraction)
+        L.srt_shade_paths_refract_device.argtypes = L.srt_shade_paths_masked_device.argtypes[:8] + [_refr] + L.srt_shade_paths_masked_device.argtypes[8:]
+        L.srt_shade_paths_refract.argtypes = L.srt_shade_paths_masked.argtypes[:8] + [_refr] + L.srt_shade_paths_masked.argtypes[8:]
+        L.srt_render_paths_refract_device.argtypes = L.srt_render_paths_masked_device.argtypes[:5] + [_refr] + L.srt_render_paths_masked_device.argtypes[5:]
+        L.srt_render_paths_refract.argtypes = L.srt_render_paths_masked.argtypes[:5] + [_refr] + L.srt_render_paths_masked.argtypes[5:]
+        for f in (L.srt_shade_paths_refract_device, L.srt_shade_paths_refract, L.srt_render_paths_refract_device, L.srt_render_paths_refract):
             f.restype = C.c_int
         L.srt_strerror.argtypes = [C.c_int]
         L.srt_strerror.restype = C.c_char_p
@@ -540,7 +549,7 @@ class DeviceScene:
 
     def shade_paths(self, rays, params: abi.Params, depth, reflectance=None, bounce_t_min=1e-3, t_range=None,
                     want=("rgb_linear", "rgb8", "seg_hit_id", "seg_t", "seg_obj", "seg_rgb_linear", "seg_rays"), count=False, smooth=False, shadow=None,
-                    visibility=None):
+                    visibility=None, ior=None):
         """srt_shade_paths: every ray of `rays` (n x 6, host array) followed through up to `depth` mirror bounces, each hit shaded as
         shade_rays(t_range=...) shades it, the segments mixed by `reflectance` (one float per object, or None = all 0).  A mirrored ray's
         interval is (bounce_t_min, +inf); t_range (n x 2) bounds segment 0.  Returns a dict of the arrays named in `want` -- rgb_linear
@@ -550,7 +559,9 @@ class DeviceScene:
         ray blocks only inside the closed (t_min, t_max) in units of light - hit point, and with self_shadow the hit object's own tree
         is walked too (srt_*_paths_shadow).
         visibility: None, or (primary, bounce, shadow) -- the object masks segment 0, every later segment and every shadow ray are
-        walked with (srt_*_paths_masked; set_object_masks gives the objects their bits)."""
+        walked with (srt_*_paths_masked; set_object_masks gives the objects their bits).
+        ior: None, or one float per object (host array) -- object k with ior[k] > 0 is glass: a ray that hits it goes on THROUGH the
+        surface, bent by Snell's law, instead of being mirrored (srt_*_paths_refract); reflectance keeps weighting what follows."""
         r = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
         n = r.shape[0]
         tr = _t_range(t_range, n)
@@ -573,30 +584,37 @@ class DeviceScene:
         head = (self.h, n, r.ctypes.data_as(_f32p), tr.ctypes.data_as(_f32p) if tr is not None else None, C.byref(params), C.byref(pd))
         tail = (g("rgb_linear", _f32p), g("rgb8", _u8p), C.byref(po), C.byref(st))
         vis = abi.visibility(visibility)
+        refr, table = _refraction(ior, self.flat.n_objects)
         try:
-            if vis is not None:
+            if refr is not None:
+                rc = self.L.srt_shade_paths_refract(*head, C.byref(rule) if rule is not None else None, C.byref(vis) if vis is not None else None, C.byref(refr), *tail)
+            elif vis is not None:
                 rc = self.L.srt_shade_paths_masked(*head, C.byref(rule) if rule is not None else None, C.byref(vis), *tail)
             else:
                 rc = self.L.srt_shade_paths(*head, *tail) if rule is None else self.L.srt_shade_paths_shadow(*head, C.byref(rule), *tail)
         finally:
             params.flags = flags
-        _check(rc, "srt_shade_paths_masked" if vis is not None else "srt_shade_paths" if rule is None else "srt_shade_paths_shadow")
+        _check(rc, "srt_shade_paths_refract" if refr is not None else "srt_shade_paths_masked" if vis is not None else "srt_shade_paths" if rule is None else "srt_shade_paths_shadow")
         out["stats"] = st.as_dict()
         return out
 
     def shade_paths_device(self, n, rays, params: abi.Params, depth, reflectance=0, bounce_t_min=1e-3, t_range=None, stream=0, rgb_linear=0, rgb8=0, seg_hit_id=0,
-                           seg_t=0, seg_obj=0, seg_rgb_linear=0, seg_rays=0, shadow=None, visibility=None):
+                           seg_t=0, seg_obj=0, seg_rgb_linear=0, seg_rays=0, shadow=None, visibility=None, ior=None):
         """srt_shade_paths_device: raw device pointers (ints, e.g. torch.Tensor.data_ptr()) in, asynchronous on `stream`, one launch.  The
         light table of `params` is a host array; `reflectance` is a DEVICE pointer to n_objects floats (0 = all 0); t_range a device
         pointer to n x 2 floats, or None; the seg_* outputs are depth x n rows, segment-major.  The flags are those of `params`.
-        shadow, visibility: as in shade_paths."""
+        shadow, visibility: as in shade_paths.  ior: None, or a DEVICE pointer to n_objects floats (0 = no table): srt_shade_paths_refract_device."""
         pd = abi.PathDesc(depth, bounce_t_min, reflectance or None)
         po = abi.PathOut(seg_hit_id or None, seg_t or None, seg_obj or None, seg_rgb_linear or None, seg_rays or None)
         rule = abi.shadow_rule(shadow)
         vis = abi.visibility(visibility)
         head = (self.h, n, C.c_void_p(rays), C.c_void_p(t_range or 0), C.byref(params), C.byref(pd))
         tail = (C.c_void_p(stream), C.c_void_p(rgb_linear), C.c_void_p(rgb8), C.byref(po))
-        if vis is not None:
+        if ior is not None:
+            refr = abi.Refraction(ior or None, 0)
+            _check(self.L.srt_shade_paths_refract_device(*head, C.byref(rule) if rule is not None else None, C.byref(vis) if vis is not None else None, C.byref(refr), *tail),
+                   "srt_shade_paths_refract_device")
+        elif vis is not None:
             _check(self.L.srt_shade_paths_masked_device(*head, C.byref(rule) if rule is not None else None, C.byref(vis), *tail), "srt_shade_paths_masked_device")
         elif rule is None:
             _check(self.L.srt_shade_paths_device(*head, *tail), "srt_shade_paths_device")
@@ -605,13 +623,13 @@ class DeviceScene:
 
     def render_paths(self, params: abi.Params, depth, reflectance=None, bounce_t_min=1e-3,
                      want=("rgb_linear", "rgb8", "seg_hit_id", "seg_t", "seg_obj", "seg_rgb_linear", "seg_rays"), count=False, smooth=False, fill=None, shadow=None,
-                     visibility=None):
+                     visibility=None, ior=None):
         """srt_render_paths: shade_paths for the rays of the frame's own pixels -- the local pixels of a call with `params` (its block or
         tile deal, camera matrix and spp included); no ray array is built.  Returns a dict of the arrays named in `want` -- rgb_linear
         [rows, cols, 3] (mixed), rgb8 [rows, cols, 3], and per segment seg_hit_id / seg_t / seg_obj [depth, rows, cols], seg_rgb_linear
         [depth, rows, cols, 3], seg_rays [depth, rows, cols, 6] -- + 'stats'.  count / smooth add SRT_FLAG_COUNT_WORK /
         SRT_FLAG_SMOOTH_NORMALS for this call.  fill: a value every array holds before the call (padding pixels of a tile deal keep it).
-        shadow, visibility: as in shade_paths."""
+        shadow, visibility, ior: as in shade_paths."""
         rows, W = self.rows(params), self.cols(params)
         refl = None if reflectance is None else np.ascontiguousarray(reflectance, np.float32).reshape(-1)
         new = (lambda shape, ty: np.empty(shape, ty)) if fill is None else (lambda shape, ty: np.full(shape, fill, ty))
@@ -633,30 +651,37 @@ class DeviceScene:
         head = (self.h, C.byref(params), C.byref(pd))
         tail = (g("rgb_linear", _f32p), g("rgb8", _u8p), C.byref(po), C.byref(st))
         vis = abi.visibility(visibility)
+        refr, table = _refraction(ior, self.flat.n_objects)
         try:
-            if vis is not None:
+            if refr is not None:
+                rc = self.L.srt_render_paths_refract(*head, C.byref(rule) if rule is not None else None, C.byref(vis) if vis is not None else None, C.byref(refr), *tail)
+            elif vis is not None:
                 rc = self.L.srt_render_paths_masked(*head, C.byref(rule) if rule is not None else None, C.byref(vis), *tail)
             else:
                 rc = self.L.srt_render_paths(*head, *tail) if rule is None else self.L.srt_render_paths_shadow(*head, C.byref(rule), *tail)
         finally:
             params.flags = flags
-        _check(rc, "srt_render_paths_masked" if vis is not None else "srt_render_paths" if rule is None else "srt_render_paths_shadow")
+        _check(rc, "srt_render_paths_refract" if refr is not None else "srt_render_paths_masked" if vis is not None else "srt_render_paths" if rule is None else "srt_render_paths_shadow")
         out["stats"] = st.as_dict()
         return out
 
     def render_paths_device(self, params: abi.Params, depth, reflectance=0, bounce_t_min=1e-3, stream=0, rgb_linear=0, rgb8=0, seg_hit_id=0, seg_t=0, seg_obj=0,
-                            seg_rgb_linear=0, seg_rays=0, shadow=None, visibility=None):
+                            seg_rgb_linear=0, seg_rays=0, shadow=None, visibility=None, ior=None):
         """srt_render_paths_device: raw device pointers (ints, e.g. torch.Tensor.data_ptr()) in, asynchronous on `stream`, one launch.  The
         light table of `params` is a host array; `reflectance` is a DEVICE pointer to n_objects floats (0 = all 0); the outputs are
         [rows, cols, ...] and the seg_* outputs [depth, rows, cols, ...] of the call's local pixels.  The flags are those of `params`.
-        shadow, visibility: as in shade_paths."""
+        shadow, visibility: as in shade_paths.  ior: as in shade_paths_device."""
         pd = abi.PathDesc(depth, bounce_t_min, reflectance or None)
         po = abi.PathOut(seg_hit_id or None, seg_t or None, seg_obj or None, seg_rgb_linear or None, seg_rays or None)
         rule = abi.shadow_rule(shadow)
         vis = abi.visibility(visibility)
         head = (self.h, C.byref(params), C.byref(pd))
         tail = (C.c_void_p(stream), C.c_void_p(rgb_linear), C.c_void_p(rgb8), C.byref(po))
-        if vis is not None:
+        if ior is not None:
+            refr = abi.Refraction(ior or None, 0)
+            _check(self.L.srt_render_paths_refract_device(*head, C.byref(rule) if rule is not None else None, C.byref(vis) if vis is not None else None, C.byref(refr), *tail),
+                   "srt_render_paths_refract_device")
+        elif vis is not None:
             _check(self.L.srt_render_paths_masked_device(*head, C.byref(rule) if rule is not None else None, C.byref(vis), *tail), "srt_render_paths_masked_device")
         elif rule is None:
             _check(self.L.srt_render_paths_device(*head, *tail), "srt_render_paths_device")
@@ -705,6 +730,15 @@ def _surface_arrays(n, want, out):
             out[name] = np.empty(n if k == 1 else (n, k), ty)
             setattr(so, name, out[name].ctypes.data)
     return so
+
+
+def _refraction(ior, n_objects):
+    """(an abi.Refraction over a host table of n_objects floats, the array that keeps it alive), or (None, None) for None."""
+    if ior is None:
+        return None, None
+    table = np.ascontiguousarray(ior, np.float32).reshape(-1)
+    assert table.shape[0] == n_objects, "ior: one float per object"
+    return abi.Refraction(table.ctypes.data, 0), table
 
 
 def _ray_mask(ray_mask, n):

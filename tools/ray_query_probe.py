@@ -31,7 +31,11 @@ srt_shade_paths_device and srt_render_paths_device with no rule (the existing ke
 kernel, the yardstick -- beside srt_trace_rays_masked_device with every mask all ones (the same answers) and with the bunny hidden by the
 ray masks; and srt_shade_paths_shadow_device under (1e-3, 1, 0) beside srt_shade_paths_masked_device with all ones and with the bunny hidden
 from every ray kind, at depth 3 and 1 / 16 light samples.
-Usage: python tools/ray_query_probe.py [--reps N] [--trace] [--shade | --range | --shade-range | --multi | --surface | --paths | --shadow-rule | --masked [--rounds R]]     (--trace: few repetitions, for a run under rocprofv3 --kernel-trace --stats)"""
+--refract: instead, what the REFRACT build costs the path calls on the rays of the same frame at depth 3 and 1 / 16 light samples, in one
+run: srt_shade_paths_masked_device under (1e-3, 1, 0) with all-ones masks -- the existing kernel, the yardstick -- beside
+srt_shade_paths_refract_device with an all-zero table (the same walks to the bit: the price of the build alone) and with the bunny as glass of
+index 1.5 (other walks: for information).  Beside every ratio stands the yardstick's own round-to-round spread.
+Usage: python tools/ray_query_probe.py [--reps N] [--trace] [--shade | --range | --shade-range | --multi | --surface | --paths | --shadow-rule | --masked | --refract [--rounds R]]     (--trace: few repetitions, for a run under rocprofv3 --kernel-trace --stats)"""
 import argparse, os, sys, time
 import numpy as np
 import torch                                   # first: torch initialises HIP before the library does
@@ -465,8 +469,48 @@ def masked_section(reps, rounds):
     ds.close()
 
 
+def refract_section(reps, rounds):
+    """What the REFRACT build costs: the _refract call with an all-zero table beside the _masked call it extends (the same walks, the
+    same bits), on the rays of the 1080p frame at depth 3; and the same call with the bunny (object 1; object 0 is the ground) as glass."""
+    dev = torch.device("cuda", 0); torch.zeros(1, device=dev)
+    g = gu.GoldenScene("ground_bunny")
+    ds = lib.DeviceScene(g.flat)
+    side = torch.cuda.Stream(device=dev)
+    cur = side.cuda_stream
+    n = W * H
+    nO = g.flat.n_objects
+    ALL = 0xFFFFFFFF
+    d_rays = torch.from_numpy(frame_rays()).to(dev)
+    refl = torch.tensor([0.6, 0.25], dtype=torch.float32, device=dev)
+    d_zero = torch.zeros(nO, dtype=torch.float32, device=dev)
+    d_glass = torch.tensor([0.0, 1.5], dtype=torch.float32, device=dev)
+    rule, vis = (1e-3, 1.0, False), (ALL, ALL, ALL)
+    print(f"refracting paths, K3 ground_bunny {W}x{H}: {n} rays, {nO} objects, depth 3; {rounds} rounds of {reps} calls, forms alternating; ms a call; min / max: the spread of the rounds")
+    print(f"{'call':34s} {'form':34s} {'median':>8s} {'min':>8s} {'max':>8s} {'/ first':>7s}")
+    for L in (1, 16):
+        pq = abi.make_params(1, 1, abi.light_staircase(g.light, L))
+        lin = {k: torch.empty((n, 3), dtype=torch.float32, device=dev) for k in ("masked", "zero", "glass")}
+        hit = {k: torch.empty((3, n), dtype=torch.int32, device=dev) for k in lin}
+        paths = lambda key, table: (lambda: ds.shade_paths_device(n, d_rays.data_ptr(), pq, 3, reflectance=refl.data_ptr(), bounce_t_min=1e-3, stream=cur,
+                                                                  rgb_linear=lin[key].data_ptr(), seg_hit_id=hit[key].data_ptr(), shadow=rule, visibility=vis, ior=table))
+        forms = {"shade_paths_masked (yardstick)": paths("masked", None), "shade_paths_refract, all zero": paths("zero", d_zero.data_ptr()),
+                 "shade_paths_refract, glass bunny": paths("glass", d_glass.data_ptr())}
+        ms = rounds_of(forms, reps, rounds, side)
+        report(f"paths, depth 3, {L} samples", ms)
+        side.synchronize()
+        assert torch.equal(lin["masked"].view(torch.int32), lin["zero"].view(torch.int32)) and torch.equal(hit["masked"], hit["zero"]), "all zero is not the _masked call"
+        yard = ms["shade_paths_masked (yardstick)"]
+        med = float(np.median(yard))
+        moved = int((hit["glass"] != hit["masked"]).any(dim=0).sum().item())
+        print(f"{'':34s} all zero gives the _masked call's bits; the yardstick's own spread: {min(yard) / med:.3f} .. {max(yard) / med:.3f} of its median; "
+              f"hits per segment, mirror {[int((hit['masked'][b] >= 0).sum().item()) for b in range(3)]}, glass {[int((hit['glass'][b] >= 0).sum().item()) for b in range(3)]}; "
+              f"paths the glass moves: {moved}")
+    ds.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--refract", action="store_true")
     ap.add_argument("--masked", action="store_true")
     ap.add_argument("--shadow-rule", action="store_true", dest="shadow_rule")
     ap.add_argument("--paths", action="store_true")
@@ -480,6 +524,8 @@ def main():
     ap.add_argument("--rounds", type=int, default=7)
     a = ap.parse_args()
     reps = 3 if a.trace else a.reps
+    if a.refract:
+        return refract_section(reps, 2 if a.trace else a.rounds)
     if a.masked:
         return masked_section(reps, 2 if a.trace else a.rounds)
     if a.shadow_rule:
