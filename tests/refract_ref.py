@@ -27,8 +27,9 @@ ALL = vr.ALL
 MISS, MIRROR, ENTER, LEAVE, TIR = -1, 0, 1, 2, 3          # what a path does at the end of a segment (kinds())
 
 
-def refract_parts(d, N, n):
-    """The header's formula, row by row: (r, entering, k).  d, N: m x 3 float32; n: m float32."""
+def refract_steps(d, N, n):
+    """The header's formula, row by row, with every step kept: dict of L, inv, I, c, entering, Nf, dv, eta, k, s, u, r (the refracted
+    way, whatever k is) and out (what refract_dir returns).  d, N: m x 3 float32; n: m float32."""
     d, N = np.ascontiguousarray(d, np.float32).reshape(-1, 3), np.ascontiguousarray(N, np.float32).reshape(-1, 3)
     n = np.ascontiguousarray(n, np.float32).reshape(-1)
     with np.errstate(all="ignore"):
@@ -50,12 +51,51 @@ def refract_parts(d, N, n):
         u = eI - sN
         r = u * L[:, None]
         out = np.where((k < F32(0.0))[:, None], sf.reflect(d, N), r)
-    return out.astype(np.float32), entering, k.astype(np.float32)
+    f = lambda a: a.astype(np.float32)
+    return dict(L=f(L), inv=f(inv), I=f(I), c=f(c), entering=entering, Nf=f(Nf), dv=f(dv), eta=f(eta), k=f(k), s=f(s), u=f(u), r=f(r), out=f(out))
+
+
+def refract_parts(d, N, n):
+    """The header's formula, row by row: (r, entering, k).  d, N: m x 3 float32; n: m float32."""
+    p = refract_steps(d, N, n)
+    return p["out"], p["entering"], p["k"]
 
 
 def refract_dir(d, N, n):
     """The direction of the next segment after a hit on a transmitting object: m x 3 float32."""
     return refract_parts(d, N, n)[0]
+
+
+def assert_snell(d, N, r, n, entering, tol=1e-4):
+    """Snell's law in float64 for the rows (d, N, n) -> r the formula refracted (k well above 0): against physics, not against the formula.
+    The quantities compared are sines and cosines of unit vectors, so tol is both absolute and relative to 1; the length is compared
+    relative to |d|."""
+    unit = lambda v: v / np.linalg.norm(v, axis=1, keepdims=True)
+    D, NN, R, n64 = (np.asarray(a, np.float32).astype(np.float64) for a in (d, N, r, n))
+    NN = unit(NN)
+    I = unit(D)
+    cos_i = (I * NN).sum(axis=1)
+    ent = cos_i < 0
+    assert np.array_equal(ent, entering)
+    eta = np.where(ent, 1.0 / n64, n64)
+    Nf = np.where(ent[:, None], NN, -NN)
+    Rh = unit(R)
+    sin_i, sin_t = np.linalg.norm(np.cross(I, NN), axis=1), np.linalg.norm(np.cross(Rh, NN), axis=1)
+    assert np.abs(sin_t - eta * sin_i).max() <= tol, "Snell's law"
+    # in the plane of d and N: no component along I x N (where that axis exists), and on the far side of the tangent from I's
+    axis = np.cross(I, NN)
+    has = sin_i > 1e-3
+    assert np.abs((Rh[has] * unit(axis[has])).sum(axis=1)).max() <= tol, "r leaves the plane of d and N"
+    tang = I - cos_i[:, None] * NN
+    bends = has & (eta * sin_i > tol)             # (a transmitted tangent below the tolerance may round to nothing in float32)
+    assert ((Rh * tang).sum(axis=1)[bends] > 0).all(), "r bends to the wrong side of the normal"
+    assert ((R * Nf).sum(axis=1) < 0).all(), "r does not go through the surface"
+    len_r, len_d = np.linalg.norm(R, axis=1), np.linalg.norm(D, axis=1)
+    assert (np.abs(len_r - len_d) / len_d).max() <= tol, "|r| is not |d|"
+    # the answer itself: Snell's direction built in float64 from the angles
+    cos_t = np.sqrt(1.0 - (eta * sin_i) ** 2)
+    want = eta[:, None] * tang - cos_t[:, None] * Nf
+    assert np.abs(Rh - unit(want)).max() <= tol
 
 
 def next_rays(cur, s, ior):

@@ -1,0 +1,199 @@
+"""GPU (-m gpu): the ray-query family on the adversarial scenes of tests/adversarial.py -- identical triangles in several objects, quads
+whose diagonal belongs to two triangles, flat boxes, a plane through the origin, slivers, scales 1, 1e-3 and 3e5 -- with ray batches aimed
+at them (tests/test_adversarial_ref.py proves on the CPU that the batches reach the cases).  Every output of every call is compared with
+its yardstick bit for bit, surface_ref.assert_same's way: ints by value, floats by bits, NaN where the yardstick is NaN; no row is left out
+and there is no tolerance.  Every test ends by asking the scene for a plain srt_trace_rays again: the non-finite rays left nothing behind."""
+import contextlib
+
+import numpy as np
+import pytest
+
+import adversarial as adv
+import ray_multi_ref as rm
+import ray_range_ref as rr
+import refract_ref as rf
+import render_paths_ref as rpr
+import shade_path_ref as sp
+import shade_query_ref as sq
+import shade_range_ref as sr
+import shadow_rule_ref as sh
+import surface_ref as sf
+import tree_shapes as ts
+import visibility_ref as vr
+from simple_raytracer_amd import abi
+
+pytestmark = pytest.mark.gpu
+bits = sf.bits
+same = sf.assert_same
+ALL = vr.ALL
+TMIN = adv.BOUNCE_T_MIN
+SMOOTH = abi.SRT_FLAG_SMOOTH_NORMALS
+
+
+@pytest.fixture(scope="module")
+def srt():
+    from simple_raytracer_amd import lib
+    lib.load()
+    return lib
+
+
+@contextlib.contextmanager
+def device_scene(srt, oracle, seed):
+    """One DeviceScene for the test; before and after it a plain srt_trace_rays of the whole batch, the yardstick's bits both times."""
+    flat, rays = adv.scene(seed)[0], adv.rays(seed)[0]
+    hit, t = rr.closest(adv.candidates(oracle, seed))
+    ds = srt.DeviceScene(flat)
+    first = ds.trace_rays(rays, want=("hit_id", "t"))
+    same(first, {"hit_id": hit, "t": t}, f"seed {seed}, before")
+    yield ds
+    same(ds.trace_rays(rays, want=("hit_id", "t")), first, f"seed {seed}, after", ("hit_id", "t"))
+    ds.close()
+
+
+def check_stats(o, want, n, n_lights):
+    hits = int((want["seg_hit_id"] >= 0).sum())
+    assert o["stats"]["primary_rays"] == n and o["stats"]["hit_rays"] == hits and o["stats"]["shadow_rays"] == hits * n_lights, o["stats"]
+
+
+# ---- closest hit and occlusion --------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("seed", [1, 2, 3])
+def test_closest_hit_and_occlusion(srt, oracle, seed):
+    flat, (rays, cls) = adv.scene(seed)[0], adv.rays(seed)
+    c = adv.candidates(oracle, seed)
+    hit, t = rr.closest(c)
+    n = rays.shape[0]
+    want = {"hit_id": hit, "t": t, "bary": rr.want_bary(oracle, flat, rays, hit, t)}
+    skip = np.where(hit >= 0, flat.tri_obj[np.maximum(hit, 0)], -1).astype(np.int32)
+    occ, occ_all = rr.occluded(c, flat, None, skip), rr.occluded(c, flat, None, None)
+    assert 0 < occ.sum() < occ_all.sum() < n
+    ok = adv.finite(rays)
+    fin = np.ascontiguousarray(rays[ok])
+    oh, ot, n_node, n_tri = ts.oracle_rays(oracle, flat, fin)
+    with device_scene(srt, oracle, seed) as ds:
+        same(ds.trace_rays(rays, want=("hit_id", "t")), want, "plain")
+        o = ds.trace_rays(rays)
+        same(o, want, "with bary")
+        assert o["stats"]["primary_rays"] == n and o["stats"]["hit_rays"] == int((hit >= 0).sum())
+        same(ds.trace_rays(rays, count=True), want, "counting")
+        o = ds.trace_rays(fin, count=True)
+        same(o, {"hit_id": oh, "t": ot}, "counting, the finite rays")
+        assert (o["stats"]["node_tests_primary"], o["stats"]["tri_tests_primary"]) == (n_node, n_tri), (o["stats"], n_node, n_tri)
+        assert np.array_equal(ds.occluded(rays, skip), occ) and np.array_equal(ds.occluded(rays), occ_all)
+        perm = np.random.default_rng(seed).permutation(n)
+        pr = np.ascontiguousarray(rays[perm])
+        assert np.array_equal(ds.occluded(pr, skip[perm]), occ[perm]) and np.array_equal(ds.occluded(pr), occ_all[perm])
+        same(ds.trace_rays(pr), {k: v[perm] for k, v in want.items()}, "permuted")
+
+
+# ---- intervals and the K nearest ------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("seed", [1, 2, 3])
+def test_intervals_and_k_nearest(srt, oracle, seed):
+    flat, (rays, cls) = adv.scene(seed)[0], adv.rays(seed)
+    c = adv.candidates(oracle, seed)
+    hit0, _ = rr.closest(c)
+    tr, kind = adv.intervals(oracle, seed)
+    hit, t = rr.closest(c, tr)
+    skip = np.where(hit0 >= 0, flat.tri_obj[np.maximum(hit0, 0)], -1).astype(np.int32)
+    with device_scene(srt, oracle, seed) as ds:
+        ranged = ds.trace_rays(rays, t_range=tr)
+        same(ranged, {"hit_id": hit, "t": t, "bary": rr.want_bary(oracle, flat, rays, hit, t)}, "interval batch")
+        assert np.array_equal(ds.occluded(rays, skip, t_range=tr), rr.occluded(c, flat, tr, skip))
+        assert np.array_equal(ds.occluded(rays, t_range=tr), rr.occluded(c, flat, tr, None))
+        for bounds, base in ((None, ds.trace_rays(rays)), (tr, ranged)):
+            for k in (1, 4, 16):
+                n_hits, mh, mt = rm.multi(c, k, bounds)
+                o = ds.trace_rays_multi(rays, k, t_range=bounds)
+                what = f"k {k}, {'no ' if bounds is None else ''}intervals"
+                same(o, {"n_hits": n_hits, "hit_id": mh, "t": mt, "bary": rm.multi_bary(oracle, flat, rays, mh, mt)}, what)
+                # column 0 is the closest-hit call's row; the count is the full one; equal t is ordered by id
+                same({"hit_id": o["hit_id"][:, 0], "t": o["t"][:, 0], "bary": o["bary"][:, 0]}, base, what + ", column 0", ("hit_id", "t", "bary"))
+                assert np.array_equal(np.minimum(o["n_hits"], k), (o["hit_id"] >= 0).sum(axis=1))
+                tie = (o["hit_id"][:, 1:] >= 0) & (bits(o["t"][:, 1:] + np.float32(0.0)) == bits(o["t"][:, :-1] + np.float32(0.0)))
+                assert (o["hit_id"][:, 1:][tie] > o["hit_id"][:, :-1][tie]).all(), what
+                if k == 16:
+                    print(f"seed {seed}, {what}: (groups of equal t on one ray, members of the deepest)", rm.equal_t_groups(c, bounds))
+
+
+# ---- shading and the surface ------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("seed", adv.SEEDS)
+def test_shading_and_surface(srt, oracle, seed):
+    flat, (rays, cls) = adv.scene(seed)[0], adv.rays(seed)
+    c = adv.candidates(oracle, seed)
+    hit, t = rr.closest(c)
+    second = np.stack([rr.next_up(np.where(hit >= 0, t, np.float32(1.0))), np.full(t.shape, np.inf, np.float32)], axis=1).astype(np.float32)
+    hit2, t2 = rr.closest(c, second)
+    assert (hit2 >= 0).sum() >= 50
+    keys = ("hit_id", "t", "rgb_linear", "rgb8")
+    with device_scene(srt, oracle, seed) as ds:
+        for flags in ((0, SMOOTH) if seed == 4 else (0,)):
+            for nl in (1, 9):
+                lights = adv.lights(seed, nl)
+                o = ds.shade_rays(rays, sq.shade_params(lights, flags=flags), count=(nl == 9))
+                same(o, dict(zip(keys, sr.shade(oracle, flat, rays, lights, flags=flags))), f"shade_rays, {nl} lights, flags {flags}")
+                assert o["stats"]["hit_rays"] == int((hit >= 0).sum()) and o["stats"]["shadow_rays"] == int((hit >= 0).sum()) * nl
+            lights = adv.lights(seed, 3)
+            same(ds.shade_rays(rays, sq.shade_params(lights, flags=flags), t_range=second), dict(zip(keys, sr.shade(oracle, flat, rays, lights, t_range=second, flags=flags))),
+                 f"shade_rays, second hits, flags {flags}")
+        for smooth in ((False, True) if seed == 4 else (False,)):
+            want = sf.surface(oracle, flat, rays, hit, t, smooth)
+            same(ds.surface_rays(rays, smooth=smooth), dict(want, hit_id=hit, t=t), f"surface_rays, smooth {smooth}")
+            same(ds.surface_hits(rays, hit, t, smooth=smooth), want, f"surface_hits, smooth {smooth}")
+            same(ds.surface_rays(rays, smooth=smooth, t_range=second), dict(sf.surface(oracle, flat, rays, hit2, t2, smooth), hit_id=hit2, t=t2), f"surface_rays, second hits, smooth {smooth}")
+
+
+# ---- paths ----------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("seed", adv.SEEDS)
+def test_paths(srt, oracle, seed):
+    flat, (rays, cls) = adv.scene(seed)[0], adv.rays(seed)
+    n = rays.shape[0]
+    lights = adv.lights(seed, adv.N_LIGHTS)
+    low, carriers = adv.lower_copy_objects(seed)
+    table, hide = vr.hidden(flat, *low)
+    glass, mirror = adv.glass_ior(seed), np.zeros(flat.n_objects, np.float32)
+    memo = adv.memo(oracle, seed)
+    cases = [("plain", None, None, None), ("self-shadowing", sh.SELF, None, None), ("ended shadow rays", sh.ENDED, None, None),
+             ("hidden from primary rays", None, (hide, ALL, ALL), None), ("hidden from bounce rays", None, (ALL, hide, ALL), None),
+             ("hidden from shadow rays", None, (ALL, ALL, hide), None), ("glass", None, None, glass), ("masks, rule and glass", sh.SELF, (hide, hide, hide), glass)]
+    with device_scene(srt, oracle, seed) as ds:
+        ds.set_object_masks(table)
+        for flags in ((0, SMOOTH) if seed == 4 else (0,)):
+            colours = vr.Colours(oracle, flat, lights, flags)
+            plain = None
+            for what, rule, vis, ior in cases:
+                want = rf.shade_paths(oracle, flat, rays, lights, adv.DEPTH, mirror if ior is None else ior, adv.REFLECTANCE, TMIN, flags=flags, rule=rule, vis=vis,
+                                      obj_mask=table if vis is not None else None, colours=colours, cands=memo)
+                plain = want if plain is None else plain
+                if what != "plain":
+                    assert any(not np.array_equal(bits(want[k]), bits(plain[k])) for k in ("seg_hit_id", "seg_rgb_linear", "rgb_linear")), f"{what} changes nothing"
+                for count in (False, True):
+                    o = ds.shade_paths(rays, sq.shade_params(lights), adv.DEPTH, adv.REFLECTANCE, TMIN, count=count, smooth=bool(flags), shadow=rule, visibility=vis, ior=ior)
+                    sp.assert_same(o, want, f"seed {seed}, {what}, flags {flags}, counting {count}")
+                    if count:
+                        check_stats(o, want, n, adv.N_LIGHTS)
+
+
+@pytest.mark.parametrize("seed", [1, 2, 3])
+def test_frames(srt, oracle, seed):
+    """srt_render_paths_refract on a 32 x 24 frame of the adversarial test's own camera (the origin, focal 400 at 161 columns), the copies'
+    carriers glass: whole and as one share of a row deal, at spp 1 and 4."""
+    flat = adv.scene(seed)[0]
+    lights = adv.lights(seed, 1)                          # one light: the yardstick renders one tiny frame per hit, light and sub-sample
+    glass = adv.glass_ior(seed)
+    w, h, focal = 32, 24, adv.FOCAL * 32 / adv.W
+    with device_scene(srt, oracle, seed) as ds:
+        for spp in (1, 4):
+            p = abi.make_params(w, h, lights, focal=focal, spp=spp)
+            want = rpr.flat_rows(rf.render_paths(oracle, flat, p, adv.DEPTH, glass, adv.REFLECTANCE, TMIN))
+            assert (want["seg_hit_id"][2] >= 0).sum() >= 100 and (want["seg_hit_id"][1] < 0).sum() >= 50      # (the scene fills this camera: no pixel misses segment 0)
+            o = ds.render_paths(p, adv.DEPTH, adv.REFLECTANCE, TMIN, count=True, ior=glass)
+            sp.assert_same(rpr.flat_rows(o), want, f"seed {seed}, spp {spp}, whole")
+            assert o["stats"]["primary_rays"] == w * h * spp
+            share = abi.make_params(w, h, lights, focal=focal, spp=spp, block_rows=8, block_first=1, block_stride=3)
+            own = rpr.owned(share).reshape(-1)
+            got = rpr.flat_rows(ds.render_paths(share, adv.DEPTH, adv.REFLECTANCE, TMIN, fill=7, ior=glass))
+            mine = np.flatnonzero(own >= 0)
+            assert mine.size == 8 * w
+            cut = lambda d, sel: {k: (v[sel] if k in ("rgb_linear", "rgb8") else v[:, sel]) for k, v in d.items() if k in sp.ALL_KEYS}
+            sp.assert_same(cut(got, mine), cut(want, own[mine]), f"seed {seed}, spp {spp}, share 1 of 3")
+            for k, v in cut(got, np.flatnonzero(own < 0)).items():
+                assert (v == 7).all(), ("padding written", k)

@@ -26,6 +26,7 @@ import shadow_rule_ref as sh
 import surface_ref as sf
 import tree_shapes as ts
 import visibility_ref as vr
+from adversarial import with_vertex_normals
 from simple_raytracer_amd import abi
 
 gpu = pytest.mark.gpu
@@ -176,20 +177,6 @@ def test_identities(srt):
 
 
 # ---- 4. the chain, on a batch too big for the yardstick ------------------------------------------------------------------------------
-def with_vertex_normals(flat):
-    """The scene with vertex normals (it has none): at every vertex the normalised sum of the face normals of the triangles that share
-    its position."""
-    pts = np.asarray(flat.tri_points, np.float32).reshape(-1, 3, 4)[..., :3].reshape(-1, 3)
-    fn = np.nan_to_num(sf.face_normal(np.asarray(flat.tri_points, np.float32).reshape(-1, 12)).astype(np.float64))
-    _, inv = np.unique(pts, axis=0, return_inverse=True)
-    inv = inv.reshape(-1)
-    acc = np.zeros((int(inv.max()) + 1, 3), np.float64)
-    np.add.at(acc, inv, np.repeat(fn, 3, axis=0))
-    length = np.linalg.norm(acc, axis=1, keepdims=True)
-    vn = np.where(length > 0, acc / np.maximum(length, 1e-30), np.float64([0.0, 0.0, 1.0]))
-    return dataclasses.replace(flat, tri_normals=np.ascontiguousarray(vn[inv].reshape(-1, 9), np.float32))
-
-
 def chain(ds, rays, params, depth, ior, reflectance, smooth, count):
     """The chain of existing host calls the one launch replaces: per segment shade_rays(t_range=...) and surface_rays' obj, normal and
     bounce on the LIVE rays only, the next direction refract_ref.refract_dir for glass hits and the bounce otherwise; the mix by

@@ -40,31 +40,7 @@ def test_refract_dir_obeys_snells_law():
     assert np.array_equal(bits(r[tir]), bits(sf.reflect(d[tir], N[tir])))
     ok = k >= np.float32(1e-3)
     assert ok.sum() > m // 2
-    D, NN, R, n64 = d[ok].astype(np.float64), N[ok].astype(np.float64), r[ok].astype(np.float64), n[ok].astype(np.float64)
-    NN = unit(NN)
-    I = unit(D)
-    cos_i = (I * NN).sum(axis=1)
-    ent = cos_i < 0
-    assert np.array_equal(ent, entering[ok])
-    eta = np.where(ent, 1.0 / n64, n64)
-    Nf = np.where(ent[:, None], NN, -NN)
-    Rh = unit(R)
-    sin_i, sin_t = np.linalg.norm(np.cross(I, NN), axis=1), np.linalg.norm(np.cross(Rh, NN), axis=1)
-    tol = 1e-4
-    assert np.abs(sin_t - eta * sin_i).max() <= tol, "Snell's law"
-    # in the plane of d and N: no component along I x N (where that axis exists), and on the far side of the tangent from I's
-    axis = np.cross(I, NN)
-    has = sin_i > 1e-3
-    assert np.abs((Rh[has] * unit(axis[has])).sum(axis=1)).max() <= tol, "r leaves the plane of d and N"
-    tang = I - cos_i[:, None] * NN
-    assert ((Rh * tang).sum(axis=1)[has] > 0).all(), "r bends to the wrong side of the normal"
-    assert ((R * Nf).sum(axis=1) < 0).all(), "r does not go through the surface"
-    len_r, len_d = np.linalg.norm(R, axis=1), np.linalg.norm(D, axis=1)
-    assert (np.abs(len_r - len_d) / len_d).max() <= tol, "|r| is not |d|"
-    # the answer itself: Snell's direction built in float64 from the angles
-    cos_t = np.sqrt(1.0 - (eta * sin_i) ** 2)
-    want = eta[:, None] * tang - cos_t[:, None] * Nf
-    assert np.abs(Rh - unit(want)).max() <= tol
+    rf.assert_snell(d[ok], N[ok], r[ok], n[ok], entering[ok])
 
 
 # (enter, leave, tir) at segments 1, 2, 3 of the cases' primary walks, as counted when the cases were chosen
