@@ -1717,35 +1717,55 @@ static int query_prologue(srt_scene* s, uint32_t n, hipStream_t stream, const sr
     return SRT_OK;
 }
 
-// d_t_range: the rays' t intervals (srt_*_range), or null: nothing bounds t, and the kernels are the ones without the interval.
-// count_hits: the host entry point wants hit_rays also without SRT_FLAG_COUNT_WORK
+extern "C++" {
+// Which build of a kernel family a call launches.  BUILDS_n(family) lists the 2^n builds of a family of n flags in the order of build_index:
+// bit k of the index is the family's template argument k, the first argument being bit 0.  What follows the family's name goes behind
+// the flags (the slot count of k_query_multi).  A table is a std::array over such a list, so a family is named once where it is chosen from.
+#define BUILDS_1(K, ...) &K<false __VA_ARGS__>, &K<true __VA_ARGS__>
+#define BUILDS_2(K, ...) BUILDS_1(K, , false __VA_ARGS__), BUILDS_1(K, , true __VA_ARGS__)
+#define BUILDS_3(K, ...) BUILDS_2(K, , false __VA_ARGS__), BUILDS_2(K, , true __VA_ARGS__)
+#define BUILDS_4(K, ...) BUILDS_3(K, , false __VA_ARGS__), BUILDS_3(K, , true __VA_ARGS__)
+template <typename... B>
+static inline size_t build_index(B... flag) {      // the flags in the order of the family's template arguments; a pointer: whether it is there
+    size_t i = 0, bit = 1;
+    ((i |= flag ? bit : 0, bit <<= 1), ...);
+    return i;
+}
+
+// One launch of workgroups of 256 lanes, and whether it was taken
+template <typename... P, typename... A>
+static int launch_query(void (*kernel)(P...), dim3 grid, hipStream_t stream, const A&... args) {
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, stream, args...);
+    HIP_TRY(hipGetLastError());
+    return SRT_OK;
+}
+}      // extern "C++"
+
 // The masks of a masked call as its kernels take them: the scene's table as it stands in the records now, the call's per-ray masks, or
 // the three masks per ray kind.
 static inline QueryMask query_mask(const srt_scene* s, const uint32_t* d_ray_mask) { return QueryMask{ s->rec->d_obj_mask, d_ray_mask, ~0u, ~0u, ~0u }; }
 static inline QueryMask query_mask(const srt_scene* s, const srt_visibility* v) { return QueryMask{ s->rec->d_obj_mask, nullptr, v->primary, v->bounce, v->shadow }; }
-struct RayMask { const uint32_t* d; };      // the per-ray masks of srt_*_masked (d may be NULL: all ones); a NULL RayMask*: not a masked call
+// Whether a closest-hit or occlusion call is srt_*_masked, and its per-ray masks (NULL: all ones): host words in a host form, device words
+// in a device form.
+struct RayMask { bool masked = false; const uint32_t* words = nullptr; };
 
-// mask: NULL launches k_query_closest as ever; otherwise the MASK build of the same choice of COUNT and BARY
+// d_t_range: the rays' t intervals (srt_*_range), or null: nothing bounds t, and the kernels are the ones without the interval.
+// count_hits: the host entry point wants hit_rays also without SRT_FLAG_COUNT_WORK
+// mask: a call that is not masked launches k_query_closest; a masked one the MASK build of the same choice of COUNT and BARY
 static int trace_rays_device_impl(srt_scene* s, uint32_t n, const float* d_rays, const float* d_t_range, uint32_t flags, hipStream_t stream, int32_t* d_hit_id,
-                                  float* d_t, float* d_bary, bool count_hits, const RayMask* mask = nullptr) {
+                                  float* d_t, float* d_bary, bool count_hits, const RayMask& mask) {
     SRT_TRY(check_query(s, n, d_rays, flags));
     if (!n) return SRT_OK;
     const bool count = (flags & SRT_FLAG_COUNT_WORK) != 0;
     QueryLaunch q;
     SRT_TRY(query_prologue(s, n, stream, nullptr, count || count_hits, &q));
-    static const decltype(&k_query_closest<false, false, false>) builds[8] = {
-        &k_query_closest<false, false, false>, &k_query_closest<false, true, false>, &k_query_closest<true, false, false>, &k_query_closest<true, true, false>,
-        &k_query_closest<false, false, true>,  &k_query_closest<false, true, true>,  &k_query_closest<true, false, true>,  &k_query_closest<true, true, true> };
-    static const decltype(&k_query_closest_masked<false, false>) masked_builds[4] = {
-        &k_query_closest_masked<false, false>, &k_query_closest_masked<false, true>, &k_query_closest_masked<true, false>, &k_query_closest_masked<true, true> };
-    if (mask)
-        hipLaunchKernelGGL(masked_builds[(count ? 2 : 0) | (d_bary ? 1 : 0)], q.grid, dim3(256), 0, q.stream, s->dev, n, d_rays, rays_wide(d_rays), d_hit_id, d_t, d_bary, q.ctr,
-                           query_range(d_t_range), query_mask(s, mask->d));
-    else
-        hipLaunchKernelGGL(builds[(d_t_range ? 4 : 0) | (count ? 2 : 0) | (d_bary ? 1 : 0)], q.grid, dim3(256), 0, q.stream, s->dev, n, d_rays, rays_wide(d_rays), d_hit_id, d_t,
-                           d_bary, q.ctr, query_range(d_t_range));
-    HIP_TRY(hipGetLastError());
-    return SRT_OK;
+    static const std::array builds = { BUILDS_3(k_query_closest) };
+    static const std::array masked_builds = { BUILDS_2(k_query_closest_masked) };
+    if (mask.masked)
+        return launch_query(masked_builds[build_index(count, d_bary)], q.grid, q.stream, s->dev, n, d_rays, rays_wide(d_rays), d_hit_id, d_t, d_bary, q.ctr,
+                            query_range(d_t_range), query_mask(s, mask.words));
+    return launch_query(builds[build_index(count, d_bary, d_t_range)], q.grid, q.stream, s->dev, n, d_rays, rays_wide(d_rays), d_hit_id, d_t, d_bary, q.ctr,
+                        query_range(d_t_range));
 }
 
 // srt_trace_rays_multi: the k nearest hits per ray in one walk (k_query_multi); the build reserves 4, 8 or 16 slots a ray
@@ -1762,32 +1782,25 @@ static int trace_rays_multi_device_impl(srt_scene* s, uint32_t n, const float* d
     const bool count = (flags & SRT_FLAG_COUNT_WORK) != 0;
     QueryLaunch q;
     SRT_TRY(query_prologue(s, n, stream, nullptr, count || count_hits, &q));
-    static const decltype(&k_query_multi<false, false, 4>) builds[12] = {
-        &k_query_multi<false, false, 4>,  &k_query_multi<false, true, 4>,  &k_query_multi<true, false, 4>,  &k_query_multi<true, true, 4>,
-        &k_query_multi<false, false, 8>,  &k_query_multi<false, true, 8>,  &k_query_multi<true, false, 8>,  &k_query_multi<true, true, 8>,
-        &k_query_multi<false, false, 16>, &k_query_multi<false, true, 16>, &k_query_multi<true, false, 16>, &k_query_multi<true, true, 16> };
+    static const std::array builds = { std::array{ BUILDS_2(k_query_multi, , 4) }, std::array{ BUILDS_2(k_query_multi, , 8) }, std::array{ BUILDS_2(k_query_multi, , 16) } };
     static_assert(SRT_MULTI_HIT_MAX == 16, "the largest bucket holds SRT_MULTI_HIT_MAX slots");
     const int bucket = k <= 4 ? 0 : k <= 8 ? 1 : 2;
-    hipLaunchKernelGGL(builds[bucket * 4 + (count ? 2 : 0) + (d_bary ? 1 : 0)], q.grid, dim3(256), 0, q.stream, s->dev, n, d_rays, rays_wide(d_rays), query_range(d_t_range),
-                       k, d_n_hits, d_hit_id, d_t, d_bary, q.ctr);
-    HIP_TRY(hipGetLastError());
-    return SRT_OK;
+    return launch_query(builds[bucket][build_index(count, d_bary)], q.grid, q.stream, s->dev, n, d_rays, rays_wide(d_rays), query_range(d_t_range), k, d_n_hits,
+                        d_hit_id, d_t, d_bary, q.ctr);
 }
 
+// mask: a call that is not masked launches k_query_any, with or without the interval; a masked one k_query_any_masked
 static int occluded_device_impl(srt_scene* s, uint32_t n, const float* d_rays, const float* d_t_range, const int32_t* d_skip_obj, hipStream_t stream,
-                                uint8_t* d_occluded, const RayMask* mask = nullptr) {
+                                uint8_t* d_occluded, const RayMask& mask) {
     SRT_TRY(check_query(s, n, d_rays, 0));
     if (!n || !d_occluded) return SRT_OK;
     QueryLaunch q;
     SRT_TRY(query_prologue(s, n, stream, nullptr, false, &q));
-    if (mask)
-        hipLaunchKernelGGL(&k_query_any_masked, q.grid, dim3(256), 0, q.stream, s->dev, n, d_rays, rays_wide(d_rays), d_skip_obj, d_occluded, query_range(d_t_range),
-                           query_mask(s, mask->d));
-    else
-        hipLaunchKernelGGL(d_t_range ? &k_query_any<true> : &k_query_any<false>, q.grid, dim3(256), 0, q.stream, s->dev, n, d_rays, rays_wide(d_rays), d_skip_obj, d_occluded,
-                           query_range(d_t_range));
-    HIP_TRY(hipGetLastError());
-    return SRT_OK;
+    static const std::array builds = { BUILDS_1(k_query_any) };
+    if (mask.masked)
+        return launch_query(&k_query_any_masked, q.grid, q.stream, s->dev, n, d_rays, rays_wide(d_rays), d_skip_obj, d_occluded, query_range(d_t_range),
+                            query_mask(s, mask.words));
+    return launch_query(builds[build_index(d_t_range)], q.grid, q.stream, s->dev, n, d_rays, rays_wide(d_rays), d_skip_obj, d_occluded, query_range(d_t_range));
 }
 
 // What a shading kernel takes of the params (after query_prologue: the light table is the handle's device copy)
@@ -1809,17 +1822,10 @@ static int shade_rays_device_impl(srt_scene* s, uint32_t n, const float* d_rays,
     const bool count = (p->flags & SRT_FLAG_COUNT_WORK) != 0, smooth = (p->flags & SRT_FLAG_SMOOTH_NORMALS) != 0;
     QueryLaunch q;
     SRT_TRY(query_prologue(s, n, stream, p, count || count_hits, &q));
-    const QueryShade qs = query_shade(s, p);
     // the build: counting, smooth normals, and the integer-shininess pow where every object of the scene allows it (as k_shade_tile)
-    static const decltype(&k_query_shade<false, false, false, false>) builds[16] = {
-        &k_query_shade<false, false, false, false>, &k_query_shade<false, false, true, false>, &k_query_shade<false, true, false, false>, &k_query_shade<false, true, true, false>,
-        &k_query_shade<true, false, false, false>,  &k_query_shade<true, false, true, false>,  &k_query_shade<true, true, false, false>,  &k_query_shade<true, true, true, false>,
-        &k_query_shade<false, false, false, true>,  &k_query_shade<false, false, true, true>,  &k_query_shade<false, true, false, true>,  &k_query_shade<false, true, true, true>,
-        &k_query_shade<true, false, false, true>,   &k_query_shade<true, false, true, true>,   &k_query_shade<true, true, false, true>,   &k_query_shade<true, true, true, true> };
-    const auto k = builds[(d_t_range ? 8 : 0) | (count ? 4 : 0) | (smooth ? 2 : 0) | (s->rec->int_shin ? 1 : 0)];
-    hipLaunchKernelGGL(k, q.grid, dim3(256), 0, q.stream, s->dev, n, d_rays, rays_wide(d_rays), qs, d_hit_id, d_t, d_rgb_linear, d_rgb8, q.ctr, query_range(d_t_range));
-    HIP_TRY(hipGetLastError());
-    return SRT_OK;
+    static const std::array builds = { BUILDS_4(k_query_shade) };
+    return launch_query(builds[build_index(count, smooth, s->rec->int_shin, d_t_range)], q.grid, q.stream, s->dev, n, d_rays, rays_wide(d_rays), query_shade(s, p),
+                        d_hit_id, d_t, d_rgb_linear, d_rgb8, q.ctr, query_range(d_t_range));
 }
 
 // srt_shade_paths: up to path->depth mirror bounces per ray, shaded and mixed, one launch (k_query_path)
@@ -1832,59 +1838,56 @@ static int check_paths(const srt_scene* s, uint32_t n, const float* rays, const 
 static inline bool paths_wanted(const float* rgb_linear, const uint8_t* rgb8, const srt_path_out* o) {
     return rgb_linear || rgb8 || (o && (o->hit_id || o->t || o->obj || o->rgb_linear || o->rays));
 }
-// The shadow rule of the srt_*_paths_shadow calls: NULL (the reference's rule, the existing kernels), or flags within SRT_SHADOW_SELF
-static inline int check_shadow(const srt_shadow_rule* r) { return (r && (r->flags & ~(uint32_t)SRT_SHADOW_SELF)) ? SRT_ERR_ARG : SRT_OK; }
-static inline ShadowRule shadow_rule(const srt_shadow_rule* r) { return ShadowRule{ r->t_min, r->t_max, (r->flags & SRT_SHADOW_SELF) ? 1u : 0u }; }
 
+// What a path call may bring beyond its rays, each part NULL where the entry point has none or its caller passes none: the shadow rule
+// of srt_*_paths_shadow, the masks per ray kind of srt_*_paths_masked, the refraction table of srt_*_paths_refract.
+struct PathOptions { const srt_shadow_rule* shadow = nullptr; const srt_visibility* vis = nullptr; const srt_refraction* refr = nullptr; };
+// A rule's flags lie within SRT_SHADOW_SELF, a table's are 0
+static inline int check_path_options(const PathOptions& o) {
+    if (o.refr && o.refr->flags) return SRT_ERR_ARG;
+    if (o.shadow && (o.shadow->flags & ~(uint32_t)SRT_SHADOW_SELF)) return SRT_ERR_ARG;
+    return SRT_OK;
+}
+static inline ShadowRule shadow_rule(const srt_shadow_rule* r) { return ShadowRule{ r->t_min, r->t_max, (r->flags & SRT_SHADOW_SELF) ? 1u : 0u }; }
 // The rule a masked call without one runs under: the reference's, stated as a rule -- no bound, the hit's object skipped
 static inline ShadowRule shadow_rule_or_reference(const srt_shadow_rule* r) { return r ? shadow_rule(r) : ShadowRule{ std::nanf(""), std::nanf(""), 0u }; }
-
-// The refraction table of the srt_*_paths_refract calls: NULL, or flags 0; without a table (NULL, or ior NULL) the call is the _masked call
-static inline int check_refraction(const srt_refraction* r) { return (r && r->flags) ? SRT_ERR_ARG : SRT_OK; }
-static inline const float* refraction_table(const srt_refraction* r) { return r ? r->ior : nullptr; }
 // The masks a refracting call without an srt_visibility runs under: every ray kind sees every object, and the scene's table is not read
 static inline QueryMask query_mask_or_all(const srt_scene* s, const srt_visibility* v) { return v ? query_mask(s, v) : QueryMask{ nullptr, nullptr, ~0u, ~0u, ~0u }; }
 
-// shadow: NULL launches k_query_path as ever; a rule launches the k_query_path_shadow build of the same choice
-// vis: NULL changes nothing; otherwise the k_query_path_masked build of the same choice, with or without a rule
-// refr: without a table nothing changes; otherwise the k_query_path_refract build of the same choice, with or without a rule or masks
+extern "C++" {
+// The four families of a path kernel, each a table over (COUNT, SMOOTH, INT_SHIN), and the one launch of a path call.  The family: with a
+// refraction table (refr and refr->ior both there) the REFRACT one, under the caller's rule or the reference's and the caller's masks or
+// all ones; else with masks the MASK one, under the caller's rule or the reference's; else with a rule the SHADOW one; else the family
+// that takes none of the three -- the kernel srt_shade_paths / srt_render_paths launched before any of them existed.  `lead`: the
+// arguments all four take.
+template <typename P, typename S, typename M, typename R>
+struct PathBuilds { std::array<P, 8> plain; std::array<S, 8> shadow; std::array<M, 8> masked; std::array<R, 8> refract; };
+template <typename P, typename S, typename M, typename R>
+static PathBuilds<P, S, M, R> path_builds(const std::array<P, 8>& plain, const std::array<S, 8>& shadow, const std::array<M, 8>& masked, const std::array<R, 8>& refract) {
+    return PathBuilds<P, S, M, R>{ plain, shadow, masked, refract };
+}
+template <typename Builds, typename... A>
+static int launch_paths(const Builds& builds, const srt_scene* s, const srt_params* p, const PathOptions& o, dim3 grid, hipStream_t stream, const A&... lead) {
+    const size_t build = build_index((p->flags & SRT_FLAG_COUNT_WORK) != 0, (p->flags & SRT_FLAG_SMOOTH_NORMALS) != 0, s->rec->int_shin);
+    if (const float* d_ior = o.refr ? o.refr->ior : nullptr)
+        return launch_query(builds.refract[build], grid, stream, lead..., shadow_rule_or_reference(o.shadow), query_mask_or_all(s, o.vis), d_ior);
+    if (o.vis) return launch_query(builds.masked[build], grid, stream, lead..., shadow_rule_or_reference(o.shadow), query_mask(s, o.vis));
+    if (o.shadow) return launch_query(builds.shadow[build], grid, stream, lead..., shadow_rule(o.shadow));
+    return launch_query(builds.plain[build], grid, stream, lead...);
+}
+}      // extern "C++"
+
 static int shade_paths_device_impl(srt_scene* s, uint32_t n, const float* d_rays, const float* d_t_range, const srt_params* p, const srt_path_desc* path,
-                                   const srt_shadow_rule* shadow, hipStream_t stream, float* d_rgb_linear, uint8_t* d_rgb8, const srt_path_out* seg, bool count_hits,
-                                   const srt_visibility* vis = nullptr, const srt_refraction* refr = nullptr) {
-    SRT_TRY(check_refraction(refr));
-    SRT_TRY(check_shadow(shadow));
+                                   const PathOptions& opt, hipStream_t stream, float* d_rgb_linear, uint8_t* d_rgb8, const srt_path_out* seg, bool count_hits) {
+    SRT_TRY(check_path_options(opt));
     SRT_TRY(check_paths(s, n, d_rays, p, path));
     if (!n || (!count_hits && !paths_wanted(d_rgb_linear, d_rgb8, seg))) return SRT_OK;
-    const bool count = (p->flags & SRT_FLAG_COUNT_WORK) != 0, smooth = (p->flags & SRT_FLAG_SMOOTH_NORMALS) != 0;
     QueryLaunch q;
-    SRT_TRY(query_prologue(s, n, stream, p, count || count_hits, &q));
-    static const decltype(&k_query_path<false, false, false>) builds[8] = {
-        &k_query_path<false, false, false>, &k_query_path<false, false, true>, &k_query_path<false, true, false>, &k_query_path<false, true, true>,
-        &k_query_path<true, false, false>,  &k_query_path<true, false, true>,  &k_query_path<true, true, false>,  &k_query_path<true, true, true> };
-    static const decltype(&k_query_path_shadow<false, false, false>) shadow_builds[8] = {
-        &k_query_path_shadow<false, false, false>, &k_query_path_shadow<false, false, true>, &k_query_path_shadow<false, true, false>, &k_query_path_shadow<false, true, true>,
-        &k_query_path_shadow<true, false, false>,  &k_query_path_shadow<true, false, true>,  &k_query_path_shadow<true, true, false>,  &k_query_path_shadow<true, true, true> };
-    const int build = (count ? 4 : 0) | (smooth ? 2 : 0) | (s->rec->int_shin ? 1 : 0);
-    static const decltype(&k_query_path_masked<false, false, false>) masked_builds[8] = {
-        &k_query_path_masked<false, false, false>, &k_query_path_masked<false, false, true>, &k_query_path_masked<false, true, false>, &k_query_path_masked<false, true, true>,
-        &k_query_path_masked<true, false, false>,  &k_query_path_masked<true, false, true>,  &k_query_path_masked<true, true, false>,  &k_query_path_masked<true, true, true> };
-    static const decltype(&k_query_path_refract<false, false, false>) refract_builds[8] = {
-        &k_query_path_refract<false, false, false>, &k_query_path_refract<false, false, true>, &k_query_path_refract<false, true, false>, &k_query_path_refract<false, true, true>,
-        &k_query_path_refract<true, false, false>,  &k_query_path_refract<true, false, true>,  &k_query_path_refract<true, true, false>,  &k_query_path_refract<true, true, true> };
-    if (const float* d_ior = refraction_table(refr))
-        hipLaunchKernelGGL(refract_builds[build], q.grid, dim3(256), 0, q.stream, s->dev, n, d_rays, rays_wide(d_rays), query_shade(s, p), query_range(d_t_range), *path,
-                           d_rgb_linear, d_rgb8, seg ? *seg : srt_path_out{}, q.ctr, shadow_rule_or_reference(shadow), query_mask_or_all(s, vis), d_ior);
-    else if (vis)
-        hipLaunchKernelGGL(masked_builds[build], q.grid, dim3(256), 0, q.stream, s->dev, n, d_rays, rays_wide(d_rays), query_shade(s, p), query_range(d_t_range), *path,
-                           d_rgb_linear, d_rgb8, seg ? *seg : srt_path_out{}, q.ctr, shadow_rule_or_reference(shadow), query_mask(s, vis));
-    else if (shadow)
-        hipLaunchKernelGGL(shadow_builds[build], q.grid, dim3(256), 0, q.stream, s->dev, n, d_rays, rays_wide(d_rays), query_shade(s, p), query_range(d_t_range), *path,
-                           d_rgb_linear, d_rgb8, seg ? *seg : srt_path_out{}, q.ctr, shadow_rule(shadow));
-    else
-        hipLaunchKernelGGL(builds[build], q.grid, dim3(256), 0, q.stream, s->dev, n, d_rays, rays_wide(d_rays), query_shade(s, p), query_range(d_t_range), *path, d_rgb_linear,
-                           d_rgb8, seg ? *seg : srt_path_out{}, q.ctr);
-    HIP_TRY(hipGetLastError());
-    return SRT_OK;
+    SRT_TRY(query_prologue(s, n, stream, p, (p->flags & SRT_FLAG_COUNT_WORK) != 0 || count_hits, &q));
+    static const auto builds = path_builds(std::array{ BUILDS_3(k_query_path) }, std::array{ BUILDS_3(k_query_path_shadow) }, std::array{ BUILDS_3(k_query_path_masked) },
+                                           std::array{ BUILDS_3(k_query_path_refract) });
+    return launch_paths(builds, s, p, opt, q.grid, q.stream, s->dev, n, d_rays, rays_wide(d_rays), query_shade(s, p), query_range(d_t_range), *path, d_rgb_linear, d_rgb8,
+                        seg ? *seg : srt_path_out{}, q.ctr);
 }
 
 // srt_render_paths: mirror paths for the pixels of a frame, one launch (k_render_path).  A query-family call: the handle's query light table
@@ -1898,47 +1901,20 @@ static int check_render_paths(const srt_scene* s, const srt_params* p, const srt
     if ((uint64_t)srt_rows_owned(p) * srt_cols_owned(p) * (p->n_lights ? p->n_lights : 1) >= (1ull << 32)) return SRT_ERR_LIMIT;
     return SRT_OK;
 }
-static int render_paths_device_impl(srt_scene* s, const srt_params* p, const srt_path_desc* path, const srt_shadow_rule* shadow, hipStream_t stream, float* d_rgb_linear,
-                                    uint8_t* d_rgb8, const srt_path_out* seg, bool count_hits, const srt_visibility* vis = nullptr,
-                                    const srt_refraction* refr = nullptr) {
-    SRT_TRY(check_refraction(refr));
-    SRT_TRY(check_shadow(shadow));
+static int render_paths_device_impl(srt_scene* s, const srt_params* p, const srt_path_desc* path, const PathOptions& opt, hipStream_t stream, float* d_rgb_linear,
+                                    uint8_t* d_rgb8, const srt_path_out* seg, bool count_hits) {
+    SRT_TRY(check_path_options(opt));
     SRT_TRY(check_render_paths(s, p, path));
     const uint32_t rows = srt_rows_owned(p), wl = srt_cols_owned(p);
     if (!rows || !wl || (!count_hits && !paths_wanted(d_rgb_linear, d_rgb8, seg))) return SRT_OK;
-    const bool count = (p->flags & SRT_FLAG_COUNT_WORK) != 0, smooth = (p->flags & SRT_FLAG_SMOOTH_NORMALS) != 0;
     QueryLaunch q;
-    SRT_TRY(query_prologue(s, 0, stream, p, count || count_hits, &q));
+    SRT_TRY(query_prologue(s, 0, stream, p, (p->flags & SRT_FLAG_COUNT_WORK) != 0 || count_hits, &q));
     const DevParams dp = dev_params(s, p, FramePlan{}).hit;      // the frame's geometry only: the kernel takes lights and literals from QueryShade
-    static const decltype(&k_render_path<false, false, false>) builds[8] = {
-        &k_render_path<false, false, false>, &k_render_path<false, false, true>, &k_render_path<false, true, false>, &k_render_path<false, true, true>,
-        &k_render_path<true, false, false>,  &k_render_path<true, false, true>,  &k_render_path<true, true, false>,  &k_render_path<true, true, true> };
-    static const decltype(&k_render_path_shadow<false, false, false>) shadow_builds[8] = {
-        &k_render_path_shadow<false, false, false>, &k_render_path_shadow<false, false, true>, &k_render_path_shadow<false, true, false>, &k_render_path_shadow<false, true, true>,
-        &k_render_path_shadow<true, false, false>,  &k_render_path_shadow<true, false, true>,  &k_render_path_shadow<true, true, false>,  &k_render_path_shadow<true, true, true> };
-    const int build = (count ? 4 : 0) | (smooth ? 2 : 0) | (s->rec->int_shin ? 1 : 0);
     const uint32_t m = (uint32_t)std::lround(std::sqrt((double)p->spp));      // (m x m == spp: check_frame)
-    const dim3 grid((wl + 15) / 16, (rows + 15) / 16);
-    static const decltype(&k_render_path_masked<false, false, false>) masked_builds[8] = {
-        &k_render_path_masked<false, false, false>, &k_render_path_masked<false, false, true>, &k_render_path_masked<false, true, false>, &k_render_path_masked<false, true, true>,
-        &k_render_path_masked<true, false, false>,  &k_render_path_masked<true, false, true>,  &k_render_path_masked<true, true, false>,  &k_render_path_masked<true, true, true> };
-    static const decltype(&k_render_path_refract<false, false, false>) refract_builds[8] = {
-        &k_render_path_refract<false, false, false>, &k_render_path_refract<false, false, true>, &k_render_path_refract<false, true, false>, &k_render_path_refract<false, true, true>,
-        &k_render_path_refract<true, false, false>,  &k_render_path_refract<true, false, true>,  &k_render_path_refract<true, true, false>,  &k_render_path_refract<true, true, true> };
-    if (const float* d_ior = refraction_table(refr))
-        hipLaunchKernelGGL(refract_builds[build], grid, dim3(256), 0, q.stream, s->dev, dp, p->spp, m, query_shade(s, p), *path, d_rgb_linear, d_rgb8,
-                           seg ? *seg : srt_path_out{}, q.ctr, shadow_rule_or_reference(shadow), query_mask_or_all(s, vis), d_ior);
-    else if (vis)
-        hipLaunchKernelGGL(masked_builds[build], grid, dim3(256), 0, q.stream, s->dev, dp, p->spp, m, query_shade(s, p), *path, d_rgb_linear, d_rgb8,
-                           seg ? *seg : srt_path_out{}, q.ctr, shadow_rule_or_reference(shadow), query_mask(s, vis));
-    else if (shadow)
-        hipLaunchKernelGGL(shadow_builds[build], grid, dim3(256), 0, q.stream, s->dev, dp, p->spp, m, query_shade(s, p), *path, d_rgb_linear, d_rgb8,
-                           seg ? *seg : srt_path_out{}, q.ctr, shadow_rule(shadow));
-    else
-        hipLaunchKernelGGL(builds[build], grid, dim3(256), 0, q.stream, s->dev, dp, p->spp, m, query_shade(s, p), *path, d_rgb_linear, d_rgb8,
-                           seg ? *seg : srt_path_out{}, q.ctr);
-    HIP_TRY(hipGetLastError());
-    return SRT_OK;
+    static const auto builds = path_builds(std::array{ BUILDS_3(k_render_path) }, std::array{ BUILDS_3(k_render_path_shadow) }, std::array{ BUILDS_3(k_render_path_masked) },
+                                           std::array{ BUILDS_3(k_render_path_refract) });
+    return launch_paths(builds, s, p, opt, dim3((wl + 15) / 16, (rows + 15) / 16), q.stream, s->dev, dp, p->spp, m, query_shade(s, p), *path, d_rgb_linear, d_rgb8,
+                        seg ? *seg : srt_path_out{}, q.ctr);
 }
 
 // srt_surface_rays / srt_surface_hits: the surface under each hit and the mirrored ray (k_query_surface, k_query_surface_hits)
@@ -1953,18 +1929,14 @@ static int surface_rays_device_impl(srt_scene* s, uint32_t n, const float* d_ray
                                     float* d_t, const srt_surface_out* out, bool count_hits) {
     SRT_TRY(check_surface(s, n, d_rays, flags, SRT_FLAG_COUNT_WORK | SRT_FLAG_SMOOTH_NORMALS));
     // nothing of the surface wanted: the call is srt_trace_rays_range without bary, and launches its kernel
-    if (!surface_wanted(out)) return trace_rays_device_impl(s, n, d_rays, d_t_range, flags & SRT_FLAG_COUNT_WORK, stream, d_hit_id, d_t, nullptr, count_hits);
+    if (!surface_wanted(out)) return trace_rays_device_impl(s, n, d_rays, d_t_range, flags & SRT_FLAG_COUNT_WORK, stream, d_hit_id, d_t, nullptr, count_hits, RayMask{});
     if (!n) return SRT_OK;
     const bool count = (flags & SRT_FLAG_COUNT_WORK) != 0, smooth = (flags & SRT_FLAG_SMOOTH_NORMALS) != 0;
     QueryLaunch q;
     SRT_TRY(query_prologue(s, n, stream, nullptr, count || count_hits, &q));
-    static const decltype(&k_query_surface<false, false, false>) builds[8] = {
-        &k_query_surface<false, false, false>, &k_query_surface<false, true, false>, &k_query_surface<true, false, false>, &k_query_surface<true, true, false>,
-        &k_query_surface<false, false, true>,  &k_query_surface<false, true, true>,  &k_query_surface<true, false, true>,  &k_query_surface<true, true, true> };
-    hipLaunchKernelGGL(builds[(d_t_range ? 4 : 0) | (count ? 2 : 0) | (smooth ? 1 : 0)], q.grid, dim3(256), 0, q.stream, s->dev, n, d_rays, rays_wide(d_rays), d_hit_id, d_t,
-                       *out, q.ctr, query_range(d_t_range));
-    HIP_TRY(hipGetLastError());
-    return SRT_OK;
+    static const std::array builds = { BUILDS_3(k_query_surface) };
+    return launch_query(builds[build_index(count, smooth, d_t_range)], q.grid, q.stream, s->dev, n, d_rays, rays_wide(d_rays), d_hit_id, d_t, *out, q.ctr,
+                        query_range(d_t_range));
 }
 
 static int check_surface_hits(const srt_scene* s, uint32_t n, const float* rays, const int32_t* hit_id, const float* t, uint32_t flags) {
@@ -1977,96 +1949,72 @@ static int surface_hits_device_impl(srt_scene* s, uint32_t n, const float* d_ray
     if (!n || !surface_wanted(out)) return SRT_OK;
     QueryLaunch q;
     SRT_TRY(query_prologue(s, n, stream, nullptr, false, &q));
-    hipLaunchKernelGGL((flags & SRT_FLAG_SMOOTH_NORMALS) ? &k_query_surface_hits<true> : &k_query_surface_hits<false>, q.grid, dim3(256), 0, q.stream, s->dev, n, d_rays,
-                       rays_wide(d_rays), d_hit_id, d_t, *out);
-    HIP_TRY(hipGetLastError());
-    return SRT_OK;
+    static const std::array builds = { BUILDS_1(k_query_surface_hits) };
+    return launch_query(builds[build_index((flags & SRT_FLAG_SMOOTH_NORMALS) != 0)], q.grid, q.stream, s->dev, n, d_rays, rays_wide(d_rays), d_hit_id, d_t, *out);
 }
 
-// The host entry points: the caller's rays go through the pinned staging block (stage_acquire, as every update does) into the handle's
-// own ray buffer on the scene's stream, the device entry point runs behind them, the call waits and copies the results out.
-// skip_obj: n int32 a call brings -- the skipped objects of srt_occluded, the hit ids of srt_surface_hits; t_in: the t of those hits
-// refl: the n_refl floats of srt_shade_paths' reflectance table; ior: the n_ior floats of srt_shade_paths_refract's table, staged the same way
-static int stage_rays(srt_scene* s, uint32_t n, const float* rays, const float* t_range, const int32_t* skip_obj, const float* t_in, hipStream_t st,
-                      const float* refl = nullptr, uint32_t n_refl = 0, const float* ior = nullptr, uint32_t n_ior = 0) {
-    auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t o_rays = 0, o_skip = rays ? pad((size_t)n * 24) : 0, o_range = o_skip + (skip_obj ? pad((size_t)n * 4) : 0), o_tin = o_range + (t_range ? pad((size_t)n * 8) : 0),
-                 o_refl = o_tin + (t_in ? pad((size_t)n * 4) : 0), o_ior = o_refl + (refl ? pad((size_t)n_refl * 4) : 0), total = o_ior + (ior ? pad((size_t)n_ior * 4) : 0);
-    if (rays) SRT_TRY(grow(s, n, s->rq_rays));
-    if (skip_obj) SRT_TRY(grow(s, n, s->rq_skip));
-    if (t_range) SRT_TRY(grow(s, n, s->rq_range));
-    if (t_in) SRT_TRY(grow(s, n, s->rq_tin));
-    if (refl) SRT_TRY(grow(s, n_refl, s->rq_refl));
-    if (ior) SRT_TRY(grow(s, n_ior, s->rq_ior));
+// The host entry points: what the caller brings goes through the pinned staging block (stage_acquire, as every update does) into the
+// handle's own buffers on the scene's stream, the device entry point runs behind it, the call waits and copies the results out.
+// One array of a host call that comes from host memory: `bytes` from src to dst on the device.  src NULL, or no bytes: absent, and it
+// costs nothing.
+struct Staged { const void* src; size_t bytes; void* dst; };
+// Each item that is there gets a 256-byte aligned piece of the block, is copied into it and sent on from it
+static int stage_rays(srt_scene* s, const Staged* items, size_t n_items, hipStream_t st) {
+    size_t total = 0;
+    for (size_t i = 0; i < n_items; i++)
+        if (items[i].src) total += (items[i].bytes + 255) & ~(size_t)255;
     char* h = nullptr;
     SRT_TRY(stage_acquire(s, total, &h));
-    if (rays) {                                               // (srt_render_paths brings none: a frame's rays are made on the device)
-        std::memcpy(h + o_rays, rays, (size_t)n * 24);
-        HIP_TRY(hipMemcpyAsync(s->rq_rays, h + o_rays, (size_t)n * 24, hipMemcpyHostToDevice, st));
-    }
-    if (skip_obj) {
-        std::memcpy(h + o_skip, skip_obj, (size_t)n * 4);
-        HIP_TRY(hipMemcpyAsync(s->rq_skip, h + o_skip, (size_t)n * 4, hipMemcpyHostToDevice, st));
-    }
-    if (t_range) {
-        std::memcpy(h + o_range, t_range, (size_t)n * 8);
-        HIP_TRY(hipMemcpyAsync(s->rq_range, h + o_range, (size_t)n * 8, hipMemcpyHostToDevice, st));
-    }
-    if (t_in) {
-        std::memcpy(h + o_tin, t_in, (size_t)n * 4);
-        HIP_TRY(hipMemcpyAsync(s->rq_tin, h + o_tin, (size_t)n * 4, hipMemcpyHostToDevice, st));
-    }
-    if (refl && n_refl) {
-        std::memcpy(h + o_refl, refl, (size_t)n_refl * 4);
-        HIP_TRY(hipMemcpyAsync(s->rq_refl, h + o_refl, (size_t)n_refl * 4, hipMemcpyHostToDevice, st));
-    }
-    if (ior && n_ior) {
-        std::memcpy(h + o_ior, ior, (size_t)n_ior * 4);
-        HIP_TRY(hipMemcpyAsync(s->rq_ior, h + o_ior, (size_t)n_ior * 4, hipMemcpyHostToDevice, st));
+    for (size_t i = 0; i < n_items; i++) {
+        const Staged& it = items[i];
+        if (!it.src || !it.bytes) continue;
+        std::memcpy(h, it.src, it.bytes);
+        HIP_TRY(hipMemcpyAsync(it.dst, h, it.bytes, hipMemcpyHostToDevice, st));
+        h += (it.bytes + 255) & ~(size_t)255;
     }
     HIP_TRY(hipEventRecord(s->staged, st));
     return SRT_OK;
 }
 
-extern "C++" {
-// One result array of a host query: where the caller wants it (null: not wanted) and the handle's buffer for it.
+extern "C++" {      // (templates, down to the entry points)
+// One array of a host query and the handle's buffer for it, `count` units long: a result the caller wants at `out` (null: not wanted), or
+// what the call brings with it at `in` (null: not brought) -- the rays (srt_render_paths brings none: a frame's rays are made on the
+// device), their t intervals, the skipped objects of srt_occluded, the hits of srt_surface_hits, the per-ray masks of the masked calls,
+// the reflectance and refraction tables of the path calls.
 template <typename T, size_t K>
-struct QueryOut {
-    T* host; DevArray<T, K>& dev;
-    size_t per;                                               // units per ray (k of srt_trace_rays_multi, else 1)
-    static constexpr size_t unit = K * sizeof(T);             // bytes per unit
-    T* wanted() const { return host ? dev.p : nullptr; }      // (after the round trip has grown it)
+struct QueryArray {
+    const void* in; T* out; DevArray<T, K>& dev;
+    size_t count;
+    static constexpr size_t unit = K * sizeof(T);                          // bytes per unit
+    bool present() const { return in || out; }
+    T* on_device() const { return present() ? dev.p : nullptr; }           // (after the round trip has grown it)
+    Staged staged() const { return Staged{ in, count * unit, dev.p }; }
 };
 template <typename T, size_t K>
-static QueryOut<T, K> query_out(T* host, DevArray<T, K>& dev, size_t per = 1) { return QueryOut<T, K>{ host, dev, per }; }
+static QueryArray<T, K> query_out(T* host, DevArray<T, K>& dev, size_t count) { return QueryArray<T, K>{ nullptr, host, dev, count }; }
+template <typename T, size_t K>
+static QueryArray<T, K> query_in(const void* host, DevArray<T, K>& dev, size_t count) { return QueryArray<T, K>{ host, nullptr, dev, count }; }
 
-// The round trip of a host query on the scene's own stream: grow the wanted result buffers, stage the rays (and what comes with them: t
-// intervals, skipped objects, the hits of srt_surface_hits, the reflectance and refraction tables of the path calls), launch(stream) -- the device entry
-// point --, wait, copy each wanted array out.
-template <typename Launch, typename... O>
-static int query_round_trip_refl(srt_scene* s, uint32_t n, const float* rays, const float* t_range, const int32_t* skip_obj, const float* t_in, const float* refl,
-                                 uint32_t n_refl, const float* ior, uint32_t n_ior, Launch launch, const O&... outs) {
+// The round trip of a host query on the scene's own stream: grow the buffers of the arrays that are there, stage the ones the call
+// brings, launch(stream) -- the device entry point --, wait, copy each wanted result out.
+template <typename Launch, typename... A>
+static int query_round_trip(srt_scene* s, Launch launch, const A&... arrays) {
     HIP_TRY(hipSetDevice(s->device));
     hipStream_t st;
     SRT_TRY(own_stream(s, &st));
     int rc = SRT_OK;
-    ((rc = (rc == SRT_OK && outs.host) ? grow(s, (size_t)n * outs.per, outs.dev) : rc), ...);
+    ((rc = (rc == SRT_OK && arrays.present()) ? grow(s, arrays.count, arrays.dev) : rc), ...);
     SRT_TRY(rc);
-    SRT_TRY(stage_rays(s, n, rays, t_range, skip_obj, t_in, st, refl, n_refl, ior, n_ior));
+    const Staged items[] = { arrays.staged()... };
+    SRT_TRY(stage_rays(s, items, sizeof...(arrays), st));
     SRT_TRY(launch(st));
     HIP_TRY(hipStreamSynchronize(st));
     if (s->qlights_stream == st) s->qlights_settled = true;      // a light table sent on this stream has arrived
     hipError_t e = hipSuccess;
-    ((e = (e == hipSuccess && outs.host) ? hipMemcpy(outs.host, outs.dev.p, (size_t)n * outs.per * outs.unit, hipMemcpyDeviceToHost) : e), ...);
+    ((e = (e == hipSuccess && arrays.out) ? hipMemcpy(arrays.out, arrays.dev.p, arrays.count * arrays.unit, hipMemcpyDeviceToHost) : e), ...);
     HIP_TRY(e);
     return SRT_OK;
 }
-template <typename Launch, typename... O>
-static int query_round_trip(srt_scene* s, uint32_t n, const float* rays, const float* t_range, const int32_t* skip_obj, const float* t_in, Launch launch, const O&... outs) {
-    return query_round_trip_refl(s, n, rays, t_range, skip_obj, t_in, nullptr, 0, nullptr, 0, launch, outs...);
-}
-
-}      // extern "C++"
 
 // The private counter set of the query that just ran (cleared before its launch), as srt_stats; n_lights: shadow rays per hit.
 static int query_stats(srt_scene* s, uint32_t n, uint32_t n_lights, srt_stats* stats) {
@@ -2080,21 +2028,23 @@ static int query_stats(srt_scene* s, uint32_t n, uint32_t n_lights, srt_stats* s
     return SRT_OK;
 }
 
-// ray_mask (the masked host forms): n words that travel as t_in does -- through the pinned block into rq_tin, bit for bit (stage_rays only
-// copies them); neither call stages a t of its own.  masked: the call is srt_*_masked, whether or not it brings per-ray masks.
-static inline const float* mask_words(const uint32_t* ray_mask) { return reinterpret_cast<const float*>(ray_mask); }
-static inline RayMask staged_mask(srt_scene* s, const uint32_t* ray_mask) { return RayMask{ ray_mask ? reinterpret_cast<const uint32_t*>(s->rq_tin.p) : nullptr }; }
+// The per-ray masks of a masked host call: n words that go through the pinned block into rq_tin, the buffer of 32-bit units that neither
+// masked call uses for a t of its own; on the device they are read as the words they are.
+static inline RayMask staged_mask(const srt_scene* s, const RayMask& mask) {
+    return RayMask{ mask.masked, mask.words ? reinterpret_cast<const uint32_t*>(s->rq_tin.p) : nullptr };
+}
 
 static int trace_rays_impl(srt_scene* s, uint32_t n, const float* rays, const float* t_range, uint32_t flags, int32_t* hit_id, float* t, float* bary,
-                           srt_stats* stats, bool masked = false, const uint32_t* ray_mask = nullptr) {
+                           srt_stats* stats, const RayMask& mask) {
     SRT_TRY(check_query(s, n, rays, flags));
     if (stats) std::memset(stats, 0, sizeof(*stats));
     if (!n) return SRT_OK;
-    const auto o_hit = query_out(hit_id, s->rq_hit); const auto o_t = query_out(t, s->rq_t); const auto o_bary = query_out(bary, s->rq_bary);
-    SRT_TRY(query_round_trip(s, n, rays, t_range, nullptr, mask_words(ray_mask), [&](hipStream_t st) {
-        const RayMask rm = staged_mask(s, ray_mask);
-        return trace_rays_device_impl(s, n, s->rq_rays, t_range ? s->rq_range.p : nullptr, flags, st, o_hit.wanted(), o_t.wanted(), o_bary.wanted(), true, masked ? &rm : nullptr);
-    }, o_hit, o_t, o_bary));
+    const auto o_hit = query_out(hit_id, s->rq_hit, n); const auto o_t = query_out(t, s->rq_t, n); const auto o_bary = query_out(bary, s->rq_bary, n);
+    const auto i_rays = query_in(rays, s->rq_rays, n); const auto i_range = query_in(t_range, s->rq_range, n); const auto i_mask = query_in(mask.words, s->rq_tin, n);
+    SRT_TRY(query_round_trip(s, [&](hipStream_t st) {
+        return trace_rays_device_impl(s, n, i_rays.on_device(), i_range.on_device(), flags, st, o_hit.on_device(), o_t.on_device(), o_bary.on_device(), true,
+                                      staged_mask(s, mask));
+    }, o_hit, o_t, o_bary, i_rays, i_range, i_mask));
     return stats ? query_stats(s, n, 0, stats) : SRT_OK;
 }
 
@@ -2103,23 +2053,26 @@ static int trace_rays_multi_impl(srt_scene* s, uint32_t n, const float* rays, co
     SRT_TRY(check_multi(s, n, rays, k, flags));
     if (stats) std::memset(stats, 0, sizeof(*stats));
     if (!n) return SRT_OK;
-    const auto o_n = query_out(n_hits, s->rq_nhits); const auto o_hit = query_out(hit_id, s->rq_hit, k);
-    const auto o_t = query_out(t, s->rq_t, k); const auto o_bary = query_out(bary, s->rq_bary, k);
-    SRT_TRY(query_round_trip(s, n, rays, t_range, nullptr, nullptr, [&](hipStream_t st) {
-        return trace_rays_multi_device_impl(s, n, s->rq_rays, t_range ? s->rq_range.p : nullptr, k, flags, st, o_n.wanted(), o_hit.wanted(), o_t.wanted(), o_bary.wanted(),
-                                            true);
-    }, o_n, o_hit, o_t, o_bary));
+    const size_t rows = (size_t)n * k;      // the n x k rows: k units a ray
+    const auto o_n = query_out(n_hits, s->rq_nhits, n); const auto o_hit = query_out(hit_id, s->rq_hit, rows);
+    const auto o_t = query_out(t, s->rq_t, rows); const auto o_bary = query_out(bary, s->rq_bary, rows);
+    const auto i_rays = query_in(rays, s->rq_rays, n); const auto i_range = query_in(t_range, s->rq_range, n);
+    SRT_TRY(query_round_trip(s, [&](hipStream_t st) {
+        return trace_rays_multi_device_impl(s, n, i_rays.on_device(), i_range.on_device(), k, flags, st, o_n.on_device(), o_hit.on_device(), o_t.on_device(),
+                                            o_bary.on_device(), true);
+    }, o_n, o_hit, o_t, o_bary, i_rays, i_range));
     return stats ? query_stats(s, n, 0, stats) : SRT_OK;
 }
 
-static int occluded_impl(srt_scene* s, uint32_t n, const float* rays, const float* t_range, const int32_t* skip_obj, uint8_t* occluded, bool masked = false,
-                         const uint32_t* ray_mask = nullptr) {
+static int occluded_impl(srt_scene* s, uint32_t n, const float* rays, const float* t_range, const int32_t* skip_obj, uint8_t* occluded, const RayMask& mask) {
     SRT_TRY(check_query(s, n, rays, 0));
     if (!n || !occluded) return SRT_OK;
-    return query_round_trip(s, n, rays, t_range, skip_obj, mask_words(ray_mask), [&](hipStream_t st) {
-        const RayMask rm = staged_mask(s, ray_mask);
-        return occluded_device_impl(s, n, s->rq_rays, t_range ? s->rq_range.p : nullptr, skip_obj ? s->rq_skip.p : nullptr, st, s->rq_occ, masked ? &rm : nullptr);
-    }, query_out(occluded, s->rq_occ));
+    const auto o_occ = query_out(occluded, s->rq_occ, n);
+    const auto i_rays = query_in(rays, s->rq_rays, n); const auto i_skip = query_in(skip_obj, s->rq_skip, n); const auto i_range = query_in(t_range, s->rq_range, n);
+    const auto i_mask = query_in(mask.words, s->rq_tin, n);
+    return query_round_trip(s, [&](hipStream_t st) {
+        return occluded_device_impl(s, n, i_rays.on_device(), i_range.on_device(), i_skip.on_device(), st, o_occ.on_device(), staged_mask(s, mask));
+    }, o_occ, i_rays, i_skip, i_range, i_mask);
 }
 
 static int shade_rays_impl(srt_scene* s, uint32_t n, const float* rays, const float* t_range, const srt_params* p, int32_t* hit_id, float* t, float* rgb_linear,
@@ -2127,121 +2080,140 @@ static int shade_rays_impl(srt_scene* s, uint32_t n, const float* rays, const fl
     SRT_TRY(check_shade(s, n, rays, p));
     if (stats) std::memset(stats, 0, sizeof(*stats));
     if (!n) return SRT_OK;
-    const auto o_hit = query_out(hit_id, s->rq_hit); const auto o_t = query_out(t, s->rq_t);
-    const auto o_lin = query_out(rgb_linear, s->rq_lin); const auto o_rgb8 = query_out(rgb8, s->rq_rgb8);
-    SRT_TRY(query_round_trip(s, n, rays, t_range, nullptr, nullptr, [&](hipStream_t st) {
-        return shade_rays_device_impl(s, n, s->rq_rays, t_range ? s->rq_range.p : nullptr, p, st, o_hit.wanted(), o_t.wanted(), o_lin.wanted(), o_rgb8.wanted(), true);
-    }, o_hit, o_t, o_lin, o_rgb8));
+    const auto o_hit = query_out(hit_id, s->rq_hit, n); const auto o_t = query_out(t, s->rq_t, n);
+    const auto o_lin = query_out(rgb_linear, s->rq_lin, n); const auto o_rgb8 = query_out(rgb8, s->rq_rgb8, n);
+    const auto i_rays = query_in(rays, s->rq_rays, n); const auto i_range = query_in(t_range, s->rq_range, n);
+    SRT_TRY(query_round_trip(s, [&](hipStream_t st) {
+        return shade_rays_device_impl(s, n, i_rays.on_device(), i_range.on_device(), p, st, o_hit.on_device(), o_t.on_device(), o_lin.on_device(), o_rgb8.on_device(), true);
+    }, o_hit, o_t, o_lin, o_rgb8, i_rays, i_range));
     return stats ? query_stats(s, n, p->n_lights, stats) : SRT_OK;
 }
 
-// srt_shade_paths: the per-segment rows are depth units a ray; hit_rays counts the hits of all segments, hence the shadow rays
-static int shade_paths_impl(srt_scene* s, uint32_t n, const float* rays, const float* t_range, const srt_params* p, const srt_path_desc* path,
-                            const srt_shadow_rule* shadow, float* rgb_linear, uint8_t* rgb8, const srt_path_out* seg, srt_stats* stats,
-                            const srt_visibility* vis = nullptr, const srt_refraction* refr = nullptr) {
-    SRT_TRY(check_refraction(refr));
-    SRT_TRY(check_shadow(shadow));
+// What the host forms of the two path calls share: the seven results of n rays or pixels (the per-segment rows are depth units each), the
+// reflectance and refraction tables (n_objects floats each, where the call brings them), and the round trip of all of them, in which
+// launch(stream, path, options, segments) gets the caller's structs with the handle's buffers in the place of the host arrays.
+struct PathArrays {
+    QueryArray<float, 3> lin; QueryArray<uint8_t, 3> rgb8;
+    QueryArray<int32_t, 1> hit; QueryArray<float, 1> t; QueryArray<int32_t, 1> obj; QueryArray<float, 3> seg_lin; QueryArray<float, 6> rays;
+    QueryArray<float, 1> refl, ior;
+    template <typename Launch, typename... In>      // in: what else the call brings
+    int round_trip(srt_scene* s, const srt_path_desc* path, const PathOptions& opt, Launch launch, const In&... in) const {
+        return query_round_trip(s, [&](hipStream_t st) -> int {
+            const srt_path_desc dpath = { path->depth, path->bounce_t_min, refl.on_device() };
+            const srt_refraction drefr = { ior.on_device(), 0u };
+            const srt_path_out dseg = { hit.on_device(), t.on_device(), obj.on_device(), seg_lin.on_device(), rays.on_device() };
+            return launch(st, &dpath, PathOptions{ .shadow = opt.shadow, .vis = opt.vis, .refr = &drefr }, &dseg);
+        }, lin, rgb8, hit, t, obj, seg_lin, rays, in..., refl, ior);
+    }
+};
+static PathArrays path_arrays(srt_scene* s, uint32_t n, const srt_path_desc* path, const PathOptions& opt, float* rgb_linear, uint8_t* rgb8, const srt_path_out* seg) {
+    const srt_path_out h = seg ? *seg : srt_path_out{};
+    const size_t rows = (size_t)path->depth * n, nO = s->dev.n_objects;
+    return PathArrays{ query_out(rgb_linear, s->rq_lin, n), query_out(rgb8, s->rq_rgb8, n), query_out(h.hit_id, s->rq_hit, rows), query_out(h.t, s->rq_t, rows),
+                       query_out(h.obj, s->rq_sobj, rows), query_out(h.rgb_linear, s->rq_plin, rows), query_out(h.rays, s->rq_sbounce, rows),
+                       query_in(path->reflectance, s->rq_refl, nO), query_in(opt.refr ? opt.refr->ior : nullptr, s->rq_ior, nO) };
+}
+
+// srt_shade_paths: hit_rays counts the hits of all segments, hence the shadow rays
+static int shade_paths_impl(srt_scene* s, uint32_t n, const float* rays, const float* t_range, const srt_params* p, const srt_path_desc* path, const PathOptions& opt,
+                            float* rgb_linear, uint8_t* rgb8, const srt_path_out* seg, srt_stats* stats) {
+    SRT_TRY(check_path_options(opt));
     SRT_TRY(check_paths(s, n, rays, p, path));
     if (stats) std::memset(stats, 0, sizeof(*stats));
     if (!n || (!stats && !paths_wanted(rgb_linear, rgb8, seg))) return SRT_OK;
-    const srt_path_out h = seg ? *seg : srt_path_out{};
-    const size_t D = path->depth;
-    const auto o_lin = query_out(rgb_linear, s->rq_lin); const auto o_rgb8 = query_out(rgb8, s->rq_rgb8);
-    const auto o_hit = query_out(h.hit_id, s->rq_hit, D); const auto o_t = query_out(h.t, s->rq_t, D); const auto o_obj = query_out(h.obj, s->rq_sobj, D);
-    const auto o_slin = query_out(h.rgb_linear, s->rq_plin, D); const auto o_rays = query_out(h.rays, s->rq_sbounce, D);
-    const float* ior = refraction_table(refr);
-    SRT_TRY(query_round_trip_refl(s, n, rays, t_range, nullptr, nullptr, path->reflectance, path->reflectance ? s->dev.n_objects : 0u, ior, ior ? s->dev.n_objects : 0u,
-                                  [&](hipStream_t st) {
-        const srt_path_desc dpath = { path->depth, path->bounce_t_min, path->reflectance ? s->rq_refl.p : nullptr };
-        const srt_refraction drefr = { ior ? s->rq_ior.p : nullptr, 0u };
-        const srt_path_out dev = { o_hit.wanted(), o_t.wanted(), o_obj.wanted(), o_slin.wanted(), o_rays.wanted() };
-        return shade_paths_device_impl(s, n, s->rq_rays, t_range ? s->rq_range.p : nullptr, p, &dpath, shadow, st, o_lin.wanted(), o_rgb8.wanted(), &dev, stats != nullptr,
-                                       vis, &drefr);
-    }, o_lin, o_rgb8, o_hit, o_t, o_obj, o_slin, o_rays));
+    const PathArrays a = path_arrays(s, n, path, opt, rgb_linear, rgb8, seg);
+    const auto i_rays = query_in(rays, s->rq_rays, n); const auto i_range = query_in(t_range, s->rq_range, n);
+    SRT_TRY(a.round_trip(s, path, opt, [&](hipStream_t st, const srt_path_desc* dpath, const PathOptions& dopt, const srt_path_out* dseg) {
+        return shade_paths_device_impl(s, n, i_rays.on_device(), i_range.on_device(), p, dpath, dopt, st, a.lin.on_device(), a.rgb8.on_device(), dseg, stats != nullptr);
+    }, i_rays, i_range));
     return stats ? query_stats(s, n, p->n_lights, stats) : SRT_OK;
 }
 
 // srt_render_paths: as shade_paths_impl, with n the call's local pixels and no rays to stage; primary_rays counts image pixels x spp
-static int render_paths_impl(srt_scene* s, const srt_params* p, const srt_path_desc* path, const srt_shadow_rule* shadow, float* rgb_linear, uint8_t* rgb8,
-                             const srt_path_out* seg, srt_stats* stats, const srt_visibility* vis = nullptr, const srt_refraction* refr = nullptr) {
-    SRT_TRY(check_refraction(refr));
-    SRT_TRY(check_shadow(shadow));
+static int render_paths_impl(srt_scene* s, const srt_params* p, const srt_path_desc* path, const PathOptions& opt, float* rgb_linear, uint8_t* rgb8,
+                             const srt_path_out* seg, srt_stats* stats) {
+    SRT_TRY(check_path_options(opt));
     SRT_TRY(check_render_paths(s, p, path));
     if (stats) std::memset(stats, 0, sizeof(*stats));
     const uint32_t n = srt_rows_owned(p) * srt_cols_owned(p);      // (< 2^32: check_render_paths)
     if (!n || (!stats && !paths_wanted(rgb_linear, rgb8, seg))) return SRT_OK;
-    const srt_path_out h = seg ? *seg : srt_path_out{};
-    const size_t D = path->depth;
-    const auto o_lin = query_out(rgb_linear, s->rq_lin); const auto o_rgb8 = query_out(rgb8, s->rq_rgb8);
-    const auto o_hit = query_out(h.hit_id, s->rq_hit, D); const auto o_t = query_out(h.t, s->rq_t, D); const auto o_obj = query_out(h.obj, s->rq_sobj, D);
-    const auto o_slin = query_out(h.rgb_linear, s->rq_plin, D); const auto o_rays = query_out(h.rays, s->rq_sbounce, D);
+    const PathArrays a = path_arrays(s, n, path, opt, rgb_linear, rgb8, seg);
     const bool padded = p->block_cols != 0;      // padding pixels are not written: what the handle's buffers hold there must not reach the caller
-    const float* ior = refraction_table(refr);
-    SRT_TRY(query_round_trip_refl(s, n, nullptr, nullptr, nullptr, nullptr, path->reflectance, path->reflectance ? s->dev.n_objects : 0u, ior, ior ? s->dev.n_objects : 0u,
-                                  [&](hipStream_t st) -> int {
-        const srt_path_desc dpath = { path->depth, path->bounce_t_min, path->reflectance ? s->rq_refl.p : nullptr };
-        const srt_refraction drefr = { ior ? s->rq_ior.p : nullptr, 0u };
-        const srt_path_out dev = { o_hit.wanted(), o_t.wanted(), o_obj.wanted(), o_slin.wanted(), o_rays.wanted() };
+    SRT_TRY(a.round_trip(s, path, opt, [&](hipStream_t st, const srt_path_desc* dpath, const PathOptions& dopt, const srt_path_out* dseg) -> int {
         if (padded) {
             // The caller's arrays first, so that the copy out returns their padding as it was.  hipMemcpy from pageable memory returns when
             // the data is on the device, so the launch enqueued on st below is ordered behind these copies without an event.  It costs a
             // second transfer of the size of the result (a tile deal in the host form is the rare case; a row-wise copy out of the live
             // columns would save it).
             hipError_t e = hipSuccess;
-            const auto up = [&](void* d, const void* src, size_t bytes) { if (src && e == hipSuccess) e = hipMemcpy(d, src, bytes, hipMemcpyHostToDevice); };
-            up(dev.hit_id, h.hit_id, D * n * 4); up(dev.t, h.t, D * n * 4); up(dev.obj, h.obj, D * n * 4); up(dev.rgb_linear, h.rgb_linear, D * n * 12);
-            up(dev.rays, h.rays, D * n * 24); up(o_lin.wanted(), rgb_linear, (size_t)n * 12); up(o_rgb8.wanted(), rgb8, (size_t)n * 3);
+            const auto up = [&](const auto& arr) { if (arr.out && e == hipSuccess) e = hipMemcpy(arr.dev.p, arr.out, arr.count * arr.unit, hipMemcpyHostToDevice); };
+            up(a.hit); up(a.t); up(a.obj); up(a.seg_lin); up(a.rays); up(a.lin); up(a.rgb8);
             HIP_TRY(e);
         }
-        return render_paths_device_impl(s, p, &dpath, shadow, st, o_lin.wanted(), o_rgb8.wanted(), &dev, stats != nullptr, vis, &drefr);
-    }, o_lin, o_rgb8, o_hit, o_t, o_obj, o_slin, o_rays));
+        return render_paths_device_impl(s, p, dpath, dopt, st, a.lin.on_device(), a.rgb8.on_device(), dseg, stats != nullptr);
+    }));
     if (!stats) return SRT_OK;
     SRT_TRY(query_stats(s, n, p->n_lights, stats));
     stats->primary_rays = pixels_owned(p) * p->spp;
     return SRT_OK;
 }
 
-// The host forms of the surface queries: the caller's srt_surface_out names host arrays; `dev` names the handle's buffers for the wanted ones.
+// What the host forms of the two surface calls share: the six arrays of the caller's srt_surface_out (host arrays), and the round trip of
+// them, in which launch(stream, out) gets the srt_surface_out that names the handle's buffers for the wanted ones.
+struct SurfaceArrays {
+    QueryArray<int32_t, 1> obj; QueryArray<float, 3> point, normal, color, material; QueryArray<float, 6> bounce;
+    template <typename Launch, typename... More>      // more: the call's other arrays
+    int round_trip(srt_scene* s, Launch launch, const More&... more) const {
+        return query_round_trip(s, [&](hipStream_t st) -> int {
+            const srt_surface_out dev = { obj.on_device(), point.on_device(), normal.on_device(), color.on_device(), material.on_device(), bounce.on_device() };
+            return launch(st, &dev);
+        }, more..., obj, point, normal, color, material, bounce);
+    }
+};
+static SurfaceArrays surface_arrays(srt_scene* s, uint32_t n, const srt_surface_out* out) {
+    const srt_surface_out h = out ? *out : srt_surface_out{};
+    return SurfaceArrays{ query_out(h.obj, s->rq_sobj, n), query_out(h.point, s->rq_spoint, n), query_out(h.normal, s->rq_snormal, n), query_out(h.color, s->rq_scolor, n),
+                          query_out(h.material, s->rq_smat, n), query_out(h.bounce, s->rq_sbounce, n) };
+}
+
 static int surface_rays_impl(srt_scene* s, uint32_t n, const float* rays, const float* t_range, uint32_t flags, int32_t* hit_id, float* t, const srt_surface_out* out,
                              srt_stats* stats) {
     SRT_TRY(check_surface(s, n, rays, flags, SRT_FLAG_COUNT_WORK | SRT_FLAG_SMOOTH_NORMALS));
     if (stats) std::memset(stats, 0, sizeof(*stats));
     if (!n) return SRT_OK;
-    const srt_surface_out h = out ? *out : srt_surface_out{};
-    const auto o_hit = query_out(hit_id, s->rq_hit); const auto o_t = query_out(t, s->rq_t);
-    const auto o_obj = query_out(h.obj, s->rq_sobj); const auto o_pt = query_out(h.point, s->rq_spoint); const auto o_nrm = query_out(h.normal, s->rq_snormal);
-    const auto o_col = query_out(h.color, s->rq_scolor); const auto o_mat = query_out(h.material, s->rq_smat); const auto o_bnc = query_out(h.bounce, s->rq_sbounce);
-    SRT_TRY(query_round_trip(s, n, rays, t_range, nullptr, nullptr, [&](hipStream_t st) {
-        const srt_surface_out dev = { o_obj.wanted(), o_pt.wanted(), o_nrm.wanted(), o_col.wanted(), o_mat.wanted(), o_bnc.wanted() };
-        return surface_rays_device_impl(s, n, s->rq_rays, t_range ? s->rq_range.p : nullptr, flags, st, o_hit.wanted(), o_t.wanted(), &dev, true);
-    }, o_hit, o_t, o_obj, o_pt, o_nrm, o_col, o_mat, o_bnc));
+    const SurfaceArrays a = surface_arrays(s, n, out);
+    const auto o_hit = query_out(hit_id, s->rq_hit, n); const auto o_t = query_out(t, s->rq_t, n);
+    const auto i_rays = query_in(rays, s->rq_rays, n); const auto i_range = query_in(t_range, s->rq_range, n);
+    SRT_TRY(a.round_trip(s, [&](hipStream_t st, const srt_surface_out* dev) {
+        return surface_rays_device_impl(s, n, i_rays.on_device(), i_range.on_device(), flags, st, o_hit.on_device(), o_t.on_device(), dev, true);
+    }, o_hit, o_t, i_rays, i_range));
     return stats ? query_stats(s, n, 0, stats) : SRT_OK;
 }
 
+// the hits a caller brings: their ids go through rq_skip, their t through rq_tin
 static int surface_hits_impl(srt_scene* s, uint32_t n, const float* rays, const int32_t* hit_id, const float* t, uint32_t flags, const srt_surface_out* out) {
     SRT_TRY(check_surface_hits(s, n, rays, hit_id, t, flags));
     if (!n || !surface_wanted(out)) return SRT_OK;
-    const srt_surface_out h = *out;
-    const auto o_obj = query_out(h.obj, s->rq_sobj); const auto o_pt = query_out(h.point, s->rq_spoint); const auto o_nrm = query_out(h.normal, s->rq_snormal);
-    const auto o_col = query_out(h.color, s->rq_scolor); const auto o_mat = query_out(h.material, s->rq_smat); const auto o_bnc = query_out(h.bounce, s->rq_sbounce);
-    return query_round_trip(s, n, rays, nullptr, hit_id, t, [&](hipStream_t st) {
-        const srt_surface_out dev = { o_obj.wanted(), o_pt.wanted(), o_nrm.wanted(), o_col.wanted(), o_mat.wanted(), o_bnc.wanted() };
-        return surface_hits_device_impl(s, n, s->rq_rays, s->rq_skip, s->rq_tin, flags, st, &dev);
-    }, o_obj, o_pt, o_nrm, o_col, o_mat, o_bnc);
+    const SurfaceArrays a = surface_arrays(s, n, out);
+    const auto i_rays = query_in(rays, s->rq_rays, n); const auto i_hit = query_in(hit_id, s->rq_skip, n); const auto i_t = query_in(t, s->rq_tin, n);
+    return a.round_trip(s, [&](hipStream_t st, const srt_surface_out* dev) {
+        return surface_hits_device_impl(s, n, i_rays.on_device(), i_hit.on_device(), i_t.on_device(), flags, st, dev);
+    }, i_rays, i_hit, i_t);
 }
+}      // extern "C++"
 
 int srt_trace_rays_device(srt_scene* s, uint32_t n, const float* d_rays, uint32_t flags, void* stream, int32_t* d_hit_id, float* d_t, float* d_bary) {
-    return guarded([&] { return trace_rays_device_impl(s, n, d_rays, nullptr, flags, (hipStream_t)stream, d_hit_id, d_t, d_bary, false); });
+    return guarded([&] { return trace_rays_device_impl(s, n, d_rays, nullptr, flags, (hipStream_t)stream, d_hit_id, d_t, d_bary, false, RayMask{}); });
 }
 int srt_trace_rays_range_device(srt_scene* s, uint32_t n, const float* d_rays, const float* d_t_range, uint32_t flags, void* stream, int32_t* d_hit_id, float* d_t,
                                 float* d_bary) {
-    return guarded([&] { return trace_rays_device_impl(s, n, d_rays, d_t_range, flags, (hipStream_t)stream, d_hit_id, d_t, d_bary, false); });
+    return guarded([&] { return trace_rays_device_impl(s, n, d_rays, d_t_range, flags, (hipStream_t)stream, d_hit_id, d_t, d_bary, false, RayMask{}); });
 }
 int srt_trace_rays(srt_scene* s, uint32_t n, const float* rays, uint32_t flags, int32_t* hit_id, float* t, float* bary, srt_stats* stats) {
-    return guarded([&] { return trace_rays_impl(s, n, rays, nullptr, flags, hit_id, t, bary, stats); });
+    return guarded([&] { return trace_rays_impl(s, n, rays, nullptr, flags, hit_id, t, bary, stats, RayMask{}); });
 }
 int srt_trace_rays_range(srt_scene* s, uint32_t n, const float* rays, const float* t_range, uint32_t flags, int32_t* hit_id, float* t, float* bary, srt_stats* stats) {
-    return guarded([&] { return trace_rays_impl(s, n, rays, t_range, flags, hit_id, t, bary, stats); });
+    return guarded([&] { return trace_rays_impl(s, n, rays, t_range, flags, hit_id, t, bary, stats, RayMask{}); });
 }
 int srt_trace_rays_multi_device(srt_scene* s, uint32_t n, const float* d_rays, const float* d_t_range, uint32_t k, uint32_t flags, void* stream, uint32_t* d_n_hits,
                                 int32_t* d_hit_id, float* d_t, float* d_bary) {
@@ -2252,16 +2224,16 @@ int srt_trace_rays_multi(srt_scene* s, uint32_t n, const float* rays, const floa
     return guarded([&] { return trace_rays_multi_impl(s, n, rays, t_range, k, flags, n_hits, hit_id, t, bary, stats); });
 }
 int srt_occluded_device(srt_scene* s, uint32_t n, const float* d_rays, const int32_t* d_skip_obj, void* stream, uint8_t* d_occluded) {
-    return guarded([&] { return occluded_device_impl(s, n, d_rays, nullptr, d_skip_obj, (hipStream_t)stream, d_occluded); });
+    return guarded([&] { return occluded_device_impl(s, n, d_rays, nullptr, d_skip_obj, (hipStream_t)stream, d_occluded, RayMask{}); });
 }
 int srt_occluded_range_device(srt_scene* s, uint32_t n, const float* d_rays, const float* d_t_range, const int32_t* d_skip_obj, void* stream, uint8_t* d_occluded) {
-    return guarded([&] { return occluded_device_impl(s, n, d_rays, d_t_range, d_skip_obj, (hipStream_t)stream, d_occluded); });
+    return guarded([&] { return occluded_device_impl(s, n, d_rays, d_t_range, d_skip_obj, (hipStream_t)stream, d_occluded, RayMask{}); });
 }
 int srt_occluded(srt_scene* s, uint32_t n, const float* rays, const int32_t* skip_obj, uint8_t* occluded) {
-    return guarded([&] { return occluded_impl(s, n, rays, nullptr, skip_obj, occluded); });
+    return guarded([&] { return occluded_impl(s, n, rays, nullptr, skip_obj, occluded, RayMask{}); });
 }
 int srt_occluded_range(srt_scene* s, uint32_t n, const float* rays, const float* t_range, const int32_t* skip_obj, uint8_t* occluded) {
-    return guarded([&] { return occluded_impl(s, n, rays, t_range, skip_obj, occluded); });
+    return guarded([&] { return occluded_impl(s, n, rays, t_range, skip_obj, occluded, RayMask{}); });
 }
 int srt_shade_rays_device(srt_scene* s, uint32_t n, const float* d_rays, const srt_params* p, void* stream, int32_t* d_hit_id, float* d_t,
                           float* d_rgb_linear, uint8_t* d_rgb8) {
@@ -2281,87 +2253,85 @@ int srt_shade_rays_range(srt_scene* s, uint32_t n, const float* rays, const floa
 }
 int srt_shade_paths_device(srt_scene* s, uint32_t n, const float* d_rays, const float* d_t_range, const srt_params* p, const srt_path_desc* path, void* stream,
                            float* d_rgb_linear, uint8_t* d_rgb8, const srt_path_out* seg) {
-    return guarded([&] { return shade_paths_device_impl(s, n, d_rays, d_t_range, p, path, nullptr, (hipStream_t)stream, d_rgb_linear, d_rgb8, seg, false); });
+    return guarded([&] { return shade_paths_device_impl(s, n, d_rays, d_t_range, p, path, PathOptions{}, (hipStream_t)stream, d_rgb_linear, d_rgb8, seg, false); });
 }
 int srt_shade_paths(srt_scene* s, uint32_t n, const float* rays, const float* t_range, const srt_params* p, const srt_path_desc* path, float* rgb_linear, uint8_t* rgb8,
                     const srt_path_out* seg, srt_stats* stats) {
-    return guarded([&] { return shade_paths_impl(s, n, rays, t_range, p, path, nullptr, rgb_linear, rgb8, seg, stats); });
+    return guarded([&] { return shade_paths_impl(s, n, rays, t_range, p, path, PathOptions{}, rgb_linear, rgb8, seg, stats); });
 }
 int srt_render_paths_device(srt_scene* s, const srt_params* p, const srt_path_desc* path, void* stream, float* d_rgb_linear, uint8_t* d_rgb8, const srt_path_out* seg) {
-    return guarded([&] { return render_paths_device_impl(s, p, path, nullptr, (hipStream_t)stream, d_rgb_linear, d_rgb8, seg, false); });
+    return guarded([&] { return render_paths_device_impl(s, p, path, PathOptions{}, (hipStream_t)stream, d_rgb_linear, d_rgb8, seg, false); });
 }
 int srt_render_paths(srt_scene* s, const srt_params* p, const srt_path_desc* path, float* rgb_linear, uint8_t* rgb8, const srt_path_out* seg, srt_stats* stats) {
-    return guarded([&] { return render_paths_impl(s, p, path, nullptr, rgb_linear, rgb8, seg, stats); });
+    return guarded([&] { return render_paths_impl(s, p, path, PathOptions{}, rgb_linear, rgb8, seg, stats); });
 }
 // The same four calls under a shadow rule (NULL: the call above, with its kernels)
 int srt_shade_paths_shadow_device(srt_scene* s, uint32_t n, const float* d_rays, const float* d_t_range, const srt_params* p, const srt_path_desc* path,
                                   const srt_shadow_rule* shadow, void* stream, float* d_rgb_linear, uint8_t* d_rgb8, const srt_path_out* seg) {
-    return guarded([&] { return shade_paths_device_impl(s, n, d_rays, d_t_range, p, path, shadow, (hipStream_t)stream, d_rgb_linear, d_rgb8, seg, false); });
+    return guarded([&] { return shade_paths_device_impl(s, n, d_rays, d_t_range, p, path, PathOptions{ .shadow = shadow }, (hipStream_t)stream, d_rgb_linear, d_rgb8, seg, false); });
 }
 int srt_shade_paths_shadow(srt_scene* s, uint32_t n, const float* rays, const float* t_range, const srt_params* p, const srt_path_desc* path, const srt_shadow_rule* shadow,
                            float* rgb_linear, uint8_t* rgb8, const srt_path_out* seg, srt_stats* stats) {
-    return guarded([&] { return shade_paths_impl(s, n, rays, t_range, p, path, shadow, rgb_linear, rgb8, seg, stats); });
+    return guarded([&] { return shade_paths_impl(s, n, rays, t_range, p, path, PathOptions{ .shadow = shadow }, rgb_linear, rgb8, seg, stats); });
 }
 int srt_render_paths_shadow_device(srt_scene* s, const srt_params* p, const srt_path_desc* path, const srt_shadow_rule* shadow, void* stream, float* d_rgb_linear,
                                    uint8_t* d_rgb8, const srt_path_out* seg) {
-    return guarded([&] { return render_paths_device_impl(s, p, path, shadow, (hipStream_t)stream, d_rgb_linear, d_rgb8, seg, false); });
+    return guarded([&] { return render_paths_device_impl(s, p, path, PathOptions{ .shadow = shadow }, (hipStream_t)stream, d_rgb_linear, d_rgb8, seg, false); });
 }
 int srt_render_paths_shadow(srt_scene* s, const srt_params* p, const srt_path_desc* path, const srt_shadow_rule* shadow, float* rgb_linear, uint8_t* rgb8,
                             const srt_path_out* seg, srt_stats* stats) {
-    return guarded([&] { return render_paths_impl(s, p, path, shadow, rgb_linear, rgb8, seg, stats); });
+    return guarded([&] { return render_paths_impl(s, p, path, PathOptions{ .shadow = shadow }, rgb_linear, rgb8, seg, stats); });
 }
 // Visibility masks: the closest-hit and occlusion calls with a mask per ray, the four path calls with a mask per ray kind (NULL vis: the
 // _shadow call above, with its kernels)
 int srt_trace_rays_masked_device(srt_scene* s, uint32_t n, const float* d_rays, const float* d_t_range, const uint32_t* d_ray_mask, uint32_t flags, void* stream,
                                  int32_t* d_hit_id, float* d_t, float* d_bary) {
-    const RayMask rm = { d_ray_mask };
-    return guarded([&] { return trace_rays_device_impl(s, n, d_rays, d_t_range, flags, (hipStream_t)stream, d_hit_id, d_t, d_bary, false, &rm); });
+    return guarded([&] { return trace_rays_device_impl(s, n, d_rays, d_t_range, flags, (hipStream_t)stream, d_hit_id, d_t, d_bary, false, RayMask{ .masked = true, .words = d_ray_mask }); });
 }
 int srt_trace_rays_masked(srt_scene* s, uint32_t n, const float* rays, const float* t_range, const uint32_t* ray_mask, uint32_t flags, int32_t* hit_id, float* t,
                           float* bary, srt_stats* stats) {
-    return guarded([&] { return trace_rays_impl(s, n, rays, t_range, flags, hit_id, t, bary, stats, true, ray_mask); });
+    return guarded([&] { return trace_rays_impl(s, n, rays, t_range, flags, hit_id, t, bary, stats, RayMask{ .masked = true, .words = ray_mask }); });
 }
 int srt_occluded_masked_device(srt_scene* s, uint32_t n, const float* d_rays, const float* d_t_range, const uint32_t* d_ray_mask, const int32_t* d_skip_obj, void* stream,
                                uint8_t* d_occluded) {
-    const RayMask rm = { d_ray_mask };
-    return guarded([&] { return occluded_device_impl(s, n, d_rays, d_t_range, d_skip_obj, (hipStream_t)stream, d_occluded, &rm); });
+    return guarded([&] { return occluded_device_impl(s, n, d_rays, d_t_range, d_skip_obj, (hipStream_t)stream, d_occluded, RayMask{ .masked = true, .words = d_ray_mask }); });
 }
 int srt_occluded_masked(srt_scene* s, uint32_t n, const float* rays, const float* t_range, const uint32_t* ray_mask, const int32_t* skip_obj, uint8_t* occluded) {
-    return guarded([&] { return occluded_impl(s, n, rays, t_range, skip_obj, occluded, true, ray_mask); });
+    return guarded([&] { return occluded_impl(s, n, rays, t_range, skip_obj, occluded, RayMask{ .masked = true, .words = ray_mask }); });
 }
 int srt_shade_paths_masked_device(srt_scene* s, uint32_t n, const float* d_rays, const float* d_t_range, const srt_params* p, const srt_path_desc* path,
                                   const srt_shadow_rule* shadow, const srt_visibility* vis, void* stream, float* d_rgb_linear, uint8_t* d_rgb8, const srt_path_out* seg) {
-    return guarded([&] { return shade_paths_device_impl(s, n, d_rays, d_t_range, p, path, shadow, (hipStream_t)stream, d_rgb_linear, d_rgb8, seg, false, vis); });
+    return guarded([&] { return shade_paths_device_impl(s, n, d_rays, d_t_range, p, path, PathOptions{ .shadow = shadow, .vis = vis }, (hipStream_t)stream, d_rgb_linear, d_rgb8, seg, false); });
 }
 int srt_shade_paths_masked(srt_scene* s, uint32_t n, const float* rays, const float* t_range, const srt_params* p, const srt_path_desc* path, const srt_shadow_rule* shadow,
                            const srt_visibility* vis, float* rgb_linear, uint8_t* rgb8, const srt_path_out* seg, srt_stats* stats) {
-    return guarded([&] { return shade_paths_impl(s, n, rays, t_range, p, path, shadow, rgb_linear, rgb8, seg, stats, vis); });
+    return guarded([&] { return shade_paths_impl(s, n, rays, t_range, p, path, PathOptions{ .shadow = shadow, .vis = vis }, rgb_linear, rgb8, seg, stats); });
 }
 int srt_render_paths_masked_device(srt_scene* s, const srt_params* p, const srt_path_desc* path, const srt_shadow_rule* shadow, const srt_visibility* vis, void* stream,
                                    float* d_rgb_linear, uint8_t* d_rgb8, const srt_path_out* seg) {
-    return guarded([&] { return render_paths_device_impl(s, p, path, shadow, (hipStream_t)stream, d_rgb_linear, d_rgb8, seg, false, vis); });
+    return guarded([&] { return render_paths_device_impl(s, p, path, PathOptions{ .shadow = shadow, .vis = vis }, (hipStream_t)stream, d_rgb_linear, d_rgb8, seg, false); });
 }
 int srt_render_paths_masked(srt_scene* s, const srt_params* p, const srt_path_desc* path, const srt_shadow_rule* shadow, const srt_visibility* vis, float* rgb_linear,
                             uint8_t* rgb8, const srt_path_out* seg, srt_stats* stats) {
-    return guarded([&] { return render_paths_impl(s, p, path, shadow, rgb_linear, rgb8, seg, stats, vis); });
+    return guarded([&] { return render_paths_impl(s, p, path, PathOptions{ .shadow = shadow, .vis = vis }, rgb_linear, rgb8, seg, stats); });
 }
 // Refracting paths: the four path calls with a refraction table after the masks (no table: the _masked call above, with its kernels)
 int srt_shade_paths_refract_device(srt_scene* s, uint32_t n, const float* d_rays, const float* d_t_range, const srt_params* p, const srt_path_desc* path,
                                    const srt_shadow_rule* shadow, const srt_visibility* vis, const srt_refraction* refr, void* stream, float* d_rgb_linear, uint8_t* d_rgb8,
                                    const srt_path_out* seg) {
-    return guarded([&] { return shade_paths_device_impl(s, n, d_rays, d_t_range, p, path, shadow, (hipStream_t)stream, d_rgb_linear, d_rgb8, seg, false, vis, refr); });
+    return guarded([&] { return shade_paths_device_impl(s, n, d_rays, d_t_range, p, path, PathOptions{ .shadow = shadow, .vis = vis, .refr = refr }, (hipStream_t)stream, d_rgb_linear, d_rgb8, seg, false); });
 }
 int srt_shade_paths_refract(srt_scene* s, uint32_t n, const float* rays, const float* t_range, const srt_params* p, const srt_path_desc* path, const srt_shadow_rule* shadow,
                             const srt_visibility* vis, const srt_refraction* refr, float* rgb_linear, uint8_t* rgb8, const srt_path_out* seg, srt_stats* stats) {
-    return guarded([&] { return shade_paths_impl(s, n, rays, t_range, p, path, shadow, rgb_linear, rgb8, seg, stats, vis, refr); });
+    return guarded([&] { return shade_paths_impl(s, n, rays, t_range, p, path, PathOptions{ .shadow = shadow, .vis = vis, .refr = refr }, rgb_linear, rgb8, seg, stats); });
 }
 int srt_render_paths_refract_device(srt_scene* s, const srt_params* p, const srt_path_desc* path, const srt_shadow_rule* shadow, const srt_visibility* vis,
                                     const srt_refraction* refr, void* stream, float* d_rgb_linear, uint8_t* d_rgb8, const srt_path_out* seg) {
-    return guarded([&] { return render_paths_device_impl(s, p, path, shadow, (hipStream_t)stream, d_rgb_linear, d_rgb8, seg, false, vis, refr); });
+    return guarded([&] { return render_paths_device_impl(s, p, path, PathOptions{ .shadow = shadow, .vis = vis, .refr = refr }, (hipStream_t)stream, d_rgb_linear, d_rgb8, seg, false); });
 }
 int srt_render_paths_refract(srt_scene* s, const srt_params* p, const srt_path_desc* path, const srt_shadow_rule* shadow, const srt_visibility* vis,
                              const srt_refraction* refr, float* rgb_linear, uint8_t* rgb8, const srt_path_out* seg, srt_stats* stats) {
-    return guarded([&] { return render_paths_impl(s, p, path, shadow, rgb_linear, rgb8, seg, stats, vis, refr); });
+    return guarded([&] { return render_paths_impl(s, p, path, PathOptions{ .shadow = shadow, .vis = vis, .refr = refr }, rgb_linear, rgb8, seg, stats); });
 }
 
 int srt_surface_rays_device(srt_scene* s, uint32_t n, const float* d_rays, const float* d_t_range, uint32_t flags, void* stream, int32_t* d_hit_id, float* d_t,

@@ -337,16 +337,9 @@ class DeviceScene:
 
     def render(self, params: abi.Params, want=("hit_id", "t", "rgb_linear", "rgb8")):
         """srt_render: host buffers out.  Returns dict of numpy arrays + 'stats'."""
-        rows, W = self.rows(params), self.cols(params)
-        out = {}
-        if "hit_id" in want: out["hit_id"] = np.empty((rows, W), np.int32)
-        if "t" in want: out["t"] = np.empty((rows, W), np.float32)
-        if "rgb_linear" in want: out["rgb_linear"] = np.empty((rows, W, 3), np.float32)
-        if "rgb8" in want: out["rgb8"] = np.empty((rows, W, 3), np.uint8)
+        out, g = _outputs(want, (self.rows(params), self.cols(params)), _FRAME)
         st = abi.Stats()
-        g = lambda k, ty: out[k].ctypes.data_as(ty) if k in out else ty()
-        _check(self.L.srt_render(self.h, C.byref(params), g("hit_id", _i32p), g("t", _f32p), g("rgb_linear", _f32p), g("rgb8", _u8p),
-                                 C.byref(st)), "srt_render")
+        _check(self.L.srt_render(self.h, C.byref(params), g("hit_id"), g("t"), g("rgb_linear"), g("rgb8"), C.byref(st)), "srt_render")
         out["stats"] = st.as_dict()
         return out
 
@@ -363,24 +356,10 @@ class DeviceScene:
         shares a bit with the ray's."""
         r = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
         n = r.shape[0]
-        tr = _t_range(t_range, n)
-        out = {}
-        if "hit_id" in want: out["hit_id"] = np.empty(n, np.int32)
-        if "t" in want: out["t"] = np.empty(n, np.float32)
-        if "bary" in want: out["bary"] = np.empty((n, 3), np.float32)
+        out, g = _outputs(want, (n,), _CLOSEST)
         st = abi.Stats()
-        g = lambda k, ty: out[k].ctypes.data_as(ty) if k in out else ty()
-        flags = abi.SRT_FLAG_COUNT_WORK if count else 0
-        if ray_mask is not None:
-            rm = _ray_mask(ray_mask, n)
-            _check(self.L.srt_trace_rays_masked(self.h, n, r.ctypes.data_as(_f32p), tr.ctypes.data_as(_f32p) if tr is not None else None,
-                                                rm.ctypes.data_as(_u32p) if rm is not None else None, flags, g("hit_id", _i32p), g("t", _f32p), g("bary", _f32p),
-                                                C.byref(st)), "srt_trace_rays_masked")
-        elif tr is None:
-            _check(self.L.srt_trace_rays(self.h, n, r.ctypes.data_as(_f32p), flags, g("hit_id", _i32p), g("t", _f32p), g("bary", _f32p), C.byref(st)), "srt_trace_rays")
-        else:
-            _check(self.L.srt_trace_rays_range(self.h, n, r.ctypes.data_as(_f32p), tr.ctypes.data_as(_f32p), flags, g("hit_id", _i32p), g("t", _f32p), g("bary", _f32p),
-                                               C.byref(st)), "srt_trace_rays_range")
+        fn, name, mid = _ray_call(self.L, "srt_trace_rays", "", _host(_t_range(t_range, n), _f32p), _host_mask(ray_mask, n))
+        _check(fn(self.h, n, _host(r, _f32p), *mid, abi.SRT_FLAG_COUNT_WORK if count else 0, g("hit_id"), g("t"), g("bary"), C.byref(st)), name)
         out["stats"] = st.as_dict()
         return out
 
@@ -390,47 +369,25 @@ class DeviceScene:
         ray_mask (n uint32, or True = all ones): srt_occluded_masked, ... among the objects whose mask shares a bit with the ray's."""
         r = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
         n = r.shape[0]
-        tr = _t_range(t_range, n)
         sk = None if skip_obj is None else np.ascontiguousarray(skip_obj, np.int32).reshape(-1)
         assert sk is None or sk.shape[0] == n, "skip_obj: one entry per ray"
         occ = np.empty(n, np.uint8)
-        skp = sk.ctypes.data_as(_i32p) if sk is not None else None
-        if ray_mask is not None:
-            rm = _ray_mask(ray_mask, n)
-            _check(self.L.srt_occluded_masked(self.h, n, r.ctypes.data_as(_f32p), tr.ctypes.data_as(_f32p) if tr is not None else None,
-                                              rm.ctypes.data_as(_u32p) if rm is not None else None, skp, occ.ctypes.data_as(_u8p)), "srt_occluded_masked")
-        elif tr is None:
-            _check(self.L.srt_occluded(self.h, n, r.ctypes.data_as(_f32p), skp, occ.ctypes.data_as(_u8p)), "srt_occluded")
-        else:
-            _check(self.L.srt_occluded_range(self.h, n, r.ctypes.data_as(_f32p), tr.ctypes.data_as(_f32p), skp, occ.ctypes.data_as(_u8p)), "srt_occluded_range")
+        fn, name, mid = _ray_call(self.L, "srt_occluded", "", _host(_t_range(t_range, n), _f32p), _host_mask(ray_mask, n))
+        _check(fn(self.h, n, _host(r, _f32p), *mid, _host(sk, _i32p), _host(occ, _u8p)), name)
         return occ
 
     def trace_rays_device(self, n, rays, stream=0, hit_id=0, t=0, bary=0, count=False, t_range=None, ray_mask=None):
         """srt_trace_rays_device: raw device pointers (ints, e.g. torch.Tensor.data_ptr()) in, asynchronous on `stream`.
         t_range (a device pointer to n x 2 floats): srt_trace_rays_range_device.
         ray_mask (a device pointer to n uint32, or 0 = all ones): srt_trace_rays_masked_device."""
-        flags = abi.SRT_FLAG_COUNT_WORK if count else 0
-        if ray_mask is not None:
-            _check(self.L.srt_trace_rays_masked_device(self.h, n, C.c_void_p(rays), C.c_void_p(t_range or 0), C.c_void_p(ray_mask or 0), flags, C.c_void_p(stream),
-                                                       C.c_void_p(hit_id), C.c_void_p(t), C.c_void_p(bary)), "srt_trace_rays_masked_device")
-        elif t_range is None:
-            _check(self.L.srt_trace_rays_device(self.h, n, C.c_void_p(rays), flags, C.c_void_p(stream), C.c_void_p(hit_id), C.c_void_p(t), C.c_void_p(bary)),
-                   "srt_trace_rays_device")
-        else:
-            _check(self.L.srt_trace_rays_range_device(self.h, n, C.c_void_p(rays), C.c_void_p(t_range), flags, C.c_void_p(stream), C.c_void_p(hit_id), C.c_void_p(t),
-                                                      C.c_void_p(bary)), "srt_trace_rays_range_device")
+        fn, name, mid = _ray_call(self.L, "srt_trace_rays", "_device", _device(t_range), _device_mask(ray_mask))
+        _check(fn(self.h, n, C.c_void_p(rays), *mid, abi.SRT_FLAG_COUNT_WORK if count else 0, C.c_void_p(stream), C.c_void_p(hit_id), C.c_void_p(t), C.c_void_p(bary)), name)
 
     def occluded_device(self, n, rays, occluded, skip_obj=0, stream=0, t_range=None, ray_mask=None):
         """srt_occluded_device: raw device pointers in, asynchronous on `stream`.  t_range (a device pointer to n x 2 floats):
         srt_occluded_range_device.  ray_mask (a device pointer to n uint32, or 0 = all ones): srt_occluded_masked_device."""
-        if ray_mask is not None:
-            _check(self.L.srt_occluded_masked_device(self.h, n, C.c_void_p(rays), C.c_void_p(t_range or 0), C.c_void_p(ray_mask or 0), C.c_void_p(skip_obj),
-                                                     C.c_void_p(stream), C.c_void_p(occluded)), "srt_occluded_masked_device")
-        elif t_range is None:
-            _check(self.L.srt_occluded_device(self.h, n, C.c_void_p(rays), C.c_void_p(skip_obj), C.c_void_p(stream), C.c_void_p(occluded)), "srt_occluded_device")
-        else:
-            _check(self.L.srt_occluded_range_device(self.h, n, C.c_void_p(rays), C.c_void_p(t_range), C.c_void_p(skip_obj), C.c_void_p(stream), C.c_void_p(occluded)),
-                   "srt_occluded_range_device")
+        fn, name, mid = _ray_call(self.L, "srt_occluded", "_device", _device(t_range), _device_mask(ray_mask))
+        _check(fn(self.h, n, C.c_void_p(rays), *mid, C.c_void_p(skip_obj), C.c_void_p(stream), C.c_void_p(occluded)), name)
 
     def trace_rays_multi(self, rays, k, want=("n_hits", "hit_id", "t", "bary"), count=False, t_range=None):
         """srt_trace_rays_multi: the k nearest hits of every ray of `rays` (n x 6, host array) in one walk, nearest first, equal t by id.
@@ -438,18 +395,12 @@ class DeviceScene:
         bary n x k x 3; unused slots -1, +inf, 0) + 'stats'.  t_range (n x 2: t_min, t_max per ray): only hits inside the closed interval."""
         r = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
         n, k = r.shape[0], int(k)
-        tr = _t_range(t_range, n)
-        kk = max(k, 0)
-        out = {}
-        if "n_hits" in want: out["n_hits"] = np.empty(n, np.uint32)
-        if "hit_id" in want: out["hit_id"] = np.empty((n, kk), np.int32)
-        if "t" in want: out["t"] = np.empty((n, kk), np.float32)
-        if "bary" in want: out["bary"] = np.empty((n, kk, 3), np.float32)
+        out, g = _outputs(want, (n,), {"n_hits": (np.uint32, ())})
+        rows, g_rows = _outputs(want, (n, max(k, 0)), _CLOSEST)
+        out.update(rows)
         st = abi.Stats()
-        g = lambda key, ty: out[key].ctypes.data_as(ty) if key in out else ty()
-        flags = abi.SRT_FLAG_COUNT_WORK if count else 0
-        _check(self.L.srt_trace_rays_multi(self.h, n, r.ctypes.data_as(_f32p), tr.ctypes.data_as(_f32p) if tr is not None else None, k, flags, g("n_hits", _u32p),
-                                           g("hit_id", _i32p), g("t", _f32p), g("bary", _f32p), C.byref(st)), "srt_trace_rays_multi")
+        _check(self.L.srt_trace_rays_multi(self.h, n, _host(r, _f32p), _host(_t_range(t_range, n), _f32p), k, abi.SRT_FLAG_COUNT_WORK if count else 0, g("n_hits"),
+                                           g_rows("hit_id"), g_rows("t"), g_rows("bary"), C.byref(st)), "srt_trace_rays_multi")
         out["stats"] = st.as_dict()
         return out
 
@@ -467,38 +418,20 @@ class DeviceScene:
         t_range (n x 2: t_min, t_max per ray): srt_shade_rays_range, the colour of the closest hit inside each ray's closed interval."""
         r = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
         n = r.shape[0]
-        tr = _t_range(t_range, n)
-        out = {}
-        if "hit_id" in want: out["hit_id"] = np.empty(n, np.int32)
-        if "t" in want: out["t"] = np.empty(n, np.float32)
-        if "rgb_linear" in want: out["rgb_linear"] = np.empty((n, 3), np.float32)
-        if "rgb8" in want: out["rgb8"] = np.empty((n, 3), np.uint8)
+        out, g = _outputs(want, (n,), _FRAME)
         st = abi.Stats()
-        g = lambda k, ty: out[k].ctypes.data_as(ty) if k in out else ty()
-        flags = params.flags
-        if count: params.flags = flags | abi.SRT_FLAG_COUNT_WORK
-        try:
-            if tr is None:
-                rc = self.L.srt_shade_rays(self.h, n, r.ctypes.data_as(_f32p), C.byref(params), g("hit_id", _i32p), g("t", _f32p), g("rgb_linear", _f32p),
-                                           g("rgb8", _u8p), C.byref(st))
-            else:
-                rc = self.L.srt_shade_rays_range(self.h, n, r.ctypes.data_as(_f32p), tr.ctypes.data_as(_f32p), C.byref(params), g("hit_id", _i32p), g("t", _f32p),
-                                                 g("rgb_linear", _f32p), g("rgb8", _u8p), C.byref(st))
-        finally:
-            params.flags = flags
-        _check(rc, "srt_shade_rays" if tr is None else "srt_shade_rays_range")
+        fn, name, mid = _ray_call(self.L, "srt_shade_rays", "", _host(_t_range(t_range, n), _f32p), None)
+        with _flags(params, count=count):
+            rc = fn(self.h, n, _host(r, _f32p), *mid, C.byref(params), g("hit_id"), g("t"), g("rgb_linear"), g("rgb8"), C.byref(st))
+        _check(rc, name)
         out["stats"] = st.as_dict()
         return out
 
     def shade_rays_device(self, n, rays, params: abi.Params, stream=0, hit_id=0, t=0, rgb_linear=0, rgb8=0, t_range=None):
         """srt_shade_rays_device: raw device pointers (ints, e.g. torch.Tensor.data_ptr()) in, asynchronous on `stream`; the light table
         of `params` is a host array.  t_range (a device pointer to n x 2 floats): srt_shade_rays_range_device."""
-        if t_range is None:
-            _check(self.L.srt_shade_rays_device(self.h, n, C.c_void_p(rays), C.byref(params), C.c_void_p(stream), C.c_void_p(hit_id), C.c_void_p(t),
-                                                C.c_void_p(rgb_linear), C.c_void_p(rgb8)), "srt_shade_rays_device")
-        else:
-            _check(self.L.srt_shade_rays_range_device(self.h, n, C.c_void_p(rays), C.c_void_p(t_range), C.byref(params), C.c_void_p(stream), C.c_void_p(hit_id),
-                                                      C.c_void_p(t), C.c_void_p(rgb_linear), C.c_void_p(rgb8)), "srt_shade_rays_range_device")
+        fn, name, mid = _ray_call(self.L, "srt_shade_rays", "_device", _device(t_range), None)
+        _check(fn(self.h, n, C.c_void_p(rays), *mid, C.byref(params), C.c_void_p(stream), C.c_void_p(hit_id), C.c_void_p(t), C.c_void_p(rgb_linear), C.c_void_p(rgb8)), name)
 
     def surface_rays(self, rays, want=("hit_id", "t", "obj", "point", "normal", "color", "material", "bounce"), smooth=False, count=False, t_range=None):
         """srt_surface_rays: the closest hit of every ray of `rays` (n x 6, host array) and the surface under it.  Returns a dict of the
@@ -507,16 +440,11 @@ class DeviceScene:
         ray's closed interval."""
         r = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
         n = r.shape[0]
-        tr = _t_range(t_range, n)
-        out = {}
-        if "hit_id" in want: out["hit_id"] = np.empty(n, np.int32)
-        if "t" in want: out["t"] = np.empty(n, np.float32)
-        so = _surface_arrays(n, want, out)
+        out, g = _outputs(want, (n,), {**_HIT, **_SURFACE})
+        so = abi.SurfaceOut(*_addresses(out, _SURFACE))
         st = abi.Stats()
-        g = lambda k, ty: out[k].ctypes.data_as(ty) if k in out else ty()
         flags = (abi.SRT_FLAG_SMOOTH_NORMALS if smooth else 0) | (abi.SRT_FLAG_COUNT_WORK if count else 0)
-        _check(self.L.srt_surface_rays(self.h, n, r.ctypes.data_as(_f32p), tr.ctypes.data_as(_f32p) if tr is not None else None, flags, g("hit_id", _i32p), g("t", _f32p),
-                                       C.byref(so), C.byref(st)), "srt_surface_rays")
+        _check(self.L.srt_surface_rays(self.h, n, _host(r, _f32p), _host(_t_range(t_range, n), _f32p), flags, g("hit_id"), g("t"), C.byref(so), C.byref(st)), "srt_surface_rays")
         out["stats"] = st.as_dict()
         return out
 
@@ -535,10 +463,10 @@ class DeviceScene:
         n = r.shape[0]
         hid = np.ascontiguousarray(hit_id, np.int32).reshape(-1); tt = np.ascontiguousarray(t, np.float32).reshape(-1)
         assert hid.shape[0] == n and tt.shape[0] == n, "hit_id, t: one entry per ray"
-        out = {}
-        so = _surface_arrays(n, want, out)
-        _check(self.L.srt_surface_hits(self.h, n, r.ctypes.data_as(_f32p), hid.ctypes.data_as(_i32p), tt.ctypes.data_as(_f32p), abi.SRT_FLAG_SMOOTH_NORMALS if smooth else 0,
-                                       C.byref(so)), "srt_surface_hits")
+        out, _ = _outputs(want, (n,), _SURFACE)
+        so = abi.SurfaceOut(*_addresses(out, _SURFACE))
+        _check(self.L.srt_surface_hits(self.h, n, _host(r, _f32p), _host(hid, _i32p), _host(tt, _f32p), abi.SRT_FLAG_SMOOTH_NORMALS if smooth else 0, C.byref(so)),
+               "srt_surface_hits")
         return out
 
     def surface_hits_device(self, n, rays, hit_id, t, stream=0, obj=0, point=0, normal=0, color=0, material=0, bounce=0, smooth=False):
@@ -546,6 +474,32 @@ class DeviceScene:
         so = abi.SurfaceOut(obj or None, point or None, normal or None, color or None, material or None, bounce or None)
         _check(self.L.srt_surface_hits_device(self.h, n, C.c_void_p(rays), C.c_void_p(hit_id), C.c_void_p(t), abi.SRT_FLAG_SMOOTH_NORMALS if smooth else 0,
                                               C.c_void_p(stream), C.byref(so)), "srt_surface_hits_device")
+
+    def _paths_host(self, kind, head, lead, params, depth, reflectance, bounce_t_min, want, count, smooth, fill, shadow, visibility, ior):
+        """The host form of a path call: srt_<kind>_paths and its _shadow, _masked and _refract forms.  head: the arguments before the
+        params; lead: the shape of one segment's rows."""
+        refl = None if reflectance is None else np.ascontiguousarray(reflectance, np.float32).reshape(-1)
+        out, g = _outputs(want, lead, _PATH_SUMS, fill)
+        seg, _ = _outputs(want, (max(int(depth), 0),) + lead, _PATH_SEGMENTS, fill)
+        out.update(seg)
+        po = abi.PathOut(*_addresses(seg, _PATH_SEGMENTS))
+        pd = abi.PathDesc(depth, bounce_t_min, refl.ctypes.data if refl is not None else None)
+        st = abi.Stats()
+        refr, table = _refraction(ior, self.flat.n_objects)
+        fn, name, mid = _path_call(self.L, kind, "", abi.shadow_rule(shadow), abi.visibility(visibility), refr)
+        with _flags(params, count=count, smooth=smooth):
+            rc = fn(*head, C.byref(params), C.byref(pd), *mid, g("rgb_linear"), g("rgb8"), C.byref(po), C.byref(st))
+        _check(rc, name)
+        out["stats"] = st.as_dict()
+        return out
+
+    def _paths_device(self, kind, head, params, depth, reflectance, bounce_t_min, stream, rgb_linear, rgb8, segments, shadow, visibility, ior):
+        """The device form of a path call.  ior: None, or a device pointer (0: the _refract call without a table)."""
+        pd = abi.PathDesc(depth, bounce_t_min, reflectance or None)
+        po = abi.PathOut(*(p or None for p in segments))
+        refr = None if ior is None else abi.Refraction(ior or None, 0)
+        fn, name, mid = _path_call(self.L, kind, "_device", abi.shadow_rule(shadow), abi.visibility(visibility), refr)
+        _check(fn(*head, C.byref(params), C.byref(pd), *mid, C.c_void_p(stream), C.c_void_p(rgb_linear), C.c_void_p(rgb8), C.byref(po)), name)
 
     def shade_paths(self, rays, params: abi.Params, depth, reflectance=None, bounce_t_min=1e-3, t_range=None,
                     want=("rgb_linear", "rgb8", "seg_hit_id", "seg_t", "seg_obj", "seg_rgb_linear", "seg_rays"), count=False, smooth=False, shadow=None,
@@ -564,39 +518,8 @@ class DeviceScene:
         surface, bent by Snell's law, instead of being mirrored (srt_*_paths_refract); reflectance keeps weighting what follows."""
         r = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
         n = r.shape[0]
-        tr = _t_range(t_range, n)
-        refl = None if reflectance is None else np.ascontiguousarray(reflectance, np.float32).reshape(-1)
-        out = {}
-        if "rgb_linear" in want: out["rgb_linear"] = np.empty((n, 3), np.float32)
-        if "rgb8" in want: out["rgb8"] = np.empty((n, 3), np.uint8)
-        po = abi.PathOut()
-        rows = max(int(depth), 0)
-        for name, (ty, k) in abi.PATH_FIELDS.items():
-            if "seg_" + name in want:
-                out["seg_" + name] = np.empty((rows, n) if k == 1 else (rows, n, k), ty)
-                setattr(po, name, out["seg_" + name].ctypes.data)
-        pd = abi.PathDesc(depth, bounce_t_min, refl.ctypes.data if refl is not None else None)
-        st = abi.Stats()
-        g = lambda k, ty: out[k].ctypes.data_as(ty) if k in out else ty()
-        flags = params.flags
-        params.flags = flags | (abi.SRT_FLAG_COUNT_WORK if count else 0) | (abi.SRT_FLAG_SMOOTH_NORMALS if smooth else 0)
-        rule = abi.shadow_rule(shadow)
-        head = (self.h, n, r.ctypes.data_as(_f32p), tr.ctypes.data_as(_f32p) if tr is not None else None, C.byref(params), C.byref(pd))
-        tail = (g("rgb_linear", _f32p), g("rgb8", _u8p), C.byref(po), C.byref(st))
-        vis = abi.visibility(visibility)
-        refr, table = _refraction(ior, self.flat.n_objects)
-        try:
-            if refr is not None:
-                rc = self.L.srt_shade_paths_refract(*head, C.byref(rule) if rule is not None else None, C.byref(vis) if vis is not None else None, C.byref(refr), *tail)
-            elif vis is not None:
-                rc = self.L.srt_shade_paths_masked(*head, C.byref(rule) if rule is not None else None, C.byref(vis), *tail)
-            else:
-                rc = self.L.srt_shade_paths(*head, *tail) if rule is None else self.L.srt_shade_paths_shadow(*head, C.byref(rule), *tail)
-        finally:
-            params.flags = flags
-        _check(rc, "srt_shade_paths_refract" if refr is not None else "srt_shade_paths_masked" if vis is not None else "srt_shade_paths" if rule is None else "srt_shade_paths_shadow")
-        out["stats"] = st.as_dict()
-        return out
+        head = (self.h, n, _host(r, _f32p), _host(_t_range(t_range, n), _f32p))
+        return self._paths_host("shade", head, (n,), params, depth, reflectance, bounce_t_min, want, count, smooth, None, shadow, visibility, ior)
 
     def shade_paths_device(self, n, rays, params: abi.Params, depth, reflectance=0, bounce_t_min=1e-3, t_range=None, stream=0, rgb_linear=0, rgb8=0, seg_hit_id=0,
                            seg_t=0, seg_obj=0, seg_rgb_linear=0, seg_rays=0, shadow=None, visibility=None, ior=None):
@@ -604,22 +527,9 @@ class DeviceScene:
         light table of `params` is a host array; `reflectance` is a DEVICE pointer to n_objects floats (0 = all 0); t_range a device
         pointer to n x 2 floats, or None; the seg_* outputs are depth x n rows, segment-major.  The flags are those of `params`.
         shadow, visibility: as in shade_paths.  ior: None, or a DEVICE pointer to n_objects floats (0 = no table): srt_shade_paths_refract_device."""
-        pd = abi.PathDesc(depth, bounce_t_min, reflectance or None)
-        po = abi.PathOut(seg_hit_id or None, seg_t or None, seg_obj or None, seg_rgb_linear or None, seg_rays or None)
-        rule = abi.shadow_rule(shadow)
-        vis = abi.visibility(visibility)
-        head = (self.h, n, C.c_void_p(rays), C.c_void_p(t_range or 0), C.byref(params), C.byref(pd))
-        tail = (C.c_void_p(stream), C.c_void_p(rgb_linear), C.c_void_p(rgb8), C.byref(po))
-        if ior is not None:
-            refr = abi.Refraction(ior or None, 0)
-            _check(self.L.srt_shade_paths_refract_device(*head, C.byref(rule) if rule is not None else None, C.byref(vis) if vis is not None else None, C.byref(refr), *tail),
-                   "srt_shade_paths_refract_device")
-        elif vis is not None:
-            _check(self.L.srt_shade_paths_masked_device(*head, C.byref(rule) if rule is not None else None, C.byref(vis), *tail), "srt_shade_paths_masked_device")
-        elif rule is None:
-            _check(self.L.srt_shade_paths_device(*head, *tail), "srt_shade_paths_device")
-        else:
-            _check(self.L.srt_shade_paths_shadow_device(*head, C.byref(rule), *tail), "srt_shade_paths_shadow_device")
+        head = (self.h, n, C.c_void_p(rays), C.c_void_p(t_range or 0))
+        self._paths_device("shade", head, params, depth, reflectance, bounce_t_min, stream, rgb_linear, rgb8, (seg_hit_id, seg_t, seg_obj, seg_rgb_linear, seg_rays),
+                           shadow, visibility, ior)
 
     def render_paths(self, params: abi.Params, depth, reflectance=None, bounce_t_min=1e-3,
                      want=("rgb_linear", "rgb8", "seg_hit_id", "seg_t", "seg_obj", "seg_rgb_linear", "seg_rays"), count=False, smooth=False, fill=None, shadow=None,
@@ -630,40 +540,8 @@ class DeviceScene:
         [depth, rows, cols, 3], seg_rays [depth, rows, cols, 6] -- + 'stats'.  count / smooth add SRT_FLAG_COUNT_WORK /
         SRT_FLAG_SMOOTH_NORMALS for this call.  fill: a value every array holds before the call (padding pixels of a tile deal keep it).
         shadow, visibility, ior: as in shade_paths."""
-        rows, W = self.rows(params), self.cols(params)
-        refl = None if reflectance is None else np.ascontiguousarray(reflectance, np.float32).reshape(-1)
-        new = (lambda shape, ty: np.empty(shape, ty)) if fill is None else (lambda shape, ty: np.full(shape, fill, ty))
-        out = {}
-        if "rgb_linear" in want: out["rgb_linear"] = new((rows, W, 3), np.float32)
-        if "rgb8" in want: out["rgb8"] = new((rows, W, 3), np.uint8)
-        po = abi.PathOut()
-        d = max(int(depth), 0)
-        for name, (ty, k) in abi.PATH_FIELDS.items():
-            if "seg_" + name in want:
-                out["seg_" + name] = new((d, rows, W) if k == 1 else (d, rows, W, k), ty)
-                setattr(po, name, out["seg_" + name].ctypes.data)
-        pd = abi.PathDesc(depth, bounce_t_min, refl.ctypes.data if refl is not None else None)
-        st = abi.Stats()
-        g = lambda k, ty: out[k].ctypes.data_as(ty) if k in out else ty()
-        flags = params.flags
-        params.flags = flags | (abi.SRT_FLAG_COUNT_WORK if count else 0) | (abi.SRT_FLAG_SMOOTH_NORMALS if smooth else 0)
-        rule = abi.shadow_rule(shadow)
-        head = (self.h, C.byref(params), C.byref(pd))
-        tail = (g("rgb_linear", _f32p), g("rgb8", _u8p), C.byref(po), C.byref(st))
-        vis = abi.visibility(visibility)
-        refr, table = _refraction(ior, self.flat.n_objects)
-        try:
-            if refr is not None:
-                rc = self.L.srt_render_paths_refract(*head, C.byref(rule) if rule is not None else None, C.byref(vis) if vis is not None else None, C.byref(refr), *tail)
-            elif vis is not None:
-                rc = self.L.srt_render_paths_masked(*head, C.byref(rule) if rule is not None else None, C.byref(vis), *tail)
-            else:
-                rc = self.L.srt_render_paths(*head, *tail) if rule is None else self.L.srt_render_paths_shadow(*head, C.byref(rule), *tail)
-        finally:
-            params.flags = flags
-        _check(rc, "srt_render_paths_refract" if refr is not None else "srt_render_paths_masked" if vis is not None else "srt_render_paths" if rule is None else "srt_render_paths_shadow")
-        out["stats"] = st.as_dict()
-        return out
+        lead = (self.rows(params), self.cols(params))
+        return self._paths_host("render", (self.h,), lead, params, depth, reflectance, bounce_t_min, want, count, smooth, fill, shadow, visibility, ior)
 
     def render_paths_device(self, params: abi.Params, depth, reflectance=0, bounce_t_min=1e-3, stream=0, rgb_linear=0, rgb8=0, seg_hit_id=0, seg_t=0, seg_obj=0,
                             seg_rgb_linear=0, seg_rays=0, shadow=None, visibility=None, ior=None):
@@ -671,22 +549,8 @@ class DeviceScene:
         light table of `params` is a host array; `reflectance` is a DEVICE pointer to n_objects floats (0 = all 0); the outputs are
         [rows, cols, ...] and the seg_* outputs [depth, rows, cols, ...] of the call's local pixels.  The flags are those of `params`.
         shadow, visibility: as in shade_paths.  ior: as in shade_paths_device."""
-        pd = abi.PathDesc(depth, bounce_t_min, reflectance or None)
-        po = abi.PathOut(seg_hit_id or None, seg_t or None, seg_obj or None, seg_rgb_linear or None, seg_rays or None)
-        rule = abi.shadow_rule(shadow)
-        vis = abi.visibility(visibility)
-        head = (self.h, C.byref(params), C.byref(pd))
-        tail = (C.c_void_p(stream), C.c_void_p(rgb_linear), C.c_void_p(rgb8), C.byref(po))
-        if ior is not None:
-            refr = abi.Refraction(ior or None, 0)
-            _check(self.L.srt_render_paths_refract_device(*head, C.byref(rule) if rule is not None else None, C.byref(vis) if vis is not None else None, C.byref(refr), *tail),
-                   "srt_render_paths_refract_device")
-        elif vis is not None:
-            _check(self.L.srt_render_paths_masked_device(*head, C.byref(rule) if rule is not None else None, C.byref(vis), *tail), "srt_render_paths_masked_device")
-        elif rule is None:
-            _check(self.L.srt_render_paths_device(*head, *tail), "srt_render_paths_device")
-        else:
-            _check(self.L.srt_render_paths_shadow_device(*head, C.byref(rule), *tail), "srt_render_paths_shadow_device")
+        self._paths_device("render", (self.h,), params, depth, reflectance, bounce_t_min, stream, rgb_linear, rgb8, (seg_hit_id, seg_t, seg_obj, seg_rgb_linear, seg_rays),
+                           shadow, visibility, ior)
 
     def sync(self):
         st = abi.Stats()
@@ -722,14 +586,93 @@ def _f(a):
     return np.ascontiguousarray(a, np.float32)
 
 
-def _surface_arrays(n, want, out):
-    """Host arrays for the fields of srt_surface_out named in `want`, added to `out`; returns the struct that points at them."""
-    so = abi.SurfaceOut()
-    for name, (ty, k) in abi.SURFACE_FIELDS.items():
-        if name in want:
-            out[name] = np.empty(n if k == 1 else (n, k), ty)
-            setattr(so, name, out[name].ctypes.data)
-    return so
+# the arrays a call can return: name -> (dtype, the shape of one ray's or pixel's entry)
+_HIT = {"hit_id": (np.int32, ()), "t": (np.float32, ())}
+_CLOSEST = {**_HIT, "bary": (np.float32, (3,))}
+_FRAME = {**_HIT, "rgb_linear": (np.float32, (3,)), "rgb8": (np.uint8, (3,))}
+_SURFACE = {k: (ty, () if c == 1 else (c,)) for k, (ty, c) in abi.SURFACE_FIELDS.items()}
+_PATH_SUMS = {"rgb_linear": (np.float32, (3,)), "rgb8": (np.uint8, (3,))}
+_PATH_SEGMENTS = {"seg_" + k: (ty, () if c == 1 else (c,)) for k, (ty, c) in abi.PATH_FIELDS.items()}
+_POINTER = {np.int32: _i32p, np.float32: _f32p, np.uint8: _u8p, np.uint32: _u32p}
+
+
+def _outputs(want, lead, spec, fill=None):
+    """Host arrays for the entries of `spec` that `want` names, each of shape lead + its own and holding `fill` where one is given.
+    Returns (name -> array, g): g(name) is the array as a pointer of its type, or that type's NULL where it is not wanted."""
+    new = np.empty if fill is None else (lambda shape, ty: np.full(shape, fill, ty))
+    out = {k: new(lead + tail, ty) for k, (ty, tail) in spec.items() if k in want}
+    return out, lambda k: out[k].ctypes.data_as(_POINTER[spec[k][0]]) if k in out else _POINTER[spec[k][0]]()
+
+
+def _addresses(out, spec):
+    """The arrays of `out` in the order of `spec`, as addresses (None: not wanted): the fields of an srt_surface_out or srt_path_out."""
+    return [out[k].ctypes.data if k in out else None for k in spec]
+
+
+class _flags:
+    """params.flags with SRT_FLAG_COUNT_WORK / SRT_FLAG_SMOOTH_NORMALS added for the call inside the `with`, and as they were after it, also
+    when it raises."""
+
+    def __init__(self, params, count=False, smooth=False):
+        self.params, self.extra = params, (abi.SRT_FLAG_COUNT_WORK if count else 0) | (abi.SRT_FLAG_SMOOTH_NORMALS if smooth else 0)
+
+    def __enter__(self):
+        self.flags = self.params.flags
+        self.params.flags = self.flags | self.extra
+
+    def __exit__(self, *exc):
+        self.params.flags = self.flags
+
+
+def _host(a, ty):
+    """A host array as the pointer a host entry point takes (the pointer keeps the array alive), or None for None."""
+    return a.ctypes.data_as(ty) if a is not None else None
+
+
+def _device(address):
+    """A device address as a _device entry point takes it, or None for None."""
+    return None if address is None else C.c_void_p(address)
+
+
+def _host_mask(ray_mask, n):
+    """The `mask` of _ray_call for a host form: None, or the masks of n rays as a pointer (NULL for True: all ones)."""
+    return None if ray_mask is None else (_host(_ray_mask(ray_mask, n), _u32p),)
+
+
+def _device_mask(ray_mask):
+    """The `mask` of _ray_call for a _device form: None, or the device address of the masks (0: all ones)."""
+    return None if ray_mask is None else (C.c_void_p(ray_mask or 0),)
+
+
+def _ray_call(L, stem, suffix, t_range, mask):
+    """Which form of a ray call its optional arguments ask for: per-ray masks (`mask` not None: a 1-tuple of them, as the C call takes
+    them) the _masked form, else intervals (`t_range` not None) the _range form, else the call itself.  Returns (the C function, its
+    name, the arguments it takes between the rays and the rest)."""
+    if mask is not None:
+        form, mid = "_masked", (t_range, *mask)
+    elif t_range is not None:
+        form, mid = "_range", (t_range,)
+    else:
+        form, mid = "", ()
+    name = stem + form + suffix
+    return getattr(L, name), name, mid
+
+
+def _path_call(L, kind, suffix, rule, vis, refr):
+    """Which form of srt_<kind>_paths (kind: shade | render; suffix: "" | _device) its optional structs ask for: a refraction the
+    _refract form, else masks the _masked form, else a rule the _shadow form, else the call itself.  Returns (the C function, its name,
+    the arguments it takes between the path desc and the outputs)."""
+    ref = lambda v: C.byref(v) if v is not None else None
+    if refr is not None:
+        form, mid = "_refract", (ref(rule), ref(vis), C.byref(refr))
+    elif vis is not None:
+        form, mid = "_masked", (ref(rule), C.byref(vis))
+    elif rule is not None:
+        form, mid = "_shadow", (C.byref(rule),)
+    else:
+        form, mid = "", ()
+    name = "srt_" + kind + "_paths" + form + suffix
+    return getattr(L, name), name, mid
 
 
 def _refraction(ior, n_objects):

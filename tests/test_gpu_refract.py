@@ -18,6 +18,7 @@ import pytest
 
 import golden_util as gu
 import ray_query_ref as rq
+import ray_range_ref as rr
 import refract_ref as rf
 import render_paths_ref as rpr
 import shade_path_ref as sp
@@ -250,6 +251,57 @@ def test_glass_that_casts_no_shadow_under_a_rule(srt, oracle):
         sp.assert_same(o, want, f"glass without a shadow, counting {count}")
         check_stats(o, want, rays.shape[0], rf.N_LIGHTS)
     sp.assert_same(ds.shade_paths(rays, sq.shade_params(lights), depth, refl, TMIN, shadow=sh.SELF, visibility=(ALL, ALL, ALL), ior=ior), casting, "glass with its shadow")
+    ds.close()
+
+
+# ---- 5b. everything a host call can bring, through the staging block at once -----------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def staged_batch():
+    """65 rays of cubes4_a40's frame (a fixed shuffle whose first ray goes through the glass inside its interval), one mixed interval per ray, the table that gives every object a bit, and a triple
+    that hides the glass from the shadow rays.  With the yardstick's rows under sh.SELF (computed once, never changed), the per-ray masks
+    of the closest-hit call that follows and the rays' candidate sets."""
+    from oracle import pyoracle
+    name = "cubes4_a40"
+    flat, frame, lights, refl = sp.frame_case(name)
+    ior = rf.case_ior(flat)
+    rays = np.ascontiguousarray(frame[np.random.default_rng(3).permutation(frame.shape[0])[:65]])
+    memo = rf.case_memo(pyoracle, name)
+    c = memo(rays)
+    tr, _, _ = rr.mixed_intervals(c, seed=5)
+    table, no_glass = vr.hidden(flat, *[k for k in range(flat.n_objects) if ior[k] > 0])
+    vis = (ALL, ALL, no_glass)
+    ref = rf.shade_paths(pyoracle, flat, rays, lights, rf.DEPTHS[name], ior, refl, TMIN, t_range=tr, rule=sh.SELF, vis=vis, obj_mask=table,
+                         colours=rf.case_colours(pyoracle, name), cands=memo)
+    masks = np.array([ALL, vr.hidden(flat, 1)[1], 0, vr.hidden(flat, 0, 2)[1]], np.uint32)[np.arange(65) % 4]
+    for v in list(ref.values()) + [rays, tr, masks]:
+        v.setflags(write=False)
+    return flat, rays, lights, refl, ior, tr, table, vis, ref, masks, c
+
+
+@gpu
+@pytest.mark.parametrize("n", [1, 65])
+def test_every_staged_array_at_once(srt, n):
+    """Host srt_shade_paths_refract with t_range, reflectance, ior, a rule and a triple all present: rays, intervals, both tables travel
+    in one staging block (at n = 65 none of n * 24, n * 8, n_objects * 4 bytes is a multiple of its 256-byte granule).  Then
+    srt_trace_rays_masked on the same handle: its mask words go through the buffer the path call left alone."""
+    flat, rays, lights, refl, ior, tr, table, vis, ref, masks, c = staged_batch()
+    assert (n * 24) % 256 and (n * 8) % 256 and (flat.n_objects * 4) % 256
+    want = cut(ref, slice(0, n))
+    assert want["seg_hit_id"][0, 0] >= 0 and ior[want["seg_obj"][0, 0]] > 0 and want["seg_hit_id"][2, 0] >= 0, "ray 0 does not go through the glass"
+    if n == 65:
+        assert (want["seg_hit_id"][0] >= 0).any() and (want["seg_hit_id"][0] < 0).any() and (want["seg_hit_id"][2] >= 0).any()
+        assert (ior[want["seg_obj"][0][want["seg_obj"][0] >= 0]] > 0).any(), "no ray enters the glass"
+    ds = srt.DeviceScene(flat)
+    ds.set_object_masks(table)
+    o = ds.shade_paths(rays[:n], sq.shade_params(lights), rf.DEPTHS["cubes4_a40"], refl, TMIN, t_range=tr[:n], shadow=sh.SELF, visibility=vis, ior=ior)
+    sp.assert_same(o, want, f"everything staged, n {n}")
+    check_stats(o, want, n, rf.N_LIGHTS)
+    sub = rr.Candidates(n, c.ray[c.ray < n], c.tri[c.ray < n], c.t[c.ray < n])
+    hit, t = vr.closest(sub, flat, masks[:n], table, tr[:n])
+    if n == 65:
+        assert (hit >= 0).any() and (hit != vr.closest(sub, flat, None, table, tr[:n])[0]).any(), "the ray masks change nothing"
+    got = ds.trace_rays(rays[:n], t_range=tr[:n], ray_mask=masks[:n], want=("hit_id", "t"))
+    assert np.array_equal(got["hit_id"], hit) and np.array_equal(bits(got["t"]), bits(t)), f"masked closest hit after the path call, n {n}"
     ds.close()
 
 
