@@ -242,6 +242,11 @@ int srt_scene_update_frame(srt_scene* s, const srt_frame_geometry* g, void* stre
  *   box      per component from (+FLT_MAX, -FLT_MAX), over the node's triangles in visit order, points one, two, three, raw xyz:
  *            if (v < mn) mn = v; if (mx < v) mx = v;  (a leaf without triangles keeps the start values; a NaN never enters a box);
  *   the union of the root boxes as srt_scene_create computes it.
+ * Matrices and points are not validated.  A matrix with inf or NaN entries, one that overflows the points or makes them subnormal, the
+ * zero matrix, a projective last row (w' of any value, 0 included), a mirror: the moved point is what IEEE arithmetic gives (inf - inf
+ * and 0 * inf are NaN), and boxes and records treat it as stated under REFIT below -- a NaN coordinate enters no box, +inf only a
+ * maximum and -inf only a minimum, subnormals compare as the numbers they are, of equal values (+0 and -0) the first in visit order
+ * stays, the box ignores w' and the records divide by it.
  * Pipeline choice: srt_scene_overlap_estimate and the packet / node-queue decision keep the value last computed on the host (create,
  * update, update_frame); results never depend on that choice.
  *
@@ -276,8 +281,17 @@ int srt_scene_pose(srt_scene* s, uint32_t n_objects, const float* obj_matrix,
  *   normals  d_normals given: tri_normals becomes exactly those floats -- direct form row i, indexed form the three gathered rows in
  *            point order one, two, three; NULL: unchanged.  Texel coordinates and texture ids stay.
  * Every render and query afterwards equals the oracle on that same flat scene.  Point values are not validated: non-finite points are
- * memory-safe and give what the arithmetic gives.  Pipeline choice: srt_scene_overlap_estimate and the packet / node-queue decision keep
- * the host's last value, as for pose.  A pose source stays valid across refits: poses apply to their source and do not accumulate.
+ * memory-safe and give what the arithmetic gives.  In full:
+ *   NaN        a NaN coordinate (quiet or signalling, either sign) enters no box; the other coordinates of the point still do.  A leaf
+ *              or an object whose points are all NaN keeps (+FLT_MAX, -FLT_MAX), as a leaf without triangles.
+ *   +-inf      +inf becomes a maximum and never a minimum (inf < FLT_MAX is false: the start value stays), -inf the reverse.
+ *   +-FLT_MAX  ties with the start value; the box holds the same bits either way.
+ *   zeros      of equal values the first in visit order stays, and an inner node keeps its left child's: a box holds -0 or +0
+ *              according to which came first (no compare of a walk tells them apart).
+ *   subnormal  coordinates compare as the numbers they are; nothing is flushed to zero, in a box or in a record.
+ *   w          the box reads raw xyz and ignores w; the records divide by it: w = +-0 gives +-inf or NaN points, w = NaN NaN points, a
+ *              huge or tiny w what the divide gives.  Rays meet such records as the oracle does on the same flat scene.
+ * Pipeline choice: srt_scene_overlap_estimate and the packet / node-queue decision keep the host's last value, as for pose.  A pose source stays valid across refits: poses apply to their source and do not accumulate.
  *
  * srt_scene_refit_prepare, a set-up call, once per tree: derives the refit's static schedule from the tree's shape (the one pose uses)
  * and, for the indexed form, takes the index buffer: tri_vertex = n_tris x 3 entries in HOST memory, in the scene's current visit order;

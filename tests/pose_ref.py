@@ -46,7 +46,10 @@ def transform_objects(flat, matrices):
 def _fold(v):
     """The reference's box fold over the rows of v (k x 3), from (+FLT_MAX, -FLT_MAX): `if (v < mn) mn = v; if (mx < v) mx = v;`.
     As a value: the smallest / largest element that compares at all -- a NaN never enters, +inf never lowers mn below FLT_MAX's
-    start (inf < FLT_MAX is false), -inf does.  fmin / fmax with the start value as `initial` are exactly that."""
+    start (inf < FLT_MAX is false), -inf does.  fmin / fmax with the start value as `initial` are exactly that for a quiet NaN.
+    For a signalling one numpy's fmin / fmax return NaN, and a reduction over one loses elements: every NaN is made quiet first
+    (tests/refit_edges.py, nan_some)."""
+    v = np.where(np.isnan(v), np.float32(np.nan), np.asarray(v, np.float32))
     mn = np.fmin.reduce(v, axis=0, initial=FLT_MAX) if len(v) else np.full(3, FLT_MAX, np.float32)
     mx = np.fmax.reduce(v, axis=0, initial=-FLT_MAX) if len(v) else np.full(3, -FLT_MAX, np.float32)
     return mn.astype(np.float32), mx.astype(np.float32)
