@@ -96,7 +96,11 @@ enum {
                                          * waves that pull work (the shadow rays of 16+ light samples) then keep only as many waves
                                          * as the frame's work can feed and leave the rest of the machine to the other frames; a
                                          * frame that has the device to itself wants every wave (1080p, 16 samples: 12-16 % faster
-                                         * with the hint on four streams, 11-23 % slower with it on one)                  */
+                                         * with the hint on four streams, 11-23 % slower with it on one).  With 1..7 light
+                                         * samples the fused trace launch then runs two waves of 8x4 pixels per 8x8 tile instead
+                                         * of four of 4x4 -- waves that live longer and leave the launch a longer tail, which the
+                                         * next frame fills (1080p, 1 sample: 18 % faster with the hint on four streams, 24 %
+                                         * slower if a single stream were given that form)                                 */
 };
 
 typedef struct srt_params {

@@ -1068,6 +1068,10 @@ enum Variant : uint32_t {
     V_UNFUSED = 10,               // the shipped node-queue kernels unfused (closest hit, then shadow)
     V_FUSED_5_WAVES = 11,         // the fused kernel built for 5 waves per SIMD
     V_FUSED_ROOTS_AGAIN = 12,     // the fused kernel with the roots re-tested by every wave (round-1 form)
+    V_FUSED_HALF = 13,            // the fused kernel's half-tile form (two waves of 8x4 pixels per tile) also without SRT_FLAG_FRAMES_IN_FLIGHT
+    V_FUSED_HALF_TINY = 14,       // the half-tile form with a 160-entry node queue: the stackless overflow walk at 32 rays per wave
+    V_FUSED_HALF_1024 = 15,       // the half-tile form with a 1024-entry node queue (nine workgroups per CU)
+    V_FUSED_HALF_32_RAYS = 16,    // the half-tile form with 32 shadow rays in flight per wave
     V_FUSED_64_RAYS = 17,         // the fused kernel with 64 shadow rays in flight per wave
     V_XCD_ROWS = 18,              // whole tile rows dealt to XCDs (what records beyond 32 MiB get), forced
     V_CHUNKED = 20,               // never fused; 8+ samples: node-queue shadow kernel, samples cut into chunks over blockIdx.z (round-1 form)
@@ -1094,6 +1098,7 @@ enum Variant : uint32_t {
     V_PK_AHEAD_SKIP = 56,         // shipped choice, ... and skip[i] / the leaf's first triangle
     V_PK_PLAIN = 57,              // shipped choice, the plain packet shadow walk under a number (never the heavy lists)
     V_PK_CLOCKS = 58,             // shipped choice, the plain walk with per-wave clock stamps (SRT_DIAG_COUNTERS)
+    V_FUSED_FOUR_WAVES = 59,      // shipped choice, the fused kernel as four waves of 4x4 pixels per tile where the half-tile form would run
     V_SHADOW_PLAIN_ROWS = 62,     // shipped choice, the node-queue shadow kernel in plain tile order where XCD rows are on
 };
 // Numbers without a name keep two fallbacks: 7..9 run the unfused node-queue chain of the shipped kernels, any other number a
@@ -1176,6 +1181,7 @@ struct FramePlan {
     // stage 3, shading: one of these (none behind k_trace_shade_nq)
     RefShadeFn ref_shade = nullptr; ShadeTileFn shade_tile = nullptr;
     dim3 grid_hit, grid_shadow, grid_shade;
+    uint32_t block_hit = 256;                     // threads per workgroup of stage 1 (the half-tile trace kernel: 128); every other launch has 256
     // the DevParams fields that belong to the choice (dev_params copies them); xcd_rows as the shadow stage sees it, shadow_px_major as
     // the shading stage does
     uint32_t exp = 0, heavy_steps = 0, pk_units = 0, pk_take = 1, xcd_rows = 0, shadow_xcd_rows = 0, shadow_px_major = 0;
@@ -1227,7 +1233,7 @@ static FramePlan plan_frame(const SceneFacts& f, const srt_params* p, BatchState
     const bool pk_shadow = L && (v == V_NQ_PK || v == V_PK_PK || (shipped && L >= 8 && !few_nodes_mid));
     const bool chunked = L >= 8 && !count && (v == V_CHUNKED || few_nodes_mid);
     // The two fallback rows for numbers without a name.  Above 10: a configuration of the fused kernel at every sample count, as the
-    // named 11, 12, 17, 18 and 28 (20 .. 23 force a pipeline through chunked / pk_shadow / pk_closest).  7 .. 9: neither row below, so
+    // named 11 .. 18 and 28 (20 .. 23 force a pipeline through chunked / pk_shadow / pk_closest).  7 .. 9: neither row below, so
     // the unfused chain of the `default` branch -- the 7-wave closest-hit build, then k_shadow_nq.
     const bool fused_config = !shipped && v > 10 && v != V_CHUNKED;
     const bool fused = L && (shipped || fused_config) && !chunked && !pk_shadow && !pk_closest;
@@ -1280,6 +1286,11 @@ static FramePlan plan_frame(const SceneFacts& f, const srt_params* p, BatchState
         } else if (fused && v == V_TRACE_SHADE && !count && !pl.xcd_rows && L < 64) {
             pl.trace_shade = &k_trace_shade_nq<512, true, 6, 16>;
         } else if (fused) {            // closest hit + shadow rays in one launch
+            // Two waves of 8x4 pixels per tile where frames are in flight on several streams: half the waves hold a CU's wave slots for the
+            // same pairs, and the next frame's launch fills the tail that a wave living twice as long leaves (36 frames on four streams
+            // 4.13 -> 3.37 ms).  A frame that has the device to itself pays for that tail -- the launch alone 0.108 -> 0.136 ms
+            // -- and keeps four waves per tile, as do the camera, counting and XCD-row builds below.
+            const bool half_tile = (v == V_SHIPPED && in_flight) || v == V_FUSED_HALF;
             if (cam_nq)                        pl.trace = &k_trace_nq<false, 512, true, 5, 16, false, false, true>;      // camera mode on the node queues
             else if (count)                    pl.trace = &k_trace_nq<true, 512, true, 5, 16>;
             else if (v == V_FUSED_5_WAVES)     pl.trace = &k_trace_nq<false, 512, true, 5, 16>;
@@ -1288,6 +1299,10 @@ static FramePlan plan_frame(const SceneFacts& f, const srt_params* p, BatchState
             else if (v == V_FUSED_6_WAVES)     pl.trace = &k_trace_nq<false, 512, true, 6, 16>;
             else if (v == V_ALL_WIDE)          pl.trace = &k_trace_nq<false, 512, true, 6, 16, false, false, false, true>;
             else if (pl.xcd_rows)            { pl.trace = &k_trace_nq<false, 512, true, 6, 16, true>; pl.grid_hit.y = xcd_pad(grid8.y); }
+            else if (v == V_FUSED_HALF_TINY) { pl.trace = &k_trace_nq_half<160, true, 6, 16>; pl.block_hit = 128; }
+            else if (v == V_FUSED_HALF_1024) { pl.trace = &k_trace_nq_half<1024, true, 5, 16>; pl.block_hit = 128; }
+            else if (v == V_FUSED_HALF_32_RAYS) { pl.trace = &k_trace_nq_half<512, true, 6, 32>; pl.block_hit = 128; }
+            else if (half_tile)              { pl.trace = &k_trace_nq_half<512, true, 6, 16>; pl.block_hit = 128; }      // two waves of 8x4 pixels per tile: 12,680 B of LDS, twelve workgroups and 24 waves per CU
             else                               pl.trace = &k_trace_nq<false, 512, true, 7, 16>;      // 72 VGPRs, no scratch, 7 waves per SIMD (lane-derived addresses are formed where they are used: lane_again, srt_kernels.h); with 14 spilled registers it was already 3 % ahead of the 6-wave build since the node-major order
         } else if (!count && v == V_COARSE_GRID) {
             // 2 x 2 tiles per workgroup (a quarter of the workgroups for frames that are mostly background).  Measured and NOT
@@ -1374,13 +1389,13 @@ struct BatchCollector {
 
 // One pass of a plan over this call's pixels: closest hit (+ shadow rays) and shading, the event records between them.
 static int launch_stages(srt_scene* s, const FramePlan& pl, const FrameParams& fp, hipStream_t stream, int32_t* o_hit, float* o_t, float* o_lin, uint8_t* o_rgb8, unsigned long long* ctr, unsigned long long* zero_next, hipEvent_t* ev) {
-    const dim3 block(256);
+    const dim3 block(256), block_hit(pl.block_hit);
     uint32_t* const ql = pl.quadrants_consumed ? s->ws_qlist.p : nullptr, * const ql_cnt = pl.quadrants_consumed ? s->d_qcount.p : nullptr;
     if (pl.ref_hit)          hipLaunchKernelGGL(pl.ref_hit, pl.grid_hit, block, 0, stream, s->dev, fp.hit, o_hit, o_t, ctr);
     else if (pl.q_hit)       hipLaunchKernelGGL(pl.q_hit, pl.grid_hit, block, 0, stream, s->dev, fp.hit, o_hit, o_t, o_lin, o_rgb8, ctr);
     else if (pl.nq_hit)      hipLaunchKernelGGL(pl.nq_hit, pl.grid_hit, block, 0, stream, s->dev, fp.hit, o_hit, o_t, o_lin, o_rgb8, ctr, ql_cnt, ql, s->qcap);
     else if (pl.pk_hit)      hipLaunchKernelGGL(pl.pk_hit, pl.grid_hit, block, 0, stream, s->dev, fp.hit, o_hit, o_t, o_lin, o_rgb8, ql_cnt, ql, s->qcap, ctr);
-    else if (pl.trace)       hipLaunchKernelGGL(pl.trace, pl.grid_hit, block, 0, stream, s->dev, fp.hit, o_hit, o_t, o_lin, o_rgb8, s->ws_shadow, ctr);
+    else if (pl.trace)       hipLaunchKernelGGL(pl.trace, pl.grid_hit, block_hit, 0, stream, s->dev, fp.hit, o_hit, o_t, o_lin, o_rgb8, s->ws_shadow, ctr);
     else                     hipLaunchKernelGGL(pl.trace_shade, pl.grid_hit, block, 0, stream, s->dev, fp.hit, o_hit, o_t, o_lin, o_rgb8, ctr, zero_next, s->d_qcount);
     HIP_TRY(hipGetLastError());
     if (ev) HIP_TRY(hipEventRecord(ev[1], stream));

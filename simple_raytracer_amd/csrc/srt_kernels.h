@@ -452,7 +452,11 @@ __device__ __forceinline__ void diag_tile_record(float* rgb_linear, uint32_t bx,
 // form (P1, e1, e2 and the ray's origin) instead of the origin form -- the arithmetic of the oracle's camera mode.
 // WIDE: the queue holds inner nodes that are known to pass, as indices of their DevWide records (srt_device.h): a pop tests BOTH
 // children.  !WIDE is the round-1/2 form (a queue entry is a node still to be tested, 32 B records), kept for A/B (variant 40).
-template <bool COUNT, int NQCAP, int TWL, int THL, bool FILTER, bool CAM = false, bool WIDE = false>
+// HALF (with TWL = 3, THL = 2): the wave owns the upper or lower half of the workgroup's 8x8 tile -- `wave` = 0 / 1, rows 4 * wave ..
+// 4 * wave + 3, all eight columns -- and ray pl < 32 is the pixel x = (pl >> 4 & 1) * 4 + (pl & 3), y = pl >> 2 & 3 of the half: pl >> 4
+// is the 4x4 quadrant inside the half and pl & 15 the pixel of that quadrant as the four-wave form numbers it, so ray pl of half h is
+// entry 32 * h + pl of the tile's root masks and bit 32 * h + pl of the tile's shadow words.
+template <bool COUNT, int NQCAP, int TWL, int THL, bool FILTER, bool CAM = false, bool WIDE = false, bool HALF = false>
 __device__ __forceinline__ void closest_hit_phase(const DevScene& s, const DevParams& p, uint32_t* nq, uint32_t* tq,
                                                   unsigned long long* best, float4* dir,
                                                   int32_t* __restrict__ hit_id, float* __restrict__ t_out,
@@ -467,8 +471,9 @@ __device__ __forceinline__ void closest_hit_phase(const DevScene& s, const DevPa
     const uint32_t lane = threadIdx.x & 63;
     const float4* nodes4 = reinterpret_cast<const float4*>(s.nodes);
     const float4* tris4 = reinterpret_cast<const float4*>(s.tris);
-    const uint32_t tile_x = (bx * 2 + (wave & 1)) << TWL, tile_r = (by * 2 + (wave >> 1)) << THL;
-    const uint32_t px = tile_x + (lane & ((1u << TWL) - 1)), r = tile_r + ((lane >> TWL) & ((1u << THL) - 1));
+    static_assert(!HALF || (TWL == 3 && THL == 2), "a half tile is 8x4 pixels");
+    const uint32_t tile_x = HALF ? bx * 8 + ((lane >> 4) & 1u) * 4 : (bx * 2 + (wave & 1)) << TWL, tile_r = HALF ? by * 8 + wave * 4 : (by * 2 + (wave >> 1)) << THL;
+    const uint32_t px = tile_x + (lane & (HALF ? 3u : (1u << TWL) - 1)), r = tile_r + ((lane >> (HALF ? 2 : TWL)) & ((1u << THL) - 1));
     const bool live = lane < P && pixel_live(p, px, r);
     const V3 o = CAM ? ray_origin(p) : mk(0.0f, 0.0f, 0.0f);
     if (lane < P) {
@@ -850,7 +855,8 @@ template <bool FILTER, bool CAM = false>
 __device__ __forceinline__ bool background_test_wave(const DevScene& s, const DevParams& p, int32_t* __restrict__ hit_id, float* __restrict__ t_out,
                                                      float* __restrict__ rgb_linear, uint8_t* __restrict__ rgb8,
                                                      unsigned long long* __restrict__ shadow_bits,
-                                                     const uint32_t bx, const uint32_t by, const uint32_t gx, uint32_t* root_pass) {
+                                                     const uint32_t bx, const uint32_t by, const uint32_t gx, uint32_t* root_pass,
+                                                     const uint32_t root_half_stride = 0) {      // != 0: the masks of rays 32 .. 63 start this many words after those of rays 0 .. 31
     const uint32_t lane = threadIdx.x & 63, quad = lane >> 4, ql = lane & 15u;
     const uint32_t px = bx * 8 + (quad & 1) * 4 + (ql & 3), r = by * 8 + (quad >> 1) * 4 + (ql >> 2);
     const bool live = pixel_live(p, px, r);
@@ -921,7 +927,7 @@ __device__ __forceinline__ bool background_test_wave(const DevScene& s, const De
         if (n_obj <= 2u) group(0u, std::integral_constant<uint32_t, 2>());
         else for (uint32_t ob0 = 0; ob0 < n_obj; ob0 += 4u) group(ob0, std::integral_constant<uint32_t, 4>());
     }
-    if (root_pass) root_pass[lane] = live ? pmask : 0u;
+    if (root_pass) root_pass[root_half_stride ? (lane >> 5) * root_half_stride + (lane & 31u) : lane] = live ? pmask : 0u;
     const unsigned long long m = __ballot(live && any);
     if (m == 0ull) {
         if (live) {      // what closest_hit_phase writes for a miss
@@ -943,10 +949,11 @@ __device__ __forceinline__ bool finish_background_tile(const DevScene& s, const 
                                                        float* __restrict__ rgb_linear, uint8_t* __restrict__ rgb8,
                                                        unsigned long long* __restrict__ shadow_bits,
                                                        const uint32_t bx, const uint32_t by, const uint32_t gx,
-                                                       uint32_t* root_pass = nullptr) {      // LDS, 64 words (quadrant * 16 + pixel): out, per ray the objects whose root box it passes
+                                                       uint32_t* root_pass = nullptr,        // LDS, 64 words (quadrant * 16 + pixel): out, per ray the objects whose root box it passes
+                                                       const uint32_t root_half_stride = 0) {
     __shared__ uint32_t tile_live;
     if ((threadIdx.x >> 6) == 0) {
-        const bool live = background_test_wave<FILTER, CAM>(s, p, hit_id, t_out, rgb_linear, rgb8, shadow_bits, bx, by, gx, root_pass);
+        const bool live = background_test_wave<FILTER, CAM>(s, p, hit_id, t_out, rgb_linear, rgb8, shadow_bits, bx, by, gx, root_pass, root_half_stride);
         if ((threadIdx.x & 63) == 0) tile_live = live ? 1u : 0u;
     }
     __syncthreads();
@@ -1166,21 +1173,23 @@ __global__ __launch_bounds__(256) void k_shade(DevScene s, DevParams p, const in
 // slab / triangle test counts are the algorithmic counts the CPU oracle mirrors.
 // =================================================================================================
 // Per-wave LDS of the shadow phase (beside the two queues)
-template <int RS>                  // RS = shadow rays in flight per round: 16, or 64 when there are many light samples
+template <int RS, int P = NQ_P>    // RS = shadow rays in flight per round: 16, or 64 when there are many light samples; P = pixels of the wave
 struct ShadowLds {
     float4 ray[2 * RS];            // per ray slot: origin, direction
-    float4 pixd[NQ_P];             // per hit rank: t, pixel lane, own object's node range
-    float4 pso[NQ_P];              // per hit rank: the shadow rays' origin d * t (:326)
+    float4 pixd[P];                // per hit rank: t, pixel lane, own object's node range
+    float4 pso[P];                 // per hit rank: the shadow rays' origin d * t (:326)
     int2 selfr[RS];                // per ray slot: node range of the hit object
     uint32_t flag[RS];
-    uint32_t mask[64];             // per light sample of the current group: shadowed pixels of this wave's 4x4 quadrant
+    uint32_t mask[64];             // per light sample of the current group: shadowed pixels of this wave's 4x4 quadrant (P = 32: of its 8x4 half)
 };
 
 // Runs per wavefront, with no workgroup-level synchronisation: `id` / `t_hit` are the hit id and t of this lane's pixel
 // (lanes < 16; -1 = miss).  The wave writes its own 16-bit field of the tile's word (field = quadrant, bit = pixel lane
 // y * 4 + x inside the quadrant), so a wave that is done leaves the CU without waiting for its three neighbours.
-template <bool SEQ, int NQCAP, bool FILTER, int RS, bool EARLY = true, bool WIDE = false>
-__device__ __forceinline__ void shadow_phase(const DevScene& s, const DevParams& p, uint32_t* nq, uint32_t* tq, ShadowLds<RS>& L,
+// P = 32: the wave owns half `wave` of the tile (closest_hit_phase's HALF: lanes < 32, pixel lane = quadrant of the half * 16 + y * 4 + x)
+// and writes the 32-bit half `wave` of the tile's word -- fields 2 * wave and 2 * wave + 1 -- in one store.
+template <bool SEQ, int NQCAP, bool FILTER, int RS, bool EARLY = true, bool WIDE = false, int P = NQ_P>
+__device__ __forceinline__ void shadow_phase(const DevScene& s, const DevParams& p, uint32_t* nq, uint32_t* tq, ShadowLds<RS, P>& L,
                                              int32_t id, float t_hit, V3 d_hit,
                                              unsigned long long* __restrict__ shadow_bits, unsigned long long* __restrict__ counters,
                                              const uint32_t bx, const uint32_t by, const uint32_t gx, const uint32_t wave,
@@ -1193,10 +1202,11 @@ __device__ __forceinline__ void shadow_phase(const DevScene& s, const DevParams&
     float4* pixd = L.pixd;
     const float4* nodes4 = reinterpret_cast<const float4*>(s.nodes);
     const float4* tris4 = reinterpret_cast<const float4*>(s.tris);
-    const uint32_t qx = wave & 1, qy = wave >> 1;
-    const uint32_t tile_x = bx * 8 + qx * 4, tile_r = by * 8 + qy * 4;
+    static_assert(P == 16 || P == 32, "a wave owns a 4x4 quadrant or an 8x4 half of the tile");
+    const uint32_t qx = P == 32 ? (lane >> 4) & 1u : wave & 1, qy = P == 32 ? 0u : wave >> 1;
+    const uint32_t tile_x = bx * 8 + qx * 4, tile_r = by * 8 + (P == 32 ? wave * 4 : qy * 4);
     const uint32_t px = tile_x + (lane & 3), r = tile_r + ((lane >> 2) & 3);
-    const bool live = lane < NQ_P && pixel_live(p, px, r);
+    const bool live = lane < P && pixel_live(p, px, r);
     const size_t tile_index = (size_t)by * gx + bx;
     const uint32_t wave_s = __builtin_amdgcn_readfirstlane(wave);      // wave-uniform: waits for the stores at the end in a scalar register
     unsigned long long n_node = 0, n_tri = 0;
@@ -1218,16 +1228,16 @@ __device__ __forceinline__ void shadow_phase(const DevScene& s, const DevParams&
     // machinery below is a chain of dependent steps to find that out (profiles/diag_timeline_parts.py: the waves of slab tiles hold 22
     // of a CU's 24 wave slots, so a wave's lifetime IS the throughput).  So the wave first puts every (ray, light sample, other
     // object) through that root's slab test -- the test the first node step would run -- at 16 rays x 4 combinations per pass; if
-    // nothing passes, the quadrant's shadow words are zero.  K3 with 4 light samples: 0.210 -> 0.187 ms per frame.
+    // nothing passes, the quadrant's shadow words are zero.  K3 with 4 light samples: 0.210 -> 0.187 ms per frame.  (P = 32: 32 rays x 2.)
     const uint32_t n_combo = (l_end - l_begin) * s.n_objects;
     if (!SEQ && EARLY && l_end > l_begin && (nh == 0u || n_combo <= 64u)) {
-        const uint32_t rl = lane & 15u, slot = lane >> 4;
+        const uint32_t rl = lane & (uint32_t)(P - 1), slot = lane / (uint32_t)P;
         const float sx = __shfl(so_mine.x, (int)rl, 64), sy = __shfl(so_mine.y, (int)rl, 64), sz = __shfl(so_mine.z, (int)rl, 64);
         const int32_t sroot = __shfl(self_root, (int)rl, 64);
         const V3 so = mk(sx, sy, sz);
         bool pass_any = false;
         if (sroot != -2 && nh) {
-            for (uint32_t c = slot; c < n_combo; c += 4u) {
+            for (uint32_t c = slot; c < n_combo; c += 64u / (uint32_t)P) {
                 const uint32_t lq = c / s.n_objects, ob = c - lq * s.n_objects, l = l_begin + lq;
                 const int32_t root = s.obj_range[ob].x;
                 const float4 a = reinterpret_cast<const float4*>(s.root_nodes)[2 * (size_t)ob], b = reinterpret_cast<const float4*>(s.root_nodes)[2 * (size_t)ob + 1];      // (independent of `root`)
@@ -1244,7 +1254,10 @@ __device__ __forceinline__ void shadow_phase(const DevScene& s, const DevParams&
         }
         if (!__ballot(pass_any)) {
             L.mask[lane] = 0u;                                        // (read by the wave that shades the tile in the one-launch build)
-            if (shadow_bits) for (uint32_t l = l_begin + lane; l < l_end; l += 64u) reinterpret_cast<uint16_t*>(shadow_bits)[(tile_index * p.n_lights + l) * 4 + wave_s] = 0;
+            if (shadow_bits) for (uint32_t l = l_begin + lane; l < l_end; l += 64u) {
+                if (P == 32) reinterpret_cast<uint32_t*>(shadow_bits)[(tile_index * p.n_lights + l) * 2 + wave_s] = 0u;
+                else reinterpret_cast<uint16_t*>(shadow_bits)[(tile_index * p.n_lights + l) * 4 + wave_s] = 0;
+            }
             return;
         }
     }
@@ -1301,7 +1314,10 @@ __device__ __forceinline__ void shadow_phase(const DevScene& s, const DevParams&
         const uint32_t n_items = nh * Lg;
         // item / Lg below as a multiplication: exact for item < 16 * Lg, Lg <= 64 ((65536 / Lg + 1) * Lg - 65536 <= Lg, and item < 65536 / Lg).
         // Wave-uniform, so it waits in a scalar register; the reciprocal of a per-lane division waited in a vector register, or in scratch.
-        const uint32_t lg_magic = __builtin_amdgcn_readfirstlane(0x10000u / Lg + 1u);
+        // (32 pixels: item < 32 * Lg reaches 2 * 65536 / Lg, so the scale is 2^20 there -- (2^20 / Lg + 1) * Lg - 2^20 <= Lg, item < 2^20 / Lg,
+        // and item * (2^20 + 1) < 2^32.)
+        constexpr uint32_t LG_SHIFT = P == 32 ? 20u : 16u;
+        const uint32_t lg_magic = __builtin_amdgcn_readfirstlane((1u << LG_SHIFT) / Lg + 1u);
         for (uint32_t base = 0; base < n_items; base += RS) {        // RS rays per round
             const uint32_t ln = lane_again(lane);                 // (the slots' addresses are formed here, not kept across the rounds)
             const uint32_t item = base + ln;
@@ -1310,7 +1326,7 @@ __device__ __forceinline__ void shadow_phase(const DevScene& s, const DevParams&
             V3 so = mk(0.f, 0.f, 0.f), sd = mk(0.f, 0.f, 1.f);
             int2 self = make_int2(-1, -1);
             if (valid) {
-                const uint32_t hr = (Lg == 1u) ? item : (item * lg_magic) >> 16;
+                const uint32_t hr = (Lg == 1u) ? item : (item * lg_magic) >> LG_SHIFT;
                 lg = item - hr * Lg;
                 const float4 pd = pixd[hr];
                 pl = __float_as_uint(pd.y);
@@ -1533,7 +1549,10 @@ __device__ __forceinline__ void shadow_phase(const DevScene& s, const DevParams&
         }
         __builtin_amdgcn_wave_barrier();
         const uint32_t lw = lane_again(lane);      // (the word's address is formed here, not kept across the walk)
-        if (shadow_bits && lw < Lg) reinterpret_cast<uint16_t*>(shadow_bits)[(tile_index * p.n_lights + l0 + lw) * 4 + wave_s] = (uint16_t)L.mask[lw];
+        if (shadow_bits && lw < Lg) {
+            if (P == 32) reinterpret_cast<uint32_t*>(shadow_bits)[(tile_index * p.n_lights + l0 + lw) * 2 + wave_s] = L.mask[lw];
+            else reinterpret_cast<uint16_t*>(shadow_bits)[(tile_index * p.n_lights + l0 + lw) * 4 + wave_s] = (uint16_t)L.mask[lw];
+        }
         __builtin_amdgcn_wave_barrier();
     }
     if (SEQ) { wave_add(counters + 3, n_node); wave_add(counters + 4, n_tri); }
@@ -1593,7 +1612,13 @@ __device__ __forceinline__ void shade_hit_pixel(const DevScene& s, const DevPara
 // WIDE (the 64 B inner-node records): measured per kernel -- the stand-alone shadow kernel, whose rays cross a
 // soup's overlapping boxes hundreds of nodes deep, gains 10 % from it; the fused kernel and the closest-hit kernel, whose frames are
 // mostly short waves, lose 5 % (16 VGPRs of record per lane instead of 8: spills at six waves per SIMD), so they keep the 32 B records.
-template <bool COUNT, int NQCAP, bool FILTER, int RS, bool XCD_ROWS, bool ROOTS_AGAIN, bool SHADE = false, bool CAM = false, bool WIDE = false, bool ROW_Z = false>
+// HALF: the workgroup is TWO waves (128 threads) and wave h owns rows 4h .. 4h + 3 of the tile, 32 rays (closest_hit_phase's HALF,
+// shadow_phase's P = 32): the same (node, ray) and (triangle, ray) pairs, merged the same way, on half the waves -- a ground-slab wave's
+// one node step and one triangle batch fill 64 lanes instead of 32, and a background tile parks one wave at the barrier, not three.
+// The tile's root masks wait in the two waves' own shadow masks (rays 32h .. 32h + 31 in lds_all[h].mask[0 .. 31]): wave h alone writes
+// that array again, in its shadow phase, after it has read them -- 256 B less, which is what lets twelve workgroups fit a CU's LDS.
+template <bool COUNT, int NQCAP, bool FILTER, int RS, bool XCD_ROWS, bool ROOTS_AGAIN, bool SHADE = false, bool CAM = false, bool WIDE = false, bool ROW_Z = false,
+          bool HALF = false>
 __device__ __forceinline__ void trace_nq_body(const DevScene& s, const DevParams& p, int32_t* __restrict__ hit_id, float* __restrict__ t_out,
                                               float* __restrict__ rgb_linear, uint8_t* __restrict__ rgb8,
                                               unsigned long long* __restrict__ shadow_bits, unsigned long long* __restrict__ counters,
@@ -1606,11 +1631,13 @@ __device__ __forceinline__ void trace_nq_body(const DevScene& s, const DevParams
         if (counters_next) zero_next_counters(counters_next);
         if (qcount && blockIdx.x == 0 && blockIdx.y == 0) for (uint32_t i = threadIdx.x; i < (uint32_t)QL_COUNTERS; i += 256u) qcount[i * QL_STRIDE] = 0u;
     }
-    __shared__ uint32_t nq_all[4][NQCAP];
-    __shared__ uint32_t tq_all[4][LQ_WORDS];
-    __shared__ unsigned long long best_all[4][NQ_P];
-    __shared__ float4 dir_all[4][NQ_P];
-    __shared__ ShadowLds<RS> lds_all[4];
+    static_assert(!HALF || (!SHADE && !COUNT), "the half-tile form has no one-launch and no counting build");
+    constexpr int NW = HALF ? 2 : 4, P = HALF ? 32 : NQ_P;      // waves per tile, rays per wave
+    __shared__ uint32_t nq_all[NW][NQCAP];
+    __shared__ uint32_t tq_all[NW][LQ_WORDS];
+    __shared__ unsigned long long best_all[NW][P];
+    __shared__ float4 dir_all[NW][P];
+    __shared__ ShadowLds<RS, P> lds_all[NW];
     const uint32_t wave = threadIdx.x >> 6;
     int32_t id; float t; V3 d;
     unsigned long long k0 = 0, k1 = 0; (void)k0; (void)k1;
@@ -1629,15 +1656,24 @@ __device__ __forceinline__ void trace_nq_body(const DevScene& s, const DevParams
     }
     __shared__ uint32_t root_pass[64];
     const bool roots_done = !COUNT && !ROOTS_AGAIN && s.n_objects <= 32u;              // wave 0 tests every root for the tile's 64 rays first
-    if (!COUNT && finish_background_tile<FILTER, CAM>(s, p, hit_id, t_out, rgb_linear, rgb8, shadow_bits, bx, by, gx, root_pass)) return;
     unsigned long long ka = 0, kb = 0; (void)ka; (void)kb;
+    if constexpr (HALF) {
+        static_assert(sizeof(ShadowLds<RS, P>) % 4 == 0, "the stride between the two waves' masks is counted in words");
+        if (finish_background_tile<FILTER, CAM>(s, p, hit_id, t_out, rgb_linear, rgb8, shadow_bits, bx, by, gx, lds_all[0].mask, sizeof(ShadowLds<RS, P>) / 4)) return;
+        SRT_STAMP(ka);
+        closest_hit_phase<COUNT, NQCAP, 3, 2, FILTER, CAM, WIDE, true>(s, p, nq_all[wave], tq_all[wave], best_all[wave], dir_all[wave],
+                                                                 hit_id, t_out, rgb_linear, rgb8, counters, id, t, d, bx, by, gx, wave, nullptr, nullptr, 0,
+                                                                 roots_done ? lds_all[wave].mask : nullptr);
+    } else {
+    if (!COUNT && finish_background_tile<FILTER, CAM>(s, p, hit_id, t_out, rgb_linear, rgb8, shadow_bits, bx, by, gx, root_pass)) return;
     SRT_STAMP(ka);
     closest_hit_phase<COUNT, NQCAP, 2, 2, FILTER, CAM, WIDE>(s, p, nq_all[wave], tq_all[wave], best_all[wave], dir_all[wave],
                                                        hit_id, t_out, rgb_linear, rgb8, counters, id, t, d, bx, by, gx, wave, nullptr, nullptr, 0,
                                                        roots_done ? root_pass + wave * 16 : nullptr);
+    }
     __builtin_amdgcn_wave_barrier();
     SRT_STAMP(kb);
-    shadow_phase<COUNT, NQCAP, FILTER, RS, true, WIDE>(s, p, nq_all[wave], tq_all[wave], lds_all[wave], id, t, d, shadow_bits, counters, bx, by, gx, wave);
+    shadow_phase<COUNT, NQCAP, FILTER, RS, true, WIDE, P>(s, p, nq_all[wave], tq_all[wave], lds_all[wave], id, t, d, shadow_bits, counters, bx, by, gx, wave);
 #ifdef SRT_DIAG
     SRT_STAMP(k1); diag_tile_record(rgb_linear, blockIdx.x, blockIdx.y, gridDim.x, k0, k1, ka, kb);
 #endif
@@ -1665,6 +1701,14 @@ __global__ __launch_bounds__(256, MINW) void k_trace_nq(DevScene s, DevParams p,
                                                   float* __restrict__ rgb_linear, uint8_t* __restrict__ rgb8,
                                                   unsigned long long* __restrict__ shadow_bits, unsigned long long* __restrict__ counters) {
     trace_nq_body<COUNT, NQCAP, FILTER, RS, XCD_ROWS, ROOTS_AGAIN, false, CAM, WIDE>(s, p, hit_id, t_out, rgb_linear, rgb8, shadow_bits, counters);
+}
+// The half-tile form (trace_nq_body's HALF): workgroups of two waves, 8x4 pixels each.  Same arguments, same grid (one workgroup per 8x8
+// tile), same outputs as k_trace_nq; launched with 128 threads.
+template <int NQCAP, bool FILTER, int MINW, int RS>
+__global__ __launch_bounds__(128, MINW) void k_trace_nq_half(DevScene s, DevParams p, int32_t* __restrict__ hit_id, float* __restrict__ t_out,
+                                                       float* __restrict__ rgb_linear, uint8_t* __restrict__ rgb8,
+                                                       unsigned long long* __restrict__ shadow_bits, unsigned long long* __restrict__ counters) {
+    trace_nq_body<false, NQCAP, FILTER, RS, false, false, false, false, false, false, true>(s, p, hit_id, t_out, rgb_linear, rgb8, shadow_bits, counters);
 }
 // closest hit, shadow rays and shading of a frame in one launch (SHADE)
 template <int NQCAP, bool FILTER, int MINW, int RS, bool XCD_ROWS = false>
