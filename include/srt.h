@@ -848,6 +848,80 @@ int srt_render_paths_refract(srt_scene* s, const srt_params* p, const srt_path_d
                              const srt_visibility* vis, const srt_refraction* refr, float* rgb_linear, uint8_t* rgb8, const srt_path_out* seg,
                              srt_stats* stats);
 
+/* Ambient occlusion: how open the surface is at a hit -- the hemisphere visibility behind ambient occlusion, sky visibility and contact
+ * shadows -- in ONE launch: the closest hit, the surface there, a tangent frame, n_dirs short occlusion rays from the hit point and their
+ * count; the chain srt_surface_rays -> a kernel of the caller's that writes n x n_dirs rays -> srt_occluded_masked -> a reduction, without
+ * the rays ever reaching memory.  srt_ao_rays finds the hit itself; srt_ao_hits takes hits the caller already holds (a render's hit_id / t
+ * with the frame's rays, any column of srt_trace_rays_multi) and walks no primary ray, as srt_surface_hits relates to srt_surface_rays:
+ * an AO pass over a rendered frame needs no second closest-hit walk.
+ * Unless said here everything is as for srt_trace_rays_masked / srt_surface_hits: the layout of rays and t_range with wide loads where they
+ * are 8-byte aligned, a NULL t_range, the ordering on `stream`, the rules of srt_scene_share, the private counter set, hipGraph capture of
+ * the _device forms without SRT_FLAG_COUNT_WORK, ONE launch with nothing allocated and nothing copied.
+ * DEFINITION.
+ *   The hit     srt_ao_rays: hit_id, t are bit for bit srt_trace_rays_masked's for that ray, interval and the ray mask vis->primary
+ *               (vis == NULL: all ones).  srt_ao_hits: row i is a miss row if hit_id[i] is outside [0, n_tris); t is taken as given.
+ *               The surface is srt_surface_out's: P = o + d * t (`point`), N the `normal` shading uses for that hit (the smooth one under
+ *               SRT_FLAG_SMOOTH_NORMALS).
+ *   The frame   all f32, no contraction, no transcendental:
+ *                   k  = (d.x * N.x + d.y * N.y) + d.z * N.z              (the dot of srt_surface_out.bounce)
+ *                   Nf = k > 0 ? -N : N                                   (the normal that FACES the ray; a NaN or zero k flips nothing)
+ *               and with (x, y, z) = Nf:
+ *                   s = copysignf(1.0f, z);   a = -1.0f / (s + z);   b = (x * y) * a
+ *                   T = ( 1.0f + ((s * x) * x) * a,   s * b,               (-s) * x )
+ *                   B = ( b,                          s + (y * y) * a,     -y       )
+ *               Nothing is normalised.  For a unit N the three are orthonormal to rounding, also at N = (0, 0, +-1).
+ *   The AO ray  j of a hit: origin P, not moved; direction, with (u, v, w) = dirs[j],
+ *                   w_i = (T_i * u + B_i * v) + Nf_i * w
+ *               so a table lives in the hit's LOCAL frame, z along the facing normal.
+ *   Blocked     direction j is blocked iff srt_occluded_masked answers 1 for the ray (P, w) with the interval (ao->t_min, ao->t_max), the ray
+ *               mask vis->shadow (vis == NULL: all ones) and skip_obj = (ao->flags & SRT_AO_SKIP_SELF) ? obj : -1.  Every rule of that call
+ *               is inherited as it stands: the closed interval in units of w, NaN bounds bounding nothing, a NaN t counting, hidden trees
+ *               not being walked.  vis->bounce is ignored.
+ *   A miss row  n_occluded 0, ao 1.0f, every word of occ_bits 0.
+ * Not validated: t_min <= 0 lets the hit's own triangle block near t = 0, depending on rounding (whole hemispheres then read as closed): use
+ * a small positive t_min, as with SRT_SHADOW_SELF.  Directions that are not unit or lie below the horizon, NaN normals and degenerate
+ * triangles give what the arithmetic gives; the call stays memory-safe.
+ * Flags: 0, SRT_FLAG_COUNT_WORK, SRT_FLAG_SMOOTH_NORMALS or both; SRT_FLAG_SMOOTH_NORMALS on a scene without normals fails as
+ * srt_surface_rays does.
+ * Errors, all before anything is touched.  SRT_ERR_ARG: a NULL handle; NULL rays with n > 0; NULL hit_id or t in srt_ao_hits with n > 0; a NULL
+ * ao, a NULL ao->dirs or n_dirs == 0; ao->flags with any bit but SRT_AO_SKIP_SELF; any other flag bit.  SRT_ERR_LIMIT: n_dirs >
+ * SRT_AO_DIRS_MAX; n * n_dirs >= 2^32.  n == 0: SRT_OK.
+ * out == NULL, or every field of it NULL: srt_ao_rays IS srt_trace_rays_masked without bary -- it launches that kernel when vis->primary is
+ * all ones or vis is NULL (that call takes its masks per ray, from an array; any other vis->primary runs this call's own kernel without a
+ * direction) --; srt_ao_hits launches nothing.
+ * Identities: srt_ao_hits fed srt_ao_rays' hit_id / t gives that call's bits in every field; results never depend on the order of the rays;
+ * a direction's bit does not depend on the other directions of the table -- the row of a table is the concatenation of the rows of its
+ * parts --; vis = { ~0, ~0, ~0 } equals vis == NULL, and with a table of all ones both equal the call on a scene whose masks were never set.
+ * The host forms stage rays, t_range, dirs, hit_id / t and the outputs through the handle's pinned block, then wait.  *stats: primary_rays = n,
+ * hit_rays, shadow_rays = hit_rays x n_dirs (0 where nothing of srt_ao_out is wanted: no AO ray is walked then); under
+ * SRT_FLAG_COUNT_WORK the primary counters are srt_trace_rays_masked's (0 in srt_ao_hits) and the shadow counters count the AO walks as they run -- objects in order, hidden and skipped objects not entered, one slab test per
+ * node met, triangle tests up to and including the first candidate in range.
+ * NOT HERE: a per-ray rotation or jitter of the table; weights per direction (a cosine-distributed table makes the plain count
+ * cosine-weighted); bent normals; a frame form without a ray array. */
+#define SRT_AO_DIRS_MAX  1024
+#define SRT_AO_SKIP_SELF 1u      /* the hit object's own tree is left out of the AO walks (default: it is walked) */
+typedef struct srt_ao_desc {
+    uint32_t     n_dirs;         /* 1 .. SRT_AO_DIRS_MAX */
+    const float* dirs;           /* n_dirs x 3 (x, y, z) in the hit's LOCAL frame, z along the facing normal; a host pointer in the host forms, a
+                                    DEVICE pointer in the _device forms (read when the kernel runs, as path->reflectance is) */
+    float        t_min, t_max;   /* every AO ray blocks only inside the closed (t_min, t_max), in units of its direction */
+    uint32_t     flags;          /* 0 or SRT_AO_SKIP_SELF */
+} srt_ao_desc;
+typedef struct srt_ao_out {      /* device pointers in the _device forms, host pointers in the host forms; any may be NULL, and so may the struct */
+    uint32_t* n_occluded;        /* n        directions that are blocked */
+    float*    ao;                /* n        (float)(n_dirs - n_occluded) / (float)n_dirs: one IEEE divide */
+    uint32_t* occ_bits;          /* n x W, W = (n_dirs + 31) / 32: bit (k & 31) of word k >> 5 set iff direction k is blocked; bits >= n_dirs are 0 */
+} srt_ao_out;
+int srt_ao_rays_device(srt_scene* s, uint32_t n, const float* d_rays, const float* d_t_range /* n x 2 or NULL */, uint32_t flags,
+                       const srt_ao_desc* ao, const srt_visibility* vis /* or NULL */, void* stream, int32_t* d_hit_id, float* d_t,
+                       const srt_ao_out* out);
+int srt_ao_rays(srt_scene* s, uint32_t n, const float* rays, const float* t_range, uint32_t flags, const srt_ao_desc* ao,
+                const srt_visibility* vis, int32_t* hit_id, float* t, const srt_ao_out* out, srt_stats* stats);
+int srt_ao_hits_device(srt_scene* s, uint32_t n, const float* d_rays, const int32_t* d_hit_id, const float* d_t, uint32_t flags,
+                       const srt_ao_desc* ao, const srt_visibility* vis /* or NULL */, void* stream, const srt_ao_out* out);
+int srt_ao_hits(srt_scene* s, uint32_t n, const float* rays, const int32_t* hit_id, const float* t, uint32_t flags,
+                const srt_ao_desc* ao, const srt_visibility* vis, const srt_ao_out* out, srt_stats* stats);
+
 /* Device-resident size of the scene records and the per-record algorithmic byte sizes used by
  * the bytes model: 32 B per node test, 36 B per triangle test. */
 uint64_t srt_scene_device_bytes(const srt_scene* s);

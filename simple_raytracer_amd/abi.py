@@ -136,6 +136,25 @@ class Refraction(C.Structure):
     _fields_ = [("ior", C.c_void_p), ("flags", C.c_uint32)]
 
 
+SRT_AO_DIRS_MAX = 1024
+SRT_AO_SKIP_SELF = 1
+
+
+class AoDesc(C.Structure):
+    """srt_ao_desc: the direction table of an ambient-occlusion call as an address (n_dirs x 3 floats in the hit's local frame, z along the
+    facing normal; a host array in the host forms, a device pointer in the _device forms), the closed interval every AO ray blocks in, and
+    flags: 0, or SRT_AO_SKIP_SELF = the hit object's own tree is left out of the AO walks."""
+    _fields_ = [("n_dirs", C.c_uint32), ("dirs", C.c_void_p), ("t_min", C.c_float), ("t_max", C.c_float), ("flags", C.c_uint32)]
+
+
+class AoOut(C.Structure):
+    """srt_ao_out: the arrays an ambient-occlusion call fills, as addresses; 0 = not wanted."""
+    _fields_ = [("n_occluded", C.c_void_p), ("ao", C.c_void_p), ("occ_bits", C.c_void_p)]
+
+
+# the fields of srt_ao_out: name -> dtype (n_occluded and ao: one entry a ray; occ_bits: (n_dirs + 31) // 32 words a ray)
+AO_FIELDS = {"n_occluded": np.uint32, "ao": np.float32, "occ_bits": np.uint32}
+
 # the fields of srt_path_out: name -> (dtype, floats or ints per ray and segment)
 PATH_FIELDS = {"hit_id": (np.int32, 1), "t": (np.float32, 1), "obj": (np.int32, 1), "rgb_linear": (np.float32, 3), "rays": (np.float32, 6)}
 

@@ -154,8 +154,29 @@ def build_surface_lane_stores(force=False):
     return LIB_SURFACE_LANE
 
 
+LIB_AO_DEAL = {True: os.path.join(HERE, "libsrt_hip_ao_spread.so"), False: os.path.join(HERE, "libsrt_hip_ao_block.so")}
+
+
+def build_ao_deal(spread, force=False):
+    """The ambient-occlusion calls with ONE deal of rays to waves whatever the direction count (-DSRT_AO_SPREAD_FROM, srt_hip.hip): the
+    spread deal from 0 directions on (libsrt_hip_ao_spread.so) or never (libsrt_hip_ao_block.so).  Never loaded by the product;
+    tools/ray_query_probe.py --ao times both beside the shipped rule."""
+    out = LIB_AO_DEAL[bool(spread)]
+    deps = [os.path.join(CSRC, f) for f in ("srt_hip.hip", "srt_device.h", "srt_kernels.h", "srt_packet.h", "srt_query.h")] + [os.path.join(HERE, "..", "include", "srt.h")]
+    if not force and not _stale(out, deps):
+        return out
+    cmd = [hipcc()] + HIPCC_FLAGS + ["-DSRT_AO_SPREAD_FROM=" + ("0u" if spread else "0xFFFFFFFFu"), "-o", out, os.path.join(CSRC, "srt_hip.hip")]
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    if r.returncode:
+        sys.stderr.write(r.stdout + r.stderr)
+        raise RuntimeError("hipcc failed for the ambient-occlusion deal build")
+    return out
+
+
 if __name__ == "__main__":
-    if "--diag" in sys.argv:
+    if "--ao-deals" in sys.argv:
+        print(build_ao_deal(True), build_ao_deal(False))
+    elif "--diag" in sys.argv:
         print(build_diag(verbose=True))
     elif "--surface-lane-stores" in sys.argv:
         print(build_surface_lane_stores())

@@ -172,6 +172,9 @@ struct srt_scene {
     // srt_shade_paths: the reflectance table of a host call (capacity counts objects) and the per-segment sums (capacity counts depth x n rows);
     // the other per-segment rows go through rq_hit / rq_t / rq_sobj / rq_sbounce, depth units a ray
     DevArray<float> rq_refl; DevArray<float> rq_ior; DevArray<float, 3> rq_plin;
+    // srt_ao_rays / srt_ao_hits: the direction table of a host call (capacity counts directions) and the three arrays of srt_ao_out (rq_aobits:
+    // capacity counts words, W a ray); a caller's hits go through rq_skip / rq_tin as srt_surface_hits' do
+    DevArray<float, 3> rq_aodirs; DevArray<uint32_t> rq_aocnt; DevArray<float> rq_aoval; DevArray<uint32_t> rq_aobits;
     DevArray<float, 3> d_qlights; Pinned<float, 3> h_qlights; uint32_t qlights_valid = 0;
     Event qlights_sent; hipStream_t qlights_stream = nullptr; bool qlights_settled = true;
     int n_cu = 256;
@@ -1968,6 +1971,40 @@ static int surface_hits_device_impl(srt_scene* s, uint32_t n, const float* d_ray
     return launch_query(builds[build_index((flags & SRT_FLAG_SMOOTH_NORMALS) != 0)], q.grid, q.stream, s->dev, n, d_rays, rays_wide(d_rays), d_hit_id, d_t, *out);
 }
 
+// srt_ao_rays / srt_ao_hits: the hemisphere visibility at each hit, one launch (k_query_ao).  hits: the hits a caller of srt_ao_hits
+// brings (NULL: srt_ao_rays, which walks for its own and returns them in d_hit_id / d_t).
+static int check_ao(const srt_scene* s, uint32_t n, const float* rays, const QueryHits* hits, uint32_t flags, const srt_ao_desc* ao) {
+    SRT_TRY(check_surface(s, n, rays, flags, SRT_FLAG_COUNT_WORK | SRT_FLAG_SMOOTH_NORMALS));
+    if (hits && n && (!hits->hit_id || !hits->t)) return SRT_ERR_ARG;
+    if (!ao || !ao->dirs || ao->n_dirs == 0 || (ao->flags & ~(uint32_t)SRT_AO_SKIP_SELF)) return SRT_ERR_ARG;
+    if (ao->n_dirs > SRT_AO_DIRS_MAX || (uint64_t)n * ao->n_dirs >= (1ull << 32)) return SRT_ERR_LIMIT;
+    return SRT_OK;
+}
+static inline bool ao_wanted(const srt_ao_out* o) { return o && (o->n_occluded || o->ao || o->occ_bits); }
+// The deal of rays to waves: the spread deal from this many directions on.  The threshold is borrowed from QueryShade::spread (n_lights >= 8)
+// and was not measured itself; the two deals were timed at 16 and 64 directions only ("Ambient occlusion").
+#ifndef SRT_AO_SPREAD_FROM
+#define SRT_AO_SPREAD_FROM 8u
+#endif
+
+static int ao_device_impl(srt_scene* s, uint32_t n, const float* d_rays, const float* d_t_range, const QueryHits* hits, uint32_t flags, const srt_ao_desc* ao,
+                          const srt_visibility* vis, hipStream_t stream, int32_t* d_hit_id, float* d_t, const srt_ao_out* out, bool count_hits) {
+    SRT_TRY(check_ao(s, n, d_rays, hits, flags, ao));
+    const bool wanted = ao_wanted(out);
+    // nothing of srt_ao_out wanted, every object visible to the primary rays: srt_ao_rays is srt_trace_rays_masked without bary, and launches its kernel
+    if (!hits && !wanted && (!vis || vis->primary == ~0u))
+        return trace_rays_device_impl(s, n, d_rays, d_t_range, flags & SRT_FLAG_COUNT_WORK, stream, d_hit_id, d_t, nullptr, count_hits, RayMask{ .masked = true });
+    if (!n || (hits && !wanted && !count_hits)) return SRT_OK;
+    const bool count = (flags & SRT_FLAG_COUNT_WORK) != 0, smooth = (flags & SRT_FLAG_SMOOTH_NORMALS) != 0;
+    QueryLaunch q;
+    SRT_TRY(query_prologue(s, n, stream, nullptr, count || count_hits, &q));
+    const QueryAo p = { ao->dirs, wanted ? ao->n_dirs : 0u, ao->t_min, ao->t_max, (ao->flags & SRT_AO_SKIP_SELF) ? 1u : 0u, ao->n_dirs >= SRT_AO_SPREAD_FROM ? 1u : 0u };
+    static const std::array builds = { BUILDS_3(k_query_ao) };
+    return launch_query(builds[build_index(count, smooth, hits)], q.grid, q.stream, s->dev, n, d_rays, rays_wide(d_rays), query_range(d_t_range),
+                        vis ? query_mask(s, vis) : query_mask(s, (const uint32_t*)nullptr),      // (a NULL vis: all ones against the scene's table)
+                        p, hits ? *hits : QueryHits{}, d_hit_id, d_t, wanted ? *out : srt_ao_out{}, q.ctr);
+}
+
 // The host entry points: what the caller brings goes through the pinned staging block (stage_acquire, as every update does) into the
 // handle's own buffers on the scene's stream, the device entry point runs behind it, the call waits and copies the results out.
 // One array of a host call that comes from host memory: `bytes` from src to dst on the device.  src NULL, or no bytes: absent, and it
@@ -2215,6 +2252,41 @@ static int surface_hits_impl(srt_scene* s, uint32_t n, const float* rays, const 
         return surface_hits_device_impl(s, n, i_rays.on_device(), i_hit.on_device(), i_t.on_device(), flags, st, dev);
     }, i_rays, i_hit, i_t);
 }
+
+// What the host forms of the two AO calls share: the direction table the call brings, the three arrays of the caller's srt_ao_out, and the
+// round trip of them, in which launch(stream, ao, out) gets the caller's structs with the handle's buffers in the place of the host arrays.
+struct AoArrays {
+    QueryArray<float, 3> dirs; QueryArray<uint32_t, 1> cnt; QueryArray<float, 1> val; QueryArray<uint32_t, 1> bits;
+    template <typename Launch, typename... More>      // more: the call's other arrays
+    int round_trip(srt_scene* s, const srt_ao_desc* ao, Launch launch, const More&... more) const {
+        return query_round_trip(s, [&](hipStream_t st) -> int {
+            const srt_ao_desc dao = { ao->n_dirs, dirs.on_device(), ao->t_min, ao->t_max, ao->flags };
+            const srt_ao_out dev = { cnt.on_device(), val.on_device(), bits.on_device() };
+            return launch(st, &dao, &dev);
+        }, more..., dirs, cnt, val, bits);
+    }
+};
+
+// hits: the hits a caller of srt_ao_hits brings (their ids go through rq_skip, their t through rq_tin), or NULL: srt_ao_rays
+static int ao_impl(srt_scene* s, uint32_t n, const float* rays, const float* t_range, const QueryHits* hits, uint32_t flags, const srt_ao_desc* ao,
+                   const srt_visibility* vis, int32_t* hit_id, float* t, const srt_ao_out* out, srt_stats* stats) {
+    SRT_TRY(check_ao(s, n, rays, hits, flags, ao));
+    if (stats) std::memset(stats, 0, sizeof(*stats));
+    if (!n || (hits && !stats && !ao_wanted(out))) return SRT_OK;
+    const srt_ao_out h = out ? *out : srt_ao_out{};
+    const size_t words = (size_t)n * ((ao->n_dirs + 31u) / 32u);
+    const AoArrays a = { query_in(ao->dirs, s->rq_aodirs, ao->n_dirs), query_out(h.n_occluded, s->rq_aocnt, n), query_out(h.ao, s->rq_aoval, n),
+                         query_out(h.occ_bits, s->rq_aobits, words) };
+    const auto o_hit = query_out(hit_id, s->rq_hit, n); const auto o_t = query_out(t, s->rq_t, n);
+    const auto i_rays = query_in(rays, s->rq_rays, n); const auto i_range = query_in(t_range, s->rq_range, n);
+    const auto i_hit = query_in(hits ? hits->hit_id : nullptr, s->rq_skip, n); const auto i_t = query_in(hits ? hits->t : nullptr, s->rq_tin, n);
+    SRT_TRY(a.round_trip(s, ao, [&](hipStream_t st, const srt_ao_desc* dao, const srt_ao_out* dev) {
+        const QueryHits dh = { i_hit.on_device(), i_t.on_device() };
+        return ao_device_impl(s, n, i_rays.on_device(), i_range.on_device(), hits ? &dh : nullptr, flags, dao, vis, st, o_hit.on_device(), o_t.on_device(), dev,
+                              stats != nullptr);
+    }, o_hit, o_t, i_rays, i_range, i_hit, i_t));
+    return stats ? query_stats(s, n, ao_wanted(out) ? ao->n_dirs : 0u, stats) : SRT_OK;      // (nothing wanted: no AO ray was walked)
+}
 }      // extern "C++"
 
 int srt_trace_rays_device(srt_scene* s, uint32_t n, const float* d_rays, uint32_t flags, void* stream, int32_t* d_hit_id, float* d_t, float* d_bary) {
@@ -2363,6 +2435,25 @@ int srt_surface_hits_device(srt_scene* s, uint32_t n, const float* d_rays, const
 }
 int srt_surface_hits(srt_scene* s, uint32_t n, const float* rays, const int32_t* hit_id, const float* t, uint32_t flags, const srt_surface_out* out) {
     return guarded([&] { return surface_hits_impl(s, n, rays, hit_id, t, flags, out); });
+}
+
+int srt_ao_rays_device(srt_scene* s, uint32_t n, const float* d_rays, const float* d_t_range, uint32_t flags, const srt_ao_desc* ao, const srt_visibility* vis, void* stream,
+                       int32_t* d_hit_id, float* d_t, const srt_ao_out* out) {
+    return guarded([&] { return ao_device_impl(s, n, d_rays, d_t_range, nullptr, flags, ao, vis, (hipStream_t)stream, d_hit_id, d_t, out, false); });
+}
+int srt_ao_rays(srt_scene* s, uint32_t n, const float* rays, const float* t_range, uint32_t flags, const srt_ao_desc* ao, const srt_visibility* vis, int32_t* hit_id, float* t,
+                const srt_ao_out* out, srt_stats* stats) {
+    return guarded([&] { return ao_impl(s, n, rays, t_range, nullptr, flags, ao, vis, hit_id, t, out, stats); });
+}
+int srt_ao_hits_device(srt_scene* s, uint32_t n, const float* d_rays, const int32_t* d_hit_id, const float* d_t, uint32_t flags, const srt_ao_desc* ao,
+                       const srt_visibility* vis, void* stream, const srt_ao_out* out) {
+    const QueryHits hits = { d_hit_id, d_t };
+    return guarded([&] { return ao_device_impl(s, n, d_rays, nullptr, &hits, flags, ao, vis, (hipStream_t)stream, nullptr, nullptr, out, false); });
+}
+int srt_ao_hits(srt_scene* s, uint32_t n, const float* rays, const int32_t* hit_id, const float* t, uint32_t flags, const srt_ao_desc* ao, const srt_visibility* vis,
+                const srt_ao_out* out, srt_stats* stats) {
+    const QueryHits hits = { hit_id, t };
+    return guarded([&] { return ao_impl(s, n, rays, nullptr, &hits, flags, ao, vis, nullptr, nullptr, out, stats); });
 }
 
 void* srt_host_alloc(size_t bytes) {

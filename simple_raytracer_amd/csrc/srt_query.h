@@ -441,18 +441,22 @@ struct WaveHits { uint32_t nh, rank; };       // hits in the wave; this lane's r
 // blocks only inside the closed (t_min, t_max), in units of L - so, and with self != 0 the hit object's own tree is walked too.  self costs
 // nothing in the walk: shade_hits_rank leaves (-1, -1) -- "skip no object", as k_query_any has it -- where the object's node range would go.
 struct ShadowRule { float t_min, t_max; uint32_t self; };
-template <bool SMOOTH, bool SHADOW = false>
+// GIVEN (k_query_ao on hits the caller brings): t comes in with the hit and is taken as it is -- nothing recomputes it, a lane without a hit
+// keeps what it was given.
+template <bool SMOOTH, bool SHADOW = false, bool GIVEN = false>
 __device__ __forceinline__ WaveHits shade_hits_rank(const DevScene& s, const bool is_hit, const int32_t id, const V3 o, const V3 d, float& t, Surface& f,
                                                     float (*wray)[64], const uint32_t walk_self = 0u) {
-    t = __builtin_inff();
+    if (!GIVEN) t = __builtin_inff();
     f.color = mk(0.0f, 0.0f, 0.0f); f.nrm = f.color; f.ka = 0.0f; f.ks = 0.0f; f.sh = 1.0f;
     const unsigned long long hm = __ballot(is_hit);
     const uint32_t nh = (uint32_t)__popcll(hm), rank = lane_prefix(hm);
     __builtin_amdgcn_wave_barrier();                    // every lane has read its key: the slots are free
     if (is_hit) {
-        V3 p1, e1, e2;
-        load_tri_edges(reinterpret_cast<const float4*>(s.tris), (size_t)id, p1, e1, e2);
-        t = ray_triangle(o, d, p1, e1, e2);             // the winner's t with its own bits (incl. the sign of a zero); the walk's value, hence in range
+        if (!GIVEN) {
+            V3 p1, e1, e2;
+            load_tri_edges(reinterpret_cast<const float4*>(s.tris), (size_t)id, p1, e1, e2);
+            t = ray_triangle(o, d, p1, e1, e2);         // the winner's t with its own bits (incl. the sign of a zero); the walk's value, hence in range
+        }
         const V3 P = o + d * t;                         // shadowIntersection:325-326 in camera mode: so = o + d * t
         int2 self = s.obj_range[s.tri_obj[id]];
         if (SHADOW && walk_self) self = make_int2(-1, -1);
@@ -714,6 +718,132 @@ __global__ __launch_bounds__(256) void k_query_surface_hits(DevScene s, uint32_t
     if (is_hit) f = surface_at(s, id, o, d, t, SMOOTH);
     const size_t left = (size_t)n_rays - base;
     surface_store(s, out, base, lane, (uint32_t)(left < 64 ? left : 64), is_hit, id, o, d, t, f, stage_all[wave]);
+}
+
+// =================================================================================================
+// Ambient occlusion (srt_ao_rays, srt_ao_hits): per hit, n_dirs occlusion rays from the hit point along a table of directions given in the
+// hit's own frame, and how many of them are blocked -- in ONE launch: the AO rays are made in registers and never reach memory.
+// One template covers both entry points.  Phase 1 -- HITS == false: query_walk exactly as k_query_closest_masked instantiates it (the RANGE
+// + MASK build, a NULL interval running as (NaN, NaN)) with the mask qm.primary; HITS == true: the caller's hit_id / t are loaded, an id
+// outside [0, n_tris) is a miss, and nothing is walked (the build has no queue).
+// Phase 2 is k_query_shade's, a wave at a time with no barrier between waves: shade_hits_rank ranks the wave's hits and leaves P and the
+// skip range ((-1, -1) unless SRT_AO_SKIP_SELF) in the wave's LDS by rank; the hit's own lane adds Nf, the normal that faces the ray, in
+// the three rows that are left -- the walk's 8 x 64 slots hold P (3), the range (2) and Nf (3) exactly.  The directions go in chunks of up
+// to 64; a chunk's nh x m items (rank, direction) are dealt to the 64 lanes round after round, consecutive lanes taking consecutive
+// directions of one hit; each lane builds the frame from Nf (ao_frame: about 15 VALU operations and one divide per item; keeping T and
+// B in LDS instead would take 6 more rows a wave, 6 KB a workgroup on top of k_query_closest_masked's 20 KB, for 6 more LDS reads per
+// item in their place), forms w, runs any_hit_range<COUNT, true, true, true> with qm.shadow and ORs its bit into the hit's 64-bit word
+// (`best`).
+// After a chunk the ray's own lane adds popcll to its count and stores the chunk's two words of occ_bits; a lane without a hit stores zeros.
+// dirs is read from global memory per item: 12 B at consecutive addresses for consecutive lanes, the whole table at most 12 KB.
+// The deal of rays to waves is k_query_shade's, QueryAo::spread included.
+// counters: as k_query_shade's -- [1] / [2] of phase 1 (0 under HITS), [3] / [4] of the AO walks (COUNT), the hit shards.
+// =================================================================================================
+struct QueryAo {
+    const float* dirs;            // device, n_dirs x 3; n_dirs == 0: no phase 2 (nothing of srt_ao_out is wanted)
+    uint32_t n_dirs;
+    float t_min, t_max;           // the AO rays' interval
+    uint32_t skip_self;           // SRT_AO_SKIP_SELF
+    uint32_t spread;              // QueryShade::spread
+};
+struct QueryHits { const int32_t* hit_id; const float* t; };      // srt_ao_hits: the hits the caller brings
+
+// The tangent and the bitangent of the frame whose third axis is n (include/srt.h, "Ambient occlusion"): no branch, no transcendental;
+// every step f32 without contraction.
+__device__ __forceinline__ void ao_frame(const V3 n, V3& T, V3& B) {
+    const float s = __builtin_copysignf(1.0f, n.z), a = -1.0f / (s + n.z), b = (n.x * n.y) * a;
+    T = mk(1.0f + ((s * n.x) * n.x) * a, s * b, (-s) * n.x);
+    B = mk(b, s + (n.y * n.y) * a, -n.y);
+}
+
+// Phase 2 for the 64 rays of one wave after shade_hits_rank, as shade_hits_lights is for light samples.  wray[5..7][rank] is written here.
+// Returns the lane's blocked directions; every live lane stores its row of occ_bits chunk by chunk.
+template <bool COUNT>
+__device__ __forceinline__ uint32_t ao_hits_dirs(const DevScene& s, const QueryAo& p, const QueryMask& qm, const uint32_t lane, const bool live, const bool is_hit,
+                                                 const WaveHits wh, const V3 d, const V3 N, const size_t ri, uint32_t* __restrict__ occ_bits, float (*wray)[64],
+                                                 unsigned long long* best, unsigned long long& n_node_s, unsigned long long& n_tri_s) {
+    const uint32_t nh = wh.nh, rank = wh.rank, W = (p.n_dirs + 31u) >> 5;
+    if (is_hit) {
+        const float k = (d.x * N.x + d.y * N.y) + d.z * N.z;       // mirror_dir's dot
+        const V3 Nf = k > 0.0f ? neg(N) : N;
+        wray[5][rank] = Nf.x; wray[6][rank] = Nf.y; wray[7][rank] = Nf.z;
+    }
+    uint32_t blocked = 0;
+    for (uint32_t l0 = 0; l0 < p.n_dirs; l0 += 64u) {                                               // wave-uniform
+        const uint32_t m = p.n_dirs - l0 < 64u ? p.n_dirs - l0 : 64u;
+        if (is_hit) best[rank] = 0ull;
+        __builtin_amdgcn_wave_barrier();
+        const uint32_t items = nh * m;                                                              // <= 4096
+        for (uint32_t w = lane; w < items; w += 64u) {
+            const uint32_t r = w / m, k = w - r * m;
+            const V3 P = mk(wray[0][r], wray[1][r], wray[2][r]);
+            const int2 self = make_int2(__float_as_int(wray[3][r]), __float_as_int(wray[4][r]));
+            const V3 Nf = mk(wray[5][r], wray[6][r], wray[7][r]);
+            V3 T, B;
+            ao_frame(Nf, T, B);
+            const float* dp = p.dirs + (size_t)(l0 + k) * 3;
+            const float u = dp[0], v = dp[1], z = dp[2];
+            const V3 wd = mk((T.x * u + B.x * v) + Nf.x * z, (T.y * u + B.y * v) + Nf.y * z, (T.z * u + B.z * v) + Nf.z * z);
+            if (any_hit_range<COUNT, true, true, true>(s, self, P, wd, n_node_s, n_tri_s, p.t_min, p.t_max, qm.obj, qm.shadow)) atomicOr(&best[r], 1ull << k);
+        }
+        __builtin_amdgcn_wave_barrier();
+        const unsigned long long mask = is_hit ? best[rank] : 0ull;
+        blocked += (uint32_t)__popcll(mask);
+        if (occ_bits && live) {
+            const uint32_t w0 = l0 >> 5;                                                            // the chunk's two words: w0 (< W) and w0 + 1
+            occ_bits[ri * W + w0] = (uint32_t)mask;
+            if (w0 + 1u < W) occ_bits[ri * W + w0 + 1u] = (uint32_t)(mask >> 32);
+        }
+        __builtin_amdgcn_wave_barrier();
+    }
+    return blocked;
+}
+
+template <bool COUNT, bool SMOOTH, bool HITS>
+__global__ __launch_bounds__(256) void k_query_ao(DevScene s, uint32_t n_rays, const float* __restrict__ rays, uint32_t wide, QueryRange tr, QueryMask qm, QueryAo p,
+                                                  QueryHits given, int32_t* __restrict__ hit_id, float* __restrict__ t_out, srt_ao_out out,
+                                                  unsigned long long* __restrict__ counters) {
+    __shared__ unsigned long long best_all[256];
+    __shared__ float ray_all[4][8][64];
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    unsigned long long* best = best_all + wave * 64;
+    float (*wray)[64] = ray_all[wave];
+    const size_t n_waves = (size_t)gridDim.x * 4, wv = (size_t)blockIdx.x * 4 + wave;
+    const size_t ri = p.spread ? ((size_t)(lane >> 3) * n_waves + wv) * 8 + (lane & 7u) : (size_t)blockIdx.x * 256 + threadIdx.x;
+    const bool live = ri < (size_t)n_rays;
+    unsigned long long n_node = 0, n_tri = 0, n_node_s = 0, n_tri_s = 0;
+    V3 o = mk(0.0f, 0.0f, 0.0f), d = mk(0.0f, 0.0f, 1.0f);
+    if (live) load_ray(rays, ri, wide != 0, o, d);
+    bool is_hit;
+    int32_t id = -1;
+    float t = __builtin_inff();
+    if constexpr (HITS) {
+        if (live) { id = given.hit_id[ri]; t = given.t[ri]; }
+        is_hit = id >= 0 && (uint32_t)id < s.n_tris;
+    } else {
+        __shared__ uint32_t q_all[4][QCAP];             // the walk's queue: the HITS builds have none
+        float t_min = __builtin_nanf(""), t_max = __builtin_nanf("");
+        if (tr.t && live) load_range(tr, ri, t_min, t_max);
+        query_walk<COUNT, true, MergeClosest, true>(s, live, o, d, lane, q_all[wave], MergeClosest{ best }, wray, n_node, n_tri, t_min, t_max, qm.obj, qm.primary);
+        const unsigned long long key = live ? best[lane] : ~0ull;
+        is_hit = key != ~0ull;
+        id = is_hit ? (int32_t)(uint32_t)key : -1;
+    }
+    Surface f;
+    const WaveHits wh = shade_hits_rank<SMOOTH, true, HITS>(s, is_hit, id, o, d, t, f, wray, p.skip_self ? 0u : 1u);
+    if (!HITS && live) {
+        if (hit_id) hit_id[ri] = id;
+        if (t_out) t_out[ri] = t;
+    }
+    if (p.n_dirs) {                                     // wave-uniform
+        const uint32_t blocked = ao_hits_dirs<COUNT>(s, p, qm, lane, live, is_hit, wh, d, f.nrm, ri, out.occ_bits, wray, best, n_node_s, n_tri_s);
+        if (live) {
+            if (out.n_occluded) out.n_occluded[ri] = blocked;
+            if (out.ao) out.ao[ri] = (float)(p.n_dirs - blocked) / (float)p.n_dirs;
+        }
+    }
+    if (counters) count_hits(counters, is_hit, blockIdx.x);
+    if (COUNT) { wave_add(counters + 1, n_node); wave_add(counters + 2, n_tri); wave_add(counters + 3, n_node_s); wave_add(counters + 4, n_tri_s); }
 }
 
 // =================================================================================================

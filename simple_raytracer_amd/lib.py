@@ -29,7 +29,8 @@ ABI_SYMBOLS = ("srt_params_default", "srt_light_staircase", "srt_rows_owned", "s
                "srt_render_paths_device", "srt_render_paths", "srt_shade_paths_shadow_device", "srt_shade_paths_shadow", "srt_render_paths_shadow_device",
                "srt_render_paths_shadow", "srt_scene_set_object_masks", "srt_trace_rays_masked_device", "srt_trace_rays_masked", "srt_occluded_masked_device",
                "srt_occluded_masked", "srt_shade_paths_masked_device", "srt_shade_paths_masked", "srt_render_paths_masked_device", "srt_render_paths_masked",
-               "srt_shade_paths_refract_device", "srt_shade_paths_refract", "srt_render_paths_refract_device", "srt_render_paths_refract")
+               "srt_shade_paths_refract_device", "srt_shade_paths_refract", "srt_render_paths_refract_device", "srt_render_paths_refract",
+               "srt_ao_rays_device", "srt_ao_rays", "srt_ao_hits_device", "srt_ao_hits")
 MULTI_HIT_MAX = 16                # SRT_MULTI_HIT_MAX
 
 _f32p, _i32p, _u8p, _u32p = C.POINTER(C.c_float), C.POINTER(C.c_int32), C.POINTER(C.c_uint8), C.POINTER(C.c_uint32)
@@ -174,6 +175,14 @@ def load(path=None):
         L.srt_render_paths_refract_device.argtypes = L.srt_render_paths_masked_device.argtypes[:5] + [_refr] + L.srt_render_paths_masked_device.argtypes[5:]
         L.srt_render_paths_refract.argtypes = L.srt_render_paths_masked.argtypes[:5] + [_refr] + L.srt_render_paths_masked.argtypes[5:]
         for f in (L.srt_shade_paths_refract_device, L.srt_shade_paths_refract, L.srt_render_paths_refract_device, L.srt_render_paths_refract):
+            f.restype = C.c_int
+        # ambient occlusion: an srt_ao_desc* and an srt_visibility* after the flags, an srt_ao_out* last of the outputs
+        _ao, _aout = C.POINTER(abi.AoDesc), C.POINTER(abi.AoOut)
+        L.srt_ao_rays_device.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, _ao, _vis, C.c_void_p, C.c_void_p, C.c_void_p, _aout]
+        L.srt_ao_rays.argtypes = [C.c_void_p, C.c_uint32, _f32p, _f32p, C.c_uint32, _ao, _vis, _i32p, _f32p, _aout, C.POINTER(abi.Stats)]
+        L.srt_ao_hits_device.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, _ao, _vis, C.c_void_p, _aout]
+        L.srt_ao_hits.argtypes = [C.c_void_p, C.c_uint32, _f32p, _i32p, _f32p, C.c_uint32, _ao, _vis, _aout, C.POINTER(abi.Stats)]
+        for f in (L.srt_ao_rays_device, L.srt_ao_rays, L.srt_ao_hits_device, L.srt_ao_hits):
             f.restype = C.c_int
         L.srt_strerror.argtypes = [C.c_int]
         L.srt_strerror.restype = C.c_char_p
@@ -475,6 +484,61 @@ class DeviceScene:
         _check(self.L.srt_surface_hits_device(self.h, n, C.c_void_p(rays), C.c_void_p(hit_id), C.c_void_p(t), abi.SRT_FLAG_SMOOTH_NORMALS if smooth else 0,
                                               C.c_void_p(stream), C.byref(so)), "srt_surface_hits_device")
 
+    def ao_rays(self, rays, dirs, t_min=1e-3, t_max=np.inf, t_range=None, skip_self=False, visibility=None, smooth=False, count=False,
+                want=("hit_id", "t", "n_occluded", "ao", "occ_bits")):
+        """srt_ao_rays: the closest hit of every ray of `rays` (n x 6, host array) and how open the surface is there -- `dirs` (K x 3, in the
+        hit's local frame, z along the normal that faces the ray: ao_directions) are turned into the hit's frame and walked as occlusion
+        rays from the hit point; a direction is blocked iff something lies inside the closed (t_min, t_max), in units of the direction.
+        Returns a dict of the arrays named in `want` (hit_id n, t n, n_occluded n uint32, ao n = (K - n_occluded) / K, occ_bits n x W uint32
+        with W = (K + 31) // 32, bit k & 31 of word k >> 5 for direction k) + 'stats'.  t_range (n x 2): the interval of the closest hit.
+        skip_self: SRT_AO_SKIP_SELF, the hit's own object blocks nothing.  visibility: None, or (primary, bounce, shadow) -- the closest
+        hit is walked with primary, the AO rays with shadow.  smooth: SRT_FLAG_SMOOTH_NORMALS; count: SRT_FLAG_COUNT_WORK."""
+        r = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
+        n = r.shape[0]
+        desc, table = _ao_desc(dirs, t_min, t_max, skip_self)
+        out, g = _outputs(want, (n,), _HIT)
+        aout, arrays = _ao_out(want, n, desc.n_dirs)
+        out.update(arrays)
+        st = abi.Stats()
+        _check(self.L.srt_ao_rays(self.h, n, _host(r, _f32p), _host(_t_range(t_range, n), _f32p), _ao_flags(smooth, count), C.byref(desc), _vis_ref(visibility),
+                                  g("hit_id"), g("t"), C.byref(aout), C.byref(st)), "srt_ao_rays")
+        out["stats"] = st.as_dict()
+        return out
+
+    def ao_hits(self, rays, hit_id, t, dirs, t_min=1e-3, t_max=np.inf, skip_self=False, visibility=None, smooth=False, count=False,
+                want=("n_occluded", "ao", "occ_bits")):
+        """srt_ao_hits: ao_rays for hits the caller already holds -- `hit_id` (n) and `t` (n) of the rays `rays` (n x 6, host arrays): a
+        render's with the frame's rays, trace_rays', a column of trace_rays_multi.  No closest-hit walk; an id outside [0, n_tris) is a
+        miss row (n_occluded 0, ao 1).  Returns a dict of the arrays named in `want` + 'stats'."""
+        r = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
+        n = r.shape[0]
+        hid = np.ascontiguousarray(hit_id, np.int32).reshape(-1); tt = np.ascontiguousarray(t, np.float32).reshape(-1)
+        assert hid.shape[0] == n and tt.shape[0] == n, "hit_id, t: one entry per ray"
+        desc, table = _ao_desc(dirs, t_min, t_max, skip_self)
+        aout, out = _ao_out(want, n, desc.n_dirs)
+        st = abi.Stats()
+        _check(self.L.srt_ao_hits(self.h, n, _host(r, _f32p), _host(hid, _i32p), _host(tt, _f32p), _ao_flags(smooth, count), C.byref(desc), _vis_ref(visibility),
+                                  C.byref(aout), C.byref(st)), "srt_ao_hits")
+        out["stats"] = st.as_dict()
+        return out
+
+    def ao_rays_device(self, n, rays, dirs, n_dirs, t_min=1e-3, t_max=np.inf, t_range=None, skip_self=False, visibility=None, smooth=False, count=False, stream=0,
+                       hit_id=0, t=0, n_occluded=0, ao=0, occ_bits=0):
+        """srt_ao_rays_device: raw device pointers (ints, e.g. torch.Tensor.data_ptr()) in -- the rays, the table `dirs` of n_dirs x 3 floats,
+        t_range (n x 2 floats, or None) and the outputs (0: not wanted) --, asynchronous on `stream`."""
+        desc = abi.AoDesc(n_dirs, dirs or None, t_min, t_max, abi.SRT_AO_SKIP_SELF if skip_self else 0)
+        aout = abi.AoOut(n_occluded or None, ao or None, occ_bits or None)
+        _check(self.L.srt_ao_rays_device(self.h, n, C.c_void_p(rays), C.c_void_p(t_range or 0), _ao_flags(smooth, count), C.byref(desc), _vis_ref(visibility),
+                                         C.c_void_p(stream), C.c_void_p(hit_id), C.c_void_p(t), C.byref(aout)), "srt_ao_rays_device")
+
+    def ao_hits_device(self, n, rays, hit_id, t, dirs, n_dirs, t_min=1e-3, t_max=np.inf, skip_self=False, visibility=None, smooth=False, count=False, stream=0,
+                       n_occluded=0, ao=0, occ_bits=0):
+        """srt_ao_hits_device: raw device pointers (ints) in -- the rays, their hit ids and t, the table --, asynchronous on `stream`."""
+        desc = abi.AoDesc(n_dirs, dirs or None, t_min, t_max, abi.SRT_AO_SKIP_SELF if skip_self else 0)
+        aout = abi.AoOut(n_occluded or None, ao or None, occ_bits or None)
+        _check(self.L.srt_ao_hits_device(self.h, n, C.c_void_p(rays), C.c_void_p(hit_id), C.c_void_p(t), _ao_flags(smooth, count), C.byref(desc), _vis_ref(visibility),
+                                         C.c_void_p(stream), C.byref(aout)), "srt_ao_hits_device")
+
     def _paths_host(self, kind, head, lead, params, depth, reflectance, bounce_t_min, want, count, smooth, fill, shadow, visibility, ior):
         """The host form of a path call: srt_<kind>_paths and its _shadow, _masked and _refract forms.  head: the arguments before the
         params; lead: the shape of one segment's rows."""
@@ -682,6 +746,44 @@ def _refraction(ior, n_objects):
     table = np.ascontiguousarray(ior, np.float32).reshape(-1)
     assert table.shape[0] == n_objects, "ior: one float per object"
     return abi.Refraction(table.ctypes.data, 0), table
+
+
+def _ao_flags(smooth, count):
+    return (abi.SRT_FLAG_SMOOTH_NORMALS if smooth else 0) | (abi.SRT_FLAG_COUNT_WORK if count else 0)
+
+
+def _vis_ref(visibility):
+    """None, a Visibility or (primary, bounce, shadow) as the srt_visibility* a call takes (None: NULL)."""
+    v = abi.visibility(visibility)
+    return C.byref(v) if v is not None else None
+
+
+def _ao_desc(dirs, t_min, t_max, skip_self):
+    """(an abi.AoDesc over a host table of K x 3 floats, the array that keeps it alive)."""
+    table = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+    return abi.AoDesc(table.shape[0], table.ctypes.data, t_min, t_max, abi.SRT_AO_SKIP_SELF if skip_self else 0), table
+
+
+def _ao_out(want, n, n_dirs):
+    """(an abi.AoOut over host arrays for the fields of srt_ao_out that `want` names, name -> array)."""
+    shape = {"n_occluded": (n,), "ao": (n,), "occ_bits": (n, (n_dirs + 31) // 32)}
+    out = {k: np.empty(shape[k], ty) for k, ty in abi.AO_FIELDS.items() if k in want}
+    return abi.AoOut(*_addresses(out, abi.AO_FIELDS)), out
+
+
+def ao_directions(n, cosine=True):
+    """A deterministic table of n unit directions over the hemisphere z >= 0 for ao_rays / ao_hits (n x 3 float32), computed in float64 and
+    rounded once: direction i has radius r = sqrt((i + 0.5) / n) in the xy plane at the golden-angle azimuth (i + 0.5) * pi * (3 - sqrt(5)) and
+    z = sqrt(1 - r * r) -- cosine-distributed, so that the plain count is cosine-weighted.  cosine=False: uniform over the hemisphere,
+    z = 1 - (i + 0.5) / n and r = sqrt(1 - z * z)."""
+    i = np.arange(int(n), dtype=np.float64)
+    u = (i + 0.5) / float(n)
+    if cosine:
+        r = np.sqrt(u); z = np.sqrt(1.0 - r * r)
+    else:
+        z = 1.0 - u; r = np.sqrt(1.0 - z * z)
+    phi = (i + 0.5) * (np.pi * (3.0 - np.sqrt(5.0)))
+    return np.stack([r * np.cos(phi), r * np.sin(phi), z], axis=1).astype(np.float32)
 
 
 def _ray_mask(ray_mask, n):

@@ -35,7 +35,12 @@ from every ray kind, at depth 3 and 1 / 16 light samples.
 run: srt_shade_paths_masked_device under (1e-3, 1, 0) with all-ones masks -- the existing kernel, the yardstick -- beside
 srt_shade_paths_refract_device with an all-zero table (the same walks to the bit: the price of the build alone) and with the bunny as glass of
 index 1.5 (other walks: for information).  Beside every ratio stands the yardstick's own round-to-round spread.
-Usage: python tools/ray_query_probe.py [--reps N] [--trace] [--shade | --range | --shade-range | --multi | --surface | --paths | --shadow-rule | --masked | --refract [--rounds R]]     (--trace: few repetitions, for a run under rocprofv3 --kernel-trace --stats)"""
+--ao: instead, ambient occlusion on the rays of the same frame at 16 and 64 cosine directions, t in (1e-3, 60), in one run: the chain the
+fused calls replace -- srt_surface_rays_device, the torch operations that build the frame and the n x K x 6 rays (a caller's own kernel
+would be one launch; torch takes a dozen elementwise ones), srt_occluded_masked_device with a ray mask of 0 on the rays of a miss, a torch
+reduction: the yardstick -- beside srt_ao_rays_device and srt_ao_hits_device (on a render's hits) under the shipped rule for the deal of rays
+to waves and under either deal alone (the libraries of python -m simple_raytracer_amd.build --ao-deals, loaded beside the shipped one).
+Usage: python tools/ray_query_probe.py [--reps N] [--trace] [--shade | --range | --shade-range | --multi | --surface | --paths | --shadow-rule | --masked | --refract | --ao [--rounds R]]     (--trace: few repetitions, for a run under rocprofv3 --kernel-trace --stats)"""
 import argparse, os, sys, time
 import numpy as np
 import torch                                   # first: torch initialises HIP before the library does
@@ -508,8 +513,79 @@ def refract_section(reps, rounds):
     ds.close()
 
 
+def ao_section(reps, rounds):
+    from simple_raytracer_amd import build
+    dev = torch.device("cuda", 0); torch.zeros(1, device=dev)
+    g = gu.GoldenScene("ground_bunny")
+    handles = {"shipped rule": lib.DeviceScene(g.flat), "spread deal": lib.DeviceScene(g.flat, library=lib.load(build.build_ao_deal(True))),
+               "block deal": lib.DeviceScene(g.flat, library=lib.load(build.build_ao_deal(False)))}
+    ds = handles["shipped rule"]
+    side = torch.cuda.Stream(device=dev)
+    cur = side.cuda_stream
+    rays = frame_rays()
+    n = rays.shape[0]
+    t_min, t_max = 1e-3, 60.0
+    d_rays = torch.from_numpy(rays).to(dev)
+    frame = ds.render(g.params(W, H, 1), want=("hit_id", "t"))
+    h0, t0 = torch.from_numpy(frame["hit_id"].reshape(-1).copy()).to(dev), torch.from_numpy(frame["t"].reshape(-1).copy()).to(dev)
+    hit = torch.empty(n, dtype=torch.int32, device=dev); t = torch.empty(n, dtype=torch.float32, device=dev)
+    point, normal = torch.empty((n, 3), dtype=torch.float32, device=dev), torch.empty((n, 3), dtype=torch.float32, device=dev)
+    print(f"ambient occlusion, K3 ground_bunny {W}x{H}: {n} rays, {int((h0 >= 0).sum().item())} hits, t in ({t_min}, {t_max}); {rounds} rounds of {reps} calls, forms "
+          f"alternating; ms a call; min / max: the spread of the rounds")
+    print(f"{'directions':34s} {'form':34s} {'median':>8s} {'min':>8s} {'max':>8s} {'/ chain':>7s}")
+    for K in (16, 64):
+        d_dirs = torch.from_numpy(lib.ao_directions(K)).to(dev)
+        cnt = {k: torch.empty(n, dtype=torch.int32, device=dev) for k in ("chain", "rays", "hits")}
+        ao = {k: torch.empty(n, dtype=torch.float32, device=dev) for k in cnt}
+        aor = torch.empty((n, K, 6), dtype=torch.float32, device=dev)
+        mask = torch.empty((n, K), dtype=torch.int32, device=dev)
+        occ = torch.empty((n, K), dtype=torch.uint8, device=dev)
+        tr = torch.tensor([t_min, t_max], dtype=torch.float32, device=dev).repeat(n * K, 1).contiguous()
+        torch.cuda.synchronize()
+
+        def chain():
+            with torch.cuda.stream(side):
+                ds.surface_rays_device(n, d_rays.data_ptr(), stream=cur, hit_id=hit.data_ptr(), point=point.data_ptr(), normal=normal.data_ptr())
+                d = d_rays[:, 3:6]
+                k = (d[:, 0] * normal[:, 0] + d[:, 1] * normal[:, 1]) + d[:, 2] * normal[:, 2]
+                Nf = torch.where((k > 0)[:, None], -normal, normal)
+                x, y, z = Nf[:, 0], Nf[:, 1], Nf[:, 2]
+                s = torch.copysign(torch.ones_like(z), z)
+                a = -1.0 / (s + z)
+                b = (x * y) * a
+                T = torch.stack([1.0 + ((s * x) * x) * a, s * b, (-s) * x], dim=1)
+                B = torch.stack([b, s + (y * y) * a, -y], dim=1)
+                aor[:, :, 0:3] = point[:, None, :]
+                aor[:, :, 3:6] = (T[:, None, :] * d_dirs[None, :, 0:1] + B[:, None, :] * d_dirs[None, :, 1:2]) + Nf[:, None, :] * d_dirs[None, :, 2:3]
+                mask[:] = torch.where(hit >= 0, -1, 0)[:, None]
+                ds.occluded_device(n * K, aor.data_ptr(), occ.data_ptr(), stream=cur, t_range=tr.data_ptr(), ray_mask=mask.data_ptr())
+                torch.sum(occ, dim=1, dtype=torch.int32, out=cnt["chain"])
+                torch.div((K - cnt["chain"]).to(torch.float32), float(K), out=ao["chain"])
+
+        fused = lambda h: (lambda: h.ao_rays_device(n, d_rays.data_ptr(), d_dirs.data_ptr(), K, t_min, t_max, stream=cur, hit_id=hit.data_ptr(), t=t.data_ptr(),
+                                                    n_occluded=cnt["rays"].data_ptr(), ao=ao["rays"].data_ptr()))
+        on_hits = lambda h: (lambda: h.ao_hits_device(n, d_rays.data_ptr(), h0.data_ptr(), t0.data_ptr(), d_dirs.data_ptr(), K, t_min, t_max, stream=cur,
+                                                      n_occluded=cnt["hits"].data_ptr(), ao=ao["hits"].data_ptr()))
+        forms = {"chain (yardstick)": chain}
+        forms.update({f"ao_rays_device, {name}": fused(h) for name, h in handles.items()})
+        forms.update({f"ao_hits_device, {name}": on_hits(h) for name, h in handles.items()})
+        report(f"{K} directions", rounds_of(forms, reps, rounds, side))
+        # every form answers alike
+        chain(); side.synchronize()
+        for name, h in handles.items():
+            cnt["rays"].fill_(-1); cnt["hits"].fill_(-1)
+            fused(h)(); on_hits(h)(); side.synchronize()
+            assert torch.equal(hit, h0) and torch.equal(t.view(torch.int32), t0.view(torch.int32)), name
+            for k in ("rays", "hits"):
+                assert torch.equal(cnt[k], cnt["chain"]) and torch.equal(ao[k].view(torch.int32), ao["chain"].view(torch.int32)), (name, k)
+        print(f"{'':34s} blocked {int(cnt['chain'].sum().item())} of {int((h0 >= 0).sum().item()) * K} AO rays; the chain, both calls and both deals give the same bits")
+    for h in handles.values():
+        h.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--ao", action="store_true")
     ap.add_argument("--refract", action="store_true")
     ap.add_argument("--masked", action="store_true")
     ap.add_argument("--shadow-rule", action="store_true", dest="shadow_rule")
@@ -524,6 +600,8 @@ def main():
     ap.add_argument("--rounds", type=int, default=7)
     a = ap.parse_args()
     reps = 3 if a.trace else a.reps
+    if a.ao:
+        return ao_section(reps, 2 if a.trace else a.rounds)
     if a.refract:
         return refract_section(reps, 2 if a.trace else a.rounds)
     if a.masked:
