@@ -879,8 +879,10 @@ int srt_render_paths_refract(srt_scene* s, const srt_params* p, const srt_path_d
  *               not being walked.  vis->bounce is ignored.
  *   A miss row  n_occluded 0, ao 1.0f, every word of occ_bits 0.
  * Not validated: t_min <= 0 lets the hit's own triangle block near t = 0, depending on rounding (whole hemispheres then read as closed): use
- * a small positive t_min, as with SRT_SHADOW_SELF.  Directions that are not unit or lie below the horizon, NaN normals and degenerate
- * triangles give what the arithmetic gives; the call stays memory-safe.
+ * a small positive t_min, as with SRT_SHADOW_SELF.  Directions that are not unit, lie below the horizon, are zero or not finite, NaN and
+ * zero normals, degenerate triangles, a valid hit_id with any t (NaN, +-inf, 0, negative, another triangle's), and t_min <= 0 give what the
+ * arithmetic of the DEFINITION gives, bit for bit -- pinned by tests/ao_edges.py and tests/test_gpu_ao_edges.py against tests/ao_ref.py --;
+ * the call stays memory-safe.
  * Flags: 0, SRT_FLAG_COUNT_WORK, SRT_FLAG_SMOOTH_NORMALS or both; SRT_FLAG_SMOOTH_NORMALS on a scene without normals fails as
  * srt_surface_rays does.
  * Errors, all before anything is touched.  SRT_ERR_ARG: a NULL handle; NULL rays with n > 0; NULL hit_id or t in srt_ao_hits with n > 0; a NULL

@@ -136,7 +136,8 @@ __device__ __forceinline__ bool ray_aabb_nb(V3 o, V3 d, float mnx, float mny, fl
 //   * |d| below 2^-126: the reciprocal overflows (or the subnormal is flushed) and the axis becomes (-inf, +inf)
 //     where the true interval is finite and may reject;
 //   * |d| above 2^126: the reciprocal is subnormal and may be flushed to 0, which collapses the axis to [0, 0].
-// All four are properties of the RAY, so ray_rcp decides them once per ray: a ray with a direction component that is
+//   * a NaN ORIGIN component: both quotients of the axis are NaN and are dropped (ray_rcp(o, d) below; the frames' origins are finite).
+// All of these are properties of the RAY, so ray_rcp decides them once per ray: a ray with a direction component that is
 // zero, subnormal, above 2^126, infinite or NaN gets NaN for ALL THREE reciprocals.  Then every quotient is NaN, so
 // are tnear, tfar and their difference, and every box is ambiguous for that ray (in a frame: the pixel column i = 0
 // and the pixel row j = 0).  Whoever assembles a RayRcp from parts must keep that all-or-nothing rule (rcp_axis_ok).
@@ -150,6 +151,18 @@ __device__ __forceinline__ bool rcp_axis_ok(float d) {
 __device__ __forceinline__ RayRcp ray_rcp(V3 d) {
     RayRcp r;
     const bool ok = rcp_axis_ok(d.x) & rcp_axis_ok(d.y) & rcp_axis_ok(d.z);
+    const float nan = __builtin_nanf("");
+    r.x = ok ? __builtin_amdgcn_rcpf(d.x) : nan; r.y = ok ? __builtin_amdgcn_rcpf(d.y) : nan; r.z = ok ? __builtin_amdgcn_rcpf(d.z) : nan;
+    return r;
+}
+// A ray whose ORIGIN a caller supplies (the ray queries, and the rays a query kernel makes from a caller's d and t): a NaN origin
+// component makes both quotients of its axis NaN, and v_min / v_max drop them exactly as they drop the NaN of a zero direction on a flat
+// box -- tnear / tfar then come from the other axes alone and may reject a box that the reference, whose comparisons with a NaN are all
+// false, passes.  It is a property of the ray as well, so such a ray gets NaN reciprocals too and every box goes to the exact form.
+// (An infinite component needs nothing: its quotients are infinite or NaN on BOTH sides of the axis, which is ambiguous already.)
+__device__ __forceinline__ RayRcp ray_rcp(V3 o, V3 d) {
+    RayRcp r;
+    const bool ok = rcp_axis_ok(d.x) & rcp_axis_ok(d.y) & rcp_axis_ok(d.z) & (o.x == o.x) & (o.y == o.y) & (o.z == o.z);
     const float nan = __builtin_nanf("");
     r.x = ok ? __builtin_amdgcn_rcpf(d.x) : nan; r.y = ok ? __builtin_amdgcn_rcpf(d.y) : nan; r.z = ok ? __builtin_amdgcn_rcpf(d.z) : nan;
     return r;

@@ -1031,7 +1031,7 @@ __device__ __forceinline__ bool any_hit_range(const DevScene& s, int2 self, V3 s
     const float4* nodes4 = reinterpret_cast<const float4*>(s.nodes);
     const float4* tris4 = reinterpret_cast<const float4*>(s.tris);
     RayRcp rc;
-    if (FILTER) rc = ray_rcp(sd);
+    if (FILTER) rc = ray_rcp(so, sd);      // (FILTER: the ray queries, whose origins a caller supplies)
     const int32_t n = (int32_t)s.n_nodes;
     int32_t i = 0;
     int32_t obj_root = 0;

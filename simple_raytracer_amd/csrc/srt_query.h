@@ -92,7 +92,7 @@ __device__ __forceinline__ void query_walk(const DevScene& s, const bool live, c
     wray[0][lane] = o.x; wray[1][lane] = o.y; wray[2][lane] = o.z;
     wray[3][lane] = d.x; wray[4][lane] = d.y; wray[5][lane] = d.z;
     if (RANGE) { wray[6][lane] = t_min; wray[7][lane] = t_max; }
-    const RayRcp rc = ray_rcp(d);
+    const RayRcp rc = ray_rcp(o, d);
     const float4* nodes4 = reinterpret_cast<const float4*>(s.nodes);
     const float4* tris4 = reinterpret_cast<const float4*>(s.tris);
     const int32_t n = (int32_t)s.n_nodes;

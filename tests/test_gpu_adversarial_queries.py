@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import adversarial as adv
+import ao_ref as ar
 import ray_multi_ref as rm
 import ray_range_ref as rr
 import refract_ref as rf
@@ -83,6 +84,38 @@ def test_closest_hit_and_occlusion(srt, oracle, seed):
         pr = np.ascontiguousarray(rays[perm])
         assert np.array_equal(ds.occluded(pr, skip[perm]), occ[perm]) and np.array_equal(ds.occluded(pr), occ_all[perm])
         same(ds.trace_rays(pr), {k: v[perm] for k, v in want.items()}, "permuted")
+
+
+# ---- ambient occlusion --------------------------------------------------------------------------------------------------------------------
+AO_DIRS = ar.directions(9)
+
+
+@pytest.mark.parametrize("seed", adv.SEEDS)
+def test_ambient_occlusion(srt, oracle, seed):
+    """srt_ao_rays / srt_ao_hits over the WHOLE batch -- origins on a triangle, in-plane rays (those that hit a neighbour have k near 0),
+    the non-finite rays (miss rows, or rows with a NaN frame) -- against ao_ref.Case: 9 directions, SRT_AO_SKIP_SELF off and on, seed 4
+    with its vertex normals.  The yardstick takes under a second a seed on all hits, so no hit is left out."""
+    flat, (rays, cls) = adv.scene(seed)[0], adv.rays(seed)
+    smooth = seed == 4
+    c = ar.Case(oracle, flat, rays, AO_DIRS, smooth=smooth)
+    hit, t = rr.closest(adv.candidates(oracle, seed))
+    assert np.array_equal(c.hit, hit) and np.array_equal(bits(c.t), bits(t))
+    _, is_dup, _ = adv.duplicates(seed)
+    on = cls[c.sel]
+    assert is_dup[hit[c.sel]].sum() >= 10 and (on == adv.F).sum() >= 4 and (on == adv.E).sum() >= 4 and (cls[hit < 0] == adv.NONFINITE).sum() >= 4
+    plain, skipped = c.reference(t_max=np.inf), c.reference(t_max=np.inf, skip_self=True)
+    assert ar.conditions(plain, 9)["partial"] >= 50 and np.any(plain["occ_bits"] != skipped["occ_bits"])
+    with device_scene(srt, oracle, seed) as ds:
+        for skip, want in ((False, plain), (True, skipped)):
+            for count in (False, True):
+                what = f"seed {seed}, skip_self {skip}, counting {count}"
+                o = ds.ao_rays(rays, AO_DIRS, skip_self=skip, smooth=smooth, count=count)
+                same(o, want, what, ("hit_id", "t") + ar.FIELDS)
+                hits = int((hit >= 0).sum())
+                assert o["stats"]["primary_rays"] == rays.shape[0] and o["stats"]["hit_rays"] == hits and o["stats"]["shadow_rays"] == hits * 9, o["stats"]
+                same(ds.ao_hits(rays, o["hit_id"], o["t"], AO_DIRS, skip_self=skip, smooth=smooth, count=count), want, what + ", ao_hits", ar.FIELDS)
+        perm = np.random.default_rng(seed).permutation(rays.shape[0])
+        same(ds.ao_rays(np.ascontiguousarray(rays[perm]), AO_DIRS, smooth=smooth), {k: v[perm] for k, v in plain.items()}, f"seed {seed}, permuted", ("hit_id", "t") + ar.FIELDS)
 
 
 # ---- intervals and the K nearest ------------------------------------------------------------------------------------------------------
