@@ -1073,10 +1073,11 @@ enum Variant : uint32_t {
     V_FUSED_ROOTS_AGAIN = 12,     // the fused kernel with the roots re-tested by every wave (round-1 form)
     V_FUSED_HALF = 13,            // the fused kernel's half-tile form (two waves of 8x4 pixels per tile) also without SRT_FLAG_FRAMES_IN_FLIGHT
     V_FUSED_HALF_TINY = 14,       // the half-tile form with a 160-entry node queue: the stackless overflow walk at 32 rays per wave
-    V_FUSED_HALF_1024 = 15,       // the half-tile form with a 1024-entry node queue (nine workgroups per CU)
+    V_FUSED_HALF_1024 = 15,       // the half-tile form with a 1024-entry node queue (15,240 B of LDS: ten workgroups per CU)
     V_FUSED_HALF_32_RAYS = 16,    // the half-tile form with 32 shadow rays in flight per wave
     V_FUSED_64_RAYS = 17,         // the fused kernel with 64 shadow rays in flight per wave
     V_XCD_ROWS = 18,              // whole tile rows dealt to XCDs (what records beyond 32 MiB get), forced
+    V_FUSED_HALF_6_WAVES = 19,    // the half-tile form built for 6 waves per SIMD: twelve workgroups per CU by VGPRs (the LDS overlay without its residency)
     V_CHUNKED = 20,               // never fused; 8+ samples: node-queue shadow kernel, samples cut into chunks over blockIdx.z (round-1 form)
     V_NQ_PK = 21,                 // node-queue closest hit + packet shadow kernel at any sample count
     V_PK_PK = 22,                 // packet closest hit + packet shadow kernel
@@ -1292,7 +1293,9 @@ static FramePlan plan_frame(const SceneFacts& f, const srt_params* p, BatchState
             // Two waves of 8x4 pixels per tile where frames are in flight on several streams: half the waves hold a CU's wave slots for the
             // same pairs, and the next frame's launch fills the tail that a wave living twice as long leaves (36 frames on four streams
             // 4.13 -> 3.37 ms).  A frame that has the device to itself pays for that tail -- the launch alone 0.108 -> 0.136 ms
-            // -- and keeps four waves per tile, as do the camera, counting and XCD-row builds below.
+            // -- and keeps four waves per tile, as do the camera, counting and XCD-row builds below.  The build for seven waves per SIMD
+            // (the closest-hit phase's dir[] and best[] over the shadow phase's LDS: fourteen workgroups per CU instead of twelve) takes the
+            // 36 frames from 3.37 to 3.23 ms; 19 keeps the six-wave build of the same body.
             const bool half_tile = (v == V_SHIPPED && in_flight) || v == V_FUSED_HALF;
             if (cam_nq)                        pl.trace = &k_trace_nq<false, 512, true, 5, 16, false, false, true>;      // camera mode on the node queues
             else if (count)                    pl.trace = &k_trace_nq<true, 512, true, 5, 16>;
@@ -1305,7 +1308,8 @@ static FramePlan plan_frame(const SceneFacts& f, const srt_params* p, BatchState
             else if (v == V_FUSED_HALF_TINY) { pl.trace = &k_trace_nq_half<160, true, 6, 16>; pl.block_hit = 128; }
             else if (v == V_FUSED_HALF_1024) { pl.trace = &k_trace_nq_half<1024, true, 5, 16>; pl.block_hit = 128; }
             else if (v == V_FUSED_HALF_32_RAYS) { pl.trace = &k_trace_nq_half<512, true, 6, 32>; pl.block_hit = 128; }
-            else if (half_tile)              { pl.trace = &k_trace_nq_half<512, true, 6, 16>; pl.block_hit = 128; }      // two waves of 8x4 pixels per tile: 12,680 B of LDS, twelve workgroups and 24 waves per CU
+            else if (v == V_FUSED_HALF_6_WAVES) { pl.trace = &k_trace_nq_half<512, true, 6, 16>; pl.block_hit = 128; }      // 73 VGPRs: twelve workgroups and 24 waves per CU, as before the LDS overlay
+            else if (half_tile)              { pl.trace = &k_trace_nq_half<512, true, 7, 16>; pl.block_hit = 128; }      // two waves of 8x4 pixels per tile: 11,144 B of LDS (HalfTileLds) and 72 VGPRs, fourteen workgroups and 28 waves per CU
             else                               pl.trace = &k_trace_nq<false, 512, true, 7, 16>;      // 72 VGPRs, no scratch, 7 waves per SIMD (lane-derived addresses are formed where they are used: lane_again, srt_kernels.h); with 14 spilled registers it was already 3 % ahead of the 6-wave build since the node-major order
         } else if (!count && v == V_COARSE_GRID) {
             // 2 x 2 tiles per workgroup (a quarter of the workgroups for frames that are mostly background).  Measured and NOT

@@ -1183,6 +1183,28 @@ struct ShadowLds {
     uint32_t mask[64];             // per light sample of the current group: shadowed pixels of this wave's 4x4 quadrant (P = 32: of its 8x4 half)
 };
 
+// Per-wave LDS of the half-tile trace kernel (trace_nq_body's HALF) beside the two queues: the closest-hit phase's dir[] and best[] lie
+// over the front of the shadow phase's ShadowLds, 768 B a wave less, which with 512-entry queues is 11,144 B a workgroup -- nine
+// 1,280-byte granules, fourteen workgroups per 160 KiB CU where the separate arrays (ten granules) admitted twelve.  Per wave:
+//
+//   data                                  written                                      read                                      dead after
+//   dir[P]                                set-up of closest_hit_phase                  every node step and triangle batch; last  the write-out
+//                                                                                      read dir[lane] at the phase's write-out
+//   best[P]                               set-up of closest_hit_phase                  last read best[lane] at the write-out     the write-out
+//   shadow.mask[0 .. 31] of wave h (the   by wave 0, before the launch-time barrier    only while closest_hit_phase queues the   rewritten by wave h in
+//   tile's root masks, rays 32h ..)       (finish_background_tile)                     roots                                     its own shadow phase
+//   shadow.ray, pixd, pso, selfr, flag    first in shadow_phase, from id, t and d      in shadow_phase                           end of the shadow phase
+//                                         held in registers
+//
+// So `closest` may share bytes with ray / pixd / pso / selfr / flag and never with mask, which is live through the closest-hit phase: it
+// ends at or before mask's offset.  One object with two views, so that the compiler knows the views alias; trace_nq_body keeps the
+// phases' accesses apart (a wavefront fence and the wave barrier between them).  ShadowLds itself is what every other kernel declares.
+template <int RS, int P>
+union HalfTileLds {
+    struct { float4 dir[P]; unsigned long long best[P]; } closest;
+    ShadowLds<RS, P> shadow;
+};
+
 // Runs per wavefront, with no workgroup-level synchronisation: `id` / `t_hit` are the hit id and t of this lane's pixel
 // (lanes < 16; -1 = miss).  The wave writes its own 16-bit field of the tile's word (field = quadrant, bit = pixel lane
 // y * 4 + x inside the quadrant), so a wave that is done leaves the CU without waiting for its three neighbours.
@@ -1615,8 +1637,9 @@ __device__ __forceinline__ void shade_hit_pixel(const DevScene& s, const DevPara
 // HALF: the workgroup is TWO waves (128 threads) and wave h owns rows 4h .. 4h + 3 of the tile, 32 rays (closest_hit_phase's HALF,
 // shadow_phase's P = 32): the same (node, ray) and (triangle, ray) pairs, merged the same way, on half the waves -- a ground-slab wave's
 // one node step and one triangle batch fill 64 lanes instead of 32, and a background tile parks one wave at the barrier, not three.
-// The tile's root masks wait in the two waves' own shadow masks (rays 32h .. 32h + 31 in lds_all[h].mask[0 .. 31]): wave h alone writes
-// that array again, in its shadow phase, after it has read them -- 256 B less, which is what lets twelve workgroups fit a CU's LDS.
+// The tile's root masks wait in the two waves' own shadow masks (rays 32h .. 32h + 31 in half_all[h].shadow.mask[0 .. 31]): wave h alone writes
+// that array again, in its shadow phase, after it has read them -- 256 B less -- and a wave's dir[] and best[] lie over the front of its
+// ShadowLds (HalfTileLds, with the lifetimes): nine LDS granules a workgroup, fourteen workgroups per CU with the 72 VGPRs of a 7-wave build.
 template <bool COUNT, int NQCAP, bool FILTER, int RS, bool XCD_ROWS, bool ROOTS_AGAIN, bool SHADE = false, bool CAM = false, bool WIDE = false, bool ROW_Z = false,
           bool HALF = false>
 __device__ __forceinline__ void trace_nq_body(const DevScene& s, const DevParams& p, int32_t* __restrict__ hit_id, float* __restrict__ t_out,
@@ -1635,10 +1658,8 @@ __device__ __forceinline__ void trace_nq_body(const DevScene& s, const DevParams
     constexpr int NW = HALF ? 2 : 4, P = HALF ? 32 : NQ_P;      // waves per tile, rays per wave
     __shared__ uint32_t nq_all[NW][NQCAP];
     __shared__ uint32_t tq_all[NW][LQ_WORDS];
-    __shared__ unsigned long long best_all[NW][P];
-    __shared__ float4 dir_all[NW][P];
-    __shared__ ShadowLds<RS, P> lds_all[NW];
     const uint32_t wave = threadIdx.x >> 6;
+    ShadowLds<RS, P>* L;                                        // this wave's shadow-phase LDS (HALF: inside the wave's HalfTileLds)
     int32_t id; float t; V3 d;
     unsigned long long k0 = 0, k1 = 0; (void)k0; (void)k1;
     SRT_STAMP(k0);
@@ -1657,23 +1678,35 @@ __device__ __forceinline__ void trace_nq_body(const DevScene& s, const DevParams
     __shared__ uint32_t root_pass[64];
     const bool roots_done = !COUNT && !ROOTS_AGAIN && s.n_objects <= 32u;              // wave 0 tests every root for the tile's 64 rays first
     unsigned long long ka = 0, kb = 0; (void)ka; (void)kb;
+    ShadowLds<RS, P>* lds_tile = nullptr;      // the four waves' shadow-phase LDS, for the wave that shades the tile (SHADE, never HALF)
     if constexpr (HALF) {
-        static_assert(sizeof(ShadowLds<RS, P>) % 4 == 0, "the stride between the two waves' masks is counted in words");
-        if (finish_background_tile<FILTER, CAM>(s, p, hit_id, t_out, rgb_linear, rgb8, shadow_bits, bx, by, gx, lds_all[0].mask, sizeof(ShadowLds<RS, P>) / 4)) return;
+        __shared__ HalfTileLds<RS, P> half_all[NW];
+        using Shadow = ShadowLds<RS, P>;
+        static_assert(sizeof(half_all[0].closest) <= offsetof(Shadow, mask), "dir[] and best[] end at or before the root masks that wait in ShadowLds::mask");
+        static_assert(sizeof(HalfTileLds<RS, P>) == sizeof(Shadow) && sizeof(Shadow) % 4 == 0, "the stride between the two waves' masks is counted in words");
+        if (finish_background_tile<FILTER, CAM>(s, p, hit_id, t_out, rgb_linear, rgb8, shadow_bits, bx, by, gx, half_all[0].shadow.mask, sizeof(HalfTileLds<RS, P>) / 4)) return;
         SRT_STAMP(ka);
-        closest_hit_phase<COUNT, NQCAP, 3, 2, FILTER, CAM, WIDE, true>(s, p, nq_all[wave], tq_all[wave], best_all[wave], dir_all[wave],
+        closest_hit_phase<COUNT, NQCAP, 3, 2, FILTER, CAM, WIDE, true>(s, p, nq_all[wave], tq_all[wave], half_all[wave].closest.best, half_all[wave].closest.dir,
                                                                  hit_id, t_out, rgb_linear, rgb8, counters, id, t, d, bx, by, gx, wave, nullptr, nullptr, 0,
-                                                                 roots_done ? lds_all[wave].mask : nullptr);
+                                                                 roots_done ? half_all[wave].shadow.mask : nullptr);
+        L = &half_all[wave].shadow;
+        // `closest` is dead from here and `shadow` (but its mask) not yet written: the phases' accesses to the shared bytes stay on their
+        // sides of this fence (no instruction: the LDS keeps a wave's accesses in order) and of the wave barrier below
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     } else {
+    __shared__ unsigned long long best_all[NW][P];
+    __shared__ float4 dir_all[NW][P];
+    __shared__ ShadowLds<RS, P> lds_all[NW];
     if (!COUNT && finish_background_tile<FILTER, CAM>(s, p, hit_id, t_out, rgb_linear, rgb8, shadow_bits, bx, by, gx, root_pass)) return;
     SRT_STAMP(ka);
     closest_hit_phase<COUNT, NQCAP, 2, 2, FILTER, CAM, WIDE>(s, p, nq_all[wave], tq_all[wave], best_all[wave], dir_all[wave],
                                                        hit_id, t_out, rgb_linear, rgb8, counters, id, t, d, bx, by, gx, wave, nullptr, nullptr, 0,
                                                        roots_done ? root_pass + wave * 16 : nullptr);
+    L = &lds_all[wave]; lds_tile = lds_all;
     }
     __builtin_amdgcn_wave_barrier();
     SRT_STAMP(kb);
-    shadow_phase<COUNT, NQCAP, FILTER, RS, true, WIDE, P>(s, p, nq_all[wave], tq_all[wave], lds_all[wave], id, t, d, shadow_bits, counters, bx, by, gx, wave);
+    shadow_phase<COUNT, NQCAP, FILTER, RS, true, WIDE, P>(s, p, nq_all[wave], tq_all[wave], *L, id, t, d, shadow_bits, counters, bx, by, gx, wave);
 #ifdef SRT_DIAG
     SRT_STAMP(k1); diag_tile_record(rgb_linear, blockIdx.x, blockIdx.y, gridDim.x, k0, k1, ka, kb);
 #endif
@@ -1690,7 +1723,7 @@ __device__ __forceinline__ void trace_nq_body(const DevScene& s, const DevParams
         const uint32_t px = bx * 8 + (q & 1u) * 4 + (pl & 3u), r = by * 8 + (q >> 1) * 4 + (pl >> 2);
         const int32_t hid = fin_id[lane];
         if (hid >= 0 && pixel_live(p, px, r)) {
-            const uint32_t* mask = lds_all[q].mask;
+            const uint32_t* mask = lds_tile[q].mask;
             shade_hit_pixel(s, p, hid, fin_t[lane], px, r, [&](uint32_t l) -> bool { return (mask[l] >> pl) & 1u; }, rgb_linear, rgb8);
         }
     }
