@@ -829,7 +829,7 @@ int srt_render_paths_masked(srt_scene* s, const srt_params* p, const srt_path_de
  * IDENTITIES, in every output and all four counters: refr == NULL or refr->ior == NULL: the call IS the _masked call and launches its
  * kernels; a table with no entry > 0 gives the _masked call's bits; depth 1 is unchanged by any table.
  * ERRORS: refr->flags != 0: SRT_ERR_ARG before anything is touched; every error of the _masked call keeps its code.
- * NOT HERE: a Fresnel split into two rays, absorption along the way, srt_surface_out reporting a refracted ray. */
+ * NOT HERE: absorption along the way, srt_surface_out reporting a refracted ray.  (A Fresnel split: the _fresnel calls below.) */
 typedef struct srt_refraction {
     const float* ior;     /* n_objects floats; object k TRANSMITS iff ior[k] > 0.0f (0, negative, NaN: it mirrors) */
     uint32_t     flags;   /* 0; any other value: SRT_ERR_ARG */
@@ -847,6 +847,75 @@ int srt_render_paths_refract_device(srt_scene* s, const srt_params* p, const srt
 int srt_render_paths_refract(srt_scene* s, const srt_params* p, const srt_path_desc* path, const srt_shadow_rule* shadow,
                              const srt_visibility* vis, const srt_refraction* refr, float* rgb_linear, uint8_t* rgb8, const srt_path_out* seg,
                              srt_stats* stats);
+
+/* Fresnel split: glass that also reflects.  In the _refract calls the whole weight of what follows a glass hit goes through the surface.
+ * The calls below take one more per-object table, f0, the reflectance at normal incidence, and at a hit on an object that SPLITS the path
+ * goes on through the glass, as before, while the mirrored ray at that hit is walked once and shaded once -- a depth-1 SIDE RAY -- and its
+ * colour enters the mix with Schlick's weight.  A path stays a row, not a tree: a side ray's hit sends no further ray.  Unless said here
+ * everything is as for srt_shade_paths_refract / srt_render_paths_refract: the rule, vis, refr and its flags, seg, staging (f0 and the
+ * four fields of `out` go through the pinned block and the handle's buffers exactly as ior and seg do), the one-light-table-per-handle
+ * rule, ordering on `stream`, srt_scene_share, ONE kernel launch, hipGraph capture of the _device forms without SRT_FLAG_COUNT_WORK, n == 0,
+ * the frame fields, spp (`out` reports sub-sample 0), the tile deals (padding pixels are not written in any output).
+ * THE TABLE.  fres->f0: n_objects floats -- a device pointer in the _device forms, a host pointer in the host forms.  Object k SPLITS iff
+ * ior[k] > 0.0f && f0[k] >= 0.0f; a negative or NaN f0[k] means no split at that object.  fres->flags must be 0.
+ * WHEN A SIDE RAY IS WALKED.  The side ray of segment b is walked iff segment b hit an object that splits, b + 1 < depth, and the hit was
+ * not totally reflected: !(k < 0.0f) with the k of "Refracting paths" -- a NaN k goes the split way and gives what the arithmetic gives.
+ * This is purely geometric: no value of f0 or reflectance changes which rays are walked.
+ * THE SIDE RAY is the `bounce` row srt_surface_rays defines for that hit under the call's flags: origin o + d * t, not moved, direction the
+ * mirrored one (d not normalised).  Its interval is (bounce_t_min, +inf), it is walked with the mask vis->bounce, and its hit is shaded
+ * exactly as a segment's is: the same shadow rule, vis->shadow, lights and literals.  Nothing bounces off its hit; the reflectance of the
+ * object it hits is not read.
+ * THE WEIGHT.  f32 without contraction, from the intermediates of "Refracting paths" for segment b (entering, dv, k):
+ *   x  = entering ? -dv : sqrtf(k)                      (the cosine on the thin side: the incident one going in, the transmitted one going out)
+ *   m  = 1.0f - x;   m2 = m * m;   m5 = (m2 * m2) * m
+ *   F  = f0[obj] + (1.0f - f0[obj]) * m5                (Schlick's polynomial; nothing is clamped or validated)
+ * THE MIX of a segment b with a side ray, in the place of the mix of srt_shade_paths; W: the weight of what follows, nxt: segment b + 1
+ * hits, side: the side ray hits, lin_b: segment b's sum, S_b: the side hit's sum:
+ *   k  = (nxt || side) ? reflectance[obj_b] : 0         (NULL table: 0)
+ *   a  = W * (1 - k);   acc_i = acc_i + a * lin_b_i;   Wk = W * k
+ *   Fe = side ? (nxt ? F : 1.0f) : 0.0f                 (a branch that misses gives its share to the other)
+ *   if side:  g = Wk * Fe;   acc_i = acc_i + g * S_b_i  (one multiply, then one add)
+ *   W  = Wk * (1.0f - Fe)
+ * Segments without a side ray mix as before.
+ * `out` (may be NULL, and so may any field): per SEGMENT, segment-major like srt_path_out -- row b of hit_id / t / rgb_linear is laid out
+ * as seg's hit_id / t / rgb_linear.  Row b reports the side ray of segment b: what it hit and where (the winner's own t bits), the side
+ * hit's pre-tone-map sum S_b, and F_b.  Without a side ray: -1, +inf, 0 and 0.  `out` is written by a call that brings both tables.
+ * IDENTITIES, in every output and all four counters: fres == NULL or fres->f0 == NULL: the call IS the _refract call and launches its
+ * kernels (so does a call without refr->ior: nothing can split); a table under which no object splits gives the _refract call's bits; so
+ * does a call in which every side ray misses (Wk * (1.0f - 0.0f) is Wk); depth 1 is unchanged by any table; at depth D the rows b < D - 1
+ * of `out` are those rows at any larger depth, and row D - 1 holds no side ray (b + 1 < depth); results never depend on the order of the rays.
+ * *stats: primary_rays is unchanged; hit_rays and shadow_rays = hit_rays x n_lights include the side hits.  Under SRT_FLAG_COUNT_WORK the
+ * four counters are the _refract call's on the same tables plus, per side ray walked, what the depth-1 _masked call reports for that ray
+ * with the interval (bounce_t_min, +inf), vis' = { bounce, bounce, shadow } and the same rule.
+ * ERRORS: fres->flags != 0: SRT_ERR_ARG before anything is touched; every error of the _refract call keeps its code.  A call with every
+ * output NULL, the fields of `out` included, returns SRT_OK and launches nothing.
+ * NOT HERE: a recursive split (a side ray of a side ray), absorption inside a solid. */
+typedef struct srt_fresnel_out {   /* per SEGMENT, segment-major like srt_path_out; any pointer may be NULL, and so may the struct */
+    int32_t* hit_id;       /* depth x n      the side ray of segment b: what it hit, -1 = miss or no side ray */
+    float*   t;            /* depth x n      +inf on a miss or without a side ray                              */
+    float*   rgb_linear;   /* depth x n x 3  the side hit's own pre-tone-map sum S_b; 0 otherwise              */
+    float*   fresnel;      /* depth x n      F_b where a side ray was walked, else 0                           */
+} srt_fresnel_out;
+typedef struct srt_fresnel {
+    const float*           f0;     /* n_objects floats: reflectance at normal incidence; device pointer in the _device forms */
+    uint32_t               flags;  /* 0; any other value: SRT_ERR_ARG */
+    const srt_fresnel_out* out;    /* or NULL */
+} srt_fresnel;
+int srt_shade_paths_fresnel_device(srt_scene* s, uint32_t n, const float* d_rays, const float* d_t_range /* n x 2 or NULL */,
+                                   const srt_params* p, const srt_path_desc* path, const srt_shadow_rule* shadow /* or NULL */,
+                                   const srt_visibility* vis /* or NULL */, const srt_refraction* refr /* or NULL */,
+                                   const srt_fresnel* fres /* or NULL */, void* stream,
+                                   float* d_rgb_linear /* n x 3, mixed */, uint8_t* d_rgb8 /* n x 3 */, const srt_path_out* seg);
+int srt_shade_paths_fresnel(srt_scene* s, uint32_t n, const float* rays, const float* t_range, const srt_params* p,
+                            const srt_path_desc* path, const srt_shadow_rule* shadow, const srt_visibility* vis, const srt_refraction* refr,
+                            const srt_fresnel* fres, float* rgb_linear, uint8_t* rgb8, const srt_path_out* seg, srt_stats* stats);
+int srt_render_paths_fresnel_device(srt_scene* s, const srt_params* p, const srt_path_desc* path, const srt_shadow_rule* shadow /* or NULL */,
+                                    const srt_visibility* vis /* or NULL */, const srt_refraction* refr /* or NULL */,
+                                    const srt_fresnel* fres /* or NULL */, void* stream,
+                                    float* d_rgb_linear /* n x 3, mixed */, uint8_t* d_rgb8 /* n x 3 */, const srt_path_out* seg);
+int srt_render_paths_fresnel(srt_scene* s, const srt_params* p, const srt_path_desc* path, const srt_shadow_rule* shadow,
+                             const srt_visibility* vis, const srt_refraction* refr, const srt_fresnel* fres, float* rgb_linear, uint8_t* rgb8,
+                             const srt_path_out* seg, srt_stats* stats);
 
 /* Ambient occlusion: how open the surface is at a hit -- the hemisphere visibility behind ambient occlusion, sky visibility and contact
  * shadows -- in ONE launch: the closest hit, the surface there, a tangent frame, n_dirs short occlusion rays from the hit point and their

@@ -136,6 +136,22 @@ class Refraction(C.Structure):
     _fields_ = [("ior", C.c_void_p), ("flags", C.c_uint32)]
 
 
+class FresnelOut(C.Structure):
+    """srt_fresnel_out: the per-segment rows of the side rays of the _fresnel path calls (segment-major, depth x n rows, laid out as
+    srt_path_out's hit_id, t and rgb_linear), as addresses; 0 = not wanted."""
+    _fields_ = [("hit_id", C.c_void_p), ("t", C.c_void_p), ("rgb_linear", C.c_void_p), ("fresnel", C.c_void_p)]
+
+
+class Fresnel(C.Structure):
+    """srt_fresnel: the per-object table of the Fresnel split.  f0: n_objects floats, the reflectance at normal incidence (a host array's
+    pointer in the host forms, a device pointer in the _device forms); object k splits iff ior[k] > 0 and f0[k] >= 0.  flags: 0.  out: the
+    address of a FresnelOut, or 0."""
+    _fields_ = [("f0", C.c_void_p), ("flags", C.c_uint32), ("out", C.POINTER(FresnelOut))]
+
+
+# srt_fresnel_out's fields: name -> (numpy type, components per row)
+FRESNEL_FIELDS = {"hit_id": (np.int32, 1), "t": (np.float32, 1), "rgb_linear": (np.float32, 3), "fresnel": (np.float32, 1)}
+
 SRT_AO_DIRS_MAX = 1024
 SRT_AO_SKIP_SELF = 1
 

@@ -172,6 +172,7 @@ struct srt_scene {
     // srt_shade_paths: the reflectance table of a host call (capacity counts objects) and the per-segment sums (capacity counts depth x n rows);
     // the other per-segment rows go through rq_hit / rq_t / rq_sobj / rq_sbounce, depth units a ray
     DevArray<float> rq_refl; DevArray<float> rq_ior; DevArray<float, 3> rq_plin;
+    DevArray<float> rq_f0; DevArray<int32_t> rq_fhit; DevArray<float> rq_ft; DevArray<float, 3> rq_flin; DevArray<float> rq_fres;      // the Fresnel table, the side rays' rows
     // srt_ao_rays / srt_ao_hits: the direction table of a host call (capacity counts directions) and the three arrays of srt_ao_out (rq_aobits:
     // capacity counts words, W a ray); a caller's hits go through rq_skip / rq_tin as srt_surface_hits' do
     DevArray<float, 3> rq_aodirs; DevArray<uint32_t> rq_aocnt; DevArray<float> rq_aoval; DevArray<uint32_t> rq_aobits;
@@ -1860,13 +1861,22 @@ static int check_paths(const srt_scene* s, uint32_t n, const float* rays, const 
 static inline bool paths_wanted(const float* rgb_linear, const uint8_t* rgb8, const srt_path_out* o) {
     return rgb_linear || rgb8 || (o && (o->hit_id || o->t || o->obj || o->rgb_linear || o->rays));
 }
+static inline bool fresnel_wanted(const srt_fresnel_out* o) { return o && (o->hit_id || o->t || o->rgb_linear || o->fresnel); }
 
 // What a path call may bring beyond its rays, each part NULL where the entry point has none or its caller passes none: the shadow rule
-// of srt_*_paths_shadow, the masks per ray kind of srt_*_paths_masked, the refraction table of srt_*_paths_refract.
-struct PathOptions { const srt_shadow_rule* shadow = nullptr; const srt_visibility* vis = nullptr; const srt_refraction* refr = nullptr; };
+// of srt_*_paths_shadow, the masks per ray kind of srt_*_paths_masked, the refraction table of srt_*_paths_refract, the Fresnel table and
+// the side rays' rows of srt_*_paths_fresnel.
+struct PathOptions {
+    const srt_shadow_rule* shadow = nullptr; const srt_visibility* vis = nullptr; const srt_refraction* refr = nullptr; const srt_fresnel* fres = nullptr;
+    // The two tables of a call that splits, both there or both NULL: without an ior nothing can split, and the call is the one without f0
+    const float* ior() const { return refr ? refr->ior : nullptr; }
+    const float* f0() const { return ior() && fres ? fres->f0 : nullptr; }
+    const srt_fresnel_out* side_rows() const { return f0() ? fres->out : nullptr; }
+};
 // A rule's flags lie within SRT_SHADOW_SELF, a table's are 0
 static inline int check_path_options(const PathOptions& o) {
     if (o.refr && o.refr->flags) return SRT_ERR_ARG;
+    if (o.fres && o.fres->flags) return SRT_ERR_ARG;
     if (o.shadow && (o.shadow->flags & ~(uint32_t)SRT_SHADOW_SELF)) return SRT_ERR_ARG;
     return SRT_OK;
 }
@@ -1877,21 +1887,28 @@ static inline ShadowRule shadow_rule_or_reference(const srt_shadow_rule* r) { re
 static inline QueryMask query_mask_or_all(const srt_scene* s, const srt_visibility* v) { return v ? query_mask(s, v) : QueryMask{ nullptr, nullptr, ~0u, ~0u, ~0u }; }
 
 extern "C++" {
-// The four families of a path kernel, each a table over (COUNT, SMOOTH, INT_SHIN), and the one launch of a path call.  The family: with a
+// The five families of a path kernel, each a table over (COUNT, SMOOTH, INT_SHIN), and the one launch of a path call.  The family: with a
+// refraction table and a Fresnel table (PathOptions::f0) the FRESNEL one, under what the REFRACT one runs under; else with a
 // refraction table (refr and refr->ior both there) the REFRACT one, under the caller's rule or the reference's and the caller's masks or
 // all ones; else with masks the MASK one, under the caller's rule or the reference's; else with a rule the SHADOW one; else the family
-// that takes none of the three -- the kernel srt_shade_paths / srt_render_paths launched before any of them existed.  `lead`: the
-// arguments all four take.
-template <typename P, typename S, typename M, typename R>
-struct PathBuilds { std::array<P, 8> plain; std::array<S, 8> shadow; std::array<M, 8> masked; std::array<R, 8> refract; };
-template <typename P, typename S, typename M, typename R>
-static PathBuilds<P, S, M, R> path_builds(const std::array<P, 8>& plain, const std::array<S, 8>& shadow, const std::array<M, 8>& masked, const std::array<R, 8>& refract) {
-    return PathBuilds<P, S, M, R>{ plain, shadow, masked, refract };
+// that takes none of them -- the kernel srt_shade_paths / srt_render_paths launched before any of them existed.  `lead`: the
+// arguments all five take.
+template <typename P, typename S, typename M, typename R, typename F>
+struct PathBuilds { std::array<P, 8> plain; std::array<S, 8> shadow; std::array<M, 8> masked; std::array<R, 8> refract; std::array<F, 8> fresnel; };
+template <typename P, typename S, typename M, typename R, typename F>
+static PathBuilds<P, S, M, R, F> path_builds(const std::array<P, 8>& plain, const std::array<S, 8>& shadow, const std::array<M, 8>& masked, const std::array<R, 8>& refract,
+                                             const std::array<F, 8>& fresnel) {
+    return PathBuilds<P, S, M, R, F>{ plain, shadow, masked, refract, fresnel };
 }
 template <typename Builds, typename... A>
 static int launch_paths(const Builds& builds, const srt_scene* s, const srt_params* p, const PathOptions& o, dim3 grid, hipStream_t stream, const A&... lead) {
     const size_t build = build_index((p->flags & SRT_FLAG_COUNT_WORK) != 0, (p->flags & SRT_FLAG_SMOOTH_NORMALS) != 0, s->rec->int_shin);
-    if (const float* d_ior = o.refr ? o.refr->ior : nullptr)
+    if (const float* d_f0 = o.f0()) {
+        const srt_fresnel_out* rows = o.side_rows();
+        return launch_query(builds.fresnel[build], grid, stream, lead..., shadow_rule_or_reference(o.shadow), query_mask_or_all(s, o.vis), o.ior(),
+                            QueryFresnel{ d_f0, rows ? *rows : srt_fresnel_out{} });
+    }
+    if (const float* d_ior = o.ior())
         return launch_query(builds.refract[build], grid, stream, lead..., shadow_rule_or_reference(o.shadow), query_mask_or_all(s, o.vis), d_ior);
     if (o.vis) return launch_query(builds.masked[build], grid, stream, lead..., shadow_rule_or_reference(o.shadow), query_mask(s, o.vis));
     if (o.shadow) return launch_query(builds.shadow[build], grid, stream, lead..., shadow_rule(o.shadow));
@@ -1903,11 +1920,11 @@ static int shade_paths_device_impl(srt_scene* s, uint32_t n, const float* d_rays
                                    const PathOptions& opt, hipStream_t stream, float* d_rgb_linear, uint8_t* d_rgb8, const srt_path_out* seg, bool count_hits) {
     SRT_TRY(check_path_options(opt));
     SRT_TRY(check_paths(s, n, d_rays, p, path));
-    if (!n || (!count_hits && !paths_wanted(d_rgb_linear, d_rgb8, seg))) return SRT_OK;
+    if (!n || (!count_hits && !paths_wanted(d_rgb_linear, d_rgb8, seg) && !fresnel_wanted(opt.side_rows()))) return SRT_OK;
     QueryLaunch q;
     SRT_TRY(query_prologue(s, n, stream, p, (p->flags & SRT_FLAG_COUNT_WORK) != 0 || count_hits, &q));
     static const auto builds = path_builds(std::array{ BUILDS_3(k_query_path) }, std::array{ BUILDS_3(k_query_path_shadow) }, std::array{ BUILDS_3(k_query_path_masked) },
-                                           std::array{ BUILDS_3(k_query_path_refract) });
+                                           std::array{ BUILDS_3(k_query_path_refract) }, std::array{ BUILDS_3(k_query_path_fresnel) });
     return launch_paths(builds, s, p, opt, q.grid, q.stream, s->dev, n, d_rays, rays_wide(d_rays), query_shade(s, p), query_range(d_t_range), *path, d_rgb_linear, d_rgb8,
                         seg ? *seg : srt_path_out{}, q.ctr);
 }
@@ -1928,13 +1945,13 @@ static int render_paths_device_impl(srt_scene* s, const srt_params* p, const srt
     SRT_TRY(check_path_options(opt));
     SRT_TRY(check_render_paths(s, p, path));
     const uint32_t rows = srt_rows_owned(p), wl = srt_cols_owned(p);
-    if (!rows || !wl || (!count_hits && !paths_wanted(d_rgb_linear, d_rgb8, seg))) return SRT_OK;
+    if (!rows || !wl || (!count_hits && !paths_wanted(d_rgb_linear, d_rgb8, seg) && !fresnel_wanted(opt.side_rows()))) return SRT_OK;
     QueryLaunch q;
     SRT_TRY(query_prologue(s, 0, stream, p, (p->flags & SRT_FLAG_COUNT_WORK) != 0 || count_hits, &q));
     const DevParams dp = dev_params(s, p, FramePlan{}).hit;      // the frame's geometry only: the kernel takes lights and literals from QueryShade
     const uint32_t m = (uint32_t)std::lround(std::sqrt((double)p->spp));      // (m x m == spp: check_frame)
     static const auto builds = path_builds(std::array{ BUILDS_3(k_render_path) }, std::array{ BUILDS_3(k_render_path_shadow) }, std::array{ BUILDS_3(k_render_path_masked) },
-                                           std::array{ BUILDS_3(k_render_path_refract) });
+                                           std::array{ BUILDS_3(k_render_path_refract) }, std::array{ BUILDS_3(k_render_path_fresnel) });
     return launch_paths(builds, s, p, opt, dim3((wl + 15) / 16, (rows + 15) / 16), q.stream, s->dev, dp, p->spp, m, query_shade(s, p), *path, d_rgb_linear, d_rgb8,
                         seg ? *seg : srt_path_out{}, q.ctr);
 }
@@ -2145,29 +2162,35 @@ static int shade_rays_impl(srt_scene* s, uint32_t n, const float* rays, const fl
     return stats ? query_stats(s, n, p->n_lights, stats) : SRT_OK;
 }
 
-// What the host forms of the two path calls share: the seven results of n rays or pixels (the per-segment rows are depth units each), the
-// reflectance and refraction tables (n_objects floats each, where the call brings them), and the round trip of all of them, in which
+// What the host forms of the two path calls share: the seven results of n rays or pixels and the four of the side rays (the per-segment rows
+// are depth units each), the reflectance, refraction and Fresnel tables (n_objects floats each, where the call brings them; the side
+// rays' rows and f0 only where the call splits, PathOptions::f0), and the round trip of all of them, in which
 // launch(stream, path, options, segments) gets the caller's structs with the handle's buffers in the place of the host arrays.
 struct PathArrays {
     QueryArray<float, 3> lin; QueryArray<uint8_t, 3> rgb8;
     QueryArray<int32_t, 1> hit; QueryArray<float, 1> t; QueryArray<int32_t, 1> obj; QueryArray<float, 3> seg_lin; QueryArray<float, 6> rays;
-    QueryArray<float, 1> refl, ior;
+    QueryArray<float, 1> refl, ior, f0;
+    QueryArray<int32_t, 1> side_hit; QueryArray<float, 1> side_t; QueryArray<float, 3> side_lin; QueryArray<float, 1> side_F;
     template <typename Launch, typename... In>      // in: what else the call brings
     int round_trip(srt_scene* s, const srt_path_desc* path, const PathOptions& opt, Launch launch, const In&... in) const {
         return query_round_trip(s, [&](hipStream_t st) -> int {
             const srt_path_desc dpath = { path->depth, path->bounce_t_min, refl.on_device() };
             const srt_refraction drefr = { ior.on_device(), 0u };
             const srt_path_out dseg = { hit.on_device(), t.on_device(), obj.on_device(), seg_lin.on_device(), rays.on_device() };
-            return launch(st, &dpath, PathOptions{ .shadow = opt.shadow, .vis = opt.vis, .refr = &drefr }, &dseg);
-        }, lin, rgb8, hit, t, obj, seg_lin, rays, in..., refl, ior);
+            const srt_fresnel_out dside = { side_hit.on_device(), side_t.on_device(), side_lin.on_device(), side_F.on_device() };
+            const srt_fresnel dfres = { f0.on_device(), 0u, &dside };
+            return launch(st, &dpath, PathOptions{ .shadow = opt.shadow, .vis = opt.vis, .refr = &drefr, .fres = &dfres }, &dseg);
+        }, lin, rgb8, hit, t, obj, seg_lin, rays, side_hit, side_t, side_lin, side_F, in..., refl, ior, f0);
     }
 };
 static PathArrays path_arrays(srt_scene* s, uint32_t n, const srt_path_desc* path, const PathOptions& opt, float* rgb_linear, uint8_t* rgb8, const srt_path_out* seg) {
     const srt_path_out h = seg ? *seg : srt_path_out{};
+    const srt_fresnel_out f = opt.side_rows() ? *opt.side_rows() : srt_fresnel_out{};
     const size_t rows = (size_t)path->depth * n, nO = s->dev.n_objects;
     return PathArrays{ query_out(rgb_linear, s->rq_lin, n), query_out(rgb8, s->rq_rgb8, n), query_out(h.hit_id, s->rq_hit, rows), query_out(h.t, s->rq_t, rows),
                        query_out(h.obj, s->rq_sobj, rows), query_out(h.rgb_linear, s->rq_plin, rows), query_out(h.rays, s->rq_sbounce, rows),
-                       query_in(path->reflectance, s->rq_refl, nO), query_in(opt.refr ? opt.refr->ior : nullptr, s->rq_ior, nO) };
+                       query_in(path->reflectance, s->rq_refl, nO), query_in(opt.ior(), s->rq_ior, nO), query_in(opt.f0(), s->rq_f0, nO),
+                       query_out(f.hit_id, s->rq_fhit, rows), query_out(f.t, s->rq_ft, rows), query_out(f.rgb_linear, s->rq_flin, rows), query_out(f.fresnel, s->rq_fres, rows) };
 }
 
 // srt_shade_paths: hit_rays counts the hits of all segments, hence the shadow rays
@@ -2176,7 +2199,7 @@ static int shade_paths_impl(srt_scene* s, uint32_t n, const float* rays, const f
     SRT_TRY(check_path_options(opt));
     SRT_TRY(check_paths(s, n, rays, p, path));
     if (stats) std::memset(stats, 0, sizeof(*stats));
-    if (!n || (!stats && !paths_wanted(rgb_linear, rgb8, seg))) return SRT_OK;
+    if (!n || (!stats && !paths_wanted(rgb_linear, rgb8, seg) && !fresnel_wanted(opt.side_rows()))) return SRT_OK;
     const PathArrays a = path_arrays(s, n, path, opt, rgb_linear, rgb8, seg);
     const auto i_rays = query_in(rays, s->rq_rays, n); const auto i_range = query_in(t_range, s->rq_range, n);
     SRT_TRY(a.round_trip(s, path, opt, [&](hipStream_t st, const srt_path_desc* dpath, const PathOptions& dopt, const srt_path_out* dseg) {
@@ -2192,7 +2215,7 @@ static int render_paths_impl(srt_scene* s, const srt_params* p, const srt_path_d
     SRT_TRY(check_render_paths(s, p, path));
     if (stats) std::memset(stats, 0, sizeof(*stats));
     const uint32_t n = srt_rows_owned(p) * srt_cols_owned(p);      // (< 2^32: check_render_paths)
-    if (!n || (!stats && !paths_wanted(rgb_linear, rgb8, seg))) return SRT_OK;
+    if (!n || (!stats && !paths_wanted(rgb_linear, rgb8, seg) && !fresnel_wanted(opt.side_rows()))) return SRT_OK;
     const PathArrays a = path_arrays(s, n, path, opt, rgb_linear, rgb8, seg);
     const bool padded = p->block_cols != 0;      // padding pixels are not written: what the handle's buffers hold there must not reach the caller
     SRT_TRY(a.round_trip(s, path, opt, [&](hipStream_t st, const srt_path_desc* dpath, const PathOptions& dopt, const srt_path_out* dseg) -> int {
@@ -2203,7 +2226,7 @@ static int render_paths_impl(srt_scene* s, const srt_params* p, const srt_path_d
             // columns would save it).
             hipError_t e = hipSuccess;
             const auto up = [&](const auto& arr) { if (arr.out && e == hipSuccess) e = hipMemcpy(arr.dev.p, arr.out, arr.count * arr.unit, hipMemcpyHostToDevice); };
-            up(a.hit); up(a.t); up(a.obj); up(a.seg_lin); up(a.rays); up(a.lin); up(a.rgb8);
+            up(a.hit); up(a.t); up(a.obj); up(a.seg_lin); up(a.rays); up(a.side_hit); up(a.side_t); up(a.side_lin); up(a.side_F); up(a.lin); up(a.rgb8);
             HIP_TRY(e);
         }
         return render_paths_device_impl(s, p, dpath, dopt, st, a.lin.on_device(), a.rgb8.on_device(), dseg, stats != nullptr);
@@ -2423,6 +2446,25 @@ int srt_render_paths_refract_device(srt_scene* s, const srt_params* p, const srt
 int srt_render_paths_refract(srt_scene* s, const srt_params* p, const srt_path_desc* path, const srt_shadow_rule* shadow, const srt_visibility* vis,
                              const srt_refraction* refr, float* rgb_linear, uint8_t* rgb8, const srt_path_out* seg, srt_stats* stats) {
     return guarded([&] { return render_paths_impl(s, p, path, PathOptions{ .shadow = shadow, .vis = vis, .refr = refr }, rgb_linear, rgb8, seg, stats); });
+}
+// Fresnel split: the four path calls with a Fresnel table after the refraction table (no f0, or no ior: the _refract call above, with its kernels)
+int srt_shade_paths_fresnel_device(srt_scene* s, uint32_t n, const float* d_rays, const float* d_t_range, const srt_params* p, const srt_path_desc* path,
+                                   const srt_shadow_rule* shadow, const srt_visibility* vis, const srt_refraction* refr, const srt_fresnel* fres, void* stream,
+                                   float* d_rgb_linear, uint8_t* d_rgb8, const srt_path_out* seg) {
+    return guarded([&] { return shade_paths_device_impl(s, n, d_rays, d_t_range, p, path, PathOptions{ .shadow = shadow, .vis = vis, .refr = refr, .fres = fres }, (hipStream_t)stream, d_rgb_linear, d_rgb8, seg, false); });
+}
+int srt_shade_paths_fresnel(srt_scene* s, uint32_t n, const float* rays, const float* t_range, const srt_params* p, const srt_path_desc* path, const srt_shadow_rule* shadow,
+                            const srt_visibility* vis, const srt_refraction* refr, const srt_fresnel* fres, float* rgb_linear, uint8_t* rgb8, const srt_path_out* seg,
+                            srt_stats* stats) {
+    return guarded([&] { return shade_paths_impl(s, n, rays, t_range, p, path, PathOptions{ .shadow = shadow, .vis = vis, .refr = refr, .fres = fres }, rgb_linear, rgb8, seg, stats); });
+}
+int srt_render_paths_fresnel_device(srt_scene* s, const srt_params* p, const srt_path_desc* path, const srt_shadow_rule* shadow, const srt_visibility* vis,
+                                    const srt_refraction* refr, const srt_fresnel* fres, void* stream, float* d_rgb_linear, uint8_t* d_rgb8, const srt_path_out* seg) {
+    return guarded([&] { return render_paths_device_impl(s, p, path, PathOptions{ .shadow = shadow, .vis = vis, .refr = refr, .fres = fres }, (hipStream_t)stream, d_rgb_linear, d_rgb8, seg, false); });
+}
+int srt_render_paths_fresnel(srt_scene* s, const srt_params* p, const srt_path_desc* path, const srt_shadow_rule* shadow, const srt_visibility* vis,
+                             const srt_refraction* refr, const srt_fresnel* fres, float* rgb_linear, uint8_t* rgb8, const srt_path_out* seg, srt_stats* stats) {
+    return guarded([&] { return render_paths_impl(s, p, path, PathOptions{ .shadow = shadow, .vis = vis, .refr = refr, .fres = fres }, rgb_linear, rgb8, seg, stats); });
 }
 
 int srt_surface_rays_device(srt_scene* s, uint32_t n, const float* d_rays, const float* d_t_range, uint32_t flags, void* stream, int32_t* d_hit_id, float* d_t,

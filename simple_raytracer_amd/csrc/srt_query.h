@@ -630,6 +630,33 @@ __device__ __forceinline__ V3 refract_dir(const V3 d, const V3 N, const float n)
     return mk(tir ? m.x : r.x, tir ? m.y : r.y, tir ? m.z : r.z);
 }
 
+// refract_dir's statements with three of their intermediates returned beside the direction: `entering`, `dv` and `k` are what the Fresnel
+// weight of the FRESNEL builds is made of (schlick_weight).  refract_dir itself is left as it is -- the builds without FRESNEL keep their
+// code -- so whoever changes one changes the other: tests/test_gpu_fresnel.py compares the two calls bit for bit.
+__device__ __forceinline__ V3 refract_dir_parts(const V3 d, const V3 N, const float n, bool& entering, float& dv, float& k) {
+    const float L = sqrtf(dot3(d, d)), inv = 1.0f / L;
+    const V3 I = mk(d.x * inv, d.y * inv, d.z * inv);
+    const float c = dot3(N, I);
+    entering = c < 0.0f;
+    const V3 Nf = entering ? N : neg(N);
+    dv = entering ? c : -c;
+    const float eta = entering ? 1.0f / n : n;
+    k = 1.0f - (eta * eta) * (1.0f - dv * dv);
+    const float sn = eta * dv + sqrtf(k);
+    const V3 r = mk((eta * I.x - sn * Nf.x) * L, (eta * I.y - sn * Nf.y) * L, (eta * I.z - sn * Nf.z) * L);
+    const V3 m = mirror_dir(d, N);
+    const bool tir = k < 0.0f;
+    return mk(tir ? m.x : r.x, tir ? m.y : r.y, tir ? m.z : r.z);
+}
+
+// Schlick's weight of the reflected share at a glass hit (include/srt.h, "Fresnel split"): x is the cosine on the thin side -- the
+// incident one going in, the transmitted one going out.  A polynomial, f32 without contraction; nothing is clamped.
+__device__ __forceinline__ float schlick_weight(const float f0, const bool entering, const float dv, const float k) {
+    const float x = entering ? -dv : sqrtf(k);
+    const float m = 1.0f - x, m2 = m * m, m5 = (m2 * m2) * m;
+    return f0 + (1.0f - f0) * m5;
+}
+
 // (is_hit, id, o, d, t, the surface there) -> the row of every wanted output.  Called by the whole wave (base < n_rays is wave-uniform).
 __device__ __forceinline__ void surface_store(const DevScene& s, const srt_surface_out& out, const size_t base, const uint32_t lane, const uint32_t rows,
                                               const bool is_hit, const int32_t id, const V3 o, const V3 d, const float t, const Surface& f, float* stage) {
@@ -869,6 +896,9 @@ __global__ __launch_bounds__(256) void k_query_ao(DevScene s, uint32_t n_rays, c
 // Refracting paths (srt_shade_paths_refract): the REFRACT build of the same statements.  The one thing that differs is the direction of
 // the next segment after a hit on an object k with ior[k] > 0: refract_dir instead of mirror_dir, from the same point, with the same
 // interval.  The walk does not skip the hit's own object, so a ray that enters a solid finds its far side.
+// Fresnel split (srt_shade_paths_fresnel): the FRESNEL build on top of REFRACT.  A glass hit of an object with f0 >= 0 also sends a depth-1
+// side ray along mirror_dir, walked and shaded by the same statements at the end of the segment's iteration; its sum enters the near-end
+// mix with Schlick's weight (path_segments).
 // =================================================================================================
 template <int K, typename RayOf>
 __device__ __forceinline__ void store_rows_dealt(float* __restrict__ dst, const uint32_t lane, const size_t n_rays, const float (&v)[K], float* stage, RayOf ray_of) {
@@ -892,6 +922,10 @@ __device__ __forceinline__ void store_rows_dealt(float* __restrict__ dst, const 
 #endif
 }
 
+// The Fresnel table and the side rays' rows of the FRESNEL builds, their own kernel argument: f0, n_objects floats; out, laid out as
+// srt_path_out's hit_id, t and rgb_linear (all NULL = no rows).
+struct QueryFresnel { const float* f0; srt_fresnel_out out; };
+
 // The segments of the paths of one wave's 64 rays (the header comment above), shared by k_query_path and k_render_path: the walk, phase 2,
 // the per-segment rows, the mirrored ray and the near-end mix.  ri: the lane's row in every output (seg's rows are n apart), ray_of: the
 // same for any lane of the wave (>= n: a lane without a ray) -- the transposed row stores need it.  seg: all NULL = no per-segment rows.
@@ -901,15 +935,27 @@ __device__ __forceinline__ void store_rows_dealt(float* __restrict__ dst, const 
 // (the builds without it never read qm).
 // REFRACT: a hit on an object k with ior[k] > 0 sends the next segment along refract_dir instead of mirror_dir, chosen per lane by a
 // select (the builds without it never read ior; ior is non-NULL in the builds with it).
-template <bool COUNT, bool SMOOTH, bool INT_SHIN, bool SHADOW, bool MASK = false, bool REFRACT = false, typename RayOf>
+// FRESNEL (on top of REFRACT; include/srt.h, "Fresnel split"): a hit on an object that SPLITS -- ior[k] > 0 and f0[k] >= 0 -- that is not
+// totally reflected and is not the path's last segment also sends a depth-1 SIDE RAY along mirror_dir from the same point.  At the end of
+// segment b's iteration, when the row stores are out and q, best and wray are free, the wave tests __ballot(split) and, if any lane
+// splits, walks its side rays with the statements of a segment: query_walk with qm.bounce and (bounce_t_min, +inf), shade_hits_rank,
+// shade_hits_lights under the same rule.  Across segment b + 1's walk a lane then carries the side hit's sum (3), the weight F and the
+// side-hit flag beside pend / pend_k, and the mix of segment b, made when b + 1's hit is known, gives the side sum its share.  A wave
+// without a split pays the ballot.  The builds without FRESNEL never read fr (fr.f0 is non-NULL in the builds with it).
+template <bool COUNT, bool SMOOTH, bool INT_SHIN, bool SHADOW, bool MASK = false, bool REFRACT = false, bool FRESNEL = false, typename RayOf>
 __device__ __forceinline__ V3 path_segments(const DevScene& s, const QueryShade& p, const srt_path_desc& path, const srt_path_out& seg, const size_t n, const size_t ri,
                                             const bool live, V3 o, V3 d, float t_min, float t_max, const uint32_t lane, uint32_t* q, unsigned long long* best,
                                             float (*wray)[64], const RayOf ray_of, unsigned long long* __restrict__ counters, const uint32_t shard, bool& hit0,
                                             unsigned long long& n_node, unsigned long long& n_tri, unsigned long long& n_node_s, unsigned long long& n_tri_s,
-                                            const ShadowRule rule, const QueryMask qm = QueryMask{}, const float* __restrict__ ior = nullptr) {
+                                            const ShadowRule rule, const QueryMask qm = QueryMask{}, const float* __restrict__ ior = nullptr,
+                                            const QueryFresnel fr = QueryFresnel{}) {
+    static_assert(!FRESNEL || REFRACT, "a side ray is taken at a transmitting hit");
     float* stage = &wray[0][0];
     V3 acc = mk(0.0f, 0.0f, 0.0f), pend = acc;          // the mix so far; the sum of the segment that waits for its weight
     float W = 1.0f, pend_k = 0.0f;                      // the weight of what follows; the waiting segment's reflectance
+    V3 side_sum = acc;                                  // FRESNEL: the waiting segment's side ray -- its hit's sum, its weight, whether it hit
+    float side_F = 0.0f;
+    bool side = false;
     bool alive = live, waiting = false;
     hit0 = false;
     uint32_t b = 0;
@@ -937,17 +983,40 @@ __device__ __forceinline__ V3 path_segments(const DevScene& s, const QueryShade&
         }
         if (counters) count_hits(counters, is_hit, shard);
         if (waiting) {                                  // segment b - 1 hit: its weight is known now
-            const float k = is_hit ? pend_k : 0.0f, a = W * (1.0f - k);
-            acc = mk(acc.x + a * pend.x, acc.y + a * pend.y, acc.z + a * pend.z);
-            W = W * k;
+            if (FRESNEL) {                              // a branch that misses gives its share to the other; no side ray: W = Wk * 1
+                const float k = (is_hit || side) ? pend_k : 0.0f, a = W * (1.0f - k), Wk = W * k;
+                acc = mk(acc.x + a * pend.x, acc.y + a * pend.y, acc.z + a * pend.z);
+                const float Fe = side ? (is_hit ? side_F : 1.0f) : 0.0f;
+                if (side) {
+                    const float g = Wk * Fe;
+                    acc = mk(acc.x + g * side_sum.x, acc.y + g * side_sum.y, acc.z + g * side_sum.z);
+                }
+                W = Wk * (1.0f - Fe);
+            } else {
+                const float k = is_hit ? pend_k : 0.0f, a = W * (1.0f - k);
+                acc = mk(acc.x + a * pend.x, acc.y + a * pend.y, acc.z + a * pend.z);
+                W = W * k;
+            }
         }
         waiting = is_hit;
         if (b == 0) hit0 = is_hit;
+        bool split = false;                             // FRESNEL: this lane's hit takes a side ray, along sdir, with the weight F
+        V3 sdir = mk(0.0f, 0.0f, 0.0f);
+        float F = 0.0f;
         if (is_hit) {
             pend = sum;
             pend_k = path.reflectance ? path.reflectance[obj] : 0.0f;
             const V3 P = o + d * t;                     // the bounce row of surface_store: the point, not moved, and the mirrored direction
-            if (REFRACT) {
+            if (FRESNEL) {
+                const float n_obj = ior[obj], f0 = fr.f0[obj];
+                bool entering;
+                float dv, k;
+                const V3 m = mirror_dir(d, f.nrm), r = refract_dir_parts(d, f.nrm, n_obj, entering, dv, k);
+                const bool glass = n_obj > 0.0f;
+                d = mk(glass ? r.x : m.x, glass ? r.y : m.y, glass ? r.z : m.z);
+                split = glass && f0 >= 0.0f && !(k < 0.0f) && b + 1 < path.depth;      // (a negative or NaN f0: no split; a NaN k splits)
+                if (split) { sdir = m; F = schlick_weight(f0, entering, dv, k); }
+            } else if (REFRACT) {
                 const float n_obj = ior[obj];           // (0, negative, NaN: the object mirrors)
                 const V3 m = mirror_dir(d, f.nrm), r = refract_dir(d, f.nrm, n_obj);
                 const bool glass = n_obj > 0.0f;
@@ -959,6 +1028,33 @@ __device__ __forceinline__ V3 path_segments(const DevScene& s, const QueryShade&
             t_min = path.bounce_t_min; t_max = __builtin_inff();
         }
         alive = is_hit;
+        if (FRESNEL) {
+            // the side rays of segment b: from the hit point (o by now), not moved, along the mirrored direction
+            int32_t sid = -1;
+            float st = __builtin_inff();
+            V3 ssum = mk(0.0f, 0.0f, 0.0f);
+            side = false;
+            if (__ballot(split)) {                      // wave-uniform
+                query_walk<COUNT, true, MergeClosest, MASK>(s, split, o, sdir, lane, q, MergeClosest{ best }, wray, n_node, n_tri, path.bounce_t_min, __builtin_inff(),
+                                                            qm.obj, qm.bounce);
+                const unsigned long long skey = split ? best[lane] : ~0ull;
+                side = skey != ~0ull;
+                sid = side ? (int32_t)(uint32_t)skey : -1;
+                Surface sf;
+                const WaveHits swh = shade_hits_rank<SMOOTH, SHADOW>(s, side, sid, o, sdir, st, sf, wray, rule.self);
+                ssum = shade_hits_lights<COUNT, INT_SHIN, SHADOW, MASK>(s, p, lane, side, swh, o, sdir, st, sf, wray, best, n_node_s, n_tri_s, rule.t_min, rule.t_max,
+                                                                        qm.obj, qm.shadow);
+                __builtin_amdgcn_wave_barrier();        // phase 2 is over: the rays' slots are the stage
+                if (counters) count_hits(counters, side, shard);
+            }
+            if (live) {
+                if (fr.out.hit_id) fr.out.hit_id[row + ri] = sid;
+                if (fr.out.t) fr.out.t[row + ri] = st;
+                if (fr.out.fresnel) fr.out.fresnel[row + ri] = F;
+            }
+            if (fr.out.rgb_linear) { const float v[3] = { ssum.x, ssum.y, ssum.z }; store_rows_dealt<3>(fr.out.rgb_linear + row * 3, lane, n, v, stage, ray_of); }
+            side_sum = ssum; side_F = F;
+        }
     }
     if (waiting) {                                      // the last segment that hit: nothing follows it, k = 0
         const float a = W * (1.0f - 0.0f);
@@ -973,17 +1069,26 @@ __device__ __forceinline__ V3 path_segments(const DevScene& s, const QueryShade&
         }
         if (seg.rgb_linear) { const float v[3] = { 0.0f, 0.0f, 0.0f }; store_rows_dealt<3>(seg.rgb_linear + row * 3, lane, n, v, stage, ray_of); }
         if (seg.rays) { const float v[6] = { 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f }; store_rows_dealt<6>(seg.rays + row * 6, lane, n, v, stage, ray_of); }
+        if (FRESNEL) {
+            if (live) {
+                if (fr.out.hit_id) fr.out.hit_id[row + ri] = -1;
+                if (fr.out.t) fr.out.t[row + ri] = __builtin_inff();
+                if (fr.out.fresnel) fr.out.fresnel[row + ri] = 0.0f;
+            }
+            if (fr.out.rgb_linear) { const float v[3] = { 0.0f, 0.0f, 0.0f }; store_rows_dealt<3>(fr.out.rgb_linear + row * 3, lane, n, v, stage, ray_of); }
+        }
     }
     return acc;
 }
 
 // The body of both k_query_path kernels: k_query_path is what a call without a shadow rule launches, argument for argument what it was;
 // k_query_path_shadow takes the rule as one more argument and is the SHADOW build of the same statements.
-template <bool COUNT, bool SMOOTH, bool INT_SHIN, bool SHADOW, bool MASK = false, bool REFRACT = false>
+template <bool COUNT, bool SMOOTH, bool INT_SHIN, bool SHADOW, bool MASK = false, bool REFRACT = false, bool FRESNEL = false>
 __device__ __forceinline__ void query_path_rays(const DevScene& s, const uint32_t n_rays, const float* __restrict__ rays, const uint32_t wide, const QueryShade& p,
                                                 const QueryRange tr, const srt_path_desc& path, float* __restrict__ rgb_linear, uint8_t* __restrict__ rgb8,
                                                 const srt_path_out& seg, unsigned long long* __restrict__ counters, const ShadowRule rule,
-                                                const QueryMask qm = QueryMask{}, const float* __restrict__ ior = nullptr) {
+                                                const QueryMask qm = QueryMask{}, const float* __restrict__ ior = nullptr,
+                                                const QueryFresnel fr = QueryFresnel{}) {
     __shared__ uint32_t q_all[4][QCAP];
     __shared__ unsigned long long best_all[256];
     __shared__ float ray_all[4][8][64];
@@ -999,9 +1104,9 @@ __device__ __forceinline__ void query_path_rays(const DevScene& s, const uint32_
     if (live) load_ray(rays, ri, wide != 0, o, d);
     if (tr.t && live) load_range(tr, ri, t_min, t_max);
     bool hit0;
-    const V3 acc = path_segments<COUNT, SMOOTH, INT_SHIN, SHADOW, MASK, REFRACT>(s, p, path, seg, n, ri, live, o, d, t_min, t_max, lane, q_all[wave], best_all + wave * 64,
-                                                                                 ray_all[wave], ray_of, counters, blockIdx.x, hit0, n_node, n_tri, n_node_s, n_tri_s, rule, qm,
-                                                                                 ior);
+    const V3 acc = path_segments<COUNT, SMOOTH, INT_SHIN, SHADOW, MASK, REFRACT, FRESNEL>(s, p, path, seg, n, ri, live, o, d, t_min, t_max, lane, q_all[wave],
+                                                                                          best_all + wave * 64, ray_all[wave], ray_of, counters, blockIdx.x, hit0, n_node, n_tri,
+                                                                                          n_node_s, n_tri_s, rule, qm, ior, fr);
     if (live) store_pixel(rgb_linear, rgb8, ri, acc, hit0, p.reinhard, p.gamma, p.bg);
     if (COUNT) { wave_add(counters + 1, n_node); wave_add(counters + 2, n_tri); wave_add(counters + 3, n_node_s); wave_add(counters + 4, n_tri_s); }
 }
@@ -1036,6 +1141,15 @@ __global__ __launch_bounds__(256) void k_query_path_refract(DevScene s, uint32_t
     query_path_rays<COUNT, SMOOTH, INT_SHIN, true, true, true>(s, n_rays, rays, wide, p, tr, path, rgb_linear, rgb8, seg, counters, rule, qm, ior);
 }
 
+// srt_shade_paths_fresnel: the FRESNEL build on top of k_query_path_refract's; f0 and the side rays' rows travel by value as one more argument.
+template <bool COUNT, bool SMOOTH, bool INT_SHIN>
+__global__ __launch_bounds__(256) void k_query_path_fresnel(DevScene s, uint32_t n_rays, const float* __restrict__ rays, uint32_t wide, QueryShade p, QueryRange tr,
+                                                            srt_path_desc path, float* __restrict__ rgb_linear, uint8_t* __restrict__ rgb8, srt_path_out seg,
+                                                            unsigned long long* __restrict__ counters, ShadowRule rule, QueryMask qm, const float* __restrict__ ior,
+                                                            QueryFresnel fr) {
+    query_path_rays<COUNT, SMOOTH, INT_SHIN, true, true, true, true>(s, n_rays, rays, wide, p, tr, path, rgb_linear, rgb8, seg, counters, rule, qm, ior, fr);
+}
+
 // =================================================================================================
 // Mirror paths in a frame (srt_render_paths): k_query_path's paths for the rays of a frame's own pixels.  The front end is the render
 // kernels': a wave owns one 8 x 8 pixel tile and a workgroup 16 x 16 (tile_pixel), the grid is 2-D over the call's local output, and a
@@ -1049,11 +1163,11 @@ __global__ __launch_bounds__(256) void k_query_path_refract(DevScene s, uint32_t
 // seg's rows are sub-sample 0's.  counters: as k_query_path's, over all sub-samples; the hit shard is the 2-D workgroup number.
 // =================================================================================================
 // The body of both k_render_path kernels, as query_path_rays is k_query_path's.  fp: the frame's geometry; sub_x / sub_y change per sub-sample.
-template <bool COUNT, bool SMOOTH, bool INT_SHIN, bool SHADOW, bool MASK = false, bool REFRACT = false>
+template <bool COUNT, bool SMOOTH, bool INT_SHIN, bool SHADOW, bool MASK = false, bool REFRACT = false, bool FRESNEL = false>
 __device__ __forceinline__ void render_path_pixels(const DevScene& s, DevParams& fp, const uint32_t spp, const uint32_t spp_m, const QueryShade& p, const srt_path_desc& path,
                                                    float* __restrict__ rgb_linear, uint8_t* __restrict__ rgb8, const srt_path_out& seg,
                                                    unsigned long long* __restrict__ counters, const ShadowRule rule, const QueryMask qm = QueryMask{},
-                                                   const float* __restrict__ ior = nullptr) {
+                                                   const float* __restrict__ ior = nullptr, const QueryFresnel fr = QueryFresnel{}) {
     __shared__ uint32_t q_all[4][QCAP];
     __shared__ unsigned long long best_all[256];
     __shared__ float ray_all[4][8][64];
@@ -1076,9 +1190,10 @@ __device__ __forceinline__ void render_path_pixels(const DevScene& s, DevParams&
         }
         const V3 d = live ? primary_dir(fp, px, y) : mk(0.0f, 0.0f, 1.0f);
         bool h;
-        const V3 acc = path_segments<COUNT, SMOOTH, INT_SHIN, SHADOW, MASK, REFRACT>(s, p, path, k == 0 ? seg : srt_path_out{}, n, ri, live, o, d, __builtin_nanf(""),
-                                                                                     __builtin_nanf(""), lane, q_all[wave], best_all + wave * 64, ray_all[wave], ray_of, counters,
-                                                                                     shard, h, n_node, n_tri, n_node_s, n_tri_s, rule, qm, ior);
+        const V3 acc = path_segments<COUNT, SMOOTH, INT_SHIN, SHADOW, MASK, REFRACT, FRESNEL>(s, p, path, k == 0 ? seg : srt_path_out{}, n, ri, live, o, d, __builtin_nanf(""),
+                                                                                              __builtin_nanf(""), lane, q_all[wave], best_all + wave * 64, ray_all[wave], ray_of,
+                                                                                              counters, shard, h, n_node, n_tri, n_node_s, n_tri_s, rule, qm, ior,
+                                                                                              k == 0 ? fr : QueryFresnel{ fr.f0, srt_fresnel_out{} });
         if (k == 0) { total = acc; hit0 = h; }
         else total = mk(total.x + acc.x, total.y + acc.y, total.z + acc.z);
     }
@@ -1111,4 +1226,12 @@ __global__ __launch_bounds__(256) void k_render_path_refract(DevScene s, DevPara
                                                              float* __restrict__ rgb_linear, uint8_t* __restrict__ rgb8, srt_path_out seg,
                                                              unsigned long long* __restrict__ counters, ShadowRule rule, QueryMask qm, const float* __restrict__ ior) {
     render_path_pixels<COUNT, SMOOTH, INT_SHIN, true, true, true>(s, fp, spp, spp_m, p, path, rgb_linear, rgb8, seg, counters, rule, qm, ior);
+}
+// srt_render_paths_fresnel: as k_query_path_fresnel is k_query_path_refract's.  The side rays' rows are sub-sample 0's, as seg's are.
+template <bool COUNT, bool SMOOTH, bool INT_SHIN>
+__global__ __launch_bounds__(256) void k_render_path_fresnel(DevScene s, DevParams fp, uint32_t spp, uint32_t spp_m, QueryShade p, srt_path_desc path,
+                                                             float* __restrict__ rgb_linear, uint8_t* __restrict__ rgb8, srt_path_out seg,
+                                                             unsigned long long* __restrict__ counters, ShadowRule rule, QueryMask qm, const float* __restrict__ ior,
+                                                             QueryFresnel fr) {
+    render_path_pixels<COUNT, SMOOTH, INT_SHIN, true, true, true, true>(s, fp, spp, spp_m, p, path, rgb_linear, rgb8, seg, counters, rule, qm, ior, fr);
 }

@@ -30,6 +30,7 @@ ABI_SYMBOLS = ("srt_params_default", "srt_light_staircase", "srt_rows_owned", "s
                "srt_render_paths_shadow", "srt_scene_set_object_masks", "srt_trace_rays_masked_device", "srt_trace_rays_masked", "srt_occluded_masked_device",
                "srt_occluded_masked", "srt_shade_paths_masked_device", "srt_shade_paths_masked", "srt_render_paths_masked_device", "srt_render_paths_masked",
                "srt_shade_paths_refract_device", "srt_shade_paths_refract", "srt_render_paths_refract_device", "srt_render_paths_refract",
+               "srt_shade_paths_fresnel_device", "srt_shade_paths_fresnel", "srt_render_paths_fresnel_device", "srt_render_paths_fresnel",
                "srt_ao_rays_device", "srt_ao_rays", "srt_ao_hits_device", "srt_ao_hits")
 MULTI_HIT_MAX = 16                # SRT_MULTI_HIT_MAX
 
@@ -175,6 +176,14 @@ def load(path=None):
         L.srt_render_paths_refract_device.argtypes = L.srt_render_paths_masked_device.argtypes[:5] + [_refr] + L.srt_render_paths_masked_device.argtypes[5:]
         L.srt_render_paths_refract.argtypes = L.srt_render_paths_masked.argtypes[:5] + [_refr] + L.srt_render_paths_masked.argtypes[5:]
         for f in (L.srt_shade_paths_refract_device, L.srt_shade_paths_refract, L.srt_render_paths_refract_device, L.srt_render_paths_refract):
+            f.restype = C.c_int
+        # the Fresnel split: one srt_fresnel* after the srt_refraction*
+        _fres = C.POINTER(abi.Fresnel)
+        L.srt_shade_paths_fresnel_device.argtypes = L.srt_shade_paths_refract_device.argtypes[:9] + [_fres] + L.srt_shade_paths_refract_device.argtypes[9:]
+        L.srt_shade_paths_fresnel.argtypes = L.srt_shade_paths_refract.argtypes[:9] + [_fres] + L.srt_shade_paths_refract.argtypes[9:]
+        L.srt_render_paths_fresnel_device.argtypes = L.srt_render_paths_refract_device.argtypes[:6] + [_fres] + L.srt_render_paths_refract_device.argtypes[6:]
+        L.srt_render_paths_fresnel.argtypes = L.srt_render_paths_refract.argtypes[:6] + [_fres] + L.srt_render_paths_refract.argtypes[6:]
+        for f in (L.srt_shade_paths_fresnel_device, L.srt_shade_paths_fresnel, L.srt_render_paths_fresnel_device, L.srt_render_paths_fresnel):
             f.restype = C.c_int
         # ambient occlusion: an srt_ao_desc* and an srt_visibility* after the flags, an srt_ao_out* last of the outputs
         _ao, _aout = C.POINTER(abi.AoDesc), C.POINTER(abi.AoOut)
@@ -539,9 +548,9 @@ class DeviceScene:
         _check(self.L.srt_ao_hits_device(self.h, n, C.c_void_p(rays), C.c_void_p(hit_id), C.c_void_p(t), _ao_flags(smooth, count), C.byref(desc), _vis_ref(visibility),
                                          C.c_void_p(stream), C.byref(aout)), "srt_ao_hits_device")
 
-    def _paths_host(self, kind, head, lead, params, depth, reflectance, bounce_t_min, want, count, smooth, fill, shadow, visibility, ior):
-        """The host form of a path call: srt_<kind>_paths and its _shadow, _masked and _refract forms.  head: the arguments before the
-        params; lead: the shape of one segment's rows."""
+    def _paths_host(self, kind, head, lead, params, depth, reflectance, bounce_t_min, want, count, smooth, fill, shadow, visibility, ior, fresnel=None):
+        """The host form of a path call: srt_<kind>_paths and its _shadow, _masked, _refract and _fresnel forms.  head: the arguments
+        before the params; lead: the shape of one segment's rows."""
         refl = None if reflectance is None else np.ascontiguousarray(reflectance, np.float32).reshape(-1)
         out, g = _outputs(want, lead, _PATH_SUMS, fill)
         seg, _ = _outputs(want, (max(int(depth), 0),) + lead, _PATH_SEGMENTS, fill)
@@ -550,24 +559,37 @@ class DeviceScene:
         pd = abi.PathDesc(depth, bounce_t_min, refl.ctypes.data if refl is not None else None)
         st = abi.Stats()
         refr, table = _refraction(ior, self.flat.n_objects)
-        fn, name, mid = _path_call(self.L, kind, "", abi.shadow_rule(shadow), abi.visibility(visibility), refr)
+        fres, f0 = None, None
+        if fresnel is not None:
+            f0 = np.ascontiguousarray(fresnel, np.float32).reshape(-1)
+            assert f0.shape[0] == self.flat.n_objects, "fresnel: one float per object"
+            side, _ = _outputs(want, (max(int(depth), 0),) + lead, _PATH_SIDE, fill)
+            out.update(side)
+            fout = abi.FresnelOut(*_addresses(side, _PATH_SIDE))
+            fres = abi.Fresnel(f0.ctypes.data, 0, C.pointer(fout))
+        fn, name, mid = _path_call(self.L, kind, "", abi.shadow_rule(shadow), abi.visibility(visibility), refr, fres)
         with _flags(params, count=count, smooth=smooth):
             rc = fn(*head, C.byref(params), C.byref(pd), *mid, g("rgb_linear"), g("rgb8"), C.byref(po), C.byref(st))
         _check(rc, name)
         out["stats"] = st.as_dict()
         return out
 
-    def _paths_device(self, kind, head, params, depth, reflectance, bounce_t_min, stream, rgb_linear, rgb8, segments, shadow, visibility, ior):
-        """The device form of a path call.  ior: None, or a device pointer (0: the _refract call without a table)."""
+    def _paths_device(self, kind, head, params, depth, reflectance, bounce_t_min, stream, rgb_linear, rgb8, segments, shadow, visibility, ior, fresnel=None, side=()):
+        """The device form of a path call.  ior: None, or a device pointer (0: the _refract call without a table).  fresnel: None, or a
+        device pointer to f0 (0: the _fresnel call without a table); side: the four device pointers of its srt_fresnel_out."""
         pd = abi.PathDesc(depth, bounce_t_min, reflectance or None)
         po = abi.PathOut(*(p or None for p in segments))
         refr = None if ior is None else abi.Refraction(ior or None, 0)
-        fn, name, mid = _path_call(self.L, kind, "_device", abi.shadow_rule(shadow), abi.visibility(visibility), refr)
+        fres = None
+        if fresnel is not None:
+            fout = abi.FresnelOut(*(p or None for p in side))
+            fres = abi.Fresnel(fresnel or None, 0, C.pointer(fout))
+        fn, name, mid = _path_call(self.L, kind, "_device", abi.shadow_rule(shadow), abi.visibility(visibility), refr, fres)
         _check(fn(*head, C.byref(params), C.byref(pd), *mid, C.c_void_p(stream), C.c_void_p(rgb_linear), C.c_void_p(rgb8), C.byref(po)), name)
 
     def shade_paths(self, rays, params: abi.Params, depth, reflectance=None, bounce_t_min=1e-3, t_range=None,
                     want=("rgb_linear", "rgb8", "seg_hit_id", "seg_t", "seg_obj", "seg_rgb_linear", "seg_rays"), count=False, smooth=False, shadow=None,
-                    visibility=None, ior=None):
+                    visibility=None, ior=None, fresnel=None):
         """srt_shade_paths: every ray of `rays` (n x 6, host array) followed through up to `depth` mirror bounces, each hit shaded as
         shade_rays(t_range=...) shades it, the segments mixed by `reflectance` (one float per object, or None = all 0).  A mirrored ray's
         interval is (bounce_t_min, +inf); t_range (n x 2) bounds segment 0.  Returns a dict of the arrays named in `want` -- rgb_linear
@@ -579,42 +601,50 @@ class DeviceScene:
         visibility: None, or (primary, bounce, shadow) -- the object masks segment 0, every later segment and every shadow ray are
         walked with (srt_*_paths_masked; set_object_masks gives the objects their bits).
         ior: None, or one float per object (host array) -- object k with ior[k] > 0 is glass: a ray that hits it goes on THROUGH the
-        surface, bent by Snell's law, instead of being mirrored (srt_*_paths_refract); reflectance keeps weighting what follows."""
+        surface, bent by Snell's law, instead of being mirrored (srt_*_paths_refract); reflectance keeps weighting what follows.
+        fresnel: None, or one float per object (host array), f0, the reflectance at normal incidence (schlick_f0(ior) for a dielectric)
+        -- at a hit on an object k with ior[k] > 0 and f0[k] >= 0 the mirrored ray is walked and shaded once as a side ray, and its sum
+        enters the mix with Schlick's weight (srt_*_paths_fresnel).  `want` may then name side_hit_id / side_t / fresnel (depth x n) and
+        side_rgb_linear (depth x n x 3): per segment, the side ray's hit, its sum and the weight F."""
         r = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
         n = r.shape[0]
         head = (self.h, n, _host(r, _f32p), _host(_t_range(t_range, n), _f32p))
-        return self._paths_host("shade", head, (n,), params, depth, reflectance, bounce_t_min, want, count, smooth, None, shadow, visibility, ior)
+        return self._paths_host("shade", head, (n,), params, depth, reflectance, bounce_t_min, want, count, smooth, None, shadow, visibility, ior, fresnel)
 
     def shade_paths_device(self, n, rays, params: abi.Params, depth, reflectance=0, bounce_t_min=1e-3, t_range=None, stream=0, rgb_linear=0, rgb8=0, seg_hit_id=0,
-                           seg_t=0, seg_obj=0, seg_rgb_linear=0, seg_rays=0, shadow=None, visibility=None, ior=None):
+                           seg_t=0, seg_obj=0, seg_rgb_linear=0, seg_rays=0, shadow=None, visibility=None, ior=None, fresnel=None, side_hit_id=0, side_t=0,
+                           side_rgb_linear=0, side_fresnel=0):
         """srt_shade_paths_device: raw device pointers (ints, e.g. torch.Tensor.data_ptr()) in, asynchronous on `stream`, one launch.  The
         light table of `params` is a host array; `reflectance` is a DEVICE pointer to n_objects floats (0 = all 0); t_range a device
         pointer to n x 2 floats, or None; the seg_* outputs are depth x n rows, segment-major.  The flags are those of `params`.
-        shadow, visibility: as in shade_paths.  ior: None, or a DEVICE pointer to n_objects floats (0 = no table): srt_shade_paths_refract_device."""
+        shadow, visibility: as in shade_paths.  ior: None, or a DEVICE pointer to n_objects floats (0 = no table): srt_shade_paths_refract_device.
+        fresnel: None, or a DEVICE pointer to the n_objects floats of f0 (0 = no table): srt_shade_paths_fresnel_device; the side_* outputs are
+        the depth x n rows of its srt_fresnel_out."""
         head = (self.h, n, C.c_void_p(rays), C.c_void_p(t_range or 0))
         self._paths_device("shade", head, params, depth, reflectance, bounce_t_min, stream, rgb_linear, rgb8, (seg_hit_id, seg_t, seg_obj, seg_rgb_linear, seg_rays),
-                           shadow, visibility, ior)
+                           shadow, visibility, ior, fresnel, (side_hit_id, side_t, side_rgb_linear, side_fresnel))
 
     def render_paths(self, params: abi.Params, depth, reflectance=None, bounce_t_min=1e-3,
                      want=("rgb_linear", "rgb8", "seg_hit_id", "seg_t", "seg_obj", "seg_rgb_linear", "seg_rays"), count=False, smooth=False, fill=None, shadow=None,
-                     visibility=None, ior=None):
+                     visibility=None, ior=None, fresnel=None):
         """srt_render_paths: shade_paths for the rays of the frame's own pixels -- the local pixels of a call with `params` (its block or
         tile deal, camera matrix and spp included); no ray array is built.  Returns a dict of the arrays named in `want` -- rgb_linear
         [rows, cols, 3] (mixed), rgb8 [rows, cols, 3], and per segment seg_hit_id / seg_t / seg_obj [depth, rows, cols], seg_rgb_linear
         [depth, rows, cols, 3], seg_rays [depth, rows, cols, 6] -- + 'stats'.  count / smooth add SRT_FLAG_COUNT_WORK /
         SRT_FLAG_SMOOTH_NORMALS for this call.  fill: a value every array holds before the call (padding pixels of a tile deal keep it).
-        shadow, visibility, ior: as in shade_paths."""
+        shadow, visibility, ior, fresnel: as in shade_paths; the side_* arrays and fresnel are [depth, rows, cols(, 3)]."""
         lead = (self.rows(params), self.cols(params))
-        return self._paths_host("render", (self.h,), lead, params, depth, reflectance, bounce_t_min, want, count, smooth, fill, shadow, visibility, ior)
+        return self._paths_host("render", (self.h,), lead, params, depth, reflectance, bounce_t_min, want, count, smooth, fill, shadow, visibility, ior, fresnel)
 
     def render_paths_device(self, params: abi.Params, depth, reflectance=0, bounce_t_min=1e-3, stream=0, rgb_linear=0, rgb8=0, seg_hit_id=0, seg_t=0, seg_obj=0,
-                            seg_rgb_linear=0, seg_rays=0, shadow=None, visibility=None, ior=None):
+                            seg_rgb_linear=0, seg_rays=0, shadow=None, visibility=None, ior=None, fresnel=None, side_hit_id=0, side_t=0, side_rgb_linear=0,
+                            side_fresnel=0):
         """srt_render_paths_device: raw device pointers (ints, e.g. torch.Tensor.data_ptr()) in, asynchronous on `stream`, one launch.  The
         light table of `params` is a host array; `reflectance` is a DEVICE pointer to n_objects floats (0 = all 0); the outputs are
         [rows, cols, ...] and the seg_* outputs [depth, rows, cols, ...] of the call's local pixels.  The flags are those of `params`.
-        shadow, visibility: as in shade_paths.  ior: as in shade_paths_device."""
+        shadow, visibility: as in shade_paths.  ior, fresnel and the side_* outputs: as in shade_paths_device."""
         self._paths_device("render", (self.h,), params, depth, reflectance, bounce_t_min, stream, rgb_linear, rgb8, (seg_hit_id, seg_t, seg_obj, seg_rgb_linear, seg_rays),
-                           shadow, visibility, ior)
+                           shadow, visibility, ior, fresnel, (side_hit_id, side_t, side_rgb_linear, side_fresnel))
 
     def sync(self):
         st = abi.Stats()
@@ -657,6 +687,8 @@ _FRAME = {**_HIT, "rgb_linear": (np.float32, (3,)), "rgb8": (np.uint8, (3,))}
 _SURFACE = {k: (ty, () if c == 1 else (c,)) for k, (ty, c) in abi.SURFACE_FIELDS.items()}
 _PATH_SUMS = {"rgb_linear": (np.float32, (3,)), "rgb8": (np.uint8, (3,))}
 _PATH_SEGMENTS = {"seg_" + k: (ty, () if c == 1 else (c,)) for k, (ty, c) in abi.PATH_FIELDS.items()}
+# the rows of srt_fresnel_out as result keys: side_hit_id, side_t, side_rgb_linear, fresnel
+_PATH_SIDE = {("fresnel" if k == "fresnel" else "side_" + k): (ty, () if c == 1 else (c,)) for k, (ty, c) in abi.FRESNEL_FIELDS.items()}
 _POINTER = {np.int32: _i32p, np.float32: _f32p, np.uint8: _u8p, np.uint32: _u32p}
 
 
@@ -722,12 +754,14 @@ def _ray_call(L, stem, suffix, t_range, mask):
     return getattr(L, name), name, mid
 
 
-def _path_call(L, kind, suffix, rule, vis, refr):
-    """Which form of srt_<kind>_paths (kind: shade | render; suffix: "" | _device) its optional structs ask for: a refraction the
-    _refract form, else masks the _masked form, else a rule the _shadow form, else the call itself.  Returns (the C function, its name,
+def _path_call(L, kind, suffix, rule, vis, refr, fres=None):
+    """Which form of srt_<kind>_paths (kind: shade | render; suffix: "" | _device) its optional structs ask for: a Fresnel table the
+    _fresnel form, else a refraction the _refract form, else masks the _masked form, else a rule the _shadow form, else the call itself.  Returns (the C function, its name,
     the arguments it takes between the path desc and the outputs)."""
     ref = lambda v: C.byref(v) if v is not None else None
-    if refr is not None:
+    if fres is not None:
+        form, mid = "_fresnel", (ref(rule), ref(vis), ref(refr), C.byref(fres))
+    elif refr is not None:
         form, mid = "_refract", (ref(rule), ref(vis), C.byref(refr))
     elif vis is not None:
         form, mid = "_masked", (ref(rule), C.byref(vis))
@@ -746,6 +780,17 @@ def _refraction(ior, n_objects):
     table = np.ascontiguousarray(ior, np.float32).reshape(-1)
     assert table.shape[0] == n_objects, "ior: one float per object"
     return abi.Refraction(table.ctypes.data, 0), table
+
+
+def schlick_f0(ior):
+    """The reflectance at normal incidence of a dielectric of index n in air, ((n - 1) / (n + 1))^2 as float32: the f0 of the Fresnel
+    split for a table of float32 indices (an entry that does not transmit, n <= 0 or NaN, gets -1: no split).  The quotient and the
+    square are taken in float64 and rounded once, so that an index of 1.5 gives float32(0.04), not its neighbour."""
+    n = np.asarray(ior, np.float32)
+    with np.errstate(all="ignore"):
+        q = (n.astype(np.float64) - 1.0) / (n.astype(np.float64) + 1.0)
+        f = (q * q).astype(np.float32)
+    return np.where(n > np.float32(0.0), f, np.float32(-1.0)).astype(np.float32)
 
 
 def _ao_flags(smooth, count):

@@ -1,0 +1,279 @@
+"""The yardstick of the Fresnel split (include/srt.h, "Fresnel split": srt_shade_paths_fresnel and srt_render_paths_fresnel).  It adds no
+arithmetic of its own except the weight (schlick) and the mix (mix), the header's formulas in numpy float32 with one array operation
+per step:
+
+  * the path is refract_ref.trace's, as it stands: the split changes no segment;
+  * the weight's inputs are refract_ref.refract_steps' entering, dv and k for the segment's direction and surface_ref.surface's normal;
+  * a side ray is the `bounce` row of surface_ref.surface for that hit, walked by visibility_ref.closest with vis[1] and the interval
+    (bounce_t_min, +inf); a ray without a side ray carries the zero ray and the interval (1, 0), as an ended path does;
+  * a side hit is a shadow_rule_ref.Segment like any other, so its sum is composed from vr.Colours and the shadow rule exactly as a
+    segment's is (shade_paths_of).
+
+tests/test_fresnel_ref.py pins a table under which nothing splits to refract_ref.shade_paths bit for bit, the weight to Schlick's
+polynomial in float64, and checks every case's input conditions."""
+import numpy as np
+
+import ray_query_ref as rq
+import refract_ref as rf
+import render_paths_ref as rpr
+import shade_path_ref as sp
+import shade_range_ref as sr
+import shadow_rule_ref as sh
+import surface_ref as sf
+import visibility_ref as vr
+from simple_raytracer_amd import abi
+
+F32 = np.float32
+INF = np.float32(np.inf)
+ALL = vr.ALL
+SIDE_KEYS = ("side_hit_id", "side_t", "side_rgb_linear", "fresnel")
+ALL_KEYS = sp.ALL_KEYS + SIDE_KEYS
+
+
+def schlick_f0(ior):
+    """lib.schlick_f0, restated: ((n - 1) / (n + 1))^2 in float64, rounded to float32 once; -1 (no split) where the entry does not transmit."""
+    n = np.asarray(ior, np.float32)
+    with np.errstate(all="ignore"):
+        q = (n.astype(np.float64) - 1.0) / (n.astype(np.float64) + 1.0)
+        f = (q * q).astype(np.float32)
+    return np.where(n > F32(0.0), f, F32(-1.0)).astype(np.float32)
+
+
+def schlick_steps(f0, entering, dv, k):
+    """The header's weight, row by row, with every step kept: dict of x, m, m2, m4, m5, g, h, F."""
+    f0, dv, k = (np.ascontiguousarray(a, np.float32).reshape(-1) for a in (f0, dv, k))
+    with np.errstate(all="ignore"):
+        x = np.where(entering, -dv, np.sqrt(k)).astype(np.float32)
+        m = (F32(1.0) - x).astype(np.float32)
+        m2 = (m * m).astype(np.float32)
+        m4 = (m2 * m2).astype(np.float32)
+        m5 = (m4 * m).astype(np.float32)
+        g = (F32(1.0) - f0).astype(np.float32)
+        h = (g * m5).astype(np.float32)
+        F = (f0 + h).astype(np.float32)
+    return dict(x=x, m=m, m2=m2, m4=m4, m5=m5, g=g, h=h, F=F)
+
+
+def schlick(f0, entering, dv, k):
+    return schlick_steps(f0, entering, dv, k)["F"]
+
+
+def splits(ior, f0):
+    """n_objects bool: the object takes a side ray at its hits."""
+    ior, f0 = np.ascontiguousarray(ior, np.float32).reshape(-1), np.ascontiguousarray(f0, np.float32).reshape(-1)
+    with np.errstate(invalid="ignore"):
+        return (ior > F32(0.0)) & (f0 >= F32(0.0))
+
+
+def side_of(oracle, flat, seg, b, depth, ior, f0, smooth):
+    """For the Segment `seg` of segment b: (walked n bool, F n float32 (0 without a side ray), the side rays n x 6 (zero rays elsewhere))."""
+    n = seg.hit.shape[0]
+    s = sf.surface(oracle, flat, seg.rays, seg.hit, seg.t, smooth)
+    obj = s["obj"]
+    at = np.maximum(obj, 0)
+    ior, f0 = np.ascontiguousarray(ior, np.float32).reshape(-1), np.ascontiguousarray(f0, np.float32).reshape(-1)
+    p = rf.refract_steps(seg.rays[:, 3:6], s["normal"], ior[at])
+    with np.errstate(invalid="ignore"):
+        walked = (obj >= 0) & splits(ior, f0)[at] & ~(p["k"] < F32(0.0))
+    if b + 1 >= depth:
+        walked = np.zeros(n, bool)
+    F = np.where(walked, schlick(f0[at], p["entering"], p["dv"], p["k"]), F32(0.0)).astype(np.float32)
+    rays = np.where(walked[:, None], np.ascontiguousarray(s["bounce"]), F32(0.0)).astype(np.float32)
+    return walked, F, rays
+
+
+def trace(oracle, flat, rays, lights, depth, ior, f0, vis=None, obj_mask=None, bounce_t_min=1e-3, t_range=None, flags=0, colours=None, cands=None,
+          walks=None):
+    """refract_ref.trace and, per segment walked, its side rays: (segs, kinds, sides).  sides[b] = (walked, F, a shadow_rule_ref.Segment of
+    the side rays -- `going` is `walked`).  walks: (segs, kinds) already traced with the same arguments."""
+    cands = cands if cands is not None else vr.CandidateMemo(oracle, flat)
+    vis = (ALL, ALL, ALL) if vis is None else vis
+    lights = np.ascontiguousarray(lights, np.float32).reshape(-1, 3)
+    nl = lights.shape[0]
+    smooth = bool(flags & abi.SRT_FLAG_SMOOTH_NORMALS)
+    segs, kinds = walks if walks is not None else rf.trace(oracle, flat, rays, lights, depth, ior, vis, obj_mask, bounce_t_min, t_range, flags, colours, cands)
+    sides = []
+    for b, seg in enumerate(segs):
+        walked, F, cur = side_of(oracle, flat, seg, b, depth, ior, f0, smooth)
+        tr = np.stack([np.where(walked, F32(bounce_t_min), F32(1.0)), np.where(walked, INF, F32(0.0))], axis=1).astype(np.float32)
+        hit, t = vr.closest(cands(cur), flat, vis[1], obj_mask, tr)
+        assert not (hit[~walked] >= 0).any(), "a ray without a side ray hit something"
+        sel = np.flatnonzero(hit >= 0)
+        skip = flat.tri_obj[hit[sel]].astype(np.int64)
+        srays = (np.concatenate([rq.shadow_rays(cur[sel], t[sel], lights[l]) for l in range(nl)]) if nl and sel.size else np.zeros((0, 6), np.float32))
+        cand = vr.visible(cands(srays), flat, vis[2], obj_mask)
+        colour = colours(cur, hit, t) if colours is not None else np.zeros((sel.size, nl, 3), np.float32)
+        obj = np.where(hit >= 0, flat.tri_obj[np.maximum(hit, 0)], -1).astype(np.int32)
+        sides.append((walked, F, sh.Segment(cur, walked, hit, t, obj, sel, colour, srays, cand, skip)))
+    return segs, kinds, sides
+
+
+def mix(seg_hit, seg_obj, seg_lin, side_hit, side_lin, fresnel, reflectance):
+    """The header's mix, from the near end: shade_path_ref.mix with the side ray's share.  acc n x 3 float32.  Segments without a side hit
+    go through the same statements with side false: Wk * (1.0f - 0.0f) is Wk."""
+    depth, n = seg_hit.shape
+    acc = np.zeros((n, 3), np.float32)
+    W = np.ones(n, np.float32)
+    going = np.ones(n, bool)
+    refl = None if reflectance is None else np.asarray(reflectance, np.float32)
+    with np.errstate(all="ignore"):
+        for b in range(depth):
+            going = going & (seg_hit[b] >= 0)
+            nxt = going & (seg_hit[b + 1] >= 0) if b + 1 < depth else np.zeros(n, bool)
+            side = going & (side_hit[b] >= 0)
+            k = np.zeros(n, np.float32)
+            if refl is not None:
+                k[nxt | side] = refl[seg_obj[b][nxt | side]]
+            a = (W * (F32(1.0) - k)).astype(np.float32)
+            term = (a[:, None] * seg_lin[b]).astype(np.float32)
+            acc = np.where(going[:, None], (acc + term).astype(np.float32), acc)
+            Wk = (W * k).astype(np.float32)
+            Fe = np.where(side, np.where(nxt, fresnel[b], F32(1.0)), F32(0.0)).astype(np.float32)
+            g = (Wk * Fe).astype(np.float32)
+            sterm = (g[:, None] * side_lin[b]).astype(np.float32)
+            acc = np.where(side[:, None], (acc + sterm).astype(np.float32), acc)
+            W = np.where(going, (Wk * (F32(1.0) - Fe).astype(np.float32)).astype(np.float32), W)
+    return acc
+
+
+def shade_paths_of(oracle, flat, segs, sides, depth, rule=None, reflectance=None, reinhard=0.5, gamma=1.1, background=abi.REFERENCE_BACKGROUND, **literals):
+    """srt_shade_paths_fresnel of a trace under `rule`: refract_ref's rows, the side rows, the mixed sum and the pixel."""
+    lit = dict(literals, reinhard=reinhard, gamma=gamma, background=background)
+    out = vr.shade_paths_of(oracle, flat, segs, depth, rule, reflectance, **lit)
+    n = segs[0].hit.shape[0]
+    nl = segs[0].colour.shape[1]
+    out = dict(out, side_hit_id=np.full((depth, n), -1, np.int32), side_t=np.full((depth, n), INF, np.float32), side_rgb_linear=np.zeros((depth, n, 3), np.float32),
+               fresnel=np.zeros((depth, n), np.float32))
+    for b, (walked, F, s) in enumerate(sides[:depth]):
+        bits = sh.shadow_bits(flat, s, rule) if s.sel.size else np.zeros((0, nl), bool)
+        lin, _ = sr.compose(oracle, s.hit, s.colour, bits, **lit)
+        out["side_hit_id"][b], out["side_t"][b], out["side_rgb_linear"][b], out["fresnel"][b] = s.hit, s.t, lin, F
+    lin = mix(out["seg_hit_id"], out["seg_obj"], out["seg_rgb_linear"], out["side_hit_id"], out["side_rgb_linear"], out["fresnel"], reflectance)
+    _, q = oracle.tonemap(lin, reinhard, gamma, pow="device")
+    q = q.copy()
+    q[out["seg_hit_id"][0] < 0] = 0
+    q[np.all(q == 0, axis=1)] = np.asarray(background[:3], np.int32)
+    out["rgb_linear"], out["rgb8"] = lin, q.astype(np.uint8)
+    return out
+
+
+def shade_paths(oracle, flat, rays, lights, depth, ior, f0, reflectance=None, bounce_t_min=1e-3, t_range=None, flags=0, rule=None, vis=None, obj_mask=None,
+                colours=None, cands=None, **literals):
+    """srt_shade_paths_fresnel by the yardstick: dict of rgb_linear, rgb8, the seg_* and the side_* arrays (depth x n ...) and fresnel."""
+    lights = np.ascontiguousarray(lights, np.float32).reshape(-1, 3)
+    colours = colours if colours is not None else vr.Colours(oracle, flat, lights, flags, **literals)
+    segs, _, sides = trace(oracle, flat, rays, lights, depth, ior, f0, vis, obj_mask, bounce_t_min, t_range, flags, colours, cands)
+    return shade_paths_of(oracle, flat, segs, sides, depth, rule, reflectance, **literals)
+
+
+def render_paths(oracle, flat, p, depth, ior, f0, reflectance=None, bounce_t_min=1e-3, rule=None, vis=None, obj_mask=None, fill=None):
+    """srt_render_paths_fresnel by the yardstick: refract_ref.render_paths' composition -- the rays of the owned pixels per sub-sample, the
+    mixed sums added in sub-sample order, divided by float32(spp), tone-mapped once; the rows are sub-sample 0's -- on the paths above."""
+    own = rpr.owned(p)
+    sel = np.flatnonzero((own >= 0).reshape(-1))
+    lit = dict(shadow_div=float(p.shadow_div), reinhard=float(p.reinhard), gamma=float(p.gamma), background=tuple(int(c) for c in p.background[:3]))
+    flags = int(p.flags) & abi.SRT_FLAG_SMOOTH_NORMALS
+    spp = int(p.spp)
+    memo = vr.CandidateMemo(oracle, flat)
+    first, total = None, None
+    for k in range(spp):
+        rays, _ = rpr.frame_rays_owned(p, k)
+        o = shade_paths(oracle, flat, rays.reshape(-1, 6)[sel], rpr.lights_of(p), depth, ior, f0, reflectance, bounce_t_min, flags=flags, rule=rule, vis=vis,
+                        obj_mask=obj_mask, cands=memo, **lit)
+        if k == 0:
+            first, total = o, o["rgb_linear"].copy()
+        else:
+            total = (total + o["rgb_linear"]).astype(np.float32)
+    if spp > 1:
+        with np.errstate(all="ignore"):
+            lin = (total / F32(spp)).astype(np.float32)
+        _, q = oracle.tonemap(lin, lit["reinhard"], lit["gamma"], pow="device")
+        q = q.copy()
+        q[np.all(q == 0, axis=1)] = np.asarray(lit["background"], np.int32)
+        first = dict(first, rgb_linear=lin, rgb8=q.astype(np.uint8))
+    out = {}
+    for key in ALL_KEYS:
+        v = first[key]
+        lead = v.shape[:1] if key not in ("rgb_linear", "rgb8") else ()
+        tail = v.shape[len(lead) + 1:]
+        full = np.zeros(lead + (own.size,) + tail, v.dtype) if fill is None else np.full(lead + (own.size,) + tail, fill, v.dtype)
+        full[(slice(None),) * len(lead) + (sel,)] = v
+        out[key] = full.reshape(lead + own.shape + tail)
+    return out
+
+
+def hits_of(ref):
+    """The hits a call's *stats counts: every segment's and every side ray's."""
+    return int((ref["seg_hit_id"] >= 0).sum()) + int((ref["side_hit_id"] >= 0).sum())
+
+
+def assert_same(got, want, what, keys=ALL_KEYS):
+    sf.assert_same(got, want, what, [k for k in keys if k in want])
+
+
+# ---- the cases of tests/test_gpu_fresnel.py ----------------------------------------------------------------------------------------------
+# refract_ref's frame cases (shade_path_ref.FRAMES, refract_ref.case_ior, 3 lights, the cases' reflectances) with f0 = schlick_f0(ior):
+# object 0 mirrors and does not split, every other object is glass of index 1.5 and f0 = 0.04.
+DEPTHS, N_LIGHTS, BOUNCE_T_MIN = rf.DEPTHS, rf.N_LIGHTS, rf.BOUNCE_T_MIN
+
+
+def case_f0(flat):
+    return schlick_f0(rf.case_ior(flat))
+
+
+def branch_counts(segs, sides):
+    """Per segment b with a side walk: rays whose side ray hits while segment b + 1 hits too / misses, whose side ray misses while b + 1
+    hits, where both miss; and the hits of segment b that are totally reflected at a splitting object (no side ray although b + 1 < depth)."""
+    n = segs[0].hit.shape[0]
+    out = []
+    for b, (walked, F, s) in enumerate(sides):
+        nxt = segs[b + 1].hit >= 0 if b + 1 < len(segs) else np.zeros(n, bool)
+        side = s.hit >= 0
+        out.append({"both": int((walked & side & nxt).sum()), "side_only": int((walked & side & ~nxt).sum()), "next_only": int((walked & ~side & nxt).sum()),
+                    "neither": int((walked & ~side & ~nxt).sum())})
+    return out
+
+
+def condition(segs, kinds, sides):
+    """The input conditions of a frame case, on the yardstick."""
+    c = branch_counts(segs, sides)
+    assert any(k["both"] > 0 for k in c), ("no side ray hits while the next segment hits", c)
+    assert any(k["side_only"] > 0 for k in c), ("no side ray hits while the next segment misses", c)
+    assert any(k["next_only"] > 0 for k in c), ("no side ray misses while the next segment hits", c)
+    assert any((k == rf.TIR).any() for k in kinds), "no hit is totally reflected"
+    return c
+
+
+_traces, _refs = {}, {}
+
+
+def case_walks(oracle, name):
+    """The walks of a frame case (no lights, no colours): (segs, kinds, sides), computed once."""
+    key = (name, "walks")
+    if key not in _traces:
+        flat, rays, _, _ = sp.frame_case(name)
+        _traces[key] = trace(oracle, flat, rays, np.zeros((0, 3), np.float32), DEPTHS[name], rf.case_ior(flat), case_f0(flat), bounce_t_min=BOUNCE_T_MIN,
+                             cands=rf.case_memo(oracle, name), walks=rf.case_walks(oracle, name))
+    return _traces[key]
+
+
+def case_trace(oracle, name):
+    """The full trace of a frame case: computed once, shared, never changed."""
+    if name not in _traces:
+        flat, rays, lights, _ = sp.frame_case(name)
+        _traces[name] = trace(oracle, flat, rays, lights, DEPTHS[name], rf.case_ior(flat), case_f0(flat), bounce_t_min=BOUNCE_T_MIN,
+                              colours=rf.case_colours(oracle, name), cands=rf.case_memo(oracle, name), walks=rf.case_trace(oracle, name))
+    return _traces[name]
+
+
+def case_reference(oracle, name, rule=None):
+    """The yardstick's rows of a frame case under `rule`: computed once, shared, never changed."""
+    key = (name, None if rule is None else tuple(str(v) for v in rule))
+    if key not in _refs:
+        flat, _, _, refl = sp.frame_case(name)
+        segs, _, sides = case_trace(oracle, name)
+        ref = shade_paths_of(oracle, flat, segs, sides, DEPTHS[name], rule, refl)
+        for v in ref.values():
+            v.setflags(write=False)
+        _refs[key] = ref
+    return _refs[key]

@@ -35,12 +35,16 @@ from every ray kind, at depth 3 and 1 / 16 light samples.
 run: srt_shade_paths_masked_device under (1e-3, 1, 0) with all-ones masks -- the existing kernel, the yardstick -- beside
 srt_shade_paths_refract_device with an all-zero table (the same walks to the bit: the price of the build alone) and with the bunny as glass of
 index 1.5 (other walks: for information).  Beside every ratio stands the yardstick's own round-to-round spread.
+--fresnel: instead, what the Fresnel split costs the path calls on the rays of the same frame at depth 3 and 1 / 16 light samples, with the
+bunny as glass of index 1.5, in one run: srt_shade_paths_refract_device -- the yardstick -- beside srt_shade_paths_fresnel_device with an
+all-negative f0 (nothing splits, the same bits: the price of the build alone) and with f0 = 0.04 (the price of the side walks), and beside the
+chain of device calls that computes the same pixels.
 --ao: instead, ambient occlusion on the rays of the same frame at 16 and 64 cosine directions, t in (1e-3, 60), in one run: the chain the
 fused calls replace -- srt_surface_rays_device, the torch operations that build the frame and the n x K x 6 rays (a caller's own kernel
 would be one launch; torch takes a dozen elementwise ones), srt_occluded_masked_device with a ray mask of 0 on the rays of a miss, a torch
 reduction: the yardstick -- beside srt_ao_rays_device and srt_ao_hits_device (on a render's hits) under the shipped rule for the deal of rays
 to waves and under either deal alone (the libraries of python -m simple_raytracer_amd.build --ao-deals, loaded beside the shipped one).
-Usage: python tools/ray_query_probe.py [--reps N] [--trace] [--shade | --range | --shade-range | --multi | --surface | --paths | --shadow-rule | --masked | --refract | --ao [--rounds R]]     (--trace: few repetitions, for a run under rocprofv3 --kernel-trace --stats)"""
+Usage: python tools/ray_query_probe.py [--reps N] [--trace] [--shade | --range | --shade-range | --multi | --surface | --paths | --shadow-rule | --masked | --refract | --fresnel | --ao [--rounds R]]     (--trace: few repetitions, for a run under rocprofv3 --kernel-trace --stats)"""
 import argparse, os, sys, time
 import numpy as np
 import torch                                   # first: torch initialises HIP before the library does
@@ -513,6 +517,115 @@ def refract_section(reps, rounds):
     ds.close()
 
 
+def fresnel_section(reps, rounds):
+    """What the Fresnel split costs srt_shade_paths_refract_device on the rays of the 1080p frame at depth 3 with the bunny (object 1) as
+    glass of index 1.5: (a) the _fresnel call with an all-negative f0 -- nothing splits, the same bits: the price of the build alone --,
+    (b) with f0 = schlick_f0(ior): the price of the side walks, beside the chain of device calls that computes the same pixels -- the
+    _refract call with seg, and per segment srt_surface_hits_device for normal and bounce row, torch for who splits, F and the
+    compaction of the side rays, the depth-1 _masked call on them, and the mix in torch."""
+    dev = torch.device("cuda", 0); torch.zeros(1, device=dev)
+    g = gu.GoldenScene("ground_bunny")
+    ds = lib.DeviceScene(g.flat)
+    side = torch.cuda.Stream(device=dev)
+    cur = side.cuda_stream
+    n, D = W * H, 3
+    ALL = 0xFFFFFFFF
+    f32, i32 = torch.float32, torch.int32
+    d_rays = torch.from_numpy(frame_rays()).to(dev)
+    refl_h = np.float32([0.6, 0.25])
+    refl = torch.from_numpy(refl_h).to(dev)
+    ior_h = np.float32([0.0, 1.5])
+    d_ior = torch.from_numpy(ior_h).to(dev)
+    d_neg = torch.full((2,), -1.0, dtype=f32, device=dev)
+    d_f0 = torch.from_numpy(lib.schlick_f0(ior_h)).to(dev)
+    rule, vis = (1e-3, 1.0, False), (ALL, ALL, ALL)
+    print(f"Fresnel split, K3 ground_bunny {W}x{H}: {n} rays, 2 objects, depth {D}; {rounds} rounds of {reps} calls, forms alternating; ms a call; min / max: the spread of the rounds")
+    print(f"{'call':34s} {'form':34s} {'median':>8s} {'min':>8s} {'max':>8s} {'/ first':>7s}")
+    for L in (1, 16):
+        pq = abi.make_params(1, 1, abi.light_staircase(g.light, L))
+        keys = ("refract", "negative", "split", "chain")
+        lin = {k: torch.empty((n, 3), dtype=f32, device=dev) for k in keys}
+        hit = {k: torch.empty((D, n), dtype=i32, device=dev) for k in keys}
+        F_rows = torch.zeros((D, n), dtype=f32, device=dev)
+        s_hit = torch.full((D, n), -1, dtype=i32, device=dev)
+        paths = lambda key, f0: (lambda: ds.shade_paths_device(n, d_rays.data_ptr(), pq, D, reflectance=refl.data_ptr(), bounce_t_min=1e-3, stream=cur,
+                                                               rgb_linear=lin[key].data_ptr(), seg_hit_id=hit[key].data_ptr(), shadow=rule, visibility=vis, ior=d_ior.data_ptr(),
+                                                               fresnel=f0, side_hit_id=s_hit.data_ptr() if key == "split" else 0,
+                                                               side_fresnel=F_rows.data_ptr() if key == "split" else 0))
+        # the chain's buffers
+        seg_t = torch.empty((D, n), dtype=f32, device=dev); seg_obj = torch.empty((D, n), dtype=i32, device=dev)
+        seg_lin = torch.empty((D, n, 3), dtype=f32, device=dev); seg_rays = torch.empty((D, n, 6), dtype=f32, device=dev)
+        nrm = torch.empty((n, 3), dtype=f32, device=dev); bounce = torch.empty((n, 6), dtype=f32, device=dev)
+        c_hit = torch.empty(n, dtype=i32, device=dev); c_lin = torch.empty((n, 3), dtype=f32, device=dev)
+
+        def chain():
+            with torch.cuda.stream(side):
+                ds.shade_paths_device(n, d_rays.data_ptr(), pq, D, reflectance=refl.data_ptr(), bounce_t_min=1e-3, stream=cur, seg_hit_id=hit["chain"].data_ptr(),
+                                      seg_t=seg_t.data_ptr(), seg_obj=seg_obj.data_ptr(), seg_rgb_linear=seg_lin.data_ptr(), seg_rays=seg_rays.data_ptr(), shadow=rule,
+                                      visibility=vis, ior=d_ior.data_ptr())
+                acc, Wt = torch.zeros((n, 3), dtype=f32, device=dev), torch.ones(n, dtype=f32, device=dev)
+                going = torch.ones(n, dtype=torch.bool, device=dev)
+                for b in range(D):
+                    going = going & (hit["chain"][b] >= 0)
+                    nxt = going & (hit["chain"][b + 1] >= 0) if b + 1 < D else torch.zeros_like(going)
+                    obj = seg_obj[b].clamp(min=0).long()
+                    sd = torch.zeros_like(going); Ssum = torch.zeros((n, 3), dtype=f32, device=dev); Fb = torch.zeros(n, dtype=f32, device=dev)
+                    if b + 1 < D:
+                        ds.surface_hits_device(n, seg_rays[b].data_ptr(), hit["chain"][b].data_ptr(), seg_t[b].data_ptr(), stream=cur, normal=nrm.data_ptr(),
+                                               bounce=bounce.data_ptr())
+                        d = seg_rays[b][:, 3:6]
+                        Ln = torch.sqrt((d * d).sum(1)); I = d / Ln[:, None]
+                        c = (nrm * I).sum(1)
+                        ent = c < 0
+                        dv = torch.where(ent, c, -c)
+                        nn = d_ior[obj]
+                        eta = torch.where(ent, 1.0 / nn, nn)
+                        k = 1.0 - (eta * eta) * (1.0 - dv * dv)
+                        walked = going & (nn > 0) & (d_f0[obj] >= 0) & ~(k < 0)
+                        x = torch.where(ent, -dv, torch.sqrt(k)); m = 1.0 - x; m2 = m * m
+                        Fb = torch.where(walked, d_f0[obj] + (1.0 - d_f0[obj]) * ((m2 * m2) * m), Fb)
+                        idx = torch.nonzero(walked).squeeze(1)
+                        ns = int(idx.numel())      # (a host sync: the chain needs the count)
+                        if ns:
+                            srays = bounce.index_select(0, idx).contiguous()
+                            tr = torch.tensor([1e-3, float("inf")], dtype=f32, device=dev).repeat(ns, 1).contiguous()
+                            ds.shade_paths_device(ns, srays.data_ptr(), pq, 1, bounce_t_min=1e-3, t_range=tr.data_ptr(), stream=cur, rgb_linear=0,
+                                                  seg_hit_id=c_hit.data_ptr(), seg_rgb_linear=c_lin.data_ptr(), shadow=rule, visibility=vis)
+                            sd[idx] = c_hit[:ns] >= 0
+                            Ssum[idx] = c_lin[:ns]
+                    kk = torch.where(nxt | sd, refl[obj], torch.zeros(n, dtype=f32, device=dev))
+                    a = Wt * (1.0 - kk)
+                    acc = torch.where(going[:, None], acc + a[:, None] * seg_lin[b], acc)
+                    Wk = Wt * kk
+                    Fe = torch.where(sd, torch.where(nxt, Fb, torch.ones_like(Fb)), torch.zeros_like(Fb))
+                    acc = torch.where(sd[:, None], acc + (Wk * Fe)[:, None] * Ssum, acc)
+                    Wt = torch.where(going, Wk * (1.0 - Fe), Wt)
+                lin["chain"].copy_(acc)
+
+        forms = {"shade_paths_refract (yardstick)": paths("refract", None), "shade_paths_fresnel, f0 all -1": paths("negative", d_neg.data_ptr()),
+                 "shade_paths_fresnel, f0 0.04": paths("split", d_f0.data_ptr()), "chain of device calls": chain}
+        ms = rounds_of(forms, reps, rounds, side)
+        report(f"paths, depth {D}, {L} samples", ms)
+        side.synchronize()
+        assert torch.equal(lin["refract"].view(i32), lin["negative"].view(i32)) and torch.equal(hit["refract"], hit["negative"]), "no split is not the _refract call"
+        assert torch.equal(hit["refract"], hit["split"]), "the split moved a segment"
+        differ = int((lin["chain"].view(i32) != lin["split"].view(i32)).any(dim=1).sum().item())
+        worst = float((lin["chain"] - lin["split"]).abs().max().item())
+        yard = ms["shade_paths_refract (yardstick)"]
+        med = float(np.median(yard))
+        # the lanes of the side walks: F > 0 marks a side ray (f0 = 0.04); waves by the deal the call used
+        walked = (F_rows > 0).cpu().numpy()
+        n_waves = ((n + 255) // 256) * 4
+        pad = np.zeros((D, n_waves * 64), bool); pad[:, :n] = walked
+        per_wave = pad.reshape(D, 8, n_waves, 8).sum(axis=(1, 3)) if L >= 8 else pad.reshape(D, n_waves, 64).sum(axis=2)
+        share = [float(per_wave[b].sum() / (64.0 * max(1, (per_wave[b] > 0).sum()))) for b in range(D - 1)]
+        print(f"{'':34s} f0 all -1 gives the _refract call's bits; the yardstick's own spread: {min(yard) / med:.3f} .. {max(yard) / med:.3f} of its median; "
+              f"side rays walked per segment {[int(walked[b].sum()) for b in range(D)]}, that hit {[int((s_hit[b] >= 0).sum().item()) for b in range(D)]}; "
+              f"waves that walk side rays {[int((per_wave[b] > 0).sum()) for b in range(D - 1)]} of {n_waves}, share of their lanes active {[round(x, 3) for x in share]}; "
+              f"chain against the one launch: {differ} pixels differ in a bit, at most {worst:.3g} (torch rounds the glue on its own)")
+    ds.close()
+
+
 def ao_section(reps, rounds):
     from simple_raytracer_amd import build
     dev = torch.device("cuda", 0); torch.zeros(1, device=dev)
@@ -586,6 +699,7 @@ def ao_section(reps, rounds):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--ao", action="store_true")
+    ap.add_argument("--fresnel", action="store_true")
     ap.add_argument("--refract", action="store_true")
     ap.add_argument("--masked", action="store_true")
     ap.add_argument("--shadow-rule", action="store_true", dest="shadow_rule")
@@ -602,6 +716,8 @@ def main():
     reps = 3 if a.trace else a.reps
     if a.ao:
         return ao_section(reps, 2 if a.trace else a.rounds)
+    if a.fresnel:
+        return fresnel_section(reps, 2 if a.trace else a.rounds)
     if a.refract:
         return refract_section(reps, 2 if a.trace else a.rounds)
     if a.masked:
