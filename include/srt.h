@@ -967,8 +967,8 @@ int srt_render_paths_fresnel(srt_scene* s, const srt_params* p, const srt_path_d
  * hit_rays, shadow_rays = hit_rays x n_dirs (0 where nothing of srt_ao_out is wanted: no AO ray is walked then); under
  * SRT_FLAG_COUNT_WORK the primary counters are srt_trace_rays_masked's (0 in srt_ao_hits) and the shadow counters count the AO walks as they run -- objects in order, hidden and skipped objects not entered, one slab test per
  * node met, triangle tests up to and including the first candidate in range.
- * NOT HERE: a per-ray rotation or jitter of the table; weights per direction (a cosine-distributed table makes the plain count
- * cosine-weighted); bent normals; a frame form without a ray array. */
+ * NOT HERE: weights per direction (a cosine-distributed table makes the plain count cosine-weighted).  (A per-pixel rotation or jitter
+ * of the table, bent normals and a frame form without a ray array: the srt_render_ao calls below, "Ambient occlusion in a frame".) */
 #define SRT_AO_DIRS_MAX  1024
 #define SRT_AO_SKIP_SELF 1u      /* the hit object's own tree is left out of the AO walks (default: it is walked) */
 typedef struct srt_ao_desc {
@@ -992,6 +992,75 @@ int srt_ao_hits_device(srt_scene* s, uint32_t n, const float* d_rays, const int3
                        const srt_ao_desc* ao, const srt_visibility* vis /* or NULL */, void* stream, const srt_ao_out* out);
 int srt_ao_hits(srt_scene* s, uint32_t n, const float* rays, const int32_t* hit_id, const float* t, uint32_t flags,
                 const srt_ao_desc* ao, const srt_visibility* vis, const srt_ao_out* out, srt_stats* stats);
+
+/* Ambient occlusion in a frame: srt_ao_rays for the rays of a frame's own pixels -- the AO pass over a frame in ONE launch without a ray
+ * array (24 B a pixel that srt_ao_rays reads and the caller has to write) -- plus the two things a frame pass needs and a ray batch does
+ * not: a rotation of the direction table chosen by the pixel, which turns the banding of a small table into noise a blur removes, and
+ * the bent normal.  srt_render_ao finds the hits itself; srt_render_ao_hits takes the hit_id / t of a render of the same frame and walks
+ * no primary ray.  They relate to srt_ao_rays / srt_ao_hits as srt_render_paths relates to srt_shade_paths.
+ * Unless said here everything is as for srt_ao_rays: ao, vis, flags, the ordering on `stream`, the rules of srt_scene_share, the private
+ * counter set (srt_sync, srt_scene_pipeline and the renders' counter sets are left alone), ONE launch with nothing allocated and nothing
+ * copied, hipGraph capture of the _device forms without SRT_FLAG_COUNT_WORK.
+ * DEFINITION.  Everything is bit for bit; f32 arithmetic is uncontracted and uses no transcendental.
+ *   Pixels      exactly as in srt_render_paths: the call writes its n = srt_rows_owned x srt_cols_owned LOCAL pixels, row-major; which image
+ *               pixel a local pixel is comes from block_rows / block_first / block_stride / block_cols; the ray of a pixel is
+ *               srt_render_device's, in camera mode (ray_matrix) and without a matrix; padding pixels of a tile deal are written in no
+ *               output.  Of *p the calls read the frame fields and spp; lights, tone-map literals and background are ignored.
+ *   Rotation    with (x, y) the IMAGE pixel of a live pixel -- image coordinates, not local ones, so that a share of a frame agrees with
+ *               the whole frame --: (c, s) = rot[((y % rot_h) * rot_w + x % rot_w) * 2 ..], and for (u, v, w) = dirs[j] the pixel's table
+ *               entry is
+ *                   u' = c * u - s * v      v' = s * u + c * v      w' = w               (each product rounded on its own)
+ *               fr == NULL or fr->rot == NULL applies no arithmetic at all (it is not a multiplication by (1, 0)).  (c, s) is neither
+ *               validated nor normalised.
+ *   The AO      of a pixel: everything of srt_ao_rays for that ray with a NULL t_range, the pixel's table dirs', the same ao->t_min /
+ *               t_max / flags, vis and flags.  hit_id, t, n_occluded, ao and occ_bits are that call's bits.
+ *   bent        from (+0, +0, +0): for j = 0 .. n_dirs - 1 in ascending order, if direction j is NOT blocked, the AO ray's direction as
+ *               walked is added, one f32 add per component.  The sum is not normalised; its order is part of the contract.  A miss row is
+ *               (0, 0, 0).
+ *   ao8         (uint8_t)(int)(ao * 255.0f + 0.5f), the product and the sum each rounded.  A miss gives 255.
+ *   spp = m x m > 1   (srt_render_ao only) the sub-samples run in the one launch with srt_render_device's offsets.  hit_id, t, n_occluded,
+ *               occ_bits and bent report sub-sample 0; ao is the sub-samples' ao values added in order starting from sub-sample 0's, then
+ *               divided by (float)spp -- a miss counts 1.0f --, and ao8 is taken from that quotient.
+ *   srt_render_ao_hits   hit_id and t are laid out as srt_render_device writes them for the same *p.  No primary ray is walked.  Only
+ *               sub-sample 0's ray is used -- that is what a render's hits are -- and ao is that sub-sample's value.  An id outside
+ *               [0, n_tris) is a miss row; t is taken as given.
+ * Identities: with rot NULL and spp 1 the rows equal srt_ao_rays on the frame's rays; srt_render_ao's hit_id / t are srt_render_device's
+ * for the same *p when vis is NULL; the _hits form fed those gives the ray form's bits in every field; a call that owns a share of the
+ * frame writes the whole-frame call's values at its owned pixels; a direction's bit does not depend on the rest of the table.
+ * Flags: SRT_FLAG_COUNT_WORK and SRT_FLAG_SMOOTH_NORMALS as in srt_ao_rays; SRT_FLAG_NO_TIMING and SRT_FLAG_FRAMES_IN_FLIGHT in p->flags are
+ * accepted and ignored, as in srt_render_paths (`flags` itself takes the first two only).
+ * Errors, all before anything is touched: what srt_render_device rejects in the frame fields, with its codes; what srt_ao_rays rejects in ao
+ * and flags; SRT_ERR_ARG for rot non-NULL with rot_w or rot_h 0, for rot NULL with either non-zero, and for a NULL hit_id or t in the _hits
+ * forms; SRT_ERR_LIMIT for rot_w or rot_h above SRT_AO_ROT_MAX and for n x n_dirs x spp >= 2^32.
+ * out == NULL, or every field of it NULL: the _hits forms launch nothing and return SRT_OK; the ray forms still write hit_id / t.
+ * The host forms stage dirs, rot, the given hits and the outputs through the handle's pinned block, then wait.  *stats: primary_rays = owned
+ * image pixels x spp (the _hits forms: owned image pixels), hit_rays = the hits of all sub-samples, shadow_rays = hit_rays x n_dirs; under
+ * SRT_FLAG_COUNT_WORK the four test counters are the sums of what srt_ao_rays reports for those rays.
+ * NOT HERE: weights per direction, as above; a rotation that differs per sub-sample; a blur of the result (a 4 x 4 table wants a 4 x 4 box
+ * filter, which is the caller's). */
+#define SRT_AO_ROT_MAX 64
+typedef struct srt_ao_frame {
+    uint32_t     rot_w, rot_h;   /* 0, 0 with rot NULL: no rotation.  Else 1 .. SRT_AO_ROT_MAX each */
+    const float* rot;            /* rot_h x rot_w x 2 floats (c, s), row-major; a host pointer in the host forms, a DEVICE pointer in the
+                                    _device forms (read when the kernel runs, as ao->dirs is) */
+} srt_ao_frame;
+typedef struct srt_ao_frame_out {   /* device pointers in the _device forms, host pointers in the host forms; any may be NULL, and so may the
+                                       struct; n local pixels, row-major */
+    uint32_t* n_occluded;        /* n        directions that are blocked (sub-sample 0) */
+    float*    ao;                /* n        srt_ao_out's ao; over the sub-samples where spp > 1 */
+    uint32_t* occ_bits;          /* n x W, W = (n_dirs + 31) / 32, as srt_ao_out's (sub-sample 0) */
+    float*    bent;              /* n x 3    the sum of the unblocked directions (sub-sample 0) */
+    uint8_t*  ao8;               /* n        ao as a byte */
+} srt_ao_frame_out;
+int srt_render_ao_device(srt_scene* s, const srt_params* p, uint32_t flags, const srt_ao_desc* ao, const srt_ao_frame* fr /* or NULL */,
+                         const srt_visibility* vis /* or NULL */, void* stream, int32_t* d_hit_id, float* d_t, const srt_ao_frame_out* out);
+int srt_render_ao(srt_scene* s, const srt_params* p, uint32_t flags, const srt_ao_desc* ao, const srt_ao_frame* fr, const srt_visibility* vis,
+                  int32_t* hit_id, float* t, const srt_ao_frame_out* out, srt_stats* stats);
+int srt_render_ao_hits_device(srt_scene* s, const srt_params* p, const int32_t* d_hit_id, const float* d_t, uint32_t flags,
+                              const srt_ao_desc* ao, const srt_ao_frame* fr /* or NULL */, const srt_visibility* vis /* or NULL */,
+                              void* stream, const srt_ao_frame_out* out);
+int srt_render_ao_hits(srt_scene* s, const srt_params* p, const int32_t* hit_id, const float* t, uint32_t flags, const srt_ao_desc* ao,
+                       const srt_ao_frame* fr, const srt_visibility* vis, const srt_ao_frame_out* out, srt_stats* stats);
 
 /* Device-resident size of the scene records and the per-record algorithmic byte sizes used by
  * the bytes model: 32 B per node test, 36 B per triangle test. */

@@ -171,6 +171,23 @@ class AoOut(C.Structure):
 # the fields of srt_ao_out: name -> dtype (n_occluded and ao: one entry a ray; occ_bits: (n_dirs + 31) // 32 words a ray)
 AO_FIELDS = {"n_occluded": np.uint32, "ao": np.float32, "occ_bits": np.uint32}
 
+SRT_AO_ROT_MAX = 64
+
+
+class AoFrame(C.Structure):
+    """srt_ao_frame: the rotation table of an ambient-occlusion frame call as an address (rot_h x rot_w x 2 floats (c, s), row-major; a host
+    array in the host forms, a device pointer in the _device forms); 0, 0 and no address: no rotation."""
+    _fields_ = [("rot_w", C.c_uint32), ("rot_h", C.c_uint32), ("rot", C.c_void_p)]
+
+
+class AoFrameOut(C.Structure):
+    """srt_ao_frame_out: the arrays an ambient-occlusion frame call fills, as addresses; 0 = not wanted."""
+    _fields_ = [("n_occluded", C.c_void_p), ("ao", C.c_void_p), ("occ_bits", C.c_void_p), ("bent", C.c_void_p), ("ao8", C.c_void_p)]
+
+
+# the fields of srt_ao_frame_out: name -> (dtype, entries per pixel; None: (n_dirs + 31) // 32 words)
+AO_FRAME_FIELDS = {"n_occluded": (np.uint32, 1), "ao": (np.float32, 1), "occ_bits": (np.uint32, None), "bent": (np.float32, 3), "ao8": (np.uint8, 1)}
+
 # the fields of srt_path_out: name -> (dtype, floats or ints per ray and segment)
 PATH_FIELDS = {"hit_id": (np.int32, 1), "t": (np.float32, 1), "obj": (np.int32, 1), "rgb_linear": (np.float32, 3), "rays": (np.float32, 6)}
 

@@ -176,6 +176,8 @@ struct srt_scene {
     // srt_ao_rays / srt_ao_hits: the direction table of a host call (capacity counts directions) and the three arrays of srt_ao_out (rq_aobits:
     // capacity counts words, W a ray); a caller's hits go through rq_skip / rq_tin as srt_surface_hits' do
     DevArray<float, 3> rq_aodirs; DevArray<uint32_t> rq_aocnt; DevArray<float> rq_aoval; DevArray<uint32_t> rq_aobits;
+    // srt_render_ao / srt_render_ao_hits: the rotation table of a host call (capacity counts entries) and the two further arrays of srt_ao_frame_out
+    DevArray<float, 2> rq_aorot; DevArray<float, 3> rq_aobent; DevArray<uint8_t> rq_ao8;
     DevArray<float, 3> d_qlights; Pinned<float, 3> h_qlights; uint32_t qlights_valid = 0;
     Event qlights_sent; hipStream_t qlights_stream = nullptr; bool qlights_settled = true;
     int n_cu = 256;
@@ -2026,6 +2028,43 @@ static int ao_device_impl(srt_scene* s, uint32_t n, const float* d_rays, const f
                         p, hits ? *hits : QueryHits{}, d_hit_id, d_t, wanted ? *out : srt_ao_out{}, q.ctr);
 }
 
+// srt_render_ao / srt_render_ao_hits: srt_ao_rays' hemisphere visibility for the pixels of a frame, one launch (k_render_ao).  A
+// query-family call, as srt_render_paths is: the query counter set; the renders' counter sets, workspaces, event ring and pipeline string
+// are left alone.  hits: the hits a caller of srt_render_ao_hits brings, laid out as srt_render_device writes them (NULL: srt_render_ao).
+static int check_render_ao(const srt_scene* s, const srt_params* p, const QueryHits* hits, uint32_t flags, const srt_ao_desc* ao, const srt_ao_frame* fr) {
+    if (!s || !p) return SRT_ERR_ARG;
+    if (p->flags & ~(uint32_t)(SRT_FLAG_COUNT_WORK | SRT_FLAG_SMOOTH_NORMALS | SRT_FLAG_NO_TIMING | SRT_FLAG_FRAMES_IN_FLIGHT)) return SRT_ERR_ARG;      // (variant bits included)
+    SRT_TRY(check_frame(scene_facts(s), p));
+    SRT_TRY(check_surface(s, 0, nullptr, flags, SRT_FLAG_COUNT_WORK | SRT_FLAG_SMOOTH_NORMALS));
+    if (hits && (!hits->hit_id || !hits->t)) return SRT_ERR_ARG;
+    if (!ao || !ao->dirs || ao->n_dirs == 0 || (ao->flags & ~(uint32_t)SRT_AO_SKIP_SELF)) return SRT_ERR_ARG;
+    if (fr && (fr->rot ? (!fr->rot_w || !fr->rot_h) : (fr->rot_w || fr->rot_h))) return SRT_ERR_ARG;
+    if (ao->n_dirs > SRT_AO_DIRS_MAX || (fr && (fr->rot_w > SRT_AO_ROT_MAX || fr->rot_h > SRT_AO_ROT_MAX))) return SRT_ERR_LIMIT;
+    if ((uint64_t)srt_rows_owned(p) * srt_cols_owned(p) * ao->n_dirs * p->spp >= (1ull << 32)) return SRT_ERR_LIMIT;      // (< 2^31 x 2^10 x 2^12: no overflow)
+    return SRT_OK;
+}
+static inline bool ao_frame_wanted(const srt_ao_frame_out* o) { return o && (o->n_occluded || o->ao || o->occ_bits || o->bent || o->ao8); }
+
+static int render_ao_device_impl(srt_scene* s, const srt_params* p, const QueryHits* hits, uint32_t flags, const srt_ao_desc* ao, const srt_ao_frame* fr,
+                                 const srt_visibility* vis, hipStream_t stream, int32_t* d_hit_id, float* d_t, const srt_ao_frame_out* out, bool count_hits) {
+    SRT_TRY(check_render_ao(s, p, hits, flags, ao, fr));
+    const uint32_t rows = srt_rows_owned(p), wl = srt_cols_owned(p);
+    const bool wanted = ao_frame_wanted(out);
+    // nothing of srt_ao_frame_out wanted: the _hits form has nothing to do; the ray form writes hit_id / t and walks no AO ray
+    if (!rows || !wl || (!wanted && !count_hits && (hits || (!d_hit_id && !d_t)))) return SRT_OK;
+    const bool count = (flags & SRT_FLAG_COUNT_WORK) != 0, smooth = (flags & SRT_FLAG_SMOOTH_NORMALS) != 0, rotated = fr && fr->rot;
+    QueryLaunch q;
+    SRT_TRY(query_prologue(s, 0, stream, nullptr, count || count_hits, &q));
+    const DevParams dp = dev_params(s, p, FramePlan{}).hit;      // the frame's geometry only
+    const uint32_t m = (uint32_t)std::lround(std::sqrt((double)p->spp));      // (m x m == spp: check_frame)
+    const QueryAo qa = { ao->dirs, wanted ? ao->n_dirs : 0u, ao->t_min, ao->t_max, (ao->flags & SRT_AO_SKIP_SELF) ? 1u : 0u, 0u };      // (spread: the deal is the tiles')
+    const QueryAoRot rot = rotated ? QueryAoRot{ fr->rot, fr->rot_w, fr->rot_h } : QueryAoRot{ nullptr, 1u, 1u };
+    static const std::array builds = { BUILDS_4(k_render_ao) };
+    return launch_query(builds[build_index(count, smooth, hits, rotated)], dim3((wl + 15) / 16, (rows + 15) / 16), q.stream, s->dev, dp, p->spp, m,
+                        vis ? query_mask(s, vis) : query_mask(s, (const uint32_t*)nullptr), qa, rot, hits ? *hits : QueryHits{}, d_hit_id, d_t,
+                        wanted ? *out : srt_ao_frame_out{}, q.ctr);
+}
+
 // The host entry points: what the caller brings goes through the pinned staging block (stage_acquire, as every update does) into the
 // handle's own buffers on the scene's stream, the device entry point runs behind it, the call waits and copies the results out.
 // One array of a host call that comes from host memory: `bytes` from src to dst on the device.  src NULL, or no bytes: absent, and it
@@ -2280,19 +2319,31 @@ static int surface_hits_impl(srt_scene* s, uint32_t n, const float* rays, const 
     }, i_rays, i_hit, i_t);
 }
 
-// What the host forms of the two AO calls share: the direction table the call brings, the three arrays of the caller's srt_ao_out, and the
-// round trip of them, in which launch(stream, ao, out) gets the caller's structs with the handle's buffers in the place of the host arrays.
+// What the host forms of the four AO calls share: the direction table the call brings, the rotation table of a frame call, the arrays of
+// the caller's srt_ao_out or srt_ao_frame_out (whose first three fields are srt_ao_out's), and the round trip of them, in which
+// launch(stream, ao, frame, out) gets the caller's structs with the handle's buffers in the place of the host arrays.
 struct AoArrays {
     QueryArray<float, 3> dirs; QueryArray<uint32_t, 1> cnt; QueryArray<float, 1> val; QueryArray<uint32_t, 1> bits;
+    QueryArray<float, 2> rot; QueryArray<float, 3> bent; QueryArray<uint8_t, 1> ao8;
+    uint32_t rot_w, rot_h;
     template <typename Launch, typename... More>      // more: the call's other arrays
     int round_trip(srt_scene* s, const srt_ao_desc* ao, Launch launch, const More&... more) const {
         return query_round_trip(s, [&](hipStream_t st) -> int {
             const srt_ao_desc dao = { ao->n_dirs, dirs.on_device(), ao->t_min, ao->t_max, ao->flags };
-            const srt_ao_out dev = { cnt.on_device(), val.on_device(), bits.on_device() };
-            return launch(st, &dao, &dev);
-        }, more..., dirs, cnt, val, bits);
+            const srt_ao_frame dfr = { rot_w, rot_h, rot.on_device() };
+            const srt_ao_frame_out dev = { cnt.on_device(), val.on_device(), bits.on_device(), bent.on_device(), ao8.on_device() };
+            return launch(st, &dao, &dfr, &dev);
+        }, more..., dirs, rot, cnt, val, bits, bent, ao8);
     }
 };
+// n rays or local pixels; fr: the rotation table of a frame call, or NULL
+static AoArrays ao_arrays(srt_scene* s, size_t n, const srt_ao_desc* ao, const srt_ao_frame* fr, const srt_ao_frame_out& h) {
+    const size_t words = n * ((ao->n_dirs + 31u) / 32u);
+    const bool rotated = fr && fr->rot;
+    return AoArrays{ query_in(ao->dirs, s->rq_aodirs, ao->n_dirs), query_out(h.n_occluded, s->rq_aocnt, n), query_out(h.ao, s->rq_aoval, n),
+                     query_out(h.occ_bits, s->rq_aobits, words), query_in(rotated ? fr->rot : nullptr, s->rq_aorot, rotated ? (size_t)fr->rot_w * fr->rot_h : 0),
+                     query_out(h.bent, s->rq_aobent, n), query_out(h.ao8, s->rq_ao8, n), rotated ? fr->rot_w : 0u, rotated ? fr->rot_h : 0u };
+}
 
 // hits: the hits a caller of srt_ao_hits brings (their ids go through rq_skip, their t through rq_tin), or NULL: srt_ao_rays
 static int ao_impl(srt_scene* s, uint32_t n, const float* rays, const float* t_range, const QueryHits* hits, uint32_t flags, const srt_ao_desc* ao,
@@ -2301,18 +2352,46 @@ static int ao_impl(srt_scene* s, uint32_t n, const float* rays, const float* t_r
     if (stats) std::memset(stats, 0, sizeof(*stats));
     if (!n || (hits && !stats && !ao_wanted(out))) return SRT_OK;
     const srt_ao_out h = out ? *out : srt_ao_out{};
-    const size_t words = (size_t)n * ((ao->n_dirs + 31u) / 32u);
-    const AoArrays a = { query_in(ao->dirs, s->rq_aodirs, ao->n_dirs), query_out(h.n_occluded, s->rq_aocnt, n), query_out(h.ao, s->rq_aoval, n),
-                         query_out(h.occ_bits, s->rq_aobits, words) };
+    const AoArrays a = ao_arrays(s, n, ao, nullptr, srt_ao_frame_out{ h.n_occluded, h.ao, h.occ_bits, nullptr, nullptr });
     const auto o_hit = query_out(hit_id, s->rq_hit, n); const auto o_t = query_out(t, s->rq_t, n);
     const auto i_rays = query_in(rays, s->rq_rays, n); const auto i_range = query_in(t_range, s->rq_range, n);
     const auto i_hit = query_in(hits ? hits->hit_id : nullptr, s->rq_skip, n); const auto i_t = query_in(hits ? hits->t : nullptr, s->rq_tin, n);
-    SRT_TRY(a.round_trip(s, ao, [&](hipStream_t st, const srt_ao_desc* dao, const srt_ao_out* dev) {
+    SRT_TRY(a.round_trip(s, ao, [&](hipStream_t st, const srt_ao_desc* dao, const srt_ao_frame*, const srt_ao_frame_out* dev) {
         const QueryHits dh = { i_hit.on_device(), i_t.on_device() };
-        return ao_device_impl(s, n, i_rays.on_device(), i_range.on_device(), hits ? &dh : nullptr, flags, dao, vis, st, o_hit.on_device(), o_t.on_device(), dev,
+        const srt_ao_out dout = { dev->n_occluded, dev->ao, dev->occ_bits };
+        return ao_device_impl(s, n, i_rays.on_device(), i_range.on_device(), hits ? &dh : nullptr, flags, dao, vis, st, o_hit.on_device(), o_t.on_device(), &dout,
                               stats != nullptr);
     }, o_hit, o_t, i_rays, i_range, i_hit, i_t));
     return stats ? query_stats(s, n, ao_wanted(out) ? ao->n_dirs : 0u, stats) : SRT_OK;      // (nothing wanted: no AO ray was walked)
+}
+
+// srt_render_ao / srt_render_ao_hits: as ao_impl, with n the call's local pixels and no rays to stage; the hits a caller of
+// srt_render_ao_hits brings go through rq_skip / rq_tin; primary_rays counts image pixels x the sub-samples walked
+static int render_ao_impl(srt_scene* s, const srt_params* p, const QueryHits* hits, uint32_t flags, const srt_ao_desc* ao, const srt_ao_frame* fr,
+                          const srt_visibility* vis, int32_t* hit_id, float* t, const srt_ao_frame_out* out, srt_stats* stats) {
+    SRT_TRY(check_render_ao(s, p, hits, flags, ao, fr));
+    if (stats) std::memset(stats, 0, sizeof(*stats));
+    const uint32_t n = srt_rows_owned(p) * srt_cols_owned(p);      // (< 2^32: check_render_ao)
+    const bool wanted = ao_frame_wanted(out);
+    if (!n || (!stats && !wanted && (hits || (!hit_id && !t)))) return SRT_OK;
+    const AoArrays a = ao_arrays(s, n, ao, fr, out ? *out : srt_ao_frame_out{});
+    const auto o_hit = query_out(hit_id, s->rq_hit, n); const auto o_t = query_out(t, s->rq_t, n);
+    const auto i_hit = query_in(hits ? hits->hit_id : nullptr, s->rq_skip, n); const auto i_t = query_in(hits ? hits->t : nullptr, s->rq_tin, n);
+    const bool padded = p->block_cols != 0;      // padding pixels are not written: what the handle's buffers hold there must not reach the caller
+    SRT_TRY(a.round_trip(s, ao, [&](hipStream_t st, const srt_ao_desc* dao, const srt_ao_frame* dfr, const srt_ao_frame_out* dev) -> int {
+        if (padded) {      // the caller's arrays first, so that the copy out returns their padding as it was (render_paths_impl has the reasoning)
+            hipError_t e = hipSuccess;
+            const auto up = [&](const auto& arr) { if (arr.out && e == hipSuccess) e = hipMemcpy(arr.dev.p, arr.out, arr.count * arr.unit, hipMemcpyHostToDevice); };
+            up(o_hit); up(o_t); up(a.cnt); up(a.val); up(a.bits); up(a.bent); up(a.ao8);
+            HIP_TRY(e);
+        }
+        const QueryHits dh = { i_hit.on_device(), i_t.on_device() };
+        return render_ao_device_impl(s, p, hits ? &dh : nullptr, flags, dao, fr ? dfr : nullptr, vis, st, o_hit.on_device(), o_t.on_device(), dev, stats != nullptr);
+    }, o_hit, o_t, i_hit, i_t));
+    if (!stats) return SRT_OK;
+    SRT_TRY(query_stats(s, n, wanted ? ao->n_dirs : 0u, stats));      // (nothing wanted: no AO ray was walked)
+    stats->primary_rays = pixels_owned(p) * (hits ? 1u : p->spp);
+    return SRT_OK;
 }
 }      // extern "C++"
 
@@ -2500,6 +2579,24 @@ int srt_ao_hits(srt_scene* s, uint32_t n, const float* rays, const int32_t* hit_
                 const srt_ao_out* out, srt_stats* stats) {
     const QueryHits hits = { hit_id, t };
     return guarded([&] { return ao_impl(s, n, rays, nullptr, &hits, flags, ao, vis, nullptr, nullptr, out, stats); });
+}
+int srt_render_ao_device(srt_scene* s, const srt_params* p, uint32_t flags, const srt_ao_desc* ao, const srt_ao_frame* fr, const srt_visibility* vis, void* stream,
+                         int32_t* d_hit_id, float* d_t, const srt_ao_frame_out* out) {
+    return guarded([&] { return render_ao_device_impl(s, p, nullptr, flags, ao, fr, vis, (hipStream_t)stream, d_hit_id, d_t, out, false); });
+}
+int srt_render_ao(srt_scene* s, const srt_params* p, uint32_t flags, const srt_ao_desc* ao, const srt_ao_frame* fr, const srt_visibility* vis, int32_t* hit_id, float* t,
+                  const srt_ao_frame_out* out, srt_stats* stats) {
+    return guarded([&] { return render_ao_impl(s, p, nullptr, flags, ao, fr, vis, hit_id, t, out, stats); });
+}
+int srt_render_ao_hits_device(srt_scene* s, const srt_params* p, const int32_t* d_hit_id, const float* d_t, uint32_t flags, const srt_ao_desc* ao, const srt_ao_frame* fr,
+                              const srt_visibility* vis, void* stream, const srt_ao_frame_out* out) {
+    const QueryHits hits = { d_hit_id, d_t };
+    return guarded([&] { return render_ao_device_impl(s, p, &hits, flags, ao, fr, vis, (hipStream_t)stream, nullptr, nullptr, out, false); });
+}
+int srt_render_ao_hits(srt_scene* s, const srt_params* p, const int32_t* hit_id, const float* t, uint32_t flags, const srt_ao_desc* ao, const srt_ao_frame* fr,
+                       const srt_visibility* vis, const srt_ao_frame_out* out, srt_stats* stats) {
+    const QueryHits hits = { hit_id, t };
+    return guarded([&] { return render_ao_impl(s, p, &hits, flags, ao, fr, vis, nullptr, nullptr, out, stats); });
 }
 
 void* srt_host_alloc(size_t bytes) {

@@ -782,18 +782,43 @@ __device__ __forceinline__ void ao_frame(const V3 n, V3& T, V3& B) {
     T = mk(1.0f + ((s * n.x) * n.x) * a, s * b, (-s) * n.x);
     B = mk(b, s + (n.y * n.y) * a, -n.y);
 }
+// The normal that faces the ray d, and the AO ray's direction for the table entry (u, v, z) in the frame of that normal
+__device__ __forceinline__ V3 ao_facing(const V3 d, const V3 N) {
+    const float k = (d.x * N.x + d.y * N.y) + d.z * N.z;       // mirror_dir's dot
+    return k > 0.0f ? neg(N) : N;
+}
+__device__ __forceinline__ V3 ao_ray_dir(const V3 Nf, const float u, const float v, const float z) {
+    V3 T, B;
+    ao_frame(Nf, T, B);
+    return mk((T.x * u + B.x * v) + Nf.x * z, (T.y * u + B.y * v) + Nf.y * z, (T.z * u + B.z * v) + Nf.z * z);
+}
+
+// The rotation of a table entry about the frame's third axis (include/srt.h, "Ambient occlusion in a frame"): (u, v) -> (c * u - s * v,
+// s * u + c * v), each product rounded on its own.
+__device__ __forceinline__ void ao_rotate(const float c, const float sn, float& u, float& v) {
+    const float u0 = u, v0 = v;
+    u = c * u0 - sn * v0;
+    v = sn * u0 + c * v0;
+}
+// What ao_hits_dirs calls after each chunk when the caller wants nothing of it
+struct AoNoChunk { __device__ __forceinline__ void operator()(uint32_t, uint32_t, unsigned long long) const {} };
 
 // Phase 2 for the 64 rays of one wave after shade_hits_rank, as shade_hits_lights is for light samples.  wray[5..7][rank] is written here.
 // Returns the lane's blocked directions; every live lane stores its row of occ_bits chunk by chunk.
-template <bool COUNT>
+// ROT (k_render_ao): every hit turns the table by its own (c, sn) before the frame is applied; the hit's lane leaves the pair in
+// wrot[0..1][rank], two more rows of the wave's LDS, where the lanes that take its items read it.  The builds without ROT never touch wrot.
+// chunk(l0, m, mask): called by every lane after each chunk with the chunk's first direction, its length and the lane's own mask (0 for a
+// lane without a hit) -- k_render_ao's bent sum.
+template <bool COUNT, bool ROT = false, typename Chunk = AoNoChunk>
 __device__ __forceinline__ uint32_t ao_hits_dirs(const DevScene& s, const QueryAo& p, const QueryMask& qm, const uint32_t lane, const bool live, const bool is_hit,
                                                  const WaveHits wh, const V3 d, const V3 N, const size_t ri, uint32_t* __restrict__ occ_bits, float (*wray)[64],
-                                                 unsigned long long* best, unsigned long long& n_node_s, unsigned long long& n_tri_s) {
+                                                 unsigned long long* best, unsigned long long& n_node_s, unsigned long long& n_tri_s,
+                                                 float (*wrot)[64] = nullptr, const float c = 0.0f, const float sn = 0.0f, const Chunk chunk = Chunk{}) {
     const uint32_t nh = wh.nh, rank = wh.rank, W = (p.n_dirs + 31u) >> 5;
     if (is_hit) {
-        const float k = (d.x * N.x + d.y * N.y) + d.z * N.z;       // mirror_dir's dot
-        const V3 Nf = k > 0.0f ? neg(N) : N;
+        const V3 Nf = ao_facing(d, N);
         wray[5][rank] = Nf.x; wray[6][rank] = Nf.y; wray[7][rank] = Nf.z;
+        if constexpr (ROT) { wrot[0][rank] = c; wrot[1][rank] = sn; }
     }
     uint32_t blocked = 0;
     for (uint32_t l0 = 0; l0 < p.n_dirs; l0 += 64u) {                                               // wave-uniform
@@ -806,16 +831,17 @@ __device__ __forceinline__ uint32_t ao_hits_dirs(const DevScene& s, const QueryA
             const V3 P = mk(wray[0][r], wray[1][r], wray[2][r]);
             const int2 self = make_int2(__float_as_int(wray[3][r]), __float_as_int(wray[4][r]));
             const V3 Nf = mk(wray[5][r], wray[6][r], wray[7][r]);
-            V3 T, B;
-            ao_frame(Nf, T, B);
             const float* dp = p.dirs + (size_t)(l0 + k) * 3;
-            const float u = dp[0], v = dp[1], z = dp[2];
-            const V3 wd = mk((T.x * u + B.x * v) + Nf.x * z, (T.y * u + B.y * v) + Nf.y * z, (T.z * u + B.z * v) + Nf.z * z);
+            float u = dp[0], v = dp[1];
+            const float z = dp[2];
+            if constexpr (ROT) ao_rotate(wrot[0][r], wrot[1][r], u, v);
+            const V3 wd = ao_ray_dir(Nf, u, v, z);
             if (any_hit_range<COUNT, true, true, true>(s, self, P, wd, n_node_s, n_tri_s, p.t_min, p.t_max, qm.obj, qm.shadow)) atomicOr(&best[r], 1ull << k);
         }
         __builtin_amdgcn_wave_barrier();
         const unsigned long long mask = is_hit ? best[rank] : 0ull;
         blocked += (uint32_t)__popcll(mask);
+        chunk(l0, m, mask);
         if (occ_bits && live) {
             const uint32_t w0 = l0 >> 5;                                                            // the chunk's two words: w0 (< W) and w0 + 1
             occ_bits[ri * W + w0] = (uint32_t)mask;
@@ -1234,4 +1260,128 @@ __global__ __launch_bounds__(256) void k_render_path_fresnel(DevScene s, DevPara
                                                              unsigned long long* __restrict__ counters, ShadowRule rule, QueryMask qm, const float* __restrict__ ior,
                                                              QueryFresnel fr) {
     render_path_pixels<COUNT, SMOOTH, INT_SHIN, true, true, true, true>(s, fp, spp, spp_m, p, path, rgb_linear, rgb8, seg, counters, rule, qm, ior, fr);
+}
+
+// =================================================================================================
+// Ambient occlusion in a frame (srt_render_ao, srt_render_ao_hits): k_query_ao's hemisphere visibility for the rays of a frame's own
+// pixels, with a rotation of the table chosen by the pixel and the bent normal.  The front end is k_render_path's: a wave owns one 8 x 8
+// tile (tile_pixel), the grid is 2-D over the call's local output, a pixel's ray is primary_dir / ray_origin under the call's block or
+// tile deal, its row in every output is its local pixel r * W + px; padding pixels and pixels beyond the frame are lanes without a ray,
+// which walk nothing and write nothing; the sub-sample loop is wave-uniform.  The back end is k_query_ao's as it stands: query_walk as
+// k_query_closest_masked instantiates it with qm.primary (HITS: the caller's hit_id / t, laid out as srt_render_device writes them; no
+// queue, one sub-sample), shade_hits_rank, ao_hits_dirs.
+// ROT: the pixel's (c, s) is rot[((y % h) * w + x % w) * 2 ..] of its IMAGE pixel, loaded once by the pixel's own lane before the
+// sub-sample loop.  The lanes that take a hit's (rank, direction) items find it in two more LDS rows a wave (ao_hits_dirs' wrot): 2 KB a
+// workgroup on top of k_query_ao's 10 KB + the queue, two LDS reads an item.  The other way -- one row that names the hit's lane, the
+// pixel recovered from it, two integer remainders and an 8-byte gather from the table per item -- saves 1 KB and costs registers for
+// the tile's origin and the table's shape inside the item loop, the loop whose any_hit_range walk sets the kernel's register count -- and
+// the ROT build of the ray form stands at 127 / 128 VGPRs, the last count at which a SIMD holds four waves (the kernel asks the compiler
+// for that occupancy, amdgpu_waves_per_eu: left alone it took 129 / 130 and a SIMD held three, profiles/render_ao_kernels.txt; the COUNT
+// builds, 131 .. 138, and the HITS builds, 80 .. 90, are left to it).  The LDS is not what bounds the waves here: 22.5 KB a
+// workgroup of four waves is seven workgroups a CU.  Without ROT no arithmetic is applied to the table and the kernel has no such rows.
+// bent: the hit's own lane adds, after each chunk and from the chunk's mask, the directions that are not blocked in ascending j --
+// ao_ray_dir on the table entry it turns itself, the statements the item's lane ran, so the sum is of the directions as walked.  The
+// loop runs only where bent is wanted and costs the lane up to 64 steps a chunk beside the chunk's walks.
+// Stores: bent through store_rows_dealt (a tile row's 8 pixels are one 96 B run); occ_bits as ao_hits_dirs stores it, chunk by chunk;
+// n_occluded, ao and ao8 by lane.  hit_id, t, n_occluded, occ_bits and bent are sub-sample 0's; ao is the sub-samples' sum in order
+// over (float)spp.
+// counters: as k_query_ao's, over all sub-samples; the hit shard is the 2-D workgroup number.
+// =================================================================================================
+struct QueryAoRot { const float* rot; uint32_t w, h; };      // device, h x w x 2 (c, s); read by the ROT builds only
+
+template <bool COUNT, bool SMOOTH, bool HITS, bool ROT>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COUNT || HITS ? 1 : 4)))
+void k_render_ao(DevScene s, DevParams fp, uint32_t spp, uint32_t spp_m, QueryMask qm, QueryAo p, QueryAoRot rt, QueryHits given, int32_t* __restrict__ hit_id,
+                 float* __restrict__ t_out, srt_ao_frame_out out, unsigned long long* __restrict__ counters) {
+    __shared__ unsigned long long best_all[256];
+    __shared__ float ray_all[4][8][64];
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    unsigned long long* best = best_all + wave * 64;
+    float (*wray)[64] = ray_all[wave];
+    float (*wrot)[64] = nullptr;
+    if constexpr (ROT) {
+        __shared__ float rot_all[4][2][64];
+        wrot = rot_all[wave];
+    }
+    uint32_t* queue = nullptr;
+    if constexpr (!HITS) {
+        __shared__ uint32_t q_all[4][QCAP];             // the walk's queue: the HITS builds have none
+        queue = q_all[wave];
+    }
+    uint32_t px, r;
+    const bool live = tile_pixel(fp, px, r);
+    const unsigned long long live_mask = __ballot(live);
+    const uint32_t tile_x = blockIdx.x * 16 + (wave & 1) * 8, tile_r = blockIdx.y * 16 + (wave >> 1) * 8, W = fp.W;
+    const auto ray_of = [=](const uint32_t l) -> size_t { return (live_mask >> l) & 1ull ? (size_t)(tile_r + (l >> 3)) * W + tile_x + (l & 7u) : ~(size_t)0; };
+    const size_t n = (size_t)fp.rows * W, ri = (size_t)r * W + px;
+    const uint32_t shard = blockIdx.y * gridDim.x + blockIdx.x, y = live ? image_row(fp, r) : 0u;
+    float c = 1.0f, sn = 0.0f;
+    if constexpr (ROT) {
+        if (live) {
+            const float* e = rt.rot + ((size_t)(y % rt.h) * rt.w + image_col(fp, px, y) % rt.w) * 2;
+            c = e[0]; sn = e[1];
+        }
+    }
+    unsigned long long n_node = 0, n_tri = 0, n_node_s = 0, n_tri_s = 0;
+    const V3 o = ray_origin(fp);
+    const uint32_t n_sub = HITS ? 1u : spp;             // a render's hits are sub-sample 0's
+    float total = 0.0f;
+    for (uint32_t k = 0; k < n_sub; k++) {                                                          // wave-uniform
+        if (spp > 1) {
+            fp.sub_x = ((float)(k % spp_m) + 0.5f) / (float)spp_m - 0.5f;
+            fp.sub_y = ((float)(k / spp_m) + 0.5f) / (float)spp_m - 0.5f;
+        }
+        const V3 d = live ? primary_dir(fp, px, y) : mk(0.0f, 0.0f, 1.0f);
+        bool is_hit;
+        int32_t id = -1;
+        float t = __builtin_inff();
+        if constexpr (HITS) {
+            if (live) { id = given.hit_id[ri]; t = given.t[ri]; }
+            is_hit = id >= 0 && (uint32_t)id < s.n_tris;
+        } else {
+            query_walk<COUNT, true, MergeClosest, true>(s, live, o, d, lane, queue, MergeClosest{ best }, wray, n_node, n_tri, __builtin_nanf(""), __builtin_nanf(""),
+                                                        qm.obj, qm.primary);
+            const unsigned long long key = live ? best[lane] : ~0ull;
+            is_hit = key != ~0ull;
+            id = is_hit ? (int32_t)(uint32_t)key : -1;
+        }
+        Surface f;
+        const WaveHits wh = shade_hits_rank<SMOOTH, true, HITS>(s, is_hit, id, o, d, t, f, wray, p.skip_self ? 0u : 1u);
+        if (!HITS && live && k == 0) {
+            if (hit_id) hit_id[ri] = id;
+            if (t_out) t_out[ri] = t;
+        }
+        if (p.n_dirs) {                                 // wave-uniform
+            const bool want_bent = out.bent && k == 0;  // wave-uniform
+            const V3 Nf = ao_facing(d, f.nrm);
+            V3 bent = mk(0.0f, 0.0f, 0.0f);
+            const auto bent_chunk = [&](const uint32_t l0, const uint32_t m, const unsigned long long mask) {
+                if (!want_bent || !is_hit) return;
+                for (uint32_t j = 0; j < m; j++) {
+                    if ((mask >> j) & 1ull) continue;
+                    const float* dp = p.dirs + (size_t)(l0 + j) * 3;
+                    float u = dp[0], v = dp[1];
+                    const float z = dp[2];
+                    if constexpr (ROT) ao_rotate(c, sn, u, v);
+                    const V3 wd = ao_ray_dir(Nf, u, v, z);
+                    bent = mk(bent.x + wd.x, bent.y + wd.y, bent.z + wd.z);
+                }
+            };
+            const uint32_t blocked = ao_hits_dirs<COUNT, ROT>(s, p, qm, lane, live, is_hit, wh, d, f.nrm, ri, k == 0 ? out.occ_bits : nullptr, wray, best, n_node_s, n_tri_s,
+                                                              wrot, c, sn, bent_chunk);
+            const float a = (float)(p.n_dirs - blocked) / (float)p.n_dirs;
+            if (k == 0) {
+                total = a;
+                if (out.n_occluded && live) out.n_occluded[ri] = blocked;
+                if (want_bent) { const float v[3] = { bent.x, bent.y, bent.z }; store_rows_dealt<3>(out.bent, lane, n, v, &wray[0][0], ray_of); }
+            } else total = total + a;
+        }
+        if (counters) count_hits(counters, is_hit, shard);
+    }
+    if (p.n_dirs && live) {
+        if (n_sub > 1) total = total / (float)spp;
+        if (out.ao) out.ao[ri] = total;
+        if (out.ao8) out.ao8[ri] = (uint8_t)(int)(total * 255.0f + 0.5f);
+    }
+    if (COUNT) { wave_add(counters + 1, n_node); wave_add(counters + 2, n_tri); wave_add(counters + 3, n_node_s); wave_add(counters + 4, n_tri_s); }
 }

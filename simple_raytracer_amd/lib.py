@@ -31,7 +31,8 @@ ABI_SYMBOLS = ("srt_params_default", "srt_light_staircase", "srt_rows_owned", "s
                "srt_occluded_masked", "srt_shade_paths_masked_device", "srt_shade_paths_masked", "srt_render_paths_masked_device", "srt_render_paths_masked",
                "srt_shade_paths_refract_device", "srt_shade_paths_refract", "srt_render_paths_refract_device", "srt_render_paths_refract",
                "srt_shade_paths_fresnel_device", "srt_shade_paths_fresnel", "srt_render_paths_fresnel_device", "srt_render_paths_fresnel",
-               "srt_ao_rays_device", "srt_ao_rays", "srt_ao_hits_device", "srt_ao_hits")
+               "srt_ao_rays_device", "srt_ao_rays", "srt_ao_hits_device", "srt_ao_hits",
+               "srt_render_ao_device", "srt_render_ao", "srt_render_ao_hits_device", "srt_render_ao_hits")
 MULTI_HIT_MAX = 16                # SRT_MULTI_HIT_MAX
 
 _f32p, _i32p, _u8p, _u32p = C.POINTER(C.c_float), C.POINTER(C.c_int32), C.POINTER(C.c_uint8), C.POINTER(C.c_uint32)
@@ -192,6 +193,14 @@ def load(path=None):
         L.srt_ao_hits_device.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, _ao, _vis, C.c_void_p, _aout]
         L.srt_ao_hits.argtypes = [C.c_void_p, C.c_uint32, _f32p, _i32p, _f32p, C.c_uint32, _ao, _vis, _aout, C.POINTER(abi.Stats)]
         for f in (L.srt_ao_rays_device, L.srt_ao_rays, L.srt_ao_hits_device, L.srt_ao_hits):
+            f.restype = C.c_int
+        # ambient occlusion in a frame: the params first, an srt_ao_frame* after the srt_ao_desc*, an srt_ao_frame_out* last of the outputs
+        _par, _afr, _afout = C.POINTER(abi.Params), C.POINTER(abi.AoFrame), C.POINTER(abi.AoFrameOut)
+        L.srt_render_ao_device.argtypes = [C.c_void_p, _par, C.c_uint32, _ao, _afr, _vis, C.c_void_p, C.c_void_p, C.c_void_p, _afout]
+        L.srt_render_ao.argtypes = [C.c_void_p, _par, C.c_uint32, _ao, _afr, _vis, _i32p, _f32p, _afout, C.POINTER(abi.Stats)]
+        L.srt_render_ao_hits_device.argtypes = [C.c_void_p, _par, C.c_void_p, C.c_void_p, C.c_uint32, _ao, _afr, _vis, C.c_void_p, _afout]
+        L.srt_render_ao_hits.argtypes = [C.c_void_p, _par, _i32p, _f32p, C.c_uint32, _ao, _afr, _vis, _afout, C.POINTER(abi.Stats)]
+        for f in (L.srt_render_ao_device, L.srt_render_ao, L.srt_render_ao_hits_device, L.srt_render_ao_hits):
             f.restype = C.c_int
         L.srt_strerror.argtypes = [C.c_int]
         L.srt_strerror.restype = C.c_char_p
@@ -548,6 +557,64 @@ class DeviceScene:
         _check(self.L.srt_ao_hits_device(self.h, n, C.c_void_p(rays), C.c_void_p(hit_id), C.c_void_p(t), _ao_flags(smooth, count), C.byref(desc), _vis_ref(visibility),
                                          C.c_void_p(stream), C.byref(aout)), "srt_ao_hits_device")
 
+    def render_ao(self, params: abi.Params, dirs, rot=None, t_min=1e-3, t_max=np.inf, skip_self=False, visibility=None, smooth=False, count=False,
+                  want=("hit_id", "t", "n_occluded", "ao", "occ_bits", "bent", "ao8"), fill=None):
+        """srt_render_ao: ao_rays for the rays of the frame's own pixels -- the local pixels of a call with `params` (its block or tile deal,
+        camera matrix and spp included); no ray array is built.  rot: None, or an h x w x 2 table of (cos, sin) (ao_rotations) -- the pixel
+        at image (x, y) turns `dirs` about z by entry (y % h, x % w) before its frame is applied.  Returns a dict of the arrays named in
+        `want` -- hit_id, t, n_occluded, ao, ao8 [rows, cols], occ_bits [rows, cols, W], bent [rows, cols, 3]: the sum of the directions that
+        are not blocked, as walked -- + 'stats'.  With spp > 1 ao is the mean over the sub-samples, the other arrays are sub-sample 0's.
+        fill: a value every array holds before the call (padding pixels of a tile deal keep it).  The rest as in ao_rays."""
+        lead = (self.rows(params), self.cols(params))
+        desc, table = _ao_desc(dirs, t_min, t_max, skip_self)
+        frame, turns = _ao_frame(rot)
+        out, g = _outputs(want, lead, _HIT, fill)
+        fout, arrays = _ao_frame_out(want, lead, desc.n_dirs, fill)
+        out.update(arrays)
+        st = abi.Stats()
+        _check(self.L.srt_render_ao(self.h, C.byref(params), _ao_flags(smooth, count), C.byref(desc), C.byref(frame), _vis_ref(visibility), g("hit_id"), g("t"),
+                                    C.byref(fout), C.byref(st)), "srt_render_ao")
+        out["stats"] = st.as_dict()
+        return out
+
+    def render_ao_hits(self, params: abi.Params, hit_id, t, dirs, rot=None, t_min=1e-3, t_max=np.inf, skip_self=False, visibility=None, smooth=False, count=False,
+                       want=("n_occluded", "ao", "occ_bits", "bent", "ao8"), fill=None):
+        """srt_render_ao_hits: render_ao for hits the caller already holds -- `hit_id` and `t` [rows, cols] as render(params) returns them
+        (host arrays).  No closest-hit walk; only sub-sample 0's ray is used; an id outside [0, n_tris) is a miss row (n_occluded 0, ao 1,
+        bent 0, ao8 255).  Returns a dict of the arrays named in `want` + 'stats'."""
+        lead = (self.rows(params), self.cols(params))
+        hid = np.ascontiguousarray(hit_id, np.int32).reshape(-1); tt = np.ascontiguousarray(t, np.float32).reshape(-1)
+        assert hid.shape[0] == lead[0] * lead[1] and tt.shape[0] == hid.shape[0], "hit_id, t: one entry per local pixel"
+        desc, table = _ao_desc(dirs, t_min, t_max, skip_self)
+        frame, turns = _ao_frame(rot)
+        fout, out = _ao_frame_out(want, lead, desc.n_dirs, fill)
+        st = abi.Stats()
+        _check(self.L.srt_render_ao_hits(self.h, C.byref(params), _host(hid, _i32p), _host(tt, _f32p), _ao_flags(smooth, count), C.byref(desc), C.byref(frame),
+                                         _vis_ref(visibility), C.byref(fout), C.byref(st)), "srt_render_ao_hits")
+        out["stats"] = st.as_dict()
+        return out
+
+    def render_ao_device(self, params: abi.Params, dirs, n_dirs, rot=0, rot_w=0, rot_h=0, t_min=1e-3, t_max=np.inf, skip_self=False, visibility=None, smooth=False,
+                         count=False, stream=0, hit_id=0, t=0, n_occluded=0, ao=0, occ_bits=0, bent=0, ao8=0):
+        """srt_render_ao_device: raw device pointers (ints, e.g. torch.Tensor.data_ptr()) in -- the table `dirs` of n_dirs x 3 floats, the
+        rotation table `rot` of rot_h x rot_w x 2 floats (0: none) and the outputs of the call's local pixels (0: not wanted) --,
+        asynchronous on `stream`, one launch."""
+        desc = abi.AoDesc(n_dirs, dirs or None, t_min, t_max, abi.SRT_AO_SKIP_SELF if skip_self else 0)
+        frame = abi.AoFrame(rot_w, rot_h, rot or None)
+        fout = abi.AoFrameOut(n_occluded or None, ao or None, occ_bits or None, bent or None, ao8 or None)
+        _check(self.L.srt_render_ao_device(self.h, C.byref(params), _ao_flags(smooth, count), C.byref(desc), C.byref(frame), _vis_ref(visibility), C.c_void_p(stream),
+                                           C.c_void_p(hit_id), C.c_void_p(t), C.byref(fout)), "srt_render_ao_device")
+
+    def render_ao_hits_device(self, params: abi.Params, hit_id, t, dirs, n_dirs, rot=0, rot_w=0, rot_h=0, t_min=1e-3, t_max=np.inf, skip_self=False, visibility=None,
+                              smooth=False, count=False, stream=0, n_occluded=0, ao=0, occ_bits=0, bent=0, ao8=0):
+        """srt_render_ao_hits_device: raw device pointers (ints) in -- a render's hit_id / t of the same `params`, the tables --, asynchronous
+        on `stream`, one launch."""
+        desc = abi.AoDesc(n_dirs, dirs or None, t_min, t_max, abi.SRT_AO_SKIP_SELF if skip_self else 0)
+        frame = abi.AoFrame(rot_w, rot_h, rot or None)
+        fout = abi.AoFrameOut(n_occluded or None, ao or None, occ_bits or None, bent or None, ao8 or None)
+        _check(self.L.srt_render_ao_hits_device(self.h, C.byref(params), C.c_void_p(hit_id), C.c_void_p(t), _ao_flags(smooth, count), C.byref(desc), C.byref(frame),
+                                                _vis_ref(visibility), C.c_void_p(stream), C.byref(fout)), "srt_render_ao_hits_device")
+
     def _paths_host(self, kind, head, lead, params, depth, reflectance, bounce_t_min, want, count, smooth, fill, shadow, visibility, ior, fresnel=None):
         """The host form of a path call: srt_<kind>_paths and its _shadow, _masked, _refract and _fresnel forms.  head: the arguments
         before the params; lead: the shape of one segment's rows."""
@@ -814,6 +881,32 @@ def _ao_out(want, n, n_dirs):
     shape = {"n_occluded": (n,), "ao": (n,), "occ_bits": (n, (n_dirs + 31) // 32)}
     out = {k: np.empty(shape[k], ty) for k, ty in abi.AO_FIELDS.items() if k in want}
     return abi.AoOut(*_addresses(out, abi.AO_FIELDS)), out
+
+
+def _ao_frame(rot):
+    """(an abi.AoFrame over a host table of h x w x 2 floats, the array that keeps it alive); rot None: no rotation."""
+    if rot is None:
+        return abi.AoFrame(0, 0, None), None
+    table = np.ascontiguousarray(rot, np.float32)
+    assert table.ndim == 3 and table.shape[2] == 2, "rot: h x w x 2 (cos, sin)"
+    return abi.AoFrame(table.shape[1], table.shape[0], table.ctypes.data), table
+
+
+def _ao_frame_out(want, lead, n_dirs, fill=None):
+    """(an abi.AoFrameOut over host arrays for the fields of srt_ao_frame_out that `want` names, name -> array [rows, cols(, k)])."""
+    new = np.empty if fill is None else (lambda shape, ty: np.full(shape, fill, ty))
+    tail = lambda c: () if c == 1 else ((n_dirs + 31) // 32,) if c is None else (c,)
+    out = {k: new(lead + tail(c), ty) for k, (ty, c) in abi.AO_FRAME_FIELDS.items() if k in want}
+    return abi.AoFrameOut(*_addresses(out, abi.AO_FRAME_FIELDS)), out
+
+
+def ao_rotations(w, h):
+    """A deterministic h x w x 2 table of rotations (cos, sin) for render_ao / render_ao_hits (float32), computed in float64 and rounded
+    once: entry k = iy * w + ix has the angle 2 pi frac((k + 0.5) * 0.6180339887498949) -- the golden-ratio sequence, so that neighbouring
+    pixels of a small tile get well-separated turns of the direction table."""
+    k = np.arange(int(w) * int(h), dtype=np.float64)
+    a = 2.0 * np.pi * np.modf((k + 0.5) * 0.6180339887498949)[0]
+    return np.stack([np.cos(a), np.sin(a)], axis=1).astype(np.float32).reshape(int(h), int(w), 2)
 
 
 def ao_directions(n, cosine=True):

@@ -44,7 +44,11 @@ fused calls replace -- srt_surface_rays_device, the torch operations that build 
 would be one launch; torch takes a dozen elementwise ones), srt_occluded_masked_device with a ray mask of 0 on the rays of a miss, a torch
 reduction: the yardstick -- beside srt_ao_rays_device and srt_ao_hits_device (on a render's hits) under the shipped rule for the deal of rays
 to waves and under either deal alone (the libraries of python -m simple_raytracer_amd.build --ao-deals, loaded beside the shipped one).
-Usage: python tools/ray_query_probe.py [--reps N] [--trace] [--shade | --range | --shade-range | --multi | --surface | --paths | --shadow-rule | --masked | --refract | --fresnel | --ao [--rounds R]]     (--trace: few repetitions, for a run under rocprofv3 --kernel-trace --stats)"""
+--render-ao: instead, ambient occlusion over the same frame's own pixels at 16 and 64 cosine directions, t in (1e-3, 60), in one run: the
+shipped calls on rays torch makes per call (24 B a pixel, four elementwise launches) -- srt_ao_rays_device and, on a render's hits,
+srt_ao_hits_device: the yardsticks -- beside srt_render_ao_device and srt_render_ao_hits_device without a table, with a 4 x 4 table of
+rotations, and with that table and the bent normal.
+Usage: python tools/ray_query_probe.py [--reps N] [--trace] [--shade | --range | --shade-range | --multi | --surface | --paths | --shadow-rule | --masked | --refract | --fresnel | --ao | --render-ao [--rounds R]]     (--trace: few repetitions, for a run under rocprofv3 --kernel-trace --stats)"""
 import argparse, os, sys, time
 import numpy as np
 import torch                                   # first: torch initialises HIP before the library does
@@ -696,8 +700,80 @@ def ao_section(reps, rounds):
         h.close()
 
 
+def render_ao_section(reps, rounds):
+    dev = torch.device("cuda", 0); torch.zeros(1, device=dev)
+    g = gu.GoldenScene("ground_bunny")
+    ds = lib.DeviceScene(g.flat)
+    side = torch.cuda.Stream(device=dev)
+    cur = side.cuda_stream
+    p = g.params(W, H, 1)
+    n = W * H
+    t_min, t_max = 1e-3, 60.0
+    frame = ds.render(p, want=("hit_id", "t"))
+    h0, t0 = torch.from_numpy(frame["hit_id"].reshape(-1).copy()).to(dev), torch.from_numpy(frame["t"].reshape(-1).copy()).to(dev)
+    i0, j0 = int(-np.float32(W) / 2), int(-np.float32(H) / 2)
+    xs = torch.arange(i0, i0 + W, dtype=torch.float32, device=dev); ys = torch.arange(j0, j0 + H, dtype=torch.float32, device=dev)
+    d_rays = torch.zeros((H, W, 6), dtype=torch.float32, device=dev)
+    hit = torch.empty(n, dtype=torch.int32, device=dev); t = torch.empty(n, dtype=torch.float32, device=dev)
+    rot = lib.ao_rotations(4, 4)
+    d_rot = torch.from_numpy(rot).to(dev)
+    turned = dict(rot=d_rot.data_ptr(), rot_w=4, rot_h=4)
+    names = ("shipped", "frame", "turned", "bent")
+    cnt = {k: torch.empty(n, dtype=torch.int32, device=dev) for k in names}
+    ao = {k: torch.empty(n, dtype=torch.float32, device=dev) for k in names}
+    bent = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    print(f"ambient occlusion in a frame, K3 ground_bunny {W}x{H}: {n} pixels, {int((h0 >= 0).sum().item())} hits, t in ({t_min}, {t_max}); {rounds} rounds of {reps} calls, "
+          f"forms alternating; ms a call; min / max: the spread of the rounds")
+    print(f"{'directions':34s} {'form':34s} {'median':>8s} {'min':>8s} {'max':>8s} {'/ first':>7s}")
+
+    def make_rays():      # what a caller of the ray forms does per frame: 24 B a pixel, written here by four elementwise launches
+        with torch.cuda.stream(side):
+            d_rays[..., 0:3] = 0.0
+            d_rays[..., 3] = xs[None, :]
+            d_rays[..., 4] = ys[:, None]
+            d_rays[..., 5] = FOCAL
+
+    for K in (16, 64):
+        d_dirs = torch.from_numpy(lib.ao_directions(K)).to(dev)
+        torch.cuda.synchronize()
+        outs = lambda k: dict(n_occluded=cnt[k].data_ptr(), ao=ao[k].data_ptr())
+
+        def shipped_rays():
+            make_rays()
+            ds.ao_rays_device(n, d_rays.data_ptr(), d_dirs.data_ptr(), K, t_min, t_max, stream=cur, hit_id=hit.data_ptr(), t=t.data_ptr(), **outs("shipped"))
+
+        def shipped_hits():
+            make_rays()
+            ds.ao_hits_device(n, d_rays.data_ptr(), h0.data_ptr(), t0.data_ptr(), d_dirs.data_ptr(), K, t_min, t_max, stream=cur, **outs("shipped"))
+
+        ray_form = lambda k, **kw: (lambda: ds.render_ao_device(p, d_dirs.data_ptr(), K, t_min=t_min, t_max=t_max, stream=cur, hit_id=hit.data_ptr(), t=t.data_ptr(),
+                                                                **outs(k), **kw))
+        hits_form = lambda k, **kw: (lambda: ds.render_ao_hits_device(p, h0.data_ptr(), t0.data_ptr(), d_dirs.data_ptr(), K, t_min=t_min, t_max=t_max, stream=cur,
+                                                                      **outs(k), **kw))
+        for title, first, form in ((f"{K} directions, the hit found", shipped_rays, ray_form), (f"{K} directions, a render's hits", shipped_hits, hits_form)):
+            kind = "ao_rays" if form is ray_form else "ao_hits"
+            own = "render_ao_device" if form is ray_form else "render_ao_hits_device"
+            forms = {f"torch rays + {kind}_device (yardstick)": first, own: form("frame"), f"{own}, 4x4 rot": form("turned", **turned),
+                     f"{own}, 4x4 rot, bent": form("bent", **turned, bent=bent.data_ptr())}
+            report(title, rounds_of(forms, reps, rounds, side))
+            # the frame form without a table answers as the shipped call; the table changes rows; bent changes nothing else
+            for k in names:
+                cnt[k].fill_(-1)
+            for fn in forms.values():
+                fn()
+            side.synchronize()
+            assert torch.equal(cnt["frame"], cnt["shipped"]) and torch.equal(ao["frame"].view(torch.int32), ao["shipped"].view(torch.int32)), title
+            assert torch.equal(cnt["bent"], cnt["turned"]) and not torch.equal(cnt["turned"], cnt["frame"]), title
+            if form is ray_form:
+                assert torch.equal(hit, h0) and torch.equal(t.view(torch.int32), t0.view(torch.int32)), title
+        print(f"{'':34s} blocked {int(cnt['frame'].sum().item())} of {int((h0 >= 0).sum().item()) * K} AO rays without the table, {int(cnt['turned'].sum().item())} with it; "
+              f"the frame forms without a table give the shipped calls' bits")
+    ds.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--render-ao", action="store_true", dest="render_ao")
     ap.add_argument("--ao", action="store_true")
     ap.add_argument("--fresnel", action="store_true")
     ap.add_argument("--refract", action="store_true")
@@ -714,6 +790,8 @@ def main():
     ap.add_argument("--rounds", type=int, default=7)
     a = ap.parse_args()
     reps = 3 if a.trace else a.reps
+    if a.render_ao:
+        return render_ao_section(reps, 2 if a.trace else a.rounds)
     if a.ao:
         return ao_section(reps, 2 if a.trace else a.rounds)
     if a.fresnel:
