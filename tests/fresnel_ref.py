@@ -13,7 +13,7 @@ tests/test_fresnel_ref.py pins a table under which nothing splits to refract_ref
 polynomial in float64, and checks every case's input conditions."""
 import numpy as np
 
-import ray_query_ref as rq
+import path_walk_ref as pw
 import refract_ref as rf
 import render_paths_ref as rpr
 import shade_path_ref as sp
@@ -89,22 +89,16 @@ def trace(oracle, flat, rays, lights, depth, ior, f0, vis=None, obj_mask=None, b
     cands = cands if cands is not None else vr.CandidateMemo(oracle, flat)
     vis = (ALL, ALL, ALL) if vis is None else vis
     lights = np.ascontiguousarray(lights, np.float32).reshape(-1, 3)
-    nl = lights.shape[0]
     smooth = bool(flags & abi.SRT_FLAG_SMOOTH_NORMALS)
     segs, kinds = walks if walks is not None else rf.trace(oracle, flat, rays, lights, depth, ior, vis, obj_mask, bounce_t_min, t_range, flags, colours, cands)
     sides = []
     for b, seg in enumerate(segs):
         walked, F, cur = side_of(oracle, flat, seg, b, depth, ior, f0, smooth)
-        tr = np.stack([np.where(walked, F32(bounce_t_min), F32(1.0)), np.where(walked, INF, F32(0.0))], axis=1).astype(np.float32)
+        tr = pw.bounce_interval(walked, bounce_t_min)
         hit, t = vr.closest(cands(cur), flat, vis[1], obj_mask, tr)
         assert not (hit[~walked] >= 0).any(), "a ray without a side ray hit something"
-        sel = np.flatnonzero(hit >= 0)
-        skip = flat.tri_obj[hit[sel]].astype(np.int64)
-        srays = (np.concatenate([rq.shadow_rays(cur[sel], t[sel], lights[l]) for l in range(nl)]) if nl and sel.size else np.zeros((0, 6), np.float32))
-        cand = vr.visible(cands(srays), flat, vis[2], obj_mask)
-        colour = colours(cur, hit, t) if colours is not None else np.zeros((sel.size, nl, 3), np.float32)
         obj = np.where(hit >= 0, flat.tri_obj[np.maximum(hit, 0)], -1).astype(np.int32)
-        sides.append((walked, F, sh.Segment(cur, walked, hit, t, obj, sel, colour, srays, cand, skip)))
+        sides.append((walked, F, pw.segment_of(flat, cur, walked, hit, t, obj, lights, lambda srays: vr.visible(cands(srays), flat, vis[2], obj_mask), colours)))
     return segs, kinds, sides
 
 
@@ -149,11 +143,7 @@ def shade_paths_of(oracle, flat, segs, sides, depth, rule=None, reflectance=None
         lin, _ = sr.compose(oracle, s.hit, s.colour, bits, **lit)
         out["side_hit_id"][b], out["side_t"][b], out["side_rgb_linear"][b], out["fresnel"][b] = s.hit, s.t, lin, F
     lin = mix(out["seg_hit_id"], out["seg_obj"], out["seg_rgb_linear"], out["side_hit_id"], out["side_rgb_linear"], out["fresnel"], reflectance)
-    _, q = oracle.tonemap(lin, reinhard, gamma, pow="device")
-    q = q.copy()
-    q[out["seg_hit_id"][0] < 0] = 0
-    q[np.all(q == 0, axis=1)] = np.asarray(background[:3], np.int32)
-    out["rgb_linear"], out["rgb8"] = lin, q.astype(np.uint8)
+    out["rgb_linear"], out["rgb8"] = sp.finish(oracle, out, reflectance, lin=lin, **lit)
     return out
 
 
@@ -167,39 +157,12 @@ def shade_paths(oracle, flat, rays, lights, depth, ior, f0, reflectance=None, bo
 
 
 def render_paths(oracle, flat, p, depth, ior, f0, reflectance=None, bounce_t_min=1e-3, rule=None, vis=None, obj_mask=None, fill=None):
-    """srt_render_paths_fresnel by the yardstick: refract_ref.render_paths' composition -- the rays of the owned pixels per sub-sample, the
-    mixed sums added in sub-sample order, divided by float32(spp), tone-mapped once; the rows are sub-sample 0's -- on the paths above."""
-    own = rpr.owned(p)
-    sel = np.flatnonzero((own >= 0).reshape(-1))
-    lit = dict(shadow_div=float(p.shadow_div), reinhard=float(p.reinhard), gamma=float(p.gamma), background=tuple(int(c) for c in p.background[:3]))
-    flags = int(p.flags) & abi.SRT_FLAG_SMOOTH_NORMALS
-    spp = int(p.spp)
+    """srt_render_paths_fresnel by the yardstick: render_paths_ref.compose_frame on the paths above, the candidate sets shared among the
+    sub-samples; the side rows and the weights carry a leading depth axis as the segments' do."""
     memo = vr.CandidateMemo(oracle, flat)
-    first, total = None, None
-    for k in range(spp):
-        rays, _ = rpr.frame_rays_owned(p, k)
-        o = shade_paths(oracle, flat, rays.reshape(-1, 6)[sel], rpr.lights_of(p), depth, ior, f0, reflectance, bounce_t_min, flags=flags, rule=rule, vis=vis,
-                        obj_mask=obj_mask, cands=memo, **lit)
-        if k == 0:
-            first, total = o, o["rgb_linear"].copy()
-        else:
-            total = (total + o["rgb_linear"]).astype(np.float32)
-    if spp > 1:
-        with np.errstate(all="ignore"):
-            lin = (total / F32(spp)).astype(np.float32)
-        _, q = oracle.tonemap(lin, lit["reinhard"], lit["gamma"], pow="device")
-        q = q.copy()
-        q[np.all(q == 0, axis=1)] = np.asarray(lit["background"], np.int32)
-        first = dict(first, rgb_linear=lin, rgb8=q.astype(np.uint8))
-    out = {}
-    for key in ALL_KEYS:
-        v = first[key]
-        lead = v.shape[:1] if key not in ("rgb_linear", "rgb8") else ()
-        tail = v.shape[len(lead) + 1:]
-        full = np.zeros(lead + (own.size,) + tail, v.dtype) if fill is None else np.full(lead + (own.size,) + tail, fill, v.dtype)
-        full[(slice(None),) * len(lead) + (sel,)] = v
-        out[key] = full.reshape(lead + own.shape + tail)
-    return out
+    shade = lambda rays, lights, flags, **lit: shade_paths(oracle, flat, rays, lights, depth, ior, f0, reflectance, bounce_t_min, flags=flags, rule=rule, vis=vis,
+                                                           obj_mask=obj_mask, cands=memo, **lit)
+    return rpr.compose_frame(oracle, p, shade, ALL_KEYS, lambda key: key not in ("rgb_linear", "rgb8"), fill)
 
 
 def hits_of(ref):
@@ -244,36 +207,31 @@ def condition(segs, kinds, sides):
     return c
 
 
-_traces, _refs = {}, {}
+_cases = pw.CaseCache()
 
 
 def case_walks(oracle, name):
     """The walks of a frame case (no lights, no colours): (segs, kinds, sides), computed once."""
-    key = (name, "walks")
-    if key not in _traces:
+    def make():
         flat, rays, _, _ = sp.frame_case(name)
-        _traces[key] = trace(oracle, flat, rays, np.zeros((0, 3), np.float32), DEPTHS[name], rf.case_ior(flat), case_f0(flat), bounce_t_min=BOUNCE_T_MIN,
-                             cands=rf.case_memo(oracle, name), walks=rf.case_walks(oracle, name))
-    return _traces[key]
+        return trace(oracle, flat, rays, np.zeros((0, 3), np.float32), DEPTHS[name], rf.case_ior(flat), case_f0(flat), bounce_t_min=BOUNCE_T_MIN,
+                     cands=rf.case_memo(oracle, name), walks=rf.case_walks(oracle, name))
+    return _cases.once(("walks", name), make)
 
 
 def case_trace(oracle, name):
     """The full trace of a frame case: computed once, shared, never changed."""
-    if name not in _traces:
+    def make():
         flat, rays, lights, _ = sp.frame_case(name)
-        _traces[name] = trace(oracle, flat, rays, lights, DEPTHS[name], rf.case_ior(flat), case_f0(flat), bounce_t_min=BOUNCE_T_MIN,
-                              colours=rf.case_colours(oracle, name), cands=rf.case_memo(oracle, name), walks=rf.case_trace(oracle, name))
-    return _traces[name]
+        return trace(oracle, flat, rays, lights, DEPTHS[name], rf.case_ior(flat), case_f0(flat), bounce_t_min=BOUNCE_T_MIN, colours=rf.case_colours(oracle, name),
+                     cands=rf.case_memo(oracle, name), walks=rf.case_trace(oracle, name))
+    return _cases.once(("trace", name), make)
 
 
 def case_reference(oracle, name, rule=None):
     """The yardstick's rows of a frame case under `rule`: computed once, shared, never changed."""
-    key = (name, None if rule is None else tuple(str(v) for v in rule))
-    if key not in _refs:
+    def make():
         flat, _, _, refl = sp.frame_case(name)
         segs, _, sides = case_trace(oracle, name)
-        ref = shade_paths_of(oracle, flat, segs, sides, DEPTHS[name], rule, refl)
-        for v in ref.values():
-            v.setflags(write=False)
-        _refs[key] = ref
-    return _refs[key]
+        return shade_paths_of(oracle, flat, segs, sides, DEPTHS[name], rule, refl)
+    return _cases.once(("ref", name, pw.rule_key(rule)), make)

@@ -2,7 +2,7 @@
 arithmetic of its own except refract_dir, the header's formula in numpy float32 with one array operation per step:
 
   * a segment is what it is in every path yardstick: the winners, the shadow rays' candidate sets and surface_ref.surface (obj, the
-    normal, the bounce row), collected by visibility_ref.trace's loop -- restated here because the next ray differs -- into
+    normal, the bounce row), collected by visibility_ref.trace's loop (visibility_ref.masked_walk, with another next ray) into
     shadow_rule_ref.Segment rows, so that masks (visibility_ref.visible / closest) and the shadow rule (shadow_rule_ref.shadow_bits) come
     in exactly as those files already compose them; without masks every ray kind sees every object;
   * segment b + 1's ray is segment b's bounce row, or -- where ior[obj] > 0 -- the same origin with refract_dir(d, normal, ior[obj]);
@@ -13,16 +13,13 @@ tests/test_refract_ref.py pins a table without a positive entry to shade_path_re
 law in float64."""
 import numpy as np
 
-import ray_query_ref as rq
+import path_walk_ref as pw
 import render_paths_ref as rpr
 import shade_path_ref as sp
-import shadow_rule_ref as sh
 import surface_ref as sf
 import visibility_ref as vr
-from simple_raytracer_amd import abi
 
 F32 = np.float32
-INF = np.float32(np.inf)
 ALL = vr.ALL
 MISS, MIRROR, ENTER, LEAVE, TIR = -1, 0, 1, 2, 3          # what a path does at the end of a segment (kinds())
 
@@ -119,31 +116,13 @@ def trace(oracle, flat, rays, lights, depth, ior, vis=None, obj_mask=None, bounc
     colours None: the colours stay zero (the walks alone, for a case's input conditions); lights may then be empty."""
     cands = cands if cands is not None else vr.CandidateMemo(oracle, flat)
     vis = (ALL, ALL, ALL) if vis is None else vis
-    rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
-    lights = np.ascontiguousarray(lights, np.float32).reshape(-1, 3)
-    n, nl = rays.shape[0], lights.shape[0]
-    smooth = bool(flags & abi.SRT_FLAG_SMOOTH_NORMALS)
-    cur = rays
-    tr = None if t_range is None else np.ascontiguousarray(t_range, np.float32).reshape(-1, 2)
-    going = np.ones(n, bool)
-    segs, kinds = [], []
-    for b in range(depth):
-        if not going.any():
-            break
-        hit, t = vr.closest(cands(cur), flat, vis[0] if b == 0 else vis[1], obj_mask, tr)
-        assert not (hit[~going] >= 0).any(), "an ended path hit something"
-        sel = np.flatnonzero(hit >= 0)
-        skip = flat.tri_obj[hit[sel]].astype(np.int64)
-        srays = (np.concatenate([rq.shadow_rays(cur[sel], t[sel], lights[l]) for l in range(nl)]) if nl and sel.size else np.zeros((0, 6), np.float32))
-        cand = vr.visible(cands(srays), flat, vis[2], obj_mask)
-        s = sf.surface(oracle, flat, cur, hit, t, smooth)
-        colour = colours(cur, hit, t) if colours is not None else np.zeros((sel.size, nl, 3), np.float32)
-        segs.append(sh.Segment(np.where(going[:, None], cur, F32(0.0)), going, hit, t, s["obj"], sel, colour, srays, cand, skip))
-        going = hit >= 0
-        cur, kind = next_rays(cur, s, ior)
+    kinds = []
+
+    def refracting(cur, s):
+        nxt, kind = next_rays(cur, s, ior)
         kinds.append(kind)
-        tr = np.stack([np.where(going, F32(bounce_t_min), F32(1.0)), np.where(going, INF, F32(0.0))], axis=1).astype(np.float32)
-    return segs, kinds
+        return nxt
+    return vr.masked_walk(oracle, flat, rays, lights, depth, vis, obj_mask, bounce_t_min, t_range, flags, colours, cands, refracting), kinds
 
 
 def shade_paths(oracle, flat, rays, lights, depth, ior, reflectance=None, bounce_t_min=1e-3, t_range=None, flags=0, rule=None, vis=None, obj_mask=None,
@@ -156,39 +135,12 @@ def shade_paths(oracle, flat, rays, lights, depth, ior, reflectance=None, bounce
 
 
 def render_paths(oracle, flat, p, depth, ior, reflectance=None, bounce_t_min=1e-3, rule=None, vis=None, obj_mask=None, fill=None):
-    """srt_render_paths_refract by the yardstick: the composition of render_paths_ref.render_paths -- the rays of the owned pixels per
-    sub-sample, the mixed sums added in sub-sample order, divided by float32(spp), tone-mapped once -- on the paths above."""
-    own = rpr.owned(p)
-    sel = np.flatnonzero((own >= 0).reshape(-1))
-    lit = dict(shadow_div=float(p.shadow_div), reinhard=float(p.reinhard), gamma=float(p.gamma), background=tuple(int(c) for c in p.background[:3]))
-    flags = int(p.flags) & abi.SRT_FLAG_SMOOTH_NORMALS
-    spp = int(p.spp)
+    """srt_render_paths_refract by the yardstick: render_paths_ref.compose_frame on the paths above, the candidate sets shared among the
+    sub-samples."""
     memo = vr.CandidateMemo(oracle, flat)
-    first, total = None, None
-    for k in range(spp):
-        rays, _ = rpr.frame_rays_owned(p, k)
-        o = shade_paths(oracle, flat, rays.reshape(-1, 6)[sel], rpr.lights_of(p), depth, ior, reflectance, bounce_t_min, flags=flags, rule=rule, vis=vis,
-                        obj_mask=obj_mask, cands=memo, **lit)
-        if k == 0:
-            first, total = o, o["rgb_linear"].copy()
-        else:
-            total = (total + o["rgb_linear"]).astype(np.float32)
-    if spp > 1:
-        with np.errstate(all="ignore"):
-            lin = (total / F32(spp)).astype(np.float32)
-        _, q = oracle.tonemap(lin, lit["reinhard"], lit["gamma"], pow="device")
-        q = q.copy()
-        q[np.all(q == 0, axis=1)] = np.asarray(lit["background"], np.int32)
-        first = dict(first, rgb_linear=lin, rgb8=q.astype(np.uint8))
-    out = {}
-    for key in sp.ALL_KEYS:
-        v = first[key]
-        lead = v.shape[:1] if key.startswith("seg_") else ()
-        tail = v.shape[len(lead) + 1:]
-        full = np.zeros(lead + (own.size,) + tail, v.dtype) if fill is None else np.full(lead + (own.size,) + tail, fill, v.dtype)
-        full[(slice(None),) * len(lead) + (sel,)] = v
-        out[key] = full.reshape(lead + own.shape + tail)
-    return out
+    shade = lambda rays, lights, flags, **lit: shade_paths(oracle, flat, rays, lights, depth, ior, reflectance, bounce_t_min, flags=flags, rule=rule, vis=vis,
+                                                           obj_mask=obj_mask, cands=memo, **lit)
+    return rpr.compose_frame(oracle, p, shade, fill=fill)
 
 
 # ---- the cases of tests/test_gpu_refract.py --------------------------------------------------------------------------------------------
@@ -220,47 +172,39 @@ def condition(segs, kinds):
     return c
 
 
-_memo, _colours, _traces, _refs = {}, {}, {}, {}
+_cases = pw.CaseCache()
 
 
 def case_memo(oracle, name):
-    if name not in _memo:
-        _memo[name] = vr.CandidateMemo(oracle, sp.frame_case(name)[0])
-    return _memo[name]
+    return _cases.once(("memo", name), lambda: vr.CandidateMemo(oracle, sp.frame_case(name)[0]))
 
 
 def case_colours(oracle, name):
-    if name not in _colours:
+    def make():
         flat, _, lights, _ = sp.frame_case(name)
-        _colours[name] = vr.Colours(oracle, flat, lights)
-    return _colours[name]
+        return vr.Colours(oracle, flat, lights)
+    return _cases.once(("colours", name), make)
 
 
 def case_walks(oracle, name):
     """The primary walks of a frame case (no lights, no colours): (segs, kinds), computed once."""
-    key = (name, "walks")
-    if key not in _traces:
+    def make():
         flat, rays, _, _ = sp.frame_case(name)
-        _traces[key] = trace(oracle, flat, rays, np.zeros((0, 3), np.float32), DEPTHS[name], case_ior(flat), bounce_t_min=BOUNCE_T_MIN, cands=case_memo(oracle, name))
-    return _traces[key]
+        return trace(oracle, flat, rays, np.zeros((0, 3), np.float32), DEPTHS[name], case_ior(flat), bounce_t_min=BOUNCE_T_MIN, cands=case_memo(oracle, name))
+    return _cases.once(("walks", name), make)
 
 
 def case_trace(oracle, name):
     """The full trace of a frame case: computed once, shared, never changed."""
-    if name not in _traces:
+    def make():
         flat, rays, lights, _ = sp.frame_case(name)
-        _traces[name] = trace(oracle, flat, rays, lights, DEPTHS[name], case_ior(flat), bounce_t_min=BOUNCE_T_MIN, colours=case_colours(oracle, name),
-                              cands=case_memo(oracle, name))
-    return _traces[name]
+        return trace(oracle, flat, rays, lights, DEPTHS[name], case_ior(flat), bounce_t_min=BOUNCE_T_MIN, colours=case_colours(oracle, name), cands=case_memo(oracle, name))
+    return _cases.once(("trace", name), make)
 
 
 def case_reference(oracle, name, rule=None):
     """The yardstick's rows of a frame case under `rule`: computed once, shared, never changed."""
-    key = (name, None if rule is None else tuple(str(v) for v in rule))
-    if key not in _refs:
+    def make():
         flat, _, _, refl = sp.frame_case(name)
-        ref = vr.shade_paths_of(oracle, flat, case_trace(oracle, name)[0], DEPTHS[name], rule, refl)
-        for v in ref.values():
-            v.setflags(write=False)
-        _refs[key] = ref
-    return _refs[key]
+        return vr.shade_paths_of(oracle, flat, case_trace(oracle, name)[0], DEPTHS[name], rule, refl)
+    return _cases.once(("ref", name, pw.rule_key(rule)), make)

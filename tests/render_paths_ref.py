@@ -5,13 +5,15 @@ them arithmetic on colours beyond the header's spp rule:
     from abi.owned_pixels (the block and the tile deal), the direction is (i, j, focal) with i = x + (int)(-W / 2), j = y + (int)(-H / 2)
     plus the sub-pixel offset of sub-sample k, taken through the ray matrix with the oracle's association (M0 * dx + M1 * dy) + M2 * dz, or
     left as it stands without one.  Every arithmetic step is its own float32 array operation, so nothing is contracted.
-  * render_paths(...): shade_path_ref.shade_paths on those rays, per sub-sample, and the header's rule for spp > 1: the mixed sums added in
+  * compose_frame(...): a path yardstick on those rays, per sub-sample, and the header's rule for spp > 1: the mixed sums added in
     sub-sample order starting from sub-sample 0's, divided by float32(spp), tone-mapped once whatever was hit; seg reports sub-sample 0.
+    render_paths(...) is that with shade_path_ref.shade_paths; the other path yardsticks compose their frames with it too.
 
 Padding pixels (owned_pixels == -1) carry no ray: their rows are left out of the oracle's batch and come back as `fill`."""
 import numpy as np
 
 import shade_path_ref as sp
+from path_walk_ref import CaseCache
 from simple_raytracer_amd import abi
 
 F32 = np.float32
@@ -76,19 +78,21 @@ def lights_of(p):
     return np.ctypeslib.as_array(p.light_pos, shape=(int(p.n_lights), 3)).copy() if p.n_lights else np.zeros((0, 3), np.float32)
 
 
-def render_paths(oracle, flat, p, depth, reflectance=None, bounce_t_min=1e-3, fill=None):
-    """srt_render_paths by the yardstick: dict of rgb_linear [rows, cols, 3], rgb8, and seg_* [depth, rows, cols, ...]; padding pixels
-    hold `fill` (default 0).  Lights, literals and flags are p's."""
+def compose_frame(oracle, p, shade, keys=sp.ALL_KEYS, leading=lambda key: key.startswith("seg_"), fill=None):
+    """The frame of a call with params p by the header's rule: shade(rays, lights, flags, **literals) -> a yardstick dict for the rays of
+    the owned pixels, per sub-sample; the mixed sums added in sub-sample order starting from sub-sample 0's, divided by float32(spp),
+    tone-mapped once whatever was hit, the background rule; the other rows are sub-sample 0's.  Every key of `keys` is scattered into
+    [rows, cols, ...] -- behind a leading depth axis where leading(key) -- and padding pixels hold `fill` (default 0).  Lights, literals and
+    flags are p's."""
     own = owned(p)
-    live = own >= 0
-    sel = np.flatnonzero(live.reshape(-1))
+    sel = np.flatnonzero((own >= 0).reshape(-1))
     lit = dict(shadow_div=float(p.shadow_div), reinhard=float(p.reinhard), gamma=float(p.gamma), background=tuple(int(c) for c in p.background[:3]))
     flags = int(p.flags) & abi.SRT_FLAG_SMOOTH_NORMALS
     spp = int(p.spp)
     first, total = None, None
     for k in range(spp):
         rays, _ = frame_rays_owned(p, k)
-        o = sp.shade_paths(oracle, flat, rays.reshape(-1, 6)[sel], lights_of(p), depth, reflectance, bounce_t_min, flags=flags, **lit)
+        o = shade(rays.reshape(-1, 6)[sel], lights_of(p), flags, **lit)
         if k == 0:
             first, total = o, o["rgb_linear"].copy()
         else:
@@ -101,14 +105,21 @@ def render_paths(oracle, flat, p, depth, reflectance=None, bounce_t_min=1e-3, fi
         q[np.all(q == 0, axis=1)] = np.asarray(lit["background"], np.int32)
         first = dict(first, rgb_linear=lin, rgb8=q.astype(np.uint8))
     out = {}
-    for key in sp.ALL_KEYS:
+    for key in keys:
         v = first[key]
-        lead = v.shape[:1] if key.startswith("seg_") else ()
+        lead = v.shape[:1] if leading(key) else ()
         tail = v.shape[len(lead) + 1:]
         full = np.zeros(lead + (own.size,) + tail, v.dtype) if fill is None else np.full(lead + (own.size,) + tail, fill, v.dtype)
         full[(slice(None),) * len(lead) + (sel,)] = v
         out[key] = full.reshape(lead + own.shape + tail)
     return out
+
+
+def render_paths(oracle, flat, p, depth, reflectance=None, bounce_t_min=1e-3, fill=None):
+    """srt_render_paths by the yardstick: dict of rgb_linear [rows, cols, 3], rgb8, and seg_* [depth, rows, cols, ...]; padding pixels
+    hold `fill` (default 0).  Lights, literals and flags are p's."""
+    shade = lambda rays, lights, flags, **lit: sp.shade_paths(oracle, flat, rays, lights, depth, reflectance, bounce_t_min, flags=flags, **lit)
+    return compose_frame(oracle, p, shade, fill=fill)
 
 
 def flat_rows(o):
@@ -191,18 +202,15 @@ def case(name):
     return g.flat, p, np.float32(sp.REFLECTANCE[:int(g.flat.tri_obj.max()) + 1])
 
 
-_case_ref = {}
+_cases = CaseCache()
 
 
 def case_reference(oracle, name):
     """The yardstick's frame of a case: computed once, shared, never changed."""
-    if name not in _case_ref:
+    def make():
         flat, p, refl = case(name)
-        ref = render_paths(oracle, flat, p, DEPTH, refl, sp.BOUNCE_T_MIN)
-        for v in ref.values():
-            v.setflags(write=False)
-        _case_ref[name] = ref
-    return _case_ref[name]
+        return render_paths(oracle, flat, p, DEPTH, refl, sp.BOUNCE_T_MIN)
+    return _cases.once(name, make)
 
 
 def condition(ref):

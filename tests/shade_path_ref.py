@@ -12,6 +12,7 @@ import numpy as np
 
 import shade_range_ref as sr
 import surface_ref as sf
+from path_walk_ref import CaseCache
 from simple_raytracer_amd import abi
 
 F32 = np.float32
@@ -66,10 +67,12 @@ def shade_paths(oracle, flat, rays, lights, depth, reflectance=None, bounce_t_mi
     return out
 
 
-def finish(oracle, seg, reflectance, reinhard=0.5, gamma=1.1, background=abi.REFERENCE_BACKGROUND, **_):
-    """(rgb_linear, rgb8) of the per-segment rows `seg` under a reflectance table: the mix, then tone map, quantiser and background rule
-    as shade_range_ref.compose applies them (a ray whose segment 0 misses is not tone-mapped: it is the background)."""
-    lin = mix(seg["seg_hit_id"], seg["seg_obj"], seg["seg_rgb_linear"], reflectance)
+def finish(oracle, seg, reflectance, reinhard=0.5, gamma=1.1, background=abi.REFERENCE_BACKGROUND, lin=None, **_):
+    """(rgb_linear, rgb8) of the per-segment rows `seg` under a reflectance table: the mix (or `lin`, rows mixed otherwise), then tone map,
+    quantiser and background rule as shade_range_ref.compose applies them (a ray whose segment 0 misses is not tone-mapped: it is the
+    background)."""
+    if lin is None:
+        lin = mix(seg["seg_hit_id"], seg["seg_obj"], seg["seg_rgb_linear"], reflectance)
     _, q = oracle.tonemap(lin, reinhard, gamma, pow="device")
     q = q.copy()
     q[seg["seg_hit_id"][0] < 0] = 0
@@ -99,18 +102,15 @@ def frame_case(name):
     return g.flat, rays, sq.lights_for(name, g.light, N_LIGHTS), refl
 
 
-_frame_ref = {}
+_cases = CaseCache()
 
 
 def frame_reference(oracle, name):
     """The yardstick's rows of a frame case: computed once, shared, never changed."""
-    if name not in _frame_ref:
+    def make():
         flat, rays, lights, refl = frame_case(name)
-        ref = shade_paths(oracle, flat, rays, lights, DEPTH, refl, BOUNCE_T_MIN)
-        for v in ref.values():
-            v.setflags(write=False)
-        _frame_ref[name] = ref
-    return _frame_ref[name]
+        return shade_paths(oracle, flat, rays, lights, DEPTH, refl, BOUNCE_T_MIN)
+    return _cases.once(name, make)
 
 
 def condition(ref):

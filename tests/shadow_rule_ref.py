@@ -15,11 +15,9 @@ srt_render_paths_shadow).  It adds no arithmetic: every number comes from a help
 Neither the walk nor a colour depends on the rule: trace() computes the segments, the colours and the candidates of the shadow rays once,
 and shade_paths_of() composes them under any number of rules.  One tiny oracle render per hit and light: keep batches at the sizes of
 shade_path_ref.FRAMES and at most 3 lights."""
-from dataclasses import dataclass
-
 import numpy as np
 
-import ray_query_ref as rq
+import path_walk_ref as pw
 import ray_range_ref as rr
 import render_paths_ref as rpr
 import shade_path_ref as sp
@@ -27,7 +25,6 @@ import shade_range_ref as sr
 import surface_ref as sf
 from simple_raytracer_amd import abi
 
-F32 = np.float32
 INF = np.float32(np.inf)
 NAN = np.float32(np.nan)
 
@@ -36,20 +33,7 @@ SELF = (1e-3, 1.0, True)
 ENDED = (1e-3, 1.0, False)
 IDENTITIES = {"(0, inf)": (0.0, INF, False), "(-inf, inf)": (-INF, INF, False), "(NaN, NaN)": (NAN, NAN, False)}
 NO_SHADOWS = (2.0, 1.0, False)         # t_min > t_max: nothing is in range
-
-
-@dataclass
-class Segment:
-    rays: np.ndarray              # n x 6: the rays the segment walked (a zero ray where the path has ended)
-    going: np.ndarray             # n bool: the path was alive when the segment began
-    hit: np.ndarray               # n int32
-    t: np.ndarray                 # n float32
-    obj: np.ndarray               # n int32
-    sel: np.ndarray               # the rays that hit, in ray order
-    colour: np.ndarray            # n_hit x n_lights x 3: every sample unshadowed (zeros when the trace was made without colours)
-    srays: np.ndarray             # (n_lights * n_hit) x 6: the shadow rays, light-major
-    cand: rr.Candidates           # their candidate sets
-    skip: np.ndarray              # n_hit int64: the hit's object
+Segment = pw.Segment                   # (the rows of a segment live beside the walk that builds them)
 
 
 def shadow_bits(flat, seg, rule):
@@ -68,35 +52,20 @@ def shadow_bits(flat, seg, rule):
 
 
 def trace(oracle, flat, rays, lights, depth, bounce_t_min=1e-3, t_range=None, flags=0, colours=True, **literals):
-    """The segments of every path (a list of Segment, one per segment walked): shade_path_ref.shade_paths' loop without the sums.
-    colours = False leaves the oracle renders out (the bits alone: for looking at a case's input conditions)."""
-    rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
+    """The segments of every path (a list of Segment, one per segment walked): shade_path_ref.shade_paths' loop without the sums, the
+    winners and the candidates straight from the oracle.  colours = False leaves the oracle renders out (the bits alone: for looking at a
+    case's input conditions)."""
     lights = np.ascontiguousarray(lights, np.float32).reshape(-1, 3)
-    n, nl = rays.shape[0], lights.shape[0]
     smooth = bool(flags & abi.SRT_FLAG_SMOOTH_NORMALS)
-    cur = rays
-    tr = None if t_range is None else np.ascontiguousarray(t_range, np.float32).reshape(-1, 2)
-    going = np.ones(n, bool)
-    segs = []
-    for b in range(depth):
-        if not going.any():
-            break
-        hit, t = sr.winners(oracle, flat, cur, tr)
-        assert not (hit[~going] >= 0).any(), "an ended path hit something"
-        sel = np.flatnonzero(hit >= 0)
-        skip = flat.tri_obj[hit[sel]].astype(np.int64)
-        srays = (np.concatenate([rq.shadow_rays(cur[sel], t[sel], lights[l]) for l in range(nl)]) if nl and sel.size else np.zeros((0, 6), np.float32))
-        cand = rr.candidates(oracle, flat, srays)
-        s = sf.surface(oracle, flat, cur, hit, t, smooth)
-        seg = Segment(np.where(going[:, None], cur, F32(0.0)), going, hit, t, s["obj"], sel, np.zeros((sel.size, nl, 3), np.float32), srays, cand, skip)
+
+    def segment(cur, going, hit, t, obj):
+        seg = pw.segment_of(flat, cur, going, hit, t, obj, lights, lambda srays: rr.candidates(oracle, flat, srays), None)
         if colours:
             seg.colour, reference_bits = sr.samples(oracle, flat, cur, hit, t, lights, flags, **literals)
             assert np.array_equal(reference_bits, shadow_bits(flat, seg, None)), "rule None is not the reference's rule"
-        segs.append(seg)
-        going = hit >= 0
-        cur = np.ascontiguousarray(s["bounce"])                                  # a miss row: the zero ray
-        tr = np.stack([np.where(going, F32(bounce_t_min), F32(1.0)), np.where(going, INF, F32(0.0))], axis=1).astype(np.float32)
-    return segs
+        return seg
+    return pw.walk(rays, depth, winners=lambda b, cur, tr: sr.winners(oracle, flat, cur, tr), segment=segment,
+                   surface=lambda cur, hit, t: sf.surface(oracle, flat, cur, hit, t, smooth), bounce_t_min=bounce_t_min, t_range=t_range)
 
 
 def shade_paths_of(oracle, flat, segs, depth, rule=None, reflectance=None, bits=None, **literals):
@@ -119,36 +88,9 @@ def shade_paths(oracle, flat, rays, lights, depth, reflectance=None, bounce_t_mi
 
 
 def render_paths(oracle, flat, p, depth, reflectance=None, bounce_t_min=1e-3, rule=None, fill=None):
-    """srt_render_paths_shadow by the yardstick: render_paths_ref.render_paths with the paths above.  Lights, literals and flags are p's."""
-    own = rpr.owned(p)
-    sel = np.flatnonzero((own >= 0).reshape(-1))
-    lit = dict(shadow_div=float(p.shadow_div), reinhard=float(p.reinhard), gamma=float(p.gamma), background=tuple(int(c) for c in p.background[:3]))
-    flags = int(p.flags) & abi.SRT_FLAG_SMOOTH_NORMALS
-    spp = int(p.spp)
-    first, total = None, None
-    for k in range(spp):
-        rays, _ = rpr.frame_rays_owned(p, k)
-        o = shade_paths(oracle, flat, rays.reshape(-1, 6)[sel], rpr.lights_of(p), depth, reflectance, bounce_t_min, flags=flags, rule=rule, **lit)
-        if k == 0:
-            first, total = o, o["rgb_linear"].copy()
-        else:
-            total = (total + o["rgb_linear"]).astype(np.float32)
-    if spp > 1:
-        with np.errstate(all="ignore"):
-            lin = (total / F32(spp)).astype(np.float32)
-        _, q = oracle.tonemap(lin, lit["reinhard"], lit["gamma"], pow="device")
-        q = q.copy()
-        q[np.all(q == 0, axis=1)] = np.asarray(lit["background"], np.int32)
-        first = dict(first, rgb_linear=lin, rgb8=q.astype(np.uint8))
-    out = {}
-    for key in sp.ALL_KEYS:
-        v = first[key]
-        lead = v.shape[:1] if key.startswith("seg_") else ()
-        tail = v.shape[len(lead) + 1:]
-        full = np.zeros(lead + (own.size,) + tail, v.dtype) if fill is None else np.full(lead + (own.size,) + tail, fill, v.dtype)
-        full[(slice(None),) * len(lead) + (sel,)] = v
-        out[key] = full.reshape(lead + own.shape + tail)
-    return out
+    """srt_render_paths_shadow by the yardstick: render_paths_ref.compose_frame with the paths above.  Lights, literals and flags are p's."""
+    shade = lambda rays, lights, flags, **lit: shade_paths(oracle, flat, rays, lights, depth, reflectance, bounce_t_min, flags=flags, rule=rule, **lit)
+    return rpr.compose_frame(oracle, p, shade, fill=fill)
 
 
 # ---- the cases of tests/test_gpu_shadow_rule.py ----------------------------------------------------------------------------------------
@@ -168,27 +110,23 @@ def lamp_case(name):
     return flat, rays, abi.light_staircase(np.asarray(LAMPS[name], np.float32), N_LIGHTS), refl
 
 
-_traces, _refs = {}, {}
+_cases = pw.CaseCache()
 
 
 def case_trace(oracle, name):
     """The trace of a case: computed once, shared, never changed."""
-    if name not in _traces:
+    def make():
         flat, rays, lights, _ = lamp_case(name)
-        _traces[name] = trace(oracle, flat, rays, lights, DEPTH, BOUNCE_T_MIN)
-    return _traces[name]
+        return trace(oracle, flat, rays, lights, DEPTH, BOUNCE_T_MIN)
+    return _cases.once(("trace", name), make)
 
 
 def case_reference(oracle, name, rule):
     """The yardstick's rows of a case under `rule`: computed once, shared, never changed."""
-    key = (name, None if rule is None else tuple(str(v) for v in rule))
-    if key not in _refs:
+    def make():
         flat, _, _, refl = lamp_case(name)
-        ref = shade_paths_of(oracle, flat, case_trace(oracle, name), DEPTH, rule, refl)
-        for v in ref.values():
-            v.setflags(write=False)
-        _refs[key] = ref
-    return _refs[key]
+        return shade_paths_of(oracle, flat, case_trace(oracle, name), DEPTH, rule, refl)
+    return _cases.once(("ref", name, pw.rule_key(rule)), make)
 
 
 def conditions(flat, segs, ref_none, ref_self):

@@ -4,28 +4,25 @@ ray_range_ref holds for every ray, by the object that owns each candidate.
 
   * visible(c, flat, ray_mask, obj_mask): the candidates of participating objects -- (obj_mask[tri_obj[tri]] & ray_mask[ray]) != 0.
   * Closest hit and occlusion: ray_range_ref.closest / ray_range_ref.occluded on the filtered set, as they stand.
-  * Paths: the loop of shadow_rule_ref.trace restated with the filtered winners per segment KIND -- vis.primary for segment 0, vis.bounce
+  * Paths: the loop of shadow_rule_ref.trace (path_walk_ref.walk) with the filtered winners per segment KIND -- vis.primary for segment 0, vis.bounce
     for every later one -- and the shadow rays' candidates filtered by vis.shadow.  The colour of a (hit, light) sample does not depend on
     any mask: shade_range_ref.samples, asked once per (ray, hit) and kept.  What comes out is a list of shadow_rule_ref.Segment, so
     shadow_rule_ref.shadow_bits and shade_paths_of compose it under any rule, and surface_ref / shade_path_ref.finish do the rest.
-  * Frames: shadow_rule_ref.render_paths' loop over the sub-samples on the paths above.
+  * Frames: render_paths_ref.compose_frame on the paths above.
   * sub_scene(flat, keep): the flat scene with only the kept objects -- the scene the definition's "oracle on the reduced scene" runs on --
     and the map from its triangle ids back to the full scene's.
 
 tests/test_visibility_ref.py pins the filter to the oracle's own frames on sub_scene, and the paths to shadow_rule_ref at all-ones masks."""
 import numpy as np
 
-import ray_query_ref as rq
+import path_walk_ref as pw
 import ray_range_ref as rr
 import render_paths_ref as rpr
-import shade_path_ref as sp
 import shade_range_ref as sr
 import shadow_rule_ref as sh
 import surface_ref as sf
 from simple_raytracer_amd import abi
 
-F32 = np.float32
-INF = np.float32(np.inf)
 ALL = 0xFFFFFFFF
 
 
@@ -150,36 +147,23 @@ class CandidateMemo:
         return rr.Candidates(rays.shape[0], np.repeat(np.arange(len(got), dtype=np.int64), cnt), tri.astype(np.int64), t.astype(np.float32))
 
 
+def masked_walk(oracle, flat, rays, lights, depth, vis, obj_mask, bounce_t_min, t_range, flags, colours, cands, next_rays=pw.mirror_rays):
+    """path_walk_ref.walk under masks: every Segment's winners are the filtered closest hits of its kind -- vis[0] for segment 0, vis[1]
+    for every later one -- and its `cand` the shadow rays' candidates filtered by vis[2].  cands(rays): their candidate sets."""
+    lights = np.ascontiguousarray(lights, np.float32).reshape(-1, 3)
+    smooth = bool(flags & abi.SRT_FLAG_SMOOTH_NORMALS)
+    return pw.walk(rays, depth, winners=lambda b, cur, tr: closest(cands(cur), flat, vis[0] if b == 0 else vis[1], obj_mask, tr),
+                   segment=lambda cur, going, hit, t, obj: pw.segment_of(flat, cur, going, hit, t, obj, lights, lambda srays: visible(cands(srays), flat, vis[2], obj_mask),
+                                                                         colours),
+                   surface=lambda cur, hit, t: sf.surface(oracle, flat, cur, hit, t, smooth), next_rays=next_rays, bounce_t_min=bounce_t_min, t_range=t_range)
+
+
 def trace(oracle, flat, rays, lights, depth, vis, obj_mask=None, bounce_t_min=1e-3, t_range=None, flags=0, colours=None, cands=None):
-    """shadow_rule_ref.trace under masks: vis = (primary, bounce, shadow), obj_mask the scene's table (None: all ones).  Every Segment's
-    winners are the filtered closest hits of its kind, and its `cand` the shadow rays' candidates filtered by vis[2].
+    """shadow_rule_ref.trace under masks: vis = (primary, bounce, shadow), obj_mask the scene's table (None: all ones).
     colours: a Colours (None: the colours stay zero -- the bits alone, for looking at a case's input conditions).
     cands: a CandidateMemo to ask for candidate sets (None: ray_range_ref.candidates itself)."""
     cands = cands if cands is not None else (lambda r: rr.candidates(oracle, flat, r))
-    rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
-    lights = np.ascontiguousarray(lights, np.float32).reshape(-1, 3)
-    n, nl = rays.shape[0], lights.shape[0]
-    smooth = bool(flags & abi.SRT_FLAG_SMOOTH_NORMALS)
-    cur = rays
-    tr = None if t_range is None else np.ascontiguousarray(t_range, np.float32).reshape(-1, 2)
-    going = np.ones(n, bool)
-    segs = []
-    for b in range(depth):
-        if not going.any():
-            break
-        hit, t = closest(cands(cur), flat, vis[0] if b == 0 else vis[1], obj_mask, tr)
-        assert not (hit[~going] >= 0).any(), "an ended path hit something"
-        sel = np.flatnonzero(hit >= 0)
-        skip = flat.tri_obj[hit[sel]].astype(np.int64)
-        srays = (np.concatenate([rq.shadow_rays(cur[sel], t[sel], lights[l]) for l in range(nl)]) if nl and sel.size else np.zeros((0, 6), np.float32))
-        cand = visible(cands(srays), flat, vis[2], obj_mask)
-        s = sf.surface(oracle, flat, cur, hit, t, smooth)
-        colour = colours(cur, hit, t) if colours is not None else np.zeros((sel.size, nl, 3), np.float32)
-        segs.append(sh.Segment(np.where(going[:, None], cur, F32(0.0)), going, hit, t, s["obj"], sel, colour, srays, cand, skip))
-        going = hit >= 0
-        cur = np.ascontiguousarray(s["bounce"])                                  # a miss row: the zero ray
-        tr = np.stack([np.where(going, F32(bounce_t_min), F32(1.0)), np.where(going, INF, F32(0.0))], axis=1).astype(np.float32)
-    return segs
+    return masked_walk(oracle, flat, rays, lights, depth, vis, obj_mask, bounce_t_min, t_range, flags, colours, cands)
 
 
 def shade_paths_of(oracle, flat, segs, depth, rule=None, reflectance=None, **literals):
@@ -198,36 +182,9 @@ def shade_paths(oracle, flat, rays, lights, depth, vis, obj_mask=None, reflectan
 
 
 def render_paths(oracle, flat, p, depth, vis, obj_mask=None, reflectance=None, bounce_t_min=1e-3, rule=None, fill=None):
-    """srt_render_paths_masked by the yardstick: shadow_rule_ref.render_paths with the paths above.  Lights, literals and flags are p's."""
-    own = rpr.owned(p)
-    sel = np.flatnonzero((own >= 0).reshape(-1))
-    lit = dict(shadow_div=float(p.shadow_div), reinhard=float(p.reinhard), gamma=float(p.gamma), background=tuple(int(c) for c in p.background[:3]))
-    flags = int(p.flags) & abi.SRT_FLAG_SMOOTH_NORMALS
-    spp = int(p.spp)
-    first, total = None, None
-    for k in range(spp):
-        rays, _ = rpr.frame_rays_owned(p, k)
-        o = shade_paths(oracle, flat, rays.reshape(-1, 6)[sel], rpr.lights_of(p), depth, vis, obj_mask, reflectance, bounce_t_min, flags=flags, rule=rule, **lit)
-        if k == 0:
-            first, total = o, o["rgb_linear"].copy()
-        else:
-            total = (total + o["rgb_linear"]).astype(np.float32)
-    if spp > 1:
-        with np.errstate(all="ignore"):
-            lin = (total / F32(spp)).astype(np.float32)
-        _, q = oracle.tonemap(lin, lit["reinhard"], lit["gamma"], pow="device")
-        q = q.copy()
-        q[np.all(q == 0, axis=1)] = np.asarray(lit["background"], np.int32)
-        first = dict(first, rgb_linear=lin, rgb8=q.astype(np.uint8))
-    out = {}
-    for key in sp.ALL_KEYS:
-        v = first[key]
-        lead = v.shape[:1] if key.startswith("seg_") else ()
-        tail = v.shape[len(lead) + 1:]
-        full = np.zeros(lead + (own.size,) + tail, v.dtype) if fill is None else np.full(lead + (own.size,) + tail, fill, v.dtype)
-        full[(slice(None),) * len(lead) + (sel,)] = v
-        out[key] = full.reshape(lead + own.shape + tail)
-    return out
+    """srt_render_paths_masked by the yardstick: render_paths_ref.compose_frame with the paths above.  Lights, literals and flags are p's."""
+    shade = lambda rays, lights, flags, **lit: shade_paths(oracle, flat, rays, lights, depth, vis, obj_mask, reflectance, bounce_t_min, flags=flags, rule=rule, **lit)
+    return rpr.compose_frame(oracle, p, shade, fill=fill)
 
 
 # ---- the cases of tests/test_gpu_visibility.py ------------------------------------------------------------------------------------------
@@ -267,50 +224,40 @@ def ray_masks(name, n):
     return kinds[kind], kind
 
 
-_colours, _traces, _refs, _cands = {}, {}, {}, {}
+_cases = pw.CaseCache()
 
 
 def case_memo(oracle, name):
-    if ("memo", name) not in _cands:
-        _cands[("memo", name)] = CandidateMemo(oracle, sh.lamp_case(name)[0])
-    return _cands[("memo", name)]
+    return _cases.once(("memo", name), lambda: CandidateMemo(oracle, sh.lamp_case(name)[0]))
 
 
 def case_colours(oracle, name):
-    if name not in _colours:
+    def make():
         flat, _, lights, _ = sh.lamp_case(name)
-        _colours[name] = Colours(oracle, flat, lights)
-    return _colours[name]
+        return Colours(oracle, flat, lights)
+    return _cases.once(("colours", name), make)
 
 
 def case_candidates(oracle, name):
     """The candidate sets of a lamp case's rays: computed once, shared, never changed."""
-    if name not in _cands:
-        flat, rays, _, _ = sh.lamp_case(name)
-        _cands[name] = case_memo(oracle, name)(rays)
-    return _cands[name]
+    return _cases.once(("candidates", name), lambda: case_memo(oracle, name)(sh.lamp_case(name)[1]))
 
 
 def case_trace(oracle, name, which, colours=True):
     """The masked trace of a lamp case under triple `which`: computed once, shared, never changed."""
-    key = (name, which, colours)
-    if key not in _traces:
+    def make():
         flat, rays, lights, _ = sh.lamp_case(name)
-        _traces[key] = trace(oracle, flat, rays, lights, DEPTH, case_vis(name, which), case_table(flat), BOUNCE_T_MIN,
-                             colours=case_colours(oracle, name) if colours else None, cands=case_memo(oracle, name))
-    return _traces[key]
+        return trace(oracle, flat, rays, lights, DEPTH, case_vis(name, which), case_table(flat), BOUNCE_T_MIN,
+                     colours=case_colours(oracle, name) if colours else None, cands=case_memo(oracle, name))
+    return _cases.once(("trace", name, which, colours), make)
 
 
 def case_reference(oracle, name, which, rule):
     """The yardstick's rows of a lamp case under triple `which` and `rule`: computed once, shared, never changed."""
-    key = (name, which, None if rule is None else tuple(str(v) for v in rule))
-    if key not in _refs:
+    def make():
         flat, _, _, refl = sh.lamp_case(name)
-        ref = shade_paths_of(oracle, flat, case_trace(oracle, name, which), DEPTH, rule, refl)
-        for v in ref.values():
-            v.setflags(write=False)
-        _refs[key] = ref
-    return _refs[key]
+        return shade_paths_of(oracle, flat, case_trace(oracle, name, which), DEPTH, rule, refl)
+    return _cases.once(("ref", name, which, pw.rule_key(rule)), make)
 
 
 def mask_conditions(flat, c, ray_mask, obj_mask):
