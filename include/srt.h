@@ -1094,6 +1094,15 @@ int srt_kat_phong(int device, uint32_t n, const float* in28, float* rgb);
 int srt_kat_interp_normal(int device, uint32_t n, const float* in12 /* 3 normals + barycentrics */, float* out3);   /* interpolateNormal :132-140 */
 int srt_kat_pow(int device, uint32_t n, const float* x, const float* y, float* fast, float* lib);   /* the device powf: shipped form vs (float)pow(double) */
 int srt_kat_tonemap(int device, uint32_t n, const float* lin, float reinhard, float gamma, float* tone, int32_t* q);
+/* The quantised tone map as the shading kernels compute it -- an f32 filter that decides the 8-bit value where a margin allows, the exact
+ * functions (srt_kat_tonemap's) where it does not -- for n VALUES (not pixels): q = what a pixel's channel gets, q_filter = the filter's
+ * own candidate (-1 where it decided nothing), decided = 1 where the filter alone decided.  q equals srt_kat_tonemap's q on every input. */
+int srt_kat_tone_filter(int device, uint32_t n, const float* lin, float reinhard, float gamma, int32_t* q, int32_t* q_filter, uint8_t* decided);
+/* The same comparison for every float whose bit pattern lies in [first_bits, last_bits], reduced on the device.  out6: [0] values,
+ * [1] undecided by the filter, [2] decided and different from the exact functions, [3] different after the fallback (what a pixel gets),
+ * [4] the largest relative deviation of the filter's 255 * tone from the exact one over decided values, [5] the largest of that deviation
+ * over the margin the filter allowed for it ([4] and [5] over values whose exact 255 * tone is at least 1e-30). */
+int srt_kat_tone_filter_sweep(int device, uint32_t first_bits, uint32_t last_bits, float reinhard, float gamma, double* out6);
 
 /* Measurement hook: the chip's VALU issue rate from independent v_fma_f32 streams at 8 waves per SIMD (the yardstick bench.py's
  * roofline prices the kernels' VALU work against).  out[0] = wave-instructions one SIMD issues per cycle (MI355X: SIMD-32, a wave64

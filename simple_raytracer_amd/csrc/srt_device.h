@@ -360,4 +360,96 @@ __device__ __forceinline__ int quant1(float c) {
     return (int)s;
 }
 
+// ---- the tone map as a filter: quant1(tone1(c)) decided in f32 where a margin allows, the exact functions where it does not ----------
+// quant1(tone1(c, reinhard, gamma)) is trunc(255 * (c / (c + reinhard))^gamma) through three f32 roundings and an f64 pow -- some 97 VALU
+// instructions a channel, 71 of them f64 -- for a value of which eight bits are kept.  The candidate is the same quantity in f32,
+//     cand = 255 * exp2(gamma * (log2 c - log2(c + reinhard))),
+// and it decides the integer whenever cand - m and cand + m have one floor below 255, m = rel * cand being a bound on |cand - exact|.
+// Like the filtered slab test (slab_pass): the answer is the exact functions' for every input, the filter only says when they need not run.
+//
+// The margin.  T = 255 * (c / s)^gamma in real numbers with s = fl(c + reinhard), the float both forms start from.  u = 2^-24.
+//   exact side: the divide rounds the quotient once (u, raised to gamma: gamma * u), the f64 pow is off by < 1e-13, its result rounds to
+//     f32 (u), the product with 255 rounds (u):                                                     |exact / T - 1| <= (gamma + 2) u
+//   filter side: v_log_f32 and v_exp_f32 are accurate to 1 ulp of their result ("CDNA4 Instruction Set Architecture", VOP1 descriptions
+//     of V_LOG_F32 and V_EXP_F32; LLVM's AMDGPU lowering of log2f / exp2f relies on the same figure), 1 ulp <= 2 u |result|:
+//       lc = log2 c, ls = log2 s         absolute error <= 2 u |lc|, 2 u |ls|
+//       d  = lc - ls                     rounds: u |d| <= u (|lc| + |ls|)                  -> |err d| <= 3 u B,   B = |lc| + |ls|
+//       z  = gamma * d                   rounds: u |z| <= gamma u B                        -> |err z| <= 4 u gamma B
+//       e  = exp2 z                      d(2^z) / 2^z = ln 2 * err z, plus 1 ulp: 2 u      -> relative  4 ln2 u gamma B + 2 u
+//       cand = 255 * e                   rounds: u
+//     and cand -+ m round once more each (u):                                 |cand / T - 1| <= 4 ln2 u gamma B + 4 u
+//   together: E(gamma, B) = u * (4 ln2 gamma B + gamma + 6); for the default gamma 1.1 and sums around 1 (B ~ 1.5) that is 7e-7.
+// Shipped: rel = TONE_SAFETY * E with TONE_SAFETY = 4.  The factor is there because the model's 1 ulp is the manual's word, not a
+// measurement, and because the sweeps (srt_kat_tone_filter_sweep: every float at the default literals, 1e-4 .. 1e4 at seven other
+// pairs) cover a handful of (reinhard, gamma) pairs and leave the others to the model.  Those sweeps observed |cand / exact - 1| up to
+// 0.78 E, never above E: rel is at least five times what was seen (the tests hold it to four; DESIGN.md s5 "The tone map as a filter"
+// has the figures).  Not wider than that: an undecided channel costs its whole wave a round of the exact functions -- 5 % of the
+// headline frame's hit waves run one at this factor, 9 % did at 8.
+//
+// The filter decides nothing -- every comparison below is false on a NaN, and B is NaN or +inf in each of these cases -- when
+//   c or c + reinhard is not a positive normal number (-0, negatives, NaN, +-inf, subnormals, a zero or overflowed sum): v_log_f32 gives
+//     NaN, +-inf or, for a subnormal (which it may or may not flush), a logarithm below -126;
+//   B >= 99: |lc|, |ls| and |lc - ls| are each below B, so B < 99 keeps c, the sum and their quotient inside (2^-99, 2^99), which lies
+//     inside pow_like_host's fast range (1e-30, 1e30) with room for the logarithms' errors;
+//   gamma is outside (0, 1e4): pow_like_host's own bound above, and nothing to gain at or below 0 (tone = 1 or beyond: the clamp);
+//     NaN fails both tests.  A large gamma inside the range needs no bound of its own: rel grows with it and soon decides nothing;
+//   cand + m >= 255: quant1's clamp.
+// One certain case is added: c == +0 (the bit pattern) with reinhard > 0 and gamma in range is 0 / reinhard = 0, 0^gamma = 0, value 0 --
+// a channel the light never reaches, which otherwise falls through pow_like_host into the library pow.
+constexpr float TONE_SAFETY = 4.0f;
+constexpr float TONE_B_MAX = 99.0f;
+struct ToneFilter {      // the wave-uniform half: what depends on reinhard and gamma alone
+    float ka, kb;        // rel = ka * B + kb
+    bool on, zero;       // gamma in range; c == +0 is certain
+};
+__device__ __forceinline__ ToneFilter tone_filter(float reinhard, float gamma) {
+    const float u = 5.9604644775390625e-8f;      // 2^-24
+    ToneFilter f;
+    f.on = gamma > 0.0f && gamma < 1.0e4f;
+    f.zero = f.on && reinhard > 0.0f;
+    f.ka = (TONE_SAFETY * 4.0f * 0.69314718f * u) * gamma;
+    f.kb = (TONE_SAFETY * u) * (gamma + 6.0f);
+    return f;
+}
+// One channel through the filter: the candidate's integer, whether it is decided, and (for the device checks) cand and rel themselves.
+__device__ __forceinline__ bool tone_candidate(const ToneFilter& f, float c, float reinhard, float gamma, int& q, float& cand, float& rel) {
+    const float lc = __builtin_amdgcn_logf(c), ls = __builtin_amdgcn_logf(c + reinhard);      // v_log_f32: log2
+    const float B = __builtin_fabsf(lc) + __builtin_fabsf(ls);
+    cand = 255.0f * __builtin_amdgcn_exp2f(gamma * (lc - ls));                                // v_exp_f32: 2^x
+    rel = __builtin_fmaf(f.ka, B, f.kb);
+    const float m = rel * cand, hi = cand + m;
+    q = (int)cand;
+    const bool inside = (B < TONE_B_MAX) & (__builtin_floorf(cand - m) == __builtin_floorf(hi)) & (hi < 255.0f);      // (&: three compares, no branch)
+    return f.on & (inside | (f.zero & (__float_as_uint(c) == 0u)));
+}
+// The quantised tone map of N channels: bit for bit quant1(tone1(c[k], reinhard, gamma)) for every input.  All channels go through the
+// filter, then one loop runs the exact functions for the lanes that still have an open channel, one channel a round: the exact code, with
+// its f64 chains and the library pow inlined, stands once at a call site however many channels there are.  exact_only (wave-uniform,
+// the A/B switch) opens every channel.
+// The exact functions out of line: ONE copy in the code object, called from the rare round below by every kernel that stores pixels.
+// Inlined into that loop, the loop's invariants -- two dozen f64 literals in register pairs -- are hoisted ahead of it and live across it:
+// k_shade_tile<1> went from 44 VGPRs to 63 with 44 B of scratch.  As a call it needs what the exact code itself needs (44 VGPRs), no scratch.
+__device__ __attribute__((noinline)) int quant_tone_exact(float c, float reinhard, float gamma) { return quant1(tone1(c, reinhard, gamma)); }
+template <int N>
+__device__ __forceinline__ void quant_tone(const float (&c)[N], float reinhard, float gamma, bool exact_only, int (&q)[N]) {
+    uint32_t open = (1u << N) - 1u;
+    if (!exact_only) {
+        const ToneFilter f = tone_filter(reinhard, gamma);
+        float cand, rel;
+#pragma unroll
+        for (int k = 0; k < N; k++) if (tone_candidate(f, c[k], reinhard, gamma, q[k], cand, rel)) open &= ~(1u << k);
+    }
+#pragma unroll 1
+    while (open) {
+        const int k = __builtin_ctz(open);
+        float x = c[0];
+#pragma unroll
+        for (int j = 1; j < N; j++) if (k == j) x = c[j];
+        const int e = quant_tone_exact(x, reinhard, gamma);
+#pragma unroll
+        for (int j = 0; j < N; j++) if (k == j) q[j] = e;
+        open &= open - 1u;
+    }
+}
+
 } // namespace srt

@@ -1107,6 +1107,7 @@ enum Variant : uint32_t {
     V_PK_CLOCKS = 58,             // shipped choice, the plain walk with per-wave clock stamps (SRT_DIAG_COUNTERS)
     V_FUSED_FOUR_WAVES = 59,      // shipped choice, the fused kernel as four waves of 4x4 pixels per tile where the half-tile form would run
     V_SHADOW_PLAIN_ROWS = 62,     // shipped choice, the node-queue shadow kernel in plain tile order where XCD rows are on
+    V_EXACT_TONE = 63,            // shipped choice, every pixel's tone map by the exact functions (no f32 filter: EXP_EXACT_TONE)
 };
 // Numbers without a name keep two fallbacks: 7..9 run the unfused node-queue chain of the shipped kernels, any other number a
 // configuration of the fused kernel (the shipped one) at every sample count.
@@ -1116,7 +1117,7 @@ static inline uint32_t variant_of(const srt_params* p) { return (p->flags >> 8) 
 // among them: it is a configuration of the fused kernel (fused_config in plan_frame) and takes the fused launch at every sample count.
 static inline bool shipped_choice(uint32_t v) {
     return v == V_SHIPPED || v == V_NO_PACKET || v == V_PK_WINDOWS || v == V_COARSE_GRID || v == V_PK_ENTRY_ORDER || v == V_CAMERA_PK ||
-           (v >= V_ROUND2_FORM && v <= V_SHADOW_PLAIN_ROWS);
+           (v >= V_ROUND2_FORM && v <= V_SHADOW_PLAIN_ROWS) || v == V_EXACT_TONE;
 }
 
 // Kernels of one argument list have one type: a plan names the instantiation as a value, one statement per list launches it.
@@ -1210,7 +1211,7 @@ static FramePlan plan_frame(const SceneFacts& f, const srt_params* p, BatchState
     const size_t n_tiles = (size_t)grid8.x * grid8.y, pixels = (size_t)wl * rows;
 
     pl.exp = ((v == V_ROUND2_FORM || v == V_LANE_ORDER) ? 1u : 0u) | (v == V_ROOT_LOOP ? 2u : 0u) | (v == V_WIDE_STEP_COUNTERS ? 4u : 0u) | (v == V_NO_UNION_BOX ? 8u : 0u) |
-             ((v == V_TRACE_SHADE || v == V_TRI_QUEUE) ? 32u : 0u);      // (32: the kernel counts the hits itself -- the hit statistic is not the shading kernel's)
+             (v == V_EXACT_TONE ? EXP_EXACT_TONE : 0u) | ((v == V_TRACE_SHADE || v == V_TRI_QUEUE) ? 32u : 0u);      // (32: the kernel counts the hits itself -- the hit statistic is not the shading kernel's)
     pl.xcd_rows = (f.bytes > (32ull << 20) || v == V_XCD_ROWS) ? 1u : 0u;      // records far beyond one XCD's 4 MiB L2
     pl.pk_units = in_flight ? f.pk_units : 0u; pl.pk_take = in_flight && f.pk_take ? f.pk_take : 1u;
     pl.grid_shade = grid16;
@@ -2766,6 +2767,34 @@ int srt_kat_tonemap(int device, uint32_t n, const float* lin, float reinhard, fl
     HIP_TRY(hipGetLastError()); HIP_TRY(hipDeviceSynchronize());
     SRT_TRY(o.down(tone, (size_t)n * 12));
     return o2.down(q, (size_t)n * 12);
+}
+
+int srt_kat_tone_filter(int device, uint32_t n, const float* lin, float reinhard, float gamma, int32_t* q, int32_t* q_filter, uint8_t* decided) {
+    if (!n || !lin || !q || !q_filter || !decided) return SRT_ERR_ARG;
+    HIP_TRY(hipSetDevice(device));
+    DevBuf a, o, o2, o3;
+    SRT_TRY(a.up(lin, (size_t)n * 4)); SRT_TRY(o.alloc((size_t)n * 4)); SRT_TRY(o2.alloc((size_t)n * 4)); SRT_TRY(o3.alloc((size_t)n));
+    const uint32_t triples = (uint32_t)(((uint64_t)n + 2) / 3);
+    hipLaunchKernelGGL(k_kat_tone_filter, dim3((triples + 255) / 256), dim3(256), 0, 0, n, (const float*)a.p, reinhard, gamma, (int32_t*)o.p, (int32_t*)o2.p, (uint8_t*)o3.p);
+    HIP_TRY(hipGetLastError()); HIP_TRY(hipDeviceSynchronize());
+    SRT_TRY(o.down(q, (size_t)n * 4)); SRT_TRY(o2.down(q_filter, (size_t)n * 4));
+    return o3.down(decided, (size_t)n);
+}
+
+int srt_kat_tone_filter_sweep(int device, uint32_t first_bits, uint32_t last_bits, float reinhard, float gamma, double* out) {
+    if (!out || last_bits < first_bits) return SRT_ERR_ARG;
+    HIP_TRY(hipSetDevice(device));
+    const unsigned long long count = (unsigned long long)last_bits - first_bits + 1ull, zero[6] = {0ull, 0ull, 0ull, 0ull, 0ull, 0ull};
+    unsigned long long h[6];
+    DevBuf o;
+    SRT_TRY(o.up(zero, sizeof(zero)));
+    const unsigned long long wgs = (count + 255ull) / 256ull;
+    hipLaunchKernelGGL(k_kat_tone_sweep, dim3((uint32_t)(wgs < 2048ull ? wgs : 2048ull)), dim3(256), 0, 0, first_bits, count, reinhard, gamma, (unsigned long long*)o.p);
+    HIP_TRY(hipGetLastError()); HIP_TRY(hipDeviceSynchronize());
+    SRT_TRY(o.down(h, sizeof(h)));
+    for (int k = 0; k < 4; k++) out[k] = (double)h[k];
+    for (int k = 4; k < 6; k++) std::memcpy(out + k, h + k, 8);
+    return SRT_OK;
 }
 
 } // extern "C"

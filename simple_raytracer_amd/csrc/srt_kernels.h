@@ -59,6 +59,7 @@ struct DevParams {
     uint32_t pk_units, pk_take;   // packet shadow kernel: units a wave should have to walk -- surplus waves of the fixed-size grid leave at once (0 = all stay) --, and how many unit numbers one atomic takes
 };
 static_assert(sizeof(DevParams) == 160, "DevParams has no implicit padding");
+constexpr uint32_t EXP_EXACT_TONE = 16u;      // DevParams.exp: store_pixel skips the tone map's filter and runs the exact functions on every channel (variant 63, A/B)
 
 // counters[0] hit pixels, [1]/[2] node/triangle tests of the closest-hit kernel, [3]/[4] of the shade kernel
 __device__ __forceinline__ void wave_add(unsigned long long* ctr, unsigned long long v) {
@@ -143,20 +144,21 @@ __device__ __forceinline__ bool tile_pixel(const DevParams& p, uint32_t& px, uin
 
 // A finished pixel, wherever it comes from: the light sum as it is into rgb_linear, and into rgb8 Reinhard + gamma (:391-398), the
 // quantiser (:447-449) and the black -> background rule (:518, drawImage:476-487).  lit = false (a miss, a ray without a hit): no tone
-// map, the background bytes.  Either output may be absent.
+// map, the background bytes.  Either output may be absent.  The three channels' quantised tone map is quant_tone's (srt_device.h): decided
+// by the f32 filter where its margin allows, by quant1(tone1()) where not -- or everywhere under exp & EXP_EXACT_TONE; the same bytes.
 __device__ __forceinline__ void store_pixel(float* __restrict__ rgb_linear, uint8_t* __restrict__ rgb8, const size_t pix, const V3 sum, const bool lit,
-                                            const float reinhard, const float gamma, const uint32_t bg) {
+                                            const float reinhard, const float gamma, const uint32_t bg, const uint32_t exp) {
     if (rgb_linear) { rgb_linear[pix * 3] = sum.x; rgb_linear[pix * 3 + 1] = sum.y; rgb_linear[pix * 3 + 2] = sum.z; }
     if (rgb8) {
-        int q0 = 0, q1 = 0, q2 = 0;
-        if (lit) { q0 = quant1(tone1(sum.x, reinhard, gamma)); q1 = quant1(tone1(sum.y, reinhard, gamma)); q2 = quant1(tone1(sum.z, reinhard, gamma)); }
-        if ((q0 | q1 | q2) == 0) { q0 = bg & 255; q1 = (bg >> 8) & 255; q2 = (bg >> 16) & 255; }
-        rgb8[pix * 3] = (uint8_t)q0; rgb8[pix * 3 + 1] = (uint8_t)q1; rgb8[pix * 3 + 2] = (uint8_t)q2;
+        int q[3] = {0, 0, 0};
+        if (lit) { const float c[3] = {sum.x, sum.y, sum.z}; quant_tone<3>(c, reinhard, gamma, (exp & EXP_EXACT_TONE) != 0u, q); }
+        if ((q[0] | q[1] | q[2]) == 0) { q[0] = bg & 255; q[1] = (bg >> 8) & 255; q[2] = (bg >> 16) & 255; }
+        rgb8[pix * 3] = (uint8_t)q[0]; rgb8[pix * 3 + 1] = (uint8_t)q[1]; rgb8[pix * 3 + 2] = (uint8_t)q[2];
     }
 }
 // A miss is final where it is found: zero light sum, background pixel.
 __device__ __forceinline__ void store_miss(float* __restrict__ rgb_linear, uint8_t* __restrict__ rgb8, const size_t pix, const uint32_t bg) {
-    store_pixel(rgb_linear, rgb8, pix, mk(0.0f, 0.0f, 0.0f), false, 0.0f, 0.0f, bg);
+    store_pixel(rgb_linear, rgb8, pix, mk(0.0f, 0.0f, 0.0f), false, 0.0f, 0.0f, bg, 0u);
 }
 
 // =================================================================================================
@@ -1153,7 +1155,7 @@ __global__ __launch_bounds__(256) void k_shade(DevScene s, DevParams p, const in
                 return any_hit_range<COUNT, false>(s, self, dt, L - dt, n_node, n_tri);
             });
         }
-        store_pixel(rgb_linear, rgb8, pix, sum, is_hit, p.reinhard, p.gamma, p.bg);
+        store_pixel(rgb_linear, rgb8, pix, sum, is_hit, p.reinhard, p.gamma, p.bg, p.exp);
     }
     count_hits(counters, is_hit, blockIdx.y * gridDim.x + blockIdx.x);
     if (COUNT) { wave_add(counters + 3, n_node); wave_add(counters + 4, n_tri); }
@@ -1618,7 +1620,7 @@ __device__ __forceinline__ void shade_hit_pixel(const DevScene& s, const DevPara
     const Surface f = surface_at(s, id, o, d, t, p.smooth != 0u);
     V3 sum = mk(0.0f, 0.0f, 0.0f);
     add_light_samples<INT_SHIN>(sum, f, o, d, t, p.lights, 0u, p.n_lights, p.shadow_div, shadowed);
-    store_pixel(rgb_linear, rgb8, (size_t)r * p.W + px, sum, true, p.reinhard, p.gamma, p.bg);
+    store_pixel(rgb_linear, rgb8, (size_t)r * p.W + px, sum, true, p.reinhard, p.gamma, p.bg, p.exp);
 }
 
 // =================================================================================================
@@ -1905,7 +1907,7 @@ __global__ __launch_bounds__(256) void k_resolve(DevParams p, const float* __res
     const uint32_t i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n_pixels || !resolve_live(p, i)) return;
     const V3 a = mk(acc[(size_t)i * 3] / spp, acc[(size_t)i * 3 + 1] / spp, acc[(size_t)i * 3 + 2] / spp);
-    store_pixel(rgb_linear, rgb8, (size_t)i, a, true, p.reinhard, p.gamma, p.bg);
+    store_pixel(rgb_linear, rgb8, (size_t)i, a, true, p.reinhard, p.gamma, p.bg, p.exp);
 }
 
 // =================================================================================================
@@ -2313,4 +2315,64 @@ __global__ void k_kat_tonemap(uint32_t n, const float* __restrict__ lin, float r
     if (i >= 3 * n) return;
     const float c = tone1(lin[i], reinhard, gamma);
     tone[i] = c; q[i] = quant1(c);
+}
+// The tone map's filter (quant_tone, srt_device.h) beside what it replaces.  Values go through quant_tone three at a time, as store_pixel's
+// do (the last triple repeats the last value): q = what store_pixel writes, q_filter = the filter's candidate (-1 where it decided
+// nothing), decided = 1 where the filter alone decided.
+__global__ void k_kat_tone_filter(uint32_t n, const float* __restrict__ lin, float reinhard, float gamma, int32_t* __restrict__ q, int32_t* __restrict__ q_filter,
+                                  uint8_t* __restrict__ decided) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (3ull * i >= n) return;
+    const uint32_t i0 = 3u * i, i1 = i0 + 1u < n ? i0 + 1u : n - 1u, i2 = i0 + 2u < n ? i0 + 2u : n - 1u;
+    const float c[3] = {lin[i0], lin[i1], lin[i2]};
+    const uint32_t at[3] = {i0, i1, i2};
+    int e[3];
+    quant_tone<3>(c, reinhard, gamma, false, e);
+    const ToneFilter f = tone_filter(reinhard, gamma);
+    for (int k = 0; k < 3; k++) {
+        int qf; float cand, rel;
+        const bool dec = tone_candidate(f, c[k], reinhard, gamma, qf, cand, rel);
+        q[at[k]] = e[k]; q_filter[at[k]] = dec ? qf : -1; decided[at[k]] = dec ? 1 : 0;
+    }
+}
+// Every float whose bit pattern is first + [0, count) through both forms, reduced here: out[0] values, [1] undecided by the filter,
+// [2] decided and different from quant1(tone1()), [3] quant_tone's result (after the fallback) different from it, [4] the largest
+// |cand / s - 1| over decided values, s = tone1() * 255 in f32 as quant1 forms it, [5] the largest of that deviation over the shipped
+// margin rel (a double's bits each: non-negative doubles order as their bits do).  [4] and [5] leave out s < 1e-30: both forms are far
+// below 1 there, and beneath 3e-36 the tone itself is a subnormal whose rounding is no longer relative.  One atomic per workgroup and
+// figure (2,048 workgroups at most).
+__global__ __launch_bounds__(256) void k_kat_tone_sweep(uint32_t first, unsigned long long count, float reinhard, float gamma, unsigned long long* __restrict__ out) {
+    __shared__ unsigned long long part[4][6];
+    const ToneFilter f = tone_filter(reinhard, gamma);
+    unsigned long long v[6] = {0ull, 0ull, 0ull, 0ull, 0ull, 0ull};
+    double dev = 0.0, ratio = 0.0;
+    const unsigned long long stride = (unsigned long long)gridDim.x * 256ull;
+    for (unsigned long long i = (unsigned long long)blockIdx.x * 256ull + threadIdx.x; i < count; i += stride) {
+        const float c[1] = {__uint_as_float(first + (uint32_t)i)};
+        const float tone = tone1(c[0], reinhard, gamma), s = tone * 255.0f;
+        const int exact = quant1(tone);
+        int qf, e[1]; float cand, rel;
+        const bool dec = tone_candidate(f, c[0], reinhard, gamma, qf, cand, rel);
+        quant_tone<1>(c, reinhard, gamma, false, e);
+        v[0]++; v[1] += dec ? 0u : 1u; v[2] += (dec && qf != exact) ? 1u : 0u; v[3] += e[0] != exact ? 1u : 0u;
+        if (dec && s >= 1.0e-30f) {
+            const double dv = __builtin_fabs((double)cand / (double)s - 1.0), rt = dv / (double)rel;
+            dev = dv > dev ? dv : dev; ratio = rt > ratio ? rt : ratio;
+        }
+    }
+    v[4] = (unsigned long long)__double_as_longlong(dev); v[5] = (unsigned long long)__double_as_longlong(ratio);
+    for (int k = 0; k < 6; k++)
+        for (int off = 32; off > 0; off >>= 1) {
+            const unsigned long long o = __shfl_xor(v[k], off, 64);
+            v[k] = k < 4 ? v[k] + o : (o > v[k] ? o : v[k]);
+        }
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) for (int k = 0; k < 6; k++) part[wave][k] = v[k];
+    __syncthreads();
+    if (threadIdx.x < 6) {
+        const int k = threadIdx.x;
+        unsigned long long a = part[0][k];
+        for (int w = 1; w < 4; w++) a = k < 4 ? a + part[w][k] : (part[w][k] > a ? part[w][k] : a);
+        if (k < 4) atomicAdd(out + k, a); else atomicMax(out + k, a);
+    }
 }

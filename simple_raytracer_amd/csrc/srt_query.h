@@ -565,7 +565,7 @@ __global__ __launch_bounds__(256) void k_query_shade(DevScene s, uint32_t n_rays
         }
         __builtin_amdgcn_wave_barrier();
     }
-    if (live) store_pixel(rgb_linear, rgb8, ri, sum, is_hit, p.reinhard, p.gamma, p.bg);
+    if (live) store_pixel(rgb_linear, rgb8, ri, sum, is_hit, p.reinhard, p.gamma, p.bg, 0u);
     if (counters) count_hits(counters, is_hit, blockIdx.x);
     if (COUNT) { wave_add(counters + 1, n_node); wave_add(counters + 2, n_tri); wave_add(counters + 3, n_node_s); wave_add(counters + 4, n_tri_s); }
 }
@@ -1133,7 +1133,7 @@ __device__ __forceinline__ void query_path_rays(const DevScene& s, const uint32_
     const V3 acc = path_segments<COUNT, SMOOTH, INT_SHIN, SHADOW, MASK, REFRACT, FRESNEL>(s, p, path, seg, n, ri, live, o, d, t_min, t_max, lane, q_all[wave],
                                                                                           best_all + wave * 64, ray_all[wave], ray_of, counters, blockIdx.x, hit0, n_node, n_tri,
                                                                                           n_node_s, n_tri_s, rule, qm, ior, fr);
-    if (live) store_pixel(rgb_linear, rgb8, ri, acc, hit0, p.reinhard, p.gamma, p.bg);
+    if (live) store_pixel(rgb_linear, rgb8, ri, acc, hit0, p.reinhard, p.gamma, p.bg, 0u);
     if (COUNT) { wave_add(counters + 1, n_node); wave_add(counters + 2, n_tri); wave_add(counters + 3, n_node_s); wave_add(counters + 4, n_tri_s); }
 }
 template <bool COUNT, bool SMOOTH, bool INT_SHIN>
@@ -1224,7 +1224,7 @@ __device__ __forceinline__ void render_path_pixels(const DevScene& s, DevParams&
         else total = mk(total.x + acc.x, total.y + acc.y, total.z + acc.z);
     }
     if (spp > 1) { const float f = (float)spp; total = mk(total.x / f, total.y / f, total.z / f); hit0 = true; }
-    if (live) store_pixel(rgb_linear, rgb8, ri, total, hit0, p.reinhard, p.gamma, p.bg);
+    if (live) store_pixel(rgb_linear, rgb8, ri, total, hit0, p.reinhard, p.gamma, p.bg, 0u);
     if (COUNT) { wave_add(counters + 1, n_node); wave_add(counters + 2, n_tri); wave_add(counters + 3, n_node_s); wave_add(counters + 4, n_tri_s); }
 }
 template <bool COUNT, bool SMOOTH, bool INT_SHIN>

@@ -19,6 +19,7 @@ LIB_PATH = os.path.join(_HERE, "libsrt_hip.so")
 ABI_SYMBOLS = ("srt_params_default", "srt_light_staircase", "srt_rows_owned", "srt_cols_owned", "srt_scene_create", "srt_scene_destroy", "srt_scene_update", "srt_scene_share",
                "srt_render_device", "srt_render_device_batch", "srt_render", "srt_render_async", "srt_host_alloc", "srt_host_free", "srt_sync", "srt_scene_device_bytes", "srt_strerror",
                "srt_last_hip_error", "srt_abi_version", "srt_kat_ray_aabb", "srt_kat_ray_triangle", "srt_kat_phong", "srt_kat_tonemap", "srt_kat_interp_normal", "srt_kat_pow",
+               "srt_kat_tone_filter", "srt_kat_tone_filter_sweep",
                "srt_kat_ray_triangle_origin", "srt_kat_barycentric", "srt_debug_fail_host_allocs", "srt_debug_valu_rate", "srt_debug_scene_records", "srt_scene_set_source", "srt_scene_update_frame",
                "srt_scene_pipeline", "srt_scene_overlap_estimate", "srt_scene_set_pose_source", "srt_scene_pose",
                "srt_scene_refit_prepare", "srt_scene_refit_device",
@@ -216,6 +217,8 @@ def load(path=None):
         L.srt_kat_interp_normal.argtypes = [C.c_int, C.c_uint32, _f32p, _f32p]
         L.srt_kat_pow.argtypes = [C.c_int, C.c_uint32, _f32p, _f32p, _f32p, _f32p]
         L.srt_kat_tonemap.argtypes = [C.c_int, C.c_uint32, _f32p, C.c_float, C.c_float, _f32p, _i32p]
+        L.srt_kat_tone_filter.argtypes = [C.c_int, C.c_uint32, _f32p, C.c_float, C.c_float, _i32p, _i32p, _u8p]
+        L.srt_kat_tone_filter_sweep.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_float, C.c_float, C.POINTER(C.c_double)]
         if path is not None:
             return L
         _lib = L
@@ -980,6 +983,26 @@ def kat_tonemap(lin, reinhard=0.5, gamma=1.1, device=0):
     tone = np.empty((n, 3), np.float32); q = np.empty((n, 3), np.int32)
     _check(L.srt_kat_tonemap(device, n, lin.ctypes.data_as(_f32p), reinhard, gamma, tone.ctypes.data_as(_f32p), q.ctypes.data_as(_i32p)), "srt_kat_tonemap")
     return tone, q
+
+
+def kat_tone_filter(lin, reinhard=0.5, gamma=1.1, device=0):
+    """(q, q_filter, decided) per value of `lin` (flat): the quantised tone map as the shading kernels compute it, the f32 filter's own
+    candidate (-1 where it decided nothing) and whether the filter alone decided (srt_kat_tone_filter)."""
+    L = load(); lin = _f(lin).reshape(-1); n = lin.shape[0]
+    q = np.empty(n, np.int32); qf = np.empty(n, np.int32); dec = np.empty(n, np.uint8)
+    _check(L.srt_kat_tone_filter(device, n, lin.ctypes.data_as(_f32p), reinhard, gamma, q.ctypes.data_as(_i32p), qf.ctypes.data_as(_i32p), dec.ctypes.data_as(_u8p)),
+           "srt_kat_tone_filter")
+    return q, qf, dec.astype(bool)
+
+
+def kat_tone_filter_sweep(first_bits, last_bits, reinhard=0.5, gamma=1.1, device=0):
+    """Every float with a bit pattern in [first_bits, last_bits] through the filter and the exact functions on the device
+    (srt_kat_tone_filter_sweep): dict of values, undecided, decided_different, results_different, max_deviation, max_deviation_over_margin."""
+    L = load()
+    out = (C.c_double * 6)()
+    _check(L.srt_kat_tone_filter_sweep(device, first_bits, last_bits, reinhard, gamma, out), "srt_kat_tone_filter_sweep")
+    return {"values": int(out[0]), "undecided": int(out[1]), "decided_different": int(out[2]), "results_different": int(out[3]),
+            "max_deviation": float(out[4]), "max_deviation_over_margin": float(out[5])}
 
 
 def kat_interp_normal(in12, device=0):

@@ -9,7 +9,8 @@ Usage: python tools/kernel_regs.py [substring ...]
                                                 of .text that the kernel's own symbol covers (address and size from the symbol table).
                                                 A kernel that merely moves because an earlier one changed length keeps its digest:
                                                 branches inside a kernel are relative; a pc-relative reference to something OUTSIDE the
-                                                kernel would change it (these kernels are fully inlined and make none).
+                                                kernel would change it (the kernels that store lit pixels make one: the call
+                                                of quant_tone_exact, srt_device.h; every other kernel is fully inlined).
        python tools/kernel_regs.py --compare OTHER.so [substring ...]
                                                 the same per kernel for two builds side by side, OTHER.so first: identical or not,
                                                 VGPR / SGPR / scratch / LDS / spills of both
