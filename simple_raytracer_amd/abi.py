@@ -1,4 +1,5 @@
-"""ctypes mirror of include/srt.h (PODs only) and a numpy container for the flat scene.
+"""ctypes mirror of include/srt.h -- its structs (STRUCTS), constants (SRT_*) and prototypes (PROTOTYPES), checked against the header by
+tests/test_abi_mirror.py -- and a numpy container for the flat scene.
 
 The flat scene is the reference's ObjectManager state (Object.h:59-89 in the reference) written out as
 arrays; see include/srt.h for the layout contract.  This module holds no compute.
@@ -10,6 +11,7 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
+SRT_ABI_VERSION = 3
 SRT_OK = 0
 SRT_ERR_ARG, SRT_ERR_LAYOUT, SRT_ERR_DEVICE, SRT_ERR_NO_GPU, SRT_ERR_TEXTURE, SRT_ERR_LIMIT, SRT_ERR_OOM = 1, 2, 3, 4, 5, 6, 7
 SRT_FLAG_SMOOTH_NORMALS = 1 << 0
@@ -85,6 +87,7 @@ class SurfaceOut(C.Structure):
     _fields_ = [("obj", C.c_void_p), ("point", C.c_void_p), ("normal", C.c_void_p), ("color", C.c_void_p), ("material", C.c_void_p), ("bounce", C.c_void_p)]
 
 
+SRT_MULTI_HIT_MAX = 16
 SRT_PATH_DEPTH_MAX = 8
 
 
@@ -194,6 +197,122 @@ PATH_FIELDS = {"hit_id": (np.int32, 1), "t": (np.float32, 1), "obj": (np.int32, 
 # the fields of srt_surface_out: name -> (dtype, floats or ints per ray)
 SURFACE_FIELDS = {"obj": (np.int32, 1), "point": (np.float32, 3), "normal": (np.float32, 3), "color": (np.float32, 3), "material": (np.float32, 3),
                   "bounce": (np.float32, 6)}
+
+
+# every struct of include/srt.h: its name there -> its class here
+STRUCTS = {"srt_scene_desc": SceneDesc, "srt_params": Params, "srt_stats": Stats, "srt_frame_geometry": FrameGeometry, "srt_refit_desc": RefitDesc,
+           "srt_surface_out": SurfaceOut, "srt_path_desc": PathDesc, "srt_path_out": PathOut, "srt_shadow_rule": ShadowRule, "srt_visibility": Visibility,
+           "srt_refraction": Refraction, "srt_fresnel_out": FresnelOut, "srt_fresnel": Fresnel, "srt_ao_desc": AoDesc, "srt_ao_out": AoOut,
+           "srt_ao_frame": AoFrame, "srt_ao_frame_out": AoFrameOut}
+
+
+# ---- the prototypes of include/srt.h, in its order: name -> (restype, [argtypes]) ----
+# srt_scene*, void* and every address that travels as an int (the d_* parameters, a stream, srt_render_async's outputs) are c_void_p;
+# srt_scene** and T* const* are POINTER(c_void_p); a pointer to an srt_ struct is POINTER(its class); a scalar is its exact ctype.
+_int, _u32, _f32, _vp = C.c_int, C.c_uint32, C.c_float, C.c_void_p
+_vpp, _f64p = C.POINTER(C.c_void_p), C.POINTER(C.c_double)
+_desc, _geom, _refit, _par, _stats = C.POINTER(SceneDesc), C.POINTER(FrameGeometry), C.POINTER(RefitDesc), C.POINTER(Params), C.POINTER(Stats)
+_surf, _path, _seg, _rule, _vis = C.POINTER(SurfaceOut), C.POINTER(PathDesc), C.POINTER(PathOut), C.POINTER(ShadowRule), C.POINTER(Visibility)
+_refr, _fres = C.POINTER(Refraction), C.POINTER(Fresnel)
+_ao, _aout, _afr, _afout = C.POINTER(AoDesc), C.POINTER(AoOut), C.POINTER(AoFrame), C.POINTER(AoFrameOut)
+
+PROTOTYPES = {
+    "srt_params_default": (None, [_par, _u32, _u32]),
+    "srt_light_staircase": (None, [_f32p, _u32, _f32p]),
+    "srt_rows_owned": (_u32, [_par]),
+    "srt_cols_owned": (_u32, [_par]),
+    "srt_scene_create": (_int, [_int, _desc, _vpp]),
+    "srt_scene_destroy": (_int, [_vp]),
+    "srt_scene_share": (_int, [_vp, _vpp]),
+    "srt_scene_update": (_int, [_vp, _desc, _vp]),
+    "srt_scene_set_source": (_int, [_vp, _f32p, _f32p, _i32p]),
+    "srt_scene_update_frame": (_int, [_vp, _geom, _vp]),
+    "srt_scene_set_pose_source": (_int, [_vp, _f32p]),
+    "srt_scene_pose": (_int, [_vp, _u32, _f32p, _f32p, _f32p, _vp]),
+    "srt_scene_refit_prepare": (_int, [_vp, _u32, _u32p]),
+    "srt_scene_refit_device": (_int, [_vp, _refit, _vp]),
+    "srt_render_device": (_int, [_vp, _par, _vp, _vp, _vp, _vp, _vp]),
+    "srt_render_device_batch": (_int, [_u32, _vpp, _par, _vp, _vpp, _vpp, _vpp, _vpp]),
+    "srt_render": (_int, [_vp, _par, _i32p, _f32p, _f32p, _u8p, _stats]),
+    "srt_render_async": (_int, [_vp, _par, _vp, _vp, _vp, _vp]),
+    "srt_host_alloc": (_vp, [C.c_size_t]),
+    "srt_host_free": (None, [_vp]),
+    "srt_sync": (_int, [_vp, _stats]),
+    "srt_trace_rays_device": (_int, [_vp, _u32, _vp, _u32, _vp, _vp, _vp, _vp]),
+    "srt_trace_rays": (_int, [_vp, _u32, _f32p, _u32, _i32p, _f32p, _f32p, _stats]),
+    "srt_occluded_device": (_int, [_vp, _u32, _vp, _vp, _vp, _vp]),
+    "srt_occluded": (_int, [_vp, _u32, _f32p, _i32p, _u8p]),
+    "srt_trace_rays_range_device": (_int, [_vp, _u32, _vp, _vp, _u32, _vp, _vp, _vp, _vp]),
+    "srt_trace_rays_range": (_int, [_vp, _u32, _f32p, _f32p, _u32, _i32p, _f32p, _f32p, _stats]),
+    "srt_occluded_range_device": (_int, [_vp, _u32, _vp, _vp, _vp, _vp, _vp]),
+    "srt_occluded_range": (_int, [_vp, _u32, _f32p, _f32p, _i32p, _u8p]),
+    "srt_trace_rays_multi_device": (_int, [_vp, _u32, _vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _vp]),
+    "srt_trace_rays_multi": (_int, [_vp, _u32, _f32p, _f32p, _u32, _u32, _u32p, _i32p, _f32p, _f32p, _stats]),
+    "srt_shade_rays_device": (_int, [_vp, _u32, _vp, _par, _vp, _vp, _vp, _vp, _vp]),
+    "srt_shade_rays": (_int, [_vp, _u32, _f32p, _par, _i32p, _f32p, _f32p, _u8p, _stats]),
+    "srt_shade_rays_range_device": (_int, [_vp, _u32, _vp, _vp, _par, _vp, _vp, _vp, _vp, _vp]),
+    "srt_shade_rays_range": (_int, [_vp, _u32, _f32p, _f32p, _par, _i32p, _f32p, _f32p, _u8p, _stats]),
+    "srt_surface_rays_device": (_int, [_vp, _u32, _vp, _vp, _u32, _vp, _vp, _vp, _surf]),
+    "srt_surface_rays": (_int, [_vp, _u32, _f32p, _f32p, _u32, _i32p, _f32p, _surf, _stats]),
+    "srt_surface_hits_device": (_int, [_vp, _u32, _vp, _vp, _vp, _u32, _vp, _surf]),
+    "srt_surface_hits": (_int, [_vp, _u32, _f32p, _i32p, _f32p, _u32, _surf]),
+    "srt_shade_paths_device": (_int, [_vp, _u32, _vp, _vp, _par, _path, _vp, _vp, _vp, _seg]),
+    "srt_shade_paths": (_int, [_vp, _u32, _f32p, _f32p, _par, _path, _f32p, _u8p, _seg, _stats]),
+    "srt_render_paths_device": (_int, [_vp, _par, _path, _vp, _vp, _vp, _seg]),
+    "srt_render_paths": (_int, [_vp, _par, _path, _f32p, _u8p, _seg, _stats]),
+}
+
+
+def _path_family(form, base, after, new):
+    """The four srt_{shade,render}_paths<form>{_device,} calls: those of the form `base` with one argument more, of type `new`, right
+    after their argument of type `after` (the header: "the same, plus ...")."""
+    for stem in ("srt_shade_paths", "srt_render_paths"):
+        for suffix in ("_device", ""):
+            restype, args = PROTOTYPES[stem + base + suffix]
+            at = args.index(after) + 1
+            PROTOTYPES[stem + form + suffix] = (restype, args[:at] + [new] + args[at:])
+
+
+_path_family("_shadow", "", after=_path, new=_rule)         # ..., const srt_path_desc* path, const srt_shadow_rule* shadow, ...
+PROTOTYPES.update({
+    "srt_scene_set_object_masks": (_int, [_vp, _u32, _u32p, _vp]),
+    "srt_trace_rays_masked_device": (_int, [_vp, _u32, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp]),
+    "srt_trace_rays_masked": (_int, [_vp, _u32, _f32p, _f32p, _u32p, _u32, _i32p, _f32p, _f32p, _stats]),
+    "srt_occluded_masked_device": (_int, [_vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "srt_occluded_masked": (_int, [_vp, _u32, _f32p, _f32p, _u32p, _i32p, _u8p]),
+})
+_path_family("_masked", "_shadow", after=_rule, new=_vis)   # ..., const srt_shadow_rule* shadow, const srt_visibility* vis, ...
+_path_family("_refract", "_masked", after=_vis, new=_refr)  # ..., const srt_visibility* vis, const srt_refraction* refr, ...
+_path_family("_fresnel", "_refract", after=_refr, new=_fres)  # ..., const srt_refraction* refr, const srt_fresnel* fres, ...
+PROTOTYPES.update({
+    "srt_ao_rays_device": (_int, [_vp, _u32, _vp, _vp, _u32, _ao, _vis, _vp, _vp, _vp, _aout]),
+    "srt_ao_rays": (_int, [_vp, _u32, _f32p, _f32p, _u32, _ao, _vis, _i32p, _f32p, _aout, _stats]),
+    "srt_ao_hits_device": (_int, [_vp, _u32, _vp, _vp, _vp, _u32, _ao, _vis, _vp, _aout]),
+    "srt_ao_hits": (_int, [_vp, _u32, _f32p, _i32p, _f32p, _u32, _ao, _vis, _aout, _stats]),
+    "srt_render_ao_device": (_int, [_vp, _par, _u32, _ao, _afr, _vis, _vp, _vp, _vp, _afout]),
+    "srt_render_ao": (_int, [_vp, _par, _u32, _ao, _afr, _vis, _i32p, _f32p, _afout, _stats]),
+    "srt_render_ao_hits_device": (_int, [_vp, _par, _vp, _vp, _u32, _ao, _afr, _vis, _vp, _afout]),
+    "srt_render_ao_hits": (_int, [_vp, _par, _i32p, _f32p, _u32, _ao, _afr, _vis, _afout, _stats]),
+    "srt_scene_device_bytes": (C.c_uint64, [_vp]),
+    "srt_scene_pipeline": (C.c_char_p, [_vp]),
+    "srt_scene_overlap_estimate": (C.c_double, [_vp]),
+    "srt_kat_ray_aabb": (_int, [_int, _u32, _f32p, _f32p, _u8p, _u8p, _u8p, _u8p]),
+    "srt_kat_ray_triangle": (_int, [_int, _u32, _f32p, _f32p, _f32p]),
+    "srt_kat_ray_triangle_origin": (_int, [_int, _u32, _f32p, _f32p, _f32p]),
+    "srt_kat_barycentric": (_int, [_int, _u32, _f32p, _f32p]),
+    "srt_kat_phong": (_int, [_int, _u32, _f32p, _f32p]),
+    "srt_kat_interp_normal": (_int, [_int, _u32, _f32p, _f32p]),
+    "srt_kat_pow": (_int, [_int, _u32, _f32p, _f32p, _f32p, _f32p]),
+    "srt_kat_tonemap": (_int, [_int, _u32, _f32p, _f32, _f32, _f32p, _i32p]),
+    "srt_kat_tone_filter": (_int, [_int, _u32, _f32p, _f32, _f32, _i32p, _i32p, _u8p]),
+    "srt_kat_tone_filter_sweep": (_int, [_int, _u32, _u32, _f32, _f32, _f64p]),
+    "srt_debug_valu_rate": (_int, [_int, _u32, _f64p]),
+    "srt_debug_scene_records": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _f32p, _f32p, _i32p]),
+    "srt_debug_fail_host_allocs": (None, [_int]),
+    "srt_strerror": (C.c_char_p, [_int]),
+    "srt_last_hip_error": (_int, []),
+    "srt_abi_version": (_u32, []),
+})
 
 
 def _ptr(a, ty):

@@ -15,26 +15,8 @@ from . import abi
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libsrt_hip.so")
 
-# every symbol include/srt.h declares
-ABI_SYMBOLS = ("srt_params_default", "srt_light_staircase", "srt_rows_owned", "srt_cols_owned", "srt_scene_create", "srt_scene_destroy", "srt_scene_update", "srt_scene_share",
-               "srt_render_device", "srt_render_device_batch", "srt_render", "srt_render_async", "srt_host_alloc", "srt_host_free", "srt_sync", "srt_scene_device_bytes", "srt_strerror",
-               "srt_last_hip_error", "srt_abi_version", "srt_kat_ray_aabb", "srt_kat_ray_triangle", "srt_kat_phong", "srt_kat_tonemap", "srt_kat_interp_normal", "srt_kat_pow",
-               "srt_kat_tone_filter", "srt_kat_tone_filter_sweep",
-               "srt_kat_ray_triangle_origin", "srt_kat_barycentric", "srt_debug_fail_host_allocs", "srt_debug_valu_rate", "srt_debug_scene_records", "srt_scene_set_source", "srt_scene_update_frame",
-               "srt_scene_pipeline", "srt_scene_overlap_estimate", "srt_scene_set_pose_source", "srt_scene_pose",
-               "srt_scene_refit_prepare", "srt_scene_refit_device",
-               "srt_trace_rays_device", "srt_trace_rays", "srt_occluded_device", "srt_occluded", "srt_shade_rays_device", "srt_shade_rays",
-               "srt_trace_rays_range_device", "srt_trace_rays_range", "srt_occluded_range_device", "srt_occluded_range",
-               "srt_trace_rays_multi_device", "srt_trace_rays_multi", "srt_shade_rays_range_device", "srt_shade_rays_range",
-               "srt_surface_rays_device", "srt_surface_rays", "srt_surface_hits_device", "srt_surface_hits", "srt_shade_paths_device", "srt_shade_paths",
-               "srt_render_paths_device", "srt_render_paths", "srt_shade_paths_shadow_device", "srt_shade_paths_shadow", "srt_render_paths_shadow_device",
-               "srt_render_paths_shadow", "srt_scene_set_object_masks", "srt_trace_rays_masked_device", "srt_trace_rays_masked", "srt_occluded_masked_device",
-               "srt_occluded_masked", "srt_shade_paths_masked_device", "srt_shade_paths_masked", "srt_render_paths_masked_device", "srt_render_paths_masked",
-               "srt_shade_paths_refract_device", "srt_shade_paths_refract", "srt_render_paths_refract_device", "srt_render_paths_refract",
-               "srt_shade_paths_fresnel_device", "srt_shade_paths_fresnel", "srt_render_paths_fresnel_device", "srt_render_paths_fresnel",
-               "srt_ao_rays_device", "srt_ao_rays", "srt_ao_hits_device", "srt_ao_hits",
-               "srt_render_ao_device", "srt_render_ao", "srt_render_ao_hits_device", "srt_render_ao_hits")
-MULTI_HIT_MAX = 16                # SRT_MULTI_HIT_MAX
+ABI_SYMBOLS = tuple(abi.PROTOTYPES)           # every symbol include/srt.h declares
+MULTI_HIT_MAX = abi.SRT_MULTI_HIT_MAX
 
 _f32p, _i32p, _u8p, _u32p = C.POINTER(C.c_float), C.POINTER(C.c_int32), C.POINTER(C.c_uint8), C.POINTER(C.c_uint32)
 _lib = None
@@ -57,168 +39,9 @@ def load(path=None):
             raise RuntimeError(f"{path or LIB_PATH} is missing: the HIP extension must be built "
                                "(python -m simple_raytracer_amd.build); there is no CPU fallback")
         L = C.CDLL(path or LIB_PATH)
-        L.srt_params_default.argtypes = [C.POINTER(abi.Params), C.c_uint32, C.c_uint32]
-        L.srt_params_default.restype = None
-        L.srt_light_staircase.argtypes = [_f32p, C.c_uint32, _f32p]
-        L.srt_light_staircase.restype = None
-        L.srt_rows_owned.argtypes = [C.POINTER(abi.Params)]
-        L.srt_rows_owned.restype = C.c_uint32
-        L.srt_cols_owned.argtypes = [C.POINTER(abi.Params)]
-        L.srt_cols_owned.restype = C.c_uint32
-        L.srt_scene_create.argtypes = [C.c_int, C.POINTER(abi.SceneDesc), C.POINTER(C.c_void_p)]
-        L.srt_scene_create.restype = C.c_int
-        L.srt_scene_update.argtypes = [C.c_void_p, C.POINTER(abi.SceneDesc), C.c_void_p]
-        L.srt_scene_update.restype = C.c_int
-        L.srt_scene_share.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
-        L.srt_scene_share.restype = C.c_int
-        L.srt_scene_destroy.argtypes = [C.c_void_p]
-        L.srt_scene_destroy.restype = C.c_int
-        L.srt_render_device.argtypes = [C.c_void_p, C.POINTER(abi.Params), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.srt_render_device.restype = C.c_int
-        L.srt_render_device_batch.argtypes = [C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(abi.Params), C.c_void_p] + [C.POINTER(C.c_void_p)] * 4
-        L.srt_render_device_batch.restype = C.c_int
-        L.srt_render.argtypes = [C.c_void_p, C.POINTER(abi.Params), _i32p, _f32p, _f32p, _u8p, C.POINTER(abi.Stats)]
-        L.srt_render.restype = C.c_int
-        L.srt_render_async.argtypes = [C.c_void_p, C.POINTER(abi.Params), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.srt_render_async.restype = C.c_int
-        L.srt_host_alloc.argtypes = [C.c_size_t]
-        L.srt_host_alloc.restype = C.c_void_p
-        L.srt_host_free.argtypes = [C.c_void_p]
-        L.srt_host_free.restype = None
-        L.srt_sync.argtypes = [C.c_void_p, C.POINTER(abi.Stats)]
-        L.srt_sync.restype = C.c_int
-        L.srt_scene_device_bytes.argtypes = [C.c_void_p]
-        L.srt_scene_device_bytes.restype = C.c_uint64
-        L.srt_scene_pipeline.argtypes = [C.c_void_p]
-        L.srt_scene_pipeline.restype = C.c_char_p
-        L.srt_scene_overlap_estimate.argtypes = [C.c_void_p]
-        L.srt_scene_overlap_estimate.restype = C.c_double
-        L.srt_scene_set_pose_source.argtypes = [C.c_void_p, _f32p]
-        L.srt_scene_set_pose_source.restype = C.c_int
-        L.srt_scene_pose.argtypes = [C.c_void_p, C.c_uint32, _f32p, _f32p, _f32p, C.c_void_p]
-        L.srt_scene_pose.restype = C.c_int
-        L.srt_scene_refit_prepare.argtypes = [C.c_void_p, C.c_uint32, _u32p]
-        L.srt_scene_refit_prepare.restype = C.c_int
-        L.srt_scene_refit_device.argtypes = [C.c_void_p, C.POINTER(abi.RefitDesc), C.c_void_p]
-        L.srt_scene_refit_device.restype = C.c_int
-        L.srt_trace_rays_device.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.srt_trace_rays_device.restype = C.c_int
-        L.srt_trace_rays.argtypes = [C.c_void_p, C.c_uint32, _f32p, C.c_uint32, _i32p, _f32p, _f32p, C.POINTER(abi.Stats)]
-        L.srt_trace_rays.restype = C.c_int
-        L.srt_occluded_device.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.srt_occluded_device.restype = C.c_int
-        L.srt_occluded.argtypes = [C.c_void_p, C.c_uint32, _f32p, _i32p, _u8p]
-        L.srt_occluded.restype = C.c_int
-        L.srt_trace_rays_range_device.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.srt_trace_rays_range_device.restype = C.c_int
-        L.srt_trace_rays_range.argtypes = [C.c_void_p, C.c_uint32, _f32p, _f32p, C.c_uint32, _i32p, _f32p, _f32p, C.POINTER(abi.Stats)]
-        L.srt_trace_rays_range.restype = C.c_int
-        L.srt_occluded_range_device.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.srt_occluded_range_device.restype = C.c_int
-        L.srt_occluded_range.argtypes = [C.c_void_p, C.c_uint32, _f32p, _f32p, _i32p, _u8p]
-        L.srt_occluded_range.restype = C.c_int
-        L.srt_trace_rays_multi_device.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                                  C.c_void_p]
-        L.srt_trace_rays_multi_device.restype = C.c_int
-        L.srt_trace_rays_multi.argtypes = [C.c_void_p, C.c_uint32, _f32p, _f32p, C.c_uint32, C.c_uint32, _u32p, _i32p, _f32p, _f32p, C.POINTER(abi.Stats)]
-        L.srt_trace_rays_multi.restype = C.c_int
-        L.srt_shade_rays_device.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(abi.Params), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.srt_shade_rays_device.restype = C.c_int
-        L.srt_shade_rays.argtypes = [C.c_void_p, C.c_uint32, _f32p, C.POINTER(abi.Params), _i32p, _f32p, _f32p, _u8p, C.POINTER(abi.Stats)]
-        L.srt_shade_rays.restype = C.c_int
-        L.srt_shade_rays_range_device.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(abi.Params), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                                  C.c_void_p]
-        L.srt_shade_rays_range_device.restype = C.c_int
-        L.srt_shade_rays_range.argtypes = [C.c_void_p, C.c_uint32, _f32p, _f32p, C.POINTER(abi.Params), _i32p, _f32p, _f32p, _u8p, C.POINTER(abi.Stats)]
-        L.srt_shade_rays_range.restype = C.c_int
-        L.srt_surface_rays_device.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(abi.SurfaceOut)]
-        L.srt_surface_rays_device.restype = C.c_int
-        L.srt_surface_rays.argtypes = [C.c_void_p, C.c_uint32, _f32p, _f32p, C.c_uint32, _i32p, _f32p, C.POINTER(abi.SurfaceOut), C.POINTER(abi.Stats)]
-        L.srt_surface_rays.restype = C.c_int
-        L.srt_surface_hits_device.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(abi.SurfaceOut)]
-        L.srt_surface_hits_device.restype = C.c_int
-        L.srt_surface_hits.argtypes = [C.c_void_p, C.c_uint32, _f32p, _i32p, _f32p, C.c_uint32, C.POINTER(abi.SurfaceOut)]
-        L.srt_surface_hits.restype = C.c_int
-        L.srt_shade_paths_device.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(abi.Params), C.POINTER(abi.PathDesc), C.c_void_p, C.c_void_p,
-                                             C.c_void_p, C.POINTER(abi.PathOut)]
-        L.srt_shade_paths_device.restype = C.c_int
-        L.srt_shade_paths.argtypes = [C.c_void_p, C.c_uint32, _f32p, _f32p, C.POINTER(abi.Params), C.POINTER(abi.PathDesc), _f32p, _u8p, C.POINTER(abi.PathOut),
-                                      C.POINTER(abi.Stats)]
-        L.srt_shade_paths.restype = C.c_int
-        L.srt_render_paths_device.argtypes = [C.c_void_p, C.POINTER(abi.Params), C.POINTER(abi.PathDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(abi.PathOut)]
-        L.srt_render_paths_device.restype = C.c_int
-        L.srt_render_paths.argtypes = [C.c_void_p, C.POINTER(abi.Params), C.POINTER(abi.PathDesc), _f32p, _u8p, C.POINTER(abi.PathOut), C.POINTER(abi.Stats)]
-        L.srt_render_paths.restype = C.c_int
-        # the same four under a shadow rule: one srt_shadow_rule* after the path
-        _rule = C.POINTER(abi.ShadowRule)
-        L.srt_shade_paths_shadow_device.argtypes = L.srt_shade_paths_device.argtypes[:6] + [_rule] + L.srt_shade_paths_device.argtypes[6:]
-        L.srt_shade_paths_shadow.argtypes = L.srt_shade_paths.argtypes[:6] + [_rule] + L.srt_shade_paths.argtypes[6:]
-        L.srt_render_paths_shadow_device.argtypes = L.srt_render_paths_device.argtypes[:3] + [_rule] + L.srt_render_paths_device.argtypes[3:]
-        L.srt_render_paths_shadow.argtypes = L.srt_render_paths.argtypes[:3] + [_rule] + L.srt_render_paths.argtypes[3:]
-        for f in (L.srt_shade_paths_shadow_device, L.srt_shade_paths_shadow, L.srt_render_paths_shadow_device, L.srt_render_paths_shadow):
-            f.restype = C.c_int
-        # visibility masks: the table, a ray_mask after t_range, one srt_visibility* after the shadow rule
-        L.srt_scene_set_object_masks.argtypes = [C.c_void_p, C.c_uint32, _u32p, C.c_void_p]
-        L.srt_trace_rays_masked_device.argtypes = L.srt_trace_rays_range_device.argtypes[:4] + [C.c_void_p] + L.srt_trace_rays_range_device.argtypes[4:]
-        L.srt_trace_rays_masked.argtypes = L.srt_trace_rays_range.argtypes[:4] + [_u32p] + L.srt_trace_rays_range.argtypes[4:]
-        L.srt_occluded_masked_device.argtypes = L.srt_occluded_range_device.argtypes[:4] + [C.c_void_p] + L.srt_occluded_range_device.argtypes[4:]
-        L.srt_occluded_masked.argtypes = L.srt_occluded_range.argtypes[:4] + [_u32p] + L.srt_occluded_range.argtypes[4:]
-        _vis = C.POINTER(abi.Visibility)
-        L.srt_shade_paths_masked_device.argtypes = L.srt_shade_paths_shadow_device.argtypes[:7] + [_vis] + L.srt_shade_paths_shadow_device.argtypes[7:]
-        L.srt_shade_paths_masked.argtypes = L.srt_shade_paths_shadow.argtypes[:7] + [_vis] + L.srt_shade_paths_shadow.argtypes[7:]
-        L.srt_render_paths_masked_device.argtypes = L.srt_render_paths_shadow_device.argtypes[:4] + [_vis] + L.srt_render_paths_shadow_device.argtypes[4:]
-        L.srt_render_paths_masked.argtypes = L.srt_render_paths_shadow.argtypes[:4] + [_vis] + L.srt_render_paths_shadow.argtypes[4:]
-        for f in (L.srt_scene_set_object_masks, L.srt_trace_rays_masked_device, L.srt_trace_rays_masked, L.srt_occluded_masked_device, L.srt_occluded_masked,
-                  L.srt_shade_paths_masked_device, L.srt_shade_paths_masked, L.srt_render_paths_masked_device, L.srt_render_paths_masked):
-            f.restype = C.c_int
-        # refracting paths: one srt_refraction* after the srt_visibility*
-        _refr = C.POINTER(abi.Refraction)
-        L.srt_shade_paths_refract_device.argtypes = L.srt_shade_paths_masked_device.argtypes[:8] + [_refr] + L.srt_shade_paths_masked_device.argtypes[8:]
-        L.srt_shade_paths_refract.argtypes = L.srt_shade_paths_masked.argtypes[:8] + [_refr] + L.srt_shade_paths_masked.argtypes[8:]
-        L.srt_render_paths_refract_device.argtypes = L.srt_render_paths_masked_device.argtypes[:5] + [_refr] + L.srt_render_paths_masked_device.argtypes[5:]
-        L.srt_render_paths_refract.argtypes = L.srt_render_paths_masked.argtypes[:5] + [_refr] + L.srt_render_paths_masked.argtypes[5:]
-        for f in (L.srt_shade_paths_refract_device, L.srt_shade_paths_refract, L.srt_render_paths_refract_device, L.srt_render_paths_refract):
-            f.restype = C.c_int
-        # the Fresnel split: one srt_fresnel* after the srt_refraction*
-        _fres = C.POINTER(abi.Fresnel)
-        L.srt_shade_paths_fresnel_device.argtypes = L.srt_shade_paths_refract_device.argtypes[:9] + [_fres] + L.srt_shade_paths_refract_device.argtypes[9:]
-        L.srt_shade_paths_fresnel.argtypes = L.srt_shade_paths_refract.argtypes[:9] + [_fres] + L.srt_shade_paths_refract.argtypes[9:]
-        L.srt_render_paths_fresnel_device.argtypes = L.srt_render_paths_refract_device.argtypes[:6] + [_fres] + L.srt_render_paths_refract_device.argtypes[6:]
-        L.srt_render_paths_fresnel.argtypes = L.srt_render_paths_refract.argtypes[:6] + [_fres] + L.srt_render_paths_refract.argtypes[6:]
-        for f in (L.srt_shade_paths_fresnel_device, L.srt_shade_paths_fresnel, L.srt_render_paths_fresnel_device, L.srt_render_paths_fresnel):
-            f.restype = C.c_int
-        # ambient occlusion: an srt_ao_desc* and an srt_visibility* after the flags, an srt_ao_out* last of the outputs
-        _ao, _aout = C.POINTER(abi.AoDesc), C.POINTER(abi.AoOut)
-        L.srt_ao_rays_device.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, _ao, _vis, C.c_void_p, C.c_void_p, C.c_void_p, _aout]
-        L.srt_ao_rays.argtypes = [C.c_void_p, C.c_uint32, _f32p, _f32p, C.c_uint32, _ao, _vis, _i32p, _f32p, _aout, C.POINTER(abi.Stats)]
-        L.srt_ao_hits_device.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, _ao, _vis, C.c_void_p, _aout]
-        L.srt_ao_hits.argtypes = [C.c_void_p, C.c_uint32, _f32p, _i32p, _f32p, C.c_uint32, _ao, _vis, _aout, C.POINTER(abi.Stats)]
-        for f in (L.srt_ao_rays_device, L.srt_ao_rays, L.srt_ao_hits_device, L.srt_ao_hits):
-            f.restype = C.c_int
-        # ambient occlusion in a frame: the params first, an srt_ao_frame* after the srt_ao_desc*, an srt_ao_frame_out* last of the outputs
-        _par, _afr, _afout = C.POINTER(abi.Params), C.POINTER(abi.AoFrame), C.POINTER(abi.AoFrameOut)
-        L.srt_render_ao_device.argtypes = [C.c_void_p, _par, C.c_uint32, _ao, _afr, _vis, C.c_void_p, C.c_void_p, C.c_void_p, _afout]
-        L.srt_render_ao.argtypes = [C.c_void_p, _par, C.c_uint32, _ao, _afr, _vis, _i32p, _f32p, _afout, C.POINTER(abi.Stats)]
-        L.srt_render_ao_hits_device.argtypes = [C.c_void_p, _par, C.c_void_p, C.c_void_p, C.c_uint32, _ao, _afr, _vis, C.c_void_p, _afout]
-        L.srt_render_ao_hits.argtypes = [C.c_void_p, _par, _i32p, _f32p, C.c_uint32, _ao, _afr, _vis, _afout, C.POINTER(abi.Stats)]
-        for f in (L.srt_render_ao_device, L.srt_render_ao, L.srt_render_ao_hits_device, L.srt_render_ao_hits):
-            f.restype = C.c_int
-        L.srt_strerror.argtypes = [C.c_int]
-        L.srt_strerror.restype = C.c_char_p
-        L.srt_last_hip_error.restype = C.c_int
-        L.srt_abi_version.restype = C.c_uint32
-        L.srt_debug_fail_host_allocs.argtypes = [C.c_int]
-        L.srt_debug_fail_host_allocs.restype = None
-        L.srt_kat_ray_aabb.argtypes = [C.c_int, C.c_uint32, _f32p, _f32p, _u8p, _u8p, _u8p, _u8p]
-        L.srt_kat_ray_triangle.argtypes = [C.c_int, C.c_uint32, _f32p, _f32p, _f32p]
-        L.srt_kat_ray_triangle_origin.argtypes = [C.c_int, C.c_uint32, _f32p, _f32p, _f32p]
-        L.srt_kat_barycentric.argtypes = [C.c_int, C.c_uint32, _f32p, _f32p]
-        L.srt_kat_phong.argtypes = [C.c_int, C.c_uint32, _f32p, _f32p]
-        L.srt_kat_interp_normal.argtypes = [C.c_int, C.c_uint32, _f32p, _f32p]
-        L.srt_kat_pow.argtypes = [C.c_int, C.c_uint32, _f32p, _f32p, _f32p, _f32p]
-        L.srt_kat_tonemap.argtypes = [C.c_int, C.c_uint32, _f32p, C.c_float, C.c_float, _f32p, _i32p]
-        L.srt_kat_tone_filter.argtypes = [C.c_int, C.c_uint32, _f32p, C.c_float, C.c_float, _i32p, _i32p, _u8p]
-        L.srt_kat_tone_filter_sweep.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_float, C.c_float, C.POINTER(C.c_double)]
+        for name, (restype, argtypes) in abi.PROTOTYPES.items():
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = restype, argtypes
         if path is not None:
             return L
         _lib = L
@@ -254,15 +77,13 @@ class DeviceScene:
     def update(self, flat: abi.FlatScene, stream=0):
         """srt_scene_update: new geometry with the same counts into the existing device allocations (asynchronous on `stream`)."""
         d = flat.desc()
-        _check(self.L.srt_scene_update(self.h, C.byref(d), C.c_void_p(stream)), "srt_scene_update")
+        _check(self.L.srt_scene_update(self.h, C.byref(d), stream), "srt_scene_update")
         self.flat = flat
 
     def set_source(self, tri_texcoord=None, tri_normals=None, tri_tex=None):
         """srt_scene_set_source: per-triangle attributes in SOURCE order (objects concatenated), for update_frame."""
-        a = [None if x is None else np.ascontiguousarray(x, ty) for x, ty in ((tri_texcoord, np.float32), (tri_normals, np.float32), (tri_tex, np.int32))]
-        self.L.srt_scene_set_source.argtypes = [C.c_void_p, _f32p, _f32p, _i32p]
-        _check(self.L.srt_scene_set_source(self.h, a[0].ctypes.data_as(_f32p) if a[0] is not None else None, a[1].ctypes.data_as(_f32p) if a[1] is not None else None,
-                                           a[2].ctypes.data_as(_i32p) if a[2] is not None else None), "srt_scene_set_source")
+        _check(self.L.srt_scene_set_source(self.h, _host(_array(tri_texcoord, np.float32), _f32p), _host(_array(tri_normals, np.float32), _f32p),
+                                           _host(_array(tri_tex, np.int32), _i32p)), "srt_scene_set_source")
 
     def update_frame(self, points, order, node_min, node_max, obj_color=None, obj_material=None, stream=0):
         """srt_scene_update_frame: per object the transformed points in source order (n x 3 x 4), the build's permutation (n), the node
@@ -278,12 +99,9 @@ class DeviceScene:
         pp = (_f32p * n)(*[p.ctypes.data_as(_f32p) for p in pts]); po = (C.POINTER(C.c_uint32) * n)(*[o.ctypes.data_as(C.POINTER(C.c_uint32)) for o in ords])
         pmn = (_f32p * n)(*[m.ctypes.data_as(_f32p) for m in mn]); pmx = (_f32p * n)(*[m.ctypes.data_as(_f32p) for m in mx])
         g.obj_n_tris, g.obj_n_nodes, g.obj_points, g.obj_order, g.obj_node_min, g.obj_node_max = nt, nn, pp, po, pmn, pmx
-        col = None if obj_color is None else np.ascontiguousarray(obj_color, np.float32)
-        mat = None if obj_material is None else np.ascontiguousarray(obj_material, np.float32)
-        g.obj_color = col.ctypes.data_as(_f32p) if col is not None else None
-        g.obj_material = mat.ctypes.data_as(_f32p) if mat is not None else None
-        self.L.srt_scene_update_frame.argtypes = [C.c_void_p, C.POINTER(abi.FrameGeometry), C.c_void_p]
-        _check(self.L.srt_scene_update_frame(self.h, C.byref(g), C.c_void_p(stream)), "srt_scene_update_frame")
+        col, mat = _array(obj_color, np.float32), _array(obj_material, np.float32)
+        g.obj_color, g.obj_material = _host(col, _f32p), _host(mat, _f32p)
+        _check(self.L.srt_scene_update_frame(self.h, C.byref(g), stream), "srt_scene_update_frame")
 
     def set_pose_source(self, tri_points=None):
         """srt_scene_set_pose_source: the points (n_tris x 3 x 4, the scene's visit order) the poses are applied to; default: the flat scene's."""
@@ -294,33 +112,29 @@ class DeviceScene:
     def pose(self, matrices, obj_color=None, obj_material=None, stream=0):
         """srt_scene_pose: one column-major 4x4 matrix per object (n_objects x 16); points, triangle records and boxes follow on the device."""
         m = np.ascontiguousarray(matrices, np.float32).reshape(-1, 16)
-        col = None if obj_color is None else np.ascontiguousarray(obj_color, np.float32)
-        mat = None if obj_material is None else np.ascontiguousarray(obj_material, np.float32)
-        _check(self.L.srt_scene_pose(self.h, m.shape[0], m.ctypes.data_as(_f32p), col.ctypes.data_as(_f32p) if col is not None else None,
-                                     mat.ctypes.data_as(_f32p) if mat is not None else None, C.c_void_p(stream)), "srt_scene_pose")
+        _check(self.L.srt_scene_pose(self.h, m.shape[0], _host(m, _f32p), _host(_array(obj_color, np.float32), _f32p), _host(_array(obj_material, np.float32), _f32p),
+                                     stream), "srt_scene_pose")
 
     def set_object_masks(self, masks, stream=0):
         """srt_scene_set_object_masks: one uint32 per object (host array), or None = all ones.  Object k takes part in a masked walk with
         mask m iff (masks[k] & m) != 0; every handle that shares this scene's records sees the table; asynchronous on `stream`."""
         m = None if masks is None else np.ascontiguousarray(masks, np.uint32).reshape(-1)
         n = self.flat.n_objects if m is None else m.shape[0]
-        _check(self.L.srt_scene_set_object_masks(self.h, n, m.ctypes.data_as(_u32p) if m is not None else None, C.c_void_p(stream)), "srt_scene_set_object_masks")
+        _check(self.L.srt_scene_set_object_masks(self.h, n, _host(m, _u32p), stream), "srt_scene_set_object_masks")
 
     def refit_prepare(self, tri_vertex=None, n_verts=0):
         """srt_scene_refit_prepare: the refit's schedule, once per tree; tri_vertex (n_tris x 3 vertex numbers, the scene's visit order,
         host array) and n_verts prepare the indexed form as well."""
-        tv = None
-        if tri_vertex is not None:
-            tv = np.ascontiguousarray(tri_vertex, np.uint32)
-            assert tv.size == 3 * self.flat.n_tris, "tri_vertex: n_tris x 3"
-        _check(self.L.srt_scene_refit_prepare(self.h, n_verts, tv.ctypes.data_as(_u32p) if tv is not None else None), "srt_scene_refit_prepare")
+        tv = _array(tri_vertex, np.uint32)
+        assert tv is None or tv.size == 3 * self.flat.n_tris, "tri_vertex: n_tris x 3"
+        _check(self.L.srt_scene_refit_prepare(self.h, n_verts, _host(tv, _u32p)), "srt_scene_refit_prepare")
 
     def refit_device(self, points, stride=4, n_verts=0, normals=0, stream=0):
         """srt_scene_refit_device: raw device pointers (ints, e.g. torch.Tensor.data_ptr()) in, async on `stream`.  n_verts 0: points =
         n_tris x 3 points of `stride` floats in visit order (normals n_tris x 9); else n_verts points gathered through the prepared
         indices (normals n_verts x 3).  self.flat is NOT updated: it keeps the scene the handle was created or last updated from."""
         g = abi.RefitDesc(n_verts, stride, points, normals)
-        _check(self.L.srt_scene_refit_device(self.h, C.byref(g), C.c_void_p(stream)), "srt_scene_refit_device")
+        _check(self.L.srt_scene_refit_device(self.h, C.byref(g), stream), "srt_scene_refit_device")
 
     def records(self):
         """srt_debug_scene_records: the device records as raw numpy arrays (dict)."""
@@ -328,10 +142,9 @@ class DeviceScene:
         out = {"nodes": np.zeros((nN, 8), np.uint32), "tris": np.zeros((nT, 12), np.uint32), "tris_o": np.zeros((nT, 12), np.uint32),
                "wide": np.zeros(((nN - nO) // 2, 16), np.uint32), "root_nodes": np.zeros((nO, 8), np.uint32),
                "tri_texcoord": np.zeros((nT, 6), np.float32), "tri_normals": np.zeros((nT, 9), np.float32), "tri_tex": np.full(nT, -7, np.int32)}
-        self.L.srt_debug_scene_records.argtypes = [C.c_void_p] * 6 + [_f32p, _f32p, _i32p]
-        v = lambda k: out[k].ctypes.data_as(C.c_void_p)
-        _check(self.L.srt_debug_scene_records(self.h, v("nodes"), v("tris"), v("tris_o"), v("wide"), v("root_nodes"), out["tri_texcoord"].ctypes.data_as(_f32p),
-                                              out["tri_normals"].ctypes.data_as(_f32p), out["tri_tex"].ctypes.data_as(_i32p)), "srt_debug_scene_records")
+        v = lambda k: out[k].ctypes.data
+        _check(self.L.srt_debug_scene_records(self.h, v("nodes"), v("tris"), v("tris_o"), v("wide"), v("root_nodes"), _host(out["tri_texcoord"], _f32p),
+                                              _host(out["tri_normals"], _f32p), _host(out["tri_tex"], _i32p)), "srt_debug_scene_records")
         return out
 
     def close(self):
@@ -368,15 +181,11 @@ class DeviceScene:
     def render(self, params: abi.Params, want=("hit_id", "t", "rgb_linear", "rgb8")):
         """srt_render: host buffers out.  Returns dict of numpy arrays + 'stats'."""
         out, g = _outputs(want, (self.rows(params), self.cols(params)), _FRAME)
-        st = abi.Stats()
-        _check(self.L.srt_render(self.h, C.byref(params), g("hit_id"), g("t"), g("rgb_linear"), g("rgb8"), C.byref(st)), "srt_render")
-        out["stats"] = st.as_dict()
-        return out
+        return _with_stats(out, self.L.srt_render, "srt_render", self.h, C.byref(params), g("hit_id"), g("t"), g("rgb_linear"), g("rgb8"))
 
     def render_device(self, params: abi.Params, stream=0, hit_id=0, t=0, rgb_linear=0, rgb8=0):
         """srt_render_device: raw device pointers (ints, e.g. torch.Tensor.data_ptr()) in, async on `stream`."""
-        _check(self.L.srt_render_device(self.h, C.byref(params), C.c_void_p(stream), C.c_void_p(hit_id), C.c_void_p(t),
-                                        C.c_void_p(rgb_linear), C.c_void_p(rgb8)), "srt_render_device")
+        _check(self.L.srt_render_device(self.h, C.byref(params), stream, hit_id, t, rgb_linear, rgb8), "srt_render_device")
 
     def trace_rays(self, rays, want=("hit_id", "t", "bary"), count=False, t_range=None, ray_mask=None):
         """srt_trace_rays: the closest hit of every ray of `rays` (n x 6: origin xyz, direction xyz; host array).  Returns a dict of
@@ -384,126 +193,101 @@ class DeviceScene:
         t_range (n x 2: t_min, t_max per ray): srt_trace_rays_range, the closest hit inside each ray's closed interval.
         ray_mask (n uint32, or True = all ones): srt_trace_rays_masked, the closest hit among the objects whose mask (set_object_masks)
         shares a bit with the ray's."""
-        r = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
-        n = r.shape[0]
+        r, n = _rays(rays)
         out, g = _outputs(want, (n,), _CLOSEST)
-        st = abi.Stats()
-        fn, name, mid = _ray_call(self.L, "srt_trace_rays", "", _host(_t_range(t_range, n), _f32p), _host_mask(ray_mask, n))
-        _check(fn(self.h, n, _host(r, _f32p), *mid, abi.SRT_FLAG_COUNT_WORK if count else 0, g("hit_id"), g("t"), g("bary"), C.byref(st)), name)
-        out["stats"] = st.as_dict()
-        return out
+        fn, name, mid = _ray_call(self.L, "srt_trace_rays", "", _t_range(t_range, n), _host_mask(ray_mask, n))
+        return _with_stats(out, fn, name, self.h, n, r, *mid, _query_flags(count=count), g("hit_id"), g("t"), g("bary"))
 
     def occluded(self, rays, skip_obj=None, t_range=None, ray_mask=None):
         """srt_occluded: one uint8 per ray of `rays` (n x 6, host array), 1 = something other than object skip_obj[i] is hit at any t.
         t_range (n x 2: t_min, t_max per ray): srt_occluded_range, ... is hit at a t inside the ray's closed interval.
         ray_mask (n uint32, or True = all ones): srt_occluded_masked, ... among the objects whose mask shares a bit with the ray's."""
-        r = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
-        n = r.shape[0]
+        r, n = _rays(rays)
         sk = None if skip_obj is None else np.ascontiguousarray(skip_obj, np.int32).reshape(-1)
         assert sk is None or sk.shape[0] == n, "skip_obj: one entry per ray"
         occ = np.empty(n, np.uint8)
-        fn, name, mid = _ray_call(self.L, "srt_occluded", "", _host(_t_range(t_range, n), _f32p), _host_mask(ray_mask, n))
-        _check(fn(self.h, n, _host(r, _f32p), *mid, _host(sk, _i32p), _host(occ, _u8p)), name)
+        fn, name, mid = _ray_call(self.L, "srt_occluded", "", _t_range(t_range, n), _host_mask(ray_mask, n))
+        _check(fn(self.h, n, r, *mid, _host(sk, _i32p), _host(occ, _u8p)), name)
         return occ
 
     def trace_rays_device(self, n, rays, stream=0, hit_id=0, t=0, bary=0, count=False, t_range=None, ray_mask=None):
         """srt_trace_rays_device: raw device pointers (ints, e.g. torch.Tensor.data_ptr()) in, asynchronous on `stream`.
         t_range (a device pointer to n x 2 floats): srt_trace_rays_range_device.
         ray_mask (a device pointer to n uint32, or 0 = all ones): srt_trace_rays_masked_device."""
-        fn, name, mid = _ray_call(self.L, "srt_trace_rays", "_device", _device(t_range), _device_mask(ray_mask))
-        _check(fn(self.h, n, C.c_void_p(rays), *mid, abi.SRT_FLAG_COUNT_WORK if count else 0, C.c_void_p(stream), C.c_void_p(hit_id), C.c_void_p(t), C.c_void_p(bary)), name)
+        fn, name, mid = _ray_call(self.L, "srt_trace_rays", "_device", t_range, _device_mask(ray_mask))
+        _check(fn(self.h, n, rays, *mid, _query_flags(count=count), stream, hit_id, t, bary), name)
 
     def occluded_device(self, n, rays, occluded, skip_obj=0, stream=0, t_range=None, ray_mask=None):
         """srt_occluded_device: raw device pointers in, asynchronous on `stream`.  t_range (a device pointer to n x 2 floats):
         srt_occluded_range_device.  ray_mask (a device pointer to n uint32, or 0 = all ones): srt_occluded_masked_device."""
-        fn, name, mid = _ray_call(self.L, "srt_occluded", "_device", _device(t_range), _device_mask(ray_mask))
-        _check(fn(self.h, n, C.c_void_p(rays), *mid, C.c_void_p(skip_obj), C.c_void_p(stream), C.c_void_p(occluded)), name)
+        fn, name, mid = _ray_call(self.L, "srt_occluded", "_device", t_range, _device_mask(ray_mask))
+        _check(fn(self.h, n, rays, *mid, skip_obj, stream, occluded), name)
 
     def trace_rays_multi(self, rays, k, want=("n_hits", "hit_id", "t", "bary"), count=False, t_range=None):
         """srt_trace_rays_multi: the k nearest hits of every ray of `rays` (n x 6, host array) in one walk, nearest first, equal t by id.
         Returns a dict of the arrays named in `want` (n_hits n uint32 -- the full count, it may exceed k --, hit_id n x k, t n x k,
         bary n x k x 3; unused slots -1, +inf, 0) + 'stats'.  t_range (n x 2: t_min, t_max per ray): only hits inside the closed interval."""
-        r = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
-        n, k = r.shape[0], int(k)
+        r, n = _rays(rays)
+        k = int(k)
         out, g = _outputs(want, (n,), {"n_hits": (np.uint32, ())})
         rows, g_rows = _outputs(want, (n, max(k, 0)), _CLOSEST)
         out.update(rows)
-        st = abi.Stats()
-        _check(self.L.srt_trace_rays_multi(self.h, n, _host(r, _f32p), _host(_t_range(t_range, n), _f32p), k, abi.SRT_FLAG_COUNT_WORK if count else 0, g("n_hits"),
-                                           g_rows("hit_id"), g_rows("t"), g_rows("bary"), C.byref(st)), "srt_trace_rays_multi")
-        out["stats"] = st.as_dict()
-        return out
+        return _with_stats(out, self.L.srt_trace_rays_multi, "srt_trace_rays_multi", self.h, n, r, _t_range(t_range, n), k, _query_flags(count=count), g("n_hits"),
+                           g_rows("hit_id"), g_rows("t"), g_rows("bary"))
 
     def trace_rays_multi_device(self, n, rays, k, stream=0, n_hits=0, hit_id=0, t=0, bary=0, count=False, t_range=None):
         """srt_trace_rays_multi_device: raw device pointers (ints, e.g. torch.Tensor.data_ptr()) in, asynchronous on `stream`; t_range a
         device pointer to n x 2 floats, or None."""
-        flags = abi.SRT_FLAG_COUNT_WORK if count else 0
-        _check(self.L.srt_trace_rays_multi_device(self.h, n, C.c_void_p(rays), C.c_void_p(t_range or 0), k, flags, C.c_void_p(stream), C.c_void_p(n_hits),
-                                                  C.c_void_p(hit_id), C.c_void_p(t), C.c_void_p(bary)), "srt_trace_rays_multi_device")
+        _check(self.L.srt_trace_rays_multi_device(self.h, n, rays, t_range or 0, k, _query_flags(count=count), stream, n_hits, hit_id, t, bary),
+               "srt_trace_rays_multi_device")
 
     def shade_rays(self, rays, params: abi.Params, want=("hit_id", "t", "rgb_linear", "rgb8"), count=False, t_range=None):
         """srt_shade_rays: the colour that comes back along every ray of `rays` (n x 6, host array) under the lights, literals and flags
         of `params` (its frame geometry is ignored).  Returns a dict of the arrays named in `want` (hit_id n, t n, rgb_linear n x 3,
         rgb8 n x 3) + 'stats'; count=True adds SRT_FLAG_COUNT_WORK for this call.
         t_range (n x 2: t_min, t_max per ray): srt_shade_rays_range, the colour of the closest hit inside each ray's closed interval."""
-        r = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
-        n = r.shape[0]
+        r, n = _rays(rays)
         out, g = _outputs(want, (n,), _FRAME)
-        st = abi.Stats()
-        fn, name, mid = _ray_call(self.L, "srt_shade_rays", "", _host(_t_range(t_range, n), _f32p), None)
+        fn, name, mid = _ray_call(self.L, "srt_shade_rays", "", _t_range(t_range, n), None)
         with _flags(params, count=count):
-            rc = fn(self.h, n, _host(r, _f32p), *mid, C.byref(params), g("hit_id"), g("t"), g("rgb_linear"), g("rgb8"), C.byref(st))
-        _check(rc, name)
-        out["stats"] = st.as_dict()
-        return out
+            return _with_stats(out, fn, name, self.h, n, r, *mid, C.byref(params), g("hit_id"), g("t"), g("rgb_linear"), g("rgb8"))
 
     def shade_rays_device(self, n, rays, params: abi.Params, stream=0, hit_id=0, t=0, rgb_linear=0, rgb8=0, t_range=None):
         """srt_shade_rays_device: raw device pointers (ints, e.g. torch.Tensor.data_ptr()) in, asynchronous on `stream`; the light table
         of `params` is a host array.  t_range (a device pointer to n x 2 floats): srt_shade_rays_range_device."""
-        fn, name, mid = _ray_call(self.L, "srt_shade_rays", "_device", _device(t_range), None)
-        _check(fn(self.h, n, C.c_void_p(rays), *mid, C.byref(params), C.c_void_p(stream), C.c_void_p(hit_id), C.c_void_p(t), C.c_void_p(rgb_linear), C.c_void_p(rgb8)), name)
+        fn, name, mid = _ray_call(self.L, "srt_shade_rays", "_device", t_range, None)
+        _check(fn(self.h, n, rays, *mid, C.byref(params), stream, hit_id, t, rgb_linear, rgb8), name)
 
     def surface_rays(self, rays, want=("hit_id", "t", "obj", "point", "normal", "color", "material", "bounce"), smooth=False, count=False, t_range=None):
         """srt_surface_rays: the closest hit of every ray of `rays` (n x 6, host array) and the surface under it.  Returns a dict of the
         arrays named in `want` (hit_id n, t n, obj n, point / normal / color / material n x 3, bounce n x 6: the mirrored ray) + 'stats'.
         smooth: SRT_FLAG_SMOOTH_NORMALS; count: SRT_FLAG_COUNT_WORK; t_range (n x 2: t_min, t_max per ray): the closest hit inside each
         ray's closed interval."""
-        r = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
-        n = r.shape[0]
+        r, n = _rays(rays)
         out, g = _outputs(want, (n,), {**_HIT, **_SURFACE})
         so = abi.SurfaceOut(*_addresses(out, _SURFACE))
-        st = abi.Stats()
-        flags = (abi.SRT_FLAG_SMOOTH_NORMALS if smooth else 0) | (abi.SRT_FLAG_COUNT_WORK if count else 0)
-        _check(self.L.srt_surface_rays(self.h, n, _host(r, _f32p), _host(_t_range(t_range, n), _f32p), flags, g("hit_id"), g("t"), C.byref(so), C.byref(st)), "srt_surface_rays")
-        out["stats"] = st.as_dict()
-        return out
+        return _with_stats(out, self.L.srt_surface_rays, "srt_surface_rays", self.h, n, r, _t_range(t_range, n), _query_flags(smooth, count), g("hit_id"), g("t"),
+                           C.byref(so))
 
     def surface_rays_device(self, n, rays, stream=0, hit_id=0, t=0, obj=0, point=0, normal=0, color=0, material=0, bounce=0, smooth=False, count=False, t_range=None):
         """srt_surface_rays_device: raw device pointers (ints, e.g. torch.Tensor.data_ptr()) in, asynchronous on `stream`; t_range a device
         pointer to n x 2 floats, or None."""
-        so = abi.SurfaceOut(obj or None, point or None, normal or None, color or None, material or None, bounce or None)
-        flags = (abi.SRT_FLAG_SMOOTH_NORMALS if smooth else 0) | (abi.SRT_FLAG_COUNT_WORK if count else 0)
-        _check(self.L.srt_surface_rays_device(self.h, n, C.c_void_p(rays), C.c_void_p(t_range or 0), flags, C.c_void_p(stream), C.c_void_p(hit_id), C.c_void_p(t),
-                                              C.byref(so)), "srt_surface_rays_device")
+        so = _wanted(abi.SurfaceOut, obj, point, normal, color, material, bounce)
+        _check(self.L.srt_surface_rays_device(self.h, n, rays, t_range or 0, _query_flags(smooth, count), stream, hit_id, t, C.byref(so)), "srt_surface_rays_device")
 
     def surface_hits(self, rays, hit_id, t, want=("obj", "point", "normal", "color", "material", "bounce"), smooth=False):
         """srt_surface_hits: the surface under hits the caller already holds -- `hit_id` (n) and `t` (n) of the rays `rays` (n x 6, host
         arrays): a render's, srt_trace_rays', a column of srt_trace_rays_multi.  No walk.  Returns a dict of the arrays named in `want`."""
-        r = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
-        n = r.shape[0]
-        hid = np.ascontiguousarray(hit_id, np.int32).reshape(-1); tt = np.ascontiguousarray(t, np.float32).reshape(-1)
-        assert hid.shape[0] == n and tt.shape[0] == n, "hit_id, t: one entry per ray"
+        r, n = _rays(rays)
         out, _ = _outputs(want, (n,), _SURFACE)
         so = abi.SurfaceOut(*_addresses(out, _SURFACE))
-        _check(self.L.srt_surface_hits(self.h, n, _host(r, _f32p), _host(hid, _i32p), _host(tt, _f32p), abi.SRT_FLAG_SMOOTH_NORMALS if smooth else 0, C.byref(so)),
-               "srt_surface_hits")
+        _check(self.L.srt_surface_hits(self.h, n, r, *_hits(hit_id, t, n), _query_flags(smooth), C.byref(so)), "srt_surface_hits")
         return out
 
     def surface_hits_device(self, n, rays, hit_id, t, stream=0, obj=0, point=0, normal=0, color=0, material=0, bounce=0, smooth=False):
         """srt_surface_hits_device: raw device pointers (ints) in -- the rays, their hit ids and t --, asynchronous on `stream`."""
-        so = abi.SurfaceOut(obj or None, point or None, normal or None, color or None, material or None, bounce or None)
-        _check(self.L.srt_surface_hits_device(self.h, n, C.c_void_p(rays), C.c_void_p(hit_id), C.c_void_p(t), abi.SRT_FLAG_SMOOTH_NORMALS if smooth else 0,
-                                              C.c_void_p(stream), C.byref(so)), "srt_surface_hits_device")
+        so = _wanted(abi.SurfaceOut, obj, point, normal, color, material, bounce)
+        _check(self.L.srt_surface_hits_device(self.h, n, rays, hit_id, t, _query_flags(smooth), stream, C.byref(so)), "srt_surface_hits_device")
 
     def ao_rays(self, rays, dirs, t_min=1e-3, t_max=np.inf, t_range=None, skip_self=False, visibility=None, smooth=False, count=False,
                 want=("hit_id", "t", "n_occluded", "ao", "occ_bits")):
@@ -514,51 +298,46 @@ class DeviceScene:
         with W = (K + 31) // 32, bit k & 31 of word k >> 5 for direction k) + 'stats'.  t_range (n x 2): the interval of the closest hit.
         skip_self: SRT_AO_SKIP_SELF, the hit's own object blocks nothing.  visibility: None, or (primary, bounce, shadow) -- the closest
         hit is walked with primary, the AO rays with shadow.  smooth: SRT_FLAG_SMOOTH_NORMALS; count: SRT_FLAG_COUNT_WORK."""
-        r = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
-        n = r.shape[0]
+        r, n = _rays(rays)
         desc, table = _ao_desc(dirs, t_min, t_max, skip_self)
         out, g = _outputs(want, (n,), _HIT)
         aout, arrays = _ao_out(want, n, desc.n_dirs)
         out.update(arrays)
-        st = abi.Stats()
-        _check(self.L.srt_ao_rays(self.h, n, _host(r, _f32p), _host(_t_range(t_range, n), _f32p), _ao_flags(smooth, count), C.byref(desc), _vis_ref(visibility),
-                                  g("hit_id"), g("t"), C.byref(aout), C.byref(st)), "srt_ao_rays")
-        out["stats"] = st.as_dict()
-        return out
+        return _with_stats(out, self.L.srt_ao_rays, "srt_ao_rays", self.h, n, r, _t_range(t_range, n), _query_flags(smooth, count), C.byref(desc), _vis_ref(visibility),
+                           g("hit_id"), g("t"), C.byref(aout))
 
     def ao_hits(self, rays, hit_id, t, dirs, t_min=1e-3, t_max=np.inf, skip_self=False, visibility=None, smooth=False, count=False,
                 want=("n_occluded", "ao", "occ_bits")):
         """srt_ao_hits: ao_rays for hits the caller already holds -- `hit_id` (n) and `t` (n) of the rays `rays` (n x 6, host arrays): a
         render's with the frame's rays, trace_rays', a column of trace_rays_multi.  No closest-hit walk; an id outside [0, n_tris) is a
         miss row (n_occluded 0, ao 1).  Returns a dict of the arrays named in `want` + 'stats'."""
-        r = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
-        n = r.shape[0]
-        hid = np.ascontiguousarray(hit_id, np.int32).reshape(-1); tt = np.ascontiguousarray(t, np.float32).reshape(-1)
-        assert hid.shape[0] == n and tt.shape[0] == n, "hit_id, t: one entry per ray"
+        r, n = _rays(rays)
+        hits = _hits(hit_id, t, n)
         desc, table = _ao_desc(dirs, t_min, t_max, skip_self)
         aout, out = _ao_out(want, n, desc.n_dirs)
-        st = abi.Stats()
-        _check(self.L.srt_ao_hits(self.h, n, _host(r, _f32p), _host(hid, _i32p), _host(tt, _f32p), _ao_flags(smooth, count), C.byref(desc), _vis_ref(visibility),
-                                  C.byref(aout), C.byref(st)), "srt_ao_hits")
-        out["stats"] = st.as_dict()
-        return out
+        return _with_stats(out, self.L.srt_ao_hits, "srt_ao_hits", self.h, n, r, *hits, _query_flags(smooth, count), C.byref(desc), _vis_ref(visibility), C.byref(aout))
+
+    def _ao_device(self, name, head, dirs, n_dirs, t_min, t_max, skip_self, rot, visibility, smooth, count, stream, hit, outs):
+        """The _device form of an ambient-occlusion call.  head: the arguments between the handle and the flags; rot: None, or the
+        (rot_w, rot_h, address) of a frame call's srt_ao_frame; hit: the hit_id and t outputs, where the call has them; outs: the
+        addresses of its srt_ao_out, or of a frame call's srt_ao_frame_out."""
+        desc = abi.AoDesc(n_dirs, dirs or None, t_min, t_max, abi.SRT_AO_SKIP_SELF if skip_self else 0)
+        frame = () if rot is None else (C.byref(abi.AoFrame(rot[0], rot[1], rot[2] or None)),)
+        out = _wanted(abi.AoOut if rot is None else abi.AoFrameOut, *outs)
+        _check(getattr(self.L, name)(self.h, *head, _query_flags(smooth, count), C.byref(desc), *frame, _vis_ref(visibility), stream, *hit, C.byref(out)), name)
 
     def ao_rays_device(self, n, rays, dirs, n_dirs, t_min=1e-3, t_max=np.inf, t_range=None, skip_self=False, visibility=None, smooth=False, count=False, stream=0,
                        hit_id=0, t=0, n_occluded=0, ao=0, occ_bits=0):
         """srt_ao_rays_device: raw device pointers (ints, e.g. torch.Tensor.data_ptr()) in -- the rays, the table `dirs` of n_dirs x 3 floats,
         t_range (n x 2 floats, or None) and the outputs (0: not wanted) --, asynchronous on `stream`."""
-        desc = abi.AoDesc(n_dirs, dirs or None, t_min, t_max, abi.SRT_AO_SKIP_SELF if skip_self else 0)
-        aout = abi.AoOut(n_occluded or None, ao or None, occ_bits or None)
-        _check(self.L.srt_ao_rays_device(self.h, n, C.c_void_p(rays), C.c_void_p(t_range or 0), _ao_flags(smooth, count), C.byref(desc), _vis_ref(visibility),
-                                         C.c_void_p(stream), C.c_void_p(hit_id), C.c_void_p(t), C.byref(aout)), "srt_ao_rays_device")
+        self._ao_device("srt_ao_rays_device", (n, rays, t_range or 0), dirs, n_dirs, t_min, t_max, skip_self, None, visibility, smooth, count, stream, (hit_id, t),
+                        (n_occluded, ao, occ_bits))
 
     def ao_hits_device(self, n, rays, hit_id, t, dirs, n_dirs, t_min=1e-3, t_max=np.inf, skip_self=False, visibility=None, smooth=False, count=False, stream=0,
                        n_occluded=0, ao=0, occ_bits=0):
         """srt_ao_hits_device: raw device pointers (ints) in -- the rays, their hit ids and t, the table --, asynchronous on `stream`."""
-        desc = abi.AoDesc(n_dirs, dirs or None, t_min, t_max, abi.SRT_AO_SKIP_SELF if skip_self else 0)
-        aout = abi.AoOut(n_occluded or None, ao or None, occ_bits or None)
-        _check(self.L.srt_ao_hits_device(self.h, n, C.c_void_p(rays), C.c_void_p(hit_id), C.c_void_p(t), _ao_flags(smooth, count), C.byref(desc), _vis_ref(visibility),
-                                         C.c_void_p(stream), C.byref(aout)), "srt_ao_hits_device")
+        self._ao_device("srt_ao_hits_device", (n, rays, hit_id, t), dirs, n_dirs, t_min, t_max, skip_self, None, visibility, smooth, count, stream, (),
+                        (n_occluded, ao, occ_bits))
 
     def render_ao(self, params: abi.Params, dirs, rot=None, t_min=1e-3, t_max=np.inf, skip_self=False, visibility=None, smooth=False, count=False,
                   want=("hit_id", "t", "n_occluded", "ao", "occ_bits", "bent", "ao8"), fill=None):
@@ -574,11 +353,8 @@ class DeviceScene:
         out, g = _outputs(want, lead, _HIT, fill)
         fout, arrays = _ao_frame_out(want, lead, desc.n_dirs, fill)
         out.update(arrays)
-        st = abi.Stats()
-        _check(self.L.srt_render_ao(self.h, C.byref(params), _ao_flags(smooth, count), C.byref(desc), C.byref(frame), _vis_ref(visibility), g("hit_id"), g("t"),
-                                    C.byref(fout), C.byref(st)), "srt_render_ao")
-        out["stats"] = st.as_dict()
-        return out
+        return _with_stats(out, self.L.srt_render_ao, "srt_render_ao", self.h, C.byref(params), _query_flags(smooth, count), C.byref(desc), C.byref(frame),
+                           _vis_ref(visibility), g("hit_id"), g("t"), C.byref(fout))
 
     def render_ao_hits(self, params: abi.Params, hit_id, t, dirs, rot=None, t_min=1e-3, t_max=np.inf, skip_self=False, visibility=None, smooth=False, count=False,
                        want=("n_occluded", "ao", "occ_bits", "bent", "ao8"), fill=None):
@@ -586,37 +362,27 @@ class DeviceScene:
         (host arrays).  No closest-hit walk; only sub-sample 0's ray is used; an id outside [0, n_tris) is a miss row (n_occluded 0, ao 1,
         bent 0, ao8 255).  Returns a dict of the arrays named in `want` + 'stats'."""
         lead = (self.rows(params), self.cols(params))
-        hid = np.ascontiguousarray(hit_id, np.int32).reshape(-1); tt = np.ascontiguousarray(t, np.float32).reshape(-1)
-        assert hid.shape[0] == lead[0] * lead[1] and tt.shape[0] == hid.shape[0], "hit_id, t: one entry per local pixel"
+        hits = _hits(hit_id, t, lead[0] * lead[1], "hit_id, t: one entry per local pixel")
         desc, table = _ao_desc(dirs, t_min, t_max, skip_self)
         frame, turns = _ao_frame(rot)
         fout, out = _ao_frame_out(want, lead, desc.n_dirs, fill)
-        st = abi.Stats()
-        _check(self.L.srt_render_ao_hits(self.h, C.byref(params), _host(hid, _i32p), _host(tt, _f32p), _ao_flags(smooth, count), C.byref(desc), C.byref(frame),
-                                         _vis_ref(visibility), C.byref(fout), C.byref(st)), "srt_render_ao_hits")
-        out["stats"] = st.as_dict()
-        return out
+        return _with_stats(out, self.L.srt_render_ao_hits, "srt_render_ao_hits", self.h, C.byref(params), *hits, _query_flags(smooth, count), C.byref(desc),
+                           C.byref(frame), _vis_ref(visibility), C.byref(fout))
 
     def render_ao_device(self, params: abi.Params, dirs, n_dirs, rot=0, rot_w=0, rot_h=0, t_min=1e-3, t_max=np.inf, skip_self=False, visibility=None, smooth=False,
                          count=False, stream=0, hit_id=0, t=0, n_occluded=0, ao=0, occ_bits=0, bent=0, ao8=0):
         """srt_render_ao_device: raw device pointers (ints, e.g. torch.Tensor.data_ptr()) in -- the table `dirs` of n_dirs x 3 floats, the
         rotation table `rot` of rot_h x rot_w x 2 floats (0: none) and the outputs of the call's local pixels (0: not wanted) --,
         asynchronous on `stream`, one launch."""
-        desc = abi.AoDesc(n_dirs, dirs or None, t_min, t_max, abi.SRT_AO_SKIP_SELF if skip_self else 0)
-        frame = abi.AoFrame(rot_w, rot_h, rot or None)
-        fout = abi.AoFrameOut(n_occluded or None, ao or None, occ_bits or None, bent or None, ao8 or None)
-        _check(self.L.srt_render_ao_device(self.h, C.byref(params), _ao_flags(smooth, count), C.byref(desc), C.byref(frame), _vis_ref(visibility), C.c_void_p(stream),
-                                           C.c_void_p(hit_id), C.c_void_p(t), C.byref(fout)), "srt_render_ao_device")
+        self._ao_device("srt_render_ao_device", (C.byref(params),), dirs, n_dirs, t_min, t_max, skip_self, (rot_w, rot_h, rot), visibility, smooth, count, stream,
+                        (hit_id, t), (n_occluded, ao, occ_bits, bent, ao8))
 
     def render_ao_hits_device(self, params: abi.Params, hit_id, t, dirs, n_dirs, rot=0, rot_w=0, rot_h=0, t_min=1e-3, t_max=np.inf, skip_self=False, visibility=None,
                               smooth=False, count=False, stream=0, n_occluded=0, ao=0, occ_bits=0, bent=0, ao8=0):
         """srt_render_ao_hits_device: raw device pointers (ints) in -- a render's hit_id / t of the same `params`, the tables --, asynchronous
         on `stream`, one launch."""
-        desc = abi.AoDesc(n_dirs, dirs or None, t_min, t_max, abi.SRT_AO_SKIP_SELF if skip_self else 0)
-        frame = abi.AoFrame(rot_w, rot_h, rot or None)
-        fout = abi.AoFrameOut(n_occluded or None, ao or None, occ_bits or None, bent or None, ao8 or None)
-        _check(self.L.srt_render_ao_hits_device(self.h, C.byref(params), C.c_void_p(hit_id), C.c_void_p(t), _ao_flags(smooth, count), C.byref(desc), C.byref(frame),
-                                                _vis_ref(visibility), C.c_void_p(stream), C.byref(fout)), "srt_render_ao_hits_device")
+        self._ao_device("srt_render_ao_hits_device", (C.byref(params), hit_id, t), dirs, n_dirs, t_min, t_max, skip_self, (rot_w, rot_h, rot), visibility, smooth, count,
+                        stream, (), (n_occluded, ao, occ_bits, bent, ao8))
 
     def _paths_host(self, kind, head, lead, params, depth, reflectance, bounce_t_min, want, count, smooth, fill, shadow, visibility, ior, fresnel=None):
         """The host form of a path call: srt_<kind>_paths and its _shadow, _masked, _refract and _fresnel forms.  head: the arguments
@@ -627,7 +393,6 @@ class DeviceScene:
         out.update(seg)
         po = abi.PathOut(*_addresses(seg, _PATH_SEGMENTS))
         pd = abi.PathDesc(depth, bounce_t_min, refl.ctypes.data if refl is not None else None)
-        st = abi.Stats()
         refr, table = _refraction(ior, self.flat.n_objects)
         fres, f0 = None, None
         if fresnel is not None:
@@ -639,23 +404,20 @@ class DeviceScene:
             fres = abi.Fresnel(f0.ctypes.data, 0, C.pointer(fout))
         fn, name, mid = _path_call(self.L, kind, "", abi.shadow_rule(shadow), abi.visibility(visibility), refr, fres)
         with _flags(params, count=count, smooth=smooth):
-            rc = fn(*head, C.byref(params), C.byref(pd), *mid, g("rgb_linear"), g("rgb8"), C.byref(po), C.byref(st))
-        _check(rc, name)
-        out["stats"] = st.as_dict()
-        return out
+            return _with_stats(out, fn, name, *head, C.byref(params), C.byref(pd), *mid, g("rgb_linear"), g("rgb8"), C.byref(po))
 
     def _paths_device(self, kind, head, params, depth, reflectance, bounce_t_min, stream, rgb_linear, rgb8, segments, shadow, visibility, ior, fresnel=None, side=()):
         """The device form of a path call.  ior: None, or a device pointer (0: the _refract call without a table).  fresnel: None, or a
         device pointer to f0 (0: the _fresnel call without a table); side: the four device pointers of its srt_fresnel_out."""
         pd = abi.PathDesc(depth, bounce_t_min, reflectance or None)
-        po = abi.PathOut(*(p or None for p in segments))
+        po = _wanted(abi.PathOut, *segments)
         refr = None if ior is None else abi.Refraction(ior or None, 0)
         fres = None
         if fresnel is not None:
-            fout = abi.FresnelOut(*(p or None for p in side))
+            fout = _wanted(abi.FresnelOut, *side)
             fres = abi.Fresnel(fresnel or None, 0, C.pointer(fout))
         fn, name, mid = _path_call(self.L, kind, "_device", abi.shadow_rule(shadow), abi.visibility(visibility), refr, fres)
-        _check(fn(*head, C.byref(params), C.byref(pd), *mid, C.c_void_p(stream), C.c_void_p(rgb_linear), C.c_void_p(rgb8), C.byref(po)), name)
+        _check(fn(*head, C.byref(params), C.byref(pd), *mid, stream, rgb_linear, rgb8, C.byref(po)), name)
 
     def shade_paths(self, rays, params: abi.Params, depth, reflectance=None, bounce_t_min=1e-3, t_range=None,
                     want=("rgb_linear", "rgb8", "seg_hit_id", "seg_t", "seg_obj", "seg_rgb_linear", "seg_rays"), count=False, smooth=False, shadow=None,
@@ -676,9 +438,8 @@ class DeviceScene:
         -- at a hit on an object k with ior[k] > 0 and f0[k] >= 0 the mirrored ray is walked and shaded once as a side ray, and its sum
         enters the mix with Schlick's weight (srt_*_paths_fresnel).  `want` may then name side_hit_id / side_t / fresnel (depth x n) and
         side_rgb_linear (depth x n x 3): per segment, the side ray's hit, its sum and the weight F."""
-        r = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
-        n = r.shape[0]
-        head = (self.h, n, _host(r, _f32p), _host(_t_range(t_range, n), _f32p))
+        r, n = _rays(rays)
+        head = (self.h, n, r, _t_range(t_range, n))
         return self._paths_host("shade", head, (n,), params, depth, reflectance, bounce_t_min, want, count, smooth, None, shadow, visibility, ior, fresnel)
 
     def shade_paths_device(self, n, rays, params: abi.Params, depth, reflectance=0, bounce_t_min=1e-3, t_range=None, stream=0, rgb_linear=0, rgb8=0, seg_hit_id=0,
@@ -690,7 +451,7 @@ class DeviceScene:
         shadow, visibility: as in shade_paths.  ior: None, or a DEVICE pointer to n_objects floats (0 = no table): srt_shade_paths_refract_device.
         fresnel: None, or a DEVICE pointer to the n_objects floats of f0 (0 = no table): srt_shade_paths_fresnel_device; the side_* outputs are
         the depth x n rows of its srt_fresnel_out."""
-        head = (self.h, n, C.c_void_p(rays), C.c_void_p(t_range or 0))
+        head = (self.h, n, rays, t_range or 0)
         self._paths_device("shade", head, params, depth, reflectance, bounce_t_min, stream, rgb_linear, rgb8, (seg_hit_id, seg_t, seg_obj, seg_rgb_linear, seg_rays),
                            shadow, visibility, ior, fresnel, (side_hit_id, side_t, side_rgb_linear, side_fresnel))
 
@@ -717,9 +478,7 @@ class DeviceScene:
                            shadow, visibility, ior, fresnel, (side_hit_id, side_t, side_rgb_linear, side_fresnel))
 
     def sync(self):
-        st = abi.Stats()
-        _check(self.L.srt_sync(self.h, C.byref(st)), "srt_sync")
-        return st.as_dict()
+        return _with_stats({}, self.L.srt_sync, "srt_sync", self.h)["stats"]
 
 
 class FrameBatch:
@@ -743,7 +502,7 @@ class FrameBatch:
         self.out = [table(v) for v in (hit_id, t, rgb_linear, rgb8)]
 
     def render(self, stream=0):
-        _check(self.L.srt_render_device_batch(self.n, self.h, self.p, C.c_void_p(stream), *self.out), "srt_render_device_batch")
+        _check(self.L.srt_render_device_batch(self.n, self.h, self.p, stream, *self.out), "srt_render_device_batch")
 
 
 def _f(a):
@@ -780,7 +539,7 @@ class _flags:
     when it raises."""
 
     def __init__(self, params, count=False, smooth=False):
-        self.params, self.extra = params, (abi.SRT_FLAG_COUNT_WORK if count else 0) | (abi.SRT_FLAG_SMOOTH_NORMALS if smooth else 0)
+        self.params, self.extra = params, _query_flags(smooth, count)
 
     def __enter__(self):
         self.flags = self.params.flags
@@ -795,9 +554,39 @@ def _host(a, ty):
     return a.ctypes.data_as(ty) if a is not None else None
 
 
-def _device(address):
-    """A device address as a _device entry point takes it, or None for None."""
-    return None if address is None else C.c_void_p(address)
+def _array(a, dtype):
+    """An optional host array as a C-contiguous array of `dtype`, or None for None."""
+    return None if a is None else np.ascontiguousarray(a, dtype)
+
+
+def _rays(rays):
+    """The rays of a host form (n x 6 float32) as the pointer it takes, and n."""
+    r = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
+    return _host(r, _f32p), r.shape[0]
+
+
+def _hits(hit_id, t, n, what="hit_id, t: one entry per ray"):
+    """The caller's hits of a host form, n of each, as the two pointers it takes."""
+    hid, tt = np.ascontiguousarray(hit_id, np.int32).reshape(-1), np.ascontiguousarray(t, np.float32).reshape(-1)
+    assert hid.shape[0] == n and tt.shape[0] == n, what
+    return _host(hid, _i32p), _host(tt, _f32p)
+
+
+def _query_flags(smooth=False, count=False):
+    return (abi.SRT_FLAG_SMOOTH_NORMALS if smooth else 0) | (abi.SRT_FLAG_COUNT_WORK if count else 0)
+
+
+def _with_stats(out, fn, name, *args):
+    """A host form that ends in an srt_stats*: fn(*args, &stats), checked; returns `out` with the stats under 'stats'."""
+    st = abi.Stats()
+    _check(fn(*args, C.byref(st)), name)
+    out["stats"] = st.as_dict()
+    return out
+
+
+def _wanted(struct, *addresses):
+    """An out struct of a _device form over the caller's device addresses (0: not wanted)."""
+    return struct(*(a or None for a in addresses))
 
 
 def _host_mask(ray_mask, n):
@@ -807,7 +596,7 @@ def _host_mask(ray_mask, n):
 
 def _device_mask(ray_mask):
     """The `mask` of _ray_call for a _device form: None, or the device address of the masks (0: all ones)."""
-    return None if ray_mask is None else (C.c_void_p(ray_mask or 0),)
+    return None if ray_mask is None else (ray_mask or 0,)
 
 
 def _ray_call(L, stem, suffix, t_range, mask):
@@ -861,10 +650,6 @@ def schlick_f0(ior):
         q = (n.astype(np.float64) - 1.0) / (n.astype(np.float64) + 1.0)
         f = (q * q).astype(np.float32)
     return np.where(n > np.float32(0.0), f, np.float32(-1.0)).astype(np.float32)
-
-
-def _ao_flags(smooth, count):
-    return (abi.SRT_FLAG_SMOOTH_NORMALS if smooth else 0) | (abi.SRT_FLAG_COUNT_WORK if count else 0)
 
 
 def _vis_ref(visibility):
@@ -937,12 +722,12 @@ def _ray_mask(ray_mask, n):
 
 
 def _t_range(t_range, n):
-    """The t intervals of n rays as a host array (n x 2 float32), or None."""
+    """The t intervals of n rays (n x 2 float32) as the pointer a host form takes, or None."""
     if t_range is None:
         return None
     tr = np.ascontiguousarray(t_range, np.float32).reshape(-1, 2)
     assert tr.shape[0] == n, "t_range: one (t_min, t_max) per ray"
-    return tr
+    return _host(tr, _f32p)
 
 
 def kat_ray_aabb(ray_od, box, device=0):
@@ -1015,7 +800,6 @@ def valu_rate(iters=2000, device=0):
     """(wave-instructions per SIMD-cycle, shader clock in GHz, the same rate over the whole launch span, waves per SIMD): srt_debug_valu_rate."""
     L = load()
     out = (C.c_double * 4)()
-    L.srt_debug_valu_rate.argtypes = [C.c_int, C.c_uint32, C.POINTER(C.c_double)]
     _check(L.srt_debug_valu_rate(device, iters, out), "srt_debug_valu_rate")
     return float(out[0]), float(out[1]), float(out[2]), float(out[3])
 

@@ -28,7 +28,8 @@ def test_header_symbols_are_exported(L):
 
 
 def test_struct_sizes_match_header(L):
-    # the C compiler's layout of the PODs == the ctypes mirror (checked through srt_params_default)
+    """One struct, indirectly: the values srt_params_default writes into an abi.Params come back in the fields they belong to.  Sizes and
+    offsets of every struct are compared with the C compiler's in test_abi_mirror.py."""
     p = abi.Params()
     L.srt_params_default(C.byref(p), 600, 400)
     assert (p.width, p.height, p.block_rows, p.block_first, p.block_stride) == (600, 400, 400, 0, 1)

@@ -1,0 +1,216 @@
+"""CPU-only: the ctypes mirror of include/srt.h -- abi.PROTOTYPES, abi.STRUCTS and the SRT_* constants of abi and lib -- against the header
+itself: every prototype argument by argument, every struct's layout as the C compiler lays it out, every constant by value.  The checks
+are plain functions over (the mirror, the parsed header); the last test feeds them doctored mirrors and expects each to be named."""
+import ctypes as C
+import os
+import re
+import subprocess
+
+import pytest
+
+from simple_raytracer_amd import abi, lib
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+INCLUDE = os.path.join(ROOT, "include")
+
+SCALARS = {"int": C.c_int, "float": C.c_float, "double": C.c_double, "size_t": C.c_size_t, "uint8_t": C.c_uint8, "int32_t": C.c_int32,
+           "uint32_t": C.c_uint32, "uint64_t": C.c_uint64}
+RESTYPES = {**SCALARS, "void": None, "char*": C.c_char_p, "void*": C.c_void_p}
+
+
+def _c_type(words):
+    """'const float * const *' -> 'float**': const dropped, the stars joined to the base type."""
+    t = re.sub(r"\bconst\b", " ", words)
+    return "".join(t.replace("*", " ").split()) + "*" * t.count("*")
+
+
+def parse_header(text):
+    """include/srt.h as {"prototypes": [(name, return type, [(parameter type, parameter name)])] in the header's order,
+    "structs": {name: [field name]}, "constants": {name: value}}; types as _c_type writes them."""
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    text = re.sub(r"//[^\n]*", " ", text)
+    value = lambda expr: eval(re.sub(r"\b(\d+)[uU]\b", r"\1", expr), {"__builtins__": {}})
+    constants = {name: value(expr) for name, expr in re.findall(r"^[ \t]*#[ \t]*define[ \t]+(SRT_\w+)[ \t]+([0-9][^\n]*)$", text, flags=re.M)}
+    text = re.sub(r"^[ \t]*#[^\n]*$", " ", text, flags=re.M)
+    for body in re.findall(r"\benum\s*\{(.*?)\}", text, flags=re.S):
+        for entry in filter(None, (e.strip() for e in body.split(","))):
+            name, expr = entry.split("=")
+            constants[name.strip()] = value(expr)
+    structs = {}
+    for body, name in re.findall(r"\btypedef\s+struct\s+\w+\s*\{(.*?)\}\s*(\w+)\s*;", text, flags=re.S):
+        structs[name] = [re.match(r"[\s\*]*(\w+)", d).group(1) for decl in filter(None, (re.sub(r"\bconst\b", "", d).strip() for d in body.split(";")))
+                         for d in re.sub(r"^\w+", "", decl).split(",")]     # 'type a, *b, c[4]' -> a, b, c
+    text = re.sub(r"\b(typedef\s+struct\s+\w+|enum)\s*\{.*?\}\s*\w*\s*;", " ", text, flags=re.S)
+    prototypes = []
+    for ret, name, params in re.findall(r"([\w\s\*]+?)\b(srt_\w+)\s*\(([^()]*)\)\s*;", text):
+        args = []
+        for p in ([] if params.strip() == "void" else params.split(",")):
+            m = re.match(r"^(.*?)(\w+)\s*(\[\s*\d*\s*\])?$", p.strip())
+            args.append((_c_type(m.group(1) + ("*" if m.group(3) else "")), m.group(2)))
+        prototypes.append((name, _c_type(ret), args))
+    return {"prototypes": prototypes, "structs": structs, "constants": constants}
+
+
+def expected_argtype(function, c_type, parameter, structs):
+    """The ctypes type the mirror's rule gives a parameter of the header."""
+    if c_type.endswith("**"):                           # srt_scene**, T* const*: a table of addresses
+        return C.POINTER(C.c_void_p)
+    if c_type in ("srt_scene*", "void*"):
+        return C.c_void_p
+    if c_type.endswith("*"):
+        base = c_type[:-1]
+        if base.startswith("srt_"):
+            return C.POINTER(structs[base])
+        # an address that travels as an int: a device pointer, the pinned outputs of srt_render_async
+        if parameter.startswith("d_") or function == "srt_render_async":
+            return C.c_void_p
+        return C.POINTER(SCALARS[base])
+    return SCALARS[c_type]
+
+
+def check_prototypes(table, structs, header):
+    """Every difference between the prototype table and the header's declarations, as 'function: what'."""
+    declared = {name: (ret, args) for name, ret, args in header["prototypes"]}
+    errors = [f"{name}: in the table, not in the header" for name in table if name not in declared]
+    errors += [f"{name}: in the header, not in the table" for name in declared if name not in table]
+    for name, (ret, args) in declared.items():
+        if name not in table:
+            continue
+        restype, argtypes = table[name]
+        if restype is not RESTYPES[ret]:
+            errors.append(f"{name}: restype {restype} for '{ret}'")
+        if len(argtypes) != len(args):
+            errors.append(f"{name}: {len(argtypes)} argtypes for {len(args)} parameters")
+            continue
+        for i, ((c_type, parameter), have) in enumerate(zip(args, argtypes)):
+            want = expected_argtype(name, c_type, parameter, structs)
+            if have is not want:
+                errors.append(f"{name}: argument {i} ({c_type} {parameter}) is {have}, not {want}")
+            if (parameter.startswith("d_") and c_type.count("*") == 1 or parameter == "stream") and have is not C.c_void_p:
+                errors.append(f"{name}: {parameter} must be c_void_p")
+    return errors
+
+
+def check_structs(structs, header, layouts):
+    """Every difference between the ctypes classes and the C compiler's layouts {struct: (size, [(field, offset, size)])}."""
+    errors = [f"{name}: in STRUCTS, not in the header" for name in structs if name not in header["structs"]]
+    errors += [f"{name}: in the header, not in STRUCTS" for name in header["structs"] if name not in structs]
+    for name, cls in structs.items():
+        if name not in layouts:
+            continue
+        size, fields = layouts[name]
+        if C.sizeof(cls) != size:
+            errors.append(f"{name}: size {C.sizeof(cls)}, the compiler's {size}")
+        mine = [(f[0], getattr(cls, f[0]).offset, getattr(cls, f[0]).size) for f in cls._fields_]
+        if [f[0] for f in mine] != [f[0] for f in fields]:
+            errors.append(f"{name}: fields {[f[0] for f in mine]}, the header's {[f[0] for f in fields]}")
+        for field, offset, width in mine:
+            if (field, offset, width) not in fields:
+                errors.append(f"{name}.{field}: offset {offset} size {width}, the compiler's {[f[1:] for f in fields if f[0] == field]}")
+    return errors
+
+
+def check_constants(mirrored, header):
+    """Every SRT_* value of the mirror {name: value} the header does not define with that value."""
+    return [f"{name}: {value}, the header's {header['constants'].get(name, 'nothing')}" for name, value in mirrored.items()
+            if header["constants"].get(name) != value]
+
+
+def mirrored_constants():
+    return {name: value for module in (abi, lib) for name, value in vars(module).items() if name.startswith("SRT_")}
+
+
+@pytest.fixture(scope="module")
+def header():
+    return parse_header(open(os.path.join(INCLUDE, "srt.h")).read())
+
+
+@pytest.fixture(scope="module")
+def layouts(header, tmp_path_factory):
+    """sizeof and offsetof of every field of every struct of the header, from a C program the host compiler builds."""
+    lines = ["#include <stdio.h>", "#include <stddef.h>", '#include "srt.h"', "int main(void) {"]
+    for name, fields in header["structs"].items():
+        lines.append(f'    printf("{name} %zu\\n", sizeof({name}));')
+        lines += [f'    printf("{name}.{f} %zu %zu\\n", offsetof({name}, {f}), sizeof((({name}*)0)->{f}));' for f in fields]
+    lines += ["    return 0;", "}"]
+    d = tmp_path_factory.mktemp("abi_mirror")
+    (d / "layout.c").write_text("\n".join(lines) + "\n")
+    subprocess.run(["gcc", "-std=c11", "-Wall", "-Wextra", "-I" + INCLUDE, "-o", str(d / "layout"), str(d / "layout.c")], check=True)
+    out = {}
+    for line in subprocess.run([str(d / "layout")], check=True, capture_output=True, text=True).stdout.splitlines():
+        what, *numbers = line.split()
+        name, _, field = what.partition(".")
+        if field:
+            out[name][1].append((field, int(numbers[0]), int(numbers[1])))
+        else:
+            out[name] = (int(numbers[0]), [])
+    return out
+
+
+def test_prototypes_match_the_header(header):
+    assert len(header["prototypes"]) == 91 and len(header["structs"]) == 17
+    assert check_prototypes(abi.PROTOTYPES, abi.STRUCTS, header) == []
+    assert list(abi.PROTOTYPES) == [name for name, _, _ in header["prototypes"]], "the table follows the header's order"
+    assert lib.ABI_SYMBOLS == tuple(abi.PROTOTYPES)
+    for name, (restype, argtypes) in abi.PROTOTYPES.items():      # what ctypes accepts: a list of types, a type or None
+        assert isinstance(argtypes, list) and (restype is None or isinstance(restype, type(C.c_int))), name
+
+
+def test_struct_layouts_match_the_compiler(header, layouts):
+    assert set(layouts) == set(header["structs"]) and all(len(layouts[n][1]) == len(f) for n, f in header["structs"].items())
+    assert check_structs(abi.STRUCTS, header, layouts) == []
+
+
+def test_constants_match_the_header(header):
+    mirrored = mirrored_constants()
+    assert check_constants(mirrored, header) == []
+    defines = {n for n in header["constants"] if n.endswith(("_MAX", "_SELF")) or n == "SRT_ABI_VERSION"}
+    assert {"SRT_MULTI_HIT_MAX", "SRT_PATH_DEPTH_MAX", "SRT_AO_DIRS_MAX", "SRT_AO_ROT_MAX", "SRT_SHADOW_SELF", "SRT_AO_SKIP_SELF", "SRT_ABI_VERSION"} <= defines
+    assert defines <= set(mirrored), defines - set(mirrored)
+    assert {"SRT_OK", "SRT_ERR_OOM", "SRT_FLAG_SMOOTH_NORMALS", "SRT_FLAG_FRAMES_IN_FLIGHT"} <= set(mirrored)
+    assert lib.MULTI_HIT_MAX == header["constants"]["SRT_MULTI_HIT_MAX"]
+
+
+def _named(errors, name):
+    return any(e.startswith(name) for e in errors)
+
+
+def test_the_checks_can_fail(header, layouts):
+    """Doctored in-memory copies of the mirror: each fault is reported, and by name."""
+    def doctored(name, change):
+        table = dict(abi.PROTOTYPES)
+        restype, argtypes = table[name]
+        table[name] = change(restype, list(argtypes))
+        errors = check_prototypes(table, abi.STRUCTS, header)
+        assert errors and all(e.startswith(name + ":") for e in errors), errors
+        return errors
+
+    def swap(restype, a):
+        a[2], a[3] = a[3], a[2]
+        return restype, a
+    doctored("srt_render_paths", swap)                                      # ..., srt_path_desc*, float*, ... swapped
+    assert "argtypes for" in doctored("srt_render_device", lambda r, a: (r, a[:-1]))[0]
+    doctored("srt_scene_pose", lambda r, a: (r, a[:1] + a[2:]))             # one dropped from the middle
+    wide = doctored("srt_trace_rays", lambda r, a: (r, [a[0], C.c_uint64] + a[2:]))
+    assert "argument 1 (uint32_t n)" in wide[0]
+    doctored("srt_trace_rays_device", lambda r, a: (r, a[:2] + [C.POINTER(C.c_float)] + a[3:]))     # d_rays as a typed pointer
+    doctored("srt_host_free", lambda r, a: (C.c_int, a))
+    doctored("srt_scene_device_bytes", lambda r, a: (C.c_uint32, a))
+    missing = {k: v for k, v in abi.PROTOTYPES.items() if k != "srt_sync"}
+    assert _named(check_prototypes(missing, abi.STRUCTS, header), "srt_sync: in the header")
+    assert _named(check_prototypes({**abi.PROTOTYPES, "srt_extra": (None, [])}, abi.STRUCTS, header), "srt_extra: in the table")
+
+    fields = list(abi.AoDesc._fields_)
+    fields[0], fields[1] = fields[1], fields[0]
+    reordered = type("AoDesc", (C.Structure,), {"_fields_": fields})
+    errors = check_structs({**abi.STRUCTS, "srt_ao_desc": reordered}, header, layouts)
+    assert errors and all(e.startswith("srt_ao_desc") for e in errors) and _named(errors, "srt_ao_desc.dirs: offset 0"), errors
+    narrow = type("Refraction", (C.Structure,), {"_fields_": [("ior", C.c_uint32), ("flags", C.c_uint32)]})
+    errors = check_structs({**abi.STRUCTS, "srt_refraction": narrow}, header, layouts)
+    assert _named(errors, "srt_refraction: size 8") and _named(errors, "srt_refraction.ior") and _named(errors, "srt_refraction.flags"), errors
+    assert _named(check_structs({k: v for k, v in abi.STRUCTS.items() if k != "srt_stats"}, header, layouts), "srt_stats: in the header")
+    assert _named(check_structs({**abi.STRUCTS, "srt_more": abi.Stats}, header, layouts), "srt_more: in STRUCTS")
+
+    errors = check_constants({**mirrored_constants(), "SRT_AO_DIRS_MAX": abi.SRT_AO_DIRS_MAX + 1}, header)
+    assert len(errors) == 1 and errors[0].startswith("SRT_AO_DIRS_MAX: 1025")
+    assert _named(check_constants({"SRT_FLAG_NO_TIMING": 3}, header), "SRT_FLAG_NO_TIMING") and _named(check_constants({"SRT_UNKNOWN": 0}, header), "SRT_UNKNOWN")
