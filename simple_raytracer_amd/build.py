@@ -10,6 +10,9 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_HIP = os.path.join(HERE, "libsrt_hip.so")
+HIP_SRC = os.path.join(CSRC, "srt_hip.hip")
+# What libsrt_hip.so, and every measurement variant of it, is compiled from: the one translation unit and the headers it includes.
+HIP_DEPS = [HIP_SRC] + [os.path.join(CSRC, f) for f in ("srt_device.h", "srt_kernels.h", "srt_packet.h", "srt_query.h")] + [os.path.join(HERE, "..", "include", "srt.h")]
 
 # -ffp-contract=off is part of the numerical contract: FMA contraction changes hit results
 # (SURVEY.md H1).  Correctly rounded f32 divide / sqrt are hipcc defaults and must stay on.
@@ -32,11 +35,9 @@ def _stale(target, sources):
 
 
 def build_hip(force=False, verbose=False):
-    srcs = [os.path.join(CSRC, "srt_hip.hip")]
-    deps = srcs + [os.path.join(CSRC, "srt_device.h"), os.path.join(CSRC, "srt_kernels.h"), os.path.join(CSRC, "srt_packet.h"), os.path.join(CSRC, "srt_query.h"), os.path.join(HERE, "..", "include", "srt.h")]
-    if not force and not _stale(LIB_HIP, deps):
+    if not force and not _stale(LIB_HIP, HIP_DEPS):
         return LIB_HIP
-    cmd = [hipcc()] + HIPCC_FLAGS + ["-o", LIB_HIP] + srcs
+    cmd = [hipcc()] + HIPCC_FLAGS + ["-o", LIB_HIP, HIP_SRC]
     if verbose:
         print(" ".join(cmd))
     r = subprocess.run(cmd, capture_output=True, text=True)
@@ -112,10 +113,9 @@ def build_c_example(force=False, verbose=False):
 def stale_artefacts():
     """Names of the product's native artefacts that are missing or older than their sources (nothing is built)."""
     hdir = os.path.join(CSRC, "host")
-    hip_deps = [os.path.join(CSRC, f) for f in ("srt_hip.hip", "srt_device.h", "srt_kernels.h", "srt_packet.h", "srt_query.h")] + [os.path.join(HERE, "..", "include", "srt.h")]
     host_deps = [os.path.join(hdir, f) for f in ("srt_host.cpp", "srt_jpeg.cpp", "srt_host_c.cpp", "srt_host.h")]
     out = []
-    if _stale(LIB_HIP, hip_deps):
+    if _stale(LIB_HIP, HIP_DEPS):
         out.append("libsrt_hip.so")
     if _stale(LIB_HOST, host_deps):
         out.append("libsrt_host.so")
@@ -129,7 +129,7 @@ def build_all(force=False, verbose=False):
 def build_diag(verbose=False):
     """Diagnostic build with in-kernel cycle stamps (-DSRT_DIAG): libsrt_hip_diag.so, never loaded by the product."""
     out = os.path.join(HERE, "libsrt_hip_diag.so")
-    cmd = [hipcc()] + HIPCC_FLAGS + ["-DSRT_DIAG", "-o", out, os.path.join(CSRC, "srt_hip.hip")]
+    cmd = [hipcc()] + HIPCC_FLAGS + ["-DSRT_DIAG", "-o", out, HIP_SRC]
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode:
         sys.stderr.write(r.stdout + r.stderr)
@@ -143,10 +143,9 @@ LIB_SURFACE_LANE = os.path.join(HERE, "libsrt_hip_surface_lane.so")
 def build_surface_lane_stores(force=False):
     """The surface kernels' other store form (-DSRT_SURFACE_LANE_STORES, srt_query.h): libsrt_hip_surface_lane.so, never loaded by the
     product; tools/ray_query_probe.py --surface times it beside the shipped library."""
-    deps = [os.path.join(CSRC, f) for f in ("srt_hip.hip", "srt_device.h", "srt_kernels.h", "srt_packet.h", "srt_query.h")] + [os.path.join(HERE, "..", "include", "srt.h")]
-    if not force and not _stale(LIB_SURFACE_LANE, deps):
+    if not force and not _stale(LIB_SURFACE_LANE, HIP_DEPS):
         return LIB_SURFACE_LANE
-    cmd = [hipcc()] + HIPCC_FLAGS + ["-DSRT_SURFACE_LANE_STORES", "-o", LIB_SURFACE_LANE, os.path.join(CSRC, "srt_hip.hip")]
+    cmd = [hipcc()] + HIPCC_FLAGS + ["-DSRT_SURFACE_LANE_STORES", "-o", LIB_SURFACE_LANE, HIP_SRC]
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode:
         sys.stderr.write(r.stdout + r.stderr)
@@ -162,10 +161,9 @@ def build_ao_deal(spread, force=False):
     spread deal from 0 directions on (libsrt_hip_ao_spread.so) or never (libsrt_hip_ao_block.so).  Never loaded by the product;
     tools/ray_query_probe.py --ao times both beside the shipped rule."""
     out = LIB_AO_DEAL[bool(spread)]
-    deps = [os.path.join(CSRC, f) for f in ("srt_hip.hip", "srt_device.h", "srt_kernels.h", "srt_packet.h", "srt_query.h")] + [os.path.join(HERE, "..", "include", "srt.h")]
-    if not force and not _stale(out, deps):
+    if not force and not _stale(out, HIP_DEPS):
         return out
-    cmd = [hipcc()] + HIPCC_FLAGS + ["-DSRT_AO_SPREAD_FROM=" + ("0u" if spread else "0xFFFFFFFFu"), "-o", out, os.path.join(CSRC, "srt_hip.hip")]
+    cmd = [hipcc()] + HIPCC_FLAGS + ["-DSRT_AO_SPREAD_FROM=" + ("0u" if spread else "0xFFFFFFFFu"), "-o", out, HIP_SRC]
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode:
         sys.stderr.write(r.stdout + r.stderr)

@@ -39,6 +39,102 @@ __device__ __forceinline__ void load_range(const QueryRange tr, size_t i, float&
 }
 
 // =================================================================================================
+// The statements AROUND the walk, each stated once: every query kernel below is these pieces in its own order, with its own walk
+// (query_walk, any_hit_range) or phase 2 between them.
+// Why they fill objects the caller declares, and take no __restrict__: DESIGN.md s5, "One statement of the code around the walk".
+// =================================================================================================
+// A lane's place in a 1-D launch of 256 threads -- its number in its wave, the wave's number in the workgroup -- and the contiguous
+// deal of rays to waves: the wave's first ray, and ray base + lane as the launch's own thread number for a kernel that needs no base.
+__device__ __forceinline__ uint32_t wave_lane() { return threadIdx.x & 63; }
+__device__ __forceinline__ uint32_t wave_index() { return threadIdx.x >> 6; }
+__device__ __forceinline__ size_t wave_base(const uint32_t wave) { return (size_t)blockIdx.x * 256 + wave * 64; }
+__device__ __forceinline__ size_t lane_ray() { return (size_t)blockIdx.x * 256 + threadIdx.x; }
+// The deal of the shaded calls (QueryShade::spread, QueryAo::spread): without spread the contiguous one; with it a wave owns 8 groups
+// of 8 consecutive rays, the groups a 64th of the batch apart.  The shadow walks of a batch are few long ones among many short ones, and
+// the long ones sit together (the pixels in one object's shadow); a wave of 64 such neighbours walks them one round after the other
+// while the rest of the machine has left.  Groups of 8 neighbours keep most of phase 1's coherence and put a region's hits into 8 times
+// as many waves.  Called with any lane of the wave: the transposed row stores need the rays of other lanes.
+struct RayDeal {
+    uint32_t spread;
+    size_t n_waves, wv;
+    __device__ __forceinline__ size_t operator()(const uint32_t l) const { return spread ? ((size_t)(l >> 3) * n_waves + wv) * 8 + (l & 7u) : wv * 64 + l; }
+};
+__device__ __forceinline__ RayDeal ray_deal(const uint32_t spread, const uint32_t wave) {
+    return RayDeal{ spread, (size_t)gridDim.x * 4, (size_t)blockIdx.x * 4 + wave };
+}
+
+// What a lane loads before its walk: its ray, its t interval and its visibility mask.  A lane without a ray gets a ray that is never
+// walked.  Two conventions for the interval: query_ray<RANGE> is the compile-time one -- the builds without RANGE load nothing and carry
+// (0, 0), which nothing reads; query_ray_opt is the run-time one of the kernels that always run the RANGE walk -- a NULL tr.t runs as
+// (NaN, NaN), which bounds nothing.  ray_mask: the per-ray masks of the masked calls (NULL: all ones).
+struct QueryRay { V3 o, d; float t_min, t_max; uint32_t m; };
+template <bool OPT, bool RANGE>
+__device__ __forceinline__ void load_query_ray(QueryRay& r, const float* rays, const uint32_t wide, const QueryRange tr, const size_t ri, const bool live,
+                                               const uint32_t* ray_mask) {
+    r.o = mk(0.0f, 0.0f, 0.0f); r.d = mk(0.0f, 0.0f, 1.0f);
+    r.t_min = OPT ? __builtin_nanf("") : 0.0f; r.t_max = r.t_min;
+    r.m = 0xFFFFFFFFu;
+    if (live) load_ray(rays, ri, wide != 0, r.o, r.d);
+    if ((OPT ? tr.t != nullptr : RANGE) && live) load_range(tr, ri, r.t_min, r.t_max);
+    if (ray_mask && live) r.m = ray_mask[ri];
+}
+template <bool RANGE>
+__device__ __forceinline__ void query_ray(QueryRay& r, const float* rays, const uint32_t wide, const QueryRange tr, const size_t ri, const bool live) {
+    load_query_ray<false, RANGE>(r, rays, wide, tr, ri, live, nullptr);
+}
+__device__ __forceinline__ void query_ray_opt(QueryRay& r, const float* rays, const uint32_t wide, const QueryRange tr, const size_t ri, const bool live,
+                                              const uint32_t* ray_mask = nullptr) {
+    load_query_ray<true, true>(r, rays, wide, tr, ri, live, ray_mask);
+}
+
+// A merged key (hit_key below; ~0: a miss) as the lane that owns the ray reads it.  winner_of: whether the ray hit, and the triangle.
+// winner_at: also the winner's t with its own bits (incl. the sign of a zero, which the key does not hold) -- the walk's function on the
+// walk's inputs, the lane's own ray, so the walk's value and hence in range -- and, BARY, calculateBarycentricCoords at that hit point.
+struct Winner { bool is_hit; int32_t id; };
+__device__ __forceinline__ Winner winner_of(const unsigned long long key) {
+    const bool is_hit = key != ~0ull;
+    return Winner{ is_hit, is_hit ? (int32_t)(uint32_t)key : -1 };
+}
+struct WinnerAt { int32_t id; float t; V3 bc; };      // (a miss: -1, +inf, zeros)
+template <bool BARY>
+__device__ __forceinline__ void winner_at(WinnerAt& w, const float4* tris4, const unsigned long long key, const V3 o, const V3 d) {
+    w.id = -1;
+    w.t = __builtin_inff();
+    w.bc = mk(0.0f, 0.0f, 0.0f);
+    if (key != ~0ull) {
+        w.id = (int32_t)(uint32_t)key;
+        V3 p1, e1, e2;
+        load_tri_edges(tris4, (size_t)w.id, p1, e1, e2);
+        w.t = ray_triangle(o, d, p1, e1, e2);
+        if (BARY) w.bc = barycentric(p1, e1, e2, o + d * w.t);
+    }
+}
+
+// The hit_id / t row of a ray; either output may be NULL.  Called by the lanes that have a row.
+__device__ __forceinline__ void store_hit(int32_t* hit_id, float* t_out, const size_t at, const int32_t id, const float t) {
+    if (hit_id) hit_id[at] = id;
+    if (t_out) t_out[at] = t;
+}
+
+// The counters a kernel leaves with (COUNT), laid out like a render's: [1] / [2] node / triangle tests of the closest-hit walks, and,
+// for the kernels with a phase 2, [3] / [4] those of its occlusion walks.  (The hit rays go to their shard through count_hits.)
+template <bool COUNT>
+__device__ __forceinline__ void count_walks(unsigned long long* counters, const unsigned long long& n_node, const unsigned long long& n_tri) {
+    if (COUNT) { wave_add(counters + 1, n_node); wave_add(counters + 2, n_tri); }
+}
+template <bool COUNT>
+__device__ __forceinline__ void count_walks(unsigned long long* counters, const unsigned long long& n_node, const unsigned long long& n_tri,
+                                            const unsigned long long& n_node_s, const unsigned long long& n_tri_s) {
+    if (COUNT) { wave_add(counters + 1, n_node); wave_add(counters + 2, n_tri); wave_add(counters + 3, n_node_s); wave_add(counters + 4, n_tri_s); }
+}
+
+// The surface of a lane without a hit: black, no normal, no material.  sh = 1 where it goes on into shading (it shades to nothing),
+// sh = 0 where it is a miss row of the surface outputs.
+__device__ __forceinline__ void no_surface(Surface& f, const float sh) {
+    f.color = mk(0.0f, 0.0f, 0.0f); f.nrm = f.color; f.ka = 0.0f; f.ks = 0.0f; f.sh = sh;
+}
+
+// =================================================================================================
 // Closest hit of caller-supplied rays: the oracle's closest_in_tree over the objects in order, with the ray's own origin.
 // One ray per lane.  The lanes of a wave walk on their own (the rays may be unrelated); a lane whose ray passes a leaf's box pushes
 // (triangle, lane) pairs into the wave's LDS queue, and whenever 64 pairs are queued the whole wave runs the general Moller-Trumbore
@@ -170,93 +266,51 @@ __device__ __forceinline__ void query_walk(const DevScene& s, const bool live, c
     __builtin_amdgcn_wave_barrier();
 }
 
+// The body of k_query_closest and k_query_closest_masked, as query_path_rays is the path kernels'.
 // RANGE: the closest hit among the candidates in range of the ray's own interval tr (the winner is in range, so its recomputed t is too).
+// MASK (srt_trace_rays_masked): ray i is walked with qm.ray[i] (a NULL array: all ones) against qm.obj; a mask that selects nothing leaves
+// the lane without a node to test, so it is a miss.  The MASK build is a RANGE build under the run-time convention: a NULL interval runs
+// as (NaN, NaN), which bounds nothing, as in k_query_multi.  counters: of the walk as it runs -- a hidden object's root is neither tested
+// nor counted.
+template <bool COUNT, bool BARY, bool RANGE, bool MASK>
+__device__ __forceinline__ void query_closest_rays(const DevScene& s, const uint32_t n_rays, const float* __restrict__ rays, const uint32_t wide,
+                                                   int32_t* __restrict__ hit_id, float* __restrict__ t_out, float* __restrict__ bary,
+                                                   unsigned long long* __restrict__ counters, const QueryRange tr, const QueryMask qm = QueryMask{}) {
+    static_assert(RANGE || !MASK, "the masked walk is the RANGE walk");
+    __shared__ uint32_t q_all[4][QCAP];
+    __shared__ unsigned long long best_all[256];
+    __shared__ float ray_all[4][RANGE ? 8 : 6][64];
+    const uint32_t lane = wave_lane(), wave = wave_index();
+    unsigned long long* best = best_all + wave * 64;
+    const size_t ri = lane_ray();
+    const bool live = ri < (size_t)n_rays;
+    unsigned long long n_node = 0, n_tri = 0;
+    QueryRay r;
+    if (MASK) query_ray_opt(r, rays, wide, tr, ri, live, qm.ray);
+    else query_ray<RANGE>(r, rays, wide, tr, ri, live);
+    const V3 o = r.o, d = r.d;
+    query_walk<COUNT, RANGE, MergeClosest, MASK>(s, live, o, d, lane, q_all[wave], MergeClosest{ best }, ray_all[wave], n_node, n_tri, r.t_min, r.t_max, qm.obj, r.m);
+    const float4* tris4 = reinterpret_cast<const float4*>(s.tris);
+    WinnerAt h;
+    winner_at<BARY>(h, tris4, live ? best[lane] : ~0ull, o, d);
+    if (live) {
+        store_hit(hit_id, t_out, ri, h.id, h.t);
+        if (BARY) { bary[ri * 3] = h.bc.x; bary[ri * 3 + 1] = h.bc.y; bary[ri * 3 + 2] = h.bc.z; }
+    }
+    if (counters) count_hits(counters, h.id >= 0, blockIdx.x);
+    count_walks<COUNT>(counters, n_node, n_tri);
+}
 template <bool COUNT, bool BARY, bool RANGE>
 __global__ __launch_bounds__(256) void k_query_closest(DevScene s, uint32_t n_rays, const float* __restrict__ rays, uint32_t wide,
                                                        int32_t* __restrict__ hit_id, float* __restrict__ t_out, float* __restrict__ bary,
                                                        unsigned long long* __restrict__ counters, QueryRange tr) {
-    __shared__ uint32_t q_all[4][QCAP];
-    __shared__ unsigned long long best_all[256];
-    __shared__ float ray_all[4][RANGE ? 8 : 6][64];
-    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    unsigned long long* best = best_all + wave * 64;
-    const size_t ri = (size_t)blockIdx.x * 256 + threadIdx.x;
-    const bool live = ri < (size_t)n_rays;
-    unsigned long long n_node = 0, n_tri = 0;
-    V3 o = mk(0.0f, 0.0f, 0.0f), d = mk(0.0f, 0.0f, 1.0f);
-    float t_min = 0.0f, t_max = 0.0f;
-    if (live) load_ray(rays, ri, wide != 0, o, d);
-    if (RANGE && live) load_range(tr, ri, t_min, t_max);
-    query_walk<COUNT, RANGE>(s, live, o, d, lane, q_all[wave], MergeClosest{ best }, ray_all[wave], n_node, n_tri, t_min, t_max);
-    const float4* tris4 = reinterpret_cast<const float4*>(s.tris);
-    bool is_hit = false;
-    if (live) {
-        const unsigned long long key = best[lane];
-        int32_t id = -1;
-        float t = __builtin_inff();
-        V3 bc = mk(0.0f, 0.0f, 0.0f);
-        if (key != ~0ull) {
-            id = (int32_t)(uint32_t)key;
-            // the winner's t with its own bits (incl. the sign of a zero): same function, same inputs
-            V3 p1, e1, e2;
-            load_tri_edges(tris4, (size_t)id, p1, e1, e2);
-            t = ray_triangle(o, d, p1, e1, e2);
-            if (BARY) bc = barycentric(p1, e1, e2, o + d * t);       // calculateBarycentricCoords at the hit point
-        }
-        if (hit_id) hit_id[ri] = id;
-        if (t_out) t_out[ri] = t;
-        if (BARY) { bary[ri * 3] = bc.x; bary[ri * 3 + 1] = bc.y; bary[ri * 3 + 2] = bc.z; }
-        is_hit = id >= 0;
-    }
-    if (counters) count_hits(counters, is_hit, blockIdx.x);
-    if (COUNT) { wave_add(counters + 1, n_node); wave_add(counters + 2, n_tri); }
+    query_closest_rays<COUNT, BARY, RANGE, false>(s, n_rays, rays, wide, hit_id, t_out, bary, counters, tr);
 }
-
-// srt_trace_rays_masked: k_query_closest's statements on the MASK walk.  Ray i is walked with qm.ray[i] (a NULL array: all ones) against
-// qm.obj; a mask that selects nothing leaves the lane without a node to test, so it is a miss.  The walk is the RANGE build; a NULL
-// interval runs as (NaN, NaN), which bounds nothing, as in k_query_multi.  counters: as k_query_closest's, of the walk as it runs --
-// a hidden object's root is neither tested nor counted.
 template <bool COUNT, bool BARY>
 __global__ __launch_bounds__(256) void k_query_closest_masked(DevScene s, uint32_t n_rays, const float* __restrict__ rays, uint32_t wide,
                                                               int32_t* __restrict__ hit_id, float* __restrict__ t_out, float* __restrict__ bary,
                                                               unsigned long long* __restrict__ counters, QueryRange tr, QueryMask qm) {
-    __shared__ uint32_t q_all[4][QCAP];
-    __shared__ unsigned long long best_all[256];
-    __shared__ float ray_all[4][8][64];
-    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    unsigned long long* best = best_all + wave * 64;
-    const size_t ri = (size_t)blockIdx.x * 256 + threadIdx.x;
-    const bool live = ri < (size_t)n_rays;
-    unsigned long long n_node = 0, n_tri = 0;
-    V3 o = mk(0.0f, 0.0f, 0.0f), d = mk(0.0f, 0.0f, 1.0f);
-    float t_min = __builtin_nanf(""), t_max = __builtin_nanf("");
-    uint32_t m = 0xFFFFFFFFu;
-    if (live) load_ray(rays, ri, wide != 0, o, d);
-    if (tr.t && live) load_range(tr, ri, t_min, t_max);
-    if (qm.ray && live) m = qm.ray[ri];
-    query_walk<COUNT, true, MergeClosest, true>(s, live, o, d, lane, q_all[wave], MergeClosest{ best }, ray_all[wave], n_node, n_tri, t_min, t_max, qm.obj, m);
-    const float4* tris4 = reinterpret_cast<const float4*>(s.tris);
-    bool is_hit = false;
-    if (live) {
-        const unsigned long long key = best[lane];
-        int32_t id = -1;
-        float t = __builtin_inff();
-        V3 bc = mk(0.0f, 0.0f, 0.0f);
-        if (key != ~0ull) {
-            id = (int32_t)(uint32_t)key;
-            // the winner's t with its own bits (incl. the sign of a zero): same function, same inputs
-            V3 p1, e1, e2;
-            load_tri_edges(tris4, (size_t)id, p1, e1, e2);
-            t = ray_triangle(o, d, p1, e1, e2);
-            if (BARY) bc = barycentric(p1, e1, e2, o + d * t);       // calculateBarycentricCoords at the hit point
-        }
-        if (hit_id) hit_id[ri] = id;
-        if (t_out) t_out[ri] = t;
-        if (BARY) { bary[ri * 3] = bc.x; bary[ri * 3 + 1] = bc.y; bary[ri * 3 + 2] = bc.z; }
-        is_hit = id >= 0;
-    }
-    if (counters) count_hits(counters, is_hit, blockIdx.x);
-    if (COUNT) { wave_add(counters + 1, n_node); wave_add(counters + 2, n_tri); }
+    query_closest_rays<COUNT, BARY, true, true>(s, n_rays, rays, wide, hit_id, t_out, bary, counters, tr, qm);
 }
 
 // =================================================================================================
@@ -267,9 +321,9 @@ __global__ __launch_bounds__(256) void k_query_closest_masked(DevScene s, uint32
 // Slot j keeps the minimum of everything offered to it and passes on everything else (and one ~0), so by induction it ends as the
 // (j + 1)-th smallest key of the ray, whatever the interleaving of the lanes that offer; keys of one ray differ because ids differ, and
 // a qualifying t is >= 0 or -0 (srt_device.h), so key order is (t with -0 as +0, id) order.  What falls off slot k - 1 is dropped.
-// After the walk the owning lane turns each kept key into (id, t): t is recomputed from the lane's own ray, as k_query_closest does for
-// its winner, because the key holds -0 as +0.  Rows leave TRANSPOSED: the (id, t bits) pairs go back into the lane's own slots, and the
-// wave then stores its 64 x k ids and its 64 x k t as 64 consecutive words per instruction (row i of the output IS words i*k .. i*k+k-1);
+// After the walk the owning lane turns each kept key into (id, t) through winner_at, as k_query_closest does for its winner: t is
+// recomputed from the lane's own ray, because the key holds -0 as +0.  Rows leave TRANSPOSED: the (id, t bits) pairs go back into the
+// lane's own slots, and the wave then stores its 64 x k ids and its 64 x k t as 64 consecutive words per instruction (row i of the output IS words i*k .. i*k+k-1);
 // SRT_MULTI_LANE_STORES builds the other choice, every lane storing its own row (measured: DESIGN.md s5).  bary, 3 floats a hit, is
 // stored by the owning lane either way.
 // KB: the slots the build reserves (k <= KB): 4, 8 or 16 -- 8, 16 or 32 KB of LDS a workgroup -- so that a small k keeps its occupancy.
@@ -302,45 +356,33 @@ __global__ __launch_bounds__(256) void k_query_multi(DevScene s, uint32_t n_rays
     __shared__ unsigned long long slot_all[4][KB][64];
     __shared__ uint32_t cnt_all[256];
     __shared__ float ray_all[4][8][64];
-    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t lane = wave_lane(), wave = wave_index();
     unsigned long long (*slot)[64] = slot_all[wave];
     uint32_t* cnt = cnt_all + wave * 64;
     k = k < (uint32_t)KB ? k : (uint32_t)KB;            // (the host picks KB >= k)
-    const size_t base = (size_t)blockIdx.x * 256 + wave * 64, ri = base + lane;
+    const size_t base = wave_base(wave), ri = base + lane;
     const bool live = ri < (size_t)n_rays;
     unsigned long long n_node = 0, n_tri = 0;
-    V3 o = mk(0.0f, 0.0f, 0.0f), d = mk(0.0f, 0.0f, 1.0f);
-    float t_min = __builtin_nanf(""), t_max = __builtin_nanf("");
-    if (live) load_ray(rays, ri, wide != 0, o, d);
-    if (tr.t && live) load_range(tr, ri, t_min, t_max);
-    query_walk<COUNT, true>(s, live, o, d, lane, q_all[wave], MergeMulti{ slot, cnt, k }, ray_all[wave], n_node, n_tri, t_min, t_max);
+    QueryRay r;
+    query_ray_opt(r, rays, wide, tr, ri, live);
+    const V3 o = r.o, d = r.d;
+    query_walk<COUNT, true>(s, live, o, d, lane, q_all[wave], MergeMulti{ slot, cnt, k }, ray_all[wave], n_node, n_tri, r.t_min, r.t_max);
     const float4* tris4 = reinterpret_cast<const float4*>(s.tris);
     const bool is_hit = live && cnt[lane] != 0u;
     if (n_hits && live) n_hits[ri] = cnt[lane];
     if (hit_id || t_out || BARY) {
         for (uint32_t j = 0; j < k; j++) {
-            const unsigned long long key = slot[j][lane];
-            int32_t id = -1;
-            float t = __builtin_inff();
-            V3 bc = mk(0.0f, 0.0f, 0.0f);
-            if (key != ~0ull) {
-                id = (int32_t)(uint32_t)key;
-                // the hit's t with its own bits (incl. the sign of a zero): same function, same inputs
-                V3 p1, e1, e2;
-                load_tri_edges(tris4, (size_t)id, p1, e1, e2);
-                t = ray_triangle(o, d, p1, e1, e2);
-                if (BARY) bc = barycentric(p1, e1, e2, o + d * t);       // calculateBarycentricCoords at THIS hit's point
-            }
+            WinnerAt h;
+            winner_at<BARY>(h, tris4, slot[j][lane], o, d);      // (t and bary of THIS hit)
             if (live) {
                 const size_t at = ri * k + j;
 #ifdef SRT_MULTI_LANE_STORES
-                if (hit_id) hit_id[at] = id;
-                if (t_out) t_out[at] = t;
+                store_hit(hit_id, t_out, at, h.id, h.t);
 #endif
-                if (BARY) { bary[at * 3] = bc.x; bary[at * 3 + 1] = bc.y; bary[at * 3 + 2] = bc.z; }
+                if (BARY) { bary[at * 3] = h.bc.x; bary[at * 3 + 1] = h.bc.y; bary[at * 3 + 2] = h.bc.z; }
             }
 #ifndef SRT_MULTI_LANE_STORES
-            slot[j][lane] = ((unsigned long long)__float_as_uint(t) << 32) | (uint32_t)id;
+            slot[j][lane] = ((unsigned long long)__float_as_uint(h.t) << 32) | (uint32_t)h.id;
 #endif
         }
 #ifndef SRT_MULTI_LANE_STORES
@@ -358,7 +400,7 @@ __global__ __launch_bounds__(256) void k_query_multi(DevScene s, uint32_t n_rays
 #endif
     }
     if (counters) count_hits(counters, is_hit, blockIdx.x);
-    if (COUNT) { wave_add(counters + 1, n_node); wave_add(counters + 2, n_tri); }
+    count_walks<COUNT>(counters, n_node, n_tri);
 }
 
 // =================================================================================================
@@ -366,43 +408,38 @@ __global__ __launch_bounds__(256) void k_query_multi(DevScene s, uint32_t n_rays
 // One ray per lane, each on its own walk (any_hit_range, filtered slab test; the skipped object's node range is stepped over).
 // An entry of skip_obj outside [0, n_objects) skips nothing.
 // RANGE: only a result in range of the ray's own interval tr blocks.
+// MASK (srt_occluded_masked): the MASK walk with qm.ray[i] against qm.obj; skip_obj still leaves its object out, on top of the masks.  One
+// build: the RANGE walk under the run-time convention, a NULL interval running as (NaN, NaN).
+// The loads keep this order -- the ray, the skipped object's range, the interval, the mask -- and so do not go through query_ray: the
+// order is what the compiler schedules, and k_query_any_masked, the one query kernel that is no template, lies among the render kernels.
 // =================================================================================================
+template <bool RANGE, bool MASK>
+__device__ __forceinline__ void query_any_rays(const DevScene& s, const uint32_t n_rays, const float* __restrict__ rays, const uint32_t wide,
+                                               const int32_t* __restrict__ skip_obj, uint8_t* __restrict__ occluded, const QueryRange tr, const QueryMask qm = QueryMask{}) {
+    static_assert(RANGE || !MASK, "the masked walk is the RANGE walk");
+    const size_t ri = lane_ray();
+    if (ri >= (size_t)n_rays) return;
+    V3 o, d;
+    load_ray(rays, ri, wide != 0, o, d);
+    int2 self = make_int2(-1, -1);
+    if (skip_obj) {
+        const int32_t k = skip_obj[ri];
+        if (k >= 0 && (uint32_t)k < s.n_objects) self = s.obj_range[k];
+    }
+    float t_min = MASK ? __builtin_nanf("") : 0.0f, t_max = t_min;
+    if (MASK ? tr.t != nullptr : RANGE) load_range(tr, ri, t_min, t_max);
+    const uint32_t m = MASK && qm.ray ? qm.ray[ri] : 0xFFFFFFFFu;
+    unsigned long long n_node = 0, n_tri = 0;
+    occluded[ri] = any_hit_range<false, true, RANGE, MASK>(s, self, o, d, n_node, n_tri, t_min, t_max, qm.obj, m) ? 1 : 0;
+}
 template <bool RANGE>
 __global__ __launch_bounds__(256) void k_query_any(DevScene s, uint32_t n_rays, const float* __restrict__ rays, uint32_t wide,
                                                    const int32_t* __restrict__ skip_obj, uint8_t* __restrict__ occluded, QueryRange tr) {
-    const size_t ri = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (ri >= (size_t)n_rays) return;
-    V3 o, d;
-    load_ray(rays, ri, wide != 0, o, d);
-    int2 self = make_int2(-1, -1);
-    if (skip_obj) {
-        const int32_t k = skip_obj[ri];
-        if (k >= 0 && (uint32_t)k < s.n_objects) self = s.obj_range[k];
-    }
-    float t_min = 0.0f, t_max = 0.0f;
-    if (RANGE) load_range(tr, ri, t_min, t_max);
-    unsigned long long n_node = 0, n_tri = 0;
-    occluded[ri] = any_hit_range<false, true, RANGE>(s, self, o, d, n_node, n_tri, t_min, t_max) ? 1 : 0;
+    query_any_rays<RANGE, false>(s, n_rays, rays, wide, skip_obj, occluded, tr);
 }
-
-// srt_occluded_masked: k_query_any on the MASK walk; skip_obj still leaves its object out, on top of the masks.  One build: the RANGE
-// walk, a NULL interval running as (NaN, NaN).
 __global__ __launch_bounds__(256) void k_query_any_masked(DevScene s, uint32_t n_rays, const float* __restrict__ rays, uint32_t wide,
                                                           const int32_t* __restrict__ skip_obj, uint8_t* __restrict__ occluded, QueryRange tr, QueryMask qm) {
-    const size_t ri = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (ri >= (size_t)n_rays) return;
-    V3 o, d;
-    load_ray(rays, ri, wide != 0, o, d);
-    int2 self = make_int2(-1, -1);
-    if (skip_obj) {
-        const int32_t k = skip_obj[ri];
-        if (k >= 0 && (uint32_t)k < s.n_objects) self = s.obj_range[k];
-    }
-    float t_min = __builtin_nanf(""), t_max = __builtin_nanf("");
-    if (tr.t) load_range(tr, ri, t_min, t_max);
-    const uint32_t m = qm.ray ? qm.ray[ri] : 0xFFFFFFFFu;
-    unsigned long long n_node = 0, n_tri = 0;
-    occluded[ri] = any_hit_range<false, true, true, true>(s, self, o, d, n_node, n_tri, t_min, t_max, qm.obj, m) ? 1 : 0;
+    query_any_rays<true, true>(s, n_rays, rays, wide, skip_obj, occluded, tr, qm);
 }
 
 // =================================================================================================
@@ -429,11 +466,11 @@ struct QueryShade {
     uint32_t spread;              // a wave owns 8 groups of 8 consecutive rays, the groups a 64th of the batch apart, instead of 64 consecutive rays
 };
 
-// Phase 2 of a shading query (the header comment above) for the 64 rays of one wave after their walk, as functions: k_query_path shades
-// every segment through them.  k_query_shade below still carries the same statements inline: called from there, the functions kept its
-// VGPR, scratch and LDS figures but moved the SGPR count of its four COUNT + INT_SHIN builds from 80 to 84 and rescheduled all sixteen
-// (profiles/shade_paths_kernels.txt), so that kernel was left as it was.  Whoever changes one changes the other: tests/test_gpu_shade_paths.py
-// compares the two bit for bit.  Two steps, because a kernel stores hit_id and t between them.
+// Phase 2 of a shading query (the header comment above) for the 64 rays of one wave after their walk, as functions: the path kernels
+// shade every segment and every side ray through them, k_query_ao and k_render_ao call the first.  k_query_shade below still carries the
+// same statements inline: called from there the functions keep its VGPR, scratch and LDS figures, but its RANGE builds measured 1.5 ..
+// 3 % slower on row-major rays, twice (profiles/query_refactor_probe.txt), so that kernel was left as it was.  Whoever changes one changes the
+// other: tests/test_gpu_shade_paths.py compares the two bit for bit.  Two steps, because a kernel stores hit_id and t between them.
 // shade_hits_rank: the wave's hits are ranked; a hit gets its t (the winner's own bits) and its surface, and leaves its shadow origin and
 // its object's node range in the wave's LDS by rank.  A lane without a hit gets t = +inf and a surface that shades to nothing.
 struct WaveHits { uint32_t nh, rank; };       // hits in the wave; this lane's rank among them
@@ -447,7 +484,7 @@ template <bool SMOOTH, bool SHADOW = false, bool GIVEN = false>
 __device__ __forceinline__ WaveHits shade_hits_rank(const DevScene& s, const bool is_hit, const int32_t id, const V3 o, const V3 d, float& t, Surface& f,
                                                     float (*wray)[64], const uint32_t walk_self = 0u) {
     if (!GIVEN) t = __builtin_inff();
-    f.color = mk(0.0f, 0.0f, 0.0f); f.nrm = f.color; f.ka = 0.0f; f.ks = 0.0f; f.sh = 1.0f;
+    no_surface(f, 1.0f);
     const unsigned long long hm = __ballot(is_hit);
     const uint32_t nh = (uint32_t)__popcll(hm), rank = lane_prefix(hm);
     __builtin_amdgcn_wave_barrier();                    // every lane has read its key: the slots are free
@@ -506,27 +543,22 @@ __global__ __launch_bounds__(256) void k_query_shade(DevScene s, uint32_t n_rays
     __shared__ uint32_t q_all[4][QCAP];
     __shared__ unsigned long long best_all[256];
     __shared__ float ray_all[4][RANGE ? 8 : 6][64];
-    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t lane = wave_lane(), wave = wave_index();
     unsigned long long* best = best_all + wave * 64;
     float (*wray)[64] = ray_all[wave];
-    // spread: the shadow walks of a batch are few long ones among many short ones, and the long ones sit together (the pixels in one
-    // object's shadow); a wave of 64 such neighbours walks them one round after the other while the rest of the machine has left.
-    // Groups of 8 neighbours keep most of phase 1's coherence and put a region's hits into 8 times as many waves.
-    const size_t n_waves = (size_t)gridDim.x * 4, wv = (size_t)blockIdx.x * 4 + wave;
-    const size_t ri = p.spread ? ((size_t)(lane >> 3) * n_waves + wv) * 8 + (lane & 7u) : (size_t)blockIdx.x * 256 + threadIdx.x;
+    const size_t ri = ray_deal(p.spread, wave)(lane);
     const bool live = ri < (size_t)n_rays;
     unsigned long long n_node = 0, n_tri = 0, n_node_s = 0, n_tri_s = 0;
-    V3 o = mk(0.0f, 0.0f, 0.0f), d = mk(0.0f, 0.0f, 1.0f);
-    float t_min = 0.0f, t_max = 0.0f;
-    if (live) load_ray(rays, ri, wide != 0, o, d);
-    if (RANGE && live) load_range(tr, ri, t_min, t_max);
-    query_walk<COUNT, RANGE>(s, live, o, d, lane, q_all[wave], MergeClosest{ best }, wray, n_node, n_tri, t_min, t_max);
-    const unsigned long long key = live ? best[lane] : ~0ull;
-    const bool is_hit = key != ~0ull;
-    const int32_t id = is_hit ? (int32_t)(uint32_t)key : -1;
+    QueryRay r;
+    query_ray<RANGE>(r, rays, wide, tr, ri, live);
+    const V3 o = r.o, d = r.d;
+    query_walk<COUNT, RANGE>(s, live, o, d, lane, q_all[wave], MergeClosest{ best }, wray, n_node, n_tri, r.t_min, r.t_max);
+    const Winner h = winner_of(live ? best[lane] : ~0ull);
+    const bool is_hit = h.is_hit;
+    const int32_t id = h.id;
     float t = __builtin_inff();
     Surface f;
-    f.color = mk(0.0f, 0.0f, 0.0f); f.nrm = f.color; f.ka = 0.0f; f.ks = 0.0f; f.sh = 1.0f;
+    no_surface(f, 1.0f);
     const unsigned long long hm = __ballot(is_hit);
     const uint32_t nh = (uint32_t)__popcll(hm), rank = lane_prefix(hm);
     __builtin_amdgcn_wave_barrier();                    // every lane has read its key: the slots are free
@@ -540,10 +572,7 @@ __global__ __launch_bounds__(256) void k_query_shade(DevScene s, uint32_t n_rays
         wray[3][rank] = __int_as_float(self.x); wray[4][rank] = __int_as_float(self.y);
         f = surface_at(s, id, o, d, t, SMOOTH);
     }
-    if (live) {
-        if (hit_id) hit_id[ri] = id;
-        if (t_out) t_out[ri] = t;
-    }
+    if (live) store_hit(hit_id, t_out, ri, id, t);
     V3 sum = mk(0.0f, 0.0f, 0.0f);
     for (uint32_t l0 = 0; l0 < p.n_lights; l0 += 64u) {                                             // wave-uniform
         const uint32_t m = p.n_lights - l0 < 64u ? p.n_lights - l0 : 64u;
@@ -567,7 +596,7 @@ __global__ __launch_bounds__(256) void k_query_shade(DevScene s, uint32_t n_rays
     }
     if (live) store_pixel(rgb_linear, rgb8, ri, sum, is_hit, p.reinhard, p.gamma, p.bg, 0u);
     if (counters) count_hits(counters, is_hit, blockIdx.x);
-    if (COUNT) { wave_add(counters + 1, n_node); wave_add(counters + 2, n_tri); wave_add(counters + 3, n_node_s); wave_add(counters + 4, n_tri_s); }
+    count_walks<COUNT>(counters, n_node, n_tri, n_node_s, n_tri_s);
 }
 
 // =================================================================================================
@@ -631,8 +660,9 @@ __device__ __forceinline__ V3 refract_dir(const V3 d, const V3 N, const float n)
 }
 
 // refract_dir's statements with three of their intermediates returned beside the direction: `entering`, `dv` and `k` are what the Fresnel
-// weight of the FRESNEL builds is made of (schlick_weight).  refract_dir itself is left as it is -- the builds without FRESNEL keep their
-// code -- so whoever changes one changes the other: tests/test_gpu_fresnel.py compares the two calls bit for bit.
+// weight of the FRESNEL builds is made of (schlick_weight).  refract_dir itself is left as it is: as a call of this
+// function with the three dropped, the REFRACT path builds measured 1 % slower at 16 light samples (profiles/query_refactor_probe.txt).
+// So whoever changes one changes the other: tests/test_gpu_fresnel.py compares the two calls bit for bit.
 __device__ __forceinline__ V3 refract_dir_parts(const V3 d, const V3 N, const float n, bool& entering, float& dv, float& k) {
     const float L = sqrtf(dot3(d, d)), inv = 1.0f / L;
     const V3 I = mk(d.x * inv, d.y * inv, d.z * inv);
@@ -690,39 +720,29 @@ __global__ __launch_bounds__(256) void k_query_surface(DevScene s, uint32_t n_ra
     __shared__ uint32_t q_all[4][QCAP];
     __shared__ unsigned long long best_all[256];
     __shared__ float ray_all[4][RANGE ? 8 : 6][64];
-    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t lane = wave_lane(), wave = wave_index();
     unsigned long long* best = best_all + wave * 64;
     float (*wray)[64] = ray_all[wave];
-    const size_t base = (size_t)blockIdx.x * 256 + wave * 64, ri = base + lane;
+    const size_t base = wave_base(wave), ri = base + lane;
     const bool live = ri < (size_t)n_rays;
     unsigned long long n_node = 0, n_tri = 0;
-    V3 o = mk(0.0f, 0.0f, 0.0f), d = mk(0.0f, 0.0f, 1.0f);
-    float t_min = 0.0f, t_max = 0.0f;
-    if (live) load_ray(rays, ri, wide != 0, o, d);
-    if (RANGE && live) load_range(tr, ri, t_min, t_max);
-    query_walk<COUNT, RANGE>(s, live, o, d, lane, q_all[wave], MergeClosest{ best }, wray, n_node, n_tri, t_min, t_max);
-    const unsigned long long key = live ? best[lane] : ~0ull;
-    const bool is_hit = key != ~0ull;
-    const int32_t id = is_hit ? (int32_t)(uint32_t)key : -1;
-    float t = __builtin_inff();
+    QueryRay r;
+    query_ray<RANGE>(r, rays, wide, tr, ri, live);
+    const V3 o = r.o, d = r.d;
+    query_walk<COUNT, RANGE>(s, live, o, d, lane, q_all[wave], MergeClosest{ best }, wray, n_node, n_tri, r.t_min, r.t_max);
+    WinnerAt h;
+    winner_at<false>(h, reinterpret_cast<const float4*>(s.tris), live ? best[lane] : ~0ull, o, d);
+    const bool is_hit = h.id >= 0;
     Surface f;
-    f.color = mk(0.0f, 0.0f, 0.0f); f.nrm = f.color; f.ka = 0.0f; f.ks = 0.0f; f.sh = 0.0f;
-    if (is_hit) {
-        V3 p1, e1, e2;
-        load_tri_edges(reinterpret_cast<const float4*>(s.tris), (size_t)id, p1, e1, e2);
-        t = ray_triangle(o, d, p1, e1, e2);             // the winner's t with its own bits (incl. the sign of a zero): same function, same inputs
-        f = surface_at(s, id, o, d, t, SMOOTH);
-    }
-    if (live) {
-        if (hit_id) hit_id[ri] = id;
-        if (t_out) t_out[ri] = t;
-    }
+    no_surface(f, 0.0f);
+    if (is_hit) f = surface_at(s, h.id, o, d, h.t, SMOOTH);
+    if (live) store_hit(hit_id, t_out, ri, h.id, h.t);
     if (base < (size_t)n_rays) {                        // wave-uniform; the walk is over: the rays' slots are the stage
         const size_t left = (size_t)n_rays - base;
-        surface_store(s, out, base, lane, (uint32_t)(left < 64 ? left : 64), is_hit, id, o, d, t, f, &wray[0][0]);
+        surface_store(s, out, base, lane, (uint32_t)(left < 64 ? left : 64), is_hit, h.id, o, d, h.t, f, &wray[0][0]);
     }
     if (counters) count_hits(counters, is_hit, blockIdx.x);
-    if (COUNT) { wave_add(counters + 1, n_node); wave_add(counters + 2, n_tri); }
+    count_walks<COUNT>(counters, n_node, n_tri);
 }
 
 // srt_surface_hits: the same rows for hits the caller already holds -- no walk, no node record, no queue; one lane per row.  A row whose
@@ -731,8 +751,8 @@ template <bool SMOOTH>
 __global__ __launch_bounds__(256) void k_query_surface_hits(DevScene s, uint32_t n_rays, const float* __restrict__ rays, uint32_t wide,
                                                             const int32_t* __restrict__ hit_id, const float* __restrict__ t_in, srt_surface_out out) {
     __shared__ float stage_all[4][6 * 64];
-    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const size_t base = (size_t)blockIdx.x * 256 + wave * 64, ri = base + lane;
+    const uint32_t lane = wave_lane(), wave = wave_index();
+    const size_t base = wave_base(wave), ri = base + lane;
     if (base >= (size_t)n_rays) return;                 // wave-uniform
     const bool live = ri < (size_t)n_rays;
     V3 o = mk(0.0f, 0.0f, 0.0f), d = mk(0.0f, 0.0f, 1.0f);
@@ -741,7 +761,7 @@ __global__ __launch_bounds__(256) void k_query_surface_hits(DevScene s, uint32_t
     if (live) { load_ray(rays, ri, wide != 0, o, d); id = hit_id[ri]; t = t_in[ri]; }
     const bool is_hit = id >= 0 && (uint32_t)id < s.n_tris;
     Surface f;
-    f.color = mk(0.0f, 0.0f, 0.0f); f.nrm = f.color; f.ka = 0.0f; f.ks = 0.0f; f.sh = 0.0f;
+    no_surface(f, 0.0f);
     if (is_hit) f = surface_at(s, id, o, d, t, SMOOTH);
     const size_t left = (size_t)n_rays - base;
     surface_store(s, out, base, lane, (uint32_t)(left < 64 ? left : 64), is_hit, id, o, d, t, f, stage_all[wave]);
@@ -750,7 +770,7 @@ __global__ __launch_bounds__(256) void k_query_surface_hits(DevScene s, uint32_t
 // =================================================================================================
 // Ambient occlusion (srt_ao_rays, srt_ao_hits): per hit, n_dirs occlusion rays from the hit point along a table of directions given in the
 // hit's own frame, and how many of them are blocked -- in ONE launch: the AO rays are made in registers and never reach memory.
-// One template covers both entry points.  Phase 1 -- HITS == false: query_walk exactly as k_query_closest_masked instantiates it (the RANGE
+// One template covers both entry points.  Phase 1 -- HITS == false: query_walk exactly as query_closest_rays' MASK build instantiates it (the RANGE
 // + MASK build, a NULL interval running as (NaN, NaN)) with the mask qm.primary; HITS == true: the caller's hit_id / t are loaded, an id
 // outside [0, n_tris) is a miss, and nothing is walked (the build has no queue).
 // Phase 2 is k_query_shade's, a wave at a time with no barrier between waves: shade_hits_rank ranks the wave's hits and leaves P and the
@@ -763,7 +783,7 @@ __global__ __launch_bounds__(256) void k_query_surface_hits(DevScene s, uint32_t
 // (`best`).
 // After a chunk the ray's own lane adds popcll to its count and stores the chunk's two words of occ_bits; a lane without a hit stores zeros.
 // dirs is read from global memory per item: 12 B at consecutive addresses for consecutive lanes, the whole table at most 12 KB.
-// The deal of rays to waves is k_query_shade's, QueryAo::spread included.
+// The deal of rays to waves is ray_deal, as in k_query_shade, QueryAo::spread included.
 // counters: as k_query_shade's -- [1] / [2] of phase 1 (0 under HITS), [3] / [4] of the AO walks (COUNT), the hit shards.
 // =================================================================================================
 struct QueryAo {
@@ -858,15 +878,15 @@ __global__ __launch_bounds__(256) void k_query_ao(DevScene s, uint32_t n_rays, c
                                                   unsigned long long* __restrict__ counters) {
     __shared__ unsigned long long best_all[256];
     __shared__ float ray_all[4][8][64];
-    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t lane = wave_lane(), wave = wave_index();
     unsigned long long* best = best_all + wave * 64;
     float (*wray)[64] = ray_all[wave];
-    const size_t n_waves = (size_t)gridDim.x * 4, wv = (size_t)blockIdx.x * 4 + wave;
-    const size_t ri = p.spread ? ((size_t)(lane >> 3) * n_waves + wv) * 8 + (lane & 7u) : (size_t)blockIdx.x * 256 + threadIdx.x;
+    const size_t ri = ray_deal(p.spread, wave)(lane);
     const bool live = ri < (size_t)n_rays;
     unsigned long long n_node = 0, n_tri = 0, n_node_s = 0, n_tri_s = 0;
-    V3 o = mk(0.0f, 0.0f, 0.0f), d = mk(0.0f, 0.0f, 1.0f);
-    if (live) load_ray(rays, ri, wide != 0, o, d);
+    QueryRay r;
+    query_ray_opt(r, rays, wide, HITS ? QueryRange{ nullptr, 0u } : tr, ri, live);       // (HITS: nothing is walked, no interval is read)
+    const V3 o = r.o, d = r.d;
     bool is_hit;
     int32_t id = -1;
     float t = __builtin_inff();
@@ -875,19 +895,13 @@ __global__ __launch_bounds__(256) void k_query_ao(DevScene s, uint32_t n_rays, c
         is_hit = id >= 0 && (uint32_t)id < s.n_tris;
     } else {
         __shared__ uint32_t q_all[4][QCAP];             // the walk's queue: the HITS builds have none
-        float t_min = __builtin_nanf(""), t_max = __builtin_nanf("");
-        if (tr.t && live) load_range(tr, ri, t_min, t_max);
-        query_walk<COUNT, true, MergeClosest, true>(s, live, o, d, lane, q_all[wave], MergeClosest{ best }, wray, n_node, n_tri, t_min, t_max, qm.obj, qm.primary);
-        const unsigned long long key = live ? best[lane] : ~0ull;
-        is_hit = key != ~0ull;
-        id = is_hit ? (int32_t)(uint32_t)key : -1;
+        query_walk<COUNT, true, MergeClosest, true>(s, live, o, d, lane, q_all[wave], MergeClosest{ best }, wray, n_node, n_tri, r.t_min, r.t_max, qm.obj, qm.primary);
+        const Winner h = winner_of(live ? best[lane] : ~0ull);
+        is_hit = h.is_hit; id = h.id;
     }
     Surface f;
     const WaveHits wh = shade_hits_rank<SMOOTH, true, HITS>(s, is_hit, id, o, d, t, f, wray, p.skip_self ? 0u : 1u);
-    if (!HITS && live) {
-        if (hit_id) hit_id[ri] = id;
-        if (t_out) t_out[ri] = t;
-    }
+    if (!HITS && live) store_hit(hit_id, t_out, ri, id, t);
     if (p.n_dirs) {                                     // wave-uniform
         const uint32_t blocked = ao_hits_dirs<COUNT>(s, p, qm, lane, live, is_hit, wh, d, f.nrm, ri, out.occ_bits, wray, best, n_node_s, n_tri_s);
         if (live) {
@@ -896,7 +910,7 @@ __global__ __launch_bounds__(256) void k_query_ao(DevScene s, uint32_t n_rays, c
         }
     }
     if (counters) count_hits(counters, is_hit, blockIdx.x);
-    if (COUNT) { wave_add(counters + 1, n_node); wave_add(counters + 2, n_tri); wave_add(counters + 3, n_node_s); wave_add(counters + 4, n_tri_s); }
+    count_walks<COUNT>(counters, n_node, n_tri, n_node_s, n_tri_s);
 }
 
 // =================================================================================================
@@ -914,7 +928,7 @@ __global__ __launch_bounds__(256) void k_query_ao(DevScene s, uint32_t n_rays, c
 // instead of an array of depth colours: segment b's weight W * (1 - k_b) needs to know whether segment b + 1 hit, so b's sum waits
 // while b + 1 is walked and is added then; the last pending segment is added after the loop with k = 0.
 // LDS: k_query_shade<.., RANGE = true>'s, reused per segment.  The rays' 8 x 64 slots are, in turn, the walk's rays, phase 2's ranked
-// hits and the stage of the transposed row stores.  The deal of rays to waves is k_query_shade's, QueryShade::spread included; under
+// hits and the stage of the transposed row stores.  The deal of rays to waves is ray_deal, as in k_query_shade, QueryShade::spread included; under
 // spread a wave's rays are 8 groups of 8 consecutive rays, so rows go out through store_rows_dealt, which is store_rows with the ray of
 // a lane given by the deal instead of base + lane (without spread the addresses are store_rows' own).
 // seg's rows are segment-major: row b of a field starts n_rays elements (x 3, x 6) after row b - 1.
@@ -987,15 +1001,15 @@ __device__ __forceinline__ V3 path_segments(const DevScene& s, const QueryShade&
     uint32_t b = 0;
     for (; b < path.depth && __ballot(alive); b++) {                                                // wave-uniform
         query_walk<COUNT, true, MergeClosest, MASK>(s, alive, o, d, lane, q, MergeClosest{ best }, wray, n_node, n_tri, t_min, t_max, qm.obj, b == 0 ? qm.primary : qm.bounce);
-        const unsigned long long key = alive ? best[lane] : ~0ull;
-        const bool is_hit = key != ~0ull;
-        const int32_t id = is_hit ? (int32_t)(uint32_t)key : -1;
+        const Winner h = winner_of(alive ? best[lane] : ~0ull);
+        const bool is_hit = h.is_hit;
+        const int32_t id = h.id;
         float t;
         Surface f;
         const WaveHits wh = shade_hits_rank<SMOOTH, SHADOW>(s, is_hit, id, o, d, t, f, wray, rule.self);
         const int32_t obj = is_hit ? s.tri_obj[id] : -1;
         const size_t row = (size_t)b * n;
-        if (live) {
+        if (live) {                                     // (not store_hit: seg's pointers are read where they are tested, not ahead of both tests)
             if (seg.hit_id) seg.hit_id[row + ri] = id;
             if (seg.t) seg.t[row + ri] = t;
             if (seg.obj) seg.obj[row + ri] = obj;
@@ -1063,9 +1077,8 @@ __device__ __forceinline__ V3 path_segments(const DevScene& s, const QueryShade&
             if (__ballot(split)) {                      // wave-uniform
                 query_walk<COUNT, true, MergeClosest, MASK>(s, split, o, sdir, lane, q, MergeClosest{ best }, wray, n_node, n_tri, path.bounce_t_min, __builtin_inff(),
                                                             qm.obj, qm.bounce);
-                const unsigned long long skey = split ? best[lane] : ~0ull;
-                side = skey != ~0ull;
-                sid = side ? (int32_t)(uint32_t)skey : -1;
+                const Winner sh = winner_of(split ? best[lane] : ~0ull);
+                side = sh.is_hit; sid = sh.id;
                 Surface sf;
                 const WaveHits swh = shade_hits_rank<SMOOTH, SHADOW>(s, side, sid, o, sdir, st, sf, wray, rule.self);
                 ssum = shade_hits_lights<COUNT, INT_SHIN, SHADOW, MASK>(s, p, lane, side, swh, o, sdir, st, sf, wray, best, n_node_s, n_tri_s, rule.t_min, rule.t_max,
@@ -1118,13 +1131,13 @@ __device__ __forceinline__ void query_path_rays(const DevScene& s, const uint32_
     __shared__ uint32_t q_all[4][QCAP];
     __shared__ unsigned long long best_all[256];
     __shared__ float ray_all[4][8][64];
-    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const size_t n_waves = (size_t)gridDim.x * 4, wv = (size_t)blockIdx.x * 4 + wave, n = (size_t)n_rays;
-    const uint32_t spread = p.spread;
-    const auto ray_of = [=](const uint32_t l) -> size_t { return spread ? ((size_t)(l >> 3) * n_waves + wv) * 8 + (l & 7u) : wv * 64 + l; };
+    const uint32_t lane = wave_lane(), wave = wave_index();
+    const size_t n = (size_t)n_rays;
+    const RayDeal ray_of = ray_deal(p.spread, wave);
     const size_t ri = ray_of(lane);
     const bool live = ri < n;
     unsigned long long n_node = 0, n_tri = 0, n_node_s = 0, n_tri_s = 0;
+    // query_ray_opt's statements, kept here: through the helper the FRESNEL builds order two register moves the other way
     V3 o = mk(0.0f, 0.0f, 0.0f), d = mk(0.0f, 0.0f, 1.0f);
     float t_min = __builtin_nanf(""), t_max = __builtin_nanf("");
     if (live) load_ray(rays, ri, wide != 0, o, d);
@@ -1134,7 +1147,7 @@ __device__ __forceinline__ void query_path_rays(const DevScene& s, const uint32_
                                                                                           best_all + wave * 64, ray_all[wave], ray_of, counters, blockIdx.x, hit0, n_node, n_tri,
                                                                                           n_node_s, n_tri_s, rule, qm, ior, fr);
     if (live) store_pixel(rgb_linear, rgb8, ri, acc, hit0, p.reinhard, p.gamma, p.bg, 0u);
-    if (COUNT) { wave_add(counters + 1, n_node); wave_add(counters + 2, n_tri); wave_add(counters + 3, n_node_s); wave_add(counters + 4, n_tri_s); }
+    count_walks<COUNT>(counters, n_node, n_tri, n_node_s, n_tri_s);
 }
 template <bool COUNT, bool SMOOTH, bool INT_SHIN>
 __global__ __launch_bounds__(256) void k_query_path(DevScene s, uint32_t n_rays, const float* __restrict__ rays, uint32_t wide, QueryShade p, QueryRange tr,
@@ -1188,6 +1201,30 @@ __global__ __launch_bounds__(256) void k_query_path_fresnel(DevScene s, uint32_t
 // and the pixel leaves once, as k_accumulate / k_resolve make it (tone-mapped whatever was hit: a black quotient is the background).
 // seg's rows are sub-sample 0's.  counters: as k_query_path's, over all sub-samples; the hit shard is the 2-D workgroup number.
 // =================================================================================================
+// The front end of the frame kernels (k_render_path*, k_render_ao), as wave_lane / ray_deal / query_ray are the batch kernels': the lane's
+// pixel (px, r) of the call's local output and whether it has one (live), its image row y, its row ri in every output (of n), the deal
+// ray_of for any lane of the wave (~0: a lane without a pixel) and the shard where the workgroup's hits are counted.
+struct FrameDeal {
+    unsigned long long live_mask;
+    uint32_t tile_x, tile_r, W;
+    __device__ __forceinline__ size_t operator()(const uint32_t l) const { return (live_mask >> l) & 1ull ? (size_t)(tile_r + (l >> 3)) * W + tile_x + (l & 7u) : ~(size_t)0; }
+};
+struct FramePixel { uint32_t px, r, y, shard; bool live; size_t n, ri; FrameDeal ray_of; };
+__device__ __forceinline__ void frame_pixel(FramePixel& at, const DevParams& fp, const uint32_t wave) {
+    at.live = tile_pixel(fp, at.px, at.r);
+    at.ray_of.live_mask = __ballot(at.live);
+    at.ray_of.tile_x = blockIdx.x * 16 + (wave & 1) * 8; at.ray_of.tile_r = blockIdx.y * 16 + (wave >> 1) * 8; at.ray_of.W = fp.W;
+    at.n = (size_t)fp.rows * fp.W; at.ri = (size_t)at.r * fp.W + at.px;
+    at.shard = blockIdx.y * gridDim.x + blockIdx.x; at.y = at.live ? image_row(fp, at.r) : 0u;
+}
+// Sub-sample k of spp = spp_m x spp_m: srt_render_device's offsets, added to dir.xy before the matrix.  spp == 1 leaves the frame's own.
+__device__ __forceinline__ void frame_sub_sample(DevParams& fp, const uint32_t spp, const uint32_t spp_m, const uint32_t k) {
+    if (spp > 1) {
+        fp.sub_x = ((float)(k % spp_m) + 0.5f) / (float)spp_m - 0.5f;
+        fp.sub_y = ((float)(k / spp_m) + 0.5f) / (float)spp_m - 0.5f;
+    }
+}
+
 // The body of both k_render_path kernels, as query_path_rays is k_query_path's.  fp: the frame's geometry; sub_x / sub_y change per sub-sample.
 template <bool COUNT, bool SMOOTH, bool INT_SHIN, bool SHADOW, bool MASK = false, bool REFRACT = false, bool FRESNEL = false>
 __device__ __forceinline__ void render_path_pixels(const DevScene& s, DevParams& fp, const uint32_t spp, const uint32_t spp_m, const QueryShade& p, const srt_path_desc& path,
@@ -1197,35 +1234,28 @@ __device__ __forceinline__ void render_path_pixels(const DevScene& s, DevParams&
     __shared__ uint32_t q_all[4][QCAP];
     __shared__ unsigned long long best_all[256];
     __shared__ float ray_all[4][8][64];
-    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t px, r;
-    const bool live = tile_pixel(fp, px, r);
-    const unsigned long long live_mask = __ballot(live);
-    const uint32_t tile_x = blockIdx.x * 16 + (wave & 1) * 8, tile_r = blockIdx.y * 16 + (wave >> 1) * 8, W = fp.W;
-    const auto ray_of = [=](const uint32_t l) -> size_t { return (live_mask >> l) & 1ull ? (size_t)(tile_r + (l >> 3)) * W + tile_x + (l & 7u) : ~(size_t)0; };
-    const size_t n = (size_t)fp.rows * W, ri = (size_t)r * W + px;
-    const uint32_t shard = blockIdx.y * gridDim.x + blockIdx.x, y = live ? image_row(fp, r) : 0u;
+    const uint32_t lane = wave_lane(), wave = wave_index();
+    FramePixel at;
+    frame_pixel(at, fp, wave);
+    const bool live = at.live;
     unsigned long long n_node = 0, n_tri = 0, n_node_s = 0, n_tri_s = 0;
     const V3 o = ray_origin(fp);
     V3 total = mk(0.0f, 0.0f, 0.0f);
     bool hit0 = false;
     for (uint32_t k = 0; k < spp; k++) {                                                            // wave-uniform
-        if (spp > 1) {
-            fp.sub_x = ((float)(k % spp_m) + 0.5f) / (float)spp_m - 0.5f;
-            fp.sub_y = ((float)(k / spp_m) + 0.5f) / (float)spp_m - 0.5f;
-        }
-        const V3 d = live ? primary_dir(fp, px, y) : mk(0.0f, 0.0f, 1.0f);
+        frame_sub_sample(fp, spp, spp_m, k);
+        const V3 d = live ? primary_dir(fp, at.px, at.y) : mk(0.0f, 0.0f, 1.0f);
         bool h;
-        const V3 acc = path_segments<COUNT, SMOOTH, INT_SHIN, SHADOW, MASK, REFRACT, FRESNEL>(s, p, path, k == 0 ? seg : srt_path_out{}, n, ri, live, o, d, __builtin_nanf(""),
-                                                                                              __builtin_nanf(""), lane, q_all[wave], best_all + wave * 64, ray_all[wave], ray_of,
-                                                                                              counters, shard, h, n_node, n_tri, n_node_s, n_tri_s, rule, qm, ior,
-                                                                                              k == 0 ? fr : QueryFresnel{ fr.f0, srt_fresnel_out{} });
+        const V3 acc = path_segments<COUNT, SMOOTH, INT_SHIN, SHADOW, MASK, REFRACT, FRESNEL>(s, p, path, k == 0 ? seg : srt_path_out{}, at.n, at.ri, live, o, d,
+                                                                                              __builtin_nanf(""), __builtin_nanf(""), lane, q_all[wave], best_all + wave * 64,
+                                                                                              ray_all[wave], at.ray_of, counters, at.shard, h, n_node, n_tri, n_node_s, n_tri_s,
+                                                                                              rule, qm, ior, k == 0 ? fr : QueryFresnel{ fr.f0, srt_fresnel_out{} });
         if (k == 0) { total = acc; hit0 = h; }
         else total = mk(total.x + acc.x, total.y + acc.y, total.z + acc.z);
     }
     if (spp > 1) { const float f = (float)spp; total = mk(total.x / f, total.y / f, total.z / f); hit0 = true; }
-    if (live) store_pixel(rgb_linear, rgb8, ri, total, hit0, p.reinhard, p.gamma, p.bg, 0u);
-    if (COUNT) { wave_add(counters + 1, n_node); wave_add(counters + 2, n_tri); wave_add(counters + 3, n_node_s); wave_add(counters + 4, n_tri_s); }
+    if (live) store_pixel(rgb_linear, rgb8, at.ri, total, hit0, p.reinhard, p.gamma, p.bg, 0u);
+    count_walks<COUNT>(counters, n_node, n_tri, n_node_s, n_tri_s);
 }
 template <bool COUNT, bool SMOOTH, bool INT_SHIN>
 __global__ __launch_bounds__(256) void k_render_path(DevScene s, DevParams fp, uint32_t spp, uint32_t spp_m, QueryShade p, srt_path_desc path,
@@ -1295,7 +1325,7 @@ void k_render_ao(DevScene s, DevParams fp, uint32_t spp, uint32_t spp_m, QueryMa
                  float* __restrict__ t_out, srt_ao_frame_out out, unsigned long long* __restrict__ counters) {
     __shared__ unsigned long long best_all[256];
     __shared__ float ray_all[4][8][64];
-    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t lane = wave_lane(), wave = wave_index();
     unsigned long long* best = best_all + wave * 64;
     float (*wray)[64] = ray_all[wave];
     float (*wrot)[64] = nullptr;
@@ -1308,17 +1338,14 @@ void k_render_ao(DevScene s, DevParams fp, uint32_t spp, uint32_t spp_m, QueryMa
         __shared__ uint32_t q_all[4][QCAP];             // the walk's queue: the HITS builds have none
         queue = q_all[wave];
     }
-    uint32_t px, r;
-    const bool live = tile_pixel(fp, px, r);
-    const unsigned long long live_mask = __ballot(live);
-    const uint32_t tile_x = blockIdx.x * 16 + (wave & 1) * 8, tile_r = blockIdx.y * 16 + (wave >> 1) * 8, W = fp.W;
-    const auto ray_of = [=](const uint32_t l) -> size_t { return (live_mask >> l) & 1ull ? (size_t)(tile_r + (l >> 3)) * W + tile_x + (l & 7u) : ~(size_t)0; };
-    const size_t n = (size_t)fp.rows * W, ri = (size_t)r * W + px;
-    const uint32_t shard = blockIdx.y * gridDim.x + blockIdx.x, y = live ? image_row(fp, r) : 0u;
+    FramePixel at;
+    frame_pixel(at, fp, wave);
+    const bool live = at.live;
+    const size_t ri = at.ri;
     float c = 1.0f, sn = 0.0f;
     if constexpr (ROT) {
         if (live) {
-            const float* e = rt.rot + ((size_t)(y % rt.h) * rt.w + image_col(fp, px, y) % rt.w) * 2;
+            const float* e = rt.rot + ((size_t)(at.y % rt.h) * rt.w + image_col(fp, at.px, at.y) % rt.w) * 2;
             c = e[0]; sn = e[1];
         }
     }
@@ -1327,11 +1354,8 @@ void k_render_ao(DevScene s, DevParams fp, uint32_t spp, uint32_t spp_m, QueryMa
     const uint32_t n_sub = HITS ? 1u : spp;             // a render's hits are sub-sample 0's
     float total = 0.0f;
     for (uint32_t k = 0; k < n_sub; k++) {                                                          // wave-uniform
-        if (spp > 1) {
-            fp.sub_x = ((float)(k % spp_m) + 0.5f) / (float)spp_m - 0.5f;
-            fp.sub_y = ((float)(k / spp_m) + 0.5f) / (float)spp_m - 0.5f;
-        }
-        const V3 d = live ? primary_dir(fp, px, y) : mk(0.0f, 0.0f, 1.0f);
+        frame_sub_sample(fp, spp, spp_m, k);
+        const V3 d = live ? primary_dir(fp, at.px, at.y) : mk(0.0f, 0.0f, 1.0f);
         bool is_hit;
         int32_t id = -1;
         float t = __builtin_inff();
@@ -1341,16 +1365,12 @@ void k_render_ao(DevScene s, DevParams fp, uint32_t spp, uint32_t spp_m, QueryMa
         } else {
             query_walk<COUNT, true, MergeClosest, true>(s, live, o, d, lane, queue, MergeClosest{ best }, wray, n_node, n_tri, __builtin_nanf(""), __builtin_nanf(""),
                                                         qm.obj, qm.primary);
-            const unsigned long long key = live ? best[lane] : ~0ull;
-            is_hit = key != ~0ull;
-            id = is_hit ? (int32_t)(uint32_t)key : -1;
+            const Winner h = winner_of(live ? best[lane] : ~0ull);
+            is_hit = h.is_hit; id = h.id;
         }
         Surface f;
         const WaveHits wh = shade_hits_rank<SMOOTH, true, HITS>(s, is_hit, id, o, d, t, f, wray, p.skip_self ? 0u : 1u);
-        if (!HITS && live && k == 0) {
-            if (hit_id) hit_id[ri] = id;
-            if (t_out) t_out[ri] = t;
-        }
+        if (!HITS && live && k == 0) store_hit(hit_id, t_out, ri, id, t);
         if (p.n_dirs) {                                 // wave-uniform
             const bool want_bent = out.bent && k == 0;  // wave-uniform
             const V3 Nf = ao_facing(d, f.nrm);
@@ -1373,15 +1393,15 @@ void k_render_ao(DevScene s, DevParams fp, uint32_t spp, uint32_t spp_m, QueryMa
             if (k == 0) {
                 total = a;
                 if (out.n_occluded && live) out.n_occluded[ri] = blocked;
-                if (want_bent) { const float v[3] = { bent.x, bent.y, bent.z }; store_rows_dealt<3>(out.bent, lane, n, v, &wray[0][0], ray_of); }
+                if (want_bent) { const float v[3] = { bent.x, bent.y, bent.z }; store_rows_dealt<3>(out.bent, lane, at.n, v, &wray[0][0], at.ray_of); }
             } else total = total + a;
         }
-        if (counters) count_hits(counters, is_hit, shard);
+        if (counters) count_hits(counters, is_hit, at.shard);
     }
     if (p.n_dirs && live) {
         if (n_sub > 1) total = total / (float)spp;
         if (out.ao) out.ao[ri] = total;
         if (out.ao8) out.ao8[ri] = (uint8_t)(int)(total * 255.0f + 0.5f);
     }
-    if (COUNT) { wave_add(counters + 1, n_node); wave_add(counters + 2, n_tri); wave_add(counters + 3, n_node_s); wave_add(counters + 4, n_tri_s); }
+    count_walks<COUNT>(counters, n_node, n_tri, n_node_s, n_tri_s);
 }
