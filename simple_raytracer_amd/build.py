@@ -51,17 +51,20 @@ def build_hip(force=False, verbose=False):
 
 LIB_HOST = os.path.join(HERE, "libsrt_host.so")
 HOST_FLAGS = ["-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-Wall", "-pthread"]
+# What libsrt_host.so is compiled from, stated once: srt_host.cpp and srt_jpeg.cpp are the half that needs no GPU (they link without
+# libsrt_hip: tools/host_sanitize.py), srt_host_render.cpp calls the C ABI, srt_host_c.cpp is the plain-C face of both.
+HOST_DIR = os.path.join(CSRC, "host")
+HOST_CPU_SRCS = [os.path.join(HOST_DIR, f) for f in ("srt_host.cpp", "srt_jpeg.cpp")]
+HOST_SRCS = HOST_CPU_SRCS + [os.path.join(HOST_DIR, f) for f in ("srt_host_render.cpp", "srt_host_c.cpp")]
+HOST_DEPS = HOST_SRCS + [os.path.join(HOST_DIR, f) for f in ("srt_host.h", "srt_host_internal.h", "srt_host_c.h")] + [os.path.join(HERE, "..", "include", "srt.h")]
 
 
 def build_host(force=False, verbose=False):
     """Host-side C++ mirror of the reference's scene interface (g++); links the HIP library for the
     drop-in sendRaysAndIntersectPointsColors."""
-    hdir = os.path.join(CSRC, "host")
-    srcs = [os.path.join(hdir, "srt_host.cpp"), os.path.join(hdir, "srt_jpeg.cpp"), os.path.join(hdir, "srt_host_c.cpp")]
-    deps = srcs + [os.path.join(hdir, "srt_host.h"), os.path.join(HERE, "..", "include", "srt.h"), LIB_HIP]
-    if not force and not _stale(LIB_HOST, deps):
+    if not force and not _stale(LIB_HOST, HOST_DEPS + [LIB_HIP]):
         return LIB_HOST
-    cmd = ["g++"] + HOST_FLAGS + ["-o", LIB_HOST] + srcs + ["-L" + HERE, "-lsrt_hip", "-Wl,-rpath,$ORIGIN", "-lz"]
+    cmd = ["g++"] + HOST_FLAGS + ["-o", LIB_HOST] + HOST_SRCS + ["-L" + HERE, "-lsrt_hip", "-Wl,-rpath,$ORIGIN", "-lz"]
     if verbose:
         print(" ".join(cmd))
     r = subprocess.run(cmd, capture_output=True, text=True)
@@ -112,12 +115,10 @@ def build_c_example(force=False, verbose=False):
 
 def stale_artefacts():
     """Names of the product's native artefacts that are missing or older than their sources (nothing is built)."""
-    hdir = os.path.join(CSRC, "host")
-    host_deps = [os.path.join(hdir, f) for f in ("srt_host.cpp", "srt_jpeg.cpp", "srt_host_c.cpp", "srt_host.h")]
     out = []
     if _stale(LIB_HIP, HIP_DEPS):
         out.append("libsrt_hip.so")
-    if _stale(LIB_HOST, host_deps):
+    if _stale(LIB_HOST, HOST_DEPS):
         out.append("libsrt_host.so")
     return out
 

@@ -2,10 +2,12 @@
 //
 // Everything here runs once per frame on the host, as in the reference: transforms (Object.cpp:183-190),
 // the median-split hierarchy builder (Object.cpp:205-284), the flattener that writes the flat scene of
-// include/srt.h, and the drop-in sendRaysAndIntersectPointsColors that calls the HIP path through the
-// C ABI.  Built with -ffp-contract=off: transformed points, boxes and the builder's comparisons must be
+// include/srt.h, and the image output.  Nothing here calls the C ABI: this file and srt_jpeg.cpp link without
+// libsrt_hip (tools/host_sanitize.py builds them so); what renders is srt_host_render.cpp.
+// Built with -ffp-contract=off: transformed points, boxes and the builder's comparisons must be
 // bit-identical to what the reference computes, because leaf order decides tie-breaks.
 #include "srt_host.h"
+#include "srt_host_internal.h"
 
 #include <algorithm>
 #include <array>
@@ -82,6 +84,7 @@ private:
 // for each other (the top-level sorts are serial stretches) and the waiting threads take the cores the other frames' builds need.
 std::atomic<bool> g_build_tasks{true};
 inline bool build_tasks_allowed() { return g_build_tasks.load(std::memory_order_relaxed) && BuildPool::get().workers(); }
+} // namespace
 
 // fn(begin, end) over [0, n) in chunks of at least `grain`, on the pool plus the calling thread
 void parallel_for(size_t n, size_t grain, const std::function<void(size_t, size_t)>& fn) {
@@ -101,7 +104,6 @@ void parallel_for(size_t n, size_t grain, const std::function<void(size_t, size_
     while (pending.load(std::memory_order_acquire) > 0)
         if (!pool.run_one()) std::this_thread::yield();
 }
-} // namespace
 
 // ------------------------------------------------------------------------------------------------
 // glm operations the reference's host code applies (exact op order)
@@ -242,7 +244,7 @@ static bool decode_png(const std::vector<unsigned char>& d, Texture& t) {
         uint32_t len = be32(&d[pos]); const unsigned char* ty = &d[pos + 4];
         if (pos + 12 + (size_t)len > d.size()) return false;
         const unsigned char* body = &d[pos + 8];
-        if (!std::memcmp(ty, "IHDR", 4)) { W = be32(body); H = be32(body + 4); depth = body[8]; ctype = body[9]; interlace = body[12]; }
+        if (!std::memcmp(ty, "IHDR", 4)) { if (len < 13) return false; W = be32(body); H = be32(body + 4); depth = body[8]; ctype = body[9]; interlace = body[12]; }
         else if (!std::memcmp(ty, "PLTE", 4)) plte.assign(body, body + len);
         else if (!std::memcmp(ty, "IDAT", 4)) idat.insert(idat.end(), body, body + len);
         else if (!std::memcmp(ty, "IEND", 4)) break;
@@ -252,6 +254,9 @@ static bool decode_png(const std::vector<unsigned char>& d, Texture& t) {
     int ch = ctype == 0 ? 1 : ctype == 2 ? 3 : ctype == 3 ? 1 : ctype == 4 ? 2 : ctype == 6 ? 4 : 0;
     if (!ch || (ctype == 3 && depth != 8)) return false;
     const size_t bpp = (size_t)ch * depth / 8, stride = (size_t)W * bpp;
+    // a header that declares more than its data can hold is refused before anything is allocated for it: deflate expands by less
+    // than 1032 : 1 (zlib's stated limit), so the idat bytes bound the image
+    if (H > ((size_t)idat.size() * 1032 + 1032) / (stride + 1)) return false;
     std::vector<unsigned char> raw((stride + 1) * H);
     uLongf rawlen = (uLongf)raw.size();
     if (uncompress(raw.data(), &rawlen, idat.data(), (uLong)idat.size()) != Z_OK || rawlen != raw.size()) return false;
@@ -305,7 +310,7 @@ static bool decode_bmp(const std::vector<unsigned char>& d, Texture& t) {
     if (d.size() < 54 || d[0] != 'B' || d[1] != 'M') return false;
     auto le32 = [&](size_t o) { return (int32_t)((uint32_t)d[o] | ((uint32_t)d[o + 1] << 8) | ((uint32_t)d[o + 2] << 16) | ((uint32_t)d[o + 3] << 24)); };
     const int32_t off = le32(10), W = le32(18), Hs = le32(22); const int bpp = d[28] | (d[29] << 8), comp = le32(30);
-    if (W <= 0 || Hs == 0 || (bpp != 24 && bpp != 32) || comp != 0) return false;
+    if (off < 0 || W <= 0 || Hs == 0 || Hs == INT32_MIN || (bpp != 24 && bpp != 32) || comp != 0) return false;
     const int32_t H = std::abs(Hs); const size_t stride = (((size_t)W * bpp / 8) + 3) & ~(size_t)3;
     if ((size_t)off + stride * H > d.size()) return false;
     t.dim.x = W; t.dim.y = H; t.rgb.resize((size_t)W * H * 3);
@@ -1051,289 +1056,8 @@ FlatScene flattenScene(ObjectManager* om) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// Drop-in entry point and image output
+// Image output
 // ------------------------------------------------------------------------------------------------
-// hit pixels of an 8-bit frame in the reference's emission order: x outer, y inner (:511-513).  Count per column, then fill the
-// slots in parallel.  Black = "not emitted" (:518).
-// `out` may come pre-sized (Renderer::collect sizes it by the previous frame's count while the GPU is still rendering: resize
-// value-initialises, 20 bytes per emitted pixel of zero fill that then costs nothing on the critical path).
-static void resize_both(ImageData& out, size_t n) {
-    parallel_for(2, 1, [&](size_t b, size_t e) { for (size_t k = b; k < e; k++) { if (k == 0) out.imagePoints.resize(n); else out.imageColors.resize(n); } });
-}
-static ImageData image_data_from_rgb8(const uint8_t* rgb8, uint32_t W, uint32_t H, ImageData&& pre = ImageData()) {
-    ImageData out = std::move(pre);
-    std::vector<size_t> col(W + 1, 0);
-    parallel_for(W, 64, [&](size_t x0, size_t x1) {
-        for (size_t x = x0; x < x1; x++) {
-            size_t n = 0;
-            for (uint32_t y = 0; y < H; y++) { const uint8_t* c = &rgb8[((size_t)y * W + x) * 3]; n += (c[0] | c[1] | c[2]) != 0; }
-            col[x + 1] = n;
-        }
-    });
-    for (uint32_t x = 0; x < W; x++) col[x + 1] += col[x];
-    if (out.imagePoints.size() < col[W] || out.imageColors.size() < col[W]) resize_both(out, col[W]);      // first frame, or more pixels than guessed
-    parallel_for(W, 64, [&](size_t x0, size_t x1) {
-        for (size_t x = x0; x < x1; x++) {
-            size_t k = col[x];
-            for (uint32_t y = 0; y < H; y++) {
-                const uint8_t* c = &rgb8[((size_t)y * W + x) * 3];
-                if (c[0] | c[1] | c[2]) {
-                    out.imagePoints[k] = vec2((float)x, (float)y);
-                    out.imageColors[k] = vec3((float)c[0], (float)c[1], (float)c[2]);
-                    k++;
-                }
-            }
-        }
-    });
-    if (out.imagePoints.size() != col[W]) { out.imagePoints.resize(col[W]); out.imageColors.resize(col[W]); }      // shrinking: no fill
-    return out;
-}
-
-Renderer::Renderer(int device) : device_(device) {}
-Renderer::~Renderer() {
-    if (scene_) srt_scene_destroy(scene_);
-    if (rgb8_) srt_host_free(rgb8_);
-}
-
-// A sample of the per-triangle attributes the device keeps in source order (texture, texel coordinates, normals): every 61st triangle
-// of every hierarchy, and the identity of the texture images.  Catches another mesh or another material under the same name and counts;
-// an edit of single triangles between two frames of otherwise the same scene is NOT seen -- setFastPath(false) for such callers.
-static uint64_t attribute_sample(ObjectManager* om) {
-    uint64_t h = 0xcbf29ce484222325ull;
-    auto mix = [&](const void* p, size_t n) { const unsigned char* c = (const unsigned char*)p; for (size_t i = 0; i < n; i++) { h ^= c[i]; h *= 0x100000001b3ull; } };
-    for (const auto& pair : om->objTriangles) {
-        auto hit = om->boundingVolumeHierarchy.find(pair.first);
-        if (hit == om->boundingVolumeHierarchy.end()) continue;
-        const std::vector<Triangle>& tr = hit->second.triangles;
-        for (size_t i = 0; i < tr.size(); i += 61) {
-            const Triangle& t = tr[i];
-            mix(&t.normalOne, 3 * sizeof(vec3)); mix(&t.colorOneCoordinate, 3 * sizeof(vec2)); mix(t.textureName.data(), t.textureName.size());
-        }
-    }
-    for (const auto& tx : om->textureData) {
-        mix(tx.first.data(), tx.first.size()); mix(&tx.second.dim, sizeof(tx.second.dim));
-        const std::vector<unsigned char>& px = tx.second.rgb;
-        const size_t n = px.size();
-        mix(&n, sizeof(n));
-        for (size_t i = 0; i < n; i += 4099) mix(&px[i], 1);
-    }
-    return h;
-}
-
-// The short way (include/srt.h, f1 device half): the hierarchies' compact arrays straight to srt_scene_update_frame.  false = the
-// resident scene is not this ObjectManager's (first frame, other objects or counts, other attributes): the caller takes the long way.
-bool Renderer::upload_frame(ObjectManager* om) {
-    if (!scene_ || !fast_path_ || sig_names_.size() != om->objTriangles.size()) return false;
-    const size_t nO = sig_names_.size();
-    std::vector<uint32_t> n_tris(nO), n_nodes(nO);
-    std::vector<const float*> pts(nO), bmin(nO), bmax(nO);
-    std::vector<const uint32_t*> ord(nO);
-    std::vector<float> color(3 * nO), mat(3 * nO);
-    size_t k = 0;
-    for (const auto& pair : om->objTriangles) {                 // the iteration order rayIntersection:409 uses (and flattenScene)
-        if (pair.first != sig_names_[k]) return false;
-        auto hit = om->boundingVolumeHierarchy.find(pair.first);
-        if (hit == om->boundingVolumeHierarchy.end()) return false;      // (the long way reports it)
-        const ObjectManager::Hierarchy& h = hit->second;
-        if (h.order.size() != sig_tris_[k] || h.nodes.size() != sig_nodes_[k] || h.points.size() != 12 * h.order.size()) return false;
-        n_tris[k] = sig_tris_[k]; n_nodes[k] = sig_nodes_[k];
-        pts[k] = h.points.data(); ord[k] = h.order.data(); bmin[k] = h.node_min.data(); bmax[k] = h.node_max.data();
-        const vec3 c = om->objColors[pair.first], m = om->objProperties[pair.first];
-        for (int a = 0; a < 3; a++) { color[3 * k + a] = c[a]; mat[3 * k + a] = m[a]; }
-        k++;
-    }
-    if (attribute_sample(om) != sig_attr_) return false;
-    srt_frame_geometry g;
-    std::memset(&g, 0, sizeof(g));
-    g.n_objects = (uint32_t)nO; g.obj_n_tris = n_tris.data(); g.obj_n_nodes = n_nodes.data();
-    g.obj_points = pts.data(); g.obj_order = ord.data(); g.obj_node_min = bmin.data(); g.obj_node_max = bmax.data();
-    g.obj_color = color.data(); g.obj_material = mat.data();
-    const int rc = srt_scene_update_frame(scene_, &g, nullptr);
-    if (rc == SRT_ERR_LAYOUT) return false;
-    if (rc != SRT_OK) throw std::runtime_error(std::string("srt_scene_update_frame: ") + srt_strerror(rc));
-    fast_frames_++;
-    return true;
-}
-
-// the ObjectManager's current state into the device scene: the device half of the rebuild when the resident scene is this one with
-// other positions (upload_frame), else flattened -- in place when the counts allow it, else a new scene
-void Renderer::upload(ObjectManager* objManager) {
-    pose_source_ = false;
-    if (upload_frame(objManager)) return;
-    FlatScene flat = flattenScene(objManager);
-    srt_scene_desc d = flat.desc();
-    int rc = scene_ ? srt_scene_update(scene_, &d, nullptr) : SRT_ERR_LAYOUT;
-    if (rc == SRT_ERR_LAYOUT) {
-        if (scene_) { srt_scene_destroy(scene_); scene_ = nullptr; }
-        rc = srt_scene_create(device_, &d, &scene_);
-        if (rc != SRT_OK) { scene_ = nullptr; throw std::runtime_error(std::string("srt_scene_create: ") + srt_strerror(rc)); }
-    } else if (rc != SRT_OK) throw std::runtime_error(std::string("srt_scene_update: ") + srt_strerror(rc));
-    // what is resident now, and its per-triangle attributes in SOURCE order for the frames that follow (the hierarchies' by-value
-    // copies are in visit order: position i holds source triangle order[i])
-    sig_names_ = flat.names; sig_tris_.clear(); sig_nodes_.clear();
-    const size_t nt = flat.tri_obj.size();
-    std::vector<float> tc(6 * nt), nrm(9 * nt);
-    std::vector<int32_t> tex(nt, -1);
-    bool any_tex = false;
-    size_t base = 0;
-    for (const std::string& name : flat.names) {
-        const ObjectManager::Hierarchy& h = objManager->boundingVolumeHierarchy.at(name);
-        sig_tris_.push_back((uint32_t)h.order.size()); sig_nodes_.push_back((uint32_t)h.nodes.size());
-        for (size_t i = 0; i < h.order.size(); i++) {
-            const size_t src = base + h.order[i], vis = base + i;
-            for (int c = 0; c < 6; c++) tc[6 * src + c] = flat.tri_texcoord[6 * vis + c];
-            for (int c = 0; c < 9; c++) nrm[9 * src + c] = flat.tri_normals[9 * vis + c];
-            tex[src] = flat.tri_tex[vis];
-            any_tex = any_tex || tex[src] >= 0;
-        }
-        base += h.order.size();
-    }
-    sig_attr_ = attribute_sample(objManager);
-    rc = srt_scene_set_source(scene_, tc.data(), nrm.data(), any_tex ? tex.data() : nullptr);
-    if (rc != SRT_OK) { sig_names_.clear(); }              // no short way for this scene (it stays correct: the long way every frame)
-}
-
-void Renderer::enqueue(const vec2& imageSize, const vec4& lightPos, int lightAmount, const mat4* viewMatrix) {
-    const uint32_t W = (uint32_t)imageSize.x, H = (uint32_t)imageSize.y;
-    const size_t bytes = (size_t)W * H * 3;
-    if (bytes > rgb8_bytes_) {
-        if (rgb8_) srt_host_free(rgb8_);
-        rgb8_ = (uint8_t*)srt_host_alloc(bytes);
-        rgb8_bytes_ = rgb8_ ? bytes : 0;
-        if (!rgb8_) throw std::runtime_error("srt_host_alloc failed");
-    }
-    srt_params p;
-    srt_params_default(&p, W, H);
-    std::vector<float> lights((size_t)lightAmount * 3);
-    const float base[3] = { lightPos.x, lightPos.y, lightPos.z };       // vec4 -> const vec3& drops w (:517 -> :405)
-    srt_light_staircase(base, (uint32_t)lightAmount, lights.data());
-    p.n_lights = (uint32_t)lightAmount; p.light_pos = lights.data();     // copied by the call
-    p.background[0] = p.background[1] = p.background[2] = 0;             // ask for black so that ImageData can skip it (:518)
-    float m16[16];
-    if (viewMatrix) { for (int c = 0; c < 4; c++) for (int r = 0; r < 4; r++) m16[c * 4 + r] = (*viewMatrix)[c][r]; p.ray_matrix = m16; }
-    const int rc = srt_render_async(scene_, &p, nullptr, nullptr, nullptr, rgb8_);
-    if (rc != SRT_OK) throw std::runtime_error(std::string("srt_render_async: ") + srt_strerror(rc));
-    W_ = W; H_ = H; pending_ = true;
-}
-
-void Renderer::submit(const vec2& imageSize, const vec4& lightPos, ObjectManager* objManager, int lightAmount) {
-    if (pending_) throw std::runtime_error("Renderer::submit: collect() the previous frame first");
-    upload(objManager);
-    enqueue(imageSize, lightPos, lightAmount, nullptr);
-}
-
-ImageData Renderer::collect() {
-    if (!pending_) throw std::runtime_error("Renderer::collect: nothing submitted");
-    pending_ = false;
-    ImageData pre;
-    if (last_count_) resize_both(pre, last_count_ + last_count_ / 16 + 64);      // while the GPU renders: the zero fill of the result vectors
-    const int rc = srt_sync(scene_, nullptr);
-    if (rc != SRT_OK) throw std::runtime_error(std::string("srt_sync: ") + srt_strerror(rc));
-    ImageData out = image_data_from_rgb8(rgb8_, W_, H_, std::move(pre));
-    last_count_ = out.imagePoints.size();
-    return out;
-}
-
-ImageData Renderer::render(const vec2& imageSize, const vec4& lightPos, ObjectManager* objManager, int lightAmount) {
-    submit(imageSize, lightPos, objManager, lightAmount);
-    return collect();
-}
-
-ImageData Renderer::renderFromCamera(const vec2& imageSize, const vec4& lightPosWorld, const mat4& viewMatrix, ObjectManager* objManager,
-                                     int lightAmount, bool sceneChanged) {
-    if (pending_) throw std::runtime_error("Renderer::renderFromCamera: collect() the previous frame first");
-    if (!scene_ || sceneChanged) upload(objManager);
-    enqueue(imageSize, lightPosWorld, lightAmount, &viewMatrix);
-    return collect();
-}
-
-// POSE: the resident scene moved by one matrix per object (srt_scene_pose); nothing proportional to triangles happens on the host
-// unless the scene has to be uploaded.
-ImageData Renderer::renderPosed(const vec2& imageSize, const vec4& lightPos, const std::vector<mat4>& objMatrices, ObjectManager* objManager,
-                                int lightAmount, bool sceneChanged) {
-    if (pending_) throw std::runtime_error("Renderer::renderPosed: collect() the previous frame first");
-    if (!scene_ || sceneChanged || !pose_source_) {
-        upload(objManager);
-        const FlatScene flat = flattenScene(objManager);       // the resident scene's visit order: the points the poses apply to
-        const int rc = srt_scene_set_pose_source(scene_, flat.tri_points.data());
-        if (rc != SRT_OK) throw std::runtime_error(std::string("srt_scene_set_pose_source: ") + srt_strerror(rc));
-        pose_source_ = true;
-    }
-    std::vector<float> m16(16 * objMatrices.size());
-    for (size_t k = 0; k < objMatrices.size(); k++) for (int c = 0; c < 4; c++) for (int r = 0; r < 4; r++) m16[16 * k + 4 * c + r] = objMatrices[k][c][r];
-    const int rc = srt_scene_pose(scene_, (uint32_t)objMatrices.size(), m16.data(), nullptr, nullptr, nullptr);
-    if (rc != SRT_OK) throw std::runtime_error(std::string("srt_scene_pose: ") + srt_strerror(rc));
-    enqueue(imageSize, lightPos, lightAmount, nullptr);
-    return collect();
-}
-
-MultiRenderer::MultiRenderer(const std::vector<int>& devices, uint32_t blockRows) : blockRows_(blockRows ? blockRows : 8) {
-    if (devices.empty()) throw std::runtime_error("MultiRenderer: no devices");
-    for (int d : devices) { Part p; p.device = d; parts_.push_back(p); }
-}
-MultiRenderer::~MultiRenderer() {
-    for (Part& p : parts_) { if (p.scene) srt_scene_destroy(p.scene); if (p.rgb8) srt_host_free(p.rgb8); }
-}
-
-ImageData MultiRenderer::render(const vec2& imageSize, const vec4& lightPos, ObjectManager* objManager, int lightAmount) {
-    const uint32_t W = (uint32_t)imageSize.x, H = (uint32_t)imageSize.y, N = (uint32_t)parts_.size();
-    FlatScene flat = flattenScene(objManager);                          // once; every device gets the same records
-    srt_scene_desc d = flat.desc();
-    std::vector<float> lights((size_t)lightAmount * 3);
-    const float base[3] = { lightPos.x, lightPos.y, lightPos.z };       // vec4 -> const vec3& drops w (:517 -> :405)
-    srt_light_staircase(base, (uint32_t)lightAmount, lights.data());
-    auto params_of = [&](uint32_t k) {
-        srt_params p;
-        srt_params_default(&p, W, H);
-        p.n_lights = (uint32_t)lightAmount; p.light_pos = lights.data();
-        p.background[0] = p.background[1] = p.background[2] = 0;         // black = not emitted (:518)
-        p.block_rows = blockRows_; p.block_first = k; p.block_stride = N;
-        return p;
-    };
-    // enqueue everywhere first (upload + render + read-back on each scene's own stream), then wait
-    for (uint32_t k = 0; k < N; k++) {
-        Part& pt = parts_[k];
-        int rc = pt.scene ? srt_scene_update(pt.scene, &d, nullptr) : SRT_ERR_LAYOUT;
-        if (rc == SRT_ERR_LAYOUT) {
-            if (pt.scene) { srt_scene_destroy(pt.scene); pt.scene = nullptr; }
-            rc = srt_scene_create(pt.device, &d, &pt.scene);
-            if (rc != SRT_OK) { pt.scene = nullptr; throw std::runtime_error(std::string("srt_scene_create: ") + srt_strerror(rc)); }
-        } else if (rc != SRT_OK) throw std::runtime_error(std::string("srt_scene_update: ") + srt_strerror(rc));
-        const srt_params p = params_of(k);
-        pt.rows = srt_rows_owned(&p);
-        const size_t bytes = (size_t)pt.rows * W * 3;
-        if (bytes > pt.bytes) {
-            if (pt.rgb8) srt_host_free(pt.rgb8);
-            pt.rgb8 = (uint8_t*)srt_host_alloc(bytes ? bytes : 1);
-            pt.bytes = pt.rgb8 ? bytes : 0;
-            if (!pt.rgb8) throw std::runtime_error("srt_host_alloc failed");
-        }
-        rc = srt_render_async(pt.scene, &p, nullptr, nullptr, nullptr, pt.rgb8);
-        if (rc != SRT_OK) throw std::runtime_error(std::string("srt_render_async: ") + srt_strerror(rc));
-    }
-    frame_.assign((size_t)W * H * 3, 0);
-    for (uint32_t k = 0; k < N; k++) {
-        Part& pt = parts_[k];
-        const int rc = srt_sync(pt.scene, nullptr);
-        if (rc != SRT_OK) throw std::runtime_error(std::string("srt_sync: ") + srt_strerror(rc));
-        for (uint32_t r = 0; r < pt.rows; r++) {                        // local row -> image row (include/srt.h srt_params)
-            const uint32_t y = ((r / blockRows_) * N + k) * blockRows_ + r % blockRows_;
-            std::memcpy(&frame_[(size_t)y * W * 3], pt.rgb8 + (size_t)r * W * 3, (size_t)W * 3);
-        }
-    }
-    return image_data_from_rgb8(frame_.data(), W, H);
-}
-
-ImageData sendRaysAndIntersectPointsColors(const vec2& imageSize, const vec4& lightPos, ObjectManager* objManager,
-                                           int lightAmount, int device) {
-    // one Renderer per thread and device, kept for the life of the thread (leaked on purpose: no HIP calls from thread-exit
-    // destructors): the second frame of an orbit re-uses the first frame's device scene and pinned buffers
-    static thread_local std::unordered_map<int, Renderer*> renderers;
-    Renderer*& r = renderers[device];
-    if (!r) r = new Renderer(device);
-    return r->render(imageSize, lightPos, objManager, lightAmount);
-}
-
 void writeBmp(const std::string& path, uint32_t W, uint32_t H, const uint8_t* rgb) {
     const uint32_t stride = (W * 3 + 3) & ~3u, size = 54 + stride * H;
     std::vector<uint8_t> f(size, 0);

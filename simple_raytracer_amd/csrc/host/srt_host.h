@@ -15,6 +15,7 @@
 // Only sendRaysAndIntersectPointsColors touches the GPU (through srt_scene_create / srt_render).
 #pragma once
 #include <cstdint>
+#include <memory>
 #include <string>
 #include <unordered_map>
 #include <vector>
@@ -154,6 +155,20 @@ struct ImageData { std::vector<vec2> imagePoints; std::vector<vec3> imageColors;
 ImageData sendRaysAndIntersectPointsColors(const vec2& imageSize, const vec4& lightPos, ObjectManager* objManager,
                                            int lightAmount = 1, int device = 0);
 
+// Move-only owners of what a renderer gets from the C ABI (srt_host_render.cpp): a device scene, released by srt_scene_destroy, and
+// the pinned buffer a frame is read back into, which only grows and is released by srt_host_free.
+struct SceneDestroy { void operator()(srt_scene* s) const; };
+using SceneHandle = std::unique_ptr<srt_scene, SceneDestroy>;
+class PinnedFrame {
+public:
+    uint8_t* reserve(size_t bytes);      // at least `bytes` of pinned memory; throws std::runtime_error when there is none
+    uint8_t* data() const { return p_.get(); }
+private:
+    struct Free { void operator()(uint8_t* p) const; };
+    std::unique_ptr<uint8_t, Free> p_;
+    size_t bytes_ = 0;
+};
+
 // A device scene that outlives the frame.  The reference builds and drops everything per frame; its drop-in call above does the
 // same through a Renderer it keeps per thread and device, so that frame n + 1 re-uses frame n's device allocations
 // (srt_scene_update) and pinned buffers instead of paying hipMalloc / hipFree / pageable copies every frame.
@@ -192,11 +207,11 @@ private:
     bool upload_frame(ObjectManager* objManager);
     void enqueue(const vec2& imageSize, const vec4& lightPos, int lightAmount, const mat4* viewMatrix);
     int device_;
-    srt_scene* scene_ = nullptr;
+    SceneHandle scene_;
     std::vector<std::string> sig_names_; std::vector<uint32_t> sig_tris_, sig_nodes_; uint64_t sig_attr_ = 0;      // what is resident
     bool fast_path_ = true; uint64_t fast_frames_ = 0;
     bool pose_source_ = false;       // the resident scene has its pose source (any upload discards it)
-    uint8_t* rgb8_ = nullptr; size_t rgb8_bytes_ = 0;      // pinned
+    PinnedFrame rgb8_;
     uint32_t W_ = 0, H_ = 0;
     bool pending_ = false;
     size_t last_count_ = 0;          // pixels the previous frame emitted: the next frame's ImageData is sized by it while the GPU renders
@@ -217,7 +232,7 @@ public:
     ImageData render(const vec2& imageSize, const vec4& lightPos, ObjectManager* objManager, int lightAmount = 1);
     const std::vector<uint8_t>& frame() const { return frame_; }      // H x W x 3 of the last render (black = nothing emitted)
 private:
-    struct Part { int device = 0; srt_scene* scene = nullptr; uint8_t* rgb8 = nullptr; size_t bytes = 0; uint32_t rows = 0; };
+    struct Part { int device = 0; SceneHandle scene; PinnedFrame rgb8; uint32_t rows = 0; };
     std::vector<Part> parts_;
     uint32_t blockRows_;
     std::vector<uint8_t> frame_;

@@ -16,8 +16,64 @@ from . import abi
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libsrt_host.so")
-_f32p, _i32p, _u8p = C.POINTER(C.c_float), C.POINTER(C.c_int32), C.POINTER(C.c_uint8)
+_f32p, _i32p, _u8p, _u32p = C.POINTER(C.c_float), C.POINTER(C.c_int32), C.POINTER(C.c_uint8), C.POINTER(C.c_uint32)
+_int, _u32, _i32, _i64, _f, _vp, _str = C.c_int, C.c_uint32, C.c_int32, C.c_int64, C.c_float, C.c_void_p, C.c_char_p
 _lib = None
+
+# ---- the prototypes of csrc/host/srt_host_c.h, in its order: name -> (restype, [argtypes]); tests/test_host_abi_mirror.py ----
+PROTOTYPES = {
+    "srth_last_error": (_str, []),
+    "srth_om_new": (_vp, []),
+    "srth_om_free": (None, [_vp]),
+    "srth_om_load_obj": (_int, [_vp, _str]),
+    "srth_om_add_object": (_int, [_vp, _str, _u32, _f32p]),
+    "srth_decode_image": (_int, [_str, _i32p, _i32p, _u8p]),
+    "srth_om_add_texture": (_int, [_vp, _str, _i32, _i32, _u8p]),
+    "srth_om_add_textured_object": (_int, [_vp, _str, _u32, _f32p, _f32p, _str]),
+    "srth_om_add_multi_textured_object": (_int, [_vp, _str, _u32, _f32p, _f32p, _i32p, _str]),
+    "srth_om_clone": (_int, [_vp, _str, _str]),
+    "srth_om_set_color": (_int, [_vp, _str, _f, _f, _f]),
+    "srth_om_set_props": (_int, [_vp, _str, _f, _f, _f]),
+    "srth_om_transform": (_int, [_vp, _str, _f32p]),
+    "srth_set_build_tasks": (None, [_int]),
+    "srth_sort_keys_both_ways": (_int, [_f32p, _u32, _u32p, _u32p]),
+    "srth_om_build_bvh": (_int, [_vp, _str]),
+    "srth_om_num_tris": (_i64, [_vp, _str]),
+    "srth_om_get_points": (_int, [_vp, _str, _f32p]),
+    "srth_om_hierarchy_nodes": (_i64, [_vp, _str]),
+    "srth_om_hierarchy": (_int, [_vp, _str, _f32p, _u32p, _f32p, _f32p]),
+    "srth_om_get_tri_attrs": (_int, [_vp, _str, _f32p, _f32p, _i32p, _f32p]),
+    "srth_flatten": (_vp, [_vp]),
+    "srth_flat_free": (None, [_vp]),
+    "srth_flat_desc": (None, [_vp, C.POINTER(abi.SceneDesc)]),
+    "srth_flat_names": (_u32, [_vp, _str, _u32]),
+    "srth_render": (_i64, [_vp, _u32, _u32, _f32p, _int, _int, _f32p]),
+    "srth_write_bmp": (_int, [_str, _u32, _u32, _u8p]),
+    "srth_radians": (_f, [_f]),
+    "srth_mat_scale": (None, [_f, _f, _f, _f32p]),
+    "srth_mat_rotx": (None, [_f, _f32p]),
+    "srth_mat_roty": (None, [_f, _f32p]),
+    "srth_mat_rotz": (None, [_f, _f32p]),
+    "srth_mat_mirror": (None, [_int, _int, _int, _f32p]),
+    "srth_mat_shear": (None, [_f, _f, _f, _f, _f, _f, _f32p]),
+    "srth_mat_translate": (None, [_f, _f, _f, _f32p]),
+    "srth_mat_view": (None, [_f32p, _f32p, _f32p]),
+    "srth_mat_inverse": (None, [_f32p, _f32p]),
+    "srth_mat_mul": (None, [_f32p, _f32p, _f32p]),
+    "srth_mat_mul_vec4": (None, [_f32p, _f32p, _f32p]),
+    "srth_renderer_new": (_vp, [_int]),
+    "srth_renderer_free": (None, [_vp]),
+    "srth_renderer_fast_frames": (C.c_uint64, [_vp]),
+    "srth_renderer_set_fast_path": (None, [_vp, _int]),
+    "srth_renderer_render": (_i64, [_vp, _vp, _u32, _u32, _f32p, _int, _f32p]),
+    "srth_renderer_submit": (_int, [_vp, _vp, _u32, _u32, _f32p, _int]),
+    "srth_renderer_collect": (_i64, [_vp, _u32, _u32, _f32p]),
+    "srth_renderer_render_from_camera": (_i64, [_vp, _vp, _u32, _u32, _f32p, _f32p, _int, _int, _f32p]),
+    "srth_renderer_render_posed": (_i64, [_vp, _vp, _u32, _u32, _f32p, _f32p, _u32, _int, _int, _f32p]),
+    "srth_multi_new": (_vp, [C.POINTER(C.c_int), _u32, _u32]),
+    "srth_multi_free": (None, [_vp]),
+    "srth_multi_render": (_i64, [_vp, _vp, _u32, _u32, _f32p, _int, _f32p]),
+}
 
 
 def load():
@@ -26,64 +82,9 @@ def load():
         if not os.path.exists(LIB_PATH):
             raise RuntimeError(f"{LIB_PATH} is missing: run python -m simple_raytracer_amd.build")
         L = C.CDLL(LIB_PATH)
-        L.srth_last_error.restype = C.c_char_p
-        L.srth_om_new.restype = C.c_void_p
-        L.srth_om_free.argtypes = [C.c_void_p]
-        for fn in ("srth_om_load_obj", "srth_om_build_bvh"):
-            getattr(L, fn).argtypes = [C.c_void_p, C.c_char_p]
-        L.srth_om_add_object.argtypes = [C.c_void_p, C.c_char_p, C.c_uint32, _f32p]
-        L.srth_om_clone.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p]
-        L.srth_sort_keys_both_ways.argtypes = [_f32p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
-        L.srth_decode_image.argtypes = [C.c_char_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _u8p]
-        L.srth_om_add_texture.argtypes = [C.c_void_p, C.c_char_p, C.c_int32, C.c_int32, _u8p]
-        L.srth_om_add_textured_object.argtypes = [C.c_void_p, C.c_char_p, C.c_uint32, _f32p, _f32p, C.c_char_p]
-        L.srth_om_add_multi_textured_object.argtypes = [C.c_void_p, C.c_char_p, C.c_uint32, _f32p, _f32p, _i32p, C.c_char_p]
-        L.srth_om_set_color.argtypes = [C.c_void_p, C.c_char_p] + [C.c_float] * 3
-        L.srth_om_set_props.argtypes = [C.c_void_p, C.c_char_p] + [C.c_float] * 3
-        L.srth_om_transform.argtypes = [C.c_void_p, C.c_char_p, _f32p]
-        L.srth_om_num_tris.argtypes = [C.c_void_p, C.c_char_p]
-        L.srth_om_num_tris.restype = C.c_int64
-        L.srth_om_get_points.argtypes = [C.c_void_p, C.c_char_p, _f32p]
-        L.srth_om_get_tri_attrs.argtypes = [C.c_void_p, C.c_char_p, _f32p, _f32p, _i32p, _f32p]
-        L.srth_om_hierarchy_nodes.argtypes = [C.c_void_p, C.c_char_p]
-        L.srth_om_hierarchy_nodes.restype = C.c_int64
-        L.srth_om_hierarchy.argtypes = [C.c_void_p, C.c_char_p, _f32p, C.POINTER(C.c_uint32), _f32p, _f32p]
-        L.srth_renderer_fast_frames.argtypes = [C.c_void_p]
-        L.srth_renderer_fast_frames.restype = C.c_uint64
-        L.srth_renderer_set_fast_path.argtypes = [C.c_void_p, C.c_int]
-        L.srth_flatten.argtypes = [C.c_void_p]
-        L.srth_flatten.restype = C.c_void_p
-        L.srth_flat_free.argtypes = [C.c_void_p]
-        L.srth_flat_desc.argtypes = [C.c_void_p, C.POINTER(abi.SceneDesc)]
-        L.srth_flat_names.argtypes = [C.c_void_p, C.c_char_p, C.c_uint32]
-        L.srth_flat_names.restype = C.c_uint32
-        L.srth_render.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, _f32p, C.c_int, C.c_int, _f32p]
-        L.srth_render.restype = C.c_int64
-        L.srth_renderer_new.argtypes = [C.c_int]
-        L.srth_renderer_new.restype = C.c_void_p
-        L.srth_renderer_free.argtypes = [C.c_void_p]
-        L.srth_renderer_render.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, _f32p, C.c_int, _f32p]
-        L.srth_renderer_render.restype = C.c_int64
-        L.srth_renderer_submit.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, _f32p, C.c_int]
-        L.srth_renderer_collect.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, _f32p]
-        L.srth_renderer_collect.restype = C.c_int64
-        L.srth_renderer_render_from_camera.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, _f32p, _f32p, C.c_int, C.c_int, _f32p]
-        L.srth_renderer_render_from_camera.restype = C.c_int64
-        L.srth_renderer_render_posed.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, _f32p, _f32p, C.c_uint32, C.c_int, C.c_int, _f32p]
-        L.srth_renderer_render_posed.restype = C.c_int64
-        L.srth_write_bmp.argtypes = [C.c_char_p, C.c_uint32, C.c_uint32, _u8p]
-        L.srth_radians.argtypes = [C.c_float]
-        L.srth_radians.restype = C.c_float
-        for name in ("srth_mat_rotx", "srth_mat_roty", "srth_mat_rotz"):
-            getattr(L, name).argtypes = [C.c_float, _f32p]
-        L.srth_mat_scale.argtypes = [C.c_float] * 3 + [_f32p]
-        L.srth_mat_translate.argtypes = [C.c_float] * 3 + [_f32p]
-        L.srth_mat_shear.argtypes = [C.c_float] * 6 + [_f32p]
-        L.srth_mat_mirror.argtypes = [C.c_int] * 3 + [_f32p]
-        L.srth_mat_view.argtypes = [_f32p, _f32p, _f32p]
-        L.srth_mat_inverse.argtypes = [_f32p, _f32p]
-        L.srth_mat_mul.argtypes = [_f32p, _f32p, _f32p]
-        L.srth_mat_mul_vec4.argtypes = [_f32p, _f32p, _f32p]
+        for name, (restype, argtypes) in PROTOTYPES.items():
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = restype, argtypes
         _lib = L
     return _lib
 
@@ -108,6 +109,25 @@ class HostError(RuntimeError):
 def _ok(rc):
     if rc != 0:
         raise HostError(load().srth_last_error().decode())
+
+
+def _count(n):
+    """A render call's count of emitted pixels; negative = it failed."""
+    if n < 0:
+        raise HostError(load().srth_last_error().decode())
+    return int(n)
+
+
+class _Handle:
+    """A handle of the library in self.h, given back by the function cls._free names when the object goes."""
+    _free = None
+
+    def __del__(self):
+        try:
+            if self.h:
+                getattr(self.L, self._free)(self.h); self.h = None
+        except Exception:
+            pass
 
 
 class Transformation:
@@ -156,21 +176,18 @@ class Transformation:
     scale, rotx, roty, rotz, mirror, shear, translate, view = scaleObj, rotateObjX, rotateObjY, rotateObjZ, mirrorObj, shearObj, changeObjPosition, createViewMatrix
 
 
-class ObjectManager:
+class ObjectManager(_Handle):
     """Object.h:59-89 of the reference: string-keyed objects, loadObjFile / transformTriangles /
     createBoundingHierarchy / setColor, plus flatten() (the flat scene of include/srt.h) and render()
     (drop-in for sendRaysAndIntersectPointsColors, on the GPU)."""
 
+    _free = "srth_om_free"
+
     def __init__(self):
         self.L = load()
-        self.om = C.c_void_p(self.L.srth_om_new())
-
-    def __del__(self):
-        try:
-            if self.om:
-                self.L.srth_om_free(self.om); self.om = None
-        except Exception:
-            pass
+        self.h = self.om = C.c_void_p(self.L.srth_om_new())
+        if not self.om:
+            raise HostError(self.L.srth_last_error().decode())
 
     def loadObjFile(self, name): _ok(self.L.srth_om_load_obj(self.om, name.encode()))
 
@@ -217,7 +234,7 @@ class ObjectManager:
             raise KeyError(name)
         pts, order = np.empty((n, 3, 4), np.float32), np.empty(n, np.uint32)
         mn, mx = np.empty((m, 3), np.float32), np.empty((m, 3), np.float32)
-        _ok(self.L.srth_om_hierarchy(self.om, name.encode(), _p(pts), order.ctypes.data_as(C.POINTER(C.c_uint32)), _p(mn), _p(mx)))
+        _ok(self.L.srth_om_hierarchy(self.om, name.encode(), _p(pts), _p(order, _u32p), _p(mn), _p(mx)))
         return pts, order, mn, mx
 
     def tri_attrs(self, name):
@@ -260,14 +277,12 @@ class ObjectManager:
         (px,py,rgb) list, 0 where nothing was emitted; returns (image, n_emitted)."""
         light4 = _f(light4)
         rgb = np.empty((H, W, 3), np.float32)
-        n = self.L.srth_render(self.om, W, H, _p(light4), light_amount, device, _p(rgb))
-        if n < 0:
-            raise HostError(self.L.srth_last_error().decode())
-        return rgb, int(n)
+        return rgb, _count(self.L.srth_render(self.om, W, H, _p(light4), light_amount, device, _p(rgb)))
 
 
-class Renderer:
+class Renderer(_Handle):
     """srt_host::Renderer: a device scene kept across frames (in-place scene updates, pinned buffers, asynchronous frames, camera mode, pose mode)."""
+    _free = "srth_renderer_free"
 
     def __init__(self, device=0):
         self.L = load()
@@ -275,20 +290,12 @@ class Renderer:
         if not self.h:
             raise HostError("srth_renderer_new failed")
 
-    def __del__(self):
-        try:
-            if self.h:
-                self.L.srth_renderer_free(self.h); self.h = None
-        except Exception:
-            pass
-
     def _out(self, W, H, want):
         return np.empty((H, W, 3), np.float32) if want else None
 
     def _ret(self, n, rgb):
-        if n < 0:
-            raise HostError(self.L.srth_last_error().decode())
-        return (rgb, int(n)) if rgb is not None else int(n)
+        n = _count(n)
+        return (rgb, n) if rgb is not None else n
 
     def render(self, om, W, H, light4, light_amount=1, image=True):
         light4 = _f(light4); rgb = self._out(W, H, image)
@@ -323,42 +330,28 @@ class Renderer:
                                                            _p(rgb) if image else None), rgb)
 
 
-class MultiRenderer:
+class MultiRenderer(_Handle):
     """srt_host::MultiRenderer: the framebuffer split over several devices from ONE host process (scene replicated, scanline blocks dealt
     block-cyclically, rows put together on the host)."""
+    _free = "srth_multi_free"
 
     def __init__(self, devices, block_rows=8):
         self.L = load()
-        self.L.srth_multi_new.restype = C.c_void_p
-        self.L.srth_multi_new.argtypes = [C.POINTER(C.c_int), C.c_uint32, C.c_uint32]
-        self.L.srth_multi_free.argtypes = [C.c_void_p]
-        self.L.srth_multi_render.restype = C.c_int64
-        self.L.srth_multi_render.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_float), C.c_int, C.POINTER(C.c_float)]
         dv = (C.c_int * len(devices))(*devices)
         self.h = self.L.srth_multi_new(dv, len(devices), block_rows)
         if not self.h:
             raise HostError(self.L.srth_last_error().decode())
 
-    def __del__(self):
-        try:
-            if self.h:
-                self.L.srth_multi_free(self.h); self.h = None
-        except Exception:
-            pass
-
     def render(self, om, W, H, light4, light_amount=1):
         light4 = _f(light4); rgb = np.empty((H, W, 3), np.float32)
-        n = self.L.srth_multi_render(self.h, om.om, W, H, _p(light4), light_amount, _p(rgb))
-        if n < 0:
-            raise HostError(self.L.srth_last_error().decode())
-        return rgb, int(n)
+        return rgb, _count(self.L.srth_multi_render(self.h, om.om, W, H, _p(light4), light_amount, _p(rgb)))
 
 
 def sort_keys_both_ways(keys):
     """Test hook: (permutation by the hierarchy builder's parallel sort, permutation by std::sort) of float keys."""
     keys = _f(keys)
     a = np.empty(keys.size, np.uint32); b = np.empty(keys.size, np.uint32)
-    _ok(load().srth_sort_keys_both_ways(_p(keys), keys.size, _p(a, C.POINTER(C.c_uint32)), _p(b, C.POINTER(C.c_uint32))))
+    _ok(load().srth_sort_keys_both_ways(_p(keys), keys.size, _p(a, _u32p), _p(b, _u32p)))
     return a, b
 
 
