@@ -1127,4 +1127,8 @@ uint32_t    srt_abi_version(void);
 #ifdef __cplusplus
 }
 #endif
+
+/* Closest-point queries, the nearest triangle within a radius per point, are declared in their own header, which this one brings along:
+ * include/srt_points.h states their definition.  SRT_ABI_VERSION is unchanged by them. */
+#include "srt_points.h"
 #endif /* SRT_H */

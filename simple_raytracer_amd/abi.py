@@ -1,5 +1,6 @@
 """ctypes mirror of include/srt.h -- its structs (STRUCTS), constants (SRT_*) and prototypes (PROTOTYPES), checked against the header by
-tests/test_abi_mirror.py -- and a numpy container for the flat scene.
+tests/test_abi_mirror.py --, of its extension header include/srt_points.h (POINT_STRUCTS, POINT_PROTOTYPES; tests/test_point_ref.py), and
+a numpy container for the flat scene.
 
 The flat scene is the reference's ObjectManager state (Object.h:59-89 in the reference) written out as
 arrays; see include/srt.h for the layout contract.  This module holds no compute.
@@ -191,6 +192,15 @@ class AoFrameOut(C.Structure):
 # the fields of srt_ao_frame_out: name -> (dtype, entries per pixel; None: (n_dirs + 31) // 32 words)
 AO_FRAME_FIELDS = {"n_occluded": (np.uint32, 1), "ao": (np.float32, 1), "occ_bits": (np.uint32, None), "bent": (np.float32, 3), "ao8": (np.uint8, 1)}
 
+class PointOut(C.Structure):
+    """srt_point_out: the arrays a closest-point query fills, as addresses (host arrays in the host form, device pointers in the _device
+    form); 0 = not wanted."""
+    _fields_ = [("tri", C.c_void_p), ("dist2", C.c_void_p), ("point", C.c_void_p), ("vw", C.c_void_p), ("region", C.c_void_p)]
+
+
+# the fields of srt_point_out: name -> (dtype, entries per point)
+POINT_FIELDS = {"tri": (np.int32, 1), "dist2": (np.float32, 1), "point": (np.float32, 3), "vw": (np.float32, 2), "region": (np.uint8, 1)}
+
 # the fields of srt_path_out: name -> (dtype, floats or ints per ray and segment)
 PATH_FIELDS = {"hit_id": (np.int32, 1), "t": (np.float32, 1), "obj": (np.int32, 1), "rgb_linear": (np.float32, 3), "rays": (np.float32, 6)}
 
@@ -204,6 +214,8 @@ STRUCTS = {"srt_scene_desc": SceneDesc, "srt_params": Params, "srt_stats": Stats
            "srt_surface_out": SurfaceOut, "srt_path_desc": PathDesc, "srt_path_out": PathOut, "srt_shadow_rule": ShadowRule, "srt_visibility": Visibility,
            "srt_refraction": Refraction, "srt_fresnel_out": FresnelOut, "srt_fresnel": Fresnel, "srt_ao_desc": AoDesc, "srt_ao_out": AoOut,
            "srt_ao_frame": AoFrame, "srt_ao_frame_out": AoFrameOut}
+# every struct of include/srt_points.h
+POINT_STRUCTS = {"srt_point_out": PointOut}
 
 
 # ---- the prototypes of include/srt.h, in its order: name -> (restype, [argtypes]) ----
@@ -313,6 +325,13 @@ PROTOTYPES.update({
     "srt_last_hip_error": (_int, []),
     "srt_abi_version": (_u32, []),
 })
+
+# ---- the prototypes of include/srt_points.h, in its order, under the same rules ----
+_pout = C.POINTER(PointOut)
+POINT_PROTOTYPES = {
+    "srt_closest_points_device": (_int, [_vp, _u32, _vp, _vp, _vp, _u32, _vp, _pout]),
+    "srt_closest_points": (_int, [_vp, _u32, _f32p, _f32p, _u32p, _u32, _pout, _stats]),
+}
 
 
 def _ptr(a, ty):

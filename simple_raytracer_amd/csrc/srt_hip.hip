@@ -178,6 +178,9 @@ struct srt_scene {
     DevArray<float, 3> rq_aodirs; DevArray<uint32_t> rq_aocnt; DevArray<float> rq_aoval; DevArray<uint32_t> rq_aobits;
     // srt_render_ao / srt_render_ao_hits: the rotation table of a host call (capacity counts entries) and the two further arrays of srt_ao_frame_out
     DevArray<float, 2> rq_aorot; DevArray<float, 3> rq_aobent; DevArray<uint8_t> rq_ao8;
+    // srt_closest_points: the points, radii and masks of a host call and its (v, w) rows; tri, dist2, point and region go through rq_hit /
+    // rq_t / rq_spoint / rq_occ
+    DevArray<float, 3> rq_points; DevArray<float> rq_radius; DevArray<uint32_t> rq_pmask; DevArray<float, 2> rq_vw;
     DevArray<float, 3> d_qlights; Pinned<float, 3> h_qlights; uint32_t qlights_valid = 0;
     Event qlights_sent; hipStream_t qlights_stream = nullptr; bool qlights_settled = true;
     int n_cu = 256;
@@ -1829,6 +1832,22 @@ static int occluded_device_impl(srt_scene* s, uint32_t n, const float* d_rays, c
     return launch_query(builds[build_index(d_t_range)], q.grid, q.stream, s->dev, n, d_rays, rays_wide(d_rays), d_skip_obj, d_occluded, query_range(d_t_range));
 }
 
+// srt_closest_points: the nearest triangle within a radius per point, one launch (k_query_points).  A call with a mask array launches the
+// MASK build; one without launches the build that reads neither the array nor the scene's table.
+// count_hits: the host entry point wants hit_rays also without SRT_FLAG_COUNT_WORK
+static inline bool points_wanted(const srt_point_out* o) { return o->tri || o->dist2 || o->point || o->vw || o->region; }
+static int closest_points_device_impl(srt_scene* s, uint32_t n, const float* d_points, const float* d_radius, const uint32_t* d_point_mask, uint32_t flags,
+                                      hipStream_t stream, const srt_point_out* out, bool count_hits) {
+    SRT_TRY(check_query(s, n, d_points, flags));
+    if (!out) return SRT_ERR_ARG;
+    if (!n || (!count_hits && !points_wanted(out))) return SRT_OK;
+    const bool count = (flags & SRT_FLAG_COUNT_WORK) != 0;
+    QueryLaunch q;
+    SRT_TRY(query_prologue(s, n, stream, nullptr, count || count_hits, &q));
+    static const std::array builds = { BUILDS_2(k_query_points) };
+    return launch_query(builds[build_index(count, d_point_mask)], q.grid, q.stream, s->dev, n, d_points, d_radius, *out, q.ctr, query_mask(s, d_point_mask));
+}
+
 // What a shading kernel takes of the params (after query_prologue: the light table is the handle's device copy)
 static QueryShade query_shade(const srt_scene* s, const srt_params* p) {
     QueryShade qs;
@@ -2158,6 +2177,22 @@ static int trace_rays_impl(srt_scene* s, uint32_t n, const float* rays, const fl
         return trace_rays_device_impl(s, n, i_rays.on_device(), i_range.on_device(), flags, st, o_hit.on_device(), o_t.on_device(), o_bary.on_device(), true,
                                       staged_mask(s, mask));
     }, o_hit, o_t, o_bary, i_rays, i_range, i_mask));
+    return stats ? query_stats(s, n, 0, stats) : SRT_OK;
+}
+
+static int closest_points_impl(srt_scene* s, uint32_t n, const float* points, const float* radius, const uint32_t* point_mask, uint32_t flags,
+                               const srt_point_out* out, srt_stats* stats) {
+    SRT_TRY(check_query(s, n, points, flags));
+    if (!out) return SRT_ERR_ARG;
+    if (stats) std::memset(stats, 0, sizeof(*stats));
+    if (!n) return SRT_OK;
+    const auto o_tri = query_out(out->tri, s->rq_hit, n); const auto o_d2 = query_out(out->dist2, s->rq_t, n); const auto o_pt = query_out(out->point, s->rq_spoint, n);
+    const auto o_vw = query_out(out->vw, s->rq_vw, n); const auto o_reg = query_out(out->region, s->rq_occ, n);
+    const auto i_pts = query_in(points, s->rq_points, n); const auto i_rad = query_in(radius, s->rq_radius, n); const auto i_mask = query_in(point_mask, s->rq_pmask, n);
+    SRT_TRY(query_round_trip(s, [&](hipStream_t st) {
+        const srt_point_out dev = { o_tri.on_device(), o_d2.on_device(), o_pt.on_device(), o_vw.on_device(), o_reg.on_device() };
+        return closest_points_device_impl(s, n, i_pts.on_device(), i_rad.on_device(), i_mask.on_device(), flags, st, &dev, stats != nullptr);
+    }, o_tri, o_d2, o_pt, o_vw, o_reg, i_pts, i_rad, i_mask));
     return stats ? query_stats(s, n, 0, stats) : SRT_OK;
 }
 
@@ -2598,6 +2633,15 @@ int srt_render_ao_hits(srt_scene* s, const srt_params* p, const int32_t* hit_id,
                        const srt_visibility* vis, const srt_ao_frame_out* out, srt_stats* stats) {
     const QueryHits hits = { hit_id, t };
     return guarded([&] { return render_ao_impl(s, p, &hits, flags, ao, fr, vis, nullptr, nullptr, out, stats); });
+}
+
+int srt_closest_points_device(srt_scene* s, uint32_t n, const float* d_points, const float* d_radius, const uint32_t* d_point_mask, uint32_t flags, void* stream,
+                              const srt_point_out* out) {
+    return guarded([&] { return closest_points_device_impl(s, n, d_points, d_radius, d_point_mask, flags, (hipStream_t)stream, out, false); });
+}
+int srt_closest_points(srt_scene* s, uint32_t n, const float* points, const float* radius, const uint32_t* point_mask, uint32_t flags, const srt_point_out* out,
+                       srt_stats* stats) {
+    return guarded([&] { return closest_points_impl(s, n, points, radius, point_mask, flags, out, stats); });
 }
 
 void* srt_host_alloc(size_t bytes) {

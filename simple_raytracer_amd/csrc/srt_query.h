@@ -178,16 +178,35 @@ __device__ __forceinline__ int32_t skip_hidden(const DevScene& s, const uint32_t
     return next;
 }
 
+// The node test of a walk: the ray's slab test, or the policy's own (query_walk below).
+template <bool RAY, typename Tests>
+__device__ __forceinline__ bool node_pass(const Tests& ts, const V3 o, const V3 d, const RayRcp rc, const float4 a, const float4 b) {
+    if constexpr (RAY) return slab_pass<true>(o, d, rc, a.x, a.y, a.z, a.w, b.x, b.y);
+    else return ts.node(a, b);
+}
+
 // MASK: only the objects k with (obj_mask[k] & ray_m) != 0 are walked (skip_hidden); the builds without it never read the two arguments.
-template <bool COUNT, bool RANGE, typename Merge, bool MASK = false>
+// TESTS: what is walked.  The queue, the prefix sum, the leaf slices, the flush and the tail are stated here once; the two leaf functions
+// and the owner's LDS rows are a policy.  WalkRay, the default, is the ray's: 6 rows (o, d), 8 with RANGE, slab_pass and ray_triangle --
+// the statements this function always had, left where they were, so that every ray kernel compiles to the code it compiled to before the
+// policy existed (profiles/point_query_kernels.txt).  Any other policy (WalkPoint, at the end of this file) brings
+//     init(rows, lane)                          the owning lane's operands into the wave's rows (`wray`)
+//     node(a, b)                                the lane's own test of a node record's box
+//     leaf(rows, src, p1, e1, e2, tri, mg)      the triangle test with the operands of owner `src`; a qualifying result is offered to mg
+// and is walked with o, d, t_min and t_max unread.
+struct WalkRay {};
+template <bool COUNT, bool RANGE, typename Merge, bool MASK = false, typename Tests = WalkRay>
 __device__ __forceinline__ void query_walk(const DevScene& s, const bool live, const V3 o, const V3 d, const uint32_t lane, uint32_t* q,
                                            const Merge mg, float (*wray)[64], unsigned long long& n_node, unsigned long long& n_tri,
                                            const float t_min = 0.0f, const float t_max = 0.0f, const uint32_t* __restrict__ obj_mask = nullptr,
-                                           const uint32_t ray_m = 0u) {
+                                           const uint32_t ray_m = 0u, const Tests ts = Tests{}) {
+    constexpr bool RAY = std::is_same<Tests, WalkRay>::value;
     mg.init(lane);
-    wray[0][lane] = o.x; wray[1][lane] = o.y; wray[2][lane] = o.z;
-    wray[3][lane] = d.x; wray[4][lane] = d.y; wray[5][lane] = d.z;
-    if (RANGE) { wray[6][lane] = t_min; wray[7][lane] = t_max; }
+    if constexpr (RAY) {
+        wray[0][lane] = o.x; wray[1][lane] = o.y; wray[2][lane] = o.z;
+        wray[3][lane] = d.x; wray[4][lane] = d.y; wray[5][lane] = d.z;
+        if (RANGE) { wray[6][lane] = t_min; wray[7][lane] = t_max; }
+    } else ts.init(wray, lane);
     const RayRcp rc = ray_rcp(o, d);
     const float4* nodes4 = reinterpret_cast<const float4*>(s.nodes);
     const float4* tris4 = reinterpret_cast<const float4*>(s.tris);
@@ -213,7 +232,7 @@ __device__ __forceinline__ void query_walk(const DevScene& s, const bool live, c
                 int32_t next;
                 bool stay = false;
                 // (a leaf pushed in slices is tested again per slice: same ray, same box, same answer)
-                if (slab_pass<true>(o, d, rc, a.x, a.y, a.z, a.w, b.x, b.y)) {
+                if (node_pass<RAY>(ts, o, d, rc, a, b)) {
                     next = i + 1;
                     if (leaf >= 0) {
                         const int32_t c = (leaf & LEAF_MAX) - leaf_off;
@@ -250,15 +269,22 @@ __device__ __forceinline__ void query_walk(const DevScene& s, const bool live, c
             if (lane < m) {
                 const uint32_t e = q[qn + lane];
                 const uint32_t src = e & 63u, tri = e >> 6;
-                const V3 os = mk(wray[0][src], wray[1][src], wray[2][src]), ds = mk(wray[3][src], wray[4][src], wray[5][src]);
-                float lo = 0.0f, hi = 0.0f;
-                if (RANGE) { lo = wray[6][src]; hi = wray[7][src]; }
-                V3 p1, e1, e2;
-                load_tri_edges(tris4, tri, p1, e1, e2);
-                if (COUNT) n_tri++;
-                const float t = ray_triangle(os, ds, p1, e1, e2);
-                // candidate iff t != -inf && t < +inf (the initial distanceComparison, :408); NaN fails '<'
-                if (t != SRT_NEG_INF && t < __builtin_inff() && (!RANGE || (!(t < lo) && !(t > hi)))) mg.offer(src, tri, t);
+                if constexpr (RAY) {
+                    const V3 os = mk(wray[0][src], wray[1][src], wray[2][src]), ds = mk(wray[3][src], wray[4][src], wray[5][src]);
+                    float lo = 0.0f, hi = 0.0f;
+                    if (RANGE) { lo = wray[6][src]; hi = wray[7][src]; }
+                    V3 p1, e1, e2;
+                    load_tri_edges(tris4, tri, p1, e1, e2);
+                    if (COUNT) n_tri++;
+                    const float t = ray_triangle(os, ds, p1, e1, e2);
+                    // candidate iff t != -inf && t < +inf (the initial distanceComparison, :408); NaN fails '<'
+                    if (t != SRT_NEG_INF && t < __builtin_inff() && (!RANGE || (!(t < lo) && !(t > hi)))) mg.offer(src, tri, t);
+                } else {
+                    V3 p1, e1, e2;
+                    load_tri_edges(tris4, tri, p1, e1, e2);
+                    if (COUNT) n_tri++;
+                    ts.leaf(wray, src, p1, e1, e2, tri, mg);
+                }
             }
             __builtin_amdgcn_wave_barrier();
         }
@@ -1404,4 +1430,135 @@ void k_render_ao(DevScene s, DevParams fp, uint32_t spp, uint32_t spp_m, QueryMa
         if (out.ao8) out.ao8[ri] = (uint8_t)(int)(total * 255.0f + 0.5f);
     }
     count_walks<COUNT>(counters, n_node, n_tri, n_node_s, n_tri_s);
+}
+
+// =================================================================================================
+// Closest point (srt_closest_points, include/srt_points.h): for a point p with radius r, the triangle nearest to p within r.
+// The walk is query_walk as it stands -- the same node records, the same queue of (triangle, owning lane) pairs, the same slices, the same
+// (value bits << 32 | id) atomicMin -- with the point's tests: a point-box distance test in the place of slab_pass, Ericson's closest
+// point on a triangle in the place of ray_triangle, on the operands load_tri_edges gives the ray test (P1, e1, e2).  The radius is the
+// caller's and never shrinks: the candidate set, and with it the counters, are a function of the scene and the point alone
+// (why a shrinking radius is not bit-safe: DESIGN.md s5, "Closest point").
+// WalkPoint keeps 4 rows a wave: p.xyz and r2.
+// =================================================================================================
+// Closest point on triangle (P1, P1 + e1, P1 + e2) to p, Real-Time Collision Detection 5.1.5, f32 without contraction.  The regions in
+// the header's order, the first true one wins; `region`: 0 face, 1 edge 1-2, 2 edge 2-3, 3 edge 1-3, 4..6 vertex 1..3.  Each of (v, w) is
+// one IEEE divide of the winning region's own operands (or a literal): the operands are selected first, so a lane divides twice, not seven
+// times; a quotient no region reads may be anything.
+struct ClosestPoint { float v, w, dist2; V3 point; uint32_t region; };
+__device__ __forceinline__ void closest_point(ClosestPoint& c, const V3 p, const V3 p1, const V3 e1, const V3 e2) {
+    const V3 ap = p - p1;
+    const float d1 = dot3(e1, ap), d2 = dot3(e2, ap);
+    const V3 bp = ap - e1;
+    const float d3 = dot3(e1, bp), d4 = dot3(e2, bp);
+    const V3 cp = ap - e2;
+    const float d5 = dot3(e1, cp), d6 = dot3(e2, cp);
+    const float vc = d1 * d4 - d3 * d2, vb = d5 * d2 - d1 * d6, va = d3 * d6 - d5 * d4;
+    const float g = d4 - d3, h = d5 - d6;
+    const bool r4 = d1 <= 0.0f && d2 <= 0.0f;
+    const bool r5 = d3 >= 0.0f && d4 <= d3;
+    const bool r1 = vc <= 0.0f && d1 >= 0.0f && d3 <= 0.0f;
+    const bool r6 = d6 >= 0.0f && d5 <= d6;
+    const bool r3 = vb <= 0.0f && d2 >= 0.0f && d6 <= 0.0f;
+    const bool r2 = va <= 0.0f && g >= 0.0f && h >= 0.0f;
+    const uint32_t region = r4 ? 4u : r5 ? 5u : r1 ? 1u : r6 ? 6u : r3 ? 3u : r2 ? 2u : 0u;
+    const float den = (va + vb) + vc;
+    // v's divide: edge 1-2 d1 / (d1 - d3), face vb / den;  w's: edge 1-3 d2 / (d2 - d6), edge 2-3 g / (g + h), face vc / den
+    const float vn = region == 1u ? d1 : vb, vd = region == 1u ? d1 - d3 : den;
+    const float wn = region == 3u ? d2 : region == 2u ? g : vc, wd = region == 3u ? d2 - d6 : region == 2u ? g + h : den;
+    const float vq = vn / vd, wq = wn / wd;
+    float v, w;
+    switch (region) {
+        case 4u: v = 0.0f; w = 0.0f; break;
+        case 5u: v = 1.0f; w = 0.0f; break;
+        case 1u: v = vq; w = 0.0f; break;
+        case 6u: v = 0.0f; w = 1.0f; break;
+        case 3u: v = 0.0f; w = wq; break;
+        case 2u: w = wq; v = 1.0f - w; break;
+        default: v = vq; w = wq; break;
+    }
+    const V3 q = mk(e1.x * v + e2.x * w, e1.y * v + e2.y * w, e1.z * v + e2.z * w);
+    const V3 rr = ap - q;
+    c.v = v; c.w = w; c.region = region;
+    c.dist2 = (rr.x * rr.x + rr.y * rr.y) + rr.z * rr.z;
+    c.point = p1 + q;
+}
+
+// The point's tests (query_walk's TESTS).  node: the squared distance from p to the box, per axis max(mn - p, p - mx, 0) by the header's two
+// comparisons (what a NaN does to them is part of the definition); a node passes iff !(b2 > r2).  leaf: a candidate qualifies iff dist2 <= r2 (a NaN fails); dist2 is a sum of
+// squares and never -0, so hit_key's order is (dist2, id) order.
+struct WalkPoint {
+    V3 p;
+    float r2;
+    __device__ __forceinline__ void init(float (*rows)[64], const uint32_t lane) const {
+        rows[0][lane] = p.x; rows[1][lane] = p.y; rows[2][lane] = p.z; rows[3][lane] = r2;
+    }
+    static __device__ __forceinline__ float axis(const float mn, const float mx, const float x) {
+        const float e = mn - x, f = x - mx;
+        const float dx = e > f ? e : f;
+        return dx > 0.0f ? dx : 0.0f;
+    }
+    __device__ __forceinline__ bool node(const float4 a, const float4 b) const {
+        const float dx = axis(a.x, a.w, p.x), dy = axis(a.y, b.x, p.y), dz = axis(a.z, b.y, p.z);
+        const float b2 = (dx * dx + dy * dy) + dz * dz;
+        return !(b2 > r2);
+    }
+    template <typename Merge>
+    __device__ __forceinline__ void leaf(float (*rows)[64], const uint32_t src, const V3 p1, const V3 e1, const V3 e2, const uint32_t tri, const Merge& mg) const {
+        ClosestPoint c;
+        closest_point(c, mk(rows[0][src], rows[1][src], rows[2][src]), p1, e1, e2);
+        if (c.dist2 <= rows[3][src]) mg.offer(src, tri, c.dist2);
+    }
+};
+
+// k_query_points: one point per lane.  radius NULL: +inf; a point whose radius is negative or NaN walks nothing.  MASK: point i is walked with
+// qm.ray[i] (NULL: all ones) against qm.obj, as k_query_closest_masked walks a ray; the build without MASK reads neither.
+// Phase 2, as winner_at for rays: the owning lane recomputes the winner's (v, w, region, point, dist2) from the key's triangle and its own p
+// -- the walk's function on the walk's operands, hence the walk's bits.  point and vw leave transposed through the wave's rows (store_rows).
+// counters: [1] / [2] node / triangle tests (COUNT), [8 + 8 * shard] the points that found a triangle.
+template <bool COUNT, bool MASK>
+__global__ __launch_bounds__(256) void k_query_points(DevScene s, uint32_t n_points, const float* __restrict__ points, const float* __restrict__ radius,
+                                                      srt_point_out out, unsigned long long* __restrict__ counters, QueryMask qm) {
+    __shared__ uint32_t q_all[4][QCAP];
+    __shared__ unsigned long long best_all[256];
+    __shared__ float row_all[4][4][64];
+    const uint32_t lane = wave_lane(), wave = wave_index();
+    unsigned long long* best = best_all + wave * 64;
+    float (*rows)[64] = row_all[wave];
+    const size_t base = wave_base(wave), ri = base + lane;
+    const bool live = ri < (size_t)n_points;
+    unsigned long long n_node = 0, n_tri = 0;
+    V3 p = mk(0.0f, 0.0f, 0.0f);
+    float r = __builtin_inff();
+    uint32_t m = 0xFFFFFFFFu;
+    if (live) {
+        const float* pp = points + 3 * ri;
+        p = mk(pp[0], pp[1], pp[2]);
+        if (radius) r = radius[ri];
+        if (MASK && qm.ray) m = qm.ray[ri];
+    }
+    const bool walks = live && r >= 0.0f;               // (a NaN radius fails the comparison)
+    query_walk<COUNT, false, MergeClosest, MASK>(s, walks, p, p, lane, q_all[wave], MergeClosest{ best }, rows, n_node, n_tri, 0.0f, 0.0f, qm.obj, m, WalkPoint{ p, r * r });
+    const Winner h = winner_of(live ? best[lane] : ~0ull);
+    ClosestPoint c;
+    c.v = 0.0f; c.w = 0.0f; c.dist2 = __builtin_inff(); c.point = mk(0.0f, 0.0f, 0.0f); c.region = 0u;
+    if (h.is_hit) {
+        V3 p1, e1, e2;
+        load_tri_edges(reinterpret_cast<const float4*>(s.tris), (size_t)h.id, p1, e1, e2);
+        closest_point(c, p, p1, e1, e2);
+    }
+    if (live) {
+        if (out.tri) out.tri[ri] = h.id;
+        if (out.dist2) out.dist2[ri] = c.dist2;
+        if (out.region) out.region[ri] = (uint8_t)c.region;
+    }
+    if (base < (size_t)n_points) {                      // wave-uniform; the walk is over: the points' rows are the stage
+        const size_t left = (size_t)n_points - base;
+        const uint32_t live_rows = (uint32_t)(left < 64 ? left : 64);
+        __builtin_amdgcn_wave_barrier();
+        if (out.point) { const float v[3] = { c.point.x, c.point.y, c.point.z }; store_rows<3>(out.point, base, lane, live_rows, v, &rows[0][0]); }
+        if (out.vw) { const float v[2] = { c.v, c.w }; store_rows<2>(out.vw, base, lane, live_rows, v, &rows[0][0]); }
+    }
+    if (counters) count_hits(counters, h.is_hit, blockIdx.x);
+    count_walks<COUNT>(counters, n_node, n_tri);
 }

@@ -1,4 +1,4 @@
-"""ctypes binding of the C ABI in include/srt.h (libsrt_hip.so).
+"""ctypes binding of the C ABI in include/srt.h and its extension header include/srt_points.h (libsrt_hip.so).
 
 The product path has NO CPU fallback: if the HIP library is missing or no GPU is visible, this
 raises.  (The CPU restatement under oracle/ is test infrastructure and is never imported here.)
@@ -16,6 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libsrt_hip.so")
 
 ABI_SYMBOLS = tuple(abi.PROTOTYPES)           # every symbol include/srt.h declares
+POINT_SYMBOLS = tuple(abi.POINT_PROTOTYPES)    # every symbol include/srt_points.h declares
 MULTI_HIT_MAX = abi.SRT_MULTI_HIT_MAX
 
 _f32p, _i32p, _u8p, _u32p = C.POINTER(C.c_float), C.POINTER(C.c_int32), C.POINTER(C.c_uint8), C.POINTER(C.c_uint32)
@@ -39,7 +40,7 @@ def load(path=None):
             raise RuntimeError(f"{path or LIB_PATH} is missing: the HIP extension must be built "
                                "(python -m simple_raytracer_amd.build); there is no CPU fallback")
         L = C.CDLL(path or LIB_PATH)
-        for name, (restype, argtypes) in abi.PROTOTYPES.items():
+        for name, (restype, argtypes) in {**abi.PROTOTYPES, **abi.POINT_PROTOTYPES}.items():
             fn = getattr(L, name)
             fn.restype, fn.argtypes = restype, argtypes
         if path is not None:
@@ -477,6 +478,29 @@ class DeviceScene:
         self._paths_device("render", (self.h,), params, depth, reflectance, bounce_t_min, stream, rgb_linear, rgb8, (seg_hit_id, seg_t, seg_obj, seg_rgb_linear, seg_rays),
                            shadow, visibility, ior, fresnel, (side_hit_id, side_t, side_rgb_linear, side_fresnel))
 
+    def closest_points(self, points, radius=None, point_mask=None, count=False, want=("tri", "dist2", "point", "vw", "region")):
+        """srt_closest_points: for every point of `points` (n x 3, host array) the nearest triangle within `radius` (n floats, one float for
+        all, or None = +inf) and the nearest point on it.  Returns a dict of the arrays named in `want` -- tri n (-1: none within the
+        radius), dist2 n (the squared distance, +inf: none), point n x 3, vw n x 2 (point = P1 + v e1 + w e2), region n uint8 (0 face, 1..3
+        edges, 4..6 vertices) -- + 'stats'; count=True fills the node / triangle test counts.  The radius never shrinks during the walk: pass
+        one for speed.  point_mask (n uint32, or None = all ones): only the objects whose mask (set_object_masks) shares a bit with the
+        point's are searched."""
+        pts = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        n = pts.shape[0]
+        rad = None if radius is None else np.ascontiguousarray(np.broadcast_to(np.asarray(radius, np.float32).reshape(-1), (n,)), np.float32)
+        pm = None if point_mask is None else _ray_mask(point_mask, n)
+        out, _ = _outputs(want, (n,), _POINT)
+        po = abi.PointOut(*_addresses(out, _POINT))
+        return _with_stats(out, self.L.srt_closest_points, "srt_closest_points", self.h, n, _host(pts, _f32p), _host(rad, _f32p), _host(pm, _u32p),
+                           _query_flags(count=count), C.byref(po))
+
+    def closest_points_device(self, n, d_points, radius=0, point_mask=0, stream=0, count=False, tri=0, dist2=0, point=0, vw=0, region=0):
+        """srt_closest_points_device: raw device pointers (ints, e.g. torch.Tensor.data_ptr()) in -- the points (n x 3 floats), `radius` (n
+        floats, 0 = +inf), `point_mask` (n uint32, 0 = all ones) and the outputs (0: not wanted) --, asynchronous on `stream`, one launch."""
+        po = _wanted(abi.PointOut, tri, dist2, point, vw, region)
+        _check(self.L.srt_closest_points_device(self.h, n, d_points, radius or None, point_mask or None, _query_flags(count=count), stream, C.byref(po)),
+               "srt_closest_points_device")
+
     def sync(self):
         return _with_stats({}, self.L.srt_sync, "srt_sync", self.h)["stats"]
 
@@ -514,6 +538,7 @@ _HIT = {"hit_id": (np.int32, ()), "t": (np.float32, ())}
 _CLOSEST = {**_HIT, "bary": (np.float32, (3,))}
 _FRAME = {**_HIT, "rgb_linear": (np.float32, (3,)), "rgb8": (np.uint8, (3,))}
 _SURFACE = {k: (ty, () if c == 1 else (c,)) for k, (ty, c) in abi.SURFACE_FIELDS.items()}
+_POINT = {k: (ty, () if c == 1 else (c,)) for k, (ty, c) in abi.POINT_FIELDS.items()}
 _PATH_SUMS = {"rgb_linear": (np.float32, (3,)), "rgb8": (np.uint8, (3,))}
 _PATH_SEGMENTS = {"seg_" + k: (ty, () if c == 1 else (c,)) for k, (ty, c) in abi.PATH_FIELDS.items()}
 # the rows of srt_fresnel_out as result keys: side_hit_id, side_t, side_rgb_linear, fresnel

@@ -48,7 +48,11 @@ to waves and under either deal alone (the libraries of python -m simple_raytrace
 shipped calls on rays torch makes per call (24 B a pixel, four elementwise launches) -- srt_ao_rays_device and, on a render's hits,
 srt_ao_hits_device: the yardsticks -- beside srt_render_ao_device and srt_render_ao_hits_device without a table, with a 4 x 4 table of
 rotations, and with that table and the bent normal.
-Usage: python tools/ray_query_probe.py [--reps N] [--trace] [--shade | --range | --shade-range | --multi | --surface | --paths | --shadow-rule | --masked | --refract | --fresnel | --ao | --render-ao [--rounds R]]     (--trace: few repetitions, for a run under rocprofv3 --kernel-trace --stats)"""
+--points: instead, the closest-point query (srt_closest_points_device) on the hit points of the same frame, pushed off the surface towards
+the camera by a few offsets, over a few radii on a sub-sample of the hits and with no radius (+inf: every triangle is a candidate) on a
+smaller one, in one run beside srt_trace_rays_device on the rays of the same pixels -- the yardstick of what a walk costs -- and the node and
+triangle tests per point from the counting build.
+Usage: python tools/ray_query_probe.py [--reps N] [--trace] [--shade | --range | --shade-range | --multi | --surface | --paths | --shadow-rule | --masked | --refract | --fresnel | --ao | --render-ao | --points [--rounds R]]     (--trace: few repetitions, for a run under rocprofv3 --kernel-trace --stats)"""
 import argparse, os, sys, time
 import numpy as np
 import torch                                   # first: torch initialises HIP before the library does
@@ -771,8 +775,55 @@ def render_ao_section(reps, rounds):
     ds.close()
 
 
+def points_section(reps, rounds):
+    """What a closest-point walk costs beside a ray's: the hit points of the 1080p frame, OFFSETS units off the surface towards the camera,
+    with RADII on every STEP-th hit and with no radius on every (16 STEP)-th, each beside srt_trace_rays_device on the rays of the same pixels."""
+    OFFSETS, RADII, STEP = (0.25, 2.0, 16.0), (1.0, 4.0, 16.0, 64.0), 4
+    dev = torch.device("cuda", 0); torch.zeros(1, device=dev)
+    g = gu.GoldenScene("ground_bunny")
+    ds = lib.DeviceScene(g.flat)
+    side = torch.cuda.Stream(device=dev)
+    cur = side.cuda_stream
+    rays = frame_rays()
+    frame = ds.trace_rays(rays, want=("hit_id", "t"))
+    hits = np.flatnonzero(frame["hit_id"] >= 0)
+    P = rays[hits, 3:6] * frame["t"][hits, None]                      # (the origin is 0)
+    unit = rays[hits, 3:6] / np.linalg.norm(rays[hits, 3:6], axis=1, keepdims=True)
+    print(f"closest points, K3 ground_bunny {W}x{H}: {g.flat.n_tris} triangles, {g.flat.n_nodes} nodes; {hits.size} hit points; {rounds} rounds of {reps} calls, forms "
+          f"alternating; ms a call; min / max: the spread of the rounds")
+    for step, radii in ((STEP, RADII), (16 * STEP, (np.inf,))):
+        sel = np.arange(0, hits.size, step)
+        n = sel.size
+        d_rays = torch.from_numpy(np.ascontiguousarray(rays[hits[sel]])).to(dev)
+        hit, t = torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.float32, device=dev)
+        tri, d2 = torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.float32, device=dev)
+        pt = torch.empty((n, 3), dtype=torch.float32, device=dev)
+        print(f"every {step}th hit: {n} points, {n} rays")
+        print(f"{'points':34s} {'form':34s} {'median':>8s} {'min':>8s} {'max':>8s} {'/ first':>7s}")
+        for off in OFFSETS:
+            pts = np.ascontiguousarray(P[sel] - unit[sel] * np.float32(off), np.float32)
+            d_pts = torch.from_numpy(pts).to(dev)
+            d_rad = {r: torch.full((n,), float(r), dtype=torch.float32, device=dev) for r in radii}
+            forms = {"trace_rays (yardstick)": lambda: ds.trace_rays_device(n, d_rays.data_ptr(), stream=cur, hit_id=hit.data_ptr(), t=t.data_ptr())}
+            for r in radii:
+                forms[f"closest_points, radius {r:g}"] = (lambda r=r: ds.closest_points_device(n, d_pts.data_ptr(), radius=0 if np.isinf(r) else d_rad[r].data_ptr(), stream=cur,
+                                                                                               tri=tri.data_ptr(), dist2=d2.data_ptr(), point=pt.data_ptr()))
+            report(f"{off:g} off the surface", rounds_of(forms, reps, rounds, side))
+            side.synchronize()
+            for r in radii:
+                o = ds.closest_points(pts, radius=None if np.isinf(r) else r, count=True, want=("tri", "dist2"))
+                st = o["stats"]
+                found = o["tri"] >= 0
+                print(f"{'':34s} radius {r:g}: found {int(found.sum())} of {n}, median distance {float(np.sqrt(np.median(o['dist2'][found]))) if found.any() else float('nan'):.3f}; "
+                      f"per point {st['node_tests_primary'] / n:.1f} node tests, {st['tri_tests_primary'] / n:.1f} triangle tests")
+            st = ds.trace_rays(rays[hits[sel]], count=True, want=())["stats"]
+            print(f"{'':34s} the rays: per ray {st['node_tests_primary'] / n:.1f} node tests, {st['tri_tests_primary'] / n:.1f} triangle tests")
+    ds.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--points", action="store_true")
     ap.add_argument("--render-ao", action="store_true", dest="render_ao")
     ap.add_argument("--ao", action="store_true")
     ap.add_argument("--fresnel", action="store_true")
@@ -790,6 +841,8 @@ def main():
     ap.add_argument("--rounds", type=int, default=7)
     a = ap.parse_args()
     reps = 3 if a.trace else a.reps
+    if a.points:
+        return points_section(reps, 2 if a.trace else a.rounds)
     if a.render_ao:
         return render_ao_section(reps, 2 if a.trace else a.rounds)
     if a.ao:
