@@ -158,29 +158,14 @@ struct srt_scene {
     DevArray<unsigned long long> ws_shadow;
     DevArray<uint32_t, 3> ws_qlist; DevArray<uint32_t> d_qcount; uint32_t qcap = 0;      // quadrants with hits: 64 shard lists of qcap entries, their counters
     DevArray<float, 3> ws_acc, ws_sub; DevArray<int32_t> ws_sub_hit; DevArray<float> ws_sub_t;
-    // ray queries (srt_trace_rays / srt_occluded, the host entry points): the rays and results of one call, capacities count rays; and the
-    // counter set private to queries (laid out like a render's), which no render reads, zeroes or reports
-    DevArray<float, 6> rq_rays; DevArray<int32_t> rq_hit; DevArray<float> rq_t; DevArray<float, 3> rq_bary; DevArray<int32_t> rq_skip; DevArray<uint8_t> rq_occ;
-    DevArray<float, 2> rq_range;                  // the t intervals of a call that brings them
-    DevArray<uint32_t> rq_nhits;                  // srt_trace_rays_multi: hits per ray (its n x k rows go through rq_hit / rq_t / rq_bary, k units a ray)
+    // ray queries, the host entry points: the device memory of ONE call -- what it brings and what it wants, cut afresh by every
+    // query_round_trip (capacity counts bytes).  One block is enough: a host form runs on the scene's own stream and synchronises before it
+    // returns, so no call finds another's arrays in use, and no _device entry point reads it.
+    DevArray<char> query_block;
+    // the counter set private to queries (laid out like a render's), which no render reads, zeroes or reports
     DevArray<unsigned long long> d_qctr;
-    // srt_shade_rays: the query's own result buffers and its own light table (a render's d_lights may be in use on another stream): the
-    // pinned copy, the event behind its last upload, the stream that upload went to, and whether it is known to have arrived
-    DevArray<float, 3> rq_lin; DevArray<uint8_t, 3> rq_rgb8;
-    // srt_surface_rays / srt_surface_hits: the six arrays of srt_surface_out, and the t of the hits a caller brings (their ids go through rq_skip)
-    DevArray<int32_t> rq_sobj; DevArray<float, 3> rq_spoint, rq_snormal, rq_scolor, rq_smat; DevArray<float, 6> rq_sbounce; DevArray<float> rq_tin;
-    // srt_shade_paths: the reflectance table of a host call (capacity counts objects) and the per-segment sums (capacity counts depth x n rows);
-    // the other per-segment rows go through rq_hit / rq_t / rq_sobj / rq_sbounce, depth units a ray
-    DevArray<float> rq_refl; DevArray<float> rq_ior; DevArray<float, 3> rq_plin;
-    DevArray<float> rq_f0; DevArray<int32_t> rq_fhit; DevArray<float> rq_ft; DevArray<float, 3> rq_flin; DevArray<float> rq_fres;      // the Fresnel table, the side rays' rows
-    // srt_ao_rays / srt_ao_hits: the direction table of a host call (capacity counts directions) and the three arrays of srt_ao_out (rq_aobits:
-    // capacity counts words, W a ray); a caller's hits go through rq_skip / rq_tin as srt_surface_hits' do
-    DevArray<float, 3> rq_aodirs; DevArray<uint32_t> rq_aocnt; DevArray<float> rq_aoval; DevArray<uint32_t> rq_aobits;
-    // srt_render_ao / srt_render_ao_hits: the rotation table of a host call (capacity counts entries) and the two further arrays of srt_ao_frame_out
-    DevArray<float, 2> rq_aorot; DevArray<float, 3> rq_aobent; DevArray<uint8_t> rq_ao8;
-    // srt_closest_points: the points, radii and masks of a host call and its (v, w) rows; tri, dist2, point and region go through rq_hit /
-    // rq_t / rq_spoint / rq_occ
-    DevArray<float, 3> rq_points; DevArray<float> rq_radius; DevArray<uint32_t> rq_pmask; DevArray<float, 2> rq_vw;
+    // srt_shade_rays: the query's own light table (a render's d_lights may be in use on another stream): the pinned copy, the event behind
+    // its last upload, the stream that upload went to, and whether it is known to have arrived
     DevArray<float, 3> d_qlights; Pinned<float, 3> h_qlights; uint32_t qlights_valid = 0;
     Event qlights_sent; hipStream_t qlights_stream = nullptr; bool qlights_settled = true;
     int n_cu = 256;
@@ -2086,64 +2071,64 @@ static int render_ao_device_impl(srt_scene* s, const srt_params* p, const QueryH
 }
 
 // The host entry points: what the caller brings goes through the pinned staging block (stage_acquire, as every update does) into the
-// handle's own buffers on the scene's stream, the device entry point runs behind it, the call waits and copies the results out.
-// One array of a host call that comes from host memory: `bytes` from src to dst on the device.  src NULL, or no bytes: absent, and it
-// costs nothing.
-struct Staged { const void* src; size_t bytes; void* dst; };
-// Each item that is there gets a 256-byte aligned piece of the block, is copied into it and sent on from it
-static int stage_rays(srt_scene* s, const Staged* items, size_t n_items, hipStream_t st) {
-    size_t total = 0;
-    for (size_t i = 0; i < n_items; i++)
-        if (items[i].src) total += (items[i].bytes + 255) & ~(size_t)255;
-    char* h = nullptr;
-    SRT_TRY(stage_acquire(s, total, &h));
-    for (size_t i = 0; i < n_items; i++) {
-        const Staged& it = items[i];
-        if (!it.src || !it.bytes) continue;
-        std::memcpy(h, it.src, it.bytes);
-        HIP_TRY(hipMemcpyAsync(it.dst, h, it.bytes, hipMemcpyHostToDevice, st));
-        h += (it.bytes + 255) & ~(size_t)255;
-    }
-    HIP_TRY(hipEventRecord(s->staged, st));
-    return SRT_OK;
-}
-
+// handle's query block on the scene's stream, the device entry point runs behind it, the call waits and copies the results out.
 extern "C++" {      // (templates, down to the entry points)
-// One array of a host query and the handle's buffer for it, `count` units long: a result the caller wants at `out` (null: not wanted), or
-// what the call brings with it at `in` (null: not brought) -- the rays (srt_render_paths brings none: a frame's rays are made on the
-// device), their t intervals, the skipped objects of srt_occluded, the hits of srt_surface_hits, the per-ray masks of the masked calls,
-// the reflectance and refraction tables of the path calls.
-template <typename T, size_t K>
+// One array of a host query, `count` elements of T: a result the caller wants at `out` (null: not wanted), or what the call brings with
+// it at `in` (null: not brought) -- the rays (srt_render_paths brings none: a frame's rays are made on the device), their t intervals,
+// the skipped objects of srt_occluded, the hits of srt_surface_hits, the per-ray masks of the masked calls, the tables of the path and
+// AO calls.  dev: its piece of the query block, which the round trip sets; an absent array takes no space and keeps NULL, which the
+// device entry points and the kernels read as "not wanted" or "not brought".
+template <typename T>
 struct QueryArray {
-    const void* in; T* out; DevArray<T, K>& dev;
-    size_t count;
-    static constexpr size_t unit = K * sizeof(T);                          // bytes per unit
+    const T* in; T* out; size_t count;
+    T* dev = nullptr;
     bool present() const { return in || out; }
-    T* on_device() const { return present() ? dev.p : nullptr; }           // (after the round trip has grown it)
-    Staged staged() const { return Staged{ in, count * unit, dev.p }; }
+    size_t bytes() const { return count * sizeof(T); }
+    size_t piece() const { return present() ? (bytes() + 255) & ~(size_t)255 : 0; }      // what it takes of the block
+    T* on_device() const { return dev; }                                                 // (inside the round trip's launch)
 };
-template <typename T, size_t K>
-static QueryArray<T, K> query_out(T* host, DevArray<T, K>& dev, size_t count) { return QueryArray<T, K>{ nullptr, host, dev, count }; }
-template <typename T, size_t K>
-static QueryArray<T, K> query_in(const void* host, DevArray<T, K>& dev, size_t count) { return QueryArray<T, K>{ host, nullptr, dev, count }; }
+template <typename T>
+static QueryArray<T> query_out(T* host, size_t count) { return QueryArray<T>{ nullptr, host, count }; }
+template <typename T>
+static QueryArray<T> query_in(const T* host, size_t count) { return QueryArray<T>{ host, nullptr, count }; }
 
-// The round trip of a host query on the scene's own stream: grow the buffers of the arrays that are there, stage the ones the call
-// brings, launch(stream) -- the device entry point --, wait, copy each wanted result out.
+// The round trip of a host query on the scene's own stream: lay the arrays that are there out in the query block, stage the ones the
+// call brings, launch(stream) -- the device entry point --, wait, copy each wanted result out.  The layout: every piece starts on a
+// multiple of 256 bytes, as a hipMalloc block does (rays_wide and query_range choose the 8-byte loads by the pointer), and what the call
+// brings comes first, so that the same offsets serve the pinned block, which holds those alone.
+// preload: the frame is a tile deal, whose padding pixels no kernel writes: the caller's arrays go to the device first, so that the copy
+// out returns their padding as it was.  hipMemcpy from pageable memory returns when the data is on the device, so the launch enqueued on
+// the stream behind it is ordered behind these copies without an event.  It costs a second transfer of the size of the result (a tile
+// deal in the host form is the rare case; a row-wise copy out of the live columns would save it).
 template <typename Launch, typename... A>
-static int query_round_trip(srt_scene* s, Launch launch, const A&... arrays) {
+static int query_round_trip(srt_scene* s, bool preload, Launch launch, A&... arrays) {
     HIP_TRY(hipSetDevice(s->device));
     hipStream_t st;
     SRT_TRY(own_stream(s, &st));
-    int rc = SRT_OK;
-    ((rc = (rc == SRT_OK && arrays.present()) ? grow(s, arrays.count, arrays.dev) : rc), ...);
-    SRT_TRY(rc);
-    const Staged items[] = { arrays.staged()... };
-    SRT_TRY(stage_rays(s, items, sizeof...(arrays), st));
+    size_t at_in = 0, at_out = ((arrays.in ? arrays.piece() : 0) + ... + 0);
+    SRT_TRY(grow(s, at_out + ((arrays.out ? arrays.piece() : 0) + ... + 0), s->query_block));
+    char* h = nullptr;
+    SRT_TRY(stage_acquire(s, at_out, &h));
+    hipError_t e = hipSuccess;
+    const auto place = [&](auto& a) {      // its piece; an array the call brings goes into the pinned block and is sent on from it
+        if (!a.present()) return;
+        size_t& at = a.in ? at_in : at_out;
+        a.dev = reinterpret_cast<decltype(a.dev)>(s->query_block.p + at);
+        if (a.in && a.bytes() && e == hipSuccess) {
+            std::memcpy(h + at, a.in, a.bytes());
+            e = hipMemcpyAsync(a.dev, h + at, a.bytes(), hipMemcpyHostToDevice, st);
+        }
+        at += a.piece();
+    };
+    (place(arrays), ...);
+    HIP_TRY(e);
+    HIP_TRY(hipEventRecord(s->staged, st));
+    if (preload) ((e = (e == hipSuccess && arrays.out) ? hipMemcpy(arrays.dev, arrays.out, arrays.bytes(), hipMemcpyHostToDevice) : e), ...);
+    HIP_TRY(e);
     SRT_TRY(launch(st));
     HIP_TRY(hipStreamSynchronize(st));
     if (s->qlights_stream == st) s->qlights_settled = true;      // a light table sent on this stream has arrived
-    hipError_t e = hipSuccess;
-    ((e = (e == hipSuccess && arrays.out) ? hipMemcpy(arrays.out, arrays.dev.p, arrays.count * arrays.unit, hipMemcpyDeviceToHost) : e), ...);
+    ((e = (e == hipSuccess && arrays.out) ? hipMemcpy(arrays.out, arrays.dev, arrays.bytes(), hipMemcpyDeviceToHost) : e), ...);
     HIP_TRY(e);
     return SRT_OK;
 }
@@ -2160,22 +2145,16 @@ static int query_stats(srt_scene* s, uint32_t n, uint32_t n_lights, srt_stats* s
     return SRT_OK;
 }
 
-// The per-ray masks of a masked host call: n words that go through the pinned block into rq_tin, the buffer of 32-bit units that neither
-// masked call uses for a t of its own; on the device they are read as the words they are.
-static inline RayMask staged_mask(const srt_scene* s, const RayMask& mask) {
-    return RayMask{ mask.masked, mask.words ? reinterpret_cast<const uint32_t*>(s->rq_tin.p) : nullptr };
-}
-
 static int trace_rays_impl(srt_scene* s, uint32_t n, const float* rays, const float* t_range, uint32_t flags, int32_t* hit_id, float* t, float* bary,
                            srt_stats* stats, const RayMask& mask) {
     SRT_TRY(check_query(s, n, rays, flags));
     if (stats) std::memset(stats, 0, sizeof(*stats));
     if (!n) return SRT_OK;
-    const auto o_hit = query_out(hit_id, s->rq_hit, n); const auto o_t = query_out(t, s->rq_t, n); const auto o_bary = query_out(bary, s->rq_bary, n);
-    const auto i_rays = query_in(rays, s->rq_rays, n); const auto i_range = query_in(t_range, s->rq_range, n); const auto i_mask = query_in(mask.words, s->rq_tin, n);
-    SRT_TRY(query_round_trip(s, [&](hipStream_t st) {
+    auto o_hit = query_out(hit_id, n); auto o_t = query_out(t, n); auto o_bary = query_out(bary, 3ull * n);
+    auto i_rays = query_in(rays, 6ull * n); auto i_range = query_in(t_range, 2ull * n); auto i_mask = query_in(mask.words, n);
+    SRT_TRY(query_round_trip(s, false, [&](hipStream_t st) {
         return trace_rays_device_impl(s, n, i_rays.on_device(), i_range.on_device(), flags, st, o_hit.on_device(), o_t.on_device(), o_bary.on_device(), true,
-                                      staged_mask(s, mask));
+                                      RayMask{ mask.masked, i_mask.on_device() });
     }, o_hit, o_t, o_bary, i_rays, i_range, i_mask));
     return stats ? query_stats(s, n, 0, stats) : SRT_OK;
 }
@@ -2186,10 +2165,10 @@ static int closest_points_impl(srt_scene* s, uint32_t n, const float* points, co
     if (!out) return SRT_ERR_ARG;
     if (stats) std::memset(stats, 0, sizeof(*stats));
     if (!n) return SRT_OK;
-    const auto o_tri = query_out(out->tri, s->rq_hit, n); const auto o_d2 = query_out(out->dist2, s->rq_t, n); const auto o_pt = query_out(out->point, s->rq_spoint, n);
-    const auto o_vw = query_out(out->vw, s->rq_vw, n); const auto o_reg = query_out(out->region, s->rq_occ, n);
-    const auto i_pts = query_in(points, s->rq_points, n); const auto i_rad = query_in(radius, s->rq_radius, n); const auto i_mask = query_in(point_mask, s->rq_pmask, n);
-    SRT_TRY(query_round_trip(s, [&](hipStream_t st) {
+    auto o_tri = query_out(out->tri, n); auto o_d2 = query_out(out->dist2, n); auto o_pt = query_out(out->point, 3ull * n);
+    auto o_vw = query_out(out->vw, 2ull * n); auto o_reg = query_out(out->region, n);
+    auto i_pts = query_in(points, 3ull * n); auto i_rad = query_in(radius, n); auto i_mask = query_in(point_mask, n);
+    SRT_TRY(query_round_trip(s, false, [&](hipStream_t st) {
         const srt_point_out dev = { o_tri.on_device(), o_d2.on_device(), o_pt.on_device(), o_vw.on_device(), o_reg.on_device() };
         return closest_points_device_impl(s, n, i_pts.on_device(), i_rad.on_device(), i_mask.on_device(), flags, st, &dev, stats != nullptr);
     }, o_tri, o_d2, o_pt, o_vw, o_reg, i_pts, i_rad, i_mask));
@@ -2201,11 +2180,10 @@ static int trace_rays_multi_impl(srt_scene* s, uint32_t n, const float* rays, co
     SRT_TRY(check_multi(s, n, rays, k, flags));
     if (stats) std::memset(stats, 0, sizeof(*stats));
     if (!n) return SRT_OK;
-    const size_t rows = (size_t)n * k;      // the n x k rows: k units a ray
-    const auto o_n = query_out(n_hits, s->rq_nhits, n); const auto o_hit = query_out(hit_id, s->rq_hit, rows);
-    const auto o_t = query_out(t, s->rq_t, rows); const auto o_bary = query_out(bary, s->rq_bary, rows);
-    const auto i_rays = query_in(rays, s->rq_rays, n); const auto i_range = query_in(t_range, s->rq_range, n);
-    SRT_TRY(query_round_trip(s, [&](hipStream_t st) {
+    const size_t rows = (size_t)n * k;      // the n x k rows
+    auto o_n = query_out(n_hits, n); auto o_hit = query_out(hit_id, rows); auto o_t = query_out(t, rows); auto o_bary = query_out(bary, 3 * rows);
+    auto i_rays = query_in(rays, 6ull * n); auto i_range = query_in(t_range, 2ull * n);
+    SRT_TRY(query_round_trip(s, false, [&](hipStream_t st) {
         return trace_rays_multi_device_impl(s, n, i_rays.on_device(), i_range.on_device(), k, flags, st, o_n.on_device(), o_hit.on_device(), o_t.on_device(),
                                             o_bary.on_device(), true);
     }, o_n, o_hit, o_t, o_bary, i_rays, i_range));
@@ -2215,11 +2193,10 @@ static int trace_rays_multi_impl(srt_scene* s, uint32_t n, const float* rays, co
 static int occluded_impl(srt_scene* s, uint32_t n, const float* rays, const float* t_range, const int32_t* skip_obj, uint8_t* occluded, const RayMask& mask) {
     SRT_TRY(check_query(s, n, rays, 0));
     if (!n || !occluded) return SRT_OK;
-    const auto o_occ = query_out(occluded, s->rq_occ, n);
-    const auto i_rays = query_in(rays, s->rq_rays, n); const auto i_skip = query_in(skip_obj, s->rq_skip, n); const auto i_range = query_in(t_range, s->rq_range, n);
-    const auto i_mask = query_in(mask.words, s->rq_tin, n);
-    return query_round_trip(s, [&](hipStream_t st) {
-        return occluded_device_impl(s, n, i_rays.on_device(), i_range.on_device(), i_skip.on_device(), st, o_occ.on_device(), staged_mask(s, mask));
+    auto o_occ = query_out(occluded, n);
+    auto i_rays = query_in(rays, 6ull * n); auto i_skip = query_in(skip_obj, n); auto i_range = query_in(t_range, 2ull * n); auto i_mask = query_in(mask.words, n);
+    return query_round_trip(s, false, [&](hipStream_t st) {
+        return occluded_device_impl(s, n, i_rays.on_device(), i_range.on_device(), i_skip.on_device(), st, o_occ.on_device(), RayMask{ mask.masked, i_mask.on_device() });
     }, o_occ, i_rays, i_skip, i_range, i_mask);
 }
 
@@ -2228,27 +2205,26 @@ static int shade_rays_impl(srt_scene* s, uint32_t n, const float* rays, const fl
     SRT_TRY(check_shade(s, n, rays, p));
     if (stats) std::memset(stats, 0, sizeof(*stats));
     if (!n) return SRT_OK;
-    const auto o_hit = query_out(hit_id, s->rq_hit, n); const auto o_t = query_out(t, s->rq_t, n);
-    const auto o_lin = query_out(rgb_linear, s->rq_lin, n); const auto o_rgb8 = query_out(rgb8, s->rq_rgb8, n);
-    const auto i_rays = query_in(rays, s->rq_rays, n); const auto i_range = query_in(t_range, s->rq_range, n);
-    SRT_TRY(query_round_trip(s, [&](hipStream_t st) {
+    auto o_hit = query_out(hit_id, n); auto o_t = query_out(t, n); auto o_lin = query_out(rgb_linear, 3ull * n); auto o_rgb8 = query_out(rgb8, 3ull * n);
+    auto i_rays = query_in(rays, 6ull * n); auto i_range = query_in(t_range, 2ull * n);
+    SRT_TRY(query_round_trip(s, false, [&](hipStream_t st) {
         return shade_rays_device_impl(s, n, i_rays.on_device(), i_range.on_device(), p, st, o_hit.on_device(), o_t.on_device(), o_lin.on_device(), o_rgb8.on_device(), true);
     }, o_hit, o_t, o_lin, o_rgb8, i_rays, i_range));
     return stats ? query_stats(s, n, p->n_lights, stats) : SRT_OK;
 }
 
 // What the host forms of the two path calls share: the seven results of n rays or pixels and the four of the side rays (the per-segment rows
-// are depth units each), the reflectance, refraction and Fresnel tables (n_objects floats each, where the call brings them; the side
+// are depth x n rows each), the reflectance, refraction and Fresnel tables (n_objects floats each, where the call brings them; the side
 // rays' rows and f0 only where the call splits, PathOptions::f0), and the round trip of all of them, in which
-// launch(stream, path, options, segments) gets the caller's structs with the handle's buffers in the place of the host arrays.
+// launch(stream, path, options, segments) gets the caller's structs with the pieces of the query block in the place of the host arrays.
 struct PathArrays {
-    QueryArray<float, 3> lin; QueryArray<uint8_t, 3> rgb8;
-    QueryArray<int32_t, 1> hit; QueryArray<float, 1> t; QueryArray<int32_t, 1> obj; QueryArray<float, 3> seg_lin; QueryArray<float, 6> rays;
-    QueryArray<float, 1> refl, ior, f0;
-    QueryArray<int32_t, 1> side_hit; QueryArray<float, 1> side_t; QueryArray<float, 3> side_lin; QueryArray<float, 1> side_F;
-    template <typename Launch, typename... In>      // in: what else the call brings
-    int round_trip(srt_scene* s, const srt_path_desc* path, const PathOptions& opt, Launch launch, const In&... in) const {
-        return query_round_trip(s, [&](hipStream_t st) -> int {
+    QueryArray<float> lin; QueryArray<uint8_t> rgb8;
+    QueryArray<int32_t> hit; QueryArray<float> t; QueryArray<int32_t> obj; QueryArray<float> seg_lin, rays;
+    QueryArray<float> refl, ior, f0;
+    QueryArray<int32_t> side_hit; QueryArray<float> side_t, side_lin, side_F;
+    template <typename Launch, typename... In>      // in: what else the call brings; preload: query_round_trip's
+    int round_trip(srt_scene* s, bool preload, const srt_path_desc* path, const PathOptions& opt, Launch launch, In&... in) {
+        return query_round_trip(s, preload, [&](hipStream_t st) -> int {
             const srt_path_desc dpath = { path->depth, path->bounce_t_min, refl.on_device() };
             const srt_refraction drefr = { ior.on_device(), 0u };
             const srt_path_out dseg = { hit.on_device(), t.on_device(), obj.on_device(), seg_lin.on_device(), rays.on_device() };
@@ -2258,14 +2234,13 @@ struct PathArrays {
         }, lin, rgb8, hit, t, obj, seg_lin, rays, side_hit, side_t, side_lin, side_F, in..., refl, ior, f0);
     }
 };
-static PathArrays path_arrays(srt_scene* s, uint32_t n, const srt_path_desc* path, const PathOptions& opt, float* rgb_linear, uint8_t* rgb8, const srt_path_out* seg) {
+static PathArrays path_arrays(const srt_scene* s, uint32_t n, const srt_path_desc* path, const PathOptions& opt, float* rgb_linear, uint8_t* rgb8, const srt_path_out* seg) {
     const srt_path_out h = seg ? *seg : srt_path_out{};
     const srt_fresnel_out f = opt.side_rows() ? *opt.side_rows() : srt_fresnel_out{};
     const size_t rows = (size_t)path->depth * n, nO = s->dev.n_objects;
-    return PathArrays{ query_out(rgb_linear, s->rq_lin, n), query_out(rgb8, s->rq_rgb8, n), query_out(h.hit_id, s->rq_hit, rows), query_out(h.t, s->rq_t, rows),
-                       query_out(h.obj, s->rq_sobj, rows), query_out(h.rgb_linear, s->rq_plin, rows), query_out(h.rays, s->rq_sbounce, rows),
-                       query_in(path->reflectance, s->rq_refl, nO), query_in(opt.ior(), s->rq_ior, nO), query_in(opt.f0(), s->rq_f0, nO),
-                       query_out(f.hit_id, s->rq_fhit, rows), query_out(f.t, s->rq_ft, rows), query_out(f.rgb_linear, s->rq_flin, rows), query_out(f.fresnel, s->rq_fres, rows) };
+    return PathArrays{ query_out(rgb_linear, 3ull * n), query_out(rgb8, 3ull * n), query_out(h.hit_id, rows), query_out(h.t, rows), query_out(h.obj, rows),
+                       query_out(h.rgb_linear, 3 * rows), query_out(h.rays, 6 * rows), query_in(path->reflectance, nO), query_in(opt.ior(), nO), query_in(opt.f0(), nO),
+                       query_out(f.hit_id, rows), query_out(f.t, rows), query_out(f.rgb_linear, 3 * rows), query_out(f.fresnel, rows) };
 }
 
 // srt_shade_paths: hit_rays counts the hits of all segments, hence the shadow rays
@@ -2275,9 +2250,9 @@ static int shade_paths_impl(srt_scene* s, uint32_t n, const float* rays, const f
     SRT_TRY(check_paths(s, n, rays, p, path));
     if (stats) std::memset(stats, 0, sizeof(*stats));
     if (!n || (!stats && !paths_wanted(rgb_linear, rgb8, seg) && !fresnel_wanted(opt.side_rows()))) return SRT_OK;
-    const PathArrays a = path_arrays(s, n, path, opt, rgb_linear, rgb8, seg);
-    const auto i_rays = query_in(rays, s->rq_rays, n); const auto i_range = query_in(t_range, s->rq_range, n);
-    SRT_TRY(a.round_trip(s, path, opt, [&](hipStream_t st, const srt_path_desc* dpath, const PathOptions& dopt, const srt_path_out* dseg) {
+    PathArrays a = path_arrays(s, n, path, opt, rgb_linear, rgb8, seg);
+    auto i_rays = query_in(rays, 6ull * n); auto i_range = query_in(t_range, 2ull * n);
+    SRT_TRY(a.round_trip(s, false, path, opt, [&](hipStream_t st, const srt_path_desc* dpath, const PathOptions& dopt, const srt_path_out* dseg) {
         return shade_paths_device_impl(s, n, i_rays.on_device(), i_range.on_device(), p, dpath, dopt, st, a.lin.on_device(), a.rgb8.on_device(), dseg, stats != nullptr);
     }, i_rays, i_range));
     return stats ? query_stats(s, n, p->n_lights, stats) : SRT_OK;
@@ -2291,19 +2266,9 @@ static int render_paths_impl(srt_scene* s, const srt_params* p, const srt_path_d
     if (stats) std::memset(stats, 0, sizeof(*stats));
     const uint32_t n = srt_rows_owned(p) * srt_cols_owned(p);      // (< 2^32: check_render_paths)
     if (!n || (!stats && !paths_wanted(rgb_linear, rgb8, seg) && !fresnel_wanted(opt.side_rows()))) return SRT_OK;
-    const PathArrays a = path_arrays(s, n, path, opt, rgb_linear, rgb8, seg);
-    const bool padded = p->block_cols != 0;      // padding pixels are not written: what the handle's buffers hold there must not reach the caller
-    SRT_TRY(a.round_trip(s, path, opt, [&](hipStream_t st, const srt_path_desc* dpath, const PathOptions& dopt, const srt_path_out* dseg) -> int {
-        if (padded) {
-            // The caller's arrays first, so that the copy out returns their padding as it was.  hipMemcpy from pageable memory returns when
-            // the data is on the device, so the launch enqueued on st below is ordered behind these copies without an event.  It costs a
-            // second transfer of the size of the result (a tile deal in the host form is the rare case; a row-wise copy out of the live
-            // columns would save it).
-            hipError_t e = hipSuccess;
-            const auto up = [&](const auto& arr) { if (arr.out && e == hipSuccess) e = hipMemcpy(arr.dev.p, arr.out, arr.count * arr.unit, hipMemcpyHostToDevice); };
-            up(a.hit); up(a.t); up(a.obj); up(a.seg_lin); up(a.rays); up(a.side_hit); up(a.side_t); up(a.side_lin); up(a.side_F); up(a.lin); up(a.rgb8);
-            HIP_TRY(e);
-        }
+    PathArrays a = path_arrays(s, n, path, opt, rgb_linear, rgb8, seg);
+    // (a tile deal's padding pixels are not written: what the query block holds there must not reach the caller)
+    SRT_TRY(a.round_trip(s, p->block_cols != 0, path, opt, [&](hipStream_t st, const srt_path_desc* dpath, const PathOptions& dopt, const srt_path_out* dseg) {
         return render_paths_device_impl(s, p, dpath, dopt, st, a.lin.on_device(), a.rgb8.on_device(), dseg, stats != nullptr);
     }));
     if (!stats) return SRT_OK;
@@ -2313,21 +2278,21 @@ static int render_paths_impl(srt_scene* s, const srt_params* p, const srt_path_d
 }
 
 // What the host forms of the two surface calls share: the six arrays of the caller's srt_surface_out (host arrays), and the round trip of
-// them, in which launch(stream, out) gets the srt_surface_out that names the handle's buffers for the wanted ones.
+// them, in which launch(stream, out) gets the srt_surface_out that names the pieces of the query block for the wanted ones.
 struct SurfaceArrays {
-    QueryArray<int32_t, 1> obj; QueryArray<float, 3> point, normal, color, material; QueryArray<float, 6> bounce;
+    QueryArray<int32_t> obj; QueryArray<float> point, normal, color, material, bounce;
     template <typename Launch, typename... More>      // more: the call's other arrays
-    int round_trip(srt_scene* s, Launch launch, const More&... more) const {
-        return query_round_trip(s, [&](hipStream_t st) -> int {
+    int round_trip(srt_scene* s, Launch launch, More&... more) {
+        return query_round_trip(s, false, [&](hipStream_t st) -> int {
             const srt_surface_out dev = { obj.on_device(), point.on_device(), normal.on_device(), color.on_device(), material.on_device(), bounce.on_device() };
             return launch(st, &dev);
         }, more..., obj, point, normal, color, material, bounce);
     }
 };
-static SurfaceArrays surface_arrays(srt_scene* s, uint32_t n, const srt_surface_out* out) {
+static SurfaceArrays surface_arrays(uint32_t n, const srt_surface_out* out) {
     const srt_surface_out h = out ? *out : srt_surface_out{};
-    return SurfaceArrays{ query_out(h.obj, s->rq_sobj, n), query_out(h.point, s->rq_spoint, n), query_out(h.normal, s->rq_snormal, n), query_out(h.color, s->rq_scolor, n),
-                          query_out(h.material, s->rq_smat, n), query_out(h.bounce, s->rq_sbounce, n) };
+    return SurfaceArrays{ query_out(h.obj, n), query_out(h.point, 3ull * n), query_out(h.normal, 3ull * n), query_out(h.color, 3ull * n), query_out(h.material, 3ull * n),
+                          query_out(h.bounce, 6ull * n) };
 }
 
 static int surface_rays_impl(srt_scene* s, uint32_t n, const float* rays, const float* t_range, uint32_t flags, int32_t* hit_id, float* t, const srt_surface_out* out,
@@ -2335,21 +2300,20 @@ static int surface_rays_impl(srt_scene* s, uint32_t n, const float* rays, const 
     SRT_TRY(check_surface(s, n, rays, flags, SRT_FLAG_COUNT_WORK | SRT_FLAG_SMOOTH_NORMALS));
     if (stats) std::memset(stats, 0, sizeof(*stats));
     if (!n) return SRT_OK;
-    const SurfaceArrays a = surface_arrays(s, n, out);
-    const auto o_hit = query_out(hit_id, s->rq_hit, n); const auto o_t = query_out(t, s->rq_t, n);
-    const auto i_rays = query_in(rays, s->rq_rays, n); const auto i_range = query_in(t_range, s->rq_range, n);
+    SurfaceArrays a = surface_arrays(n, out);
+    auto o_hit = query_out(hit_id, n); auto o_t = query_out(t, n);
+    auto i_rays = query_in(rays, 6ull * n); auto i_range = query_in(t_range, 2ull * n);
     SRT_TRY(a.round_trip(s, [&](hipStream_t st, const srt_surface_out* dev) {
         return surface_rays_device_impl(s, n, i_rays.on_device(), i_range.on_device(), flags, st, o_hit.on_device(), o_t.on_device(), dev, true);
     }, o_hit, o_t, i_rays, i_range));
     return stats ? query_stats(s, n, 0, stats) : SRT_OK;
 }
 
-// the hits a caller brings: their ids go through rq_skip, their t through rq_tin
 static int surface_hits_impl(srt_scene* s, uint32_t n, const float* rays, const int32_t* hit_id, const float* t, uint32_t flags, const srt_surface_out* out) {
     SRT_TRY(check_surface_hits(s, n, rays, hit_id, t, flags));
     if (!n || !surface_wanted(out)) return SRT_OK;
-    const SurfaceArrays a = surface_arrays(s, n, out);
-    const auto i_rays = query_in(rays, s->rq_rays, n); const auto i_hit = query_in(hit_id, s->rq_skip, n); const auto i_t = query_in(t, s->rq_tin, n);
+    SurfaceArrays a = surface_arrays(n, out);
+    auto i_rays = query_in(rays, 6ull * n); auto i_hit = query_in(hit_id, n); auto i_t = query_in(t, n);
     return a.round_trip(s, [&](hipStream_t st, const srt_surface_out* dev) {
         return surface_hits_device_impl(s, n, i_rays.on_device(), i_hit.on_device(), i_t.on_device(), flags, st, dev);
     }, i_rays, i_hit, i_t);
@@ -2357,14 +2321,14 @@ static int surface_hits_impl(srt_scene* s, uint32_t n, const float* rays, const 
 
 // What the host forms of the four AO calls share: the direction table the call brings, the rotation table of a frame call, the arrays of
 // the caller's srt_ao_out or srt_ao_frame_out (whose first three fields are srt_ao_out's), and the round trip of them, in which
-// launch(stream, ao, frame, out) gets the caller's structs with the handle's buffers in the place of the host arrays.
+// launch(stream, ao, frame, out) gets the caller's structs with the pieces of the query block in the place of the host arrays.
 struct AoArrays {
-    QueryArray<float, 3> dirs; QueryArray<uint32_t, 1> cnt; QueryArray<float, 1> val; QueryArray<uint32_t, 1> bits;
-    QueryArray<float, 2> rot; QueryArray<float, 3> bent; QueryArray<uint8_t, 1> ao8;
+    QueryArray<float> dirs; QueryArray<uint32_t> cnt; QueryArray<float> val; QueryArray<uint32_t> bits;
+    QueryArray<float> rot, bent; QueryArray<uint8_t> ao8;
     uint32_t rot_w, rot_h;
-    template <typename Launch, typename... More>      // more: the call's other arrays
-    int round_trip(srt_scene* s, const srt_ao_desc* ao, Launch launch, const More&... more) const {
-        return query_round_trip(s, [&](hipStream_t st) -> int {
+    template <typename Launch, typename... More>      // more: the call's other arrays; preload: query_round_trip's
+    int round_trip(srt_scene* s, bool preload, const srt_ao_desc* ao, Launch launch, More&... more) {
+        return query_round_trip(s, preload, [&](hipStream_t st) -> int {
             const srt_ao_desc dao = { ao->n_dirs, dirs.on_device(), ao->t_min, ao->t_max, ao->flags };
             const srt_ao_frame dfr = { rot_w, rot_h, rot.on_device() };
             const srt_ao_frame_out dev = { cnt.on_device(), val.on_device(), bits.on_device(), bent.on_device(), ao8.on_device() };
@@ -2373,26 +2337,26 @@ struct AoArrays {
     }
 };
 // n rays or local pixels; fr: the rotation table of a frame call, or NULL
-static AoArrays ao_arrays(srt_scene* s, size_t n, const srt_ao_desc* ao, const srt_ao_frame* fr, const srt_ao_frame_out& h) {
+static AoArrays ao_arrays(size_t n, const srt_ao_desc* ao, const srt_ao_frame* fr, const srt_ao_frame_out& h) {
     const size_t words = n * ((ao->n_dirs + 31u) / 32u);
     const bool rotated = fr && fr->rot;
-    return AoArrays{ query_in(ao->dirs, s->rq_aodirs, ao->n_dirs), query_out(h.n_occluded, s->rq_aocnt, n), query_out(h.ao, s->rq_aoval, n),
-                     query_out(h.occ_bits, s->rq_aobits, words), query_in(rotated ? fr->rot : nullptr, s->rq_aorot, rotated ? (size_t)fr->rot_w * fr->rot_h : 0),
-                     query_out(h.bent, s->rq_aobent, n), query_out(h.ao8, s->rq_ao8, n), rotated ? fr->rot_w : 0u, rotated ? fr->rot_h : 0u };
+    return AoArrays{ query_in(ao->dirs, 3ull * ao->n_dirs), query_out(h.n_occluded, n), query_out(h.ao, n), query_out(h.occ_bits, words),
+                     query_in(rotated ? fr->rot : nullptr, rotated ? 2ull * fr->rot_w * fr->rot_h : 0), query_out(h.bent, 3 * n), query_out(h.ao8, n),
+                     rotated ? fr->rot_w : 0u, rotated ? fr->rot_h : 0u };
 }
 
-// hits: the hits a caller of srt_ao_hits brings (their ids go through rq_skip, their t through rq_tin), or NULL: srt_ao_rays
+// hits: the hits a caller of srt_ao_hits brings, or NULL: srt_ao_rays
 static int ao_impl(srt_scene* s, uint32_t n, const float* rays, const float* t_range, const QueryHits* hits, uint32_t flags, const srt_ao_desc* ao,
                    const srt_visibility* vis, int32_t* hit_id, float* t, const srt_ao_out* out, srt_stats* stats) {
     SRT_TRY(check_ao(s, n, rays, hits, flags, ao));
     if (stats) std::memset(stats, 0, sizeof(*stats));
     if (!n || (hits && !stats && !ao_wanted(out))) return SRT_OK;
     const srt_ao_out h = out ? *out : srt_ao_out{};
-    const AoArrays a = ao_arrays(s, n, ao, nullptr, srt_ao_frame_out{ h.n_occluded, h.ao, h.occ_bits, nullptr, nullptr });
-    const auto o_hit = query_out(hit_id, s->rq_hit, n); const auto o_t = query_out(t, s->rq_t, n);
-    const auto i_rays = query_in(rays, s->rq_rays, n); const auto i_range = query_in(t_range, s->rq_range, n);
-    const auto i_hit = query_in(hits ? hits->hit_id : nullptr, s->rq_skip, n); const auto i_t = query_in(hits ? hits->t : nullptr, s->rq_tin, n);
-    SRT_TRY(a.round_trip(s, ao, [&](hipStream_t st, const srt_ao_desc* dao, const srt_ao_frame*, const srt_ao_frame_out* dev) {
+    AoArrays a = ao_arrays(n, ao, nullptr, srt_ao_frame_out{ h.n_occluded, h.ao, h.occ_bits, nullptr, nullptr });
+    auto o_hit = query_out(hit_id, n); auto o_t = query_out(t, n);
+    auto i_rays = query_in(rays, 6ull * n); auto i_range = query_in(t_range, 2ull * n);
+    auto i_hit = query_in(hits ? hits->hit_id : nullptr, n); auto i_t = query_in(hits ? hits->t : nullptr, n);
+    SRT_TRY(a.round_trip(s, false, ao, [&](hipStream_t st, const srt_ao_desc* dao, const srt_ao_frame*, const srt_ao_frame_out* dev) {
         const QueryHits dh = { i_hit.on_device(), i_t.on_device() };
         const srt_ao_out dout = { dev->n_occluded, dev->ao, dev->occ_bits };
         return ao_device_impl(s, n, i_rays.on_device(), i_range.on_device(), hits ? &dh : nullptr, flags, dao, vis, st, o_hit.on_device(), o_t.on_device(), &dout,
@@ -2401,8 +2365,8 @@ static int ao_impl(srt_scene* s, uint32_t n, const float* rays, const float* t_r
     return stats ? query_stats(s, n, ao_wanted(out) ? ao->n_dirs : 0u, stats) : SRT_OK;      // (nothing wanted: no AO ray was walked)
 }
 
-// srt_render_ao / srt_render_ao_hits: as ao_impl, with n the call's local pixels and no rays to stage; the hits a caller of
-// srt_render_ao_hits brings go through rq_skip / rq_tin; primary_rays counts image pixels x the sub-samples walked
+// srt_render_ao / srt_render_ao_hits: as ao_impl, with n the call's local pixels and no rays to stage; primary_rays counts image pixels x
+// the sub-samples walked
 static int render_ao_impl(srt_scene* s, const srt_params* p, const QueryHits* hits, uint32_t flags, const srt_ao_desc* ao, const srt_ao_frame* fr,
                           const srt_visibility* vis, int32_t* hit_id, float* t, const srt_ao_frame_out* out, srt_stats* stats) {
     SRT_TRY(check_render_ao(s, p, hits, flags, ao, fr));
@@ -2410,17 +2374,11 @@ static int render_ao_impl(srt_scene* s, const srt_params* p, const QueryHits* hi
     const uint32_t n = srt_rows_owned(p) * srt_cols_owned(p);      // (< 2^32: check_render_ao)
     const bool wanted = ao_frame_wanted(out);
     if (!n || (!stats && !wanted && (hits || (!hit_id && !t)))) return SRT_OK;
-    const AoArrays a = ao_arrays(s, n, ao, fr, out ? *out : srt_ao_frame_out{});
-    const auto o_hit = query_out(hit_id, s->rq_hit, n); const auto o_t = query_out(t, s->rq_t, n);
-    const auto i_hit = query_in(hits ? hits->hit_id : nullptr, s->rq_skip, n); const auto i_t = query_in(hits ? hits->t : nullptr, s->rq_tin, n);
-    const bool padded = p->block_cols != 0;      // padding pixels are not written: what the handle's buffers hold there must not reach the caller
-    SRT_TRY(a.round_trip(s, ao, [&](hipStream_t st, const srt_ao_desc* dao, const srt_ao_frame* dfr, const srt_ao_frame_out* dev) -> int {
-        if (padded) {      // the caller's arrays first, so that the copy out returns their padding as it was (render_paths_impl has the reasoning)
-            hipError_t e = hipSuccess;
-            const auto up = [&](const auto& arr) { if (arr.out && e == hipSuccess) e = hipMemcpy(arr.dev.p, arr.out, arr.count * arr.unit, hipMemcpyHostToDevice); };
-            up(o_hit); up(o_t); up(a.cnt); up(a.val); up(a.bits); up(a.bent); up(a.ao8);
-            HIP_TRY(e);
-        }
+    AoArrays a = ao_arrays(n, ao, fr, out ? *out : srt_ao_frame_out{});
+    auto o_hit = query_out(hit_id, n); auto o_t = query_out(t, n);
+    auto i_hit = query_in(hits ? hits->hit_id : nullptr, n); auto i_t = query_in(hits ? hits->t : nullptr, n);
+    // (a tile deal's padding pixels are not written: what the query block holds there must not reach the caller)
+    SRT_TRY(a.round_trip(s, p->block_cols != 0, ao, [&](hipStream_t st, const srt_ao_desc* dao, const srt_ao_frame* dfr, const srt_ao_frame_out* dev) {
         const QueryHits dh = { i_hit.on_device(), i_t.on_device() };
         return render_ao_device_impl(s, p, hits ? &dh : nullptr, flags, dao, fr ? dfr : nullptr, vis, st, o_hit.on_device(), o_t.on_device(), dev, stats != nullptr);
     }, o_hit, o_t, i_hit, i_t));
