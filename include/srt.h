@@ -1131,4 +1131,5 @@ uint32_t    srt_abi_version(void);
 /* Closest-point queries, the nearest triangle within a radius per point, are declared in their own header, which this one brings along:
  * include/srt_points.h states their definition.  SRT_ABI_VERSION is unchanged by them. */
 #include "srt_points.h"
+#include "srt_nearest.h"      /* the same query with a bound that shrinks: no radius to choose */
 #endif /* SRT_H */

@@ -333,6 +333,13 @@ POINT_PROTOTYPES = {
     "srt_closest_points": (_int, [_vp, _u32, _f32p, _f32p, _u32p, _u32, _pout, _stats]),
 }
 
+# ---- the prototypes of include/srt_nearest.h, in its order, under the same rules; SRT_NEAREST_K is the header's margin constant ----
+NEAREST_K = 64      # SRT_NEAREST_K
+NEAREST_PROTOTYPES = {
+    "srt_nearest_points_device": POINT_PROTOTYPES["srt_closest_points_device"],
+    "srt_nearest_points": POINT_PROTOTYPES["srt_closest_points"],
+}
+
 
 def _ptr(a, ty):
     return a.ctypes.data_as(ty) if a is not None else ty()

@@ -1821,8 +1821,9 @@ static int occluded_device_impl(srt_scene* s, uint32_t n, const float* d_rays, c
 // MASK build; one without launches the build that reads neither the array nor the scene's table.
 // count_hits: the host entry point wants hit_rays also without SRT_FLAG_COUNT_WORK
 static inline bool points_wanted(const srt_point_out* o) { return o->tri || o->dist2 || o->point || o->vw || o->region; }
+// nearest: srt_nearest_points (include/srt_nearest.h) -- the same call with k_query_nearest, whose bound shrinks
 static int closest_points_device_impl(srt_scene* s, uint32_t n, const float* d_points, const float* d_radius, const uint32_t* d_point_mask, uint32_t flags,
-                                      hipStream_t stream, const srt_point_out* out, bool count_hits) {
+                                      hipStream_t stream, const srt_point_out* out, bool count_hits, bool nearest = false) {
     SRT_TRY(check_query(s, n, d_points, flags));
     if (!out) return SRT_ERR_ARG;
     if (!n || (!count_hits && !points_wanted(out))) return SRT_OK;
@@ -1830,7 +1831,8 @@ static int closest_points_device_impl(srt_scene* s, uint32_t n, const float* d_p
     QueryLaunch q;
     SRT_TRY(query_prologue(s, n, stream, nullptr, count || count_hits, &q));
     static const std::array builds = { BUILDS_2(k_query_points) };
-    return launch_query(builds[build_index(count, d_point_mask)], q.grid, q.stream, s->dev, n, d_points, d_radius, *out, q.ctr, query_mask(s, d_point_mask));
+    static const std::array shrinking = { BUILDS_2(k_query_nearest) };
+    return launch_query((nearest ? shrinking : builds)[build_index(count, d_point_mask)], q.grid, q.stream, s->dev, n, d_points, d_radius, *out, q.ctr, query_mask(s, d_point_mask));
 }
 
 // What a shading kernel takes of the params (after query_prologue: the light table is the handle's device copy)
@@ -2160,7 +2162,7 @@ static int trace_rays_impl(srt_scene* s, uint32_t n, const float* rays, const fl
 }
 
 static int closest_points_impl(srt_scene* s, uint32_t n, const float* points, const float* radius, const uint32_t* point_mask, uint32_t flags,
-                               const srt_point_out* out, srt_stats* stats) {
+                               const srt_point_out* out, srt_stats* stats, bool nearest = false) {
     SRT_TRY(check_query(s, n, points, flags));
     if (!out) return SRT_ERR_ARG;
     if (stats) std::memset(stats, 0, sizeof(*stats));
@@ -2170,7 +2172,7 @@ static int closest_points_impl(srt_scene* s, uint32_t n, const float* points, co
     auto i_pts = query_in(points, 3ull * n); auto i_rad = query_in(radius, n); auto i_mask = query_in(point_mask, n);
     SRT_TRY(query_round_trip(s, false, [&](hipStream_t st) {
         const srt_point_out dev = { o_tri.on_device(), o_d2.on_device(), o_pt.on_device(), o_vw.on_device(), o_reg.on_device() };
-        return closest_points_device_impl(s, n, i_pts.on_device(), i_rad.on_device(), i_mask.on_device(), flags, st, &dev, stats != nullptr);
+        return closest_points_device_impl(s, n, i_pts.on_device(), i_rad.on_device(), i_mask.on_device(), flags, st, &dev, stats != nullptr, nearest);
     }, o_tri, o_d2, o_pt, o_vw, o_reg, i_pts, i_rad, i_mask));
     return stats ? query_stats(s, n, 0, stats) : SRT_OK;
 }
@@ -2600,6 +2602,15 @@ int srt_closest_points_device(srt_scene* s, uint32_t n, const float* d_points, c
 int srt_closest_points(srt_scene* s, uint32_t n, const float* points, const float* radius, const uint32_t* point_mask, uint32_t flags, const srt_point_out* out,
                        srt_stats* stats) {
     return guarded([&] { return closest_points_impl(s, n, points, radius, point_mask, flags, out, stats); });
+}
+
+int srt_nearest_points_device(srt_scene* s, uint32_t n, const float* d_points, const float* d_radius, const uint32_t* d_point_mask, uint32_t flags, void* stream,
+                              const srt_point_out* out) {
+    return guarded([&] { return closest_points_device_impl(s, n, d_points, d_radius, d_point_mask, flags, (hipStream_t)stream, out, false, true); });
+}
+int srt_nearest_points(srt_scene* s, uint32_t n, const float* points, const float* radius, const uint32_t* point_mask, uint32_t flags, const srt_point_out* out,
+                       srt_stats* stats) {
+    return guarded([&] { return closest_points_impl(s, n, points, radius, point_mask, flags, out, stats, true); });
 }
 
 void* srt_host_alloc(size_t bytes) {

@@ -194,7 +194,9 @@ __device__ __forceinline__ bool node_pass(const Tests& ts, const V3 o, const V3 
 //     node(a, b)                                the lane's own test of a node record's box
 //     leaf(rows, src, p1, e1, e2, tri, mg)      the triangle test with the operands of owner `src`; a qualifying result is offered to mg
 // and is walked with o, d, t_min and t_max unread.
+// walk_shrinks<Tests>: node() of this policy may give another answer for the same node later in the walk (WalkNearest); no other policy does.
 struct WalkRay {};
+template <typename Tests> struct walk_shrinks : std::false_type {};
 template <bool COUNT, bool RANGE, typename Merge, bool MASK = false, typename Tests = WalkRay>
 __device__ __forceinline__ void query_walk(const DevScene& s, const bool live, const V3 o, const V3 d, const uint32_t lane, uint32_t* q,
                                            const Merge mg, float (*wray)[64], unsigned long long& n_node, unsigned long long& n_tri,
@@ -242,6 +244,7 @@ __device__ __forceinline__ void query_walk(const DevScene& s, const bool live, c
                     }
                 } else {
                     next = skip;
+                    if constexpr (walk_shrinks<Tests>::value) leaf_off = 0;      // (a bound that moved can fail a LATER slice of a leaf: the rest is not taken)
                 }
                 if (!stay) {
                     if (MASK) next = skip_hidden(s, obj_mask, ray_m, cur, next);      // (a slice of a leaf stays: the cursor does not move)
@@ -1516,49 +1519,111 @@ struct WalkPoint {
 // Phase 2, as winner_at for rays: the owning lane recomputes the winner's (v, w, region, point, dist2) from the key's triangle and its own p
 // -- the walk's function on the walk's operands, hence the walk's bits.  point and vw leave transposed through the wave's rows (store_rows).
 // counters: [1] / [2] node / triangle tests (COUNT), [8 + 8 * shard] the points that found a triangle.
+// The body is stated once, as SRT_QUERY_POINTS_BODY(TESTS), for this kernel and k_query_nearest below: TESTS is the walk's policy and nothing
+// else differs.  (A macro and not a function template: through a function the compiler allocates k_query_points' registers in another
+// order, and this file's rule is that a kernel nobody meant to change keeps its bytes -- profiles/nearest_kernels.txt.)
+// In it: a NaN radius fails `r >= 0`; once the walk is over the points' rows are the stage of store_rows (the branch is wave-uniform).
+#define SRT_QUERY_POINTS_BODY(TESTS)                                                                                                                    \
+    __shared__ uint32_t q_all[4][QCAP];                                                                                                                 \
+    __shared__ unsigned long long best_all[256];                                                                                                        \
+    __shared__ float row_all[4][4][64];                                                                                                                 \
+    const uint32_t lane = wave_lane(), wave = wave_index();                                                                                             \
+    unsigned long long* best = best_all + wave * 64;                                                                                                    \
+    float (*rows)[64] = row_all[wave];                                                                                                                  \
+    const size_t base = wave_base(wave), ri = base + lane;                                                                                              \
+    const bool live = ri < (size_t)n_points;                                                                                                            \
+    unsigned long long n_node = 0, n_tri = 0;                                                                                                           \
+    V3 p = mk(0.0f, 0.0f, 0.0f);                                                                                                                        \
+    float r = __builtin_inff();                                                                                                                         \
+    uint32_t m = 0xFFFFFFFFu;                                                                                                                           \
+    if (live) {                                                                                                                                         \
+        const float* pp = points + 3 * ri;                                                                                                              \
+        p = mk(pp[0], pp[1], pp[2]);                                                                                                                    \
+        if (radius) r = radius[ri];                                                                                                                     \
+        if (MASK && qm.ray) m = qm.ray[ri];                                                                                                             \
+    }                                                                                                                                                   \
+    const bool walks = live && r >= 0.0f;                                                                                                               \
+    query_walk<COUNT, false, MergeClosest, MASK>(s, walks, p, p, lane, q_all[wave], MergeClosest{ best }, rows, n_node, n_tri, 0.0f, 0.0f, qm.obj, m, TESTS); \
+    const Winner h = winner_of(live ? best[lane] : ~0ull);                                                                                              \
+    ClosestPoint c;                                                                                                                                     \
+    c.v = 0.0f; c.w = 0.0f; c.dist2 = __builtin_inff(); c.point = mk(0.0f, 0.0f, 0.0f); c.region = 0u;                                                  \
+    if (h.is_hit) {                                                                                                                                     \
+        V3 p1, e1, e2;                                                                                                                                  \
+        load_tri_edges(reinterpret_cast<const float4*>(s.tris), (size_t)h.id, p1, e1, e2);                                                              \
+        closest_point(c, p, p1, e1, e2);                                                                                                                \
+    }                                                                                                                                                   \
+    if (live) {                                                                                                                                         \
+        if (out.tri) out.tri[ri] = h.id;                                                                                                                \
+        if (out.dist2) out.dist2[ri] = c.dist2;                                                                                                         \
+        if (out.region) out.region[ri] = (uint8_t)c.region;                                                                                             \
+    }                                                                                                                                                   \
+    if (base < (size_t)n_points) {                                                                                                                      \
+        const size_t left = (size_t)n_points - base;                                                                                                    \
+        const uint32_t live_rows = (uint32_t)(left < 64 ? left : 64);                                                                                   \
+        __builtin_amdgcn_wave_barrier();                                                                                                                \
+        if (out.point) { const float v[3] = { c.point.x, c.point.y, c.point.z }; store_rows<3>(out.point, base, lane, live_rows, v, &rows[0][0]); }     \
+        if (out.vw) { const float v[2] = { c.v, c.w }; store_rows<2>(out.vw, base, lane, live_rows, v, &rows[0][0]); }                                  \
+    }                                                                                                                                                   \
+    if (counters) count_hits(counters, h.is_hit, blockIdx.x);                                                                                           \
+    count_walks<COUNT>(counters, n_node, n_tri);
 template <bool COUNT, bool MASK>
 __global__ __launch_bounds__(256) void k_query_points(DevScene s, uint32_t n_points, const float* __restrict__ points, const float* __restrict__ radius,
                                                       srt_point_out out, unsigned long long* __restrict__ counters, QueryMask qm) {
-    __shared__ uint32_t q_all[4][QCAP];
-    __shared__ unsigned long long best_all[256];
-    __shared__ float row_all[4][4][64];
-    const uint32_t lane = wave_lane(), wave = wave_index();
-    unsigned long long* best = best_all + wave * 64;
-    float (*rows)[64] = row_all[wave];
-    const size_t base = wave_base(wave), ri = base + lane;
-    const bool live = ri < (size_t)n_points;
-    unsigned long long n_node = 0, n_tri = 0;
-    V3 p = mk(0.0f, 0.0f, 0.0f);
-    float r = __builtin_inff();
-    uint32_t m = 0xFFFFFFFFu;
-    if (live) {
-        const float* pp = points + 3 * ri;
-        p = mk(pp[0], pp[1], pp[2]);
-        if (radius) r = radius[ri];
-        if (MASK && qm.ray) m = qm.ray[ri];
-    }
-    const bool walks = live && r >= 0.0f;               // (a NaN radius fails the comparison)
-    query_walk<COUNT, false, MergeClosest, MASK>(s, walks, p, p, lane, q_all[wave], MergeClosest{ best }, rows, n_node, n_tri, 0.0f, 0.0f, qm.obj, m, WalkPoint{ p, r * r });
-    const Winner h = winner_of(live ? best[lane] : ~0ull);
-    ClosestPoint c;
-    c.v = 0.0f; c.w = 0.0f; c.dist2 = __builtin_inff(); c.point = mk(0.0f, 0.0f, 0.0f); c.region = 0u;
-    if (h.is_hit) {
-        V3 p1, e1, e2;
-        load_tri_edges(reinterpret_cast<const float4*>(s.tris), (size_t)h.id, p1, e1, e2);
-        closest_point(c, p, p1, e1, e2);
-    }
-    if (live) {
-        if (out.tri) out.tri[ri] = h.id;
-        if (out.dist2) out.dist2[ri] = c.dist2;
-        if (out.region) out.region[ri] = (uint8_t)c.region;
-    }
-    if (base < (size_t)n_points) {                      // wave-uniform; the walk is over: the points' rows are the stage
-        const size_t left = (size_t)n_points - base;
-        const uint32_t live_rows = (uint32_t)(left < 64 ? left : 64);
-        __builtin_amdgcn_wave_barrier();
-        if (out.point) { const float v[3] = { c.point.x, c.point.y, c.point.z }; store_rows<3>(out.point, base, lane, live_rows, v, &rows[0][0]); }
-        if (out.vw) { const float v[2] = { c.v, c.w }; store_rows<2>(out.vw, base, lane, live_rows, v, &rows[0][0]); }
-    }
-    if (counters) count_hits(counters, h.is_hit, blockIdx.x);
-    count_walks<COUNT>(counters, n_node, n_tri);
+    SRT_QUERY_POINTS_BODY((WalkPoint{ p, r * r }))
 }
+
+// =================================================================================================
+// Nearest point (srt_nearest_points, include/srt_nearest.h): k_query_points with a bound that shrinks.  The policy is WalkPoint's plus
+// one more reason for a node to fail: the header's `low` of the node's box exceeds the best dist2 offered so far for the lane's point.
+// That best is the high word of the lane's own best[lane], where MergeClosest keeps (dist2 bits << 32 | id); the initial ~0 reads as a
+// NaN and `low > NaN` is false, so "no bound yet" needs no case of its own.  The word moves only when the wave's queue flushes (64 pairs,
+// or no lane active), which is query_walk's schedule as it stands -- no statement of query_walk knows about the bound.
+// Why the result is k_query_points' bit for bit, and when it is not: the header, and DESIGN.md s5 "Nearest point".
+// =================================================================================================
+struct WalkNearest {
+    WalkPoint pt;
+    float mp, zp;                    // of the lane's point: the largest |coordinate|; 0, or NaN if one is not finite
+    const uint32_t* bound;           // the wave's best[] as words: [2 * lane + 1] holds the dist2 bits of lane's best
+    uint32_t lane;
+    static __device__ __forceinline__ WalkNearest make(const V3 p, const float r2, const unsigned long long* best, const uint32_t lane) {
+        const float mp = __builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(p.x), __builtin_fabsf(p.y)), __builtin_fabsf(p.z));
+        const float zp = __builtin_fmaf(0.0f, p.z, __builtin_fmaf(0.0f, p.y, 0.0f * p.x));
+        return WalkNearest{ WalkPoint{ p, r2 }, mp, zp, reinterpret_cast<const uint32_t*>(best), lane };
+    }
+    __device__ __forceinline__ float best_of(const uint32_t owner) const {
+        return __uint_as_float(__hip_atomic_load(bound + 2 * owner + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT));
+    }
+    __device__ __forceinline__ void init(float (*rows)[64], const uint32_t l) const { pt.init(rows, l); }
+    __device__ __forceinline__ bool node(const float4 a, const float4 b) const {
+        const V3 p = pt.p;
+        const float dx = WalkPoint::axis(a.x, a.w, p.x), dy = WalkPoint::axis(a.y, b.x, p.y), dz = WalkPoint::axis(a.z, b.y, p.z);
+        const float b2 = (dx * dx + dy * dy) + dz * dz;
+        if (b2 > pt.r2) return false;
+        // the header's low: the box grown by s = K half-ulps of the largest coordinate in play; a NaN or an infinity makes s a NaN and low 0
+        float m = __builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(a.x), __builtin_fabsf(a.y)), __builtin_fabsf(a.z));
+        m = __builtin_fmaxf(__builtin_fmaxf(m, __builtin_fabsf(a.w)), __builtin_fmaxf(__builtin_fabsf(b.x), __builtin_fabsf(b.y)));
+        m = __builtin_fmaxf(m, mp);
+        float z = __builtin_fmaf(0.0f, a.x, zp);
+        z = __builtin_fmaf(0.0f, a.y, z); z = __builtin_fmaf(0.0f, a.z, z); z = __builtin_fmaf(0.0f, a.w, z);
+        z = __builtin_fmaf(0.0f, b.x, z); z = __builtin_fmaf(0.0f, b.y, z);
+        const float s = __builtin_fmaf((float)SRT_NEAREST_K * 0x1p-24f, m, z);      // (one rounding, of K 2^-24 M: z is 0 or a NaN)
+        float tx = dx - s, ty = dy - s, tz = dz - s;
+        tx = tx > 0.0f ? tx : 0.0f; ty = ty > 0.0f ? ty : 0.0f; tz = tz > 0.0f ? tz : 0.0f;
+        const float low = ((tx * tx + ty * ty) + tz * tz) * (1.0f - 0x1p-20f);
+        return !(low > best_of(lane) && low < __builtin_inff());
+    }
+    // (a candidate above its owner's current best cannot win: the atomicMin is skipped; an equal one goes on, for the lowest id)
+    template <typename Merge>
+    __device__ __forceinline__ void leaf(float (*rows)[64], const uint32_t src, const V3 p1, const V3 e1, const V3 e2, const uint32_t tri, const Merge& mg) const {
+        ClosestPoint c;
+        closest_point(c, mk(rows[0][src], rows[1][src], rows[2][src]), p1, e1, e2);
+        if (c.dist2 <= rows[3][src] && !(c.dist2 > best_of(src))) mg.offer(src, tri, c.dist2);
+    }
+};
+template <> struct walk_shrinks<WalkNearest> : std::true_type {};
+template <bool COUNT, bool MASK>
+__global__ __launch_bounds__(256) void k_query_nearest(DevScene s, uint32_t n_points, const float* __restrict__ points, const float* __restrict__ radius,
+                                                       srt_point_out out, unsigned long long* __restrict__ counters, QueryMask qm) {
+    SRT_QUERY_POINTS_BODY(WalkNearest::make(p, r * r, best, lane))
+}
+#undef SRT_QUERY_POINTS_BODY

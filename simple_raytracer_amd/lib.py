@@ -1,4 +1,4 @@
-"""ctypes binding of the C ABI in include/srt.h and its extension header include/srt_points.h (libsrt_hip.so).
+"""ctypes binding of the C ABI in include/srt.h and its extension headers include/srt_points.h and include/srt_nearest.h (libsrt_hip.so).
 
 The product path has NO CPU fallback: if the HIP library is missing or no GPU is visible, this
 raises.  (The CPU restatement under oracle/ is test infrastructure and is never imported here.)
@@ -17,6 +17,7 @@ LIB_PATH = os.path.join(_HERE, "libsrt_hip.so")
 
 ABI_SYMBOLS = tuple(abi.PROTOTYPES)           # every symbol include/srt.h declares
 POINT_SYMBOLS = tuple(abi.POINT_PROTOTYPES)    # every symbol include/srt_points.h declares
+NEAREST_SYMBOLS = tuple(abi.NEAREST_PROTOTYPES)    # every symbol include/srt_nearest.h declares
 MULTI_HIT_MAX = abi.SRT_MULTI_HIT_MAX
 
 _f32p, _i32p, _u8p, _u32p = C.POINTER(C.c_float), C.POINTER(C.c_int32), C.POINTER(C.c_uint8), C.POINTER(C.c_uint32)
@@ -40,7 +41,7 @@ def load(path=None):
             raise RuntimeError(f"{path or LIB_PATH} is missing: the HIP extension must be built "
                                "(python -m simple_raytracer_amd.build); there is no CPU fallback")
         L = C.CDLL(path or LIB_PATH)
-        for name, (restype, argtypes) in {**abi.PROTOTYPES, **abi.POINT_PROTOTYPES}.items():
+        for name, (restype, argtypes) in {**abi.PROTOTYPES, **abi.POINT_PROTOTYPES, **abi.NEAREST_PROTOTYPES}.items():
             fn = getattr(L, name)
             fn.restype, fn.argtypes = restype, argtypes
         if path is not None:
@@ -485,21 +486,36 @@ class DeviceScene:
         edges, 4..6 vertices) -- + 'stats'; count=True fills the node / triangle test counts.  The radius never shrinks during the walk: pass
         one for speed.  point_mask (n uint32, or None = all ones): only the objects whose mask (set_object_masks) shares a bit with the
         point's are searched."""
+        return self._points("srt_closest_points", points, radius, point_mask, count, want)
+
+    def _points(self, symbol, points, radius, point_mask, count, want):
         pts = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
         n = pts.shape[0]
         rad = None if radius is None else np.ascontiguousarray(np.broadcast_to(np.asarray(radius, np.float32).reshape(-1), (n,)), np.float32)
         pm = None if point_mask is None else _ray_mask(point_mask, n)
         out, _ = _outputs(want, (n,), _POINT)
         po = abi.PointOut(*_addresses(out, _POINT))
-        return _with_stats(out, self.L.srt_closest_points, "srt_closest_points", self.h, n, _host(pts, _f32p), _host(rad, _f32p), _host(pm, _u32p),
+        return _with_stats(out, getattr(self.L, symbol), symbol, self.h, n, _host(pts, _f32p), _host(rad, _f32p), _host(pm, _u32p),
                            _query_flags(count=count), C.byref(po))
 
     def closest_points_device(self, n, d_points, radius=0, point_mask=0, stream=0, count=False, tri=0, dist2=0, point=0, vw=0, region=0):
         """srt_closest_points_device: raw device pointers (ints, e.g. torch.Tensor.data_ptr()) in -- the points (n x 3 floats), `radius` (n
         floats, 0 = +inf), `point_mask` (n uint32, 0 = all ones) and the outputs (0: not wanted) --, asynchronous on `stream`, one launch."""
-        po = _wanted(abi.PointOut, tri, dist2, point, vw, region)
-        _check(self.L.srt_closest_points_device(self.h, n, d_points, radius or None, point_mask or None, _query_flags(count=count), stream, C.byref(po)),
-               "srt_closest_points_device")
+        self._points_device("srt_closest_points_device", n, d_points, radius, point_mask, stream, count, (tri, dist2, point, vw, region))
+
+    def _points_device(self, symbol, n, d_points, radius, point_mask, stream, count, outs):
+        po = _wanted(abi.PointOut, *outs)
+        _check(getattr(self.L, symbol)(self.h, n, d_points, radius or None, point_mask or None, _query_flags(count=count), stream, C.byref(po)), symbol)
+
+    def nearest_points(self, points, radius=None, point_mask=None, count=False, want=("tri", "dist2", "point", "vw", "region")):
+        """srt_nearest_points (include/srt_nearest.h): closest_points' arguments and closest_points' results, bit for bit, on every scene whose
+        boxes nest -- but the walk also prunes by the best distance found so far, so no radius has to be chosen: None costs the
+        neighbourhood of the answer, not the scene.  count=True: the counts are of the walk as it ran and depend on the batch."""
+        return self._points("srt_nearest_points", points, radius, point_mask, count, want)
+
+    def nearest_points_device(self, n, d_points, radius=0, point_mask=0, stream=0, count=False, tri=0, dist2=0, point=0, vw=0, region=0):
+        """srt_nearest_points_device: closest_points_device's arguments, asynchronous on `stream`, one launch."""
+        self._points_device("srt_nearest_points_device", n, d_points, radius, point_mask, stream, count, (tri, dist2, point, vw, region))
 
     def sync(self):
         return _with_stats({}, self.L.srt_sync, "srt_sync", self.h)["stats"]

@@ -52,7 +52,9 @@ rotations, and with that table and the bent normal.
 the camera by a few offsets, over a few radii on a sub-sample of the hits and with no radius (+inf: every triangle is a candidate) on a
 smaller one, in one run beside srt_trace_rays_device on the rays of the same pixels -- the yardstick of what a walk costs -- and the node and
 triangle tests per point from the counting build.
-Usage: python tools/ray_query_probe.py [--reps N] [--trace] [--shade | --range | --shade-range | --multi | --surface | --paths | --shadow-rule | --masked | --refract | --fresnel | --ao | --render-ao | --points [--rounds R]]     (--trace: few repetitions, for a run under rocprofv3 --kernel-trace --stats)"""
+--nearest: the table of --points with srt_nearest_points_device (the bound shrinks) beside srt_closest_points_device, the yardstick, on the same
+points in the same rounds at every radius; the outputs of the two are compared on the way.
+Usage: python tools/ray_query_probe.py [--reps N] [--trace] [--shade | --range | --shade-range | --multi | --surface | --paths | --shadow-rule | --masked | --refract | --fresnel | --ao | --render-ao | --points | --nearest [--rounds R]]     (--trace: few repetitions, for a run under rocprofv3 --kernel-trace --stats)"""
 import argparse, os, sys, time
 import numpy as np
 import torch                                   # first: torch initialises HIP before the library does
@@ -775,9 +777,11 @@ def render_ao_section(reps, rounds):
     ds.close()
 
 
-def points_section(reps, rounds):
+def points_section(reps, rounds, nearest=False):
     """What a closest-point walk costs beside a ray's: the hit points of the 1080p frame, OFFSETS units off the surface towards the camera,
-    with RADII on every STEP-th hit and with no radius on every (16 STEP)-th, each beside srt_trace_rays_device on the rays of the same pixels."""
+    with RADII on every STEP-th hit and with no radius on every (16 STEP)-th, each beside srt_trace_rays_device on the rays of the same pixels.
+    nearest: srt_nearest_points_device beside srt_closest_points_device, the yardstick, on the same points in the same rounds, radius by
+    radius: the ratio of the medians, and both calls' node and triangle tests per point."""
     OFFSETS, RADII, STEP = (0.25, 2.0, 16.0), (1.0, 4.0, 16.0, 64.0), 4
     dev = torch.device("cuda", 0); torch.zeros(1, device=dev)
     g = gu.GoldenScene("ground_bunny")
@@ -808,6 +812,23 @@ def points_section(reps, rounds):
             for r in radii:
                 forms[f"closest_points, radius {r:g}"] = (lambda r=r: ds.closest_points_device(n, d_pts.data_ptr(), radius=0 if np.isinf(r) else d_rad[r].data_ptr(), stream=cur,
                                                                                                tri=tri.data_ptr(), dist2=d2.data_ptr(), point=pt.data_ptr()))
+            if nearest:
+                forms = {}
+                for r in radii:
+                    for call in ("closest_points", "nearest_points"):
+                        forms[f"{call}, radius {r:g}"] = (lambda r=r, fn=getattr(ds, call + "_device"): fn(n, d_pts.data_ptr(), radius=0 if np.isinf(r) else d_rad[r].data_ptr(),
+                                                                                                          stream=cur, tri=tri.data_ptr(), dist2=d2.data_ptr(), point=pt.data_ptr()))
+                ms = rounds_of(forms, reps, rounds, side)
+                side.synchronize()
+                for r in radii:
+                    pair = {k: ms[f"{k}, radius {r:g}"] for k in ("closest_points", "nearest_points")}
+                    report(f"{off:g} off the surface, radius {r:g}", pair)
+                    both = {k: getattr(ds, k)(pts, radius=None if np.isinf(r) else r, count=True, want=("tri", "dist2")) for k in pair}
+                    assert all(np.array_equal(both["closest_points"][k].view(np.uint32), both["nearest_points"][k].view(np.uint32)) for k in ("tri", "dist2"))
+                    for k, o in both.items():
+                        print(f"{'':34s} {k}: found {int((o['tri'] >= 0).sum())} of {n}; per point {o['stats']['node_tests_primary'] / n:.1f} node tests, "
+                              f"{o['stats']['tri_tests_primary'] / n:.1f} triangle tests")
+                continue
             report(f"{off:g} off the surface", rounds_of(forms, reps, rounds, side))
             side.synchronize()
             for r in radii:
@@ -824,6 +845,7 @@ def points_section(reps, rounds):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--points", action="store_true")
+    ap.add_argument("--nearest", action="store_true")
     ap.add_argument("--render-ao", action="store_true", dest="render_ao")
     ap.add_argument("--ao", action="store_true")
     ap.add_argument("--fresnel", action="store_true")
@@ -841,8 +863,8 @@ def main():
     ap.add_argument("--rounds", type=int, default=7)
     a = ap.parse_args()
     reps = 3 if a.trace else a.reps
-    if a.points:
-        return points_section(reps, 2 if a.trace else a.rounds)
+    if a.points or a.nearest:
+        return points_section(reps, 2 if a.trace else a.rounds, nearest=a.nearest)
     if a.render_ao:
         return render_ao_section(reps, 2 if a.trace else a.rounds)
     if a.ao:
