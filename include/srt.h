@@ -1132,4 +1132,5 @@ uint32_t    srt_abi_version(void);
  * include/srt_points.h states their definition.  SRT_ABI_VERSION is unchanged by them. */
 #include "srt_points.h"
 #include "srt_nearest.h"      /* the same query with a bound that shrinks: no radius to choose */
+#include "srt_signed.h"       /* that distance with a sign, and containment, by winding along a few rays */
 #endif /* SRT_H */

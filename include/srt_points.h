@@ -57,8 +57,9 @@ extern "C" {
  * SRT_OK with nothing done.  Every field of *out NULL in the _device form: SRT_OK, nothing launched.
  * The host form stages points, radius, point_mask and the outputs through the handle's pinned block, then waits.  *stats: primary_rays = n,
  * hit_rays = the points that found a triangle, node_tests_primary / tri_tests_primary under SRT_FLAG_COUNT_WORK.
- * NOT HERE: a shrinking radius (above); a SIGN -- the distance is unsigned; `region` is the hook for a later signed distance by
- * pseudo-normals (face, edge or vertex normal by region) --; the K nearest triangles; an any-within-radius form that stops at the first. */
+ * NOT HERE: a shrinking radius (above; see srt_nearest.h); a SIGN -- the distance is unsigned; see srt_signed.h, which counts the sign
+ * along rays; `region` serves a caller who keeps pseudo-normals of their own (face, edge or vertex normal by region) --; the K nearest
+ * triangles; an any-within-radius form that stops at the first. */
 typedef struct srt_point_out {    /* device pointers in the _device form, host pointers in the host form */
     int32_t* tri;                /* n       canonical triangle id, -1 = none within the radius */
     float*   dist2;              /* n       the winner's dist2 with its own bits, +inf = none */

@@ -1,6 +1,7 @@
 """ctypes mirror of include/srt.h -- its structs (STRUCTS), constants (SRT_*) and prototypes (PROTOTYPES), checked against the header by
-tests/test_abi_mirror.py --, of its extension header include/srt_points.h (POINT_STRUCTS, POINT_PROTOTYPES; tests/test_point_ref.py), and
-a numpy container for the flat scene.
+tests/test_abi_mirror.py --, of its extension headers include/srt_points.h (POINT_STRUCTS, POINT_PROTOTYPES; tests/test_point_ref.py),
+include/srt_nearest.h (NEAREST_PROTOTYPES; tests/test_nearest_ref.py) and include/srt_signed.h (SIGNED_STRUCTS, SIGNED_PROTOTYPES;
+tests/test_sign_ref.py), and a numpy container for the flat scene.
 
 The flat scene is the reference's ObjectManager state (Object.h:59-89 in the reference) written out as
 arrays; see include/srt.h for the layout contract.  This module holds no compute.
@@ -218,6 +219,23 @@ STRUCTS = {"srt_scene_desc": SceneDesc, "srt_params": Params, "srt_stats": Stats
 POINT_STRUCTS = {"srt_point_out": PointOut}
 
 
+class Sign(C.Structure):
+    """srt_sign: the direction table of a signed-distance query (an address: host memory in the host form, device memory in the _device
+    form; 0 with n_dirs 0 = the default table) and the vote's flags."""
+    _fields_ = [("dirs", C.c_void_p), ("n_dirs", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class SignOut(C.Structure):
+    """srt_sign_out: the arrays a signed-distance query fills, as addresses; 0 = not wanted."""
+    _fields_ = [("sdist", C.c_void_p), ("inside", C.c_void_p), ("winding", C.c_void_p), ("crossings", C.c_void_p)]
+
+
+# the fields of srt_sign_out: name -> (dtype, entries per point; None: n_dirs)
+SIGN_FIELDS = {"sdist": (np.float32, 1), "inside": (np.uint8, 1), "winding": (np.int32, None), "crossings": (np.uint32, None)}
+# every struct of include/srt_signed.h
+SIGNED_STRUCTS = {"srt_sign": Sign, "srt_sign_out": SignOut}
+
+
 # ---- the prototypes of include/srt.h, in its order: name -> (restype, [argtypes]) ----
 # srt_scene*, void* and every address that travels as an int (the d_* parameters, a stream, srt_render_async's outputs) are c_void_p;
 # srt_scene** and T* const* are POINTER(c_void_p); a pointer to an srt_ struct is POINTER(its class); a scalar is its exact ctype.
@@ -338,6 +356,16 @@ NEAREST_K = 64      # SRT_NEAREST_K
 NEAREST_PROTOTYPES = {
     "srt_nearest_points_device": POINT_PROTOTYPES["srt_closest_points_device"],
     "srt_nearest_points": POINT_PROTOTYPES["srt_closest_points"],
+}
+
+# ---- include/srt_signed.h: its constants, its default table (SRT_SIGN_DEFAULT_DIRS, float literals) and its prototypes, in its order ----
+SIGN_MAX_DIRS = 16      # SRT_SIGN_MAX_DIRS
+SIGN_PARITY = 1         # SRT_SIGN_PARITY
+SIGN_DEFAULT_DIRS = np.array([[0.57, 0.31, 0.76], [-0.43, 0.81, -0.39], [0.29, -0.66, -0.69]], np.float32)
+_sign, _sout = C.POINTER(Sign), C.POINTER(SignOut)
+SIGNED_PROTOTYPES = {
+    "srt_signed_points_device": (_int, [_vp, _u32, _vp, _vp, _vp, _sign, _u32, _vp, _pout, _sout]),
+    "srt_signed_points": (_int, [_vp, _u32, _f32p, _f32p, _u32p, _sign, _u32, _pout, _sout, _stats]),
 }
 
 

@@ -1835,6 +1835,34 @@ static int closest_points_device_impl(srt_scene* s, uint32_t n, const float* d_p
     return launch_query((nearest ? shrinking : builds)[build_index(count, d_point_mask)], q.grid, q.stream, s->dev, n, d_points, d_radius, *out, q.ctr, query_mask(s, d_point_mask));
 }
 
+// srt_signed_points (include/srt_signed.h): srt_nearest_points' outputs and a sign by winding along the rays of a direction table, one
+// launch (k_query_signed).  No sign output wanted: the call IS srt_nearest_points, with that call's kernels, and `sign` is not read.
+// NEAR: whether the nearest phase runs -- a point output or sdist is wanted; without it hit_rays is 0.
+static inline bool sign_wanted(const srt_sign_out* o) { return o && (o->sdist || o->inside || o->winding || o->crossings); }
+static int check_signed(const srt_scene* s, uint32_t n, const float* points, const srt_sign* sign, uint32_t flags, const srt_point_out* out, const srt_sign_out* sout) {
+    SRT_TRY(check_query(s, n, points, flags));
+    if (!out && !sout) return SRT_ERR_ARG;
+    if (sign_wanted(sout) && sign) {
+        if (sign->n_dirs > SRT_SIGN_MAX_DIRS || (sign->n_dirs == 0) != (sign->dirs == nullptr) || (sign->flags & ~(uint32_t)SRT_SIGN_PARITY)) return SRT_ERR_ARG;
+    }
+    return SRT_OK;
+}
+static inline uint32_t sign_dirs(const srt_sign* sign) { return sign && sign->dirs ? sign->n_dirs : 3u; }      // (the default table has three)
+static int signed_points_device_impl(srt_scene* s, uint32_t n, const float* d_points, const float* d_radius, const uint32_t* d_point_mask, const srt_sign* sign,
+                                     uint32_t flags, hipStream_t stream, const srt_point_out* out, const srt_sign_out* sout, bool count_hits) {
+    SRT_TRY(check_signed(s, n, d_points, sign, flags, out, sout));
+    const srt_point_out none = {};
+    if (!sign_wanted(sout)) return closest_points_device_impl(s, n, d_points, d_radius, d_point_mask, flags, stream, out ? out : &none, count_hits, true);
+    if (!n) return SRT_OK;
+    const bool count = (flags & SRT_FLAG_COUNT_WORK) != 0, near = (out && points_wanted(out)) || sout->sdist;
+    QueryLaunch q;
+    SRT_TRY(query_prologue(s, n, stream, nullptr, count || count_hits, &q));
+    static const std::array builds = { BUILDS_3(k_query_signed) };
+    const QuerySign sg = { sign ? sign->dirs : nullptr, sign_dirs(sign), sign && (sign->flags & SRT_SIGN_PARITY) ? 1u : 0u };
+    return launch_query(builds[build_index(count, d_point_mask, near)], q.grid, q.stream, s->dev, n, d_points, d_radius, out ? *out : none, *sout, sg, q.ctr,
+                        query_mask(s, d_point_mask));
+}
+
 // What a shading kernel takes of the params (after query_prologue: the light table is the handle's device copy)
 static QueryShade query_shade(const srt_scene* s, const srt_params* p) {
     QueryShade qs;
@@ -2175,6 +2203,33 @@ static int closest_points_impl(srt_scene* s, uint32_t n, const float* points, co
         return closest_points_device_impl(s, n, i_pts.on_device(), i_rad.on_device(), i_mask.on_device(), flags, st, &dev, stats != nullptr, nearest);
     }, o_tri, o_d2, o_pt, o_vw, o_reg, i_pts, i_rad, i_mask));
     return stats ? query_stats(s, n, 0, stats) : SRT_OK;
+}
+
+static int signed_points_impl(srt_scene* s, uint32_t n, const float* points, const float* radius, const uint32_t* point_mask, const srt_sign* sign, uint32_t flags,
+                              const srt_point_out* out, const srt_sign_out* sout, srt_stats* stats) {
+    SRT_TRY(check_signed(s, n, points, sign, flags, out, sout));
+    const srt_point_out none = {};
+    if (!sign_wanted(sout)) return closest_points_impl(s, n, points, radius, point_mask, flags, out ? out : &none, stats, true);
+    if (stats) std::memset(stats, 0, sizeof(*stats));
+    if (!n) return SRT_OK;
+    if (!out) out = &none;
+    const uint32_t nd = sign_dirs(sign);
+    const size_t rows = (size_t)n * nd;      // the n x n_dirs rows
+    auto o_tri = query_out(out->tri, n); auto o_d2 = query_out(out->dist2, n); auto o_pt = query_out(out->point, 3ull * n);
+    auto o_vw = query_out(out->vw, 2ull * n); auto o_reg = query_out(out->region, n);
+    auto o_sd = query_out(sout->sdist, n); auto o_in = query_out(sout->inside, n); auto o_wind = query_out(sout->winding, rows); auto o_cross = query_out(sout->crossings, rows);
+    auto i_pts = query_in(points, 3ull * n); auto i_rad = query_in(radius, n); auto i_mask = query_in(point_mask, n);
+    auto i_dirs = query_in(sign ? sign->dirs : nullptr, 3ull * nd);
+    SRT_TRY(query_round_trip(s, false, [&](hipStream_t st) {
+        const srt_point_out dev = { o_tri.on_device(), o_d2.on_device(), o_pt.on_device(), o_vw.on_device(), o_reg.on_device() };
+        const srt_sign_out sdev = { o_sd.on_device(), o_in.on_device(), o_wind.on_device(), o_cross.on_device() };
+        const srt_sign sg = { i_dirs.on_device(), i_dirs.on_device() ? nd : 0u, sign ? sign->flags : 0u };
+        return signed_points_device_impl(s, n, i_pts.on_device(), i_rad.on_device(), i_mask.on_device(), &sg, flags, st, &dev, &sdev, stats != nullptr);
+    }, o_tri, o_d2, o_pt, o_vw, o_reg, o_sd, o_in, o_wind, o_cross, i_pts, i_rad, i_mask, i_dirs));
+    if (!stats) return SRT_OK;
+    SRT_TRY(query_stats(s, n, 0, stats));
+    stats->shadow_rays = rows;
+    return SRT_OK;
 }
 
 static int trace_rays_multi_impl(srt_scene* s, uint32_t n, const float* rays, const float* t_range, uint32_t k, uint32_t flags, uint32_t* n_hits, int32_t* hit_id,
@@ -2611,6 +2666,15 @@ int srt_nearest_points_device(srt_scene* s, uint32_t n, const float* d_points, c
 int srt_nearest_points(srt_scene* s, uint32_t n, const float* points, const float* radius, const uint32_t* point_mask, uint32_t flags, const srt_point_out* out,
                        srt_stats* stats) {
     return guarded([&] { return closest_points_impl(s, n, points, radius, point_mask, flags, out, stats, true); });
+}
+
+int srt_signed_points_device(srt_scene* s, uint32_t n, const float* d_points, const float* d_radius, const uint32_t* d_point_mask, const srt_sign* sign, uint32_t flags,
+                             void* stream, const srt_point_out* out, const srt_sign_out* sout) {
+    return guarded([&] { return signed_points_device_impl(s, n, d_points, d_radius, d_point_mask, sign, flags, (hipStream_t)stream, out, sout, false); });
+}
+int srt_signed_points(srt_scene* s, uint32_t n, const float* points, const float* radius, const uint32_t* point_mask, const srt_sign* sign, uint32_t flags,
+                      const srt_point_out* out, const srt_sign_out* sout, srt_stats* stats) {
+    return guarded([&] { return signed_points_impl(s, n, points, radius, point_mask, sign, flags, out, sout, stats); });
 }
 
 void* srt_host_alloc(size_t bytes) {

@@ -1523,13 +1523,16 @@ struct WalkPoint {
 // else differs.  (A macro and not a function template: through a function the compiler allocates k_query_points' registers in another
 // order, and this file's rule is that a kernel nobody meant to change keeps its bytes -- profiles/nearest_kernels.txt.)
 // In it: a NaN radius fails `r >= 0`; once the walk is over the points' rows are the stage of store_rows (the branch is wave-uniform).
-#define SRT_QUERY_POINTS_BODY(TESTS)                                                                                                                    \
+// It comes in four pieces -- the wave's LDS with ROWS rows, the point's loads, the walk with the winner recomputed, the stores -- because
+// k_query_signed at the end of this file runs the same pieces around its sign rays; the body expands to the tokens it always had.
+#define SRT_QUERY_POINTS_LDS(ROWS)                                                                                                                      \
     __shared__ uint32_t q_all[4][QCAP];                                                                                                                 \
     __shared__ unsigned long long best_all[256];                                                                                                        \
-    __shared__ float row_all[4][4][64];                                                                                                                 \
+    __shared__ float row_all[4][ROWS][64];                                                                                                              \
     const uint32_t lane = wave_lane(), wave = wave_index();                                                                                             \
     unsigned long long* best = best_all + wave * 64;                                                                                                    \
-    float (*rows)[64] = row_all[wave];                                                                                                                  \
+    float (*rows)[64] = row_all[wave];
+#define SRT_QUERY_POINTS_LOAD                                                                                                                           \
     const size_t base = wave_base(wave), ri = base + lane;                                                                                              \
     const bool live = ri < (size_t)n_points;                                                                                                            \
     unsigned long long n_node = 0, n_tri = 0;                                                                                                           \
@@ -1541,9 +1544,10 @@ struct WalkPoint {
         p = mk(pp[0], pp[1], pp[2]);                                                                                                                    \
         if (radius) r = radius[ri];                                                                                                                     \
         if (MASK && qm.ray) m = qm.ray[ri];                                                                                                             \
-    }                                                                                                                                                   \
+    }
+#define SRT_QUERY_POINTS_FIND(TESTS)                                                                                                                    \
     const bool walks = live && r >= 0.0f;                                                                                                               \
-    query_walk<COUNT, false, MergeClosest, MASK>(s, walks, p, p, lane, q_all[wave], MergeClosest{ best }, rows, n_node, n_tri, 0.0f, 0.0f, qm.obj, m, TESTS); \
+    query_walk<COUNT, false, MergeClosest, MASK>(s, walks, p, p, lane, q_all[wave], MergeClosest{ best }, rows, n_node, n_tri, 0.0f, 0.0f, qm.obj, m, TESTS);\
     const Winner h = winner_of(live ? best[lane] : ~0ull);                                                                                              \
     ClosestPoint c;                                                                                                                                     \
     c.v = 0.0f; c.w = 0.0f; c.dist2 = __builtin_inff(); c.point = mk(0.0f, 0.0f, 0.0f); c.region = 0u;                                                  \
@@ -1551,7 +1555,8 @@ struct WalkPoint {
         V3 p1, e1, e2;                                                                                                                                  \
         load_tri_edges(reinterpret_cast<const float4*>(s.tris), (size_t)h.id, p1, e1, e2);                                                              \
         closest_point(c, p, p1, e1, e2);                                                                                                                \
-    }                                                                                                                                                   \
+    }
+#define SRT_QUERY_POINTS_STORE                                                                                                                          \
     if (live) {                                                                                                                                         \
         if (out.tri) out.tri[ri] = h.id;                                                                                                                \
         if (out.dist2) out.dist2[ri] = c.dist2;                                                                                                         \
@@ -1563,7 +1568,9 @@ struct WalkPoint {
         __builtin_amdgcn_wave_barrier();                                                                                                                \
         if (out.point) { const float v[3] = { c.point.x, c.point.y, c.point.z }; store_rows<3>(out.point, base, lane, live_rows, v, &rows[0][0]); }     \
         if (out.vw) { const float v[2] = { c.v, c.w }; store_rows<2>(out.vw, base, lane, live_rows, v, &rows[0][0]); }                                  \
-    }                                                                                                                                                   \
+    }
+#define SRT_QUERY_POINTS_BODY(TESTS)                                                                                                                    \
+    SRT_QUERY_POINTS_LDS(4) SRT_QUERY_POINTS_LOAD SRT_QUERY_POINTS_FIND(TESTS) SRT_QUERY_POINTS_STORE                                                   \
     if (counters) count_hits(counters, h.is_hit, blockIdx.x);                                                                                           \
     count_walks<COUNT>(counters, n_node, n_tri);
 template <bool COUNT, bool MASK>
@@ -1627,3 +1634,88 @@ __global__ __launch_bounds__(256) void k_query_nearest(DevScene s, uint32_t n_po
     SRT_QUERY_POINTS_BODY(WalkNearest::make(p, r * r, best, lane))
 }
 #undef SRT_QUERY_POINTS_BODY
+
+// =================================================================================================
+// Signed distance and containment (srt_signed_points, include/srt_signed.h): k_query_nearest's distance, and a sign by winding along
+// n_dirs rays from the point.
+// Phase 1 (NEAR) is k_query_nearest's body, piece by piece: WalkNearest, MergeClosest, the winner recomputed from the key, the stores.  The
+// host picks NEAR = false when neither a field of the point outputs nor sdist is wanted: containment for the price of the ray walks.
+// Phase 2: the table (the caller's, or the header's default) goes into LDS once per workgroup; for every direction j the wave's 64 rays
+// (p, dirs[j]) are ONE query_walk -- every live lane is busy, neighbouring points share a direction, nothing is compacted or dealt.  The
+// walk is the ray's with another leaf: WalkCross keeps (o, d) in 6 rows as WalkRay does, tests a node with slab_pass<true> on the lane's
+// own ray_rcp, and a leaf with ray_triangle on the OWNER's ray; a candidate that counts by the closest hit's rule offers the sign of its
+// det.  MergeCross keeps two words a lane -- entries, exits -- in the 8 bytes that held phase 1's key, added to by whichever lane tested
+// the pair.  A point whose radius walks nothing in phase 1 still gets its rays.
+// LDS a workgroup: the queue 10,240 B, the keys / counts 2,048 B, 6 rows 6,144 B (phase 1 uses 4 of them, and 3 as its stage), the table
+// 192 B: 18,624 B, eight workgroups a CU, which the registers do not reach.
+// counters: [1] / [2] phase 1 as k_query_nearest counts it, [3] / [4] node / triangle tests of the sign rays, [8 + 8 * shard] the points
+// that found a triangle.
+// =================================================================================================
+__constant__ float sign_default_dirs[9] = SRT_SIGN_DEFAULT_DIRS;
+struct QuerySign { const float* dirs; uint32_t n_dirs, parity; };      // dirs NULL: sign_default_dirs (n_dirs is 3 then)
+struct MergeCross {
+    uint32_t* cnt;                // 2 x 64 words: [2 * lane] entries, [2 * lane + 1] exits of the lane's ray
+    __device__ __forceinline__ void init(const uint32_t lane) const { cnt[2 * lane] = 0u; cnt[2 * lane + 1] = 0u; }
+    __device__ __forceinline__ void offer(const uint32_t src, const uint32_t, const float det) const { atomicAdd(&cnt[2 * src + (det < 0.0f ? 1u : 0u)], 1u); }
+};
+struct WalkCross {
+    V3 o, d;
+    RayRcp rc;
+    __device__ __forceinline__ void init(float (*rows)[64], const uint32_t lane) const {
+        rows[0][lane] = o.x; rows[1][lane] = o.y; rows[2][lane] = o.z;
+        rows[3][lane] = d.x; rows[4][lane] = d.y; rows[5][lane] = d.z;
+    }
+    __device__ __forceinline__ bool node(const float4 a, const float4 b) const { return slab_pass<true>(o, d, rc, a.x, a.y, a.z, a.w, b.x, b.y); }
+    template <typename Merge>
+    __device__ __forceinline__ void leaf(float (*rows)[64], const uint32_t src, const V3 p1, const V3 e1, const V3 e2, const uint32_t tri, const Merge& mg) const {
+        const V3 os = mk(rows[0][src], rows[1][src], rows[2][src]), ds = mk(rows[3][src], rows[4][src], rows[5][src]);
+        const float t = ray_triangle(os, ds, p1, e1, e2);
+        // counts iff t != -inf && t < +inf (the closest hit's rule); then |det| >= 1e-12: an entry (det > 0) or an exit (det < 0)
+        if (t != SRT_NEG_INF && t < __builtin_inff()) mg.offer(src, tri, dot3(e1, cross3(ds, e2)));
+    }
+};
+template <bool COUNT, bool MASK, bool NEAR>
+__global__ __launch_bounds__(256) void k_query_signed(DevScene s, uint32_t n_points, const float* __restrict__ points, const float* __restrict__ radius,
+                                                      srt_point_out out, srt_sign_out sout, QuerySign sg, unsigned long long* __restrict__ counters, QueryMask qm) {
+    __shared__ float dir_tab[SRT_SIGN_MAX_DIRS * 3];
+    SRT_QUERY_POINTS_LDS(6)
+    if (threadIdx.x < 3u * sg.n_dirs) dir_tab[threadIdx.x] = sg.dirs ? sg.dirs[threadIdx.x] : sign_default_dirs[threadIdx.x];
+    __syncthreads();
+    SRT_QUERY_POINTS_LOAD
+    bool found = false;
+    float dist2 = __builtin_inff();
+    if constexpr (NEAR) {
+        SRT_QUERY_POINTS_FIND(WalkNearest::make(p, r * r, best, lane))
+        SRT_QUERY_POINTS_STORE
+        found = h.is_hit; dist2 = c.dist2;
+        __builtin_amdgcn_wave_barrier();              // every lane has read its key: the 8 bytes are the counts' now
+    }
+    unsigned long long n_node_s = 0, n_tri_s = 0;
+    uint32_t* cnt = reinterpret_cast<uint32_t*>(best);
+    uint32_t votes = 0;
+    for (uint32_t j = 0; j < sg.n_dirs; j++) {        // wave-uniform
+        const V3 d = mk(dir_tab[3 * j], dir_tab[3 * j + 1], dir_tab[3 * j + 2]);
+        query_walk<COUNT, false, MergeCross, MASK>(s, live, p, d, lane, q_all[wave], MergeCross{ cnt }, rows, n_node_s, n_tri_s, 0.0f, 0.0f, qm.obj, m,
+                                                   WalkCross{ p, d, ray_rcp(p, d) });
+        const uint32_t entries = cnt[2 * lane], exits = cnt[2 * lane + 1];
+        const int32_t winding = (int32_t)exits - (int32_t)entries;
+        const uint32_t crossings = exits + entries;
+        votes += sg.parity ? (crossings & 1u) : (winding > 0 ? 1u : 0u);
+        if (live) {
+            if (sout.winding) sout.winding[ri * sg.n_dirs + j] = winding;
+            if (sout.crossings) sout.crossings[ri * sg.n_dirs + j] = crossings;
+        }
+        __builtin_amdgcn_wave_barrier();              // (the next direction clears the counts)
+    }
+    const bool inside = 2u * votes > sg.n_dirs;
+    if (live) {
+        if (sout.inside) sout.inside[ri] = inside ? 1 : 0;
+        if (NEAR && sout.sdist) sout.sdist[ri] = inside ? -sqrtf(dist2) : sqrtf(dist2);
+    }
+    if (counters) count_hits(counters, found, blockIdx.x);
+    count_walks<COUNT>(counters, n_node, n_tri, n_node_s, n_tri_s);
+}
+#undef SRT_QUERY_POINTS_LDS
+#undef SRT_QUERY_POINTS_LOAD
+#undef SRT_QUERY_POINTS_FIND
+#undef SRT_QUERY_POINTS_STORE

@@ -1,4 +1,5 @@
-"""ctypes binding of the C ABI in include/srt.h and its extension headers include/srt_points.h and include/srt_nearest.h (libsrt_hip.so).
+"""ctypes binding of the C ABI in include/srt.h and its extension headers include/srt_points.h, include/srt_nearest.h and
+include/srt_signed.h (libsrt_hip.so).
 
 The product path has NO CPU fallback: if the HIP library is missing or no GPU is visible, this
 raises.  (The CPU restatement under oracle/ is test infrastructure and is never imported here.)
@@ -18,6 +19,7 @@ LIB_PATH = os.path.join(_HERE, "libsrt_hip.so")
 ABI_SYMBOLS = tuple(abi.PROTOTYPES)           # every symbol include/srt.h declares
 POINT_SYMBOLS = tuple(abi.POINT_PROTOTYPES)    # every symbol include/srt_points.h declares
 NEAREST_SYMBOLS = tuple(abi.NEAREST_PROTOTYPES)    # every symbol include/srt_nearest.h declares
+SIGNED_SYMBOLS = tuple(abi.SIGNED_PROTOTYPES)    # every symbol include/srt_signed.h declares
 MULTI_HIT_MAX = abi.SRT_MULTI_HIT_MAX
 
 _f32p, _i32p, _u8p, _u32p = C.POINTER(C.c_float), C.POINTER(C.c_int32), C.POINTER(C.c_uint8), C.POINTER(C.c_uint32)
@@ -41,7 +43,7 @@ def load(path=None):
             raise RuntimeError(f"{path or LIB_PATH} is missing: the HIP extension must be built "
                                "(python -m simple_raytracer_amd.build); there is no CPU fallback")
         L = C.CDLL(path or LIB_PATH)
-        for name, (restype, argtypes) in {**abi.PROTOTYPES, **abi.POINT_PROTOTYPES, **abi.NEAREST_PROTOTYPES}.items():
+        for name, (restype, argtypes) in {**abi.PROTOTYPES, **abi.POINT_PROTOTYPES, **abi.NEAREST_PROTOTYPES, **abi.SIGNED_PROTOTYPES}.items():
             fn = getattr(L, name)
             fn.restype, fn.argtypes = restype, argtypes
         if path is not None:
@@ -517,6 +519,35 @@ class DeviceScene:
         """srt_nearest_points_device: closest_points_device's arguments, asynchronous on `stream`, one launch."""
         self._points_device("srt_nearest_points_device", n, d_points, radius, point_mask, stream, count, (tri, dist2, point, vw, region))
 
+    def signed_points(self, points, radius=None, point_mask=None, dirs=None, parity=False, count=False,
+                      want=("sdist", "inside", "winding", "crossings", "tri", "dist2", "point", "vw", "region")):
+        """srt_signed_points (include/srt_signed.h): nearest_points' arguments and results, and per point a sign by winding along the rays
+        (point, dirs[j]): sdist n (-sqrt(dist2) inside, +sqrt(dist2) outside), inside n uint8, winding n x n_dirs int32 (exits - entries),
+        crossings n x n_dirs uint32.  dirs: n_dirs x 3 floats (1 .. 16 directions), or None = the header's three.  parity=True votes by
+        crossings & 1 instead of winding > 0.  The sign does not depend on the radius; want=("inside",) runs no nearest phase at all.
+        count=True: the sign rays' tests are stats' node_tests_shadow / tri_tests_shadow, the nearest phase's the primary pair."""
+        pts = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        n = pts.shape[0]
+        rad = None if radius is None else np.ascontiguousarray(np.broadcast_to(np.asarray(radius, np.float32).reshape(-1), (n,)), np.float32)
+        pm = None if point_mask is None else _ray_mask(point_mask, n)
+        d = None if dirs is None else np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+        nd = 3 if d is None else d.shape[0]
+        out, _ = _outputs(want, (n,), _POINT)
+        so, _ = _outputs(want, (n,), {k: (ty, tail if tail is not None else (nd,)) for k, (ty, tail) in _SIGN.items()})
+        sign = abi.Sign(None if d is None else d.ctypes.data, 0 if d is None else nd, abi.SIGN_PARITY if parity else 0)
+        po, sg = abi.PointOut(*_addresses(out, _POINT)), abi.SignOut(*_addresses(so, _SIGN))
+        return _with_stats({**so, **out}, self.L.srt_signed_points, "srt_signed_points", self.h, n, _host(pts, _f32p), _host(rad, _f32p), _host(pm, _u32p),
+                           C.byref(sign), _query_flags(count=count), C.byref(po), C.byref(sg))
+
+    def signed_points_device(self, n, d_points, radius=0, point_mask=0, dirs=0, n_dirs=0, parity=False, stream=0, count=False, sdist=0, inside=0, winding=0,
+                             crossings=0, tri=0, dist2=0, point=0, vw=0, region=0):
+        """srt_signed_points_device: raw device pointers (ints) in -- nearest_points_device's, `dirs` (n_dirs x 3 floats on the device; 0 with
+        n_dirs 0 = the header's three) and the sign outputs (winding, crossings: n x n_dirs) --, asynchronous on `stream`, one launch."""
+        sign = abi.Sign(dirs or None, n_dirs, abi.SIGN_PARITY if parity else 0)
+        po, sg = _wanted(abi.PointOut, tri, dist2, point, vw, region), _wanted(abi.SignOut, sdist, inside, winding, crossings)
+        _check(self.L.srt_signed_points_device(self.h, n, d_points, radius or None, point_mask or None, C.byref(sign), _query_flags(count=count), stream,
+                                               C.byref(po), C.byref(sg)), "srt_signed_points_device")
+
     def sync(self):
         return _with_stats({}, self.L.srt_sync, "srt_sync", self.h)["stats"]
 
@@ -555,6 +586,7 @@ _CLOSEST = {**_HIT, "bary": (np.float32, (3,))}
 _FRAME = {**_HIT, "rgb_linear": (np.float32, (3,)), "rgb8": (np.uint8, (3,))}
 _SURFACE = {k: (ty, () if c == 1 else (c,)) for k, (ty, c) in abi.SURFACE_FIELDS.items()}
 _POINT = {k: (ty, () if c == 1 else (c,)) for k, (ty, c) in abi.POINT_FIELDS.items()}
+_SIGN = {k: (ty, None if c is None else ()) for k, (ty, c) in abi.SIGN_FIELDS.items()}      # (None: one entry per direction)
 _PATH_SUMS = {"rgb_linear": (np.float32, (3,)), "rgb8": (np.uint8, (3,))}
 _PATH_SEGMENTS = {"seg_" + k: (ty, () if c == 1 else (c,)) for k, (ty, c) in abi.PATH_FIELDS.items()}
 # the rows of srt_fresnel_out as result keys: side_hit_id, side_t, side_rgb_linear, fresnel

@@ -54,7 +54,11 @@ smaller one, in one run beside srt_trace_rays_device on the rays of the same pix
 triangle tests per point from the counting build.
 --nearest: the table of --points with srt_nearest_points_device (the bound shrinks) beside srt_closest_points_device, the yardstick, on the same
 points in the same rounds at every radius; the outputs of the two are compared on the way.
-Usage: python tools/ray_query_probe.py [--reps N] [--trace] [--shade | --range | --shade-range | --multi | --surface | --paths | --shadow-rule | --masked | --refract | --fresnel | --ao | --render-ao | --points | --nearest [--rounds R]]     (--trace: few repetitions, for a run under rocprofv3 --kernel-trace --stats)"""
+--signed: srt_signed_points_device (the default table's 3 directions, parity) on the points of --nearest without a radius, beside the chain it
+replaces on the calls that existed before it, in the same rounds: srt_nearest_points_device, torch writing the n x 3 rays,
+srt_trace_rays_multi_device for n_hits alone, the vote and the sign in torch.  Equal bits are asserted.  Also srt_nearest_points_device
+alone (what the sign costs on top of it) and containment only (no nearest phase).
+Usage: python tools/ray_query_probe.py [--reps N] [--trace] [--shade | --range | --shade-range | --multi | --surface | --paths | --shadow-rule | --masked | --refract | --fresnel | --ao | --render-ao | --points | --nearest | --signed [--rounds R]]     (--trace: few repetitions, for a run under rocprofv3 --kernel-trace --stats)"""
 import argparse, os, sys, time
 import numpy as np
 import torch                                   # first: torch initialises HIP before the library does
@@ -842,8 +846,73 @@ def points_section(reps, rounds, nearest=False):
     ds.close()
 
 
+def signed_section(reps, rounds):
+    """srt_signed_points_device beside the chain of shipped calls it replaces, beside srt_nearest_points_device alone, and containment only:
+    the hit points of the 1080p frame OFFSETS units off the surface towards the camera, every STEP-th and every (16 STEP)-th as in --nearest,
+    and all of them (the one batch here that fills the machine more than once), no radius."""
+    OFFSETS, STEP = (0.25, 2.0, 16.0), 4
+    dev = torch.device("cuda", 0); torch.zeros(1, device=dev)
+    g = gu.GoldenScene("ground_bunny")
+    ds = lib.DeviceScene(g.flat)
+    side = torch.cuda.Stream(device=dev)
+    cur = side.cuda_stream
+    rays = frame_rays()
+    frame = ds.trace_rays(rays, want=("hit_id", "t"))
+    hits = np.flatnonzero(frame["hit_id"] >= 0)
+    P = rays[hits, 3:6] * frame["t"][hits, None]                      # (the origin is 0)
+    unit = rays[hits, 3:6] / np.linalg.norm(rays[hits, 3:6], axis=1, keepdims=True)
+    d_dirs = torch.from_numpy(abi.SIGN_DEFAULT_DIRS).to(dev)
+    print(f"signed distance, K3 ground_bunny {W}x{H}: {g.flat.n_tris} triangles, {g.flat.n_nodes} nodes; {hits.size} hit points; 3 directions, parity; no radius; "
+          f"{rounds} rounds of {reps} calls, forms alternating; ms a call; min / max: the spread of the rounds")
+    for step in (1, STEP, 16 * STEP):
+        sel = np.arange(0, hits.size, step)
+        n = sel.size
+        new = lambda shape, ty: torch.empty(shape, dtype=ty, device=dev)
+        s_tri, s_d2, s_pt, s_sd, s_in = new(n, torch.int32), new(n, torch.float32), new((n, 3), torch.float32), new(n, torch.float32), new(n, torch.uint8)
+        c_tri, c_d2, c_pt, c_nh, c_rays = new(n, torch.int32), new(n, torch.float32), new((n, 3), torch.float32), new((n, 3), torch.int32), new((n, 3, 6), torch.float32)
+        only = new(n, torch.uint8)
+        kept = {}
+        print(f"every {step}th hit: {n} points" if step > 1 else f"every hit: {n} points")
+        print(f"{'points':34s} {'form':34s} {'median':>8s} {'min':>8s} {'max':>8s} {'/ first':>7s}")
+        for off in OFFSETS:
+            pts = np.ascontiguousarray(P[sel] - unit[sel] * np.float32(off), np.float32)
+            d_pts = torch.from_numpy(pts).to(dev)
+            torch.cuda.synchronize()
+
+            def chain():
+                ds.nearest_points_device(n, d_pts.data_ptr(), stream=cur, tri=c_tri.data_ptr(), dist2=c_d2.data_ptr(), point=c_pt.data_ptr())
+                with torch.cuda.stream(side):
+                    c_rays[:, :, :3] = d_pts[:, None, :]
+                    c_rays[:, :, 3:] = d_dirs[None, :, :]
+                ds.trace_rays_multi_device(3 * n, c_rays.data_ptr(), 1, stream=cur, n_hits=c_nh.data_ptr())
+                with torch.cuda.stream(side):
+                    inside = 2 * (c_nh & 1).sum(1) > 3
+                    root = torch.sqrt(c_d2)
+                    kept["inside"], kept["sdist"] = inside.to(torch.uint8), torch.where(inside, -root, root)
+            forms = {
+                "chain of shipped calls": chain,
+                "signed_points, one launch": lambda: ds.signed_points_device(n, d_pts.data_ptr(), parity=True, stream=cur, tri=s_tri.data_ptr(), dist2=s_d2.data_ptr(),
+                                                                             point=s_pt.data_ptr(), sdist=s_sd.data_ptr(), inside=s_in.data_ptr()),
+                "nearest_points alone": lambda: ds.nearest_points_device(n, d_pts.data_ptr(), stream=cur, tri=c_tri.data_ptr(), dist2=c_d2.data_ptr(), point=c_pt.data_ptr()),
+                "signed_points, containment only": lambda: ds.signed_points_device(n, d_pts.data_ptr(), parity=True, stream=cur, inside=only.data_ptr()),
+            }
+            ms = rounds_of(forms, reps, rounds, side)
+            side.synchronize()
+            report(f"{off:g} off the surface", ms)
+            same = all(torch.equal(a, b) for a, b in ((s_tri, c_tri), (s_d2.view(torch.int32), c_d2.view(torch.int32)), (s_pt.view(torch.int32), c_pt.view(torch.int32)),
+                                                      (s_in, kept["inside"]), (s_sd.view(torch.int32), kept["sdist"].view(torch.int32)), (only, s_in)))
+            med = {k: float(np.median(v)) for k, v in ms.items()}
+            c = ms["chain of shipped calls"]
+            print(f"{'':34s} equal bits: {same}; inside {int(s_in.sum().item())} of {n}; the chain's own spread {(max(c) - min(c)) / med['chain of shipped calls'] * 100:.1f} % of its median; "
+                  f"the sign on top of nearest_points {med['signed_points, one launch'] - med['nearest_points alone']:.3f} ms; containment only "
+                  f"{med['signed_points, containment only'] * 1e6 / n:.1f} ns a point")
+            assert same
+    ds.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--signed", action="store_true")
     ap.add_argument("--points", action="store_true")
     ap.add_argument("--nearest", action="store_true")
     ap.add_argument("--render-ao", action="store_true", dest="render_ao")
@@ -863,6 +932,8 @@ def main():
     ap.add_argument("--rounds", type=int, default=7)
     a = ap.parse_args()
     reps = 3 if a.trace else a.reps
+    if a.signed:
+        return signed_section(reps, 2 if a.trace else a.rounds)
     if a.points or a.nearest:
         return points_section(reps, 2 if a.trace else a.rounds, nearest=a.nearest)
     if a.render_ao:
