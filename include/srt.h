@@ -140,6 +140,20 @@ typedef struct srt_params {
                                     * older or differently configured kernels; `enum Variant` in
                                     * simple_raytracer_amd/csrc/srt_hip.hip is the list of the numbers)                  */
 } srt_params;
+/* TILE SPANS.  A whole frame in the reference's ray form with 1..7 light samples (the fused pipeline, variant 0) starts trace
+ * workgroups only for the 8x8 tiles that the projection of the objects' root boxes can reach -- per tile row one span of tiles,
+ * computed on the host from the boxes of the last srt_scene_create / srt_scene_update / srt_scene_update_frame -- and the shading
+ * launch writes the background into the others: the same outputs, bit for bit.  It does not apply (every tile gets its workgroup, as
+ * before) in camera mode, to shares of a split (block_stride != 1 or block_cols != 0), with spp > 1, under SRT_FLAG_COUNT_WORK, to the
+ * frames of srt_render_device_batch, to scenes whose records take the XCD-row or packet pipelines, to a frame of more than 4096 rows, to a scene of more than 4096 objects,
+ * to a scene with a non-finite, inverted or huge (beyond 2^100) root box -- and after srt_scene_pose or srt_scene_refit_device, which
+ * change the boxes on the device only, until the next of the three uploads above.  Variant 64 is variant 0 with the spans off.
+ * A render CAPTURED into a hipGraph holds the table of the boxes it was captured with.  It therefore launches the whole grid, and its
+ * kernels skip the tiles outside the spans only while a word of the records -- rewritten in stream order by srt_scene_update,
+ * srt_scene_update_frame, srt_scene_pose and srt_scene_refit_device -- still holds the number the table was made at: a replay after any
+ * of those calls renders the new scene, without culling, until the render is captured again.  And once one of those four calls has
+ * ITSELF been captured into a graph -- its replays change the boxes with no host code running, so the host's copy of them can be stale
+ * at any time -- the scene's records (every handle that shares them) get no tile spans any more. */
 
 typedef struct srt_stats {
     uint64_t primary_rays;         /* width x owned rows x spp (of the last render)                 */

@@ -12,7 +12,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB_HIP = os.path.join(HERE, "libsrt_hip.so")
 HIP_SRC = os.path.join(CSRC, "srt_hip.hip")
 # What libsrt_hip.so, and every measurement variant of it, is compiled from: the one translation unit and the headers it includes.
-HIP_DEPS = [HIP_SRC] + [os.path.join(CSRC, f) for f in ("srt_device.h", "srt_kernels.h", "srt_packet.h", "srt_query.h")] + [os.path.join(HERE, "..", "include", f) for f in ("srt.h", "srt_points.h", "srt_nearest.h", "srt_signed.h")]
+HIP_DEPS = [HIP_SRC] + [os.path.join(CSRC, f) for f in ("srt_device.h", "srt_kernels.h", "srt_packet.h", "srt_query.h", "srt_tile_spans.h")] + [os.path.join(HERE, "..", "include", f) for f in ("srt.h", "srt_points.h", "srt_nearest.h", "srt_signed.h")]
 
 # -ffp-contract=off is part of the numerical contract: FMA contraction changes hit results
 # (SURVEY.md H1).  Correctly rounded f32 divide / sqrt are hipcc defaults and must stay on.

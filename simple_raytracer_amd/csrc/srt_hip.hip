@@ -107,6 +107,8 @@ struct Stream {
     operator hipStream_t() const { return st; }
 };
 
+struct Boxes;
+
 // The device records of a scene: owned by the handle that uploaded them and by every handle made from it with srt_scene_share.
 struct SceneRecords {
     int device = 0;
@@ -118,6 +120,18 @@ struct SceneRecords {
     bool int_shin = false;           // every object's shininess is an integer in [1, 64]: the shading kernel without the general pow
     // host copies of the static topology (srt_scene_update_frame checks counts against them and re-estimates the overlap from a frame's boxes)
     std::vector<int2> h_ranges; std::vector<int32_t> h_tri_first, h_leaf;
+    // host copy of the objects' root boxes (n_objects x 3 each): what a frame's tile spans are computed from (srt_tile_spans.h).  Valid after
+    // an upload from the host (create, update, update_frame); a pose or a refit changes the boxes on the device only and makes it invalid
+    // -- no culling -- until the next upload.  Part of the records: every handle of srt_scene_share sees the one truth.
+    std::vector<float> h_root_min, h_root_max; bool root_boxes_valid = false;
+    // The box epoch: a number that every upload, pose and refit of these records raises, and the same number in a word of device memory,
+    // written in stream order by the call that changes the boxes.  A frame's tile spans carry the epoch they were made at; a launch
+    // captured into a graph compares it with the word at every replay (srt_kernels.h, trace_nq_body) and culls nothing once they differ.
+    uint32_t box_epoch = 1; uint32_t* d_box_epoch = nullptr;
+    // One of those calls was CAPTURED into a graph: its replays change the boxes on the device with no host code running, so the host
+    // copy can be stale at any time from then on, whatever is uploaded later.  Sticky: these records never get tile spans again.
+    bool boxes_change_in_replays = false;
+    void note_root_boxes(const struct Boxes& box, const int2* ranges, uint32_t n_objects);
     // f1, device half: node -> DevWide index (static), this frame's inputs, the per-triangle attributes in source order
     int32_t* d_widx = nullptr; float4* d_src_points = nullptr; uint32_t* d_order = nullptr; float* d_box_min = nullptr; float* d_box_max = nullptr;
     float* d_src_tc = nullptr; float* d_src_nrm = nullptr; int32_t* d_src_tex = nullptr; bool have_source = false;
@@ -384,6 +398,13 @@ struct Boxes {
     }
 };
 
+void SceneRecords::note_root_boxes(const Boxes& box, const int2* ranges, uint32_t n_objects) {
+    root_boxes_valid = false;
+    h_root_min.resize(3 * (size_t)n_objects); h_root_max.resize(3 * (size_t)n_objects);
+    for (uint32_t k = 0; k < n_objects; k++) box((size_t)ranges[k].x, h_root_min.data() + 3 * k, h_root_max.data() + 3 * k);
+    root_boxes_valid = true;
+}
+
 // the union of the objects' root boxes, in a node's box layout (min.xyz max.x | max.yz 0 0): what a tile's rays are tested against
 // before the roots themselves in scenes of several objects (srt_kernels.h background_test_wave)
 static void union_of_roots(const Boxes& box, const int2* ranges, uint32_t n_objects, float* out8) {
@@ -591,6 +612,7 @@ static void note_records(SceneRecords& r, const srt_scene_desc* d, const RecordL
     r.overlap = overlap_estimate(Boxes(nodes), r.h_leaf.data(), d->n_nodes, ranges, d->n_objects);
     r.prefer_packet = r.overlap > PACKET_OVERLAP_THRESHOLD;
     r.int_shin = all_integer_shininess(d->obj_material, d->n_objects);
+    r.note_root_boxes(Boxes(nodes), ranges, d->n_objects);
     r.have_source = false;               // attributes in source order belong to the previous contents
     r.have_pose = false;                 // ... and so do the pose source's order and the refit's schedule
     r.have_refit = r.have_refit_index = false;
@@ -639,6 +661,8 @@ static int scene_create_impl(int device, const srt_scene_desc* d, srt_scene** ou
     }
     s->dev.n_nodes = d->n_nodes; s->dev.n_tris = d->n_tris; s->dev.n_objects = d->n_objects;
     s->n_textures = d->n_textures; s->has_tex = any_tex;
+    HIP_TRY(r.make((void**)&r.d_box_epoch, sizeof(uint32_t)));
+    HIP_TRY(hipMemcpy(r.d_box_epoch, &r.box_epoch, sizeof(uint32_t), hipMemcpyHostToDevice));
     HIP_TRY(init_handle_state(s.get()));
     *out = s.release();
     return SRT_OK;
@@ -667,6 +691,8 @@ int srt_scene_create(int device, const srt_scene_desc* d, srt_scene** out) {
 }
 
 // The scene's own stream: srt_render / srt_render_async / srt_scene_update(stream = NULL) are ordered on it.
+static void bump_box_epoch(srt_scene* s, hipStream_t stream);
+
 static int own_stream(srt_scene* s, hipStream_t* out) {
     if (!s->stream) HIP_TRY(hipStreamCreateWithFlags(&s->stream.st, hipStreamNonBlocking));
     *out = s->stream;
@@ -725,11 +751,23 @@ static int scene_update_impl(srt_scene* s, const srt_scene_desc* d, hipStream_t 
         HIP_TRY(hipMemcpyAsync(*a.dev, h + a.off, a.bytes(), hipMemcpyHostToDevice, stream));
     }
     HIP_TRY(hipEventRecord(s->staged, stream));
+    bump_box_epoch(s, stream);
     if (tex_changed) r.tex_hash = tex_hash_new;
     note_records(r, d, l, h);
     return SRT_OK;
 }
 
+// Raises the records' box epoch and writes it to the device word in stream order (SceneRecords::box_epoch).  A call captured into a
+// graph writes, at every replay, the number it was captured with: never a number that a table made from the host copy carries after it,
+// since every later upload has a higher one.
+static void bump_box_epoch(srt_scene* s, hipStream_t stream) {
+    SceneRecords& r = *s->rec;
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(stream, &cs) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusActive; }      // (not known: as if it were)
+    if (cs != hipStreamCaptureStatusNone) r.boxes_change_in_replays = true;
+    r.box_epoch++;
+    hipLaunchKernelGGL(k_set_box_epoch, dim3(1), dim3(64), 0, stream, r.d_box_epoch, r.box_epoch);
+}
 // ---- f1, device half -------------------------------------------------------------------------------------------------------------
 static int scene_set_source_impl(srt_scene* s, const float* tri_texcoord, const float* tri_normals, const int32_t* tri_tex) {
     if (!s) return SRT_ERR_ARG;
@@ -799,11 +837,13 @@ static int scene_update_frame_impl(srt_scene* s, const srt_frame_geometry* g, hi
                        const_cast<DevNode*>(s->dev.nodes), const_cast<DevWide*>(s->dev.wide), (const int32_t*)r.d_widx);
     hipLaunchKernelGGL(k_update_roots, dim3((nO + 63) / 64), dim3(64), 0, stream, nO, s->dev.obj_range, (const float*)r.d_box_min, (const float*)r.d_box_max,
                        s->dev.nodes, const_cast<DevNode*>(s->dev.root_nodes));
+    bump_box_epoch(s, stream);
     HIP_TRY(hipGetLastError());
     r.have_pose = false;                                        // another visit order: the pose source is no longer these triangles
     r.have_refit = r.have_refit_index = false;                  // ... nor are the refit's indices
     r.overlap = overlap_estimate(boxes, r.h_leaf.data(), (uint32_t)nN, r.h_ranges.data(), nO);      // expected slab tests per ray, from this frame's boxes
     r.prefer_packet = r.overlap > PACKET_OVERLAP_THRESHOLD;
+    r.note_root_boxes(boxes, r.h_ranges.data(), nO);
     return SRT_OK;
 }
 
@@ -857,10 +897,12 @@ static int refit_schedule_upload(srt_scene* s, const RefitSchedule& c) {
 }
 
 // Everything behind the per-triangle launch of a pose or a refit: the boxes from the triangles' own boxes up to the roots, into the
-// 32 B, 64 B and root records, and the scene box.  Five launches.
+// 32 B, 64 B and root records, and the scene box.  Five launches and the one store of the records' box epoch (bump_box_epoch).
 static void enqueue_refit_boxes(srt_scene* s, hipStream_t stream) {
     SceneRecords& r = *s->rec;
     const uint32_t nO = s->dev.n_objects; const size_t nN = s->dev.n_nodes;
+    r.root_boxes_valid = false;      // the root boxes change on the device only: no tile spans until the next upload from the host
+    bump_box_epoch(s, stream);
     hipLaunchKernelGGL(k_pose_boxes, dim3(r.n_sub), dim3(128), 0, stream, (const int32_t*)r.d_sub_root, s->dev.nodes, (const uint8_t*)r.d_height,
                        (const float2*)r.d_tri_box, r.d_box_min, r.d_box_max);
     hipLaunchKernelGGL(k_pose_top, dim3(nO), dim3(256), 0, stream, (const int32_t*)r.d_top_off, (const int32_t*)r.d_top_nodes, s->dev.nodes,
@@ -894,7 +936,7 @@ int srt_scene_set_pose_source(srt_scene* s, const float* tri_points) {
     return guarded([&] { return scene_set_pose_source_impl(s, tri_points); });
 }
 
-// Per frame the host copies 64 bytes an object (+ 24 for colours and materials) into the staging block and enqueues six launches; it
+// Per frame the host copies 64 bytes an object (+ 24 for colours and materials) into the staging block and enqueues seven launches (the seventh a single store, the records' box epoch); it
 // neither looks at a triangle or a node nor waits for the device (but for the staging block's previous use, as srt_scene_update_frame).
 static int scene_pose_impl(srt_scene* s, uint32_t n_objects, const float* obj_matrix, const float* obj_color, const float* obj_material, hipStream_t stream) {
     if (!s || !obj_matrix) return SRT_ERR_ARG;
@@ -992,7 +1034,7 @@ static void launch_refit_tris(srt_scene* s, const srt_refit_desc* g, hipStream_t
                            const_cast<DevTri*>(s->dev.tris), const_cast<DevTriO*>(s->dev.tris_o), r.d_tri_box, (float*)nullptr);
 }
 
-// Per frame: six launches and nothing else -- no allocation, no copy, no staging, no look at a triangle or a node, no wait.
+// Per frame: seven launches (the seventh a single store, the records' box epoch) and nothing else -- no allocation, no copy, no staging, no look at a triangle or a node, no wait.
 static int scene_refit_device_impl(srt_scene* s, const srt_refit_desc* g, hipStream_t stream) {
     if (!s || !g || !g->d_points) return SRT_ERR_ARG;
     if (g->stride != 3 && g->stride != 4) return SRT_ERR_ARG;
@@ -1096,6 +1138,7 @@ enum Variant : uint32_t {
     V_FUSED_FOUR_WAVES = 59,      // shipped choice, the fused kernel as four waves of 4x4 pixels per tile where the half-tile form would run
     V_SHADOW_PLAIN_ROWS = 62,     // shipped choice, the node-queue shadow kernel in plain tile order where XCD rows are on
     V_EXACT_TONE = 63,            // shipped choice, every pixel's tone map by the exact functions (no f32 filter: EXP_EXACT_TONE)
+    V_FULL_GRID = 64,             // 0 in everything (batch hold-back, heavy lists, camera build included) but the tile spans: off, every tile gets its workgroup
 };
 // Numbers without a name keep two fallbacks: 7..9 run the unfused node-queue chain of the shipped kernels, any other number a
 // configuration of the fused kernel (the shipped one) at every sample count.
@@ -1119,6 +1162,8 @@ using TraceShadeFn = decltype(&k_trace_shade_nq<512, true, 6, 16>);
 using ShadowPkFn = decltype(&k_shadow_pk<false, true, false>);
 using ShadowNqFn = decltype(&k_shadow_nq<false, 512, true, 16, 6>);
 using ShadeTileFn = decltype(&k_shade_tile<0>);
+using TraceSpansFn = decltype(&k_trace_nq_spans<512, true, 7, 16>);
+using ShadeTileSpansFn = decltype(&k_shade_tile_spans<0>);
 
 // CONSTRAINT on plan_frame and the batch launches below: every kernel is named in a chain of plain assignments, in this order.  The
 // compiler emits the instantiations in the order it meets them, and ?: chains are met last operand first: reordering the statements
@@ -1133,19 +1178,23 @@ enum Hold { HOLD_NONE, HOLD_FUSED, HOLD_PK };                       // the two c
 struct SceneFacts {
     bool prefer_packet, int_shin, normals; double overlap; uint64_t bytes; uint32_t n_cu;
     uint32_t heavy_steps, pk_units, pk_take;      // SRT_HEAVY_STEPS, SRT_PK_UNITS, SRT_PK_TAKE (read once per process)
+    // the host copy of the root boxes (n_objects x 3 floats each) where it is valid, else null: what the tile spans are made from
+    uint32_t n_objects; const float* root_min; const float* root_max; uint32_t box_epoch;
 };
 static SceneFacts scene_facts(const srt_scene* s) {
     static const auto env = [](const char* name, uint32_t dflt) { const char* e = std::getenv(name); return e ? (uint32_t)std::strtoul(e, nullptr, 10) : dflt; };
     static const uint32_t heavy_steps = env("SRT_HEAVY_STEPS", 64u);      // walks of this many node steps make a quadrant a heavy one (0 = off)
     static const uint32_t pk_units = env("SRT_PK_UNITS", 64u), pk_take = env("SRT_PK_TAKE", 4u);
+    const bool boxes_known = s->rec->root_boxes_valid && !s->rec->boxes_change_in_replays;
     return SceneFacts{s->rec->prefer_packet, s->rec->int_shin, s->dev.tri_normals != nullptr, s->rec->overlap, s->bytes, (uint32_t)s->n_cu,
-                      heavy_steps, pk_units, pk_take};
+                      heavy_steps, pk_units, pk_take, s->dev.n_objects,
+                      boxes_known ? s->rec->h_root_min.data() : nullptr, boxes_known ? s->rec->h_root_max.data() : nullptr, s->rec->box_epoch};
 }
 
 // Every check of a render's arguments: before any state of the handle changes (counter sets, pending work).
 static int check_frame(const SceneFacts& f, const srt_params* p) {
     if (!p || !p->width || !p->height || !p->block_rows || !p->block_stride) return SRT_ERR_ARG;
-    const uint32_t v = variant_of(p);
+    const uint32_t v = variant_of(p) == V_FULL_GRID ? (uint32_t)V_SHIPPED : variant_of(p);
     if (p->ray_matrix && v != V_SHIPPED && v != V_PK_PK && v != V_CAMERA_PK) return SRT_ERR_ARG;      // camera mode: shipped pipelines only
     if (p->n_lights && !p->light_pos) return SRT_ERR_ARG;
     if (p->block_cols && ((p->block_cols & 7u) || (p->block_rows & 7u) || p->block_first >= p->block_stride)) return SRT_ERR_ARG;   // tiles of whole 8x8 pixel blocks
@@ -1187,12 +1236,18 @@ struct FramePlan {
     bool quadrants_consumed = false;              // the closest-hit kernel fills the quadrant list only for a consumer
     Hold hold = HOLD_NONE;                        // held back for the batch call's launches: no stage kernel is set
     char pipeline[96] = "";                       // srt_scene_pipeline
+    // the frame's tile spans (srt_tile_spans.h).  on: trace_spans and shade_tile_spans take the places of trace and shade_tile -- the same
+    // bodies with the table as their last argument --, grid_hit is (widest span, live tile rows), and the shading launch fills the tiles
+    // outside the spans with background
+    TileSpans spans{}; TraceSpansFn trace_spans = nullptr; ShadeTileSpansFn shade_tile_spans = nullptr;
+    dim3 grid_hit_full;                           // with spans: the frame's whole grid, which a launch that is being captured into a graph keeps
 };
 
 // Decides a render: touches nothing, calls nothing of HIP.  p has passed check_frame and owns at least one row.
 static FramePlan plan_frame(const SceneFacts& f, const srt_params* p, BatchState batch) {
     FramePlan pl;
-    const uint32_t v = variant_of(p), L = p->n_lights, wl = srt_cols_owned(p), rows = srt_rows_owned(p);
+    const bool full_grid = variant_of(p) == V_FULL_GRID;
+    const uint32_t v = full_grid ? (uint32_t)V_SHIPPED : variant_of(p), L = p->n_lights, wl = srt_cols_owned(p), rows = srt_rows_owned(p);
     const bool count = (p->flags & SRT_FLAG_COUNT_WORK) != 0, in_flight = (p->flags & SRT_FLAG_FRAMES_IN_FLIGHT) != 0, cam = p->ray_matrix != nullptr, shipped = shipped_choice(v);
     const dim3 grid16((wl + 15) / 16, (rows + 15) / 16), grid8((wl + 7) / 8, (rows + 7) / 8);      // grid8: 8x8 pixels per workgroup, 4 waves x (4x4 pixels)
     const auto xcd_pad = [](uint32_t y) { return (y + 7) / 8 * 8; };      // whole tile rows per XCD: y padded to 8 rows
@@ -1350,6 +1405,22 @@ static FramePlan plan_frame(const SceneFacts& f, const srt_params* p, BatchState
     // stage 3
     if (pl.trace_shade) { std::snprintf(pl.pipeline, sizeof(pl.pipeline), "k_trace_shade_nq"); return pl; }
     if (f.int_shin && v != V_GENERAL_SHADE) pl.shade_tile = &k_shade_tile<1>; else pl.shade_tile = &k_shade_tile<0>;
+    // Tile spans: the shipped fused frame only, whole and in the reference's ray form -- the kernels' tile arithmetic under a camera
+    // matrix, the XCD-row deal, column tiles and scanline blocks of a split is not the table's, a counting build counts every tile, a
+    // supersampled frame moves its rays, and the frames of a batch call keep their one grid.  Not the 8+-sample pipelines: their
+    // shadow kernels run between the closest-hit launch and the shading and read the hit id of every tile.
+    if (pl.trace && v == V_SHIPPED && !full_grid && !cam && !count && !pl.xcd_rows && !p->block_cols && p->block_stride == 1 && p->block_first == 0 &&
+        p->spp == 1 && batch == NOT_BATCHED && f.root_min && wl == p->width && rows == p->height &&
+        tile_spans(f.root_min, f.root_max, f.n_objects, p->width, p->height, (int)(-(float)p->width / 2), (int)(-(float)p->height / 2), p->focal, &pl.spans))
+    {
+        pl.spans.epoch = f.box_epoch;
+        if (pl.block_hit == 128) pl.trace_spans = &k_trace_nq_half_spans<512, true, 7, 16>; else pl.trace_spans = &k_trace_nq_spans<512, true, 7, 16>;
+        if (pl.shade_tile == &k_shade_tile<1>) pl.shade_tile_spans = &k_shade_tile_spans<1>; else pl.shade_tile_spans = &k_shade_tile_spans<0>;
+        pl.grid_hit_full = grid8;
+        pl.grid_hit = dim3(tile_spans_max_n(pl.spans), pl.spans.n_rows);
+    } else {
+        pl.spans.on = 0u;
+    }
     std::snprintf(pl.pipeline, sizeof(pl.pipeline), "%s%s+k_shade_tile", fused ? "k_trace_nq" : (pk_closest ? "k_closest_hit_pk" : "k_closest_hit_nq"),
                   fused || !L ? "" : (pk_shadow ? "+k_shadow_pk" : "+k_shadow_nq"));
     return pl;
@@ -1390,10 +1461,22 @@ struct BatchCollector {
 static int launch_stages(srt_scene* s, const FramePlan& pl, const FrameParams& fp, hipStream_t stream, int32_t* o_hit, float* o_t, float* o_lin, uint8_t* o_rgb8, unsigned long long* ctr, unsigned long long* zero_next, hipEvent_t* ev) {
     const dim3 block(256), block_hit(pl.block_hit);
     uint32_t* const ql = pl.quadrants_consumed ? s->ws_qlist.p : nullptr, * const ql_cnt = pl.quadrants_consumed ? s->d_qcount.p : nullptr;
+    // Tile spans in a launch that is being captured into a graph: the replay may come after the boxes have changed, so the launch keeps
+    // the whole grid and the kernels cull only while the records' epoch word is the table's (srt_kernels.h, trace_nq_body)
+    const TileSpans* spans = &pl.spans; TileSpans spans_whole; const uint32_t* box_epoch = nullptr; dim3 grid_hit = pl.grid_hit;
+    if (pl.trace_spans) {
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(stream, &cs) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusActive; }      // (not known: as if it were)
+        if (cs != hipStreamCaptureStatusNone) {
+            spans_whole = tile_spans_from_row_zero(pl.spans); spans = &spans_whole;
+            box_epoch = s->rec->d_box_epoch; grid_hit = pl.grid_hit_full;
+        }
+    }
     if (pl.ref_hit)          hipLaunchKernelGGL(pl.ref_hit, pl.grid_hit, block, 0, stream, s->dev, fp.hit, o_hit, o_t, ctr);
     else if (pl.q_hit)       hipLaunchKernelGGL(pl.q_hit, pl.grid_hit, block, 0, stream, s->dev, fp.hit, o_hit, o_t, o_lin, o_rgb8, ctr);
     else if (pl.nq_hit)      hipLaunchKernelGGL(pl.nq_hit, pl.grid_hit, block, 0, stream, s->dev, fp.hit, o_hit, o_t, o_lin, o_rgb8, ctr, ql_cnt, ql, s->qcap);
     else if (pl.pk_hit)      hipLaunchKernelGGL(pl.pk_hit, pl.grid_hit, block, 0, stream, s->dev, fp.hit, o_hit, o_t, o_lin, o_rgb8, ql_cnt, ql, s->qcap, ctr);
+    else if (pl.trace_spans) hipLaunchKernelGGL(pl.trace_spans, grid_hit, block_hit, 0, stream, s->dev, fp.hit, o_hit, o_t, o_lin, o_rgb8, s->ws_shadow, ctr, box_epoch, *spans);
     else if (pl.trace)       hipLaunchKernelGGL(pl.trace, pl.grid_hit, block_hit, 0, stream, s->dev, fp.hit, o_hit, o_t, o_lin, o_rgb8, s->ws_shadow, ctr);
     else                     hipLaunchKernelGGL(pl.trace_shade, pl.grid_hit, block, 0, stream, s->dev, fp.hit, o_hit, o_t, o_lin, o_rgb8, ctr, zero_next, s->d_qcount);
     HIP_TRY(hipGetLastError());
@@ -1403,6 +1486,7 @@ static int launch_stages(srt_scene* s, const FramePlan& pl, const FrameParams& f
     if (pl.shadow_pk || pl.shadow_nq) HIP_TRY(hipGetLastError());
     if (ev) HIP_TRY(hipEventRecord(ev[2], stream));
     if (pl.ref_shade)        hipLaunchKernelGGL(pl.ref_shade, pl.grid_shade, block, 0, stream, s->dev, fp.shade, o_hit, o_t, o_lin, o_rgb8, ctr, zero_next);
+    else if (pl.shade_tile_spans) hipLaunchKernelGGL(pl.shade_tile_spans, pl.grid_shade, block, 0, stream, s->dev, fp.shade, o_hit, o_t, s->ws_shadow, o_lin, o_rgb8, zero_next, s->d_qcount, ctr, box_epoch, *spans);
     else if (pl.shade_tile)  hipLaunchKernelGGL(pl.shade_tile, pl.grid_shade, block, 0, stream, s->dev, fp.shade, o_hit, o_t, s->ws_shadow, o_lin, o_rgb8, zero_next, s->d_qcount, ctr);
     if (pl.ref_shade || pl.shade_tile) HIP_TRY(hipGetLastError());
     std::snprintf(s->pipeline, sizeof(s->pipeline), "%s", pl.pipeline);

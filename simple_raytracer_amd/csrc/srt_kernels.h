@@ -5,6 +5,7 @@
 #include <type_traits>
 
 #include "srt_device.h"
+#include "srt_tile_spans.h"
 
 using namespace srt;
 
@@ -1647,7 +1648,34 @@ template <bool COUNT, int NQCAP, bool FILTER, int RS, bool XCD_ROWS, bool ROOTS_
 __device__ __forceinline__ void trace_nq_body(const DevScene& s, const DevParams& p, int32_t* __restrict__ hit_id, float* __restrict__ t_out,
                                               float* __restrict__ rgb_linear, uint8_t* __restrict__ rgb8,
                                               unsigned long long* __restrict__ shadow_bits, unsigned long long* __restrict__ counters,
-                                              unsigned long long* __restrict__ counters_next = nullptr, uint32_t* __restrict__ qcount = nullptr) {
+                                              unsigned long long* __restrict__ counters_next = nullptr, uint32_t* __restrict__ qcount = nullptr,
+                                              const TileSpans* spans = nullptr,      // the frame's tile spans (k_trace_nq_spans, k_trace_nq_half_spans); null: the kernel has none
+                                              const uint32_t* __restrict__ box_epoch = nullptr) {      // with spans, a launch captured into a graph: the records' box epoch word (below)
+    // Tile spans (the _spans kernels, launched only with a table that is on): the grid is (widest span, live tile rows), and a workgroup
+    // beyond its row's span leaves before it touches LDS or a barrier.  The two words this takes -- row0 and the row's span, which is
+    // indexed by blockIdx.y itself -- are requested together and waited for once (the empty asm keeps both loads in front of the branch).
+    // A launch that is being CAPTURED into a graph (box_epoch non-null) may be replayed after the boxes have changed, with the table of
+    // the boxes it was captured with in its arguments.  It keeps the full grid; a workgroup outside the spans leaves only if the records'
+    // epoch word -- rewritten in stream order by every upload, pose and refit -- still is the table's, and otherwise does a tile's whole
+    // work, as k_shade_tile_spans then shades every tile.  A workgroup inside the spans never reads the word.
+    uint32_t span_bx = blockIdx.x, span_by = blockIdx.y; bool span_on = false;
+    if (spans) {
+        if (!box_epoch) {
+            uint32_t row0 = spans->row0;
+            uint32_t sp = reinterpret_cast<const uint32_t*>(spans->row)[blockIdx.y < TILE_SPAN_ROWS ? blockIdx.y : TILE_SPAN_ROWS - 1u];      // x0 | n << 16
+            asm volatile("" : "+s"(sp), "+s"(row0));
+            if (blockIdx.x >= (sp >> 16)) return;
+            span_on = true;
+            span_by = row0 + blockIdx.y;
+            span_bx = (sp & 0xffffu) + blockIdx.x;
+        } else {      // (the host hands a captured launch a table whose rows count from tile row 0: row0 == 0, again no load waits for another)
+            uint32_t sp = reinterpret_cast<const uint32_t*>(spans->row)[blockIdx.y < TILE_SPAN_ROWS ? blockIdx.y : TILE_SPAN_ROWS - 1u];
+            uint32_t n_rows = spans->n_rows;
+            asm volatile("" : "+s"(sp), "+s"(n_rows));
+            const bool outside = blockIdx.y >= n_rows || blockIdx.x - (sp & 0xffffu) >= (sp >> 16);
+            if (outside && *box_epoch == spans->epoch) return;
+        }
+    }
     __shared__ uint32_t fin_count;
     __shared__ int32_t fin_id[64];
     __shared__ float fin_t[64];
@@ -1670,8 +1698,8 @@ __device__ __forceinline__ void trace_nq_body(const DevScene& s, const DevParams
     // XCD gets whole rows of tiles -- XCD j walks tile rows j, j + 8, ... left to right -- so that neighbouring tiles, which
     // read the same nodes and triangles, hit in the same L2: 1 M-triangle soup -15 %.  For a scene of a few MB the plain
     // order is as good or slightly better (K3: +1 % with the row deal, +2 % with a run-time switch), so it has its own build.
-    const uint32_t gx = gridDim.x;
-    uint32_t bx = blockIdx.x, by = ROW_Z ? blockIdx.z : blockIdx.y;      // ROW_Z: a batch launched with the tile row in z and the frame in y
+    const uint32_t gx = span_on ? (p.W + 7u) / 8u : gridDim.x;      // tiles per row of the FRAME: the shadow words and the quadrant list are indexed by tile
+    uint32_t bx = span_bx, by = ROW_Z ? blockIdx.z : span_by;      // ROW_Z: a batch launched with the tile row in z and the frame in y
     if (XCD_ROWS) {
         const uint32_t w = blockIdx.y * gx + blockIdx.x, idx = w >> 3;
         by = (idx / gx) * 8u + (w & 7u); bx = idx % gx;
@@ -1710,7 +1738,7 @@ __device__ __forceinline__ void trace_nq_body(const DevScene& s, const DevParams
     SRT_STAMP(kb);
     shadow_phase<COUNT, NQCAP, FILTER, RS, true, WIDE, P>(s, p, nq_all[wave], tq_all[wave], *L, id, t, d, shadow_bits, counters, bx, by, gx, wave);
 #ifdef SRT_DIAG
-    SRT_STAMP(k1); diag_tile_record(rgb_linear, blockIdx.x, blockIdx.y, gridDim.x, k0, k1, ka, kb);
+    SRT_STAMP(k1); diag_tile_record(rgb_linear, bx, by, gx, k0, k1, ka, kb);
 #endif
     if (SHADE) {
         const uint32_t lane = threadIdx.x & 63;
@@ -1744,6 +1772,23 @@ __global__ __launch_bounds__(128, MINW) void k_trace_nq_half(DevScene s, DevPara
                                                        float* __restrict__ rgb_linear, uint8_t* __restrict__ rgb8,
                                                        unsigned long long* __restrict__ shadow_bits, unsigned long long* __restrict__ counters) {
     trace_nq_body<false, NQCAP, FILTER, RS, false, false, false, false, false, false, true>(s, p, hit_id, t_out, rgb_linear, rgb8, shadow_bits, counters);
+}
+// The same two kernels over a frame's tile spans (srt_tile_spans.h): grid (widest span, live tile rows), the table by value behind the
+// other arguments.  Kernels of their own, so that a frame without a table runs the kernels above untouched: even one more scalar load in
+// front of a wave's first instructions shows in the frame ("Tile spans").
+template <int NQCAP, bool FILTER, int MINW, int RS>
+__global__ __launch_bounds__(256, MINW) void k_trace_nq_spans(DevScene s, DevParams p, int32_t* __restrict__ hit_id, float* __restrict__ t_out,
+                                                        float* __restrict__ rgb_linear, uint8_t* __restrict__ rgb8,
+                                                        unsigned long long* __restrict__ shadow_bits, unsigned long long* __restrict__ counters,
+                                                        const uint32_t* __restrict__ box_epoch, const TileSpans spans) {
+    trace_nq_body<false, NQCAP, FILTER, RS, false, false>(s, p, hit_id, t_out, rgb_linear, rgb8, shadow_bits, counters, nullptr, nullptr, &spans, box_epoch);
+}
+template <int NQCAP, bool FILTER, int MINW, int RS>
+__global__ __launch_bounds__(128, MINW) void k_trace_nq_half_spans(DevScene s, DevParams p, int32_t* __restrict__ hit_id, float* __restrict__ t_out,
+                                                             float* __restrict__ rgb_linear, uint8_t* __restrict__ rgb8,
+                                                             unsigned long long* __restrict__ shadow_bits, unsigned long long* __restrict__ counters,
+                                                             const uint32_t* __restrict__ box_epoch, const TileSpans spans) {
+    trace_nq_body<false, NQCAP, FILTER, RS, false, false, false, false, false, false, true>(s, p, hit_id, t_out, rgb_linear, rgb8, shadow_bits, counters, nullptr, nullptr, &spans, box_epoch);
 }
 // closest hit, shadow rays and shading of a frame in one launch (SHADE)
 template <int NQCAP, bool FILTER, int MINW, int RS, bool XCD_ROWS = false>
@@ -1817,13 +1862,29 @@ __global__ __launch_bounds__(256, MINW) void k_trace_nq_batch(const FrameTab tab
 // phongIllumination:144-200, quantiser :447-449, black -> background (:518, drawImage:476-487).
 // Pure ALU, no traversal; misses were finished by the closest-hit kernel.
 // =================================================================================================
-template <bool INT_SHIN = false>
-__device__ __forceinline__ void shade_tile_body(const DevScene& s, const DevParams& p, const int32_t* __restrict__ hit_id,
-                                                const float* __restrict__ t_in,
+// SPANS: the kernel takes the frame's tile spans (k_shade_tile_spans), and then WRITES hit_id and t of the tiles outside them: HIT and T are
+// its plain pointers there, the read-only restrict pointers of every other kernel otherwise
+template <bool INT_SHIN = false, bool SPANS = false, typename HIT = const int32_t* __restrict__, typename T = const float* __restrict__>
+__device__ __forceinline__ void shade_tile_body(const DevScene& s, const DevParams& p, HIT hit_id,
+                                                T t_in,
                                                 const unsigned long long* __restrict__ shadow_bits,
                                                 float* __restrict__ rgb_linear, uint8_t* __restrict__ rgb8,
                                                 unsigned long long* __restrict__ counters_next, uint32_t* __restrict__ qcount,
-                                                unsigned long long* __restrict__ counters) {
+                                                unsigned long long* __restrict__ counters, const TileSpans* spans = nullptr,
+                                                const uint32_t* __restrict__ box_epoch = nullptr) {
+    // Tile spans on and this wave's tile outside them (wave-uniform): the trace launch never started a workgroup for it.  The wave writes
+    // what background_test_wave writes for a tile no ray of which passes a root box, reads nothing, and counts as a wave of zero hits below.
+    // (The tile's shadow words stay unwritten: they are only ever read for a pixel with a hit.)  Decided first, so that the two dependent
+    // scalar loads are under way while the workgroup meets at its barrier.
+    bool outside = false;
+    if constexpr (SPANS) {
+        const uint32_t w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+        const uint32_t tx = blockIdx.x * 2u + (w & 1u), rel = blockIdx.y * 2u + (w >> 1) - spans->row0;      // rel: the tile row, counted from row0
+        outside = rel >= spans->n_rows;
+        if (!outside) { const TileSpan sp = spans->row[rel]; outside = tx - sp.x0 >= sp.n; }
+        // a captured launch (trace_nq_body): the table is only as good as its epoch -- if the boxes have changed, the trace launch did every tile
+        if (outside && box_epoch && *box_epoch != spans->epoch) outside = false;
+    }
     __shared__ uint32_t wg_hits, wg_done;
     if (threadIdx.x == 0) { wg_hits = 0u; wg_done = 0u; }
     __syncthreads();
@@ -1837,7 +1898,12 @@ __device__ __forceinline__ void shade_tile_body(const DevScene& s, const DevPara
     uint32_t px, r;
     const bool live = tile_pixel(p, px, r);
     const size_t pix = (size_t)r * p.W + px;
-    const int32_t id = live ? hit_id[pix] : -1;
+    if constexpr (SPANS) if (outside && live) {
+        hit_id[pix] = -1;
+        t_in[pix] = __builtin_inff();
+        store_miss(rgb_linear, rgb8, pix, p.bg);
+    }
+    const int32_t id = (SPANS ? live && !outside : live) ? hit_id[pix] : -1;
     const size_t tile_index = (size_t)(blockIdx.y * 2 + (wave >> 1)) * ((p.W + 7) / 8) + blockIdx.x * 2 + (wave & 1);   // 8x8 tile
     // The frame's hit statistic, here, where the launch overlaps the next frame's tracing.  The closest-hit phase used to add one global
     // atomic per 4x4 quadrant with hits (56 k a K3 frame): 4 % of the trace launch; one per 8x8 tile here (14 k) still made this launch
@@ -1881,6 +1947,17 @@ __global__ __launch_bounds__(256, INT_SHIN ? 8 : 1) void k_shade_tile(DevScene s
                                                     unsigned long long* __restrict__ counters) {
     shade_tile_body<INT_SHIN != 0>(s, p, hit_id, t_in, shadow_bits, rgb_linear, rgb8, counters_next, qcount, counters);
 }
+// k_shade_tile behind k_trace_nq_spans / k_trace_nq_half_spans: a wave whose tile lies outside the frame's spans writes the background
+template <int INT_SHIN>
+__global__ __launch_bounds__(256, INT_SHIN ? 8 : 1) void k_shade_tile_spans(DevScene s, DevParams p, int32_t* hit_id,
+                                                          float* t_in,      // (both read AND written: no const, no restrict)
+                                                          const unsigned long long* __restrict__ shadow_bits,
+                                                          float* __restrict__ rgb_linear, uint8_t* __restrict__ rgb8,
+                                                          unsigned long long* __restrict__ counters_next, uint32_t* __restrict__ qcount,
+                                                          unsigned long long* __restrict__ counters, const uint32_t* __restrict__ box_epoch,
+                                                          const TileSpans spans) {
+    shade_tile_body<INT_SHIN != 0, true, int32_t*, float*>(s, p, hit_id, t_in, shadow_bits, rgb_linear, rgb8, counters_next, qcount, counters, &spans, box_epoch);
+}
 template <int INT_SHIN>
 __global__ __launch_bounds__(256, INT_SHIN ? 8 : 1) void k_shade_tile_batch(const FrameTab tab) {      // the shading of the frames k_trace_nq_batch traced
     const FrameItem& it = tab.it[blockIdx.z];
@@ -1896,6 +1973,9 @@ __global__ __launch_bounds__(256, INT_SHIN ? 8 : 1) void k_shade_tile_batch(cons
 __device__ __forceinline__ bool resolve_live(const DevParams& p, uint32_t i) {
     return !p.col_block || pixel_live(p, i % p.W, i / p.W);
 }
+// the records' box epoch word (SceneRecords::d_box_epoch): written in stream order by whatever changes the boxes on the device
+__global__ void k_set_box_epoch(uint32_t* __restrict__ word, uint32_t value) { if (threadIdx.x == 0 && blockIdx.x == 0) *word = value; }
+
 __global__ __launch_bounds__(256) void k_accumulate(DevParams p, float* __restrict__ acc, const float* __restrict__ sub, uint32_t n, int first) {
     const uint32_t i = blockIdx.x * 256 + threadIdx.x;
     if (i < n && resolve_live(p, i / 3u)) acc[i] = first ? sub[i] : acc[i] + sub[i];
