@@ -1147,4 +1147,5 @@ uint32_t    srt_abi_version(void);
 #include "srt_points.h"
 #include "srt_nearest.h"      /* the same query with a bound that shrinks: no radius to choose */
 #include "srt_signed.h"       /* that distance with a sign, and containment, by winding along a few rays */
+#include "srt_points_multi.h" /* the K nearest triangles per point, in either walk: all contacts within a radius */
 #endif /* SRT_H */

@@ -59,7 +59,8 @@ extern "C" {
  * hit_rays = the points that found a triangle, node_tests_primary / tri_tests_primary under SRT_FLAG_COUNT_WORK.
  * NOT HERE: a shrinking radius (above; see srt_nearest.h); a SIGN -- the distance is unsigned; see srt_signed.h, which counts the sign
  * along rays; `region` serves a caller who keeps pseudo-normals of their own (face, edge or vertex normal by region) --; the K nearest
- * triangles; an any-within-radius form that stops at the first. */
+ * triangles, and how many lie within the radius: see srt_points_multi.h (n_within > 0 is the any-within-radius answer, without the early
+ * stop). */
 typedef struct srt_point_out {    /* device pointers in the _device form, host pointers in the host form */
     int32_t* tri;                /* n       canonical triangle id, -1 = none within the radius */
     float*   dist2;              /* n       the winner's dist2 with its own bits, +inf = none */

@@ -1,7 +1,8 @@
 """ctypes mirror of include/srt.h -- its structs (STRUCTS), constants (SRT_*) and prototypes (PROTOTYPES), checked against the header by
 tests/test_abi_mirror.py --, of its extension headers include/srt_points.h (POINT_STRUCTS, POINT_PROTOTYPES; tests/test_point_ref.py),
-include/srt_nearest.h (NEAREST_PROTOTYPES; tests/test_nearest_ref.py) and include/srt_signed.h (SIGNED_STRUCTS, SIGNED_PROTOTYPES;
-tests/test_sign_ref.py), and a numpy container for the flat scene.
+include/srt_nearest.h (NEAREST_PROTOTYPES; tests/test_nearest_ref.py), include/srt_signed.h (SIGNED_STRUCTS, SIGNED_PROTOTYPES;
+tests/test_sign_ref.py) and include/srt_points_multi.h (POINT_MULTI_STRUCTS, POINT_MULTI_PROTOTYPES; tests/test_points_multi_ref.py), and
+a numpy container for the flat scene.
 
 The flat scene is the reference's ObjectManager state (Object.h:59-89 in the reference) written out as
 arrays; see include/srt.h for the layout contract.  This module holds no compute.
@@ -236,6 +237,20 @@ SIGN_FIELDS = {"sdist": (np.float32, 1), "inside": (np.uint8, 1), "winding": (np
 SIGNED_STRUCTS = {"srt_sign": Sign, "srt_sign_out": SignOut}
 
 
+class PointMultiOut(C.Structure):
+    """srt_point_multi_out: the arrays a k-nearest-triangles query fills, as addresses (host arrays in the host forms, device pointers in
+    the _device forms); 0 = not wanted."""
+    _fields_ = [("n_within", C.c_void_p), ("n_found", C.c_void_p), ("tri", C.c_void_p), ("dist2", C.c_void_p), ("point", C.c_void_p), ("vw", C.c_void_p),
+                ("region", C.c_void_p)]
+
+
+# the fields of srt_point_multi_out: name -> (dtype, entries per point and column; None: one entry per point, no columns)
+POINT_MULTI_FIELDS = {"n_within": (np.uint32, None), "n_found": (np.uint32, None), "tri": (np.int32, 1), "dist2": (np.float32, 1), "point": (np.float32, 3),
+                      "vw": (np.float32, 2), "region": (np.uint8, 1)}
+# every struct of include/srt_points_multi.h
+POINT_MULTI_STRUCTS = {"srt_point_multi_out": PointMultiOut}
+
+
 # ---- the prototypes of include/srt.h, in its order: name -> (restype, [argtypes]) ----
 # srt_scene*, void* and every address that travels as an int (the d_* parameters, a stream, srt_render_async's outputs) are c_void_p;
 # srt_scene** and T* const* are POINTER(c_void_p); a pointer to an srt_ struct is POINTER(its class); a scalar is its exact ctype.
@@ -367,6 +382,18 @@ SIGNED_PROTOTYPES = {
     "srt_signed_points_device": (_int, [_vp, _u32, _vp, _vp, _vp, _sign, _u32, _vp, _pout, _sout]),
     "srt_signed_points": (_int, [_vp, _u32, _f32p, _f32p, _u32p, _sign, _u32, _pout, _sout, _stats]),
 }
+
+# ---- include/srt_points_multi.h: its constant and its prototypes, in its order, under the same rules ----
+POINT_MULTI_MAX = 16      # SRT_POINT_MULTI_MAX
+_pmout = C.POINTER(PointMultiOut)
+POINT_MULTI_PROTOTYPES = {
+    "srt_closest_points_multi_device": (_int, [_vp, _u32, _vp, _vp, _vp, _u32, _u32, _vp, _pmout]),
+    "srt_closest_points_multi": (_int, [_vp, _u32, _f32p, _f32p, _u32p, _u32, _u32, _pmout, _stats]),
+}
+POINT_MULTI_PROTOTYPES.update({
+    "srt_nearest_points_multi_device": POINT_MULTI_PROTOTYPES["srt_closest_points_multi_device"],
+    "srt_nearest_points_multi": POINT_MULTI_PROTOTYPES["srt_closest_points_multi"],
+})
 
 
 def _ptr(a, ty):

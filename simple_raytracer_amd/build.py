@@ -12,7 +12,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB_HIP = os.path.join(HERE, "libsrt_hip.so")
 HIP_SRC = os.path.join(CSRC, "srt_hip.hip")
 # What libsrt_hip.so, and every measurement variant of it, is compiled from: the one translation unit and the headers it includes.
-HIP_DEPS = [HIP_SRC] + [os.path.join(CSRC, f) for f in ("srt_device.h", "srt_kernels.h", "srt_packet.h", "srt_query.h", "srt_tile_spans.h")] + [os.path.join(HERE, "..", "include", f) for f in ("srt.h", "srt_points.h", "srt_nearest.h", "srt_signed.h")]
+HIP_DEPS = [HIP_SRC] + [os.path.join(CSRC, f) for f in ("srt_device.h", "srt_kernels.h", "srt_packet.h", "srt_query.h", "srt_tile_spans.h")] + [os.path.join(HERE, "..", "include", f) for f in ("srt.h", "srt_points.h", "srt_nearest.h", "srt_signed.h", "srt_points_multi.h")]
 
 # -ffp-contract=off is part of the numerical contract: FMA contraction changes hit results
 # (SURVEY.md H1).  Correctly rounded f32 divide / sqrt are hipcc defaults and must stay on.
@@ -56,7 +56,7 @@ HOST_FLAGS = ["-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-Wa
 HOST_DIR = os.path.join(CSRC, "host")
 HOST_CPU_SRCS = [os.path.join(HOST_DIR, f) for f in ("srt_host.cpp", "srt_jpeg.cpp")]
 HOST_SRCS = HOST_CPU_SRCS + [os.path.join(HOST_DIR, f) for f in ("srt_host_render.cpp", "srt_host_c.cpp")]
-HOST_DEPS = HOST_SRCS + [os.path.join(HOST_DIR, f) for f in ("srt_host.h", "srt_host_internal.h", "srt_host_c.h")] + [os.path.join(HERE, "..", "include", f) for f in ("srt.h", "srt_points.h", "srt_nearest.h", "srt_signed.h")]
+HOST_DEPS = HOST_SRCS + [os.path.join(HOST_DIR, f) for f in ("srt_host.h", "srt_host_internal.h", "srt_host_c.h")] + [os.path.join(HERE, "..", "include", f) for f in ("srt.h", "srt_points.h", "srt_nearest.h", "srt_signed.h", "srt_points_multi.h")]
 
 
 def build_host(force=False, verbose=False):

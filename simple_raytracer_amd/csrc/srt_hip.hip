@@ -1919,6 +1919,30 @@ static int closest_points_device_impl(srt_scene* s, uint32_t n, const float* d_p
     return launch_query((nearest ? shrinking : builds)[build_index(count, d_point_mask)], q.grid, q.stream, s->dev, n, d_points, d_radius, *out, q.ctr, query_mask(s, d_point_mask));
 }
 
+// srt_closest_points_multi / srt_nearest_points_multi (include/srt_points_multi.h): the k nearest triangles per point in one walk, one
+// launch (k_query_points_multi); the build reserves 4, 8 or 16 slots a point, as trace_rays_multi_device_impl picks them.
+// nearest: the walk prunes by the k-th best dist2; n_within is not defined then and is refused.
+static inline bool points_multi_wanted(const srt_point_multi_out* o) { return o->n_within || o->n_found || o->tri || o->dist2 || o->point || o->vw || o->region; }
+static int check_points_multi(const srt_scene* s, uint32_t n, const float* points, uint32_t k, uint32_t flags, const srt_point_multi_out* out, bool nearest) {
+    SRT_TRY(check_query(s, n, points, flags));
+    if (!out || k == 0 || k > SRT_POINT_MULTI_MAX || (nearest && out->n_within)) return SRT_ERR_ARG;
+    return SRT_OK;
+}
+static int points_multi_device_impl(srt_scene* s, uint32_t n, const float* d_points, const float* d_radius, const uint32_t* d_point_mask, uint32_t k, uint32_t flags,
+                                    hipStream_t stream, const srt_point_multi_out* out, bool count_hits, bool nearest) {
+    SRT_TRY(check_points_multi(s, n, d_points, k, flags, out, nearest));
+    if (!n || (!count_hits && !points_multi_wanted(out))) return SRT_OK;
+    const bool count = (flags & SRT_FLAG_COUNT_WORK) != 0;
+    QueryLaunch q;
+    SRT_TRY(query_prologue(s, n, stream, nullptr, count || count_hits, &q));
+    static const std::array builds = { std::array{ BUILDS_3(k_query_points_multi, , 4) }, std::array{ BUILDS_3(k_query_points_multi, , 8) },
+                                       std::array{ BUILDS_3(k_query_points_multi, , 16) } };
+    static_assert(SRT_POINT_MULTI_MAX == 16, "the largest bucket holds SRT_POINT_MULTI_MAX slots");
+    const int bucket = k <= 4 ? 0 : k <= 8 ? 1 : 2;
+    return launch_query(builds[bucket][build_index(count, d_point_mask, nearest)], q.grid, q.stream, s->dev, n, d_points, d_radius, k, *out, q.ctr,
+                        query_mask(s, d_point_mask));
+}
+
 // srt_signed_points (include/srt_signed.h): srt_nearest_points' outputs and a sign by winding along the rays of a direction table, one
 // launch (k_query_signed).  No sign output wanted: the call IS srt_nearest_points, with that call's kernels, and `sign` is not read.
 // NEAR: whether the nearest phase runs -- a point output or sdist is wanted; without it hit_rays is 0.
@@ -2286,6 +2310,22 @@ static int closest_points_impl(srt_scene* s, uint32_t n, const float* points, co
         const srt_point_out dev = { o_tri.on_device(), o_d2.on_device(), o_pt.on_device(), o_vw.on_device(), o_reg.on_device() };
         return closest_points_device_impl(s, n, i_pts.on_device(), i_rad.on_device(), i_mask.on_device(), flags, st, &dev, stats != nullptr, nearest);
     }, o_tri, o_d2, o_pt, o_vw, o_reg, i_pts, i_rad, i_mask));
+    return stats ? query_stats(s, n, 0, stats) : SRT_OK;
+}
+
+static int points_multi_impl(srt_scene* s, uint32_t n, const float* points, const float* radius, const uint32_t* point_mask, uint32_t k, uint32_t flags,
+                             const srt_point_multi_out* out, srt_stats* stats, bool nearest) {
+    SRT_TRY(check_points_multi(s, n, points, k, flags, out, nearest));
+    if (stats) std::memset(stats, 0, sizeof(*stats));
+    if (!n) return SRT_OK;
+    const size_t rows = (size_t)n * k;      // the n x k rows
+    auto o_nw = query_out(out->n_within, n); auto o_nf = query_out(out->n_found, n); auto o_tri = query_out(out->tri, rows); auto o_d2 = query_out(out->dist2, rows);
+    auto o_pt = query_out(out->point, 3 * rows); auto o_vw = query_out(out->vw, 2 * rows); auto o_reg = query_out(out->region, rows);
+    auto i_pts = query_in(points, 3ull * n); auto i_rad = query_in(radius, n); auto i_mask = query_in(point_mask, n);
+    SRT_TRY(query_round_trip(s, false, [&](hipStream_t st) {
+        const srt_point_multi_out dev = { o_nw.on_device(), o_nf.on_device(), o_tri.on_device(), o_d2.on_device(), o_pt.on_device(), o_vw.on_device(), o_reg.on_device() };
+        return points_multi_device_impl(s, n, i_pts.on_device(), i_rad.on_device(), i_mask.on_device(), k, flags, st, &dev, stats != nullptr, nearest);
+    }, o_nw, o_nf, o_tri, o_d2, o_pt, o_vw, o_reg, i_pts, i_rad, i_mask));
     return stats ? query_stats(s, n, 0, stats) : SRT_OK;
 }
 
@@ -2759,6 +2799,23 @@ int srt_signed_points_device(srt_scene* s, uint32_t n, const float* d_points, co
 int srt_signed_points(srt_scene* s, uint32_t n, const float* points, const float* radius, const uint32_t* point_mask, const srt_sign* sign, uint32_t flags,
                       const srt_point_out* out, const srt_sign_out* sout, srt_stats* stats) {
     return guarded([&] { return signed_points_impl(s, n, points, radius, point_mask, sign, flags, out, sout, stats); });
+}
+
+int srt_closest_points_multi_device(srt_scene* s, uint32_t n, const float* d_points, const float* d_radius, const uint32_t* d_point_mask, uint32_t k, uint32_t flags,
+                                    void* stream, const srt_point_multi_out* out) {
+    return guarded([&] { return points_multi_device_impl(s, n, d_points, d_radius, d_point_mask, k, flags, (hipStream_t)stream, out, false, false); });
+}
+int srt_closest_points_multi(srt_scene* s, uint32_t n, const float* points, const float* radius, const uint32_t* point_mask, uint32_t k, uint32_t flags,
+                             const srt_point_multi_out* out, srt_stats* stats) {
+    return guarded([&] { return points_multi_impl(s, n, points, radius, point_mask, k, flags, out, stats, false); });
+}
+int srt_nearest_points_multi_device(srt_scene* s, uint32_t n, const float* d_points, const float* d_radius, const uint32_t* d_point_mask, uint32_t k, uint32_t flags,
+                                    void* stream, const srt_point_multi_out* out) {
+    return guarded([&] { return points_multi_device_impl(s, n, d_points, d_radius, d_point_mask, k, flags, (hipStream_t)stream, out, false, true); });
+}
+int srt_nearest_points_multi(srt_scene* s, uint32_t n, const float* points, const float* radius, const uint32_t* point_mask, uint32_t k, uint32_t flags,
+                             const srt_point_multi_out* out, srt_stats* stats) {
+    return guarded([&] { return points_multi_impl(s, n, points, radius, point_mask, k, flags, out, stats, true); });
 }
 
 void* srt_host_alloc(size_t bytes) {

@@ -1719,3 +1719,98 @@ __global__ __launch_bounds__(256) void k_query_signed(DevScene s, uint32_t n_poi
 #undef SRT_QUERY_POINTS_LOAD
 #undef SRT_QUERY_POINTS_FIND
 #undef SRT_QUERY_POINTS_STORE
+
+// =================================================================================================
+// The K nearest triangles of a point (srt_closest_points_multi, srt_nearest_points_multi; include/srt_points_multi.h): the two halves
+// that existed, put together -- the point's policies (WalkPoint, WalkNearest) with srt_trace_rays_multi's merge (MergeMulti: k slots of 64
+// keys a wave, a key carried down them by atomicMin).  hit_key(dist2, id) orders candidates by (dist2, id): dist2 is never -0.  Nothing of
+// query_walk, the policies or the merge changes; cnt[] counts the offers, which in the closest form are ALL qualifying candidates.
+// NEAR: WalkNearest as it stands with its `bound` on the wave's slot[k - 1] in the place of best[]: the high word of slot[k - 1][lane] is
+// the k-th best dist2 offered so far for the lane's point.  An empty slot's ~0 reads as a NaN -- "no bound yet", as there.  The slot is
+// written by atomicMin alone, so it only decreases, and MergeMulti's induction makes its FINAL value the k-th smallest key offered: any
+// value read from it on the way is never below the final k-th dist2, so by (a) and (c) of include/srt_nearest.h no ancestor of any of the
+// k winners is pruned, and the leaf filter !(dist2 > best_of(src)) drops only what cannot be among the k.  cnt[] counts the offers that
+// passed that filter and means nothing to a caller: the kernel argument n_within is NULL in this form (the host refuses it).
+// Phase 2: column by column the owning lane recomputes closest_point from the key's triangle and its own p -- the walk's function on the
+// walk's operands, hence the walk's bits -- and stores that column's point, vw and region itself (rows of 12, 8 and 1 B at a stride of k
+// rows: a per-column store_rows would need the stage k times for runs of 3 words; the bits do not depend on it).  tri and dist2 leave
+// TRANSPOSED through the slots, as k_query_multi's hit_id and t do: 64 consecutive words per store.  n_within and n_found, one word a
+// point, are coalesced as they stand; n_found is the number of filled slots, min(k, offers) in both forms.
+// KB: the slots the build reserves (k <= KB; the host picks 4, 8 or 16).  LDS a workgroup: the queue 10,240 B, the slots KB x 2,048 B,
+// the counts 1,024 B, 4 rows 4,096 B: 23,552 / 31,744 / 48,128 B -- six, five and three workgroups a CU of 160 KB.
+// counters: [1] / [2] node / triangle tests (COUNT), [8 + 8 * shard] the points with n_found > 0.
+// =================================================================================================
+template <bool COUNT, bool MASK, bool NEAR, int KB>
+__global__ __launch_bounds__(256) void k_query_points_multi(DevScene s, uint32_t n_points, const float* __restrict__ points, const float* __restrict__ radius,
+                                                            uint32_t k, srt_point_multi_out out, unsigned long long* __restrict__ counters, QueryMask qm) {
+    __shared__ uint32_t q_all[4][QCAP];
+    __shared__ unsigned long long slot_all[4][KB][64];
+    __shared__ uint32_t cnt_all[256];
+    __shared__ float row_all[4][4][64];
+    const uint32_t lane = wave_lane(), wave = wave_index();
+    unsigned long long (*slot)[64] = slot_all[wave];
+    uint32_t* cnt = cnt_all + wave * 64;
+    k = k < 1u ? 1u : k < (uint32_t)KB ? k : (uint32_t)KB;      // (the host picks KB >= k >= 1)
+    const size_t base = wave_base(wave), ri = base + lane;
+    const bool live = ri < (size_t)n_points;
+    unsigned long long n_node = 0, n_tri = 0;
+    V3 p = mk(0.0f, 0.0f, 0.0f);
+    float r = __builtin_inff();
+    uint32_t m = 0xFFFFFFFFu;
+    if (live) {
+        const float* pp = points + 3 * ri;
+        p = mk(pp[0], pp[1], pp[2]);
+        if (radius) r = radius[ri];
+        if (MASK && qm.ray) m = qm.ray[ri];
+    }
+    const bool walks = live && r >= 0.0f;               // (a NaN radius fails the comparison)
+    const MergeMulti mg{ slot, cnt, k };
+    if constexpr (NEAR)
+        query_walk<COUNT, false, MergeMulti, MASK>(s, walks, p, p, lane, q_all[wave], mg, row_all[wave], n_node, n_tri, 0.0f, 0.0f, qm.obj, m,
+                                                   WalkNearest::make(p, r * r, slot[k - 1], lane));
+    else
+        query_walk<COUNT, false, MergeMulti, MASK>(s, walks, p, p, lane, q_all[wave], mg, row_all[wave], n_node, n_tri, 0.0f, 0.0f, qm.obj, m,
+                                                   WalkPoint{ p, r * r });
+    const float4* tris4 = reinterpret_cast<const float4*>(s.tris);
+    const bool found = live && slot[0][lane] != ~0ull;
+    if (live) {
+        if (!NEAR && out.n_within) out.n_within[ri] = cnt[lane];
+        if (out.n_found) {
+            uint32_t nf = 0;
+            for (uint32_t j = 0; j < k; j++) nf += slot[j][lane] != ~0ull ? 1u : 0u;
+            out.n_found[ri] = nf;
+        }
+    }
+    if (out.tri || out.dist2 || out.point || out.vw || out.region) {      // (wave-uniform: a kernel argument)
+        for (uint32_t j = 0; j < k; j++) {
+            const Winner h = winner_of(live ? slot[j][lane] : ~0ull);
+            ClosestPoint c;
+            c.v = 0.0f; c.w = 0.0f; c.dist2 = __builtin_inff(); c.point = mk(0.0f, 0.0f, 0.0f); c.region = 0u;
+            if (h.is_hit) {
+                V3 p1, e1, e2;
+                load_tri_edges(tris4, (size_t)h.id, p1, e1, e2);
+                closest_point(c, p, p1, e1, e2);          // (dist2, point, vw and region of THIS triangle)
+            }
+            if (live) {
+                const size_t at = ri * k + j;
+                if (out.region) out.region[at] = (uint8_t)c.region;
+                if (out.point) { out.point[at * 3] = c.point.x; out.point[at * 3 + 1] = c.point.y; out.point[at * 3 + 2] = c.point.z; }
+                if (out.vw) { out.vw[at * 2] = c.v; out.vw[at * 2 + 1] = c.w; }
+            }
+            slot[j][lane] = ((unsigned long long)__float_as_uint(c.dist2) << 32) | (uint32_t)h.id;
+        }
+        __builtin_amdgcn_wave_barrier();
+        if (base < (size_t)n_points && (out.tri || out.dist2)) {      // wave-uniform
+            const size_t left = (size_t)n_points - base;
+            const uint32_t words = (uint32_t)(left < 64 ? left : 64) * k;      // the wave's rows are words [base * k, base * k + words)
+            for (uint32_t w = lane; w < words; w += 64u) {
+                const uint32_t row = w / k, j = w - row * k;
+                const unsigned long long v = slot[j][row];
+                if (out.tri) out.tri[base * k + w] = (int32_t)(uint32_t)v;
+                if (out.dist2) out.dist2[base * k + w] = __uint_as_float((uint32_t)(v >> 32));
+            }
+        }
+    }
+    if (counters) count_hits(counters, found, blockIdx.x);
+    count_walks<COUNT>(counters, n_node, n_tri);
+}

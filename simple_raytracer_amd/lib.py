@@ -1,5 +1,5 @@
-"""ctypes binding of the C ABI in include/srt.h and its extension headers include/srt_points.h, include/srt_nearest.h and
-include/srt_signed.h (libsrt_hip.so).
+"""ctypes binding of the C ABI in include/srt.h and its extension headers include/srt_points.h, include/srt_nearest.h,
+include/srt_signed.h and include/srt_points_multi.h (libsrt_hip.so).
 
 The product path has NO CPU fallback: if the HIP library is missing or no GPU is visible, this
 raises.  (The CPU restatement under oracle/ is test infrastructure and is never imported here.)
@@ -20,7 +20,9 @@ ABI_SYMBOLS = tuple(abi.PROTOTYPES)           # every symbol include/srt.h decla
 POINT_SYMBOLS = tuple(abi.POINT_PROTOTYPES)    # every symbol include/srt_points.h declares
 NEAREST_SYMBOLS = tuple(abi.NEAREST_PROTOTYPES)    # every symbol include/srt_nearest.h declares
 SIGNED_SYMBOLS = tuple(abi.SIGNED_PROTOTYPES)    # every symbol include/srt_signed.h declares
+POINT_MULTI_SYMBOLS = tuple(abi.POINT_MULTI_PROTOTYPES)    # every symbol include/srt_points_multi.h declares
 MULTI_HIT_MAX = abi.SRT_MULTI_HIT_MAX
+POINT_MULTI_MAX = abi.POINT_MULTI_MAX
 
 _f32p, _i32p, _u8p, _u32p = C.POINTER(C.c_float), C.POINTER(C.c_int32), C.POINTER(C.c_uint8), C.POINTER(C.c_uint32)
 _lib = None
@@ -43,7 +45,8 @@ def load(path=None):
             raise RuntimeError(f"{path or LIB_PATH} is missing: the HIP extension must be built "
                                "(python -m simple_raytracer_amd.build); there is no CPU fallback")
         L = C.CDLL(path or LIB_PATH)
-        for name, (restype, argtypes) in {**abi.PROTOTYPES, **abi.POINT_PROTOTYPES, **abi.NEAREST_PROTOTYPES, **abi.SIGNED_PROTOTYPES}.items():
+        for name, (restype, argtypes) in {**abi.PROTOTYPES, **abi.POINT_PROTOTYPES, **abi.NEAREST_PROTOTYPES, **abi.SIGNED_PROTOTYPES,
+                                            **abi.POINT_MULTI_PROTOTYPES}.items():
             fn = getattr(L, name)
             fn.restype, fn.argtypes = restype, argtypes
         if path is not None:
@@ -547,6 +550,46 @@ class DeviceScene:
         po, sg = _wanted(abi.PointOut, tri, dist2, point, vw, region), _wanted(abi.SignOut, sdist, inside, winding, crossings)
         _check(self.L.srt_signed_points_device(self.h, n, d_points, radius or None, point_mask or None, C.byref(sign), _query_flags(count=count), stream,
                                                C.byref(po), C.byref(sg)), "srt_signed_points_device")
+
+    def closest_points_multi(self, points, k, radius=None, point_mask=None, count=False,
+                             want=("n_within", "n_found", "tri", "dist2", "point", "vw", "region")):
+        """srt_closest_points_multi (include/srt_points_multi.h): closest_points' arguments, and per point the k nearest triangles within
+        `radius`, nearest first, equal dist2 by lowest id (k = 1 .. POINT_MULTI_MAX).  Returns a dict of the arrays named in `want` --
+        n_within n uint32 (ALL triangles within the radius; it may exceed k), n_found n uint32 (the filled columns, min(k, n_within)),
+        tri n x k (-1: an empty column), dist2 n x k (+inf), point n x k x 3, vw n x k x 2, region n x k -- + 'stats'.  Column 0 is
+        closest_points' result; the radius never shrinks, and the counts under count=True are closest_points'."""
+        return self._points_multi("srt_closest_points_multi", points, k, radius, point_mask, count, want)
+
+    def nearest_points_multi(self, points, k, radius=None, point_mask=None, count=False, want=("n_found", "tri", "dist2", "point", "vw", "region")):
+        """srt_nearest_points_multi: closest_points_multi's columns and n_found, bit for bit, on every scene whose boxes nest -- but the walk
+        also prunes by the k-th best distance found so far, so no radius has to be chosen.  There is no n_within under pruning: naming it
+        in `want` is an error.  count=True: the counts are of the walk as it ran and depend on the batch."""
+        return self._points_multi("srt_nearest_points_multi", points, k, radius, point_mask, count, want)
+
+    def _points_multi(self, symbol, points, k, radius, point_mask, count, want):
+        pts = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        n, k = pts.shape[0], int(k)
+        rad = None if radius is None else np.ascontiguousarray(np.broadcast_to(np.asarray(radius, np.float32).reshape(-1), (n,)), np.float32)
+        pm = None if point_mask is None else _ray_mask(point_mask, n)
+        spec = {key: (ty, ()) if c is None else (ty, (max(k, 0),) + (() if c == 1 else (c,))) for key, (ty, c) in abi.POINT_MULTI_FIELDS.items()}
+        out, _ = _outputs(want, (n,), spec)
+        po = abi.PointMultiOut(*_addresses(out, spec))
+        return _with_stats(out, getattr(self.L, symbol), symbol, self.h, n, _host(pts, _f32p), _host(rad, _f32p), _host(pm, _u32p), k,
+                           _query_flags(count=count), C.byref(po))
+
+    def closest_points_multi_device(self, n, d_points, k, radius=0, point_mask=0, stream=0, count=False, n_within=0, n_found=0, tri=0, dist2=0, point=0, vw=0,
+                                    region=0):
+        """srt_closest_points_multi_device: raw device pointers (ints, e.g. torch.Tensor.data_ptr()) in -- closest_points_device's, and the
+        outputs (n_within, n_found: n; the others n x k rows; 0: not wanted) --, asynchronous on `stream`, one launch."""
+        self._points_multi_device("srt_closest_points_multi_device", n, d_points, k, radius, point_mask, stream, count, (n_within, n_found, tri, dist2, point, vw, region))
+
+    def nearest_points_multi_device(self, n, d_points, k, radius=0, point_mask=0, stream=0, count=False, n_found=0, tri=0, dist2=0, point=0, vw=0, region=0):
+        """srt_nearest_points_multi_device: closest_points_multi_device's arguments without n_within, asynchronous on `stream`, one launch."""
+        self._points_multi_device("srt_nearest_points_multi_device", n, d_points, k, radius, point_mask, stream, count, (0, n_found, tri, dist2, point, vw, region))
+
+    def _points_multi_device(self, symbol, n, d_points, k, radius, point_mask, stream, count, outs):
+        po = _wanted(abi.PointMultiOut, *outs)
+        _check(getattr(self.L, symbol)(self.h, n, d_points, radius or None, point_mask or None, k, _query_flags(count=count), stream, C.byref(po)), symbol)
 
     def sync(self):
         return _with_stats({}, self.L.srt_sync, "srt_sync", self.h)["stats"]

@@ -58,7 +58,10 @@ points in the same rounds at every radius; the outputs of the two are compared o
 replaces on the calls that existed before it, in the same rounds: srt_nearest_points_device, torch writing the n x 3 rays,
 srt_trace_rays_multi_device for n_hits alone, the vote and the sign in torch.  Equal bits are asserted.  Also srt_nearest_points_device
 alone (what the sign costs on top of it) and containment only (no nearest phase).
-Usage: python tools/ray_query_probe.py [--reps N] [--trace] [--shade | --range | --shade-range | --multi | --surface | --paths | --shadow-rule | --masked | --refract | --fresnel | --ao | --render-ao | --points | --nearest | --signed [--rounds R]]     (--trace: few repetitions, for a run under rocprofv3 --kernel-trace --stats)"""
+--points-multi: the K nearest triangles per point (srt_closest_points_multi_device, srt_nearest_points_multi_device; k = 1, 4, 16) on the
+points of --nearest at radii 1, 4, 16 and none, beside srt_closest_points_device and srt_nearest_points_device in the same rounds; equal bits
+of column 0 and of the two forms are asserted, the counters printed.
+Usage: python tools/ray_query_probe.py [--reps N] [--trace] [--shade | --range | --shade-range | --multi | --surface | --paths | --shadow-rule | --masked | --refract | --fresnel | --ao | --render-ao | --points | --nearest | --signed | --points-multi [--rounds R]]     (--trace: few repetitions, for a run under rocprofv3 --kernel-trace --stats)"""
 import argparse, os, sys, time
 import numpy as np
 import torch                                   # first: torch initialises HIP before the library does
@@ -846,6 +849,67 @@ def points_section(reps, rounds, nearest=False):
     ds.close()
 
 
+def points_multi_section(reps, rounds):
+    """The K nearest triangles per point (srt_closest_points_multi_device, srt_nearest_points_multi_device; k = 1, 4, 16) beside the
+    single-winner calls srt_closest_points_device and srt_nearest_points_device, in the same rounds: the points of --nearest -- the hit
+    points of the 1080p frame OFFSETS units off the surface, radii RADII on every STEP-th hit, no radius on every (16 STEP)-th.  Written:
+    n_found, tri, dist2 (the single-winner calls: tri, dist2).  The spread of the single-winner calls across the rounds is the noise floor;
+    k = 1 against them is the price of the slots.  Equal bits of column 0 are asserted, and the counters are printed: the closest form's are
+    srt_closest_points', the nearest form's lie below them."""
+    OFFSETS, RADII, STEP, KS = (0.25, 2.0), (1.0, 4.0, 16.0), 4, (1, 4, 16)
+    dev = torch.device("cuda", 0); torch.zeros(1, device=dev)
+    g = gu.GoldenScene("ground_bunny")
+    ds = lib.DeviceScene(g.flat)
+    side = torch.cuda.Stream(device=dev)
+    cur = side.cuda_stream
+    rays = frame_rays()
+    frame = ds.trace_rays(rays, want=("hit_id", "t"))
+    hits = np.flatnonzero(frame["hit_id"] >= 0)
+    P = rays[hits, 3:6] * frame["t"][hits, None]                      # (the origin is 0)
+    unit = rays[hits, 3:6] / np.linalg.norm(rays[hits, 3:6], axis=1, keepdims=True)
+    print(f"K nearest triangles per point, K3 ground_bunny {W}x{H}: {g.flat.n_tris} triangles, {g.flat.n_nodes} nodes; {hits.size} hit points; {rounds} rounds of {reps} "
+          f"calls, forms alternating; ms a call; min / max: the spread of the rounds; / first: over srt_closest_points_device")
+    for step, radii in ((STEP, RADII), (16 * STEP, (np.inf,))):
+        sel = np.arange(0, hits.size, step)
+        n = sel.size
+        tri, d2 = torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.float32, device=dev)
+        nf = torch.empty(n, dtype=torch.int32, device=dev)
+        mtri, md2 = torch.empty((n, max(KS)), dtype=torch.int32, device=dev), torch.empty((n, max(KS)), dtype=torch.float32, device=dev)
+        print(f"every {step}th hit: {n} points")
+        print(f"{'points':34s} {'form':34s} {'median':>8s} {'min':>8s} {'max':>8s} {'/ first':>7s}")
+        for off in OFFSETS:
+            pts = np.ascontiguousarray(P[sel] - unit[sel] * np.float32(off), np.float32)
+            d_pts = torch.from_numpy(pts).to(dev)
+            for r in radii:
+                d_rad = 0 if np.isinf(r) else torch.full((n,), float(r), dtype=torch.float32, device=dev)
+                rad = 0 if np.isinf(r) else d_rad.data_ptr()
+                forms = {}
+                for call in ("closest_points", "nearest_points"):
+                    forms[call] = (lambda fn=getattr(ds, call + "_device"): fn(n, d_pts.data_ptr(), radius=rad, stream=cur, tri=tri.data_ptr(), dist2=d2.data_ptr()))
+                for k in KS:
+                    for call in ("closest_points_multi", "nearest_points_multi"):
+                        forms[f"{call}, k {k}"] = (lambda k=k, fn=getattr(ds, call + "_device"): fn(n, d_pts.data_ptr(), k, radius=rad, stream=cur, n_found=nf.data_ptr(),
+                                                                                                  tri=mtri.data_ptr(), dist2=md2.data_ptr()))
+                report(f"{off:g} off the surface, radius {r:g}", rounds_of(forms, reps, rounds, side))
+                side.synchronize()
+                host_r = None if np.isinf(r) else r
+                one = ds.closest_points(pts, radius=host_r, count=True, want=("tri", "dist2"))
+                print(f"{'':34s} closest_points: found {int((one['tri'] >= 0).sum())} of {n}; per point {one['stats']['node_tests_primary'] / n:.1f} node tests, "
+                      f"{one['stats']['tri_tests_primary'] / n:.1f} triangle tests")
+                for k in KS:
+                    close = ds.closest_points_multi(pts, k, radius=host_r, count=True, want=("n_within", "n_found", "tri", "dist2"))
+                    near = ds.nearest_points_multi(pts, k, radius=host_r, count=True, want=("n_found", "tri", "dist2"))
+                    assert all(np.array_equal(close[key].view(np.uint32), near[key].view(np.uint32)) for key in ("n_found", "tri", "dist2"))
+                    assert all(np.array_equal(close[key][:, 0].view(np.uint32), one[key].view(np.uint32)) for key in ("tri", "dist2"))
+                    a, b = close["stats"], near["stats"]
+                    assert (a["node_tests_primary"], a["tri_tests_primary"]) == (one["stats"]["node_tests_primary"], one["stats"]["tri_tests_primary"])
+                    assert b["node_tests_primary"] <= a["node_tests_primary"] and b["tri_tests_primary"] <= a["tri_tests_primary"]
+                    print(f"{'':34s} k {k}: within the radius, median {int(np.median(close['n_within']))}, mean found {close['n_found'].mean():.2f}; per point, closest form "
+                          f"{a['node_tests_primary'] / n:.1f} node / {a['tri_tests_primary'] / n:.1f} triangle tests, nearest form {b['node_tests_primary'] / n:.1f} / "
+                          f"{b['tri_tests_primary'] / n:.1f}")
+    ds.close()
+
+
 def signed_section(reps, rounds):
     """srt_signed_points_device beside the chain of shipped calls it replaces, beside srt_nearest_points_device alone, and containment only:
     the hit points of the 1080p frame OFFSETS units off the surface towards the camera, every STEP-th and every (16 STEP)-th as in --nearest,
@@ -914,6 +978,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--signed", action="store_true")
     ap.add_argument("--points", action="store_true")
+    ap.add_argument("--points-multi", action="store_true", dest="points_multi")
     ap.add_argument("--nearest", action="store_true")
     ap.add_argument("--render-ao", action="store_true", dest="render_ao")
     ap.add_argument("--ao", action="store_true")
@@ -934,6 +999,8 @@ def main():
     reps = 3 if a.trace else a.reps
     if a.signed:
         return signed_section(reps, 2 if a.trace else a.rounds)
+    if a.points_multi:
+        return points_multi_section(reps, 2 if a.trace else a.rounds)
     if a.points or a.nearest:
         return points_section(reps, 2 if a.trace else a.rounds, nearest=a.nearest)
     if a.render_ao:
