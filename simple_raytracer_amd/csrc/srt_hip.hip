@@ -1120,6 +1120,7 @@ enum Variant : uint32_t {
     V_COARSE_GRID = 27,           // shipped choice, 2 x 2 tiles per workgroup in the unfused closest-hit launch
     V_TRACE_SHADE = 28,           // the fused kernel shades its tiles itself: the frame in one launch (below 64 samples, no XCD rows)
     V_PK_ENTRY_ORDER = 29,        // shipped choice, the packet shadow kernel's units in entry order
+    V_FUSED_HALF_8_WAVES = 30,    // the half-tile form's eight-wave build (384-entry queue, no packed f32 operations) also without SRT_FLAG_FRAMES_IN_FLIGHT, as 13 is the seven-wave one
     V_CAMERA_PK = 35,             // shipped choice, camera mode on the packet closest-hit kernel at every sample count
     V_ROUND2_FORM = 40,           // shipped choice, the round-2 form everywhere: 32 B node records, queue pushes in lane order
     V_ALL_WIDE = 41,              // shipped choice, 64 B node records in every node-queue kernel
@@ -1139,10 +1140,14 @@ enum Variant : uint32_t {
     V_SHADOW_PLAIN_ROWS = 62,     // shipped choice, the node-queue shadow kernel in plain tile order where XCD rows are on
     V_EXACT_TONE = 63,            // shipped choice, every pixel's tone map by the exact functions (no f32 filter: EXP_EXACT_TONE)
     V_FULL_GRID = 64,             // 0 in everything (batch hold-back, heavy lists, camera build included) but the tile spans: off, every tile gets its workgroup
+    V_HALF_7_WAVES = 65,          // 0 in everything (tile spans included) but the half-tile form's build: the seven-wave one with its 512-entry queue, as before the eight-wave build
+    V_HALF_8_WAVES_256 = 66,      // 0 in everything but the half-tile form's node queue: the eight-wave build with 256 entries (eight LDS granules as well: what the smaller queue costs)
 };
 // Numbers without a name keep two fallbacks: 7..9 run the unfused node-queue chain of the shipped kernels, any other number a
 // configuration of the fused kernel (the shipped one) at every sample count.
 static inline uint32_t variant_of(const srt_params* p) { return (p->flags >> 8) & 0xffu; }
+// 64 .. 66 are 0 with one thing of the shipped frame switched: every rule that asks for 0 holds for them.
+static inline uint32_t variant_or_shipped(const srt_params* p) { const uint32_t v = variant_of(p); return v >= V_FULL_GRID && v <= V_HALF_8_WAVES_256 ? (uint32_t)V_SHIPPED : v; }
 // These run the pipeline the dispatcher picks for 0.  They are NOT 0 for what only the shipped frame gets: the batch hold-back, the
 // chunked launch for scenes of few nodes, the heavy-quadrant lists and the camera build of the fused kernel.  28 is deliberately not
 // among them: it is a configuration of the fused kernel (fused_config in plan_frame) and takes the fused launch at every sample count.
@@ -1194,7 +1199,7 @@ static SceneFacts scene_facts(const srt_scene* s) {
 // Every check of a render's arguments: before any state of the handle changes (counter sets, pending work).
 static int check_frame(const SceneFacts& f, const srt_params* p) {
     if (!p || !p->width || !p->height || !p->block_rows || !p->block_stride) return SRT_ERR_ARG;
-    const uint32_t v = variant_of(p) == V_FULL_GRID ? (uint32_t)V_SHIPPED : variant_of(p);
+    const uint32_t v = variant_or_shipped(p);
     if (p->ray_matrix && v != V_SHIPPED && v != V_PK_PK && v != V_CAMERA_PK) return SRT_ERR_ARG;      // camera mode: shipped pipelines only
     if (p->n_lights && !p->light_pos) return SRT_ERR_ARG;
     if (p->block_cols && ((p->block_cols & 7u) || (p->block_rows & 7u) || p->block_first >= p->block_stride)) return SRT_ERR_ARG;   // tiles of whole 8x8 pixel blocks
@@ -1247,7 +1252,7 @@ struct FramePlan {
 static FramePlan plan_frame(const SceneFacts& f, const srt_params* p, BatchState batch) {
     FramePlan pl;
     const bool full_grid = variant_of(p) == V_FULL_GRID;
-    const uint32_t v = full_grid ? (uint32_t)V_SHIPPED : variant_of(p), L = p->n_lights, wl = srt_cols_owned(p), rows = srt_rows_owned(p);
+    const uint32_t v = variant_or_shipped(p), L = p->n_lights, wl = srt_cols_owned(p), rows = srt_rows_owned(p);
     const bool count = (p->flags & SRT_FLAG_COUNT_WORK) != 0, in_flight = (p->flags & SRT_FLAG_FRAMES_IN_FLIGHT) != 0, cam = p->ray_matrix != nullptr, shipped = shipped_choice(v);
     const dim3 grid16((wl + 15) / 16, (rows + 15) / 16), grid8((wl + 7) / 8, (rows + 7) / 8);      // grid8: 8x8 pixels per workgroup, 4 waves x (4x4 pixels)
     const auto xcd_pad = [](uint32_t y) { return (y + 7) / 8 * 8; };      // whole tile rows per XCD: y padded to 8 rows
@@ -1342,8 +1347,11 @@ static FramePlan plan_frame(const SceneFacts& f, const srt_params* p, BatchState
             // 4.13 -> 3.37 ms).  A frame that has the device to itself pays for that tail -- the launch alone 0.108 -> 0.136 ms
             // -- and keeps four waves per tile, as do the camera, counting and XCD-row builds below.  The build for seven waves per SIMD
             // (the closest-hit phase's dir[] and best[] over the shadow phase's LDS: fourteen workgroups per CU instead of twelve) takes the
-            // 36 frames from 3.37 to 3.23 ms; 19 keeps the six-wave build of the same body.
+            // 36 frames from 3.37 to 3.23 ms; 19 keeps the six-wave build of the same body.  The build for eight waves per SIMD (no packed f32
+            // operations: 64 VGPRs without scratch; 384 queue entries: eight LDS granules, sixteen workgroups per CU) takes them from 3.03 to
+            // 2.67 ms; 65 keeps the seven-wave build in its place, 66 runs the eight-wave one with 256 entries, 30 forces it without the hint.
             const bool half_tile = (v == V_SHIPPED && in_flight) || v == V_FUSED_HALF;
+            const bool half_eight = (v == V_SHIPPED && in_flight && variant_of(p) != V_HALF_7_WAVES) || v == V_FUSED_HALF_8_WAVES;      // (13 keeps the seven-wave build)
             if (cam_nq)                        pl.trace = &k_trace_nq<false, 512, true, 5, 16, false, false, true>;      // camera mode on the node queues
             else if (count)                    pl.trace = &k_trace_nq<true, 512, true, 5, 16>;
             else if (v == V_FUSED_5_WAVES)     pl.trace = &k_trace_nq<false, 512, true, 5, 16>;
@@ -1356,6 +1364,8 @@ static FramePlan plan_frame(const SceneFacts& f, const srt_params* p, BatchState
             else if (v == V_FUSED_HALF_1024) { pl.trace = &k_trace_nq_half<1024, true, 5, 16>; pl.block_hit = 128; }
             else if (v == V_FUSED_HALF_32_RAYS) { pl.trace = &k_trace_nq_half<512, true, 6, 32>; pl.block_hit = 128; }
             else if (v == V_FUSED_HALF_6_WAVES) { pl.trace = &k_trace_nq_half<512, true, 6, 16>; pl.block_hit = 128; }      // 73 VGPRs: twelve workgroups and 24 waves per CU, as before the LDS overlay
+            else if (half_eight && variant_of(p) == V_HALF_8_WAVES_256) { pl.trace = &k_trace_nq_half8<256, true, 16>; pl.block_hit = 128; }      // 9,096 B: eight granules too, the same sixteen workgroups
+            else if (half_eight)             { pl.trace = &k_trace_nq_half8<384, true, 16>; pl.block_hit = 128; }      // built without packed f32 operations: 64 VGPRs and no scratch; 384 queue entries: 10,120 B of LDS, eight granules -- sixteen workgroups and 32 waves per CU
             else if (half_tile)              { pl.trace = &k_trace_nq_half<512, true, 7, 16>; pl.block_hit = 128; }      // two waves of 8x4 pixels per tile: 11,144 B of LDS (HalfTileLds) and 72 VGPRs, fourteen workgroups and 28 waves per CU
             else                               pl.trace = &k_trace_nq<false, 512, true, 7, 16>;      // 72 VGPRs, no scratch, 7 waves per SIMD (lane-derived addresses are formed where they are used: lane_again, srt_kernels.h); with 14 spilled registers it was already 3 % ahead of the 6-wave build since the node-major order
         } else if (!count && v == V_COARSE_GRID) {
@@ -1415,6 +1425,8 @@ static FramePlan plan_frame(const SceneFacts& f, const srt_params* p, BatchState
     {
         pl.spans.epoch = f.box_epoch;
         if (pl.block_hit == 128) pl.trace_spans = &k_trace_nq_half_spans<512, true, 7, 16>; else pl.trace_spans = &k_trace_nq_spans<512, true, 7, 16>;
+        if (pl.trace == &k_trace_nq_half8<384, true, 16>) pl.trace_spans = &k_trace_nq_half8_spans<384, true, 16>;      // the twin of the build chosen above
+        if (pl.trace == &k_trace_nq_half8<256, true, 16>) pl.trace_spans = &k_trace_nq_half8_spans<256, true, 16>;
         if (pl.shade_tile == &k_shade_tile<1>) pl.shade_tile_spans = &k_shade_tile_spans<1>; else pl.shade_tile_spans = &k_shade_tile_spans<0>;
         pl.grid_hit_full = grid8;
         pl.grid_hit = dim3(tile_spans_max_n(pl.spans), pl.spans.n_rows);

@@ -1790,6 +1790,34 @@ __global__ __launch_bounds__(128, MINW) void k_trace_nq_half_spans(DevScene s, D
                                                              const uint32_t* __restrict__ box_epoch, const TileSpans spans) {
     trace_nq_body<false, NQCAP, FILTER, RS, false, false, false, false, false, false, true>(s, p, hit_id, t_out, rgb_linear, rgb8, shadow_bits, counters, nullptr, nullptr, &spans, box_epoch);
 }
+// The half-tile form built for EIGHT waves per SIMD (64 VGPRs), and its twin over the tile spans.  Kernels of their own, not further
+// instantiations of the two templates above, because they carry a target attribute: without packed f32 operations.  The SLP vectoriser
+// pairs this body's f32 multiplies and adds into v_pk_mul_f32 / v_pk_add_f32, which need aligned register pairs and a trail of moves to
+// form them -- about ten of the 72 VGPRs of the seven-wave build.  At the 64-register bound the paired code spills 26 registers; without
+// the pairing the same source needs 64 and no scratch.  The attribute holds for these kernels alone (the compiler flag that switches the
+// vectoriser off would change every kernel of the library).  The LDS side: a 384-entry node queue makes a workgroup 10,120 B, eight
+// 1,280-byte granules, and sixteen workgroups -- 32 waves -- fill a CU's 128 granules ("Half tiles at eight waves per SIMD").
+// No power of two is asked of NQCAP: the capacity checks are <=, and the roots are pushed NQCAP / (2 * rays) objects at a time.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define SRT_NO_PACKED_F32 __attribute__((target("no-packed-fp32-ops")))
+#else
+#define SRT_NO_PACKED_F32      // (the host pass knows no such feature and would warn that it ignores the attribute)
+#endif
+template <int NQCAP, bool FILTER, int RS>
+__global__ __launch_bounds__(128, 8) SRT_NO_PACKED_F32
+void k_trace_nq_half8(DevScene s, DevParams p, int32_t* __restrict__ hit_id, float* __restrict__ t_out,
+                      float* __restrict__ rgb_linear, uint8_t* __restrict__ rgb8,
+                      unsigned long long* __restrict__ shadow_bits, unsigned long long* __restrict__ counters) {
+    trace_nq_body<false, NQCAP, FILTER, RS, false, false, false, false, false, false, true>(s, p, hit_id, t_out, rgb_linear, rgb8, shadow_bits, counters);
+}
+template <int NQCAP, bool FILTER, int RS>
+__global__ __launch_bounds__(128, 8) SRT_NO_PACKED_F32
+void k_trace_nq_half8_spans(DevScene s, DevParams p, int32_t* __restrict__ hit_id, float* __restrict__ t_out,
+                            float* __restrict__ rgb_linear, uint8_t* __restrict__ rgb8,
+                            unsigned long long* __restrict__ shadow_bits, unsigned long long* __restrict__ counters,
+                            const uint32_t* __restrict__ box_epoch, const TileSpans spans) {
+    trace_nq_body<false, NQCAP, FILTER, RS, false, false, false, false, false, false, true>(s, p, hit_id, t_out, rgb_linear, rgb8, shadow_bits, counters, nullptr, nullptr, &spans, box_epoch);
+}
 // closest hit, shadow rays and shading of a frame in one launch (SHADE)
 template <int NQCAP, bool FILTER, int MINW, int RS, bool XCD_ROWS = false>
 __global__ __launch_bounds__(256, MINW) void k_trace_shade_nq(DevScene s, DevParams p, int32_t* __restrict__ hit_id, float* __restrict__ t_out,
