@@ -148,6 +148,9 @@ typedef struct srt_params {
  * frames of srt_render_device_batch, to scenes whose records take the XCD-row or packet pipelines, to a frame of more than 4096 rows, to a scene of more than 4096 objects,
  * to a scene with a non-finite, inverted or huge (beyond 2^100) root box -- and after srt_scene_pose or srt_scene_refit_device, which
  * change the boxes on the device only, until the next of the three uploads above.  Variant 64 is variant 0 with the spans off.
+ * Under SRT_FLAG_FRAMES_IN_FLIGHT with 1..4 light samples the trace workgroups over the spans are single waves, half a tile each
+ * (k_trace_nq_wave8_spans): the same outputs, bit for bit.  Variant 67 is variant 0 with the two-wave workgroups kept, 31 takes the
+ * one-wave workgroups without the flag and at every sample count, 32 is 31 with a tile's halves next to each other in dispatch order.
  * A render CAPTURED into a hipGraph holds the table of the boxes it was captured with.  It therefore launches the whole grid, and its
  * kernels skip the tiles outside the spans only while a word of the records -- rewritten in stream order by srt_scene_update,
  * srt_scene_update_frame, srt_scene_pose and srt_scene_refit_device -- still holds the number the table was made at: a replay after any

@@ -1121,6 +1121,8 @@ enum Variant : uint32_t {
     V_TRACE_SHADE = 28,           // the fused kernel shades its tiles itself: the frame in one launch (below 64 samples, no XCD rows)
     V_PK_ENTRY_ORDER = 29,        // shipped choice, the packet shadow kernel's units in entry order
     V_FUSED_HALF_8_WAVES = 30,    // the half-tile form's eight-wave build (384-entry queue, no packed f32 operations) also without SRT_FLAG_FRAMES_IN_FLIGHT, as 13 is the seven-wave one
+    V_WAVE_8 = 31,                // 0 in everything but the in-flight hint's part in the trace kernel: the eight-wave build, and over tile spans its one-wave workgroups, also without SRT_FLAG_FRAMES_IN_FLIGHT
+    V_WAVE_8_ADJACENT = 32,       // 0 in everything but the dispatch order of the one-wave workgroups: a tile's halves next to each other (on neighbouring XCDs), at every light-sample count (measured, not shipped)
     V_CAMERA_PK = 35,             // shipped choice, camera mode on the packet closest-hit kernel at every sample count
     V_ROUND2_FORM = 40,           // shipped choice, the round-2 form everywhere: 32 B node records, queue pushes in lane order
     V_ALL_WIDE = 41,              // shipped choice, 64 B node records in every node-queue kernel
@@ -1142,12 +1144,13 @@ enum Variant : uint32_t {
     V_FULL_GRID = 64,             // 0 in everything (batch hold-back, heavy lists, camera build included) but the tile spans: off, every tile gets its workgroup
     V_HALF_7_WAVES = 65,          // 0 in everything (tile spans included) but the half-tile form's build: the seven-wave one with its 512-entry queue, as before the eight-wave build
     V_HALF_8_WAVES_256 = 66,      // 0 in everything but the half-tile form's node queue: the eight-wave build with 256 entries (eight LDS granules as well: what the smaller queue costs)
+    V_HALF_8_TWO_WAVES = 67,      // 0 in everything but the workgroups of the eight-wave build over tile spans: two waves a tile (k_trace_nq_half8_spans), as before the one-wave workgroups
 };
 // Numbers without a name keep two fallbacks: 7..9 run the unfused node-queue chain of the shipped kernels, any other number a
 // configuration of the fused kernel (the shipped one) at every sample count.
 static inline uint32_t variant_of(const srt_params* p) { return (p->flags >> 8) & 0xffu; }
-// 64 .. 66 are 0 with one thing of the shipped frame switched: every rule that asks for 0 holds for them.
-static inline uint32_t variant_or_shipped(const srt_params* p) { const uint32_t v = variant_of(p); return v >= V_FULL_GRID && v <= V_HALF_8_WAVES_256 ? (uint32_t)V_SHIPPED : v; }
+// 64 .. 67, 31 and 32 are 0 with one thing of the shipped frame switched: every rule that asks for 0 holds for them.
+static inline uint32_t variant_or_shipped(const srt_params* p) { const uint32_t v = variant_of(p); return (v >= V_FULL_GRID && v <= V_HALF_8_TWO_WAVES) || v == V_WAVE_8 || v == V_WAVE_8_ADJACENT ? (uint32_t)V_SHIPPED : v; }
 // These run the pipeline the dispatcher picks for 0.  They are NOT 0 for what only the shipped frame gets: the batch hold-back, the
 // chunked launch for scenes of few nodes, the heavy-quadrant lists and the camera build of the fused kernel.  28 is deliberately not
 // among them: it is a configuration of the fused kernel (fused_config in plan_frame) and takes the fused launch at every sample count.
@@ -1231,7 +1234,7 @@ struct FramePlan {
     // stage 3, shading: one of these (none behind k_trace_shade_nq)
     RefShadeFn ref_shade = nullptr; ShadeTileFn shade_tile = nullptr;
     dim3 grid_hit, grid_shadow, grid_shade;
-    uint32_t block_hit = 256;                     // threads per workgroup of stage 1 (the half-tile trace kernel: 128); every other launch has 256
+    uint32_t block_hit = 256;                     // threads per workgroup of stage 1 (the half-tile trace kernel: 128, its one-wave workgroups over tile spans: 64); every other launch has 256
     // the DevParams fields that belong to the choice (dev_params copies them); xcd_rows as the shadow stage sees it, shadow_px_major as
     // the shading stage does
     uint32_t exp = 0, heavy_steps = 0, pk_units = 0, pk_take = 1, xcd_rows = 0, shadow_xcd_rows = 0, shadow_px_major = 0;
@@ -1350,8 +1353,12 @@ static FramePlan plan_frame(const SceneFacts& f, const srt_params* p, BatchState
             // 36 frames from 3.37 to 3.23 ms; 19 keeps the six-wave build of the same body.  The build for eight waves per SIMD (no packed f32
             // operations: 64 VGPRs without scratch; 384 queue entries: eight LDS granules, sixteen workgroups per CU) takes them from 3.03 to
             // 2.67 ms; 65 keeps the seven-wave build in its place, 66 runs the eight-wave one with 256 entries, 30 forces it without the hint.
-            const bool half_tile = (v == V_SHIPPED && in_flight) || v == V_FUSED_HALF;
-            const bool half_eight = (v == V_SHIPPED && in_flight && variant_of(p) != V_HALF_7_WAVES) || v == V_FUSED_HALF_8_WAVES;      // (13 keeps the seven-wave build)
+            // Over tile spans the eight-wave build runs as workgroups of ONE wave, a half tile each (k_trace_nq_wave8_spans, chosen with the
+            // spans below) up to four light samples; 67 keeps the two-wave workgroups, 31 takes the eight-wave build and its one-wave workgroups
+            // without the hint and at every sample count.
+            const bool hinted = in_flight || variant_of(p) == V_WAVE_8;
+            const bool half_tile = (v == V_SHIPPED && hinted) || v == V_FUSED_HALF;
+            const bool half_eight = (v == V_SHIPPED && hinted && variant_of(p) != V_HALF_7_WAVES) || v == V_FUSED_HALF_8_WAVES;      // (13 keeps the seven-wave build)
             if (cam_nq)                        pl.trace = &k_trace_nq<false, 512, true, 5, 16, false, false, true>;      // camera mode on the node queues
             else if (count)                    pl.trace = &k_trace_nq<true, 512, true, 5, 16>;
             else if (v == V_FUSED_5_WAVES)     pl.trace = &k_trace_nq<false, 512, true, 5, 16>;
@@ -1427,9 +1434,18 @@ static FramePlan plan_frame(const SceneFacts& f, const srt_params* p, BatchState
         if (pl.block_hit == 128) pl.trace_spans = &k_trace_nq_half_spans<512, true, 7, 16>; else pl.trace_spans = &k_trace_nq_spans<512, true, 7, 16>;
         if (pl.trace == &k_trace_nq_half8<384, true, 16>) pl.trace_spans = &k_trace_nq_half8_spans<384, true, 16>;      // the twin of the build chosen above
         if (pl.trace == &k_trace_nq_half8<256, true, 16>) pl.trace_spans = &k_trace_nq_half8_spans<256, true, 16>;
+        // One wave per workgroup where it was measured ahead: 1 .. 4 light samples (-3.2 % of the headline step at 1, -2.0 % at 4; level at
+        // 5 and 6, +0.5 % at 7 -- longer shadow phases, and the two-wave workgroups stay there).  31 and 32 take it at every count.
+        const bool one_wave = pl.trace == &k_trace_nq_half8<384, true, 16> && variant_of(p) != V_HALF_8_TWO_WAVES &&
+                              (L <= 4 || variant_of(p) == V_WAVE_8 || variant_of(p) == V_WAVE_8_ADJACENT);
+        const bool xcd_pairs = one_wave && variant_of(p) != V_WAVE_8_ADJACENT;      // a tile's halves eight workgroups apart, on one XCD: the order shipped
+        if (one_wave) { pl.trace_spans = &k_trace_nq_wave8_spans<384, true, 16, false>; pl.block_hit = 64; }      // 5,056 B of LDS, four granules: thirty-two workgroups of one wave per CU
+        if (xcd_pairs) pl.trace_spans = &k_trace_nq_wave8_spans<384, true, 16, true>;
         if (pl.shade_tile == &k_shade_tile<1>) pl.shade_tile_spans = &k_shade_tile_spans<1>; else pl.shade_tile_spans = &k_shade_tile_spans<0>;
         pl.grid_hit_full = grid8;
         pl.grid_hit = dim3(tile_spans_max_n(pl.spans), pl.spans.n_rows);
+        if (xcd_pairs) { pl.grid_hit_full.x = (pl.grid_hit_full.x + 7u) / 8u * 8u; pl.grid_hit.x = (pl.grid_hit.x + 7u) / 8u * 8u; }      // (groups of eight tiles: upper halves, then lower halves)
+        if (one_wave) { pl.grid_hit_full.x *= 2u; pl.grid_hit.x *= 2u; }      // two workgroups a tile; the table stays in tiles
     } else {
         pl.spans.on = 0u;
     }

@@ -459,7 +459,10 @@ __device__ __forceinline__ void diag_tile_record(float* rgb_linear, uint32_t bx,
 // 4 * wave + 3, all eight columns -- and ray pl < 32 is the pixel x = (pl >> 4 & 1) * 4 + (pl & 3), y = pl >> 2 & 3 of the half: pl >> 4
 // is the 4x4 quadrant inside the half and pl & 15 the pixel of that quadrant as the four-wave form numbers it, so ray pl of half h is
 // entry 32 * h + pl of the tile's root masks and bit 32 * h + pl of the tile's shadow words.
-template <bool COUNT, int NQCAP, int TWL, int THL, bool FILTER, bool CAM = false, bool WIDE = false, bool HALF = false>
+// OWN_ROOTS (with HALF and !WIDE, and only where `own_roots` is set): nobody has tested the roots for this wave -- it has no partner and
+// no launch-time barrier (k_trace_nq_wave8_spans) -- so it puts its own 32 rays through the root table, one (ray, object) pair per lane,
+// and queues for a passing root what the root_pass branch queues: the same pairs in the same order.
+template <bool COUNT, int NQCAP, int TWL, int THL, bool FILTER, bool CAM = false, bool WIDE = false, bool HALF = false, bool OWN_ROOTS = false>
 __device__ __forceinline__ void closest_hit_phase(const DevScene& s, const DevParams& p, uint32_t* nq, uint32_t* tq,
                                                   unsigned long long* best, float4* dir,
                                                   int32_t* __restrict__ hit_id, float* __restrict__ t_out,
@@ -468,9 +471,11 @@ __device__ __forceinline__ void closest_hit_phase(const DevScene& s, const DevPa
                                                   const uint32_t bx, const uint32_t by, const uint32_t gx,      // workgroup tile coordinates, tiles per row
                                                   const uint32_t wave,                                          // quadrant of the tile this wave owns
                                                   uint32_t* __restrict__ qcount = nullptr, uint32_t* __restrict__ qlist = nullptr, uint32_t qcap = 0,   // list of quadrants with hits (4x4 waves only)
-                                                  const uint32_t* root_pass = nullptr) {      // per ray of this quadrant: which objects' ROOT boxes it passes (bit = object), from
+                                                  const uint32_t* root_pass = nullptr,        // per ray of this quadrant: which objects' ROOT boxes it passes (bit = object), from
                                                                                               // finish_background_tile, which has put all 64 rays of the tile through every root already
+                                                  const bool own_roots = false) {             // OWN_ROOTS: the wave tests the roots itself and queues their children (at most 32 objects)
     constexpr int P = 1 << (TWL + THL);           // rays per wavefront
+    static_assert(!OWN_ROOTS || (HALF && !WIDE && !COUNT), "the wave's own root pass is the half-tile form's, over the 32 B records");
     const uint32_t lane = threadIdx.x & 63;
     const float4* nodes4 = reinterpret_cast<const float4*>(s.nodes);
     const float4* tris4 = reinterpret_cast<const float4*>(s.tris);
@@ -676,7 +681,38 @@ __device__ __forceinline__ void closest_hit_phase(const DevScene& s, const DevPa
     for (uint32_t obj0 = 0; obj0 < n_obj && nlive; obj0 += OBJ_G) {
         // roots of up to OBJ_G objects for every live pixel, in chunks of 64 (node, pixel) pairs
         const uint32_t g = (n_obj - obj0) < OBJ_G ? (n_obj - obj0) : OBJ_G;
-        if (!COUNT && root_pass) {
+        if (OWN_ROOTS && own_roots) {      // (a constant false where OWN_ROOTS is: those builds get the statement below as they always did)
+            // the wave's own root pass: the record from the contiguous root table (index = object: nothing waits for obj_range), the
+            // filtered test with the exact fallback, and a passing root queues its two children, or its triangles, as below
+            for (uint32_t base = 0; base < P * g; base += 64) {
+                const uint32_t k = base + lane_again(lane);
+                const uint32_t pl = k & (P - 1), ob = k >> (TWL + THL);
+                bool ok = k < P * g && ((livem >> pl) & 1ull);
+                int32_t root = 0, info = -1;
+                if (ok) {
+                    const float4* rn = reinterpret_cast<const float4*>(s.root_nodes) + 2 * (size_t)(obj0 + ob);
+                    const float4 a = rn[0], b = rn[1];
+                    root = s.obj_range[obj0 + ob].x;
+                    const float4 dxy = dir[pl];
+                    const V3 d = mk(dxy.x, dxy.y, CAM ? dxy.z : p.focal);
+                    RayRcp rc;
+                    if (CAM) rc = ray_rcp(d);
+                    else { rc.x = dxy.z; rc.y = dxy.w; rc.z = __builtin_fmaf(dxy.z, 0.0f, rcp_focal); }      // rcp_focal, or NaN with the other two (ray_rcp's rule)
+                    info = __float_as_int(b.w);
+                    ok = slab_pass<FILTER>(o, d, rc, a.x, a.y, a.z, a.w, b.x, b.y);
+                }
+                const bool inner = ok && info < 0, leafp = ok && info >= 0 && (info & LEAF_MAX) != 0;
+                const unsigned long long im = __ballot(inner);
+                if (inner) {
+                    uint32_t pos = nqn + 2 * lane_prefix(im), pos1 = pos + 1;
+                    if (!(p.exp & 1u)) { pos = nqn + lane_prefix(im); pos1 = pos + (uint32_t)__popcll(im); }      // node-major
+                    nq[pos] = ((uint32_t)(~info) << 6) | pl;          // right child
+                    nq[pos1] = ((uint32_t)(root + 1) << 6) | pl;      // left child on top: popped first
+                }
+                nqn += 2 * (uint32_t)__popcll(im);
+                leaf_queue_push(tq, tqn, (uint32_t)info, leafp, pl, tri_batch);
+            }
+        } else if (!COUNT && root_pass) {
             // the root tests are done (wave 0 ran them for the whole tile with full lanes): queue what a passing root queues -- its two
             // children, or its triangles -- and skip the first node step, which would run at 16 rays x 2 roots = 32 of 64 lanes
             for (uint32_t base = 0; base < P * g; base += 64) {
@@ -1643,8 +1679,16 @@ __device__ __forceinline__ void shade_hit_pixel(const DevScene& s, const DevPara
 // The tile's root masks wait in the two waves' own shadow masks (rays 32h .. 32h + 31 in half_all[h].shadow.mask[0 .. 31]): wave h alone writes
 // that array again, in its shadow phase, after it has read them -- 256 B less -- and a wave's dir[] and best[] lie over the front of its
 // ShadowLds (HalfTileLds, with the lifetimes): nine LDS granules a workgroup, fourteen workgroups per CU with the 72 VGPRs of a 7-wave build.
+// ONE (with HALF, over tile spans only): the workgroup is ONE wave, a half tile.  Blocks 2b and 2b + 1 of a grid row are the upper and
+// lower half of the tile that block b of the two-wave form owns, so the grid is twice as wide and the span table still counts tiles.  No
+// tile-wide root pass, no barrier and no root masks: the wave tests the roots of its own 32 rays (closest_hit_phase's OWN_ROOTS) and
+// leaves the CU -- with its LDS -- when it is done, whatever the tile's other half is doing.  ONE == 2, the dispatch order that ships (ONE ==
+// 1 is kept under variant 32): a tile's halves EIGHT workgroups apart -- blocks 16g .. 16g + 7 are the upper halves of tiles 8g .. 8g + 7,
+// the next eight their lower halves -- on a grid row padded to a multiple of sixteen, so that both halves of a tile run on one XCD
+// (workgroups are dealt round-robin over the eight) and read their records through the same L2: 39 % of the L2 requests miss instead of
+// 44 %, and the headline step is another 1.3 % shorter.
 template <bool COUNT, int NQCAP, bool FILTER, int RS, bool XCD_ROWS, bool ROOTS_AGAIN, bool SHADE = false, bool CAM = false, bool WIDE = false, bool ROW_Z = false,
-          bool HALF = false>
+          bool HALF = false, int ONE = 0>
 __device__ __forceinline__ void trace_nq_body(const DevScene& s, const DevParams& p, int32_t* __restrict__ hit_id, float* __restrict__ t_out,
                                               float* __restrict__ rgb_linear, uint8_t* __restrict__ rgb8,
                                               unsigned long long* __restrict__ shadow_bits, unsigned long long* __restrict__ counters,
@@ -1658,7 +1702,28 @@ __device__ __forceinline__ void trace_nq_body(const DevScene& s, const DevParams
     // the boxes it was captured with in its arguments.  It keeps the full grid; a workgroup outside the spans leaves only if the records'
     // epoch word -- rewritten in stream order by every upload, pose and refit -- still is the table's, and otherwise does a tile's whole
     // work, as k_shade_tile_spans then shades every tile.  A workgroup inside the spans never reads the word.
+    static_assert(!ONE || HALF, "one wave per workgroup is a half tile");
     uint32_t span_bx = blockIdx.x, span_by = blockIdx.y; bool span_on = false;
+    if constexpr (ONE != 0) {      // the same prologue for two workgroups a tile (stated apart: the other builds keep their code to the byte)
+        const uint32_t blk_x = ONE == 2 ? ((blockIdx.x >> 4) << 3) | (blockIdx.x & 7u) : blockIdx.x >> 1;      // the workgroup's tile in its grid row
+        if (ONE == 2 && blk_x >= (p.W + 7u) / 8u) return;      // (the padding of a captured launch's whole grid; a span's is beyond the span)
+        span_bx = blk_x;
+        if (!box_epoch) {
+            uint32_t row0 = spans->row0;
+            uint32_t sp = reinterpret_cast<const uint32_t*>(spans->row)[blockIdx.y < TILE_SPAN_ROWS ? blockIdx.y : TILE_SPAN_ROWS - 1u];      // x0 | n << 16
+            asm volatile("" : "+s"(sp), "+s"(row0));
+            if (blk_x >= (sp >> 16)) return;
+            span_on = true;
+            span_by = row0 + blockIdx.y;
+            span_bx = (sp & 0xffffu) + blk_x;
+        } else {
+            uint32_t sp = reinterpret_cast<const uint32_t*>(spans->row)[blockIdx.y < TILE_SPAN_ROWS ? blockIdx.y : TILE_SPAN_ROWS - 1u];
+            uint32_t n_rows = spans->n_rows;
+            asm volatile("" : "+s"(sp), "+s"(n_rows));
+            const bool outside = blockIdx.y >= n_rows || blk_x - (sp & 0xffffu) >= (sp >> 16);
+            if (outside && *box_epoch == spans->epoch) return;
+        }
+    } else
     if (spans) {
         if (!box_epoch) {
             uint32_t row0 = spans->row0;
@@ -1685,10 +1750,12 @@ __device__ __forceinline__ void trace_nq_body(const DevScene& s, const DevParams
         if (qcount && blockIdx.x == 0 && blockIdx.y == 0) for (uint32_t i = threadIdx.x; i < (uint32_t)QL_COUNTERS; i += 256u) qcount[i * QL_STRIDE] = 0u;
     }
     static_assert(!HALF || (!SHADE && !COUNT), "the half-tile form has no one-launch and no counting build");
-    constexpr int NW = HALF ? 2 : 4, P = HALF ? 32 : NQ_P;      // waves per tile, rays per wave
+    static_assert(!ONE || (!XCD_ROWS && !ROW_Z && !CAM && !ROOTS_AGAIN), "one wave per workgroup: the plain tile order of a frame with spans only");
+    constexpr int NW = ONE ? 1 : HALF ? 2 : 4, P = HALF ? 32 : NQ_P;      // waves per workgroup, rays per wave
     __shared__ uint32_t nq_all[NW][NQCAP];
     __shared__ uint32_t tq_all[NW][LQ_WORDS];
-    const uint32_t wave = threadIdx.x >> 6;
+    const uint32_t wave = ONE == 2 ? (blockIdx.x >> 3) & 1u : ONE ? blockIdx.x & 1u : threadIdx.x >> 6;      // which part of the tile the wave owns (ONE: the half, from the grid)
+    const uint32_t wq = ONE ? 0u : wave;                                 // ... and which of the workgroup's LDS sets
     ShadowLds<RS, P>* L;                                        // this wave's shadow-phase LDS (HALF: inside the wave's HalfTileLds)
     int32_t id; float t; V3 d;
     unsigned long long k0 = 0, k1 = 0; (void)k0; (void)k1;
@@ -1698,7 +1765,7 @@ __device__ __forceinline__ void trace_nq_body(const DevScene& s, const DevParams
     // XCD gets whole rows of tiles -- XCD j walks tile rows j, j + 8, ... left to right -- so that neighbouring tiles, which
     // read the same nodes and triangles, hit in the same L2: 1 M-triangle soup -15 %.  For a scene of a few MB the plain
     // order is as good or slightly better (K3: +1 % with the row deal, +2 % with a run-time switch), so it has its own build.
-    const uint32_t gx = span_on ? (p.W + 7u) / 8u : gridDim.x;      // tiles per row of the FRAME: the shadow words and the quadrant list are indexed by tile
+    const uint32_t gx = ONE ? (p.W + 7u) / 8u : span_on ? (p.W + 7u) / 8u : gridDim.x;      // tiles per row of the FRAME (ONE: only whole frames, and the grid counts half tiles): the shadow words and the quadrant list are indexed by tile
     uint32_t bx = span_bx, by = ROW_Z ? blockIdx.z : span_by;      // ROW_Z: a batch launched with the tile row in z and the frame in y
     if (XCD_ROWS) {
         const uint32_t w = blockIdx.y * gx + blockIdx.x, idx = w >> 3;
@@ -1714,12 +1781,24 @@ __device__ __forceinline__ void trace_nq_body(const DevScene& s, const DevParams
         using Shadow = ShadowLds<RS, P>;
         static_assert(sizeof(half_all[0].closest) <= offsetof(Shadow, mask), "dir[] and best[] end at or before the root masks that wait in ShadowLds::mask");
         static_assert(sizeof(HalfTileLds<RS, P>) == sizeof(Shadow) && sizeof(Shadow) % 4 == 0, "the stride between the two waves' masks is counted in words");
+        if constexpr (ONE) {
+            // a half with no live pixel (the lower one of a last tile row that is cut at or above its middle) has nothing to write: its
+            // shadow bits belong to pixels that do not exist.  Every other wave goes straight into the phase, which tests the roots of
+            // its own rays (32 objects at most; more keep the queue path) -- a wave none of whose rays passes a root writes its misses
+            // through the phase's write-out, and the shadow phase's quick exit leaves its half of the tile's words all-clear
+            if (by * 8u + wave * 4u >= p.rows) return;
+            SRT_STAMP(ka);
+            closest_hit_phase<COUNT, NQCAP, 3, 2, FILTER, CAM, WIDE, true, true>(s, p, nq_all[0], tq_all[0], half_all[0].closest.best, half_all[0].closest.dir,
+                                                                           hit_id, t_out, rgb_linear, rgb8, counters, id, t, d, bx, by, gx, wave, nullptr, nullptr, 0,
+                                                                           nullptr, roots_done);
+        } else {
         if (finish_background_tile<FILTER, CAM>(s, p, hit_id, t_out, rgb_linear, rgb8, shadow_bits, bx, by, gx, half_all[0].shadow.mask, sizeof(HalfTileLds<RS, P>) / 4)) return;
         SRT_STAMP(ka);
         closest_hit_phase<COUNT, NQCAP, 3, 2, FILTER, CAM, WIDE, true>(s, p, nq_all[wave], tq_all[wave], half_all[wave].closest.best, half_all[wave].closest.dir,
                                                                  hit_id, t_out, rgb_linear, rgb8, counters, id, t, d, bx, by, gx, wave, nullptr, nullptr, 0,
                                                                  roots_done ? half_all[wave].shadow.mask : nullptr);
-        L = &half_all[wave].shadow;
+        }
+        L = &half_all[wq].shadow;
         // `closest` is dead from here and `shadow` (but its mask) not yet written: the phases' accesses to the shared bytes stay on their
         // sides of this fence (no instruction: the LDS keeps a wave's accesses in order) and of the wave barrier below
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
@@ -1736,7 +1815,7 @@ __device__ __forceinline__ void trace_nq_body(const DevScene& s, const DevParams
     }
     __builtin_amdgcn_wave_barrier();
     SRT_STAMP(kb);
-    shadow_phase<COUNT, NQCAP, FILTER, RS, true, WIDE, P>(s, p, nq_all[wave], tq_all[wave], *L, id, t, d, shadow_bits, counters, bx, by, gx, wave);
+    shadow_phase<COUNT, NQCAP, FILTER, RS, true, WIDE, P>(s, p, nq_all[wq], tq_all[wq], *L, id, t, d, shadow_bits, counters, bx, by, gx, wave);
 #ifdef SRT_DIAG
     SRT_STAMP(k1); diag_tile_record(rgb_linear, bx, by, gx, k0, k1, ka, kb);
 #endif
@@ -1817,6 +1896,23 @@ void k_trace_nq_half8_spans(DevScene s, DevParams p, int32_t* __restrict__ hit_i
                             unsigned long long* __restrict__ shadow_bits, unsigned long long* __restrict__ counters,
                             const uint32_t* __restrict__ box_epoch, const TileSpans spans) {
     trace_nq_body<false, NQCAP, FILTER, RS, false, false, false, false, false, false, true>(s, p, hit_id, t_out, rgb_linear, rgb8, shadow_bits, counters, nullptr, nullptr, &spans, box_epoch);
+}
+// The eight-wave build over the tile spans as workgroups of ONE wave (trace_nq_body's ONE): launched with 64 threads on a grid twice as
+// wide as the spans' (XCD_PAIRS, shipped: padded to groups of eight tiles, eight upper halves, then their lower halves; else blocks 2b and
+// 2b + 1 the two halves of tile b).  A wave of the two-wave form's lower half waits at the launch-time
+// barrier while wave 0 tests the tile's roots, and a workgroup's LDS -- sixteen workgroups fill a CU's -- stays taken until its slower
+// wave is done; here a wave starts on its own rays at once and its slot and its four LDS granules (5,056 B: thirty-two workgroups a CU)
+// are free the moment it ends.  Under the spans nearly every tile that reaches the phases is live, so the price -- the root tests run
+// at 32 rays x 2 objects a pass instead of 64 rays a pass -- is paid where the tile-wide pass bought nothing.  There is no twin for frames
+// without a table: there two thirds of the tiles are background, and one wave's 64 root tests beat two waves' 32 each.
+// XCD_PAIRS: trace_nq_body's ONE == 2, a tile's halves on one XCD (what variant 0 launches; false: variant 32).
+template <int NQCAP, bool FILTER, int RS, bool XCD_PAIRS = false>
+__global__ __launch_bounds__(64, 8) SRT_NO_PACKED_F32
+void k_trace_nq_wave8_spans(DevScene s, DevParams p, int32_t* __restrict__ hit_id, float* __restrict__ t_out,
+                            float* __restrict__ rgb_linear, uint8_t* __restrict__ rgb8,
+                            unsigned long long* __restrict__ shadow_bits, unsigned long long* __restrict__ counters,
+                            const uint32_t* __restrict__ box_epoch, const TileSpans spans) {
+    trace_nq_body<false, NQCAP, FILTER, RS, false, false, false, false, false, false, true, XCD_PAIRS ? 2 : 1>(s, p, hit_id, t_out, rgb_linear, rgb8, shadow_bits, counters, nullptr, nullptr, &spans, box_epoch);
 }
 // closest hit, shadow rays and shading of a frame in one launch (SHADE)
 template <int NQCAP, bool FILTER, int MINW, int RS, bool XCD_ROWS = false>

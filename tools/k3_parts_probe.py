@@ -2,8 +2,9 @@
 """Where the K3 frame's time goes by part of the image: the bench scene (bunny over the ground slab) against the same frame with
 only the slab and only the bunny, each at 1920x1080 with one light sample -- per-kernel HIP-event times of eager launches and
 the wall time per frame with frames overlapped on 4 streams (srt_scene_share handles), without and with SRT_FLAG_FRAMES_IN_FLIGHT
-(four waves per tile / the half-tile seven-wave build the headline runs).  --variant N: the kernel selector of every frame (64: the
-full grid, tile spans off -- "far" is then 32,400 background tiles again)."""
+(four waves per tile / what the headline runs: the half-tile eight-wave build, over tile spans as workgroups of one wave,
+k_trace_nq_wave8_spans).  --variant N: the kernel selector of every frame (64: the full grid, tile spans off -- "far" is then 32,400
+background tiles again; 67: two-wave workgroups over the spans, k_trace_nq_half8_spans; 31: the one-wave workgroups in both columns)."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -62,7 +63,7 @@ def main():
                 w = (time.perf_counter() - t0) / n * 1e3
                 best = w if best is None or w < best else best
             return best
-        # four-wave tiles, and what the headline runs: the half-tile seven-wave build under the frames-in-flight hint
+        # four-wave tiles, and what the headline runs: the half-tile eight-wave build under the frames-in-flight hint
         w4, wh = wall(0), wall(abi.SRT_FLAG_FRAMES_IN_FLIGHT)
         print(f"{'+'.join(parts):12s} hit px {sc['hit_rays']:8d}  tests {sc['node_tests'] + sc['tri_tests']:10d}   trace {st['ms_primary'] + st['ms_shadow']:.4f}  shade {st['ms_shade']:.4f} ms alone;"
               f"  {w4:.4f} ms per frame on 4 streams (eager), {wh:.4f} with frames in flight (half tiles)", flush=True)

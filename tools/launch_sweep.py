@@ -20,8 +20,10 @@ sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 # estimates 3.7, 11.7, 17.4, 214 and 478; main_nocats with vertex normals is 36.9 MB of records (over 32 MiB: whole tile rows per XCD), the soups 3.3 and 31.7 MB
 SCENES = ("cube_ground", "ground_bunny", "main_nocats", "soup20k", "soup200k")
-SELECTORS = (0, 1, 2, 3, 4, 5, 6, 9, 10, 11, 12, 13, 17, 18, 20, 21, 22, 23, 24, 25, 27, 28, 29, 35, 40, 41, 42, 43, 44, 45, 46, 47,
-             53, 54, 55, 56, 57, 58, 62, 99)
+# (31 and 67 -- the one-wave workgroups of the trace kernel over tile spans without the in-flight hint, and the two-wave workgroups in
+# their place -- came after the listing of profiles/launch_sweep.txt: its digests are those of this tuple without them)
+SELECTORS = (0, 1, 2, 3, 4, 5, 6, 9, 10, 11, 12, 13, 17, 18, 20, 21, 22, 23, 24, 25, 27, 28, 29, 31, 35, 40, 41, 42, 43, 44, 45, 46, 47,
+             53, 54, 55, 56, 57, 58, 62, 67, 99)
 LIGHTS = (0, 1, 7, 8, 15, 16, 63, 64)
 
 
