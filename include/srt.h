@@ -1162,4 +1162,5 @@ uint32_t    srt_abi_version(void);
 #include "srt_nearest.h"      /* the same query with a bound that shrinks: no radius to choose */
 #include "srt_signed.h"       /* that distance with a sign, and containment, by winding along a few rays */
 #include "srt_points_multi.h" /* the K nearest triangles per point, in either walk: all contacts within a radius */
+#include "srt_segments.h"     /* the nearest triangle to a SEGMENT within a radius: swept particles, capsules, clearance along a path */
 #endif /* SRT_H */

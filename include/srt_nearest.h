@@ -55,7 +55,7 @@ extern "C" {
  * at least the mandatory set's: the nodes all of whose ancestors pass the radius test with low <= the final dist2, and the triangles of
  * such leaves.  A node pruned by the bound counts as tested.
  * NOT HERE: a near-child-first order (the node layout has one order).  (The K nearest, pruned by the k-th best: see srt_points_multi.h.
- * A sign: see srt_signed.h.) */
+ * A sign: see srt_signed.h.  The distance of a SEGMENT, within a radius that does not shrink: see srt_segments.h.) */
 #define SRT_NEAREST_K 64     /* a power of two; at least four times the measured worst deficit (profiles/nearest_margin.txt) */
 int srt_nearest_points_device(srt_scene* s, uint32_t n, const float* d_points /* n x 3 */, const float* d_radius /* n or NULL */,
                               const uint32_t* d_point_mask /* n or NULL */, uint32_t flags, void* stream, const srt_point_out* out);

@@ -60,7 +60,8 @@ extern "C" {
  * NOT HERE: a shrinking radius (above; see srt_nearest.h); a SIGN -- the distance is unsigned; see srt_signed.h, which counts the sign
  * along rays; `region` serves a caller who keeps pseudo-normals of their own (face, edge or vertex normal by region) --; the K nearest
  * triangles, and how many lie within the radius: see srt_points_multi.h (n_within > 0 is the any-within-radius answer, without the early
- * stop). */
+ * stop); the distance of a SEGMENT -- a particle's step, a capsule, a path with a width --: see srt_segments.h, whose point segments are
+ * this call bit for bit. */
 typedef struct srt_point_out {    /* device pointers in the _device form, host pointers in the host form */
     int32_t* tri;                /* n       canonical triangle id, -1 = none within the radius */
     float*   dist2;              /* n       the winner's dist2 with its own bits, +inf = none */

@@ -1,8 +1,8 @@
 """ctypes mirror of include/srt.h -- its structs (STRUCTS), constants (SRT_*) and prototypes (PROTOTYPES), checked against the header by
 tests/test_abi_mirror.py --, of its extension headers include/srt_points.h (POINT_STRUCTS, POINT_PROTOTYPES; tests/test_point_ref.py),
 include/srt_nearest.h (NEAREST_PROTOTYPES; tests/test_nearest_ref.py), include/srt_signed.h (SIGNED_STRUCTS, SIGNED_PROTOTYPES;
-tests/test_sign_ref.py) and include/srt_points_multi.h (POINT_MULTI_STRUCTS, POINT_MULTI_PROTOTYPES; tests/test_points_multi_ref.py), and
-a numpy container for the flat scene.
+tests/test_sign_ref.py), include/srt_points_multi.h (POINT_MULTI_STRUCTS, POINT_MULTI_PROTOTYPES; tests/test_points_multi_ref.py) and
+include/srt_segments.h (SEGMENT_STRUCTS, SEGMENT_PROTOTYPES; tests/test_segment_ref.py), and a numpy container for the flat scene.
 
 The flat scene is the reference's ObjectManager state (Object.h:59-89 in the reference) written out as
 arrays; see include/srt.h for the layout contract.  This module holds no compute.
@@ -251,6 +251,18 @@ POINT_MULTI_FIELDS = {"n_within": (np.uint32, None), "n_found": (np.uint32, None
 POINT_MULTI_STRUCTS = {"srt_point_multi_out": PointMultiOut}
 
 
+class SegmentOut(C.Structure):
+    """srt_segment_out: the arrays a segment query fills, as addresses (host arrays in the host form, device pointers in the _device
+    form); 0 = not wanted."""
+    _fields_ = [("tri", C.c_void_p), ("dist2", C.c_void_p), ("s", C.c_void_p), ("point", C.c_void_p), ("vw", C.c_void_p), ("feature", C.c_void_p)]
+
+
+# the fields of srt_segment_out: name -> (dtype, entries per segment)
+SEGMENT_FIELDS = {"tri": (np.int32, 1), "dist2": (np.float32, 1), "s": (np.float32, 1), "point": (np.float32, 3), "vw": (np.float32, 2), "feature": (np.uint8, 1)}
+# every struct of include/srt_segments.h
+SEGMENT_STRUCTS = {"srt_segment_out": SegmentOut}
+
+
 # ---- the prototypes of include/srt.h, in its order: name -> (restype, [argtypes]) ----
 # srt_scene*, void* and every address that travels as an int (the d_* parameters, a stream, srt_render_async's outputs) are c_void_p;
 # srt_scene** and T* const* are POINTER(c_void_p); a pointer to an srt_ struct is POINTER(its class); a scalar is its exact ctype.
@@ -394,6 +406,13 @@ POINT_MULTI_PROTOTYPES.update({
     "srt_nearest_points_multi_device": POINT_MULTI_PROTOTYPES["srt_closest_points_multi_device"],
     "srt_nearest_points_multi": POINT_MULTI_PROTOTYPES["srt_closest_points_multi"],
 })
+
+# ---- include/srt_segments.h: its prototypes, in its order, under the same rules ----
+_sgout = C.POINTER(SegmentOut)
+SEGMENT_PROTOTYPES = {
+    "srt_closest_segments_device": (_int, [_vp, _u32, _vp, _vp, _vp, _u32, _vp, _sgout]),
+    "srt_closest_segments": (_int, [_vp, _u32, _f32p, _f32p, _u32p, _u32, _sgout, _stats]),
+}
 
 
 def _ptr(a, ty):

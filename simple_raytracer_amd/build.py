@@ -12,7 +12,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB_HIP = os.path.join(HERE, "libsrt_hip.so")
 HIP_SRC = os.path.join(CSRC, "srt_hip.hip")
 # What libsrt_hip.so, and every measurement variant of it, is compiled from: the one translation unit and the headers it includes.
-HIP_DEPS = [HIP_SRC] + [os.path.join(CSRC, f) for f in ("srt_device.h", "srt_kernels.h", "srt_packet.h", "srt_query.h", "srt_tile_spans.h")] + [os.path.join(HERE, "..", "include", f) for f in ("srt.h", "srt_points.h", "srt_nearest.h", "srt_signed.h", "srt_points_multi.h")]
+HIP_DEPS = [HIP_SRC] + [os.path.join(CSRC, f) for f in ("srt_device.h", "srt_kernels.h", "srt_packet.h", "srt_query.h", "srt_tile_spans.h")] + [os.path.join(HERE, "..", "include", f) for f in ("srt.h", "srt_points.h", "srt_nearest.h", "srt_signed.h", "srt_points_multi.h", "srt_segments.h")]
 
 # -ffp-contract=off is part of the numerical contract: FMA contraction changes hit results
 # (SURVEY.md H1).  Correctly rounded f32 divide / sqrt are hipcc defaults and must stay on.
@@ -56,7 +56,7 @@ HOST_FLAGS = ["-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-Wa
 HOST_DIR = os.path.join(CSRC, "host")
 HOST_CPU_SRCS = [os.path.join(HOST_DIR, f) for f in ("srt_host.cpp", "srt_jpeg.cpp")]
 HOST_SRCS = HOST_CPU_SRCS + [os.path.join(HOST_DIR, f) for f in ("srt_host_render.cpp", "srt_host_c.cpp")]
-HOST_DEPS = HOST_SRCS + [os.path.join(HOST_DIR, f) for f in ("srt_host.h", "srt_host_internal.h", "srt_host_c.h")] + [os.path.join(HERE, "..", "include", f) for f in ("srt.h", "srt_points.h", "srt_nearest.h", "srt_signed.h", "srt_points_multi.h")]
+HOST_DEPS = HOST_SRCS + [os.path.join(HOST_DIR, f) for f in ("srt_host.h", "srt_host_internal.h", "srt_host_c.h")] + [os.path.join(HERE, "..", "include", f) for f in ("srt.h", "srt_points.h", "srt_nearest.h", "srt_signed.h", "srt_points_multi.h", "srt_segments.h")]
 
 
 def build_host(force=False, verbose=False):
@@ -154,6 +154,22 @@ def build_surface_lane_stores(force=False):
     return LIB_SURFACE_LANE
 
 
+LIB_SEGMENTS_NO_BOX_TEST_2 = os.path.join(HERE, "libsrt_hip_segments_no_box_test_2.so")
+
+
+def build_segments_no_box_test_2(force=False):
+    """The segment query without its second box test (-DSRT_SEGMENTS_NO_BOX_TEST_2, srt_query.h): libsrt_hip_segments_no_box_test_2.so, never
+    loaded by the product; tools/ray_query_probe.py --segments times it beside the shipped library."""
+    if not force and not _stale(LIB_SEGMENTS_NO_BOX_TEST_2, HIP_DEPS):
+        return LIB_SEGMENTS_NO_BOX_TEST_2
+    cmd = [hipcc()] + HIPCC_FLAGS + ["-DSRT_SEGMENTS_NO_BOX_TEST_2", "-o", LIB_SEGMENTS_NO_BOX_TEST_2, HIP_SRC]
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    if r.returncode:
+        sys.stderr.write(r.stdout + r.stderr)
+        raise RuntimeError("hipcc failed for the build without box test 2")
+    return LIB_SEGMENTS_NO_BOX_TEST_2
+
+
 LIB_AO_DEAL = {True: os.path.join(HERE, "libsrt_hip_ao_spread.so"), False: os.path.join(HERE, "libsrt_hip_ao_block.so")}
 
 
@@ -175,6 +191,8 @@ def build_ao_deal(spread, force=False):
 if __name__ == "__main__":
     if "--ao-deals" in sys.argv:
         print(build_ao_deal(True), build_ao_deal(False))
+    elif "--segments-no-box-test-2" in sys.argv:
+        print(build_segments_no_box_test_2())
     elif "--diag" in sys.argv:
         print(build_diag(verbose=True))
     elif "--surface-lane-stores" in sys.argv:

@@ -1971,6 +1971,25 @@ static int points_multi_device_impl(srt_scene* s, uint32_t n, const float* d_poi
                         query_mask(s, d_point_mask));
 }
 
+// srt_closest_segments (include/srt_segments.h): the nearest triangle within a radius per segment, one launch (k_query_segments).  A call
+// with a mask array launches the MASK build; one without launches the build that reads neither the array nor the scene's table.
+static inline bool segments_wanted(const srt_segment_out* o) { return o->tri || o->dist2 || o->s || o->point || o->vw || o->feature; }
+static int check_segments(const srt_scene* s, uint32_t n, const float* segments, uint32_t flags, const srt_segment_out* out) {
+    SRT_TRY(check_query(s, n, segments, flags));
+    if (!out) return SRT_ERR_ARG;
+    return SRT_OK;
+}
+static int segments_device_impl(srt_scene* s, uint32_t n, const float* d_segments, const float* d_radius, const uint32_t* d_seg_mask, uint32_t flags,
+                                hipStream_t stream, const srt_segment_out* out, bool count_hits) {
+    SRT_TRY(check_segments(s, n, d_segments, flags, out));
+    if (!n || (!count_hits && !segments_wanted(out))) return SRT_OK;
+    const bool count = (flags & SRT_FLAG_COUNT_WORK) != 0;
+    QueryLaunch q;
+    SRT_TRY(query_prologue(s, n, stream, nullptr, count || count_hits, &q));
+    static const std::array builds = { BUILDS_2(k_query_segments) };
+    return launch_query(builds[build_index(count, d_seg_mask)], q.grid, q.stream, s->dev, n, d_segments, d_radius, *out, q.ctr, query_mask(s, d_seg_mask));
+}
+
 // srt_signed_points (include/srt_signed.h): srt_nearest_points' outputs and a sign by winding along the rays of a direction table, one
 // launch (k_query_signed).  No sign output wanted: the call IS srt_nearest_points, with that call's kernels, and `sign` is not read.
 // NEAR: whether the nearest phase runs -- a point output or sdist is wanted; without it hit_rays is 0.
@@ -2354,6 +2373,21 @@ static int points_multi_impl(srt_scene* s, uint32_t n, const float* points, cons
         const srt_point_multi_out dev = { o_nw.on_device(), o_nf.on_device(), o_tri.on_device(), o_d2.on_device(), o_pt.on_device(), o_vw.on_device(), o_reg.on_device() };
         return points_multi_device_impl(s, n, i_pts.on_device(), i_rad.on_device(), i_mask.on_device(), k, flags, st, &dev, stats != nullptr, nearest);
     }, o_nw, o_nf, o_tri, o_d2, o_pt, o_vw, o_reg, i_pts, i_rad, i_mask));
+    return stats ? query_stats(s, n, 0, stats) : SRT_OK;
+}
+
+static int segments_impl(srt_scene* s, uint32_t n, const float* segments, const float* radius, const uint32_t* seg_mask, uint32_t flags,
+                         const srt_segment_out* out, srt_stats* stats) {
+    SRT_TRY(check_segments(s, n, segments, flags, out));
+    if (stats) std::memset(stats, 0, sizeof(*stats));
+    if (!n) return SRT_OK;
+    auto o_tri = query_out(out->tri, n); auto o_d2 = query_out(out->dist2, n); auto o_s = query_out(out->s, n); auto o_pt = query_out(out->point, 3ull * n);
+    auto o_vw = query_out(out->vw, 2ull * n); auto o_feat = query_out(out->feature, n);
+    auto i_seg = query_in(segments, 6ull * n); auto i_rad = query_in(radius, n); auto i_mask = query_in(seg_mask, n);
+    SRT_TRY(query_round_trip(s, false, [&](hipStream_t st) {
+        const srt_segment_out dev = { o_tri.on_device(), o_d2.on_device(), o_s.on_device(), o_pt.on_device(), o_vw.on_device(), o_feat.on_device() };
+        return segments_device_impl(s, n, i_seg.on_device(), i_rad.on_device(), i_mask.on_device(), flags, st, &dev, stats != nullptr);
+    }, o_tri, o_d2, o_s, o_pt, o_vw, o_feat, i_seg, i_rad, i_mask));
     return stats ? query_stats(s, n, 0, stats) : SRT_OK;
 }
 
@@ -2844,6 +2878,14 @@ int srt_nearest_points_multi_device(srt_scene* s, uint32_t n, const float* d_poi
 int srt_nearest_points_multi(srt_scene* s, uint32_t n, const float* points, const float* radius, const uint32_t* point_mask, uint32_t k, uint32_t flags,
                              const srt_point_multi_out* out, srt_stats* stats) {
     return guarded([&] { return points_multi_impl(s, n, points, radius, point_mask, k, flags, out, stats, true); });
+}
+int srt_closest_segments_device(srt_scene* s, uint32_t n, const float* d_segments, const float* d_radius, const uint32_t* d_seg_mask, uint32_t flags,
+                                void* stream, const srt_segment_out* out) {
+    return guarded([&] { return segments_device_impl(s, n, d_segments, d_radius, d_seg_mask, flags, (hipStream_t)stream, out, false); });
+}
+int srt_closest_segments(srt_scene* s, uint32_t n, const float* segments, const float* radius, const uint32_t* seg_mask, uint32_t flags,
+                         const srt_segment_out* out, srt_stats* stats) {
+    return guarded([&] { return segments_impl(s, n, segments, radius, seg_mask, flags, out, stats); });
 }
 
 void* srt_host_alloc(size_t bytes) {

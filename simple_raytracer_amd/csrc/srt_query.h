@@ -1814,3 +1814,170 @@ __global__ __launch_bounds__(256) void k_query_points_multi(DevScene s, uint32_t
     if (counters) count_hits(counters, found, blockIdx.x);
     count_walks<COUNT>(counters, n_node, n_tri);
 }
+
+// =================================================================================================
+// Segment queries (srt_closest_segments, include/srt_segments.h): for a segment A-B with radius r, the triangle nearest to it within r.
+// query_walk as it stands with a policy that carries a segment: WalkSegment keeps 7 rows a wave -- A, B and r2 (8 allocated); d = B - A
+// is recomputed from the rows by whichever lane tests a pair, the owner's subtraction on the owner's operands, so every lane has the
+// owner's d AND the owner's B with their own bits.  The reciprocals, r and the sloped flag of box test 2 are read by node() alone and
+// stay in the owning lane's registers.  The radius never shrinks: candidates and counters are a function of the scene and the segment.
+// =================================================================================================
+// The header's triangle function.  The five candidates are a RUNNING minimum -- (dist2, s, v, w, feature), one candidate live at a time:
+// the two ends through closest_point, the three edges through one loop that is not unrolled (origin and dir are selected by the edge's
+// number), so the leaf holds one closest_point and one edge body in registers, not five results.  The crossing overrides them.
+// FULL = false is the walk's leaf, which offers dist2 alone: a crossing is +0 without its closest_point, and everything but dist2 is dead.
+struct SegmentHit { float dist2, s, v, w; uint32_t feature; };
+__device__ __forceinline__ float clamp01(const float x) { return x < 0.0f ? 0.0f : (x > 1.0f ? 1.0f : x); }
+template <bool FULL>
+__device__ __forceinline__ void segment_triangle(SegmentHit& h, const V3 A, const V3 B, const V3 p1, const V3 e1, const V3 e2) {
+    const V3 d = B - A;
+    ClosestPoint c;
+    closest_point(c, A, p1, e1, e2);
+    h.dist2 = c.dist2; h.s = 0.0f; h.v = c.v; h.w = c.w; h.feature = 0u;
+    if (d.x == 0.0f && d.y == 0.0f && d.z == 0.0f) return;      // a point: candidate 0 only
+    const float t = ray_triangle(A, d, p1, e1, e2);
+    if (t != SRT_NEG_INF && t >= 0.0f && t <= 1.0f) {
+        h.dist2 = 0.0f; h.s = t; h.feature = 5u;
+        if (FULL) { closest_point(c, A + d * t, p1, e1, e2); h.v = c.v; h.w = c.w; }
+        return;
+    }
+    closest_point(c, B, p1, e1, e2);
+    if (c.dist2 < h.dist2 || (h.dist2 != h.dist2 && c.dist2 == c.dist2)) { h.dist2 = c.dist2; h.s = 1.0f; h.v = c.v; h.w = c.w; h.feature = 1u; }
+    const float a = dot3(d, d);
+    #pragma nounroll
+    for (uint32_t k = 0; k < 3u; k++) {
+        const V3 origin = k == 1u ? p1 + e1 : p1;
+        const V3 dir = k == 0u ? e1 : k == 1u ? e2 - e1 : e2;
+        const V3 rr = A - origin;
+        const float e = dot3(dir, dir), f = dot3(dir, rr), cc = dot3(d, rr), b = dot3(d, dir);
+        float s = 0.0f, u = 0.0f, num = -cc;
+        bool again = true;                              // s = clamp(num / a), the divide of whichever case asks for it
+        if (e != 0.0f) {
+            const float den = a * e - b * b;
+            s = den > 0.0f ? clamp01((b * f - cc * e) / den) : 0.0f;
+            u = (b * s + f) / e;
+            again = false;
+            if (u < 0.0f) { u = 0.0f; again = true; }
+            else if (u > 1.0f) { u = 1.0f; num = b - cc; again = true; }
+        }
+        if (again) s = clamp01(num / a);
+        const V3 x = (A + d * s) - (origin + dir * u);
+        const float d2 = dot3(x, x);
+        if (d2 < h.dist2 || (h.dist2 != h.dist2 && d2 == d2)) {
+            h.dist2 = d2; h.s = s; h.feature = 2u + k;
+            h.v = k == 0u ? u : k == 1u ? 1.0f - u : 0.0f;
+            h.w = k == 0u ? 0.0f : u;
+        }
+    }
+}
+
+// The segment's tests (query_walk's TESTS).  node: the header's box test 1 -- for a point WalkPoint::axis, operation for operation -- and,
+// for a sloped segment with a finite radius, box test 2.  leaf: the triangle qualifies iff its result's dist2 <= r2 (a NaN fails); dist2
+// is a sum of squares or the crossing's +0 and never -0, so hit_key's order is (dist2, id) order.
+struct WalkSegment {
+    V3 A, B;
+    float r, r2;
+    V3 inv;                          // 1 / d per axis; read only when slab
+    bool slab;                       // the segment is sloped and r < +inf: box test 2 applies
+    static __device__ __forceinline__ bool finite(const float x) { return __builtin_fabsf(x) < __builtin_inff(); }
+    static __device__ __forceinline__ WalkSegment make(const V3 A, const V3 B, const float r) {
+        const V3 d = B - A;
+        const V3 inv = mk(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
+        const bool sloped = finite(d.x) && finite(d.y) && finite(d.z) && d.x != 0.0f && d.y != 0.0f && d.z != 0.0f && finite(inv.x) && finite(inv.y) && finite(inv.z);
+        return WalkSegment{ A, B, r, r * r, inv, sloped && r < __builtin_inff() };
+    }
+    __device__ __forceinline__ void init(float (*rows)[64], const uint32_t lane) const {
+        rows[0][lane] = A.x; rows[1][lane] = A.y; rows[2][lane] = A.z;
+        rows[3][lane] = B.x; rows[4][lane] = B.y; rows[5][lane] = B.z; rows[6][lane] = r2;
+    }
+    static __device__ __forceinline__ float gap(const float mn, const float mx, const float a, const float b) {
+        const float lo = a < b ? a : b, hi = a < b ? b : a;
+        const float e = mn - hi, f = lo - mx;
+        const float g = e > f ? e : f;
+        return g > 0.0f ? g : 0.0f;
+    }
+    __device__ __forceinline__ bool node(const float4 a, const float4 b) const {
+        const float gx = gap(a.x, a.w, A.x, B.x), gy = gap(a.y, b.x, A.y, B.y), gz = gap(a.z, b.y, A.z, B.z);
+        const float b2 = (gx * gx + gy * gy) + gz * gz;
+        if (b2 > r2) return false;
+#ifdef SRT_SEGMENTS_NO_BOX_TEST_2
+        return true;                                    // (a measurement build: what box test 2 buys, tools/ray_query_probe.py --segments)
+#endif
+        if (!slab) return true;
+        const float x0 = ((a.x - r) - A.x) * inv.x, x1 = ((a.w + r) - A.x) * inv.x;
+        const float y0 = ((a.y - r) - A.y) * inv.y, y1 = ((b.x + r) - A.y) * inv.y;
+        const float z0 = ((a.z - r) - A.z) * inv.z, z1 = ((b.y + r) - A.z) * inv.z;
+        const float xn = x0 < x1 ? x0 : x1, xf = x0 < x1 ? x1 : x0;
+        const float yn = y0 < y1 ? y0 : y1, yf = y0 < y1 ? y1 : y0;
+        const float zn = z0 < z1 ? z0 : z1, zf = z0 < z1 ? z1 : z0;
+        float near = 0.0f, far = 1.0f;
+        near = xn > near ? xn : near; near = yn > near ? yn : near; near = zn > near ? zn : near;
+        far = xf < far ? xf : far; far = yf < far ? yf : far; far = zf < far ? zf : far;
+        const bool nan = __builtin_isunordered(x0, x1) || __builtin_isunordered(y0, y1) || __builtin_isunordered(z0, z1);
+        return !(near > far) || nan;
+    }
+    template <typename Merge>
+    __device__ __forceinline__ void leaf(float (*rows)[64], const uint32_t src, const V3 p1, const V3 e1, const V3 e2, const uint32_t tri, const Merge& mg) const {
+        SegmentHit h;
+        segment_triangle<false>(h, mk(rows[0][src], rows[1][src], rows[2][src]), mk(rows[3][src], rows[4][src], rows[5][src]), p1, e1, e2);
+        if (h.dist2 <= rows[6][src]) mg.offer(src, tri, h.dist2);
+    }
+};
+
+// k_query_segments: one segment per lane, k_query_points' shape.  radius NULL: +inf; a segment whose radius is negative or NaN walks
+// nothing.  MASK: segment i is walked with qm.ray[i] (NULL: all ones) against qm.obj; the build without MASK reads neither.
+// Phase 2, as k_query_points': the owning lane recomputes the winner's (dist2, s, v, w, feature) from the key's triangle and its own A
+// and B -- the walk's function on the walk's operands, hence the walk's bits -- and point = P1 + (e1 v + e2 w).  point and vw leave
+// transposed through the wave's rows (store_rows), which are free once the walk is over.
+// LDS a workgroup: the queue 10,240 B, the keys 2,048 B, 8 rows 8,192 B: 20,480 B.
+// counters: [1] / [2] node / triangle tests (COUNT), [8 + 8 * shard] the segments that found a triangle.
+template <bool COUNT, bool MASK>
+__global__ __launch_bounds__(256) void k_query_segments(DevScene s, uint32_t n_segments, const float* __restrict__ segments, const float* __restrict__ radius,
+                                                        srt_segment_out out, unsigned long long* __restrict__ counters, QueryMask qm) {
+    __shared__ uint32_t q_all[4][QCAP];
+    __shared__ unsigned long long best_all[256];
+    __shared__ float row_all[4][8][64];
+    const uint32_t lane = wave_lane(), wave = wave_index();
+    unsigned long long* best = best_all + wave * 64;
+    float (*rows)[64] = row_all[wave];
+    const size_t base = wave_base(wave), ri = base + lane;
+    const bool live = ri < (size_t)n_segments;
+    unsigned long long n_node = 0, n_tri = 0;
+    V3 A = mk(0.0f, 0.0f, 0.0f), B = A;
+    float r = __builtin_inff();
+    uint32_t m = 0xFFFFFFFFu;
+    if (live) {
+        const float* sp = segments + 6 * ri;
+        A = mk(sp[0], sp[1], sp[2]); B = mk(sp[3], sp[4], sp[5]);
+        if (radius) r = radius[ri];
+        if (MASK && qm.ray) m = qm.ray[ri];
+    }
+    const bool walks = live && r >= 0.0f;               // (a NaN radius fails the comparison)
+    query_walk<COUNT, false, MergeClosest, MASK>(s, walks, A, A, lane, q_all[wave], MergeClosest{ best }, rows, n_node, n_tri, 0.0f, 0.0f, qm.obj, m,
+                                                 WalkSegment::make(A, B, r));
+    const Winner h = winner_of(live ? best[lane] : ~0ull);
+    SegmentHit c;
+    c.dist2 = __builtin_inff(); c.s = 0.0f; c.v = 0.0f; c.w = 0.0f; c.feature = 0u;
+    V3 pt = mk(0.0f, 0.0f, 0.0f);
+    if (h.is_hit) {
+        V3 p1, e1, e2;
+        load_tri_edges(reinterpret_cast<const float4*>(s.tris), (size_t)h.id, p1, e1, e2);
+        segment_triangle<true>(c, A, B, p1, e1, e2);
+        pt = p1 + mk(e1.x * c.v + e2.x * c.w, e1.y * c.v + e2.y * c.w, e1.z * c.v + e2.z * c.w);
+    }
+    if (live) {
+        if (out.tri) out.tri[ri] = h.id;
+        if (out.dist2) out.dist2[ri] = c.dist2;
+        if (out.s) out.s[ri] = c.s;
+        if (out.feature) out.feature[ri] = (uint8_t)c.feature;
+    }
+    if (base < (size_t)n_segments) {                    // wave-uniform
+        const size_t left = (size_t)n_segments - base;
+        const uint32_t live_rows = (uint32_t)(left < 64 ? left : 64);
+        __builtin_amdgcn_wave_barrier();
+        if (out.point) { const float v[3] = { pt.x, pt.y, pt.z }; store_rows<3>(out.point, base, lane, live_rows, v, &rows[0][0]); }
+        if (out.vw) { const float v[2] = { c.v, c.w }; store_rows<2>(out.vw, base, lane, live_rows, v, &rows[0][0]); }
+    }
+    if (counters) count_hits(counters, h.is_hit, blockIdx.x);
+    count_walks<COUNT>(counters, n_node, n_tri);
+}

@@ -1,5 +1,5 @@
 """ctypes binding of the C ABI in include/srt.h and its extension headers include/srt_points.h, include/srt_nearest.h,
-include/srt_signed.h and include/srt_points_multi.h (libsrt_hip.so).
+include/srt_signed.h, include/srt_points_multi.h and include/srt_segments.h (libsrt_hip.so).
 
 The product path has NO CPU fallback: if the HIP library is missing or no GPU is visible, this
 raises.  (The CPU restatement under oracle/ is test infrastructure and is never imported here.)
@@ -21,6 +21,7 @@ POINT_SYMBOLS = tuple(abi.POINT_PROTOTYPES)    # every symbol include/srt_points
 NEAREST_SYMBOLS = tuple(abi.NEAREST_PROTOTYPES)    # every symbol include/srt_nearest.h declares
 SIGNED_SYMBOLS = tuple(abi.SIGNED_PROTOTYPES)    # every symbol include/srt_signed.h declares
 POINT_MULTI_SYMBOLS = tuple(abi.POINT_MULTI_PROTOTYPES)    # every symbol include/srt_points_multi.h declares
+SEGMENT_SYMBOLS = tuple(abi.SEGMENT_PROTOTYPES)    # every symbol include/srt_segments.h declares
 MULTI_HIT_MAX = abi.SRT_MULTI_HIT_MAX
 POINT_MULTI_MAX = abi.POINT_MULTI_MAX
 
@@ -46,7 +47,7 @@ def load(path=None):
                                "(python -m simple_raytracer_amd.build); there is no CPU fallback")
         L = C.CDLL(path or LIB_PATH)
         for name, (restype, argtypes) in {**abi.PROTOTYPES, **abi.POINT_PROTOTYPES, **abi.NEAREST_PROTOTYPES, **abi.SIGNED_PROTOTYPES,
-                                            **abi.POINT_MULTI_PROTOTYPES}.items():
+                                            **abi.POINT_MULTI_PROTOTYPES, **abi.SEGMENT_PROTOTYPES}.items():
             fn = getattr(L, name)
             fn.restype, fn.argtypes = restype, argtypes
         if path is not None:
@@ -591,6 +592,29 @@ class DeviceScene:
         po = _wanted(abi.PointMultiOut, *outs)
         _check(getattr(self.L, symbol)(self.h, n, d_points, radius or None, point_mask or None, k, _query_flags(count=count), stream, C.byref(po)), symbol)
 
+    def closest_segments(self, segments, radius=None, seg_mask=None, count=False, want=("tri", "dist2", "s", "point", "vw", "feature")):
+        """srt_closest_segments (include/srt_segments.h): for every segment of `segments` (n x 6, host array: A, B) the nearest triangle
+        within `radius` (n floats, one float for all, or None = +inf) of the segment.  Returns a dict of the arrays named in `want` -- tri n
+        (-1: none within the radius), dist2 n (+0: the segment crosses the triangle, +inf: none), s n (the segment's closest point is
+        A + (B - A) s), point n x 3 (the closest point on the triangle), vw n x 2 (point = P1 + v e1 + w e2), feature n uint8 (0 / 1 end A / B,
+        2 / 3 / 4 triangle edge 1-2 / 2-3 / 1-3, 5 a crossing) -- + 'stats'; count=True fills the node / triangle test counts.  The radius
+        never shrinks during the walk.  seg_mask (n uint32, or None = all ones): as closest_points' point_mask."""
+        seg = np.ascontiguousarray(segments, np.float32).reshape(-1, 6)
+        n = seg.shape[0]
+        rad = None if radius is None else np.ascontiguousarray(np.broadcast_to(np.asarray(radius, np.float32).reshape(-1), (n,)), np.float32)
+        sm = None if seg_mask is None else _ray_mask(seg_mask, n)
+        out, _ = _outputs(want, (n,), _SEGMENT)
+        so = abi.SegmentOut(*_addresses(out, _SEGMENT))
+        return _with_stats(out, self.L.srt_closest_segments, "srt_closest_segments", self.h, n, _host(seg, _f32p), _host(rad, _f32p), _host(sm, _u32p),
+                           _query_flags(count=count), C.byref(so))
+
+    def closest_segments_device(self, n, d_segments, radius=0, seg_mask=0, stream=0, count=False, tri=0, dist2=0, s=0, point=0, vw=0, feature=0):
+        """srt_closest_segments_device: raw device pointers (ints, e.g. torch.Tensor.data_ptr()) in -- the segments (n x 6 floats), `radius` (n
+        floats, 0 = +inf), `seg_mask` (n uint32, 0 = all ones) and the outputs (0: not wanted) --, asynchronous on `stream`, one launch."""
+        so = _wanted(abi.SegmentOut, tri, dist2, s, point, vw, feature)
+        _check(self.L.srt_closest_segments_device(self.h, n, d_segments, radius or None, seg_mask or None, _query_flags(count=count), stream, C.byref(so)),
+               "srt_closest_segments_device")
+
     def sync(self):
         return _with_stats({}, self.L.srt_sync, "srt_sync", self.h)["stats"]
 
@@ -629,6 +653,7 @@ _CLOSEST = {**_HIT, "bary": (np.float32, (3,))}
 _FRAME = {**_HIT, "rgb_linear": (np.float32, (3,)), "rgb8": (np.uint8, (3,))}
 _SURFACE = {k: (ty, () if c == 1 else (c,)) for k, (ty, c) in abi.SURFACE_FIELDS.items()}
 _POINT = {k: (ty, () if c == 1 else (c,)) for k, (ty, c) in abi.POINT_FIELDS.items()}
+_SEGMENT = {k: (ty, () if c == 1 else (c,)) for k, (ty, c) in abi.SEGMENT_FIELDS.items()}
 _SIGN = {k: (ty, None if c is None else ()) for k, (ty, c) in abi.SIGN_FIELDS.items()}      # (None: one entry per direction)
 _PATH_SUMS = {"rgb_linear": (np.float32, (3,)), "rgb8": (np.uint8, (3,))}
 _PATH_SEGMENTS = {"seg_" + k: (ty, () if c == 1 else (c,)) for k, (ty, c) in abi.PATH_FIELDS.items()}

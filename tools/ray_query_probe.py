@@ -61,7 +61,10 @@ alone (what the sign costs on top of it) and containment only (no nearest phase)
 --points-multi: the K nearest triangles per point (srt_closest_points_multi_device, srt_nearest_points_multi_device; k = 1, 4, 16) on the
 points of --nearest at radii 1, 4, 16 and none, beside srt_closest_points_device and srt_nearest_points_device in the same rounds; equal bits
 of column 0 and of the two forms are asserted, the counters printed.
-Usage: python tools/ray_query_probe.py [--reps N] [--trace] [--shade | --range | --shade-range | --multi | --surface | --paths | --shadow-rule | --masked | --refract | --fresnel | --ao | --render-ao | --points | --nearest | --signed | --points-multi [--rounds R]]     (--trace: few repetitions, for a run under rocprofv3 --kernel-trace --stats)"""
+--segments: instead, the segment query (srt_closest_segments_device) on every 64th and on every 4th hit point of the same frame: point segments beside
+srt_closest_points_device (the price of the policy), segments of length 4 and 32 in random directions at radius 1 and 4 beside the point call
+at the midpoint with radius r + L / 2 (what a caller could do before), and the same through the build without box test 2 when it is there.
+Usage: python tools/ray_query_probe.py [--reps N] [--trace] [--segments | --shade | --range | --shade-range | --multi | --surface | --paths | --shadow-rule | --masked | --refract | --fresnel | --ao | --render-ao | --points | --nearest | --signed | --points-multi [--rounds R]]     (--trace: few repetitions, for a run under rocprofv3 --kernel-trace --stats)"""
 import argparse, os, sys, time
 import numpy as np
 import torch                                   # first: torch initialises HIP before the library does
@@ -974,8 +977,86 @@ def signed_section(reps, rounds):
     ds.close()
 
 
+def segments_section(reps, rounds):
+    """What a segment walk costs (srt_closest_segments_device): the hit points of the 1080p frame, 0.25 off the surface towards the camera,
+    every 64th of them (12,270, the sample tools/ray_query_probe.py --nearest walks without a radius) and every 4th (196,319, its sample with radii).
+    (a) point segments (B = A) beside srt_closest_points_device at the same radii: the price of the policy itself.
+    (b) segments of length L in random directions with the point as their midpoint, radius r, beside what a caller could do before:
+    srt_closest_points_device at the midpoint with radius r + L / 2 (a ball that holds the capsule; it answers another question).
+    (c) the same segments through the library built without box test 2 (python -m simple_raytracer_amd.build --segments-no-box-test-2), when
+    that build is there: what the test buys on sloped segments.  Written: tri, dist2, s (the point calls: tri, dist2)."""
+    from simple_raytracer_amd import build
+    OFF = 0.25
+    dev = torch.device("cuda", 0); torch.zeros(1, device=dev)
+    g = gu.GoldenScene("ground_bunny")
+    ds = lib.DeviceScene(g.flat)
+    other = lib.DeviceScene(g.flat, library=lib.load(build.LIB_SEGMENTS_NO_BOX_TEST_2)) if os.path.exists(build.LIB_SEGMENTS_NO_BOX_TEST_2) else None
+    side = torch.cuda.Stream(device=dev)
+    cur = side.cuda_stream
+    rays = frame_rays()
+    frame = ds.trace_rays(rays, want=("hit_id", "t"))
+    hits = np.flatnonzero(frame["hit_id"] >= 0)
+    for STEP in (64, 4):
+        sel = hits[::STEP]
+        n = sel.size
+        unit = rays[sel, 3:6] / np.linalg.norm(rays[sel, 3:6], axis=1, keepdims=True)
+        pts = np.ascontiguousarray(rays[sel, 3:6] * frame["t"][sel, None] - unit * np.float32(OFF), np.float32)
+        print(f"closest segments, K3 ground_bunny {W}x{H}: {g.flat.n_tris} triangles, {g.flat.n_nodes} nodes; every {STEP}th of {hits.size} hit points, {OFF} off the "
+              f"surface: {n} segments; {rounds} rounds of {reps} calls, forms alternating; ms a call; min / max: the spread of the rounds")
+        print(f"box test 2 compiled out: {'libsrt_hip_segments_no_box_test_2.so' if other else 'that build is not here, (c) is left out'}")
+        print(f"{'segments':34s} {'form':34s} {'median':>8s} {'min':>8s} {'max':>8s} {'/ first':>7s}")
+        tri, d2, s = torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.float32, device=dev), torch.empty(n, dtype=torch.float32, device=dev)
+        d_pts = torch.from_numpy(pts).to(dev)
+
+        def counts(o):
+            st = o["stats"]
+            return f"found {int((o['tri'] >= 0).sum())} of {n}; per item {st['node_tests_primary'] / n:.1f} node tests, {st['tri_tests_primary'] / n:.1f} triangle tests"
+        # (a) the policy: point segments beside the point call
+        seg0 = np.ascontiguousarray(np.concatenate([pts, pts], 1))
+        d_seg0 = torch.from_numpy(seg0).to(dev)
+        for r in (1.0, 4.0, 16.0):
+            d_rad = torch.full((n,), r, dtype=torch.float32, device=dev)
+            forms = {"closest_points (yardstick)": lambda: ds.closest_points_device(n, d_pts.data_ptr(), radius=d_rad.data_ptr(), stream=cur, tri=tri.data_ptr(), dist2=d2.data_ptr()),
+                     "closest_segments, B = A": lambda: ds.closest_segments_device(n, d_seg0.data_ptr(), radius=d_rad.data_ptr(), stream=cur, tri=tri.data_ptr(), dist2=d2.data_ptr(),
+                                                                                   s=s.data_ptr())}
+            report(f"(a) points, radius {r:g}", rounds_of(forms, reps, rounds, side))
+            side.synchronize()
+            a, b = ds.closest_points(pts, radius=r, count=True, want=("tri", "dist2")), ds.closest_segments(seg0, radius=r, count=True, want=("tri", "dist2"))
+            assert all(np.array_equal(a[k].view(np.uint32), b[k].view(np.uint32)) for k in ("tri", "dist2")) and a["stats"] == b["stats"]
+            print(f"{'':34s} both: {counts(a)}")
+        # (b), (c) segments of length L about the points
+        rng = np.random.default_rng(9)
+        u = rng.normal(size=(n, 3)); u /= np.linalg.norm(u, axis=1, keepdims=True)
+        for L in (4.0, 32.0):
+            seg = np.ascontiguousarray(np.concatenate([pts - u * (L / 2), pts + u * (L / 2)], 1), np.float32)
+            d_seg = torch.from_numpy(seg).to(dev)
+            for r in (1.0, 4.0):
+                d_rad = torch.full((n,), r, dtype=torch.float32, device=dev)
+                d_ball = torch.full((n,), r + L / 2, dtype=torch.float32, device=dev)
+                forms = {f"closest_points, radius {r + L / 2:g}": lambda: ds.closest_points_device(n, d_pts.data_ptr(), radius=d_ball.data_ptr(), stream=cur, tri=tri.data_ptr(),
+                                                                                                    dist2=d2.data_ptr()),
+                         "closest_segments": lambda: ds.closest_segments_device(n, d_seg.data_ptr(), radius=d_rad.data_ptr(), stream=cur, tri=tri.data_ptr(), dist2=d2.data_ptr(),
+                                                                                s=s.data_ptr())}
+                if other:
+                    forms["closest_segments, no box test 2"] = lambda: other.closest_segments_device(n, d_seg.data_ptr(), radius=d_rad.data_ptr(), stream=cur, tri=tri.data_ptr(),
+                                                                                                       dist2=d2.data_ptr(), s=s.data_ptr())
+                report(f"(b) length {L:g}, radius {r:g}", rounds_of(forms, reps, rounds, side))
+                side.synchronize()
+                ball, cap = ds.closest_points(pts, radius=r + L / 2, count=True, want=("tri", "dist2")), ds.closest_segments(seg, radius=r, count=True, want=("tri", "dist2", "feature"))
+                print(f"{'':34s} the ball: {counts(ball)}")
+                print(f"{'':34s} the segment: {counts(cap)}; crossings {int((cap['feature'][cap['tri'] >= 0] == 5).sum())}")
+                if other:
+                    wide = other.closest_segments(seg, radius=r, count=True, want=("tri", "dist2"))
+                    same = all(np.array_equal(wide[k].view(np.uint32), cap[k].view(np.uint32)) for k in ("tri", "dist2"))
+                    print(f"{'':34s} no box test 2: {counts(wide)}; same tri and dist2: {same}")
+    if other:
+        other.close()
+    ds.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--segments", action="store_true")
     ap.add_argument("--signed", action="store_true")
     ap.add_argument("--points", action="store_true")
     ap.add_argument("--points-multi", action="store_true", dest="points_multi")
@@ -997,6 +1078,8 @@ def main():
     ap.add_argument("--rounds", type=int, default=7)
     a = ap.parse_args()
     reps = 3 if a.trace else a.reps
+    if a.segments:
+        return segments_section(reps, 2 if a.trace else a.rounds)
     if a.signed:
         return signed_section(reps, 2 if a.trace else a.rounds)
     if a.points_multi:
