@@ -1145,12 +1145,13 @@ enum Variant : uint32_t {
     V_HALF_7_WAVES = 65,          // 0 in everything (tile spans included) but the half-tile form's build: the seven-wave one with its 512-entry queue, as before the eight-wave build
     V_HALF_8_WAVES_256 = 66,      // 0 in everything but the half-tile form's node queue: the eight-wave build with 256 entries (eight LDS granules as well: what the smaller queue costs)
     V_HALF_8_TWO_WAVES = 67,      // 0 in everything but the workgroups of the eight-wave build over tile spans: two waves a tile (k_trace_nq_half8_spans), as before the one-wave workgroups
+    V_WAVE_8_GENERAL = 68,        // 0 in everything but the one-wave workgroups' kernels: the general frame's (k_trace_nq_wave8_spans, k_shade_tile_spans), as before the whole-frame form
 };
 // Numbers without a name keep two fallbacks: 7..9 run the unfused node-queue chain of the shipped kernels, any other number a
 // configuration of the fused kernel (the shipped one) at every sample count.
 static inline uint32_t variant_of(const srt_params* p) { return (p->flags >> 8) & 0xffu; }
-// 64 .. 67, 31 and 32 are 0 with one thing of the shipped frame switched: every rule that asks for 0 holds for them.
-static inline uint32_t variant_or_shipped(const srt_params* p) { const uint32_t v = variant_of(p); return (v >= V_FULL_GRID && v <= V_HALF_8_TWO_WAVES) || v == V_WAVE_8 || v == V_WAVE_8_ADJACENT ? (uint32_t)V_SHIPPED : v; }
+// 64 .. 68, 31 and 32 are 0 with one thing of the shipped frame switched: every rule that asks for 0 holds for them.
+static inline uint32_t variant_or_shipped(const srt_params* p) { const uint32_t v = variant_of(p); return (v >= V_FULL_GRID && v <= V_WAVE_8_GENERAL) || v == V_WAVE_8 || v == V_WAVE_8_ADJACENT ? (uint32_t)V_SHIPPED : v; }
 // These run the pipeline the dispatcher picks for 0.  They are NOT 0 for what only the shipped frame gets: the batch hold-back, the
 // chunked launch for scenes of few nodes, the heavy-quadrant lists and the camera build of the fused kernel.  28 is deliberately not
 // among them: it is a configuration of the fused kernel (fused_config in plan_frame) and takes the fused launch at every sample count.
@@ -1442,6 +1443,17 @@ static FramePlan plan_frame(const SceneFacts& f, const srt_params* p, BatchState
         if (one_wave) { pl.trace_spans = &k_trace_nq_wave8_spans<384, true, 16, false>; pl.block_hit = 64; }      // 5,056 B of LDS, four granules: thirty-two workgroups of one wave per CU
         if (xcd_pairs) pl.trace_spans = &k_trace_nq_wave8_spans<384, true, 16, true>;
         if (pl.shade_tile == &k_shade_tile<1>) pl.shade_tile_spans = &k_shade_tile_spans<1>; else pl.shade_tile_spans = &k_shade_tile_spans<0>;
+        // The whole-frame form (srt_kernels.h, whole_frame_params) where variant 0 names the one-wave workgroups in the shipped order: 1 .. 4
+        // light samples under the in-flight hint.  Its kernels hold as constants what the condition above asks of the frame; said once
+        // more here, so that a change to that condition cannot launch them on a frame they do not fit.  68 keeps the general frame's kernels.
+        if (xcd_pairs && variant_of(p) == V_SHIPPED) {
+            const bool whole = !cam && !count && !pl.xcd_rows && !pl.exp && !p->ray_matrix && p->block_cols == 0 && p->block_stride == 1 && p->block_first == 0 &&
+                               p->spp == 1 && wl == p->width && rows == p->height;
+            if (whole) {
+                pl.trace_spans = &k_trace_nq_whole8_spans<384, true, 16, true>;
+                if (pl.shade_tile == &k_shade_tile<1>) pl.shade_tile_spans = &k_shade_tile_whole_spans<1>; else pl.shade_tile_spans = &k_shade_tile_whole_spans<0>;
+            }
+        }
         pl.grid_hit_full = grid8;
         pl.grid_hit = dim3(tile_spans_max_n(pl.spans), pl.spans.n_rows);
         if (xcd_pairs) { pl.grid_hit_full.x = (pl.grid_hit_full.x + 7u) / 8u * 8u; pl.grid_hit.x = (pl.grid_hit.x + 7u) / 8u * 8u; }      // (groups of eight tiles: upper halves, then lower halves)

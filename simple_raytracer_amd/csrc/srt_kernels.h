@@ -132,6 +132,31 @@ __device__ __forceinline__ V3 primary_dir(const DevParams& p, uint32_t px, uint3
 __device__ __forceinline__ V3 ray_origin(const DevParams& p) {
     return p.cam ? mk(p.cm[9], p.cm[10], p.cm[11]) : mk(0.0f, 0.0f, 0.0f);
 }
+// The parameters of a WHOLE frame in the reference's ray form, as constants (the WHOLE kernels: k_trace_nq_whole8_spans,
+// k_shade_tile_whole_spans): no column tiles, consecutive scanline blocks from row 0, one ray per pixel, no camera matrix, no experiment
+// switch -- what plan_frame asserts before it names such a kernel.  Every function above is inlined, so with these fields constant
+// image_row(p, r) is r, image_col is px, pixel_live is px < p.W && r < p.rows, primary_dir is ((float)(p.i0 + px), (float)(p.j0 + r),
+// p.focal) -- (float)n + 0.0f has the bits of (float)n for every integer n, 0 included: a conversion never gives -0.0 --, ray_origin is the
+// zero vector and every p.exp arm is gone, and the kernel neither loads these words nor keeps them in registers.
+__device__ __forceinline__ DevParams whole_frame_params(const DevParams& p) {
+    DevParams q = p;
+    q.Wimg = p.W; q.col_block = 0u; q.block_first = 0u; q.block_stride = 1u;
+    q.sub_x = 0.0f; q.sub_y = 0.0f;
+    q.cam = 0u;
+    for (int i = 0; i < 12; i++) q.cm[i] = 0.0f;
+    q.exp = 0u;
+    return q;
+}
+// a body's parameters and scene: the caller's, or (WHOLE) a copy -- the parameters in their whole-frame form --, whose words the body
+// may then ask for where it wants them
+template <bool WHOLE>
+__device__ __forceinline__ decltype(auto) frame_params(const DevParams& p) {
+    if constexpr (WHOLE) return whole_frame_params(p); else return (p);
+}
+template <bool WHOLE>
+__device__ __forceinline__ decltype(auto) frame_scene(const DevScene& s) {
+    if constexpr (WHOLE) return DevScene(s); else return (s);
+}
 
 // 16x16 pixel tile per 256-thread workgroup, one 8x8 sub-tile per wavefront: the 64 primary rays of
 // a wave are neighbours, so they walk the same top-of-tree nodes (loads of one node by many lanes
@@ -462,7 +487,8 @@ __device__ __forceinline__ void diag_tile_record(float* rgb_linear, uint32_t bx,
 // OWN_ROOTS (with HALF and !WIDE, and only where `own_roots` is set): nobody has tested the roots for this wave -- it has no partner and
 // no launch-time barrier (k_trace_nq_wave8_spans) -- so it puts its own 32 rays through the root table, one (ray, object) pair per lane,
 // and queues for a passing root what the root_pass branch queues: the same pairs in the same order.
-template <bool COUNT, int NQCAP, int TWL, int THL, bool FILTER, bool CAM = false, bool WIDE = false, bool HALF = false, bool OWN_ROOTS = false>
+// PAIRS: the triangle loop of a batch holds two named records and runs over pairs of tests (below); the same tests in the same order.
+template <bool COUNT, int NQCAP, int TWL, int THL, bool FILTER, bool CAM = false, bool WIDE = false, bool HALF = false, bool OWN_ROOTS = false, bool PAIRS = false>
 __device__ __forceinline__ void closest_hit_phase(const DevScene& s, const DevParams& p, uint32_t* nq, uint32_t* tq,
                                                   unsigned long long* best, float4* dir,
                                                   int32_t* __restrict__ hit_id, float* __restrict__ t_out,
@@ -476,6 +502,7 @@ __device__ __forceinline__ void closest_hit_phase(const DevScene& s, const DevPa
                                                   const bool own_roots = false) {             // OWN_ROOTS: the wave tests the roots itself and queues their children (at most 32 objects)
     constexpr int P = 1 << (TWL + THL);           // rays per wavefront
     static_assert(!OWN_ROOTS || (HALF && !WIDE && !COUNT), "the wave's own root pass is the half-tile form's, over the 32 B records");
+    static_assert(!PAIRS || !COUNT, "the pair loop has no counting build");
     const uint32_t lane = threadIdx.x & 63;
     const float4* nodes4 = reinterpret_cast<const float4*>(s.nodes);
     const float4* tris4 = reinterpret_cast<const float4*>(s.tris);
@@ -532,6 +559,29 @@ __device__ __forceinline__ void closest_hit_phase(const DevScene& s, const DevPa
             // cross(tvec, e1) with the host's operations: same bits.  Same box: K3 4.30 -> 4.25 ms per 36 frames, cube over ground
             // 3.12 -> 3.06, K4's closest-hit launch 0.239 -> 0.232 ms.
             const float4* tp = reinterpret_cast<const float4*>(s.tris) + ((size_t)first + sub) * 3;
+            if constexpr (PAIRS) {
+                // The same loop without its rotation (n -> a: eight moves at the head of every test and nine at its end, 17 of about 91
+                // VALU instructions): two named records, A and B.  A is tested while B's loads are in flight, B while the next A's are; an odd
+                // count, and a count of one, end in A.  Ascending ids, the strict '<' and `bi` as below.
+                auto test = [&](const float4 c0, const float4 c1, const float c2, const uint32_t k) {
+                    const float ta = ray_triangle(o, d, mk(c0.x, c0.y, c0.z), mk(c0.w, c1.x, c1.y), mk(c1.z, c1.w, c2));
+                    if (ta != SRT_NEG_INF && ta < bt) { bt = ta; bi = first + k; }
+                };
+                float4 a0, a1, b0, b1; float a2, b2;
+                // (every path that goes on has loaded the set it goes on with: no set is carried round the loop beside its successor,
+                // which is what the compiler turned into copies)
+                if (sub < cnt) {
+                    a0 = tp[0]; a1 = tp[1]; a2 = tp[2].x;
+                    for (uint32_t k = sub;; k += 2u * S) {
+                        if (k + S >= cnt) { test(a0, a1, a2, k); break; }                    // ends in A
+                        tp += 3 * S; b0 = tp[0]; b1 = tp[1]; b2 = tp[2].x;
+                        test(a0, a1, a2, k);
+                        if (k + 2u * S >= cnt) { test(b0, b1, b2, k + S); break; }            // ends in B
+                        tp += 3 * S; a0 = tp[0]; a1 = tp[1]; a2 = tp[2].x;
+                        test(b0, b1, b2, k + S);
+                    }
+                }
+            } else {
             float4 n0, n1; float n2;                     // (the record's last three words are the face normal: not read here)
             if (sub < cnt) { n0 = tp[0]; n1 = tp[1]; n2 = tp[2].x; }
             for (uint32_t k = sub; k < cnt; k += S) {
@@ -541,6 +591,7 @@ __device__ __forceinline__ void closest_hit_phase(const DevScene& s, const DevPa
                 const float ta = ray_triangle(o, d, mk(a0.x, a0.y, a0.z), mk(a0.w, a1.x, a1.y), mk(a1.z, a1.w, a2));
                 // candidate iff t != -inf && t < best (initially +inf, :408); NaN fails '<'; -0.0 == +0.0 keeps the first
                 if (ta != SRT_NEG_INF && ta < bt) { bt = ta; bi = first + k; }
+            }
             }
             if (bt < __builtin_inff()) {
                 const uint32_t tb = (bt == 0.0f) ? 0u : __float_as_uint(bt);     // -0.0 ties with +0.0
@@ -1249,7 +1300,8 @@ union HalfTileLds {
 // y * 4 + x inside the quadrant), so a wave that is done leaves the CU without waiting for its three neighbours.
 // P = 32: the wave owns half `wave` of the tile (closest_hit_phase's HALF: lanes < 32, pixel lane = quadrant of the half * 16 + y * 4 + x)
 // and writes the 32-bit half `wave` of the tile's word -- fields 2 * wave and 2 * wave + 1 -- in one store.
-template <bool SEQ, int NQCAP, bool FILTER, int RS, bool EARLY = true, bool WIDE = false, int P = NQ_P>
+// PAIRS: the triangle loop over pairs of tests with two named records, as closest_hit_phase's.
+template <bool SEQ, int NQCAP, bool FILTER, int RS, bool EARLY = true, bool WIDE = false, int P = NQ_P, bool PAIRS = false>
 __device__ __forceinline__ void shadow_phase(const DevScene& s, const DevParams& p, uint32_t* nq, uint32_t* tq, ShadowLds<RS, P>& L,
                                              int32_t id, float t_hit, V3 d_hit,
                                              unsigned long long* __restrict__ shadow_bits, unsigned long long* __restrict__ counters,
@@ -1340,6 +1392,28 @@ __device__ __forceinline__ void shadow_phase(const DevScene& s, const DevParams&
                 float4 t0 = tp[0], t1 = tp[1];
                 float e2z = reinterpret_cast<const float*>(tp + 2)[0];
                 bool hit = false;
+                if constexpr (PAIRS) {
+                    // two named records instead of the rotation (closest_hit_phase's pair loop): the same tests in the same order, the stop at
+                    // the first hit -- a record already requested is simply not used
+                    auto test = [&](const float4 c0, const float4 c1, const float c2) -> bool {
+                        return ray_triangle(ro, rd, mk(c0.x, c0.y, c0.z), mk(c0.w, c1.x, c1.y), mk(c1.z, c1.w, c2)) != SRT_NEG_INF;      // any t >= 0, NaN included (:335)
+                    };
+                    float4 u0, u1; float u2;
+                    uint32_t k = 0;
+                    bool have_a = cnt != 0u;
+                    while (have_a && k + 1 < cnt) {
+                        tp += 3; u0 = tp[0]; u1 = tp[1]; u2 = reinterpret_cast<const float*>(tp + 2)[0];
+                        hit = test(t0, t1, e2z);
+                        have_a = k + 2 < cnt;
+                        if (!hit) {
+                            if (have_a) { tp += 3; t0 = tp[0]; t1 = tp[1]; e2z = reinterpret_cast<const float*>(tp + 2)[0]; }
+                            hit = test(u0, u1, u2);
+                        }
+                        k += 2;
+                        if (hit) have_a = false;
+                    }
+                    if (have_a) hit = test(t0, t1, e2z);
+                } else
                 for (uint32_t k = 0; k < cnt && !hit; k++) {
                     const float4 c0_ = t0, c1_ = t1; const float cz = e2z;
                     if (k + 1 < cnt) { tp += 3; t0 = tp[0]; t1 = tp[1]; e2z = reinterpret_cast<const float*>(tp + 2)[0]; }
@@ -1688,8 +1762,8 @@ __device__ __forceinline__ void shade_hit_pixel(const DevScene& s, const DevPara
 // (workgroups are dealt round-robin over the eight) and read their records through the same L2: 39 % of the L2 requests miss instead of
 // 44 %, and the headline step is another 1.3 % shorter.
 template <bool COUNT, int NQCAP, bool FILTER, int RS, bool XCD_ROWS, bool ROOTS_AGAIN, bool SHADE = false, bool CAM = false, bool WIDE = false, bool ROW_Z = false,
-          bool HALF = false, int ONE = 0>
-__device__ __forceinline__ void trace_nq_body(const DevScene& s, const DevParams& p, int32_t* __restrict__ hit_id, float* __restrict__ t_out,
+          bool HALF = false, int ONE = 0, bool WHOLE = false>
+__device__ __forceinline__ void trace_nq_body(const DevScene& s_given, const DevParams& p_given, int32_t* __restrict__ hit_id, float* __restrict__ t_out,
                                               float* __restrict__ rgb_linear, uint8_t* __restrict__ rgb8,
                                               unsigned long long* __restrict__ shadow_bits, unsigned long long* __restrict__ counters,
                                               unsigned long long* __restrict__ counters_next = nullptr, uint32_t* __restrict__ qcount = nullptr,
@@ -1703,7 +1777,40 @@ __device__ __forceinline__ void trace_nq_body(const DevScene& s, const DevParams
     // epoch word -- rewritten in stream order by every upload, pose and refit -- still is the table's, and otherwise does a tile's whole
     // work, as k_shade_tile_spans then shades every tile.  A workgroup inside the spans never reads the word.
     static_assert(!ONE || HALF, "one wave per workgroup is a half tile");
+    // WHOLE (with ONE): the frame is whole and in the reference's ray form, at compile time -- the parameters a split frame, a camera matrix
+    // and the A/B switches need are constants from here on (whole_frame_params), and the triangle loops of both phases run over pairs
+    static_assert(!WHOLE || ONE, "the whole-frame form is the one-wave kernel's");
+    decltype(auto) p_own = frame_params<WHOLE>(p_given);      // (WHOLE: a copy, the general frame: the caller's)
+    decltype(auto) s_own = frame_scene<WHOLE>(s_given);
+    const DevParams& p = p_own; const DevScene& s = s_own;
     uint32_t span_bx = blockIdx.x, span_by = blockIdx.y; bool span_on = false;
+    if constexpr (WHOLE) {
+        // The general prologue below reads its arguments where it uses them: the frame's width, the epoch pointer, the span words, the row
+        // count, the set-up's words, one scalar round trip each in front of the wave's first LDS write.  Here everything between entry and
+        // the end of the root pass -- the span words, the frame's extent, the ray's three words, the root table -- is ONE batch: no address
+        // depends on a loaded word (the span is indexed by blockIdx.y), and the empty asm keeps all of it in front of the first branch.
+        static_assert(ONE == 2, "the whole-frame form has the shipped dispatch order only");
+        const uint32_t blk_x = ((blockIdx.x >> 4) << 3) | (blockIdx.x & 7u);
+        uint32_t sp = reinterpret_cast<const uint32_t*>(spans->row)[blockIdx.y < TILE_SPAN_ROWS ? blockIdx.y : TILE_SPAN_ROWS - 1u];      // x0 | n << 16
+        uint32_t row0 = spans->row0, n_rows = spans->n_rows;
+        unsigned long long epoch_at = reinterpret_cast<unsigned long long>(box_epoch);
+        asm volatile("" : "+s"(sp), "+s"(row0), "+s"(n_rows), "+s"(epoch_at), "+s"(p_own.W), "+s"(p_own.rows), "+s"(p_own.i0), "+s"(p_own.j0), "+s"(p_own.focal),
+                          "+s"(s_own.n_objects), "+s"(s_own.root_nodes), "+s"(s_own.obj_range));
+        if (blk_x >= (p.W + 7u) / 8u) return;      // (the padding of a captured launch's whole grid; a span's is beyond the span)
+        span_bx = blk_x;
+        // (the pointer comes back from the asm without its address space: named again, so that the word stays a scalar load)
+        typedef const uint32_t __attribute__((address_space(4))) * EpochWord;
+        const EpochWord epoch_word = (EpochWord)epoch_at;
+        if (!epoch_word) {
+            if (blk_x >= (sp >> 16)) return;
+            span_on = true;
+            span_by = row0 + blockIdx.y;
+            span_bx = (sp & 0xffffu) + blk_x;
+        } else {      // a captured launch: the table counts from tile row 0, and is only as good as its epoch
+            const bool outside = blockIdx.y >= n_rows || blk_x - (sp & 0xffffu) >= (sp >> 16);
+            if (outside && *epoch_word == spans->epoch) return;
+        }
+    } else
     if constexpr (ONE != 0) {      // the same prologue for two workgroups a tile (stated apart: the other builds keep their code to the byte)
         const uint32_t blk_x = ONE == 2 ? ((blockIdx.x >> 4) << 3) | (blockIdx.x & 7u) : blockIdx.x >> 1;      // the workgroup's tile in its grid row
         if (ONE == 2 && blk_x >= (p.W + 7u) / 8u) return;      // (the padding of a captured launch's whole grid; a span's is beyond the span)
@@ -1788,7 +1895,7 @@ __device__ __forceinline__ void trace_nq_body(const DevScene& s, const DevParams
             // through the phase's write-out, and the shadow phase's quick exit leaves its half of the tile's words all-clear
             if (by * 8u + wave * 4u >= p.rows) return;
             SRT_STAMP(ka);
-            closest_hit_phase<COUNT, NQCAP, 3, 2, FILTER, CAM, WIDE, true, true>(s, p, nq_all[0], tq_all[0], half_all[0].closest.best, half_all[0].closest.dir,
+            closest_hit_phase<COUNT, NQCAP, 3, 2, FILTER, CAM, WIDE, true, true, WHOLE>(s, p, nq_all[0], tq_all[0], half_all[0].closest.best, half_all[0].closest.dir,
                                                                            hit_id, t_out, rgb_linear, rgb8, counters, id, t, d, bx, by, gx, wave, nullptr, nullptr, 0,
                                                                            nullptr, roots_done);
         } else {
@@ -1815,7 +1922,7 @@ __device__ __forceinline__ void trace_nq_body(const DevScene& s, const DevParams
     }
     __builtin_amdgcn_wave_barrier();
     SRT_STAMP(kb);
-    shadow_phase<COUNT, NQCAP, FILTER, RS, true, WIDE, P>(s, p, nq_all[wq], tq_all[wq], *L, id, t, d, shadow_bits, counters, bx, by, gx, wave);
+    shadow_phase<COUNT, NQCAP, FILTER, RS, true, WIDE, P, WHOLE>(s, p, nq_all[wq], tq_all[wq], *L, id, t, d, shadow_bits, counters, bx, by, gx, wave);
 #ifdef SRT_DIAG
     SRT_STAMP(k1); diag_tile_record(rgb_linear, bx, by, gx, k0, k1, ka, kb);
 #endif
@@ -1914,6 +2021,20 @@ void k_trace_nq_wave8_spans(DevScene s, DevParams p, int32_t* __restrict__ hit_i
                             const uint32_t* __restrict__ box_epoch, const TileSpans spans) {
     trace_nq_body<false, NQCAP, FILTER, RS, false, false, false, false, false, false, true, XCD_PAIRS ? 2 : 1>(s, p, hit_id, t_out, rgb_linear, rgb8, shadow_bits, counters, nullptr, nullptr, &spans, box_epoch);
 }
+// The one-wave kernel for a WHOLE frame in the reference's ray form (trace_nq_body's WHOLE) -- what every frame over tile spans is: the same
+// arguments, grid and outputs.  k_trace_nq_wave8_spans is the general frame's code: column tiles (three 32-bit divisions, three times
+// over), three forms of scanline blocks, the camera matrix's twelve words and the experiment switches, behind wave-uniform branches a
+// frame over spans never takes, in a kernel at the SGPR limit that parks 21 scalars in the lanes of a VGPR and reads them back through
+// write-out and shadow set-up.  Here they are constants, and the triangle loops of both phases run over pairs of named records instead of
+// rotating one into the other (17 moves a test).  Same rays, same tests in the same order: the same bits.
+template <int NQCAP, bool FILTER, int RS, bool XCD_PAIRS = false>
+__global__ __launch_bounds__(64, 8) SRT_NO_PACKED_F32
+void k_trace_nq_whole8_spans(DevScene s, DevParams p, int32_t* __restrict__ hit_id, float* __restrict__ t_out,
+                             float* __restrict__ rgb_linear, uint8_t* __restrict__ rgb8,
+                             unsigned long long* __restrict__ shadow_bits, unsigned long long* __restrict__ counters,
+                             const uint32_t* __restrict__ box_epoch, const TileSpans spans) {
+    trace_nq_body<false, NQCAP, FILTER, RS, false, false, false, false, false, false, true, XCD_PAIRS ? 2 : 1, true>(s, p, hit_id, t_out, rgb_linear, rgb8, shadow_bits, counters, nullptr, nullptr, &spans, box_epoch);
+}
 // closest hit, shadow rays and shading of a frame in one launch (SHADE)
 template <int NQCAP, bool FILTER, int MINW, int RS, bool XCD_ROWS = false>
 __global__ __launch_bounds__(256, MINW) void k_trace_shade_nq(DevScene s, DevParams p, int32_t* __restrict__ hit_id, float* __restrict__ t_out,
@@ -1988,8 +2109,9 @@ __global__ __launch_bounds__(256, MINW) void k_trace_nq_batch(const FrameTab tab
 // =================================================================================================
 // SPANS: the kernel takes the frame's tile spans (k_shade_tile_spans), and then WRITES hit_id and t of the tiles outside them: HIT and T are
 // its plain pointers there, the read-only restrict pointers of every other kernel otherwise
-template <bool INT_SHIN = false, bool SPANS = false, typename HIT = const int32_t* __restrict__, typename T = const float* __restrict__>
-__device__ __forceinline__ void shade_tile_body(const DevScene& s, const DevParams& p, HIT hit_id,
+// WHOLE (with SPANS): a whole frame in the reference's ray form at compile time, as trace_nq_body's WHOLE (whole_frame_params)
+template <bool INT_SHIN = false, bool SPANS = false, typename HIT = const int32_t* __restrict__, typename T = const float* __restrict__, bool WHOLE = false>
+__device__ __forceinline__ void shade_tile_body(const DevScene& s, const DevParams& p_given, HIT hit_id,
                                                 T t_in,
                                                 const unsigned long long* __restrict__ shadow_bits,
                                                 float* __restrict__ rgb_linear, uint8_t* __restrict__ rgb8,
@@ -2000,6 +2122,8 @@ __device__ __forceinline__ void shade_tile_body(const DevScene& s, const DevPara
     // what background_test_wave writes for a tile no ray of which passes a root box, reads nothing, and counts as a wave of zero hits below.
     // (The tile's shadow words stay unwritten: they are only ever read for a pixel with a hit.)  Decided first, so that the two dependent
     // scalar loads are under way while the workgroup meets at its barrier.
+    static_assert(!WHOLE || SPANS, "the whole-frame form is a frame over tile spans");
+    const DevParams& p = frame_params<WHOLE>(p_given);
     bool outside = false;
     if constexpr (SPANS) {
         const uint32_t w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -2081,6 +2205,17 @@ __global__ __launch_bounds__(256, INT_SHIN ? 8 : 1) void k_shade_tile_spans(DevS
                                                           unsigned long long* __restrict__ counters, const uint32_t* __restrict__ box_epoch,
                                                           const TileSpans spans) {
     shade_tile_body<INT_SHIN != 0, true, int32_t*, float*>(s, p, hit_id, t_in, shadow_bits, rgb_linear, rgb8, counters_next, qcount, counters, &spans, box_epoch);
+}
+// k_shade_tile_spans behind k_trace_nq_whole8_spans: the same launch with the whole frame's parameters as constants (shade_tile_body's WHOLE)
+template <int INT_SHIN>
+__global__ __launch_bounds__(256, INT_SHIN ? 8 : 1) void k_shade_tile_whole_spans(DevScene s, DevParams p, int32_t* hit_id,
+                                                                float* t_in,
+                                                                const unsigned long long* __restrict__ shadow_bits,
+                                                                float* __restrict__ rgb_linear, uint8_t* __restrict__ rgb8,
+                                                                unsigned long long* __restrict__ counters_next, uint32_t* __restrict__ qcount,
+                                                                unsigned long long* __restrict__ counters, const uint32_t* __restrict__ box_epoch,
+                                                                const TileSpans spans) {
+    shade_tile_body<INT_SHIN != 0, true, int32_t*, float*, true>(s, p, hit_id, t_in, shadow_bits, rgb_linear, rgb8, counters_next, qcount, counters, &spans, box_epoch);
 }
 template <int INT_SHIN>
 __global__ __launch_bounds__(256, INT_SHIN ? 8 : 1) void k_shade_tile_batch(const FrameTab tab) {      // the shading of the frames k_trace_nq_batch traced
